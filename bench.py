@@ -19,7 +19,13 @@ the full report -- per-kernel table, the secondary runs (C5, C2, C4 on one GPU, 
 step on a map that is being explored, the closed loop, a soak, the replay of the shipped recording), notes -- goes to the
 file the line names under "report" (--report, default bench_report.json beside this file).
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+A plain run sets up, warms up (an untimed pre-roll, then W steps), times ONE region of exactly K steps and prints the line:
+value and ms_per_step, roofline and cpu_baseline null.  --full adds everything else, as before: the cold first region, K-step
+regions timed five times over (the median one reported), the self-verification of sharded runs, the event-bracketed replay
+behind the roofline and the per-kernel table, the CPU baseline and the secondary runs.  --dump-outputs DIR writes what the
+timed steps computed in the last of them (particles, weights, statistics, the map) as DIR/<name>.npy.
+
+  python bench.py --gpus 1 --steps 200 --warmup 20 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
 
@@ -105,6 +111,43 @@ def pmc_traffic(config: str, kernel_class: str):
         if kernel_class in d:
             best = d[kernel_class].get("hbm_bytes_per_launch")
     return best
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per array, float32 or float64
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_MAP_CELLS = 1 << 22        # a map array of more cells than this is written as a sample of this many (32 MiB of float64)
+DUMP_LIK_CELLS = 1 << 21        # the likelihood field: a sample of this many cells (the map's log-odds determine it)
+
+
+def sample_cells(a, n: int, seed: int) -> np.ndarray:
+    """`a` flattened: whole when it holds at most n values, else the n values at indices drawn from `seed` (in index order) --
+    the same cells in every run for the same shape"""
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.size <= n:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))]
+
+
+def filter_outputs(pf, m) -> dict:
+    """what a caller of the scan step receives: the particles and their weights, the filter's statistics and weighted pose, the map"""
+    st = pf.stats()
+    st = st if isinstance(st, list) else [st]
+    return {"poses": pf.get_poses(), "weights": pf.get_weights(), "weighted_pose": pf.weighted_pose(),
+            "stats": np.array([[s["weight_sum"], s["neff"], s["strongest"], s["n_zero"], s["max_log_weight"]] for s in st], dtype=np.float64),
+            "map_log_odds": sample_cells(m.download_log(), DUMP_MAP_CELLS, seed=1),
+            "map_likelihood": sample_cells(m.download_likelihood(), DUMP_LIK_CELLS, seed=2)}
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in ((k, np.asarray(v)) for k, v in arrays.items())}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -432,6 +475,11 @@ class Workload:
             probe.close()
         return visits, int(dirty)
 
+    def outputs(self) -> dict:
+        """what the last step left on this rank (--dump-outputs)"""
+        self.torch.cuda.synchronize()
+        return filter_outputs(self.pf, self.m)
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 def preroll_steps() -> int:
@@ -448,12 +496,15 @@ def timed_regions() -> int:
         return 5
 
 
-def measure(wl: Workload, steps: int, warmup: int):
+def measure(wl: Workload, steps: int, warmup: int, full: bool = True, capture: bool = False):
     """warm-up (untimed), the timed region (exactly `steps` steps, NO event brackets: nothing but the steps themselves
-    between the two barriers), then a bracketed replay of the same steps: every launch of every kernel class between
-    HIP events on the library's stream, for the roofline and the per-kernel table."""
+    between the two barriers).  full: the timed region five times over (the median one reported) behind a cold first one,
+    then a bracketed replay of the same steps: every launch of every kernel class between HIP events on the library's
+    stream, for the roofline and the per-kernel table.  capture: what the last timed step left (Workload.outputs)."""
     m, torch, dist = wl.m, wl.torch, wl.dist
-    bracket_ms, noop_ms = m.profile_calibrate2(200)
+    bracket_ms = noop_ms = None
+    if full:
+        bracket_ms, noop_ms = m.profile_calibrate2(200)
     m.profile(False)
     # An untimed pre-roll in front of the warm-up: a timed region of the driver's 20 steps is one millisecond long and starts 0.3 ms
     # after the process's first scan step -- clocks still ramping, first-use allocations of the runtime still ahead
@@ -462,18 +513,19 @@ def measure(wl: Workload, steps: int, warmup: int):
     # process's first scan steps.  Reported as first_region_ms_per_step so that rounds stay comparable; never `value`.
     cold = None
     if not wl.loop:
-        for i in range(warmup):
-            wl.step(i)
-        wl.barrier()
-        t0 = time.perf_counter()
-        for i in range(steps):
-            wl.step(warmup + i)
-        wl.barrier()
-        cold = time.perf_counter() - t0
-        if wl.world > 1 and dist.is_initialized():
-            tt = torch.tensor([cold], dtype=torch.float64, device=wl.dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            cold = float(tt.item())
+        if full:
+            for i in range(warmup):
+                wl.step(i)
+            wl.barrier()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                wl.step(warmup + i)
+            wl.barrier()
+            cold = time.perf_counter() - t0
+            if wl.world > 1 and dist.is_initialized():
+                tt = torch.tensor([cold], dtype=torch.float64, device=wl.dev)
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                cold = float(tt.item())
         for i in range(preroll_steps()):
             wl.step(i % max(warmup + steps, 1))
         wl.barrier()
@@ -481,21 +533,21 @@ def measure(wl: Workload, steps: int, warmup: int):
     gc.collect()
     gc.disable()                              # (a collection inside a one-millisecond region is half of it: one process in ten read 70 us per step)
     try:
-        return _measure_timed(wl, steps, warmup, bracket_ms, noop_ms, cold)
+        return _measure_timed(wl, steps, warmup, full, capture, bracket_ms, noop_ms, cold)
     finally:
         gc.enable()
 
 
-def _measure_timed(wl: Workload, steps: int, warmup: int, bracket_ms: float, noop_ms: float, cold):
+def _measure_timed(wl: Workload, steps: int, warmup: int, full: bool, capture: bool, bracket_ms: float, noop_ms: float, cold):
     m, torch, dist = wl.m, wl.torch, wl.dist
     for i in range(warmup):
         wl.step(i)
-    # The timed region -- exactly `steps` steps between two barriers -- is taken timed_regions() times over, back to back, and the
-    # MEDIAN region is the one reported (all of them are in the report): at the driver's 20 steps a region is one millisecond long,
-    # and about one process in ten had a 0.3-0.5 ms stall of unknown origin land in it (tools/bench20_spread.sh: 47 us per step read
-    # as 61-74).  Every region is K steps of the same workload; at N > 1 a region's time is the maximum over the ranks.
+    # The timed region -- exactly `steps` steps between two barriers.  With --full it is taken timed_regions() times over, back to back,
+    # and the MEDIAN region is the one reported (all of them are in the report): at 20 steps a region is one millisecond long, and
+    # about one process in ten had a 0.3-0.5 ms stall of unknown origin land in it (tools/bench20_spread.sh: 47 us per step read as
+    # 61-74).  Every region is K steps of the same workload; at N > 1 a region's time is the maximum over the ranks.
     regions = []
-    for r in range(timed_regions()):
+    for r in range(timed_regions() if full else 1):
         base = warmup + (r * steps if wl.loop else 0)
         wl.barrier()
         t0 = time.perf_counter()
@@ -514,6 +566,10 @@ def _measure_timed(wl: Workload, steps: int, warmup: int, bracket_ms: float, noo
     import gc
     gc.enable()
     elapsed, issue, per_rank = sorted(regions, key=lambda x: x[0])[len(regions) // 2]
+    outputs = wl.outputs() if capture else None        # (before anything below steps the filter on)
+    if not full:
+        return dict(elapsed=elapsed, issue=issue, per_rank=per_rank, regions=[x[0] for x in regions], outputs=outputs,
+                    preroll=0 if wl.loop else preroll_steps(), warmup_effective=warmup if wl.loop else preroll_steps() + warmup)
     if wl.loop:
         warmup += (len(regions) - 1) * steps   # (a closed loop's replay below goes on from where the last region ended)
 
@@ -552,19 +608,59 @@ def _measure_timed(wl: Workload, steps: int, warmup: int, bracket_ms: float, noo
     compute = [k for k in prof if prof[k][1] > 0 and k != "exchange"]
     dominant = max(compute, key=lambda k: prof[k][0], default="score")
     return dict(elapsed=elapsed, issue=issue, per_rank=per_rank, dominant=dominant, prof=prof, nb=nb, steady=steady, steady_steps=ns, tiles=tiles,
-                preroll=0 if wl.loop else preroll_steps(), regions=[x[0] for x in regions], cold_region=cold,
+                preroll=0 if wl.loop else preroll_steps(), regions=[x[0] for x in regions], cold_region=cold, outputs=outputs,
                 warmup_effective=warmup if wl.loop else warmup + steps + preroll_steps() + warmup,
                 bracket_us=bracket_ms * 1e3, noop_us=noop_ms * 1e3)
 
 
-def report(wl: Workload, meas: dict, steps: int, warmup: int):
-    """the JSON fields of one configuration (rank 0)."""
-    a = wl.args
-    visits, dirty = wl.scan_footprint()
-    m = wl.m
+def headline(wl: Workload, meas: dict, steps: int, warmup: int):
+    """the JSON fields of one configuration (rank 0) that the timed region alone gives: value, ms_per_step, the configuration."""
+    a, m = wl.args, wl.m
     n_total = wl.n_global * wl.M * (wl.world if (wl.batched and wl.world > 1) else 1)
     elapsed = meas["elapsed"]
     value = n_total * steps / elapsed
+    return {
+        "ms_per_step": elapsed / steps * 1e3,
+        "timed_region_s": elapsed,
+        "preroll_steps": meas.get("preroll", 0),            # untimed, in front of the warm-up (measure)
+        "timed_regions": len(meas.get("regions", [1])),     # regions of `steps` steps timed back to back; ms_per_step is the median one's
+        "region_ms_per_step": [round(x / steps * 1e3, 6) for x in meas.get("regions", [])],
+        # the protocol of rounds 1-4 (W warm-up steps, then one region of K steps, the process's first): for comparison across rounds
+        "first_region_ms_per_step": (round(meas["cold_region"] / steps * 1e3, 6) if meas.get("cold_region") else None),
+        "warmup_effective": meas.get("warmup_effective", warmup),   # untimed steps in front of the reported regions
+        "host_issue_ms_per_step": meas["issue"] / steps * 1e3,
+        "config": {
+            "workload": (f"{wl.name}: {wl.M} maps x {m.W}x{m.H} @ {wl.res} m x {wl.n_local} particles x {wl.B} beams ({wl.n_hit} hits), batched handle, "
+                         if wl.batched else
+                         f"{wl.name}: {wl.n_local} particles/GPU x {wl.B} beams ({wl.n_hit} hits), {m.W}x{m.H} grid @ {wl.res} m, ")
+                        + "full scan step (score+normalise+resample+ray-cast+likelihood rebuild"
+                        + (": every cell, likelihoodData written, as the reference does)" if a.full_rebuild else
+                           "; the rebuild is dirty-tile / factor-table-only: bit-identical results, likelihoodData on demand -- the reference's own "
+                           "every-cell rebuild is cpu_baseline.gpu_like_for_like_ms_per_step)"),
+            "particles_total": n_total, "particles_per_gpu": wl.n_local * wl.M, "beams": wl.B, "grid": [m.W, m.H], "resolution_m": wl.res, "maps": wl.M, "maps_total": wl.maps_total,
+            "parallelism": ("single GPU" if wl.world == 1 else
+                            (f"{wl.maps_total} independent maps split over {wl.world} ranks ({wl.M} per GPU), no collective" if wl.batched else
+                             f"particles sharded x{wl.world}, map replicated")),
+            "exchange": wl.exchange_text(),
+            "likelihood_rebuild": "full" if a.full_rebuild else
+                                  ("dirty-rect (bit-identical to full)" if os.environ.get("GMS_LIK_SKIP") == "0" else
+                                   "dirty-rect; tiles whose thresholded codes the scan does not change are left alone (bit-identical to full; "
+                                   "GMS_LIK_SKIP=0 rebuilds every dirty tile); the rebuilds write the scoring factor table only, likelihoodData is "
+                                   "materialised on demand outside the timed loop (gms_ensure_lik)"),
+            "inputs": "host buffers every step (PCIe-inclusive)" if a.host_inputs else "resident in HBM",
+        },
+        "value": value,
+        "beam_evals_per_s": value * wl.n_hit,
+        "scans_per_s": steps * wl.M * (wl.world if wl.batched else 1) / elapsed,
+    }
+
+
+def report(wl: Workload, meas: dict, steps: int, warmup: int):
+    """headline() and what --full measures beside it: the per-kernel table, the roofline, the filter's state, the scan's footprint."""
+    a = wl.args
+    visits, dirty = wl.scan_footprint()
+    m = wl.m
+    elapsed = meas["elapsed"]
     paired = not a.full_rebuild and not a.host_inputs or wl.batched
     # the likelihood rebuild is charged for the cells it REWRITES (16 B each: log-odds read, factor written): the census' written and
     # blurred tiles; tiles the unchanged-tile rule leaves alone, and uniform tiles that already hold their constants, move nothing
@@ -681,39 +777,8 @@ def report(wl: Workload, meas: dict, steps: int, warmup: int):
         lw = np.asarray(wl.pf.get_log_weights(), dtype=np.float64).reshape(wl.M, -1)[0]
         sm = np.exp(lw - lw.max())
         neff_log = float(sm.sum() ** 2 / (sm * sm).sum())
-    out = {
-        "ms_per_step": elapsed / steps * 1e3,
-        "timed_region_s": elapsed,
-        "preroll_steps": meas.get("preroll", 0),            # untimed, in front of the warm-up (measure)
-        "timed_regions": len(meas.get("regions", [1])),     # regions of `steps` steps timed back to back; ms_per_step is the median one's
-        "region_ms_per_step": [round(x / steps * 1e3, 6) for x in meas.get("regions", [])],
-        # the protocol of rounds 1-4 (W warm-up steps, then one region of K steps, the process's first): for comparison across rounds
-        "first_region_ms_per_step": (round(meas["cold_region"] / steps * 1e3, 6) if meas.get("cold_region") else None),
-        "warmup_effective": meas.get("warmup_effective", warmup),   # untimed steps in front of the reported regions: warm-up + cold region + pre-roll + warm-up
-        "host_issue_ms_per_step": meas["issue"] / steps * 1e3,
-        "config": {
-            "workload": (f"{wl.name}: {wl.M} maps x {m.W}x{m.H} @ {wl.res} m x {wl.n_local} particles x {wl.B} beams ({wl.n_hit} hits), batched handle, "
-                         if wl.batched else
-                         f"{wl.name}: {wl.n_local} particles/GPU x {wl.B} beams ({wl.n_hit} hits), {m.W}x{m.H} grid @ {wl.res} m, ")
-                        + "full scan step (score+normalise+resample+ray-cast+likelihood rebuild"
-                        + (": every cell, likelihoodData written, as the reference does)" if a.full_rebuild else
-                           "; the rebuild is dirty-tile / factor-table-only: bit-identical results, likelihoodData on demand -- the reference's own "
-                           "every-cell rebuild is cpu_baseline.gpu_like_for_like_ms_per_step)"),
-            "particles_total": n_total, "particles_per_gpu": wl.n_local * wl.M, "beams": wl.B, "grid": [m.W, m.H], "resolution_m": wl.res, "maps": wl.M, "maps_total": wl.maps_total,
-            "parallelism": ("single GPU" if wl.world == 1 else
-                            (f"{wl.maps_total} independent maps split over {wl.world} ranks ({wl.M} per GPU), no collective" if wl.batched else
-                             f"particles sharded x{wl.world}, map replicated")),
-            "exchange": wl.exchange_text(),
-            "likelihood_rebuild": "full" if a.full_rebuild else
-                                  ("dirty-rect (bit-identical to full)" if os.environ.get("GMS_LIK_SKIP") == "0" else
-                                   "dirty-rect; tiles whose thresholded codes the scan does not change are left alone (bit-identical to full; "
-                                   "GMS_LIK_SKIP=0 rebuilds every dirty tile); the rebuilds write the scoring factor table only, likelihoodData is "
-                                   "materialised on demand outside the timed loop (gms_ensure_lik)"),
-            "inputs": "host buffers every step (PCIe-inclusive)" if a.host_inputs else "resident in HBM",
-        },
-        "value": value,
-        "beam_evals_per_s": value * wl.n_hit,
-        "scans_per_s": steps * wl.M * (wl.world if wl.batched else 1) / elapsed,
+    out = headline(wl, meas, steps, warmup)
+    out.update({
         "kernels": kernels,
         "kernel_symbols": {k: symbols.get(k, k) for k in kernels},
         "filter": {"neff": st0["neff"], "n_zero_weights": st0["n_zero"], "weight_sum": st0["weight_sum"],
@@ -723,7 +788,7 @@ def report(wl: Workload, meas: dict, steps: int, warmup: int):
         "roofline": roof,
         "scan_footprint": {"visited_cells": visits, "dirty_box_cells": dirty_box_cells, "rebuilt_cells_per_step_per_map": dirty,
                            "likelihood_tiles_per_step": None if tiles is None else {k: round(v, 2) for k, v in tiles.items()}},
-    }
+    })
     return out
 
 
@@ -853,7 +918,7 @@ def cpu_baseline(wl: Workload, budget_s: float, with_score_sweep: bool):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def trace_replay(path: str, steps: int, warmup: int, particles: int, extent: float, res: float, local_rank: int, torch):
+def trace_replay(path: str, steps: int, warmup: int, particles: int, extent: float, res: float, local_rank: int, torch, capture: bool = False):
     """A recorded trace (DataRecorder format, gridmap_slam_robot_amd/trace.py) through the device path frame by frame, as
     GridMapApp.onHandleData runs it (J/app/GridMapApp.java:133-192): read_trace -> ONE call per frame, gms_slam_frame (the raw
     measurements handed over as host arrays, 17 bytes per measurement over PCIe; de-skew and motion-model sample in one launch,
@@ -899,6 +964,8 @@ def trace_replay(path: str, steps: int, warmup: int, particles: int, extent: flo
            "calls_per_frame": ["gms_slam_frame"] if rp.one_call else ["gms_map_deskew", "gms_pf_sample_motion", "gms_slam_update_dev"],
            "launches_per_frame": 5 if rp.one_call else 6,
            "neff_last": st["neff"], "weighted_pose_last": [float(x) for x in est]}
+    if capture:
+        out["outputs"] = filter_outputs(pf, m)
     pf.close(); m.close()
     return out
 
@@ -919,13 +986,13 @@ def particle_maps_run(*args, **kwargs):
 
 
 def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, res: float, beams: int, steps: int, warm_frames: int = 12,
-                      cpu_seconds: float = 0.0, refine: bool = False):
+                      cpu_seconds: float = 0.0, refine: bool = False, full: bool = True, capture: bool = False):
     """The reference's own filter shape (SLAM.java: one GridMapData per particle; gms_slam_*): `particles` particles with a map of
     extent x extent metres each, scans of `beams` measurements of a synthetic drive through a room that fits the map.  Timed, inputs
     resident in HBM, nothing read back: `steps` SLAM.update calls (motion model inside, no resampling: the maps keep growing), then
     update / resample pairs (SLAM.resample as the filter runs it) and `steps` draws back to back (both arrays moved per call); then
     the pairs with HIP-event brackets around every launch for the per-kernel table.  Rooflines by algorithmic bytes: computeLikelihoodMap 16 B per cell and particle; the resampling copy 32 B per
-    cell and particle (both arrays read and written, GridMap.java:118-121)."""
+    cell and particle (both arrays read and written, GridMap.java:118-121).  full = False: the `steps` SLAM.update calls only, one region."""
     from gridmap_slam_robot_amd import SLAMParticleMaps, synth
     from gridmap_slam_robot_amd._lib import BEAM_DTYPE
     T = 48
@@ -957,11 +1024,11 @@ def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, re
             s.resample(float(r01[i % 4096]))
     torch.cuda.synchronize()
     warm_frames += pre                                  # (sequence numbers go on from here)
-    # Every figure below is the median of three regions of `steps` steps that start from the SAME poses (a region is a few milliseconds
+    # Every figure below is the median of three regions (one without --full) of `steps` steps that start from the SAME poses (a region is a few milliseconds
     # and one host hiccup inside it -- a collection, a scheduler tick of a busy box -- is a third of it; without the reset the particles,
     # which diffuse while nothing resamples them, would hand every later region another workload).
     regions = {}
-    def timed(name, body, reps=3):
+    def timed(name, body, reps=3 if full else 1):
         nonlocal k
         P0, k0 = s.get_particles()[0].copy(), k
         out = []
@@ -978,10 +1045,29 @@ def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, re
         return sorted(out)[len(out) // 2]
     upd = timed("update_ms", lambda i: step(warm_frames + i))
     st = s.pf.stats()
+    outputs = None
+    if capture:
+        P, w = s.get_particles()
+        outputs = {"poses": P, "weights": w, "stats": np.array([st["weight_sum"], st["neff"], st["strongest"], st["n_zero"], st["max_log_weight"]]),
+                   "maps_log_odds": sample_cells(s.maps(), DUMP_MAP_CELLS, seed=1)}
+    lazy = os.environ.get("GMS_SLAM_LAZY_LIK_COPY", "1") != "0"
+    on_demand = os.environ.get("GMS_SLAM_EAGER_LIK", "0") != "1" and not refine
+    out = {"workload": f"SLAM.java's own shape: {particles} particles x one {s.W}x{s.H} map each @ {res} m, {beams} beams per scan; SLAM.update per particle "
+                       "(motion model, computeLikelihoodMap" + (" evaluated under the scan's end points -- likelihoodData itself on demand, the same values; the every-cell rebuild is update_every_cell_rebuilt_ms" if on_demand else "") +
+                       ", " + ("findBestPose against the particle's own field, " if refine else "") +
+                       "probabilityOf, integrateObservation), SLAM.resample with its deep copies of the maps ("
+                       + ("logData at once, likelihoodData when it is read: the next update overwrites it first" if lazy else "both arrays at once") + ")",
+           "particles": particles, "grid": [s.W, s.H], "beams": beams, "steps": steps, "refine": bool(refine), "mean_hit_beams": float(np.mean(hits)),
+           "update_ms": upd * 1e3, "regions_ms": regions, "updates_per_s": 1.0 / upd, "particle_scan_evals_per_s": particles / upd,
+           "likelihood_on_demand": bool(on_demand), "neff_last": st["neff"], "n_zero_weights": st["n_zero"], "kernels": {}}
+    if outputs is not None:
+        out["outputs"] = outputs
+    if not full:
+        s.close()
+        return out
     # SLAM.resample as the filter runs it: update, resample, update, ... (the pair's time less the update's).  The library copies
     # logData at once and likelihoodData only if somebody reads it before the next update's computeLikelihoodMap has overwritten every
     # cell of it (gms_slam::lazy_lik; GMS_SLAM_LAZY_LIK_COPY=0: both at once) ...
-    lazy = os.environ.get("GMS_SLAM_LAZY_LIK_COPY", "1") != "0"
     def pair_body(i):
         step(warm_frames + steps + i)
         s.resample(float(r01[(17 + i) % 4096]))
@@ -1040,7 +1126,6 @@ def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, re
     # reference does (GMS_SLAM_EAGER_LIK=1, read when a handle is created); the default evaluates the field under the scan's end points
     # only and writes likelihoodData when a caller asks for it -- the same values either way
     eager_ms = None
-    on_demand = os.environ.get("GMS_SLAM_EAGER_LIK", "0") != "1" and not refine
     if on_demand:
         old_env = os.environ.get("GMS_SLAM_EAGER_LIK")
         os.environ["GMS_SLAM_EAGER_LIK"] = "1"
@@ -1064,14 +1149,7 @@ def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, re
         torch.cuda.synchronize()
         eager_ms = (time.perf_counter() - t0) / steps * 1e3
         e.close()
-    out = {"workload": f"SLAM.java's own shape: {particles} particles x one {s.W}x{s.H} map each @ {res} m, {beams} beams per scan; SLAM.update per particle "
-                       "(motion model, computeLikelihoodMap" + (" evaluated under the scan's end points -- likelihoodData itself on demand, the same values; the every-cell rebuild is update_every_cell_rebuilt_ms" if on_demand else "") +
-                       ", " + ("findBestPose against the particle's own field, " if refine else "") +
-                       "probabilityOf, integrateObservation), SLAM.resample with its deep copies of the maps ("
-                       + ("logData at once, likelihoodData when it is read: the next update overwrites it first" if lazy else "both arrays at once") + ")",
-           "particles": particles, "grid": [s.W, s.H], "beams": beams, "steps": steps, "refine": bool(refine), "mean_hit_beams": float(np.mean(hits)),
-           "update_ms": upd * 1e3, "regions_ms": regions, "updates_per_s": 1.0 / upd, "particle_scan_evals_per_s": particles / upd,
-           "likelihood_on_demand": bool(on_demand),
+    out.update({
            "update_every_cell_rebuilt_ms": eager_ms,
            "update_every_cell_rebuilt_what": "the same update with computeLikelihoodMap over every cell of every particle's map, as the reference and the CPU port run it "
                                               "(GMS_SLAM_EAGER_LIK=1): the like-for-like figure; the default evaluates the field under the scan's end points only (same values)",
@@ -1082,8 +1160,8 @@ def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, re
            "revolution_no_resample_what": "the same revolution while no resampling step is due: the rule decided on the device, no draw, no map copied (the reference does nothing either)",
            "revolution_ms": rev * 1e3, "revolution_what": "SLAM.update + `if (neff < n / 2) resample()` (GridMapApp.java:185-186) with the rule decided on the device: no host round trip",
            "resample_both_arrays_ms": rsm_both * 1e3, "resample_copy_TBps_algorithmic": copy_b / rsm_both / 1e12, "resample_copy_hbm_frac": copy_b / rsm_both / 8e12,
-           "gridmapdata_bytes_on_device": 4.0 * 8 * cells * particles, "neff_last": st["neff"], "n_zero_weights": st["n_zero"],
-           "kernels": kern}
+           "gridmapdata_bytes_on_device": 4.0 * 8 * cells * particles,
+           "kernels": kern})
     if cpu_seconds > 0:
         from oracle import oracle as orc                  # the reported CPU baseline of this mode: the oracle's SLAM loop, one thread
         g = orc.Grid(extent, extent, res, -extent / 2, -extent / 2)
@@ -1109,12 +1187,13 @@ def _particle_maps_run(torch, local_rank: int, particles: int, extent: float, re
     return out
 
 
-def particle_maps_sharded_run(torch, dist, rank: int, world: int, local_rank: int, particles: int, extent: float, res: float, beams: int, steps: int):
+def particle_maps_sharded_run(torch, dist, rank: int, world: int, local_rank: int, particles: int, extent: float, res: float, beams: int, steps: int,
+                              full: bool = True):
     """The reference's own filter shape over the ranks of this run: particles WITH their maps, no replica (gms_slam_create_shard +
     distributed.ShardedSlamParticleMaps over torch.distributed = RCCL).  `particles` is the WHOLE population (fixed: strong scaling);
     every rank holds particles / world of them and their maps.  Timed between barriers, maximum over the ranks: `steps` SLAM.update calls
     (the per-particle body + the two small weight collectives), then update / resample pairs with the caller's rule (the draw, the
-    all-gather of the sources, the records of the particles that crossed a rank boundary).  This pool has one GPU per box: with more
+    all-gather of the sources, the records of the particles that crossed a rank boundary; with `full` only).  This pool has one GPU per box: with more
     than one rank this path has only ever run as two gloo ranks on one device (tests/test_gpu_bench_two_ranks.py); unmeasured on xGMI."""
     from gridmap_slam_robot_amd import synth
     from gridmap_slam_robot_amd._lib import GMS_BLOCK
@@ -1152,6 +1231,15 @@ def particle_maps_sharded_run(torch, dist, rank: int, world: int, local_rank: in
         if i % 4 == 3:
             f.resample(float(r01[i % 4096]))
     upd = timed(lambda i: f.update(scans[(24 + i) % T][0], scans[(24 + i) % T][1], seed=11, sequence=100 + i), steps)
+    out = {"workload": f"SLAM.java's own shape sharded: {particles} particles x one {ops.slam.W}x{ops.slam.H} map each @ {res} m over {world} rank(s) "
+                       f"({n} particles and their maps per rank, no replica), {beams} beams per scan; SLAM.update = per-particle body + block partials "
+                       "all-reduced + packed particles all-gathered; SLAM.resample = the draw per rank + the records of the particles that crossed a rank boundary",
+           "particles": particles, "particles_per_rank": n, "ranks": world, "grid": [ops.slam.W, ops.slam.H], "beams": beams, "steps": steps,
+           "update_ms": upd * 1e3, "particle_scan_evals_per_s": particles / upd, "neff_last": f.stats()["neff"],
+           "measured_on": "one GPU per box in this pool: figures with more than one rank come from ranks sharing a device over gloo, never from xGMI"}
+    if not full:
+        ops.slam.close()
+        return out
     sent0, res0 = f.records_sent, f.resamples
 
     def pair(i):
@@ -1163,16 +1251,10 @@ def particle_maps_sharded_run(torch, dist, rank: int, world: int, local_rank: in
     if world > 1:
         dist.all_reduce(moved)
     rec_bytes = ops.record_doubles * 8
-    out = {"workload": f"SLAM.java's own shape sharded: {particles} particles x one {ops.slam.W}x{ops.slam.H} map each @ {res} m over {world} rank(s) "
-                       f"({n} particles and their maps per rank, no replica), {beams} beams per scan; SLAM.update = per-particle body + block partials "
-                       "all-reduced + packed particles all-gathered; SLAM.resample = the draw per rank + the records of the particles that crossed a rank boundary",
-           "particles": particles, "particles_per_rank": n, "ranks": world, "grid": [ops.slam.W, ops.slam.H], "beams": beams, "steps": steps,
-           "update_ms": upd * 1e3, "particle_scan_evals_per_s": particles / upd, "update_resample_pair_ms": pr * 1e3,
-           "resample_ms": max(pr - upd, 0.0) * 1e3, "resampling_steps_timed": nres,
-           "records_moved_per_resample": (float(moved.item()) / nres) if nres else 0.0, "record_bytes": rec_bytes,
-           "bytes_moved_per_resample": (float(moved.item()) / nres * rec_bytes) if nres else 0.0,
-           "neff_last": f.stats()["neff"],
-           "measured_on": "one GPU per box in this pool: figures with more than one rank come from ranks sharing a device over gloo, never from xGMI"}
+    out.update({"update_resample_pair_ms": pr * 1e3, "resample_ms": max(pr - upd, 0.0) * 1e3, "resampling_steps_timed": nres,
+                "records_moved_per_resample": (float(moved.item()) / nres) if nres else 0.0, "record_bytes": rec_bytes,
+                "bytes_moved_per_resample": (float(moved.item()) / nres * rec_bytes) if nres else 0.0,
+                "neff_last": f.stats()["neff"]})
     ops.slam.close()
     return out
 
@@ -1420,9 +1502,16 @@ def main() -> int:
     ap.add_argument("--refine", action="store_true", help="with --particle-maps: SLAM.update refines every particle's pose (findBestPose against its own field, SLAM.java:96)")
     ap.add_argument("--report", default=os.path.join(ROOT, "bench_report.json"),
                     help="where the full report goes (kernel table, secondary runs, notes); stdout carries one compact line that names it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: repeated regions, self-verification, per-kernel table and roofline, CPU baseline, secondary runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (particles, weights, statistics, the map; seeded samples of large maps) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.config not in (None, "C2", "C3", "C4", "C5"):
         print("bench.py: --config must be C2, C3, C4 or C5", file=sys.stderr)
+        return 2
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or (args.particle_maps and args.force_sharded)):
+        print("bench.py: --dump-outputs is a one-GPU, unsharded run", file=sys.stderr)
         return 2
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, exactly as the driver's command line does
@@ -1467,7 +1556,7 @@ def main() -> int:
     if args.particle_maps and (world > 1 or args.force_sharded):
         # the reference-shape filter sharded over the ranks: particles with their maps (fixed population: strong scaling)
         n_, ext_, b_ = args.particle_maps.split(",")
-        pm = particle_maps_sharded_run(torch, dist, rank, world, local_rank, int(n_), float(ext_), 0.05, int(b_), args.steps)
+        pm = particle_maps_sharded_run(torch, dist, rank, world, local_rank, int(n_), float(ext_), 0.05, int(b_), args.steps, full=args.full)
         if rank == 0:
             out = {"metric": "particle-scan evals/sec", "value": pm["particle_scan_evals_per_s"], "unit": "particle-scan evals/s", "n_gpus": world,
                    "steps": args.steps, "warmup": args.warmup, "ms_per_step": pm["update_ms"], "higher_is_better": True, "scaling": "strong",
@@ -1480,8 +1569,11 @@ def main() -> int:
         return 0
     if args.particle_maps:
         n_, ext_, b_ = args.particle_maps.split(",")
-        pm = particle_maps_run(torch, local_rank, int(n_), float(ext_), 0.05, int(b_), args.steps, cpu_seconds=0.0 if (args.no_cpu_baseline or args.refine) else 5.0,
-                               refine=args.refine)
+        pm = particle_maps_run(torch, local_rank, int(n_), float(ext_), 0.05, int(b_), args.steps,
+                               cpu_seconds=5.0 if (args.full and not (args.no_cpu_baseline or args.refine)) else 0.0, refine=args.refine,
+                               full=args.full, capture=bool(args.dump_outputs))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, pm.pop("outputs"))
         out = {"metric": "particle-scan evals/sec", "value": pm["particle_scan_evals_per_s"], "unit": "particle-scan evals/s", "n_gpus": 1,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": pm["update_ms"], "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": {"workload": pm["workload"]},
@@ -1504,7 +1596,10 @@ def main() -> int:
         return 0
 
     if args.trace:
-        tr = trace_replay(args.trace, args.steps, args.warmup, args.trace_particles, args.trace_extent, args.trace_res, local_rank, torch)
+        tr = trace_replay(args.trace, args.steps, args.warmup, args.trace_particles, args.trace_extent, args.trace_res, local_rank, torch,
+                          capture=bool(args.dump_outputs))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, tr.pop("outputs"))
         out = {"metric": "particle-scan evals/sec", "value": tr["particle_scan_evals_per_s"], "unit": "particle-scan evals/s", "n_gpus": 1,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": tr["ms_per_frame"], "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "f64", "data": "synthetic recording (tools/make_recording.py)",
@@ -1516,32 +1611,37 @@ def main() -> int:
 
     config = args.config or ("C3" if world == 1 else "C4")      # BASELINE.json configs[2] at one GPU, configs[3] over several
     sharded = world > 1 or args.force_sharded
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
 
-    def run_sharded_or_single(name, steps, warmup, comm=None, keep_log=False):
+    def run_sharded_or_single(name, steps, warmup, comm=None, keep_log=False, capture=False):
         """one configuration on this run's ranks: route, self-verification, measurement; rank 0 gets the report"""
         w = Workload(name, args, torch, dist, rank, world, local_rank, sharded, keep_log=keep_log, comm=comm, n_maps=(args.maps or None))
         ver = None
         if w.spf is not None:
             w.pick_route()
-            if not args.no_verify:
+            if args.full and not args.no_verify:
                 try:
                     ver = w.verify_against_standalone()
                 except Exception as e:      # the check must never take the measurement down with it
                     print(f"bench.py: sharded-vs-standalone check failed to run: {e!r}", file=sys.stderr)
                     ver = {"sharded_equals_standalone": None, "error": repr(e)} if rank == 0 else None
-        ms = measure(w, steps, warmup)
+        ms = measure(w, steps, warmup, full=args.full, capture=capture)
         if rank != 0:
             return w, None
-        r = report(w, ms, steps, warmup)
+        if ms["outputs"] is not None:
+            dump_outputs(args.dump_outputs, ms.pop("outputs"))
+        if not args.full:
+            r = headline(w, ms, steps, warmup)
+        else:
+            r = report(w, ms, steps, warmup)
+            mu_ = map_update_ms(w, ms["nb"])
+            if mu_ is not None:
+                r["map_update_ms_per_scan"] = mu_
         r["steps"], r["warmup"] = steps, warmup
         r["scaling"] = "strong" if w.strong else "weak"
-        mu_ = map_update_ms(w, ms["nb"])
-        if mu_ is not None:
-            r["map_update_ms_per_scan"] = mu_
         if world > 1 or w.spf is not None:
             r["per_rank_ms_per_step"] = [round(t / steps * 1e3, 5) for t in ms["per_rank"]]
-            ex = r["kernels"].get("exchange")
+            ex = r.get("kernels", {}).get("exchange")
             r["exchange_latency_us"] = ex["avg_launch_us"] if ex else None     # the L of DESIGN.md section 7 (event-bracketed, in-library route)
             if ver is not None:
                 r["verify"] = ver
@@ -1549,11 +1649,11 @@ def main() -> int:
                 r["rccl_ranks"] = ver.get("rccl_ranks")
         return w, r
 
-    wl, rep = run_sharded_or_single(config, args.steps, args.warmup, keep_log=(want_cpu and rank == 0))
+    wl, rep = run_sharded_or_single(config, args.steps, args.warmup, keep_log=(want_cpu and rank == 0), capture=bool(args.dump_outputs))
     # N > 1 with the default configuration: the fixed population is the line; the weak series (16384 particles per GPU, the
     # 1-GPU line's shape on every rank) rides along as secondary.weak -- every rank takes part in both
     weak_rep = None
-    if world > 1 and args.config is None and not args.no_secondary and not args.particles:
+    if args.full and world > 1 and args.config is None and not args.no_secondary and not args.particles:
         try:
             comm = wl.comm
             wl.comm = None                   # (the communicator outlives the first workload: one per device)
@@ -1599,7 +1699,7 @@ def main() -> int:
             fr_args = argparse.Namespace(**vars(args))
             fr_args.full_rebuild = True
             wf = Workload("C3", fr_args, torch, dist, 0, 1, local_rank, False)
-            mf = measure(wf, 60, 8)
+            mf = measure(wf, 60, 8, full=True)
             out["cpu_baseline"]["gpu_like_for_like_ms_per_step"] = mf["steady"] * 1e3
             out["cpu_baseline"]["gpu_like_for_like_what"] = ("the same scan step through the separate entry points with computeLikelihoodMap over ALL cells and "
                                                              "likelihoodData written every scan (bench.py --full-rebuild), as the CPU port does")
@@ -1610,7 +1710,7 @@ def main() -> int:
             print(f"bench.py: like-for-like (full rebuild) run failed: {e!r}", file=sys.stderr)
 
     # ---- the other single-GPU configurations, shorter runs of the same measurement ------------------------------------
-    if world == 1 and not args.no_secondary and config == "C3" and not (args.full_rebuild or args.host_inputs or args.particles or args.force_sharded):
+    if args.full and world == 1 and not args.no_secondary and config == "C3" and not (args.full_rebuild or args.host_inputs or args.particles or args.force_sharded):
         sec = {}
         # C5 and C2 as BASELINE states them; C4_1gpu = the N = 1 point of the fixed-population series (65536 particles on one GPU);
         # C3x8_batched = eight maps of the headline shape in one batched handle (config 5's mode at 2 cm: what the chip does when the

@@ -5,6 +5,8 @@ import importlib.util
 import json
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -132,3 +134,90 @@ def test_plain_gpus_n_launches_the_ranks_itself(tmp_path):
     env2 = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", GMS_BENCH_LAUNCH_DRYRUN="1")
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index('return self_launch(args.gpus, sys.argv[1:])') < src.index("import torch\n    import torch.distributed as dist")
+
+
+class _StandInWorkload:
+    """the parts of bench.Workload that measure() and outputs() touch, on the host: counts the steps it is asked for"""
+    loop, world, dist = False, 1, None
+
+    def __init__(self, b):
+        import numpy as np
+        import types
+
+        class Map:
+            W = H = 1024
+
+            def profile(self, on):
+                pass
+
+            def profile_calibrate2(self, reps):
+                raise AssertionError("a plain run calibrates no event brackets")
+
+            def download_log(self):
+                return np.arange(self.W * self.H, dtype=np.float64).reshape(self.H, self.W)
+
+            def download_likelihood(self):
+                return np.ones((self.H, self.W))
+
+        class Filter:
+            def stats(self):
+                return dict(weight_sum=1.0, neff=3.5, strongest=7, n_zero=2, max_log_weight=-4.0)
+
+            def get_poses(self):
+                return np.zeros((256, 3), np.float32)
+
+            def get_weights(self):
+                return np.full(256, 1 / 256)
+
+            def weighted_pose(self):
+                return np.zeros(3, np.float32)
+
+        self.m, self.pf, self.steps = Map(), Filter(), []
+        self.torch = types.SimpleNamespace(cuda=types.SimpleNamespace(synchronize=lambda: None))
+        self.outputs = types.MethodType(b.Workload.outputs, self)
+
+    def step(self, i):
+        self.steps.append(i)
+
+    def barrier(self):
+        pass
+
+
+def test_a_plain_measurement_times_exactly_the_requested_steps_once(monkeypatch):
+    b = _bench()
+    monkeypatch.setenv("GMS_BENCH_PREROLL", "7")
+    wl = _StandInWorkload(b)
+    meas = b.measure(wl, 20, 5, full=False, capture=False)
+    assert len(wl.steps) == 7 + 5 + 20 and wl.steps[-20:] == list(range(5, 25))      # pre-roll, warm-up, then one region of 20
+    assert len(meas["regions"]) == 1 and meas["elapsed"] == meas["regions"][0] and meas["outputs"] is None
+    assert meas["warmup_effective"] == 7 + 5 and "prof" not in meas
+
+
+def test_dumped_outputs_are_float_arrays_within_the_limit_and_the_same_cells_every_time(tmp_path):
+    import numpy as np
+    b = _bench()
+    wl = _StandInWorkload(b)
+    wl.m.W = wl.m.H = 4096                  # 16 M cells: more than a dump takes whole
+    b.dump_outputs(str(tmp_path / "a"), wl.outputs())
+    b.dump_outputs(str(tmp_path / "b"), wl.outputs())
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["map_likelihood.npy", "map_log_odds.npy", "poses.npy", "stats.npy", "weighted_pose.npy", "weights.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= b.DUMP_LIMIT_BYTES
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    log = np.load(tmp_path / "a" / "map_log_odds.npy")
+    assert log.size == b.DUMP_MAP_CELLS and np.all(np.diff(log) > 0)        # distinct cells, in index order
+    assert np.load(tmp_path / "a" / "stats.npy").tolist() == [[1.0, 3.5, 7.0, 2.0, -4.0]]
+    with pytest.raises(RuntimeError):
+        b.dump_outputs(str(tmp_path / "c"), {"big": np.zeros(b.DUMP_LIMIT_BYTES // 8 + 1)})
+
+
+def test_dump_outputs_is_refused_where_it_is_not_supported():
+    import subprocess
+    import sys
+    env = dict(os.environ, GMS_BENCH_LAUNCH_DRYRUN="1")
+    env.pop("WORLD_SIZE", None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "x"], capture_output=True,
+                         text=True, env=env, timeout=120)
+    assert out.returncode == 2 and "--dump-outputs" in out.stderr and not out.stdout

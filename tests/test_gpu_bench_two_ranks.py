@@ -53,7 +53,7 @@ def _run(cmd_tail, timeout):
 
 def test_bench_with_two_ranks_on_one_gpu_falls_back_verifies_and_reports(tmp_path):
     rep = str(tmp_path / "report.json")
-    out = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--config", "C2", "--particles", "1024", "--report", rep], 240)
+    out = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--config", "C2", "--particles", "1024", "--full", "--report", rep], 240)
     d, full = _line_and_report(out, rep)
     assert d["n_gpus"] == 2 and d["steps"] == 6 and d["scaling"] == "weak"
     assert d["config"]["particles_total"] == 2048 and "sharded x2" in d["config"]["parallelism"]
@@ -68,7 +68,7 @@ def test_bench_default_configuration_with_two_ranks_is_the_fixed_population_with
     """No --config at N > 1 = BASELINE configs[3]: ONE population split over the ranks ("strong"); the weak series rides along.
     (--particles would switch the companion run off, so the sizes here are the real ones: 2 x 32768 and 2 x 16384 on one GPU.)"""
     rep = str(tmp_path / "report.json")
-    out = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--report", rep], 420)
+    out = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--report", rep], 420)
     d, full = _line_and_report(out, rep)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["config"]["particles_total"] == 65536 and d["config"]["particles_per_gpu"] == 32768
@@ -104,7 +104,7 @@ def test_plain_python_bench_gpus_2_launches_its_own_ranks(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--config", "C2",
-                          "--particles", "1024", "--report", rep], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+                          "--particles", "1024", "--full", "--report", rep], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d, full = _line_and_report(out, rep)
     assert d["n_gpus"] == 2 and d["steps"] == 5 and d["config"]["particles_total"] == 2048
@@ -117,7 +117,7 @@ def test_bench_particle_maps_sharded_over_two_ranks_on_one_gpu(tmp_path):
     ranks sharing device 0 with gloo collectives (records staged through the host): one well-formed line from rank 0, the population
     fixed (strong scaling), maps crossing the rank boundary counted."""
     rep = str(tmp_path / "report.json")
-    out = _run(["--gpus", "2", "--particle-maps", "512,4,72", "--steps", "4", "--report", rep], 240)
+    out = _run(["--gpus", "2", "--particle-maps", "512,4,72", "--steps", "4", "--full", "--report", rep], 240)
     d, full = _line_and_report(out, rep)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
     pm = full["per_particle_maps_sharded"]

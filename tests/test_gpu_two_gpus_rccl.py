@@ -37,7 +37,7 @@ def test_bench_over_rccl_shards_the_fixed_population_and_equals_the_standalone_f
     env.pop("GMS_BENCH_SHARE_DEVICE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "3",
-           "--no-secondary", "--report", rep]
+           "--full", "--no-secondary", "--report", rep]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

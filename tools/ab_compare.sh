@@ -11,7 +11,7 @@ ROUNDS=${1:-3}; [ $# -gt 0 ] && shift
 ARGS=${@:---steps 200 --warmup 20 --no-cpu-baseline --no-secondary}
 for r in $(seq 1 $ROUNDS); do
   for v in A B; do
-    GMS_LIBRARY=$L/$v.so python bench.py $ARGS 2>/dev/null | tail -1 | python -c "
+    GMS_LIBRARY=$L/$v.so python bench.py --full $ARGS 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$v', round(d['ms_per_step']*1e3,2), 'us/step', {k:v.get('avg_launch_us') for k,v in d['kernels'].items()}, flush=True)"

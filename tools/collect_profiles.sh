@@ -18,7 +18,7 @@ pmc() {     # name, counter, command...
   local name=$1 ctr=$2; shift 2
   rocprofv3 --kernel-trace --pmc "$ctr" --output-format csv -d "$OUT/${name}_$ctr" -- "$@" > /dev/null 2> "$OUT/${name}_$ctr.stderr"
 }
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-secondary"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-secondary"
 stats c3_bench $B --steps 200 --warmup 20
 pmc c3 FETCH_SIZE $B --steps 50 --warmup 5
 pmc c3 WRITE_SIZE $B --steps 50 --warmup 5
@@ -31,7 +31,7 @@ pmc dense FETCH_SIZE $K
 pmc dense WRITE_SIZE $K
 stats c3_full_rebuild $B --full-rebuild --steps 100 --warmup 10
 # the reference's own filter shape (one GridMapData per particle): kernel trace at both sizes, fabric traffic at the size that leaves the caches
-PM="python3 $ROOT/bench.py --no-cpu-baseline"
+PM="python3 $ROOT/bench.py --full --no-cpu-baseline"
 stats pm500 $PM --particle-maps 500,6,90 --steps 50 --report "$OUT/pm500_report.json"
 stats pm4096 $PM --particle-maps 4096,12.8,180 --steps 10 --report "$OUT/pm4096_report.json"
 pmc pm4096 FETCH_SIZE $PM --particle-maps 4096,12.8,180 --steps 6 --report "$OUT/pm4096_pmc_report.json"
@@ -67,25 +67,25 @@ cp gpurun_out/microbench/persistent_step.txt "$OUT/keep/persistent_step_model_ru
 mkdir -p "profiles/$R"
 cp "$OUT/keep/pmc_traffic.json" "$OUT/keep/microbench.json" "profiles/$R/" 2>/dev/null
 # un-profiled bench lines (stdout = the one compact line; --report = the full report)
-python3 bench.py --report "$OUT/keep/bench_report.json" > "$OUT/keep/bench.json" 2> "$OUT/bench.stderr"
-python3 bench.py --steps 20 --warmup 5 --report "$OUT/keep/bench_steps20_report.json" > "$OUT/keep/bench_steps20.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --report "$OUT/keep/bench_report.json" > "$OUT/keep/bench.json" 2> "$OUT/bench.stderr"
+python3 bench.py --full --steps 20 --warmup 5 --report "$OUT/keep/bench_steps20_report.json" > "$OUT/keep/bench_steps20.json" 2>> "$OUT/bench.stderr"
 Q="--no-cpu-baseline --no-secondary"
-python3 bench.py --force-sharded $Q --report "$OUT/keep/bench_sharded_one_rank_report.json" > "$OUT/keep/bench_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --config C4 --force-sharded $Q --steps 50 --warmup 5 --report "$OUT/keep/bench_c4_sharded_one_rank_report.json" > "$OUT/keep/bench_c4_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --host-inputs $Q --report "$OUT/keep/bench_host_inputs_report.json" > "$OUT/keep/bench_host_inputs.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --full-rebuild $Q --report "$OUT/keep/bench_full_rebuild_report.json" > "$OUT/keep/bench_full_rebuild.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --config C5 --steps 50 --warmup 5 --report "$OUT/keep/bench_c5_report.json" > "$OUT/keep/bench_c5.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --trace tests/golden/recording_360.bin --steps 300 --warmup 20 --report "$OUT/keep/bench_trace_replay_report.json" > "$OUT/keep/bench_trace_replay.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 500,6,90 --steps 50 --report "$OUT/keep/bench_particle_maps_500_report.json" > "$OUT/keep/bench_particle_maps_500.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 500,6,180 --steps 50 --no-cpu-baseline --report "$OUT/keep/bench_particle_maps_500_b180_report.json" > "$OUT/keep/bench_particle_maps_500_b180.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 4096,12.8,180 --steps 20 --no-cpu-baseline --report "$OUT/keep/bench_particle_maps_4096_report.json" > "$OUT/keep/bench_particle_maps_4096.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 500,6,90 --refine --steps 50 --report "$OUT/keep/bench_particle_maps_500_refine_report.json" > "$OUT/keep/bench_particle_maps_500_refine.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 500,6,180 --refine --steps 50 --report "$OUT/keep/bench_particle_maps_500_b180_refine_report.json" > "$OUT/keep/bench_particle_maps_500_b180_refine.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 1024,6,90 --force-sharded --steps 200 --report "$OUT/keep/bench_particle_maps_sharded_one_rank_report.json" > "$OUT/keep/bench_particle_maps_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
-python3 bench.py --particle-maps 4096,12.8,180 --force-sharded --steps 20 --report "$OUT/keep/bench_particle_maps_4096_sharded_one_rank_report.json" > "$OUT/keep/bench_particle_maps_4096_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --force-sharded $Q --report "$OUT/keep/bench_sharded_one_rank_report.json" > "$OUT/keep/bench_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --config C4 --force-sharded $Q --steps 50 --warmup 5 --report "$OUT/keep/bench_c4_sharded_one_rank_report.json" > "$OUT/keep/bench_c4_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --host-inputs $Q --report "$OUT/keep/bench_host_inputs_report.json" > "$OUT/keep/bench_host_inputs.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --full-rebuild $Q --report "$OUT/keep/bench_full_rebuild_report.json" > "$OUT/keep/bench_full_rebuild.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --config C5 --steps 50 --warmup 5 --report "$OUT/keep/bench_c5_report.json" > "$OUT/keep/bench_c5.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --trace tests/golden/recording_360.bin --steps 300 --warmup 20 --report "$OUT/keep/bench_trace_replay_report.json" > "$OUT/keep/bench_trace_replay.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 500,6,90 --steps 50 --report "$OUT/keep/bench_particle_maps_500_report.json" > "$OUT/keep/bench_particle_maps_500.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 500,6,180 --steps 50 --no-cpu-baseline --report "$OUT/keep/bench_particle_maps_500_b180_report.json" > "$OUT/keep/bench_particle_maps_500_b180.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 4096,12.8,180 --steps 20 --no-cpu-baseline --report "$OUT/keep/bench_particle_maps_4096_report.json" > "$OUT/keep/bench_particle_maps_4096.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 500,6,90 --refine --steps 50 --report "$OUT/keep/bench_particle_maps_500_refine_report.json" > "$OUT/keep/bench_particle_maps_500_refine.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 500,6,180 --refine --steps 50 --report "$OUT/keep/bench_particle_maps_500_b180_refine_report.json" > "$OUT/keep/bench_particle_maps_500_b180_refine.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 1024,6,90 --force-sharded --steps 200 --report "$OUT/keep/bench_particle_maps_sharded_one_rank_report.json" > "$OUT/keep/bench_particle_maps_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
+python3 bench.py --full --particle-maps 4096,12.8,180 --force-sharded --steps 20 --report "$OUT/keep/bench_particle_maps_4096_sharded_one_rank_report.json" > "$OUT/keep/bench_particle_maps_4096_sharded_one_rank.json" 2>> "$OUT/bench.stderr"
 # one rank's SLAM.update at the shard sizes of 2 / 4 / 8 GPUs for 4096 x 256^2 (DESIGN.md section 7's table), and the refinement with the field in memory
 for n in 2048 1024 512; do
-  python3 bench.py --particle-maps $n,12.8,180 --steps 20 --no-cpu-baseline --report "$OUT/keep/pm_shard_${n}_report.json" > "$OUT/keep/pm_shard_$n.json" 2>> "$OUT/bench.stderr"
+  python3 bench.py --full --particle-maps $n,12.8,180 --steps 20 --no-cpu-baseline --report "$OUT/keep/pm_shard_${n}_report.json" > "$OUT/keep/pm_shard_$n.json" 2>> "$OUT/bench.stderr"
 done
 python3 tools/pm_refine_big.py > "$OUT/keep/pm_refine_4096.txt" 2>> "$OUT/bench.stderr"
 python3 tools/ab_update.py gridmap_slam_robot_amd/lib/libgridmapslam.so gridmap_slam_robot_amd/lib/libgridmapslam.so 500 6.0 90 2 > "$OUT/keep/pm500_update_unbracketed.txt" 2>> "$OUT/bench.stderr"
@@ -98,7 +98,7 @@ cp gpurun_out/pmc_lik/summary.json "$OUT/keep/dense_likelihood_counters.json" 2>
 bash tools/nseg_table.sh > "$OUT/keep/nseg_8_vs_16.txt" 2>&1
 # the per-GPU step of the fixed-population series (config 4) at 1 / 2 / 4 / 8 GPUs' shard sizes, on one GPU (no exchange): DESIGN.md section 7's curve
 for n in 65536 32768 16384 8192; do
-  python3 bench.py --config C4 --particles $n $Q --steps 100 --warmup 10 --report "$OUT/keep/bench_c4_shard_${n}_report.json" > "$OUT/keep/bench_c4_shard_${n}.json" 2>> "$OUT/bench.stderr"
+  python3 bench.py --full --config C4 --particles $n $Q --steps 100 --warmup 10 --report "$OUT/keep/bench_c4_shard_${n}_report.json" > "$OUT/keep/bench_c4_shard_${n}.json" 2>> "$OUT/bench.stderr"
 done
 # the float domain of the rounded primitives, exhausted, with the record kept
 GMS_EXHAUSTIVE=1 python3 -m pytest tests/test_gpu_exhaustive_float.py -m gpu -q > "$OUT/exhaustive.stdout" 2>&1
@@ -119,7 +119,7 @@ bash tools/lik_phases.sh > "$OUT/keep/dense_likelihood_phases.txt" 2>> "$OUT/ben
 python3 tools/lognorm_probe.py > "$OUT/keep/lognorm_probe.txt" 2>> "$OUT/bench.stderr"
 # config 5 split by map: one GPU's share at 1 / 2 / 4 / 8 GPUs
 for mm in 64 32 16 8; do
-  python3 bench.py --config C5 --maps $mm --steps 30 --warmup 4 $Q --report "$OUT/keep/bench_c5_maps_${mm}_report.json" > "$OUT/keep/bench_c5_maps_${mm}.json" 2>> "$OUT/bench.stderr"
+  python3 bench.py --full --config C5 --maps $mm --steps 30 --warmup 4 $Q --report "$OUT/keep/bench_c5_maps_${mm}_report.json" > "$OUT/keep/bench_c5_maps_${mm}.json" 2>> "$OUT/bench.stderr"
 done
 ls -la "$OUT/keep"
 for f in "$OUT"/keep/*_kernel_stats.csv; do echo "== $f"; python3 tools/kstats.py "$f" | head -8; done

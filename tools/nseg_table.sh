@@ -7,7 +7,7 @@ for r in 1 2 3; do
   for v in seg16 seg8; do
     for cfg in "C3:--config C3" "C4_8192:--config C4 --particles 8192"; do
       name=${cfg%%:*}; args=${cfg#*:}
-      GMS_LIBRARY=$L/$v.so python bench.py $args --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --report /tmp/nseg_rep.json 2>/dev/null | python -c "
+      GMS_LIBRARY=$L/$v.so python bench.py --full $args --steps 200 --warmup 20 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernel_us']

@@ -1,7 +1,8 @@
 # per-particle-map update: builds lib/pm_*.so against the product, alternated on one box; then the parity tests of this tree
 L=$PWD/gridmap_slam_robot_amd/lib
-pm() { python3 bench.py --particle-maps $1 --steps $2 --no-cpu-baseline --report /tmp/r.json 2>/dev/null >/dev/null; python3 -c "
-import json; d=json.load(open('/tmp/r.json')); k=d.get('kernels') or d.get('per_kernel') or {}
+REP=$(mktemp)
+pm() { python3 bench.py --full --particle-maps $1 --steps $2 --no-cpu-baseline --report "$REP" 2>/dev/null >/dev/null; python3 -c "
+import json; d=json.load(open('$REP')); k=d.get('kernels') or d.get('per_kernel') or {}
 print(d.get('ms_per_step'), {a: (b.get('us') if isinstance(b, dict) else b) for a, b in k.items()} if k else list(d.keys())[:12])"; }
 for r in 1 2; do
 for v in $(ls $L | grep '^pm_' | sed 's/.so//') libgridmapslam; do
