@@ -14,6 +14,11 @@
 // write-back: for data nobody in this launch reads again.
 __device__ __forceinline__ void store_through(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void store_through(uint64_t *p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// COHERENT: a load that sees what another workgroup of the same launch wrote through (agent scope: past this XCD's L2 copy)
+template <bool COHERENT>
+__device__ __forceinline__ double load_coherent(const double *p) {
+    return COHERENT ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+}
 
 // Development builds only (-DGMS_STAMPS, tools/stamps.py): wall-clock stamps (100 MHz) of a kernel's stages, one row of
 // GMS_STAMP_SLOTS per workgroup, written by thread 0.  Compiled out of the product library.

@@ -37,10 +37,13 @@ k_norm_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_
                int32_t n, int64_t offset, PackedParticle *__restrict__ packed, double *__restrict__ cum,
                double *__restrict__ chunk_tot, int64_t nchunks, double *__restrict__ p2, PfStatsDev *__restrict__ stats,
                uint32_t n_norm_blocks, double *__restrict__ logd, uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend,
-               uint32_t n_near_blocks, const double *__restrict__ logw_lognorm) {
+               uint32_t n_near_blocks, const double *__restrict__ logw_lognorm, uint32_t *__restrict__ res_ticket,
+               double *__restrict__ res_pre) {
     extern __shared__ __align__(16) unsigned char smem[];
     // workgroups: [far-field ray blocks | near-field ray blocks) = n_ray_blocks, then normalise, then the riding apply pass
     // logw_lognorm != nullptr: the partial vector is block-relative (gms_pf_set_log_normalize, block_partials)
+    // res_ticket != nullptr: the last normalise workgroup folds Neff and scans the chunk offsets for k_lik_resample (resample_prefix_last),
+    // in the shadow of the ray cast
     GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 0);
     if (blockIdx.x >= n_ray_blocks + n_norm_blocks) {
         // The PREVIOUS scan's `logData[c] += ...` (GridMap.java:223) from the other count grid: it needs nothing of this launch
@@ -75,7 +78,8 @@ k_norm_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_
                                              smem, s_pose, n_near_blocks ? 1 : 0);
     } else {
         normalize_pack_body(partials, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2, stats,
-                            blockIdx.x - n_ray_blocks, 0, LOGNORM ? logw_lognorm : (const double *)nullptr);
+                            blockIdx.x - n_ray_blocks, 0, LOGNORM ? logw_lognorm : (const double *)nullptr, res_ticket, n_norm_blocks,
+                            res_pre, smem);
         GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 14);
     }
 }
@@ -162,7 +166,7 @@ k_lik_resample(GridDev g, const double *__restrict__ logd, double *__restrict__ 
                int32_t n, int64_t offset,
                float *__restrict__ pose2, float *__restrict__ cs2, double *__restrict__ w2, int32_t *__restrict__ idx_out,
                const double *__restrict__ p2, int64_t nblk_global, PfStatsDev *__restrict__ stats, int32_t raw_weights,
-               int32_t *__restrict__ bbox_clear, int32_t lik_mode) {
+               int32_t *__restrict__ bbox_clear, int32_t lik_mode, const double *__restrict__ res_pre) {
     extern __shared__ __align__(16) unsigned char smem[];
     // the box half the next ray cast will raise: cleared here because that ray cast may share its launch with this scan's
     // deferred apply pass (k_raycast_apply), which otherwise does the clearing
@@ -170,7 +174,7 @@ k_lik_resample(GridDev g, const double *__restrict__ logd, double *__restrict__ 
     if (blockIdx.x == 0 && threadIdx.x < 4) bbox_clear[4 * blockIdx.y + threadIdx.x] = 0;
     if (blockIdx.x < n_res_blocks)                      // a multiple of 8 keeps the likelihood tiles' XCD round-robin aligned
         resample_body(glob, n_global, nchunks, cum, chunk_off, r01_maps, r01, fraction, n, offset, pose2, cs2, w2, idx_out, p2,
-                      nblk_global, stats, blockIdx.x, blockIdx.y, smem, raw_weights != 0);
+                      nblk_global, stats, blockIdx.x, blockIdx.y, smem, raw_weights != 0, res_pre);
     else
         likelihood_body<KH, SPLIT>(g, logd, lik, fac, fac_stride, taps_g, bbox, 1, tiles_x, tiles_y, blockIdx.x - n_res_blocks,
                                    blockIdx.y, gridDim.x - n_res_blocks, smem, cnt_pending, tile_state, lik_mode);
@@ -207,7 +211,11 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
     if (own) { pf->d_global = pf->d_global_own; pf->global_raw = 0; }     // normalised weights are packed (as apply_partials does)
     const uint32_t n_near = rc_near_blocks(m, B);
     const uint32_t n_ray = (uint32_t)((B + RCF_RAYS - 1) / RCF_RAYS) + n_near, n_norm = (uint32_t)((pf->n + 255) / 256);
-    const size_t smem = rc_smem(m, RCF_RAYS, n_near);
+    // own population: the last normalise workgroup also folds Neff and scans the chunk offsets (resample_prefix_last) in LDS
+    const int64_t nch = nchunks_of(pf);
+    const size_t smem_pre = own ? (size_t)(nch + 1 + (nch + 63) / 64 + 1) * sizeof(double) : 0;
+    size_t smem = rc_smem(m, RCF_RAYS, n_near);
+    if (smem < smem_pre) smem = smem_pre;
     // a deferred apply pass rides along: the ray cast then raises the OTHER box half (cleared by the previous likelihood launch)
     // while the pass reads the pending scan's half; afterwards that other half is the current one (gms_apply_done)
     uint32_t n_apply = 0;
@@ -226,14 +234,16 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
                            rc_nw_max(m), n_ray, d_partials, nblk_global_of(pf), pf->d_w, pf->d_pose, pf->n, pf->offset, d_packed_local, \
                            own ? pf->d_cum : (double *)nullptr, own ? pf->d_chunk_tot : (double *)nullptr, nchunks_of(pf),          \
                            own ? pf->d_p2 : (double *)nullptr, pf->d_stats, n_norm, m->d_log, m->d_cnt_pend, pend, n_near,          \
-                           LN ? (const double *)pf->d_logw : (const double *)nullptr);                                              \
+                           LN ? (const double *)pf->d_logw : (const double *)nullptr, own ? pf->d_res_ticket : (uint32_t *)nullptr,       \
+                           pf->d_res_pre);                                                                                              \
     } while (0)
     if (lognorm) NR_LAUNCH(true); else NR_LAUNCH(false);
 #undef NR_LAUNCH
     pf->score_fresh = 0;                                              // the scoring pass has been consumed
     if (n_apply) gms_apply_done(m);
     pf->chunks_ready = own ? 1 : 0;
-    pf->neff_folded = 0;
+    pf->neff_folded = own ? 1 : 0;                                    // (resample_prefix_last wrote stats.norm_sum / sq_sum)
+    pf->res_pre_ready = own ? 1 : 0;
 }
 
 // block partials (SLAM.java:100-115) beside the apply pass the previous paired step left pending
@@ -259,6 +269,9 @@ void gms_launch_partials_apply(gms_pf *pf, double *d_partials, bool apply_rides_
 void gms_launch_lik_resample(gms_pf *pf, double fraction) {
     gms_map *m = pf->map;
     gms_launch_pf_chunk_sums(pf);                     // no-op when level 0 is already there
+    // the chunk offsets and Neff folded by the paired normalise (gms_launch_norm_raycast), or the resample workgroups fold them
+    const double *pre = pf->res_pre_ready ? (const double *)pf->d_res_pre : (const double *)nullptr;
+    pf->res_pre_ready = 0;
     ProfScope ps(m, GMS_K_LIKELIHOOD);
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
@@ -287,7 +300,7 @@ void gms_launch_lik_resample(gms_pf *pf, double fraction) {
                            m->d_lik, m->d_fac, m->fac_stride, m->d_taps, bb, tiles_x, tiles_y, m->d_cnt, m->d_tile_state, n_res, pf->d_global, \
                            pf->n_global, nch, pf->d_cum, pf->d_chunk_tot, r01_maps, pf->r01_scalar, fraction, pf->n, pf->offset, \
                            pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, pf->d_p2, nblk_global_of(pf), pf->d_stats,       \
-                           pf->global_raw, m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4, lik_mode);             \
+                           pf->global_raw, m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4, lik_mode, pre);        \
     } while (0)
     if (k == 3) { if (split) LR_LAUNCH(3, 2); else LR_LAUNCH(3, 1); }
     else if (k == 5) { if (split) LR_LAUNCH(5, 2); else LR_LAUNCH(5, 1); }
@@ -346,6 +359,7 @@ void gms_launch_raycast_norm_chunks(gms_pf *pf, const gms_beam *d_beams, int32_t
     if (n_apply) gms_apply_done(m);
     pf->chunks_ready = 1;
     pf->neff_folded = 0;
+    pf->res_pre_ready = 0;                            // (sharded: the resample workgroups fold Neff and scan the offsets themselves)
 }
 
 // de-skew of one raw scan beside the motion-model sample of a single-map filter's particles

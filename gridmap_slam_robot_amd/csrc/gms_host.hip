@@ -888,7 +888,9 @@ static int64_t nchunks_of(int64_t n) { return (n + 63) / 64; }
 
 static void pf_free_global(gms_pf *pf) {
     hipFree(pf->d_partials); hipFree(pf->d_p2); hipFree(pf->d_global_own); hipFree(pf->d_chunk_tot); hipFree(pf->d_cum);
+    hipFree(pf->d_res_pre); hipFree(pf->d_res_ticket);
     pf->d_partials = pf->d_p2 = nullptr; pf->d_global = pf->d_global_own = nullptr; pf->d_chunk_tot = pf->d_cum = nullptr;
+    pf->d_res_pre = nullptr; pf->d_res_ticket = nullptr; pf->res_pre_ready = 0;
 }
 
 static int pf_alloc_global(gms_pf *pf) {
@@ -901,6 +903,9 @@ static int pf_alloc_global(gms_pf *pf) {
     pf->d_global = pf->d_global_own;
     HIPCHK(hipMalloc(&pf->d_chunk_tot, M * (nch + 1 + nch * 8) * sizeof(double)));     // chunk totals of all maps, then every chunk's eight octet boundaries (chunk_sub_of)
     HIPCHK(hipMalloc(&pf->d_cum, M * pf->n_global * sizeof(double)));
+    HIPCHK(hipMalloc(&pf->d_res_pre, M * (nch + 3) * sizeof(double)));
+    HIPCHK(hipMalloc(&pf->d_res_ticket, M * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(pf->d_res_ticket, 0, M * sizeof(uint32_t), pf->map->stream));
     return GMS_OK;
 }
 

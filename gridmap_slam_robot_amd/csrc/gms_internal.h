@@ -172,6 +172,9 @@ struct gms_pf {
     PackedParticle *d_global;       // [n_maps][n_global] source population (own copy when unsharded)
     double *d_chunk_tot;            // [n_maps][nchunks] scan chunk totals / offsets
     double *d_cum;                  // [n_maps][n_global] in-chunk inclusive sums
+    double *d_res_pre;              // [n_maps][nchunks + 3] chunk offsets + grand total, sum wn, sq_sum: folded by the paired step's normalise (resample_prefix_last)
+    uint32_t *d_res_ticket;         // [n_maps] its ticket counter (0 between launches)
+    int32_t res_pre_ready;          // d_res_pre describes d_global's current level 0 (set by gms_launch_norm_raycast, consumed by gms_launch_lik_resample)
     PfStatsDev *d_stats;            // [2][n_maps]: [0] of the last normalise, [1] of the current particles (recomputed on demand)
     int32_t stats_current;          // d_stats[0] still describes the current particles
     PfStatsDev *h_stats;            // pinned

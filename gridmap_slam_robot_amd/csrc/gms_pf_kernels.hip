@@ -817,10 +817,12 @@ __device__ __forceinline__ int64_t block_count(int64_t n, int64_t blk) {
 
 // calculateNeff (SLAM.java:180-190) from the per-block {sum wn, sum wn^2} of the normalised population:
 // sum = fold(sum wn); sq_sum = fold(sum wn^2) / sum^2; Neff = 1 / sq_sum.  Every thread of the workgroup calls.
+// COHERENT: the partials were written through by other workgroups of the same launch (normalize_pack_body's last workgroup)
+template <bool COHERENT = false>
 __device__ __forceinline__ void fold_neff(const double *__restrict__ p2, int64_t nblk, double &norm_sum, double &sq_sum,
                                           double *lds) {
     double a = 0.0, q = 0.0;
-    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) { a += p2[2 * b]; q += p2[2 * b + 1]; }
+    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) { a += load_coherent<COHERENT>(&p2[2 * b]); q += load_coherent<COHERENT>(&p2[2 * b + 1]); }
     norm_sum = group_sum(a, lds);
     const double qq = group_sum(q, lds);
     sq_sum = qq / (norm_sum * norm_sum);
@@ -882,9 +884,11 @@ k_partials(double *__restrict__ w, double *__restrict__ logw, const float *__res
 __device__ __forceinline__ double *chunk_sub_of(double *chunk_tot_all, int64_t nchunks, int32_t n_maps, int32_t mi) {
     return chunk_tot_all + (size_t)n_maps * (nchunks + 1) + (size_t)mi * nchunks * 8;
 }
+// through: the chunk totals and the block's {sum wn, sum wn^2} are written through to memory, for a workgroup of the same launch that
+// folds them (normalize_pack_body's ticket)
 __device__ __forceinline__ void block_chunk_scan(double v, int64_t i, int64_t n_pop, int64_t blk, int64_t nchunks,
                                                  double *__restrict__ cum, double *__restrict__ chunk_tot,
-                                                 double *__restrict__ p2_blk, double *__restrict__ sub) {
+                                                 double *__restrict__ p2_blk, double *__restrict__ sub, bool through = false) {
     __shared__ double s_ct[4][2];
     const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double inc = v;
@@ -899,16 +903,109 @@ __device__ __forceinline__ void block_chunk_scan(double v, int64_t i, int64_t n_
     if ((lane & 7) == 7 && blk * 4 + wave < nchunks) sub[(blk * 4 + wave) * 8 + (lane >> 3)] = inc;
     if (lane == 0) {
         const int64_t c = blk * 4 + wave;
-        if (c < nchunks) chunk_tot[c] = tot;
+        if (c < nchunks) { if (through) store_through(&chunk_tot[c], tot); else chunk_tot[c] = tot; }
         s_ct[wave][0] = tot; s_ct[wave][1] = sq;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        p2_blk[0] = ((s_ct[0][0] + s_ct[1][0]) + s_ct[2][0]) + s_ct[3][0];
-        p2_blk[1] = ((s_ct[0][1] + s_ct[1][1]) + s_ct[2][1]) + s_ct[3][1];
+        const double a = ((s_ct[0][0] + s_ct[1][0]) + s_ct[2][0]) + s_ct[3][0];
+        const double q = ((s_ct[0][1] + s_ct[1][1]) + s_ct[2][1]) + s_ct[3][1];
+        if (through) { store_through(&p2_blk[0], a); store_through(&p2_blk[1], q); } else { p2_blk[0] = a; p2_blk[1] = q; }
     }
 }
 static_assert(4 * SCAN_CHUNK == GMS_BLOCK, "a reduction block is four scan chunks");
+
+// Levels 1 and 2 of the cumulative weights in LDS: off[0, nchunks) holds the chunk totals on entry, the chunk offsets on return, off[nchunks]
+// the grand total; off[nchunks + 1, + nsuper + 1) is the super-chunk scratch.  Every thread of the workgroup calls.  (resample_body, and the
+// last normalise workgroup of a paired step: normalize_pack_body)
+__device__ __forceinline__ void chunk_offsets_scan(double *off, int64_t nchunks) {
+    const int64_t nsuper = (nchunks + 63) / 64;
+    double *sup = off + nchunks + 1;                                   // [nsuper + 1]
+    __syncthreads();
+    // level 1: one wavefront per super-chunk of 64 chunk totals, exclusive scan by shuffles (a fixed shape)
+    for (int64_t sidx = threadIdx.x >> 6; sidx < nsuper; sidx += blockDim.x >> 6) {
+        const int32_t lane = threadIdx.x & 63;
+        const int64_t c = sidx * 64 + lane;
+        const double v = c < nchunks ? off[c] : 0.0;
+        double inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const double up = __shfl_up(inc, o, GMS_WAVE);
+            if (lane >= o) inc += up;
+        }
+        const double excl = __shfl_up(inc, 1, GMS_WAVE);
+        if (c < nchunks) off[c] = lane == 0 ? 0.0 : excl;
+        if (lane == 63) sup[sidx] = inc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {                                                   // level 2: wavefront 0, 64 totals per pass
+        const int32_t lane = threadIdx.x;
+        double carry = 0.0;
+        for (int64_t s0 = 0; s0 < nsuper; s0 += 64) {
+            const int64_t sidx = s0 + lane;
+            const double v = sidx < nsuper ? sup[sidx] : 0.0;
+            double inc = v;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const double up = __shfl_up(inc, o, GMS_WAVE);
+                if (lane >= o) inc += up;
+            }
+            const double excl = __shfl_up(inc, 1, GMS_WAVE);
+            if (sidx < nsuper) sup[sidx] = s0 == 0 ? (lane == 0 ? 0.0 : excl) : carry + (lane == 0 ? 0.0 : excl);
+            const double tot = __shfl(inc, 63, GMS_WAVE);
+            carry = s0 == 0 ? tot : carry + tot;
+        }
+        if (lane == 0) off[nchunks] = carry;                                  // grand total
+    }
+    __syncthreads();
+    for (int64_t c = 64 + threadIdx.x; c < nchunks; c += blockDim.x) off[c] = sup[c >> 6] + off[c];   // super-chunk 0 adds nothing
+    __syncthreads();
+}
+
+// The paired step's resampling prefix, folded where it hides (k_norm_raycast: the ray cast beside it runs several microseconds longer than the
+// normalise workgroups): the workgroup that finishes its level 0 last -- a ticket tells -- folds calculateNeff (SLAM.java:180-190) and scans
+// levels 1 and 2 of the chunk totals, with fold_neff and chunk_offsets_scan as resample_body would, and publishes pre[0, nchunks] = the chunk
+// offsets and the grand total, pre[nchunks + 1] = sum wn, pre[nchunks + 2] = sq_sum (and both in stats).  The hand-off is DESIGN 4's hardware
+// protocol: the totals were written through (block_chunk_scan), every wavefront waits for their acknowledgement, one relaxed agent-scope
+// ticket, coherent loads by the last workgroup -- no release fence, which would write back the whole L2 of the XCD under the ray cast.  The
+// last ticket also puts the counter back to 0 for the next step (nothing of this launch touches it after that).
+// smem: (nchunks + 1) + (nchunks + 63) / 64 + 1 doubles; lds: the caller's reduction scratch.  Every thread of the workgroup calls.
+__device__ __forceinline__ void
+resample_prefix_last(const double *__restrict__ p2, int64_t nblk, const double *__restrict__ tot, int64_t nchunks, uint32_t *__restrict__ ticket,
+                     uint32_t n_blocks, double *__restrict__ pre, PfStatsDev *__restrict__ stats, unsigned char *smem, double *lds) {
+    __shared__ int32_t s_last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // this wavefront's write-through stores are acknowledged
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == n_blocks - 1;
+        if (s_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    double *off = reinterpret_cast<double *>(smem);
+    double tv[8];                                                      // in flight during the fold, as in resample_body
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const int64_t c = (int64_t)threadIdx.x + k * (int64_t)blockDim.x; tv[k] = c < nchunks ? load_coherent<true>(&tot[c]) : 0.0; }
+    double norm_sum, sq_sum;
+    fold_neff<true>(p2, nblk, norm_sum, sq_sum, lds);
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const int64_t c = (int64_t)threadIdx.x + k * (int64_t)blockDim.x; if (c < nchunks) off[c] = tv[k]; }
+    for (int64_t c0 = (int64_t)threadIdx.x + 8 * (int64_t)blockDim.x; c0 < nchunks; c0 += 8 * (int64_t)blockDim.x) {
+        double v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) { const int64_t c = c0 + k * (int64_t)blockDim.x; v[k] = c < nchunks ? load_coherent<true>(&tot[c]) : 0.0; }
+#pragma unroll
+        for (int k = 0; k < 8; k++) { const int64_t c = c0 + k * (int64_t)blockDim.x; if (c < nchunks) off[c] = v[k]; }
+    }
+    chunk_offsets_scan(off, nchunks);
+    for (int64_t c = threadIdx.x; c <= nchunks; c += blockDim.x) pre[c] = off[c];
+    if (threadIdx.x == 0) {
+        pre[nchunks + 1] = norm_sum; pre[nchunks + 2] = sq_sum;
+        stats->norm_sum = norm_sum; stats->sq_sum = sq_sum;
+    }
+    GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 13);
+}
 
 // phase 2: every workgroup folds the (all-reduced) partials; weight /= weightSum (SLAM.java:120-121);
 // packs {w,x,y,theta} (the all-gather payload / the resampling source).  A stand-alone filter also
@@ -918,7 +1015,8 @@ normalize_pack_body(const double *__restrict__ partials_all, int64_t nblk_global
                     const float *__restrict__ pose, int32_t n, int64_t offset, PackedParticle *__restrict__ packed,
                     double *__restrict__ cum, double *__restrict__ chunk_tot, int64_t nchunks,
                     double *__restrict__ p2_all, PfStatsDev *__restrict__ stats, uint32_t bx, uint32_t by,
-                    const double *__restrict__ logw_lognorm = nullptr) {
+                    const double *__restrict__ logw_lognorm = nullptr, uint32_t *__restrict__ ticket = nullptr,
+                    uint32_t n_blocks = 0, double *__restrict__ pre = nullptr, unsigned char *smem = nullptr) {
     // logw_lognorm != nullptr (gms_pf_set_log_normalize): the partial vector is block-relative (block_partials) and the weights are
     // formed here from the log-weights, exp(logw - M) / sum
     __shared__ RedLds L;
@@ -944,7 +1042,10 @@ normalize_pack_body(const double *__restrict__ partials_all, int64_t nblk_global
     }
     if (cum)                                          // uniform
         block_chunk_scan(wn, i, n, bx, nchunks, cum + (size_t)mi * n, chunk_tot + (size_t)mi * (nchunks + 1),
-                         p2_all + ((size_t)mi * nblk_global + bx) * 2, chunk_sub_of(chunk_tot, nchunks, (int32_t)gridDim.y, mi));
+                         p2_all + ((size_t)mi * nblk_global + bx) * 2, chunk_sub_of(chunk_tot, nchunks, (int32_t)gridDim.y, mi),
+                         ticket != nullptr);
+    if (cum && ticket) resample_prefix_last(p2_all + (size_t)mi * nblk_global * 2, nblk_global, chunk_tot + (size_t)mi * (nchunks + 1),
+                                            nchunks, ticket + mi, n_blocks, pre + (size_t)mi * (nchunks + 3), stats + mi, smem, L.a);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1051,7 +1152,8 @@ __global__ void k_pack(const double *__restrict__ w, const float *__restrict__ p
 //   level 1  super-chunk of 64 chunks: one wavefront's shuffle scan of the chunk totals;
 //   level 2  wavefront 0 scans the super-chunk totals, 64 per pass, passes chained in order.
 // offset[c] = level2[c / 64] + level1[c]; cumulative weight of particle i = offset[i / 64] + cum[i].
-// Levels 1 and 2 are a few hundred additions: every workgroup of k_resample redoes them in LDS.
+// Levels 1 and 2 are a few hundred additions: every workgroup of k_resample redoes them in LDS (chunk_offsets_scan); in the paired
+// scan step the last normalise workgroup does them once instead (resample_prefix_last) and the resample workgroups load the result.
 // ---------------------------------------------------------------------------------------------
 // one lane per output slot (SLAM.java:140-149); the chunk offsets are staged in LDS for the first search level
 __device__ __forceinline__ void
@@ -1059,17 +1161,22 @@ resample_body(const PackedParticle *__restrict__ glob_all, int64_t n_global, int
               const double *__restrict__ cum_all, const double *__restrict__ chunk_off, const double *__restrict__ r01,
               double r01_scalar, double fraction, int32_t n, int64_t offset, float *__restrict__ pose2, float *__restrict__ cs2,
               double *__restrict__ w2, int32_t *__restrict__ idx_out, const double *__restrict__ p2_all, int64_t nblk_global,
-              PfStatsDev *__restrict__ stats, uint32_t bx, uint32_t by, unsigned char *smem, bool raw_weights = false) {
+              PfStatsDev *__restrict__ stats, uint32_t bx, uint32_t by, unsigned char *smem, bool raw_weights = false,
+              const double *__restrict__ pre = nullptr) {
+    // pre != nullptr: the population's chunk offsets (grand total included), sum wn and sq_sum are ready, [nchunks + 3] per map
+    // (the last normalise workgroup of the paired step folded and scanned them: normalize_pack_body); only the search and the copy
+    // are left
     double *off = reinterpret_cast<double *>(smem);                    // [nchunks + 1]
     const int32_t mi = (int32_t)by;
     __shared__ RedLds L;
     // The chunk totals are loaded BEFORE the Neff fold decides whether the resample runs (they sit in registers meanwhile):
     // one global round trip fewer on the critical path of the paired launch.  (More than 8 * blockDim chunks: the rest in
     // the loop below.)
-    const double *tot = chunk_off + (size_t)mi * (nchunks + 1);
+    const double *tot = pre ? pre + (size_t)mi * (nchunks + 3) : chunk_off + (size_t)mi * (nchunks + 1);
+    const int64_t nload = pre ? nchunks + 1 : nchunks;                 // (the offsets come with their grand total)
     double tv[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) { const int64_t c = (int64_t)threadIdx.x + k * (int64_t)blockDim.x; tv[k] = c < nchunks ? tot[c] : 0.0; }
+    for (int k = 0; k < 8; k++) { const int64_t c = (int64_t)threadIdx.x + k * (int64_t)blockDim.x; tv[k] = c < nload ? tot[c] : 0.0; }
     // Populations of at most RES_SUB_MAX_CHUNKS chunks: the in-chunk cumulative weight at the end of every octet, eight per chunk
     // (a compact table the scan's level 0 leaves behind the chunk totals), goes to LDS as well (loaded here, beside the chunk totals: the
     // loads fly during the Neff fold).  The search below then takes
@@ -1087,61 +1194,26 @@ resample_body(const PackedParticle *__restrict__ glob_all, int64_t n_global, int
         }
     }
     double norm_sum, sq_sum;
-    fold_neff(p2_all + (size_t)mi * nblk_global * 2, nblk_global, norm_sum, sq_sum, L.a);   // calculateNeff (SLAM.java:180-190)
-    if (bx == 0 && threadIdx.x == 0) { stats[mi].norm_sum = norm_sum; stats[mi].sq_sum = sq_sum; }
+    if (pre) {
+        sq_sum = tot[nchunks + 2];                                     // (stats[mi] has it already)
+    } else {
+        fold_neff(p2_all + (size_t)mi * nblk_global * 2, nblk_global, norm_sum, sq_sum, L.a);   // calculateNeff (SLAM.java:180-190)
+        if (bx == 0 && threadIdx.x == 0) { stats[mi].norm_sum = norm_sum; stats[mi].sq_sum = sq_sum; }
+    }
     GMS_STAMP(GMS_STAMP_ROW(3, blockIdx.x), 5);                                              // (development builds) Neff folded
     const bool go = fraction < 0.0 || (1.0 / sq_sum) < fraction * (double)n_global;         // GridMapApp.java:185
-    const int64_t nsuper = (nchunks + 63) / 64;
-    double *sup = off + nchunks + 1;                                   // [nsuper + 1]
     if (go) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) { const int64_t c = (int64_t)threadIdx.x + k * (int64_t)blockDim.x; if (c < nchunks) off[c] = tv[k]; }
-        for (int64_t c0 = (int64_t)threadIdx.x + 8 * (int64_t)blockDim.x; c0 < nchunks; c0 += 8 * (int64_t)blockDim.x) {  // eight loads in flight per thread
+        for (int k = 0; k < 8; k++) { const int64_t c = (int64_t)threadIdx.x + k * (int64_t)blockDim.x; if (c < nload) off[c] = tv[k]; }
+        for (int64_t c0 = (int64_t)threadIdx.x + 8 * (int64_t)blockDim.x; c0 < nload; c0 += 8 * (int64_t)blockDim.x) {  // eight loads in flight per thread
             double v[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const int64_t c = c0 + k * (int64_t)blockDim.x; v[k] = c < nchunks ? tot[c] : 0.0; }
+            for (int k = 0; k < 8; k++) { const int64_t c = c0 + k * (int64_t)blockDim.x; v[k] = c < nload ? tot[c] : 0.0; }
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const int64_t c = c0 + k * (int64_t)blockDim.x; if (c < nchunks) off[c] = v[k]; }
+            for (int k = 0; k < 8; k++) { const int64_t c = c0 + k * (int64_t)blockDim.x; if (c < nload) off[c] = v[k]; }
         }
-        __syncthreads();
-        // level 1: one wavefront per super-chunk of 64 chunk totals, exclusive scan by shuffles (a fixed shape)
-        for (int64_t sidx = threadIdx.x >> 6; sidx < nsuper; sidx += blockDim.x >> 6) {
-            const int32_t lane = threadIdx.x & 63;
-            const int64_t c = sidx * 64 + lane;
-            const double v = c < nchunks ? off[c] : 0.0;
-            double inc = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const double up = __shfl_up(inc, o, GMS_WAVE);
-                if (lane >= o) inc += up;
-            }
-            const double excl = __shfl_up(inc, 1, GMS_WAVE);
-            if (c < nchunks) off[c] = lane == 0 ? 0.0 : excl;
-            if (lane == 63) sup[sidx] = inc;
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {                                                   // level 2: wavefront 0, 64 totals per pass
-            const int32_t lane = threadIdx.x;
-            double carry = 0.0;
-            for (int64_t s0 = 0; s0 < nsuper; s0 += 64) {
-                const int64_t sidx = s0 + lane;
-                const double v = sidx < nsuper ? sup[sidx] : 0.0;
-                double inc = v;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const double up = __shfl_up(inc, o, GMS_WAVE);
-                    if (lane >= o) inc += up;
-                }
-                const double excl = __shfl_up(inc, 1, GMS_WAVE);
-                if (sidx < nsuper) sup[sidx] = s0 == 0 ? (lane == 0 ? 0.0 : excl) : carry + (lane == 0 ? 0.0 : excl);
-                const double tot = __shfl(inc, 63, GMS_WAVE);
-                carry = s0 == 0 ? tot : carry + tot;
-            }
-            if (lane == 0) off[nchunks] = carry;                                  // grand total
-        }
-        __syncthreads();
-        for (int64_t c = 64 + threadIdx.x; c < nchunks; c += blockDim.x) off[c] = sup[c >> 6] + off[c];   // super-chunk 0 adds nothing
-        __syncthreads();
+        if (pre) __syncthreads();
+        else chunk_offsets_scan(off, nchunks);
     }
     GMS_STAMP(GMS_STAMP_ROW(3, blockIdx.x), 6);                                              // chunk offsets scanned
     const int32_t t = (int32_t)bx * blockDim.x + threadIdx.x;
@@ -1665,6 +1737,7 @@ void gms_launch_pf_apply_partials(gms_pf *pf, const double *d_partials, PackedPa
     pf->score_fresh = 0;                                              // the scoring pass has been consumed
     pf->chunks_ready = own ? 1 : 0;
     pf->neff_folded = 0;
+    pf->res_pre_ready = 0;
 }
 
 void gms_launch_pf_stats_only(gms_pf *pf, const double *d_partials, PfStatsDev *d_stats_out) {
@@ -1678,7 +1751,7 @@ void gms_launch_pf_pack(gms_pf *pf, PackedParticle *d_packed) {
     gms_map *m = pf->map;
     hipLaunchKernelGGL(k_pack, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), 0, m->stream, pf->d_w, pf->d_pose,
                        pf->n, d_packed);
-    if (d_packed == pf->d_global) { pf->chunks_ready = 0; pf->neff_folded = 0; pf->global_raw = 0; }
+    if (d_packed == pf->d_global) { pf->chunks_ready = 0; pf->neff_folded = 0; pf->global_raw = 0; pf->res_pre_ready = 0; }
 }
 
 // level 0 of the scan + {sum wn, sum wn^2} + strongest pose from d_global (paths that did not come through a
@@ -1691,6 +1764,7 @@ void gms_launch_pf_chunk_sums(gms_pf *pf) {
     hipLaunchKernelGGL(k_chunk_sums, dim3((unsigned)nblk_global_of(pf), pf->n_maps), dim3(256), 0, m->stream, pf->d_global,
                        pf->n_global, nch, pf->d_cum, pf->d_chunk_tot, pf->d_p2, nblk_global_of(pf), pf->d_stats);
     pf->chunks_ready = 1;
+    pf->res_pre_ready = 0;
 }
 
 void gms_launch_pf_fold_neff(gms_pf *pf) {
@@ -1705,6 +1779,7 @@ void gms_launch_pf_after_gather(gms_pf *pf) {
     pf->global_raw = 0;
     pf->chunks_ready = 0;
     pf->neff_folded = 0;
+    pf->res_pre_ready = 0;
     gms_launch_pf_chunk_sums(pf);          // eagerly: it also publishes the strongest particle's pose
 }
 
