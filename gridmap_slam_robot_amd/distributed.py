@@ -399,14 +399,15 @@ class SlamShardOps:
     """One rank's block of the particles WITH their maps, through the C-ABI (gms_slam_create_shard): the shard-local half of
     SLAM.update / SLAM.resample plus the weight-exchange hooks ShardedParticleFilter drives.  No CPU path."""
 
-    def __init__(self, width, height, resolution, position, n_local: int, offset: int, n_global: int, device: Optional[int] = None, max_beams: int = 0):
+    def __init__(self, width, height, resolution, position, n_local: int, offset: int, n_global: int, device: Optional[int] = None, max_beams: int = 0,
+                 kernel=None):
         import ctypes as C
         if not torch.cuda.is_available():
             raise RuntimeError("SlamShardOps needs a HIP device (there is no CPU path)")
         from .gridmap import SLAMParticleMaps
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.slam = SLAMParticleMaps.__new__(SLAMParticleMaps)
-        self.slam._init_shard(width, height, resolution, position, n_local, offset, n_global, self.device.index, max_beams)
+        self.slam._init_shard(width, height, resolution, position, n_local, offset, n_global, self.device.index, max_beams, kernel)
         self.pf = self.slam.pf
         self.n, self.offset, self.n_global = n_local, offset, n_global
         cur = torch.cuda.current_stream(self.device)

@@ -725,6 +725,15 @@ class _BorrowedFilter(_Borrowed, ParticleFilter):
         self.offset, self.n_global = 0, n
 
 
+def _put_kernel(p, kernel):
+    """the caller's blur kernel (None: gms_params_default's) into gms_params"""
+    if kernel is not None:
+        k = np.asarray(kernel, dtype=np.float64)
+        p.ktaps = k.size
+        for i, t in enumerate(k):
+            p.kernel[i] = float(t)
+
+
 class SLAMParticleMaps:
     """SLAM as the reference has it (J/slam/SLAM.java:26-204): num_particles particles, each with its own pose, weight AND
     GridMapData -- update() scores a particle against its own likelihood field and integrates the scan into its own map at its own
@@ -738,11 +747,7 @@ class SLAMParticleMaps:
         check(L.gms_params_default(C.byref(p), width, height, resolution, position[0], position[1]))   # SLAM.java:57
         p.device = device
         p.max_beams = max_beams
-        if kernel is not None:
-            k = np.asarray(kernel, dtype=np.float64)
-            p.ktaps = k.size
-            for i, t in enumerate(k):
-                p.kernel[i] = float(t)
+        _put_kernel(p, kernel)
         self.params = p
         self.num_particles = int(num_particles)                                                          # :50
         self._h = C.c_void_p()
@@ -756,13 +761,14 @@ class SLAMParticleMaps:
         self.neff = float(num_particles)
         self.sequence = 0
 
-    def _init_shard(self, width, height, resolution, position, n_local, offset, n_global, device=0, max_beams=0):
+    def _init_shard(self, width, height, resolution, position, n_local, offset, n_global, device=0, max_beams=0, kernel=None):
         """one rank's block of a sharded filter (gms_slam_create_shard): distributed.SlamShardOps"""
         L = load()
         p = GmsParams()
         check(L.gms_params_default(C.byref(p), width, height, resolution, position[0], position[1]))
         p.device = device or 0
         p.max_beams = max_beams
+        _put_kernel(p, kernel)
         self.params = p
         self.num_particles = int(n_local)
         self._h = C.c_void_p()

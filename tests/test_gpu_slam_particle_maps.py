@@ -252,28 +252,47 @@ def test_sixteen_bit_count_tiles_and_their_fallback(monkeypatch):
         dev.close()
 
 
-@pytest.mark.parametrize("lazy", ["1", "0"])
-def test_resample_copies_likelihood_data_late_or_at_once(lazy, monkeypatch):
+@pytest.mark.parametrize("lazy, held", [
+    pytest.param("1", "planes", id="1"),                    # slam_resample: lik_from_codes -- the planes travel with logData
+    pytest.param("0", "planes", id="0"),                    # (the same branch: the planes define likelihoodData either way)
+    pytest.param("1", "eager", id="eager-1"),               # lazy_lik: logData now (d_idx_lik kept), the owed copy in slam_lik_current
+    pytest.param("0", "eager", id="eager-0"),               # the last branch: k_slam_gather_maps, both arrays at once, no planes
+    pytest.param("1", "refined_from_memory", id="refined_from_memory-1"),    # lazy_lik with planes: logData + planes now, the field owed
+    pytest.param("0", "refined_from_memory", id="refined_from_memory-0"),    # the last branch: k_slam_gather_maps, then k_slam_gather_codes
+])
+def test_resample_copies_likelihood_data_late_or_at_once(lazy, held, monkeypatch):
     """resample() copies logData at once and likelihoodData when it is asked for (the next update's computeLikelihoodMap overwrites
     every cell of it first; GMS_SLAM_LAZY_LIK_COPY=0: both at once).  What a caller can see is the reference's deep copy either way:
     after one resample(), after two in a row (the second must move the first one's fields), after an upload into one slot while the
-    copies are still owed, and across an update that makes them moot."""
+    copies are still owed, and across an update that makes them moot.  likelihoodData is held as the field of the class planes
+    (planes: whatever GMS_SLAM_LAZY_LIK_COPY says, it travels with them), as an array rebuilt by every update (eager:
+    GMS_SLAM_EAGER_LIK=1, on a map of 81 x 79 cells -- an odd count, the copies' scalar forms), or as an array beside planes that the
+    last update did not evaluate it from (refined_from_memory: the pose refinement reading its field from memory)."""
     monkeypatch.setenv("GMS_SLAM_LAZY_LIK_COPY", lazy)
+    refine = held == "refined_from_memory"
+    if held == "eager":
+        monkeypatch.setenv("GMS_SLAM_EAGER_LIK", "1")
+    if refine:
+        monkeypatch.setenv("GMS_SLAM_REFINE_LDS", "0")
+    W, H = (4.05, 3.95) if held == "eager" else (4.0, 4.0)
     ext, res, B, N = 4.0, 0.05, 60, 32
     tr = synth.make_trace(ext, res, B, T=6, seed=13)
-    g = orc.Grid(ext, ext, res, -ext / 2, -ext / 2)
-    dev = SLAMParticleMaps(ext, ext, res, (-ext / 2, -ext / 2), num_particles=N, max_beams=128)
+    g = orc.Grid(W, H, res, -W / 2, -H / 2)
+    dev = SLAMParticleMaps(W, H, res, (-W / 2, -H / 2), num_particles=N, max_beams=128)
+    assert (dev.W, dev.H) == ((81, 79) if held == "eager" else (80, 80))
+    dev.set_refine(refine)
     o = orc.Slam(g, N)
     P = synth.make_particles(tr.poses[0], N, seed=9, sigma_xy=0.05, sigma_theta_deg=3.0)
     dev.set_poses(P); o.set_poses(P)
     for k in range(2):
-        dev.update(tr.scans[k], None); o.update(tr.scans[k], None, threads=THREADS)
+        dev.update(tr.scans[k], None); o.update(tr.scans[k], None, refine=refine, threads=THREADS)
+        assert np.array_equal(dev.get_particles()[0], o.poses)
     for r01 in (0.31, 0.77):                                                   # two in a row
         idx, _ = dev.resample(r01, want_indices=True)
         want, _ = o.resample(r01)
         assert np.array_equal(idx, want)
     _compare_maps(dev, o, "two resamples in a row")
-    dev.update(tr.scans[2], None); o.update(tr.scans[2], None, threads=THREADS)
+    dev.update(tr.scans[2], None); o.update(tr.scans[2], None, refine=refine, threads=THREADS)
     idx, _ = dev.resample(0.5, want_indices=True)
     want, _ = o.resample(0.5)
     assert np.array_equal(idx, want)
@@ -282,7 +301,7 @@ def test_resample_copies_likelihood_data_late_or_at_once(lazy, monkeypatch):
     liks = dev.maps(likelihood=True)
     for i in range(N):
         assert np.array_equal(liks[i].reshape(-1), field.reshape(-1) if i == 3 else o.lik(i)), f"slot {i}"
-    dev.update(tr.scans[3], None); o.update(tr.scans[3], None, threads=THREADS)      # ... and an update makes every field current
+    dev.update(tr.scans[3], None); o.update(tr.scans[3], None, refine=refine, threads=THREADS)      # ... and an update makes every field current
     _compare_maps(dev, o, "update after the resample")
     dev.close()
 
@@ -344,11 +363,15 @@ def test_the_resampling_rule_decided_on_the_device():
     dev.close()
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
-def test_random_call_sequences_against_the_oracle(seed):
+@pytest.mark.parametrize("seed, eager", [pytest.param(s, False, id=str(s)) for s in (1, 2, 3, 4, 5, 6)] +
+                         [pytest.param(s, True, id=f"eager-{s}") for s in (1, 2, 3)])
+def test_random_call_sequences_against_the_oracle(seed, eager, monkeypatch):
     """forty calls drawn at random -- update (with and without the motion sample, sometimes with a turn that skips the integration),
     resample, download of one or of all maps, upload of a log or of a field into a slot, reset, the combined map -- on the device
-    and on the oracle: the handle's state machine (which generation is current, which copies are owed) against the plain loop."""
+    and on the oracle: the handle's state machine (which generation is current, which copies are owed) against the plain loop.
+    eager: a handle without class planes (GMS_SLAM_EAGER_LIK=1), whose likelihoodData is always an array of its own."""
+    if eager:
+        monkeypatch.setenv("GMS_SLAM_EAGER_LIK", "1")
     rng = np.random.default_rng(seed)
     ext, res, B, N = 3.2, 0.05, 48, 12
     tr = synth.make_trace(ext, res, B, T=8, seed=50 + seed)
