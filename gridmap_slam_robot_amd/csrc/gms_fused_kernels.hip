@@ -208,7 +208,6 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
                              const gms_beam *d_beams, int32_t B) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_RAYCAST);
-    if (own) { pf->d_global = pf->d_global_own; pf->global_raw = 0; }     // normalised weights are packed (as apply_partials does)
     const uint32_t n_near = rc_near_blocks(m, B);
     const uint32_t n_ray = (uint32_t)((B + RCF_RAYS - 1) / RCF_RAYS) + n_near, n_norm = (uint32_t)((pf->n + 255) / 256);
     // own population: the last normalise workgroup also folds Neff and scans the chunk offsets (resample_prefix_last) in LDS
@@ -239,11 +238,8 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
     } while (0)
     if (lognorm) NR_LAUNCH(true); else NR_LAUNCH(false);
 #undef NR_LAUNCH
-    pf->score_fresh = 0;                                              // the scoring pass has been consumed
     if (n_apply) gms_apply_done(m);
-    pf->chunks_ready = own ? 1 : 0;
-    pf->neff_folded = own ? 1 : 0;                                    // (resample_prefix_last wrote stats.norm_sum / sq_sum)
-    pf->res_pre_ready = own ? 1 : 0;
+    pf_normalized(pf, own, own);                                      // (resample_prefix_last wrote stats.norm_sum / sq_sum)
 }
 
 // block partials (SLAM.java:100-115) beside the apply pass the previous paired step left pending
@@ -261,7 +257,7 @@ void gms_launch_partials_apply(gms_pf *pf, double *d_partials, bool apply_rides_
                        pf->d_pose, pf->n, pf->offset, nblk, d_partials,
                        pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->pending_nseg, m->gd, m->d_log,
                        m->d_cnt_pend, cur, idle, lognorm_stats);
-    pf->pending_nseg = 0;
+    pf_weights_combined(pf);
     gms_apply_done(m);
 }
 
@@ -271,7 +267,6 @@ void gms_launch_lik_resample(gms_pf *pf, double fraction) {
     gms_launch_pf_chunk_sums(pf);                     // no-op when level 0 is already there
     // the chunk offsets and Neff folded by the paired normalise (gms_launch_norm_raycast), or the resample workgroups fold them
     const double *pre = pf->res_pre_ready ? (const double *)pf->d_res_pre : (const double *)nullptr;
-    pf->res_pre_ready = 0;
     ProfScope ps(m, GMS_K_LIKELIHOOD);
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
@@ -287,9 +282,8 @@ void gms_launch_lik_resample(gms_pf *pf, double fraction) {
     const int32_t *bb = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4;
     const double *r01_maps = pf->n_maps == 1 ? (const double *)nullptr : pf->d_r01_src;
     int32_t lik_mode = m->lik_lazy ? 2 : 3;                   // the factor table only: likelihoodData follows on demand (gms_ensure_lik)
-    if (m->lik_lazy) m->lik_stale = 1;
     if (m->fac_current && m->lik_skip) lik_mode |= 4;         // tiles whose codes this scan does not change are left alone (likelihood_body)
-    m->fac_current = 1;
+    map_field_built(m, lik_mode);
     const bool split = k != 0 && gms_likelihood_split(m, blocks);              // (likelihood_body, "split")
 #define LR_LAUNCH(KH, SP)                                                                                                 \
     do {                                                                                                                  \
@@ -306,7 +300,7 @@ void gms_launch_lik_resample(gms_pf *pf, double fraction) {
     else if (k == 5) { if (split) LR_LAUNCH(5, 2); else LR_LAUNCH(5, 1); }
     else LR_LAUNCH(0, 1);
 #undef LR_LAUNCH
-    pf->neff_folded = 1;
+    pf_prefix_consumed(pf);
 }
 
 // ---- sharded filters, one all-gather per scan ----------------------------------------------------------------------
@@ -326,8 +320,7 @@ void gms_launch_partials_pack_apply(gms_pf *pf, bool apply_rides_later) {
                        pf->n, pf->offset, nblk_global_of(pf), pf->d_partials,
                        pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->pending_nseg,
                        pf->d_global_own + pf->offset, n_local, m->gd, m->d_log, m->d_cnt_pend, cur, idle);
-    pf->pending_nseg = 0;
-    pf->score_fresh = 0;               // the scoring pass has been consumed (raw weights packed for the exchange)
+    pf_raw_packed(pf);
     if (n_apply) gms_apply_done(m);
 }
 
@@ -335,8 +328,6 @@ void gms_launch_partials_pack_apply(gms_pf *pf, bool apply_rides_later) {
 void gms_launch_raycast_norm_chunks(gms_pf *pf, const gms_beam *d_beams, int32_t B, bool raycast) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_RAYCAST);
-    pf->d_global = pf->d_global_own;
-    pf->global_raw = 1;
     const uint32_t n_near = raycast ? rc_near_blocks(m, B) : 0u;
     const uint32_t n_ray = raycast ? (uint32_t)((B + RCF_RAYS - 1) / RCF_RAYS) + n_near : 0u, n_norm = (uint32_t)((pf->n + 255) / 256);
     const uint32_t n_chunk = (uint32_t)nblk_global_of(pf);
@@ -357,9 +348,7 @@ void gms_launch_raycast_norm_chunks(gms_pf *pf, const gms_beam *d_beams, int32_t
                        pf->offset, pf->d_global_own, pf->n_global, nchunks_of(pf), pf->d_cum, pf->d_chunk_tot, pf->d_p2, pf->d_stats,
                        n_chunk, m->d_log, m->d_cnt_pend, pend, n_near);
     if (n_apply) gms_apply_done(m);
-    pf->chunks_ready = 1;
-    pf->neff_folded = 0;
-    pf->res_pre_ready = 0;                            // (sharded: the resample workgroups fold Neff and scan the offsets themselves)
+    pf_normalized_gathered(pf);                       // (sharded: the resample workgroups fold Neff and scan the offsets themselves)
 }
 
 // de-skew of one raw scan beside the motion-model sample of a single-map filter's particles

@@ -368,7 +368,7 @@ int gms_map_create(const gms_params *p, gms_map **out) {
     hipMemsetAsync(m->d_tile_stats, 0, 64 * 4 * sizeof(uint32_t), m->stream);
     gms_launch_factors(m);        // likelihoodData == 0 everywhere (createMapData(null))
     HIPCHK(hipStreamSynchronize(m->stream));
-    m->need_full_build = 1; m->fac_current = 0;
+    map_log_replaced(m);
     m->pair_launches = 1;
     {   // the tiled batched ray cast: 8 KiB of slots + a 64 KiB tile + static LDS
         int lds_max = 0;
@@ -385,7 +385,6 @@ int gms_map_create(const gms_params *p, gms_map **out) {
     if (const char *v = getenv("GMS_LIK_LAZY")) m->lik_lazy = atoi(v) != 0;
     m->lik_skip = 1;
     if (const char *v = getenv("GMS_LIK_SKIP")) m->lik_skip = atoi(v) != 0;
-    m->fac_current = 0;
     if (const char *v = getenv("GMS_PAIR_LAUNCHES")) m->pair_launches = atoi(v) != 0;
     if (const char *v = getenv("GMS_SLAM_TILE_CELLS")) m->slam_tile_cells = atoi(v);
     m->lik_split = 1;
@@ -429,10 +428,9 @@ int gms_map_synchronize(gms_map *m) {
 int gms_map_reset(gms_map *m) {                                        // GridMap.java:129-132
     REQUIRE(m, "null map");
     HIPCHK(hipSetDevice(m->device));
-    gms_ensure_lik(m);                 // likelihoodData keeps the last field (reset touches logData only)
-    gms_flush_apply(m);
+    gms_map_settle(m);                 // likelihoodData keeps the last field (reset touches logData only)
     HIPCHK(hipMemsetAsync(m->d_log, 0, (size_t)m->gd.cells * m->n_maps * sizeof(double), m->stream));
-    m->need_full_build = 1; m->fac_current = 0;
+    map_log_replaced(m);
     return GMS_OK;
 }
 
@@ -447,9 +445,8 @@ static int map_xfer(gms_map *m, void *dev, void *host, bool to_device) {
 
 int gms_map_upload_log(gms_map *m, const double *log_data) {
     REQUIRE(m && log_data, "null argument");
-    gms_ensure_lik(m);
-    gms_flush_apply(m);
-    m->need_full_build = 1; m->fac_current = 0;
+    gms_map_settle(m);
+    map_log_replaced(m);
     return map_xfer(m, m->d_log, const_cast<double *>(log_data), true);
 }
 int gms_map_download_log(gms_map *m, double *log_data) {
@@ -459,8 +456,8 @@ int gms_map_download_log(gms_map *m, double *log_data) {
 }
 int gms_map_upload_likelihood(gms_map *m, const double *lik) {
     REQUIRE(m && lik, "null argument");
-    m->need_full_build = 1; m->fac_current = 0;
-    m->lik_stale = 0;                  // replaced wholesale
+    map_log_replaced(m);
+    map_lik_current(m);                // replaced wholesale
     int rc = map_xfer(m, m->d_lik, const_cast<double *>(lik), true);
     if (rc) return rc;
     gms_launch_factors(m);
@@ -491,10 +488,9 @@ int gms_map_copy(gms_map *dst, const gms_map *src) {                  // GridMap
     REQUIRE(dst->device == src->device, "gms_map_copy: both handles must live on the same device (the copies and their stream hand-over are device-local)");
     const size_t bytes = (size_t)src->gd.cells * src->n_maps * sizeof(double);
     HIPCHK(hipSetDevice(dst->device));
-    gms_ensure_lik(const_cast<gms_map *>(src));
-    gms_flush_apply(const_cast<gms_map *>(src));
+    gms_map_settle(const_cast<gms_map *>(src));
     gms_flush_apply(dst);
-    dst->lik_stale = 0;
+    map_lik_current(dst);
     // The copies run on dst's stream and read src's arrays: dst's stream waits for what src's stream holds so far (the flushed
     // apply pass among it), and src's stream waits for the copies before anything enqueued on it later may write those arrays
     // again (a ray cast's apply pass, reset, upload): both directions in stream order, no host synchronise.
@@ -505,7 +501,7 @@ int gms_map_copy(gms_map *dst, const gms_map *src) {                  // GridMap
     rc = stream_after(src->stream, dst->stream, "gms_map_copy");
     if (rc) return rc;
     gms_launch_factors(dst);
-    dst->need_full_build = 1; dst->fac_current = 0;
+    map_log_replaced(dst);
     return GMS_OK;
 }
 
@@ -528,7 +524,7 @@ int gms_map_combine(gms_map *dst, gms_map *src) {                        // Grid
     gms_launch_combine(src, dst);
     rc = stream_after(src->stream, dst->stream, "gms_map_combine");
     if (rc) return rc;
-    dst->need_full_build = 1; dst->fac_current = 0;
+    map_log_replaced(dst);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -594,8 +590,7 @@ int gms_map_get_at_point(gms_map *m, int32_t mi, float point_x, float point_y, d
     if (idx < 0 || (int64_t)idx >= m->gd.cells)
         return fail(GMS_ERR_INVALID, "gms_map_get_at_point: index %d out of bounds (Java: ArrayIndexOutOfBoundsException)", idx);
     HIPCHK(hipSetDevice(m->device));
-    gms_ensure_lik(m);
-    gms_flush_apply(m);
+    gms_map_settle(m);
     double *h = reinterpret_cast<double *>(m->h_poses + (size_t)m->n_maps * 3);
     h = reinterpret_cast<double *>(((uintptr_t)h + 7) & ~(uintptr_t)7);
     const size_t o = (size_t)mi * m->gd.cells + idx;
@@ -649,11 +644,6 @@ static const float *stats_pose_ptr(const gms_pf *pf, int32_t which) {
 static int finish_likelihood(gms_map *m, int32_t dirty_only) {
     if (dirty_only && !m->bbox_dirty) return GMS_OK;     // nothing changed since the last build
     gms_launch_likelihood(m, dirty_only);
-    if (m->bbox_dirty) {          // the box is consumed; the other half was cleared by k_apply
-        m->bbox_cur = 1 - m->bbox_cur;
-        m->bbox_dirty = 0;
-    }
-    m->need_full_build = 0;
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -890,7 +880,7 @@ static void pf_free_global(gms_pf *pf) {
     hipFree(pf->d_partials); hipFree(pf->d_p2); hipFree(pf->d_global_own); hipFree(pf->d_chunk_tot); hipFree(pf->d_cum);
     hipFree(pf->d_res_pre); hipFree(pf->d_res_ticket);
     pf->d_partials = pf->d_p2 = nullptr; pf->d_global = pf->d_global_own = nullptr; pf->d_chunk_tot = pf->d_cum = nullptr;
-    pf->d_res_pre = nullptr; pf->d_res_ticket = nullptr; pf->res_pre_ready = 0;
+    pf->d_res_pre = nullptr; pf->d_res_ticket = nullptr; pf->res_pre_ready = 0; pf->have_global = 0;
 }
 
 static int pf_alloc_global(gms_pf *pf) {
@@ -977,7 +967,6 @@ int gms_pf_set_shard(gms_pf *pf, int64_t offset, int64_t n_global) {
     HIPCHK(hipStreamSynchronize(pf->map->stream));
     pf->offset = offset;
     pf->n_global = n_global;
-    pf->have_global = 0;
     if (offset != 0 || n_global != pf->n) { pf->log_norm = 0; pf->reference_order = 0; }      // (stand-alone filters only)
     return pf_alloc_global(pf);
 }
@@ -1001,8 +990,7 @@ int gms_pf_set_poses(gms_pf *pf, const float *xytheta) {
     HIPCHK(hipSetDevice(m->device));
     int rc = upload_poses(pf, xytheta);
     if (rc) return rc;
-    pf->have_global = 0;
-    pf->stats_current = 0;
+    pf_particles_changed(pf);
     return GMS_OK;
 }
 
@@ -1029,10 +1017,7 @@ static int pf_copy_f64(gms_pf *pf, double *dev, double *host, bool to_device) {
 
 int gms_pf_set_weights(gms_pf *pf, const double *w) {
     REQUIRE(pf && w, "null argument");
-    pf->pending_nseg = 0;
-    pf->have_global = 0;
-    pf->stats_current = 0;
-    pf->score_fresh = 0;                // d_w no longer belongs to d_logw: a log-normalising filter takes these weights as they are
+    pf_weights_set(pf);                 // a log-normalising filter takes these weights as they are
     return pf_copy_f64(pf, pf->d_w, const_cast<double *>(w), true);
 }
 int gms_pf_get_weights(gms_pf *pf, double *w) {
@@ -1054,8 +1039,6 @@ int gms_pf_score(gms_pf *pf, const gms_beam *beams, int32_t B) {       // GridMa
     int rc = stage_beams(m, beams, B);
     if (rc) return rc;
     gms_launch_pf_score(pf, m->d_beams, B, m->max_beams);
-    pf->have_global = 0;
-    pf->stats_current = 0;
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1076,8 +1059,6 @@ static int set_poses_and_score_dev(gms_pf *pf, const float *dev_xytheta, const g
         motion = nullptr;
     }
     gms_launch_pf_score(pf, dev_beams, B, B, dev_xytheta, motion);                // (a motion-model sample rides in the scoring launch)
-    pf->have_global = 0;
-    pf->stats_current = 0;
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1090,8 +1071,7 @@ int gms_pf_set_poses_dev(gms_pf *pf, const float *dev_xytheta) {
     REQUIRE(pf && dev_xytheta, "null argument");
     HIPCHK(hipSetDevice(pf->map->device));
     gms_launch_pf_pose_trig(pf, dev_xytheta);          // copy + the per-particle trig, one launch
-    pf->have_global = 0;
-    pf->stats_current = 0;
+    pf_particles_changed(pf);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1132,18 +1112,13 @@ int gms_pf_normalize(gms_pf *pf, gms_pf_stats *stats) {                 // SLAM.
     if (pf->reference_order) {                         // the audit path: one lane, the reference's own loops
         gms_launch_pf_combine(pf);
         gms_launch_pf_normalize_seq(pf, pf->d_stats, true);
-        pf->have_global = 0;
-        pf->stats_current = 1;
-        pf->score_fresh = 0;
+        pf_normalized_in_place(pf);
         HIPCHK(hipGetLastError());
         if (stats) { int rc_ = pull_stats(pf); if (rc_) return rc_; fill_stats(pf, stats); }
         return GMS_OK;
     }
-    pf->d_global = pf->d_global_own;
     gms_launch_pf_partials(pf, pf->d_partials);
-    gms_launch_pf_apply_partials(pf, pf->d_partials, pf->d_global, true);
-    pf->have_global = 1;
-    pf->stats_current = 1;
+    gms_launch_pf_apply_partials(pf, pf->d_partials, pf->d_global_own, true);
     HIPCHK(hipGetLastError());
     if (stats) return gms_pf_get_stats(pf, stats);
     return GMS_OK;
@@ -1167,8 +1142,6 @@ int gms_pf_apply_partials(gms_pf *pf, const double *dev_partials, void *dev_pack
     REQUIRE(pf && dev_partials && dev_packed, "null argument");
     HIPCHK(hipSetDevice(pf->map->device));
     gms_launch_pf_apply_partials(pf, dev_partials, reinterpret_cast<PackedParticle *>(dev_packed), false);
-    pf->have_global = 0;
-    pf->stats_current = 1;
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1177,7 +1150,7 @@ int gms_pf_stats_from_partials(gms_pf *pf, const double *dev_partials) {
     REQUIRE(pf && dev_partials, "null argument");
     HIPCHK(hipSetDevice(pf->map->device));
     gms_launch_pf_stats_only(pf, dev_partials, pf->d_stats + pf->n_maps);
-    pf->stats_current = 2;        // current-particle statistics live in the second slot
+    pf_stats_recomputed(pf);      // current-particle statistics live in the second slot
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1196,9 +1169,8 @@ int gms_pf_import_global(gms_pf *pf, const void *dev_packed_global) {
     gms_map *m = pf->map;
     HIPCHK(hipSetDevice(m->device));
     // zero copy: the gathered buffer becomes the resampling source as it is (see the header for its lifetime)
-    pf->d_global = const_cast<PackedParticle *>(reinterpret_cast<const PackedParticle *>(dev_packed_global));
-    gms_launch_pf_after_gather(pf);
-    pf->have_global = 1;
+    pf_source_replaced(pf, const_cast<PackedParticle *>(reinterpret_cast<const PackedParticle *>(dev_packed_global)), 0);
+    gms_launch_pf_chunk_sums(pf);      // eagerly: it also publishes the strongest particle's pose
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1208,10 +1180,9 @@ static int ensure_global(gms_pf *pf) {
     if (pf->have_global) return GMS_OK;
     if (pf->offset != 0 || pf->n_global != pf->n)
         return fail(GMS_ERR_STATE, "sharded filter: all-gather the packed particles and call gms_pf_import_global first");
-    pf->d_global = pf->d_global_own;
     gms_launch_pf_combine(pf);
-    gms_launch_pf_pack(pf, pf->d_global);
-    pf->have_global = 1;
+    gms_launch_pf_pack(pf, pf->d_global_own);
+    pf_source_replaced(pf, pf->d_global_own, 0);
     return GMS_OK;
 }
 
@@ -1231,7 +1202,7 @@ int gms_pf_weighted_pose(gms_pf *pf, float *out) {                      // SLAM.
             gms_launch_pf_partials(pf, pf->d_partials);
             gms_launch_pf_stats_only(pf, pf->d_partials, pf->d_stats + pf->n_maps);
         }
-        pf->stats_current = 2;
+        pf_stats_recomputed(pf);
     }
     const PfStatsDev *src = pf->d_stats + (pf->stats_current == 2 ? pf->n_maps : 0);
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -1281,9 +1252,7 @@ static int do_resample(gms_pf *pf, const double *r01, double fraction, int32_t *
     rc = commit_r01(pf);
     if (rc) return rc;
     std::swap(pf->d_pose, pf->d_pose2); std::swap(pf->d_cs, pf->d_cs2); std::swap(pf->d_w, pf->d_w2);
-    pf->have_global = 0;
-    pf->stats_current = 0;
-    pf->score_fresh = 0;                // the copies' weights are not the log-weights' (d_logw is not permuted): never rescale them from those
+    pf_resampled(pf);                   // never rescale the copies' weights from the log-weights
     HIPCHK(hipGetLastError());
     if (indices) {
         HIPCHK(hipMemcpyAsync(indices, pf->d_idx, (size_t)pf->n * pf->n_maps * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
@@ -1318,9 +1287,7 @@ static int paired_likelihood_resample(gms_pf *pf, const double *r01, double frac
         rc = commit_r01(pf);
         if (rc) return rc;
         std::swap(pf->d_pose, pf->d_pose2); std::swap(pf->d_cs, pf->d_cs2); std::swap(pf->d_w, pf->d_w2);
-        pf->have_global = 0;
-        pf->stats_current = 0;
-        pf->score_fresh = 0;
+        pf_resampled(pf);
         gms_defer_apply(m);
     } else {                                // no resample to pair with: the immediate protocol
         gms_launch_apply_counts(m);
@@ -1364,22 +1331,16 @@ static int slam_update_impl(gms_pf *pf, const float *dev_xytheta, const MotionMo
     if (!rc && integrate && !pf->reference_order && gms_can_pair_launches(pf, B)) {
         // The weight branch and the map branch are independent once the partials exist: they share launches
         // (gms_fused_kernels.hip).  (Two streams were measured: the event fork/join costs more than it hides.)
-        pf->d_global = pf->d_global_own;
         gms_launch_partials_apply(pf, pf->d_partials, true);                              // :100-115
-        gms_launch_norm_raycast(pf, pf->d_partials, pf->d_global, true, dev_beams, B);    // :120-124 | :93 | previous scan's :223
-        pf->have_global = 1;
-        pf->stats_current = 1;
+        gms_launch_norm_raycast(pf, pf->d_partials, pf->d_global_own, true, dev_beams, B);   // :120-124 | :93 | previous scan's :223
         return paired_likelihood_resample(pf, r01, resample_fraction);           // :105 | GridMapApp.java:185-186
     }
     if (!rc && integrate && !pf->reference_order && pf->n_maps > 1 && B > 0 && !m->need_full_build && m->pair_launches) {
         // batched maps: the ray cast runs 16 rays per workgroup (1024 threads), so only the other two pairs apply:
         // [partials | previous apply] -> normalise -> ray cast -> [likelihood | resample]
-        pf->d_global = pf->d_global_own;
         const bool ride = gms_raycast_tiled(m, B);     // the tiled ray cast takes the pending apply pass along
         gms_launch_partials_apply(pf, pf->d_partials, ride);
-        gms_launch_pf_apply_partials(pf, pf->d_partials, pf->d_global, true);
-        pf->have_global = 1;
-        pf->stats_current = 1;
+        gms_launch_pf_apply_partials(pf, pf->d_partials, pf->d_global_own, true);
         gms_launch_raycast(m, dev_beams, B, B, stats_pose_ptr(pf, 0), (int32_t)(sizeof(PfStatsDev) / sizeof(float)), ride);
         return paired_likelihood_resample(pf, r01, resample_fraction);
     }
@@ -1412,8 +1373,7 @@ int gms_slam_frame(gms_pf *pf, const double *angle, const double *distance, cons
     gms_launch_deskew_motion(pf, h_a, h_d, h_h, length, d_center, d_theta, seed, sequence);
     rc = ring_commit(m->beam_ring, m->stream);
     if (rc) return rc;
-    pf->have_global = 0;
-    pf->stats_current = 0;
+    pf_particles_changed(pf);
     HIPCHK(hipGetLastError());
     return gms_slam_update_dev(pf, nullptr, m->d_beams, length, r01, resample_fraction, integrate);
 }
@@ -1435,7 +1395,6 @@ int gms_slam_update(gms_pf *pf, const float *xytheta, const gms_beam *beams, int
         // staging-stride launchers instead
         if (pf->refine) gms_launch_pf_refine(pf, m->d_beams, B, m->max_beams);
         gms_launch_pf_score(pf, m->d_beams, B, m->max_beams);
-        pf->have_global = 0; pf->stats_current = 0;
         rc = gms_pf_normalize(pf, nullptr);
         if (!rc && resample_fraction >= 0.0) rc = gms_pf_resample_if(pf, r01, resample_fraction);
         if (!rc && integrate) {
@@ -1455,8 +1414,7 @@ int gms_pf_sample_motion(gms_pf *pf, double d_center, double d_theta, uint64_t s
     REQUIRE(pf, "null filter");
     HIPCHK(hipSetDevice(pf->map->device));
     gms_launch_pf_motion(pf, d_center, d_theta, seed, sequence);
-    pf->have_global = 0;
-    pf->stats_current = 0;
+    pf_particles_changed(pf);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1502,8 +1460,7 @@ int gms_pf_set_reference_order(gms_pf *pf, int32_t on) {
         return fail(GMS_ERR_STATE, "gms_pf_set_reference_order: stand-alone filters only (the audit path adds up on ONE lane of ONE device)");
     if (on && pf->log_norm) return fail(GMS_ERR_STATE, "gms_pf_set_reference_order: log-normalisation is on (not the reference's arithmetic): turn it off first");
     pf->reference_order = on ? 1 : 0;
-    pf->have_global = 0;
-    pf->stats_current = 0;
+    pf_particles_changed(pf);
     return GMS_OK;
 }
 
@@ -1536,8 +1493,7 @@ int gms_pf_refine_poses(gms_pf *pf, const gms_beam *beams, int32_t B) {   // Gri
     int rc = stage_beams(m, beams, B);
     if (rc) return rc;
     gms_launch_pf_refine(pf, m->d_beams, B, m->max_beams);
-    pf->have_global = 0;
-    pf->stats_current = 0;
+    pf_particles_changed(pf);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1679,8 +1635,6 @@ int gms_pf_normalize_sharded_begin(gms_pf *pf, gms_comm *c) {
     RCCLCHK(g_rccl.AllReduce(pf->d_partials, pf->d_partials, np, RCCL_FLOAT64, RCCL_SUM, c->nccl, m->stream));
     PackedParticle *own_slot = pf->d_global_own + pf->offset;
     gms_launch_pf_apply_partials(pf, pf->d_partials, own_slot, false);
-    pf->have_global = 0;
-    pf->stats_current = 1;
     hipStream_t s = m->stream;
     if (c->overlap) {                                   // the gather proceeds beside whatever the caller enqueues next
         HIPCHK(hipEventRecord(c->ev_fork, m->stream));
@@ -1702,9 +1656,8 @@ int gms_pf_normalize_sharded_end(gms_pf *pf, gms_comm *c) {
     HIPCHK(hipSetDevice(m->device));
     if (c->overlap) HIPCHK(hipStreamWaitEvent(m->stream, c->ev_join, 0));
     c->pending = 0;
-    pf->d_global = pf->d_global_own;
-    gms_launch_pf_after_gather(pf);
-    pf->have_global = 1;
+    pf_source_replaced(pf, pf->d_global_own, 0);
+    gms_launch_pf_chunk_sums(pf);      // eagerly: it also publishes the strongest particle's pose
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -1764,8 +1717,6 @@ int gms_slam_update_sharded_end_dev(gms_pf *pf, const gms_beam *dev_beams, int32
     HIPCHK(hipSetDevice(m->device));
     const bool pair = integrate && gms_can_pair_launches(pf, B);
     gms_launch_raycast_norm_chunks(pf, dev_beams, B, pair);                      // :93 | :120-124 | level 0 of :140-149
-    pf->have_global = 1;
-    pf->stats_current = 1;
     HIPCHK(hipGetLastError());
     if (pair) return paired_likelihood_resample(pf, r01, resample_fraction);     // :105 | GridMapApp.java:185-186
     if (integrate) rc = gms_map_update_at_dev(m, dev_beams, B, pf, 0);

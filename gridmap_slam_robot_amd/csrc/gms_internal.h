@@ -149,6 +149,39 @@ struct gms_map {
     int64_t prof_n[GMS_K_COUNT];
 };
 
+// ---- map state transitions (need_full_build, fac_current, lik_stale, apply_pending, bbox_dirty, bbox_cur): each is named for
+// what happened and sets every field that event affects ----
+// logData (or, gms_map_upload_likelihood, the field) was replaced: the next rebuild covers every tile and leaves none alone
+static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; }
+// likelihoodData is up to date everywhere (made so, or about to be replaced wholesale)
+static inline void map_lik_current(gms_map *m) { m->lik_stale = 0; }
+// an immediate apply pass added the counts to logData without a rebuild having seen them
+static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; }
+// a deferred apply pass has been enqueued: the box of the scan it applied is the current half now
+static inline void gms_apply_done(gms_map *m) {
+    m->bbox_cur = 1 - m->bbox_cur;
+    m->bbox_dirty = 0;
+    m->apply_pending = 0;
+}
+// the scan just cast (and already in the likelihood field) keeps its counts for a later launch
+static inline void gms_defer_apply(gms_map *m) {
+    uint32_t *t = m->d_cnt; m->d_cnt = m->d_cnt_pend; m->d_cnt_pend = t;       // the other grid is all zero: the next ray cast's
+    m->apply_pending = 1;
+    m->bbox_dirty = 0;
+}
+// a likelihood rebuild of `mode` (likelihood_body) has been enqueued: 1 likelihoodData from what the factor table's last rebuild saw;
+// 2 the factor table only, 3 both, from logData + the pending counts
+static inline void map_field_built(gms_map *m, int32_t mode) {
+    if ((mode & 3) == 1) { map_lik_current(m); return; }
+    m->lik_stale = (mode & 3) == 2;
+    m->fac_current = 1;
+    m->need_full_build = 0;
+}
+// an immediate rebuild has read the box of the cells changed since the last one; k_apply cleared the other half
+static inline void map_box_consumed(gms_map *m) {
+    if (m->bbox_dirty) { m->bbox_cur = 1 - m->bbox_cur; m->bbox_dirty = 0; }
+}
+
 struct gms_pf {
     gms_map *map;
     int32_t n;            // particles held here (per map)
@@ -166,17 +199,12 @@ struct gms_pf {
     int32_t *d_nhit;                // [n_maps]
     double *d_partials;             // [n_maps][nblk_global][GMS_PARTIAL_STRIDE]
     double *d_p2;                   // [n_maps][nblk_global][2] {sum wn, sum wn^2} of the normalised global population
-    int32_t neff_folded;            // stats.sq_sum has been folded from d_p2 (d_p2 is produced with the chunk sums)
-    int32_t global_raw;             // d_global holds RAW weights (gathered before the normalisation): resample divides
     PackedParticle *d_global_own;   // the library's own buffer; d_global may alias a caller's all-gather result
-    PackedParticle *d_global;       // [n_maps][n_global] source population (own copy when unsharded)
     double *d_chunk_tot;            // [n_maps][nchunks] scan chunk totals / offsets
     double *d_cum;                  // [n_maps][n_global] in-chunk inclusive sums
     double *d_res_pre;              // [n_maps][nchunks + 3] chunk offsets + grand total, sum wn, sq_sum: folded by the paired step's normalise (resample_prefix_last)
     uint32_t *d_res_ticket;         // [n_maps] its ticket counter (0 between launches)
-    int32_t res_pre_ready;          // d_res_pre describes d_global's current level 0 (set by gms_launch_norm_raycast, consumed by gms_launch_lik_resample)
     PfStatsDev *d_stats;            // [2][n_maps]: [0] of the last normalise, [1] of the current particles (recomputed on demand)
-    int32_t stats_current;          // d_stats[0] still describes the current particles
     PfStatsDev *h_stats;            // pinned
     double *d_r01;                  // [n_maps] (unused since the kernels read the pinned ring slot; kept for the allocation's alignment slack)
     const double *d_r01_src;        // [n_maps] where the resample kernel reads the draws: the current pinned ring slot (batched maps)
@@ -185,14 +213,10 @@ struct gms_pf {
     float *h_stage;                 // pinned staging for poses (read-back)
     StageRing pose_ring;            // pinned staging of pose proposals handed over as host buffers
     StageRing r01_ring;             // pinned staging of the per-map resampling draws (n_maps > 1)
-    int32_t have_global;            // d_global holds the current normalised population
-    int32_t chunks_ready;           // d_cum / d_chunk_tot hold level 0 of the scan of d_global
     int32_t refine;                 // scan steps run findBestPose on every particle before weighting (gms_pf_set_refine)
-    int32_t pending_nseg;           // > 0: d_w is stale, the weights are still d_part's segment products
     float4 *d_ord;                  // [n_maps][n] {x, y, cos, sin} of the particles in locality order (k_order)
     int32_t *d_perm;                // [n_maps][n] the particle at each position of that order
     int32_t log_norm;               // gms_pf_set_log_normalize: weights = exp(logw - max logw) instead of the plain product (stand-alone filters)
-    int32_t score_fresh;            // d_w / d_logw (or the segment products) come from a scoring pass nothing has consumed yet
     int32_t score_threads;          // 0 the launcher decides (the largest of 1024 / 512 / 256 lanes per scoring workgroup that still gives every CU one); GMS_SCORE_THREADS forces 64..1024
     int32_t reference_order;        // gms_pf_set_reference_order: the audit path -- every re-associated chain (the scan's product, weightSum, the
                                     // cumulative weights) as ONE chain in the reference's order (tests; slow)
@@ -200,7 +224,76 @@ struct gms_pf {
     int32_t order_mode;             // -1 the launcher decides (large launches only), 0 never, 1 always (GMS_SCORE_ORDER; results do not depend on it)
     int32_t slam_owned;             // the filter of a gms_slam: its particles own maps, so resampling, sharding and the shared-map scan steps are refused on it
     int32_t *d_epoch2;              // the filter of a gms_slam, during gms_slam_resample_maps[_if]: {draws that ran so far, the last resample() drew}, kept by the resampling kernels (NULL otherwise)
+    // What the derived device data describes.  Written by the pf_* transitions below only (and pf_alloc_global / pf_free_global).
+    // weights:
+    int32_t pending_nseg;           // > 0: d_w / d_logw are stale, the weights are still d_part's pending_nseg segment products
+    int32_t score_fresh;            // d_w / d_logw (or the segment products) come from a scoring pass nothing has consumed yet: only those
+                                    // may be log-normalised (gms_pf_lognorm_now); weights the caller set or a resample copied are taken as they are
+    // statistics:
+    int32_t stats_current;          // the d_stats slot that describes the current particles: 0 none, 1 d_stats[0] (a normalise), 2 d_stats[1] (recomputed)
+    int32_t neff_folded;            // d_stats[0].norm_sum / sq_sum have been folded from d_p2 (d_p2 is produced with the chunk sums)
+    // resampling source:
+    PackedParticle *d_global;       // [n_maps][n_global] source population: d_global_own, or a caller's all-gather result (gms_pf_import_global)
+    int32_t have_global;            // d_global holds the current population
+    int32_t global_raw;             // ... with RAW weights (gathered before the normalisation): resample divides
+    int32_t chunks_ready;           // d_cum / d_chunk_tot hold level 0 of the scan of d_global
+    int32_t res_pre_ready;          // d_res_pre holds that level 0's chunk offsets, grand total, sum wn and sq_sum (folded by the paired normalise)
 };
+
+// ---- filter state transitions: each is named for what happened and sets every field that event affects ----
+// the poses changed (host, motion model, refinement) or how they are weighed did: the source and the statistics are stale
+static inline void pf_particles_changed(gms_pf *pf) { pf->have_global = 0; pf->stats_current = 0; }
+// a scoring launch wrote new weights: nseg > 1 segment products per particle, or the combined product (nseg <= 1)
+static inline void pf_scored(gms_pf *pf, int64_t nseg) {
+    pf_particles_changed(pf);
+    pf->pending_nseg = nseg > 1 ? (int32_t)nseg : 0;
+    pf->score_fresh = 1;
+}
+// a resample replaced the particles by copies: their weights are not the log-weights' (d_logw is not permuted)
+static inline void pf_resampled(gms_pf *pf) { pf_particles_changed(pf); pf->score_fresh = 0; }
+// the host set the weights (or reset the particles): d_w no longer belongs to d_logw
+static inline void pf_weights_set(gms_pf *pf) { pf_particles_changed(pf); pf->pending_nseg = 0; pf->score_fresh = 0; }
+// a launch stored the combined weights in d_w / d_logw
+static inline void pf_weights_combined(gms_pf *pf) { pf->pending_nseg = 0; }
+// the raw weights were combined and packed for an exchange: the scoring pass has been consumed
+static inline void pf_raw_packed(gms_pf *pf) { pf->pending_nseg = 0; pf->score_fresh = 0; }
+// the weights were normalised (the scoring pass consumed) and d_stats[0] describes the particles.  own: the population was packed into
+// d_global_own with level 0 of its scan; folded: Neff and the chunk offsets as well (d_res_pre).  Otherwise it went to a caller's slot only.
+static inline void pf_normalized(gms_pf *pf, bool own, bool folded) {
+    pf->score_fresh = 0;
+    pf->stats_current = 1;
+    if (own) { pf->d_global = pf->d_global_own; pf->global_raw = 0; }
+    pf->have_global = pf->chunks_ready = own;
+    pf->neff_folded = pf->res_pre_ready = own && folded;
+}
+// the audit path normalised d_w in place (k_normalize_seq): no packed population
+static inline void pf_normalized_in_place(gms_pf *pf) { pf->have_global = 0; pf->stats_current = 1; pf->score_fresh = 0; }
+// d_stats[1] was recomputed from the current particles
+static inline void pf_stats_recomputed(gms_pf *pf) { pf->stats_current = 2; }
+// d_global's contents were rewritten: nothing derived from them holds
+static inline void pf_source_written(gms_pf *pf, int32_t raw) {
+    pf->global_raw = raw;
+    pf->chunks_ready = 0;
+    pf->neff_folded = 0;
+    pf->res_pre_ready = 0;
+}
+// src (a gather, an import, a pack) is the current population now
+static inline void pf_source_replaced(gms_pf *pf, PackedParticle *src, int32_t raw) {
+    pf->d_global = src;
+    pf->have_global = 1;
+    pf_source_written(pf, raw);
+}
+// level 0 of the scan of d_global was made (k_chunk_sums or beside a normalise), without the paired prefix
+static inline void pf_chunks_made(gms_pf *pf) { pf->chunks_ready = 1; pf->res_pre_ready = 0; }
+// the own weights normalised beside the chunk sums of the gathered raw population (k_raycast_norm_chunks)
+static inline void pf_normalized_gathered(gms_pf *pf) {
+    pf_source_replaced(pf, pf->d_global_own, 1);
+    pf_chunks_made(pf);
+    pf->stats_current = 1;
+}
+static inline void pf_neff_folded(gms_pf *pf) { pf->neff_folded = 1; }
+// a resampling launch folded Neff, from the paired prefix where there was one
+static inline void pf_prefix_consumed(gms_pf *pf) { pf->res_pre_ready = 0; pf->neff_folded = 1; }
 
 // one rank's side of the RCCL exchanges of a sharded filter (gms_host.hip)
 struct gms_comm {
@@ -267,11 +360,13 @@ void gms_launch_apply_ray(gms_map *m, RayIn ray);
 void gms_launch_apply_counts(gms_map *m);
 void gms_launch_likelihood(gms_map *m, int32_t dirty_only, bool counts_pending = false, bool materialize = false);
 void gms_ensure_lik(gms_map *m);        // likelihoodData up to date everywhere (the scan steps' rebuilds write the factor table only)
+void gms_flush_apply(gms_map *m);       // the deferred apply pass, if one is pending
+// likelihoodData up to date, then logData (the deferred apply pass): what entry points that read or replace logData open with
+static inline void gms_map_settle(gms_map *m) { gms_ensure_lik(m); gms_flush_apply(m); }
 bool gms_likelihood_split(const gms_map *m, int32_t blocks);      // likelihood_body's SPLIT = 2 for a dirty-tile rebuild launched with `blocks` workgroups?
 size_t gms_likelihood_lds_bytes(int32_t khalf, bool coded = true);   // coded: the byte-coded staging of the compile-time half widths (gms_map::lik_kh != 0)
 int32_t gms_likelihood_blocks_cap(const gms_map *m, size_t smem);
 void gms_launch_raycast_apply(gms_map *m, const gms_beam *d_beams, int32_t B, int32_t beam_stride, const float *d_poses, int32_t pose_stride);
-void gms_defer_apply(gms_map *m);       // host bookkeeping: the scan just cast keeps its counts until a later launch applies them
 void gms_launch_fill(gms_map *m, double *d, double v, int64_t n);
 void gms_launch_combine(gms_map *src, gms_map *dst);
 void gms_launch_deskew(gms_map *m, const double *d_angle, const double *d_distance, const uint8_t *d_hit, int32_t length,
@@ -289,11 +384,8 @@ void gms_launch_pf_init(gms_pf *pf);
 void gms_launch_pf_pose_trig(gms_pf *pf, const float *d_src);
 void gms_launch_pf_combine(gms_pf *pf);
 void gms_launch_pf_motion(gms_pf *pf, double d_center, double d_theta, uint64_t seed, uint64_t sequence);
-void gms_launch_pf_after_gather(gms_pf *pf);
 void gms_launch_pf_chunk_sums(gms_pf *pf);
 // paired launches (gms_fused_kernels.hip)
-void gms_flush_apply(gms_map *m);
-void gms_apply_done(gms_map *m);
 void gms_launch_partials_apply(gms_pf *pf, double *d_partials, bool apply_rides_later = false);
 bool gms_can_pair_launches(const gms_pf *pf, int32_t B);
 void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticle *d_packed_local, bool own,

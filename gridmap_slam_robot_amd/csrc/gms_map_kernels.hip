@@ -1287,17 +1287,6 @@ static void apply_launch(gms_map *m) {
     // a deferred pass applies the grid that was set aside (gms_defer_apply); the immediate one the grid just cast into
     hipLaunchKernelGGL(k_apply, grid, dim3(256), 0, m->stream, m->gd, m->d_log, m->apply_pending ? m->d_cnt_pend : m->d_cnt, cur, idle);
 }
-void gms_apply_done(gms_map *m) {          // host bookkeeping after a deferred apply pass has been enqueued
-    m->bbox_cur = 1 - m->bbox_cur;
-    m->bbox_dirty = 0;
-    m->apply_pending = 0;
-}
-void gms_defer_apply(gms_map *m) {         // the scan just cast (and already in the likelihood field) keeps its counts for a later launch
-    uint32_t *t = m->d_cnt; m->d_cnt = m->d_cnt_pend; m->d_cnt_pend = t;       // the other grid is all zero: the next ray cast's
-    m->apply_pending = 1;
-    m->bbox_dirty = 0;
-}
-
 // this scan's ray cast beside the previous scan's deferred apply pass (k_raycast_apply); single maps, scans of <= 4096 beams
 void gms_launch_raycast_apply(gms_map *m, const gms_beam *d_beams, int32_t B, int32_t beam_stride, const float *d_poses,
                               int32_t pose_stride) {
@@ -1324,8 +1313,7 @@ void gms_flush_apply(gms_map *m) {
 void gms_launch_apply_counts(gms_map *m) {
     gms_flush_apply(m);
     apply_launch(m);
-    m->bbox_dirty = 1;
-    m->fac_current = 0;            // logData moved on without a rebuild having seen these counts: the next rebuild leaves no tile alone
+    map_counts_applied(m);         // logData moved on without a rebuild having seen these counts: the next rebuild leaves no tile alone
 }
 
 // dynamic LDS of a likelihood workgroup (likelihood_body's layout) and how many of them to launch per map
@@ -1371,18 +1359,14 @@ void gms_launch_likelihood(gms_map *m, int32_t dirty_only, bool counts_pending, 
     // is deferred by the caller (gms_defer_apply); the other box half is cleared for the next ray cast
     // materialize: bring likelihoodData up to date everywhere (mode 1) from logData and -- when an apply pass is still deferred --
     // the counts that pass will add: exactly what the last rebuild of the factor table saw (gms_ensure_lik)
-    if (!counts_pending && !materialize) gms_flush_apply(m);
+    const bool immediate = !counts_pending && !materialize;
+    if (immediate) gms_flush_apply(m);
     int32_t mode = 3;
     if (materialize) mode = 1;
-    else if (dirty_only && m->lik_lazy && (counts_pending || m->lik_stale)) { mode = 2; m->lik_stale = 1; }   // the hot path: factor table only
-    else if (!dirty_only) {
-        if (m->lik_stale) gms_invalidate_tile_state(m);       // the tile states speak for the factor table only: trust none of them for likelihoodData
-        m->lik_stale = 0;
-    }
-    if (!materialize) {
-        if (dirty_only && counts_pending && m->fac_current && m->lik_skip) mode |= 4;     // unchanged tiles are left alone
-        m->fac_current = 1;                                   // after this launch the factor table is the field of logData + pending counts
-    }
+    else if (dirty_only && m->lik_lazy && (counts_pending || m->lik_stale)) mode = 2;   // the hot path: factor table only
+    else if (!dirty_only && m->lik_stale) gms_invalidate_tile_state(m);       // the tile states speak for the factor table only: trust none of them for likelihoodData
+    if (dirty_only && counts_pending && m->fac_current && m->lik_skip) mode |= 4;     // unchanged tiles are left alone
+    map_field_built(m, mode);
     ProfScope ps(m, GMS_K_LIKELIHOOD);
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
@@ -1422,6 +1406,7 @@ void gms_launch_likelihood(gms_map *m, int32_t dirty_only, bool counts_pending, 
     else { if (counts_pending) LK_LAUNCH2(0, true, 1); else LK_LAUNCH2(0, false, 1); }
 #undef LK_LAUNCH
 #undef LK_LAUNCH2
+    if (immediate) map_box_consumed(m);
 }
 
 // likelihoodData as the reference would have it: the field of the last computeLikelihoodMap / scan step, everywhere
@@ -1429,7 +1414,6 @@ void gms_ensure_lik(gms_map *m) {
     if (!m->lik_stale) return;
     hipSetDevice(m->device);
     gms_launch_likelihood(m, 0, false, true);
-    m->lik_stale = 0;
 }
 
 // pinned host memory -> device memory, 16 bytes per lane (nbytes rounded up by the caller's buffers).  A kernel rather

@@ -1632,8 +1632,7 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
         ProfScope ps(m, GMS_K_SCORE);
         hipLaunchKernelGGL(k_score_seq, dim3((unsigned)((pf->n + 255) / 256), pf->n_maps), dim3(256), 0, m->stream, m->gd, m->d_fac, m->fac_stride,
                            d_beams, B, beam_stride, pf->d_pose, pf->d_cs, pf->n, pf->d_w, pf->d_logw);
-        pf->pending_nseg = 0;
-        pf->score_fresh = 1;
+        pf_scored(pf, 1);
         return;
     }
     MotionArgs mo;
@@ -1666,7 +1665,6 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
         d_pose_src = pf->d_pose; pose_dst = pf->d_pose2; cs_dst = pf->d_cs2;
     }
     ProfScope ps(m, GMS_K_SCORE);
-    pf->pending_nseg = 0;
     // Lanes per workgroup: 1024 (sixteen wavefronts sharing one segment's L1 patch) while that still gives every CU a workgroup;
     // a smaller population -- one shard of eight of config 4's 65 536 particles, config 2 -- takes 512 or 256 lanes per workgroup
     // instead, so that the look-ups spread over all the CUs' address pipes rather than queueing on half or an eighth of them
@@ -1695,8 +1693,7 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
                            pf->d_part, pf->d_w, pf->d_logw, d_pose_src, pose_dst, cs_dst, (const float4 *)nullptr,
                            (const int32_t *)nullptr, mo, pf->offset, spread);
     if (motion) { std::swap(pf->d_pose, pf->d_pose2); std::swap(pf->d_cs, pf->d_cs2); }
-    pf->score_fresh = 1;
-    if (nseg > 1) pf->pending_nseg = (int32_t)nseg;               // combined by the next consumer of the weights
+    pf_scored(pf, nseg);                                          // segment products: combined by the next consumer of the weights
 }
 
 // materialise weight / log-weight from the per-segment products if nobody has yet
@@ -1706,7 +1703,7 @@ void gms_launch_pf_combine(gms_pf *pf) {
     ProfScope ps(m, GMS_K_SCORE);
     hipLaunchKernelGGL(k_score_combine, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), 0, m->stream, pf->d_part, pf->n,
                        pf->pending_nseg, pf->d_w, pf->d_logw);
-    pf->pending_nseg = 0;
+    pf_weights_combined(pf);
 }
 
 // whether the next partials / normalise pair takes the log-normalising form: the option is on and the weights are those of a scoring
@@ -1721,23 +1718,18 @@ void gms_launch_pf_partials(gms_pf *pf, double *d_partials) {
                        pf->d_pose, pf->n, pf->offset, nblk, d_partials,
                        pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->pending_nseg,
                        gms_pf_lognorm_now(pf) ? pf->d_stats : (PfStatsDev *)nullptr);
-    pf->pending_nseg = 0;                                             // k_partials stored the combined weights
+    pf_weights_combined(pf);                                          // k_partials stored the combined weights
 }
 
 void gms_launch_pf_apply_partials(gms_pf *pf, const double *d_partials, PackedParticle *d_packed_local, bool own) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_REDUCE);
     const int64_t nblk = nblk_global_of(pf);
-    // a stand-alone filter packs straight into its own population and gets level 0 of the scan with it
-    if (own) { pf->d_global = pf->d_global_own; pf->global_raw = 0; }
     hipLaunchKernelGGL(k_normalize_pack, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), 0, m->stream, d_partials, nblk,
                        pf->d_w, pf->d_pose, pf->n, pf->offset, d_packed_local, own ? pf->d_cum : (double *)nullptr,
                        own ? pf->d_chunk_tot : (double *)nullptr, nchunks_of(pf), own ? pf->d_p2 : (double *)nullptr, pf->d_stats,
                        gms_pf_lognorm_now(pf) ? (const double *)pf->d_logw : (const double *)nullptr);
-    pf->score_fresh = 0;                                              // the scoring pass has been consumed
-    pf->chunks_ready = own ? 1 : 0;
-    pf->neff_folded = 0;
-    pf->res_pre_ready = 0;
+    pf_normalized(pf, own, false);       // a stand-alone filter packs straight into its own population and gets level 0 of the scan with it
 }
 
 void gms_launch_pf_stats_only(gms_pf *pf, const double *d_partials, PfStatsDev *d_stats_out) {
@@ -1751,7 +1743,7 @@ void gms_launch_pf_pack(gms_pf *pf, PackedParticle *d_packed) {
     gms_map *m = pf->map;
     hipLaunchKernelGGL(k_pack, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), 0, m->stream, pf->d_w, pf->d_pose,
                        pf->n, d_packed);
-    if (d_packed == pf->d_global) { pf->chunks_ready = 0; pf->neff_folded = 0; pf->global_raw = 0; pf->res_pre_ready = 0; }
+    if (d_packed == pf->d_global) pf_source_written(pf, 0);
 }
 
 // level 0 of the scan + {sum wn, sum wn^2} + strongest pose from d_global (paths that did not come through a
@@ -1763,8 +1755,7 @@ void gms_launch_pf_chunk_sums(gms_pf *pf) {
     const int64_t nch = nchunks_of(pf);
     hipLaunchKernelGGL(k_chunk_sums, dim3((unsigned)nblk_global_of(pf), pf->n_maps), dim3(256), 0, m->stream, pf->d_global,
                        pf->n_global, nch, pf->d_cum, pf->d_chunk_tot, pf->d_p2, nblk_global_of(pf), pf->d_stats);
-    pf->chunks_ready = 1;
-    pf->res_pre_ready = 0;
+    pf_chunks_made(pf);
 }
 
 void gms_launch_pf_fold_neff(gms_pf *pf) {
@@ -1772,15 +1763,7 @@ void gms_launch_pf_fold_neff(gms_pf *pf) {
     gms_map *m = pf->map;
     gms_launch_pf_chunk_sums(pf);
     hipLaunchKernelGGL(k_fold_neff, dim3(pf->n_maps), dim3(256), 0, m->stream, pf->d_p2, nblk_global_of(pf), pf->d_stats);
-    pf->neff_folded = 1;
-}
-
-void gms_launch_pf_after_gather(gms_pf *pf) {
-    pf->global_raw = 0;
-    pf->chunks_ready = 0;
-    pf->neff_folded = 0;
-    pf->res_pre_ready = 0;
-    gms_launch_pf_chunk_sums(pf);          // eagerly: it also publishes the strongest particle's pose
+    pf_neff_folded(pf);
 }
 
 void gms_launch_pf_resample(gms_pf *pf, double fraction) {
@@ -1796,7 +1779,7 @@ void gms_launch_pf_resample(gms_pf *pf, double fraction) {
                        pf->n_global, nch, pf->d_cum, pf->d_chunk_tot, pf->n_maps == 1 ? (const double *)nullptr : pf->d_r01_src,
                        pf->r01_scalar, fraction, pf->n, pf->offset,
                        pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, pf->d_p2, nblk_global_of(pf), pf->d_stats, pf->global_raw, pf->d_epoch2);
-    pf->neff_folded = 1;
+    pf_neff_folded(pf);
 }
 
 void gms_launch_pf_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t beam_stride) {

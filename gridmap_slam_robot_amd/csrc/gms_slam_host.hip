@@ -145,7 +145,7 @@ int gms_slam_reset(gms_slam *s) {                                               
     s->lik_behind = 0;
     s->lik_from_codes = 0;
     gms_launch_pf_init(s->pf);                                                               // Pose(0, 0, 0), weight 1 / numParticles (:68-71)
-    s->pf->pending_nseg = 0; s->pf->have_global = 0; s->pf->stats_current = 0; s->pf->score_fresh = 0;
+    pf_weights_set(s->pf);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -206,8 +206,6 @@ static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, 
         drawn = true;
     }
     gms_launch_slam_particle(pf, dev_beams, B, sb, !on_demand, sample_motion && !drawn ? &mo : nullptr, skip_update ? 0 : 1, s->code_words);   // :90, :99, :102-107
-    pf->have_global = 0;
-    pf->stats_current = 0;
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -430,10 +428,9 @@ int gms_slam_combined(gms_slam *s) {
     REQUIRE(s, "null handle");
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
-    gms_ensure_lik(m);
-    gms_flush_apply(m);
+    gms_map_settle(m);
     gms_launch_slam_combine(m, gms_slam_bufs(s), s->n);                                       // :441-455
-    m->need_full_build = 1; m->fac_current = 0;
+    map_log_replaced(m);
     HIPCHK(hipGetLastError());
     return gms_map_build_likelihood(m);                                                       // :457
 }

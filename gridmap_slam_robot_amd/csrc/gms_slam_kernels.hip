@@ -1352,8 +1352,7 @@ void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, co
     else { if (narrow_allowed) PS_LAUNCH2(1024, true); else PS_LAUNCH2(1024, false); }
 #undef PS_LAUNCH2
 #undef PS_LAUNCH
-    pf->pending_nseg = 0;
-    pf->score_fresh = 1;
+    pf_scored(pf, 1);
 }
 
 void gms_launch_slam_trace(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t particle, int32_t *d_cells, uint8_t *d_cls, int32_t cap, int32_t *d_counts) {
