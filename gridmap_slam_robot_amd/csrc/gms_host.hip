@@ -17,14 +17,6 @@
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 int gms_fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -32,17 +24,6 @@ int gms_fail(int code, const char *fmt, ...) {
     va_end(ap);
     return code;
 }
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(GMS_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
-#define REQUIRE(cond, msg)                                     \
-    do {                                                       \
-        if (!(cond)) return fail(GMS_ERR_INVALID, "%s", msg);  \
-    } while (0)
 
 // Java (int) of a double for the host-side constructor arithmetic
 static int32_t j_d2i_host(double d) {
@@ -106,7 +87,7 @@ int gms_params_default(gms_params *p, float width_m, float height_m, float resol
     const double sigma = sqrt(0.05 / (double)resolution);     // GridMap.java:94
     const int32_t size = j_d2i_host(ceil(sigma * 3));         // GridMap.java:95
     if (size < 0 || 2 * size + 1 > GMS_MAX_TAPS)
-        return fail(GMS_ERR_INVALID, "likelihood kernel of %d taps exceeds GMS_MAX_TAPS", 2 * size + 1);
+        return gms_fail(GMS_ERR_INVALID, "likelihood kernel of %d taps exceeds GMS_MAX_TAPS", 2 * size + 1);
     p->ktaps = 2 * size + 1;
     gms_generate_gaussian_kernel(sigma, size, p->kernel);
     p->extra_steps = 2;                                       // GridMap.java:210
@@ -291,19 +272,19 @@ int gms_map_create(const gms_params *p, gms_map **out) {
     REQUIRE(W > 0 && H > 0 && (int64_t)W * H < (1ll << 31), "gms_map_create: grid size out of range");
     REQUIRE(W + 16 < (1 << 24) && H < (1 << 24) && (int64_t)(H + 1) * (W + 16) < (1ll << 32), "gms_map_create: grid size out of range");   // fac_index: 24-bit factors, 32-bit index
     int ndev = gms_device_count();
-    if (ndev <= 0) return fail(GMS_ERR_NO_DEVICE, "no HIP device visible: libgridmapslam has no CPU path");
-    if (p->device < 0 || p->device >= ndev) return fail(GMS_ERR_NO_DEVICE, "device %d of %d not available", p->device, ndev);
+    if (ndev <= 0) return gms_fail(GMS_ERR_NO_DEVICE, "no HIP device visible: libgridmapslam has no CPU path");
+    if (p->device < 0 || p->device >= ndev) return gms_fail(GMS_ERR_NO_DEVICE, "device %d of %d not available", p->device, ndev);
     HIPCHK(hipSetDevice(p->device));
     {   // the likelihood pass stages a tile with a halo of (ktaps - 1) / 2 cells in LDS: 11 taps 25 KiB, 65 taps 149 KiB
         int lds_max = 0;
         if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, p->device) != hipSuccess) lds_max = 64 * 1024;
         if (gms_likelihood_lds_bytes((p->ktaps - 1) / 2) + 4096 > (size_t)lds_max)
-            return fail(GMS_ERR_INVALID, "gms_map_create: a blur kernel of %d taps needs %zu bytes of LDS per workgroup, this device offers %d",
-                        p->ktaps, gms_likelihood_lds_bytes((p->ktaps - 1) / 2) + 4096, lds_max);
+            return gms_fail(GMS_ERR_INVALID, "gms_map_create: a blur kernel of %d taps needs %zu bytes of LDS per workgroup, this device offers %d",
+                            p->ktaps, gms_likelihood_lds_bytes((p->ktaps - 1) / 2) + 4096, lds_max);
     }
 
     gms_map *m = new (std::nothrow) gms_map();
-    if (!m) return fail(GMS_ERR_NOMEM, "out of host memory");
+    if (!m) return gms_fail(GMS_ERR_NOMEM, "out of host memory");
     m->prm = *p;
     m->n_maps = p->n_maps;
     m->device = p->device;
@@ -337,7 +318,7 @@ int gms_map_create(const gms_params *p, gms_map **out) {
 
     const size_t cells = (size_t)g.cells * m->n_maps;
     hipError_t e = hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete m; return fail(GMS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete m; return gms_fail(GMS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
     m->stream = m->own_stream;
     bool ok = true;
 
@@ -358,7 +339,7 @@ int gms_map_create(const gms_params *p, gms_map **out) {
     ok = ok && hipHostMalloc(&m->h_beams, (size_t)m->n_maps * m->max_beams * sizeof(gms_beam)) == hipSuccess;
     ok = ok && ring_alloc(m->beam_ring, (size_t)m->n_maps * m->max_beams * sizeof(gms_beam)) == GMS_OK;
     ok = ok && hipHostMalloc(&m->h_poses, (size_t)m->n_maps * 3 * sizeof(float) + 64 * sizeof(double)) == hipSuccess;
-    if (!ok) { map_free(m); return fail(GMS_ERR_NOMEM, "device allocation failed (%zu cells x %d maps)", (size_t)g.cells, m->n_maps); }
+    if (!ok) { map_free(m); return gms_fail(GMS_ERR_NOMEM, "device allocation failed (%zu cells x %d maps)", (size_t)g.cells, m->n_maps); }
     hipMemcpyAsync(m->d_taps, p->kernel, p->ktaps * sizeof(double), hipMemcpyHostToDevice, m->stream);
     hipMemsetAsync(m->d_log, 0, cells * sizeof(double), m->stream);   // logOdds(0.5) == 0.0 (createMapData(null))
     hipMemsetAsync(m->d_lik, 0, cells * sizeof(double), m->stream);
@@ -397,7 +378,7 @@ int gms_map_create(const gms_params *p, gms_map **out) {
 int gms_map_destroy(gms_map *m) {
     if (!m) return GMS_OK;
     // a filter keeps a pointer to its map (stream, device, grids): destroy the filters first
-    if (m->n_filters > 0) return fail(GMS_ERR_STATE, "gms_map_destroy: %d particle filter(s) still bound to this map", m->n_filters);
+    if (m->n_filters > 0) return gms_fail(GMS_ERR_STATE, "gms_map_destroy: %d particle filter(s) still bound to this map", m->n_filters);
     hipSetDevice(m->device);
     hipStreamSynchronize(m->stream);
     return map_free(m);
@@ -478,7 +459,7 @@ static int stream_after(hipStream_t later, hipStream_t earlier, const char *what
     hipError_t e = hipEventRecord(ev, earlier);
     if (e == hipSuccess) e = hipStreamWaitEvent(later, ev, 0);
     hipEventDestroy(ev);                                             // released once the recorded work has completed
-    if (e != hipSuccess) return fail(GMS_ERR_HIP, "%s: stream hand-over: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return gms_fail(GMS_ERR_HIP, "%s: stream hand-over: %s", what, hipGetErrorString(e));
     return GMS_OK;
 }
 
@@ -588,7 +569,7 @@ int gms_map_get_at_point(gms_map *m, int32_t mi, float point_x, float point_y, d
     const int32_t ix = j_f2i_host(tx), iy = j_f2i_host(ty);
     const int32_t idx = (int32_t)((uint32_t)ix + (uint32_t)iy * (uint32_t)m->gd.W);       // Java int arithmetic wraps
     if (idx < 0 || (int64_t)idx >= m->gd.cells)
-        return fail(GMS_ERR_INVALID, "gms_map_get_at_point: index %d out of bounds (Java: ArrayIndexOutOfBoundsException)", idx);
+        return gms_fail(GMS_ERR_INVALID, "gms_map_get_at_point: index %d out of bounds (Java: ArrayIndexOutOfBoundsException)", idx);
     HIPCHK(hipSetDevice(m->device));
     gms_map_settle(m);
     double *h = reinterpret_cast<double *>(m->h_poses + (size_t)m->n_maps * 3);
@@ -635,12 +616,6 @@ static int stage_poses(gms_map *m, const float *poses) {
     return GMS_OK;
 }
 
-// device address of the filter's weighted pose (which = 0) or strongest particle's pose (1), map 0
-static const float *stats_pose_ptr(const gms_pf *pf, int32_t which) {
-    const char *base = reinterpret_cast<const char *>(pf->d_stats);
-    return reinterpret_cast<const float *>(base + (which == 0 ? offsetof(PfStatsDev, wpose) : offsetof(PfStatsDev, spose)));
-}
-
 static int finish_likelihood(gms_map *m, int32_t dirty_only) {
     if (dirty_only && !m->bbox_dirty) return GMS_OK;     // nothing changed since the last build
     gms_launch_likelihood(m, dirty_only);
@@ -648,60 +623,124 @@ static int finish_likelihood(gms_map *m, int32_t dirty_only) {
     return GMS_OK;
 }
 
-int gms_map_integrate(gms_map *m, const gms_beam *beams, int32_t B, const float *poses) {   // GridMap.java:173-191
-    REQUIRE(m, "null map");
-    gms_ensure_lik(m);                 // integrateObservation leaves likelihoodData as the last rebuild made it: have it made first
-    int rc = stage_beams(m, beams, B);
-    if (rc) return rc;
-    rc = stage_poses(m, poses);
-    if (rc) return rc;
-    if (B > 0) {
-        gms_launch_raycast(m, m->d_beams, B, m->max_beams, m->d_poses, 3);
-        gms_launch_apply_counts(m);
-    }
+// integrateObservation + computeLikelihoodMap with the scan's apply pass deferred: [ray cast | the previous scan's apply pass]
+// -> dirty-tile likelihood rebuild with the new counts added on the fly.  Two launches per scan instead of three; the map
+// comes out bit-identical (tests/test_gpu_parity.py, test_gpu_closed_loop.py); anything else that touches the map first
+// runs the pending pass (gms_flush_apply).  Single maps in the steady state (a field to rebuild incrementally exists).
+static bool can_defer_update(const gms_map *m, int32_t B) {
+    return m->pair_launches && m->n_maps == 1 && B > 0 && B <= 4096 && !m->need_full_build;
+}
+static int deferred_update(gms_map *m, const gms_beam *dev_beams, int32_t B, int32_t beam_stride, const float *dev_poses, int32_t pose_stride) {
+    if (m->apply_pending) gms_launch_raycast_apply(m, dev_beams, B, beam_stride, dev_poses, pose_stride);
+    else gms_launch_raycast(m, dev_beams, B, beam_stride, dev_poses, pose_stride);
+    gms_launch_likelihood(m, 1, true);
+    gms_defer_apply(m);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
 
+// ---- a scan's inputs ------------------------------------------------------------------------------
+// Where the beams and the pose of a scan come from.  Host inputs are staged: the beams [n_maps][B] into d_beams, where they
+// are read at stride max_beams, the poses [n_maps][3] into d_poses.  Device beams are read in place at beam_stride, device
+// poses at stride 3.  With pf set, the pose is the filter's weighted pose (which = 0) or its strongest particle's (1).
+struct ScanIn {
+    bool host;                // beams and poses are host arrays
+    const gms_beam *beams;
+    int32_t B;
+    int32_t beam_stride;      // (device beams)
+    const float *poses;       // (pf == nullptr)
+    const gms_pf *pf;
+    int32_t which;
+};
+// ... and where the launches read them
+struct ScanDev {
+    const gms_beam *beams;
+    int32_t beam_stride;
+    const float *poses;
+    int32_t pose_stride;
+};
+
+static ScanIn host_scan(const gms_beam *beams, int32_t B, const float *poses, const gms_pf *pf = nullptr, int32_t which = 0) {
+    return ScanIn{true, beams, B, 0, poses, pf, which};
+}
+static ScanIn dev_scan(const gms_beam *beams, int32_t B, int32_t beam_stride, const float *poses, const gms_pf *pf = nullptr,
+                       int32_t which = 0) {
+    return ScanIn{false, beams, B, beam_stride, poses, pf, which};
+}
+
+static int scan_check(const gms_map *m, const ScanIn &in) {
+    REQUIRE(m && in.beams && (in.pf || in.poses), "null argument");
+    REQUIRE(in.B >= 0 && in.B <= m->max_beams, "beam count exceeds gms_params.max_beams");
+    REQUIRE(!in.pf || in.pf->map == m, "the filter does not belong to this map");
+    REQUIRE(!in.pf || in.which == 0 || in.which == 1, "which must be 0 (weighted pose) or 1 (strongest particle)");
+    return GMS_OK;
+}
+
+// the beams where the launches read them (host beams: staged, and checked by stage_beams)
+static int scan_beams(gms_map *m, const ScanIn &in, ScanDev *d) {
+    d->beams = in.host ? m->d_beams : in.beams;
+    d->beam_stride = in.host ? m->max_beams : in.beam_stride;
+    return in.host ? stage_beams(m, in.beams, in.B) : GMS_OK;
+}
+
+// the pose where the ray cast reads it (map 0's; the filter's in d_stats, at the PfStatsDev stride)
+static int scan_pose(gms_map *m, const ScanIn &in, ScanDev *d) {
+    if (in.pf) {
+        const char *stats = reinterpret_cast<const char *>(in.pf->d_stats);
+        d->poses = reinterpret_cast<const float *>(stats + (in.which == 0 ? offsetof(PfStatsDev, wpose) : offsetof(PfStatsDev, spose)));
+        d->pose_stride = (int32_t)(sizeof(PfStatsDev) / sizeof(float));
+        return GMS_OK;
+    }
+    d->poses = in.host ? m->d_poses : in.poses;
+    d->pose_stride = 3;
+    return in.host ? stage_poses(m, in.poses) : GMS_OK;
+}
+
+// integrateObservation (GridMap.java:173-191), and for the updates computeLikelihoodMap after it, of one scan
+enum MapScan { SCAN_INTEGRATE, SCAN_UPDATE, SCAN_UPDATE_MAY_DEFER };
+static int map_scan(gms_map *m, const ScanIn &in, MapScan mode) {
+    int rc = scan_check(m, in);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    const bool defer = mode == SCAN_UPDATE_MAY_DEFER && can_defer_update(m, in.B);
+    if (!defer) gms_ensure_lik(m);     // integrateObservation leaves likelihoodData as the last rebuild made it: have it made first
+    ScanDev d;
+    rc = scan_beams(m, in, &d);
+    if (!rc) rc = scan_pose(m, in, &d);
+    if (rc) return rc;
+    if (defer) return deferred_update(m, d.beams, in.B, d.beam_stride, d.poses, d.pose_stride);
+    if (in.B > 0) {
+        gms_launch_raycast(m, d.beams, in.B, d.beam_stride, d.poses, d.pose_stride);
+        gms_launch_apply_counts(m);
+    }
+    HIPCHK(hipGetLastError());
+    return mode == SCAN_INTEGRATE ? GMS_OK : finish_likelihood(m, m->need_full_build ? 0 : 1);
+}
+
+int gms_map_integrate(gms_map *m, const gms_beam *beams, int32_t B, const float *poses) {
+    return map_scan(m, host_scan(beams, B, poses), SCAN_INTEGRATE);
+}
 int gms_map_integrate_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, const float *dev_poses) {
-    REQUIRE(m && dev_beams && dev_poses, "null argument");
-    REQUIRE(B >= 0 && B <= m->max_beams, "beam count exceeds gms_params.max_beams");
-    HIPCHK(hipSetDevice(m->device));
-    gms_ensure_lik(m);
-    if (B > 0) {
-        gms_launch_raycast(m, dev_beams, B, B, dev_poses, 3);
-        gms_launch_apply_counts(m);
-    }
-    HIPCHK(hipGetLastError());
-    return GMS_OK;
+    return map_scan(m, dev_scan(dev_beams, B, B, dev_poses), SCAN_INTEGRATE);
 }
-
-int gms_map_integrate_at_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, gms_pf *pf, int32_t which) {
-    REQUIRE(m && dev_beams && pf && pf->map == m, "gms_map_integrate_at_dev: bad arguments");
-    REQUIRE(which == 0 || which == 1, "which must be 0 (weighted pose) or 1 (strongest particle)");
-    REQUIRE(B >= 0 && B <= m->max_beams, "beam count exceeds gms_params.max_beams");
-    HIPCHK(hipSetDevice(m->device));
-    gms_ensure_lik(m);
-    if (B > 0) {
-        gms_launch_raycast(m, dev_beams, B, B, stats_pose_ptr(pf, which), (int32_t)(sizeof(PfStatsDev) / sizeof(float)));
-        gms_launch_apply_counts(m);
-    }
-    HIPCHK(hipGetLastError());
-    return GMS_OK;
-}
-
 int gms_map_integrate_at(gms_map *m, const gms_beam *beams, int32_t B, gms_pf *pf, int32_t which) {
-    REQUIRE(m && pf && pf->map == m, "gms_map_integrate_at: filter does not belong to this map");
-    REQUIRE(which == 0 || which == 1, "which must be 0 (weighted pose) or 1 (strongest particle)");
-    gms_ensure_lik(m);
-    int rc = stage_beams(m, beams, B);
-    if (rc) return rc;
-    if (B > 0) {
-        gms_launch_raycast(m, m->d_beams, B, m->max_beams, stats_pose_ptr(pf, which), (int32_t)(sizeof(PfStatsDev) / sizeof(float)));
-        gms_launch_apply_counts(m);
-    }
-    HIPCHK(hipGetLastError());
-    return GMS_OK;
+    return map_scan(m, host_scan(beams, B, nullptr, pf, which), SCAN_INTEGRATE);
+}
+int gms_map_integrate_at_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, gms_pf *pf, int32_t which) {
+    return map_scan(m, dev_scan(dev_beams, B, B, nullptr, pf, which), SCAN_INTEGRATE);
+}
+int gms_map_update(gms_map *m, const gms_beam *beams, int32_t B, const float *poses) {
+    return map_scan(m, host_scan(beams, B, poses), SCAN_UPDATE_MAY_DEFER);
+}
+int gms_map_update_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, const float *dev_poses) {
+    return map_scan(m, dev_scan(dev_beams, B, B, dev_poses), SCAN_UPDATE_MAY_DEFER);
+}
+int gms_map_update_at(gms_map *m, const gms_beam *beams, int32_t B, gms_pf *pf, int32_t which) {
+    // never deferred, unlike the other three updates: deferring would change the launches of the JNI path that calls it
+    return map_scan(m, host_scan(beams, B, nullptr, pf, which), SCAN_UPDATE);
+}
+int gms_map_update_at_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, gms_pf *pf, int32_t which) {
+    return map_scan(m, dev_scan(dev_beams, B, B, nullptr, pf, which), SCAN_UPDATE_MAY_DEFER);
 }
 
 int gms_map_apply_ray(gms_map *m, float sx, float sy, float ex, float ey, float measured, int32_t hit) {
@@ -777,64 +816,6 @@ int gms_map_build_likelihood(gms_map *m) {                              // GridM
     return finish_likelihood(m, 0);
 }
 
-// integrateObservation + computeLikelihoodMap with the scan's apply pass deferred: [ray cast | the previous scan's apply pass]
-// -> dirty-tile likelihood rebuild with the new counts added on the fly.  Two launches per scan instead of three; the map
-// comes out bit-identical (tests/test_gpu_parity.py, test_gpu_closed_loop.py); anything else that touches the map first
-// runs the pending pass (gms_flush_apply).  Single maps in the steady state (a field to rebuild incrementally exists).
-static bool can_defer_update(const gms_map *m, int32_t B) {
-    return m->pair_launches && m->n_maps == 1 && B > 0 && B <= 4096 && !m->need_full_build;
-}
-static int deferred_update(gms_map *m, const gms_beam *dev_beams, int32_t B, int32_t beam_stride, const float *dev_poses, int32_t pose_stride) {
-    if (m->apply_pending) gms_launch_raycast_apply(m, dev_beams, B, beam_stride, dev_poses, pose_stride);
-    else gms_launch_raycast(m, dev_beams, B, beam_stride, dev_poses, pose_stride);
-    gms_launch_likelihood(m, 1, true);
-    gms_defer_apply(m);
-    HIPCHK(hipGetLastError());
-    return GMS_OK;
-}
-
-int gms_map_update(gms_map *m, const gms_beam *beams, int32_t B, const float *poses) {
-    if (m && can_defer_update(m, B)) {
-        int rc = stage_beams(m, beams, B);
-        if (!rc) rc = stage_poses(m, poses);
-        return rc ? rc : deferred_update(m, m->d_beams, B, m->max_beams, m->d_poses, 3);
-    }
-    int rc = gms_map_integrate(m, beams, B, poses);
-    if (rc) return rc;
-    return finish_likelihood(m, m->need_full_build ? 0 : 1);
-}
-
-int gms_map_update_at(gms_map *m, const gms_beam *beams, int32_t B, gms_pf *pf, int32_t which) {
-    int rc = gms_map_integrate_at(m, beams, B, pf, which);
-    if (rc) return rc;
-    return finish_likelihood(m, m->need_full_build ? 0 : 1);
-}
-
-int gms_map_update_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, const float *dev_poses) {
-    REQUIRE(m && dev_beams && dev_poses, "null argument");
-    REQUIRE(B >= 0 && B <= m->max_beams, "beam count exceeds gms_params.max_beams");
-    if (can_defer_update(m, B)) {
-        HIPCHK(hipSetDevice(m->device));
-        return deferred_update(m, dev_beams, B, B, dev_poses, 3);
-    }
-    int rc = gms_map_integrate_dev(m, dev_beams, B, dev_poses);
-    if (rc) return rc;
-    return finish_likelihood(m, m->need_full_build ? 0 : 1);
-}
-
-int gms_map_update_at_dev(gms_map *m, const gms_beam *dev_beams, int32_t B, gms_pf *pf, int32_t which) {
-    REQUIRE(m && dev_beams && pf && pf->map == m, "gms_map_update_at_dev: bad arguments");
-    REQUIRE(which == 0 || which == 1, "which must be 0 (weighted pose) or 1 (strongest particle)");
-    REQUIRE(B >= 0 && B <= m->max_beams, "beam count exceeds gms_params.max_beams");
-    if (can_defer_update(m, B)) {
-        HIPCHK(hipSetDevice(m->device));
-        return deferred_update(m, dev_beams, B, B, stats_pose_ptr(pf, which), (int32_t)(sizeof(PfStatsDev) / sizeof(float)));
-    }
-    int rc = gms_map_integrate_at_dev(m, dev_beams, B, pf, which);
-    if (rc) return rc;
-    return finish_likelihood(m, m->need_full_build ? 0 : 1);
-}
-
 int gms_map_tile_stats(gms_map *m, int32_t enable, int64_t *out4) {
     REQUIRE(m, "null map");
     HIPCHK(hipSetDevice(m->device));
@@ -855,7 +836,7 @@ int gms_map_tile_stats(gms_map *m, int32_t enable, int64_t *out4) {
 int gms_debug_set_stamps(gms_map *m, void *dev_buffer) {
     REQUIRE(m, "null map");
     HIPCHK(hipSetDevice(m->device));
-    return gms_set_stamp_buffer(m, dev_buffer) ? GMS_OK : fail(GMS_ERR_STATE, "this build carries no stage stamps (compile with -DGMS_STAMPS)");
+    return gms_set_stamp_buffer(m, dev_buffer) ? GMS_OK : gms_fail(GMS_ERR_STATE, "this build carries no stage stamps (compile with -DGMS_STAMPS)");
 }
 
 int gms_debug_f32(gms_map *m, int32_t op, const float *in, float *out, int64_t n) {
@@ -923,7 +904,7 @@ int gms_pf_create(gms_map *m, int32_t n, gms_pf **out) {               // Partic
     REQUIRE(n >= 1 && n <= GMS_MAX_PARTICLES, "gms_pf_create: particle count out of range (1 .. GMS_MAX_PARTICLES)");
     HIPCHK(hipSetDevice(m->device));
     gms_pf *pf = new (std::nothrow) gms_pf();
-    if (!pf) return fail(GMS_ERR_NOMEM, "out of host memory");
+    if (!pf) return gms_fail(GMS_ERR_NOMEM, "out of host memory");
     pf->map = m; pf->n = n; pf->offset = 0; pf->n_global = n; pf->n_maps = m->n_maps;
     m->n_filters++;
     const size_t T = (size_t)n * m->n_maps;
@@ -949,7 +930,7 @@ int gms_pf_create(gms_map *m, int32_t n, gms_pf **out) {               // Partic
     ok = ok && hipHostMalloc(&pf->h_stats, (size_t)m->n_maps * sizeof(PfStatsDev) + (size_t)m->n_maps * 8) == hipSuccess;
     ok = ok && hipHostMalloc(&pf->h_stage, T * 3 * sizeof(float)) == hipSuccess;
     ok = ok && ring_alloc(pf->pose_ring, T * 3 * sizeof(float)) == GMS_OK;
-    if (!ok || pf_alloc_global(pf) != GMS_OK) { gms_pf_destroy(pf); return fail(GMS_ERR_NOMEM, "device allocation failed for %d particles", n); }
+    if (!ok || pf_alloc_global(pf) != GMS_OK) { gms_pf_destroy(pf); return gms_fail(GMS_ERR_NOMEM, "device allocation failed for %d particles", n); }
     hipMemsetAsync(pf->d_stats, 0, (size_t)m->n_maps * 2 * sizeof(PfStatsDev), m->stream);
     gms_launch_pf_init(pf);
     HIPCHK(hipGetLastError());
@@ -957,17 +938,24 @@ int gms_pf_create(gms_map *m, int32_t n, gms_pf **out) {               // Partic
     return GMS_OK;
 }
 
+// the filter of a gms_slam: what would move its particles without their maps is refused (gms_slam's own calls set d_epoch2)
+static int refuse_owned_maps(const gms_pf *pf) {
+    if (pf->slam_owned && !pf->d_epoch2)
+        return gms_fail(GMS_ERR_STATE, "this filter's particles own maps (gms_slam): resample through gms_slam_resample_maps[_if], update through gms_slam_update_per_particle");
+    return GMS_OK;
+}
+
 int gms_pf_set_shard(gms_pf *pf, int64_t offset, int64_t n_global) {
     REQUIRE(pf, "null filter");
-    if (pf->slam_owned && !pf->d_epoch2)
-        return fail(GMS_ERR_STATE, "this filter's particles own maps (gms_slam): resample through gms_slam_resample_maps[_if], update through gms_slam_update_per_particle");
+    int rc = refuse_owned_maps(pf);
+    if (rc) return rc;
     REQUIRE(offset >= 0 && offset % GMS_BLOCK == 0, "shard offset must be a multiple of GMS_BLOCK");
     REQUIRE(n_global >= offset + pf->n && n_global <= GMS_MAX_PARTICLES, "shard does not fit n_global (at most GMS_MAX_PARTICLES in all)");
     HIPCHK(hipSetDevice(pf->map->device));
     HIPCHK(hipStreamSynchronize(pf->map->stream));
     pf->offset = offset;
     pf->n_global = n_global;
-    if (offset != 0 || n_global != pf->n) { pf->log_norm = 0; pf->reference_order = 0; }      // (stand-alone filters only)
+    if (pf_is_shard(pf)) { pf->log_norm = 0; pf->reference_order = 0; }      // (stand-alone filters only)
     return pf_alloc_global(pf);
 }
 
@@ -1033,20 +1021,10 @@ int gms_pf_get_log_weights(gms_pf *pf, double *lw) {
     return pf_copy_f64(pf, pf->d_logw, lw, false);
 }
 
-int gms_pf_score(gms_pf *pf, const gms_beam *beams, int32_t B) {       // GridMap.java:261-294 x N
-    REQUIRE(pf, "null filter");
-    gms_map *m = pf->map;
-    int rc = stage_beams(m, beams, B);
-    if (rc) return rc;
-    gms_launch_pf_score(pf, m->d_beams, B, m->max_beams);
-    HIPCHK(hipGetLastError());
-    return GMS_OK;
-}
-
 // poses := dev_xytheta (may be NULL: keep the current ones), then weights: one launch with the default scoring kernel.
 // refine: the poses are replaced by findBestPose's argmax first (SLAM.java:96-97), which takes launches of its own.
-static int set_poses_and_score_dev(gms_pf *pf, const float *dev_xytheta, const gms_beam *dev_beams, int32_t B, bool refine = false,
-                                   const MotionModel *motion = nullptr) {
+static int set_poses_and_score_dev(gms_pf *pf, const float *dev_xytheta, const gms_beam *dev_beams, int32_t B, int32_t beam_stride,
+                                   bool refine = false, const MotionModel *motion = nullptr) {
     REQUIRE(pf && dev_beams, "null argument");
     gms_map *m = pf->map;
     REQUIRE(B >= 0 && B <= m->max_beams, "beam count exceeds gms_params.max_beams");
@@ -1054,18 +1032,23 @@ static int set_poses_and_score_dev(gms_pf *pf, const float *dev_xytheta, const g
     if (refine) {
         if (dev_xytheta) gms_launch_pf_pose_trig(pf, dev_xytheta);                // SLAM.java:90
         if (motion) gms_launch_pf_motion(pf, motion->d_center, motion->d_theta, motion->seed, motion->sequence);
-        gms_launch_pf_refine(pf, dev_beams, B, B);                                // :96-97
+        gms_launch_pf_refine(pf, dev_beams, B, beam_stride);                      // :96-97
         dev_xytheta = nullptr;
         motion = nullptr;
     }
-    gms_launch_pf_score(pf, dev_beams, B, B, dev_xytheta, motion);                // (a motion-model sample rides in the scoring launch)
+    gms_launch_pf_score(pf, dev_beams, B, beam_stride, dev_xytheta, motion);      // (a motion-model sample rides in the scoring launch)
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
 
-int gms_pf_score_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B) {
-    return set_poses_and_score_dev(pf, nullptr, dev_beams, B);
+static int pf_score(gms_pf *pf, const ScanIn &in) {                      // GridMap.java:261-294 x N
+    REQUIRE(pf, "null filter");
+    ScanDev d;
+    int rc = scan_beams(pf->map, in, &d);
+    return rc ? rc : set_poses_and_score_dev(pf, nullptr, d.beams, in.B, d.beam_stride);
 }
+int gms_pf_score(gms_pf *pf, const gms_beam *beams, int32_t B) { return pf_score(pf, host_scan(beams, B, nullptr)); }
+int gms_pf_score_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B) { return pf_score(pf, dev_scan(dev_beams, B, B, nullptr)); }
 
 int gms_pf_set_poses_dev(gms_pf *pf, const float *dev_xytheta) {
     REQUIRE(pf && dev_xytheta, "null argument");
@@ -1106,8 +1089,8 @@ int gms_pf_get_stats(gms_pf *pf, gms_pf_stats *stats) {
 
 int gms_pf_normalize(gms_pf *pf, gms_pf_stats *stats) {                 // SLAM.java:87-129
     REQUIRE(pf, "null filter");
-    if (pf->offset != 0 || pf->n_global != pf->n)
-        return fail(GMS_ERR_STATE, "sharded filter: use gms_pf_local_partials / apply_partials / import_global");
+    if (pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "sharded filter: use gms_pf_local_partials / apply_partials / import_global");
     HIPCHK(hipSetDevice(pf->map->device));
     if (pf->reference_order) {                         // the audit path: one lane, the reference's own loops
         gms_launch_pf_combine(pf);
@@ -1178,8 +1161,8 @@ int gms_pf_import_global(gms_pf *pf, const void *dev_packed_global) {
 // make d_global describe the current particles (stand-alone filters only)
 static int ensure_global(gms_pf *pf) {
     if (pf->have_global) return GMS_OK;
-    if (pf->offset != 0 || pf->n_global != pf->n)
-        return fail(GMS_ERR_STATE, "sharded filter: all-gather the packed particles and call gms_pf_import_global first");
+    if (pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "sharded filter: all-gather the packed particles and call gms_pf_import_global first");
     gms_launch_pf_combine(pf);
     gms_launch_pf_pack(pf, pf->d_global_own);
     pf_source_replaced(pf, pf->d_global_own, 0);
@@ -1193,8 +1176,8 @@ int gms_pf_weighted_pose(gms_pf *pf, float *out) {                      // SLAM.
     if (!pf->stats_current) {
         // the particles changed since the last normalise (resample, set_poses, ...): the reference
         // recomputes the pose from whatever the particles are now (J/app/GridMapApp.java:192)
-        if (pf->offset != 0 || pf->n_global != pf->n)
-            return fail(GMS_ERR_STATE, "sharded filter: gms_pf_local_partials -> all-reduce -> gms_pf_stats_from_partials first");
+        if (pf_is_shard(pf))
+            return gms_fail(GMS_ERR_STATE, "sharded filter: gms_pf_local_partials -> all-reduce -> gms_pf_stats_from_partials first");
         if (pf->reference_order) {
             gms_launch_pf_combine(pf);
             gms_launch_pf_normalize_seq(pf, pf->d_stats + pf->n_maps, false);
@@ -1237,11 +1220,10 @@ static int commit_r01(gms_pf *pf) {
 
 static int do_resample(gms_pf *pf, const double *r01, double fraction, int32_t *indices, int32_t *n_ambiguous) {
     REQUIRE(pf && r01, "null argument");
-    if (pf->slam_owned && !pf->d_epoch2)
-        return fail(GMS_ERR_STATE, "this filter's particles own maps (gms_slam): resample through gms_slam_resample_maps[_if], update through gms_slam_update_per_particle");
+    int rc = refuse_owned_maps(pf);
+    if (rc) return rc;
     gms_map *m = pf->map;
     HIPCHK(hipSetDevice(m->device));
-    int rc = GMS_OK;
     if (!pf->reference_order) rc = ensure_global(pf);
     else gms_launch_pf_combine(pf);
     if (rc) return rc;
@@ -1301,11 +1283,11 @@ static int paired_likelihood_resample(gms_pf *pf, const double *r01, double frac
 // call on device-resident inputs: poses := dev_xytheta (the motion-model samples), weights, bookkeeping,
 // conditional resample, map update at the weighted pose, likelihood rebuild.  Nothing is read back.
 static int slam_update_impl(gms_pf *pf, const float *dev_xytheta, const MotionModel *motion, const gms_beam *dev_beams, int32_t B,
-                            const double *r01, double resample_fraction, int32_t integrate);
+                            int32_t beam_stride, const double *r01, double resample_fraction, int32_t integrate);
 
 int gms_slam_update_dev(gms_pf *pf, const float *dev_xytheta, const gms_beam *dev_beams, int32_t B, const double *r01,
                         double resample_fraction, int32_t integrate) {
-    return slam_update_impl(pf, dev_xytheta, nullptr, dev_beams, B, r01, resample_fraction, integrate);
+    return slam_update_impl(pf, dev_xytheta, nullptr, dev_beams, B, B, r01, resample_fraction, integrate);
 }
 
 // SLAM.update(z, u) with its motion-model sample inside (SLAM.java:80-131, :90 included) + the caller's resampling rule: the
@@ -1315,38 +1297,43 @@ int gms_slam_update_u_dev(gms_pf *pf, double d_center, double d_theta, uint64_t 
                           int32_t B, const double *r01, double resample_fraction, int32_t integrate) {
     MotionModel mo;
     mo.d_center = d_center; mo.d_theta = d_theta; mo.seed = seed; mo.sequence = sequence;
-    return slam_update_impl(pf, nullptr, &mo, dev_beams, B, r01, resample_fraction, integrate);
+    return slam_update_impl(pf, nullptr, &mo, dev_beams, B, B, r01, resample_fraction, integrate);
 }
 
+// dev_beams: [n_maps][beam_stride]
 static int slam_update_impl(gms_pf *pf, const float *dev_xytheta, const MotionModel *motion, const gms_beam *dev_beams, int32_t B,
-                            const double *r01, double resample_fraction, int32_t integrate) {
+                            int32_t beam_stride, const double *r01, double resample_fraction, int32_t integrate) {
     REQUIRE(pf && dev_beams && r01, "null argument");
-    if (pf->slam_owned && !pf->d_epoch2)
-        return fail(GMS_ERR_STATE, "this filter's particles own maps (gms_slam): resample through gms_slam_resample_maps[_if], update through gms_slam_update_per_particle");
+    int rc = refuse_owned_maps(pf);
+    if (rc) return rc;
     gms_map *m = pf->map;
-    if (pf->offset != 0 || pf->n_global != pf->n)
-        return fail(GMS_ERR_STATE, "sharded filter: the collectives belong to the caller (see distributed.py)");
-    int rc = GMS_OK;
-    rc = set_poses_and_score_dev(pf, dev_xytheta, dev_beams, B, pf->refine != 0, motion);   // SLAM.java:90, :96-97, :99
-    if (!rc && integrate && !pf->reference_order && gms_can_pair_launches(pf, B)) {
+    if (pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "sharded filter: the collectives belong to the caller (see distributed.py)");
+    const ScanIn at_pose = dev_scan(dev_beams, B, beam_stride, nullptr, pf, 0);     // the map update at the weighted pose
+    rc = set_poses_and_score_dev(pf, dev_xytheta, dev_beams, B, beam_stride, pf->refine != 0, motion);   // SLAM.java:90, :96-97, :99
+    // The two paired branches read the beams at stride B (gms_launch_norm_raycast, and the batched branch's ray cast): only then.
+    const bool pair = !rc && integrate && !pf->reference_order && beam_stride == B;
+    if (pair && gms_can_pair_launches(pf, B)) {
         // The weight branch and the map branch are independent once the partials exist: they share launches
         // (gms_fused_kernels.hip).  (Two streams were measured: the event fork/join costs more than it hides.)
         gms_launch_partials_apply(pf, pf->d_partials, true);                              // :100-115
         gms_launch_norm_raycast(pf, pf->d_partials, pf->d_global_own, true, dev_beams, B);   // :120-124 | :93 | previous scan's :223
         return paired_likelihood_resample(pf, r01, resample_fraction);           // :105 | GridMapApp.java:185-186
     }
-    if (!rc && integrate && !pf->reference_order && pf->n_maps > 1 && B > 0 && !m->need_full_build && m->pair_launches) {
+    if (pair && pf->n_maps > 1 && B > 0 && !m->need_full_build && m->pair_launches) {
         // batched maps: the ray cast runs 16 rays per workgroup (1024 threads), so only the other two pairs apply:
         // [partials | previous apply] -> normalise -> ray cast -> [likelihood | resample]
         const bool ride = gms_raycast_tiled(m, B);     // the tiled ray cast takes the pending apply pass along
         gms_launch_partials_apply(pf, pf->d_partials, ride);
         gms_launch_pf_apply_partials(pf, pf->d_partials, pf->d_global_own, true);
-        gms_launch_raycast(m, dev_beams, B, B, stats_pose_ptr(pf, 0), (int32_t)(sizeof(PfStatsDev) / sizeof(float)), ride);
+        ScanDev d;
+        scan_pose(m, at_pose, &d);
+        gms_launch_raycast(m, dev_beams, B, B, d.poses, d.pose_stride, ride);
         return paired_likelihood_resample(pf, r01, resample_fraction);
     }
     if (!rc) rc = gms_pf_normalize(pf, nullptr);                                 // :100-124
     if (!rc && resample_fraction >= 0.0) rc = gms_pf_resample_if(pf, r01, resample_fraction);   // GridMapApp.java:185-186
-    if (!rc && integrate) rc = gms_map_update_at_dev(m, dev_beams, B, pf, 0);    // SLAM.java:102-105, :93
+    if (!rc && integrate) rc = map_scan(m, at_pose, SCAN_UPDATE_MAY_DEFER);      // SLAM.java:102-105, :93
     return rc;
 }
 
@@ -1358,9 +1345,9 @@ int gms_slam_frame(gms_pf *pf, const double *angle, const double *distance, cons
                    double d_theta, uint64_t seed, uint64_t sequence, const double *r01, double resample_fraction, int32_t integrate) {
     REQUIRE(pf && angle && distance && hit && r01, "null argument");
     gms_map *m = pf->map;
-    if (pf->n_maps != 1) return fail(GMS_ERR_STATE, "gms_slam_frame: one map per handle (a frame is one robot's revolution)");
-    if (pf->offset != 0 || pf->n_global != pf->n)
-        return fail(GMS_ERR_STATE, "sharded filter: the collectives belong to the caller (see distributed.py)");
+    if (pf->n_maps != 1) return gms_fail(GMS_ERR_STATE, "gms_slam_frame: one map per handle (a frame is one robot's revolution)");
+    if (pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "sharded filter: the collectives belong to the caller (see distributed.py)");
     REQUIRE(length > 0 && length <= m->max_beams, "measurement count exceeds gms_params.max_beams");
     REQUIRE((size_t)length * 17 + 16 <= (size_t)m->n_maps * m->max_beams * sizeof(gms_beam), "scan too long for the staging buffer");
     HIPCHK(hipSetDevice(m->device));
@@ -1378,34 +1365,22 @@ int gms_slam_frame(gms_pf *pf, const double *angle, const double *distance, cons
     return gms_slam_update_dev(pf, nullptr, m->d_beams, length, r01, resample_fraction, integrate);
 }
 
+// the host inputs of a scan step: the poses (may be NULL) into the filter, the beams into the map's staging buffer
+static int stage_step(gms_pf *pf, const float *xytheta, const gms_beam *beams, int32_t B, ScanDev *d) {
+    int rc = xytheta ? gms_pf_set_poses(pf, xytheta) : GMS_OK;
+    return rc ? rc : scan_beams(pf->map, host_scan(beams, B, nullptr), d);
+}
+
 // The same with host-resident inputs (what a JNI caller has): one staging copy of the scan, one of the poses.
 int gms_slam_update(gms_pf *pf, const float *xytheta, const gms_beam *beams, int32_t B, const double *r01,
                     double resample_fraction, int32_t integrate, gms_pf_stats *stats) {
     REQUIRE(pf && beams && r01, "null argument");
-    gms_map *m = pf->map;
-    if (pf->offset != 0 || pf->n_global != pf->n)
-        return fail(GMS_ERR_STATE, "sharded filter: the collectives belong to the caller (see distributed.py)");
-    int rc = GMS_OK;
-    const int32_t stride_ok = (m->n_maps == 1) || (B == m->max_beams);
-    if (xytheta) rc = gms_pf_set_poses(pf, xytheta);
-    if (!rc) rc = stage_beams(m, beams, B);
-    const gms_beam *d = m->d_beams;
-    if (!rc && !stride_ok) {
-        // batched handles stage [n_maps][max_beams]; the *_dev entry points expect [n_maps][B]: go through the
-        // staging-stride launchers instead
-        if (pf->refine) gms_launch_pf_refine(pf, m->d_beams, B, m->max_beams);
-        gms_launch_pf_score(pf, m->d_beams, B, m->max_beams);
-        rc = gms_pf_normalize(pf, nullptr);
-        if (!rc && resample_fraction >= 0.0) rc = gms_pf_resample_if(pf, r01, resample_fraction);
-        if (!rc && integrate) {
-            gms_ensure_lik(m);
-            gms_launch_raycast(m, m->d_beams, B, m->max_beams, stats_pose_ptr(pf, 0), (int32_t)(sizeof(PfStatsDev) / sizeof(float)));
-            gms_launch_apply_counts(m);
-            rc = finish_likelihood(m, m->need_full_build ? 0 : 1);
-        }
-    } else if (!rc) {
-        rc = gms_slam_update_dev(pf, nullptr, d, B, r01, resample_fraction, integrate);
-    }
+    if (pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "sharded filter: the collectives belong to the caller (see distributed.py)");
+    ScanDev d;
+    int rc = stage_step(pf, xytheta, beams, B, &d);
+    // (one map's staged beams are [B]: read at stride B, the step may pair its launches)
+    if (!rc) rc = slam_update_impl(pf, nullptr, nullptr, d.beams, B, pf->n_maps == 1 ? B : d.beam_stride, r01, resample_fraction, integrate);
     if (!rc && stats) rc = gms_pf_get_stats(pf, stats);
     return rc;
 }
@@ -1447,18 +1422,18 @@ int gms_pf_did_resample(gms_pf *pf, int32_t *flags) {
 
 int gms_pf_set_log_normalize(gms_pf *pf, int32_t on) {
     REQUIRE(pf, "null filter");
-    if (on && (pf->offset != 0 || pf->n_global != pf->n))
-        return fail(GMS_ERR_STATE, "gms_pf_set_log_normalize: stand-alone filters only (a shard does not know the other shards' largest log-weight)");
-    if (on && pf->reference_order) return fail(GMS_ERR_STATE, "gms_pf_set_log_normalize: the reference-order audit path is on (gms_pf_set_reference_order)");
+    if (on && pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "gms_pf_set_log_normalize: stand-alone filters only (a shard does not know the other shards' largest log-weight)");
+    if (on && pf->reference_order) return gms_fail(GMS_ERR_STATE, "gms_pf_set_log_normalize: the reference-order audit path is on (gms_pf_set_reference_order)");
     pf->log_norm = on ? 1 : 0;
     return GMS_OK;
 }
 
 int gms_pf_set_reference_order(gms_pf *pf, int32_t on) {
     REQUIRE(pf, "null filter");
-    if (on && (pf->offset != 0 || pf->n_global != pf->n))
-        return fail(GMS_ERR_STATE, "gms_pf_set_reference_order: stand-alone filters only (the audit path adds up on ONE lane of ONE device)");
-    if (on && pf->log_norm) return fail(GMS_ERR_STATE, "gms_pf_set_reference_order: log-normalisation is on (not the reference's arithmetic): turn it off first");
+    if (on && pf_is_shard(pf))
+        return gms_fail(GMS_ERR_STATE, "gms_pf_set_reference_order: stand-alone filters only (the audit path adds up on ONE lane of ONE device)");
+    if (on && pf->log_norm) return gms_fail(GMS_ERR_STATE, "gms_pf_set_reference_order: log-normalisation is on (not the reference's arithmetic): turn it off first");
     pf->reference_order = on ? 1 : 0;
     pf_particles_changed(pf);
     return GMS_OK;
@@ -1489,10 +1464,10 @@ int gms_pf_last_step(gms_pf *pf, float *weighted_pose, float *strongest_pose, in
 
 int gms_pf_refine_poses(gms_pf *pf, const gms_beam *beams, int32_t B) {   // GridMap.java:319-346
     REQUIRE(pf, "null filter");
-    gms_map *m = pf->map;
-    int rc = stage_beams(m, beams, B);
+    ScanDev d;
+    int rc = scan_beams(pf->map, host_scan(beams, B, nullptr), &d);
     if (rc) return rc;
-    gms_launch_pf_refine(pf, m->d_beams, B, m->max_beams);
+    gms_launch_pf_refine(pf, d.beams, B, d.beam_stride);
     pf_particles_changed(pf);
     HIPCHK(hipGetLastError());
     return GMS_OK;
@@ -1527,7 +1502,7 @@ static struct {
 #define RCCLCHK(expr)                                                                                              \
     do {                                                                                                           \
         int r_ = (expr);                                                                                           \
-        if (r_ != 0) return fail(GMS_ERR_HIP, "%s: %s", #expr, g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error"); \
+        if (r_ != 0) return gms_fail(GMS_ERR_HIP, "%s: %s", #expr, g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error"); \
     } while (0)
 
 int gms_comm_load(const char *librccl_path) {
@@ -1541,7 +1516,7 @@ int gms_comm_load(const char *librccl_path) {
         for (const char *nm : names) if (!dl) dl = dlopen(nm, RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);
         for (const char *nm : names) if (!dl) dl = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
     }
-    if (!dl) return fail(GMS_ERR_STATE, "RCCL not found: %s", dlerror());
+    if (!dl) return gms_fail(GMS_ERR_STATE, "RCCL not found: %s", dlerror());
     *(void **)&g_rccl.GetUniqueId = dlsym(dl, "ncclGetUniqueId");
     *(void **)&g_rccl.CommInitRank = dlsym(dl, "ncclCommInitRank");
     *(void **)&g_rccl.CommDestroy = dlsym(dl, "ncclCommDestroy");
@@ -1554,7 +1529,7 @@ int gms_comm_load(const char *librccl_path) {
     *(void **)&g_rccl.GetErrorString = dlsym(dl, "ncclGetErrorString");
     if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.CommDestroy || !g_rccl.AllReduce || !g_rccl.AllGather ||
         !g_rccl.GroupStart || !g_rccl.GroupEnd)
-        return fail(GMS_ERR_STATE, "RCCL library lacks the collective entry points");
+        return gms_fail(GMS_ERR_STATE, "RCCL library lacks the collective entry points");
     g_rccl.dl = dl;
     return GMS_OK;
 }
@@ -1583,11 +1558,11 @@ int gms_comm_create(gms_comm **out, const void *id128, int32_t rank, int32_t wor
     rccl_unique_id id;
     memcpy(&id, id128, sizeof(id));
     int r = g_rccl.CommInitRank(&c->nccl, world, id, rank);        // blocks until every rank has joined
-    if (r != 0) { delete c; return fail(GMS_ERR_HIP, "ncclCommInitRank: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "error"); }
+    if (r != 0) { delete c; return gms_fail(GMS_ERR_HIP, "ncclCommInitRank: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "error"); }
     hipError_t e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
-    if (e != hipSuccess) { gms_comm_destroy(c); return fail(GMS_ERR_HIP, "communicator streams: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { gms_comm_destroy(c); return gms_fail(GMS_ERR_HIP, "communicator streams: %s", hipGetErrorString(e)); }
     *out = c;
     return GMS_OK;
 }
@@ -1610,13 +1585,13 @@ int gms_comm_rank(const gms_comm *c, int32_t *rank, int32_t *world) {
 }
 
 static int check_shard(const gms_pf *pf, const gms_comm *c) {
-    if (pf->n_maps != 1) return fail(GMS_ERR_STATE, "sharded filters hold one map per handle");
+    if (pf->n_maps != 1) return gms_fail(GMS_ERR_STATE, "sharded filters hold one map per handle");
     if (pf->n_global != (int64_t)pf->n * c->world || pf->offset != (int64_t)pf->n * c->rank)
-        return fail(GMS_ERR_INVALID, "shard mismatch: n_local %d offset %lld n_global %lld on rank %d of %d (equal shards, rank order)",
-                    pf->n, (long long)pf->offset, (long long)pf->n_global, c->rank, c->world);
+        return gms_fail(GMS_ERR_INVALID, "shard mismatch: n_local %d offset %lld n_global %lld on rank %d of %d (equal shards, rank order)",
+                        pf->n, (long long)pf->offset, (long long)pf->n_global, c->rank, c->world);
     if (c->world > 1 && pf->n % GMS_BLOCK)
-        return fail(GMS_ERR_INVALID, "shard size %d must be a multiple of GMS_BLOCK=%d", pf->n, GMS_BLOCK);
-    if (pf->map->device != c->device) return fail(GMS_ERR_INVALID, "filter and communicator are on different devices");
+        return gms_fail(GMS_ERR_INVALID, "shard size %d must be a multiple of GMS_BLOCK=%d", pf->n, GMS_BLOCK);
+    if (pf->map->device != c->device) return gms_fail(GMS_ERR_INVALID, "filter and communicator are on different devices");
     return GMS_OK;
 }
 
@@ -1628,8 +1603,8 @@ int gms_pf_normalize_sharded_begin(gms_pf *pf, gms_comm *c) {
     if (rc) return rc;
     gms_map *m = pf->map;
     HIPCHK(hipSetDevice(m->device));
-    if (c->broken) return fail(GMS_ERR_STATE, "communicator is broken (an earlier exchange failed): destroy it");
-    if (c->pending) return fail(GMS_ERR_STATE, "gms_pf_normalize_sharded_end has not been called for the previous exchange");
+    if (c->broken) return gms_fail(GMS_ERR_STATE, "communicator is broken (an earlier exchange failed): destroy it");
+    if (c->pending) return gms_fail(GMS_ERR_STATE, "gms_pf_normalize_sharded_end has not been called for the previous exchange");
     const size_t np = (size_t)nblk_of(pf->n_global) * GMS_PARTIAL_STRIDE;
     gms_launch_pf_partials(pf, pf->d_partials);
     RCCLCHK(g_rccl.AllReduce(pf->d_partials, pf->d_partials, np, RCCL_FLOAT64, RCCL_SUM, c->nccl, m->stream));
@@ -1651,7 +1626,7 @@ int gms_pf_normalize_sharded_begin(gms_pf *pf, gms_comm *c) {
 // joins the exchange: the gathered population becomes the resampling source
 int gms_pf_normalize_sharded_end(gms_pf *pf, gms_comm *c) {
     REQUIRE(pf && c, "null argument");
-    if (!c->pending) return fail(GMS_ERR_STATE, "no exchange in flight");
+    if (!c->pending) return gms_fail(GMS_ERR_STATE, "no exchange in flight");
     gms_map *m = pf->map;
     HIPCHK(hipSetDevice(m->device));
     if (c->overlap) HIPCHK(hipStreamWaitEvent(m->stream, c->ev_join, 0));
@@ -1668,15 +1643,15 @@ int gms_pf_normalize_sharded_end(gms_pf *pf, gms_comm *c) {
 // launch, and everything after it is local: fold, normalise own, cumulative sums of the normalised global weights
 // (the owner's division, w / weightSum, repeated on the gathered copy: same operands, same bits), ray cast, resample.
 static int sharded_shape_ok(const gms_pf *pf) {
-    if (pf->n_maps != 1) return fail(GMS_ERR_STATE, "sharded filters hold one map per handle");
-    if (pf->reference_order) return fail(GMS_ERR_STATE, "gms_pf_set_reference_order is on: stand-alone scan steps only");
+    if (pf->n_maps != 1) return gms_fail(GMS_ERR_STATE, "sharded filters hold one map per handle");
+    if (pf->reference_order) return gms_fail(GMS_ERR_STATE, "gms_pf_set_reference_order is on: stand-alone scan steps only");
     if (pf->log_norm)
-        return fail(GMS_ERR_STATE, "gms_pf_set_log_normalize is on: the sharded scan steps exchange raw weights and do not rescale them; turn it off (stand-alone steps only)");
+        return gms_fail(GMS_ERR_STATE, "gms_pf_set_log_normalize is on: the sharded scan steps exchange raw weights and do not rescale them; turn it off (stand-alone steps only)");
     if (pf->n_global != pf->n && pf->n % GMS_BLOCK)
-        return fail(GMS_ERR_INVALID, "shard size %d must be a multiple of GMS_BLOCK=%d", pf->n, GMS_BLOCK);
+        return gms_fail(GMS_ERR_INVALID, "shard size %d must be a multiple of GMS_BLOCK=%d", pf->n, GMS_BLOCK);
     if (pf->n_global % pf->n || pf->offset % pf->n)
-        return fail(GMS_ERR_INVALID, "equal shards in rank order are required (n_local %d, offset %lld, n_global %lld)", pf->n,
-                    (long long)pf->offset, (long long)pf->n_global);
+        return gms_fail(GMS_ERR_INVALID, "equal shards in rank order are required (n_local %d, offset %lld, n_global %lld)", pf->n,
+                        (long long)pf->offset, (long long)pf->n_global);
     return GMS_OK;
 }
 
@@ -1686,7 +1661,7 @@ static int sharded_begin(gms_pf *pf, const float *dev_xytheta, const gms_beam *d
     REQUIRE(pf && dev_beams, "null argument");
     int rc = sharded_shape_ok(pf);
     if (rc) return rc;
-    rc = set_poses_and_score_dev(pf, dev_xytheta, dev_beams, B, pf->refine != 0);   // SLAM.java:90, :96-97, :99
+    rc = set_poses_and_score_dev(pf, dev_xytheta, dev_beams, B, B, pf->refine != 0);   // SLAM.java:90, :96-97, :99
     if (rc) return rc;
     gms_launch_partials_pack_apply(pf, apply_rides_later);                       // :100-115 | previous scan's GridMap.java:223 (unless it rides beside the ray cast)
     HIPCHK(hipGetLastError());
@@ -1731,8 +1706,8 @@ int gms_slam_update_sharded_dev(gms_pf *pf, gms_comm *c, const float *dev_xythet
     gms_map *m = pf->map;
     int rc = check_shard(pf, c);
     if (rc) return rc;
-    if (c->broken) return fail(GMS_ERR_STATE, "communicator is broken (an earlier exchange failed): destroy it");
-    if (c->pending) return fail(GMS_ERR_STATE, "gms_pf_normalize_sharded_end has not been called for the previous exchange");
+    if (c->broken) return gms_fail(GMS_ERR_STATE, "communicator is broken (an earlier exchange failed): destroy it");
+    if (c->pending) return gms_fail(GMS_ERR_STATE, "gms_pf_normalize_sharded_end has not been called for the previous exchange");
     rc = sharded_begin(pf, dev_xytheta, dev_beams, B, integrate && gms_can_pair_launches(pf, B));
     if (rc) return rc;
     const size_t np = (size_t)nblk_of(pf->n) * GMS_PARTIAL_STRIDE;               // doubles per rank
@@ -1770,8 +1745,8 @@ int gms_slam_update_sharded_dev(gms_pf *pf, gms_comm *c, const float *dev_xythet
         // the begin half may have consumed a deferred apply pass; bring the map to a defined state for the fallback route
         gms_flush_apply(m);
         const int r_ = first ? first : end;
-        return fail(GMS_ERR_HIP, "%s: %s (communicator marked broken)", first ? what : "ncclGroupEnd",
-                    g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error");
+        return gms_fail(GMS_ERR_HIP, "%s: %s (communicator marked broken)", first ? what : "ncclGroupEnd",
+                        g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error");
     }
     return gms_slam_update_sharded_end_dev(pf, dev_beams, B, r01, resample_fraction, integrate);
 }
@@ -1779,12 +1754,10 @@ int gms_slam_update_sharded_dev(gms_pf *pf, gms_comm *c, const float *dev_xythet
 int gms_slam_update_sharded(gms_pf *pf, gms_comm *c, const float *xytheta, const gms_beam *beams, int32_t B, const double *r01,
                             double resample_fraction, int32_t integrate, gms_pf_stats *stats) {
     REQUIRE(pf && c && beams && r01, "null argument");
-    gms_map *m = pf->map;
-    REQUIRE(m->n_maps == 1, "sharded filters hold one map per handle");
-    int rc = GMS_OK;
-    if (xytheta) rc = gms_pf_set_poses(pf, xytheta);
-    if (!rc) rc = stage_beams(m, beams, B);
-    if (!rc) rc = gms_slam_update_sharded_dev(pf, c, nullptr, m->d_beams, B, r01, resample_fraction, integrate);
+    REQUIRE(pf->n_maps == 1, "sharded filters hold one map per handle");
+    ScanDev d;
+    int rc = stage_step(pf, xytheta, beams, B, &d);
+    if (!rc) rc = gms_slam_update_sharded_dev(pf, c, nullptr, d.beams, B, r01, resample_fraction, integrate);
     if (!rc && stats) rc = gms_pf_get_stats(pf, stats);
     return rc;
 }
@@ -1860,7 +1833,7 @@ int gms_slam_resample_sharded_maps(gms_slam *s, gms_comm *c, double r01, double 
     gms_map *m = s->map;
     int rc = check_shard(pf, c);
     if (rc) return rc;
-    if (c->broken) return fail(GMS_ERR_STATE, "communicator is broken (an earlier exchange failed): destroy it");
+    if (c->broken) return gms_fail(GMS_ERR_STATE, "communicator is broken (an earlier exchange failed): destroy it");
     HIPCHK(hipSetDevice(m->device));
     const int32_t n = pf->n, world = c->world;
     std::vector<int32_t> src((size_t)n), all((size_t)n * world);
@@ -1876,20 +1849,20 @@ int gms_slam_resample_sharded_maps(gms_slam *s, gms_comm *c, double r01, double 
     int32_t *d_all = nullptr;
     double *d_send = nullptr, *d_recv = nullptr;
     auto cleanup = [&]() { hipFree(d_all); hipFree(d_send); hipFree(d_recv); };
-    if (hipMalloc(&d_all, (size_t)n * world * sizeof(int32_t)) != hipSuccess) return fail(GMS_ERR_NOMEM, "gms_slam_resample_sharded_maps: device allocation failed");
+    if (hipMalloc(&d_all, (size_t)n * world * sizeof(int32_t)) != hipSuccess) return gms_fail(GMS_ERR_NOMEM, "gms_slam_resample_sharded_maps: device allocation failed");
     {
         const int r_ = g_rccl.AllGather(pf->d_idx, d_all, (size_t)n * sizeof(int32_t), RCCL_INT8, c->nccl, m->stream);
-        if (r_ != 0) { c->broken = 1; cleanup(); return fail(GMS_ERR_HIP, "ncclAllGather (sources): %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error"); }
+        if (r_ != 0) { c->broken = 1; cleanup(); return gms_fail(GMS_ERR_HIP, "ncclAllGather (sources): %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error"); }
     }
     if (hipStreamSynchronize(m->stream) != hipSuccess ||
-        hipMemcpy(all.data(), d_all, (size_t)n * world * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { cleanup(); return fail(GMS_ERR_HIP, "gms_slam_resample_sharded_maps: reading the sources back failed"); }
+        hipMemcpy(all.data(), d_all, (size_t)n * world * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { cleanup(); return gms_fail(GMS_ERR_HIP, "gms_slam_resample_sharded_maps: reading the sources back failed"); }
     std::vector<int32_t> send_counts((size_t)world), send_lists((size_t)world * n), recv_counts((size_t)world), src_local((size_t)n), recv_pos((size_t)n);
     rc = gms_slam_plan_exchange(all.data(), world, c->rank, n, send_counts.data(), send_lists.data(), recv_counts.data(), src_local.data(), recv_pos.data());
     if (rc) { cleanup(); return rc; }
     int64_t n_send = 0, n_recv = 0;
     for (int32_t q = 0; q < world; q++) { n_send += send_counts[q]; n_recv += recv_counts[q]; }
-    if (n_send && hipMalloc(&d_send, (size_t)n_send * rec * sizeof(double)) != hipSuccess) { cleanup(); return fail(GMS_ERR_NOMEM, "gms_slam_resample_sharded_maps: %lld records to send do not fit", (long long)n_send); }
-    if (n_recv && hipMalloc(&d_recv, (size_t)n_recv * rec * sizeof(double)) != hipSuccess) { cleanup(); return fail(GMS_ERR_NOMEM, "gms_slam_resample_sharded_maps: %lld records to receive do not fit", (long long)n_recv); }
+    if (n_send && hipMalloc(&d_send, (size_t)n_send * rec * sizeof(double)) != hipSuccess) { cleanup(); return gms_fail(GMS_ERR_NOMEM, "gms_slam_resample_sharded_maps: %lld records to send do not fit", (long long)n_send); }
+    if (n_recv && hipMalloc(&d_recv, (size_t)n_recv * rec * sizeof(double)) != hipSuccess) { cleanup(); return gms_fail(GMS_ERR_NOMEM, "gms_slam_resample_sharded_maps: %lld records to receive do not fit", (long long)n_recv); }
     int64_t off = 0;
     for (int32_t q = 0; q < world && !rc; q++) {
         if (!send_counts[q]) continue;
@@ -1898,7 +1871,7 @@ int gms_slam_resample_sharded_maps(gms_slam *s, gms_comm *c, double r01, double 
     }
     if (rc) { cleanup(); return rc; }
     if (n_send || n_recv) {
-        if (!g_rccl.Send || !g_rccl.Recv) { cleanup(); return fail(GMS_ERR_STATE, "this RCCL has no ncclSend / ncclRecv"); }
+        if (!g_rccl.Send || !g_rccl.Recv) { cleanup(); return gms_fail(GMS_ERR_STATE, "this RCCL has no ncclSend / ncclRecv"); }
         int first = 0, end = 0;
         const char *what = "";
         {
@@ -1922,8 +1895,8 @@ int gms_slam_resample_sharded_maps(gms_slam *s, gms_comm *c, double r01, double 
             hipStreamSynchronize(m->stream);
             cleanup();
             const int r_ = first ? first : end;
-            return fail(GMS_ERR_HIP, "%s: %s (communicator marked broken; the maps of this generation are incomplete)", first ? what : "ncclGroupEnd",
-                        g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error");
+            return gms_fail(GMS_ERR_HIP, "%s: %s (communicator marked broken; the maps of this generation are incomplete)", first ? what : "ncclGroupEnd",
+                            g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error");
         }
     }
     rc = gms_slam_shard_gather(s, src_local.data(), recv_pos.data(), d_recv);

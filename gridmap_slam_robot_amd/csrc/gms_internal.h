@@ -241,6 +241,8 @@ struct gms_pf {
 };
 
 // ---- filter state transitions: each is named for what happened and sets every field that event affects ----
+// one rank's block of a filter spread over several (gms_pf_set_shard), not a stand-alone filter
+static inline bool pf_is_shard(const gms_pf *pf) { return pf->offset != 0 || pf->n_global != pf->n; }
 // the poses changed (host, motion model, refinement) or how they are weighed did: the source and the statistics are stale
 static inline void pf_particles_changed(gms_pf *pf) { pf->have_global = 0; pf->stats_current = 0; }
 // a scoring launch wrote new weights: nseg > 1 segment products per particle, or the combined product (nseg <= 1)
@@ -344,6 +346,15 @@ struct gms_slam {
 
 // the thread's last-error text + code (gms_host.hip); every C-ABI file reports through it
 int gms_fail(int code, const char *fmt, ...);
+#define HIPCHK(expr)                                                                                  \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) return gms_fail(GMS_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
+#define REQUIRE(cond, msg)                                         \
+    do {                                                           \
+        if (!(cond)) return gms_fail(GMS_ERR_INVALID, "%s", msg);  \
+    } while (0)
 // host beams [n_maps][B] -> the map's device staging buffer [n_maps][max_beams] through the pinned ring (gms_host.hip)
 int gms_stage_beams(gms_map *m, const gms_beam *beams, int32_t B);
 

@@ -8,16 +8,6 @@
 
 #include "gms_internal.h"
 
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return gms_fail(GMS_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-#define REQUIRE(cond, msg)                                         \
-    do {                                                           \
-        if (!(cond)) return gms_fail(GMS_ERR_INVALID, "%s", msg);  \
-    } while (0)
-
 SlamBufs gms_slam_bufs(const gms_slam *s) {
     SlamBufs b;
     for (int k = 0; k < 2; k++) { b.log[k] = s->d_log[k]; b.lik[k] = s->d_lik[k]; b.code[k] = s->d_code[k]; }
@@ -214,7 +204,7 @@ static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, 
 int gms_slam_update_per_particle_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                                      uint64_t seed, uint64_t sequence, gms_pf_stats *stats) {
     REQUIRE(s, "null handle");
-    if (s->pf->offset != 0 || s->pf->n_global != s->pf->n)
+    if (pf_is_shard(s->pf))
         return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_update_local_dev, then the weight exchange (gms_pf_local_partials / apply_partials / import_global)");
     int rc = slam_update_local(s, dev_beams, B, sample_motion, d_center, d_theta, seed, sequence);
     if (rc) return rc;
@@ -291,7 +281,7 @@ static int slam_resample(gms_slam *s, double r01, double fraction, int32_t *indi
 
 int gms_slam_resample_maps(gms_slam *s, double r01, int32_t *indices, int32_t *n_ambiguous) {
     REQUIRE(s, "null handle");
-    if (s->pf->offset != 0 || s->pf->n_global != s->pf->n)
+    if (pf_is_shard(s->pf))
         return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_shard_draw / export / gather move its maps (the sources may live on other ranks)");
     return slam_resample(s, r01, -1.0, indices, n_ambiguous);
 }
@@ -363,7 +353,7 @@ int gms_slam_shard_gather(gms_slam *s, const int32_t *src_local, const int32_t *
 
 int gms_slam_resample_maps_if(gms_slam *s, double r01, double fraction) {
     REQUIRE(s, "null handle");
-    if (s->pf->offset != 0 || s->pf->n_global != s->pf->n)
+    if (pf_is_shard(s->pf))
         return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_shard_draw / export / gather move its maps (the sources may live on other ranks)");
     REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if: fraction must be non-negative");
     return slam_resample(s, r01, fraction, nullptr, nullptr);
