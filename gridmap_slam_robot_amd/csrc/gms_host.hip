@@ -602,6 +602,22 @@ static int stage_beams(gms_map *m, const gms_beam *beams, int32_t B) {
 
 }  // extern "C"
 int gms_stage_beams(gms_map *m, const gms_beam *beams, int32_t B) { return stage_beams(m, beams, B); }
+int gms_stage_block(gms_map *m, StageRing &ring, const gms_beam *beams, int32_t B, int32_t rows, int32_t pitch, const void *tab, size_t tab_bytes,
+                    void *dst) {
+    HIPCHK(hipSetDevice(m->device));
+    void *slot = nullptr;
+    int rc = ring_acquire(ring, &slot);
+    if (rc) return rc;
+    gms_beam *h = static_cast<gms_beam *>(slot);
+    const size_t beam_bytes = beams ? (size_t)rows * pitch * sizeof(gms_beam) : 0;
+    if (beams)
+        for (int32_t r = 0; r < rows; r++) memcpy(h + (size_t)r * pitch, beams + (size_t)r * B, (size_t)B * sizeof(gms_beam));
+    if (tab_bytes) memcpy(reinterpret_cast<unsigned char *>(slot) + beam_bytes, tab, tab_bytes);
+    gms_launch_copy(m, dst, slot, beam_bytes + tab_bytes);      // (16-byte multiples: gms_beam and the tables that ride behind it)
+    return ring_commit(ring, m->stream);
+}
+int gms_ring_alloc(StageRing &r, size_t bytes) { return ring_alloc(r, bytes); }
+void gms_ring_free(StageRing &r) { ring_free(r); }
 extern "C" {
 
 static int stage_poses(gms_map *m, const float *poses) {

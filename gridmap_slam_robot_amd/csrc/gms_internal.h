@@ -313,10 +313,26 @@ struct gms_comm {
 // fact: resample() writes its deep copies into the other one, and `if (neff < n / 2) resample()` (GridMapApp.java:185-186) is decided on
 // the device, so the host cannot know without a round trip.  epoch[0] counts the draws that ran (kept by the resampling kernels,
 // gms_pf::d_epoch2): its parity is the current generation; epoch[1] says whether the last resample() drew.
+// A batched handle (gms_params.n_maps = S filters of n_per particles each, particle p of filter p / n_per) keeps one such pair per
+// filter: epoch[2 f], epoch[2 f + 1].
 struct SlamBufs {
     double *log[2], *lik[2];        // [n][H][W]
     uint32_t *code[2];              // [n][2][code_words] class planes, or NULL
-    int32_t *epoch;
+    int32_t *epoch;                 // [S][2]
+    int32_t n_per;                  // particles per filter
+};
+// one filter of a batched update (gms_slam_update_batch): a table of S of them travels with the scans' beams, in the same copy
+struct SlamFilterArgs {
+    double d_center, d_theta, d_center_sd, d_theta_sd;     // its odometry and the motion model's deviations (Odometry.java:63-64)
+    uint64_t seed;
+    int32_t count;                  // beams of its scan
+    int32_t flags;                  // bit 0: draw the motion-model sample (SLAM.java:90); bit 1: integrate the scan (not skipUpdate, :82)
+};
+static_assert(sizeof(SlamFilterArgs) % 16 == 0, "the table is staged behind the beams in 16-byte units");
+// the update kernels' view of a batch: filter f = particle / n reads beams + f * beam_stride and tab[f] (tab NULL: not batched)
+struct SlamBatch {
+    const SlamFilterArgs *tab;
+    int32_t n, beam_stride;
 };
 
 // SLAM as the reference has it (J/slam/SLAM.java): N particles, each with its own GridMapData (gms_slam_host.hip, gms_slam_kernels.hip)
@@ -324,10 +340,14 @@ struct gms_slam {
     gms_map *map;                   // ONE map's worth of handle: the GridMap (geometry, constants, taps), the stream, staging, profiling; its own
                                     // logData / likelihoodData receive the combined map (gms_slam_combined, GridMapApp.calculateCombined)
     gms_pf *pf;                     // the N particles' poses, weights, statistics and resampling indices (one "map" of N particles)
-    int32_t n;
+    int32_t n;                      // particles held: n_filters * n_per, filter f's particle k at f * n_per + k
+    int32_t n_filters;              // independent filters of the handle (gms_params.n_maps): batched entry points only when > 1
+    int32_t n_per;                  // particles per filter
     double *d_log[2], *d_lik[2];    // [n][H][W] every particle's GridMapData, double-buffered for resample()'s deep copies
-    int32_t *d_epoch;               // {draws that ran so far, the last resample() drew}: the current generation is d_epoch[0] & 1 (SlamBufs)
-    int64_t copies_base;            // maps copied by resampling steps before the last reset (the rest: d_epoch[0] * n)
+    int32_t *d_epoch;               // [n_filters] x {draws that ran so far, the last resample() drew}: filter f's current generation is d_epoch[2 f] & 1 (SlamBufs)
+    int64_t copies_base;            // maps copied by resampling steps before the last reset (the rest: sum of d_epoch[2 f] * n_per)
+    gms_beam *d_batch;              // [n_filters][max_beams] beams | [n_filters] SlamFilterArgs: a batched update's inputs (gms_slam_update_batch)
+    StageRing batch_ring;           // pinned staging of that block
     int32_t *d_plan;                // a shard's resample(): [3][n] device staging of {export list | local sources | positions in the received buffer}
     int32_t lazy_lik;               // resample() copies logData at once and likelihoodData when somebody asks for it: the next update's
                                     // computeLikelihoodMap overwrites every cell of it before anything on the path reads one (GMS_SLAM_LAZY_LIK_COPY=0: both at once)
@@ -357,6 +377,12 @@ int gms_fail(int code, const char *fmt, ...);
     } while (0)
 // host beams [n_maps][B] -> the map's device staging buffer [n_maps][max_beams] through the pinned ring (gms_host.hip)
 int gms_stage_beams(gms_map *m, const gms_beam *beams, int32_t B);
+// host beams [rows][B] (or none: beams NULL) -> dst [rows][pitch], then tab_bytes of tab behind them, as ONE copy out of a slot of ring
+// (gms_host.hip; the ring's slots hold rows * pitch beams + tab_bytes)
+int gms_stage_block(gms_map *m, StageRing &ring, const gms_beam *beams, int32_t B, int32_t rows, int32_t pitch, const void *tab, size_t tab_bytes,
+                    void *dst);
+int gms_ring_alloc(StageRing &r, size_t bytes);
+void gms_ring_free(StageRing &r);
 
 // ---- kernel launchers (gms_map_kernels.hip / gms_pf_kernels.hip) -----------------------------
 
@@ -425,19 +451,20 @@ void gms_launch_pf_resample_seq(gms_pf *pf, double fraction);
 // one GridMapData per particle (gms_slam_kernels.hip); the buffers' current generation is read on the device (SlamBufs)
 SlamBufs gms_slam_bufs(const gms_slam *s);
 void gms_launch_slam_likelihood(gms_map *m, const SlamBufs &sb, int32_t n);
+// batch (may be NULL): the filters' own beams, counts, motion and skipUpdate (B is then the largest count, motion non-NULL: the sequence)
 void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, bool field_in_memory, const MotionModel *motion,
-                              int32_t integrate, int64_t code_words);
+                              int32_t integrate, int64_t code_words, const SlamBatch *batch = nullptr);
 void gms_launch_slam_likelihood_codes(gms_map *m, const SlamBufs &sb, int64_t code_words, int32_t n, int32_t plane);
 void gms_launch_slam_codes_from_log(gms_map *m, const SlamBufs &sb, int32_t first, int32_t count, int64_t code_words);
 int64_t gms_slam_code_words(int64_t cells);
 void gms_launch_slam_trace(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t particle, int32_t *d_cells, uint8_t *d_cls, int32_t cap, int32_t *d_counts);
 bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, const MotionModel *motion, int32_t field_in_lds,
-                            int64_t code_words);
+                            int64_t code_words, const SlamBatch *batch = nullptr);
 bool gms_slam_refine_from_planes(const gms_map *m, int32_t B, int32_t field_in_lds, int64_t code_words);
 // resample()'s copies into the generation the draw has just made current, where it drew (epoch[1]); what: bit 0 logData (+ the class
 // planes), bit 1 likelihoodData; d_idx_keep (may be NULL) receives the indices for a likelihoodData copy that is still owed
 void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const int32_t *d_idx, int32_t *d_idx_keep, int64_t code_words);
-void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n);
+void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n_filters);   // filter f's particles into map f of dst
 void gms_launch_slam_export_records(gms_pf *pf, const SlamBufs &sb, const int32_t *d_list, int32_t count, int64_t code_words, double *d_dst);
 void gms_launch_slam_shard_gather(gms_pf *pf, const SlamBufs &sb, const int32_t *d_src_local, const int32_t *d_recv_pos, const double *d_recv, int64_t code_words);
 

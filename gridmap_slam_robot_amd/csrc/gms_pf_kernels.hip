@@ -1298,11 +1298,13 @@ k_resample(const PackedParticle *__restrict__ glob_all, int64_t n_global, int64_
     resample_body(glob_all, n_global, nchunks, cum_all, chunk_off, r01, r01_scalar, fraction, n, offset, pose2, cs2, w2, idx_out,
                   p2_all, nblk_global, stats, blockIdx.x, blockIdx.y, smem, raw_weights != 0);
     // a filter whose particles own maps (gms_slam): which generation of the maps is current is a device-side fact -- epoch2[0] counts the
-    // draws that ran (the generation is its parity), epoch2[1] says whether this one did; the thread that published did_resample adds it up
-    if (epoch2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        const int32_t did = stats[0].did_resample;
-        epoch2[1] = did;
-        if (did) epoch2[0] = epoch2[0] + 1;
+    // draws that ran (the generation is its parity), epoch2[1] says whether this one did; the thread that published did_resample adds it up.
+    // Map blockIdx.y keeps the pair epoch2[2 mi], epoch2[2 mi + 1] (a batched gms_slam: one pair per filter)
+    if (epoch2 && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int32_t mi = blockIdx.y;
+        const int32_t did = stats[mi].did_resample;
+        epoch2[2 * mi + 1] = did;
+        if (did) epoch2[2 * mi] = epoch2[2 * mi] + 1;
     }
 }
 
@@ -1528,7 +1530,7 @@ __global__ void k_resample_seq_idx(const double *__restrict__ w_all, int32_t n, 
     const bool go = fraction < 0.0 || (1.0 / st->sq_sum) < fraction * (double)n;        // GridMapApp.java:185
     st->did_resample = go ? 1 : 0;
     st->n_ambiguous = 0;
-    if (epoch2 && mi == 0) { epoch2[1] = go ? 1 : 0; if (go) epoch2[0] = epoch2[0] + 1; }   // (see k_resample)
+    if (epoch2) { epoch2[2 * mi + 1] = go ? 1 : 0; if (go) epoch2[2 * mi] = epoch2[2 * mi] + 1; }   // (see k_resample)
     if (!go) { for (int32_t m = 0; m < n; m++) idx[m] = m; return; }
     const double N = (double)n;
     const double r = (r01_maps ? r01_maps[mi] : r01_scalar) * 1.0 / N;                  // :136

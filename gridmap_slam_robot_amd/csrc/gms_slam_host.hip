@@ -4,7 +4,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
+#include <vector>
 
 #include "gms_internal.h"
 
@@ -12,17 +14,31 @@ SlamBufs gms_slam_bufs(const gms_slam *s) {
     SlamBufs b;
     for (int k = 0; k < 2; k++) { b.log[k] = s->d_log[k]; b.lik[k] = s->d_lik[k]; b.code[k] = s->d_code[k]; }
     b.epoch = s->d_epoch;
+    b.n_per = s->n_per;
     return b;
 }
 
-// The current generation on the HOST: a stream synchronise and an 8-byte read.  Only where the host itself must address a particle's
-// arrays -- downloads, uploads, reset, the copy counter -- never on the update / resample path.
-static int slam_host_gen(gms_slam *s, int32_t *gen, int64_t *draws = nullptr) {
-    int32_t e[2] = {0, 0};
+// The current generations on the HOST: a stream synchronise and an 8-byte read per filter.  Only where the host itself must address a
+// particle's arrays -- downloads, uploads, reset, the copy counter -- never on the update / resample path.  gen [n_filters] (may be
+// NULL): filter f's current generation; draws: the draws that ran, summed over the filters' particles (maps copied).
+static int slam_host_gen(gms_slam *s, int32_t *gen, int64_t *copies = nullptr) {
+    std::vector<int32_t> e((size_t)2 * s->n_filters);
     HIPCHK(hipStreamSynchronize(s->map->stream));
-    HIPCHK(hipMemcpy(e, s->d_epoch, sizeof(e), hipMemcpyDeviceToHost));
-    if (gen) *gen = e[0] & 1;
-    if (draws) *draws = e[0];
+    HIPCHK(hipMemcpy(e.data(), s->d_epoch, e.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t c = 0;
+    for (int32_t f = 0; f < s->n_filters; f++) {
+        if (gen) gen[f] = e[2 * (size_t)f] & 1;
+        c += (int64_t)e[2 * (size_t)f] * s->n_per;
+    }
+    if (copies) *copies = c;
+    return GMS_OK;
+}
+
+// the calls that take one scan, one odometry or one draw for the whole handle: one filter only
+static int refuse_batched(const gms_slam *s, const char *what) {
+    if (s->n_filters > 1)
+        return gms_fail(GMS_ERR_STATE, "%s: this handle holds %d filters (gms_params.n_maps): use the batch form%s", what, s->n_filters,
+                        strstr(what, "update") ? " (gms_slam_update_batch[_dev])" : (strstr(what, "resample") ? " (gms_slam_resample_maps[_if]_batch)" : ""));
     return GMS_OK;
 }
 
@@ -36,6 +52,8 @@ int gms_slam_destroy(gms_slam *s) {
     hipFree(s->d_code[0]); hipFree(s->d_code[1]);
     hipFree(s->d_epoch);
     hipFree(s->d_plan);
+    hipFree(s->d_batch);
+    gms_ring_free(s->batch_ring);
     if (s->pf) gms_pf_destroy(s->pf);
     if (s->map) gms_map_destroy(s->map);
     delete s;
@@ -60,11 +78,17 @@ int gms_slam_create_shard(const gms_params *p, int32_t n_local, int64_t offset, 
 static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset, int64_t n_global, gms_slam **out, bool shard_api) {
     REQUIRE(p && out, "gms_slam_create: null argument");
     *out = nullptr;
-    REQUIRE(p->n_maps == 1, "gms_slam_create: gms_params.n_maps must be 1 (every particle gets a map of its own)");
+    const bool shard_call = shard_api || offset != 0 || n_global != n_particles;
+    if (shard_call) REQUIRE(p->n_maps == 1, "gms_slam_create_shard: gms_params.n_maps must be 1 (a shard holds one block of one filter)");
+    REQUIRE(p->n_maps >= 1 && p->n_maps <= 1024, "gms_slam_create: gms_params.n_maps (the number of filters) out of range (1 .. 1024)");
     REQUIRE(n_particles >= 1 && n_particles <= 65535, "gms_slam_create: particle count out of range (1 .. 65535)");
+    if ((int64_t)p->n_maps * n_particles > 65535)
+        return gms_fail(GMS_ERR_INVALID, "gms_slam_create: %d filters x %d particles exceed the handle's 65535 particles", p->n_maps, n_particles);
     gms_slam *s = new (std::nothrow) gms_slam();
     if (!s) return gms_fail(GMS_ERR_NOMEM, "out of host memory");
-    s->n = n_particles;
+    s->n_filters = p->n_maps;
+    s->n_per = n_particles;
+    s->n = p->n_maps * n_particles;
     int rc = gms_map_create(p, &s->map);                                                   // new GridMap(...) :57
     if (!rc) rc = gms_pf_create(s->map, n_particles, &s->pf);                              // the particle list :59
     if (rc) { gms_slam_destroy(s); return rc; }
@@ -75,7 +99,7 @@ static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset,
         gms_slam_destroy(s);
         return gms_fail(GMS_ERR_INVALID, "gms_slam_create: %d beams and rows of %d cells do not fit a workgroup's LDS", m->max_beams, m->gd.W);
     }
-    const size_t bytes = (size_t)n_particles * (size_t)m->gd.cells * sizeof(double);
+    const size_t bytes = (size_t)s->n * (size_t)m->gd.cells * sizeof(double);
     const char *lazy_env = getenv("GMS_SLAM_LAZY_LIK_COPY");
     s->lazy_lik = !(lazy_env && lazy_env[0] == '0');
     const char *rl_env = getenv("GMS_SLAM_REFINE_LDS");
@@ -85,8 +109,9 @@ static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset,
     bool ok = true;
     for (int k = 0; k < 2; k++)
         ok = ok && hipMalloc(&s->d_log[k], bytes) == hipSuccess && hipMalloc(&s->d_lik[k], bytes) == hipSuccess;
-    ok = ok && hipMalloc(&s->d_idx_lik, (size_t)n_particles * sizeof(int32_t)) == hipSuccess;
-    ok = ok && hipMalloc(&s->d_epoch, 2 * sizeof(int32_t)) == hipSuccess && hipMemset(s->d_epoch, 0, 2 * sizeof(int32_t)) == hipSuccess;
+    ok = ok && hipMalloc(&s->d_idx_lik, (size_t)s->n * sizeof(int32_t)) == hipSuccess;
+    const size_t epoch_bytes = (size_t)2 * s->n_filters * sizeof(int32_t);
+    ok = ok && hipMalloc(&s->d_epoch, epoch_bytes) == hipSuccess && hipMemset(s->d_epoch, 0, epoch_bytes) == hipSuccess;
     s->pf->slam_owned = 1;          // its particles own maps: resampling goes through gms_slam_resample_maps[_if], which moves them
     // The class planes (gms_slam_kernels.hip): kept unless the blur kernel is wider than the on-demand evaluation takes, a plane would
     // crowd the count tile out of a workgroup's LDS, or GMS_SLAM_EAGER_LIK=1 asks for the reference's own schedule -- every cell of every
@@ -94,14 +119,14 @@ static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset,
     const char *eager_env = getenv("GMS_SLAM_EAGER_LIK");
     s->code_words = gms_slam_code_words(m->gd.cells);
     if (!(eager_env && eager_env[0] == '1') && m->gd.khalf <= 7 && s->code_words * 4 <= 24 * 1024 && m->gd.W <= 65535 && m->gd.H <= 65535) {
-        const size_t cb = (size_t)n_particles * 2 * (size_t)s->code_words * sizeof(uint32_t);
+        const size_t cb = (size_t)s->n * 2 * (size_t)s->code_words * sizeof(uint32_t);
         for (int k = 0; k < 2; k++) ok = ok && hipMalloc(&s->d_code[k], cb) == hipSuccess;
     }
-    const bool sharded = shard_api || offset != 0 || n_global != n_particles;
+    const bool sharded = shard_call;
     if (sharded) ok = ok && hipMalloc(&s->d_plan, (size_t)3 * n_particles * sizeof(int32_t)) == hipSuccess;
     if (!ok) {
         gms_slam_destroy(s);
-        return gms_fail(GMS_ERR_NOMEM, "gms_slam_create: device allocation failed (%d particles x %lld cells x 32 bytes)", n_particles, (long long)m->gd.cells);
+        return gms_fail(GMS_ERR_NOMEM, "gms_slam_create: device allocation failed (%d particles x %lld cells x 32 bytes)", s->n, (long long)m->gd.cells);
     }
     if (sharded) {
         if (!s->d_code[0]) {
@@ -123,11 +148,11 @@ int gms_slam_reset(gms_slam *s) {                                               
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
     const size_t bytes = (size_t)s->n * (size_t)m->gd.cells * sizeof(double);
-    int64_t draws = 0;
-    int rc0 = slam_host_gen(s, nullptr, &draws);
+    int64_t copies = 0;
+    int rc0 = slam_host_gen(s, nullptr, &copies);
     if (rc0) return rc0;
-    s->copies_base += draws * s->n;                                                          // (the copy counter outlives a reset)
-    HIPCHK(hipMemsetAsync(s->d_epoch, 0, 2 * sizeof(int32_t), m->stream));                   // generation 0 is current again
+    s->copies_base += copies;                                                                // (the copy counter outlives a reset)
+    HIPCHK(hipMemsetAsync(s->d_epoch, 0, (size_t)2 * s->n_filters * sizeof(int32_t), m->stream));   // generation 0 is current again
     // createMapData(null) per particle (GridMap.java:106-117): logData = logOdds(0.5) = 0.0, likelihoodData a fresh double[] = 0.0
     HIPCHK(hipMemsetAsync(s->d_log[0], 0, bytes, m->stream));
     HIPCHK(hipMemsetAsync(s->d_lik[0], 0, bytes, m->stream));
@@ -155,23 +180,20 @@ int gms_slam_handles(gms_slam *s, gms_map **map, gms_pf **pf) {
 
 int gms_slam_count(const gms_slam *s, int32_t *n, int32_t *W, int32_t *H) {
     REQUIRE(s, "null handle");
-    if (n) *n = s->n;
+    if (n) *n = s->n_per;
     if (W) *W = s->map->gd.W;
     if (H) *H = s->map->gd.H;
     return GMS_OK;
 }
 
-// the per-particle body of SLAM.update(z, u) (SLAM.java:88-107) for the particles this handle holds; the weights stay raw
-static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
-                             uint64_t seed, uint64_t sequence) {
-    REQUIRE(s && dev_beams, "null argument");
+static bool slam_skip_update(double d_theta) { return fabs(d_theta) > (3.141592653589793 / 180.0) * 30; }    // SLAM.java:82
+
+// the per-particle body of SLAM.update(z, u) (SLAM.java:88-107) for the particles this handle holds; the weights stay raw.  batch (may be
+// NULL): every filter's own scan, count, odometry, seed and skipUpdate (B: the largest count; motion: the sequence, drawn where the
+// filter's table says so)
+static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, const MotionModel *motion, bool skip_update, const SlamBatch *batch) {
     gms_map *m = s->map;
     gms_pf *pf = s->pf;
-    REQUIRE(B >= 0 && B <= m->max_beams, "beam count exceeds gms_params.max_beams");
-    HIPCHK(hipSetDevice(m->device));
-    const bool skip_update = fabs(d_theta) > (3.141592653589793 / 180.0) * 30;                              // :82
-    MotionModel mo;
-    mo.d_center = d_center; mo.d_theta = d_theta; mo.seed = seed; mo.sequence = sequence;
     // :93 for every particle.  With the class planes and no refinement the field is not written here: probabilityOf reads it under the
     // scan's end points only (GridMap.java:273-277), and k_slam_particle evaluates exactly those cells from the particle's plane; what a
     // caller may read afterwards -- the field of logData as it stands NOW -- stays defined by plane 1 and is written when asked for
@@ -191,13 +213,25 @@ static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, 
     s->lik_from_codes = on_demand ? 1 : 0;
     bool drawn = false;
     if (s->refine) {                                                                                        // :90, then :96 (the lattice form of :97)
-        if (!gms_launch_slam_refine(pf, dev_beams, B, sb, sample_motion ? &mo : nullptr, s->refine_lds, planes ? s->code_words : 0))
+        if (!gms_launch_slam_refine(pf, dev_beams, B, sb, motion, s->refine_lds, planes ? s->code_words : 0, batch))
             return gms_fail(GMS_ERR_INVALID, "gms_slam_update_per_particle: the pose refinement's tables do not fit the LDS for a scan of %d beams", B);
         drawn = true;
     }
-    gms_launch_slam_particle(pf, dev_beams, B, sb, !on_demand, sample_motion && !drawn ? &mo : nullptr, skip_update ? 0 : 1, s->code_words);   // :90, :99, :102-107
+    gms_launch_slam_particle(pf, dev_beams, B, sb, !on_demand, drawn ? nullptr : motion, skip_update ? 0 : 1, s->code_words, batch);   // :90, :99, :102-107
     HIPCHK(hipGetLastError());
     return GMS_OK;
+}
+
+static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
+                             uint64_t seed, uint64_t sequence) {
+    REQUIRE(s && dev_beams, "null argument");
+    int rc = refuse_batched(s, "gms_slam_update_per_particle / update_local");
+    if (rc) return rc;
+    REQUIRE(B >= 0 && B <= s->map->max_beams, "beam count exceeds gms_params.max_beams");
+    HIPCHK(hipSetDevice(s->map->device));
+    MotionModel mo;
+    mo.d_center = d_center; mo.d_theta = d_theta; mo.seed = seed; mo.sequence = sequence;
+    return slam_update_core(s, dev_beams, B, sample_motion ? &mo : nullptr, slam_skip_update(d_theta), nullptr);
 }
 
 // SLAM.update(z, u) on a device-resident scan (SLAM.java:80-131)
@@ -206,7 +240,9 @@ int gms_slam_update_per_particle_dev(gms_slam *s, const gms_beam *dev_beams, int
     REQUIRE(s, "null handle");
     if (pf_is_shard(s->pf))
         return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_update_local_dev, then the weight exchange (gms_pf_local_partials / apply_partials / import_global)");
-    int rc = slam_update_local(s, dev_beams, B, sample_motion, d_center, d_theta, seed, sequence);
+    int rc = refuse_batched(s, "gms_slam_update_per_particle_dev");
+    if (rc) return rc;
+    rc = slam_update_local(s, dev_beams, B, sample_motion, d_center, d_theta, seed, sequence);
     if (rc) return rc;
     return gms_pf_normalize(s->pf, stats);                                                                 // :100, :110-124 (stats: synchronises)
 }
@@ -221,7 +257,9 @@ int gms_slam_update_local_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B,
 int gms_slam_update_local(gms_slam *s, const gms_beam *beams, int32_t B, int32_t sample_motion, double d_center, double d_theta, uint64_t seed,
                           uint64_t sequence) {
     REQUIRE(s && beams, "null argument");
-    int rc = gms_stage_beams(s->map, beams, B);
+    int rc = refuse_batched(s, "gms_slam_update_local");
+    if (rc) return rc;
+    rc = gms_stage_beams(s->map, beams, B);
     if (rc) return rc;
     return slam_update_local(s, s->map->d_beams, B, sample_motion, d_center, d_theta, seed, sequence);
 }
@@ -229,9 +267,76 @@ int gms_slam_update_local(gms_slam *s, const gms_beam *beams, int32_t B, int32_t
 int gms_slam_update_per_particle(gms_slam *s, const gms_beam *beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                                  uint64_t seed, uint64_t sequence, gms_pf_stats *stats) {
     REQUIRE(s && beams, "null argument");
-    int rc = gms_stage_beams(s->map, beams, B);
+    int rc = refuse_batched(s, "gms_slam_update_per_particle");
+    if (rc) return rc;
+    rc = gms_stage_beams(s->map, beams, B);
     if (rc) return rc;
     return gms_slam_update_per_particle_dev(s, s->map->d_beams, B, sample_motion, d_center, d_theta, seed, sequence, stats);
+}
+
+// SLAM.update(z, u) of every filter of the handle (filter f: beams [f][0 .. counts[f]) of the [S][B] block, odometry [f][2], seeds[f],
+// sample_motion[f]; one sequence).  One filter: exactly the scalar call.  Several: one launch of each update kernel for all of them, the
+// filters' table (SlamFilterArgs) in the same copy as the beams where those come from the host (on_device: the beams are the caller's)
+static int slam_update_batch(gms_slam *s, const gms_beam *beams, bool on_device, int32_t B, const int32_t *counts, const double *odometry,
+                             const uint64_t *seeds, const int32_t *sample_motion, uint64_t sequence, gms_pf_stats *stats) {
+    REQUIRE(s, "null handle");
+    REQUIRE(beams && odometry && seeds && sample_motion, "gms_slam_update_batch: null argument (beams, odometry, seeds and sample_motion are required)");
+    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_update_batch: a shard of a filter (gms_slam_update_local[_dev])");
+    gms_map *m = s->map;
+    const int32_t S = s->n_filters;
+    if (B < 0 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "gms_slam_update_batch: B = %d outside 0 .. gms_params.max_beams (%d)", B, m->max_beams);
+    int32_t Bmax = 0;
+    for (int32_t f = 0; f < S; f++) {
+        const int32_t c = counts ? counts[f] : B;
+        if (c < 0 || c > B) return gms_fail(GMS_ERR_INVALID, "gms_slam_update_batch: counts[%d] = %d outside 0 .. B (%d)", f, c, B);
+        Bmax = std::max(Bmax, c);
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (S == 1) {
+        const int32_t c = counts ? counts[0] : B;
+        int rc = GMS_OK;
+        const gms_beam *d = beams;
+        if (!on_device) { rc = gms_stage_beams(m, beams, c); d = m->d_beams; }
+        if (!rc) rc = gms_slam_update_per_particle_dev(s, d, c, sample_motion[0], odometry[0], odometry[1], seeds[0], sequence, stats);
+        return rc;
+    }
+    if (!s->d_batch) {                                 // (first batched update: [S][max_beams] beams | [S] SlamFilterArgs, and their pinned ring)
+        const size_t bytes = (size_t)S * m->max_beams * sizeof(gms_beam) + (size_t)S * sizeof(SlamFilterArgs);
+        if (hipMalloc(&s->d_batch, bytes) != hipSuccess || gms_ring_alloc(s->batch_ring, bytes) != GMS_OK) {
+            hipFree(s->d_batch); s->d_batch = nullptr; gms_ring_free(s->batch_ring);
+            return gms_fail(GMS_ERR_NOMEM, "gms_slam_update_batch: staging allocation failed");
+        }
+    }
+    std::vector<SlamFilterArgs> tab((size_t)S);
+    for (int32_t f = 0; f < S; f++) {
+        SlamFilterArgs &a = tab[f];
+        a.d_center = odometry[2 * (size_t)f]; a.d_theta = odometry[2 * (size_t)f + 1];
+        a.d_center_sd = (0.01 + fabs(a.d_center) * 0.05) / 2;                          // Odometry.java:63 (as gms_launch_slam_particle)
+        a.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(a.d_theta);        // :64
+        a.seed = seeds[f];
+        a.count = counts ? counts[f] : B;
+        a.flags = (sample_motion[f] ? 1 : 0) | (slam_skip_update(a.d_theta) ? 0 : 2);
+    }
+    SlamFilterArgs *d_tab = reinterpret_cast<SlamFilterArgs *>(s->d_batch + (size_t)S * m->max_beams);
+    int rc = gms_stage_block(m, s->batch_ring, on_device ? nullptr : beams, B, S, m->max_beams, tab.data(), tab.size() * sizeof(SlamFilterArgs),
+                             on_device ? static_cast<void *>(d_tab) : static_cast<void *>(s->d_batch));
+    if (rc) return rc;
+    SlamBatch bt;
+    bt.tab = d_tab; bt.n = s->n_per; bt.beam_stride = on_device ? B : m->max_beams;
+    MotionModel mo;                                    // (the kernels take the odometry and seed from the table; the draw where its flag says so)
+    mo.d_center = 0.0; mo.d_theta = 0.0; mo.seed = 0; mo.sequence = sequence;
+    rc = slam_update_core(s, on_device ? beams : s->d_batch, Bmax, &mo, false, &bt);
+    if (rc) return rc;
+    return gms_pf_normalize(s->pf, stats);
+}
+
+int gms_slam_update_batch(gms_slam *s, const gms_beam *beams, int32_t B, const int32_t *counts, const double *odometry, const uint64_t *seeds,
+                          const int32_t *sample_motion, uint64_t sequence, gms_pf_stats *stats) {
+    return slam_update_batch(s, beams, false, B, counts, odometry, seeds, sample_motion, sequence, stats);
+}
+int gms_slam_update_batch_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, const int32_t *counts, const double *odometry,
+                              const uint64_t *seeds, const int32_t *sample_motion, uint64_t sequence, gms_pf_stats *stats) {
+    return slam_update_batch(s, dev_beams, true, B, counts, odometry, seeds, sample_motion, sequence, stats);
 }
 
 // likelihoodData as the last resample() left it, for whoever reads it before the next update (downloads; a second resample())
@@ -252,15 +357,16 @@ static int slam_lik_current(gms_slam *s) {
 // SLAM.resample() (SLAM.java:133-153): the systematic draw over the particles' weights, then every slot's deep copy into the OTHER
 // generation of the maps, which the draw makes current (:152); fraction >= 0: only where Neff < fraction * n (GridMapApp.java:185-186),
 // decided on the device -- where the rule says no, nothing is drawn, no generation changes and the copy kernels return at once (the
-// reference does nothing either)
-static int slam_resample(gms_slam *s, double r01, double fraction, int32_t *indices, int32_t *n_ambiguous) {
+// reference does nothing either).  r01 [n_filters]; a batched handle draws, and decides, per filter (its own generation pair: the
+// handle-wide lik_behind / lik_from_codes hold for every filter, since the copy kernels skip the filters that did not draw)
+static int slam_resample(gms_slam *s, const double *r01, double fraction, int32_t *indices, int32_t *n_ambiguous) {
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
     int rc = s->lik_behind ? slam_lik_current(s) : GMS_OK;                                                 // (two resample() calls in a row)
     if (rc) return rc;
     s->pf->d_epoch2 = s->d_epoch;                      // the draw counts itself (k_resample): the maps' generation follows it
-    rc = fraction >= 0.0 ? gms_pf_resample_if(s->pf, &r01, fraction)
-                         : gms_pf_resample(s->pf, &r01, indices, n_ambiguous);                             // :136-145 + pose, weight (:42-43)
+    rc = fraction >= 0.0 ? gms_pf_resample_if(s->pf, r01, fraction)
+                         : gms_pf_resample(s->pf, r01, indices, n_ambiguous);                              // :136-145 + pose, weight (:42-43)
     s->pf->d_epoch2 = nullptr;
     if (rc) return rc;
     const SlamBufs sb = gms_slam_bufs(s);
@@ -283,6 +389,16 @@ int gms_slam_resample_maps(gms_slam *s, double r01, int32_t *indices, int32_t *n
     REQUIRE(s, "null handle");
     if (pf_is_shard(s->pf))
         return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_shard_draw / export / gather move its maps (the sources may live on other ranks)");
+    int rc = refuse_batched(s, "gms_slam_resample_maps");
+    if (rc) return rc;
+    return slam_resample(s, &r01, -1.0, indices, n_ambiguous);
+}
+
+// resample() of every filter: r01 [S], indices [S][n] filter-local (may be NULL), n_ambiguous [S] (may be NULL)
+int gms_slam_resample_maps_batch(gms_slam *s, const double *r01, int32_t *indices, int32_t *n_ambiguous) {
+    REQUIRE(s, "null handle");
+    REQUIRE(r01, "gms_slam_resample_maps_batch: null r01");
+    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_resample_maps_batch: a shard of a filter (gms_slam_shard_draw / export / gather)");
     return slam_resample(s, r01, -1.0, indices, n_ambiguous);
 }
 
@@ -291,6 +407,8 @@ int gms_slam_resample_maps(gms_slam *s, double r01, int32_t *indices, int32_t *n
 //    maps' generation advances if it drew.  sources[n_local] = the GLOBAL index of every slot's source particle; *did as the rule decided.
 int gms_slam_shard_draw(gms_slam *s, double r01, double fraction, int32_t *did, int32_t *sources) {
     REQUIRE(s && did && sources, "null argument");
+    int rc0 = refuse_batched(s, "gms_slam_shard_draw");
+    if (rc0) return rc0;
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
     if (s->lik_behind || !s->lik_from_codes) {
@@ -321,6 +439,8 @@ int gms_slam_record_doubles(const gms_slam *s, int64_t *doubles) {
 //    [count][record_doubles]: what the ranks whose slots drew them receive
 int gms_slam_shard_export(gms_slam *s, const int32_t *local_indices, int32_t count, double *dev_dst) {
     REQUIRE(s && (count == 0 || (local_indices && dev_dst)), "null argument");
+    int rc0 = refuse_batched(s, "gms_slam_shard_export");
+    if (rc0) return rc0;
     REQUIRE(s->d_plan && count >= 0 && count <= s->n, "gms_slam_shard_export: not a shard, or more records than particles");
     if (count == 0) return GMS_OK;
     gms_map *m = s->map;
@@ -336,6 +456,8 @@ int gms_slam_shard_export(gms_slam *s, const int32_t *local_indices, int32_t cou
 //    recv_pos[m] of dev_recv (the records this rank received).  Both arrays [n_local], host.
 int gms_slam_shard_gather(gms_slam *s, const int32_t *src_local, const int32_t *recv_pos, const double *dev_recv) {
     REQUIRE(s && src_local && recv_pos, "null argument");
+    int rc0 = refuse_batched(s, "gms_slam_shard_gather");
+    if (rc0) return rc0;
     REQUIRE(s->d_plan, "gms_slam_shard_gather: not a shard");
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
@@ -356,6 +478,17 @@ int gms_slam_resample_maps_if(gms_slam *s, double r01, double fraction) {
     if (pf_is_shard(s->pf))
         return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_shard_draw / export / gather move its maps (the sources may live on other ranks)");
     REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if: fraction must be non-negative");
+    int rc = refuse_batched(s, "gms_slam_resample_maps_if");
+    if (rc) return rc;
+    return slam_resample(s, &r01, fraction, nullptr, nullptr);
+}
+
+// `if (neff < fraction * n) resample()` for every filter, each decided on the device from its own Neff: r01 [S]
+int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fraction) {
+    REQUIRE(s, "null handle");
+    REQUIRE(r01, "gms_slam_resample_maps_if_batch: null r01");
+    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_resample_maps_if_batch: a shard of a filter (gms_slam_shard_draw / export / gather)");
+    REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if_batch: fraction must be non-negative");
     return slam_resample(s, r01, fraction, nullptr, nullptr);
 }
 
@@ -373,8 +506,9 @@ int gms_slam_download_map(gms_slam *s, int32_t i, double *log_data, double *lik)
     REQUIRE(s && i >= 0 && i < s->n, "gms_slam_download_map: particle index out of range");
     HIPCHK(hipSetDevice(s->map->device));
     int rc = lik ? slam_lik_current(s) : GMS_OK;
-    int32_t cur = 0;
-    if (!rc) rc = slam_host_gen(s, &cur);
+    std::vector<int32_t> gen((size_t)s->n_filters);
+    if (!rc) rc = slam_host_gen(s, gen.data());
+    const int32_t cur = gen[(size_t)(i / s->n_per)];
     if (!rc && log_data) rc = slam_map_xfer(s, i, 1, s->d_log[cur], log_data, false);
     if (!rc && lik) rc = slam_map_xfer(s, i, 1, s->d_lik[cur], lik, false);
     if (rc) return rc;
@@ -386,10 +520,14 @@ int gms_slam_download_maps(gms_slam *s, double *log_all, double *lik_all) {
     REQUIRE(s, "null handle");
     HIPCHK(hipSetDevice(s->map->device));
     int rc = lik_all ? slam_lik_current(s) : GMS_OK;
-    int32_t cur = 0;
-    if (!rc) rc = slam_host_gen(s, &cur);
-    if (!rc && log_all) rc = slam_map_xfer(s, 0, s->n, s->d_log[cur], log_all, false);
-    if (!rc && lik_all) rc = slam_map_xfer(s, 0, s->n, s->d_lik[cur], lik_all, false);
+    std::vector<int32_t> gen((size_t)s->n_filters);
+    if (!rc) rc = slam_host_gen(s, gen.data());
+    const size_t per = (size_t)s->n_per * (size_t)s->map->gd.cells;
+    for (int32_t f = 0; f < s->n_filters && !rc; f++) {             // (every filter from its own current generation)
+        const int32_t cur = gen[f], i0 = f * s->n_per;
+        if (log_all) rc = slam_map_xfer(s, i0, s->n_per, s->d_log[cur], log_all + f * per, false);
+        if (!rc && lik_all) rc = slam_map_xfer(s, i0, s->n_per, s->d_lik[cur], lik_all + f * per, false);
+    }
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s->map->stream));
     return GMS_OK;
@@ -399,8 +537,9 @@ int gms_slam_upload_map(gms_slam *s, int32_t i, const double *log_data, const do
     REQUIRE(s && i >= 0 && i < s->n, "gms_slam_upload_map: particle index out of range");
     HIPCHK(hipSetDevice(s->map->device));
     int rc = lik ? slam_lik_current(s) : GMS_OK;                  // (the other slots' fields first, then this one's over its copy)
-    int32_t cur = 0;
-    if (!rc) rc = slam_host_gen(s, &cur);
+    std::vector<int32_t> gen((size_t)s->n_filters);
+    if (!rc) rc = slam_host_gen(s, gen.data());
+    const int32_t cur = gen[(size_t)(i / s->n_per)];
     if (!rc && log_data) {
         rc = slam_map_xfer(s, i, 1, s->d_log[cur], const_cast<double *>(log_data), true);
         if (!rc && s->d_code[0])                                  // the slot's class plane 0 follows its logData (plane 1, its field's, does not)
@@ -419,7 +558,7 @@ int gms_slam_combined(gms_slam *s) {
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
     gms_map_settle(m);
-    gms_launch_slam_combine(m, gms_slam_bufs(s), s->n);                                       // :441-455
+    gms_launch_slam_combine(m, gms_slam_bufs(s), s->n_filters);                               // :441-455 (filter f into map f)
     map_log_replaced(m);
     HIPCHK(hipGetLastError());
     return gms_map_build_likelihood(m);                                                       // :457
@@ -433,7 +572,9 @@ int gms_slam_trace_scan(gms_slam *s, int32_t i, const gms_beam *beams, int32_t B
     REQUIRE(B >= 0 && B <= s->map->max_beams && cap >= 0, "gms_slam_trace_scan: beam count or capacity out of range");
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
-    int rc = gms_stage_beams(m, beams, B);
+    int rc = GMS_OK;
+    if (s->n_filters == 1) rc = gms_stage_beams(m, beams, B);
+    else HIPCHK(hipMemcpyAsync(m->d_beams, beams, (size_t)B * sizeof(gms_beam), hipMemcpyHostToDevice, m->stream));   // (one scan: the map stages S)
     if (rc) return rc;
     int32_t *d_cells = nullptr, *d_counts = nullptr;
     uint8_t *d_cls = nullptr;
@@ -455,12 +596,12 @@ int gms_slam_trace_scan(gms_slam *s, int32_t i, const gms_beam *beams, int32_t B
 
 int gms_slam_copies(const gms_slam *s, int64_t *maps_copied) {
     REQUIRE(s && maps_copied, "null argument");
-    int64_t draws = 0;
+    int64_t copies = 0;
     gms_slam *sm = const_cast<gms_slam *>(s);
     HIPCHK(hipSetDevice(sm->map->device));
-    int rc = slam_host_gen(sm, nullptr, &draws);               // (the draws are counted on the device: a conditional resample() may not have run)
+    int rc = slam_host_gen(sm, nullptr, &copies);              // (the draws are counted on the device: a conditional resample() may not have run)
     if (rc) return rc;
-    *maps_copied = s->copies_base + draws * s->n;
+    *maps_copied = s->copies_base + copies;
     return GMS_OK;
 }
 

@@ -29,15 +29,29 @@
 __device__ __forceinline__ double *sb_log(const SlamBufs &sb, int32_t g) { return g ? sb.log[1] : sb.log[0]; }
 __device__ __forceinline__ double *sb_lik(const SlamBufs &sb, int32_t g) { return g ? sb.lik[1] : sb.lik[0]; }
 __device__ __forceinline__ uint32_t *sb_code(const SlamBufs &sb, int32_t g) { return g ? sb.code[1] : sb.code[0]; }
+// the generation pair of particle p's filter: {draws that ran, the last resample() drew} (one filter: sb.epoch itself)
+__device__ __forceinline__ const int32_t *sb_epoch(const SlamBufs &sb, int32_t p) { return sb.epoch + 2 * (p / sb.n_per); }
+// a batched update: particle p's filter f = p / n -- its scan, count, motion and skipUpdate (SlamFilterArgs), its generation pair.
+// The motion-model variates are keyed by the filter-local index (mo.index0 = -f n): what a stand-alone handle of that seed draws.
+__device__ __forceinline__ void slam_batch_filter(const SlamBatch &bt, int32_t p, const gms_beam *__restrict__ &beams, int32_t &B, MotionArgs &mo,
+                                                  int32_t &integrate, const int32_t *&epoch) {
+    const int32_t f = p / bt.n;
+    const SlamFilterArgs fa = bt.tab[f];
+    beams += (size_t)f * (size_t)bt.beam_stride;
+    B = fa.count;
+    mo.on &= fa.flags & 1;
+    mo.d_center = fa.d_center; mo.d_theta = fa.d_theta; mo.d_center_sd = fa.d_center_sd; mo.d_theta_sd = fa.d_theta_sd;
+    mo.seed = fa.seed;
+    mo.index0 = -(int64_t)f * bt.n;
+    integrate &= (fa.flags >> 1) & 1;
+    epoch += 2 * f;
+}
 
 // likelihoodData of every particle's map from its logData (mode 1 of likelihood_body: no factor table, no tile states, every tile)
 template <int KH>
 __global__ void __launch_bounds__(256)
 k_slam_likelihood(GridDev g, SlamBufs sb, const double *__restrict__ taps_g, int32_t tiles_x, int32_t tiles_y) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t cur = sb.epoch[0] & 1;               // the current generation (SlamBufs)
-    const double *__restrict__ logd = sb_log(sb, cur);
-    double *__restrict__ lik = sb_lik(sb, cur);
     // Eight workgroups walk a map's tiles (the launcher's usual shape): they are given ids that differ by 8, i.e. ONE XCD, so that
     // the tiles' halos are read from that XCD's L2 instead of once per XCD from memory.  Workgroups are dispatched to the XCDs round
     // robin by their linear id: of 64 consecutive ones, id & 7 picks the map of a group of eight and (id >> 3) & 7 the walker.
@@ -46,6 +60,9 @@ k_slam_likelihood(GridDev g, SlamBufs sb, const double *__restrict__ taps_g, int
         const uint32_t L = blockIdx.x + 8u * blockIdx.y, grp = L >> 6;
         if (grp * 8u + 8u <= gridDim.y) { by = grp * 8u + (L & 7u); bx = (L >> 3) & 7u; }
     }
+    const int32_t cur = sb_epoch(sb, (int32_t)by)[0] & 1;  // the current generation of this particle's filter (SlamBufs)
+    const double *__restrict__ logd = sb_log(sb, cur);
+    double *__restrict__ lik = sb_lik(sb, cur);
     likelihood_body<KH>(g, logd, lik, lik, 0, taps_g, nullptr, 0, tiles_x, tiles_y, bx, by, gridDim.x, smem, nullptr, nullptr, 1);
 }
 
@@ -71,15 +88,15 @@ template <int KH>
 __global__ void __launch_bounds__(256)
 k_slam_likelihood_codes(GridDev g, SlamBufs sb, int64_t code_words, int32_t plane, const double *__restrict__ taps_g, int32_t tiles_x, int32_t tiles_y) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t cur = sb.epoch[0] & 1;
-    const uint32_t *__restrict__ planes = sb_code(sb, cur) + (plane ? code_words : 0);           // that plane of every particle
-    const int64_t code_stride = 2 * code_words;
-    double *__restrict__ lik = sb_lik(sb, cur);
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     if (gridDim.x == 8u) {
         const uint32_t L = blockIdx.x + 8u * blockIdx.y, grp = L >> 6;
         if (grp * 8u + 8u <= gridDim.y) { by = grp * 8u + (L & 7u); bx = (L >> 3) & 7u; }
     }
+    const int32_t cur = sb_epoch(sb, (int32_t)by)[0] & 1;
+    const uint32_t *__restrict__ planes = sb_code(sb, cur) + (plane ? code_words : 0);           // that plane of every particle
+    const int64_t code_stride = 2 * code_words;
+    double *__restrict__ lik = sb_lik(sb, cur);
     likelihood_body<KH, 1, true>(g, reinterpret_cast<const double *>(planes), lik, lik, 0, taps_g, nullptr, 0, tiles_x, tiles_y, bx, by, gridDim.x, smem,
                                  nullptr, nullptr, 1, code_stride);
 }
@@ -89,11 +106,9 @@ __global__ void __launch_bounds__(256)
 k_slam_codes_from_log(SlamBufs sb, int64_t cells, int32_t first, int64_t code_words, int64_t words) {
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= words) return;
-    const int32_t cur = sb.epoch[0] & 1;
-    const double *__restrict__ logd = sb_log(sb, cur) + (size_t)first * (size_t)cells;
-    uint32_t *__restrict__ planes = sb_code(sb, cur) + (size_t)first * 2 * (size_t)code_words;
-    const int64_t code_stride = 2 * code_words;
-    const double *ml = logd + (size_t)blockIdx.y * (size_t)cells;
+    const int32_t p = first + (int32_t)blockIdx.y;
+    const int32_t cur = sb_epoch(sb, p)[0] & 1;
+    const double *ml = sb_log(sb, cur) + (size_t)p * (size_t)cells;
     uint32_t word = 0;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -101,7 +116,7 @@ k_slam_codes_from_log(SlamBufs sb, int64_t cells, int32_t first, int64_t code_wo
         const double v = c < cells ? ml[c] : 0.0;
         word |= (v > 0.0 ? 2u : (v < 0.0 ? 1u : 0u)) << (2 * k);
     }
-    planes[(size_t)blockIdx.y * (size_t)code_stride + w] = word;
+    sb_code(sb, cur)[(size_t)p * 2 * (size_t)code_words + w] = word;
 }
 
 // GridMap.integrateObservation's per-beam locals (GridMap.java:175-188) from a transform that is already at hand (make_ray takes
@@ -195,14 +210,18 @@ __device__ __forceinline__ void ps_phase_b(const GridDev &g, const PsRay &mt, co
 // (A lane per ray running the reference's loop as it stands -- walk, distance, class, count -- was built and measured: 80 instructions
 // per step on one or two wavefronts per SIMD, which issue one instruction per ~4.6 clocks: 29 us of walking for 90 rays against 17 for
 // this split form, whose cell work spreads over every wavefront of the workgroup.)
-template <int NT, int NP, bool NA, bool CODES>      // NA: 16-bit count cells are on offer (the map does not fit as 32-bit cells); CODES: the class planes are kept
+// BATCH: several filters in one launch (slam_batch_filter; B and Bpad are then the largest scan's)
+template <int NT, int NP, bool NA, bool CODES, bool BATCH>      // NA: 16-bit count cells are on offer (the map does not fit as 32-bit cells); CODES: the class planes are kept
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4)))       // (2 x 512 or 1024 lanes per CU: 128 registers)
 k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t Bpad, SlamBufs sb, int32_t field_in_memory,
                 float *__restrict__ pose, float *__restrict__ cs, double *__restrict__ w,
                 double *__restrict__ logw, MotionArgs mo, int32_t integrate, int32_t tile_bytes, int32_t code_words,
-                const double *__restrict__ taps_g, int32_t taps_plain) {
+                const double *__restrict__ taps_g, int32_t taps_plain, SlamBatch bt) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t cur = sb.epoch[0] & 1;               // the current generation of the particles' maps (SlamBufs)
+    const int32_t p = blockIdx.x;
+    const int32_t *epoch = sb.epoch;
+    if constexpr (BATCH) slam_batch_filter(bt, p, beams, B, mo, integrate, epoch);
+    const int32_t cur = epoch[0] & 1;                  // the current generation of the particles' maps (SlamBufs)
     double *__restrict__ log_all = sb_log(sb, cur);
     const double *__restrict__ lik_all = field_in_memory ? sb_lik(sb, cur) : nullptr;
     uint32_t *__restrict__ code_all = sb_code(sb, cur);
@@ -222,7 +241,6 @@ k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
     __shared__ int32_t s_nzero;                                                // rays of zero length: the only ones that visit a cell more than once
     __shared__ double s_taps[CODES ? 2 * PS_CODE_MAX_KHALF + 2 : 2];           // the blur kernel (CODES)
     __shared__ int32_t s_changed;                                              // a cell of this particle changed its class (CODES): plane 0 is written back
-    const int32_t p = blockIdx.x;
     const int32_t lane = threadIdx.x & 63;
     const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
     GMS_STAMP(GMS_STAMP_ROW(0, blockIdx.x), 0);
@@ -738,14 +756,20 @@ __host__ __device__ inline int32_t slam_lattice_steps(float span, float step, fl
 //   pass 2  a thread takes a column and a band of rows and marches down it with a ring of the 2 k + 1 horizontal sums (the rows it
 //           needs of the neighbouring bands are read before anybody overwrites anything), replacing them by the factor of the
 //           vertical sum (:413-422, GridMap.java:285-288): lane = column, so the LDS accesses are contiguous.
-template <bool LDSF, int KHF>
+template <bool LDSF, int KHF, bool BATCH>            // BATCH: several filters in one launch (slam_batch_filter)
 __global__ void __launch_bounds__(SR_NT_OF(LDSF, KHF)) __attribute__((amdgpu_waves_per_eu(LDSF ? (KHF == 5 ? 3 : 4) : 8)))      // (the field in LDS: one workgroup of sixteen wavefronts per CU; in memory: three of ten, 64 registers)
 k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t Bpad, SlamBufs sb,
               float *__restrict__ pose, float *__restrict__ cs, MotionArgs mo, int32_t fp, int32_t nt_batch, int32_t code_words,
-              const double *__restrict__ taps_g) {
+              const double *__restrict__ taps_g, SlamBatch bt) {
     static_assert(KHF == 0 || LDSF, "the field is computed into LDS");
     extern __shared__ __align__(16) unsigned char smem[];
-    const double *__restrict__ lik_all = sb_lik(sb, sb.epoch[0] & 1);
+    const int32_t p = blockIdx.x;
+    const int32_t *epoch = sb.epoch;
+    if constexpr (BATCH) {
+        int32_t integrate = 0;
+        slam_batch_filter(bt, p, beams, B, mo, integrate, epoch);
+    }
+    const double *__restrict__ lik_all = sb_lik(sb, epoch[0] & 1);
     constexpr int NT = SR_NT_OF(LDSF, KHF), NW = NT / 64;
     double *s_f = reinterpret_cast<double *>(smem);                            // [H + 1][fp] factors, column W and row H neutral (LDSF)
     // (every carve offset a multiple of 16: a 16-byte LDS access off its alignment is replayed at 64 cycles -- 121 x 121 doubles are not)
@@ -756,7 +780,6 @@ k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t 
     __shared__ float s_pose[3];
     __shared__ double s_best[NW];
     __shared__ int32_t s_bestq[NW];
-    const int32_t p = blockIdx.x;
     const int32_t lane = threadIdx.x & 63;
     const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
     GMS_STAMP(GMS_STAMP_ROW(3, blockIdx.x), 0);
@@ -807,7 +830,7 @@ k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t 
     if (KHF > 0) {
         // ---- pass 1: horizontal sums.  16 (the power of two that holds a row's strips) threads per row, thread = strip
         constexpr int K = KHF > 0 ? KHF : 1, NTAP = 2 * K + 1, STRIP = K <= 3 ? 8 : 4, NV = STRIP + 2 * K;      // NV <= 14 classes: 28 bits
-        const uint32_t *__restrict__ gpl = sb_code(sb, sb.epoch[0] & 1) + (size_t)p * 2 * (size_t)code_words;    // plane 0: logData as it stands (the start of the update)
+        const uint32_t *__restrict__ gpl = sb_code(sb, epoch[0] & 1) + (size_t)p * 2 * (size_t)code_words;    // plane 0: logData as it stands (the start of the update)
         double tp[NTAP];
 #pragma unroll
         for (int i = 0; i < NTAP; i++) tp[i] = taps_g[i];
@@ -1110,7 +1133,8 @@ k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t 
 __global__ void __launch_bounds__(256)
 k_slam_gather_maps(SlamBufs sb, const int32_t *__restrict__ idx, int64_t cells) {
     const int32_t m = blockIdx.y;
-    const int32_t did = sb.epoch[1], epoch = sb.epoch[0], i = idx[m];
+    const int32_t *ep = sb_epoch(sb, m);               // (slot m's filter; idx[] holds filter-local indices)
+    const int32_t did = ep[1], epoch = ep[0], i = m - m % sb.n_per + idx[m];
     if (!did) return;                                  // the rule said no (GridMapApp.java:185): nothing was drawn, nothing moves
     const int32_t cur = epoch & 1;                     // the generation the draw has just made current receives the copies
     const double *__restrict__ src_log = sb_log(sb, cur ^ 1), *__restrict__ src_lik = sb_lik(sb, cur ^ 1);
@@ -1169,10 +1193,11 @@ __device__ __forceinline__ void gather_copy_array(const double *__restrict__ src
 __global__ void __launch_bounds__(256)
 k_slam_gather_one(SlamBufs sb, int32_t lik_array, const int32_t *__restrict__ idx, int64_t cells, int32_t *__restrict__ idx_keep, int64_t code_words2) {
     const int32_t m = blockIdx.y;
-    const int32_t did = sb.epoch[1], epoch = sb.epoch[0], i = idx[m];          // (three independent scalar loads: one round trip in front of the data's)
+    const int32_t *ep = sb_epoch(sb, m);               // (slot m's filter; idx[] holds filter-local indices)
+    const int32_t did = ep[1], epoch = ep[0], il = idx[m], i = m - m % sb.n_per + il;    // (three independent scalar loads: one round trip in front of the data's)
     if (!did) return;                                  // the rule said no (GridMapApp.java:185): nothing was drawn, nothing moves
     const int32_t cur = epoch & 1;                     // the generation the draw has just made current receives the copies
-    if (idx_keep && blockIdx.x == 0 && threadIdx.x == 0) idx_keep[m] = i;      // for the copy that is still owed (gms_slam::d_idx_lik)
+    if (idx_keep && blockIdx.x == 0 && threadIdx.x == 0) idx_keep[m] = il;     // for the copy that is still owed (gms_slam::d_idx_lik)
     if (!lik_array && code_words2 && blockIdx.x == gridDim.x - 1) {            // the particle's two class planes travel with its logData (16-byte multiples)
         const uint4 *sc = reinterpret_cast<const uint4 *>(sb_code(sb, cur ^ 1) + (size_t)i * (size_t)code_words2);
         uint4 *dc = reinterpret_cast<uint4 *>(sb_code(sb, cur) + (size_t)m * (size_t)code_words2);
@@ -1185,12 +1210,13 @@ k_slam_gather_one(SlamBufs sb, int32_t lik_array, const int32_t *__restrict__ id
 // the class planes alone (the resampling copy that moves both arrays at once, k_slam_gather_maps, does not carry them)
 __global__ void __launch_bounds__(256)
 k_slam_gather_codes(SlamBufs sb, const int32_t *__restrict__ idx, int64_t code_words2) {
-    if (!sb.epoch[1]) return;
-    const int32_t cur = sb.epoch[0] & 1;
+    const int32_t m = blockIdx.x;
+    const int32_t *ep = sb_epoch(sb, m);
+    if (!ep[1]) return;
+    const int32_t cur = ep[0] & 1;
     const uint32_t *__restrict__ src_code = sb_code(sb, cur ^ 1);
     uint32_t *__restrict__ dst_code = sb_code(sb, cur);
-    const int32_t m = blockIdx.x;
-    const uint4 *sc = reinterpret_cast<const uint4 *>(src_code + (size_t)idx[m] * (size_t)code_words2);
+    const uint4 *sc = reinterpret_cast<const uint4 *>(src_code + (size_t)(m - m % sb.n_per + idx[m]) * (size_t)code_words2);
     uint4 *dc = reinterpret_cast<uint4 *>(dst_code + (size_t)m * (size_t)code_words2);
     for (int64_t e = threadIdx.x; e < code_words2 / 4; e += 256) dc[e] = sc[e];
 }
@@ -1308,7 +1334,7 @@ static inline size_t slam_particle_fixed_lds(int32_t Bpad, int np) {
 // sb.code (may be NULL): the particles' class planes [n][2][code_words], kept in step with logData; with them field_in_memory may be
 // false: the field is then evaluated at the scan's end points from the planes instead of read from sb.lik
 void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, bool field_in_memory, const MotionModel *motion,
-                              int32_t integrate, int64_t code_words) {
+                              int32_t integrate, int64_t code_words, const SlamBatch *batch) {
     const uint32_t *d_code = sb.code[0];
     gms_map *m = pf->map;
     MotionArgs mo;
@@ -1340,18 +1366,22 @@ void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, co
     // the read-modify-write of the touched cells -- overlap), 1024 when the tile leaves room for one only.  GMS_SLAM_THREADS forces one.
     int32_t threads = smem <= lds_wg / 2 ? 512 : 1024;
     if (m->slam_threads == 512 || m->slam_threads == 1024) threads = m->slam_threads;
-#define PS_LAUNCH(NT, NA, CD)                                                                                                           \
+    const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
+    const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
+#define PS_LAUNCH1(NT, NA, CD, BT)                                                                                                      \
     do {                                                                                                                                \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_particle<NT, NP, NA, CD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL((k_slam_particle<NT, NP, NA, CD>), dim3((unsigned)pf->n), dim3(NT), smem, m->stream, m->gd, d_beams, B, Bpad, sb,           \
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_particle<NT, NP, NA, CD, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+        hipLaunchKernelGGL((k_slam_particle<NT, NP, NA, CD, BT>), dim3(grid), dim3(NT), smem, m->stream, m->gd, d_beams, B, Bpad, sb,           \
                            field_in_memory ? 1 : 0, pf->d_pose, pf->d_cs, pf->d_w, pf->d_logw, mo, integrate, (int32_t)(tile * 4), (int32_t)code_words, \
-                           m->d_taps, m->taps_plain);                                                                                   \
+                           m->d_taps, m->taps_plain, bt);                                                                               \
     } while (0)
+#define PS_LAUNCH(NT, NA, CD) do { if (batch) PS_LAUNCH1(NT, NA, CD, true); else PS_LAUNCH1(NT, NA, CD, false); } while (0)
 #define PS_LAUNCH2(NT, NA) do { if (d_code) PS_LAUNCH(NT, NA, true); else PS_LAUNCH(NT, NA, false); } while (0)
     if (threads == 512) { if (narrow_allowed) PS_LAUNCH2(512, true); else PS_LAUNCH2(512, false); }
     else { if (narrow_allowed) PS_LAUNCH2(1024, true); else PS_LAUNCH2(1024, false); }
 #undef PS_LAUNCH2
 #undef PS_LAUNCH
+#undef PS_LAUNCH1
     pf_scored(pf, 1);
 }
 
@@ -1404,7 +1434,7 @@ bool gms_slam_refine_from_planes(const gms_map *m, int32_t B, int32_t field_in_l
 // from memory wherever it fits (tests of the other forms).  Returns false (nothing launched) where a theta step's tables do not fit
 // a workgroup's LDS (scans of more than ~2600 beams) or a map side does not fit their 16-bit entries.
 bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, const MotionModel *motion, int32_t field_in_lds,
-                            int64_t code_words) {
+                            int64_t code_words, const SlamBatch *batch) {
     gms_map *m = pf->map;
     const RefinePlan r = slam_refine_plan(m, B, field_in_lds, code_words);
     if (!r.ok) return false;
@@ -1416,17 +1446,21 @@ bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, cons
         mo.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(motion->d_theta);   // :64
     }
     ProfScope ps(m, GMS_K_REFINE);
-#define SR_LAUNCH(LF, KF)                                                                                                               \
+    const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
+    const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
+#define SR_LAUNCH1(LF, KF, BT)                                                                                                          \
     do {                                                                                                                                \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_refine<LF, KF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.smem); \
-        hipLaunchKernelGGL((k_slam_refine<LF, KF>), dim3((unsigned)pf->n), dim3(SR_NT_OF(LF, KF)), r.smem, m->stream, m->gd, d_beams, B, r.Bpad, sb, \
-                           pf->d_pose, pf->d_cs, mo, r.fp, r.nt_batch, (int32_t)code_words, m->d_taps);                                \
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_refine<LF, KF, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.smem); \
+        hipLaunchKernelGGL((k_slam_refine<LF, KF, BT>), dim3(grid), dim3(SR_NT_OF(LF, KF)), r.smem, m->stream, m->gd, d_beams, B, r.Bpad, sb, \
+                           pf->d_pose, pf->d_cs, mo, r.fp, r.nt_batch, (int32_t)code_words, m->d_taps, bt);                            \
     } while (0)
+#define SR_LAUNCH(LF, KF) do { if (batch) SR_LAUNCH1(LF, KF, true); else SR_LAUNCH1(LF, KF, false); } while (0)
     if (r.khf == 3) SR_LAUNCH(true, 3);
     else if (r.khf == 5) SR_LAUNCH(true, 5);
     else if (r.ldsf) SR_LAUNCH(true, 0);
     else SR_LAUNCH(false, 0);
 #undef SR_LAUNCH
+#undef SR_LAUNCH1
     return true;
 }
 
@@ -1434,31 +1468,32 @@ void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const 
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_MAPCOPY);
     const int64_t cells = m->gd.cells;
+    const int64_t slots = (int64_t)pf->n * pf->n_maps;        // (a batched handle: every filter's slots, filter-local indices in d_idx)
     if (what == 3) {
         // both arrays at once: 256 lanes x 16 bytes x 2 in flight per array = 8 KiB of each array per workgroup pass
         int64_t chunks = (cells / 2 + 511) / 512;
         if (chunks < 1) chunks = 1;
-        while (chunks > 1 && chunks * pf->n > 65536) chunks = (chunks + 1) / 2;
-        hipLaunchKernelGGL(k_slam_gather_maps, dim3((unsigned)chunks, (unsigned)pf->n), dim3(256), 0, m->stream, sb, d_idx, cells);
-        if (sb.code[0]) hipLaunchKernelGGL(k_slam_gather_codes, dim3((unsigned)pf->n), dim3(256), 0, m->stream, sb, d_idx, 2 * code_words);
+        while (chunks > 1 && chunks * slots > 65536) chunks = (chunks + 1) / 2;
+        hipLaunchKernelGGL(k_slam_gather_maps, dim3((unsigned)chunks, (unsigned)slots), dim3(256), 0, m->stream, sb, d_idx, cells);
+        if (sb.code[0]) hipLaunchKernelGGL(k_slam_gather_codes, dim3((unsigned)slots), dim3(256), 0, m->stream, sb, d_idx, 2 * code_words);
         return;
     }
     // one array: 256 lanes x 16 bytes x GATHER_U in flight = 32 KiB of the array per workgroup pass
     // ... while that is a residency or two of workgroups (500 maps of 120 x 120: 2000); a copy that streams from memory does better with
     // a quarter of that per workgroup and pass (4096 x 256 x 256: 443 us at 32 KiB, 409 at 16, 367 at 8, 496 at 4; 1024 x 256 x 256: 147 / 122)
     int64_t per = 256 * GATHER_U;
-    const bool streams = ((cells / 2 + per - 1) / per) * pf->n > 4096;
+    const bool streams = ((cells / 2 + per - 1) / per) * slots > 4096;
     if (streams) per = 512;
     int64_t chunks = (cells / 2 + per - 1) / per;
     if (chunks < 1) chunks = 1;
-    while (chunks > 1 && chunks * pf->n > 262144) chunks = (chunks + 1) / 2;
+    while (chunks > 1 && chunks * slots > 262144) chunks = (chunks + 1) / 2;
     // the class planes ride in the copy's last workgroup of every map while the launch is one residency of workgroups (500 x 120 x 120:
     // resample() 21.6 us against 24.1 with a launch of their own); where the copy streams from memory that workgroup's nine round
     // trips in a row hold the launch's tail open (4096 x 256 x 256: 0.60 ms against 0.38): there they get a launch of their own
     const bool separate = streams;
-    hipLaunchKernelGGL(k_slam_gather_one, dim3((unsigned)chunks, (unsigned)pf->n), dim3(256), 0, m->stream, sb, what == 2 ? 1 : 0, d_idx, cells, d_idx_keep,
+    hipLaunchKernelGGL(k_slam_gather_one, dim3((unsigned)chunks, (unsigned)slots), dim3(256), 0, m->stream, sb, what == 2 ? 1 : 0, d_idx, cells, d_idx_keep,
                        what == 1 && sb.code[0] && !separate ? 2 * code_words : (int64_t)0);
-    if (what == 1 && sb.code[0] && separate) hipLaunchKernelGGL(k_slam_gather_codes, dim3((unsigned)pf->n), dim3(256), 0, m->stream, sb, d_idx, 2 * code_words);
+    if (what == 1 && sb.code[0] && separate) hipLaunchKernelGGL(k_slam_gather_codes, dim3((unsigned)slots), dim3(256), 0, m->stream, sb, d_idx, 2 * code_words);
 }
 
 // GridMapApp.calculateCombined over the particles' maps (J/app/GridMapApp.java:439-458) into a single map's logData
@@ -1480,7 +1515,12 @@ void gms_launch_slam_shard_gather(gms_pf *pf, const SlamBufs &sb, const int32_t 
                        code_words);
 }
 
-__global__ void k_slam_combine(SlamBufs sb, int32_t n, int64_t cells, double *__restrict__ out) { combine_body(sb_log(sb, sb.epoch[0] & 1), n, cells, out); }
-void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n) {
-    hipLaunchKernelGGL(k_slam_combine, dim3(2048), dim3(256), 0, dst->stream, sb, n, dst->gd.cells, dst->d_log);
+// filter blockIdx.y's particles into map blockIdx.y of out
+__global__ void k_slam_combine(SlamBufs sb, int64_t cells, double *__restrict__ out) {
+    const int32_t f = blockIdx.y, p0 = f * sb.n_per;
+    combine_body(sb_log(sb, sb_epoch(sb, p0)[0] & 1) + (size_t)p0 * (size_t)cells, sb.n_per, cells, out + (size_t)f * (size_t)cells);
+}
+void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n_filters) {
+    const unsigned gx = n_filters > 1 ? (unsigned)std::max(2048 / n_filters, 64) : 2048u;
+    hipLaunchKernelGGL(k_slam_combine, dim3(gx, (unsigned)n_filters), dim3(256), 0, dst->stream, sb, dst->gd.cells, dst->d_log);
 }

@@ -905,3 +905,184 @@ class SLAMParticleMaps:
     getParticles = get_particles
     getStrongestParticle = get_strongest_particle
     getGridMap = get_grid_map
+
+
+class SLAMParticleMapsBatch:
+    """num_filters independent SLAMParticleMaps filters in ONE handle (gms_slam_create with gms_params.n_maps = S): every update and
+    resampling step is one launch of each kernel for all of them, and filter f computes, bit for bit, what a stand-alone
+    SLAMParticleMaps would from the same scans, odometry and seed.  Filter-local particle indices throughout."""
+
+    def __init__(self, num_filters: int, width=6.0, height=6.0, resolution=0.05, position=(-3.0, -3.0), num_particles=500,
+                 device: int = 0, max_beams: int = 0, kernel=None):
+        L = load()
+        p = GmsParams()
+        check(L.gms_params_default(C.byref(p), width, height, resolution, position[0], position[1]))
+        p.n_maps = int(num_filters)
+        p.device = device
+        p.max_beams = max_beams
+        _put_kernel(p, kernel)
+        self.params = p
+        self.num_filters = int(num_filters)
+        self.num_particles = int(num_particles)
+        self._h = C.c_void_p()
+        check(L.gms_slam_create(C.byref(p), self.num_particles, C.byref(self._h)))
+        mh, ph = C.c_void_p(), C.c_void_p()
+        check(L.gms_slam_handles(self._h, C.byref(mh), C.byref(ph)))
+        self.grid_map = _BorrowedMap(mh, p)                     # map f receives calculate_combined(f)
+        self.pf = _BorrowedFilter(ph, self.grid_map, self.num_particles)
+        self.pf.n_maps = self.num_filters                       # (the filter's arrays are [S][n])
+        self.W, self.H = self.grid_map.W, self.grid_map.H
+        self.strongest = np.zeros(self.num_filters, dtype=np.int64)
+        self.neff = np.full(self.num_filters, float(num_particles))
+        self.sequence = 0
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.grid_map.close(); self.pf.close()
+            check(load().gms_slam_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(load().gms_slam_reset(self._h))
+
+    def set_refine(self, on: bool = True):
+        check(load().gms_slam_set_refine(self._h, int(bool(on))))
+
+    def _per_filter(self, v, dtype):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (self.num_filters,)))
+
+    def update(self, scans, odometry=None, seeds=0, sequence: Optional[int] = None, fetch: bool = True, sample_motion=True):
+        """update(z, u) of every filter: scans = S scans (each an Observation or a beam array of its own length), odometry = None or S
+        entries of (dCenter, dTheta) or None (as SLAMParticleMaps.update), seeds = S seeds (or one for all), sample_motion = S flags (or
+        one).  Returns the filters' Neff [S] (fetch)."""
+        S = self.num_filters
+        if len(scans) != S:
+            raise ValueError(f"update: {len(scans)} scans for {S} filters")
+        bs = [_beams_of(z) for z in scans]
+        counts = np.array([len(b) for b in bs], dtype=np.int32)
+        B = int(counts.max()) if S else 0
+        block = np.zeros((S, max(B, 1)), dtype=BEAM_DTYPE)
+        for f, b in enumerate(bs):
+            block[f, :len(b)] = b
+        odo = [None] * S if odometry is None else list(odometry)
+        if len(odo) != S:
+            raise ValueError(f"update: {len(odo)} odometry entries for {S} filters")
+        u = np.array([(0.0, 0.0) if o is None else (float(o[0]), float(o[1])) for o in odo], dtype=np.float64).reshape(S, 2)
+        sm = self._per_filter(sample_motion, np.int32) != 0
+        have = np.array([o is not None for o in odo]) & sm
+        have = np.ascontiguousarray(have.astype(np.int32))
+        sd = self._per_filter(seeds, np.uint64)
+        if sequence is None:
+            sequence = self.sequence
+            self.sequence += 1
+        st = (GmsPfStats * S)()
+        check(load().gms_slam_update_batch(self._h, ptr(block), B, ptr(counts), ptr(u), ptr(sd), ptr(have), int(sequence),
+                                           st if fetch else None))
+        if not fetch:
+            return None
+        self.last_stats = [{"weight_sum": s.weight_sum, "neff": s.neff, "strongest": s.strongest, "n_zero": s.n_zero,
+                            "max_log_weight": s.max_log_weight} for s in st]
+        self.strongest = np.array([s.strongest for s in st], dtype=np.int64)       # (filter-local)
+        self.neff = np.array([s.neff for s in st], dtype=np.float64)
+        return self.neff.copy()
+
+    def update_dev(self, dev_beams: int, B: int, counts=None, odometry=None, seeds=0, sequence: int = 0, sample_motion=True):
+        """the same on device beams [S][B] (row pitch B); counts [S] or None (all B); odometry [S][2] or None (no motion)"""
+        S = self.num_filters
+        c = None if counts is None else self._per_filter(counts, np.int32)
+        u = np.zeros((S, 2)) if odometry is None else np.ascontiguousarray(np.asarray(odometry, dtype=np.float64).reshape(S, 2))
+        have = self._per_filter(sample_motion, np.int32) * (0 if odometry is None else 1)
+        have = np.ascontiguousarray(have.astype(np.int32))
+        check(load().gms_slam_update_batch_dev(self._h, C.c_void_p(dev_beams), int(B), None if c is None else ptr(c), ptr(u),
+                                               ptr(self._per_filter(seeds, np.uint64)), ptr(have), int(sequence), None))
+
+    def resample(self, r01=None, want_indices: bool = False):
+        """resample() of every filter; r01 [S] (or one for all).  want_indices: (indices [S][n] filter-local, n_ambiguous [S])"""
+        r = self._per_filter(np.random.random(self.num_filters) if r01 is None else r01, np.float64)
+        if not want_indices:
+            check(load().gms_slam_resample_maps_batch(self._h, ptr(r), None, None))
+            return None
+        idx = np.empty((self.num_filters, self.num_particles), dtype=np.int32)
+        amb = np.empty(self.num_filters, dtype=np.int32)
+        check(load().gms_slam_resample_maps_batch(self._h, ptr(r), ptr(idx), ptr(amb)))
+        return idx, amb
+
+    def resample_if(self, r01=None, fraction: float = 0.5):
+        """`if (neff < fraction * n) resample()` per filter, decided on the device; did_resample() / last_resample_indices() tell"""
+        r = self._per_filter(np.random.random(self.num_filters) if r01 is None else r01, np.float64)
+        check(load().gms_slam_resample_maps_if_batch(self._h, ptr(r), float(fraction)))
+
+    def did_resample(self) -> np.ndarray:
+        return np.asarray(self.pf.did_resample(), dtype=bool).reshape(self.num_filters)
+
+    def last_resample_indices(self) -> np.ndarray:
+        return self.pf.last_resample_indices().reshape(self.num_filters, self.num_particles)
+
+    def get_weighted_pose(self) -> np.ndarray:
+        return np.asarray(self.pf.weighted_pose()).reshape(self.num_filters, 3)
+
+    def calculate_neff(self) -> np.ndarray:
+        st = self.pf.stats()
+        st = st if isinstance(st, list) else [st]
+        return np.array([s["neff"] for s in st], dtype=np.float64)
+
+    def get_particles(self):
+        """(poses [S][n][3], weights [S][n])"""
+        poses, w = self.pf.get_particles()
+        return poses.reshape(self.num_filters, self.num_particles, 3), w.reshape(self.num_filters, self.num_particles)
+
+    def set_poses(self, xytheta):
+        self.pf.set_poses(xytheta)
+
+    def _slot(self, f: int, i: int) -> int:
+        if not (0 <= f < self.num_filters and 0 <= i < self.num_particles):
+            raise IndexError(f"particle {i} of filter {f}: out of range ({self.num_filters} x {self.num_particles})")
+        return int(f) * self.num_particles + int(i)
+
+    def map_of(self, f: int, i: int, likelihood: bool = False) -> np.ndarray:
+        """filter f's particle i's logData (or likelihoodData) as [H][W]"""
+        out = np.empty((self.H, self.W), dtype=np.float64)
+        check(load().gms_slam_download_map(self._h, self._slot(f, i), None if likelihood else ptr(out), ptr(out) if likelihood else None))
+        return out
+
+    def maps(self, f: Optional[int] = None, likelihood: bool = False) -> np.ndarray:
+        """filter f's maps [n][H][W]; f = None: every filter's [S][n][H][W]"""
+        out = np.empty((self.num_filters, self.num_particles, self.H, self.W), dtype=np.float64)
+        check(load().gms_slam_download_maps(self._h, None if likelihood else ptr(out), ptr(out) if likelihood else None))
+        return out if f is None else out[int(f)]
+
+    def set_map(self, f: int, i: int, log=None, lik=None):
+        lg = None if log is None else np.ascontiguousarray(log, dtype=np.float64)
+        lk = None if lik is None else np.ascontiguousarray(lik, dtype=np.float64)
+        for name, a in (("log", lg), ("lik", lk)):
+            if a is not None and a.size != self.W * self.H:
+                raise ValueError(f"set_map: {name} has {a.size} values, the map has {self.W} x {self.H} cells")
+        check(load().gms_slam_upload_map(self._h, self._slot(f, i), None if lg is None else ptr(lg), None if lk is None else ptr(lk)))
+
+    def calculate_combined(self, f: int, likelihood: bool = False) -> np.ndarray:
+        """GridMapApp.calculateCombined over filter f's particles: its logData [H][W] (likelihood: the field of it)"""
+        if not 0 <= f < self.num_filters:
+            raise IndexError(f"filter {f} out of range ({self.num_filters})")
+        check(load().gms_slam_combined(self._h))
+        out = self.grid_map.download_likelihood() if likelihood else self.grid_map.download_log()
+        return out.reshape(self.num_filters, self.H, self.W)[int(f)]
+
+    def trace_scan(self, f: int, i: int, z, cap: int = 0):
+        b = _beams_of(z)
+        cap = int(cap) if cap > 0 else self.W + self.H + 8
+        cells = np.zeros((len(b), cap, 2), dtype=np.int32)
+        cls = np.zeros((len(b), cap), dtype=np.uint8)
+        counts = np.zeros(len(b), dtype=np.int32)
+        check(load().gms_slam_trace_scan(self._h, self._slot(f, i), ptr(b), len(b), ptr(cells), ptr(cls), cap, ptr(counts)))
+        return cells, cls, counts
+
+    def maps_copied(self) -> int:
+        v = C.c_int64(0)
+        check(load().gms_slam_copies(self._h, C.byref(v)))
+        return int(v.value)

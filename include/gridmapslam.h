@@ -277,11 +277,18 @@ int gms_pf_set_reference_order(gms_pf *pf, int32_t on);
  * slot index (see gms_pf_sample_motion). */
 typedef struct gms_slam gms_slam;
 /* new SLAM() (SLAM.java:56-62) + reset() (:65-77): n_particles particles at Pose(0, 0, 0) with weight 1 / n and a blank map each
- * (createMapData(null)).  p as for gms_map_create, with p->n_maps == 1 (the GridMap whose GridMapData every particle instantiates). */
+ * (createMapData(null)).  p as for gms_map_create (the GridMap whose GridMapData every particle instantiates).
+ * p->n_maps = S > 1 (at most 1024, S * n_particles at most 65535): S independent filters of n_particles particles in one handle -- a
+ * batched handle.  Filter f's particle k is particle f * n_particles + k of every entry point that takes a particle index
+ * (download_map / upload_map / trace_scan) and of the handle's gms_pf ([S][n] poses, weights, indices; its gms_pf_stats are per filter,
+ * `strongest` filter-local); download_maps, reset and combined cover every filter (combined: filter f into map f of the handle's own
+ * map).  Only the batch forms update and resample it (gms_slam_update_batch[_dev], gms_slam_resample_maps[_if]_batch); the calls that
+ * take one scan, one odometry or one draw return GMS_ERR_STATE on it.  Every filter computes, bit for bit, what a stand-alone handle of
+ * the same parameters computes from the same inputs and seed. */
 int gms_slam_create(const gms_params *p, int32_t n_particles, gms_slam **out);
 int gms_slam_destroy(gms_slam *s);
-int gms_slam_reset(gms_slam *s);                                    /* SLAM.reset() (SLAM.java:65-77) */
-int gms_slam_count(const gms_slam *s, int32_t *n_particles, int32_t *W, int32_t *H);
+int gms_slam_reset(gms_slam *s);                                    /* SLAM.reset() (SLAM.java:65-77): every filter */
+int gms_slam_count(const gms_slam *s, int32_t *n_particles, int32_t *W, int32_t *H);   /* n_particles: per filter */
 /* The handles behind it, owned by the gms_slam (do not destroy them; the filter refuses gms_pf_resample[_if], gms_pf_set_shard and the
  * shared-map scan steps with GMS_ERR_STATE: they would move its particles without their maps): *map = SLAM.getGridMap() (:200) -- geometry, constants, the
  * stream every call of this handle runs on, and a GridMapData of its own that receives gms_slam_combined; *pf = getParticles()
@@ -298,6 +305,17 @@ int gms_slam_update_per_particle(gms_slam *s, const gms_beam *beams, int32_t B, 
                                  uint64_t seed, uint64_t sequence, gms_pf_stats *stats);
 int gms_slam_update_per_particle_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                                      uint64_t seed, uint64_t sequence, gms_pf_stats *stats);
+/* SLAM.update(z, u) of every filter of a handle (any S, 1 included), one launch of each update kernel for all of them.  beams [S][B]:
+ * filter f's scan is beams[f][0 .. counts[f]) (counts [S] may be NULL: all B; padding a scan is not neutral -- a beam that hits nothing
+ * is still ray-cast), odometry [S][2] {dCenter, dTheta}, seeds [S], sample_motion [S] (0: keep the poses, as sample_motion of the scalar
+ * call), one sequence: filter f's motion-model variates are Philox(seeds[f]; filter-local particle index, sequence), what a stand-alone
+ * handle with seed seeds[f] draws.  skipUpdate (|dTheta| > 30 degrees, SLAM.java:82) is decided per filter.  stats [S] (may be NULL;
+ * when given the call synchronises).  The host form stages the beams and the filters' table in one copy; _dev reads the caller's
+ * device beams (row pitch B) and stages the table alone.  S = 1 runs exactly the scalar call. */
+int gms_slam_update_batch(gms_slam *s, const gms_beam *beams, int32_t B, const int32_t *counts, const double *odometry, const uint64_t *seeds,
+                          const int32_t *sample_motion, uint64_t sequence, gms_pf_stats *stats);
+int gms_slam_update_batch_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, const int32_t *counts, const double *odometry,
+                              const uint64_t *seeds, const int32_t *sample_motion, uint64_t sequence, gms_pf_stats *stats);
 /* SLAM.update's pose refinement (SLAM.java:96-97): on != 0, every update runs GridMap.findBestPose (J/slam/GridMap.java:319-346: the
  * lattice of 11 x 11 x 10 poses around the motion-model sample, float loop counters, strict `>` against maxProb = 0 so that the first
  * maximum wins) for every particle against ITS OWN likelihood field, between computeLikelihoodMap(p.m) (:93) and the weighting (:99);
@@ -322,6 +340,11 @@ int gms_slam_resample_maps(gms_slam *s, double r01, int32_t *indices, int32_t *n
  * happened.  The threshold is fraction * n in doubles; the reference's `numParticles / 2` is an integer division, so for an odd
  * particle count its threshold is half a particle lower than fraction = 0.5's. */
 int gms_slam_resample_maps_if(gms_slam *s, double r01, double fraction);
+/* The same for every filter of a handle (any S): r01 [S], indices [S][n] FILTER-LOCAL source indices and n_ambiguous [S] (either may be
+ * NULL); _if: each filter's rule decided on the device from its own Neff -- some filters may draw and others not, each keeps its own
+ * generation of the maps. */
+int gms_slam_resample_maps_batch(gms_slam *s, const double *r01, int32_t *indices, int32_t *n_ambiguous);
+int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fraction);
 /* ---- the reference-shape filter over several GPUs: particles WITH their maps, no replica ------------------------------------------
  * Rank r holds the contiguous block [r * n_local, (r + 1) * n_local) of the n_global particles (n_local a multiple of GMS_BLOCK) and
  * nothing else.  update(): gms_slam_update_local[_dev] (the per-particle body of SLAM.java:88-107 for this block; the motion model's
@@ -335,7 +358,7 @@ int gms_slam_resample_maps_if(gms_slam *s, double r01, double fraction);
  * generation and the received records.  The collectives stay with the caller (gridmap_slam_robot_amd/distributed.py:
  * ShardedSlamParticleMaps over torch.distributed = RCCL).  Poses, weights and every map equal the one-GPU gms_slam's for any number of
  * ranks.  A sharded handle needs the class planes (see gms_slam_create_shard's error text); its likelihoodData is produced on demand. */
-int gms_slam_create_shard(const gms_params *p, int32_t n_local, int64_t offset, int64_t n_global, gms_slam **out);
+int gms_slam_create_shard(const gms_params *p, int32_t n_local, int64_t offset, int64_t n_global, gms_slam **out);   /* p->n_maps == 1 */
 int gms_slam_update_local(gms_slam *s, const gms_beam *beams, int32_t B, int32_t sample_motion, double d_center, double d_theta, uint64_t seed,
                           uint64_t sequence);
 int gms_slam_update_local_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
@@ -357,12 +380,14 @@ int gms_slam_update_sharded_maps(gms_slam *s, gms_comm *c, const gms_beam *beams
 int gms_slam_resample_sharded_maps(gms_slam *s, gms_comm *c, double r01, double fraction, int32_t *did);
 int gms_slam_plan_exchange(const int32_t *all_sources, int32_t world, int32_t rank, int32_t n_local, int32_t *send_counts, int32_t *send_lists,
                            int32_t *recv_counts, int32_t *src_local, int32_t *recv_pos);
-/* Particle i's GridMapData (SLAM.java:33; GridMap.java:72-74): W * H doubles each, either pointer may be NULL. */
+/* Particle i's GridMapData (SLAM.java:33; GridMap.java:72-74): W * H doubles each, either pointer may be NULL.  A batched handle: i over
+ * [S * n], filter f's particle k = f * n + k; download_maps gives [S][n][H][W]. */
 int gms_slam_download_map(gms_slam *s, int32_t i, double *log_data, double *lik);
 int gms_slam_upload_map(gms_slam *s, int32_t i, const double *log_data, const double *lik);
 int gms_slam_download_maps(gms_slam *s, double *log_all, double *lik_all);        /* all particles: [n][H][W] */
 /* GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458) over the particles' maps, likelihood field included (:457), into the
- * GridMapData of the handle's own map (gms_slam_handles -> gms_map_download_log / gms_map_download_likelihood). */
+ * GridMapData of the handle's own map (gms_slam_handles -> gms_map_download_log / gms_map_download_likelihood); a batched handle: filter
+ * f's into map f of it. */
 int gms_slam_combined(gms_slam *s);
 /* Diagnostics: the cell walk of integrateObservation(p.m, z, p.pose) (SLAM.java:105 -> GridMap.java:173-228) for particle i at its
  * current pose, exactly as the per-particle update kernel walks and classifies it, written out instead of counted: for beam b,
