@@ -207,12 +207,15 @@ def load() -> C.CDLL:
     sig("gms_slam_update_batch_dev", C.c_int, vp, vp, i32, vp, vp, vp, vp, C.c_uint64, sp)
     sig("gms_slam_resample_maps_batch", C.c_int, vp, vp, vp, vp)
     sig("gms_slam_resample_maps_if_batch", C.c_int, vp, vp, f64)
+    sig("gms_slam_frame_per_particle", C.c_int, vp, vp, vp, vp, i32, f64, f64, C.c_uint64, C.c_uint64, f64, f64, sp)
+    sig("gms_slam_frame_batch", C.c_int, vp, vp, vp, vp, i32, vp, vp, vp, C.c_uint64, vp, f64, sp)
     sig("gms_slam_download_map", C.c_int, vp, i32, vp, vp)
     sig("gms_slam_upload_map", C.c_int, vp, i32, vp, vp)
     sig("gms_slam_download_maps", C.c_int, vp, vp, vp)
     sig("gms_slam_combined", C.c_int, vp)
     sig("gms_slam_copies", C.c_int, vp, C.POINTER(C.c_int64))
     sig("gms_slam_trace_scan", C.c_int, vp, i32, vp, i32, vp, vp, i32, vp)
+    sig("gms_slam_last_beams", C.c_int, vp, i32, vp, i32, C.POINTER(C.c_int32))
     sig("gms_slam_create_shard", C.c_int, pp, i32, C.c_int64, C.c_int64, C.POINTER(vp))
     sig("gms_slam_update_local", C.c_int, vp, vp, i32, i32, f64, f64, C.c_uint64, C.c_uint64)
     sig("gms_slam_update_local_dev", C.c_int, vp, vp, i32, i32, f64, f64, C.c_uint64, C.c_uint64)

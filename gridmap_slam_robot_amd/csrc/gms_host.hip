@@ -618,6 +618,8 @@ int gms_stage_block(gms_map *m, StageRing &ring, const gms_beam *beams, int32_t 
 }
 int gms_ring_alloc(StageRing &r, size_t bytes) { return ring_alloc(r, bytes); }
 void gms_ring_free(StageRing &r) { ring_free(r); }
+int gms_ring_acquire(StageRing &r, void **out) { return ring_acquire(r, out); }
+int gms_ring_commit(StageRing &r, hipStream_t stream) { return ring_commit(r, stream); }
 extern "C" {
 
 static int stage_poses(gms_map *m, const float *poses) {

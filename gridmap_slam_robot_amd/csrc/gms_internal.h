@@ -347,7 +347,8 @@ struct gms_slam {
     int32_t *d_epoch;               // [n_filters] x {draws that ran so far, the last resample() drew}: filter f's current generation is d_epoch[2 f] & 1 (SlamBufs)
     int64_t copies_base;            // maps copied by resampling steps before the last reset (the rest: sum of d_epoch[2 f] * n_per)
     gms_beam *d_batch;              // [n_filters][max_beams] beams | [n_filters] SlamFilterArgs: a batched update's inputs (gms_slam_update_batch)
-    StageRing batch_ring;           // pinned staging of that block
+    StageRing batch_ring;           // pinned staging of that block, or of a frame's raw revolutions and table (gms_slam_frame_batch)
+    std::vector<int32_t> frame_counts;   // [n_filters] measurements of every filter's revolution in the last frame call (empty: none yet; gms_slam_last_beams)
     int32_t *d_plan;                // a shard's resample(): [3][n] device staging of {export list | local sources | positions in the received buffer}
     int32_t lazy_lik;               // resample() copies logData at once and likelihoodData when somebody asks for it: the next update's
                                     // computeLikelihoodMap overwrites every cell of it before anything on the path reads one (GMS_SLAM_LAZY_LIK_COPY=0: both at once)
@@ -383,6 +384,9 @@ int gms_stage_block(gms_map *m, StageRing &ring, const gms_beam *beams, int32_t 
                     void *dst);
 int gms_ring_alloc(StageRing &r, size_t bytes);
 void gms_ring_free(StageRing &r);
+// the ring's next slot, free for the host to fill; commit after enqueueing whatever reads it on `stream` (gms_host.hip)
+int gms_ring_acquire(StageRing &r, void **out);
+int gms_ring_commit(StageRing &r, hipStream_t stream);
 
 // ---- kernel launchers (gms_map_kernels.hip / gms_pf_kernels.hip) -----------------------------
 
@@ -451,6 +455,11 @@ void gms_launch_pf_resample_seq(gms_pf *pf, double fraction);
 // one GridMapData per particle (gms_slam_kernels.hip); the buffers' current generation is read on the device (SlamBufs)
 SlamBufs gms_slam_bufs(const gms_slam *s);
 void gms_launch_slam_likelihood(gms_map *m, const SlamBufs &sb, int32_t n);
+// the de-skew of a frame call: one raw revolution (tab_src NULL: length, d_center, d_theta) into d_out, or S of them -- rows of L raw
+// measurements, filter f's length and odometry from tab_src[f], which the launch also copies to tab_dst[f] -- into rows of out_pitch beams
+void gms_launch_slam_deskew(gms_map *m, const double *angle, const double *distance, const uint8_t *hit, int32_t L, int32_t S, int32_t Lmax,
+                            int32_t length, double d_center, double d_theta, const SlamFilterArgs *tab_src, SlamFilterArgs *tab_dst, gms_beam *d_out,
+                            int32_t out_pitch);
 // batch (may be NULL): the filters' own beams, counts, motion and skipUpdate (B is then the largest count, motion non-NULL: the sequence)
 void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, bool field_in_memory, const MotionModel *motion,
                               int32_t integrate, int64_t code_words, const SlamBatch *batch = nullptr);

@@ -274,6 +274,43 @@ int gms_slam_update_per_particle(gms_slam *s, const gms_beam *beams, int32_t B, 
     return gms_slam_update_per_particle_dev(s, s->map->d_beams, B, sample_motion, d_center, d_theta, seed, sequence, stats);
 }
 
+// the staging of a batched handle, made by its first batched call: d_batch = [S][max_beams] beams | [S] SlamFilterArgs, and the pinned ring
+// whose slots hold that block or a frame's raw revolutions with the table behind them (17 bytes per measurement: never more than the beams)
+static int slam_batch_staging(gms_slam *s, const char *what) {
+    if (s->d_batch) return GMS_OK;
+    const size_t S = (size_t)s->n_filters, mb = (size_t)s->map->max_beams;
+    const size_t bytes = std::max(S * mb * sizeof(gms_beam), ((S * mb * 17 + 15) & ~(size_t)15)) + S * sizeof(SlamFilterArgs);
+    if (hipMalloc(&s->d_batch, bytes) != hipSuccess || gms_ring_alloc(s->batch_ring, bytes) != GMS_OK) {
+        hipFree(s->d_batch); s->d_batch = nullptr; gms_ring_free(s->batch_ring);
+        return gms_fail(GMS_ERR_NOMEM, "%s: staging allocation failed", what);
+    }
+    return GMS_OK;
+}
+static SlamFilterArgs *slam_batch_tab(const gms_slam *s) {
+    return reinterpret_cast<SlamFilterArgs *>(s->d_batch + (size_t)s->n_filters * s->map->max_beams);
+}
+// one filter's row of the table: odometry {dCenter, dTheta}
+static SlamFilterArgs slam_filter_args(const double *odometry, uint64_t seed, int32_t count, bool sample_motion) {
+    SlamFilterArgs a;
+    a.d_center = odometry[0]; a.d_theta = odometry[1];
+    a.d_center_sd = (0.01 + fabs(a.d_center) * 0.05) / 2;                              // Odometry.java:63 (as gms_launch_slam_particle)
+    a.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(a.d_theta);            // :64
+    a.seed = seed;
+    a.count = count;
+    a.flags = (sample_motion ? 1 : 0) | (slam_skip_update(a.d_theta) ? 0 : 2);
+    return a;
+}
+// update() of every filter once the table is on its way to slam_batch_tab: filter f's beams at d_beams + f * beam_stride
+static int slam_update_staged_batch(gms_slam *s, const gms_beam *d_beams, int32_t beam_stride, int32_t Bmax, uint64_t sequence, gms_pf_stats *stats) {
+    SlamBatch bt;
+    bt.tab = slam_batch_tab(s); bt.n = s->n_per; bt.beam_stride = beam_stride;
+    MotionModel mo;                                    // (the kernels take the odometry and seed from the table; the draw where its flag says so)
+    mo.d_center = 0.0; mo.d_theta = 0.0; mo.seed = 0; mo.sequence = sequence;
+    int rc = slam_update_core(s, d_beams, Bmax, &mo, false, &bt);
+    if (rc) return rc;
+    return gms_pf_normalize(s->pf, stats);
+}
+
 // SLAM.update(z, u) of every filter of the handle (filter f: beams [f][0 .. counts[f]) of the [S][B] block, odometry [f][2], seeds[f],
 // sample_motion[f]; one sequence).  One filter: exactly the scalar call.  Several: one launch of each update kernel for all of them, the
 // filters' table (SlamFilterArgs) in the same copy as the beams where those come from the host (on_device: the beams are the caller's)
@@ -300,34 +337,15 @@ static int slam_update_batch(gms_slam *s, const gms_beam *beams, bool on_device,
         if (!rc) rc = gms_slam_update_per_particle_dev(s, d, c, sample_motion[0], odometry[0], odometry[1], seeds[0], sequence, stats);
         return rc;
     }
-    if (!s->d_batch) {                                 // (first batched update: [S][max_beams] beams | [S] SlamFilterArgs, and their pinned ring)
-        const size_t bytes = (size_t)S * m->max_beams * sizeof(gms_beam) + (size_t)S * sizeof(SlamFilterArgs);
-        if (hipMalloc(&s->d_batch, bytes) != hipSuccess || gms_ring_alloc(s->batch_ring, bytes) != GMS_OK) {
-            hipFree(s->d_batch); s->d_batch = nullptr; gms_ring_free(s->batch_ring);
-            return gms_fail(GMS_ERR_NOMEM, "gms_slam_update_batch: staging allocation failed");
-        }
-    }
+    int rc = slam_batch_staging(s, "gms_slam_update_batch");
+    if (rc) return rc;
     std::vector<SlamFilterArgs> tab((size_t)S);
-    for (int32_t f = 0; f < S; f++) {
-        SlamFilterArgs &a = tab[f];
-        a.d_center = odometry[2 * (size_t)f]; a.d_theta = odometry[2 * (size_t)f + 1];
-        a.d_center_sd = (0.01 + fabs(a.d_center) * 0.05) / 2;                          // Odometry.java:63 (as gms_launch_slam_particle)
-        a.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(a.d_theta);        // :64
-        a.seed = seeds[f];
-        a.count = counts ? counts[f] : B;
-        a.flags = (sample_motion[f] ? 1 : 0) | (slam_skip_update(a.d_theta) ? 0 : 2);
-    }
-    SlamFilterArgs *d_tab = reinterpret_cast<SlamFilterArgs *>(s->d_batch + (size_t)S * m->max_beams);
-    int rc = gms_stage_block(m, s->batch_ring, on_device ? nullptr : beams, B, S, m->max_beams, tab.data(), tab.size() * sizeof(SlamFilterArgs),
-                             on_device ? static_cast<void *>(d_tab) : static_cast<void *>(s->d_batch));
+    for (int32_t f = 0; f < S; f++) tab[f] = slam_filter_args(odometry + 2 * (size_t)f, seeds[f], counts ? counts[f] : B, sample_motion[f] != 0);
+    SlamFilterArgs *d_tab = slam_batch_tab(s);
+    rc = gms_stage_block(m, s->batch_ring, on_device ? nullptr : beams, B, S, m->max_beams, tab.data(), tab.size() * sizeof(SlamFilterArgs),
+                         on_device ? static_cast<void *>(d_tab) : static_cast<void *>(s->d_batch));
     if (rc) return rc;
-    SlamBatch bt;
-    bt.tab = d_tab; bt.n = s->n_per; bt.beam_stride = on_device ? B : m->max_beams;
-    MotionModel mo;                                    // (the kernels take the odometry and seed from the table; the draw where its flag says so)
-    mo.d_center = 0.0; mo.d_theta = 0.0; mo.seed = 0; mo.sequence = sequence;
-    rc = slam_update_core(s, on_device ? beams : s->d_batch, Bmax, &mo, false, &bt);
-    if (rc) return rc;
-    return gms_pf_normalize(s->pf, stats);
+    return slam_update_staged_batch(s, on_device ? beams : s->d_batch, on_device ? B : m->max_beams, Bmax, sequence, stats);
 }
 
 int gms_slam_update_batch(gms_slam *s, const gms_beam *beams, int32_t B, const int32_t *counts, const double *odometry, const uint64_t *seeds,
@@ -490,6 +508,104 @@ int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fract
     if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_resample_maps_if_batch: a shard of a filter (gms_slam_shard_draw / export / gather)");
     REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if_batch: fraction must be non-negative");
     return slam_resample(s, r01, fraction, nullptr, nullptr);
+}
+
+// One recorded revolution as GridMapApp.onHandleData treats it (J/app/GridMapApp.java:133-192) for the filter with a map per particle:
+// the de-skew (:143-175), SLAM.update(z, u) (:178) and `if (neff < fraction * n) resample()` (:185-186) as one call -- what
+// gms_map_deskew on the handle's map, gms_slam_update_per_particle_dev and gms_slam_resample_maps_if do in three, the same bits.  The raw
+// revolution goes into a slot of the map's pinned ring and is read there by the de-skew launch (as gms_map_deskew does).
+int gms_slam_frame_per_particle(gms_slam *s, const double *angle, const double *distance, const uint8_t *hit, int32_t length, double d_center,
+                                double d_theta, uint64_t seed, uint64_t sequence, double r01, double resample_fraction, gms_pf_stats *stats) {
+    REQUIRE(s, "gms_slam_frame_per_particle: null handle");
+    REQUIRE(angle && distance && hit, "gms_slam_frame_per_particle: null argument (angle, distance and hit are required)");
+    if (pf_is_shard(s->pf))
+        return gms_fail(GMS_ERR_STATE, "gms_slam_frame_per_particle: a shard of a filter (de-skew, gms_slam_update_local[_dev] and the exchanges stay with the caller)");
+    int rc = refuse_batched(s, "gms_slam_frame_per_particle");
+    if (rc) return rc;
+    gms_map *m = s->map;
+    if (length <= 0 || length > m->max_beams)
+        return gms_fail(GMS_ERR_INVALID, "gms_slam_frame_per_particle: length = %d outside 1 .. gms_params.max_beams (%d)", length, m->max_beams);
+    REQUIRE((size_t)length * 17 + 16 <= (size_t)m->max_beams * sizeof(gms_beam), "gms_slam_frame_per_particle: scan too long for the staging buffer");
+    HIPCHK(hipSetDevice(m->device));
+    void *slot = nullptr;
+    rc = gms_ring_acquire(m->beam_ring, &slot);
+    if (rc) return rc;
+    double *h_a = static_cast<double *>(slot), *h_d = h_a + length;
+    uint8_t *h_h = reinterpret_cast<uint8_t *>(h_d + length);
+    memcpy(h_a, angle, (size_t)length * 8); memcpy(h_d, distance, (size_t)length * 8); memcpy(h_h, hit, (size_t)length);
+    gms_launch_slam_deskew(m, h_a, h_d, h_h, length, 1, length, length, d_center, d_theta, nullptr, nullptr, m->d_beams, m->max_beams);
+    rc = gms_ring_commit(m->beam_ring, m->stream);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    s->frame_counts.assign(1, length);
+    rc = gms_slam_update_per_particle_dev(s, m->d_beams, length, 1, d_center, d_theta, seed, sequence, stats);      // :178 (stats: synchronises)
+    if (!rc && resample_fraction >= 0.0) rc = slam_resample(s, &r01, resample_fraction, nullptr, nullptr);          // :185-186
+    return rc;
+}
+
+// The same for every filter of a handle: angle / distance / hit [S][L], filter f's revolution its first lengths[f] measurements (NULL:
+// all L), de-skewed with its own length and odometry[f] in ONE launch, then gms_slam_update_batch_dev with every filter drawing its
+// motion sample and gms_slam_resample_maps_if_batch.  The raw rows and the filters' table share one slot of the pinned ring; the
+// de-skew launch reads both in place and carries the table over to the device for the update kernels behind it.
+int gms_slam_frame_batch(gms_slam *s, const double *angle, const double *distance, const uint8_t *hit, int32_t L, const int32_t *lengths,
+                         const double *odometry, const uint64_t *seeds, uint64_t sequence, const double *r01, double resample_fraction,
+                         gms_pf_stats *stats) {
+    REQUIRE(s, "gms_slam_frame_batch: null handle");
+    REQUIRE(angle && distance && hit && odometry && seeds && r01,
+            "gms_slam_frame_batch: null argument (angle, distance, hit, odometry, seeds and r01 are required)");
+    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_frame_batch: a shard of a filter (de-skew, gms_slam_update_local[_dev] and the exchanges stay with the caller)");
+    gms_map *m = s->map;
+    const int32_t S = s->n_filters;
+    if (L <= 0 || L > m->max_beams) return gms_fail(GMS_ERR_INVALID, "gms_slam_frame_batch: L = %d outside 1 .. gms_params.max_beams (%d)", L, m->max_beams);
+    int32_t Lmax = 0;
+    for (int32_t f = 0; f < S; f++) {
+        const int32_t c = lengths ? lengths[f] : L;
+        if (c < 1 || c > L) return gms_fail(GMS_ERR_INVALID, "gms_slam_frame_batch: lengths[%d] = %d outside 1 .. L (%d)", f, c, L);
+        Lmax = std::max(Lmax, c);
+    }
+    if (S == 1)
+        return gms_slam_frame_per_particle(s, angle, distance, hit, Lmax, odometry[0], odometry[1], seeds[0], sequence, r01[0], resample_fraction, stats);
+    HIPCHK(hipSetDevice(m->device));
+    int rc = slam_batch_staging(s, "gms_slam_frame_batch");
+    if (rc) return rc;
+    void *slot = nullptr;
+    rc = gms_ring_acquire(s->batch_ring, &slot);
+    if (rc) return rc;
+    // [S][L] angle | [S][L] distance | [S][L] hit | (to a 16-byte boundary) [S] SlamFilterArgs
+    const size_t SL = (size_t)S * (size_t)L;
+    double *h_a = static_cast<double *>(slot), *h_d = h_a + SL;
+    uint8_t *h_h = reinterpret_cast<uint8_t *>(h_d + SL);
+    SlamFilterArgs *h_tab = reinterpret_cast<SlamFilterArgs *>(static_cast<unsigned char *>(slot) + ((SL * 17 + 15) & ~(size_t)15));
+    memcpy(h_a, angle, SL * 8); memcpy(h_d, distance, SL * 8); memcpy(h_h, hit, SL);
+    s->frame_counts.resize((size_t)S);
+    for (int32_t f = 0; f < S; f++) {
+        s->frame_counts[f] = lengths ? lengths[f] : L;
+        h_tab[f] = slam_filter_args(odometry + 2 * (size_t)f, seeds[f], s->frame_counts[f], true);
+    }
+    gms_launch_slam_deskew(m, h_a, h_d, h_h, L, S, Lmax, 0, 0.0, 0.0, h_tab, slam_batch_tab(s), s->d_batch, m->max_beams);
+    rc = gms_ring_commit(s->batch_ring, m->stream);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    rc = slam_update_staged_batch(s, s->d_batch, m->max_beams, Lmax, sequence, stats);
+    if (!rc && resample_fraction >= 0.0) rc = slam_resample(s, r01, resample_fraction, nullptr, nullptr);
+    return rc;
+}
+
+// Diagnostics: filter f's de-skewed revolution of the last frame call, out [cap] beams, *count its length.  Holds until the next call
+// that stages a scan on this handle.  Synchronises.
+int gms_slam_last_beams(gms_slam *s, int32_t f, gms_beam *out, int32_t cap, int32_t *count) {
+    REQUIRE(s && out && count, "gms_slam_last_beams: null argument");
+    REQUIRE(f >= 0 && f < s->n_filters, "gms_slam_last_beams: filter index out of range");
+    if (s->frame_counts.size() != (size_t)s->n_filters) return gms_fail(GMS_ERR_STATE, "gms_slam_last_beams: no frame call has run on this handle");
+    const int32_t c = s->frame_counts[(size_t)f];
+    REQUIRE(cap >= c, "gms_slam_last_beams: capacity below the revolution's length");
+    gms_map *m = s->map;
+    HIPCHK(hipSetDevice(m->device));
+    const gms_beam *src = s->n_filters == 1 ? m->d_beams : s->d_batch + (size_t)f * m->max_beams;
+    HIPCHK(hipMemcpyAsync(out, src, (size_t)c * sizeof(gms_beam), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    *count = c;
+    return GMS_OK;
 }
 
 static int slam_map_xfer(gms_slam *s, int32_t i, int32_t count, double *dev_base, double *host, bool to_device) {

@@ -22,6 +22,8 @@
 //                       `logData[c] += ...` (GridMap.java:223) is applied from that tile straight to the particle's rows: no count grid
 //                       in memory, no global atomic, touched cells read and written once
 //   k_slam_gather_maps  resample()'s deep copies: map[m] <- map[idx[m]] for both arrays, a pure HBM stream (32 bytes per cell)
+//   k_slam_deskew       the de-skew in front of update() where the caller hands over a raw revolution (GridMapApp.java:143-175): one
+//                       revolution, or every filter's own in one launch (gms_slam_frame_per_particle / gms_slam_frame_batch)
 #include "gms_device.h"
 
 // a generation's arrays out of SlamBufs by SELECTION, never by a run-time index into the by-value kernel argument (that moves the
@@ -1462,6 +1464,39 @@ bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, cons
 #undef SR_LAUNCH
 #undef SR_LAUNCH1
     return true;
+}
+
+// The de-skew loop of GridMapApp.onHandleData (J/app/GridMapApp.java:143-175) in front of SLAM.update, deskew_body as k_deskew runs it:
+// the same bits.  BATCH: workgroups [ceil(Lmax / 256)][S]; filter f = blockIdx.y de-skews the first tab_src[f].count measurements of its
+// row of the [S][L] raw arrays with ITS OWN count (the d_i of :150 divides by it) and odometry into its row of `out`; nothing beyond
+// that count is read or written.  The raw arrays and tab_src are the pinned ring slot, read in place; the filters' table is needed by the
+// update kernels behind this launch, so row 0's first lanes carry tab_src[f] over to tab_dst[f] (three 16-byte words).
+template <bool BATCH>
+__global__ void __launch_bounds__(256)
+k_slam_deskew(const double *__restrict__ angle, const double *__restrict__ distance, const uint8_t *__restrict__ hit, int32_t L, int32_t length,
+              double d_center, double d_theta, const SlamFilterArgs *__restrict__ tab_src, SlamFilterArgs *__restrict__ tab_dst,
+              gms_beam *__restrict__ out, int32_t out_pitch) {
+    if constexpr (BATCH) {
+        const uint32_t f = blockIdx.y;
+        constexpr uint32_t words = sizeof(SlamFilterArgs) / 16;
+        if (blockIdx.x == 0 && threadIdx.x < words)
+            reinterpret_cast<uint4 *>(tab_dst + f)[threadIdx.x] = reinterpret_cast<const uint4 *>(tab_src + f)[threadIdx.x];
+        length = tab_src[f].count; d_center = tab_src[f].d_center; d_theta = tab_src[f].d_theta;
+        const size_t row = (size_t)f * (size_t)L;
+        angle += row; distance += row; hit += row;
+        out += (size_t)f * (size_t)out_pitch;
+    }
+    deskew_body(angle, distance, hit, length, d_center, d_theta, out, (int32_t)(blockIdx.x * 256u + threadIdx.x));
+}
+void gms_launch_slam_deskew(gms_map *m, const double *angle, const double *distance, const uint8_t *hit, int32_t L, int32_t S, int32_t Lmax,
+                            int32_t length, double d_center, double d_theta, const SlamFilterArgs *tab_src, SlamFilterArgs *tab_dst, gms_beam *d_out,
+                            int32_t out_pitch) {
+    const dim3 grid((unsigned)((Lmax + 255) / 256), (unsigned)S);
+    if (tab_src)
+        hipLaunchKernelGGL(k_slam_deskew<true>, grid, dim3(256), 0, m->stream, angle, distance, hit, L, 0, 0.0, 0.0, tab_src, tab_dst, d_out, out_pitch);
+    else
+        hipLaunchKernelGGL(k_slam_deskew<false>, grid, dim3(256), 0, m->stream, angle, distance, hit, L, length, d_center, d_theta, tab_src, tab_dst,
+                           d_out, out_pitch);
 }
 
 void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const int32_t *d_idx, int32_t *d_idx_keep, int64_t code_words) {

@@ -826,6 +826,37 @@ class SLAMParticleMaps:
         check(load().gms_slam_update_per_particle_dev(self._h, C.c_void_p(dev_beams), B, int(have), float(dc), float(dt), int(seed),
                                                       int(sequence), None))
 
+    def frame(self, angles, distances, hits, d_center: float, d_theta: float, seed: int = 0, sequence: Optional[int] = None,
+              r01: Optional[float] = None, fraction: float = 0.5, fetch: bool = False):
+        """One recorded revolution as GridMapApp.onHandleData treats it (J/app/GridMapApp.java:133-192) in one call: the de-skew of the
+        raw measurements (:143-175), update(z, u) (:178) and `if (neff < fraction * n) resample()` (:185-186; fraction < 0: no
+        resampling).  The same bits as grid_map.deskew -> update_dev -> resample_if.  fetch: returns update()'s Neff (synchronises)."""
+        a = np.ascontiguousarray(angles, dtype=np.float64)
+        d = np.ascontiguousarray(distances, dtype=np.float64)
+        h = np.ascontiguousarray(hits, dtype=np.uint8)
+        if not (a.ndim == d.ndim == h.ndim == 1 and a.size == d.size == h.size):
+            raise ValueError("frame: angles, distances and hits must be one-dimensional and of one length")
+        if sequence is None:
+            sequence = self.sequence
+            self.sequence += 1
+        r = float(np.random.random() if r01 is None else r01)
+        st = GmsPfStats()
+        check(load().gms_slam_frame_per_particle(self._h, ptr(a), ptr(d), ptr(h), a.size, float(d_center), float(d_theta), int(seed),
+                                                 int(sequence), r, float(fraction), C.byref(st) if fetch else None))
+        if fetch:
+            self.strongest, self.neff = st.strongest, st.neff
+            self.last_stats = {"weight_sum": st.weight_sum, "neff": st.neff, "strongest": st.strongest, "n_zero": st.n_zero,
+                               "max_log_weight": st.max_log_weight}
+            return st.neff
+        return None
+
+    def last_beams(self) -> np.ndarray:
+        """the de-skewed revolution of the last frame() call (diagnostics; synchronises)"""
+        out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
+        c = C.c_int32(0)
+        check(load().gms_slam_last_beams(self._h, 0, ptr(out), len(out), C.byref(c)))
+        return out[:c.value].copy()
+
     def resample(self, r01: Optional[float] = None, want_indices: bool = False):
         """resample() (:133-153): r01 stands for Math.random()"""
         r = float(np.random.random() if r01 is None else r01)
@@ -1001,6 +1032,43 @@ class SLAMParticleMapsBatch:
         have = np.ascontiguousarray(have.astype(np.int32))
         check(load().gms_slam_update_batch_dev(self._h, C.c_void_p(dev_beams), int(B), None if c is None else ptr(c), ptr(u),
                                                ptr(self._per_filter(seeds, np.uint64)), ptr(have), int(sequence), None))
+
+    def frame(self, angles, distances, hits, odometry, seeds=0, sequence: Optional[int] = None, r01=None, fraction: float = 0.5,
+              lengths=None, fetch: bool = False):
+        """One recorded revolution per filter (GridMapApp.java:133-192) in one call: angles / distances / hits [S][L], filter f's
+        revolution its first lengths[f] measurements (None: all L), de-skewed with its own length and odometry[f] = (dCenter, dTheta),
+        then update(z, u) of every filter and the rule `if (neff < fraction * n) resample()` per filter (fraction < 0: no resampling).
+        Filter f computes what a stand-alone SLAMParticleMaps.frame does.  fetch: the filters' Neff [S] (synchronises)."""
+        S = self.num_filters
+        a = np.ascontiguousarray(angles, dtype=np.float64)
+        d = np.ascontiguousarray(distances, dtype=np.float64)
+        h = np.ascontiguousarray(hits, dtype=np.uint8)
+        if not (a.ndim == 2 and a.shape[0] == S and a.shape == d.shape == h.shape):
+            raise ValueError(f"frame: angles, distances and hits must be [S][L] arrays of one shape for {S} filters")
+        u = np.ascontiguousarray(np.asarray(odometry, dtype=np.float64).reshape(S, 2))
+        ln = None if lengths is None else self._per_filter(lengths, np.int32)
+        sd = self._per_filter(seeds, np.uint64)
+        r = self._per_filter(np.random.random(S) if r01 is None else r01, np.float64)
+        if sequence is None:
+            sequence = self.sequence
+            self.sequence += 1
+        st = (GmsPfStats * S)()
+        check(load().gms_slam_frame_batch(self._h, ptr(a), ptr(d), ptr(h), a.shape[1], None if ln is None else ptr(ln), ptr(u), ptr(sd),
+                                          int(sequence), ptr(r), float(fraction), st if fetch else None))
+        if not fetch:
+            return None
+        self.last_stats = [{"weight_sum": s.weight_sum, "neff": s.neff, "strongest": s.strongest, "n_zero": s.n_zero,
+                            "max_log_weight": s.max_log_weight} for s in st]
+        self.strongest = np.array([s.strongest for s in st], dtype=np.int64)
+        self.neff = np.array([s.neff for s in st], dtype=np.float64)
+        return self.neff.copy()
+
+    def last_beams(self, f: int) -> np.ndarray:
+        """filter f's de-skewed revolution of the last frame() call (diagnostics; synchronises)"""
+        out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
+        c = C.c_int32(0)
+        check(load().gms_slam_last_beams(self._h, int(f), ptr(out), len(out), C.byref(c)))
+        return out[:c.value].copy()
 
     def resample(self, r01=None, want_indices: bool = False):
         """resample() of every filter; r01 [S] (or one for all).  want_indices: (indices [S][n] filter-local, n_ambiguous [S])"""

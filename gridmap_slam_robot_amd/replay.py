@@ -2,14 +2,16 @@
 revolution (J/app/GridMapApp.java:133-192) -- de-skew the raw measurements with the frame's odometry (:143-175), then
 SLAM.update(z, u) (J/slam/SLAM.java:80-131: motion-model sample per particle, weight, map update at the filter's pose) and
 `if (neff < N / 2) resample()` (:185-186).  Here: gms_slam_frame, one call per frame (= gms_map_deskew -> gms_pf_sample_motion ->
-gms_slam_update_dev), the scan handed over as the recording's raw host arrays, everything else resident on the device."""
+gms_slam_update_dev), the scan handed over as the recording's raw host arrays, everything else resident on the device.
+ParticleMapsReplay / ParticleMapsBatchReplay are the same for the filter of the reference's own shape, one GridMapData per particle:
+gms_slam_frame_per_particle / gms_slam_frame_batch, one call per revolution."""
 from __future__ import annotations
 
 import math
 
 import numpy as np
 
-from .gridmap import GridMap, ParticleFilter
+from .gridmap import GridMap, ParticleFilter, SLAMParticleMaps, SLAMParticleMapsBatch
 from .synth import dead_reckon
 from .trace import Frame
 
@@ -43,3 +45,63 @@ class TraceReplay:
             self.pf.sample_motion(f.d_center, f.d_theta, self.seed, self.frame_no)                 # SLAM.java:90, 155-163
             self.pf.slam_update_dev(0, dev, B, r01, self.fraction, integrate)                      # :87-131 + GridMapApp.java:185-186
         self.frame_no += 1
+
+
+class ParticleMapsReplay:
+    """The counterpart of TraceReplay for SLAMParticleMaps: every revolution is ONE frame() call (de-skew, update(z, u), the
+    resampling rule), nothing read back.  The reference starts every particle at Pose(0, 0, 0) (SLAM.java:65-77); start_pose puts them
+    where a recording's drive begins instead."""
+
+    def __init__(self, slam: SLAMParticleMaps, seed: int = 2024, resample_fraction: float = 0.5, start_pose=None):
+        self.slam, self.seed, self.fraction = slam, seed, resample_fraction
+        self.pose = np.zeros(3, dtype=np.float32) if start_pose is None else np.asarray(start_pose, dtype=np.float32)
+        self.frame_no = 0
+        if start_pose is not None:
+            slam.set_poses(np.broadcast_to(self.pose, (slam.num_particles, 3)).copy())
+
+    def bootstrap(self, f: Frame):
+        """A mapping-only frame (as TraceReplay.bootstrap): every particle sits at the dead-reckoned pose and integrates the scan into
+        its own map there; no motion sample, no resampling.  (Over blank maps a scan of 360 beams weighs every particle 0.1^360 = 0 and
+        update() divides 0 by 0, as the reference does: the weights are rewritten by the next update.)"""
+        self.pose = dead_reckon(self.pose, f.d_center, f.d_theta)
+        self.slam.set_poses(np.broadcast_to(self.pose, (self.slam.num_particles, 3)).copy())
+        obs = self.slam.grid_map.deskew(f.angle, f.distance, f.hit, f.d_center, f.d_theta)         # GridMapApp.java:143-175
+        self.slam.update(obs, (f.d_center, f.d_theta), sequence=self.frame_no, fetch=False, sample_motion=False)
+        self.frame_no += 1
+
+    def step(self, f: Frame, r01: float, fetch: bool = False):
+        """One recorded revolution through the filter (GridMapApp.java:143-192)."""
+        out = self.slam.frame(f.angle, f.distance, f.hit, f.d_center, f.d_theta, seed=self.seed, sequence=self.frame_no, r01=r01,
+                              fraction=self.fraction, fetch=fetch)
+        self.frame_no += 1
+        return out
+
+
+class ParticleMapsBatchReplay:
+    """S recordings, one per filter of a SLAMParticleMapsBatch, stepped together: every step is ONE frame() call for all of them.
+    Frames of unequal measurement counts are padded to the longest and go through `lengths`."""
+
+    def __init__(self, slam: SLAMParticleMapsBatch, seeds=2024, resample_fraction: float = 0.5, start_poses=None):
+        self.slam, self.fraction = slam, resample_fraction
+        S = slam.num_filters
+        self.seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (S,)))
+        self.frame_no = 0
+        if start_poses is not None:
+            P = np.asarray(start_poses, dtype=np.float32).reshape(S, 1, 3)
+            slam.set_poses(np.ascontiguousarray(np.broadcast_to(P, (S, slam.num_particles, 3))))
+
+    def step(self, frames, r01, fetch: bool = False):
+        """frames: S Frame objects, filter f's revolution frames[f]; r01 [S] (or one for all)"""
+        S = self.slam.num_filters
+        if len(frames) != S:
+            raise ValueError(f"step: {len(frames)} frames for {S} filters")
+        lengths = np.array([len(f.angle) for f in frames], dtype=np.int32)
+        L = int(lengths.max())
+        a, d, h = np.zeros((S, L)), np.zeros((S, L)), np.zeros((S, L), dtype=np.uint8)
+        for k, f in enumerate(frames):
+            a[k, :lengths[k]], d[k, :lengths[k]], h[k, :lengths[k]] = f.angle, f.distance, f.hit
+        odo = np.array([(f.d_center, f.d_theta) for f in frames], dtype=np.float64)
+        out = self.slam.frame(a, d, h, odo, seeds=self.seeds, sequence=self.frame_no, r01=r01, fraction=self.fraction, lengths=lengths,
+                              fetch=fetch)
+        self.frame_no += 1
+        return out

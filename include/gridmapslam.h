@@ -345,6 +345,24 @@ int gms_slam_resample_maps_if(gms_slam *s, double r01, double fraction);
  * generation of the maps. */
 int gms_slam_resample_maps_batch(gms_slam *s, const double *r01, int32_t *indices, int32_t *n_ambiguous);
 int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fraction);
+/* One recorded revolution as GridMapApp.onHandleData treats it (J/app/GridMapApp.java:133-192), for this filter, in one call: the raw
+ * polar measurements are de-skewed with the frame's odometry (:143-175), then SLAM.update(z, u) (:178; skipUpdate decided from d_theta,
+ * the pose refinement if gms_slam_set_refine is on) and `if (neff < resample_fraction * n) resample()` (:185-186; resample_fraction < 0
+ * skips it).  Bit-identical to gms_map_deskew on the handle's map, gms_slam_update_per_particle_dev with sample_motion = 1 and
+ * gms_slam_resample_maps_if, in that order; one small de-skew launch in front of the update's.  angle / distance / hit [length] are
+ * host arrays and may be reused on return.  stats (may be NULL: nothing is read back, no synchronise; when given the call synchronises)
+ * receives SLAM.update's return values, i.e. the Neff BEFORE the resampling.  One filter, not a shard. */
+int gms_slam_frame_per_particle(gms_slam *s, const double *angle, const double *distance, const uint8_t *hit, int32_t length, double d_center,
+                                double d_theta, uint64_t seed, uint64_t sequence, double r01, double resample_fraction, gms_pf_stats *stats);
+/* The same for every filter of a handle (any S; S = 1 runs the scalar call): angle / distance / hit [S][L], row pitch L; filter f's
+ * revolution is its first lengths[f] measurements (1 .. L; lengths may be NULL: all L) and is de-skewed with ITS OWN length (the d_i of
+ * GridMapApp.java:150 divides by it) and odometry [f][2] {dCenter, dTheta} -- all S revolutions in one launch -- then
+ * gms_slam_update_batch_dev with every filter drawing its motion sample (seeds [S], one sequence) and gms_slam_resample_maps_if_batch
+ * (r01 [S]).  Every filter ends up bit-identical to a stand-alone handle of the same parameters and seed given
+ * gms_slam_frame_per_particle.  The raw revolutions and the filters' table travel as one staging copy.  stats [S] (may be NULL). */
+int gms_slam_frame_batch(gms_slam *s, const double *angle, const double *distance, const uint8_t *hit, int32_t L, const int32_t *lengths,
+                         const double *odometry, const uint64_t *seeds, uint64_t sequence, const double *r01, double resample_fraction,
+                         gms_pf_stats *stats);
 /* ---- the reference-shape filter over several GPUs: particles WITH their maps, no replica ------------------------------------------
  * Rank r holds the contiguous block [r * n_local, (r + 1) * n_local) of the n_global particles (n_local a multiple of GMS_BLOCK) and
  * nothing else.  update(): gms_slam_update_local[_dev] (the per-particle body of SLAM.java:88-107 for this block; the motion model's
@@ -394,6 +412,10 @@ int gms_slam_combined(gms_slam *s);
  * counts[b] cells in walk order (RayIterator.java:107-130), cells_xy / classes [B][cap] entries as gms_map_trace_scan (class 0 free,
  * 1 prior, 2 occupied; either may be NULL).  Touches no map.  Synchronises. */
 int gms_slam_trace_scan(gms_slam *s, int32_t i, const gms_beam *beams, int32_t B, int32_t *cells_xy, uint8_t *classes, int32_t cap, int32_t *counts);
+/* Diagnostics: filter f's de-skewed revolution as the last gms_slam_frame_per_particle / gms_slam_frame_batch call produced it, out
+ * [cap] beams, *count its length (GMS_ERR_STATE before the first frame call; it holds until the next call that stages a scan on this
+ * handle).  Synchronises. */
+int gms_slam_last_beams(gms_slam *s, int32_t f, gms_beam *out, int32_t cap, int32_t *count);
 /* maps copied by resampling steps since creation (measurement: bytes moved = copies * W * H * 32) */
 int gms_slam_copies(const gms_slam *s, int64_t *maps_copied);
 

@@ -323,6 +323,20 @@ public:
         strongest_ = st.strongest;
         return st.neff;
     }
+    /** GridMapApp.onHandleData for one raw revolution (J/app/GridMapApp.java:133-192) as one call: the de-skew (:143-175), update(z, u)
+     *  (:178) and `if (neff < fraction * n) resample()` (:185-186; fraction < 0: no resampling).  angle / distance / hit: `length`
+     *  measurements.  Nothing is read back and the stream is not synchronised; onHandleDataNeff is the form that returns update()'s Neff. */
+    void onHandleData(const double *angle, const double *distance, const uint8_t *hit, int length, const Odometry &u, uint64_t seed,
+                      uint64_t sequence, double r01, double fraction = 0.5) {
+        check(gms_slam_frame_per_particle(h_, angle, distance, hit, length, u.dCenter, u.dTheta, seed, sequence, r01, fraction, nullptr));
+    }
+    double onHandleDataNeff(const double *angle, const double *distance, const uint8_t *hit, int length, const Odometry &u, uint64_t seed,
+                            uint64_t sequence, double r01, double fraction = 0.5) {
+        gms_pf_stats st{};
+        check(gms_slam_frame_per_particle(h_, angle, distance, hit, length, u.dCenter, u.dTheta, seed, sequence, r01, fraction, &st));
+        strongest_ = st.strongest;
+        return st.neff;
+    }
     /** update(z, u) over all ranks of a sharded filter (every rank: the same scan, odometry, seed and sequence); returns Neff */
     double updateSharded(Comm &comm, const Observation &z, const Odometry &u, uint64_t seed, uint64_t sequence, bool sampleMotion = true) {
         gms_pf_stats st{};
