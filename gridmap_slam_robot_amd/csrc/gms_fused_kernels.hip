@@ -355,8 +355,8 @@ void gms_launch_raycast_norm_chunks(gms_pf *pf, const gms_beam *d_beams, int32_t
 void gms_launch_deskew_motion(gms_pf *pf, const double *d_angle, const double *d_distance, const uint8_t *d_hit, int32_t length,
                               double d_center, double d_theta, uint64_t seed, uint64_t sequence) {
     gms_map *m = pf->map;
-    const double d_center_sd = (0.01 + fabs(d_center) * 0.05) / 2;               // Odometry.java:63
-    const double d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(d_theta);   // :64
+    double d_center_sd, d_theta_sd;
+    motion_deviations(d_center, d_theta, &d_center_sd, &d_theta_sd);
     const uint32_t n_dk = (uint32_t)((length + 255) / 256), n_mo = (uint32_t)((pf->n + 255) / 256);
     hipLaunchKernelGGL(k_deskew_motion, dim3(n_dk + n_mo), dim3(256), 0, m->stream, d_angle, d_distance, d_hit, length, d_center,
                        d_theta, m->d_beams, n_dk, pf->d_pose, pf->d_cs, pf->n, pf->offset, d_center_sd, d_theta_sd, seed, sequence);

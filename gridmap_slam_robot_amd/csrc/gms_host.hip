@@ -956,7 +956,8 @@ int gms_pf_create(gms_map *m, int32_t n, gms_pf **out) {               // Partic
     return GMS_OK;
 }
 
-// the filter of a gms_slam: what would move its particles without their maps is refused (gms_slam's own calls set d_epoch2)
+// the filter of a gms_slam: what would move its particles without their maps is refused.  d_epoch2 is non-NULL only inside that
+// handle's own draw (slam_draw, gms_slam_host.hip), which moves the maps behind it
 static int refuse_owned_maps(const gms_pf *pf) {
     if (pf->slam_owned && !pf->d_epoch2)
         return gms_fail(GMS_ERR_STATE, "this filter's particles own maps (gms_slam): resample through gms_slam_resample_maps[_if], update through gms_slam_update_per_particle");
@@ -967,6 +968,10 @@ int gms_pf_set_shard(gms_pf *pf, int64_t offset, int64_t n_global) {
     REQUIRE(pf, "null filter");
     int rc = refuse_owned_maps(pf);
     if (rc) return rc;
+    return gms_pf_place_shard(pf, offset, n_global);
+}
+
+int gms_pf_place_shard(gms_pf *pf, int64_t offset, int64_t n_global) {
     REQUIRE(offset >= 0 && offset % GMS_BLOCK == 0, "shard offset must be a multiple of GMS_BLOCK");
     REQUIRE(n_global >= offset + pf->n && n_global <= GMS_MAX_PARTICLES, "shard does not fit n_global (at most GMS_MAX_PARTICLES in all)");
     HIPCHK(hipSetDevice(pf->map->device));

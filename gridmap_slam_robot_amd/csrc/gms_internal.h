@@ -223,7 +223,7 @@ struct gms_pf {
     int32_t score_spread;           // -1 the launcher decides (launches of two or more workgroups per CU), 0 / 1 forced (GMS_SCORE_SPREAD, read at creation)
     int32_t order_mode;             // -1 the launcher decides (large launches only), 0 never, 1 always (GMS_SCORE_ORDER; results do not depend on it)
     int32_t slam_owned;             // the filter of a gms_slam: its particles own maps, so resampling, sharding and the shared-map scan steps are refused on it
-    int32_t *d_epoch2;              // the filter of a gms_slam, during gms_slam_resample_maps[_if]: {draws that ran so far, the last resample() drew}, kept by the resampling kernels (NULL otherwise)
+    int32_t *d_epoch2;              // the filter of a gms_slam, inside its draw only (slam_draw): {draws that ran so far, the last resample() drew}, kept by the resampling kernels (NULL otherwise)
     // What the derived device data describes.  Written by the pf_* transitions below only (and pf_alloc_global / pf_free_global).
     // weights:
     int32_t pending_nseg;           // > 0: d_w / d_logw are stale, the weights are still d_part's pending_nseg segment products
@@ -335,6 +335,13 @@ struct SlamBatch {
     int32_t n, beam_stride;
 };
 
+// where the likelihoodData of a gms_slam's particles stands between the calls that write it
+enum SlamField : int32_t {
+    SLAM_FIELD_IN_MEMORY,           // the current generation holds it
+    SLAM_FIELD_OWED_COPY,           // ... does not hold the last resample()'s copies yet (if it drew): slot m's field is the other generation's [d_idx_lik[m]]
+    SLAM_FIELD_FROM_PLANES          // it is behind: every particle's is the field of plane 1 of its class planes (made on demand)
+};
+
 // SLAM as the reference has it (J/slam/SLAM.java): N particles, each with its own GridMapData (gms_slam_host.hip, gms_slam_kernels.hip)
 struct gms_slam {
     gms_map *map;                   // ONE map's worth of handle: the GridMap (geometry, constants, taps), the stream, staging, profiling; its own
@@ -352,18 +359,37 @@ struct gms_slam {
     int32_t *d_plan;                // a shard's resample(): [3][n] device staging of {export list | local sources | positions in the received buffer}
     int32_t lazy_lik;               // resample() copies logData at once and likelihoodData when somebody asks for it: the next update's
                                     // computeLikelihoodMap overwrites every cell of it before anything on the path reads one (GMS_SLAM_LAZY_LIK_COPY=0: both at once)
-    int32_t lik_behind;             // the current generation's likelihoodData does not hold the last resample()'s copies yet (if it drew): slot m's field is the other generation's [d_idx_lik[m]]
-    int32_t *d_idx_lik;             // [n] the source indices of that resample()
+    SlamField field;                // where every particle's likelihoodData stands (handle-wide).  Written by the slam_* transitions below only.
+    int32_t *d_idx_lik;             // [n] SLAM_FIELD_OWED_COPY: the source indices of the resample() that owes the copies
     uint32_t *d_code[2];            // [n][2][code_words] every particle's class planes (gms_slam_kernels.hip), double-buffered with logData; NULL: not kept
                                     // (the blur kernel is wider than the on-demand evaluation takes, the plane does not fit the LDS, or GMS_SLAM_EAGER_LIK=1)
     int64_t code_words;             // 32-bit words per plane
-    int32_t lik_from_codes;         // likelihoodData is behind: every particle's is the field of plane 1 of its class planes (made on demand)
     int32_t refine;                 // gms_slam_set_refine: update() runs findBestPose on every particle against its own field before weighting it (SLAM.java:96)
     int32_t refine_field;           // the field in front of the refinement: -1 from the class plane where logData exceeds the infinity cache, 0 from logData
                                     // always, 1 from the plane always (GMS_SLAM_REFINE_FIELD=log|codes: tests of both forms)
     int32_t refine_lds;             // -1 the field in LDS whenever it fits (computed there from the class plane where it can be), 0 never, 2 staged from
                                     // memory wherever it fits (GMS_SLAM_REFINE_LDS: tests of the other forms)
 };
+
+// ---- field state transitions of a gms_slam (gms_slam::field): each is named for what happened; together they are its only writers.
+// A batched handle keeps one state for all its filters: the copy kernels skip the filters that did not draw ----
+// createMapData(null) per particle (GridMap.java:106-117): likelihoodData a fresh double[] = 0.0, written out
+static inline void slam_was_reset(gms_slam *s) { s->field = SLAM_FIELD_IN_MEMORY; }
+// an update rewrote every cell of every field (an owed copy is moot), or -- on_demand -- skipped it: probabilityOf reads the field under
+// the scan's end points only (GridMap.java:273-277) and the kernels evaluate exactly those cells from the particle's plane; what a caller
+// may read afterwards, the field of logData as it stands NOW, stays defined by plane 1 and is written when asked for
+static inline void slam_field_updated(gms_slam *s, bool on_demand) { s->field = on_demand ? SLAM_FIELD_FROM_PLANES : SLAM_FIELD_IN_MEMORY; }
+// a resample ran on a field that was not owed a copy.  From the planes: they travel with logData, and so does the field.  In memory:
+// copied at once (GridMap.java:121), or -- lazy_lik -- when it is asked for: SLAM.update starts with computeLikelihoodMap of every
+// particle (SLAM.java:93), which overwrites every cell of it, so nothing on the path ever reads the copies
+static inline void slam_resampled(gms_slam *s, bool lazy_lik) {
+    if (s->field == SLAM_FIELD_IN_MEMORY && lazy_lik) s->field = SLAM_FIELD_OWED_COPY;
+}
+// the field was written out for a reader (a download, an upload's other slots, a second resample() in a row)
+static inline void slam_field_materialised(gms_slam *s) { s->field = SLAM_FIELD_IN_MEMORY; }
+// a shard's draw: its likelihoodData is never copied, it is the field of plane 1 of the class planes, which travel.  Whatever was
+// written out for a reader is dropped (the planes still define it)
+static inline void slam_shard_drew(gms_slam *s) { s->field = SLAM_FIELD_FROM_PLANES; }
 
 // the thread's last-error text + code (gms_host.hip); every C-ABI file reports through it
 int gms_fail(int code, const char *fmt, ...);
@@ -376,6 +402,8 @@ int gms_fail(int code, const char *fmt, ...);
     do {                                                           \
         if (!(cond)) return gms_fail(GMS_ERR_INVALID, "%s", msg);  \
     } while (0)
+// gms_pf_set_shard behind its refuse_owned_maps guard (gms_host.hip; not exported): gms_slam_create_shard places its own filter through it
+extern "C" int gms_pf_place_shard(gms_pf *pf, int64_t offset, int64_t n_global);
 // host beams [n_maps][B] -> the map's device staging buffer [n_maps][max_beams] through the pinned ring (gms_host.hip)
 int gms_stage_beams(gms_map *m, const gms_beam *beams, int32_t B);
 // host beams [rows][B] (or none: beams NULL) -> dst [rows][pitch], then tab_bytes of tab behind them, as ONE copy out of a slot of ring
@@ -441,6 +469,12 @@ struct MotionModel {            // one odometry step for gms_launch_pf_score's m
     double d_center, d_theta;
     uint64_t seed, sequence;
 };
+// the motion model's deviations for one odometry step: the ONE copy of the two expressions -- bit parity between a batched filter, a
+// stand-alone one and the shared-map filters rests on it (motion_args in gms_pf_kernels.hip, slam_filter_args)
+static inline void motion_deviations(double d_center, double d_theta, double *d_center_sd, double *d_theta_sd) {
+    *d_center_sd = (0.01 + fabs(d_center) * 0.05) / 2;                           // Odometry.java:63
+    *d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(d_theta);         // :64
+}
 void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t beam_stride, const float *d_pose_src = nullptr,
                          const MotionModel *motion = nullptr);   // d_pose_src: set the poses in the same launch
 void gms_launch_pf_partials(gms_pf *pf, double *d_partials);

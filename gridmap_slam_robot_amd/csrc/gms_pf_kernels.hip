@@ -61,6 +61,16 @@ struct MotionArgs {
     uint64_t seed, sequence;
     int64_t index0;             // global index of the launch's particle 0 (a shard's offset): the variates are keyed by the GLOBAL index
 };
+// one odometry step as the kernels take it; motion NULL: no sample is drawn (on = 0)
+static MotionArgs motion_args(const MotionModel *motion, int64_t index0) {
+    MotionArgs mo;
+    mo.on = 0; mo.d_center = mo.d_theta = mo.d_center_sd = mo.d_theta_sd = 0.0; mo.seed = mo.sequence = 0; mo.index0 = index0;
+    if (motion) {
+        mo.on = 1; mo.d_center = motion->d_center; mo.d_theta = motion->d_theta; mo.seed = motion->seed; mo.sequence = motion->sequence;
+        motion_deviations(motion->d_center, motion->d_theta, &mo.d_center_sd, &mo.d_theta_sd);
+    }
+    return mo;
+}
 __device__ __forceinline__ void motion_apply(float &x, float &y, float &th, float &fc, float &fs, uint64_t index, double d_center,
                                              double d_theta, double d_center_sd, double d_theta_sd, uint64_t seed, uint64_t sequence) {
     uint32_t c[4] = { (uint32_t)index, (uint32_t)(index >> 32), (uint32_t)sequence, (uint32_t)(sequence >> 32) };
@@ -1582,8 +1592,8 @@ void gms_launch_pf_pose_trig(gms_pf *pf, const float *d_src) {
 }
 
 void gms_launch_pf_motion(gms_pf *pf, double d_center, double d_theta, uint64_t seed, uint64_t sequence) {
-    const double d_center_sd = (0.01 + fabs(d_center) * 0.05) / 2;               // Odometry.java:63
-    const double d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(d_theta);   // :64
+    double d_center_sd, d_theta_sd;
+    motion_deviations(d_center, d_theta, &d_center_sd, &d_theta_sd);
     hipLaunchKernelGGL(k_motion, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), 0, pf->map->stream, pf->d_pose, pf->d_cs,
                        pf->n, pf->offset, d_center, d_theta, d_center_sd, d_theta_sd, seed, sequence);
 }
@@ -1637,8 +1647,6 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
         pf_scored(pf, 1);
         return;
     }
-    MotionArgs mo;
-    mo.on = 0; mo.d_center = mo.d_theta = mo.d_center_sd = mo.d_theta_sd = 0.0; mo.seed = mo.sequence = 0; mo.index0 = 0;
     const int64_t nseg = score_segments(B, pf->n_maps > 1);
     // The locality order (k_order) costs a launch of its own, ~8 us for 4096 particles per map, and takes a fifth to a
     // quarter off the scoring kernel: it pays once the scoring launch is several rounds of workgroups deep (C5: 6144
@@ -1660,12 +1668,8 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
         d_pose_src = nullptr;                                     // stored by k_order
     }
     float *pose_dst = pf->d_pose, *cs_dst = pf->d_cs;
-    if (motion) {
-        mo.on = 1; mo.d_center = motion->d_center; mo.d_theta = motion->d_theta; mo.seed = motion->seed; mo.sequence = motion->sequence;
-        mo.d_center_sd = (0.01 + fabs(motion->d_center) * 0.05) / 2;             // Odometry.java:63
-        mo.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(motion->d_theta);   // :64
-        d_pose_src = pf->d_pose; pose_dst = pf->d_pose2; cs_dst = pf->d_cs2;
-    }
+    const MotionArgs mo = motion_args(motion, 0);                 // (k_score_c takes the shard's offset as an argument of its own)
+    if (motion) { d_pose_src = pf->d_pose; pose_dst = pf->d_pose2; cs_dst = pf->d_cs2; }
     ProfScope ps(m, GMS_K_SCORE);
     // Lanes per workgroup: 1024 (sixteen wavefronts sharing one segment's L1 patch) while that still gives every CU a workgroup;
     // a smaller population -- one shard of eight of config 4's 65 536 particles, config 2 -- takes 512 or 256 lanes per workgroup

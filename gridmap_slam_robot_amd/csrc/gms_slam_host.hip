@@ -34,11 +34,18 @@ static int slam_host_gen(gms_slam *s, int32_t *gen, int64_t *copies = nullptr) {
     return GMS_OK;
 }
 
-// the calls that take one scan, one odometry or one draw for the whole handle: one filter only
-static int refuse_batched(const gms_slam *s, const char *what) {
-    if (s->n_filters > 1)
-        return gms_fail(GMS_ERR_STATE, "%s: this handle holds %d filters (gms_params.n_maps): use the batch form%s", what, s->n_filters,
-                        strstr(what, "update") ? " (gms_slam_update_batch[_dev])" : (strstr(what, "resample") ? " (gms_slam_resample_maps[_if]_batch)" : ""));
+// What the entry points open with: the null handle, then the kinds of handle the entry does not take (allow: those it does).  A shard
+// of a filter has its own calls, since the weights and the sources of its copies may live on other ranks; the calls that take one scan,
+// one odometry or one draw for the whole handle are for one filter only.
+enum { SLAM_ALLOW_SHARD = 1, SLAM_ALLOW_BATCHED = 2 };
+static int slam_enter(const gms_slam *s, const char *what, int allow) {
+    if (!s) return gms_fail(GMS_ERR_INVALID, "%s: null handle", what);
+    if (!(allow & SLAM_ALLOW_SHARD) && pf_is_shard(s->pf))
+        return gms_fail(GMS_ERR_STATE, "%s: a shard of a filter (de-skew, gms_slam_update_local[_dev] and the weight exchange stay with the caller; "
+                                       "gms_slam_shard_draw / export / gather move its maps)", what);
+    if (!(allow & SLAM_ALLOW_BATCHED) && s->n_filters > 1)
+        return gms_fail(GMS_ERR_STATE, "%s: this handle holds %d filters (gms_params.n_maps): use the batch form (gms_slam_update_batch[_dev], "
+                                       "gms_slam_resample_maps[_if]_batch, gms_slam_frame_batch)", what, s->n_filters);
     return GMS_OK;
 }
 
@@ -134,9 +141,7 @@ static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset,
             return gms_fail(GMS_ERR_INVALID, "gms_slam_create_shard: a sharded filter moves a particle as logData + its class planes; this map's planes are "
                                              "not kept (blur kernel wider than 15 taps, a plane over 24 KiB, or GMS_SLAM_EAGER_LIK=1)");
         }
-        s->pf->d_epoch2 = s->d_epoch;                  // (lets gms_pf_set_shard through: the filter is otherwise closed to it)
-        rc = gms_pf_set_shard(s->pf, offset, n_global);
-        s->pf->d_epoch2 = nullptr;
+        rc = gms_pf_place_shard(s->pf, offset, n_global);      // (gms_pf_set_shard itself is closed to a filter whose particles own maps)
         if (rc) { gms_slam_destroy(s); return rc; }
     }
     *out = s;
@@ -157,8 +162,7 @@ int gms_slam_reset(gms_slam *s) {                                               
     HIPCHK(hipMemsetAsync(s->d_log[0], 0, bytes, m->stream));
     HIPCHK(hipMemsetAsync(s->d_lik[0], 0, bytes, m->stream));
     if (s->d_code[0]) HIPCHK(hipMemsetAsync(s->d_code[0], 0, (size_t)s->n * 2 * (size_t)s->code_words * sizeof(uint32_t), m->stream));   // every class "logData == 0"
-    s->lik_behind = 0;
-    s->lik_from_codes = 0;
+    slam_was_reset(s);
     gms_launch_pf_init(s->pf);                                                               // Pose(0, 0, 0), weight 1 / numParticles (:68-71)
     pf_weights_set(s->pf);
     HIPCHK(hipGetLastError());
@@ -194,10 +198,8 @@ static bool slam_skip_update(double d_theta) { return fabs(d_theta) > (3.1415926
 static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, const MotionModel *motion, bool skip_update, const SlamBatch *batch) {
     gms_map *m = s->map;
     gms_pf *pf = s->pf;
-    // :93 for every particle.  With the class planes and no refinement the field is not written here: probabilityOf reads it under the
-    // scan's end points only (GridMap.java:273-277), and k_slam_particle evaluates exactly those cells from the particle's plane; what a
-    // caller may read afterwards -- the field of logData as it stands NOW -- stays defined by plane 1 and is written when asked for
-    // (slam_lik_current).  The pose refinement looks up most of a field: it gets all of it.
+    // :93 for every particle.  With the class planes and no refinement the field is not written here (slam_field_updated; written when
+    // asked for: slam_lik_current).  The pose refinement looks up most of a field: it gets all of it.
     // ... unless it computes it itself: a field that fits a workgroup's LDS is computed there from the same plane.
     const bool planes = s->d_code[0] != nullptr;
     const bool on_demand = planes && (!s->refine || gms_slam_refine_from_planes(m, B, s->refine_lds, s->code_words));
@@ -209,8 +211,7 @@ static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, c
         if (s->d_code[0] && (s->refine_field < 0 ? big : s->refine_field == 1)) gms_launch_slam_likelihood_codes(m, sb, s->code_words, s->n, 0);
         else gms_launch_slam_likelihood(m, sb, s->n);
     }
-    s->lik_behind = 0;                                                                                     // (every cell of every field is rewritten: an owed copy is moot)
-    s->lik_from_codes = on_demand ? 1 : 0;
+    slam_field_updated(s, on_demand);
     bool drawn = false;
     if (s->refine) {                                                                                        // :90, then :96 (the lattice form of :97)
         if (!gms_launch_slam_refine(pf, dev_beams, B, sb, motion, s->refine_lds, planes ? s->code_words : 0, batch))
@@ -225,7 +226,7 @@ static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, c
 static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                              uint64_t seed, uint64_t sequence) {
     REQUIRE(s && dev_beams, "null argument");
-    int rc = refuse_batched(s, "gms_slam_update_per_particle / update_local");
+    int rc = slam_enter(s, "gms_slam_update_per_particle / update_local", SLAM_ALLOW_SHARD);
     if (rc) return rc;
     REQUIRE(B >= 0 && B <= s->map->max_beams, "beam count exceeds gms_params.max_beams");
     HIPCHK(hipSetDevice(s->map->device));
@@ -237,10 +238,7 @@ static int slam_update_local(gms_slam *s, const gms_beam *dev_beams, int32_t B, 
 // SLAM.update(z, u) on a device-resident scan (SLAM.java:80-131)
 int gms_slam_update_per_particle_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                                      uint64_t seed, uint64_t sequence, gms_pf_stats *stats) {
-    REQUIRE(s, "null handle");
-    if (pf_is_shard(s->pf))
-        return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_update_local_dev, then the weight exchange (gms_pf_local_partials / apply_partials / import_global)");
-    int rc = refuse_batched(s, "gms_slam_update_per_particle_dev");
+    int rc = slam_enter(s, "gms_slam_update_per_particle_dev", 0);
     if (rc) return rc;
     rc = slam_update_local(s, dev_beams, B, sample_motion, d_center, d_theta, seed, sequence);
     if (rc) return rc;
@@ -257,7 +255,7 @@ int gms_slam_update_local_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B,
 int gms_slam_update_local(gms_slam *s, const gms_beam *beams, int32_t B, int32_t sample_motion, double d_center, double d_theta, uint64_t seed,
                           uint64_t sequence) {
     REQUIRE(s && beams, "null argument");
-    int rc = refuse_batched(s, "gms_slam_update_local");
+    int rc = slam_enter(s, "gms_slam_update_local", SLAM_ALLOW_SHARD);
     if (rc) return rc;
     rc = gms_stage_beams(s->map, beams, B);
     if (rc) return rc;
@@ -267,19 +265,37 @@ int gms_slam_update_local(gms_slam *s, const gms_beam *beams, int32_t B, int32_t
 int gms_slam_update_per_particle(gms_slam *s, const gms_beam *beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                                  uint64_t seed, uint64_t sequence, gms_pf_stats *stats) {
     REQUIRE(s && beams, "null argument");
-    int rc = refuse_batched(s, "gms_slam_update_per_particle");
+    int rc = slam_enter(s, "gms_slam_update_per_particle", SLAM_ALLOW_SHARD);       // (a shard: refused behind the staging, by the _dev form)
     if (rc) return rc;
     rc = gms_stage_beams(s->map, beams, B);
     if (rc) return rc;
     return gms_slam_update_per_particle_dev(s, s->map->d_beams, B, sample_motion, d_center, d_theta, seed, sequence, stats);
 }
 
+// rows x L raw measurements as a frame call lays them into a slot of a pinned ring: [rows][L] angle | [rows][L] distance | [rows][L] hit,
+// 17 bytes per measurement; `behind` (slam_raw_bytes): the offset of what follows them (the filters' table), on a 16-byte boundary
+static size_t slam_raw_bytes(size_t rows, size_t L) { return (rows * L * 17 + 15) & ~(size_t)15; }
+struct RawRows {
+    double *angle, *distance;
+    uint8_t *hit;
+    size_t behind;
+};
+static RawRows slam_lay_raw(void *slot, size_t rows, size_t L, const double *angle, const double *distance, const uint8_t *hit) {
+    const size_t n = rows * L;
+    RawRows r;
+    r.angle = static_cast<double *>(slot); r.distance = r.angle + n;
+    r.hit = reinterpret_cast<uint8_t *>(r.distance + n);
+    r.behind = slam_raw_bytes(rows, L);
+    memcpy(r.angle, angle, n * 8); memcpy(r.distance, distance, n * 8); memcpy(r.hit, hit, n);
+    return r;
+}
+
 // the staging of a batched handle, made by its first batched call: d_batch = [S][max_beams] beams | [S] SlamFilterArgs, and the pinned ring
-// whose slots hold that block or a frame's raw revolutions with the table behind them (17 bytes per measurement: never more than the beams)
+// whose slots hold that block or a frame's raw revolutions with the table behind them (never more than the beams)
 static int slam_batch_staging(gms_slam *s, const char *what) {
     if (s->d_batch) return GMS_OK;
     const size_t S = (size_t)s->n_filters, mb = (size_t)s->map->max_beams;
-    const size_t bytes = std::max(S * mb * sizeof(gms_beam), ((S * mb * 17 + 15) & ~(size_t)15)) + S * sizeof(SlamFilterArgs);
+    const size_t bytes = std::max(S * mb * sizeof(gms_beam), slam_raw_bytes(S, mb)) + S * sizeof(SlamFilterArgs);
     if (hipMalloc(&s->d_batch, bytes) != hipSuccess || gms_ring_alloc(s->batch_ring, bytes) != GMS_OK) {
         hipFree(s->d_batch); s->d_batch = nullptr; gms_ring_free(s->batch_ring);
         return gms_fail(GMS_ERR_NOMEM, "%s: staging allocation failed", what);
@@ -293,8 +309,7 @@ static SlamFilterArgs *slam_batch_tab(const gms_slam *s) {
 static SlamFilterArgs slam_filter_args(const double *odometry, uint64_t seed, int32_t count, bool sample_motion) {
     SlamFilterArgs a;
     a.d_center = odometry[0]; a.d_theta = odometry[1];
-    a.d_center_sd = (0.01 + fabs(a.d_center) * 0.05) / 2;                              // Odometry.java:63 (as gms_launch_slam_particle)
-    a.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(a.d_theta);            // :64
+    motion_deviations(a.d_center, a.d_theta, &a.d_center_sd, &a.d_theta_sd);
     a.seed = seed;
     a.count = count;
     a.flags = (sample_motion ? 1 : 0) | (slam_skip_update(a.d_theta) ? 0 : 2);
@@ -316,9 +331,10 @@ static int slam_update_staged_batch(gms_slam *s, const gms_beam *d_beams, int32_
 // filters' table (SlamFilterArgs) in the same copy as the beams where those come from the host (on_device: the beams are the caller's)
 static int slam_update_batch(gms_slam *s, const gms_beam *beams, bool on_device, int32_t B, const int32_t *counts, const double *odometry,
                              const uint64_t *seeds, const int32_t *sample_motion, uint64_t sequence, gms_pf_stats *stats) {
-    REQUIRE(s, "null handle");
-    REQUIRE(beams && odometry && seeds && sample_motion, "gms_slam_update_batch: null argument (beams, odometry, seeds and sample_motion are required)");
-    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_update_batch: a shard of a filter (gms_slam_update_local[_dev])");
+    REQUIRE(s && beams && odometry && seeds && sample_motion,
+            "gms_slam_update_batch: null argument (the handle, beams, odometry, seeds and sample_motion are required)");
+    int rc = slam_enter(s, "gms_slam_update_batch", SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
     gms_map *m = s->map;
     const int32_t S = s->n_filters;
     if (B < 0 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "gms_slam_update_batch: B = %d outside 0 .. gms_params.max_beams (%d)", B, m->max_beams);
@@ -331,13 +347,12 @@ static int slam_update_batch(gms_slam *s, const gms_beam *beams, bool on_device,
     HIPCHK(hipSetDevice(m->device));
     if (S == 1) {
         const int32_t c = counts ? counts[0] : B;
-        int rc = GMS_OK;
         const gms_beam *d = beams;
         if (!on_device) { rc = gms_stage_beams(m, beams, c); d = m->d_beams; }
         if (!rc) rc = gms_slam_update_per_particle_dev(s, d, c, sample_motion[0], odometry[0], odometry[1], seeds[0], sequence, stats);
         return rc;
     }
-    int rc = slam_batch_staging(s, "gms_slam_update_batch");
+    rc = slam_batch_staging(s, "gms_slam_update_batch");
     if (rc) return rc;
     std::vector<SlamFilterArgs> tab((size_t)S);
     for (int32_t f = 0; f < S; f++) tab[f] = slam_filter_args(odometry + 2 * (size_t)f, seeds[f], counts ? counts[f] : B, sample_motion[f] != 0);
@@ -359,64 +374,64 @@ int gms_slam_update_batch_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B,
 
 // likelihoodData as the last resample() left it, for whoever reads it before the next update (downloads; a second resample())
 static int slam_lik_current(gms_slam *s) {
-    if (s->lik_from_codes) {                                                                               // computeLikelihoodMap(p.m) of the last update (:93), late
+    switch (s->field) {
+    case SLAM_FIELD_IN_MEMORY: return GMS_OK;
+    case SLAM_FIELD_FROM_PLANES:                                                                           // computeLikelihoodMap(p.m) of the last update (:93), late
         gms_launch_slam_likelihood_codes(s->map, gms_slam_bufs(s), s->code_words, s->n, 1);
-        s->lik_from_codes = 0;
-        HIPCHK(hipGetLastError());
-        return GMS_OK;
+        break;
+    case SLAM_FIELD_OWED_COPY:                                                                             // GridMap.java:121, late (if that resample() drew)
+        gms_launch_slam_gather(s->pf, gms_slam_bufs(s), 2, s->d_idx_lik, nullptr, s->code_words);
+        break;
     }
-    if (!s->lik_behind) return GMS_OK;
-    gms_launch_slam_gather(s->pf, gms_slam_bufs(s), 2, s->d_idx_lik, nullptr, s->code_words);              // GridMap.java:121, late (if that resample() drew)
-    s->lik_behind = 0;
+    slam_field_materialised(s);
     HIPCHK(hipGetLastError());
     return GMS_OK;
+}
+
+// The draw of resample() over the particles' weights (SLAM.java:136-145 + pose, weight, :42-43; fraction >= 0: where the rule says so).
+// The one place that opens the filter to it (refuse_owned_maps): the draw counts itself in the handle's generation pair (k_resample),
+// which the maps follow, and the pair is lent for exactly this call.
+static int slam_draw(gms_slam *s, const double *r01, double fraction, int32_t *indices, int32_t *n_ambiguous) {
+    s->pf->d_epoch2 = s->d_epoch;
+    const int rc = fraction >= 0.0 ? gms_pf_resample_if(s->pf, r01, fraction) : gms_pf_resample(s->pf, r01, indices, n_ambiguous);
+    s->pf->d_epoch2 = nullptr;
+    return rc;
 }
 
 // SLAM.resample() (SLAM.java:133-153): the systematic draw over the particles' weights, then every slot's deep copy into the OTHER
 // generation of the maps, which the draw makes current (:152); fraction >= 0: only where Neff < fraction * n (GridMapApp.java:185-186),
 // decided on the device -- where the rule says no, nothing is drawn, no generation changes and the copy kernels return at once (the
 // reference does nothing either).  r01 [n_filters]; a batched handle draws, and decides, per filter (its own generation pair: the
-// handle-wide lik_behind / lik_from_codes hold for every filter, since the copy kernels skip the filters that did not draw)
+// handle-wide field state holds for every filter, since the copy kernels skip the filters that did not draw)
 static int slam_resample(gms_slam *s, const double *r01, double fraction, int32_t *indices, int32_t *n_ambiguous) {
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
-    int rc = s->lik_behind ? slam_lik_current(s) : GMS_OK;                                                 // (two resample() calls in a row)
+    int rc = s->field == SLAM_FIELD_OWED_COPY ? slam_lik_current(s) : GMS_OK;                              // (two resample() calls in a row)
     if (rc) return rc;
-    s->pf->d_epoch2 = s->d_epoch;                      // the draw counts itself (k_resample): the maps' generation follows it
-    rc = fraction >= 0.0 ? gms_pf_resample_if(s->pf, r01, fraction)
-                         : gms_pf_resample(s->pf, r01, indices, n_ambiguous);                              // :136-145 + pose, weight (:42-43)
-    s->pf->d_epoch2 = nullptr;
+    rc = slam_draw(s, r01, fraction, indices, n_ambiguous);
     if (rc) return rc;
     const SlamBufs sb = gms_slam_bufs(s);
-    if (s->lik_from_codes) {
-        // likelihoodData is the field of plane 1 of a particle's class planes: they travel with logData, and so does it
-        gms_launch_slam_gather(s->pf, sb, 1, s->pf->d_idx, nullptr, s->code_words);
-    } else if (s->lazy_lik) {
-        // logData now (GridMap.java:120); likelihoodData (:121) when it is asked for: SLAM.update starts with computeLikelihoodMap of
-        // every particle (:93), which overwrites every cell of it -- nothing on the path ever reads the copies
-        gms_launch_slam_gather(s->pf, sb, 1, s->pf->d_idx, s->d_idx_lik, s->code_words);                   // (keeps the indices for that)
-        s->lik_behind = 1;
-    } else {
-        gms_launch_slam_gather(s->pf, sb, 3, s->pf->d_idx, nullptr, s->code_words);                        // :44
+    slam_resampled(s, s->lazy_lik != 0);
+    switch (s->field) {                                                                                     // (what each state copies, and why: slam_resampled)
+    case SLAM_FIELD_FROM_PLANES: gms_launch_slam_gather(s->pf, sb, 1, s->pf->d_idx, nullptr, s->code_words); break;
+    case SLAM_FIELD_OWED_COPY: gms_launch_slam_gather(s->pf, sb, 1, s->pf->d_idx, s->d_idx_lik, s->code_words); break;   // logData now (GridMap.java:120); keeps the indices
+    case SLAM_FIELD_IN_MEMORY: gms_launch_slam_gather(s->pf, sb, 3, s->pf->d_idx, nullptr, s->code_words); break;        // :44
     }
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
 
 int gms_slam_resample_maps(gms_slam *s, double r01, int32_t *indices, int32_t *n_ambiguous) {
-    REQUIRE(s, "null handle");
-    if (pf_is_shard(s->pf))
-        return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_shard_draw / export / gather move its maps (the sources may live on other ranks)");
-    int rc = refuse_batched(s, "gms_slam_resample_maps");
+    int rc = slam_enter(s, "gms_slam_resample_maps", 0);
     if (rc) return rc;
     return slam_resample(s, &r01, -1.0, indices, n_ambiguous);
 }
 
 // resample() of every filter: r01 [S], indices [S][n] filter-local (may be NULL), n_ambiguous [S] (may be NULL)
 int gms_slam_resample_maps_batch(gms_slam *s, const double *r01, int32_t *indices, int32_t *n_ambiguous) {
-    REQUIRE(s, "null handle");
-    REQUIRE(r01, "gms_slam_resample_maps_batch: null r01");
-    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_resample_maps_batch: a shard of a filter (gms_slam_shard_draw / export / gather)");
+    REQUIRE(s && r01, "gms_slam_resample_maps_batch: null handle or r01");
+    int rc = slam_enter(s, "gms_slam_resample_maps_batch", SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
     return slam_resample(s, r01, -1.0, indices, n_ambiguous);
 }
 
@@ -425,19 +440,12 @@ int gms_slam_resample_maps_batch(gms_slam *s, const double *r01, int32_t *indice
 //    maps' generation advances if it drew.  sources[n_local] = the GLOBAL index of every slot's source particle; *did as the rule decided.
 int gms_slam_shard_draw(gms_slam *s, double r01, double fraction, int32_t *did, int32_t *sources) {
     REQUIRE(s && did && sources, "null argument");
-    int rc0 = refuse_batched(s, "gms_slam_shard_draw");
-    if (rc0) return rc0;
+    int rc = slam_enter(s, "gms_slam_shard_draw", SLAM_ALLOW_SHARD);
+    if (rc) return rc;
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
-    if (s->lik_behind || !s->lik_from_codes) {
-        // a shard's likelihoodData is never copied: it is the field of plane 1 of the class planes, which travel.  Whatever was written
-        // out for a reader is dropped here (the planes still define it).
-        s->lik_behind = 0;
-        s->lik_from_codes = 1;
-    }
-    s->pf->d_epoch2 = s->d_epoch;
-    int rc = fraction >= 0.0 ? gms_pf_resample_if(s->pf, &r01, fraction) : gms_pf_resample(s->pf, &r01, nullptr, nullptr);
-    s->pf->d_epoch2 = nullptr;
+    slam_shard_drew(s);
+    rc = slam_draw(s, &r01, fraction, nullptr, nullptr);
     if (rc) return rc;
     int32_t e[2] = {0, 0};
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -457,7 +465,7 @@ int gms_slam_record_doubles(const gms_slam *s, int64_t *doubles) {
 //    [count][record_doubles]: what the ranks whose slots drew them receive
 int gms_slam_shard_export(gms_slam *s, const int32_t *local_indices, int32_t count, double *dev_dst) {
     REQUIRE(s && (count == 0 || (local_indices && dev_dst)), "null argument");
-    int rc0 = refuse_batched(s, "gms_slam_shard_export");
+    int rc0 = slam_enter(s, "gms_slam_shard_export", SLAM_ALLOW_SHARD);
     if (rc0) return rc0;
     REQUIRE(s->d_plan && count >= 0 && count <= s->n, "gms_slam_shard_export: not a shard, or more records than particles");
     if (count == 0) return GMS_OK;
@@ -474,7 +482,7 @@ int gms_slam_shard_export(gms_slam *s, const int32_t *local_indices, int32_t cou
 //    recv_pos[m] of dev_recv (the records this rank received).  Both arrays [n_local], host.
 int gms_slam_shard_gather(gms_slam *s, const int32_t *src_local, const int32_t *recv_pos, const double *dev_recv) {
     REQUIRE(s && src_local && recv_pos, "null argument");
-    int rc0 = refuse_batched(s, "gms_slam_shard_gather");
+    int rc0 = slam_enter(s, "gms_slam_shard_gather", SLAM_ALLOW_SHARD);
     if (rc0) return rc0;
     REQUIRE(s->d_plan, "gms_slam_shard_gather: not a shard");
     gms_map *m = s->map;
@@ -492,20 +500,17 @@ int gms_slam_shard_gather(gms_slam *s, const int32_t *src_local, const int32_t *
 }
 
 int gms_slam_resample_maps_if(gms_slam *s, double r01, double fraction) {
-    REQUIRE(s, "null handle");
-    if (pf_is_shard(s->pf))
-        return gms_fail(GMS_ERR_STATE, "a shard of a filter: gms_slam_shard_draw / export / gather move its maps (the sources may live on other ranks)");
-    REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if: fraction must be non-negative");
-    int rc = refuse_batched(s, "gms_slam_resample_maps_if");
+    int rc = slam_enter(s, "gms_slam_resample_maps_if", 0);
     if (rc) return rc;
+    REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if: fraction must be non-negative");
     return slam_resample(s, &r01, fraction, nullptr, nullptr);
 }
 
 // `if (neff < fraction * n) resample()` for every filter, each decided on the device from its own Neff: r01 [S]
 int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fraction) {
-    REQUIRE(s, "null handle");
-    REQUIRE(r01, "gms_slam_resample_maps_if_batch: null r01");
-    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_resample_maps_if_batch: a shard of a filter (gms_slam_shard_draw / export / gather)");
+    REQUIRE(s && r01, "gms_slam_resample_maps_if_batch: null handle or r01");
+    int rc = slam_enter(s, "gms_slam_resample_maps_if_batch", SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
     REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if_batch: fraction must be non-negative");
     return slam_resample(s, r01, fraction, nullptr, nullptr);
 }
@@ -516,24 +521,19 @@ int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fract
 // revolution goes into a slot of the map's pinned ring and is read there by the de-skew launch (as gms_map_deskew does).
 int gms_slam_frame_per_particle(gms_slam *s, const double *angle, const double *distance, const uint8_t *hit, int32_t length, double d_center,
                                 double d_theta, uint64_t seed, uint64_t sequence, double r01, double resample_fraction, gms_pf_stats *stats) {
-    REQUIRE(s, "gms_slam_frame_per_particle: null handle");
-    REQUIRE(angle && distance && hit, "gms_slam_frame_per_particle: null argument (angle, distance and hit are required)");
-    if (pf_is_shard(s->pf))
-        return gms_fail(GMS_ERR_STATE, "gms_slam_frame_per_particle: a shard of a filter (de-skew, gms_slam_update_local[_dev] and the exchanges stay with the caller)");
-    int rc = refuse_batched(s, "gms_slam_frame_per_particle");
+    REQUIRE(s && angle && distance && hit, "gms_slam_frame_per_particle: null argument (the handle, angle, distance and hit are required)");
+    int rc = slam_enter(s, "gms_slam_frame_per_particle", 0);
     if (rc) return rc;
     gms_map *m = s->map;
     if (length <= 0 || length > m->max_beams)
         return gms_fail(GMS_ERR_INVALID, "gms_slam_frame_per_particle: length = %d outside 1 .. gms_params.max_beams (%d)", length, m->max_beams);
-    REQUIRE((size_t)length * 17 + 16 <= (size_t)m->max_beams * sizeof(gms_beam), "gms_slam_frame_per_particle: scan too long for the staging buffer");
+    REQUIRE(slam_raw_bytes(1, length) + 16 <= (size_t)m->max_beams * sizeof(gms_beam), "gms_slam_frame_per_particle: scan too long for the staging buffer");
     HIPCHK(hipSetDevice(m->device));
     void *slot = nullptr;
     rc = gms_ring_acquire(m->beam_ring, &slot);
     if (rc) return rc;
-    double *h_a = static_cast<double *>(slot), *h_d = h_a + length;
-    uint8_t *h_h = reinterpret_cast<uint8_t *>(h_d + length);
-    memcpy(h_a, angle, (size_t)length * 8); memcpy(h_d, distance, (size_t)length * 8); memcpy(h_h, hit, (size_t)length);
-    gms_launch_slam_deskew(m, h_a, h_d, h_h, length, 1, length, length, d_center, d_theta, nullptr, nullptr, m->d_beams, m->max_beams);
+    const RawRows raw = slam_lay_raw(slot, 1, length, angle, distance, hit);
+    gms_launch_slam_deskew(m, raw.angle, raw.distance, raw.hit, length, 1, length, length, d_center, d_theta, nullptr, nullptr, m->d_beams, m->max_beams);
     rc = gms_ring_commit(m->beam_ring, m->stream);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
@@ -550,10 +550,10 @@ int gms_slam_frame_per_particle(gms_slam *s, const double *angle, const double *
 int gms_slam_frame_batch(gms_slam *s, const double *angle, const double *distance, const uint8_t *hit, int32_t L, const int32_t *lengths,
                          const double *odometry, const uint64_t *seeds, uint64_t sequence, const double *r01, double resample_fraction,
                          gms_pf_stats *stats) {
-    REQUIRE(s, "gms_slam_frame_batch: null handle");
-    REQUIRE(angle && distance && hit && odometry && seeds && r01,
-            "gms_slam_frame_batch: null argument (angle, distance, hit, odometry, seeds and r01 are required)");
-    if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_frame_batch: a shard of a filter (de-skew, gms_slam_update_local[_dev] and the exchanges stay with the caller)");
+    REQUIRE(s && angle && distance && hit && odometry && seeds && r01,
+            "gms_slam_frame_batch: null argument (the handle, angle, distance, hit, odometry, seeds and r01 are required)");
+    int rc = slam_enter(s, "gms_slam_frame_batch", SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
     gms_map *m = s->map;
     const int32_t S = s->n_filters;
     if (L <= 0 || L > m->max_beams) return gms_fail(GMS_ERR_INVALID, "gms_slam_frame_batch: L = %d outside 1 .. gms_params.max_beams (%d)", L, m->max_beams);
@@ -566,23 +566,19 @@ int gms_slam_frame_batch(gms_slam *s, const double *angle, const double *distanc
     if (S == 1)
         return gms_slam_frame_per_particle(s, angle, distance, hit, Lmax, odometry[0], odometry[1], seeds[0], sequence, r01[0], resample_fraction, stats);
     HIPCHK(hipSetDevice(m->device));
-    int rc = slam_batch_staging(s, "gms_slam_frame_batch");
+    rc = slam_batch_staging(s, "gms_slam_frame_batch");
     if (rc) return rc;
     void *slot = nullptr;
     rc = gms_ring_acquire(s->batch_ring, &slot);
     if (rc) return rc;
-    // [S][L] angle | [S][L] distance | [S][L] hit | (to a 16-byte boundary) [S] SlamFilterArgs
-    const size_t SL = (size_t)S * (size_t)L;
-    double *h_a = static_cast<double *>(slot), *h_d = h_a + SL;
-    uint8_t *h_h = reinterpret_cast<uint8_t *>(h_d + SL);
-    SlamFilterArgs *h_tab = reinterpret_cast<SlamFilterArgs *>(static_cast<unsigned char *>(slot) + ((SL * 17 + 15) & ~(size_t)15));
-    memcpy(h_a, angle, SL * 8); memcpy(h_d, distance, SL * 8); memcpy(h_h, hit, SL);
+    const RawRows raw = slam_lay_raw(slot, S, L, angle, distance, hit);                // ... | [S] SlamFilterArgs
+    SlamFilterArgs *h_tab = reinterpret_cast<SlamFilterArgs *>(static_cast<unsigned char *>(slot) + raw.behind);
     s->frame_counts.resize((size_t)S);
     for (int32_t f = 0; f < S; f++) {
         s->frame_counts[f] = lengths ? lengths[f] : L;
         h_tab[f] = slam_filter_args(odometry + 2 * (size_t)f, seeds[f], s->frame_counts[f], true);
     }
-    gms_launch_slam_deskew(m, h_a, h_d, h_h, L, S, Lmax, 0, 0.0, 0.0, h_tab, slam_batch_tab(s), s->d_batch, m->max_beams);
+    gms_launch_slam_deskew(m, raw.angle, raw.distance, raw.hit, L, S, Lmax, 0, 0.0, 0.0, h_tab, slam_batch_tab(s), s->d_batch, m->max_beams);
     rc = gms_ring_commit(s->batch_ring, m->stream);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
@@ -608,63 +604,47 @@ int gms_slam_last_beams(gms_slam *s, int32_t f, gms_beam *out, int32_t cap, int3
     return GMS_OK;
 }
 
-static int slam_map_xfer(gms_slam *s, int32_t i, int32_t count, double *dev_base, double *host, bool to_device) {
+// logData and / or likelihoodData (NULL: not that one) of particles [first, first + count), between the host and every filter's current
+// generation.  Opens with the device, likelihoodData written out if it is the subject (an upload: the other slots' fields first, then this
+// one's over its copy) and the generations; closes when the copies have landed.
+static int slam_maps_xfer(gms_slam *s, int32_t first, int32_t count, double *log_data, double *lik, bool to_device) {
     gms_map *m = s->map;
+    HIPCHK(hipSetDevice(m->device));
+    int rc = lik ? slam_lik_current(s) : GMS_OK;
+    std::vector<int32_t> gen((size_t)s->n_filters);
+    if (!rc) rc = slam_host_gen(s, gen.data());
+    if (rc) return rc;
     const size_t cells = (size_t)m->gd.cells;
-    double *dev = dev_base + (size_t)i * cells;
-    const size_t bytes = (size_t)count * cells * sizeof(double);
-    if (to_device) HIPCHK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, m->stream));
-    else HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, m->stream));
+    const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    for (int32_t i = first, end; i < first + count; i = end) {                // (every filter from its own current generation)
+        const int32_t f = i / s->n_per, cur = gen[(size_t)f];
+        end = std::min(first + count, (f + 1) * s->n_per);
+        const size_t at = (size_t)i * cells, host_at = (size_t)(i - first) * cells, bytes = (size_t)(end - i) * cells * sizeof(double);
+        double *const host[2] = {log_data, lik}, *const dev[2] = {s->d_log[cur], s->d_lik[cur]};
+        for (int k = 0; k < 2; k++) {
+            if (!host[k]) continue;
+            HIPCHK(hipMemcpyAsync(to_device ? dev[k] + at : host[k] + host_at, to_device ? host[k] + host_at : dev[k] + at, bytes, kind, m->stream));
+            if (k == 0 && to_device && s->d_code[0])                          // the slots' class plane 0 follows their logData (plane 1, their field's, does not)
+                gms_launch_slam_codes_from_log(m, gms_slam_bufs(s), i, end - i, s->code_words);
+        }
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
     return GMS_OK;
 }
 
 int gms_slam_download_map(gms_slam *s, int32_t i, double *log_data, double *lik) {          // Particle.m (SLAM.java:33)
     REQUIRE(s && i >= 0 && i < s->n, "gms_slam_download_map: particle index out of range");
-    HIPCHK(hipSetDevice(s->map->device));
-    int rc = lik ? slam_lik_current(s) : GMS_OK;
-    std::vector<int32_t> gen((size_t)s->n_filters);
-    if (!rc) rc = slam_host_gen(s, gen.data());
-    const int32_t cur = gen[(size_t)(i / s->n_per)];
-    if (!rc && log_data) rc = slam_map_xfer(s, i, 1, s->d_log[cur], log_data, false);
-    if (!rc && lik) rc = slam_map_xfer(s, i, 1, s->d_lik[cur], lik, false);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->map->stream));
-    return GMS_OK;
+    return slam_maps_xfer(s, i, 1, log_data, lik, false);
 }
 
 int gms_slam_download_maps(gms_slam *s, double *log_all, double *lik_all) {
     REQUIRE(s, "null handle");
-    HIPCHK(hipSetDevice(s->map->device));
-    int rc = lik_all ? slam_lik_current(s) : GMS_OK;
-    std::vector<int32_t> gen((size_t)s->n_filters);
-    if (!rc) rc = slam_host_gen(s, gen.data());
-    const size_t per = (size_t)s->n_per * (size_t)s->map->gd.cells;
-    for (int32_t f = 0; f < s->n_filters && !rc; f++) {             // (every filter from its own current generation)
-        const int32_t cur = gen[f], i0 = f * s->n_per;
-        if (log_all) rc = slam_map_xfer(s, i0, s->n_per, s->d_log[cur], log_all + f * per, false);
-        if (!rc && lik_all) rc = slam_map_xfer(s, i0, s->n_per, s->d_lik[cur], lik_all + f * per, false);
-    }
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->map->stream));
-    return GMS_OK;
+    return slam_maps_xfer(s, 0, s->n, log_all, lik_all, false);
 }
 
 int gms_slam_upload_map(gms_slam *s, int32_t i, const double *log_data, const double *lik) {
     REQUIRE(s && i >= 0 && i < s->n, "gms_slam_upload_map: particle index out of range");
-    HIPCHK(hipSetDevice(s->map->device));
-    int rc = lik ? slam_lik_current(s) : GMS_OK;                  // (the other slots' fields first, then this one's over its copy)
-    std::vector<int32_t> gen((size_t)s->n_filters);
-    if (!rc) rc = slam_host_gen(s, gen.data());
-    const int32_t cur = gen[(size_t)(i / s->n_per)];
-    if (!rc && log_data) {
-        rc = slam_map_xfer(s, i, 1, s->d_log[cur], const_cast<double *>(log_data), true);
-        if (!rc && s->d_code[0])                                  // the slot's class plane 0 follows its logData (plane 1, its field's, does not)
-            gms_launch_slam_codes_from_log(s->map, gms_slam_bufs(s), i, 1, s->code_words);
-    }
-    if (!rc && lik) rc = slam_map_xfer(s, i, 1, s->d_lik[cur], const_cast<double *>(lik), true);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->map->stream));
-    return GMS_OK;
+    return slam_maps_xfer(s, i, 1, const_cast<double *>(log_data), const_cast<double *>(lik), true);
 }
 
 // GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458) over the particles' maps, into the handle's own GridMap:

@@ -1164,7 +1164,7 @@ k_slam_gather_maps(SlamBufs sb, const int32_t *__restrict__ idx, int64_t cells) 
     }
 }
 
-// ... and one array only: resample() with likelihoodData's copies deferred (gms_slam::lik_behind) moves logData at once and
+// ... and one array only: resample() with likelihoodData's copies deferred (SLAM_FIELD_OWED_COPY) moves logData at once and
 // likelihoodData if and when somebody reads it before the next update's computeLikelihoodMap has overwritten it
 #ifndef GATHER_U
 #define GATHER_U 8
@@ -1339,13 +1339,7 @@ void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, co
                               int32_t integrate, int64_t code_words, const SlamBatch *batch) {
     const uint32_t *d_code = sb.code[0];
     gms_map *m = pf->map;
-    MotionArgs mo;
-    mo.on = 0; mo.d_center = mo.d_theta = mo.d_center_sd = mo.d_theta_sd = 0.0; mo.seed = mo.sequence = 0; mo.index0 = pf->offset;
-    if (motion) {
-        mo.on = 1; mo.d_center = motion->d_center; mo.d_theta = motion->d_theta; mo.seed = motion->seed; mo.sequence = motion->sequence;
-        mo.d_center_sd = (0.01 + fabs(motion->d_center) * 0.05) / 2;             // Odometry.java:63
-        mo.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(motion->d_theta);   // :64
-    }
+    const MotionArgs mo = motion_args(motion, pf->offset);
     ProfScope ps(m, GMS_K_SCORE);
     const int32_t Bpad = (B + 7) & ~7;
     constexpr int NP = 2;
@@ -1440,13 +1434,7 @@ bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, cons
     gms_map *m = pf->map;
     const RefinePlan r = slam_refine_plan(m, B, field_in_lds, code_words);
     if (!r.ok) return false;
-    MotionArgs mo;
-    mo.on = 0; mo.d_center = mo.d_theta = mo.d_center_sd = mo.d_theta_sd = 0.0; mo.seed = mo.sequence = 0; mo.index0 = pf->offset;
-    if (motion) {
-        mo.on = 1; mo.d_center = motion->d_center; mo.d_theta = motion->d_theta; mo.seed = motion->seed; mo.sequence = motion->sequence;
-        mo.d_center_sd = (0.01 + fabs(motion->d_center) * 0.05) / 2;             // Odometry.java:63
-        mo.d_theta_sd = 5 * (3.141592653589793 / 180.0) + 0.1 * fabs(motion->d_theta);   // :64
-    }
+    const MotionArgs mo = motion_args(motion, pf->offset);
     ProfScope ps(m, GMS_K_REFINE);
     const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;

@@ -734,52 +734,35 @@ def _put_kernel(p, kernel):
             p.kernel[i] = float(t)
 
 
-class SLAMParticleMaps:
-    """SLAM as the reference has it (J/slam/SLAM.java:26-204): num_particles particles, each with its own pose, weight AND
-    GridMapData -- update() scores a particle against its own likelihood field and integrates the scan into its own map at its own
-    pose (:88-107), resample() deep-copies the surviving particles' maps (:41-45).  (`SLAM` above is the shared-map filter that
-    BASELINE's configurations need.)  findBestPoseOptim (:97) is left out; the motion-model draw is Philox(seed; particle, sequence)."""
+class _SlamHandle:
+    """What SLAMParticleMaps and SLAMParticleMapsBatch share: one gms_slam handle with its borrowed map and filter; the particles'
+    maps are addressed by handle-wide slot (filter f's particle i: f * num_particles + i)."""
 
-    def __init__(self, width=6.0, height=6.0, resolution=0.05, position=(-3.0, -3.0), num_particles=500, device: int = 0,
-                 max_beams: int = 0, kernel=None):
+    def _create(self, width, height, resolution, position, num_particles, device, max_beams, kernel, n_maps=1, offset=None, n_global=None):
+        """gms_slam_create with n_maps filters of num_particles each, or -- offset, n_global -- gms_slam_create_shard for one block"""
         L = load()
         p = GmsParams()
         check(L.gms_params_default(C.byref(p), width, height, resolution, position[0], position[1]))   # SLAM.java:57
+        p.n_maps = int(n_maps)
         p.device = device
         p.max_beams = max_beams
         _put_kernel(p, kernel)
         self.params = p
         self.num_particles = int(num_particles)                                                          # :50
         self._h = C.c_void_p()
-        check(L.gms_slam_create(C.byref(p), self.num_particles, C.byref(self._h)))
+        if offset is None:
+            check(L.gms_slam_create(C.byref(p), self.num_particles, C.byref(self._h)))
+        else:
+            check(L.gms_slam_create_shard(C.byref(p), self.num_particles, int(offset), int(n_global), C.byref(self._h)))
         mh, ph = C.c_void_p(), C.c_void_p()
         check(L.gms_slam_handles(self._h, C.byref(mh), C.byref(ph)))
-        self.grid_map = _BorrowedMap(mh, p)                     # getGridMap() (:200); its GridMapData receives calculate_combined()
+        self.grid_map = _BorrowedMap(mh, p)                     # getGridMap() (:200); map f's GridMapData receives filter f's combined map
         self.pf = _BorrowedFilter(ph, self.grid_map, self.num_particles)
+        self.pf.n_maps = int(n_maps)                            # (the filter's arrays are [n_maps][n])
+        if offset is not None:
+            self.pf.offset, self.pf.n_global = int(offset), int(n_global)
         self.W, self.H = self.grid_map.W, self.grid_map.H
-        self.strongest = 0
-        self.neff = float(num_particles)
         self.sequence = 0
-
-    def _init_shard(self, width, height, resolution, position, n_local, offset, n_global, device=0, max_beams=0, kernel=None):
-        """one rank's block of a sharded filter (gms_slam_create_shard): distributed.SlamShardOps"""
-        L = load()
-        p = GmsParams()
-        check(L.gms_params_default(C.byref(p), width, height, resolution, position[0], position[1]))
-        p.device = device or 0
-        p.max_beams = max_beams
-        _put_kernel(p, kernel)
-        self.params = p
-        self.num_particles = int(n_local)
-        self._h = C.c_void_p()
-        check(L.gms_slam_create_shard(C.byref(p), int(n_local), int(offset), int(n_global), C.byref(self._h)))
-        mh, ph = C.c_void_p(), C.c_void_p()
-        check(L.gms_slam_handles(self._h, C.byref(mh), C.byref(ph)))
-        self.grid_map = _BorrowedMap(mh, p)
-        self.pf = _BorrowedFilter(ph, self.grid_map, self.num_particles)
-        self.pf.offset, self.pf.n_global = int(offset), int(n_global)
-        self.W, self.H = self.grid_map.W, self.grid_map.H
-        self.strongest, self.neff, self.sequence = 0, float(n_global), 0
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -801,24 +784,84 @@ class SLAMParticleMaps:
         before weighting it (SLAM.java:96; the reference calls findBestPoseOptim, :97, and keeps this search commented out beside it)"""
         check(load().gms_slam_set_refine(self._h, int(bool(on))))
 
+    def maps_copied(self) -> int:
+        v = C.c_int64(0)
+        check(load().gms_slam_copies(self._h, C.byref(v)))
+        return int(v.value)
+
+    def _next_sequence(self, sequence: Optional[int]) -> int:
+        """the caller's sequence number, or the handle's own counter"""
+        if sequence is None:
+            sequence = self.sequence
+            self.sequence += 1
+        return int(sequence)
+
+    @staticmethod
+    def _stats_dict(st) -> dict:
+        return {"weight_sum": st.weight_sum, "neff": st.neff, "strongest": st.strongest, "n_zero": st.n_zero,
+                "max_log_weight": st.max_log_weight}
+
+    def _map_of(self, slot: int, likelihood: bool) -> np.ndarray:
+        out = np.empty((self.H, self.W), dtype=np.float64)
+        check(load().gms_slam_download_map(self._h, int(slot), None if likelihood else ptr(out), ptr(out) if likelihood else None))
+        return out
+
+    def _set_map(self, slot: int, log, lik):
+        lg = None if log is None else np.ascontiguousarray(log, dtype=np.float64)
+        lk = None if lik is None else np.ascontiguousarray(lik, dtype=np.float64)
+        for name, a in (("log", lg), ("lik", lk)):          # (the library copies W * H doubles from the pointer it is given)
+            if a is not None and a.size != self.W * self.H:
+                raise ValueError(f"set_map: {name} has {a.size} values, the map has {self.W} x {self.H} cells")
+        check(load().gms_slam_upload_map(self._h, int(slot), None if lg is None else ptr(lg), None if lk is None else ptr(lk)))
+
+    def _trace_scan(self, slot: int, z, cap: int):
+        b = _beams_of(z)
+        cap = int(cap) if cap > 0 else self.W + self.H + 8
+        cells = np.zeros((len(b), cap, 2), dtype=np.int32)
+        cls = np.zeros((len(b), cap), dtype=np.uint8)
+        counts = np.zeros(len(b), dtype=np.int32)
+        check(load().gms_slam_trace_scan(self._h, int(slot), ptr(b), len(b), ptr(cells), ptr(cls), cap, ptr(counts)))
+        return cells, cls, counts
+
+    def _last_beams(self, f: int) -> np.ndarray:
+        out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
+        c = C.c_int32(0)
+        check(load().gms_slam_last_beams(self._h, int(f), ptr(out), len(out), C.byref(c)))
+        return out[:c.value].copy()
+
+
+class SLAMParticleMaps(_SlamHandle):
+    """SLAM as the reference has it (J/slam/SLAM.java:26-204): num_particles particles, each with its own pose, weight AND
+    GridMapData -- update() scores a particle against its own likelihood field and integrates the scan into its own map at its own
+    pose (:88-107), resample() deep-copies the surviving particles' maps (:41-45).  (`SLAM` above is the shared-map filter that
+    BASELINE's configurations need.)  findBestPoseOptim (:97) is left out; the motion-model draw is Philox(seed; particle, sequence)."""
+
+    def __init__(self, width=6.0, height=6.0, resolution=0.05, position=(-3.0, -3.0), num_particles=500, device: int = 0,
+                 max_beams: int = 0, kernel=None):
+        self._create(width, height, resolution, position, num_particles, device, max_beams, kernel)
+        self.strongest = 0
+        self.neff = float(num_particles)
+
+    def _init_shard(self, width, height, resolution, position, n_local, offset, n_global, device=0, max_beams=0, kernel=None):
+        """one rank's block of a sharded filter (gms_slam_create_shard): distributed.SlamShardOps"""
+        self._create(width, height, resolution, position, n_local, device or 0, max_beams, kernel, offset=offset, n_global=n_global)
+        self.strongest, self.neff = 0, float(n_global)
+
     def update(self, z, odometry=None, seed: int = 0, sequence: Optional[int] = None, fetch: bool = True, sample_motion: bool = True):
         """update(z, u) (:80-131); odometry = (dCenter, dTheta) or None (= (0, 0) and no motion sample: `u == null` in
         sampleMotionModel, :159); sample_motion = False keeps the poses (dTheta still decides skipUpdate, :82); returns Neff"""
         b = _beams_of(z)
         have = odometry is not None and sample_motion
         dc, dt = (odometry if odometry is not None else (0.0, 0.0))
-        if sequence is None:
-            sequence = self.sequence
-            self.sequence += 1
         st = GmsPfStats()
-        check(load().gms_slam_update_per_particle(self._h, ptr(b), len(b), int(have), float(dc), float(dt), int(seed), int(sequence),
-                                                  C.byref(st) if fetch else None))
-        if fetch:
-            self.strongest, self.neff = st.strongest, st.neff
-            self.last_stats = {"weight_sum": st.weight_sum, "neff": st.neff, "strongest": st.strongest, "n_zero": st.n_zero,
-                               "max_log_weight": st.max_log_weight}
-            return st.neff
-        return None
+        check(load().gms_slam_update_per_particle(self._h, ptr(b), len(b), int(have), float(dc), float(dt), int(seed),
+                                                  self._next_sequence(sequence), C.byref(st) if fetch else None))
+        return self._fetched(st) if fetch else None
+
+    def _fetched(self, st) -> float:
+        self.strongest, self.neff = st.strongest, st.neff
+        self.last_stats = self._stats_dict(st)
+        return st.neff
 
     def update_dev(self, dev_beams: int, B: int, odometry=None, seed: int = 0, sequence: int = 0, sample_motion: bool = True):
         have = odometry is not None and sample_motion
@@ -836,26 +879,16 @@ class SLAMParticleMaps:
         h = np.ascontiguousarray(hits, dtype=np.uint8)
         if not (a.ndim == d.ndim == h.ndim == 1 and a.size == d.size == h.size):
             raise ValueError("frame: angles, distances and hits must be one-dimensional and of one length")
-        if sequence is None:
-            sequence = self.sequence
-            self.sequence += 1
+        sequence = self._next_sequence(sequence)
         r = float(np.random.random() if r01 is None else r01)
         st = GmsPfStats()
         check(load().gms_slam_frame_per_particle(self._h, ptr(a), ptr(d), ptr(h), a.size, float(d_center), float(d_theta), int(seed),
-                                                 int(sequence), r, float(fraction), C.byref(st) if fetch else None))
-        if fetch:
-            self.strongest, self.neff = st.strongest, st.neff
-            self.last_stats = {"weight_sum": st.weight_sum, "neff": st.neff, "strongest": st.strongest, "n_zero": st.n_zero,
-                               "max_log_weight": st.max_log_weight}
-            return st.neff
-        return None
+                                                 sequence, r, float(fraction), C.byref(st) if fetch else None))
+        return self._fetched(st) if fetch else None
 
     def last_beams(self) -> np.ndarray:
         """the de-skewed revolution of the last frame() call (diagnostics; synchronises)"""
-        out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
-        c = C.c_int32(0)
-        check(load().gms_slam_last_beams(self._h, 0, ptr(out), len(out), C.byref(c)))
-        return out[:c.value].copy()
+        return self._last_beams(0)
 
     def resample(self, r01: Optional[float] = None, want_indices: bool = False):
         """resample() (:133-153): r01 stands for Math.random()"""
@@ -886,9 +919,7 @@ class SLAMParticleMaps:
 
     def map_of(self, i: int, likelihood: bool = False) -> np.ndarray:
         """Particle i's logData (or likelihoodData) as [H][W] (Particle.m, :33)"""
-        out = np.empty((self.H, self.W), dtype=np.float64)
-        check(load().gms_slam_download_map(self._h, int(i), None if likelihood else ptr(out), ptr(out) if likelihood else None))
-        return out
+        return self._map_of(i, likelihood)
 
     def maps(self, likelihood: bool = False) -> np.ndarray:
         out = np.empty((self.num_particles, self.H, self.W), dtype=np.float64)
@@ -896,12 +927,7 @@ class SLAMParticleMaps:
         return out
 
     def set_map(self, i: int, log=None, lik=None):
-        lg = None if log is None else np.ascontiguousarray(log, dtype=np.float64)
-        lk = None if lik is None else np.ascontiguousarray(lik, dtype=np.float64)
-        for name, a in (("log", lg), ("lik", lk)):          # (the library copies W * H doubles from the pointer it is given)
-            if a is not None and a.size != self.W * self.H:
-                raise ValueError(f"set_map: {name} has {a.size} values, the map has {self.W} x {self.H} cells")
-        check(load().gms_slam_upload_map(self._h, int(i), None if lg is None else ptr(lg), None if lk is None else ptr(lk)))
+        self._set_map(i, log, lik)
 
     def calculate_combined(self) -> np.ndarray:
         """GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458): the combined logData [H][W]; the likelihood field of it is
@@ -912,18 +938,7 @@ class SLAMParticleMaps:
     def trace_scan(self, i: int, z, cap: int = 0):
         """(cells [B][cap][2], classes [B][cap], counts [B]): the cell walk of integrateObservation for particle i at its current pose
         as the update kernel walks and classifies it (prior-class visits included), in walk order; nothing is written to a map"""
-        b = _beams_of(z)
-        cap = int(cap) if cap > 0 else self.W + self.H + 8
-        cells = np.zeros((len(b), cap, 2), dtype=np.int32)
-        cls = np.zeros((len(b), cap), dtype=np.uint8)
-        counts = np.zeros(len(b), dtype=np.int32)
-        check(load().gms_slam_trace_scan(self._h, int(i), ptr(b), len(b), ptr(cells), ptr(cls), cap, ptr(counts)))
-        return cells, cls, counts
-
-    def maps_copied(self) -> int:
-        v = C.c_int64(0)
-        check(load().gms_slam_copies(self._h, C.byref(v)))
-        return int(v.value)
+        return self._trace_scan(i, z, cap)
 
     def get_strongest_particle(self) -> int:
         return self.strongest                                                                            # :196
@@ -938,52 +953,17 @@ class SLAMParticleMaps:
     getGridMap = get_grid_map
 
 
-class SLAMParticleMapsBatch:
+class SLAMParticleMapsBatch(_SlamHandle):
     """num_filters independent SLAMParticleMaps filters in ONE handle (gms_slam_create with gms_params.n_maps = S): every update and
     resampling step is one launch of each kernel for all of them, and filter f computes, bit for bit, what a stand-alone
     SLAMParticleMaps would from the same scans, odometry and seed.  Filter-local particle indices throughout."""
 
     def __init__(self, num_filters: int, width=6.0, height=6.0, resolution=0.05, position=(-3.0, -3.0), num_particles=500,
                  device: int = 0, max_beams: int = 0, kernel=None):
-        L = load()
-        p = GmsParams()
-        check(L.gms_params_default(C.byref(p), width, height, resolution, position[0], position[1]))
-        p.n_maps = int(num_filters)
-        p.device = device
-        p.max_beams = max_beams
-        _put_kernel(p, kernel)
-        self.params = p
         self.num_filters = int(num_filters)
-        self.num_particles = int(num_particles)
-        self._h = C.c_void_p()
-        check(L.gms_slam_create(C.byref(p), self.num_particles, C.byref(self._h)))
-        mh, ph = C.c_void_p(), C.c_void_p()
-        check(L.gms_slam_handles(self._h, C.byref(mh), C.byref(ph)))
-        self.grid_map = _BorrowedMap(mh, p)                     # map f receives calculate_combined(f)
-        self.pf = _BorrowedFilter(ph, self.grid_map, self.num_particles)
-        self.pf.n_maps = self.num_filters                       # (the filter's arrays are [S][n])
-        self.W, self.H = self.grid_map.W, self.grid_map.H
+        self._create(width, height, resolution, position, num_particles, device, max_beams, kernel, n_maps=num_filters)
         self.strongest = np.zeros(self.num_filters, dtype=np.int64)
         self.neff = np.full(self.num_filters, float(num_particles))
-        self.sequence = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.grid_map.close(); self.pf.close()
-            check(load().gms_slam_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        check(load().gms_slam_reset(self._h))
-
-    def set_refine(self, on: bool = True):
-        check(load().gms_slam_set_refine(self._h, int(bool(on))))
 
     def _per_filter(self, v, dtype):
         return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (self.num_filters,)))
@@ -1009,16 +989,13 @@ class SLAMParticleMapsBatch:
         have = np.array([o is not None for o in odo]) & sm
         have = np.ascontiguousarray(have.astype(np.int32))
         sd = self._per_filter(seeds, np.uint64)
-        if sequence is None:
-            sequence = self.sequence
-            self.sequence += 1
         st = (GmsPfStats * S)()
-        check(load().gms_slam_update_batch(self._h, ptr(block), B, ptr(counts), ptr(u), ptr(sd), ptr(have), int(sequence),
+        check(load().gms_slam_update_batch(self._h, ptr(block), B, ptr(counts), ptr(u), ptr(sd), ptr(have), self._next_sequence(sequence),
                                            st if fetch else None))
-        if not fetch:
-            return None
-        self.last_stats = [{"weight_sum": s.weight_sum, "neff": s.neff, "strongest": s.strongest, "n_zero": s.n_zero,
-                            "max_log_weight": s.max_log_weight} for s in st]
+        return self._fetched(st) if fetch else None
+
+    def _fetched(self, st) -> np.ndarray:
+        self.last_stats = [self._stats_dict(s) for s in st]
         self.strongest = np.array([s.strongest for s in st], dtype=np.int64)       # (filter-local)
         self.neff = np.array([s.neff for s in st], dtype=np.float64)
         return self.neff.copy()
@@ -1049,26 +1026,14 @@ class SLAMParticleMapsBatch:
         ln = None if lengths is None else self._per_filter(lengths, np.int32)
         sd = self._per_filter(seeds, np.uint64)
         r = self._per_filter(np.random.random(S) if r01 is None else r01, np.float64)
-        if sequence is None:
-            sequence = self.sequence
-            self.sequence += 1
         st = (GmsPfStats * S)()
         check(load().gms_slam_frame_batch(self._h, ptr(a), ptr(d), ptr(h), a.shape[1], None if ln is None else ptr(ln), ptr(u), ptr(sd),
-                                          int(sequence), ptr(r), float(fraction), st if fetch else None))
-        if not fetch:
-            return None
-        self.last_stats = [{"weight_sum": s.weight_sum, "neff": s.neff, "strongest": s.strongest, "n_zero": s.n_zero,
-                            "max_log_weight": s.max_log_weight} for s in st]
-        self.strongest = np.array([s.strongest for s in st], dtype=np.int64)
-        self.neff = np.array([s.neff for s in st], dtype=np.float64)
-        return self.neff.copy()
+                                          self._next_sequence(sequence), ptr(r), float(fraction), st if fetch else None))
+        return self._fetched(st) if fetch else None
 
     def last_beams(self, f: int) -> np.ndarray:
         """filter f's de-skewed revolution of the last frame() call (diagnostics; synchronises)"""
-        out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
-        c = C.c_int32(0)
-        check(load().gms_slam_last_beams(self._h, int(f), ptr(out), len(out), C.byref(c)))
-        return out[:c.value].copy()
+        return self._last_beams(f)
 
     def resample(self, r01=None, want_indices: bool = False):
         """resample() of every filter; r01 [S] (or one for all).  want_indices: (indices [S][n] filter-local, n_ambiguous [S])"""
@@ -1115,9 +1080,7 @@ class SLAMParticleMapsBatch:
 
     def map_of(self, f: int, i: int, likelihood: bool = False) -> np.ndarray:
         """filter f's particle i's logData (or likelihoodData) as [H][W]"""
-        out = np.empty((self.H, self.W), dtype=np.float64)
-        check(load().gms_slam_download_map(self._h, self._slot(f, i), None if likelihood else ptr(out), ptr(out) if likelihood else None))
-        return out
+        return self._map_of(self._slot(f, i), likelihood)
 
     def maps(self, f: Optional[int] = None, likelihood: bool = False) -> np.ndarray:
         """filter f's maps [n][H][W]; f = None: every filter's [S][n][H][W]"""
@@ -1126,12 +1089,7 @@ class SLAMParticleMapsBatch:
         return out if f is None else out[int(f)]
 
     def set_map(self, f: int, i: int, log=None, lik=None):
-        lg = None if log is None else np.ascontiguousarray(log, dtype=np.float64)
-        lk = None if lik is None else np.ascontiguousarray(lik, dtype=np.float64)
-        for name, a in (("log", lg), ("lik", lk)):
-            if a is not None and a.size != self.W * self.H:
-                raise ValueError(f"set_map: {name} has {a.size} values, the map has {self.W} x {self.H} cells")
-        check(load().gms_slam_upload_map(self._h, self._slot(f, i), None if lg is None else ptr(lg), None if lk is None else ptr(lk)))
+        self._set_map(self._slot(f, i), log, lik)
 
     def calculate_combined(self, f: int, likelihood: bool = False) -> np.ndarray:
         """GridMapApp.calculateCombined over filter f's particles: its logData [H][W] (likelihood: the field of it)"""
@@ -1142,15 +1100,4 @@ class SLAMParticleMapsBatch:
         return out.reshape(self.num_filters, self.H, self.W)[int(f)]
 
     def trace_scan(self, f: int, i: int, z, cap: int = 0):
-        b = _beams_of(z)
-        cap = int(cap) if cap > 0 else self.W + self.H + 8
-        cells = np.zeros((len(b), cap, 2), dtype=np.int32)
-        cls = np.zeros((len(b), cap), dtype=np.uint8)
-        counts = np.zeros(len(b), dtype=np.int32)
-        check(load().gms_slam_trace_scan(self._h, self._slot(f, i), ptr(b), len(b), ptr(cells), ptr(cls), cap, ptr(counts)))
-        return cells, cls, counts
-
-    def maps_copied(self) -> int:
-        v = C.c_int64(0)
-        check(load().gms_slam_copies(self._h, C.byref(v)))
-        return int(v.value)
+        return self._trace_scan(self._slot(f, i), z, cap)

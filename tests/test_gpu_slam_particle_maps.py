@@ -253,7 +253,7 @@ def test_sixteen_bit_count_tiles_and_their_fallback(monkeypatch):
 
 
 @pytest.mark.parametrize("lazy, held", [
-    pytest.param("1", "planes", id="1"),                    # slam_resample: lik_from_codes -- the planes travel with logData
+    pytest.param("1", "planes", id="1"),                    # slam_resample: SLAM_FIELD_FROM_PLANES -- the planes travel with logData
     pytest.param("0", "planes", id="0"),                    # (the same branch: the planes define likelihoodData either way)
     pytest.param("1", "eager", id="eager-1"),               # lazy_lik: logData now (d_idx_lik kept), the owed copy in slam_lik_current
     pytest.param("0", "eager", id="eager-0"),               # the last branch: k_slam_gather_maps, both arrays at once, no planes
