@@ -54,6 +54,19 @@ class GmsPfStats(C.Structure):
     ]
 
 
+class GmsView(C.Structure):
+    """gms_view: a rectangle of a map as grey levels (gridmapslam.h "map views")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("decimate", C.c_int32), ("source", C.c_int32), ("format", C.c_int32), ("filter", C.c_int32),
+    ]
+
+
+GMS_VIEW_GREY8, GMS_VIEW_PACKED32 = 0, 1
+GMS_VIEW_LOG, GMS_VIEW_LIKELIHOOD = 0, 1
+GMS_VIEW_STRONGEST = -1
+
+
 class GmsError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libgridmapslam error {code}: {msg}")
@@ -227,6 +240,12 @@ def load() -> C.CDLL:
     sig("gms_slam_resample_sharded_maps", C.c_int, vp, vp, f64, f64, C.POINTER(C.c_int32))
     sig("gms_slam_plan_exchange", C.c_int, vp, i32, i32, i32, vp, vp, vp, vp, vp)
     sig("gms_debug_set_stamps", C.c_int, vp, vp)
+    vw = C.POINTER(GmsView)
+    sig("gms_view_size", C.c_int, vw, vp, vp, vp)
+    sig("gms_map_view", C.c_int, vp, i32, vw, vp)
+    sig("gms_map_view_dev", C.c_int, vp, i32, vw, vp)
+    sig("gms_slam_view", C.c_int, vp, i32, vw, vp, vp)
+    sig("gms_slam_view_dev", C.c_int, vp, i32, vw, vp, vp)
     _lib = L
     return L
 

@@ -244,7 +244,7 @@ static int map_free(gms_map *m) {
     prof_drain(m);
     for (ProfSlot &s : m->prof_free) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
     hipFree(m->d_log); hipFree(m->d_lik); hipFree(m->d_fac); hipFree(m->d_cnt); hipFree(m->d_cnt_pend); hipFree(m->d_bbox); hipFree(m->d_taps); hipFree(m->d_tile_state); hipFree(m->d_tile_stats);
-    hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch);
+    hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch); hipFree(m->d_view);
     hipFree(m->d_trace_cells); hipFree(m->d_trace_cls); hipFree(m->d_trace_cnt);
     if (m->h_beams) hipHostFree(m->h_beams);
     ring_free(m->beam_ring);
@@ -582,6 +582,69 @@ int gms_map_get_at_point(gms_map *m, int32_t mi, float point_x, float point_y, d
     if (likelihood) *likelihood = h[1];
     return GMS_OK;
 }
+
+// ---- map views (gridmapslam.h "map views") -----------------------------------------------------------------------------------
+int gms_view_size(const gms_view *v, int32_t *out_w, int32_t *out_h, int64_t *bytes) {
+    REQUIRE(v, "gms_view_size: null view");
+    REQUIRE(v->w >= 1 && v->h >= 1 && v->x0 >= 0 && v->y0 >= 0, "gms_view: the rectangle needs w, h >= 1 and x0, y0 >= 0");
+    REQUIRE(v->decimate >= 1, "gms_view: decimate must be >= 1");
+    REQUIRE(v->source == GMS_VIEW_LOG || v->source == GMS_VIEW_LIKELIHOOD, "gms_view: source must be GMS_VIEW_LOG or GMS_VIEW_LIKELIHOOD");
+    REQUIRE(v->format == GMS_VIEW_GREY8 || v->format == GMS_VIEW_PACKED32, "gms_view: format must be GMS_VIEW_GREY8 or GMS_VIEW_PACKED32");
+    const int64_t d = v->decimate, ow = (v->w + d - 1) / d, oh = (v->h + d - 1) / d;
+    if (out_w) *out_w = (int32_t)ow;
+    if (out_h) *out_h = (int32_t)oh;
+    if (bytes) *bytes = ow * oh * (v->format == GMS_VIEW_PACKED32 ? 4 : 1);
+    return GMS_OK;
+}
+
+static int map_view(gms_map *m, int32_t mi, const gms_view *v, void *out, bool on_device) {
+    REQUIRE(m && v && out, "gms_map_view: null argument (the map, the view and the output are required)");
+    REQUIRE(mi >= 0 && mi < m->n_maps, "gms_map_view: map index out of range");
+    int64_t bytes = 0;
+    int rc = gms_view_check(v, m->gd.W, m->gd.H, "gms_map_view", &bytes);
+    if (rc) return rc;
+    REQUIRE(!on_device || v->format != GMS_VIEW_PACKED32 || ((uintptr_t)out & 3) == 0, "gms_map_view_dev: a packed view needs a 4-byte aligned output");
+    HIPCHK(hipSetDevice(m->device));
+    const bool lik = v->source == GMS_VIEW_LIKELIHOOD;
+    if (lik) gms_ensure_lik(m);                        // what gms_map_download_likelihood opens with
+    else gms_flush_apply(m);                           // ... and gms_map_download_log
+    unsigned char *base = nullptr;
+    if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
+    gms_launch_view(m, (lik ? m->d_lik : m->d_log) + (size_t)mi * (size_t)m->gd.cells, v, on_device ? out : base + 16);
+    HIPCHK(hipGetLastError());
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(out, base + 16, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    return GMS_OK;
+}
+int gms_map_view(gms_map *m, int32_t mi, const gms_view *v, void *out) { return map_view(m, mi, v, out, false); }
+int gms_map_view_dev(gms_map *m, int32_t mi, const gms_view *v, void *dev_out) { return map_view(m, mi, v, dev_out, true); }
+
+}  // extern "C"
+// v against a W x H map: gms_view_size's checks, then the rectangle inside [0, W] x [0, H]; *bytes: the image's size
+int gms_view_check(const gms_view *v, int32_t W, int32_t H, const char *what, int64_t *bytes) {
+    int rc = gms_view_size(v, nullptr, nullptr, bytes);
+    if (rc) return rc;
+    if ((int64_t)v->x0 + v->w > W || (int64_t)v->y0 + v->h > H)
+        return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, v->x0, v->y0, v->w, v->h, W, H);
+    return GMS_OK;
+}
+// The host forms' device staging: 16 bytes for the shown index, the image behind them.  Kept on the handle and only ever grown (a
+// stream synchronise, then a larger allocation), so a sequence of views of one size allocates once.
+int gms_view_staging(gms_map *m, int64_t image_bytes, unsigned char **base) {
+    const size_t need = 16 + (size_t)image_bytes;
+    if (m->view_cap < need) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        hipFree(m->d_view); m->d_view = nullptr; m->view_cap = 0;
+        const size_t cap = (need + 65535) & ~(size_t)65535;
+        if (hipMalloc(&m->d_view, cap) != hipSuccess) { m->d_view = nullptr; return gms_fail(GMS_ERR_NOMEM, "gms_view: staging allocation of %zu bytes failed", cap); }
+        m->view_cap = cap;
+    }
+    *base = m->d_view;
+    return GMS_OK;
+}
+extern "C" {
 
 // beams [n_maps][B] (host) -> d_beams [n_maps][max_beams]
 static int stage_beams(gms_map *m, const gms_beam *beams, int32_t B) {

@@ -114,6 +114,8 @@ struct gms_map {
     gms_beam *d_beams;    // [n_maps][max_beams] staging
     float *d_poses;       // [n_maps][3] staging
     double *d_scratch;    // small device scratch
+    unsigned char *d_view; // staging of the host forms of gms_map_view / gms_slam_view: [16 bytes: the shown index][the image]; grows, never per view
+    size_t view_cap;      // its size in bytes
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -364,6 +366,7 @@ struct gms_slam {
     uint32_t *d_code[2];            // [n][2][code_words] every particle's class planes (gms_slam_kernels.hip), double-buffered with logData; NULL: not kept
                                     // (the blur kernel is wider than the on-demand evaluation takes, the plane does not fit the LDS, or GMS_SLAM_EAGER_LIK=1)
     int64_t code_words;             // 32-bit words per plane
+    int32_t have_strongest;         // an update has normalised since the last reset: the filter's statistics name a strongest particle (gms_slam_view)
     int32_t refine;                 // gms_slam_set_refine: update() runs findBestPose on every particle against its own field before weighting it (SLAM.java:96)
     int32_t refine_field;           // the field in front of the refinement: -1 from the class plane where logData exceeds the infinity cache, 0 from logData
                                     // always, 1 from the plane always (GMS_SLAM_REFINE_FIELD=log|codes: tests of both forms)
@@ -448,6 +451,12 @@ void gms_launch_copy(gms_map *m, void *dst, const void *src, size_t nbytes);   /
 void gms_invalidate_tile_state(gms_map *m);
 void gms_launch_get_raw(gms_map *m, int32_t mi, int32_t x, int32_t y, double *d_out2);
 void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out, int64_t n);
+// map views (GridMap.render's grey levels, gridmapslam.h "map views"): the checked rectangle of v against a W x H map and its output
+// size (gms_host.hip); the host forms' staging, base[0 .. 16) for the shown index and the image behind it; the launch for one map's
+// array (src: W x H doubles of v->source's kind)
+int gms_view_check(const gms_view *v, int32_t W, int32_t H, const char *what, int64_t *bytes);
+int gms_view_staging(gms_map *m, int64_t image_bytes, unsigned char **base);
+void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
 
 void gms_launch_pf_init(gms_pf *pf);
 void gms_launch_pf_pose_trig(gms_pf *pf, const float *d_src);
@@ -508,6 +517,13 @@ bool gms_slam_refine_from_planes(const gms_map *m, int32_t B, int32_t field_in_l
 // planes), bit 1 likelihoodData; d_idx_keep (may be NULL) receives the indices for a likelihoodData copy that is still owed
 void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const int32_t *d_idx, int32_t *d_idx_keep, int64_t code_words);
 void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n_filters);   // filter f's particles into map f of dst
+// a view of one particle's map: which >= 0 the particle, which < 0 the strongest of `filter` by d_stats[filter] (picked on the device).
+// field: where a likelihood view reads (ignored by a log view) -- SLAM_FIELD_IN_MEMORY the current generation, SLAM_FIELD_OWED_COPY the
+// source d_idx_lik names in the other one where the last resample() drew.  d_shown (may be NULL) receives the handle-wide index.
+void gms_launch_slam_view(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_stats, int32_t which, int32_t filter, SlamField field,
+                          const int32_t *d_idx_lik, const gms_view *v, void *d_out, int32_t *d_shown);
+// likelihoodData of that ONE particle from plane 1 of its class planes, into its slot of the current generation (SLAM_FIELD_FROM_PLANES)
+void gms_launch_slam_likelihood_shown(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_stats, int32_t which, int32_t filter, int64_t code_words);
 void gms_launch_slam_export_records(gms_pf *pf, const SlamBufs &sb, const int32_t *d_list, int32_t count, int64_t code_words, double *d_dst);
 void gms_launch_slam_shard_gather(gms_pf *pf, const SlamBufs &sb, const int32_t *d_src_local, const int32_t *d_recv_pos, const double *d_recv, int64_t code_words);
 

@@ -1166,6 +1166,121 @@ __global__ void k_get_raw(GridDev g, const double *__restrict__ logd, int32_t mi
     out2[1] = (double)1.0f - (double)1.0f / (1.0 + exp(l));
 }
 
+// ---- map views: GridMap.render's grey levels (GridMap.java:371-388; the definition is in gridmapslam.h, "map views") ------------
+// One streaming pass over a rectangle of ONE map's logData or likelihoodData: 8 bytes read per cell, at most 1 (grey) or 4 (packed)
+// bytes written.  A lane makes four consecutive output pixels: at d = 1 four consecutive cells of a row, read as two 16-byte loads
+// (or 8 + 16 + 8 where the row starts on an odd cell), stored as one dword (grey) or one 16-byte store (packed).  The groups of four
+// are cut at the OUTPUT's own 4- / 16-byte boundaries, so every full group's store is aligned whatever the output pointer's
+// alignment and the rectangle's width; the first and the last group may be short and store their pixels one by one -- nothing
+// outside [out, out + bytes) is written.  Grid-stride over the groups.
+struct ViewDev {
+    int32_t W;                  // row pitch of the map in cells
+    int32_t x0, y0, w, h;       // the rectangle
+    int32_t d;                  // cells per pixel and axis (clamped to the rectangle's longer side: the same picture)
+    int32_t ow, oh;             // pixels
+};
+static ViewDev view_dev(const gms_map *m, const gms_view *v) {
+    ViewDev vd;
+    vd.W = m->gd.W; vd.x0 = v->x0; vd.y0 = v->y0; vd.w = v->w; vd.h = v->h;
+    const int32_t longer = v->w > v->h ? v->w : v->h;
+    vd.d = v->decimate < longer ? v->decimate : longer;
+    vd.ow = (v->w + vd.d - 1) / vd.d; vd.oh = (v->h + vd.d - 1) / vd.d;
+    return vd;
+}
+static dim3 view_grid(const ViewDev &vd) {
+    const int64_t groups = ((int64_t)vd.ow * vd.oh + 3 + 3) / 4, blocks = (groups + 255) / 256;      // (+ 3: the short first group)
+    return dim3((unsigned)(blocks < 2048 ? blocks : 2048));
+}
+
+// the LUT index of Util.getColorBitsGrayscale (Util.java:106-107): (int)((float)value * 255), NaN -> 0; the clamp is the library's
+template <bool LIK>
+__device__ __forceinline__ int32_t view_idx(double c) {
+    const double value = LIK ? c : (double)1.0f - ((double)1.0f - (double)1.0f / (1.0 + exp(c)));      // GridMap.java:382 / :384, Util.java:46-48
+    const float t = (float)value * 255.0f;
+    return t != t ? 0 : (t >= 255.0f ? 255 : (t <= 0.0f ? 0 : (int32_t)t));
+}
+// the LUT entry's channel: (int)(255 * ratio), ratio = i / 256f (Util.java:92-96, Color.java:62-65)
+__device__ __forceinline__ uint32_t view_grey(int32_t idx) { return (uint32_t)(int32_t)(255.0f * ((float)idx / 256.0f)); }
+// a pixel's block of cells (any d; ragged at the rectangle's far edges): the cell most likely occupied -- min idx of the log view, max
+// idx of the likelihood view
+template <bool LIK>
+__device__ __forceinline__ int32_t view_block_idx(const double *__restrict__ src, const ViewDev &vd, int32_t u, int32_t v) {
+    const int32_t cx0 = vd.x0 + u * vd.d, cy0 = vd.y0 + v * vd.d;
+    const int32_t cx1 = min(cx0 + vd.d, vd.x0 + vd.w), cy1 = min(cy0 + vd.d, vd.y0 + vd.h);
+    int32_t best = LIK ? 0 : 255;
+#define VIEW_FOLD_(c) { const int32_t i_ = view_idx<LIK>(c); best = LIK ? max(best, i_) : min(best, i_); }
+    for (int32_t y = cy0; y < cy1; y++) {
+        const double *__restrict__ row = src + (size_t)y * (size_t)vd.W;
+        int32_t x = cx0;
+        if (((uintptr_t)(row + x) & 15) != 0) { VIEW_FOLD_(row[x]); x++; }                 // (cx0 < cx1 always)
+        for (; x + 2 <= cx1; x += 2) {
+            const double2 t = *reinterpret_cast<const double2 *>(row + x);
+            VIEW_FOLD_(t.x); VIEW_FOLD_(t.y);
+        }
+        if (x < cx1) VIEW_FOLD_(row[x]);
+    }
+#undef VIEW_FOLD_
+    return (int32_t)view_grey(best);
+}
+template <bool LIK, bool PACKED>
+__device__ __forceinline__ void view_body(const double *__restrict__ src, const ViewDev &vd, void *__restrict__ out) {
+    const int64_t npix = (int64_t)vd.ow * vd.oh;
+    const uintptr_t oa = reinterpret_cast<uintptr_t>(out);
+    const int32_t head = PACKED ? (int32_t)((oa >> 2) & 3) : (int32_t)(oa & 3);      // pixels the first group is short of four
+    const int64_t groups = (npix + head + 3) >> 2;
+    for (int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p0 = 4 * gi - head;                                            // pixels p0 .. p0 + 3, those inside [0, npix)
+        const int64_t lo = p0 < 0 ? 0 : p0;
+        const bool full = p0 >= 0 && p0 + 4 <= npix;
+        const int32_t v0 = (int32_t)(lo / vd.ow), u0 = (int32_t)(lo - (int64_t)v0 * vd.ow);
+        uint32_t g[4];
+        if (vd.d == 1 && full && u0 + 4 <= vd.ow) {                                  // four cells of one row
+            const double *__restrict__ c = src + (size_t)(vd.y0 + v0) * (size_t)vd.W + (size_t)(vd.x0 + u0);
+            double a0, a1, a2, a3;
+            if ((reinterpret_cast<uintptr_t>(c) & 15) == 0) {
+                const double2 s = *reinterpret_cast<const double2 *>(c), t = *reinterpret_cast<const double2 *>(c + 2);
+                a0 = s.x; a1 = s.y; a2 = t.x; a3 = t.y;
+            } else {
+                const double2 s = *reinterpret_cast<const double2 *>(c + 1);
+                a0 = c[0]; a1 = s.x; a2 = s.y; a3 = c[3];
+            }
+            g[0] = view_grey(view_idx<LIK>(a0)); g[1] = view_grey(view_idx<LIK>(a1));
+            g[2] = view_grey(view_idx<LIK>(a2)); g[3] = view_grey(view_idx<LIK>(a3));
+        } else {
+            int32_t u = u0, v = v0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int64_t p = p0 + k;
+                g[k] = 0;
+                if (p < lo || p >= npix) continue;
+                g[k] = (uint32_t)view_block_idx<LIK>(src, vd, u, v);
+                if (++u == vd.ow) { u = 0; v++; }
+            }
+        }
+        if (PACKED) {
+            uint32_t *o = static_cast<uint32_t *>(out);
+            uint4 px;                                                                // colorToFloatBits(ratio, ratio, ratio, 1.0f) & 0xfeffffff
+            px.x = 0xFE000000u | g[0] * 0x010101u; px.y = 0xFE000000u | g[1] * 0x010101u;
+            px.z = 0xFE000000u | g[2] * 0x010101u; px.w = 0xFE000000u | g[3] * 0x010101u;
+            if (full) *reinterpret_cast<uint4 *>(o + p0) = px;
+            else {
+                const uint32_t e[4] = {px.x, px.y, px.z, px.w};
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (p0 + k >= 0 && p0 + k < npix) o[p0 + k] = e[k];
+            }
+        } else {
+            uint8_t *o = static_cast<uint8_t *>(out);
+            if (full) *reinterpret_cast<uint32_t *>(o + p0) = g[0] | g[1] << 8 | g[2] << 16 | g[3] << 24;
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (p0 + k >= 0 && p0 + k < npix) o[p0 + k] = (uint8_t)g[k];
+            }
+        }
+    }
+}
+template <bool LIK, bool PACKED>
+__global__ void __launch_bounds__(256) k_view(const double *__restrict__ src, ViewDev vd, void *__restrict__ out) { view_body<LIK, PACKED>(src, vd, out); }
+
 // diagnostics: the float-rounded primitives the parity contract leans on
 __global__ void k_debug_f32(int32_t op, const float *__restrict__ a, float *__restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1481,6 +1596,19 @@ void gms_launch_fill(gms_map *m, double *d, double v, int64_t n) {
 
 void gms_launch_get_raw(gms_map *m, int32_t mi, int32_t x, int32_t y, double *d_out2) {
     hipLaunchKernelGGL(k_get_raw, dim3(1), dim3(1), 0, m->stream, m->gd, m->d_log, mi, x, y, d_out2);
+}
+
+void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out) {
+    const ViewDev vd = view_dev(m, v);
+    const dim3 grid = view_grid(vd);
+    const bool lik = v->source == GMS_VIEW_LIKELIHOOD;
+    if (v->format == GMS_VIEW_PACKED32) {
+        if (lik) hipLaunchKernelGGL((k_view<true, true>), grid, dim3(256), 0, m->stream, src, vd, d_out);
+        else hipLaunchKernelGGL((k_view<false, true>), grid, dim3(256), 0, m->stream, src, vd, d_out);
+    } else {
+        if (lik) hipLaunchKernelGGL((k_view<true, false>), grid, dim3(256), 0, m->stream, src, vd, d_out);
+        else hipLaunchKernelGGL((k_view<false, false>), grid, dim3(256), 0, m->stream, src, vd, d_out);
+    }
 }
 
 void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out, int64_t n) {

@@ -163,6 +163,7 @@ int gms_slam_reset(gms_slam *s) {                                               
     HIPCHK(hipMemsetAsync(s->d_lik[0], 0, bytes, m->stream));
     if (s->d_code[0]) HIPCHK(hipMemsetAsync(s->d_code[0], 0, (size_t)s->n * 2 * (size_t)s->code_words * sizeof(uint32_t), m->stream));   // every class "logData == 0"
     slam_was_reset(s);
+    s->have_strongest = 0;                                                                   // (no update yet: nothing names a strongest particle)
     gms_launch_pf_init(s->pf);                                                               // Pose(0, 0, 0), weight 1 / numParticles (:68-71)
     pf_weights_set(s->pf);
     HIPCHK(hipGetLastError());
@@ -242,7 +243,9 @@ int gms_slam_update_per_particle_dev(gms_slam *s, const gms_beam *dev_beams, int
     if (rc) return rc;
     rc = slam_update_local(s, dev_beams, B, sample_motion, d_center, d_theta, seed, sequence);
     if (rc) return rc;
-    return gms_pf_normalize(s->pf, stats);                                                                 // :100, :110-124 (stats: synchronises)
+    rc = gms_pf_normalize(s->pf, stats);                                                                   // :100, :110-124 (stats: synchronises)
+    if (!rc) s->have_strongest = 1;
+    return rc;
 }
 
 // ... and for one rank's block of a sharded filter: the local half of update() -- motion sample (keyed by the GLOBAL particle index),
@@ -323,7 +326,9 @@ static int slam_update_staged_batch(gms_slam *s, const gms_beam *d_beams, int32_
     mo.d_center = 0.0; mo.d_theta = 0.0; mo.seed = 0; mo.sequence = sequence;
     int rc = slam_update_core(s, d_beams, Bmax, &mo, false, &bt);
     if (rc) return rc;
-    return gms_pf_normalize(s->pf, stats);
+    rc = gms_pf_normalize(s->pf, stats);
+    if (!rc) s->have_strongest = 1;
+    return rc;
 }
 
 // SLAM.update(z, u) of every filter of the handle (filter f: beams [f][0 .. counts[f]) of the [S][B] block, odometry [f][2], seeds[f],
@@ -659,6 +664,44 @@ int gms_slam_combined(gms_slam *s) {
     HIPCHK(hipGetLastError());
     return gms_map_build_likelihood(m);                                                       // :457
 }
+
+// A view of one particle's map (gridmapslam.h "map views"): GridMapApp.render's "strongest" and "chosen" cases (GridMapApp.java:374-393)
+// handed to GridMap.render (GridMap.java:371-388), on the device.  The strongest particle and the maps' current generation are read
+// there; the host decides only what it knows without a round trip: where the fields stand (gms_slam::field).
+static int slam_view(gms_slam *s, int32_t which, const gms_view *v, void *out, int32_t *shown, bool on_device) {
+    REQUIRE(s && v && out, "gms_slam_view: null argument (the handle, the view and the output are required)");
+    gms_map *m = s->map;
+    int64_t bytes = 0;
+    int rc = gms_view_check(v, m->gd.W, m->gd.H, "gms_slam_view", &bytes);
+    if (rc) return rc;
+    REQUIRE(!on_device || v->format != GMS_VIEW_PACKED32 || ((uintptr_t)out & 3) == 0, "gms_slam_view_dev: a packed view needs a 4-byte aligned output");
+    if (which == GMS_VIEW_STRONGEST) {
+        REQUIRE(v->filter >= 0 && v->filter < s->n_filters, "gms_slam_view: gms_view.filter out of range");
+        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_view: a shard of a filter (its strongest particle may live on another rank): name the particle");
+        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_view: no update since the handle was created or reset: there is no strongest particle yet");
+    } else REQUIRE(which >= 0 && which < s->n, "gms_slam_view: particle index out of range");
+    HIPCHK(hipSetDevice(m->device));
+    const SlamBufs sb = gms_slam_bufs(s);
+    const int32_t filter = which == GMS_VIEW_STRONGEST ? v->filter : 0;
+    SlamField field = s->field;
+    if (v->source == GMS_VIEW_LIKELIHOOD && field == SLAM_FIELD_FROM_PLANES) {       // the shown particle's field alone; the state stays as it is
+        gms_launch_slam_likelihood_shown(m, sb, s->pf->d_stats, which, filter, s->code_words);
+        field = SLAM_FIELD_IN_MEMORY;
+    }
+    unsigned char *base = nullptr;
+    if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
+    gms_launch_slam_view(m, sb, s->pf->d_stats, which, filter, field, s->d_idx_lik, v, on_device ? out : base + 16,
+                         on_device ? shown : reinterpret_cast<int32_t *>(base));
+    HIPCHK(hipGetLastError());
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(out, base + 16, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
+        if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    return GMS_OK;
+}
+int gms_slam_view(gms_slam *s, int32_t which, const gms_view *v, void *out, int32_t *shown) { return slam_view(s, which, v, out, shown, false); }
+int gms_slam_view_dev(gms_slam *s, int32_t which, const gms_view *v, void *dev_out, int32_t *dev_shown) { return slam_view(s, which, v, dev_out, dev_shown, true); }
 
 // The cell walk of SLAM.update's integrateObservation(p.m, z, p.pose) for particle i at its current pose, as k_slam_particle walks and
 // classifies it, written out instead of counted (tests): gms_map_trace_scan's layout.

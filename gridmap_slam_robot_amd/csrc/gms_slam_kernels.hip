@@ -1547,3 +1547,74 @@ void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n_filters
     const unsigned gx = n_filters > 1 ? (unsigned)std::max(2048 / n_filters, 64) : 2048u;
     hipLaunchKernelGGL(k_slam_combine, dim3(gx, (unsigned)n_filters), dim3(256), 0, dst->stream, sb, dst->gd.cells, dst->d_log);
 }
+
+// ---- a view of ONE particle's map (gms_slam_view; the grey levels and the streaming pass are view_body's, gms_map_kernels.hip) ------
+// The particle a view shows: `which` itself, or -- which < 0 -- the strongest particle of `filter` as the last update's statistics name
+// it (SLAM.java:110-115; filter-local there, handle-wide here), read on the device: the host does not know it without a round trip.
+__device__ __forceinline__ int32_t slam_view_particle(const SlamBufs &sb, const PfStatsDev *__restrict__ stats, int32_t which, int32_t filter) {
+    return which >= 0 ? which : filter * sb.n_per + stats[filter].strongest;
+}
+// field: where a likelihood view finds the particle's likelihoodData (a log view reads logData of the current generation) --
+// SLAM_FIELD_IN_MEMORY: in the current generation (as kept, or as k_slam_likelihood_shown has just written it from the class plane);
+// SLAM_FIELD_OWED_COPY: where the last resample() drew, still in the OTHER generation, at the source idx_lik names (k_slam_gather_one)
+template <bool LIK, bool PACKED>
+__global__ void __launch_bounds__(256)
+k_slam_view(SlamBufs sb, const PfStatsDev *__restrict__ stats, int32_t which, int32_t filter, int32_t field, const int32_t *__restrict__ idx_lik,
+            int64_t cells, ViewDev vd, void *__restrict__ out, int32_t *__restrict__ shown) {
+    const int32_t p = slam_view_particle(sb, stats, which, filter);
+    const int32_t *ep = sb_epoch(sb, p);
+    const int32_t cur = ep[0] & 1;
+    if (shown && blockIdx.x == 0 && threadIdx.x == 0) *shown = p;
+    const double *src;
+    if (!LIK) src = sb_log(sb, cur) + (size_t)p * (size_t)cells;
+    else if (field == SLAM_FIELD_OWED_COPY && ep[1]) src = sb_lik(sb, cur ^ 1) + (size_t)(p - p % sb.n_per + idx_lik[p]) * (size_t)cells;
+    else src = sb_lik(sb, cur) + (size_t)p * (size_t)cells;
+    view_body<LIK, PACKED>(src, vd, out);
+}
+// likelihoodData of the shown particle alone from plane 1 of its class planes, into its own slot of the current generation (mode 1 of
+// likelihood_body, as k_slam_likelihood_codes): while the fields are implicit in the planes that slot holds nothing anybody reads,
+// and what lands there is what writing every field out would put there
+template <int KH>
+__global__ void __launch_bounds__(256)
+k_slam_likelihood_shown(GridDev g, SlamBufs sb, const PfStatsDev *__restrict__ stats, int32_t which, int32_t filter, int64_t code_words,
+                        const double *__restrict__ taps_g, int32_t tiles_x, int32_t tiles_y) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int32_t p = slam_view_particle(sb, stats, which, filter);
+    const int32_t cur = sb_epoch(sb, p)[0] & 1;
+    const uint32_t *__restrict__ planes = sb_code(sb, cur) + code_words;
+    double *__restrict__ lik = sb_lik(sb, cur);
+    likelihood_body<KH, 1, true>(g, reinterpret_cast<const double *>(planes), lik, lik, 0, taps_g, nullptr, 0, tiles_x, tiles_y, blockIdx.x, (uint32_t)p,
+                                 gridDim.x, smem, nullptr, nullptr, 1, 2 * code_words);
+}
+
+void gms_launch_slam_view(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_stats, int32_t which, int32_t filter, SlamField field,
+                          const int32_t *d_idx_lik, const gms_view *v, void *d_out, int32_t *d_shown) {
+    const ViewDev vd = view_dev(m, v);
+    const dim3 grid = view_grid(vd);
+    const bool lik = v->source == GMS_VIEW_LIKELIHOOD;
+#define SV_LAUNCH(LIK, PACKED)                                                                                                    \
+    hipLaunchKernelGGL((k_slam_view<LIK, PACKED>), grid, dim3(256), 0, m->stream, sb, d_stats, which, filter, (int32_t)field, d_idx_lik, \
+                       m->gd.cells, vd, d_out, d_shown)
+    if (v->format == GMS_VIEW_PACKED32) { if (lik) SV_LAUNCH(true, true); else SV_LAUNCH(false, true); }
+    else { if (lik) SV_LAUNCH(true, false); else SV_LAUNCH(false, false); }
+#undef SV_LAUNCH
+}
+
+void gms_launch_slam_likelihood_shown(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_stats, int32_t which, int32_t filter, int64_t code_words) {
+    ProfScope ps(m, GMS_K_LIKELIHOOD);
+    const int32_t k = m->lik_kh;
+    const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
+    const size_t smem = gms_likelihood_lds_bytes(m->gd.khalf, k != 0);
+    const dim3 grid((unsigned)(tiles_x * tiles_y));                                  // one map: a workgroup per tile
+#define SLS_LAUNCH(KH)                                                                                                          \
+    do {                                                                                                                          \
+        if (smem > 48 * 1024)                                                                                                     \
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_likelihood_shown<KH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+        hipLaunchKernelGGL((k_slam_likelihood_shown<KH>), grid, dim3(256), smem, m->stream, m->gd, sb, d_stats, which, filter, code_words, m->d_taps, \
+                           tiles_x, tiles_y);                                                                                     \
+    } while (0)
+    if (k == 3) SLS_LAUNCH(3);
+    else if (k == 5) SLS_LAUNCH(5);
+    else SLS_LAUNCH(0);
+#undef SLS_LAUNCH
+}

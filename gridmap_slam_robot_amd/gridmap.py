@@ -69,6 +69,42 @@ class Observation:
         return self.getNumberOfMeasurements()
 
 
+def _view_args(W: int, H: int, rect, decimate: int, likelihood: bool, packed: bool, filter: int = 0):
+    """(gms_view, output shape, numpy dtype) of a view of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
+    v = _lib.GmsView(x0, y0, w, h, int(decimate), _lib.GMS_VIEW_LIKELIHOOD if likelihood else _lib.GMS_VIEW_LOG,
+                     _lib.GMS_VIEW_PACKED32 if packed else _lib.GMS_VIEW_GREY8, int(filter))
+    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    check(load().gms_view_size(C.byref(v), C.byref(ow), C.byref(oh), C.byref(nbytes)))
+    return v, (oh.value, ow.value), np.dtype(np.uint32 if packed else np.uint8), nbytes.value
+
+
+def _view_device_out(out, nbytes: int) -> int:
+    """the device address of a caller's torch tensor that is to receive a view of nbytes bytes"""
+    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
+        raise ValueError("view: out must be a contiguous torch tensor on the device")
+    if out.numel() * out.element_size() < nbytes:
+        raise ValueError(f"view: out holds {out.numel() * out.element_size()} bytes, the view needs {nbytes}")
+    return int(out.data_ptr())
+
+
+def world_rect_to_cells(grid_map, center, size):
+    """The cell rectangle (x0, y0, w, h) a world rectangle -- centre and size in metres -- covers on grid_map, clamped to the map.
+    A world coordinate becomes a cell as the reference's lookups do it (J/slam/GridMap.java:273-276): (int)((x - position) /
+    resolution) in float arithmetic, truncated toward zero.  ValueError where the rectangle misses the map."""
+    f = np.float32
+    res = f(grid_map.params.resolution)
+    out = []
+    for c, sz, pos, n in ((center[0], size[0], grid_map.params.pos_x, grid_map.W), (center[1], size[1], grid_map.params.pos_y, grid_map.H)):
+        half = f(sz) / f(2)
+        lo_w, hi_w = (f(c) - half - f(pos)) / res, (f(c) + half - f(pos)) / res
+        if not (hi_w >= 0 and lo_w < n):                # (also refuses NaN)
+            raise ValueError("world_rect_to_cells: the rectangle lies outside the map")
+        lo, hi = max(int(lo_w), 0), min(int(min(hi_w, f(n))), n - 1)
+        out.append((lo, hi - lo + 1))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
 def _beams_of(obs) -> np.ndarray:
     b = obs.beams if isinstance(obs, Observation) else obs
     return np.ascontiguousarray(b, dtype=BEAM_DTYPE)
@@ -179,6 +215,24 @@ class GridMap:
         out = np.empty(self._shape(), dtype=np.float64)
         check(load().gms_map_download_likelihood(self._h, ptr(out)))
         return out
+
+    def view(self, rect=None, decimate: int = 1, likelihood: bool = False, packed: bool = False, mi: int = 0, out=None):
+        """GridMap.render's grey levels (GridMap.java:371-388) of map mi, made on the device: rect = (x0, y0, w, h) in cells (None: the
+        whole map), decimate cells per pixel and axis, likelihood: likelihoodData instead of logData, packed: 0xFE000000 | g << 16 |
+        g << 8 | g words instead of bytes.  Returns a numpy uint8 / uint32 array [ceil(h / d)][ceil(w / d)] (synchronises); with out -- a
+        contiguous torch device tensor of that many bytes -- the picture is written there on the handle's stream, nothing is
+        synchronised, and out is returned."""
+        v, shape, dtype, nbytes = _view_args(self.W, self.H, rect, decimate, likelihood, packed)
+        if out is not None:
+            check(load().gms_map_view_dev(self._h, int(mi), C.byref(v), C.c_void_p(_view_device_out(out, nbytes))))
+            return out
+        img = np.empty(shape, dtype=dtype)
+        check(load().gms_map_view(self._h, int(mi), C.byref(v), ptr(img)))
+        return img
+
+    def world_rect(self, center, size):
+        """(x0, y0, w, h): the cells under a world rectangle (centre, size in metres), clamped to the map (world_rect_to_cells)"""
+        return world_rect_to_cells(self, center, size)
 
     def copy_from(self, other: "GridMap"):
         """createMapData(other) (GridMap.java:106-124)."""
@@ -823,6 +877,26 @@ class _SlamHandle:
         check(load().gms_slam_trace_scan(self._h, int(slot), ptr(b), len(b), ptr(cells), ptr(cls), cap, ptr(counts)))
         return cells, cls, counts
 
+    def _view(self, which, filter: int, rect, decimate: int, likelihood: bool, packed: bool, out, shown_out):
+        """gms_slam_view[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (image, shown)"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('view: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        v, shape, dtype, nbytes = _view_args(self.W, self.H, rect, decimate, likelihood, packed, filter)
+        if out is not None:
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("view: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_view_dev(self._h, int(which), C.byref(v), C.c_void_p(_view_device_out(out, nbytes)), sh))
+            return out, shown_out
+        img = np.empty(shape, dtype=dtype)
+        shown = C.c_int32(-1)
+        check(load().gms_slam_view(self._h, int(which), C.byref(v), ptr(img), C.byref(shown)))
+        return img, int(shown.value)
+
     def _last_beams(self, f: int) -> np.ndarray:
         out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
         c = C.c_int32(0)
@@ -928,6 +1002,14 @@ class SLAMParticleMaps(_SlamHandle):
 
     def set_map(self, i: int, log=None, lik=None):
         self._set_map(i, log, lik)
+
+    def view(self, which="strongest", rect=None, decimate: int = 1, likelihood: bool = False, packed: bool = False, out=None, shown_out=None):
+        """GridMapApp.render's "strongest" / "chosen particle" cases (J/app/GridMapApp.java:374-393) through GridMap.render
+        (GridMap.java:371-388), on the device: (image, shown) -- the grey levels of particle `which`'s map as GridMap.view makes them, and
+        the particle that was drawn.  which = "strongest": the strongest particle of the last update (:110-115), picked on the device
+        without a read-back (GmsError GMS_ERR_STATE before the first update and after reset()).  out / shown_out: torch device tensors
+        for the picture and the int32 index (nothing is synchronised).  The combined map: calculate_combined(), then grid_map.view()."""
+        return self._view(which, 0, rect, decimate, likelihood, packed, out, shown_out)
 
     def calculate_combined(self) -> np.ndarray:
         """GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458): the combined logData [H][W]; the likelihood field of it is
@@ -1090,6 +1172,16 @@ class SLAMParticleMapsBatch(_SlamHandle):
 
     def set_map(self, f: int, i: int, log=None, lik=None):
         self._set_map(self._slot(f, i), log, lik)
+
+    def view(self, which="strongest", filter: int = 0, rect=None, decimate: int = 1, likelihood: bool = False, packed: bool = False, out=None,
+             shown_out=None):
+        """SLAMParticleMaps.view for filter `filter`: which = "strongest" (that filter's, picked on the device) or a FILTER-LOCAL particle
+        index.  shown is the handle-wide slot filter * num_particles + k that was drawn (the index space of gms_slam_download_map)."""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._view(which, filter, rect, decimate, likelihood, packed, out, shown_out)
 
     def calculate_combined(self, f: int, likelihood: bool = False) -> np.ndarray:
         """GridMapApp.calculateCombined over filter f's particles: its logData [H][W] (likelihood: the field of it)"""

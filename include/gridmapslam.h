@@ -419,6 +419,65 @@ int gms_slam_last_beams(gms_slam *s, int32_t f, gms_beam *out, int32_t cap, int3
 /* maps copied by resampling steps since creation (measurement: bytes moved = copies * W * H * 32) */
 int gms_slam_copies(const gms_slam *s, int64_t *maps_copied);
 
+/* ---- map views: GridMap.render's grey levels, produced on the device ---------------------------------------------------------
+ * GridMapApp.render (J/app/GridMapApp.java:374-393) hands one GridMapData -- the strongest particle's, a chosen particle's or the
+ * combined map -- to GridMap.render (J/slam/GridMap.java:371-388), which turns every cell into a grey level.  A view is that picture
+ * as one byte (or one packed colour word) per pixel: a rectangle of the map, optionally reduced, made by one streaming launch instead
+ * of a download of W * H doubles and an exp per cell on the host.
+ *
+ * The grey level of a cell with log-odds l / likelihood L, bit for bit the Java's:
+ *   value (double)  log view:        (double)1.0f - ((double)1.0f - (double)1.0f / (1.0 + exp(l)))
+ *                                    (GridMap.java:384 `1.0f - Util.invLogOdds(logData[i])`, Util.java:46-48)
+ *                   likelihood view: L                                                                  (GridMap.java:382)
+ *   v   = (float)value
+ *   idx = (int)(v * 255), a float multiply and Java's (int): NaN -> 0, truncation toward zero (Util.java:106-107).  Java would throw
+ *         on an index outside the 256-entry LUT; THE CLAMP TO [0, 255] IS THIS LIBRARY'S, not the reference's.
+ *   g   = (int)(255 * (idx / 256.0f)) in float: the LUT's ratio is i / 256f and Color.colorToFloatBits truncates 255 * ratio
+ *         (Util.java:92-96, Color.java:62-65).  White is therefore 254, not 255.
+ *   GMS_VIEW_GREY8:    the byte g.
+ *   GMS_VIEW_PACKED32: 0xFE000000 | g << 16 | g << 8 | g -- the int bits colorToFloatBits(ratio, ratio, ratio, 1.0f) produces after its
+ *                      `& 0xfeffffff` mask.
+ *
+ * The rectangle: cells [x0, x0 + w) x [y0, y0 + h), w, h >= 1, inside [0, W] x [0, H] (GMS_ERR_INVALID otherwise, nothing touched).
+ * The output: ceil(w / decimate) x ceil(h / decimate) pixels, row-major, row 0 = y0 (logData's orientation), no row padding.  Pixel
+ * (u, v) covers cells x0 + u d .. min(x0 + u d + d, x0 + w) - 1 and likewise in y: the last column and row may be ragged.
+ * Decimation (d > 1) IS THIS LIBRARY'S OWN RULE -- the reference has none: a pixel is the cell of its block most likely to be
+ * occupied, i.e. the minimum idx of the block in the log view and the maximum idx in the likelihood view, so that a wall one cell
+ * wide does not vanish from an overview. */
+enum { GMS_VIEW_GREY8 = 0, GMS_VIEW_PACKED32 = 1 };            /* gms_view.format: 1 / 4 bytes per pixel */
+enum { GMS_VIEW_LOG = 0, GMS_VIEW_LIKELIHOOD = 1 };            /* gms_view.source: logData / likelihoodData */
+#define GMS_VIEW_STRONGEST (-1)                                /* gms_slam_view's `which`: the strongest particle of filter gms_view.filter */
+typedef struct gms_view {
+    int32_t x0, y0, w, h;       /* the cell rectangle */
+    int32_t decimate;           /* d >= 1 cells per pixel and axis */
+    int32_t source;             /* GMS_VIEW_LOG / GMS_VIEW_LIKELIHOOD */
+    int32_t format;             /* GMS_VIEW_GREY8 / GMS_VIEW_PACKED32 */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+} gms_view;
+/* The output's size in pixels and bytes (any of the three may be NULL).  Pure host code: checks w, h, decimate >= 1, x0, y0 >= 0,
+ * source and format -- not the map's bounds, which it does not know. */
+int gms_view_size(const gms_view *v, int32_t *out_w, int32_t *out_h, int64_t *bytes);
+/* Map mi of a shared or batched map, exactly as gms_map_download_log / gms_map_download_likelihood would return it at this moment (a
+ * scan whose `logData +=` pass is still deferred and a lazily kept likelihood field included; like those downloads it changes no
+ * later result of the handle).  out: `bytes` of host memory; the call synchronises.  _dev: out is device memory (4-byte aligned
+ * for GMS_VIEW_PACKED32), written on the handle's stream; nothing is synchronised. */
+int gms_map_view(gms_map *m, int32_t mi, const gms_view *v, void *out);
+int gms_map_view_dev(gms_map *m, int32_t mi, const gms_view *v, void *dev_out);
+/* One particle's map of the per-particle filter (GridMapApp.render's mapDrawSelect cases "strongest" and "chosen"; the combined map
+ * is the handle's own gms_map: gms_slam_combined, then gms_map_view on the map of gms_slam_handles).  which >= 0: the particle, in
+ * the index space of gms_slam_download_map (a batched handle: f * n + k).  which == GMS_VIEW_STRONGEST: the strongest particle of
+ * filter v->filter, picked ON THE DEVICE from the statistics the last update left there (SLAM.java:110-115; they outlive a
+ * resample(), as strongestParticle does) -- the host reads nothing back in front of the launch; GMS_ERR_STATE before the first
+ * update, after gms_slam_reset until the next one, and on a shard of a filter (its strongest particle may live on another rank).
+ * *shown (may be NULL) receives the index that was drawn, in `which`'s own index space (a batched handle: f * n + k, NOT the
+ * filter-local gms_pf_stats.strongest); the host form reads it back in the image's synchronise, the _dev form takes a device int32_t *.
+ * The generation of the maps is picked on the device from the epoch counters, as by every kernel of the handle.  The likelihood view
+ * is the particle's likelihoodData as gms_slam_download_map would return it, wherever the handle keeps it: read in place, read from
+ * the source of a resampling copy that is still owed, or -- where the fields are implicit in the class planes -- computed for the
+ * SHOWN particle alone; no other particle's field is written, and the handle's state and later results do not change. */
+int gms_slam_view(gms_slam *s, int32_t which, const gms_view *v, void *out, int32_t *shown);
+int gms_slam_view_dev(gms_slam *s, int32_t which, const gms_view *v, void *dev_out, int32_t *dev_shown);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -139,6 +139,19 @@ public:
     std::vector<double> logData() { std::vector<double> v((size_t)w_ * hgt_); check(gms_map_download_log(h_, v.data())); return v; }
     std::vector<double> likelihoodData() { std::vector<double> v((size_t)w_ * hgt_); check(gms_map_download_likelihood(h_, v.data())); return v; }
     void setLogData(const std::vector<double> &v) { check(gms_map_upload_log(h_, v.data())); }
+    /** GridMap.render's grey levels (:371-388) of map mi, made on the device: one byte per pixel (GMS_VIEW_GREY8) or one packed colour
+     *  word (GMS_VIEW_PACKED32) of the view's rectangle, ceil(w / d) x ceil(h / d) pixels row-major (gridmapslam.h "map views") */
+    std::vector<uint8_t> render(const gms_view &v, int mi = 0) {
+        int64_t bytes = 0;
+        check(gms_view_size(&v, nullptr, nullptr, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(gms_map_view(h_, mi, &v, out.data()));
+        return out;
+    }
+    /** the whole map at one cell per pixel */
+    gms_view fullView(bool likelihood = false, bool packed = false, int decimate = 1) const {
+        return gms_view{0, 0, w_, hgt_, decimate, likelihood ? GMS_VIEW_LIKELIHOOD : GMS_VIEW_LOG, packed ? GMS_VIEW_PACKED32 : GMS_VIEW_GREY8, 0};
+    }
 
     float getResolution() const { return params_.resolution; }                               // :426-428
     std::pair<float, float> getPosition() const { return {params_.pos_x, params_.pos_y}; }   // :430-432
@@ -377,6 +390,19 @@ public:
     std::vector<double> mapOf(int i, bool likelihood = false) {
         std::vector<double> out((size_t)w_ * hgt_);
         check(gms_slam_download_map(h_, i, likelihood ? nullptr : out.data(), likelihood ? out.data() : nullptr));
+        return out;
+    }
+    /** GridMapApp.render's "strongest" / "chosen particle" cases (J/app/GridMapApp.java:374-393) through GridMap.render (GridMap.java:371-388):
+     *  the grey levels of particle `which`'s map, or -- which == GMS_VIEW_STRONGEST -- of the strongest particle's, picked on the device;
+     *  *shown (may be null) receives the particle that was drawn.  The combined map: calculateCombined(), then gms_map_view on the map of
+     *  gms_slam_handles. */
+    std::vector<uint8_t> render(const gms_view &v, int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        int64_t bytes = 0;
+        check(gms_view_size(&v, nullptr, nullptr, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        int32_t drawn = 0;
+        check(gms_slam_view(h_, which, &v, out.data(), &drawn));
+        if (shown) *shown = drawn;
         return out;
     }
     /** GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458): the combined logData */
