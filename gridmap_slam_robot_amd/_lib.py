@@ -246,6 +246,13 @@ def load() -> C.CDLL:
     sig("gms_map_view_dev", C.c_int, vp, i32, vw, vp)
     sig("gms_slam_view", C.c_int, vp, i32, vw, vp, vp)
     sig("gms_slam_view_dev", C.c_int, vp, i32, vw, vp, vp)
+    sig("gms_slam_history_bytes", C.c_int, i32, i32, C.POINTER(C.c_int64))
+    sig("gms_slam_set_history", C.c_int, vp, i32)
+    sig("gms_slam_history_len", C.c_int, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32))
+    sig("gms_slam_trajectory", C.c_int, vp, i32, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+    sig("gms_slam_trajectory_dev", C.c_int, vp, i32, i32, vp, i32, vp)
+    sig("gms_slam_trajectories", C.c_int, vp, i32, vp, vp, i32, C.POINTER(C.c_int32))
+    sig("gms_slam_history_walk_rows", C.c_int, vp, C.POINTER(C.c_int32))
     _lib = L
     return L
 

@@ -370,8 +370,26 @@ struct gms_slam {
     int32_t refine;                 // gms_slam_set_refine: update() runs findBestPose on every particle against its own field before weighting it (SLAM.java:96)
     int32_t refine_field;           // the field in front of the refinement: -1 from the class plane where logData exceeds the infinity cache, 0 from logData
                                     // always, 1 from the plane always (GMS_SLAM_REFINE_FIELD=log|codes: tests of both forms)
+    // the particles' paths (gms_slam_set_history; off while hist_cap == 0: nothing allocated, nothing launched)
+    int32_t hist_cap;               // rows of the ring
+    int32_t *d_hist_parent;         // [hist_cap][n]     (SlamHist)
+    float *d_hist_pose;             // [hist_cap][n][3]
+    int32_t *d_hist_lin[2];         // [n] the composed source of every slot over the draws since the last recorded update, and the buffer the next
+                                    // draw composes into (a filter's slots may span workgroups: in place would race)
+    int32_t hist_lin_cur;           // which of the two holds it: every draw's compose writes the other one, drawn or not, so the host knows
+    int64_t *d_hist_steps;          // {updates recorded, ticket}: the count the kernels go by
+    int64_t hist_steps;             // ... and the host's mirror of it: every update through slam_update_core records exactly one row
+    int32_t hist_walk_mem;          // the back-trace chases through memory even where a row fits the LDS (GMS_SLAM_HISTORY_WALK=mem: tests)
     int32_t refine_lds;             // -1 the field in LDS whenever it fits (computed there from the class plane where it can be), 0 never, 2 staged from
                                     // memory wherever it fits (GMS_SLAM_REFINE_LDS: tests of the other forms)
+};
+
+// the history of a gms_slam as its kernels see it (gms_slam_set_history): a ring of cap rows, update number t in row t % cap
+struct SlamHist {
+    int32_t *parent;                // [cap][n] the filter-local slot of the row before that every slot's particle descends from
+    float *pose;                    // [cap][n][3] every slot's pose when that update returned
+    int64_t *steps;                 // {updates recorded since the history was cleared, the append kernel's ticket}
+    int32_t cap, n, n_per;
 };
 
 // ---- field state transitions of a gms_slam (gms_slam::field): each is named for what happened; together they are its only writers.
@@ -526,6 +544,17 @@ void gms_launch_slam_view(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_st
 void gms_launch_slam_likelihood_shown(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_stats, int32_t which, int32_t filter, int64_t code_words);
 void gms_launch_slam_export_records(gms_pf *pf, const SlamBufs &sb, const int32_t *d_list, int32_t count, int64_t code_words, double *d_dst);
 void gms_launch_slam_shard_gather(gms_pf *pf, const SlamBufs &sb, const int32_t *d_src_local, const int32_t *d_recv_pos, const double *d_recv, int64_t code_words);
+
+// the particles' paths (gms_slam_set_history): lin := identity and the count 0; a row appended from lin and the poses; a draw composed
+// into lin_out (epoch: whether each filter drew); the back-trace -- bundle: every chain of `filter`, d_out [kept][n_per][3], d_anc
+// [kept][n_per] or NULL; else the chain of `which` (< 0: the strongest of `filter` by d_stats), d_out [kept][3], d_shown or NULL --
+// with `rows` parent rows per LDS buffer (gms_slam_hist_walk_rows; 0: through memory)
+void gms_launch_slam_hist_init(gms_map *m, const SlamHist &h, int32_t *d_lin);
+void gms_launch_slam_hist_append(gms_map *m, const SlamHist &h, const float *d_pose, int32_t *d_lin);
+void gms_launch_slam_hist_compose(gms_map *m, const SlamHist &h, const int32_t *d_lin, int32_t *d_lin_out, const int32_t *d_idx, const int32_t *d_epoch);
+int32_t gms_slam_hist_walk_rows(int32_t n_per, int32_t force_mem);
+void gms_launch_slam_hist_walk(gms_map *m, const SlamHist &h, const int32_t *d_lin, const PfStatsDev *d_stats, int32_t which, int32_t filter, bool bundle,
+                               int32_t kept, int32_t rows, float *d_out, int32_t *d_anc, int32_t *d_shown);
 
 // profiling brackets
 void gms_prof_begin(gms_map *m, int32_t k);

@@ -49,6 +49,33 @@ static int slam_enter(const gms_slam *s, const char *what, int allow) {
     return GMS_OK;
 }
 
+// ---- the particles' paths (gridmapslam.h "trajectories") ----
+static SlamHist slam_hist(const gms_slam *s) {
+    SlamHist h;
+    h.parent = s->d_hist_parent; h.pose = s->d_hist_pose; h.steps = s->d_hist_steps;
+    h.cap = s->hist_cap; h.n = s->n; h.n_per = s->n_per;
+    return h;
+}
+static void slam_hist_free(gms_slam *s) {
+    hipFree(s->d_hist_parent); hipFree(s->d_hist_pose); hipFree(s->d_hist_lin[0]); hipFree(s->d_hist_lin[1]); hipFree(s->d_hist_steps);
+    s->d_hist_parent = nullptr; s->d_hist_pose = nullptr; s->d_hist_lin[0] = s->d_hist_lin[1] = nullptr; s->d_hist_steps = nullptr;
+    s->hist_cap = 0; s->hist_steps = 0; s->hist_lin_cur = 0;
+}
+// no row kept, every slot its own source (the capacity stays)
+static void slam_hist_clear(gms_slam *s) {
+    s->hist_steps = 0; s->hist_lin_cur = 0;
+    gms_launch_slam_hist_init(s->map, slam_hist(s), s->d_hist_lin[0]);
+}
+// what a history of `capacity` rows over n particles allocates: the two planes of the ring, the two lineage arrays, the count and its ticket
+static int slam_hist_bytes(int64_t n, int64_t capacity, int64_t *bytes) {
+    int64_t rows = 0, ring = 0, all = 0;
+    if (__builtin_mul_overflow(n, capacity, &rows) || __builtin_mul_overflow(rows, (int64_t)16, &ring) ||
+        __builtin_add_overflow(ring, n * 8 + 16, &all))
+        return gms_fail(GMS_ERR_INVALID, "gms_slam_set_history: %lld rows of %lld particles overflow the allocation's size", (long long)capacity, (long long)n);
+    *bytes = all;
+    return GMS_OK;
+}
+
 extern "C" {
 
 int gms_slam_destroy(gms_slam *s) {
@@ -60,6 +87,7 @@ int gms_slam_destroy(gms_slam *s) {
     hipFree(s->d_epoch);
     hipFree(s->d_plan);
     hipFree(s->d_batch);
+    slam_hist_free(s);
     gms_ring_free(s->batch_ring);
     if (s->pf) gms_pf_destroy(s->pf);
     if (s->map) gms_map_destroy(s->map);
@@ -113,6 +141,8 @@ static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset,
     s->refine_lds = rl_env && rl_env[0] == '0' ? 0 : (rl_env && rl_env[0] == '2' ? 2 : -1);
     const char *rf_env = getenv("GMS_SLAM_REFINE_FIELD");
     s->refine_field = rf_env && rf_env[0] == 'c' ? 1 : (rf_env && rf_env[0] == 'l' ? 0 : -1);
+    const char *hw_env = getenv("GMS_SLAM_HISTORY_WALK");
+    s->hist_walk_mem = hw_env && hw_env[0] == 'm';
     bool ok = true;
     for (int k = 0; k < 2; k++)
         ok = ok && hipMalloc(&s->d_log[k], bytes) == hipSuccess && hipMalloc(&s->d_lik[k], bytes) == hipSuccess;
@@ -164,6 +194,7 @@ int gms_slam_reset(gms_slam *s) {                                               
     if (s->d_code[0]) HIPCHK(hipMemsetAsync(s->d_code[0], 0, (size_t)s->n * 2 * (size_t)s->code_words * sizeof(uint32_t), m->stream));   // every class "logData == 0"
     slam_was_reset(s);
     s->have_strongest = 0;                                                                   // (no update yet: nothing names a strongest particle)
+    if (s->hist_cap) slam_hist_clear(s);                                                     // (the history starts over, at the same capacity)
     gms_launch_pf_init(s->pf);                                                               // Pose(0, 0, 0), weight 1 / numParticles (:68-71)
     pf_weights_set(s->pf);
     HIPCHK(hipGetLastError());
@@ -220,6 +251,10 @@ static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, c
         drawn = true;
     }
     gms_launch_slam_particle(pf, dev_beams, B, sb, !on_demand, drawn ? nullptr : motion, skip_update ? 0 : 1, s->code_words, batch);   // :90, :99, :102-107
+    if (s->hist_cap) {                                                                                      // the poses stand (the normalisation moves none): one row
+        gms_launch_slam_hist_append(m, slam_hist(s), pf->d_pose, s->d_hist_lin[s->hist_lin_cur]);
+        s->hist_steps++;
+    }
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
@@ -415,6 +450,10 @@ static int slam_resample(gms_slam *s, const double *r01, double fraction, int32_
     if (rc) return rc;
     rc = slam_draw(s, r01, fraction, indices, n_ambiguous);
     if (rc) return rc;
+    if (s->hist_cap) {                                                                                      // the lineage follows the draw, where there was one
+        gms_launch_slam_hist_compose(m, slam_hist(s), s->d_hist_lin[s->hist_lin_cur], s->d_hist_lin[s->hist_lin_cur ^ 1], s->pf->d_idx, s->d_epoch);
+        s->hist_lin_cur ^= 1;
+    }
     const SlamBufs sb = gms_slam_bufs(s);
     slam_resampled(s, s->lazy_lik != 0);
     switch (s->field) {                                                                                     // (what each state copies, and why: slam_resampled)
@@ -731,6 +770,101 @@ int gms_slam_trace_scan(gms_slam *s, int32_t i, const gms_beam *beams, int32_t B
     hipFree(d_cells); hipFree(d_cls); hipFree(d_counts);
     if (!ok) return gms_fail(GMS_ERR_HIP, "gms_slam_trace_scan: device allocation, launch or copy failed");
     return GMS_OK;
+}
+
+// ---- trajectories (gridmapslam.h): the ring is written by slam_update_core and slam_resample; these calls only read it ----
+int gms_slam_history_bytes(int32_t n_particles_total, int32_t capacity, int64_t *bytes) {
+    REQUIRE(bytes, "gms_slam_history_bytes: null argument");
+    REQUIRE(n_particles_total >= 1 && capacity >= 0, "gms_slam_history_bytes: the particle count must be positive and the capacity non-negative");
+    if (capacity == 0) { *bytes = 0; return GMS_OK; }
+    return slam_hist_bytes(n_particles_total, capacity, bytes);
+}
+
+int gms_slam_set_history(gms_slam *s, int32_t capacity) {
+    REQUIRE(s, "gms_slam_set_history: null handle");
+    if (pf_is_shard(s->pf))
+        return gms_fail(GMS_ERR_STATE, "gms_slam_set_history: a shard of a filter (a particle's ancestors cross ranks)");
+    REQUIRE(capacity >= 0, "gms_slam_set_history: negative capacity");
+    int64_t bytes = 0;
+    if (capacity > 0) { int rc = slam_hist_bytes(s->n, capacity, &bytes); if (rc) return rc; }
+    gms_map *m = s->map;
+    HIPCHK(hipSetDevice(m->device));
+    if (s->hist_cap) HIPCHK(hipStreamSynchronize(m->stream));                                // (launches in flight still write the old ring)
+    slam_hist_free(s);
+    if (capacity == 0) return GMS_OK;
+    const size_t slots = (size_t)capacity * (size_t)s->n;
+    const bool ok = hipMalloc(&s->d_hist_parent, slots * sizeof(int32_t)) == hipSuccess && hipMalloc(&s->d_hist_pose, slots * 3 * sizeof(float)) == hipSuccess &&
+                    hipMalloc(&s->d_hist_lin[0], (size_t)s->n * sizeof(int32_t)) == hipSuccess &&
+                    hipMalloc(&s->d_hist_lin[1], (size_t)s->n * sizeof(int32_t)) == hipSuccess && hipMalloc(&s->d_hist_steps, 2 * sizeof(int64_t)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        slam_hist_free(s);
+        return gms_fail(GMS_ERR_NOMEM, "gms_slam_set_history: device allocation of %lld bytes failed", (long long)bytes);
+    }
+    s->hist_cap = capacity;
+    slam_hist_clear(s);
+    HIPCHK(hipGetLastError());
+    return GMS_OK;
+}
+
+int gms_slam_history_len(gms_slam *s, int64_t *steps_total, int32_t *steps_kept) {
+    REQUIRE(s, "gms_slam_history_len: null handle");
+    if (!s->hist_cap) return gms_fail(GMS_ERR_STATE, "gms_slam_history_len: the history is off (gms_slam_set_history)");
+    if (steps_total) *steps_total = s->hist_steps;
+    if (steps_kept) *steps_kept = (int32_t)std::min<int64_t>(s->hist_steps, s->hist_cap);
+    return GMS_OK;
+}
+
+int gms_slam_history_walk_rows(gms_slam *s, int32_t *rows) {
+    REQUIRE(s && rows, "gms_slam_history_walk_rows: null argument");
+    *rows = gms_slam_hist_walk_rows(s->n_per, s->hist_walk_mem);
+    return GMS_OK;
+}
+
+// one chain (bundle false: `which`, or the strongest of `filter`) or all of `filter`'s, into host or device memory
+static int slam_trajectory(gms_slam *s, const char *what, bool bundle, int32_t which, int32_t filter, float *xytheta, int32_t *ancestors, int32_t cap,
+                           int32_t *count, int32_t *shown, bool on_device) {
+    if (!s) return gms_fail(GMS_ERR_INVALID, "%s: null handle", what);
+    if (!s->hist_cap) return gms_fail(GMS_ERR_STATE, "%s: the history is off (gms_slam_set_history)", what);
+    if (bundle || which == GMS_VIEW_STRONGEST) {
+        if (filter < 0 || filter >= s->n_filters) return gms_fail(GMS_ERR_INVALID, "%s: filter out of range", what);
+    } else if (which < 0 || which >= s->n) return gms_fail(GMS_ERR_INVALID, "%s: particle index out of range", what);
+    if (!bundle && which == GMS_VIEW_STRONGEST && !s->have_strongest)
+        return gms_fail(GMS_ERR_STATE, "%s: no update since the handle was created or reset: there is no strongest particle yet", what);
+    const int32_t kept = (int32_t)std::min<int64_t>(s->hist_steps, s->hist_cap);
+    if (count) *count = kept;
+    if (cap < kept) return gms_fail(GMS_ERR_INVALID, "%s: room for %d steps, %d are kept", what, cap, kept);
+    if (kept == 0) return GMS_OK;
+    if (!xytheta) return gms_fail(GMS_ERR_INVALID, "%s: null output", what);
+    gms_map *m = s->map;
+    HIPCHK(hipSetDevice(m->device));
+    const int32_t nch = bundle ? s->n_per : 1;
+    const size_t pose_bytes = (size_t)kept * nch * 3 * sizeof(float), anc_bytes = ancestors ? (size_t)kept * nch * sizeof(int32_t) : 0;
+    unsigned char *base = nullptr;
+    if (!on_device) { int rc = gms_view_staging(m, (int64_t)(pose_bytes + anc_bytes), &base); if (rc) return rc; }
+    float *d_out = on_device ? xytheta : reinterpret_cast<float *>(base + 16);
+    int32_t *d_anc = !ancestors ? nullptr : on_device ? ancestors : reinterpret_cast<int32_t *>(base + 16 + pose_bytes);
+    int32_t *d_shown = bundle ? nullptr : on_device ? shown : reinterpret_cast<int32_t *>(base);
+    gms_launch_slam_hist_walk(m, slam_hist(s), s->d_hist_lin[s->hist_lin_cur], s->pf->d_stats, which, filter, bundle, kept,
+                              gms_slam_hist_walk_rows(s->n_per, s->hist_walk_mem), d_out, d_anc, d_shown);
+    HIPCHK(hipGetLastError());
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(xytheta, d_out, pose_bytes, hipMemcpyDeviceToHost, m->stream));
+        if (ancestors) HIPCHK(hipMemcpyAsync(ancestors, d_anc, anc_bytes, hipMemcpyDeviceToHost, m->stream));
+        if (shown && !bundle) HIPCHK(hipMemcpyAsync(shown, d_shown, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    return GMS_OK;
+}
+
+int gms_slam_trajectory(gms_slam *s, int32_t which, int32_t filter, float *xytheta, int32_t cap, int32_t *count, int32_t *shown) {
+    return slam_trajectory(s, "gms_slam_trajectory", false, which, filter, xytheta, nullptr, cap, count, shown, false);
+}
+int gms_slam_trajectory_dev(gms_slam *s, int32_t which, int32_t filter, float *dev_xytheta, int32_t cap, int32_t *dev_shown) {
+    return slam_trajectory(s, "gms_slam_trajectory_dev", false, which, filter, dev_xytheta, nullptr, cap, nullptr, dev_shown, true);
+}
+int gms_slam_trajectories(gms_slam *s, int32_t filter, float *xytheta, int32_t *ancestors, int32_t cap, int32_t *count) {
+    return slam_trajectory(s, "gms_slam_trajectories", true, 0, filter, xytheta, ancestors, cap, count, nullptr, false);
 }
 
 int gms_slam_copies(const gms_slam *s, int64_t *maps_copied) {

@@ -1618,3 +1618,161 @@ void gms_launch_slam_likelihood_shown(gms_map *m, const SlamBufs &sb, const PfSt
     else SLS_LAUNCH(0);
 #undef SLS_LAUNCH
 }
+
+// ---- the particles' paths (gms_slam_set_history; gridmapslam.h "trajectories") -------------------------------------------------
+// A ring of `cap` rows, row t % cap for update number t: parent[row][slot] = the filter-local slot of the row before that the particle
+// descends from, pose[row][slot][3] its pose when that update returned -- two planes, so that the back-trace stages 4 bytes per slot.
+// lin[slot] composes the draws since the last recorded update (identity after an append).  steps[0] counts the updates recorded, on the
+// device (steps[1]: the append's ticket); the host keeps a mirror it computes on its own.
+__global__ void __launch_bounds__(256)
+k_slam_hist_init(SlamHist h, int32_t *__restrict__ lin) {
+    const int32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < h.n) lin[i] = i % h.n_per;
+    if (i == 0) { h.steps[0] = 0; h.steps[1] = 0; }
+}
+// update number t = steps[0] returned: parent[t] = lin, pose[t] = the current poses, lin = identity, steps[0] = t + 1.  Every workgroup
+// reads t before it takes its ticket and the last ticket writes t + 1, so no workgroup can see the new count.
+__global__ void __launch_bounds__(256)
+k_slam_hist_append(SlamHist h, const float *__restrict__ pose, int32_t *__restrict__ lin) {
+    const int64_t t = h.steps[0];
+    const size_t row = (size_t)(t % h.cap);
+    const int32_t e = blockIdx.x * 256 + threadIdx.x;                      // (the grid covers the 3 n floats of the poses)
+    if (e < 3 * h.n) h.pose[row * 3 * (size_t)h.n + e] = pose[e];
+    if (e < h.n) {
+        h.parent[row * (size_t)h.n + e] = lin[e];
+        lin[e] = e % h.n_per;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const unsigned long long done = atomicAdd(reinterpret_cast<unsigned long long *>(h.steps + 1), 1ull);
+        if (done == (unsigned long long)gridDim.x - 1) { h.steps[1] = 0; h.steps[0] = t + 1; }
+    }
+}
+// a draw ran (or, the rule said no, did not: epoch[2 f + 1], written by the resampling kernels): lin'[m] = lin[idx[m]] where filter f drew,
+// lin[m] where it did not -- idx is stale there.  Out of place: a filter's slots may span workgroups.
+__global__ void __launch_bounds__(256)
+k_slam_hist_compose(const int32_t *__restrict__ lin, int32_t *__restrict__ lin_out, const int32_t *__restrict__ idx, const int32_t *__restrict__ epoch,
+                    int32_t n, int32_t n_per) {
+    const int32_t m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= n) return;
+    const int32_t f = m / n_per;
+    int32_t src = m;
+    if (epoch[2 * f + 1]) src = f * n_per + min(max(idx[m], 0), n_per - 1);
+    lin_out[m] = lin[src];
+}
+
+// The back-trace.  A lineage is a chain of `kept` dependent look-ups; followed through memory each costs a round trip.  LDS form: the
+// workgroup stages the parent rows of its filter in LDS, newest first, `rows` at a time (HW_WORDS words a buffer, two buffers: the next
+// chunk's loads are issued before the current chunk is walked and land in the other buffer behind it), and every chain is followed
+// inside LDS by one lane; only the poses are gathered from memory, by the slot each row resolved to.  Chains beyond the workgroup's
+// lanes take turns, their places kept in LDS between chunks.  rows == 0: the memory form, every look-up a load (a row that does not fit
+// a buffer; GMS_SLAM_HISTORY_WALK=mem).
+// bundle: all n_per chains of `filter`, out [kept][n_per][3], anc [kept][n_per] (may be NULL); else the chain of `which` (< 0: the
+// strongest of `filter`, slam_view_particle), out [kept][3].  A chain starts at lin[slot] in the newest row.  Oldest first.
+#define HW_NT 1024
+#define HW_WORDS 8192
+#define HW_PF (HW_WORDS / HW_NT)
+template <bool LDS>
+__global__ void __launch_bounds__(HW_NT)
+k_slam_hist_walk(SlamHist h, const int32_t *__restrict__ lin, const PfStatsDev *__restrict__ stats, int32_t which, int32_t filter, int32_t bundle,
+                 int32_t kept_host, int32_t rows, float *__restrict__ out, int32_t *__restrict__ anc, int32_t *__restrict__ shown) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int64_t total = h.steps[0];
+    const int32_t kept = (int32_t)min((int64_t)min(h.cap, kept_host), total);      // (the host sized the outputs by its mirror)
+    const int32_t n_per = h.n_per;
+    int32_t p = 0;
+    if (!bundle) {
+        p = which >= 0 ? which : filter * n_per + stats[filter].strongest;      // (slam_view_particle's choice)
+        if (shown && threadIdx.x == 0) *shown = p;
+        filter = p / n_per;
+    }
+    if (kept <= 0) return;
+    const int32_t nch = bundle ? n_per : 1;
+    const size_t fbase = (size_t)filter * n_per;
+    const int32_t *__restrict__ lin_f = lin + (bundle ? fbase : (size_t)p);
+    const int32_t r0 = (int32_t)((total - 1) % h.cap);                      // the newest row's place in the ring; d rows back: r0 - d (+ cap)
+    const size_t n = (size_t)h.n;
+    if (!LDS) {
+        for (int32_t k = threadIdx.x; k < nch; k += HW_NT) {
+            int32_t slot = lin_f[k];
+            for (int32_t d = 0; d < kept; d++) {
+                const int32_t pr = r0 - d < 0 ? r0 - d + h.cap : r0 - d;
+                const size_t at = (size_t)pr * n + fbase + slot, o = (size_t)(kept - 1 - d) * nch + k;
+                const float x = h.pose[3 * at], y = h.pose[3 * at + 1], th = h.pose[3 * at + 2];
+                if (anc) anc[o] = slot;
+                slot = h.parent[at];
+                out[3 * o] = x; out[3 * o + 1] = y; out[3 * o + 2] = th;
+            }
+        }
+        return;
+    }
+    int32_t *lds = reinterpret_cast<int32_t *>(smem);                       // two chunk buffers of HW_WORDS, then the chains' places [nch]
+    int32_t *state = lds + 2 * HW_WORDS;
+    for (int32_t k = threadIdx.x; k < nch; k += HW_NT) state[k] = lin_f[k];
+    const int32_t nchunks = (kept + rows - 1) / rows;
+    int32_t v[HW_PF];
+    // chunk c = rows [c rows, c rows + rc) back from the newest: element e = i n_per + col <- parent[row i of the chunk][fbase + col]
+    auto load_chunk = [&](int32_t c) {
+        const int32_t rc = min(rows, kept - c * rows), words = rc * n_per;
+#pragma unroll
+        for (int u = 0; u < HW_PF; u++) {
+            const int32_t e = min((int32_t)threadIdx.x + u * HW_NT, words - 1);                      // (clamped: no load behind a branch)
+            const int32_t i = e / n_per, col = e - i * n_per, d = c * rows + i;
+            const int32_t pr = r0 - d < 0 ? r0 - d + h.cap : r0 - d;
+            v[u] = h.parent[(size_t)pr * n + fbase + col];
+        }
+    };
+    auto store_chunk = [&](int32_t c, int32_t *dst) {
+        const int32_t words = min(rows, kept - c * rows) * n_per;
+#pragma unroll
+        for (int u = 0; u < HW_PF; u++) { const int32_t e = (int32_t)threadIdx.x + u * HW_NT; if (e < words) dst[e] = v[u]; }
+    };
+    load_chunk(0);
+    store_chunk(0, lds);
+    __syncthreads();
+    for (int32_t c = 0; c < nchunks; c++) {
+        const int32_t rc = min(rows, kept - c * rows);
+        if (c + 1 < nchunks) load_chunk(c + 1);                             // in flight while this chunk is walked
+        const int32_t *cur = lds + (c & 1) * HW_WORDS;
+        for (int32_t k = threadIdx.x; k < nch; k += HW_NT) {
+            int32_t slot = state[k];
+            for (int32_t i = 0; i < rc; i++) {
+                const int32_t d = c * rows + i;
+                const int32_t pr = r0 - d < 0 ? r0 - d + h.cap : r0 - d;
+                const size_t at = (size_t)pr * n + fbase + slot, o = (size_t)(kept - 1 - d) * nch + k;
+                const float x = h.pose[3 * at], y = h.pose[3 * at + 1], th = h.pose[3 * at + 2];
+                if (anc) anc[o] = slot;
+                slot = cur[i * n_per + slot];
+                out[3 * o] = x; out[3 * o + 1] = y; out[3 * o + 2] = th;
+            }
+            state[k] = slot;
+        }
+        if (c + 1 < nchunks) store_chunk(c + 1, lds + ((c + 1) & 1) * HW_WORDS);          // (last read before the barrier that closed chunk c - 1)
+        __syncthreads();
+    }
+}
+
+void gms_launch_slam_hist_init(gms_map *m, const SlamHist &h, int32_t *d_lin) {
+    hipLaunchKernelGGL(k_slam_hist_init, dim3((unsigned)((h.n + 255) / 256)), dim3(256), 0, m->stream, h, d_lin);
+}
+void gms_launch_slam_hist_append(gms_map *m, const SlamHist &h, const float *d_pose, int32_t *d_lin) {
+    hipLaunchKernelGGL(k_slam_hist_append, dim3((unsigned)((3 * h.n + 255) / 256)), dim3(256), 0, m->stream, h, d_pose, d_lin);
+}
+void gms_launch_slam_hist_compose(gms_map *m, const SlamHist &h, const int32_t *d_lin, int32_t *d_lin_out, const int32_t *d_idx, const int32_t *d_epoch) {
+    hipLaunchKernelGGL(k_slam_hist_compose, dim3((unsigned)((h.n + 255) / 256)), dim3(256), 0, m->stream, d_lin, d_lin_out, d_idx, d_epoch, h.n, h.n_per);
+}
+// rows of a filter's parents per LDS buffer of the walk; 0: the memory form (not one row fits, or it was asked for)
+int32_t gms_slam_hist_walk_rows(int32_t n_per, int32_t force_mem) { return force_mem ? 0 : HW_WORDS / n_per; }
+void gms_launch_slam_hist_walk(gms_map *m, const SlamHist &h, const int32_t *d_lin, const PfStatsDev *d_stats, int32_t which, int32_t filter, bool bundle,
+                               int32_t kept, int32_t rows, float *d_out, int32_t *d_anc, int32_t *d_shown) {
+    if (rows > 0) {
+        const size_t smem = (size_t)2 * HW_WORDS * 4 + (size_t)(bundle ? h.n_per : 1) * 4;
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_hist_walk<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipLaunchKernelGGL(k_slam_hist_walk<true>, dim3(1), dim3(HW_NT), smem, m->stream, h, d_lin, d_stats, which, filter, bundle ? 1 : 0, kept, rows, d_out,
+                           d_anc, d_shown);
+    } else {
+        hipLaunchKernelGGL(k_slam_hist_walk<false>, dim3(1), dim3(HW_NT), 0, m->stream, h, d_lin, d_stats, which, filter, bundle ? 1 : 0, kept, 0, d_out, d_anc,
+                           d_shown);
+    }
+}

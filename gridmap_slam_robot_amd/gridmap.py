@@ -897,6 +897,53 @@ class _SlamHandle:
         check(load().gms_slam_view(self._h, int(which), C.byref(v), ptr(img), C.byref(shown)))
         return img, int(shown.value)
 
+    def set_history(self, capacity: int):
+        """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
+        resampling (0: off, the memory freed).  reset() clears the history and keeps it on.  Refused on a shard of a filter."""
+        check(load().gms_slam_set_history(self._h, int(capacity)))
+
+    def history_len(self):
+        """(steps_total, steps_kept): updates recorded since the history was turned on or cleared, and min(total, capacity)"""
+        total, kept = C.c_int64(0), C.c_int32(0)
+        check(load().gms_slam_history_len(self._h, C.byref(total), C.byref(kept)))
+        return int(total.value), int(kept.value)
+
+    def history_walk_rows(self) -> int:
+        """diagnostics: the parent rows per LDS chunk of the back-trace; 0 = it chases through memory"""
+        rows = C.c_int32(-1)
+        check(load().gms_slam_history_walk_rows(self._h, C.byref(rows)))
+        return int(rows.value)
+
+    def _trajectory(self, which, filter: int, out, shown_out):
+        """gms_slam_trajectory[_dev]: which = a handle-wide slot or "strongest" (of `filter`); (xytheta [kept][3] oldest first, shown)"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('trajectory: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        kept = self.history_len()[1]
+        if out is not None:
+            if not (getattr(out, "is_cuda", False) and out.is_contiguous() and out.element_size() == 4 and out.numel() >= 3 * kept):
+                raise ValueError(f"trajectory: out must be a contiguous float32 torch tensor on the device of at least {kept} x 3 values")
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("trajectory: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_trajectory_dev(self._h, int(which), int(filter), C.c_void_p(int(out.data_ptr())), out.numel() // 3, sh))
+            return out, shown_out
+        xy = np.empty((kept, 3), dtype=np.float32)
+        count, shown = C.c_int32(0), C.c_int32(-1)
+        check(load().gms_slam_trajectory(self._h, int(which), int(filter), ptr(xy), kept, C.byref(count), C.byref(shown)))
+        return xy[:count.value], int(shown.value)
+
+    def _trajectories(self, filter: int, ancestors: bool):
+        kept = self.history_len()[1]
+        xy = np.empty((kept, self.num_particles, 3), dtype=np.float32)
+        anc = np.empty((kept, self.num_particles), dtype=np.int32) if ancestors else None
+        count = C.c_int32(0)
+        check(load().gms_slam_trajectories(self._h, int(filter), ptr(xy), ptr(anc) if ancestors else None, kept, C.byref(count)))
+        return (xy, anc) if ancestors else xy
+
     def _last_beams(self, f: int) -> np.ndarray:
         out = np.zeros(4096, dtype=BEAM_DTYPE)                          # GMS_MAX_BEAMS
         c = C.c_int32(0)
@@ -1010,6 +1057,17 @@ class SLAMParticleMaps(_SlamHandle):
         without a read-back (GmsError GMS_ERR_STATE before the first update and after reset()).  out / shown_out: torch device tensors
         for the picture and the int32 index (nothing is synchronised).  The combined map: calculate_combined(), then grid_map.view()."""
         return self._view(which, 0, rect, decimate, likelihood, packed, out, shown_out)
+
+    def trajectory(self, which="strongest", out=None, shown_out=None):
+        """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
+        first over the kept updates of set_history() -- the path its map was built along, whatever resampling did to the slots since.
+        out / shown_out: torch device tensors (float32 [>= kept][3], int32); nothing is synchronised."""
+        return self._trajectory(which, 0, out, shown_out)
+
+    def trajectories(self, ancestors: bool = False):
+        """every particle's path at once: xytheta [kept][n][3]; ancestors: also [kept][n], the slot present particle k occupied at
+        each kept update"""
+        return self._trajectories(0, ancestors)
 
     def calculate_combined(self) -> np.ndarray:
         """GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458): the combined logData [H][W]; the likelihood field of it is
@@ -1182,6 +1240,21 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._view(which, filter, rect, decimate, likelihood, packed, out, shown_out)
+
+    def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
+        """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
+        is the handle-wide slot that was followed, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._trajectory(which, filter, out, shown_out)
+
+    def trajectories(self, f: int, ancestors: bool = False):
+        """filter f's particles' paths: xytheta [kept][n][3] (and, ancestors, the filter-local slots [kept][n])"""
+        if not 0 <= f < self.num_filters:
+            raise IndexError(f"filter {f} out of range ({self.num_filters})")
+        return self._trajectories(f, ancestors)
 
     def calculate_combined(self, f: int, likelihood: bool = False) -> np.ndarray:
         """GridMapApp.calculateCombined over filter f's particles: its logData [H][W] (likelihood: the field of it)"""

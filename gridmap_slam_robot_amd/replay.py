@@ -52,8 +52,10 @@ class ParticleMapsReplay:
     resampling rule), nothing read back.  The reference starts every particle at Pose(0, 0, 0) (SLAM.java:65-77); start_pose puts them
     where a recording's drive begins instead."""
 
-    def __init__(self, slam: SLAMParticleMaps, seed: int = 2024, resample_fraction: float = 0.5, start_pose=None):
+    def __init__(self, slam: SLAMParticleMaps, seed: int = 2024, resample_fraction: float = 0.5, start_pose=None, history=None):
         self.slam, self.seed, self.fraction = slam, seed, resample_fraction
+        if history is not None:         # keep the particles' paths of the last `history` revolutions (SLAMParticleMaps.set_history)
+            slam.set_history(history)
         self.pose = np.zeros(3, dtype=np.float32) if start_pose is None else np.asarray(start_pose, dtype=np.float32)
         self.frame_no = 0
         if start_pose is not None:
@@ -76,13 +78,19 @@ class ParticleMapsReplay:
         self.frame_no += 1
         return out
 
+    def trajectory(self, which="strongest"):
+        """(xytheta [kept][3], shown): where the robot was according to particle `which`, the one whose map view() shows (history=...)"""
+        return self.slam.trajectory(which)
+
 
 class ParticleMapsBatchReplay:
     """S recordings, one per filter of a SLAMParticleMapsBatch, stepped together: every step is ONE frame() call for all of them.
     Frames of unequal measurement counts are padded to the longest and go through `lengths`."""
 
-    def __init__(self, slam: SLAMParticleMapsBatch, seeds=2024, resample_fraction: float = 0.5, start_poses=None):
+    def __init__(self, slam: SLAMParticleMapsBatch, seeds=2024, resample_fraction: float = 0.5, start_poses=None, history=None):
         self.slam, self.fraction = slam, resample_fraction
+        if history is not None:
+            slam.set_history(history)
         S = slam.num_filters
         self.seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (S,)))
         self.frame_no = 0
@@ -105,3 +113,7 @@ class ParticleMapsBatchReplay:
                               fetch=fetch)
         self.frame_no += 1
         return out
+
+    def trajectory(self, which="strongest", filter: int = 0):
+        """(xytheta [kept][3], shown) of filter `filter`'s particle `which` (history=...)"""
+        return self.slam.trajectory(which, filter)

@@ -478,6 +478,58 @@ int gms_map_view_dev(gms_map *m, int32_t mi, const gms_view *v, void *dev_out);
 int gms_slam_view(gms_slam *s, int32_t which, const gms_view *v, void *out, int32_t *shown);
 int gms_slam_view_dev(gms_slam *s, int32_t which, const gms_view *v, void *dev_out, int32_t *dev_shown);
 
+/* ---- trajectories: every particle's path, kept through resampling -------------------------------------------------------------
+ * The per-particle filter estimates a path together with the map built along it (SLAM.java:33: a Particle is pose, weight and map).
+ * The poses a caller collects frame by frame are NOT the path any returned map was built along: resample() rewrites slot m with the
+ * map and pose of slot idx[m] (:41-45), and the next one can hand "strongest" to a particle with another past.  An opt-in history keeps,
+ * on the device, what is needed to answer "where was the robot, according to the particle whose map is shown": a ring of the last
+ * `capacity` updates, row t holding every slot's pose as it stood when update number t returned (what gms_pf_get_poses would have
+ * given then: motion sample and, with gms_slam_set_refine, the refinement included) and the slot of row t - 1 the particle descends
+ * from.  Every update of the handle -- gms_slam_update_per_particle[_dev], gms_slam_update_batch[_dev], the frame calls; one whose
+ * scan is not integrated (|d_theta| > 30 degrees) or that draws no motion sample is a step like any other -- records one row; every
+ * draw -- gms_slam_resample_maps[_if][_batch], the frame calls' -- composes its indices into the lineage, per filter and only where
+ * the filter did draw, which the kernel reads on the device.  Nothing is read back, by these or by any other call of the handle.
+ * Off (the default) the handle allocates nothing and launches nothing for it; on, an update and a resample each take one small
+ * launch more on the handle's stream, and no result of any other call changes.
+ *
+ * gms_slam_set_history: capacity > 0 keeps the last `capacity` updates from now on (a history already kept is dropped); 0 turns it
+ * off and frees its memory.  GMS_ERR_STATE on a shard of a filter (gms_slam_create_shard: ancestors cross ranks), GMS_ERR_INVALID for
+ * a negative capacity, GMS_ERR_NOMEM where the device cannot hold it.  gms_slam_reset clears the history (no step kept) and keeps it
+ * on at the same capacity; gms_pf_set_poses on the handle's filter, gms_slam_upload_map and gms_slam_combined do not touch it (a pose
+ * set by hand shows in the rows recorded after it, never in one already there).
+ * gms_slam_history_bytes: what gms_slam_set_history allocates for n_particles_total (= filters x particles) slots, with the same
+ * checks and without a device: capacity * n * 16 (4 bytes of parent and 12 of pose per slot and row) + n * 8 (the lineage and the
+ * buffer the next draw composes it into) + 16 (the device's step count and its ticket); 0 for capacity 0.  GMS_ERR_INVALID for a
+ * particle count < 1, a negative capacity or a size beyond int64.
+ * gms_slam_history_len: *steps_total = updates recorded since the history was turned on or cleared, *steps_kept = min(total,
+ * capacity) (either may be NULL).  The host counts them itself: nothing is synchronised.  GMS_ERR_STATE while the history is off.
+ *
+ * gms_slam_trajectory: the path of ONE particle as it stands now -- `which` in the index space of gms_slam_view (>= 0: the slot, a
+ * batched handle's f * n + k, `filter` ignored; GMS_VIEW_STRONGEST: the strongest particle of `filter`, picked on the device from
+ * the statistics the last update left there, with gms_slam_view's GMS_ERR_STATE conditions) -- into xytheta [cap][3] floats, oldest
+ * first: entry j is the pose at update number steps_total - kept + j of the ancestor the particle descends from, *count = kept (may
+ * be NULL), *shown (may be NULL) the slot that was followed, as gms_slam_view reports it.  A slot resampled since the last update
+ * yields the path of the particle it was copied from: the path its map was built along.  cap < kept: GMS_ERR_INVALID, *count set
+ * to what is needed, nothing written.  kept == 0: GMS_OK, *count = 0.  GMS_ERR_STATE while the history is off.  Synchronises.
+ * gms_slam_trajectory_dev: the same into device memory ([cap][3] floats and a device int32_t * or NULL), written on the handle's
+ * stream; nothing is synchronised, and the count is gms_slam_history_len's.
+ * gms_slam_trajectories: every particle of `filter` at once: xytheta [kept][n][3] (cap counts steps), oldest first, and -- ancestors
+ * may be NULL -- ancestors [kept][n], the filter-local slot present particle k occupied at each kept step.  Synchronises.
+ * None of the three changes the handle's state or any later result.
+ *
+ * The back-trace (one workgroup) follows the chains inside LDS: it stages the filter's parent rows there, newest first, a chunk of
+ * rows at a time, the next chunk's loads in flight while the current one is walked, and gathers only the poses from memory.  Where
+ * not one row of a filter fits a chunk buffer (more than 8192 particles per filter), or with GMS_SLAM_HISTORY_WALK=mem in the
+ * environment at creation (tests), every look-up is a load.  gms_slam_history_walk_rows (diagnostics): the rows per chunk, 0 = the
+ * memory form. */
+int gms_slam_history_bytes(int32_t n_particles_total, int32_t capacity, int64_t *bytes);
+int gms_slam_set_history(gms_slam *s, int32_t capacity);
+int gms_slam_history_len(gms_slam *s, int64_t *steps_total, int32_t *steps_kept);
+int gms_slam_trajectory(gms_slam *s, int32_t which, int32_t filter, float *xytheta, int32_t cap, int32_t *count, int32_t *shown);
+int gms_slam_trajectory_dev(gms_slam *s, int32_t which, int32_t filter, float *dev_xytheta, int32_t cap, int32_t *dev_shown);
+int gms_slam_trajectories(gms_slam *s, int32_t filter, float *xytheta, int32_t *ancestors, int32_t cap, int32_t *count);
+int gms_slam_history_walk_rows(gms_slam *s, int32_t *rows);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -412,6 +412,26 @@ public:
         check(gms_map_download_log(map_, out.data()));
         return out;
     }
+    /** Keep every particle's path of the last `capacity` updates on the device, through resampling (gridmapslam.h "trajectories"); 0: off */
+    void setHistory(int capacity) { check(gms_slam_set_history(h_, capacity)); }
+    /** updates kept = min(updates recorded, capacity); *total (may be null): the updates recorded */
+    int historyLength(int64_t *total = nullptr) {
+        int32_t kept = 0;
+        check(gms_slam_history_len(h_, total, &kept));
+        return kept;
+    }
+    /** The path particle `which` -- or, GMS_VIEW_STRONGEST, the strongest particle as render() picks it -- descends along, oldest first
+     *  over the kept updates: the path its map was built along.  *shown (may be null) receives the particle that was followed. */
+    std::vector<Pose> trajectory(int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        const int kept = historyLength();
+        std::vector<float> p((size_t)3 * kept + 1);
+        int32_t count = 0, followed = 0;
+        check(gms_slam_trajectory(h_, which, 0, p.data(), kept, &count, &followed));
+        if (shown) *shown = followed;
+        std::vector<Pose> out((size_t)count);
+        for (int j = 0; j < count; j++) out[j] = Pose(p[3 * j], p[3 * j + 1], p[3 * j + 2]);
+        return out;
+    }
     int size() const { return n_; }
     int width() const { return w_; }
     int height() const { return hgt_; }
