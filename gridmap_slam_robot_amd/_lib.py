@@ -29,6 +29,7 @@ assert len(KERNEL_NAMES) == K_COUNT
 BEAM_DTYPE = np.dtype(
     [("local_x", "<f8"), ("local_y", "<f8"), ("distance", "<f8"), ("hit", "u1"), ("pad_", "u1", (7,))]
 )
+CAST_DTYPE = np.dtype([("step", "<i4"), ("x", "<i4"), ("y", "<i4"), ("range", "<f4")])      # gms_cast_hit, 16 bytes
 PACKED_DTYPE = np.dtype([("w", "<f8"), ("x", "<f4"), ("y", "<f4"), ("theta", "<f4"), ("pad", "<u4")])
 
 
@@ -65,6 +66,7 @@ class GmsView(C.Structure):
 GMS_VIEW_GREY8, GMS_VIEW_PACKED32 = 0, 1
 GMS_VIEW_LOG, GMS_VIEW_LIKELIHOOD = 0, 1
 GMS_VIEW_STRONGEST = -1
+GMS_CAST_ALL = -2
 
 
 class GmsError(RuntimeError):
@@ -253,6 +255,13 @@ def load() -> C.CDLL:
     sig("gms_slam_trajectory_dev", C.c_int, vp, i32, i32, vp, i32, vp)
     sig("gms_slam_trajectories", C.c_int, vp, i32, vp, vp, i32, C.POINTER(C.c_int32))
     sig("gms_slam_history_walk_rows", C.c_int, vp, C.POINTER(C.c_int32))
+    sig("gms_map_cast", C.c_int, vp, i32, vp, i32, vp, i32, vp)
+    sig("gms_map_cast_dev", C.c_int, vp, i32, vp, i32, vp, i32, vp)
+    sig("gms_map_cast_at", C.c_int, vp, vp, i32, vp, i32, vp)
+    sig("gms_map_cast_at_dev", C.c_int, vp, vp, i32, vp, i32, vp)
+    sig("gms_slam_cast", C.c_int, vp, i32, i32, vp, i32, vp, vp)
+    sig("gms_slam_cast_dev", C.c_int, vp, i32, i32, vp, i32, vp, vp)
+    sig("gms_map_cast_plane_builds", C.c_int, vp, C.POINTER(C.c_int64))
     _lib = L
     return L
 

@@ -244,7 +244,7 @@ static int map_free(gms_map *m) {
     prof_drain(m);
     for (ProfSlot &s : m->prof_free) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
     hipFree(m->d_log); hipFree(m->d_lik); hipFree(m->d_fac); hipFree(m->d_cnt); hipFree(m->d_cnt_pend); hipFree(m->d_bbox); hipFree(m->d_taps); hipFree(m->d_tile_state); hipFree(m->d_tile_stats);
-    hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch); hipFree(m->d_view);
+    hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch); hipFree(m->d_view); hipFree(m->d_cast_plane);
     hipFree(m->d_trace_cells); hipFree(m->d_trace_cls); hipFree(m->d_trace_cnt);
     if (m->h_beams) hipHostFree(m->h_beams);
     ring_free(m->beam_ring);
@@ -351,6 +351,10 @@ int gms_map_create(const gms_params *p, gms_map **out) {
     HIPCHK(hipStreamSynchronize(m->stream));
     map_log_replaced(m);
     m->pair_launches = 1;
+    {   // the casts' memory form wherever an LDS form exists (tests; gms_cast.hip)
+        const char *cw_env = getenv("GMS_CAST_WALK");
+        m->cast_walk_mem = cw_env && cw_env[0] == 'm';
+    }
     {   // the tiled batched ray cast: 8 KiB of slots + a 64 KiB tile + static LDS
         int lds_max = 0;
         if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, m->device) != hipSuccess) lds_max = 64 * 1024;

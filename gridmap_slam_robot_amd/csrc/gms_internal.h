@@ -116,6 +116,11 @@ struct gms_map {
     double *d_scratch;    // small device scratch
     unsigned char *d_view; // staging of the host forms of gms_map_view / gms_slam_view: [16 bytes: the shown index][the image]; grows, never per view
     size_t view_cap;      // its size in bytes
+    uint32_t *d_cast_plane;   // [n_maps][H][cast_wpr] the bit plane the casts walk (gms_cast.hip): bit x & 31 of word x >> 5 of row y = logData > 0; allocated by the first cast
+    int32_t cast_wpr;         // its 32-bit words per row (rows padded to 64 cells)
+    int32_t cast_plane_current;   // it is the plane of logData as it stands (cleared by the transitions below that move logData)
+    int32_t cast_walk_mem;    // casts walk memory even where their window or class plane fits the LDS (GMS_CAST_WALK=mem: tests)
+    int64_t cast_plane_builds;    // launches of the plane's pre-pass so far (tests: an unchanged map is not packed again)
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -154,16 +159,17 @@ struct gms_map {
 // ---- map state transitions (need_full_build, fac_current, lik_stale, apply_pending, bbox_dirty, bbox_cur): each is named for
 // what happened and sets every field that event affects ----
 // logData (or, gms_map_upload_likelihood, the field) was replaced: the next rebuild covers every tile and leaves none alone
-static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; }
+static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; m->cast_plane_current = 0; }
 // likelihoodData is up to date everywhere (made so, or about to be replaced wholesale)
 static inline void map_lik_current(gms_map *m) { m->lik_stale = 0; }
 // an immediate apply pass added the counts to logData without a rebuild having seen them
-static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; }
+static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; m->cast_plane_current = 0; }
 // a deferred apply pass has been enqueued: the box of the scan it applied is the current half now
 static inline void gms_apply_done(gms_map *m) {
     m->bbox_cur = 1 - m->bbox_cur;
     m->bbox_dirty = 0;
     m->apply_pending = 0;
+    m->cast_plane_current = 0;         // (logData moved)
 }
 // the scan just cast (and already in the likelihood field) keeps its counts for a later launch
 static inline void gms_defer_apply(gms_map *m) {

@@ -21,9 +21,9 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import BEAM_DTYPE, GmsParams, GmsPfStats, check, load, ptr
+from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
-__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose"]
+__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -108,6 +108,51 @@ def world_rect_to_cells(grid_map, center, size):
 def _beams_of(obs) -> np.ndarray:
     b = obs.beams if isinstance(obs, Observation) else obs
     return np.ascontiguousarray(b, dtype=BEAM_DTYPE)
+
+
+RESIDUAL_AGREE, RESIDUAL_MEASURED_SHORTER, RESIDUAL_MEASURED_LONGER, RESIDUAL_NO_PREDICTION = 0, 1, 2, 3
+
+
+def scan_residual(measured_beams, cast, resolution: float, hit_tolerance: float) -> np.ndarray:
+    """Holds a measured scan against the scan predicted for the same beams (cast = the gms_cast_hit records of GridMap.cast /
+    SLAMParticleMaps.cast of measured_beams as probes): one uint8 class per beam.  Pure numpy, float32 like the sensor model.
+
+    With m = float32(distance) / float32(resolution), the beam's measuredDistance in grid units (GridMap.java:188), r = cast.range and
+    t = float32(hit_tolerance) / 2, the band inverseSensorModel puts around a measurement (SensorModel.java:35-40):
+
+      RESIDUAL_NO_PREDICTION (3)     cast.step < 0 and the beam hit: the map has no occupied cell on the beam's walk, there is nothing to
+                                     hold the return against (an unmapped or free stretch)
+      RESIDUAL_AGREE (0)             both hit and |m - r| <= t; or the beam missed and the walk found nothing either
+      RESIDUAL_MEASURED_SHORTER (1)  the beam hit and m < r - t: something is there that the map lacks
+      RESIDUAL_MEASURED_LONGER (2)   m > r + t, or the beam missed although the walk found a wall: the map has a wall the beam passed
+
+    A hit beam whose distance is NaN satisfies none of the three comparisons and stays RESIDUAL_NO_PREDICTION."""
+    b = _beams_of(measured_beams)
+    c = np.asarray(cast)
+    if b.shape != c.shape:
+        raise ValueError(f"scan_residual: {b.shape} beams against {c.shape} predictions")
+    f = np.float32
+    m = b["distance"].astype(f) / f(resolution)
+    r = c["range"].astype(f)
+    t = f(hit_tolerance) / f(2)
+    hit, pred = b["hit"] != 0, c["step"] >= 0
+    out = np.full(b.shape, RESIDUAL_NO_PREDICTION, dtype=np.uint8)
+    both = hit & pred
+    out[both & (np.abs(m - r) <= t)] = RESIDUAL_AGREE
+    out[both & (m < r - t)] = RESIDUAL_MEASURED_SHORTER
+    out[both & (m > r + t)] = RESIDUAL_MEASURED_LONGER
+    out[~hit & ~pred] = RESIDUAL_AGREE
+    out[~hit & pred] = RESIDUAL_MEASURED_LONGER
+    return out
+
+
+def _cast_device_out(out, n: int) -> int:
+    """the device address of a caller's torch tensor that is to receive n gms_cast_hit records"""
+    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
+        raise ValueError("cast: out must be a contiguous torch tensor on the device")
+    if out.numel() * out.element_size() < 16 * n:
+        raise ValueError(f"cast: out holds {out.numel() * out.element_size()} bytes, the records need {16 * n}")
+    return int(out.data_ptr())
 
 
 class GridMap:
@@ -233,6 +278,42 @@ class GridMap:
     def world_rect(self, center, size):
         """(x0, y0, w, h): the cells under a world rectangle (centre, size in metres), clamped to the map (world_rect_to_cells)"""
         return world_rect_to_cells(self, center, size)
+
+    def cast(self, poses, probes, mi: int = 0) -> np.ndarray:
+        """The predicted scan (gridmapslam.h "predicted scans"): from each of poses [P][3], the first occupied cell (logData > 0) on the
+        walk integrateObservation would make for each probe -- a beam of which local_x, local_y and distance are read -- in map mi.
+        Returns gms_cast_hit records [P][B] (step, x, y, range; step -1: nothing on the walk, range = the probe's own distance in grid
+        units).  The walk includes the extra_steps cells past a probe's end point: a wall that close behind it is still reported."""
+        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        b = _beams_of(probes).reshape(-1)
+        out = np.empty((len(p), len(b)), dtype=CAST_DTYPE)
+        check(load().gms_map_cast(self._h, int(mi), ptr(p), len(p), ptr(b), len(b), ptr(out)))
+        return out
+
+    def cast_dev(self, dev_poses: int, P: int, dev_probes: int, B: int, out, mi: int = 0):
+        """cast() with device pointers; out: a contiguous torch device tensor of P * B * 16 bytes, written on the handle's stream"""
+        check(load().gms_map_cast_dev(self._h, int(mi), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
+                                      C.c_void_p(_cast_device_out(out, P * B))))
+        return out
+
+    def cast_at(self, probes, pf: "ParticleFilter", strongest: bool = False) -> np.ndarray:
+        """cast() from the filter's device-resident weighted (or strongest particle's) pose, as integrate_at takes it: records [B]
+        ([n_maps][B] on a batched handle, map i from its own filter pose)"""
+        b = _beams_of(probes).reshape(-1)
+        out = np.empty((self.n_maps, len(b)), dtype=CAST_DTYPE)
+        check(load().gms_map_cast_at(self._h, ptr(b), len(b), pf._h, 1 if strongest else 0, ptr(out)))
+        return out[0] if self.n_maps == 1 else out
+
+    def cast_at_dev(self, dev_probes: int, B: int, pf: "ParticleFilter", out, strongest: bool = False):
+        check(load().gms_map_cast_at_dev(self._h, C.c_void_p(dev_probes), int(B), pf._h, 1 if strongest else 0,
+                                         C.c_void_p(_cast_device_out(out, self.n_maps * B))))
+        return out
+
+    def cast_plane_builds(self) -> int:
+        """diagnostics: launches of the casts' bit-plane pre-pass so far (casts of an unchanged map add none)"""
+        n = C.c_int64(0)
+        check(load().gms_map_cast_plane_builds(self._h, C.byref(n)))
+        return int(n.value)
 
     def copy_from(self, other: "GridMap"):
         """createMapData(other) (GridMap.java:106-124)."""
@@ -897,6 +978,30 @@ class _SlamHandle:
         check(load().gms_slam_view(self._h, int(which), C.byref(v), ptr(img), C.byref(shown)))
         return img, int(shown.value)
 
+    def _cast(self, which, filter: int, probes, out, shown_out):
+        """gms_slam_cast[_dev]: which = a handle-wide slot, "strongest" (of `filter`, picked on the device) or "all"; (records, shown)"""
+        if isinstance(which, str):
+            if which not in ("strongest", "all"):
+                raise ValueError('cast: which must be a particle index, "strongest" or "all"')
+            which = _lib.GMS_VIEW_STRONGEST if which == "strongest" else _lib.GMS_CAST_ALL
+        every = which == _lib.GMS_CAST_ALL
+        n_total = self.num_particles * int(self.params.n_maps)
+        if out is not None:                                  # probes: (device address, B)
+            dev_probes, B = probes
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("cast: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_cast_dev(self._h, int(which), int(filter), C.c_void_p(dev_probes), int(B),
+                                           C.c_void_p(_cast_device_out(out, (n_total if every else 1) * B)), sh))
+            return out, shown_out
+        b = _beams_of(probes).reshape(-1)
+        rec = np.empty((n_total, len(b)) if every else (len(b),), dtype=CAST_DTYPE)
+        shown = C.c_int32(-1)
+        check(load().gms_slam_cast(self._h, int(which), int(filter), ptr(b), len(b), ptr(rec), C.byref(shown)))
+        return rec, (None if every else int(shown.value))
+
     def set_history(self, capacity: int):
         """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
         resampling (0: off, the memory freed).  reset() clears the history and keeps it on.  Refused on a shard of a filter."""
@@ -1057,6 +1162,13 @@ class SLAMParticleMaps(_SlamHandle):
         without a read-back (GmsError GMS_ERR_STATE before the first update and after reset()).  out / shown_out: torch device tensors
         for the picture and the int32 index (nothing is synchronised).  The combined map: calculate_combined(), then grid_map.view()."""
         return self._view(which, 0, rect, decimate, likelihood, packed, out, shown_out)
+
+    def cast(self, probes, which="strongest", out=None, shown_out=None):
+        """The predicted scan of particles at THEIR OWN pose in THEIR OWN map (gridmapslam.h "predicted scans"; GridMap.cast's records):
+        which = a particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update):
+        (records [B], shown); which = "all": (records [n][B], None).  out / shown_out: torch device tensors, probes then
+        (device address, B); nothing is synchronised."""
+        return self._cast(which, 0, probes, out, shown_out)
 
     def trajectory(self, which="strongest", out=None, shown_out=None):
         """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
@@ -1240,6 +1352,15 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._view(which, filter, rect, decimate, likelihood, packed, out, shown_out)
+
+    def cast(self, probes, which="strongest", filter: int = 0, out=None, shown_out=None):
+        """SLAMParticleMaps.cast for filter `filter`: which = "strongest" (that filter's), a FILTER-LOCAL particle index, or "all":
+        every particle of EVERY filter, records [S * n][B] in handle-wide slot order; shown is the handle-wide slot, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._cast(which, filter, probes, out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown

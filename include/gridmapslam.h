@@ -530,6 +530,56 @@ int gms_slam_trajectory_dev(gms_slam *s, int32_t which, int32_t filter, float *d
 int gms_slam_trajectories(gms_slam *s, int32_t filter, float *xytheta, int32_t *ancestors, int32_t cap, int32_t *count);
 int gms_slam_history_walk_rows(gms_slam *s, int32_t *rows);
 
+/* ---- predicted scans: what the LIDAR would see in a map from a pose -----------------------------------------------------------
+ * The inverse of integrateObservation, and this library's own definition (the reference has no such method).  A PROBE is a gms_beam
+ * of which only local_x, local_y and distance are read (`hit` is ignored).  Casting probe b from pose p in a map walks exactly the
+ * cells, in exactly the order, that integrateObservation(map, {b}, p) visits for it -- start and end point as GridMap.java:175-188,
+ * rayIterator.init(start + 0.5f, end + 0.5f, extra_steps) as :210, the walk ending where it leaves the map as
+ * RayIterator.java:107-130: the list gms_map_trace_scan returns for that beam -- and reports the FIRST cell of that walk whose
+ * logData > logOdds(0.5) = 0, the class GridMap.java:239 maps to 1.  A cell at exactly 0, at -0.0 or NaN is not occupied.  A ray that
+ * starts outside the map visits no cell (RayIterator.hasNext, :108) and reports none.
+ * NB the walk includes the gms_params.extra_steps cells PAST the probe's end point (they are part of integrateObservation's walk), so
+ * a wall up to that many steps beyond the end point is still reported; one step further it is not.
+ * Every walk is cut after W + H + extra_steps + 2 cells whatever its inputs (non-finite poses and probes included; no defined walk is
+ * that long), so a cast always terminates.
+ *
+ * A cast sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment (a scan whose `logData +=` pass
+ * is still deferred is applied first, as by those downloads) and changes no later result of its handle.  Arguments are checked before
+ * anything is enqueued (GMS_ERR_INVALID, nothing touched). */
+typedef struct gms_cast_hit {
+    int32_t step;               /* index of the cell in the walk (0 = the first cell next() returns); -1: no occupied cell on the walk */
+    int32_t x, y;               /* that cell; -1, -1 when step < 0 */
+    float range;                /* grid units.  step >= 0: applyMeasurement's `distance` of that cell (GridMap.java:215-217): dX = startX -
+                                   (x + 0.5f), dY likewise, (float)sqrt(dX * dX + dY * dY) in float, every operation rounded, nothing fused.
+                                   step < 0: the probe's own measuredDistance, (float)distance / resolution (:188).  The unit
+                                   inverseSensorModel compares in: a predicted and a measured beam can be held against hit_tolerance */
+} gms_cast_hit;
+#define GMS_CAST_ALL (-2)                                      /* gms_slam_cast's `which`: every particle the handle holds */
+/* Map mi of a shared or batched map: P poses (poses [P][3] = x, y, theta; 1 <= P <= GMS_MAX_PARTICLES) cast the same B probes
+ * (1 <= B <= the handle's max_beams); out [P][B].  The host form stages its inputs, reads the records back and synchronises; _dev
+ * takes device pointers (out 16-byte aligned), runs on the handle's stream and synchronises nothing.
+ * The lanes of a workgroup walk neighbouring probes of one pose through a BIT PLANE of the map (logData > 0, one bit per cell), which
+ * a pre-pass packs and the handle keeps until logData changes: repeated casts on an unchanged map do not rebuild it.  A workgroup
+ * stages the window of the plane its rays can reach in LDS and walks there; where that window exceeds the LDS it asked for (64 KiB),
+ * or with GMS_CAST_WALK=mem in the environment at creation (tests), it walks the plane in memory. */
+int gms_map_cast(gms_map *m, int32_t mi, const float *poses, int32_t P, const gms_beam *probes, int32_t B, gms_cast_hit *out);
+int gms_map_cast_dev(gms_map *m, int32_t mi, const float *dev_poses, int32_t P, const gms_beam *dev_probes, int32_t B, gms_cast_hit *dev_out);
+/* The same from the filter's device-resident weighted (which = 0) or strongest (1) pose, as gms_map_integrate_at takes it -- no host
+ * round trip; out [n_maps][B]: map i of a batched handle is cast from ITS filter pose (one map: out [B]). */
+int gms_map_cast_at(gms_map *m, const gms_beam *probes, int32_t B, gms_pf *pf, int32_t which, gms_cast_hit *out);
+int gms_map_cast_at_dev(gms_map *m, const gms_beam *dev_probes, int32_t B, gms_pf *pf, int32_t which, gms_cast_hit *dev_out);
+/* The per-particle filter: particles cast at THEIR OWN pose in THEIR OWN map.  which >= 0: that particle, in the index space of
+ * gms_slam_download_map, out [B]; GMS_VIEW_STRONGEST: the strongest particle of `filter`, picked on the device exactly as gms_slam_view
+ * picks it, with its GMS_ERR_STATE cases (before the first update, after a reset, on a shard), out [B]; *shown (may be NULL; _dev: a
+ * device int32_t *) receives the index that was cast, as there; GMS_CAST_ALL: every particle the handle holds (a shard: its local
+ * ones), out [n_total][B], nothing written to shown.  `filter` is read with GMS_VIEW_STRONGEST only (gms_slam_trajectory's rule).
+ * Pose, its trig and the maps' generation come from device state (the epoch counters, like every kernel of the handle): nothing is
+ * read back in front of the launch.  One workgroup per particle: it stages plane 0 of the particle's class planes (2 bits per cell,
+ * 3.6 KB at 120 x 120) in LDS and the lanes walk the codes.  Handles that keep no planes (an eager field, a kernel wider than 15 taps,
+ * a plane over 24 KiB), and every handle created with GMS_CAST_WALK=mem in the environment (tests), read logData itself. */
+int gms_slam_cast(gms_slam *s, int32_t which, int32_t filter, const gms_beam *probes, int32_t B, gms_cast_hit *out, int32_t *shown);
+int gms_slam_cast_dev(gms_slam *s, int32_t which, int32_t filter, const gms_beam *dev_probes, int32_t B, gms_cast_hit *dev_out, int32_t *dev_shown);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,
@@ -673,6 +723,8 @@ int gms_map_tile_stats(gms_map *m, int32_t enable, int64_t *out4);
  * 4 / 5 = the squared thresholds the per-particle-map ray cast classifies cells with instead of a square root per cell: the smallest float s with
  * (float)sqrt(s) >= a, resp. the largest with (float)sqrt(s) <= a (SensorModel.java:31-41 compares (float)Math.sqrt(s) with a). */
 int gms_debug_f32(gms_map *m, int32_t op, const float *in, float *out, int64_t n);
+/* Launches of the casts' bit-plane pre-pass on this handle so far (gms_map_cast): casts of an unchanged map add none. */
+int gms_map_cast_plane_builds(const gms_map *m, int64_t *builds);
 /* Development: instrumented builds (-DGMS_STAMPS) write wall-clock stamps of their kernels' stages to dev_buffer
  * ([workgroup][16] uint64, 10 ns units; NULL turns it off); a product build returns GMS_ERR_STATE.  tools/stamps.py. */
 int gms_debug_set_stamps(gms_map *m, void *dev_buffer);

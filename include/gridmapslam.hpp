@@ -148,6 +148,17 @@ public:
         check(gms_map_view(h_, mi, &v, out.data()));
         return out;
     }
+    /** The predicted scan (gridmapslam.h "predicted scans"): for every pose, the first occupied cell on the walk integrateObservation
+     *  would make for every probe (local_x, local_y, distance of the measurements are read); records [poses][probes].  The walk includes
+     *  the extra_steps cells past a probe's end point. */
+    std::vector<gms_cast_hit> cast(const std::vector<Pose> &poses, const Observation &probes, int mi = 0) {
+        const auto &ms = probes.getMeasurements();
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        std::vector<gms_cast_hit> out(poses.size() * ms.size());
+        check(gms_map_cast(h_, mi, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data()));
+        return out;
+    }
     /** the whole map at one cell per pixel */
     gms_view fullView(bool likelihood = false, bool packed = false, int decimate = 1) const {
         return gms_view{0, 0, w_, hgt_, decimate, likelihood ? GMS_VIEW_LIKELIHOOD : GMS_VIEW_LOG, packed ? GMS_VIEW_PACKED32 : GMS_VIEW_GREY8, 0};
@@ -403,6 +414,17 @@ public:
         int32_t drawn = 0;
         check(gms_slam_view(h_, which, &v, out.data(), &drawn));
         if (shown) *shown = drawn;
+        return out;
+    }
+    /** The predicted scan of particle `which` -- GMS_VIEW_STRONGEST: the strongest, as render() picks it; GMS_CAST_ALL: every particle,
+     *  records [size()][probes] -- at its own pose in its own map (gridmapslam.h "predicted scans"); *shown (may be null) receives the
+     *  particle that was cast (not written for GMS_CAST_ALL). */
+    std::vector<gms_cast_hit> cast(const Observation &probes, int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        const auto &ms = probes.getMeasurements();
+        std::vector<gms_cast_hit> out((which == GMS_CAST_ALL ? (size_t)n_ : 1) * ms.size());
+        int32_t picked = 0;
+        check(gms_slam_cast(h_, which, 0, ms.data(), (int32_t)ms.size(), out.data(), &picked));
+        if (shown && which != GMS_CAST_ALL) *shown = picked;
         return out;
     }
     /** GridMapApp.calculateCombined (J/app/GridMapApp.java:439-458): the combined logData */

@@ -1,0 +1,60 @@
+"""The expected records of a predicted scan (include/gridmapslam.h "predicted scans"), built only from what the oracle exports:
+Grid.scan_rays gives a beam's start, end and measured distance (GridMap.java:175-188), Grid.trace_ray the ordered cells of
+rayIterator.init(start + 0.5f, end + 0.5f, extra_steps) (:210, RayIterator.java:65-130); the first cell whose log-odds exceed 0 is
+the hit, and its range is applyMeasurement's `distance` (:215-217) restated in numpy.float32, operation by operation."""
+import numpy as np
+
+from gridmap_slam_robot_amd._lib import BEAM_DTYPE, CAST_DTYPE
+
+F = np.float32
+
+
+def walks(grid, probes, pose):
+    """[(rays row, cells [n][2], n_planned)] per probe: the walk and how many cells init() planned for it (more than were walked: the
+    ray left the map)"""
+    probes = np.ascontiguousarray(probes, dtype=BEAM_DTYPE)
+    rays = grid.scan_rays(probes, np.asarray(pose, dtype=np.float32))
+    extra = int(grid.g.extra_steps)
+    out = []
+    for r in rays:
+        sx, sy, ex, ey = (F(r[0]) + F(0.5), F(r[1]) + F(0.5), F(r[2]) + F(0.5), F(r[3]) + F(0.5))
+        cells = grid.trace_ray(sx, sy, ex, ey, extra)
+        out.append((r, cells))
+    return out
+
+
+def planned_cells(ray, extra):
+    """n of RayIterator.init for finite coordinates: 1 + extra + |floor(x1) - floor(x0)| + |floor(y1) - floor(y0)| (:75-100)"""
+    x0, y0, x1, y1 = (float(F(ray[k]) + F(0.5)) for k in range(4))
+    return 1 + extra + abs(int(np.floor(x1)) - int(np.floor(x0))) + abs(int(np.floor(y1)) - int(np.floor(y0)))
+
+
+def expect(grid, log, probes, pose):
+    """gms_cast_hit records [B] of the probes cast from pose in the map whose logData is log (any shape holding H * W doubles)"""
+    log = np.asarray(log, dtype=np.float64).reshape(-1)
+    W = grid.W
+    out = np.empty(len(probes), dtype=CAST_DTYPE)
+    for b, (r, cells) in enumerate(walks(grid, probes, pose)):
+        rec = (-1, -1, -1, F(r[4]))                                         # the probe's own measuredDistance (:188)
+        for k, (x, y) in enumerate(cells):
+            if log[int(x) + int(y) * W] > 0:                                # GridMap.java:239 (NaN, 0 and -0.0: not occupied)
+                dX = F(r[0]) - (F(x) + F(0.5))                              # :215
+                dY = F(r[1]) - (F(y) + F(0.5))                              # :216
+                rec = (k, int(x), int(y), F(np.sqrt(F(F(dX * dX) + F(dY * dY)))))   # :217 (the float sqrt is correctly rounded)
+                break
+        out[b] = rec
+    return out
+
+
+def expect_poses(grid, log, probes, poses):
+    return np.stack([expect(grid, log, probes, p) for p in np.asarray(poses, dtype=np.float32).reshape(-1, 3)])
+
+
+def probes_from(local_x, local_y, distance=None):
+    x = np.asarray(local_x, dtype=np.float64)
+    y = np.asarray(local_y, dtype=np.float64)
+    b = np.zeros(x.shape, dtype=BEAM_DTYPE)
+    b["local_x"], b["local_y"] = x, y
+    b["distance"] = np.sqrt(x * x + y * y) if distance is None else distance
+    b["hit"] = 1
+    return b
