@@ -50,6 +50,31 @@ def expect_poses(grid, log, probes, poses):
     return np.stack([expect(grid, log, probes, p) for p in np.asarray(poses, dtype=np.float32).reshape(-1, 3)])
 
 
+def window_box_of(grid, probes, pose):
+    """(wx0, wy0, ww, wh): the box a workgroup of k_cast_map takes for these probes of one pose, as DESIGN.md 4e documents it: every
+    ray's start and end cell, floor(coord + 0.5f) held to [-1, n] (NaN: cell 0, as a saturating conversion makes it), padded by
+    extra_steps + 1, clipped to the map; columns counted in 32-bit words (x >> 5).  (0, 0, 0, 0): the box misses the map.  For the
+    preconditions of tests only -- what a cast returns never depends on it."""
+    rays = np.asarray(grid.scan_rays(np.ascontiguousarray(probes, dtype=BEAM_DTYPE), np.asarray(pose, dtype=np.float32)))
+    W, H, pad = int(grid.W), int(grid.H), int(grid.g.extra_steps) + 1
+
+    def cells(v, n):
+        f = np.floor((v.astype(F) + F(0.5)).astype(np.float64))
+        return np.clip(np.where(np.isnan(f), 0.0, f), -1, n).astype(np.int64)
+    xs = np.concatenate([cells(rays[:, 0], W), cells(rays[:, 2], W)])
+    ys = np.concatenate([cells(rays[:, 1], H), cells(rays[:, 3], H)])
+    x0, y0 = max(0, int(xs.min()) - pad), max(0, int(ys.min()) - pad)
+    x1, y1 = min(W - 1, int(xs.max()) + pad), min(H - 1, int(ys.max()) + pad)
+    if x1 < x0 or y1 < y0:
+        return 0, 0, 0, 0
+    return x0 >> 5, y0, (x1 >> 5) - (x0 >> 5) + 1, y1 - y0 + 1
+
+
+def window_of(grid, probes, pose):
+    """(ww, wh) of window_box_of: words x rows; ww * wh against the words a launch may stage decides LDS or memory"""
+    return window_box_of(grid, probes, pose)[2:]
+
+
 def probes_from(local_x, local_y, distance=None):
     x = np.asarray(local_x, dtype=np.float64)
     y = np.asarray(local_y, dtype=np.float64)
