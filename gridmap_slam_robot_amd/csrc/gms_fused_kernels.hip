@@ -56,7 +56,11 @@ k_norm_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_
     }
     if (blockIdx.x < n_ray_blocks) {
         __shared__ RedLds L;
-        __shared__ float s_pose[3];
+        // what does not need the pose goes in front of the fold: slots (and the near field's tile) cleared, the beams' loads in
+        // flight beside the partials'; the fold's barriers publish the clearing
+        const bool near = blockIdx.x >= n_ray_blocks - n_near_blocks;
+        const RayPre pre = near ? raycast_near_prologue(beams, B, B, blockIdx.x - (n_ray_blocks - n_near_blocks), 0, smem)
+                                : raycast_prologue<RCF_RAYS, 4>(beams, B, B, nullptr, nw_max, blockIdx.x, 0, smem);
         const int cols[4] = { COL_SUM, COL_XW, COL_YW, COL_TW };
         double f[4];
         if (LOGNORM) {                                                 // the population's reference, then the rescaled sums
@@ -64,18 +68,12 @@ k_norm_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_
         } else {
             fold_sums<4>(partials, nblk_global, cols, f, L);           // one round trip, one barrier pair
         }
-        if (threadIdx.x == 0) {
-            s_pose[0] = (float)(f[1] / f[0]);                          // SLAM.java:176
-            s_pose[1] = (float)(f[2] / f[0]);
-            s_pose[2] = (float)(f[3] / f[0]);
-        }
-        __syncthreads();
+        // every thread holds the four sums (the fold's last step reads them from LDS in every wavefront) and forms the pose itself:
+        // the same three divisions on the same bits, nothing to publish, no barrier
+        const float wpose[3] = { (float)(f[1] / f[0]), (float)(f[2] / f[0]), (float)(f[3] / f[0]) };       // SLAM.java:176
         GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 1);
-        if (blockIdx.x >= n_ray_blocks - n_near_blocks)
-            raycast_near_body(g, beams, B, B, nullptr, 0, cnt, bbox, blockIdx.x - (n_ray_blocks - n_near_blocks), 0, smem, s_pose);
-        else
-            raycast_body<false, RCF_RAYS, 4>(g, beams, B, B, nullptr, 0, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, nw_max, blockIdx.x, 0,
-                                             smem, s_pose, n_near_blocks ? 1 : 0);
+        if (near) raycast_near_body(g, pre, wpose, cnt, bbox, 0, smem);
+        else raycast_body<false, RCF_RAYS, 4>(g, pre, wpose, B, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, blockIdx.x, 0, smem, n_near_blocks ? 1 : 0);
     } else {
         normalize_pack_body(partials, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2, stats,
                             blockIdx.x - n_ray_blocks, 0, LOGNORM ? logw_lognorm : (const double *)nullptr, res_ticket, n_norm_blocks,
@@ -132,21 +130,15 @@ k_raycast_norm_chunks(GridDev g, const gms_beam *__restrict__ beams, int32_t B, 
     }
     if (blockIdx.x < n_ray_blocks) {
         __shared__ RedLds L;
-        __shared__ float s_pose[3];
+        const bool near = blockIdx.x >= n_ray_blocks - n_near_blocks;              // (as in k_norm_raycast)
+        const RayPre pre = near ? raycast_near_prologue(beams, B, B, blockIdx.x - (n_ray_blocks - n_near_blocks), 0, smem)
+                                : raycast_prologue<RCF_RAYS, 4>(beams, B, B, nullptr, nw_max, blockIdx.x, 0, smem);
         const int cols[4] = { COL_SUM, COL_XW, COL_YW, COL_TW };
         double f[4];
         fold_sums<4>(partials, nblk_global, cols, f, L);               // one round trip, one barrier pair
-        if (threadIdx.x == 0) {
-            s_pose[0] = (float)(f[1] / f[0]);                          // SLAM.java:176
-            s_pose[1] = (float)(f[2] / f[0]);
-            s_pose[2] = (float)(f[3] / f[0]);
-        }
-        __syncthreads();
-        if (blockIdx.x >= n_ray_blocks - n_near_blocks)
-            raycast_near_body(g, beams, B, B, nullptr, 0, cnt, bbox, blockIdx.x - (n_ray_blocks - n_near_blocks), 0, smem, s_pose);
-        else
-            raycast_body<false, RCF_RAYS, 4>(g, beams, B, B, nullptr, 0, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, nw_max, blockIdx.x, 0,
-                                             smem, s_pose, n_near_blocks ? 1 : 0);
+        const float wpose[3] = { (float)(f[1] / f[0]), (float)(f[2] / f[0]), (float)(f[3] / f[0]) };       // SLAM.java:176
+        if (near) raycast_near_body(g, pre, wpose, cnt, bbox, 0, smem);
+        else raycast_body<false, RCF_RAYS, 4>(g, pre, wpose, B, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, blockIdx.x, 0, smem, n_near_blocks ? 1 : 0);
     } else if (blockIdx.x < n_ray_blocks + n_norm_blocks) {
         normalize_own_body(partials, nblk_global, w, pose, n, offset, glob_raw, stats, blockIdx.x - n_ray_blocks);
     } else {

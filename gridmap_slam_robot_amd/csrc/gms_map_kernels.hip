@@ -79,14 +79,18 @@ __device__ __forceinline__ void lds_poll_2xu64(const uint64_t *p0, const uint64_
                  : "=&v"(a), "=&v"(c) : "v"(lds_offset(p0)), "v"(lds_offset(p1)) : "memory");
 }
 
-// ray_init + the parts of the walk that do not depend on the recurrence
-__device__ __forceinline__ RayMeta ray_meta(const GridDev &g, const RayIn &ray, RayDev &r) {
-    RayMeta mt;
+// ray_meta in two parts.  ray_walk_init is all the PRODUCER of a walk needs: ray_init (error, dx, dy) and the number of steps the walk
+// emits.  ray_meta_rest is what only the consumers of the decision words read: the cell arithmetic's constants and the walk's box.
+__device__ __forceinline__ int32_t ray_walk_init(const GridDev &g, const RayIn &ray, RayDev &r) {
     ray_init(r, ray.sx + 0.5f, ray.sy + 0.5f, ray.ex + 0.5f, ray.ey + 0.5f, g.extra);   // GridMap.java:210
+    const bool inb0 = !(r.x < 0 || r.x >= g.W || r.y < 0 || r.y >= g.H);
+    return (inb0 && r.n > 0) ? min(r.n, g.W + g.H + 1) : 0;
+}
+__device__ __forceinline__ RayMeta ray_meta_rest(const GridDev &g, const RayIn &ray, const RayDev &r, int32_t n_eff) {
+    RayMeta mt;
     mt.x0 = r.x; mt.y0 = r.y; mt.x_inc = r.x_inc; mt.y_inc = r.y_inc;
     mt.sx = ray.sx; mt.sy = ray.sy; mt.measured = ray.measured; mt.hit = ray.hit;
-    const bool inb0 = !(r.x < 0 || r.x >= g.W || r.y < 0 || r.y >= g.H);
-    mt.n_eff = (inb0 && r.n > 0) ? min(r.n, g.W + g.H + 1) : 0;
+    mt.n_eff = n_eff;
     // Where the walk can go.  It is monotonic in x and in y and makes n - 1 moves; the recurrence keeps `error` inside (-dx, dy], so
     // after k moves the number of x moves is within (max(dx, dy) + drift) / (dx + dy) < 1.3 of k dx / (dx + dy) (the float drift of
     // `error` over a walk is below a quarter of a cell), and n - 1 = extra + |floor x1 - x| + |floor y1 - y| (RayIterator.java:75-100):
@@ -99,6 +103,28 @@ __device__ __forceinline__ RayMeta ray_meta(const GridDev &g, const RayIn &ray, 
     const int32_t moves = mt.n_eff > 0 ? mt.n_eff - 1 : 0;
     mt.hx = min(max(r.x + r.x_inc * (int32_t)min((int64_t)moves, ax), 0), g.W - 1);
     mt.hy = min(max(r.y + r.y_inc * (int32_t)min((int64_t)moves, ay), 0), g.H - 1);
+    return mt;
+}
+// ray_init + the parts of the walk that do not depend on the recurrence
+__device__ __forceinline__ RayMeta ray_meta(const GridDev &g, const RayIn &ray, RayDev &r) {
+    const int32_t n_eff = ray_walk_init(g, ray, r);
+    return ray_meta_rest(g, ray, r, n_eff);
+}
+// lane l's RayMeta, l wave-uniform: every wavefront that consumes decision words keeps the metas of its workgroup's rays in its own
+// lanes (ray q in lane q) and takes the one it works on from there -- no LDS copy, nothing to wait for
+__device__ __forceinline__ RayMeta ray_meta_of_lane(const RayMeta &m, int32_t l) {
+    RayMeta o;
+#define GMS_RL_(F) o.F = __builtin_amdgcn_readlane(m.F, l)
+#define GMS_RLF_(F) o.F = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m.F), l))
+    GMS_RL_(x0); GMS_RL_(y0); GMS_RL_(x_inc); GMS_RL_(y_inc); GMS_RL_(n_eff); GMS_RL_(hit); GMS_RL_(hx); GMS_RL_(hy);
+    GMS_RLF_(sx); GMS_RLF_(sy); GMS_RLF_(measured);
+#undef GMS_RL_
+#undef GMS_RLF_
+    return o;
+}
+__device__ __forceinline__ RayMeta ray_meta_none() {
+    RayMeta mt;
+    mt.n_eff = 0; mt.x0 = mt.y0 = mt.x_inc = mt.y_inc = mt.hit = mt.hx = mt.hy = 0; mt.sx = mt.sy = mt.measured = 0.0f;
     return mt;
 }
 // encoded box of one ray's walk (all zero: the ray visits nothing)
@@ -227,73 +253,102 @@ __device__ __forceinline__ int32_t ray_phase_b(const GridDev &g, const RayMeta &
 // all rays round-robin (block-major, the order in which the producer publishes them) and run phase B as soon as a
 // block's words are there, so the cell work -- distance, sensor class, count atomics -- hides under the recurrence
 // instead of following it (measured at C3: 17.4 -> see DESIGN.md).  The producer never waits for a consumer.
-// (bx, by) = workgroup / map index and `smem` = the dynamic LDS: the body is shared by k_raycast and by the
-// launch that runs the ray cast beside the weight normalisation (gms_fused_kernels.hip); pose_lds, when given,
-// replaces poses[] (a pose the workgroup has just folded itself).
+// (bx, by) = workgroup / map index and `smem` = the dynamic LDS: the body is shared by k_raycast, k_raycast_apply and by the
+// launches that run the ray cast beside the weight normalisation (gms_fused_kernels.hip), where the pose is one every
+// thread of the workgroup has just folded itself.
+// The part of a ray workgroup's set-up that does not depend on the pose, for the caller to run BEFORE whatever produces the pose
+// (the weighted-pose fold of the paired launches; the pose load of the stand-alone ones): the decision slots are cleared and
+// lane q of EVERY wavefront loads the beam of ray q, so the load's round trip is over when the pose is there.  The caller puts
+// one workgroup barrier between this and the body (the fold's barriers serve): no slot is published or polled before it.
+struct RayPre {
+    gms_beam beam;
+    bool in;               // this lane holds a ray of the scan
+};
+template <int RC_RAYS, int NWAVES>
+__device__ __forceinline__ RayPre
+raycast_prologue(const gms_beam *__restrict__ beams, int32_t B, int32_t beam_stride, const RayIn *__restrict__ single,
+                 int32_t nw_max, uint32_t bx, uint32_t by, unsigned char *smem) {
+    uint64_t *s_slots = reinterpret_cast<uint64_t *>(smem);            // [nw_max][RC_RAYS]
+    const int32_t lane = threadIdx.x & 63;
+    const int32_t b = (int32_t)bx * RC_RAYS + lane;
+    RayPre pre;
+    pre.in = lane < RC_RAYS && b < B;
+    pre.beam.local_x = pre.beam.local_y = pre.beam.distance = 0.0; pre.beam.hit = 0;
+    if (pre.in && !single) {
+        const gms_beam *src = beams + (size_t)by * beam_stride + b;
+        pre.beam.local_x = src->local_x; pre.beam.local_y = src->local_y; pre.beam.distance = src->distance; pre.beam.hit = src->hit;
+    }
+    for (int32_t i = threadIdx.x; i < nw_max * RC_RAYS; i += NWAVES * 64) s_slots[i] = 0ull;
+    return pre;
+}
+
+// The set-up is split between the wavefronts.  The producer lanes form their rays (make_ray), run ray_init and take the number of
+// steps (ray_walk_init) -- error, dx, dy and n_eff are all the recurrence needs -- and start walking at once.  The rest of a ray's
+// RayMeta (the constants of the cell arithmetic, the walk's box: 64-bit and double arithmetic the walk never reads) is formed by
+// every CONSUMER wavefront for itself, from the same beam and the same pose in its own lanes: the same instructions on the same
+// inputs, hence the same bits, and nothing travels through LDS -- no s_meta, no set-up barrier; the consumers find the producer
+// through the slots alone.  (The pose's trig is one v-instruction stream per wavefront whichever lanes are active, so each
+// wavefront taking it for itself costs the producer nothing.)
+// `pose`: the three floats of the pose in registers (folded by every thread itself, or loaded from poses[]).
 template <bool TRACE, int RC_RAYS, int NWAVES = RC_RAYS>
 __device__ __forceinline__ void
-raycast_body(const GridDev &g, const gms_beam *__restrict__ beams, int32_t B, int32_t beam_stride,
-             const float *__restrict__ poses, int32_t pose_stride, const RayIn *__restrict__ single,
+raycast_body(const GridDev &g, const RayPre &pre, const float (&pose)[3], int32_t B, const RayIn *__restrict__ single,
              uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox, int32_t *__restrict__ t_cells,
-             uint8_t *__restrict__ t_cls, int32_t cap, int32_t *__restrict__ t_counts, int32_t nw_max,
-             uint32_t bx, uint32_t by, unsigned char *smem, const float *pose_lds, int32_t first_blk = 0) {
+             uint8_t *__restrict__ t_cls, int32_t cap, int32_t *__restrict__ t_counts,
+             uint32_t bx, uint32_t by, unsigned char *smem, int32_t first_blk = 0) {
     // first_blk = 1: the rays' first 64 steps (block 0) are counted by the near-field workgroups (raycast_near_body)
+    static_assert(NWAVES >= 2 && RC_RAYS <= 64, "one producer wavefront (a lane per ray) and at least one consumer");
     uint64_t *s_slots = reinterpret_cast<uint64_t *>(smem);            // [nw_max][RC_RAYS]
-    __shared__ RayMeta s_meta[RC_RAYS];
     __shared__ int32_t s_count[RC_RAYS];
 
     const int32_t mi = (int32_t)by;
     const int32_t lane = threadIdx.x & 63;
     const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int32_t i = threadIdx.x; i < nw_max * RC_RAYS; i += NWAVES * 64) s_slots[i] = 0ull;
     RayDev r;
     r.dx = r.dy = r.error = 0.0f; r.x = r.y = r.x_inc = r.y_inc = r.n = 0;
+    RayIn ray;
+    ray.sx = ray.sy = ray.ex = ray.ey = ray.measured = 0.0f; ray.hit = 0;
     int32_t my_n_eff = 0;
-    if (wave == 0 && lane < RC_RAYS) {
-        const int32_t b = (int32_t)bx * RC_RAYS + lane;
-        RayMeta mt;
-        mt.n_eff = 0; mt.x0 = mt.y0 = mt.x_inc = mt.y_inc = mt.hit = 0; mt.sx = mt.sy = mt.measured = 0.0f;
-        if (b < B) {
-            RayIn ray;
-            if (single) ray = *single;
-            else ray = make_ray(g, beams[(size_t)mi * beam_stride + b], pose_lds ? pose_lds : poses + (size_t)pose_stride * mi);
-            mt = ray_meta(g, ray, r);
-        }
-        my_n_eff = mt.n_eff;
-        s_meta[lane] = mt;
-        s_count[lane] = 0;
+    if (pre.in) {
+        if (single) ray = *single;
+        else ray = make_ray(g, pre.beam, pose);
+        my_n_eff = ray_walk_init(g, ray, r);
     }
-    __syncthreads();
-    GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 2);
-    if (!TRACE && first_blk == 0 && wave == (NWAVES > 1 ? 1 : 0)) {
-        // The scan's dirty box from the rays' boxes, up front (with near-field workgroups in the launch, they raise it for their
-        // wedges).  On a CONSUMER wavefront, behind the set-up barrier: a few hundred workgroups raise the same four words, the
-        // requests queue up on their way to the memory-side atomic unit, and the wavefront that issues them is held up with them
-        // (the barrier itself waits for LDS only).  Issued by the producer's wavefront in front of the barrier they delayed the
-        // walk: measured 0.7 us of k_norm_raycast on a 360-beam scan (c2_step_timeline.txt of that build: rays set up 2.7-6 us
-        // after the pose).
-        int32_t hb[4] = { 0, 0, 0, 0 };
-        if (lane < RC_RAYS) ray_box(g, s_meta[lane], hb);
-        bbox_raise_wave(hb, lane, bbox + 4 * mi);
+    if (TRACE) {
+        if (threadIdx.x < RC_RAYS) s_count[threadIdx.x] = 0;
+        __syncthreads();
     }
     if (wave == 0) {
+        GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 2);
         if (lane < RC_RAYS) {
             RayWalk wk = ray_walk_begin(r);
             ray_phase_a(wk, 0, (my_n_eff + 31) >> 5, s_slots, RC_RAYS, lane);
         }
         GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 3);
     } else {
-        int32_t nblk_max = 0;
-#pragma unroll
-        for (int q = 0; q < RC_RAYS; q++) nblk_max = max(nblk_max, (s_meta[q].n_eff + 63) >> 6);
+        const RayMeta mine = pre.in ? ray_meta_rest(g, ray, r, my_n_eff) : ray_meta_none();      // ray q's in lane q
+        if (!TRACE && first_blk == 0 && wave == 1) {
+            // The scan's dirty box from the rays' boxes, up front (with near-field workgroups in the launch, they raise it for their
+            // wedges).  On a CONSUMER wavefront: a few hundred workgroups raise the same four words, the requests queue up on their
+            // way to the memory-side atomic unit, and the wavefront that issues them is held up with them.  Issued by the
+            // producer's wavefront they delayed the walk: measured 0.7 us of k_norm_raycast on a 360-beam scan.
+            int32_t hb[4];
+            ray_box(g, mine, hb);
+            bbox_raise_wave(hb, lane, bbox + 4 * mi);
+        }
+        int32_t nblk_max = (mine.n_eff + 63) >> 6;
+#define GMS_STEP_(O) nblk_max = max(nblk_max, wave_xor<O>(nblk_max));
+        GMS_BUTTERFLY(GMS_STEP_)
+#undef GMS_STEP_
+        nblk_max = __builtin_amdgcn_readfirstlane(nblk_max);
         constexpr int32_t NC = NWAVES - 1;
         for (int32_t q = wave - 1 + first_blk * RC_RAYS; q < nblk_max * RC_RAYS; q += NC) {
-            const int32_t blk = q / RC_RAYS, ray = q - blk * RC_RAYS;
-            const RayMeta mt = s_meta[ray];
+            const int32_t blk = q / RC_RAYS, rq = q - blk * RC_RAYS;
+            const RayMeta mt = ray_meta_of_lane(mine, rq);
             if (blk * 64 >= mt.n_eff) continue;
-            const int32_t n = ray_phase_b<TRACE>(g, mt, s_slots, RC_RAYS, ray, blk, lane, TRACE ? nullptr : cnt + (size_t)mi * g.cells, TRACE ? nullptr : bbox + 4 * mi,
-                                                 (int32_t)bx * RC_RAYS + ray, t_cells, t_cls, cap);
-            if (TRACE && lane == 0) atomicAdd(&s_count[ray], n);
+            const int32_t n = ray_phase_b<TRACE>(g, mt, s_slots, RC_RAYS, rq, blk, lane, TRACE ? nullptr : cnt + (size_t)mi * g.cells, TRACE ? nullptr : bbox + 4 * mi,
+                                                 (int32_t)bx * RC_RAYS + rq, t_cells, t_cls, cap);
+            if (TRACE && lane == 0) atomicAdd(&s_count[rq], n);
         }
         GMS_STAMP_T(64, GMS_STAMP_ROW(2, blockIdx.x), 4);
     }
@@ -326,76 +381,100 @@ raycast_body(const GridDev &g, const gms_beam *__restrict__ beams, int32_t B, in
 #define RCN_LDS_BYTES (2 * RCN_RAYS * 8 + RCN_TILE_CELLS * 2)
 static_assert(RCN_RAYS >= 1 && RCN_RAYS <= 64, "the near-field producer is one wavefront, a lane per ray");
 
+// the pose-independent part of a near-field workgroup's set-up (see raycast_prologue): slots and the WHOLE count tile cleared --
+// where the tile lies depends on the pose, clearing it does not: 24 KiB, six 16-byte stores per thread -- and the wedge's beams
+// loaded, lane q of every wavefront beam q
+__device__ __forceinline__ RayPre
+raycast_near_prologue(const gms_beam *__restrict__ beams, int32_t B, int32_t beam_stride, uint32_t bx, uint32_t by, unsigned char *smem) {
+    uint64_t *s_slots = reinterpret_cast<uint64_t *>(smem);                                   // [2][RCN_RAYS]
+    uint4 *s_tile4 = reinterpret_cast<uint4 *>(s_slots + 2 * RCN_RAYS);                       // [RCN_TILE_CELLS / 8]
+    static_assert((2 * RCN_RAYS * 8) % 16 == 0 && RCN_TILE_CELLS % 8 == 0, "the tile is cleared in 16-byte stores");
+    const int32_t lane = threadIdx.x & 63;
+    const int32_t b = (int32_t)bx * RCN_RAYS + lane;
+    RayPre pre;
+    pre.in = lane < RCN_RAYS && b < B;
+    pre.beam.local_x = pre.beam.local_y = pre.beam.distance = 0.0; pre.beam.hit = 0;
+    if (pre.in) {
+        const gms_beam *src = beams + (size_t)by * beam_stride + b;
+        pre.beam.local_x = src->local_x; pre.beam.local_y = src->local_y; pre.beam.distance = src->distance; pre.beam.hit = src->hit;
+    }
+    for (int32_t i = threadIdx.x; i < 2 * RCN_RAYS; i += blockDim.x) s_slots[i] = 0ull;
+    for (int32_t i = threadIdx.x; i < RCN_TILE_CELLS / 8; i += blockDim.x) s_tile4[i] = make_uint4(0u, 0u, 0u, 0u);
+    return pre;
+}
+
+// the wedge's count tile from the rays a wavefront holds in its lanes (ray q in lane q): every wavefront forms it for itself
+__device__ __forceinline__ CountTile
+near_tile(const GridDev &g, const RayDev &r, int32_t n_eff, uint32_t *s_tile) {
+    int32_t bx0 = INT32_MAX, by0 = INT32_MAX, bx1 = INT32_MIN, by1 = INT32_MIN;
+    if (n_eff > 0) {
+        // the first 64 steps: at most 63 moves from the start cell, split between x and y roughly as dx : dy (+2 for
+        // the rounding of the recurrence); a cell outside the box takes the direct-atomic path: the box is a hint
+        const int32_t steps = min(n_eff, 64) - 1;
+        const float tot = r.dx + r.dy;
+        const int32_t mx = tot > 0.0f ? min(steps, (int32_t)((float)steps * (r.dx / tot)) + 2) : 0;
+        const int32_t my = tot > 0.0f ? min(steps, (int32_t)((float)steps * (r.dy / tot)) + 2) : 0;
+        const int32_t ex = r.x + r.x_inc * mx, ey = r.y + r.y_inc * my;
+        bx0 = max(min(r.x, ex), 0); bx1 = min(max(r.x, ex), g.W - 1);
+        by0 = max(min(r.y, ey), 0); by1 = min(max(r.y, ey), g.H - 1);
+    }
+#define GMS_STEP_(O) { bx0 = min(bx0, wave_xor<O>(bx0)); by0 = min(by0, wave_xor<O>(by0)); bx1 = max(bx1, wave_xor<O>(bx1)); by1 = max(by1, wave_xor<O>(by1)); }
+    GMS_BUTTERFLY(GMS_STEP_)
+#undef GMS_STEP_
+    bx0 = __builtin_amdgcn_readfirstlane(bx0); by0 = __builtin_amdgcn_readfirstlane(by0);
+    bx1 = __builtin_amdgcn_readfirstlane(bx1); by1 = __builtin_amdgcn_readfirstlane(by1);
+    CountTile tile;
+    tile.cells = s_tile; tile.x0 = bx0; tile.y0 = by0;
+    tile.w = bx1 >= bx0 ? bx1 - bx0 + 1 : 0;
+    tile.h = by1 >= by0 ? by1 - by0 + 1 : 0;
+    // 8 bits per count: RCN_RAYS * (1 + extra) visits of one cell at most
+    if ((int64_t)tile.w * tile.h > RCN_TILE_CELLS || RCN_RAYS * (1 + g.extra) > 255) tile.w = tile.h = 0;       // direct atomics
+    return tile;
+}
+
+// Between raycast_near_prologue and this body the caller has one workgroup barrier (the fold's; see raycast_body for the split
+// of the set-up: here, too, the producer walks as soon as it has error, dx, dy and the step counts, and the consumers form
+// the metas and the tile's box for themselves; the producer forms the box after its walk, for the flush).
 __device__ __forceinline__ void
-raycast_near_body(const GridDev &g, const gms_beam *__restrict__ beams, int32_t B, int32_t beam_stride,
-                  const float *__restrict__ poses, int32_t pose_stride, uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox,
-                  uint32_t bx, uint32_t by, unsigned char *smem, const float *pose_lds) {
+raycast_near_body(const GridDev &g, const RayPre &pre, const float (&pose)[3], uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox,
+                  uint32_t by, unsigned char *smem) {
     uint64_t *s_slots = reinterpret_cast<uint64_t *>(smem);                                   // [2][RCN_RAYS]
     uint32_t *s_tile = reinterpret_cast<uint32_t *>(s_slots + 2 * RCN_RAYS);                  // [RCN_TILE_CELLS / 2]
-    __shared__ RayMeta s_nmeta[RCN_RAYS];
-    __shared__ int32_t s_nbox[4];                                                             // wedge box x0, y0, x1, y1 (inclusive)
     const int32_t mi = (int32_t)by;
     const int32_t lane = threadIdx.x & 63;
     const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int32_t nwaves = __builtin_amdgcn_readfirstlane((int32_t)(blockDim.x >> 6));
-    for (int32_t i = threadIdx.x; i < 2 * RCN_RAYS; i += blockDim.x) s_slots[i] = 0ull;
     RayDev r;
     r.dx = r.dy = r.error = 0.0f; r.x = r.y = r.x_inc = r.y_inc = r.n = 0;
-    int32_t my_nwords = 0;
-    if (wave == 0) {
-        const int32_t b = (int32_t)bx * RCN_RAYS + lane;
-        RayMeta mt;
-        mt.n_eff = 0; mt.x0 = mt.y0 = mt.x_inc = mt.y_inc = mt.hit = 0; mt.sx = mt.sy = mt.measured = 0.0f;
-        int32_t bx0 = INT32_MAX, by0 = INT32_MAX, bx1 = INT32_MIN, by1 = INT32_MIN;
-        if (lane < RCN_RAYS && b < B) {
-            const RayIn ray = make_ray(g, beams[(size_t)mi * beam_stride + b], pose_lds ? pose_lds : poses + (size_t)pose_stride * mi);
-            mt = ray_meta(g, ray, r);
-            if (mt.n_eff > 0) {
-                // the first 64 steps: at most 63 moves from the start cell, split between x and y roughly as dx : dy (+2 for
-                // the rounding of the recurrence); a cell outside the box takes the direct-atomic path: the box is a hint
-                const int32_t steps = min(mt.n_eff, 64) - 1;
-                const float tot = r.dx + r.dy;
-                const int32_t mx = tot > 0.0f ? min(steps, (int32_t)((float)steps * (r.dx / tot)) + 2) : 0;
-                const int32_t my = tot > 0.0f ? min(steps, (int32_t)((float)steps * (r.dy / tot)) + 2) : 0;
-                const int32_t ex = mt.x0 + mt.x_inc * mx, ey = mt.y0 + mt.y_inc * my;
-                bx0 = max(min(mt.x0, ex), 0); bx1 = min(max(mt.x0, ex), g.W - 1);
-                by0 = max(min(mt.y0, ey), 0); by1 = min(max(mt.y0, ey), g.H - 1);
-            }
-        }
-        my_nwords = min((mt.n_eff + 31) >> 5, 2);
-        if (lane < RCN_RAYS) s_nmeta[lane] = mt;
-#define GMS_STEP_(O) { bx0 = min(bx0, wave_xor<O>(bx0)); by0 = min(by0, wave_xor<O>(by0)); bx1 = max(bx1, wave_xor<O>(bx1)); by1 = max(by1, wave_xor<O>(by1)); }
-        GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-        if (lane == 0) { s_nbox[0] = bx0; s_nbox[1] = by0; s_nbox[2] = bx1; s_nbox[3] = by1; }
+    RayIn ray;
+    ray.sx = ray.sy = ray.ex = ray.ey = ray.measured = 0.0f; ray.hit = 0;
+    int32_t my_n_eff = 0;
+    if (pre.in) {
+        ray = make_ray(g, pre.beam, pose);
+        my_n_eff = ray_walk_init(g, ray, r);
     }
-    __syncthreads();
     CountTile tile;
-    tile.cells = s_tile; tile.x0 = s_nbox[0]; tile.y0 = s_nbox[1];
-    tile.w = s_nbox[2] >= s_nbox[0] ? s_nbox[2] - s_nbox[0] + 1 : 0;
-    tile.h = s_nbox[3] >= s_nbox[1] ? s_nbox[3] - s_nbox[1] + 1 : 0;
-    // 8 bits per count: RCN_RAYS * (1 + extra) visits of one cell at most
-    if ((int64_t)tile.w * tile.h > RCN_TILE_CELLS || RCN_RAYS * (1 + g.extra) > 255) tile.w = tile.h = 0;       // direct atomics
-    const int32_t tcells = tile.w * tile.h;
-    for (int32_t i = threadIdx.x; i < (tcells + 1) / 2; i += blockDim.x) s_tile[i] = 0u;
-    __syncthreads();
-    GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 9);
     if (wave == 0) {
+        GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 9);
+        const int32_t my_nwords = min((my_n_eff + 31) >> 5, 2);
         RayWalk wk = ray_walk_begin(r);
         if (lane < RCN_RAYS && my_nwords > 0) ray_phase_a(wk, 0, my_nwords, s_slots, RCN_RAYS, lane);
+        tile = near_tile(g, r, my_n_eff, s_tile);
     } else {
+        const RayMeta mine = pre.in ? ray_meta_rest(g, ray, r, my_n_eff) : ray_meta_none();      // ray q's in lane q
+        tile = near_tile(g, r, my_n_eff, s_tile);
         if (wave == 1) {
             // the scan's dirty box from the WHOLE walks of this wedge's rays (the far-field workgroups of these rays leave it to this
-            // one), by a consumer wavefront behind the barriers: see raycast_body
-            int32_t hb[4] = { 0, 0, 0, 0 };
-            if (lane < RCN_RAYS) ray_box(g, s_nmeta[lane], hb);
+            // one), by a consumer wavefront: see raycast_body
+            int32_t hb[4];
+            ray_box(g, mine, hb);
             bbox_raise_wave(hb, lane, bbox + 4 * mi);
         }
-        for (int32_t ray = wave - 1; ray < RCN_RAYS; ray += nwaves - 1) {
-            RayMeta mt = s_nmeta[ray];
+        for (int32_t rq = wave - 1; rq < RCN_RAYS; rq += nwaves - 1) {
+            RayMeta mt = ray_meta_of_lane(mine, rq);
             if (mt.n_eff <= 0) continue;
             mt.n_eff = min(mt.n_eff, 64);                      // block 0 only: the far-field workgroups count the rest
-            ray_phase_b<false>(g, mt, s_slots, RCN_RAYS, ray, 0, lane, cnt + (size_t)mi * g.cells, bbox + 4 * mi, 0, nullptr, nullptr, 0, tile, 0);
+            ray_phase_b<false>(g, mt, s_slots, RCN_RAYS, rq, 0, lane, cnt + (size_t)mi * g.cells, bbox + 4 * mi, 0, nullptr, nullptr, 0, tile, 0);
         }
     }
     __syncthreads();
@@ -430,13 +509,15 @@ k_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t beam
           uint8_t *__restrict__ t_cls, int32_t cap, int32_t *__restrict__ t_counts, int32_t nw_max, uint32_t n_near_blocks) {
     extern __shared__ __align__(16) unsigned char smem[];
     // grid.x = ray blocks + near-field blocks (the latter only for the count form with four rays per workgroup)
-    if (!TRACE && RC_RAYS == 4 && n_near_blocks && blockIdx.x >= gridDim.x - n_near_blocks) {
-        raycast_near_body(g, beams, B, beam_stride, poses, pose_stride, cnt, bbox, blockIdx.x - (gridDim.x - n_near_blocks), blockIdx.y, smem,
-                          nullptr);
-        return;
-    }
-    raycast_body<TRACE, RC_RAYS>(g, beams, B, beam_stride, poses, pose_stride, single, cnt, bbox, t_cells, t_cls, cap, t_counts,
-                                 nw_max, blockIdx.x, blockIdx.y, smem, nullptr, n_near_blocks ? 1 : 0);
+    const bool near = !TRACE && RC_RAYS == 4 && n_near_blocks && blockIdx.x >= gridDim.x - n_near_blocks;
+    const RayPre pre = near ? raycast_near_prologue(beams, B, beam_stride, blockIdx.x - (gridDim.x - n_near_blocks), blockIdx.y, smem)
+                            : raycast_prologue<RC_RAYS, RC_RAYS>(beams, B, beam_stride, single, nw_max, blockIdx.x, blockIdx.y, smem);
+    float pose[3] = { 0.0f, 0.0f, 0.0f };
+    if (!single) { const float *p = poses + (size_t)pose_stride * blockIdx.y; pose[0] = p[0]; pose[1] = p[1]; pose[2] = p[2]; }
+    __syncthreads();                                        // slots (and tile) cleared
+    if (near) { raycast_near_body(g, pre, pose, cnt, bbox, blockIdx.y, smem); return; }
+    raycast_body<TRACE, RC_RAYS>(g, pre, pose, B, single, cnt, bbox, t_cells, t_cls, cap, t_counts, blockIdx.x, blockIdx.y, smem,
+                                 n_near_blocks ? 1 : 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1097,13 +1178,17 @@ k_raycast_apply(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
                 int32_t pose_stride, uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox_next, int32_t nw_max, uint32_t n_ray_blocks,
                 uint32_t n_near_blocks, double *__restrict__ logd, uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend) {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (blockIdx.x < n_ray_blocks)
-        raycast_body<false, 4>(g, beams, B, beam_stride, poses, pose_stride, nullptr, cnt, bbox_next, nullptr, nullptr, 0, nullptr, nw_max,
-                               blockIdx.x, 0, smem, nullptr, n_near_blocks ? 1 : 0);
-    else if (blockIdx.x < n_ray_blocks + n_near_blocks)
-        raycast_near_body(g, beams, B, beam_stride, poses, pose_stride, cnt, bbox_next, blockIdx.x - n_ray_blocks, 0, smem, nullptr);
-    else
+    if (blockIdx.x >= n_ray_blocks + n_near_blocks) {
         apply_body(g, logd, cnt_pend, bbox_pend, nullptr, blockIdx.x - n_ray_blocks - n_near_blocks, 0, gridDim.x - n_ray_blocks - n_near_blocks);
+        return;
+    }
+    const bool near = blockIdx.x >= n_ray_blocks;
+    const RayPre pre = near ? raycast_near_prologue(beams, B, beam_stride, blockIdx.x - n_ray_blocks, 0, smem)
+                            : raycast_prologue<4, 4>(beams, B, beam_stride, nullptr, nw_max, blockIdx.x, 0, smem);
+    const float pose[3] = { poses[0], poses[1], poses[2] };
+    __syncthreads();                                        // slots (and tile) cleared
+    if (near) raycast_near_body(g, pre, pose, cnt, bbox_next, 0, smem);
+    else raycast_body<false, 4>(g, pre, pose, B, nullptr, cnt, bbox_next, nullptr, nullptr, 0, nullptr, blockIdx.x, 0, smem, n_near_blocks ? 1 : 0);
 }
 
 // scoring factors from an existing likelihood field (upload / copy), and the table's neutral border (fac_index)
