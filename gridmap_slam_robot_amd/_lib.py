@@ -63,6 +63,17 @@ class GmsView(C.Structure):
     ]
 
 
+class GmsClearance(C.Structure):
+    """gms_clearance: a rectangle of a map as squared distances to the nearest obstacle (gridmapslam.h "clearance fields")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("max_radius", C.c_int32), ("mode", C.c_int32), ("filter", C.c_int32),
+    ]
+
+
+CLEARANCE = GmsClearance
+GMS_CLEAR_OCCUPIED, GMS_CLEAR_NOT_FREE = 0, 1
+GMS_CLEAR_FAR, GMS_CLEAR_OUTSIDE = 0xFFFF, 0xFFFE
 GMS_VIEW_GREY8, GMS_VIEW_PACKED32 = 0, 1
 GMS_VIEW_LOG, GMS_VIEW_LIKELIHOOD = 0, 1
 GMS_VIEW_STRONGEST = -1
@@ -262,6 +273,14 @@ def load() -> C.CDLL:
     sig("gms_slam_cast", C.c_int, vp, i32, i32, vp, i32, vp, vp)
     sig("gms_slam_cast_dev", C.c_int, vp, i32, i32, vp, i32, vp, vp)
     sig("gms_map_cast_plane_builds", C.c_int, vp, C.POINTER(C.c_int64))
+    cl = C.POINTER(GmsClearance)
+    sig("gms_clearance_size", C.c_int, cl, vp, vp, vp)
+    sig("gms_map_clearance", C.c_int, vp, i32, cl, vp)
+    sig("gms_map_clearance_dev", C.c_int, vp, i32, cl, vp)
+    sig("gms_map_clearance_poses", C.c_int, vp, i32, vp, i32, i32, i32, vp)
+    sig("gms_map_clearance_poses_dev", C.c_int, vp, i32, vp, i32, i32, i32, vp)
+    sig("gms_slam_clearance", C.c_int, vp, i32, cl, vp, vp)
+    sig("gms_slam_clearance_dev", C.c_int, vp, i32, cl, vp, vp)
     _lib = L
     return L
 

@@ -186,7 +186,7 @@ k_cast_slam(GridDev g, SlamBufs sb, int64_t code_words, const PfStatsDev *__rest
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 // the plane of logData as it stands: the deferred apply pass first (what gms_map_download_log opens with), then the pre-pass unless the
 // handle still holds the plane of this logData
-static int cast_plane(gms_map *m) {
+int gms_cast_plane(gms_map *m) {
     gms_flush_apply(m);
     const int32_t wpr64 = (m->gd.W + 63) / 64;
     if (!m->d_cast_plane) {
@@ -211,7 +211,7 @@ static int cast_plane(gms_map *m) {
 // P poses at d_poses (pose_stride floats apart) cast d_probes [B] in map mi (per_map: pose i in map i) into d_out [P][B]
 static int cast_launch(gms_map *m, int32_t mi, bool per_map, const float *d_poses, int32_t pose_stride, int32_t P, const gms_beam *d_probes, int32_t B,
                        gms_cast_hit *d_out) {
-    int rc = cast_plane(m);
+    int rc = gms_cast_plane(m);
     if (rc) return rc;
     const int64_t plane_stride = (int64_t)m->gd.H * m->cast_wpr;
     const int64_t lds_words = m->cast_walk_mem ? 0 : std::min<int64_t>(CAST_LDS_CAP / 4, plane_stride);

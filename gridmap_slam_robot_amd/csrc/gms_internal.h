@@ -121,6 +121,9 @@ struct gms_map {
     int32_t cast_plane_current;   // it is the plane of logData as it stands (cleared by the transitions below that move logData)
     int32_t cast_walk_mem;    // casts walk memory even where their window or class plane fits the LDS (GMS_CAST_WALK=mem: tests)
     int64_t cast_plane_builds;    // launches of the plane's pre-pass so far (tests: an unchanged map is not packed again)
+    uint32_t *d_clear_plane;  // [n_maps][H][cast_wpr] the second plane of the clearance fields (gms_clearance.hip): !(logData < 0), same layout; allocated by the first GMS_CLEAR_NOT_FREE field
+    int32_t clear_plane_current;  // it is the plane of logData as it stands (cleared wherever cast_plane_current is)
+    uint32_t *d_clear_scratch;    // [H][cast_wpr] a gms_slam's clearance: the shown particle's plane, packed per request
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -159,17 +162,18 @@ struct gms_map {
 // ---- map state transitions (need_full_build, fac_current, lik_stale, apply_pending, bbox_dirty, bbox_cur): each is named for
 // what happened and sets every field that event affects ----
 // logData (or, gms_map_upload_likelihood, the field) was replaced: the next rebuild covers every tile and leaves none alone
-static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; m->cast_plane_current = 0; }
+static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; m->cast_plane_current = 0; m->clear_plane_current = 0; }
 // likelihoodData is up to date everywhere (made so, or about to be replaced wholesale)
 static inline void map_lik_current(gms_map *m) { m->lik_stale = 0; }
 // an immediate apply pass added the counts to logData without a rebuild having seen them
-static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; m->cast_plane_current = 0; }
+static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; m->cast_plane_current = 0; m->clear_plane_current = 0; }
 // a deferred apply pass has been enqueued: the box of the scan it applied is the current half now
 static inline void gms_apply_done(gms_map *m) {
     m->bbox_cur = 1 - m->bbox_cur;
     m->bbox_dirty = 0;
     m->apply_pending = 0;
     m->cast_plane_current = 0;         // (logData moved)
+    m->clear_plane_current = 0;
 }
 // the scan just cast (and already in the likelihood field) keeps its counts for a later launch
 static inline void gms_defer_apply(gms_map *m) {
@@ -481,6 +485,9 @@ void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out
 int gms_view_check(const gms_view *v, int32_t W, int32_t H, const char *what, int64_t *bytes);
 int gms_view_staging(gms_map *m, int64_t image_bytes, unsigned char **base);
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
+// the casts' bit plane (logData > 0) of logData as it stands, on the handle: the deferred apply pass first, then the pre-pass unless the
+// handle still holds the plane of this logData (gms_cast.hip; the clearance fields of GMS_CLEAR_OCCUPIED read the same plane)
+int gms_cast_plane(gms_map *m);
 
 void gms_launch_pf_init(gms_pf *pf);
 void gms_launch_pf_pose_trig(gms_pf *pf, const float *d_src);

@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
-__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual"]
+__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -153,6 +153,25 @@ def _cast_device_out(out, n: int) -> int:
     if out.numel() * out.element_size() < 16 * n:
         raise ValueError(f"cast: out holds {out.numel() * out.element_size()} bytes, the records need {16 * n}")
     return int(out.data_ptr())
+
+
+def _clearance_args(W: int, H: int, rect, max_radius: int, not_free: bool, filter: int = 0):
+    """(gms_clearance, output shape, bytes) of a clearance field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
+    c = _lib.GmsClearance(x0, y0, w, h, int(max_radius), _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED, int(filter))
+    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    check(load().gms_clearance_size(C.byref(c), C.byref(ow), C.byref(oh), C.byref(nbytes)))
+    return c, (oh.value, ow.value), nbytes.value
+
+
+def clearance_metres(d2, resolution: float) -> np.ndarray:
+    """Clearance values (GridMap.clearance / clearance_poses: squared cell distances as uint16) as metres, float64: sqrt(d2) *
+    resolution; GMS_CLEAR_FAR (beyond the radius, or no obstacle at all) becomes inf, GMS_CLEAR_OUTSIDE (a pose off the map) nan."""
+    a = np.asarray(d2)
+    out = np.sqrt(a.astype(np.float64)) * float(resolution)
+    out[a == _lib.GMS_CLEAR_FAR] = np.inf
+    out[a == _lib.GMS_CLEAR_OUTSIDE] = np.nan
+    return out
 
 
 class GridMap:
@@ -314,6 +333,41 @@ class GridMap:
         n = C.c_int64(0)
         check(load().gms_map_cast_plane_builds(self._h, C.byref(n)))
         return int(n.value)
+
+    def clearance(self, rect=None, max_radius: int = 25, not_free: bool = False, mi: int = 0, out=None):
+        """The clearance field (gridmapslam.h "clearance fields") of map mi: for every cell of rect = (x0, y0, w, h) (None: the whole
+        map) the squared distance in cells to the nearest obstacle cell of the whole map -- logData > 0, or with not_free every cell
+        that is not known free, !(logData < 0) -- as uint16 [h][w]; GMS_CLEAR_FAR (0xFFFF) beyond max_radius (1 .. 255 cells).
+        Returns a numpy array (synchronises); with out -- a contiguous torch device tensor of h * w * 2 bytes -- the field is written
+        there on the handle's stream, nothing is synchronised, and out is returned (clearance_dev).  Metres: clearance_metres()."""
+        c, shape, nbytes = _clearance_args(self.W, self.H, rect, max_radius, not_free)
+        if out is not None:
+            check(load().gms_map_clearance_dev(self._h, int(mi), C.byref(c), C.c_void_p(_view_device_out(out, nbytes))))
+            return out
+        field = np.empty(shape, dtype=np.uint16)
+        check(load().gms_map_clearance(self._h, int(mi), C.byref(c), ptr(field)))
+        return field
+
+    def clearance_dev(self, out, rect=None, max_radius: int = 25, not_free: bool = False, mi: int = 0):
+        """clearance() into out, a contiguous torch device tensor of h * w * 2 bytes, on the handle's stream"""
+        return self.clearance(rect, max_radius, not_free, mi, out)
+
+    def clearance_poses(self, poses, max_radius: int = 25, not_free: bool = False, mi: int = 0) -> np.ndarray:
+        """The clearance under each of poses [P][3] (x, y, theta; theta is not read) without making a field: uint16 [P], the field's
+        value at the pose's cell -- (int)((x - position) / resolution) as probabilityOf takes it -- or GMS_CLEAR_OUTSIDE (0xFFFE)
+        where that cell is off the map."""
+        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        out = np.empty(len(p), dtype=np.uint16)
+        check(load().gms_map_clearance_poses(self._h, int(mi), ptr(p), len(p), int(max_radius),
+                                             _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED, ptr(out)))
+        return out
+
+    def clearance_poses_dev(self, dev_poses: int, P: int, out, max_radius: int = 25, not_free: bool = False, mi: int = 0):
+        """clearance_poses() with a device pointer; out: a contiguous torch device tensor of P * 2 bytes, written on the handle's stream"""
+        check(load().gms_map_clearance_poses_dev(self._h, int(mi), C.c_void_p(dev_poses), int(P), int(max_radius),
+                                                 _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED,
+                                                 C.c_void_p(_view_device_out(out, 2 * int(P)))))
+        return out
 
     def copy_from(self, other: "GridMap"):
         """createMapData(other) (GridMap.java:106-124)."""
@@ -1002,6 +1056,26 @@ class _SlamHandle:
         check(load().gms_slam_cast(self._h, int(which), int(filter), ptr(b), len(b), ptr(rec), C.byref(shown)))
         return rec, (None if every else int(shown.value))
 
+    def _clearance(self, which, filter: int, rect, max_radius: int, not_free: bool, out, shown_out):
+        """gms_slam_clearance[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (field, shown)"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('clearance: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        c, shape, nbytes = _clearance_args(self.W, self.H, rect, max_radius, not_free, filter)
+        if out is not None:
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("clearance: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_clearance_dev(self._h, int(which), C.byref(c), C.c_void_p(_view_device_out(out, nbytes)), sh))
+            return out, shown_out
+        field = np.empty(shape, dtype=np.uint16)
+        shown = C.c_int32(-1)
+        check(load().gms_slam_clearance(self._h, int(which), C.byref(c), ptr(field), C.byref(shown)))
+        return field, int(shown.value)
+
     def set_history(self, capacity: int):
         """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
         resampling (0: off, the memory freed).  reset() clears the history and keeps it on.  Refused on a shard of a filter."""
@@ -1169,6 +1243,12 @@ class SLAMParticleMaps(_SlamHandle):
         (records [B], shown); which = "all": (records [n][B], None).  out / shown_out: torch device tensors, probes then
         (device address, B); nothing is synchronised."""
         return self._cast(which, 0, probes, out, shown_out)
+
+    def clearance(self, which="strongest", rect=None, max_radius: int = 25, not_free: bool = False, out=None, shown_out=None):
+        """The clearance field of particle `which`'s OWN map (GridMap.clearance's values): (field uint16 [h][w], shown).  which = a
+        particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  out /
+        shown_out: torch device tensors for the field and the int32 index; nothing is synchronised."""
+        return self._clearance(which, 0, rect, max_radius, not_free, out, shown_out)
 
     def trajectory(self, which="strongest", out=None, shown_out=None):
         """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
@@ -1361,6 +1441,15 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._cast(which, filter, probes, out, shown_out)
+
+    def clearance(self, which="strongest", filter: int = 0, rect=None, max_radius: int = 25, not_free: bool = False, out=None, shown_out=None):
+        """SLAMParticleMaps.clearance for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
+        is the handle-wide slot filter * num_particles + k whose field was made, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._clearance(which, filter, rect, max_radius, not_free, out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown

@@ -580,6 +580,63 @@ int gms_map_cast_at_dev(gms_map *m, const gms_beam *dev_probes, int32_t B, gms_p
 int gms_slam_cast(gms_slam *s, int32_t which, int32_t filter, const gms_beam *probes, int32_t B, gms_cast_hit *out, int32_t *shown);
 int gms_slam_cast_dev(gms_slam *s, int32_t which, int32_t filter, const gms_beam *dev_probes, int32_t B, gms_cast_hit *dev_out, int32_t *dev_shown);
 
+/* ---- clearance fields: how far the nearest wall is from a place ------------------------------------------------------------------
+ * What collision warning, costmap inflation, path planning and the choice of exploration goals rest on, and this library's own
+ * definition (the reference has no such method).  All of it is integer arithmetic.
+ *
+ * An OBSTACLE cell is chosen by gms_clearance.mode:
+ *   GMS_CLEAR_OCCUPIED   logData > logOdds(0.5) = 0: the class GridMap.java:239 maps to 1 and the predicate the casts use.  NaN, 0 and
+ *                        -0.0 are not obstacles.
+ *   GMS_CLEAR_NOT_FREE   !(logData < 0): occupied or never observed; NaN counts as an obstacle.  What a planner wants that must not
+ *                        drive into the unknown.
+ * For a cell (x, y), d2 = min((x - ox)^2 + (y - oy)^2) over every obstacle cell (ox, oy) of the WHOLE map, not only of the requested
+ * rectangle.  An obstacle cell has d2 = 0.  Cells outside the map are not obstacles (the map's border is none).  The output is one
+ * uint16_t per cell: d2 where d2 <= max_radius^2, GMS_CLEAR_FAR otherwise -- farther than the radius, or no obstacle at all.
+ * max_radius is in cells, 1 <= max_radius <= 255 (255^2 = 65025 fits).  The clearance in metres is sqrt(d2) * resolution, the caller's
+ * to take.
+ *
+ * The rectangle: cells [x0, x0 + w) x [y0, y0 + h), w, h >= 1, inside [0, W] x [0, H] (GMS_ERR_INVALID otherwise, nothing touched):
+ * gms_view's rules.  The output: [h][w], row-major, row 0 = y0 (logData's orientation), no row padding.
+ *
+ * A field sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment (a scan whose `logData +=` pass
+ * is still deferred is applied first, a resampling copy that is owed is looked through, the generation of a per-particle map is picked
+ * from the epoch counters) and changes no later result of its handle.  Arguments are checked before anything is enqueued
+ * (GMS_ERR_INVALID, nothing touched).  These are the casts' rules. */
+enum { GMS_CLEAR_OCCUPIED = 0, GMS_CLEAR_NOT_FREE = 1 };       /* gms_clearance.mode */
+#define GMS_CLEAR_FAR 0xFFFF                                   /* farther than max_radius from every obstacle, or no obstacle at all */
+#define GMS_CLEAR_OUTSIDE 0xFFFE                               /* gms_map_clearance_poses: the pose's cell is outside the map */
+typedef struct gms_clearance {
+    int32_t x0, y0, w, h;       /* the cell rectangle */
+    int32_t max_radius;         /* cells, 1 .. 255 */
+    int32_t mode;               /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+} gms_clearance;
+/* The output's size in cells and bytes (any of the three may be NULL).  Pure host code: checks w, h >= 1, x0, y0 >= 0, the radius
+ * and the mode -- not the map's bounds, which it does not know. */
+int gms_clearance_size(const gms_clearance *c, int32_t *out_w, int32_t *out_h, int64_t *bytes);
+/* Map mi of a shared or batched map.  out: [h][w] uint16_t of host memory, staged through the views' buffer; the call synchronises.
+ * _dev: out is device memory (2-byte aligned), written on the handle's stream; nothing is synchronised.
+ * GMS_CLEAR_OCCUPIED reads the casts' bit plane: a field of a map whose plane is current packs none, and a cast after a field packs
+ * none either (gms_map_cast_plane_builds).  GMS_CLEAR_NOT_FREE keeps a second plane of its own predicate beside it, by the same rules.
+ * The field is the exact separable transform capped at max_radius: a workgroup stages the horizontal distances of its rows and of
+ * max_radius rows above and below in LDS (at most 64 KiB) and every lane takes the minimum down its column. */
+int gms_map_clearance(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *out);
+int gms_map_clearance_dev(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *dev_out);
+/* The clearance under P points (poses [P][3] = x, y, theta, of which theta is not read; 1 <= P <= GMS_MAX_PARTICLES) without making a
+ * field; out [P].  The cell of a pose is probabilityOf's: gx = (int)((x - position.x) / resolution), gy likewise, in double with
+ * Java's cast (GridMap.java:273-274: truncation toward zero, so a coordinate in (-1, 0) cells lands in cell 0; NaN -> 0).  A pose whose
+ * cell is outside the map (:276) yields GMS_CLEAR_OUTSIDE; every other value is the field's at that cell. */
+int gms_map_clearance_poses(gms_map *m, int32_t mi, const float *poses, int32_t P, int32_t max_radius, int32_t mode, uint16_t *out);
+int gms_map_clearance_poses_dev(gms_map *m, int32_t mi, const float *dev_poses, int32_t P, int32_t max_radius, int32_t mode, uint16_t *dev_out);
+/* One particle's map of the per-particle filter.  The rectangle's rules, the index space of `which` (>= 0: the particle, a batched
+ * handle's f * n + k; GMS_VIEW_STRONGEST: the strongest particle of filter c->filter, picked on the device), *shown (may be NULL; _dev:
+ * a device int32_t *) and the GMS_ERR_STATE cases of "strongest" (before the first update, after a reset, on a shard) are
+ * gms_slam_view's.  Particle and generation come from device state: nothing is read back in front of the launches.  A pre-pass packs
+ * the shown particle's obstacle bits -- from plane 0 of its class planes (code 2 occupied, code 1 free), or from logData itself on a
+ * handle that keeps no planes -- into a scratch plane of the handle, and the shared maps' field kernel runs on that. */
+int gms_slam_clearance(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *out, int32_t *shown);
+int gms_slam_clearance_dev(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *dev_out, int32_t *dev_shown);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

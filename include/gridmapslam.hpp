@@ -159,6 +159,27 @@ public:
         check(gms_map_cast(h_, mi, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data()));
         return out;
     }
+    /** The clearance field (gridmapslam.h "clearance fields") of map mi: per cell of c's rectangle the squared distance in cells to the
+     *  nearest obstacle cell of the whole map, GMS_CLEAR_FAR beyond c.max_radius; [h][w] row-major */
+    std::vector<uint16_t> clearance(const gms_clearance &c, int mi = 0) {
+        int64_t bytes = 0;
+        check(gms_clearance_size(&c, nullptr, nullptr, &bytes));
+        std::vector<uint16_t> out((size_t)bytes / sizeof(uint16_t));
+        check(gms_map_clearance(h_, mi, &c, out.data()));
+        return out;
+    }
+    /** the clearance under every pose's cell, without making a field; GMS_CLEAR_OUTSIDE for a pose off the map */
+    std::vector<uint16_t> clearanceOf(const std::vector<Pose> &poses, int maxRadius, bool notFree = false, int mi = 0) {
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        std::vector<uint16_t> out(poses.size());
+        check(gms_map_clearance_poses(h_, mi, p.data(), (int32_t)poses.size(), maxRadius, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, out.data()));
+        return out;
+    }
+    /** the whole map's clearance request */
+    gms_clearance fullClearance(int maxRadius, bool notFree = false) const {
+        return gms_clearance{0, 0, w_, hgt_, maxRadius, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, 0};
+    }
     /** the whole map at one cell per pixel */
     gms_view fullView(bool likelihood = false, bool packed = false, int decimate = 1) const {
         return gms_view{0, 0, w_, hgt_, decimate, likelihood ? GMS_VIEW_LIKELIHOOD : GMS_VIEW_LOG, packed ? GMS_VIEW_PACKED32 : GMS_VIEW_GREY8, 0};
@@ -414,6 +435,17 @@ public:
         int32_t drawn = 0;
         check(gms_slam_view(h_, which, &v, out.data(), &drawn));
         if (shown) *shown = drawn;
+        return out;
+    }
+    /** The clearance field of particle `which`'s own map (GridMap::clearance's values) -- GMS_VIEW_STRONGEST: the strongest, as render()
+     *  picks it; *shown (may be null) receives the particle whose field was made. */
+    std::vector<uint16_t> clearance(const gms_clearance &c, int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        int64_t bytes = 0;
+        check(gms_clearance_size(&c, nullptr, nullptr, &bytes));
+        std::vector<uint16_t> out((size_t)bytes / sizeof(uint16_t));
+        int32_t picked = 0;
+        check(gms_slam_clearance(h_, which, &c, out.data(), &picked));
+        if (shown) *shown = picked;
         return out;
     }
     /** The predicted scan of particle `which` -- GMS_VIEW_STRONGEST: the strongest, as render() picks it; GMS_CAST_ALL: every particle,
