@@ -21,7 +21,7 @@ GMS_BLOCK = 256
 GMS_PARTIAL_STRIDE = 9
 PACKED_BYTES = 24
 
-GMS_OK, GMS_ERR_INVALID, GMS_ERR_NO_DEVICE, GMS_ERR_HIP, GMS_ERR_NOMEM, GMS_ERR_STATE = 0, -1, -2, -3, -4, -5
+GMS_OK, GMS_ERR_INVALID, GMS_ERR_NO_DEVICE, GMS_ERR_HIP, GMS_ERR_NOMEM, GMS_ERR_STATE, GMS_ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 K_RAYCAST, K_APPLY, K_LIKELIHOOD, K_SCORE, K_REDUCE, K_RESAMPLE, K_REFINE, K_EXCHANGE, K_ORDER, K_MAPCOPY, K_COUNT = range(11)   # enum of gridmapslam.h (GMS_K_*)
 KERNEL_NAMES = ["raycast", "apply", "likelihood", "score", "reduce", "resample", "refine", "exchange", "order", "mapcopy"]
 assert len(KERNEL_NAMES) == K_COUNT
@@ -71,7 +71,16 @@ class GmsClearance(C.Structure):
     ]
 
 
+class GmsReach(C.Structure):
+    """gms_reach: a rectangle of a map's cost-to-go field (gridmapslam.h "cost-to-go fields")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("max_cost", C.c_int32), ("inflate", C.c_int32), ("mode", C.c_int32), ("filter", C.c_int32),
+    ]
+
+
 CLEARANCE = GmsClearance
+GMS_REACH_AXIS, GMS_REACH_DIAG, GMS_REACH_FAR, GMS_REACH_MAX_SEEDS = 5, 7, 0xFFFF, 4096
 GMS_CLEAR_OCCUPIED, GMS_CLEAR_NOT_FREE = 0, 1
 GMS_CLEAR_FAR, GMS_CLEAR_OUTSIDE = 0xFFFF, 0xFFFE
 GMS_VIEW_GREY8, GMS_VIEW_PACKED32 = 0, 1
@@ -281,6 +290,13 @@ def load() -> C.CDLL:
     sig("gms_map_clearance_poses_dev", C.c_int, vp, i32, vp, i32, i32, i32, vp)
     sig("gms_slam_clearance", C.c_int, vp, i32, cl, vp, vp)
     sig("gms_slam_clearance_dev", C.c_int, vp, i32, cl, vp, vp)
+    rp = C.POINTER(GmsReach)
+    sig("gms_reach_size", C.c_int, rp, vp, vp, vp)
+    sig("gms_map_reach", C.c_int, vp, i32, rp, vp, i32, vp)
+    sig("gms_map_reach_dev", C.c_int, vp, i32, rp, vp, i32, vp)
+    sig("gms_slam_reach", C.c_int, vp, i32, rp, vp, i32, vp, vp)
+    sig("gms_slam_reach_dev", C.c_int, vp, i32, rp, vp, i32, vp, vp)
+    sig("gms_map_reach_stats", C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64))
     _lib = L
     return L
 

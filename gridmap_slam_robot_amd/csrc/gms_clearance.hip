@@ -179,10 +179,8 @@ k_clear_poses(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, const 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-static inline int32_t clear_wpr(const gms_map *m) { return 2 * ((m->gd.W + 63) / 64); }        // (= gms_map::cast_wpr once the casts' plane exists)
-
 // the plane of `mode` of logData as it stands, every map's: the casts' own, or the second one (apply pass, allocation, pre-pass as there)
-static int clear_plane(gms_map *m, int32_t mode, const uint32_t **plane) {
+int gms_clear_plane(gms_map *m, int32_t mode, const uint32_t **plane) {
     if (mode == GMS_CLEAR_OCCUPIED) {
         int rc = gms_cast_plane(m);
         *plane = m->d_cast_plane;
@@ -212,7 +210,7 @@ static int clear_plane(gms_map *m, int32_t mode, const uint32_t **plane) {
 static inline int32_t clear_tile_rows(int32_t R, int32_t h) { return std::min(h, std::min(256, std::max(64, (2 * R + 7) & ~7))); }
 
 // the field of rectangle c of ONE map's plane into d_out
-static int clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out) {
+int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out) {
     const int32_t R = c->max_radius, TY = clear_tile_rows(R, c->h), rows_cap = std::min(TY + 2 * R, m->gd.H);
     const size_t lds = (size_t)rows_cap * CLR_ROW_BYTES;
     static bool attr_set = false;
@@ -222,7 +220,7 @@ static int clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance
     }
     const int32_t words = ((c->x0 + c->w - 1) >> 5) - (c->x0 >> 5) + 1, bands = (c->h + TY - 1) / TY;
     if (bands > 65535) return gms_fail(GMS_ERR_INVALID, "gms_clearance: a rectangle of %d rows exceeds one launch", c->h);
-    hipLaunchKernelGGL(k_clear_field, dim3((unsigned)words, (unsigned)bands), dim3(CLR_NT), lds, m->stream, d_plane, clear_wpr(m), m->gd.H, c->x0, c->y0,
+    hipLaunchKernelGGL(k_clear_field, dim3((unsigned)words, (unsigned)bands), dim3(CLR_NT), lds, m->stream, d_plane, gms_clear_wpr(m), m->gd.H, c->x0, c->y0,
                        c->w, c->h, R, TY, rows_cap, d_out);
     HIPCHK(hipGetLastError());
     return GMS_OK;
@@ -248,10 +246,10 @@ static int map_clearance(gms_map *m, int32_t mi, const gms_clearance *c, uint16_
     unsigned char *base = nullptr;
     if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
     const uint32_t *plane = nullptr;
-    rc = clear_plane(m, c->mode, &plane);
+    rc = gms_clear_plane(m, c->mode, &plane);
     if (rc) return rc;
     uint16_t *d_out = on_device ? out : reinterpret_cast<uint16_t *>(base + 16);
-    rc = clear_launch(m, plane + (size_t)mi * (size_t)m->gd.H * (size_t)clear_wpr(m), c, d_out);
+    rc = gms_clear_launch(m, plane + (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m), c, d_out);
     if (rc || on_device) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -279,14 +277,39 @@ static int map_clearance_poses(gms_map *m, int32_t mi, const float *poses, int32
         d_poses = stage;
     }
     const uint32_t *plane = nullptr;
-    int rc = clear_plane(m, mode, &plane);
+    int rc = gms_clear_plane(m, mode, &plane);
     if (rc) return rc;
     hipLaunchKernelGGL(k_clear_poses, dim3((unsigned)((P + CLR_NT / 64 - 1) / (CLR_NT / 64))), dim3(CLR_NT), 0, m->stream, m->gd,
-                       plane + (size_t)mi * (size_t)m->gd.H * (size_t)clear_wpr(m), clear_wpr(m), d_poses, P, max_radius, d_out);
+                       plane + (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m), gms_clear_wpr(m), d_poses, P, max_radius, d_out);
     HIPCHK(hipGetLastError());
     if (on_device) return GMS_OK;
     HIPCHK(hipMemcpyAsync(out, d_out, (size_t)P * sizeof(uint16_t), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
+    return GMS_OK;
+}
+
+// the shown particle's plane under `mode` into gms_map::d_clear_scratch (allocated by the first request), and its handle-wide index into
+// d_shown (may be NULL); which / filter as gms_slam_view takes them, already checked
+int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown) {
+    gms_map *m = s->map;
+    const int32_t wpr64 = (m->gd.W + 63) / 64;
+    if (!m->d_clear_scratch) {
+        const size_t plane_bytes = (size_t)m->gd.H * (size_t)wpr64 * sizeof(uint64_t);
+        if (hipMalloc(&m->d_clear_scratch, plane_bytes) != hipSuccess) {
+            m->d_clear_scratch = nullptr;
+            return gms_fail(GMS_ERR_NOMEM, "gms_slam_clearance: the particle's bit plane of %zu bytes could not be allocated", plane_bytes);
+        }
+    }
+    const SlamBufs sb = gms_slam_bufs(s);
+    if (which != GMS_VIEW_STRONGEST) filter = 0;
+    const dim3 grid((unsigned)((wpr64 + 3) / 4), (unsigned)m->gd.H);
+    if (s->d_code[0])
+        hipLaunchKernelGGL((k_clear_plane_slam<true>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, mode, wpr64,
+                           reinterpret_cast<uint64_t *>(m->d_clear_scratch), d_shown);
+    else
+        hipLaunchKernelGGL((k_clear_plane_slam<false>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, mode, wpr64,
+                           reinterpret_cast<uint64_t *>(m->d_clear_scratch), d_shown);
+    HIPCHK(hipGetLastError());
     return GMS_OK;
 }
 
@@ -303,29 +326,13 @@ static int slam_clearance(gms_slam *s, int32_t which, const gms_clearance *c, ui
         if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_clearance: no update since the handle was created or reset: there is no strongest particle yet");
     } else REQUIRE(which >= 0 && which < s->n, "gms_slam_clearance: particle index out of range");
     HIPCHK(hipSetDevice(m->device));
-    const int32_t wpr64 = (m->gd.W + 63) / 64;
-    if (!m->d_clear_scratch) {
-        const size_t plane_bytes = (size_t)m->gd.H * (size_t)wpr64 * sizeof(uint64_t);
-        if (hipMalloc(&m->d_clear_scratch, plane_bytes) != hipSuccess) {
-            m->d_clear_scratch = nullptr;
-            return gms_fail(GMS_ERR_NOMEM, "gms_slam_clearance: the particle's bit plane of %zu bytes could not be allocated", plane_bytes);
-        }
-    }
     unsigned char *base = nullptr;
     if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
-    const SlamBufs sb = gms_slam_bufs(s);
-    const int32_t filter = which == GMS_VIEW_STRONGEST ? c->filter : 0;
     int32_t *d_shown = on_device ? shown : reinterpret_cast<int32_t *>(base);
     uint16_t *d_out = on_device ? out : reinterpret_cast<uint16_t *>(base + 16);
-    const dim3 grid((unsigned)((wpr64 + 3) / 4), (unsigned)m->gd.H);
-    if (s->d_code[0])
-        hipLaunchKernelGGL((k_clear_plane_slam<true>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, c->mode, wpr64,
-                           reinterpret_cast<uint64_t *>(m->d_clear_scratch), d_shown);
-    else
-        hipLaunchKernelGGL((k_clear_plane_slam<false>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, c->mode, wpr64,
-                           reinterpret_cast<uint64_t *>(m->d_clear_scratch), d_shown);
-    HIPCHK(hipGetLastError());
-    rc = clear_launch(m, m->d_clear_scratch, c, d_out);
+    rc = gms_clear_plane_slam(s, which, c->filter, c->mode, d_shown);
+    if (rc) return rc;
+    rc = gms_clear_launch(m, m->d_clear_scratch, c, d_out);
     if (rc || on_device) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
     if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));

@@ -245,6 +245,8 @@ static int map_free(gms_map *m) {
     for (ProfSlot &s : m->prof_free) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
     hipFree(m->d_log); hipFree(m->d_lik); hipFree(m->d_fac); hipFree(m->d_cnt); hipFree(m->d_cnt_pend); hipFree(m->d_bbox); hipFree(m->d_taps); hipFree(m->d_tile_state); hipFree(m->d_tile_stats);
     hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch); hipFree(m->d_view); hipFree(m->d_cast_plane); hipFree(m->d_clear_plane); hipFree(m->d_clear_scratch);
+    hipFree(m->d_reach_field); hipFree(m->d_reach_d2); hipFree(m->d_reach_plane); hipFree(m->d_reach_ctl);
+    if (m->h_reach_ctl) hipHostFree(m->h_reach_ctl);
     hipFree(m->d_trace_cells); hipFree(m->d_trace_cls); hipFree(m->d_trace_cnt);
     if (m->h_beams) hipHostFree(m->h_beams);
     ring_free(m->beam_ring);

@@ -124,6 +124,14 @@ struct gms_map {
     uint32_t *d_clear_plane;  // [n_maps][H][cast_wpr] the second plane of the clearance fields (gms_clearance.hip): !(logData < 0), same layout; allocated by the first GMS_CLEAR_NOT_FREE field
     int32_t clear_plane_current;  // it is the plane of logData as it stands (cleared wherever cast_plane_current is)
     uint32_t *d_clear_scratch;    // [H][cast_wpr] a gms_slam's clearance: the shown particle's plane, packed per request
+    // cost-to-go fields (gms_reach.hip); everything below is allocated by the first field that needs it and only ever grows
+    uint16_t *d_reach_field;      // [H][W] the working field the tiles relax
+    uint16_t *d_reach_d2;         // [H][W] inflate > 0: the whole map's clearance field at R = inflate ...
+    uint32_t *d_reach_plane;      // [H][cast_wpr] ... and the blocked plane balloted from it
+    uint32_t *d_reach_ctl;        // {tile runs (64 bits), the active count of four rounds, 2 spare} | [2][tiles] the tiles' active flags of this round and the next
+    uint32_t *h_reach_ctl;        // pinned: the first 8 words of it, read back once per batch of rounds
+    int32_t reach_rounds;         // gms_map_reach_stats: rounds launched for the last field
+    int64_t reach_tile_runs;      // ... and tile relaxations that ran
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -488,6 +496,14 @@ void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_o
 // the casts' bit plane (logData > 0) of logData as it stands, on the handle: the deferred apply pass first, then the pre-pass unless the
 // handle still holds the plane of this logData (gms_cast.hip; the clearance fields of GMS_CLEAR_OCCUPIED read the same plane)
 int gms_cast_plane(gms_map *m);
+// the clearance fields' host helpers that the cost-to-go fields share (gms_clearance.hip): a plane's 32-bit words per row; the plane of
+// `mode` of logData as it stands, every map's (GMS_CLEAR_OCCUPIED: the casts' own); the field of rectangle c of ONE map's plane into d_out;
+// the shown particle's plane of a gms_slam into gms_map::d_clear_scratch and its index into d_shown (may be NULL)
+static inline int32_t gms_clear_wpr(const gms_map *m) { return 2 * ((m->gd.W + 63) / 64); }        // (= gms_map::cast_wpr once the casts' plane exists)
+int gms_clear_plane(gms_map *m, int32_t mode, const uint32_t **plane);
+int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out);
+struct gms_slam;
+int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown);
 
 void gms_launch_pf_init(gms_pf *pf);
 void gms_launch_pf_pose_trig(gms_pf *pf, const float *d_src);

@@ -23,7 +23,8 @@ import numpy as np
 from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
-__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres"]
+__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres",
+           "cells_of_poses", "descend"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -172,6 +173,82 @@ def clearance_metres(d2, resolution: float) -> np.ndarray:
     out[a == _lib.GMS_CLEAR_FAR] = np.inf
     out[a == _lib.GMS_CLEAR_OUTSIDE] = np.nan
     return out
+
+
+def _reach_args(W: int, H: int, rect, max_cost: int, inflate: int, not_free: bool, filter: int = 0):
+    """(gms_reach, output shape, bytes) of a cost-to-go field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
+    r = _lib.GmsReach(x0, y0, w, h, int(max_cost), int(inflate), _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED, int(filter))
+    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    check(load().gms_reach_size(C.byref(r), C.byref(ow), C.byref(oh), C.byref(nbytes)))
+    return r, (oh.value, ow.value), nbytes.value
+
+
+def _reach_seeds(seeds) -> np.ndarray:
+    """seeds as the int32 [K][2] (x, y) array the library takes"""
+    a = np.ascontiguousarray(seeds, dtype=np.int32)
+    if a.ndim == 1 and a.size == 2:
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"reach: seeds must be [K][2] (x, y) cells, not {a.shape}")
+    return a
+
+
+def reach_metres(field, resolution: float) -> np.ndarray:
+    """Cost-to-go values (GridMap.reach: uint16, 5 per axis step, 7 per diagonal one) as metres, float64: cost / 5 * resolution;
+    GMS_REACH_FAR (blocked, unreachable, or beyond the cap) becomes inf."""
+    a = np.asarray(field)
+    out = a.astype(np.float64) / _lib.GMS_REACH_AXIS * float(resolution)
+    out[a == _lib.GMS_REACH_FAR] = np.inf
+    return out
+
+
+def cells_of_poses(poses, position, resolution: float):
+    """probabilityOf's cell of every pose of poses [P][3] (GridMap.java:273-274): (int)((x - position.x) / resolution) in double -- the
+    pose's floats and the map's float position and resolution widened -- with Java's cast: toward zero (a coordinate in (-1, 0) cells
+    lands in cell 0), NaN -> 0, saturating.  (gx, gy), int64 [P] each; a cell off the map is the caller's to test for."""
+    p = np.asarray(poses, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    out = []
+    for col in (0, 1):
+        with np.errstate(invalid="ignore", over="ignore"):
+            q = (p[:, col] - np.float64(np.float32(position[col]))) / np.float64(np.float32(resolution))
+        q = np.where(np.isnan(q), 0.0, np.clip(np.trunc(q), -2147483648.0, 2147483647.0))
+        out.append(q.astype(np.int64))
+    return out[0], out[1]
+
+
+_DESCEND_ORDER = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))       # E, N, W, S, NE, NW, SW, SE; north is y + 1
+
+
+def descend(field, start) -> list:
+    """The cells of one cheapest path from start = (x, y) down to a seed over a WHOLE-MAP cost-to-go field, in order, start first: from
+    the current cell the first neighbour n, in the order E, N, W, S, NE, NW, SW, SE (north = y + 1), with field[n] + step ==
+    field[current].  A diagonal is admitted only if both cells it squeezes between are not FAR -- sound, because the side cells of a
+    legal diagonal predecessor cost at most predecessor + 5 < current.  A FAR start (or one off the map) returns an empty list."""
+    f = np.asarray(field)
+    H, W = f.shape
+    x, y = int(start[0]), int(start[1])
+    far = _lib.GMS_REACH_FAR
+    if not (0 <= x < W and 0 <= y < H) or f[y, x] == far:
+        return []
+    path = [(x, y)]
+    while f[y, x] != 0:
+        cur = int(f[y, x])
+        for dx, dy in _DESCEND_ORDER:
+            nx, ny = x + dx, y + dy
+            if not (0 <= nx < W and 0 <= ny < H) or f[ny, nx] == far:
+                continue
+            if dx and dy:
+                if f[y, nx] == far or f[ny, x] == far or int(f[ny, nx]) + _lib.GMS_REACH_DIAG != cur:
+                    continue
+            elif int(f[ny, nx]) + _lib.GMS_REACH_AXIS != cur:
+                continue
+            x, y = nx, ny
+            break
+        else:
+            raise ValueError(f"descend: no predecessor at ({x}, {y}): not a whole-map cost-to-go field")
+        path.append((x, y))
+    return path
 
 
 class GridMap:
@@ -351,6 +428,37 @@ class GridMap:
     def clearance_dev(self, out, rect=None, max_radius: int = 25, not_free: bool = False, mi: int = 0):
         """clearance() into out, a contiguous torch device tensor of h * w * 2 bytes, on the handle's stream"""
         return self.clearance(rect, max_radius, not_free, mi, out)
+
+    def reach(self, seeds, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None, mi: int = 0, out=None):
+        """The cost-to-go field (gridmapslam.h "cost-to-go fields") of map mi: for every cell of rect = (x0, y0, w, h) (None: the whole
+        map) the cost of the cheapest 8-connected path (5 per axis step, 7 per diagonal one, no corner cutting) from any of seeds
+        [K][2] (x, y) cells through the cells that have no obstacle within `inflate` cells -- an obstacle is every cell not known free,
+        !(logData < 0), or with not_free=False logData > 0 -- as uint16 [h][w]; GMS_REACH_FAR (0xFFFF) where blocked, unreachable or
+        beyond max_cost.  Paths use the whole map.  Returns a numpy array; with out (a contiguous torch device tensor of h * w * 2
+        bytes) seeds must be an int32 torch device tensor [K][2], the field is written there on the handle's stream, and out is
+        returned (reach_dev).  Metres: reach_metres(); a path: descend()."""
+        r, shape, nbytes = _reach_args(self.W, self.H, rect, max_cost, inflate, not_free)
+        if out is not None:
+            if not (getattr(seeds, "is_cuda", False) and seeds.is_contiguous() and seeds.element_size() == 4 and seeds.numel() % 2 == 0):
+                raise ValueError("reach_dev: seeds must be a contiguous int32 torch tensor [K][2] on the device")
+            check(load().gms_map_reach_dev(self._h, int(mi), C.byref(r), C.c_void_p(int(seeds.data_ptr())), seeds.numel() // 2,
+                                           C.c_void_p(_view_device_out(out, nbytes))))
+            return out
+        sd = _reach_seeds(seeds)
+        field = np.empty(shape, dtype=np.uint16)
+        check(load().gms_map_reach(self._h, int(mi), C.byref(r), ptr(sd), len(sd), ptr(field)))
+        return field
+
+    def reach_dev(self, out, seeds, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None, mi: int = 0):
+        """reach() from device seeds into out, on the handle's stream; the call waits on that stream between batches of rounds"""
+        return self.reach(seeds, max_cost, inflate, not_free, rect, mi, out)
+
+    def reach_stats(self) -> dict:
+        """diagnostics of the last cost-to-go field made on this handle: {"rounds": launches over the tiles, "tile_runs": tile
+        relaxations that actually ran}"""
+        rounds, runs = C.c_int32(0), C.c_int64(0)
+        check(load().gms_map_reach_stats(self._h, C.byref(rounds), C.byref(runs)))
+        return {"rounds": int(rounds.value), "tile_runs": int(runs.value)}
 
     def clearance_poses(self, poses, max_radius: int = 25, not_free: bool = False, mi: int = 0) -> np.ndarray:
         """The clearance under each of poses [P][3] (x, y, theta; theta is not read) without making a field: uint16 [P], the field's
@@ -1076,6 +1184,33 @@ class _SlamHandle:
         check(load().gms_slam_clearance(self._h, int(which), C.byref(c), ptr(field), C.byref(shown)))
         return field, int(shown.value)
 
+    def _reach(self, which, filter: int, seeds, max_cost: int, inflate: int, not_free: bool, rect, out, shown_out):
+        """gms_slam_reach[_dev]: which = a handle-wide slot or "strongest" (of `filter`); seeds None: the shown particle's own cell"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('reach: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        r, shape, nbytes = _reach_args(self.W, self.H, rect, max_cost, inflate, not_free, filter)
+        if out is not None:
+            sp, K = None, 0
+            if seeds is not None:
+                if not (getattr(seeds, "is_cuda", False) and seeds.is_contiguous() and seeds.element_size() == 4 and seeds.numel() % 2 == 0):
+                    raise ValueError("reach: with out, seeds must be a contiguous int32 torch tensor [K][2] on the device (or None)")
+                sp, K = C.c_void_p(int(seeds.data_ptr())), seeds.numel() // 2
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("reach: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_reach_dev(self._h, int(which), C.byref(r), sp, K, C.c_void_p(_view_device_out(out, nbytes)), sh))
+            return out, shown_out
+        sd = None if seeds is None else _reach_seeds(seeds)
+        field = np.empty(shape, dtype=np.uint16)
+        shown = C.c_int32(-1)
+        check(load().gms_slam_reach(self._h, int(which), C.byref(r), None if sd is None else ptr(sd), 0 if sd is None else len(sd), ptr(field),
+                                    C.byref(shown)))
+        return field, int(shown.value)
+
     def set_history(self, capacity: int):
         """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
         resampling (0: off, the memory freed).  reset() clears the history and keeps it on.  Refused on a shard of a filter."""
@@ -1249,6 +1384,14 @@ class SLAMParticleMaps(_SlamHandle):
         particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  out /
         shown_out: torch device tensors for the field and the int32 index; nothing is synchronised."""
         return self._clearance(which, 0, rect, max_radius, not_free, out, shown_out)
+
+    def reach(self, which="strongest", seeds=None, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None, out=None,
+              shown_out=None):
+        """The cost-to-go field of particle `which`'s OWN map (GridMap.reach's values): (field uint16 [h][w], shown).  which = a
+        particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  seeds=None:
+        the shown particle's own pose cell, picked on the device.  out / shown_out: torch device tensors (seeds then a device int32
+        tensor or None).  Diagnostics: grid_map.reach_stats()."""
+        return self._reach(which, 0, seeds, max_cost, inflate, not_free, rect, out, shown_out)
 
     def trajectory(self, which="strongest", out=None, shown_out=None):
         """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
@@ -1450,6 +1593,16 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._clearance(which, filter, rect, max_radius, not_free, out, shown_out)
+
+    def reach(self, which="strongest", filter: int = 0, seeds=None, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None,
+              out=None, shown_out=None):
+        """SLAMParticleMaps.reach for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
+        the handle-wide slot filter * num_particles + k whose field was made, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._reach(which, filter, seeds, max_cost, inflate, not_free, rect, out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown

@@ -52,7 +52,8 @@ enum {
     GMS_ERR_NO_DEVICE = -2,     /* no usable HIP device (there is no CPU path) */
     GMS_ERR_HIP = -3,           /* a HIP runtime call failed */
     GMS_ERR_NOMEM = -4,
-    GMS_ERR_STATE = -5          /* call order violated (e.g. resample before normalise) */
+    GMS_ERR_STATE = -5,         /* call order violated (e.g. resample before normalise) */
+    GMS_ERR_INTERNAL = -6       /* a bound the library proves for itself was exceeded (gms_map_reach's rounds): a bug, reported instead of looping */
 };
 
 /* One LIDAR beam = the fields of Observation.Measurement the path reads
@@ -636,6 +637,66 @@ int gms_map_clearance_poses_dev(gms_map *m, int32_t mi, const float *dev_poses, 
  * handle that keeps no planes -- into a scratch plane of the handle, and the shared maps' field kernel runs on that. */
 int gms_slam_clearance(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *out, int32_t *shown);
 int gms_slam_clearance_dev(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *dev_out, int32_t *dev_shown);
+
+/* ---- cost-to-go fields: how far it is to drive from a set of places to everywhere else -------------------------------------------
+ * What grid planners, the choice of exploration goals and every "can I get there at all" check start from, and this library's own
+ * definition (the reference has no such method).  All of it is integer arithmetic, and the field is unique.
+ *
+ * BLOCKED: a cell is blocked if an obstacle cell under gms_reach.mode -- GMS_CLEAR_OCCUPIED or GMS_CLEAR_NOT_FREE, exactly the
+ * clearance fields' predicates, NaN, 0 and -0.0 as there -- lies within `inflate` cells of it: d2 <= inflate^2, 0 <= inflate <= 255;
+ * inflate = 0 blocks the obstacles alone.  Cells outside the map do not exist: they are neither obstacles nor traversable.  Every
+ * other cell of the map is traversable.
+ * MOVES are 8-connected: an axis step costs GMS_REACH_AXIS, a diagonal step GMS_REACH_DIAG, and a diagonal step is allowed only when
+ * both cells it squeezes between -- the two axis neighbours that share the corner -- are traversable (no corner cutting).
+ * SEEDS: seeds [K][2] int32_t (x, y) cells, 1 <= K <= GMS_REACH_MAX_SEEDS.  A seed that is off the map or blocked contributes nothing
+ * and is no error; with no seed left the whole field is GMS_REACH_FAR and the call returns GMS_OK.  A traversable seed has cost 0.
+ * THE FIELD: cost(c) = the minimum, over legal paths from any seed, of the summed step costs.  One uint16_t per cell: cost where
+ * cost <= max_cost (1 <= max_cost <= 0xFFFE), GMS_REACH_FAR otherwise -- blocked, unreachable, or farther than the cap.  Candidate
+ * costs are formed in 32 bits: a path that leaves the cap can never wrap into it.  Paths use the WHOLE map; only the output is a
+ * rectangle.  In metres along axis steps: cost / GMS_REACH_AXIS * resolution.
+ *
+ * The rectangle, the [h][w] row-major output, the argument checks before anything is enqueued (GMS_ERR_INVALID, nothing touched),
+ * "sees the map as a download would return it at that moment" and "changes no later result of its handle" are the clearance fields'
+ * rules.
+ *
+ * How: the blocked plane is a bit plane in the casts' layout -- with inflate = 0 the casts' plane or the clearance fields' second
+ * plane itself, read in place and packed only when stale (gms_map_cast_plane_builds does not move for a current plane); with
+ * inflate > 0 the clearance field of the whole map at max_radius = inflate, balloted into a scratch plane.  The field is relaxed in a
+ * uint16 working field of the whole map on the handle (allocated by the first field) in ROUNDS: one launch, one workgroup per
+ * 64 x 64 tile; an active tile loads its cells and a one-cell halo into LDS, relaxes to its own fixpoint there, writes back, and marks
+ * the neighbours across every edge or corner that changed active for the next round.  No workgroup waits on another.  The host
+ * launches rounds in batches and reads the count of active tiles back once per batch (GMS_REACH_BATCH in the environment, default 8
+ * rounds), so EVERY form, _dev included, waits on the handle's stream between batches -- unlike the other _dev forms.  After round k
+ * every cell whose cheapest path crosses fewer than k tile borders is final, so rounds <= max_cost / GMS_REACH_AXIS + 2; exceeding
+ * that returns GMS_ERR_INTERNAL instead of looping. */
+#define GMS_REACH_AXIS 5                                       /* the cost of a step along an axis */
+#define GMS_REACH_DIAG 7                                       /* ... and of a diagonal one */
+#define GMS_REACH_FAR 0xFFFF                                   /* blocked, unreachable, or farther than max_cost */
+#define GMS_REACH_MAX_SEEDS 4096
+typedef struct gms_reach {
+    int32_t x0, y0, w, h;       /* the cell rectangle of the output */
+    int32_t max_cost;           /* 1 .. 0xFFFE */
+    int32_t inflate;            /* cells, 0 .. 255 */
+    int32_t mode;               /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+} gms_reach;
+/* The output's size in cells and bytes (any of the three may be NULL).  Pure host code: checks w, h >= 1, x0, y0 >= 0, max_cost,
+ * inflate and the mode -- not the map's bounds, which it does not know, nor K. */
+int gms_reach_size(const gms_reach *r, int32_t *out_w, int32_t *out_h, int64_t *bytes);
+/* Map mi of a shared or batched map.  out: [h][w] uint16_t of host memory, staged through the views' buffer (the seeds behind it).
+ * _dev: dev_seeds (4-byte aligned) and dev_out (2-byte aligned) are device memory, read and written on the handle's stream; the call
+ * waits on that stream between batches of rounds and returns with the copy into dev_out enqueued, not waited for. */
+int gms_map_reach(gms_map *m, int32_t mi, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out);
+int gms_map_reach_dev(gms_map *m, int32_t mi, const gms_reach *r, const int32_t *dev_seeds, int32_t K, uint16_t *dev_out);
+/* One particle's map of the per-particle filter: `which`, GMS_VIEW_STRONGEST, r->filter, *shown and the GMS_ERR_STATE cases are
+ * gms_slam_view's (gms_slam_clearance's pre-pass packs the shown particle's obstacle bits).  Here only, K == 0 with seeds NULL means:
+ * the seed is the SHOWN particle's own pose cell, (int)((x - position.x) / resolution) as probabilityOf takes it (GridMap.java:273-274),
+ * picked on the device -- with "strongest", nothing is read back to learn where to plant it. */
+int gms_slam_reach(gms_slam *s, int32_t which, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out, int32_t *shown);
+int gms_slam_reach_dev(gms_slam *s, int32_t which, const gms_reach *r, const int32_t *dev_seeds, int32_t K, uint16_t *dev_out, int32_t *dev_shown);
+/* The last field made on this handle (either may be NULL): the rounds launched, and the tile relaxations that actually ran (a round
+ * launches every tile; those that are not active leave at once).  A gms_slam's: on the gms_map of gms_slam_handles. */
+int gms_map_reach_stats(const gms_map *m, int32_t *rounds, int64_t *tile_runs);
 
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a

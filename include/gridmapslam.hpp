@@ -168,6 +168,21 @@ public:
         check(gms_map_clearance(h_, mi, &c, out.data()));
         return out;
     }
+    /** The cost-to-go field (gridmapslam.h "cost-to-go fields") of map mi: per cell of r's rectangle the cost of the cheapest path from
+     *  any of seeds ({x, y} pairs) through the cells that are not blocked, GMS_REACH_FAR beyond r.max_cost; [h][w] row-major */
+    std::vector<uint16_t> reach(const gms_reach &r, const std::vector<int32_t> &seeds, int mi = 0) {
+        int64_t bytes = 0;
+        check(gms_reach_size(&r, nullptr, nullptr, &bytes));
+        std::vector<uint16_t> out((size_t)bytes / sizeof(uint16_t));
+        check(gms_map_reach(h_, mi, &r, seeds.data(), (int32_t)(seeds.size() / 2), out.data()));
+        return out;
+    }
+    /** the whole map's cost-to-go request */
+    gms_reach fullReach(int maxCost = 0xFFFE, int inflate = 0, bool notFree = true) const {
+        return gms_reach{0, 0, w_, hgt_, maxCost, inflate, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, 0};
+    }
+    /** rounds launched and tile relaxations run for the last cost-to-go field of this handle */
+    void reachStats(int32_t *rounds, int64_t *tileRuns) const { check(gms_map_reach_stats(h_, rounds, tileRuns)); }
     /** the clearance under every pose's cell, without making a field; GMS_CLEAR_OUTSIDE for a pose off the map */
     std::vector<uint16_t> clearanceOf(const std::vector<Pose> &poses, int maxRadius, bool notFree = false, int mi = 0) {
         std::vector<float> p(3 * poses.size());
@@ -435,6 +450,17 @@ public:
         int32_t drawn = 0;
         check(gms_slam_view(h_, which, &v, out.data(), &drawn));
         if (shown) *shown = drawn;
+        return out;
+    }
+    /** The cost-to-go field of particle `which`'s own map (GridMap::reach's values); no seeds: the shown particle's own pose cell,
+     *  picked on the device.  *shown (may be null) receives the particle whose field was made. */
+    std::vector<uint16_t> reach(const gms_reach &r, const std::vector<int32_t> &seeds = {}, int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        int64_t bytes = 0;
+        check(gms_reach_size(&r, nullptr, nullptr, &bytes));
+        std::vector<uint16_t> out((size_t)bytes / sizeof(uint16_t));
+        int32_t picked = 0;
+        check(gms_slam_reach(h_, which, &r, seeds.empty() ? nullptr : seeds.data(), (int32_t)(seeds.size() / 2), out.data(), &picked));
+        if (shown) *shown = picked;
         return out;
     }
     /** The clearance field of particle `which`'s own map (GridMap::clearance's values) -- GMS_VIEW_STRONGEST: the strongest, as render()
