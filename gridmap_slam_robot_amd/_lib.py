@@ -79,6 +79,26 @@ class GmsReach(C.Structure):
     ]
 
 
+class GmsFrontiers(C.Structure):
+    """gms_frontiers: a request for a map's frontier regions (gridmapslam.h "frontier regions")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("min_size", C.c_int32), ("inflate", C.c_int32), ("filter", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+class GmsFrontier(C.Structure):
+    """gms_frontier: one region's record, 56 bytes"""
+    _fields_ = [
+        ("anchor_x", C.c_int32), ("anchor_y", C.c_int32), ("count", C.c_int32), ("goal_cost", C.c_int32),
+        ("min_x", C.c_int32), ("min_y", C.c_int32), ("max_x", C.c_int32), ("max_y", C.c_int32),
+        ("goal_x", C.c_int32), ("goal_y", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64),
+    ]
+
+
+FRONTIER_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsFrontier._fields_])     # gms_frontier
+assert FRONTIER_DTYPE.itemsize == C.sizeof(GmsFrontier) == 56
+GMS_FRONTIER_NONE = 0xFFFFFFFF
 CLEARANCE = GmsClearance
 GMS_REACH_AXIS, GMS_REACH_DIAG, GMS_REACH_FAR, GMS_REACH_MAX_SEEDS = 5, 7, 0xFFFF, 4096
 GMS_CLEAR_OCCUPIED, GMS_CLEAR_NOT_FREE = 0, 1
@@ -297,6 +317,12 @@ def load() -> C.CDLL:
     sig("gms_slam_reach", C.c_int, vp, i32, rp, vp, i32, vp, vp)
     sig("gms_slam_reach_dev", C.c_int, vp, i32, rp, vp, i32, vp, vp)
     sig("gms_map_reach_stats", C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64))
+    fp = C.POINTER(GmsFrontiers)
+    sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
+    sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))
+    sig("gms_map_frontiers_dev", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))
+    sig("gms_slam_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32), vp)
+    sig("gms_slam_frontiers_dev", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32), vp)
     _lib = L
     return L
 

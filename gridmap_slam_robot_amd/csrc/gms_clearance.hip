@@ -289,11 +289,11 @@ static int map_clearance_poses(gms_map *m, int32_t mi, const float *poses, int32
 }
 
 // the shown particle's plane under `mode` into gms_map::d_clear_scratch (allocated by the first request), and its handle-wide index into
-// d_shown (may be NULL); which / filter as gms_slam_view takes them, already checked
-int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown) {
+// d_shown (may be NULL); which / filter as gms_slam_view takes them, already checked.  d_dst: a plane of the caller's instead
+int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown, uint32_t *d_dst) {
     gms_map *m = s->map;
     const int32_t wpr64 = (m->gd.W + 63) / 64;
-    if (!m->d_clear_scratch) {
+    if (!d_dst && !m->d_clear_scratch) {
         const size_t plane_bytes = (size_t)m->gd.H * (size_t)wpr64 * sizeof(uint64_t);
         if (hipMalloc(&m->d_clear_scratch, plane_bytes) != hipSuccess) {
             m->d_clear_scratch = nullptr;
@@ -302,13 +302,14 @@ int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mod
     }
     const SlamBufs sb = gms_slam_bufs(s);
     if (which != GMS_VIEW_STRONGEST) filter = 0;
+    uint64_t *dst = reinterpret_cast<uint64_t *>(d_dst ? d_dst : m->d_clear_scratch);
     const dim3 grid((unsigned)((wpr64 + 3) / 4), (unsigned)m->gd.H);
     if (s->d_code[0])
         hipLaunchKernelGGL((k_clear_plane_slam<true>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, mode, wpr64,
-                           reinterpret_cast<uint64_t *>(m->d_clear_scratch), d_shown);
+                           dst, d_shown);
     else
         hipLaunchKernelGGL((k_clear_plane_slam<false>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, mode, wpr64,
-                           reinterpret_cast<uint64_t *>(m->d_clear_scratch), d_shown);
+                           dst, d_shown);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }

@@ -1,0 +1,610 @@
+// gms_frontier.hip -- frontier regions (gridmapslam.h "frontier regions"): the FREE cells with an UNKNOWN axis neighbour inside the map,
+// grouped into maximal 8-connected regions; per region its anchor (the member of the smallest linear index), count, box, coordinate sums
+// and -- with a cost-to-go field -- the member that is cheapest to drive to.  All integer arithmetic; every output is unique, so
+// however the unions and the atomics are scheduled the result is the same.
+//
+// A translation unit of its own, kernels and C-ABI: nothing here is on the scan step's path, and no kernel of the other units is
+// compiled differently for it.
+//
+//   k_front_plane       the frontier plane in the casts' layout (rows of 64-bit words, the padding zero), a lane per word: unknown = the
+//                       second plane and not the casts' plane; a word's east / west shifts carry a bit from the neighbouring words, north
+//                       and south are the words of the rows above and below; free = not the second plane; inflate > 0: and not the
+//                       cost-to-go fields' blocked plane (gms_reach_inflate).  Both planes are read in place (gms_clear_plane; a
+//                       gms_slam's: gms_clear_plane_slam, twice).
+//   k_front_tiles       a workgroup per 64 x 64 tile; a tile whose 64 words are all zero leaves at once.  Every frontier cell starts as
+//                       its own root in LDS and is united with its W, N, NW and NE neighbours inside the tile (front_unite); then every
+//                       cell chases to its root and writes the root's GLOBAL linear index into the label field.  Tile-local order is the
+//                       global order restricted to the tile, so that root is the tile's smallest member of the cell's component.
+//   k_front_merge       a lane per cell on the first column / row behind a tile border: united, in the global label field, with its (up
+//                       to) three neighbours across that border -- every pair adjacent across an edge or a corner, both diagonals.
+//   k_front_flatten     a wavefront per plane word: every frontier cell chases to its root and stores it; the ballot of "I am my own
+//                       root" is the root plane's word, its popcount the word's count.
+//   k_front_scan_*      exclusive scan of those counts (blocks of FRT_SCAN in one launch, the blocks' sums in a second, single
+//                       workgroup): the roots in linear order = the regions in anchor order; the total is the number of regions.
+//   k_front_table_init, k_front_reduce, k_front_finish
+//                       the table: a wavefront per plane word looks up every cell's region index, and the lanes that share one combine
+//                       (count, box and sums from the group's ballot alone; the goal key cost << 32 | index by a butterfly) before ONE
+//                       lane issues the atomics -- integer min / max / add only.  The finish decodes the goal and flags count >= min_size.
+//   k_front_scan_*, k_front_emit   the flags scanned, the kept regions' records stored in order, the first `cap` of them.
+//   k_front_labels      the label rectangle: the label where the plane has a bit, GMS_FRONTIER_NONE elsewhere.
+//
+// front_unite is the lock-free union: find both roots, hang the LARGER under the smaller with atomicMin, and if that root had moved in
+// the meantime (the old value is not the root itself) go on with what it moved to.  A label only ever decreases and never exceeds its
+// own index, so chains end, nothing cycles, and nobody waits for anybody: a retry follows another lane's progress.
+//
+// LDS of k_front_tiles: 64 words + 4096 uint32 labels = 16.5 KiB.  A lane owns 16 cells of a row and visits the set bits only.
+#undef GMS_STAMPS
+#include <limits.h>
+#include <stddef.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "gms_device.h"
+
+#define FRT_T 64                         // tile edge in cells = cells of a plane word
+#define FRT_NT 256
+#define FRT_SCAN 1024                    // items a workgroup of k_front_scan_blocks scans
+#define FRT_CAP0 4096                    // regions the handle's table holds at first (a multiple of FRT_SCAN)
+#define FRT_NONE 0xffffffffu
+#define FRT_NO_GOAL 0xffffffffffffffffull
+
+static_assert(GMS_FRONTIER_NONE == FRT_NONE, "the header's constant is the kernels'");
+static_assert(sizeof(gms_frontiers) == 32 && sizeof(gms_frontier) == 56 && offsetof(gms_frontier, count) == 8 && offsetof(gms_frontier, goal_cost) == 12 &&
+              offsetof(gms_frontier, min_x) == 16 && offsetof(gms_frontier, max_x) == 24 && offsetof(gms_frontier, goal_x) == 32 &&
+              offsetof(gms_frontier, sum_x) == 40 && offsetof(gms_frontier, sum_y) == 48, "the header fixes the record's offsets");
+static_assert(FRT_CAP0 % FRT_SCAN == 0, "the table's parts stay 8-byte aligned");
+
+__device__ __forceinline__ uint32_t front_find(const uint32_t *L, uint32_t a) {
+    for (;;) {
+        const uint32_t p = __atomic_load_n(L + a, __ATOMIC_RELAXED);
+        if (p == a) return a;
+        a = p;
+    }
+}
+__device__ __forceinline__ void front_unite(uint32_t *L, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = front_find(L, a);
+        b = front_find(L, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = atomicMin(L + a, b);                               // the larger root under the smaller
+        if (old == a) return;
+        a = old;                                                                // a had moved: unite what it moved to
+    }
+}
+
+// occ, nf, blocked (NULL: inflate == 0): ONE map's planes, H rows of wpr64 words; out likewise
+__global__ void __launch_bounds__(FRT_NT)
+k_front_plane(const uint64_t *__restrict__ occ, const uint64_t *__restrict__ nf, const uint64_t *__restrict__ blocked, int32_t W, int32_t H, int32_t wpr64,
+              uint64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x;
+    if (i >= (int64_t)H * wpr64) return;
+    const int32_t y = (int32_t)(i / wpr64), wx = (int32_t)(i - (int64_t)y * wpr64);
+    auto unknown = [&](int32_t yy, int32_t ww) -> uint64_t {                    // (off the map: nothing is unknown)
+        if (yy < 0 || yy >= H || ww < 0 || ww >= wpr64) return 0ull;
+        const size_t k = (size_t)yy * (size_t)wpr64 + (size_t)ww;
+        return nf[k] & ~occ[k];
+    };
+    const uint64_t u = unknown(y, wx);
+    const uint64_t beside = (u << 1) | (unknown(y, wx - 1) >> 63) | (u >> 1) | (unknown(y, wx + 1) << 63) | unknown(y - 1, wx) | unknown(y + 1, wx);
+    const uint64_t on_map = wx == wpr64 - 1 && (W & 63) ? (1ull << (W & 63)) - 1ull : ~0ull;
+    uint64_t f = ~nf[i] & on_map & beside;
+    if (blocked) f &= ~blocked[i];
+    out[i] = f;
+}
+
+// plane: the frontier plane; label [H][W]; grid (ntx, nty)
+__global__ void __launch_bounds__(FRT_NT)
+k_front_tiles(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, uint32_t *__restrict__ label) {
+    __shared__ uint64_t s_word[FRT_T];
+    __shared__ uint32_t s_lab[FRT_T * FRT_T];
+    const int32_t t = (int32_t)threadIdx.x, tx = (int32_t)blockIdx.x, x0 = tx * FRT_T, y0 = (int32_t)blockIdx.y * FRT_T;
+    uint64_t w = 0ull;
+    if (t < FRT_T) {
+        w = y0 + t < H ? plane[(size_t)(y0 + t) * (size_t)wpr64 + (size_t)tx] : 0ull;
+        s_word[t] = w;
+    }
+    if (!__syncthreads_or(w != 0ull)) return;
+    const int32_t r = t >> 2, c0 = (t & 3) * 16;                                // this lane's 16 cells of row r
+    const uint32_t mine = (uint32_t)(s_word[r] >> c0) & 0xffffu;
+    for (uint32_t b = mine; b; b &= b - 1u) {
+        const uint32_t c = (uint32_t)(r * FRT_T + c0 + __builtin_ctz(b));
+        s_lab[c] = c;
+    }
+    __syncthreads();
+    const uint64_t row = s_word[r], up = r > 0 ? s_word[r - 1] : 0ull;
+    for (uint32_t b = mine; b; b &= b - 1u) {
+        const int32_t lx = c0 + __builtin_ctz(b);
+        const uint32_t c = (uint32_t)(r * FRT_T + lx);
+        if (lx > 0 && ((row >> (lx - 1)) & 1ull)) front_unite(s_lab, c, c - 1u);
+        if ((up >> lx) & 1ull) front_unite(s_lab, c, c - FRT_T);                // (N joins NW and NE through its own W link and NE's)
+        else {
+            if (lx > 0 && ((up >> (lx - 1)) & 1ull)) front_unite(s_lab, c, c - FRT_T - 1u);
+            if (lx < FRT_T - 1 && ((up >> (lx + 1)) & 1ull)) front_unite(s_lab, c, c - FRT_T + 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t b = mine; b; b &= b - 1u) {
+        const int32_t lx = c0 + __builtin_ctz(b);
+        const uint32_t root = front_find(s_lab, (uint32_t)(r * FRT_T + lx));
+        label[(size_t)(y0 + r) * (size_t)W + (size_t)(x0 + lx)] = (uint32_t)(y0 + (int32_t)(root >> 6)) * (uint32_t)W + (uint32_t)(x0 + (int32_t)(root & 63u));
+    }
+}
+
+// a lane per cell of column 64 k (k = 1 .. ntx - 1; the first (ntx - 1) * H lanes) and of row 64 k (k = 1 .. nty - 1; W lanes each)
+__global__ void __launch_bounds__(FRT_NT)
+k_front_merge(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, int32_t ntx, int32_t nty, uint32_t *label) {
+    const int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x, nv = (int64_t)(ntx - 1) * H, nh = (int64_t)(nty - 1) * W;
+    if (i >= nv + nh) return;
+    auto bit = [&](int32_t x, int32_t y) -> bool {
+        return x >= 0 && x < W && y >= 0 && y < H && ((plane[(size_t)y * (size_t)wpr64 + (size_t)(x >> 6)] >> (x & 63)) & 1ull) != 0ull;
+    };
+    const bool column = i < nv;
+    int32_t x, y;
+    if (column) { x = ((int32_t)(i / H) + 1) * FRT_T; y = (int32_t)(i % H); }
+    else { const int64_t j = i - nv; y = ((int32_t)(j / W) + 1) * FRT_T; x = (int32_t)(j % W); }
+    if (!bit(x, y)) return;
+    const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x;
+    for (int32_t d = -1; d <= 1; d++) {
+        const int32_t ox = column ? x - 1 : x + d, oy = column ? y + d : y - 1;
+        if (bit(ox, oy)) front_unite(label, c, (uint32_t)oy * (uint32_t)W + (uint32_t)ox);
+    }
+}
+
+// a wavefront per word of the plane; roots: the root plane; wcount [words]
+__global__ void __launch_bounds__(FRT_NT)
+k_front_flatten(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, uint32_t *label, uint64_t *__restrict__ roots,
+                uint32_t *__restrict__ wcount) {
+    const int32_t lane = (int32_t)threadIdx.x & 63;
+    const int64_t word = (int64_t)blockIdx.x * (FRT_NT / 64) + ((int32_t)threadIdx.x >> 6);
+    if (word >= (int64_t)H * wpr64) return;                                     // (uniform per wavefront)
+    const uint64_t bits = plane[word];
+    bool root = false;
+    if ((bits >> lane) & 1ull) {
+        const int32_t y = (int32_t)(word / wpr64), x = (int32_t)(word - (int64_t)y * wpr64) * 64 + lane;
+        const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x, r = front_find(label, c);
+        if (r != c) __atomic_store_n(label + c, r, __ATOMIC_RELAXED);           // (another lane's chase reads the old parent or the root: both lead there)
+        root = r == c;
+    }
+    const uint64_t rb = __ballot(root);
+    if (lane == 0) {
+        roots[word] = rb;
+        wcount[word] = (uint32_t)__popcll(rb);
+    }
+}
+
+// vals [n] -> the exclusive prefix of each within its block of FRT_SCAN, in place; sums [blocks] the blocks' totals.  n = n_cap, or --
+// n_dev -- min(*n_dev, n_cap); what lies behind n counts as 0 and is neither read nor written
+__global__ void __launch_bounds__(FRT_NT)
+k_front_scan_blocks(uint32_t *__restrict__ vals, const uint32_t *__restrict__ n_dev, int64_t n_cap, uint32_t *__restrict__ sums) {
+    __shared__ uint32_t s[FRT_NT];
+    const int32_t t = (int32_t)threadIdx.x;
+    const int64_t n = n_dev ? std::min<int64_t>((int64_t)*n_dev, n_cap) : n_cap, base = (int64_t)blockIdx.x * FRT_SCAN + t * 4;
+    uint32_t v[4], mine = 0u;
+    for (int32_t k = 0; k < 4; k++) {
+        v[k] = base + k < n ? vals[base + k] : 0u;
+        mine += v[k];
+    }
+    s[t] = mine;
+    __syncthreads();
+    for (int32_t off = 1; off < FRT_NT; off <<= 1) {
+        const uint32_t add = t >= off ? s[t - off] : 0u;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    uint32_t run = s[t] - mine;
+    for (int32_t k = 0; k < 4; k++) {
+        if (base + k < n) vals[base + k] = run;
+        run += v[k];
+    }
+    if (t == FRT_NT - 1) sums[blockIdx.x] = s[t];
+}
+// ONE workgroup: sums [nb] -> their exclusive prefix in place, the total into *total
+__global__ void __launch_bounds__(FRT_NT)
+k_front_scan_top(uint32_t *__restrict__ sums, int32_t nb, uint32_t *__restrict__ total) {
+    __shared__ uint32_t s[FRT_NT];
+    const int32_t t = (int32_t)threadIdx.x;
+    uint32_t carry = 0u;
+    for (int32_t base = 0; base < nb; base += FRT_NT) {
+        const uint32_t v = base + t < nb ? sums[base + t] : 0u;
+        s[t] = v;
+        __syncthreads();
+        for (int32_t off = 1; off < FRT_NT; off <<= 1) {
+            const uint32_t add = t >= off ? s[t - off] : 0u;
+            __syncthreads();
+            s[t] += add;
+            __syncthreads();
+        }
+        if (base + t < nb) sums[base + t] = carry + s[t] - v;
+        carry += s[FRT_NT - 1];
+        __syncthreads();
+    }
+    if (t == 0) *total = carry;
+}
+
+// the first min(ctl[0], cap) entries of the table
+__global__ void __launch_bounds__(FRT_NT)
+k_front_table_init(gms_frontier *__restrict__ rec, unsigned long long *__restrict__ goal, const uint32_t *__restrict__ ctl, int32_t cap) {
+    const int64_t n = std::min<int64_t>((int64_t)ctl[0], cap);
+    for (int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FRT_NT) {
+        rec[i] = gms_frontier{0, 0, 0, GMS_REACH_FAR, INT_MAX, INT_MAX, -1, -1, -1, -1, 0, 0};
+        goal[i] = FRT_NO_GOAL;
+    }
+}
+
+// the minimum over the wavefront
+__device__ __forceinline__ uint64_t front_wave_min(uint64_t v) {
+#define GMS_STEP_(O)                                                                                                       \
+    {                                                                                                                      \
+        const uint64_t o = ((uint64_t)wave_xor<O>((uint32_t)(v >> 32)) << 32) | (uint64_t)wave_xor<O>((uint32_t)v);        \
+        v = o < v ? o : v;                                                                                                 \
+    }
+    GMS_BUTTERFLY(GMS_STEP_)
+#undef GMS_STEP_
+    return v;
+}
+// the sum of the positions of mask's set bits
+__device__ __forceinline__ uint32_t front_bit_sum(uint64_t mask) {
+    return (uint32_t)__popcll(mask & 0xaaaaaaaaaaaaaaaaull) + 2u * (uint32_t)__popcll(mask & 0xccccccccccccccccull) +
+           4u * (uint32_t)__popcll(mask & 0xf0f0f0f0f0f0f0f0ull) + 8u * (uint32_t)__popcll(mask & 0xff00ff00ff00ff00ull) +
+           16u * (uint32_t)__popcll(mask & 0xffff0000ffff0000ull) + 32u * (uint32_t)__popcll(mask & 0xffffffff00000000ull);
+}
+
+// a wavefront per word of the plane.  roots / wscan / wblocks: the root plane and the scan of its counts; cost (may be NULL) [H][W];
+// regions behind cap are left out (the host grows the table and runs this again)
+__global__ void __launch_bounds__(FRT_NT)
+k_front_reduce(const uint64_t *__restrict__ plane, const uint64_t *__restrict__ roots, const uint32_t *__restrict__ wscan, const uint32_t *__restrict__ wblocks,
+               int32_t wpr64, int32_t W, int32_t H, const uint32_t *__restrict__ label, const uint16_t *__restrict__ cost, gms_frontier *rec,
+               unsigned long long *goal, int32_t cap) {
+    const int32_t lane = (int32_t)threadIdx.x & 63;
+    const int64_t word = (int64_t)blockIdx.x * (FRT_NT / 64) + ((int32_t)threadIdx.x >> 6);
+    if (word >= (int64_t)H * wpr64) return;                                     // (uniform per wavefront)
+    const uint64_t bits = plane[word];
+    if (bits == 0ull) return;                                                   // (uniform)
+    const int32_t y = (int32_t)(word / wpr64), xw = (int32_t)(word - (int64_t)y * wpr64) * 64, x = xw + lane;
+    uint32_t region = FRT_NONE;
+    uint64_t key = FRT_NO_GOAL;
+    if ((bits >> lane) & 1ull) {
+        const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x, r = label[c];
+        const uint32_t ry = r / (uint32_t)W, rx = r - ry * (uint32_t)W;
+        const size_t rw = (size_t)ry * (size_t)wpr64 + (size_t)(rx >> 6);
+        region = wblocks[rw / FRT_SCAN] + wscan[rw] + (uint32_t)__popcll(roots[rw] & ((1ull << (rx & 63u)) - 1ull));
+        if (region >= (uint32_t)cap) region = FRT_NONE;
+        else if (r == c) { rec[region].anchor_x = x; rec[region].anchor_y = y; }                  // (the root alone writes these)
+        if (cost) {
+            const uint32_t v = cost[c];
+            if (v != (uint32_t)GMS_REACH_FAR) key = ((uint64_t)v << 32) | c;
+        }
+    }
+    uint64_t todo = __ballot(region != FRT_NONE);
+    while (todo) {                                                              // (uniform: one turn per distinct region of the word)
+        const int32_t leader = __builtin_ctzll(todo);
+        const uint32_t R = (uint32_t)__shfl((int)region, leader);
+        const bool in = region == R;
+        const uint64_t grp = __ballot(in);
+        const uint64_t best = cost ? front_wave_min(in ? key : FRT_NO_GOAL) : FRT_NO_GOAL;
+        if (lane == leader) {
+            const int32_t n = __popcll(grp);
+            gms_frontier *q = rec + R;
+            atomicAdd(&q->count, n);
+            atomicMin(&q->min_x, xw + __builtin_ctzll(grp));
+            atomicMax(&q->max_x, xw + 63 - __builtin_clzll(grp));
+            atomicMin(&q->min_y, y);
+            atomicMax(&q->max_y, y);
+            atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + front_bit_sum(grp)));
+            atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_y), (unsigned long long)((int64_t)n * y));
+            if (best != FRT_NO_GOAL) atomicMin(goal + R, (unsigned long long)best);
+        }
+        todo &= ~grp;
+    }
+}
+
+// the goals decoded; kept [i] = count >= min_size
+__global__ void __launch_bounds__(FRT_NT)
+k_front_finish(gms_frontier *__restrict__ rec, const unsigned long long *__restrict__ goal, const uint32_t *__restrict__ ctl, int32_t cap, int32_t min_size,
+               int32_t W, uint32_t *__restrict__ kept) {
+    const int64_t n = std::min<int64_t>((int64_t)ctl[0], cap);
+    for (int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FRT_NT) {
+        const uint64_t k = goal[i];
+        if (k != FRT_NO_GOAL) {
+            const uint32_t c = (uint32_t)k, gy = c / (uint32_t)W;
+            rec[i].goal_x = (int32_t)(c - gy * (uint32_t)W);
+            rec[i].goal_y = (int32_t)gy;
+            rec[i].goal_cost = (int32_t)(k >> 32);
+        }
+        kept[i] = rec[i].count >= min_size ? 1u : 0u;
+    }
+}
+
+// kept / kblocks: the scan of the flags; out [out_cap]
+__global__ void __launch_bounds__(FRT_NT)
+k_front_emit(const gms_frontier *__restrict__ rec, const uint32_t *__restrict__ kept, const uint32_t *__restrict__ kblocks, const uint32_t *__restrict__ ctl,
+             int32_t cap, int32_t min_size, gms_frontier *__restrict__ out, int32_t out_cap) {
+    const int64_t n = std::min<int64_t>((int64_t)ctl[0], cap);
+    for (int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FRT_NT) {
+        if (rec[i].count < min_size) continue;
+        const uint32_t at = kblocks[i / FRT_SCAN] + kept[i];
+        if (at < (uint32_t)out_cap) out[at] = rec[i];
+    }
+}
+
+// out [h][w]
+__global__ void __launch_bounds__(FRT_NT)
+k_front_labels(const uint64_t *__restrict__ plane, int32_t wpr64, const uint32_t *__restrict__ label, int32_t W, int32_t x0, int32_t y0, int32_t w, int32_t h,
+               uint32_t *__restrict__ out) {
+    const int64_t n = (int64_t)w * h;
+    for (int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FRT_NT) {
+        const int32_t y = y0 + (int32_t)(i / w), x = x0 + (int32_t)(i % w);
+        const bool on = (plane[(size_t)y * (size_t)wpr64 + (size_t)(x >> 6)] >> (x & 63)) & 1ull;
+        out[i] = on ? label[(size_t)y * (size_t)W + (size_t)x] : FRT_NONE;
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+// f against a W x H map: gms_frontiers_size's checks, then the rectangle inside [0, W] x [0, H] (gms_view_check's rule)
+static int front_check(const gms_frontiers *f, int32_t W, int32_t H, const char *what, int64_t *bytes) {
+    int rc = gms_frontiers_size(f, nullptr, nullptr, bytes);
+    if (rc) return rc;
+    if ((int64_t)f->x0 + f->w > W || (int64_t)f->y0 + f->h > H)
+        return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, f->x0, f->y0, f->w, f->h, W, H);
+    if ((int64_t)W * H >= (int64_t)FRT_NONE) return gms_fail(GMS_ERR_INVALID, "%s: a map of %d x %d cells exceeds a 32-bit label", what, W, H);
+    return GMS_OK;
+}
+// the checks the four entry points share, before anything is touched
+static int front_args(const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap, bool on_device, const char *what) {
+    if (cap < 0 || (cap > 0 && !records)) return gms_fail(GMS_ERR_INVALID, "%s: cap >= 0, and records unless cap == 0", what);
+    if (on_device && ((uintptr_t)cost & 1 || (uintptr_t)labels & 3 || (uintptr_t)records & 7))
+        return gms_fail(GMS_ERR_INVALID, "%s: the cost field must be 2-byte aligned, the labels 4-byte aligned, the records 8-byte aligned", what);
+    (void)f;
+    return GMS_OK;
+}
+
+static inline size_t front_table_bytes(int32_t cap) {
+    return (size_t)cap * (sizeof(gms_frontier) + sizeof(uint64_t) + sizeof(uint32_t)) + ((size_t)cap / FRT_SCAN + 1) * sizeof(uint32_t);
+}
+struct FrontTable {
+    gms_frontier *rec;
+    unsigned long long *goal;
+    uint32_t *kept, *kblocks;
+};
+static inline FrontTable front_table(const gms_map *m) {
+    FrontTable t;
+    const size_t cap = (size_t)m->front_cap;
+    t.rec = reinterpret_cast<gms_frontier *>(m->d_front_table);
+    t.goal = reinterpret_cast<unsigned long long *>(m->d_front_table + cap * sizeof(gms_frontier));
+    t.kept = reinterpret_cast<uint32_t *>(m->d_front_table + cap * (sizeof(gms_frontier) + sizeof(uint64_t)));
+    t.kblocks = t.kept + cap;
+    return t;
+}
+// a table of at least `need` regions (nothing of the handle's is in flight on it: the caller has waited)
+static int front_table_grow(gms_map *m, int64_t need) {
+    if (m->d_front_table && m->front_cap >= need) return GMS_OK;
+    const int64_t cap = (std::max<int64_t>(need, FRT_CAP0) + FRT_SCAN - 1) / FRT_SCAN * FRT_SCAN;
+    if (cap > INT_MAX / 2) return gms_fail(GMS_ERR_NOMEM, "gms_frontiers: a table of %lld regions", (long long)cap);
+    hipFree(m->d_front_table);
+    m->d_front_table = nullptr;
+    m->front_cap = 0;
+    if (hipMalloc(&m->d_front_table, front_table_bytes((int32_t)cap)) != hipSuccess) {
+        m->d_front_table = nullptr;
+        return gms_fail(GMS_ERR_NOMEM, "gms_frontiers: the region table's %zu bytes could not be allocated", front_table_bytes((int32_t)cap));
+    }
+    m->front_cap = (int32_t)cap;
+    return GMS_OK;
+}
+
+template <typename T>
+static int front_alloc(T **p, size_t bytes, const char *what) {
+    if (*p) return GMS_OK;
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        *p = nullptr;
+        return gms_fail(GMS_ERR_NOMEM, "gms_frontiers: %s of %zu bytes could not be allocated", what, bytes);
+    }
+    return GMS_OK;
+}
+// what a request needs on the handle (a handle's W and H never change: only the table ever grows)
+static int front_buffers(gms_map *m, bool per_particle) {
+    const size_t plane_bytes = (size_t)m->gd.H * (size_t)gms_clear_wpr(m) * sizeof(uint32_t), words = plane_bytes / sizeof(uint64_t);
+    int rc = front_alloc(&m->d_front_plane, 2 * plane_bytes, "the frontier plane and the root plane");
+    if (!rc) rc = front_alloc(&m->d_front_label, (size_t)m->gd.cells * sizeof(uint32_t), "the label field");
+    if (!rc) rc = front_alloc(&m->d_front_wscan, (words + words / FRT_SCAN + 1) * sizeof(uint32_t), "the root plane's scan");
+    if (!rc) rc = front_alloc(&m->d_front_ctl, 2 * sizeof(uint32_t), "the region counts");
+    if (!rc && per_particle) rc = front_alloc(&m->d_front_nf, plane_bytes, "the particle's second plane");
+    if (!rc) rc = front_table_grow(m, FRT_CAP0);
+    if (!rc && !m->h_front_ctl && hipHostMalloc(reinterpret_cast<void **>(&m->h_front_ctl), 2 * sizeof(uint32_t)) != hipSuccess) {
+        m->h_front_ctl = nullptr;
+        rc = gms_fail(GMS_ERR_NOMEM, "gms_frontiers: pinned memory for the read-back could not be allocated");
+    }
+    return rc;
+}
+
+static inline unsigned front_grid(int64_t n, int64_t per_block, int64_t most) { return (unsigned)std::max<int64_t>(1, std::min(most, (n + per_block - 1) / per_block)); }
+
+// The regions of ONE map's two planes (of logData as it stands) into the caller's device buffers; the handle's buffers exist.  Waits
+// on the stream once -- twice where the table has to grow -- and leaves the numbers of regions in h_front_ctl.
+static int front_run(gms_map *m, const uint32_t *d_occ, const uint32_t *d_nf, const gms_frontiers *f, const uint16_t *d_cost, uint32_t *d_labels,
+                     gms_frontier *d_records, int32_t cap) {
+    const int32_t W = m->gd.W, H = m->gd.H, wpr64 = (W + 63) / 64, ntx = (W + FRT_T - 1) / FRT_T, nty = (H + FRT_T - 1) / FRT_T;
+    if (nty > 65535) return gms_fail(GMS_ERR_INVALID, "gms_frontiers: a map of %d rows exceeds one launch", H);
+    const uint32_t *d_blocked = nullptr;
+    if (f->inflate > 0) {
+        int rc = gms_reach_inflate(m, d_occ, f->inflate, GMS_CLEAR_OCCUPIED, &d_blocked);
+        if (rc) return rc;
+    }
+    const int64_t words = (int64_t)H * wpr64, wblocks_n = (words + FRT_SCAN - 1) / FRT_SCAN;
+    uint64_t *plane = reinterpret_cast<uint64_t *>(m->d_front_plane), *roots = plane + words;
+    uint32_t *wscan = m->d_front_wscan, *wblocks = wscan + words, *ctl = m->d_front_ctl, *label = m->d_front_label;
+    hipStream_t st = m->stream;
+    hipLaunchKernelGGL(k_front_plane, dim3((unsigned)((words + FRT_NT - 1) / FRT_NT)), dim3(FRT_NT), 0, st, reinterpret_cast<const uint64_t *>(d_occ),
+                       reinterpret_cast<const uint64_t *>(d_nf), reinterpret_cast<const uint64_t *>(d_blocked), W, H, wpr64, plane);
+    hipLaunchKernelGGL(k_front_tiles, dim3((unsigned)ntx, (unsigned)nty), dim3(FRT_NT), 0, st, plane, wpr64, W, H, label);
+    const int64_t border = (int64_t)(ntx - 1) * H + (int64_t)(nty - 1) * W;
+    if (border > 0)
+        hipLaunchKernelGGL(k_front_merge, dim3((unsigned)((border + FRT_NT - 1) / FRT_NT)), dim3(FRT_NT), 0, st, plane, wpr64, W, H, ntx, nty, label);
+    const unsigned word_waves = (unsigned)((words + FRT_NT / 64 - 1) / (FRT_NT / 64));
+    hipLaunchKernelGGL(k_front_flatten, dim3(word_waves), dim3(FRT_NT), 0, st, plane, wpr64, W, H, label, roots, wscan);
+    hipLaunchKernelGGL(k_front_scan_blocks, dim3((unsigned)wblocks_n), dim3(FRT_NT), 0, st, wscan, (const uint32_t *)nullptr, words, wblocks);
+    hipLaunchKernelGGL(k_front_scan_top, dim3(1), dim3(FRT_NT), 0, st, wblocks, (int32_t)wblocks_n, ctl);
+    HIPCHK(hipGetLastError());
+    if (d_labels) {
+        const int64_t n = (int64_t)f->w * f->h;
+        hipLaunchKernelGGL(k_front_labels, dim3(front_grid(n, FRT_NT, 4096)), dim3(FRT_NT), 0, st, plane, wpr64, label, W, f->x0, f->y0, f->w, f->h, d_labels);
+        HIPCHK(hipGetLastError());
+    }
+    for (int32_t pass = 0;; pass++) {
+        const int32_t tcap = m->front_cap;
+        const FrontTable t = front_table(m);
+        const unsigned tgrid = front_grid(tcap, FRT_NT, 1024);
+        hipLaunchKernelGGL(k_front_table_init, dim3(tgrid), dim3(FRT_NT), 0, st, t.rec, t.goal, ctl, tcap);
+        hipLaunchKernelGGL(k_front_reduce, dim3(word_waves), dim3(FRT_NT), 0, st, plane, roots, wscan, wblocks, wpr64, W, H, label, d_cost, t.rec, t.goal, tcap);
+        hipLaunchKernelGGL(k_front_finish, dim3(tgrid), dim3(FRT_NT), 0, st, t.rec, t.goal, ctl, tcap, f->min_size, W, t.kept);
+        hipLaunchKernelGGL(k_front_scan_blocks, dim3((unsigned)(tcap / FRT_SCAN)), dim3(FRT_NT), 0, st, t.kept, ctl, (int64_t)tcap, t.kblocks);
+        hipLaunchKernelGGL(k_front_scan_top, dim3(1), dim3(FRT_NT), 0, st, t.kblocks, tcap / FRT_SCAN, ctl + 1);
+        if (cap > 0) hipLaunchKernelGGL(k_front_emit, dim3(tgrid), dim3(FRT_NT), 0, st, t.rec, t.kept, t.kblocks, ctl, tcap, f->min_size, d_records, cap);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(m->h_front_ctl, ctl, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if ((int64_t)m->h_front_ctl[0] <= tcap) return GMS_OK;
+        if (pass > 0) return gms_fail(GMS_ERR_INTERNAL, "gms_frontiers: %u regions after the table grew to %d", m->h_front_ctl[0], tcap);
+        int rc = front_table_grow(m, (int64_t)m->h_front_ctl[0]);                // (more regions than the table held: steps 6 and 7 again)
+        if (rc) return rc;
+    }
+}
+
+// the staging of a host form behind the views' 16 bytes: [labels][records][cost], each part padded to 16 bytes
+struct FrontStage {
+    size_t labels, records, cost, total;
+};
+static FrontStage front_stage(int64_t label_bytes, bool labels, int32_t cap, bool cost, int64_t cells) {
+    FrontStage s;
+    s.labels = 0;
+    s.records = labels ? (((size_t)label_bytes + 15) & ~(size_t)15) : 0;
+    s.cost = s.records + (((size_t)cap * sizeof(gms_frontier) + 15) & ~(size_t)15);
+    s.total = s.cost + (cost ? (size_t)cells * sizeof(uint16_t) : 0);
+    return s;
+}
+
+// what a host form copies back once front_run has returned
+static int front_copy_back(gms_map *m, const unsigned char *base, const FrontStage &sg, int64_t label_bytes, uint32_t *labels, gms_frontier *records, int32_t cap,
+                           int32_t *shown) {
+    const int64_t stored = std::min<int64_t>(m->h_front_ctl[1], cap);
+    if (labels) HIPCHK(hipMemcpyAsync(labels, base + 16 + sg.labels, (size_t)label_bytes, hipMemcpyDeviceToHost, m->stream));
+    if (stored > 0) HIPCHK(hipMemcpyAsync(records, base + 16 + sg.records, (size_t)stored * sizeof(gms_frontier), hipMemcpyDeviceToHost, m->stream));
+    if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return GMS_OK;
+}
+
+static int map_frontiers(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                         int32_t *n_found, bool on_device) {
+    REQUIRE(m && f, "gms_map_frontiers: null argument (the map and the request are required)");
+    REQUIRE(mi >= 0 && mi < m->n_maps, "gms_map_frontiers: map index out of range");
+    int64_t bytes = 0;
+    int rc = front_check(f, m->gd.W, m->gd.H, "gms_map_frontiers", &bytes);
+    if (!rc) rc = front_args(f, cost, labels, records, cap, on_device, on_device ? "gms_map_frontiers_dev" : "gms_map_frontiers");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    rc = front_buffers(m, false);
+    if (rc) return rc;
+    const FrontStage sg = front_stage(bytes, labels != nullptr, cap, cost != nullptr, m->gd.cells);
+    unsigned char *base = nullptr;
+    const uint16_t *d_cost = cost;
+    uint32_t *d_labels = labels;
+    gms_frontier *d_records = records;
+    if (!on_device) {
+        rc = gms_view_staging(m, (int64_t)sg.total, &base);
+        if (rc) return rc;
+        d_labels = labels ? reinterpret_cast<uint32_t *>(base + 16 + sg.labels) : nullptr;
+        d_records = cap > 0 ? reinterpret_cast<gms_frontier *>(base + 16 + sg.records) : nullptr;
+        if (cost) {
+            HIPCHK(hipMemcpyAsync(base + 16 + sg.cost, cost, (size_t)m->gd.cells * sizeof(uint16_t), hipMemcpyHostToDevice, m->stream));
+            d_cost = reinterpret_cast<const uint16_t *>(base + 16 + sg.cost);
+        }
+    }
+    const uint32_t *occ = nullptr, *nf = nullptr;
+    rc = gms_clear_plane(m, GMS_CLEAR_OCCUPIED, &occ);
+    if (!rc) rc = gms_clear_plane(m, GMS_CLEAR_NOT_FREE, &nf);
+    if (rc) return rc;
+    const size_t at = (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m);
+    rc = front_run(m, occ + at, nf + at, f, d_cost, d_labels, d_records, cap);
+    if (rc) return rc;
+    if (n_found) *n_found = (int32_t)m->h_front_ctl[1];
+    return on_device ? GMS_OK : front_copy_back(m, base, sg, bytes, labels, records, cap, nullptr);
+}
+
+static int slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                          int32_t *n_found, int32_t *shown, bool on_device) {
+    REQUIRE(s && f, "gms_slam_frontiers: null argument (the handle and the request are required)");
+    gms_map *m = s->map;
+    int64_t bytes = 0;
+    int rc = front_check(f, m->gd.W, m->gd.H, "gms_slam_frontiers", &bytes);
+    if (!rc) rc = front_args(f, cost, labels, records, cap, on_device, on_device ? "gms_slam_frontiers_dev" : "gms_slam_frontiers");
+    if (rc) return rc;
+    if (which == GMS_VIEW_STRONGEST) {
+        REQUIRE(f->filter >= 0 && f->filter < s->n_filters, "gms_slam_frontiers: gms_frontiers.filter out of range");
+        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_frontiers: a shard of a filter (its strongest particle may live on another rank): name the particle");
+        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_frontiers: no update since the handle was created or reset: there is no strongest particle yet");
+    } else REQUIRE(which >= 0 && which < s->n, "gms_slam_frontiers: particle index out of range");
+    HIPCHK(hipSetDevice(m->device));
+    rc = front_buffers(m, true);
+    if (rc) return rc;
+    const FrontStage sg = front_stage(bytes, labels != nullptr, cap, cost != nullptr, m->gd.cells);
+    const int32_t filter = which == GMS_VIEW_STRONGEST ? f->filter : 0;
+    unsigned char *base = nullptr;
+    const uint16_t *d_cost = cost;
+    uint32_t *d_labels = labels;
+    gms_frontier *d_records = records;
+    int32_t *d_shown = shown;
+    if (!on_device) {
+        rc = gms_view_staging(m, (int64_t)sg.total, &base);
+        if (rc) return rc;
+        d_shown = reinterpret_cast<int32_t *>(base);
+        d_labels = labels ? reinterpret_cast<uint32_t *>(base + 16 + sg.labels) : nullptr;
+        d_records = cap > 0 ? reinterpret_cast<gms_frontier *>(base + 16 + sg.records) : nullptr;
+        if (cost) {
+            HIPCHK(hipMemcpyAsync(base + 16 + sg.cost, cost, (size_t)m->gd.cells * sizeof(uint16_t), hipMemcpyHostToDevice, m->stream));
+            d_cost = reinterpret_cast<const uint16_t *>(base + 16 + sg.cost);
+        }
+    }
+    rc = gms_clear_plane_slam(s, which, filter, GMS_CLEAR_OCCUPIED, d_shown);                     // both predicates of the shown particle
+    if (!rc) rc = gms_clear_plane_slam(s, which, filter, GMS_CLEAR_NOT_FREE, nullptr, m->d_front_nf);
+    if (rc) return rc;
+    rc = front_run(m, m->d_clear_scratch, m->d_front_nf, f, d_cost, d_labels, d_records, cap);
+    if (rc) return rc;
+    if (n_found) *n_found = (int32_t)m->h_front_ctl[1];
+    return on_device ? GMS_OK : front_copy_back(m, base, sg, bytes, labels, records, cap, shown);
+}
+
+extern "C" {
+
+int gms_frontiers_size(const gms_frontiers *f, int32_t *out_w, int32_t *out_h, int64_t *bytes) {
+    REQUIRE(f, "gms_frontiers: null request");
+    REQUIRE(f->w >= 1 && f->h >= 1, "gms_frontiers: w and h must be at least 1");
+    REQUIRE(f->x0 >= 0 && f->y0 >= 0, "gms_frontiers: x0 and y0 must not be negative");
+    REQUIRE(f->min_size >= 1, "gms_frontiers: min_size must be at least 1");
+    REQUIRE(f->inflate >= 0 && f->inflate <= 255, "gms_frontiers: 0 <= inflate <= 255 cells");
+    if (out_w) *out_w = f->w;
+    if (out_h) *out_h = f->h;
+    if (bytes) *bytes = (int64_t)f->w * f->h * (int64_t)sizeof(uint32_t);
+    return GMS_OK;
+}
+int gms_map_frontiers(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                      int32_t *n_found) {
+    return map_frontiers(m, mi, f, cost, labels, records, cap, n_found, false);
+}
+int gms_map_frontiers_dev(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
+                          int32_t cap, int32_t *n_found) {
+    return map_frontiers(m, mi, f, dev_cost, dev_labels, dev_records, cap, n_found, true);
+}
+int gms_slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                       int32_t *n_found, int32_t *shown) {
+    return slam_frontiers(s, which, f, cost, labels, records, cap, n_found, shown, false);
+}
+int gms_slam_frontiers_dev(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
+                           int32_t cap, int32_t *n_found, int32_t *dev_shown) {
+    return slam_frontiers(s, which, f, dev_cost, dev_labels, dev_records, cap, n_found, dev_shown, true);
+}
+
+}  // extern "C"

@@ -132,6 +132,15 @@ struct gms_map {
     uint32_t *h_reach_ctl;        // pinned: the first 8 words of it, read back once per batch of rounds
     int32_t reach_rounds;         // gms_map_reach_stats: rounds launched for the last field
     int64_t reach_tile_runs;      // ... and tile relaxations that ran
+    // frontier regions (gms_frontier.hip); allocated by the first request, the region table grows and never shrinks
+    uint32_t *d_front_plane;      // [2][H][cast_wpr] the frontier plane, and the plane of the regions' roots (label == own index)
+    uint32_t *d_front_nf;         // [H][cast_wpr] a gms_slam's: the shown particle's second plane (its first: d_clear_scratch)
+    uint32_t *d_front_label;      // [H][W] the label field of the whole map; defined where the frontier plane has a bit
+    uint32_t *d_front_wscan;      // [words] the root plane's word counts, scanned within blocks of FRT_SCAN | [blocks] the blocks' offsets
+    unsigned char *d_front_table; // [front_cap] gms_frontier | [front_cap] the goals' 64-bit keys | [front_cap] the kept flags, scanned | [blocks] their offsets
+    int32_t front_cap;            // regions the table holds
+    uint32_t *d_front_ctl;        // {regions, regions with count >= min_size}
+    uint32_t *h_front_ctl;        // pinned: read back once per request
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -503,7 +512,10 @@ static inline int32_t gms_clear_wpr(const gms_map *m) { return 2 * ((m->gd.W + 6
 int gms_clear_plane(gms_map *m, int32_t mode, const uint32_t **plane);
 int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out);
 struct gms_slam;
-int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown);
+int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown, uint32_t *d_dst = nullptr);   // d_dst: another plane than the scratch one
+// the cost-to-go fields' blocked plane for inflate > 0 (gms_reach.hip): the clearance field of ONE map's obstacle plane at R = inflate over
+// the whole map, balloted into gms_map::d_reach_plane (both allocated by the first request); the frontier regions share it
+int gms_reach_inflate(gms_map *m, const uint32_t *d_obstacles, int32_t inflate, int32_t mode, const uint32_t **d_blocked);
 
 void gms_launch_pf_init(gms_pf *pf);
 void gms_launch_pf_pose_trig(gms_pf *pf, const float *d_src);

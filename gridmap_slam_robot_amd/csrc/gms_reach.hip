@@ -249,13 +249,28 @@ static int reach_buffers(gms_map *m, bool inflated) {
     const size_t cells = (size_t)m->gd.cells, ntiles = (size_t)((m->gd.W + RCH_T - 1) / RCH_T) * (size_t)((m->gd.H + RCH_T - 1) / RCH_T);
     int rc = reach_alloc(&m->d_reach_field, ((cells + 1) & ~(size_t)1) * sizeof(uint16_t), "the working field");
     if (!rc) rc = reach_alloc(&m->d_reach_ctl, (RCH_CTL_WORDS + 2 * ntiles) * sizeof(uint32_t), "the tiles' flags");
-    if (!rc && inflated) rc = reach_alloc(&m->d_reach_d2, cells * sizeof(uint16_t), "the inflation's clearance field");
-    if (!rc && inflated) rc = reach_alloc(&m->d_reach_plane, (size_t)m->gd.H * (size_t)gms_clear_wpr(m) * sizeof(uint32_t), "the blocked plane");
+    // (inflate > 0: the clearance field and the blocked plane are gms_reach_inflate's)
     if (!rc && !m->h_reach_ctl && hipHostMalloc(reinterpret_cast<void **>(&m->h_reach_ctl), RCH_CTL_WORDS * sizeof(uint32_t)) != hipSuccess) {
         m->h_reach_ctl = nullptr;
         rc = gms_fail(GMS_ERR_NOMEM, "gms_reach: pinned memory for the read-back could not be allocated");
     }
     return rc;
+}
+
+// inflate > 0: the blocked plane of ONE map's obstacle plane -- "clearance at R = inflate, balloted" -- in d_reach_plane
+int gms_reach_inflate(gms_map *m, const uint32_t *d_obstacles, int32_t inflate, int32_t mode, const uint32_t **d_blocked) {
+    const int32_t W = m->gd.W, H = m->gd.H, wpr64 = (W + 63) / 64;
+    int rc = reach_alloc(&m->d_reach_d2, (size_t)m->gd.cells * sizeof(uint16_t), "the inflation's clearance field");
+    if (!rc) rc = reach_alloc(&m->d_reach_plane, (size_t)H * (size_t)gms_clear_wpr(m) * sizeof(uint32_t), "the blocked plane");
+    if (rc) return rc;
+    const gms_clearance c = {0, 0, W, H, inflate, mode, 0};
+    rc = gms_clear_launch(m, d_obstacles, &c, m->d_reach_d2);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_reach_block, dim3((unsigned)((wpr64 + 3) / 4), (unsigned)H), dim3(256), 0, m->stream, m->d_reach_d2, W, wpr64,
+                       reinterpret_cast<uint64_t *>(m->d_reach_plane));
+    HIPCHK(hipGetLastError());
+    *d_blocked = m->d_reach_plane;
+    return GMS_OK;
 }
 
 // who plants the seeds: a list on the device, or (seeds NULL) the shown particle of a gms_slam
@@ -273,13 +288,8 @@ static int reach_run(gms_map *m, const uint32_t *d_obstacles, const gms_reach *r
     if (nty > 65535) return gms_fail(GMS_ERR_INVALID, "gms_reach: a map of %d rows exceeds one launch", H);
     const uint32_t *d_blocked = d_obstacles;
     if (r->inflate > 0) {
-        const gms_clearance c = {0, 0, W, H, r->inflate, r->mode, 0};
-        int rc = gms_clear_launch(m, d_obstacles, &c, m->d_reach_d2);
+        int rc = gms_reach_inflate(m, d_obstacles, r->inflate, r->mode, &d_blocked);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_reach_block, dim3((unsigned)((wpr64 + 3) / 4), (unsigned)H), dim3(256), 0, m->stream, m->d_reach_d2, W, wpr64,
-                           reinterpret_cast<uint64_t *>(m->d_reach_plane));
-        HIPCHK(hipGetLastError());
-        d_blocked = m->d_reach_plane;
     }
     const uint64_t *plane = reinterpret_cast<const uint64_t *>(d_blocked);
     const int64_t words32 = (m->gd.cells + 1) / 2;

@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
-__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres",
+__all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
            "cells_of_poses", "descend"]
 
 
@@ -201,6 +201,43 @@ def reach_metres(field, resolution: float) -> np.ndarray:
     out = a.astype(np.float64) / _lib.GMS_REACH_AXIS * float(resolution)
     out[a == _lib.GMS_REACH_FAR] = np.inf
     return out
+
+
+def _frontier_args(W: int, H: int, rect, min_size: int, inflate: int, filter: int = 0):
+    """(gms_frontiers, label field shape, bytes) of a frontier request of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
+    f = _lib.GmsFrontiers(x0, y0, w, h, int(min_size), int(inflate), int(filter), 0)
+    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    check(load().gms_frontiers_size(C.byref(f), C.byref(ow), C.byref(oh), C.byref(nbytes)))
+    return f, (oh.value, ow.value), nbytes.value
+
+
+def _frontier_cost(cost, W: int, H: int):
+    """a whole-map cost-to-go field (what reach() returns for the full rectangle) as the contiguous uint16 [H][W] the library takes"""
+    if cost is None:
+        return None
+    a = np.asarray(cost)
+    if a.shape != (H, W) or a.dtype != np.uint16:
+        raise ValueError(f"frontiers: cost must be the whole map's uint16 [{H}][{W}] cost-to-go field, not {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _frontier_device(t, nbytes: int, what: str):
+    """the device address of a caller's torch tensor of at least nbytes (None: the output is omitted)"""
+    if t is None:
+        return None
+    if not (getattr(t, "is_cuda", False) and t.is_contiguous()):
+        raise ValueError(f"frontiers: {what} must be a contiguous torch tensor on the device")
+    if t.numel() * t.element_size() < nbytes:
+        raise ValueError(f"frontiers: {what} holds {t.numel() * t.element_size()} bytes, {nbytes} are needed")
+    return C.c_void_p(int(t.data_ptr()))
+
+
+def frontier_centroids(records) -> np.ndarray:
+    """The centroids of frontier regions (GridMap.frontiers' records) in cells, float64 [n][2] = (x, y): sum / count"""
+    r = np.asarray(records)
+    n = r["count"].astype(np.float64)
+    return np.stack([r["sum_x"] / n, r["sum_y"] / n], axis=-1)
 
 
 def cells_of_poses(poses, position, resolution: float):
@@ -452,6 +489,37 @@ class GridMap:
     def reach_dev(self, out, seeds, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None, mi: int = 0):
         """reach() from device seeds into out, on the handle's stream; the call waits on that stream between batches of rounds"""
         return self.reach(seeds, max_cost, inflate, not_free, rect, mi, out)
+
+    def frontiers(self, min_size: int = 1, inflate: int = 0, cost=None, rect=None, labels: bool = False, cap: int = 4096, mi: int = 0):
+        """The frontier regions (gridmapslam.h "frontier regions") of map mi: the known-free cells (logData < 0) with a never-observed
+        axis neighbour inside the map (0, -0.0, NaN), without those that have an occupied cell within `inflate` cells, grouped into
+        maximal 8-connected regions.  Returns (records, n_found): records a structured array (FRONTIER_DTYPE: anchor, count, box,
+        coordinate sums, goal) of the regions with count >= min_size in ascending anchor order, at most cap of them; n_found how
+        many qualify.  cost: the whole map's cost-to-go field (the array reach() returns) -- a region's goal is then its member of the
+        smallest cost, goal_cost that cost; without it goal = (-1, -1).  labels=True appends the label field of rect = (x0, y0, w, h)
+        (None: the whole map), uint32 [h][w]: every frontier cell its region's anchor index y * W + x, GMS_FRONTIER_NONE elsewhere.
+        Centroids: frontier_centroids()."""
+        f, shape, _ = _frontier_args(self.W, self.H, rect, min_size, inflate)
+        cst = _frontier_cost(cost, self.W, self.H)
+        rec = np.zeros(int(cap), dtype=_lib.FRONTIER_DTYPE)
+        lab = np.empty(shape, dtype=np.uint32) if labels else None
+        n = C.c_int32(0)
+        check(load().gms_map_frontiers(self._h, int(mi), C.byref(f), None if cst is None else ptr(cst), None if lab is None else ptr(lab),
+                                       ptr(rec) if cap else None, int(cap), C.byref(n)))
+        out = (rec[:min(n.value, int(cap))], int(n.value))
+        return out + (lab,) if labels else out
+
+    def frontiers_dev(self, records=None, labels=None, cost=None, min_size: int = 1, inflate: int = 0, rect=None, mi: int = 0) -> int:
+        """frontiers() with device memory on the handle's stream: records (room for cap = bytes // 56 gms_frontier, 8-byte aligned),
+        labels (h * w * 4 bytes, 4-byte aligned) and cost (the whole map's uint16 field) are contiguous torch device tensors, any of
+        them None.  Returns n_found; the call waits on the stream once (once more when the handle's region table has to grow), so the
+        outputs are complete when it returns."""
+        f, _, nbytes = _frontier_args(self.W, self.H, rect, min_size, inflate)
+        cap = 0 if records is None else records.numel() * records.element_size() // _lib.FRONTIER_DTYPE.itemsize
+        n = C.c_int32(0)
+        check(load().gms_map_frontiers_dev(self._h, int(mi), C.byref(f), _frontier_device(cost, self.W * self.H * 2, "cost"),
+                                           _frontier_device(labels, nbytes, "labels"), _frontier_device(records, 0, "records"), int(cap), C.byref(n)))
+        return int(n.value)
 
     def reach_stats(self) -> dict:
         """diagnostics of the last cost-to-go field made on this handle: {"rounds": launches over the tiles, "tile_runs": tile
@@ -1211,6 +1279,34 @@ class _SlamHandle:
                                     C.byref(shown)))
         return field, int(shown.value)
 
+    def _frontiers(self, which, filter: int, min_size: int, inflate: int, cost, rect, labels, cap: int, records_out, labels_out, shown_out):
+        """gms_slam_frontiers[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device)"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('frontiers: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        f, shape, nbytes = _frontier_args(self.W, self.H, rect, min_size, inflate, filter)
+        n = C.c_int32(0)
+        if records_out is not None or labels_out is not None or shown_out is not None or getattr(cost, "is_cuda", False):
+            cap = 0 if records_out is None else records_out.numel() * records_out.element_size() // _lib.FRONTIER_DTYPE.itemsize
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("frontiers: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_frontiers_dev(self._h, int(which), C.byref(f), _frontier_device(cost, self.W * self.H * 2, "cost"),
+                                                _frontier_device(labels_out, nbytes, "labels_out"), _frontier_device(records_out, 0, "records_out"),
+                                                int(cap), C.byref(n), sh))
+            return int(n.value)
+        cst = _frontier_cost(cost, self.W, self.H)
+        rec = np.zeros(int(cap), dtype=_lib.FRONTIER_DTYPE)
+        lab = np.empty(shape, dtype=np.uint32) if labels else None
+        shown = C.c_int32(-1)
+        check(load().gms_slam_frontiers(self._h, int(which), C.byref(f), None if cst is None else ptr(cst), None if lab is None else ptr(lab),
+                                        ptr(rec) if cap else None, int(cap), C.byref(n), C.byref(shown)))
+        out = (rec[:min(n.value, int(cap))], int(n.value))
+        return (out + (lab,) if labels else out) + (int(shown.value),)
+
     def set_history(self, capacity: int):
         """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
         resampling (0: off, the memory freed).  reset() clears the history and keeps it on.  Refused on a shard of a filter."""
@@ -1392,6 +1488,14 @@ class SLAMParticleMaps(_SlamHandle):
         the shown particle's own pose cell, picked on the device.  out / shown_out: torch device tensors (seeds then a device int32
         tensor or None).  Diagnostics: grid_map.reach_stats()."""
         return self._reach(which, 0, seeds, max_cost, inflate, not_free, rect, out, shown_out)
+
+    def frontiers(self, which="strongest", min_size: int = 1, inflate: int = 0, cost=None, rect=None, labels: bool = False, cap: int = 4096,
+                  records_out=None, labels_out=None, shown_out=None):
+        """The frontier regions of particle `which`'s OWN map (GridMap.frontiers' values): (records, n_found[, labels], shown).  which =
+        a particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  cost: that
+        particle's whole-map field, as reach() returns it.  records_out / labels_out / shown_out (torch device tensors, cost then a
+        device tensor or None): the device form, which returns n_found alone."""
+        return self._frontiers(which, 0, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
 
     def trajectory(self, which="strongest", out=None, shown_out=None):
         """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
@@ -1603,6 +1707,16 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._reach(which, filter, seeds, max_cost, inflate, not_free, rect, out, shown_out)
+
+    def frontiers(self, which="strongest", filter: int = 0, min_size: int = 1, inflate: int = 0, cost=None, rect=None, labels: bool = False,
+                  cap: int = 4096, records_out=None, labels_out=None, shown_out=None):
+        """SLAMParticleMaps.frontiers for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
+        is the handle-wide slot filter * num_particles + k whose regions were made, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._frontiers(which, filter, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown

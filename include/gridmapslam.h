@@ -698,6 +698,84 @@ int gms_slam_reach_dev(gms_slam *s, int32_t which, const gms_reach *r, const int
  * launches every tile; those that are not active leave at once).  A gms_slam's: on the gms_map of gms_slam_handles. */
 int gms_map_reach_stats(const gms_map *m, int32_t *rounds, int64_t *tile_runs);
 
+/* ---- frontier regions: where the exploration goals are -----------------------------------------------------------------------------
+ * The known-free cells that border never-observed space, grouped into regions a caller can rank -- with a cost-to-go field, by how far
+ * it is to drive there.  This library's own definition (the reference has no such method); all of it is integer arithmetic and every
+ * output is unique.
+ *
+ * CELL CLASSES: FREE is logData < 0, OCCUPIED is logData > 0, UNKNOWN is neither: 0, -0.0 and NaN.  In the planes' terms: free = not the
+ * clearance fields' second plane; unknown = the second plane and not the casts' plane.
+ * A FRONTIER CELL is a FREE cell with at least one of its four axis neighbours INSIDE the map UNKNOWN.  Cells outside the map are not
+ * unknown: the map's border makes no frontier (the clearance fields' rule).  A diagonal-only unknown neighbour does not count.  With
+ * inflate > 0 (0 <= inflate <= 255 cells) a cell with an OCCUPIED cell within `inflate` cells of it, d2 <= inflate^2, is no frontier
+ * cell: exactly the cost-to-go fields' BLOCKED under GMS_CLEAR_OCCUPIED, so a goal is a cell gms_map_reach can give a cost.
+ * A REGION is a maximal 8-connected set of frontier cells (plain 8-connectivity, no corner rule), taken over the WHOLE map.  Its
+ * ANCHOR is its member with the smallest linear index y * W + x.
+ *
+ * Two outputs, either may be omitted (NULL):
+ *   the LABEL FIELD   of the rectangle [x0, x0 + w) x [y0, y0 + h) -- gms_view's rules: inside [0, W] x [0, H], GMS_ERR_INVALID
+ *                     otherwise, nothing touched --, uint32_t [h][w], row 0 = y0: every frontier cell holds its region's anchor index
+ *                     y * W + x (whatever min_size is), every other cell GMS_FRONTIER_NONE.  The rectangle is checked even when no
+ *                     label field is asked for.
+ *   the REGION TABLE  gms_frontier records of the regions with count >= min_size (min_size >= 1), in ascending anchor order; the first
+ *                     `cap` of them are stored, *n_found (may be NULL) is the number that qualify and may exceed cap.  cap == 0 with
+ *                     records == NULL is allowed.
+ * THE GOAL: `cost` (may be NULL) is a WHOLE-MAP uint16_t [H][W] field, what gms_map_reach returns for the full rectangle.  With it a
+ * region's goal is its member of the smallest cost, ties to the smallest linear index, and goal_cost that cost; a region whose members
+ * are all GMS_REACH_FAR, and every region when cost is NULL, has goal = (-1, -1) and goal_cost = GMS_REACH_FAR.
+ *
+ * "Sees the map as a download would return it at that moment" (a deferred apply pass is flushed first, an owed resampling copy is
+ * looked through, the generation of a per-particle map is picked from the epoch counters), "changes no later result of its handle"
+ * and the argument checks before anything is enqueued are the clearance fields' rules.  A map of 2^32 - 1 cells or more is refused.
+ *
+ * How: (1) the frontier plane, one bit per cell in the casts' layout, a lane per 64-bit word from the casts' plane and the clearance
+ * fields' second plane read in place (packed only when stale: gms_map_cast_plane_builds does not move for a current plane), with
+ * inflate > 0 also from the cost-to-go fields' blocked plane; (2) one workgroup per 64 x 64 tile -- a tile without a frontier cell
+ * leaves at once -- unites its cells in LDS and writes every cell's label as the global index of the tile-local smallest member;
+ * (3) the pairs of cells adjacent across a tile edge or corner are united in the global label field, lock-free, the larger root
+ * always hung under the smaller, so the final root is the anchor; (4) every frontier cell chases to its root; (5) the roots are
+ * numbered in anchor order by a scan over the root plane's word counts; (6) count, box, sums and goal by integer atomics, the lanes
+ * of a wavefront that share a label combined first; (7) a second scan keeps the regions with count >= min_size.  Scans that span
+ * workgroups are separate launches; no workgroup waits on another.  The number of regions is known on the device only: every form
+ * reads it back once, together with *n_found, so EVERY form, _dev included, waits on the handle's stream once -- and once more in a
+ * call that finds more regions than the handle's table holds so far: the table grows (it never shrinks) and steps 6 and 7 run
+ * again. */
+#define GMS_FRONTIER_NONE 0xFFFFFFFFu                          /* a label: no frontier cell */
+typedef struct gms_frontiers {
+    int32_t x0, y0, w, h;       /* the cell rectangle of the label field */
+    int32_t min_size;           /* >= 1: the smallest region the table lists */
+    int32_t inflate;            /* cells, 0 .. 255 */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+    int32_t pad;                /* not read */
+} gms_frontiers;
+typedef struct gms_frontier {   /* 56 bytes */
+    int32_t anchor_x, anchor_y; /*  0,  4: the member of the smallest linear index */
+    int32_t count;              /*  8: members */
+    int32_t goal_cost;          /* 12: the goal's cost, or GMS_REACH_FAR */
+    int32_t min_x, min_y;       /* 16, 20: the bounding box, inclusive */
+    int32_t max_x, max_y;       /* 24, 28 */
+    int32_t goal_x, goal_y;     /* 32, 36: the member of the smallest cost, or (-1, -1) */
+    int64_t sum_x, sum_y;       /* 40, 48: the members' coordinate sums; the centroid is sum / count, the caller's division */
+} gms_frontier;
+/* The label field's size in cells and bytes (any of the three may be NULL).  Pure host code: checks w, h >= 1, x0, y0 >= 0, min_size
+ * and inflate -- not the map's bounds, which it does not know. */
+int gms_frontiers_size(const gms_frontiers *f, int32_t *out_w, int32_t *out_h, int64_t *bytes);
+/* Map mi of a shared or batched map.  cost, labels, records: host memory, staged through the views' buffer.
+ * _dev: dev_cost (2-byte aligned), dev_labels (4-byte aligned) and dev_records (8-byte aligned) are device memory, read and written
+ * on the handle's stream (a misaligned pointer: GMS_ERR_INVALID, nothing touched); n_found stays a HOST pointer, and the call waits
+ * on that stream as said above, so both outputs are complete when it returns. */
+int gms_map_frontiers(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                      int32_t *n_found);
+int gms_map_frontiers_dev(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
+                          int32_t cap, int32_t *n_found);
+/* One particle's own map of the per-particle filter: `which`, GMS_VIEW_STRONGEST, f->filter, *shown (may be NULL; _dev: a device
+ * int32_t *) and the GMS_ERR_STATE cases are gms_slam_view's.  gms_slam_clearance's pre-pass packs both of the shown particle's
+ * planes, and the shared maps' kernels run on those. */
+int gms_slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                       int32_t *n_found, int32_t *shown);
+int gms_slam_frontiers_dev(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
+                           int32_t cap, int32_t *n_found, int32_t *dev_shown);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

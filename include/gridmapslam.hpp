@@ -181,6 +181,23 @@ public:
     gms_reach fullReach(int maxCost = 0xFFFE, int inflate = 0, bool notFree = true) const {
         return gms_reach{0, 0, w_, hgt_, maxCost, inflate, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, 0};
     }
+    /** The frontier regions (gridmapslam.h "frontier regions") of map mi: the records of the regions with count >= f.min_size in
+     *  ascending anchor order, at most cap of them; *found (may be null) how many qualify.  cost (may be null): the whole map's
+     *  cost-to-go field, [H][W]; labels (may be null) receives f's rectangle of the label field, [h][w] */
+    std::vector<gms_frontier> frontiers(const gms_frontiers &f, int cap = 4096, const std::vector<uint16_t> *cost = nullptr,
+                                        std::vector<uint32_t> *labels = nullptr, int *found = nullptr, int mi = 0) {
+        int64_t bytes = 0;
+        check(gms_frontiers_size(&f, nullptr, nullptr, &bytes));
+        if (labels) labels->resize((size_t)bytes / sizeof(uint32_t));
+        std::vector<gms_frontier> rec((size_t)cap);
+        int32_t n = 0;
+        check(gms_map_frontiers(h_, mi, &f, cost ? cost->data() : nullptr, labels ? labels->data() : nullptr, cap ? rec.data() : nullptr, cap, &n));
+        rec.resize((size_t)(n < cap ? n : cap));
+        if (found) *found = n;
+        return rec;
+    }
+    /** the whole map's frontier request */
+    gms_frontiers fullFrontiers(int minSize = 1, int inflate = 0) const { return gms_frontiers{0, 0, w_, hgt_, minSize, inflate, 0, 0}; }
     /** rounds launched and tile relaxations run for the last cost-to-go field of this handle */
     void reachStats(int32_t *rounds, int64_t *tileRuns) const { check(gms_map_reach_stats(h_, rounds, tileRuns)); }
     /** the clearance under every pose's cell, without making a field; GMS_CLEAR_OUTSIDE for a pose off the map */
@@ -451,6 +468,21 @@ public:
         check(gms_slam_view(h_, which, &v, out.data(), &drawn));
         if (shown) *shown = drawn;
         return out;
+    }
+    /** The frontier regions of particle `which`'s own map (GridMap::frontiers' values); *shown (may be null) receives the particle
+     *  whose regions were made */
+    std::vector<gms_frontier> frontiers(const gms_frontiers &f, int cap = 4096, const std::vector<uint16_t> *cost = nullptr,
+                                        std::vector<uint32_t> *labels = nullptr, int *found = nullptr, int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        int64_t bytes = 0;
+        check(gms_frontiers_size(&f, nullptr, nullptr, &bytes));
+        if (labels) labels->resize((size_t)bytes / sizeof(uint32_t));
+        std::vector<gms_frontier> rec((size_t)cap);
+        int32_t n = 0, picked = 0;
+        check(gms_slam_frontiers(h_, which, &f, cost ? cost->data() : nullptr, labels ? labels->data() : nullptr, cap ? rec.data() : nullptr, cap, &n, &picked));
+        rec.resize((size_t)(n < cap ? n : cap));
+        if (found) *found = n;
+        if (shown) *shown = picked;
+        return rec;
     }
     /** The cost-to-go field of particle `which`'s own map (GridMap::reach's values); no seeds: the shown particle's own pose cell,
      *  picked on the device.  *shown (may be null) receives the particle whose field was made. */
