@@ -3,9 +3,8 @@
 // A translation unit of its own, kernels and C-ABI: nothing here is on the scan step's path, and no kernel of the other units is
 // compiled differently for it.
 //
-//   k_cast_plane   the pre-pass of the shared-map casts: logData > 0 of every map packed to one bit per cell (a wavefront's ballot over
-//                  64 consecutive cells of a row is one 64-bit word of the plane); 2048 x 2048 cells: 512 KB, cache-resident.  Kept on
-//                  the handle until logData moves (gms_map::cast_plane_current).
+//   the plane      the shared-map casts walk the map's GMS_CLEAR_OCCUPIED plane (gms_map_plane, gms_query.hip): logData > 0 of every map
+//                  at one bit per cell, kept on the handle until logData moves.
 //   k_cast_map     lane = probe, workgroup = 256 neighbouring probes of ONE pose.  The workgroup takes the box of its rays' start and end
 //                  cells (+ extra_steps + 1, clipped to the map), stages those rows' words of the plane in LDS when they fit what the
 //                  launch asked for, and every lane walks RayIterator's float recurrence (ray_init / ray_step, gms_device.h) to the first
@@ -32,17 +31,6 @@
 #define CAST_LDS_CAP (64 * 1024)         // k_cast_map's window: bytes of LDS a workgroup asks for at most
 
 static_assert(sizeof(gms_cast_hit) == 16, "gms_cast_hit is one 16-byte store");
-
-__global__ void __launch_bounds__(256)
-k_cast_plane(const double *__restrict__ logd, int32_t W, int32_t H, int64_t cells, int32_t wpr64, uint64_t *__restrict__ plane) {
-    const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int32_t wx = (int32_t)blockIdx.x * 4 + wave, y = (int32_t)blockIdx.y, mi = (int32_t)blockIdx.z;
-    if (wx >= wpr64) return;                                                    // (uniform per wavefront)
-    const int32_t x = wx * 64 + lane;
-    const double v = x < W ? logd[(size_t)mi * (size_t)cells + (size_t)y * (size_t)W + (size_t)x] : 0.0;
-    const uint64_t bits = __ballot(v > 0.0);                                    // GridMap.java:239: NaN, 0 and -0.0 are not occupied
-    if (lane == 0) plane[((size_t)mi * (size_t)H + (size_t)y) * (size_t)wpr64 + (size_t)wx] = bits;
-}
 
 // the record of a probe whose walk found no occupied cell
 __device__ __forceinline__ gms_cast_hit cast_miss(float measured) {
@@ -184,36 +172,14 @@ k_cast_slam(GridDev g, SlamBufs sb, int64_t code_words, const PfStatsDev *__rest
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// the plane of logData as it stands: the deferred apply pass first (what gms_map_download_log opens with), then the pre-pass unless the
-// handle still holds the plane of this logData
-int gms_cast_plane(gms_map *m) {
-    gms_flush_apply(m);
-    const int32_t wpr64 = (m->gd.W + 63) / 64;
-    if (!m->d_cast_plane) {
-        const size_t bytes = (size_t)m->n_maps * (size_t)m->gd.H * (size_t)wpr64 * sizeof(uint64_t);
-        if (hipMalloc(&m->d_cast_plane, bytes) != hipSuccess) {
-            m->d_cast_plane = nullptr;
-            return gms_fail(GMS_ERR_NOMEM, "gms_map_cast: the bit plane's %zu bytes could not be allocated", bytes);
-        }
-        m->cast_wpr = 2 * wpr64;
-        m->cast_plane_current = 0;
-    }
-    if (!m->cast_plane_current) {
-        hipLaunchKernelGGL(k_cast_plane, dim3((unsigned)((wpr64 + 3) / 4), (unsigned)m->gd.H, (unsigned)m->n_maps), dim3(256), 0, m->stream, m->d_log, m->gd.W,
-                           m->gd.H, m->gd.cells, wpr64, reinterpret_cast<uint64_t *>(m->d_cast_plane));
-        HIPCHK(hipGetLastError());
-        m->cast_plane_current = 1;
-        m->cast_plane_builds++;
-    }
-    return GMS_OK;
-}
-
 // P poses at d_poses (pose_stride floats apart) cast d_probes [B] in map mi (per_map: pose i in map i) into d_out [P][B]
 static int cast_launch(gms_map *m, int32_t mi, bool per_map, const float *d_poses, int32_t pose_stride, int32_t P, const gms_beam *d_probes, int32_t B,
                        gms_cast_hit *d_out) {
-    int rc = gms_cast_plane(m);
+    const uint32_t *plane = nullptr;
+    int rc = gms_map_plane(m, GMS_CLEAR_OCCUPIED, &plane);
     if (rc) return rc;
-    const int64_t plane_stride = (int64_t)m->gd.H * m->cast_wpr;
+    const int32_t wpr = gms_plane_wpr(m);
+    const int64_t plane_stride = (int64_t)m->gd.H * wpr;
     const int64_t lds_words = m->cast_walk_mem ? 0 : std::min<int64_t>(CAST_LDS_CAP / 4, plane_stride);
     const int32_t bpp = (B + CAST_NT - 1) / CAST_NT;
     static bool attr_set = false;
@@ -222,37 +188,26 @@ static int cast_launch(gms_map *m, int32_t mi, bool per_map, const float *d_pose
         attr_set = true;
     }
     hipLaunchKernelGGL(k_cast_map, dim3((unsigned)((int64_t)P * bpp)), dim3(CAST_NT), (size_t)lds_words * 4, m->stream, m->gd,
-                       m->d_cast_plane + (size_t)mi * (size_t)plane_stride, m->cast_wpr, plane_stride, per_map ? 1 : 0, d_probes, B, bpp, d_poses, pose_stride,
+                       plane + (size_t)mi * (size_t)plane_stride, wpr, plane_stride, per_map ? 1 : 0, d_probes, B, bpp, d_poses, pose_stride,
                        d_out, (int32_t)lds_words);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
 
-// the host forms' device staging (the views' buffer, gms_view_staging): [16 bytes: shown][out][probes][poses]
-struct CastStage {
-    int32_t *shown;
-    gms_cast_hit *out;
-    gms_beam *probes;
-    float *poses;
-};
-static int cast_stage(gms_map *m, size_t n_out, const gms_beam *probes, int32_t B, const float *poses, int32_t P, CastStage *st) {
-    const size_t out_bytes = n_out * sizeof(gms_cast_hit), probe_bytes = (size_t)B * sizeof(gms_beam), pose_bytes = (size_t)P * 3 * sizeof(float);
-    unsigned char *base = nullptr;
-    int rc = gms_view_staging(m, (int64_t)(out_bytes + probe_bytes + pose_bytes), &base);
+// the tail map_cast and map_cast_at share: the host form's probes (and poses, where they are the caller's) staged, the launch, the records back
+static int cast_run(gms_map *m, int32_t mi, bool per_map, const float *poses, int32_t pose_stride, int32_t P, const gms_beam *probes, int32_t B, gms_cast_hit *out,
+                    bool on_device) {
+    HostStage st(m, on_device);
+    const size_t out_bytes = (size_t)P * (size_t)B * sizeof(gms_cast_hit), probe_bytes = (size_t)B * sizeof(gms_beam);
+    const size_t pose_bytes = per_map ? 0 : (size_t)P * 3 * sizeof(float);                      // (per_map: the filter's statistics, on the device already)
+    const size_t p_out = st.part(out_bytes), p_probes = st.part(probe_bytes), p_poses = st.part(pose_bytes);
+    int rc = st.open();
+    if (!rc) rc = st.up(p_probes, probes, probe_bytes);
+    if (!rc && pose_bytes) rc = st.up(p_poses, poses, pose_bytes);
+    if (!rc) rc = cast_launch(m, mi, per_map, pose_bytes ? st.at(p_poses, poses) : poses, pose_stride, P, st.at(p_probes, probes), B, st.at(p_out, out));
     if (rc) return rc;
-    st->shown = reinterpret_cast<int32_t *>(base);
-    st->out = reinterpret_cast<gms_cast_hit *>(base + 16);
-    st->probes = reinterpret_cast<gms_beam *>(base + 16 + out_bytes);
-    st->poses = reinterpret_cast<float *>(base + 16 + out_bytes + probe_bytes);
-    HIPCHK(hipMemcpyAsync(st->probes, probes, probe_bytes, hipMemcpyHostToDevice, m->stream));
-    if (P) HIPCHK(hipMemcpyAsync(st->poses, poses, pose_bytes, hipMemcpyHostToDevice, m->stream));
-    return GMS_OK;
-}
-static int cast_fetch(gms_map *m, const CastStage &st, size_t n_out, gms_cast_hit *out, int32_t *shown) {
-    HIPCHK(hipMemcpyAsync(out, st.out, n_out * sizeof(gms_cast_hit), hipMemcpyDeviceToHost, m->stream));
-    if (shown) HIPCHK(hipMemcpyAsync(shown, st.shown, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
+    st.fetch(out, p_out, out_bytes);
+    return st.finish(nullptr);
 }
 
 static int map_cast(gms_map *m, int32_t mi, const float *poses, int32_t P, const gms_beam *probes, int32_t B, gms_cast_hit *out, bool on_device) {
@@ -262,12 +217,7 @@ static int map_cast(gms_map *m, int32_t mi, const float *poses, int32_t P, const
     REQUIRE(P >= 1 && P <= GMS_MAX_PARTICLES, "gms_map_cast: 1 <= P <= GMS_MAX_PARTICLES poses");
     REQUIRE(!on_device || ((uintptr_t)out & 15) == 0, "gms_map_cast_dev: the output must be 16-byte aligned");
     HIPCHK(hipSetDevice(m->device));
-    if (on_device) return cast_launch(m, mi, false, poses, 3, P, probes, B, out);
-    CastStage st;
-    const size_t n_out = (size_t)P * (size_t)B;
-    int rc = cast_stage(m, n_out, probes, B, poses, P, &st);
-    if (!rc) rc = cast_launch(m, mi, false, st.poses, 3, P, st.probes, B, st.out);
-    return rc ? rc : cast_fetch(m, st, n_out, out, nullptr);
+    return cast_run(m, mi, false, poses, 3, P, probes, B, out, on_device);
 }
 
 static int map_cast_at(gms_map *m, const gms_beam *probes, int32_t B, gms_pf *pf, int32_t which, gms_cast_hit *out, bool on_device) {
@@ -281,12 +231,7 @@ static int map_cast_at(gms_map *m, const gms_beam *probes, int32_t B, gms_pf *pf
     const char *stats = reinterpret_cast<const char *>(pf->d_stats);
     const float *d_poses = reinterpret_cast<const float *>(stats + (which == 0 ? offsetof(PfStatsDev, wpose) : offsetof(PfStatsDev, spose)));
     const int32_t stride = (int32_t)(sizeof(PfStatsDev) / sizeof(float));
-    if (on_device) return cast_launch(m, 0, true, d_poses, stride, m->n_maps, probes, B, out);
-    CastStage st;
-    const size_t n_out = (size_t)m->n_maps * (size_t)B;
-    int rc = cast_stage(m, n_out, probes, B, nullptr, 0, &st);
-    if (!rc) rc = cast_launch(m, 0, true, d_poses, stride, m->n_maps, st.probes, B, st.out);
-    return rc ? rc : cast_fetch(m, st, n_out, out, nullptr);
+    return cast_run(m, 0, true, d_poses, stride, m->n_maps, probes, B, out, on_device);
 }
 
 static int slam_cast(gms_slam *s, int32_t which, int32_t filter, const gms_beam *probes, int32_t B, gms_cast_hit *out, int32_t *shown, bool on_device) {
@@ -294,20 +239,22 @@ static int slam_cast(gms_slam *s, int32_t which, int32_t filter, const gms_beam 
     gms_map *m = s->map;
     REQUIRE(B >= 1 && B <= m->max_beams, "gms_slam_cast: 1 <= B <= gms_params.max_beams probes");
     REQUIRE(!on_device || ((uintptr_t)out & 15) == 0, "gms_slam_cast_dev: the output must be 16-byte aligned");
-    if (which == GMS_VIEW_STRONGEST) {
-        REQUIRE(filter >= 0 && filter < s->n_filters, "gms_slam_cast: filter out of range");
-        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_cast: a shard of a filter (its strongest particle may live on another rank): name the particle");
-        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_cast: no update since the handle was created or reset: there is no strongest particle yet");
-    } else if (which != GMS_CAST_ALL) REQUIRE(which >= 0 && which < s->n, "gms_slam_cast: particle index out of range");
+    if (which != GMS_CAST_ALL) {
+        int rc = gms_slam_shown(s, which, filter, "gms_slam_cast", "filter", &filter);
+        if (rc) return rc;
+    } else shown = nullptr;
     HIPCHK(hipSetDevice(m->device));
     const int32_t n_cast = which == GMS_CAST_ALL ? s->n : 1;
-    const size_t n_out = (size_t)n_cast * (size_t)B;
-    CastStage st = {};
-    if (!on_device) { int rc = cast_stage(m, n_out, probes, B, nullptr, 0, &st); if (rc) return rc; }
+    HostStage st(m, on_device);
+    const size_t out_bytes = (size_t)n_cast * (size_t)B * sizeof(gms_cast_hit), probe_bytes = (size_t)B * sizeof(gms_beam);
+    const size_t p_out = st.part(out_bytes), p_probes = st.part(probe_bytes);
+    int rc = st.open();
+    if (!rc) rc = st.up(p_probes, probes, probe_bytes);
+    if (rc) return rc;
     const SlamBufs sb = gms_slam_bufs(s);
-    const gms_beam *d_probes = on_device ? probes : st.probes;
-    gms_cast_hit *d_out = on_device ? out : st.out;
-    int32_t *d_shown = which == GMS_CAST_ALL ? nullptr : (on_device ? shown : st.shown);
+    const gms_beam *d_probes = st.at(p_probes, probes);
+    gms_cast_hit *d_out = st.at(p_out, out);
+    int32_t *d_shown = which == GMS_CAST_ALL ? nullptr : st.shown(shown);
     const bool codes = s->d_code[0] && !m->cast_walk_mem;
     if (codes)
         hipLaunchKernelGGL((k_cast_slam<true>), dim3((unsigned)n_cast), dim3(CAST_NT), (size_t)s->code_words * 4, m->stream, m->gd, sb, s->code_words, s->pf->d_stats,
@@ -316,7 +263,8 @@ static int slam_cast(gms_slam *s, int32_t which, int32_t filter, const gms_beam 
         hipLaunchKernelGGL((k_cast_slam<false>), dim3((unsigned)n_cast), dim3(CAST_NT), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter,
                            s->pf->d_pose, s->pf->d_cs, d_probes, B, d_out, d_shown);
     HIPCHK(hipGetLastError());
-    return on_device ? GMS_OK : cast_fetch(m, st, n_out, out, which == GMS_CAST_ALL ? nullptr : shown);
+    st.fetch(out, p_out, out_bytes);
+    return st.finish(shown);
 }
 
 extern "C" {

@@ -4,13 +4,8 @@
 // A translation unit of its own, kernels and C-ABI: nothing here is on the scan step's path, and no kernel of the other units is
 // compiled differently for it.
 //
-//   the planes       one bit per cell, rows of cast_wpr 32-bit words (padded to 64 cells, the padding zero).  GMS_CLEAR_OCCUPIED of a shared
-//                    map IS the casts' plane (gms_cast_plane: logData > 0, kept on the handle until logData moves); GMS_CLEAR_NOT_FREE is a
-//                    second plane, !(logData < 0), packed by k_clear_plane_map with the same ballot and kept beside it
-//                    (gms_map::clear_plane_current, cleared wherever cast_plane_current is).  The per-particle filter has no plane kept
-//                    per mode: k_clear_plane_slam packs the SHOWN particle's -- from plane 0 of its class planes (code 2 occupied, code 1
-//                    free), or from logData where the handle keeps no planes -- into a scratch plane of the handle; particle and
-//                    generation are picked there, on the device.
+//   the planes       one bit per cell, rows of gms_plane_wpr 32-bit words (padded to 64 cells, the padding zero): the map's plane of the
+//                    request's mode, or the shown particle's, packed per request (query_plane, gms_query.hip).
 //   k_clear_field    the exact separable transform, capped at R.  A workgroup owns ONE WORD of the plane's columns (32 cells) x TY rows
 //                    of the rectangle, plus R rows of halo above and below (clipped to the map).  Stage 1a, a lane per staged row: the
 //                    row's word and the distance from its ends to the nearest set bit of the (R + 31) / 32 words on either side (count
@@ -38,47 +33,6 @@
 #define CLR_G_FAR 0xffffu                // g: no set bit of the row within R
 
 static_assert((256 + 2 * 255) * CLR_ROW_BYTES <= CLR_LDS_CAP, "the tallest tile at the largest radius fits the LDS the kernel may ask for");
-
-// the second plane of the shared maps: !(logData < 0) -- occupied, never observed, or NaN (k_cast_plane's layout and ballot)
-__global__ void __launch_bounds__(256)
-k_clear_plane_map(const double *__restrict__ logd, int32_t W, int32_t H, int64_t cells, int32_t wpr64, uint64_t *__restrict__ plane) {
-    const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int32_t wx = (int32_t)blockIdx.x * 4 + wave, y = (int32_t)blockIdx.y, mi = (int32_t)blockIdx.z;
-    if (wx >= wpr64) return;                                                    // (uniform per wavefront)
-    const int32_t x = wx * 64 + lane;
-    const double v = x < W ? logd[(size_t)mi * (size_t)cells + (size_t)y * (size_t)W + (size_t)x] : -1.0;     // (padding: free)
-    const uint64_t bits = __ballot(!(v < 0.0));
-    if (lane == 0) plane[((size_t)mi * (size_t)H + (size_t)y) * (size_t)wpr64 + (size_t)wx] = bits;
-}
-
-// the shown particle's plane under `mode`: which >= 0 that particle, GMS_VIEW_STRONGEST the strongest of `filter` by the last update's
-// statistics (as k_cast_slam picks it); the generation from the epoch counters
-template <bool CODES>
-__global__ void __launch_bounds__(256)
-k_clear_plane_slam(GridDev g, SlamBufs sb, int64_t code_words, const PfStatsDev *__restrict__ stats, int32_t which, int32_t filter, int32_t mode,
-                   int32_t wpr64, uint64_t *__restrict__ plane, int32_t *__restrict__ shown) {
-    const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int32_t wx = (int32_t)blockIdx.x * 4 + wave, y = (int32_t)blockIdx.y;
-    const int32_t p = which >= 0 ? which : filter * sb.n_per + stats[filter].strongest;
-    if (shown && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *shown = p;
-    if (wx >= wpr64) return;                                                    // (uniform per wavefront)
-    const int32_t cur = sb.epoch[2 * (p / sb.n_per)] & 1;                       // the current generation of the particle's filter
-    const int32_t x = wx * 64 + lane;
-    bool obstacle = false;
-    if (x < g.W) {
-        if (CODES) {
-            const uint32_t *__restrict__ codes = (cur ? sb.code[1] : sb.code[0]) + (size_t)p * 2 * (size_t)code_words;     // plane 0: logData as it stands
-            const int32_t c = x + y * g.W;
-            const uint32_t code = (codes[c >> 4] >> (2 * (c & 15))) & 3u;       // 0: logData == 0 or NaN, 1: < 0, 2: > 0
-            obstacle = mode == GMS_CLEAR_OCCUPIED ? code == 2u : code != 1u;
-        } else {
-            const double v = ((cur ? sb.log[1] : sb.log[0]) + (size_t)p * (size_t)g.cells)[(size_t)x + (size_t)y * (size_t)g.W];
-            obstacle = mode == GMS_CLEAR_OCCUPIED ? v > 0.0 : !(v < 0.0);
-        }
-    }
-    const uint64_t bits = __ballot(obstacle);
-    if (lane == 0) plane[(size_t)y * (size_t)wpr64 + (size_t)wx] = bits;
-}
 
 // Word wx of a plane row of nw words: L = the distance from its bit 0 to the nearest set bit of the K words on its left, Rr = from its bit
 // 31 to the nearest of the K on its right (CLR_NONE: none; words outside the row hold nothing)
@@ -179,33 +133,6 @@ k_clear_poses(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, const 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// the plane of `mode` of logData as it stands, every map's: the casts' own, or the second one (apply pass, allocation, pre-pass as there)
-int gms_clear_plane(gms_map *m, int32_t mode, const uint32_t **plane) {
-    if (mode == GMS_CLEAR_OCCUPIED) {
-        int rc = gms_cast_plane(m);
-        *plane = m->d_cast_plane;
-        return rc;
-    }
-    gms_flush_apply(m);
-    const int32_t wpr64 = (m->gd.W + 63) / 64;
-    if (!m->d_clear_plane) {
-        const size_t bytes = (size_t)m->n_maps * (size_t)m->gd.H * (size_t)wpr64 * sizeof(uint64_t);
-        if (hipMalloc(&m->d_clear_plane, bytes) != hipSuccess) {
-            m->d_clear_plane = nullptr;
-            return gms_fail(GMS_ERR_NOMEM, "gms_map_clearance: the second bit plane's %zu bytes could not be allocated", bytes);
-        }
-        m->clear_plane_current = 0;
-    }
-    if (!m->clear_plane_current) {
-        hipLaunchKernelGGL(k_clear_plane_map, dim3((unsigned)((wpr64 + 3) / 4), (unsigned)m->gd.H, (unsigned)m->n_maps), dim3(256), 0, m->stream, m->d_log,
-                           m->gd.W, m->gd.H, m->gd.cells, wpr64, reinterpret_cast<uint64_t *>(m->d_clear_plane));
-        HIPCHK(hipGetLastError());
-        m->clear_plane_current = 1;
-    }
-    *plane = m->d_clear_plane;
-    return GMS_OK;
-}
-
 // the rows of the rectangle a workgroup of k_clear_field owns
 static inline int32_t clear_tile_rows(int32_t R, int32_t h) { return std::min(h, std::min(256, std::max(64, (2 * R + 7) & ~7))); }
 
@@ -220,40 +147,35 @@ int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c
     }
     const int32_t words = ((c->x0 + c->w - 1) >> 5) - (c->x0 >> 5) + 1, bands = (c->h + TY - 1) / TY;
     if (bands > 65535) return gms_fail(GMS_ERR_INVALID, "gms_clearance: a rectangle of %d rows exceeds one launch", c->h);
-    hipLaunchKernelGGL(k_clear_field, dim3((unsigned)words, (unsigned)bands), dim3(CLR_NT), lds, m->stream, d_plane, gms_clear_wpr(m), m->gd.H, c->x0, c->y0,
+    hipLaunchKernelGGL(k_clear_field, dim3((unsigned)words, (unsigned)bands), dim3(CLR_NT), lds, m->stream, d_plane, gms_plane_wpr(m), m->gd.H, c->x0, c->y0,
                        c->w, c->h, R, TY, rows_cap, d_out);
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }
 
-// c against a W x H map: gms_clearance_size's checks, then the rectangle inside [0, W] x [0, H] (gms_view_check's rule)
-static int clear_check(const gms_clearance *c, int32_t W, int32_t H, const char *what, int64_t *bytes) {
-    int rc = gms_clearance_size(c, nullptr, nullptr, bytes);
-    if (rc) return rc;
-    if ((int64_t)c->x0 + c->w > W || (int64_t)c->y0 + c->h > H)
-        return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, c->x0, c->y0, c->w, c->h, W, H);
-    return GMS_OK;
-}
-
-static int map_clearance(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *out, bool on_device) {
-    REQUIRE(m && c && out, "gms_map_clearance: null argument (the map, the request and the output are required)");
-    REQUIRE(mi >= 0 && mi < m->n_maps, "gms_map_clearance: map index out of range");
+// the field of one map of a shared handle or of the shown particle of a per-particle one; `shown` exists for a particle only
+static int clearance(QuerySource src, const char *what, const gms_clearance *c, uint16_t *out, int32_t *shown, bool on_device) {
+    if ((!src.m && !src.s) || !c || !out) return gms_fail(GMS_ERR_INVALID, "%s: null argument (the handle, the request and the output are required)", what);
+    gms_map *m = src.m;
     int64_t bytes = 0;
-    int rc = clear_check(c, m->gd.W, m->gd.H, "gms_map_clearance", &bytes);
+    int rc = src.s ? GMS_OK : query_check(src, what, nullptr);                  // (a map's index: ahead of the request, the shown particle behind it)
+    if (!rc) rc = gms_clearance_size(c, nullptr, nullptr, &bytes);
+    if (!rc) rc = gms_rect_check(c->x0, c->y0, c->w, c->h, m->gd.W, m->gd.H, what);
     if (rc) return rc;
-    REQUIRE(!on_device || ((uintptr_t)out & 1) == 0, "gms_map_clearance_dev: the output must be 2-byte aligned");
+    if (on_device && ((uintptr_t)out & 1) != 0) return gms_fail(GMS_ERR_INVALID, "%s_dev: the output must be 2-byte aligned", what);
+    src.filter = c->filter;
+    if (src.s && (rc = query_check(src, what, "gms_clearance.filter")) != 0) return rc;
     HIPCHK(hipSetDevice(m->device));
-    unsigned char *base = nullptr;
-    if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
-    const uint32_t *plane = nullptr;
-    rc = gms_clear_plane(m, c->mode, &plane);
+    HostStage st(m, on_device);
+    const size_t p_out = st.part((size_t)bytes);
+    rc = st.open();
     if (rc) return rc;
-    uint16_t *d_out = on_device ? out : reinterpret_cast<uint16_t *>(base + 16);
-    rc = gms_clear_launch(m, plane + (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m), c, d_out);
-    if (rc || on_device) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
+    const uint32_t *plane = nullptr;
+    rc = query_plane(src, c->mode, st.shown(shown), nullptr, &plane);
+    if (!rc) rc = gms_clear_launch(m, plane, c, st.at(p_out, out));
+    if (rc) return rc;
+    st.fetch(out, p_out, (size_t)bytes);
+    return st.finish(shown);
 }
 
 static int map_clearance_poses(gms_map *m, int32_t mi, const float *poses, int32_t P, int32_t max_radius, int32_t mode, uint16_t *out, bool on_device) {
@@ -264,81 +186,20 @@ static int map_clearance_poses(gms_map *m, int32_t mi, const float *poses, int32
     REQUIRE(mode == GMS_CLEAR_OCCUPIED || mode == GMS_CLEAR_NOT_FREE, "gms_map_clearance_poses: mode must be GMS_CLEAR_OCCUPIED or GMS_CLEAR_NOT_FREE");
     REQUIRE(!on_device || ((uintptr_t)out & 1) == 0, "gms_map_clearance_poses_dev: the output must be 2-byte aligned");
     HIPCHK(hipSetDevice(m->device));
-    const size_t out_bytes = ((size_t)P * sizeof(uint16_t) + 15) & ~(size_t)15, pose_bytes = (size_t)P * 3 * sizeof(float);
-    unsigned char *base = nullptr;
-    const float *d_poses = poses;
-    uint16_t *d_out = out;
-    if (!on_device) {                                       // the views' staging: [16 bytes][out][poses]
-        int rc = gms_view_staging(m, (int64_t)(out_bytes + pose_bytes), &base);
-        if (rc) return rc;
-        d_out = reinterpret_cast<uint16_t *>(base + 16);
-        float *stage = reinterpret_cast<float *>(base + 16 + out_bytes);
-        HIPCHK(hipMemcpyAsync(stage, poses, pose_bytes, hipMemcpyHostToDevice, m->stream));
-        d_poses = stage;
-    }
+    HostStage st(m, on_device);
+    const size_t out_bytes = (size_t)P * sizeof(uint16_t), pose_bytes = (size_t)P * 3 * sizeof(float);
+    const size_t p_out = st.part(out_bytes), p_poses = st.part(pose_bytes);
+    int rc = st.open();
+    if (!rc) rc = st.up(p_poses, poses, pose_bytes);
+    if (rc) return rc;
     const uint32_t *plane = nullptr;
-    int rc = gms_clear_plane(m, mode, &plane);
+    rc = query_plane(query_map(m, mi), mode, nullptr, nullptr, &plane);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_clear_poses, dim3((unsigned)((P + CLR_NT / 64 - 1) / (CLR_NT / 64))), dim3(CLR_NT), 0, m->stream, m->gd,
-                       plane + (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m), gms_clear_wpr(m), d_poses, P, max_radius, d_out);
+    hipLaunchKernelGGL(k_clear_poses, dim3((unsigned)((P + CLR_NT / 64 - 1) / (CLR_NT / 64))), dim3(CLR_NT), 0, m->stream, m->gd, plane, gms_plane_wpr(m),
+                       st.at(p_poses, poses), P, max_radius, st.at(p_out, out));
     HIPCHK(hipGetLastError());
-    if (on_device) return GMS_OK;
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)P * sizeof(uint16_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
-}
-
-// the shown particle's plane under `mode` into gms_map::d_clear_scratch (allocated by the first request), and its handle-wide index into
-// d_shown (may be NULL); which / filter as gms_slam_view takes them, already checked.  d_dst: a plane of the caller's instead
-int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown, uint32_t *d_dst) {
-    gms_map *m = s->map;
-    const int32_t wpr64 = (m->gd.W + 63) / 64;
-    if (!d_dst && !m->d_clear_scratch) {
-        const size_t plane_bytes = (size_t)m->gd.H * (size_t)wpr64 * sizeof(uint64_t);
-        if (hipMalloc(&m->d_clear_scratch, plane_bytes) != hipSuccess) {
-            m->d_clear_scratch = nullptr;
-            return gms_fail(GMS_ERR_NOMEM, "gms_slam_clearance: the particle's bit plane of %zu bytes could not be allocated", plane_bytes);
-        }
-    }
-    const SlamBufs sb = gms_slam_bufs(s);
-    if (which != GMS_VIEW_STRONGEST) filter = 0;
-    uint64_t *dst = reinterpret_cast<uint64_t *>(d_dst ? d_dst : m->d_clear_scratch);
-    const dim3 grid((unsigned)((wpr64 + 3) / 4), (unsigned)m->gd.H);
-    if (s->d_code[0])
-        hipLaunchKernelGGL((k_clear_plane_slam<true>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, mode, wpr64,
-                           dst, d_shown);
-    else
-        hipLaunchKernelGGL((k_clear_plane_slam<false>), grid, dim3(256), 0, m->stream, m->gd, sb, s->code_words, s->pf->d_stats, which, filter, mode, wpr64,
-                           dst, d_shown);
-    HIPCHK(hipGetLastError());
-    return GMS_OK;
-}
-
-static int slam_clearance(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *out, int32_t *shown, bool on_device) {
-    REQUIRE(s && c && out, "gms_slam_clearance: null argument (the handle, the request and the output are required)");
-    gms_map *m = s->map;
-    int64_t bytes = 0;
-    int rc = clear_check(c, m->gd.W, m->gd.H, "gms_slam_clearance", &bytes);
-    if (rc) return rc;
-    REQUIRE(!on_device || ((uintptr_t)out & 1) == 0, "gms_slam_clearance_dev: the output must be 2-byte aligned");
-    if (which == GMS_VIEW_STRONGEST) {
-        REQUIRE(c->filter >= 0 && c->filter < s->n_filters, "gms_slam_clearance: gms_clearance.filter out of range");
-        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_clearance: a shard of a filter (its strongest particle may live on another rank): name the particle");
-        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_clearance: no update since the handle was created or reset: there is no strongest particle yet");
-    } else REQUIRE(which >= 0 && which < s->n, "gms_slam_clearance: particle index out of range");
-    HIPCHK(hipSetDevice(m->device));
-    unsigned char *base = nullptr;
-    if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
-    int32_t *d_shown = on_device ? shown : reinterpret_cast<int32_t *>(base);
-    uint16_t *d_out = on_device ? out : reinterpret_cast<uint16_t *>(base + 16);
-    rc = gms_clear_plane_slam(s, which, c->filter, c->mode, d_shown);
-    if (rc) return rc;
-    rc = gms_clear_launch(m, m->d_clear_scratch, c, d_out);
-    if (rc || on_device) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
-    if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
+    st.fetch(out, p_out, out_bytes);
+    return st.finish(nullptr);
 }
 
 extern "C" {
@@ -354,8 +215,8 @@ int gms_clearance_size(const gms_clearance *c, int32_t *out_w, int32_t *out_h, i
     if (bytes) *bytes = (int64_t)c->w * c->h * (int64_t)sizeof(uint16_t);
     return GMS_OK;
 }
-int gms_map_clearance(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *out) { return map_clearance(m, mi, c, out, false); }
-int gms_map_clearance_dev(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *dev_out) { return map_clearance(m, mi, c, dev_out, true); }
+int gms_map_clearance(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *out) { return clearance(query_map(m, mi), "gms_map_clearance", c, out, nullptr, false); }
+int gms_map_clearance_dev(gms_map *m, int32_t mi, const gms_clearance *c, uint16_t *dev_out) { return clearance(query_map(m, mi), "gms_map_clearance", c, dev_out, nullptr, true); }
 int gms_map_clearance_poses(gms_map *m, int32_t mi, const float *poses, int32_t P, int32_t max_radius, int32_t mode, uint16_t *out) {
     return map_clearance_poses(m, mi, poses, P, max_radius, mode, out, false);
 }
@@ -363,10 +224,10 @@ int gms_map_clearance_poses_dev(gms_map *m, int32_t mi, const float *dev_poses, 
     return map_clearance_poses(m, mi, dev_poses, P, max_radius, mode, dev_out, true);
 }
 int gms_slam_clearance(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *out, int32_t *shown) {
-    return slam_clearance(s, which, c, out, shown, false);
+    return clearance(query_slam(s, which), "gms_slam_clearance", c, out, shown, false);
 }
 int gms_slam_clearance_dev(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *dev_out, int32_t *dev_shown) {
-    return slam_clearance(s, which, c, dev_out, dev_shown, true);
+    return clearance(query_slam(s, which), "gms_slam_clearance", c, dev_out, dev_shown, true);
 }
 
 }  // extern "C"

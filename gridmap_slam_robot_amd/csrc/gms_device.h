@@ -275,6 +275,15 @@ template <int O> __device__ __forceinline__ double wave_xor(double v) {
 // the six steps of a descending butterfly: GMS_BUTTERFLY(STEP) expands STEP(32) ... STEP(1)
 #define GMS_BUTTERFLY(STEP) STEP(32) STEP(16) STEP(8) STEP(4) STEP(2) STEP(1)
 
+// The bit planes' pre-passes (k_map_plane, k_slam_plane, k_reach_block): 256 lanes over a grid of ((wpr64 + 3) / 4, rows[, maps]), a
+// wavefront per 64-bit word of a plane row.  plane_wave_word: the word of its row this wavefront packs (>= wpr64: none, uniform), the
+// lane's cell being 64 * word + lane; plane_pack_word: the word from every lane's predicate, stored once at plane[at]
+__device__ __forceinline__ int32_t plane_wave_word() { return (int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6); }
+__device__ __forceinline__ void plane_pack_word(uint64_t *__restrict__ plane, size_t at, bool bit) {
+    const uint64_t bits = __ballot(bit);
+    if ((threadIdx.x & 63) == 0) plane[at] = bits;
+}
+
 __device__ __forceinline__ double wave_sum_f64(double v) {   // fixed xor-butterfly shape
 #define GMS_STEP_(O) v += wave_xor<O>(v);
     GMS_BUTTERFLY(GMS_STEP_)

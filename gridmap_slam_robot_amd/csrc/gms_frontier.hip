@@ -9,8 +9,8 @@
 //   k_front_plane       the frontier plane in the casts' layout (rows of 64-bit words, the padding zero), a lane per word: unknown = the
 //                       second plane and not the casts' plane; a word's east / west shifts carry a bit from the neighbouring words, north
 //                       and south are the words of the rows above and below; free = not the second plane; inflate > 0: and not the
-//                       cost-to-go fields' blocked plane (gms_reach_inflate).  Both planes are read in place (gms_clear_plane; a
-//                       gms_slam's: gms_clear_plane_slam, twice).
+//                       cost-to-go fields' blocked plane (gms_reach_inflate).  Both planes are read in place (query_plane; a gms_slam's:
+//                       the shown particle's, packed per request, twice).
 //   k_front_tiles       a workgroup per 64 x 64 tile; a tile whose 64 words are all zero leaves at once.  Every frontier cell starts as
 //                       its own root in LDS and is united with its W, N, NW and NE neighbours inside the tile (front_unite); then every
 //                       cell chases to its root and writes the root's GLOBAL linear index into the label field.  Tile-local order is the
@@ -344,21 +344,17 @@ k_front_labels(const uint64_t *__restrict__ plane, int32_t wpr64, const uint32_t
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// f against a W x H map: gms_frontiers_size's checks, then the rectangle inside [0, W] x [0, H] (gms_view_check's rule)
-static int front_check(const gms_frontiers *f, int32_t W, int32_t H, const char *what, int64_t *bytes) {
+// the checks the four entry points share behind the source's, before anything is touched; *bytes: the label rectangle's size
+static int front_args(const gms_frontiers *f, int32_t W, int32_t H, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap, bool on_device,
+                      const char *what, int64_t *bytes) {
     int rc = gms_frontiers_size(f, nullptr, nullptr, bytes);
+    if (!rc) rc = gms_rect_check(f->x0, f->y0, f->w, f->h, W, H, what);
     if (rc) return rc;
-    if ((int64_t)f->x0 + f->w > W || (int64_t)f->y0 + f->h > H)
-        return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, f->x0, f->y0, f->w, f->h, W, H);
     if ((int64_t)W * H >= (int64_t)FRT_NONE) return gms_fail(GMS_ERR_INVALID, "%s: a map of %d x %d cells exceeds a 32-bit label", what, W, H);
-    return GMS_OK;
-}
-// the checks the four entry points share, before anything is touched
-static int front_args(const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap, bool on_device, const char *what) {
-    if (cap < 0 || (cap > 0 && !records)) return gms_fail(GMS_ERR_INVALID, "%s: cap >= 0, and records unless cap == 0", what);
+    const char *dev = on_device ? "_dev" : "";
+    if (cap < 0 || (cap > 0 && !records)) return gms_fail(GMS_ERR_INVALID, "%s%s: cap >= 0, and records unless cap == 0", what, dev);
     if (on_device && ((uintptr_t)cost & 1 || (uintptr_t)labels & 3 || (uintptr_t)records & 7))
-        return gms_fail(GMS_ERR_INVALID, "%s: the cost field must be 2-byte aligned, the labels 4-byte aligned, the records 8-byte aligned", what);
-    (void)f;
+        return gms_fail(GMS_ERR_INVALID, "%s%s: the cost field must be 2-byte aligned, the labels 4-byte aligned, the records 8-byte aligned", what, dev);
     return GMS_OK;
 }
 
@@ -387,31 +383,20 @@ static int front_table_grow(gms_map *m, int64_t need) {
     hipFree(m->d_front_table);
     m->d_front_table = nullptr;
     m->front_cap = 0;
-    if (hipMalloc(&m->d_front_table, front_table_bytes((int32_t)cap)) != hipSuccess) {
-        m->d_front_table = nullptr;
-        return gms_fail(GMS_ERR_NOMEM, "gms_frontiers: the region table's %zu bytes could not be allocated", front_table_bytes((int32_t)cap));
-    }
+    int rc = gms_dev_alloc(&m->d_front_table, front_table_bytes((int32_t)cap), "gms_frontiers", "the region table");
+    if (rc) return rc;
     m->front_cap = (int32_t)cap;
     return GMS_OK;
 }
 
-template <typename T>
-static int front_alloc(T **p, size_t bytes, const char *what) {
-    if (*p) return GMS_OK;
-    if (hipMalloc(p, bytes) != hipSuccess) {
-        *p = nullptr;
-        return gms_fail(GMS_ERR_NOMEM, "gms_frontiers: %s of %zu bytes could not be allocated", what, bytes);
-    }
-    return GMS_OK;
-}
 // what a request needs on the handle (a handle's W and H never change: only the table ever grows)
 static int front_buffers(gms_map *m, bool per_particle) {
-    const size_t plane_bytes = (size_t)m->gd.H * (size_t)gms_clear_wpr(m) * sizeof(uint32_t), words = plane_bytes / sizeof(uint64_t);
-    int rc = front_alloc(&m->d_front_plane, 2 * plane_bytes, "the frontier plane and the root plane");
-    if (!rc) rc = front_alloc(&m->d_front_label, (size_t)m->gd.cells * sizeof(uint32_t), "the label field");
-    if (!rc) rc = front_alloc(&m->d_front_wscan, (words + words / FRT_SCAN + 1) * sizeof(uint32_t), "the root plane's scan");
-    if (!rc) rc = front_alloc(&m->d_front_ctl, 2 * sizeof(uint32_t), "the region counts");
-    if (!rc && per_particle) rc = front_alloc(&m->d_front_nf, plane_bytes, "the particle's second plane");
+    const size_t plane_bytes = (size_t)m->gd.H * (size_t)gms_plane_wpr(m) * sizeof(uint32_t), words = plane_bytes / sizeof(uint64_t);
+    int rc = gms_dev_alloc(&m->d_front_plane, 2 * plane_bytes, "gms_frontiers", "the frontier plane and the root plane");
+    if (!rc) rc = gms_dev_alloc(&m->d_front_label, (size_t)m->gd.cells * sizeof(uint32_t), "gms_frontiers", "the label field");
+    if (!rc) rc = gms_dev_alloc(&m->d_front_wscan, (words + words / FRT_SCAN + 1) * sizeof(uint32_t), "gms_frontiers", "the root plane's scan");
+    if (!rc) rc = gms_dev_alloc(&m->d_front_ctl, 2 * sizeof(uint32_t), "gms_frontiers", "the region counts");
+    if (!rc && per_particle) rc = gms_dev_alloc(&m->d_front_nf, plane_bytes, "gms_frontiers", "the particle's second plane");
     if (!rc) rc = front_table_grow(m, FRT_CAP0);
     if (!rc && !m->h_front_ctl && hipHostMalloc(reinterpret_cast<void **>(&m->h_front_ctl), 2 * sizeof(uint32_t)) != hipSuccess) {
         m->h_front_ctl = nullptr;
@@ -473,108 +458,37 @@ static int front_run(gms_map *m, const uint32_t *d_occ, const uint32_t *d_nf, co
     }
 }
 
-// the staging of a host form behind the views' 16 bytes: [labels][records][cost], each part padded to 16 bytes
-struct FrontStage {
-    size_t labels, records, cost, total;
-};
-static FrontStage front_stage(int64_t label_bytes, bool labels, int32_t cap, bool cost, int64_t cells) {
-    FrontStage s;
-    s.labels = 0;
-    s.records = labels ? (((size_t)label_bytes + 15) & ~(size_t)15) : 0;
-    s.cost = s.records + (((size_t)cap * sizeof(gms_frontier) + 15) & ~(size_t)15);
-    s.total = s.cost + (cost ? (size_t)cells * sizeof(uint16_t) : 0);
-    return s;
-}
-
-// what a host form copies back once front_run has returned
-static int front_copy_back(gms_map *m, const unsigned char *base, const FrontStage &sg, int64_t label_bytes, uint32_t *labels, gms_frontier *records, int32_t cap,
-                           int32_t *shown) {
-    const int64_t stored = std::min<int64_t>(m->h_front_ctl[1], cap);
-    if (labels) HIPCHK(hipMemcpyAsync(labels, base + 16 + sg.labels, (size_t)label_bytes, hipMemcpyDeviceToHost, m->stream));
-    if (stored > 0) HIPCHK(hipMemcpyAsync(records, base + 16 + sg.records, (size_t)stored * sizeof(gms_frontier), hipMemcpyDeviceToHost, m->stream));
-    if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
-}
-
-static int map_frontiers(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
-                         int32_t *n_found, bool on_device) {
-    REQUIRE(m && f, "gms_map_frontiers: null argument (the map and the request are required)");
-    REQUIRE(mi >= 0 && mi < m->n_maps, "gms_map_frontiers: map index out of range");
+// the regions of one map of a shared handle or of the shown particle of a per-particle one; `shown` exists for a particle only
+static int frontiers(QuerySource src, const char *what, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
+                     int32_t *n_found, int32_t *shown, bool on_device) {
+    if ((!src.m && !src.s) || !f) return gms_fail(GMS_ERR_INVALID, "%s: null argument (the handle and the request are required)", what);
+    gms_map *m = src.m;
     int64_t bytes = 0;
-    int rc = front_check(f, m->gd.W, m->gd.H, "gms_map_frontiers", &bytes);
-    if (!rc) rc = front_args(f, cost, labels, records, cap, on_device, on_device ? "gms_map_frontiers_dev" : "gms_map_frontiers");
+    int rc = src.s ? GMS_OK : query_check(src, what, nullptr);                  // (a map's index: ahead of the request, the shown particle behind it)
+    if (!rc) rc = front_args(f, m->gd.W, m->gd.H, cost, labels, records, cap, on_device, what, &bytes);
     if (rc) return rc;
+    src.filter = f->filter;
+    if (src.s && (rc = query_check(src, what, "gms_frontiers.filter")) != 0) return rc;
     HIPCHK(hipSetDevice(m->device));
-    rc = front_buffers(m, false);
+    rc = front_buffers(m, src.s != nullptr);
     if (rc) return rc;
-    const FrontStage sg = front_stage(bytes, labels != nullptr, cap, cost != nullptr, m->gd.cells);
-    unsigned char *base = nullptr;
-    const uint16_t *d_cost = cost;
-    uint32_t *d_labels = labels;
-    gms_frontier *d_records = records;
-    if (!on_device) {
-        rc = gms_view_staging(m, (int64_t)sg.total, &base);
-        if (rc) return rc;
-        d_labels = labels ? reinterpret_cast<uint32_t *>(base + 16 + sg.labels) : nullptr;
-        d_records = cap > 0 ? reinterpret_cast<gms_frontier *>(base + 16 + sg.records) : nullptr;
-        if (cost) {
-            HIPCHK(hipMemcpyAsync(base + 16 + sg.cost, cost, (size_t)m->gd.cells * sizeof(uint16_t), hipMemcpyHostToDevice, m->stream));
-            d_cost = reinterpret_cast<const uint16_t *>(base + 16 + sg.cost);
-        }
-    }
+    HostStage st(m, on_device);
+    const size_t label_bytes = labels ? (size_t)bytes : 0, cost_bytes = cost ? (size_t)m->gd.cells * sizeof(uint16_t) : 0;
+    const size_t p_labels = st.part(label_bytes), p_records = st.part((size_t)cap * sizeof(gms_frontier)), p_cost = st.part(cost_bytes);
+    rc = st.open();
+    if (!rc && cost) rc = st.up(p_cost, cost, cost_bytes);
+    if (rc) return rc;
+    // both predicates: the map's two planes in place; a particle's packed per request, the second into d_front_nf
     const uint32_t *occ = nullptr, *nf = nullptr;
-    rc = gms_clear_plane(m, GMS_CLEAR_OCCUPIED, &occ);
-    if (!rc) rc = gms_clear_plane(m, GMS_CLEAR_NOT_FREE, &nf);
-    if (rc) return rc;
-    const size_t at = (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m);
-    rc = front_run(m, occ + at, nf + at, f, d_cost, d_labels, d_records, cap);
-    if (rc) return rc;
-    if (n_found) *n_found = (int32_t)m->h_front_ctl[1];
-    return on_device ? GMS_OK : front_copy_back(m, base, sg, bytes, labels, records, cap, nullptr);
-}
-
-static int slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
-                          int32_t *n_found, int32_t *shown, bool on_device) {
-    REQUIRE(s && f, "gms_slam_frontiers: null argument (the handle and the request are required)");
-    gms_map *m = s->map;
-    int64_t bytes = 0;
-    int rc = front_check(f, m->gd.W, m->gd.H, "gms_slam_frontiers", &bytes);
-    if (!rc) rc = front_args(f, cost, labels, records, cap, on_device, on_device ? "gms_slam_frontiers_dev" : "gms_slam_frontiers");
-    if (rc) return rc;
-    if (which == GMS_VIEW_STRONGEST) {
-        REQUIRE(f->filter >= 0 && f->filter < s->n_filters, "gms_slam_frontiers: gms_frontiers.filter out of range");
-        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_frontiers: a shard of a filter (its strongest particle may live on another rank): name the particle");
-        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_frontiers: no update since the handle was created or reset: there is no strongest particle yet");
-    } else REQUIRE(which >= 0 && which < s->n, "gms_slam_frontiers: particle index out of range");
-    HIPCHK(hipSetDevice(m->device));
-    rc = front_buffers(m, true);
-    if (rc) return rc;
-    const FrontStage sg = front_stage(bytes, labels != nullptr, cap, cost != nullptr, m->gd.cells);
-    const int32_t filter = which == GMS_VIEW_STRONGEST ? f->filter : 0;
-    unsigned char *base = nullptr;
-    const uint16_t *d_cost = cost;
-    uint32_t *d_labels = labels;
-    gms_frontier *d_records = records;
-    int32_t *d_shown = shown;
-    if (!on_device) {
-        rc = gms_view_staging(m, (int64_t)sg.total, &base);
-        if (rc) return rc;
-        d_shown = reinterpret_cast<int32_t *>(base);
-        d_labels = labels ? reinterpret_cast<uint32_t *>(base + 16 + sg.labels) : nullptr;
-        d_records = cap > 0 ? reinterpret_cast<gms_frontier *>(base + 16 + sg.records) : nullptr;
-        if (cost) {
-            HIPCHK(hipMemcpyAsync(base + 16 + sg.cost, cost, (size_t)m->gd.cells * sizeof(uint16_t), hipMemcpyHostToDevice, m->stream));
-            d_cost = reinterpret_cast<const uint16_t *>(base + 16 + sg.cost);
-        }
-    }
-    rc = gms_clear_plane_slam(s, which, filter, GMS_CLEAR_OCCUPIED, d_shown);                     // both predicates of the shown particle
-    if (!rc) rc = gms_clear_plane_slam(s, which, filter, GMS_CLEAR_NOT_FREE, nullptr, m->d_front_nf);
-    if (rc) return rc;
-    rc = front_run(m, m->d_clear_scratch, m->d_front_nf, f, d_cost, d_labels, d_records, cap);
+    rc = query_plane(src, GMS_CLEAR_OCCUPIED, st.shown(shown), nullptr, &occ);
+    if (!rc) rc = query_plane(src, GMS_CLEAR_NOT_FREE, nullptr, src.s ? m->d_front_nf : nullptr, &nf);
+    if (!rc)
+        rc = front_run(m, occ, nf, f, cost ? st.at(p_cost, cost) : nullptr, labels ? st.at(p_labels, labels) : nullptr, cap > 0 ? st.at(p_records, records) : nullptr, cap);
     if (rc) return rc;
     if (n_found) *n_found = (int32_t)m->h_front_ctl[1];
-    return on_device ? GMS_OK : front_copy_back(m, base, sg, bytes, labels, records, cap, shown);
+    st.fetch(labels, p_labels, label_bytes);
+    st.fetch(records, p_records, (size_t)std::min<int64_t>(m->h_front_ctl[1], cap) * sizeof(gms_frontier));
+    return st.finish(shown);
 }
 
 extern "C" {
@@ -592,19 +506,19 @@ int gms_frontiers_size(const gms_frontiers *f, int32_t *out_w, int32_t *out_h, i
 }
 int gms_map_frontiers(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
                       int32_t *n_found) {
-    return map_frontiers(m, mi, f, cost, labels, records, cap, n_found, false);
+    return frontiers(query_map(m, mi), "gms_map_frontiers", f, cost, labels, records, cap, n_found, nullptr, false);
 }
 int gms_map_frontiers_dev(gms_map *m, int32_t mi, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
                           int32_t cap, int32_t *n_found) {
-    return map_frontiers(m, mi, f, dev_cost, dev_labels, dev_records, cap, n_found, true);
+    return frontiers(query_map(m, mi), "gms_map_frontiers", f, dev_cost, dev_labels, dev_records, cap, n_found, nullptr, true);
 }
 int gms_slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *cost, uint32_t *labels, gms_frontier *records, int32_t cap,
                        int32_t *n_found, int32_t *shown) {
-    return slam_frontiers(s, which, f, cost, labels, records, cap, n_found, shown, false);
+    return frontiers(query_slam(s, which), "gms_slam_frontiers", f, cost, labels, records, cap, n_found, shown, false);
 }
 int gms_slam_frontiers_dev(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
                            int32_t cap, int32_t *n_found, int32_t *dev_shown) {
-    return slam_frontiers(s, which, f, dev_cost, dev_labels, dev_records, cap, n_found, dev_shown, true);
+    return frontiers(query_slam(s, which), "gms_slam_frontiers", f, dev_cost, dev_labels, dev_records, cap, n_found, dev_shown, true);
 }
 
 }  // extern "C"

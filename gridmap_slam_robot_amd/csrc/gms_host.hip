@@ -244,7 +244,7 @@ static int map_free(gms_map *m) {
     prof_drain(m);
     for (ProfSlot &s : m->prof_free) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
     hipFree(m->d_log); hipFree(m->d_lik); hipFree(m->d_fac); hipFree(m->d_cnt); hipFree(m->d_cnt_pend); hipFree(m->d_bbox); hipFree(m->d_taps); hipFree(m->d_tile_state); hipFree(m->d_tile_stats);
-    hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch); hipFree(m->d_view); hipFree(m->d_cast_plane); hipFree(m->d_clear_plane); hipFree(m->d_clear_scratch);
+    hipFree(m->d_beams); hipFree(m->d_poses); hipFree(m->d_scratch); hipFree(m->d_view); hipFree(m->plane[0].d); hipFree(m->plane[1].d); hipFree(m->d_clear_scratch);
     hipFree(m->d_reach_field); hipFree(m->d_reach_d2); hipFree(m->d_reach_plane); hipFree(m->d_reach_ctl);
     if (m->h_reach_ctl) hipHostFree(m->h_reach_ctl);
     hipFree(m->d_front_plane); hipFree(m->d_front_nf); hipFree(m->d_front_label); hipFree(m->d_front_wscan); hipFree(m->d_front_table); hipFree(m->d_front_ctl);
@@ -616,43 +616,17 @@ static int map_view(gms_map *m, int32_t mi, const gms_view *v, void *out, bool o
     const bool lik = v->source == GMS_VIEW_LIKELIHOOD;
     if (lik) gms_ensure_lik(m);                        // what gms_map_download_likelihood opens with
     else gms_flush_apply(m);                           // ... and gms_map_download_log
-    unsigned char *base = nullptr;
-    if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
-    gms_launch_view(m, (lik ? m->d_lik : m->d_log) + (size_t)mi * (size_t)m->gd.cells, v, on_device ? out : base + 16);
+    HostStage st(m, on_device);
+    const size_t p_out = st.part((size_t)bytes);
+    rc = st.open();
+    if (rc) return rc;
+    gms_launch_view(m, (lik ? m->d_lik : m->d_log) + (size_t)mi * (size_t)m->gd.cells, v, st.at(p_out, out));
     HIPCHK(hipGetLastError());
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(out, base + 16, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-    }
-    return GMS_OK;
+    st.fetch(out, p_out, (size_t)bytes);
+    return st.finish(nullptr);
 }
 int gms_map_view(gms_map *m, int32_t mi, const gms_view *v, void *out) { return map_view(m, mi, v, out, false); }
 int gms_map_view_dev(gms_map *m, int32_t mi, const gms_view *v, void *dev_out) { return map_view(m, mi, v, dev_out, true); }
-
-}  // extern "C"
-// v against a W x H map: gms_view_size's checks, then the rectangle inside [0, W] x [0, H]; *bytes: the image's size
-int gms_view_check(const gms_view *v, int32_t W, int32_t H, const char *what, int64_t *bytes) {
-    int rc = gms_view_size(v, nullptr, nullptr, bytes);
-    if (rc) return rc;
-    if ((int64_t)v->x0 + v->w > W || (int64_t)v->y0 + v->h > H)
-        return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, v->x0, v->y0, v->w, v->h, W, H);
-    return GMS_OK;
-}
-// The host forms' device staging: 16 bytes for the shown index, the image behind them.  Kept on the handle and only ever grown (a
-// stream synchronise, then a larger allocation), so a sequence of views of one size allocates once.
-int gms_view_staging(gms_map *m, int64_t image_bytes, unsigned char **base) {
-    const size_t need = 16 + (size_t)image_bytes;
-    if (m->view_cap < need) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        hipFree(m->d_view); m->d_view = nullptr; m->view_cap = 0;
-        const size_t cap = (need + 65535) & ~(size_t)65535;
-        if (hipMalloc(&m->d_view, cap) != hipSuccess) { m->d_view = nullptr; return gms_fail(GMS_ERR_NOMEM, "gms_view: staging allocation of %zu bytes failed", cap); }
-        m->view_cap = cap;
-    }
-    *base = m->d_view;
-    return GMS_OK;
-}
-extern "C" {
 
 // beams [n_maps][B] (host) -> d_beams [n_maps][max_beams]
 static int stage_beams(gms_map *m, const gms_beam *beams, int32_t B) {

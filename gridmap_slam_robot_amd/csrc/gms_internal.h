@@ -114,27 +114,26 @@ struct gms_map {
     gms_beam *d_beams;    // [n_maps][max_beams] staging
     float *d_poses;       // [n_maps][3] staging
     double *d_scratch;    // small device scratch
-    unsigned char *d_view; // staging of the host forms of gms_map_view / gms_slam_view: [16 bytes: the shown index][the image]; grows, never per view
+    unsigned char *d_view; // staging of the host forms of the map queries (HostStage): [16 bytes: the shown index][the parts]; grows, never per request
     size_t view_cap;      // its size in bytes
-    uint32_t *d_cast_plane;   // [n_maps][H][cast_wpr] the bit plane the casts walk (gms_cast.hip): bit x & 31 of word x >> 5 of row y = logData > 0; allocated by the first cast
-    int32_t cast_wpr;         // its 32-bit words per row (rows padded to 64 cells)
-    int32_t cast_plane_current;   // it is the plane of logData as it stands (cleared by the transitions below that move logData)
+    // the map's bit planes (gms_map_plane), indexed by GMS_CLEAR_OCCUPIED (logData > 0: what the casts walk) / GMS_CLEAR_NOT_FREE
+    // (!(logData < 0)): d [n_maps][H][gms_plane_wpr], bit x & 31 of word x >> 5 of row y, allocated by the first request of that mode;
+    // current: it is the plane of logData as it stands (map_planes_stale clears it)
+    struct { uint32_t *d; int32_t current; } plane[2];
     int32_t cast_walk_mem;    // casts walk memory even where their window or class plane fits the LDS (GMS_CAST_WALK=mem: tests)
-    int64_t cast_plane_builds;    // launches of the plane's pre-pass so far (tests: an unchanged map is not packed again)
-    uint32_t *d_clear_plane;  // [n_maps][H][cast_wpr] the second plane of the clearance fields (gms_clearance.hip): !(logData < 0), same layout; allocated by the first GMS_CLEAR_NOT_FREE field
-    int32_t clear_plane_current;  // it is the plane of logData as it stands (cleared wherever cast_plane_current is)
-    uint32_t *d_clear_scratch;    // [H][cast_wpr] a gms_slam's clearance: the shown particle's plane, packed per request
+    int64_t cast_plane_builds;    // launches of the GMS_CLEAR_OCCUPIED plane's pre-pass so far (tests: an unchanged map is not packed again)
+    uint32_t *d_clear_scratch;    // [H][gms_plane_wpr] a gms_slam's queries: the shown particle's plane, packed per request (gms_slam_plane)
     // cost-to-go fields (gms_reach.hip); everything below is allocated by the first field that needs it and only ever grows
     uint16_t *d_reach_field;      // [H][W] the working field the tiles relax
     uint16_t *d_reach_d2;         // [H][W] inflate > 0: the whole map's clearance field at R = inflate ...
-    uint32_t *d_reach_plane;      // [H][cast_wpr] ... and the blocked plane balloted from it
+    uint32_t *d_reach_plane;      // [H][gms_plane_wpr] ... and the blocked plane balloted from it
     uint32_t *d_reach_ctl;        // {tile runs (64 bits), the active count of four rounds, 2 spare} | [2][tiles] the tiles' active flags of this round and the next
     uint32_t *h_reach_ctl;        // pinned: the first 8 words of it, read back once per batch of rounds
     int32_t reach_rounds;         // gms_map_reach_stats: rounds launched for the last field
     int64_t reach_tile_runs;      // ... and tile relaxations that ran
     // frontier regions (gms_frontier.hip); allocated by the first request, the region table grows and never shrinks
-    uint32_t *d_front_plane;      // [2][H][cast_wpr] the frontier plane, and the plane of the regions' roots (label == own index)
-    uint32_t *d_front_nf;         // [H][cast_wpr] a gms_slam's: the shown particle's second plane (its first: d_clear_scratch)
+    uint32_t *d_front_plane;      // [2][H][gms_plane_wpr] the frontier plane, and the plane of the regions' roots (label == own index)
+    uint32_t *d_front_nf;         // [H][gms_plane_wpr] a gms_slam's: the shown particle's second plane (its first: d_clear_scratch)
     uint32_t *d_front_label;      // [H][W] the label field of the whole map; defined where the frontier plane has a bit
     uint32_t *d_front_wscan;      // [words] the root plane's word counts, scanned within blocks of FRT_SCAN | [blocks] the blocks' offsets
     unsigned char *d_front_table; // [front_cap] gms_frontier | [front_cap] the goals' 64-bit keys | [front_cap] the kept flags, scanned | [blocks] their offsets
@@ -178,19 +177,20 @@ struct gms_map {
 
 // ---- map state transitions (need_full_build, fac_current, lik_stale, apply_pending, bbox_dirty, bbox_cur): each is named for
 // what happened and sets every field that event affects ----
+// logData moved: neither bit plane is the plane of logData as it stands
+static inline void map_planes_stale(gms_map *m) { m->plane[GMS_CLEAR_OCCUPIED].current = m->plane[GMS_CLEAR_NOT_FREE].current = 0; }
 // logData (or, gms_map_upload_likelihood, the field) was replaced: the next rebuild covers every tile and leaves none alone
-static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; m->cast_plane_current = 0; m->clear_plane_current = 0; }
+static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; map_planes_stale(m); }
 // likelihoodData is up to date everywhere (made so, or about to be replaced wholesale)
 static inline void map_lik_current(gms_map *m) { m->lik_stale = 0; }
 // an immediate apply pass added the counts to logData without a rebuild having seen them
-static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; m->cast_plane_current = 0; m->clear_plane_current = 0; }
+static inline void map_counts_applied(gms_map *m) { m->bbox_dirty = 1; m->fac_current = 0; map_planes_stale(m); }
 // a deferred apply pass has been enqueued: the box of the scan it applied is the current half now
 static inline void gms_apply_done(gms_map *m) {
     m->bbox_cur = 1 - m->bbox_cur;
     m->bbox_dirty = 0;
     m->apply_pending = 0;
-    m->cast_plane_current = 0;         // (logData moved)
-    m->clear_plane_current = 0;
+    map_planes_stale(m);
 }
 // the scan just cast (and already in the likelihood field) keeps its counts for a later launch
 static inline void gms_defer_apply(gms_map *m) {
@@ -496,23 +496,72 @@ void gms_launch_copy(gms_map *m, void *dst, const void *src, size_t nbytes);   /
 void gms_invalidate_tile_state(gms_map *m);
 void gms_launch_get_raw(gms_map *m, int32_t mi, int32_t x, int32_t y, double *d_out2);
 void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out, int64_t n);
-// map views (GridMap.render's grey levels, gridmapslam.h "map views"): the checked rectangle of v against a W x H map and its output
-// size (gms_host.hip); the host forms' staging, base[0 .. 16) for the shown index and the image behind it; the launch for one map's
-// array (src: W x H doubles of v->source's kind)
-int gms_view_check(const gms_view *v, int32_t W, int32_t H, const char *what, int64_t *bytes);
-int gms_view_staging(gms_map *m, int64_t image_bytes, unsigned char **base);
+// a view of one map's array (GridMap.render's grey levels, gridmapslam.h "map views"; src: W x H doubles of v->source's kind)
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
-// the casts' bit plane (logData > 0) of logData as it stands, on the handle: the deferred apply pass first, then the pre-pass unless the
-// handle still holds the plane of this logData (gms_cast.hip; the clearance fields of GMS_CLEAR_OCCUPIED read the same plane)
-int gms_cast_plane(gms_map *m);
-// the clearance fields' host helpers that the cost-to-go fields share (gms_clearance.hip): a plane's 32-bit words per row; the plane of
-// `mode` of logData as it stands, every map's (GMS_CLEAR_OCCUPIED: the casts' own); the field of rectangle c of ONE map's plane into d_out;
-// the shown particle's plane of a gms_slam into gms_map::d_clear_scratch and its index into d_shown (may be NULL)
-static inline int32_t gms_clear_wpr(const gms_map *m) { return 2 * ((m->gd.W + 63) / 64); }        // (= gms_map::cast_wpr once the casts' plane exists)
-int gms_clear_plane(gms_map *m, int32_t mode, const uint32_t **plane);
-int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out);
+
+// ---- map queries: views, predicted scans (gms_cast.hip), clearance fields (gms_clearance.hip), cost-to-go fields (gms_reach.hip) and
+// frontier regions (gms_frontier.hip).  The layering: the query base (gms_query.hip: everything down to query_plane), then clearance, then
+// reach (it inflates with gms_clear_launch), then frontier (it inflates with gms_reach_inflate); cast beside clearance, on the base alone ----
 struct gms_slam;
-int gms_clear_plane_slam(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown, uint32_t *d_dst = nullptr);   // d_dst: another plane than the scratch one
+// the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
+int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);
+// gms_view_size's checks, then the rectangle; *bytes: the image's size
+int gms_view_check(const gms_view *v, int32_t W, int32_t H, const char *what, int64_t *bytes);
+// which particle of a gms_slam a request shows: `which` in range, or GMS_VIEW_STRONGEST with `filter` in range on a handle that is no
+// shard and has updated.  *filter_out: the filter the kernels receive (0 when a particle is named)
+int gms_slam_shown(const gms_slam *s, int32_t which, int32_t filter, const char *what, const char *filter_name, int32_t *filter_out);
+// the one lazy allocator: *p stays what it is, or becomes `bytes` of device memory
+template <typename T>
+static inline int gms_dev_alloc(T **p, size_t bytes, const char *who, const char *what) {
+    if (*p) return GMS_OK;
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        *p = nullptr;
+        return gms_fail(GMS_ERR_NOMEM, "%s: %s of %zu bytes could not be allocated", who, what, bytes);
+    }
+    return GMS_OK;
+}
+// a bit plane's 32-bit words per row (rows padded to 64 cells)
+static inline int32_t gms_plane_wpr(const gms_map *m) { return 2 * ((m->gd.W + 63) / 64); }
+// the plane of `mode` of logData as it stands, every map's: the deferred apply pass first, then the pre-pass unless the handle still
+// holds the plane of this logData
+int gms_map_plane(gms_map *m, int32_t mode, const uint32_t **plane);
+// its per-particle counterpart: the shown particle's plane under `mode` into gms_map::d_clear_scratch (d_dst: into that plane instead)
+// and its handle-wide index into d_shown (may be NULL); which / filter as gms_slam_shown passed them
+int gms_slam_plane(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int32_t *d_shown, uint32_t *d_dst = nullptr);
+// The device staging of a request's host form (none for a device form), over gms_map::d_view: [16 bytes: the shown index][the parts,
+// each padded to 16 bytes].  Reserve the parts, open (the buffer grows only after a stream synchronise), take their device addresses
+// (a device form's: the caller's own pointer), copy inputs up; after the launches queue the outputs and finish: the copies back, the
+// shown index, ONE stream synchronise.
+struct HostStage {
+    gms_map *m;
+    bool on_device;
+    unsigned char *base = nullptr;
+    size_t total = 0;
+    struct { void *dst; size_t part, bytes; } out[3];
+    int32_t n_out = 0;
+    HostStage(gms_map *mm, bool dev) : m(mm), on_device(dev) {}
+    size_t part(size_t bytes) { const size_t at = 16 + total; total += (bytes + 15) & ~(size_t)15; return at; }
+    int open();
+    template <typename T> T *at(size_t part, T *dev) const { return on_device ? dev : reinterpret_cast<T *>(base + part); }
+    int32_t *shown(int32_t *dev) const { return at(0, dev); }
+    int up(size_t part, const void *src, size_t bytes);
+    void fetch(void *dst, size_t part, size_t bytes) { out[n_out].dst = dst; out[n_out].part = part; out[n_out++].bytes = bytes; }
+    int finish(int32_t *shown);
+};
+// Where a query reads: map `index` of a shared handle (s NULL), or particle `index` (GMS_VIEW_STRONGEST: the strongest of `filter`) of
+// a per-particle handle, m its map.  query_check: the map index in range, or gms_slam_shown (which settles `filter`); query_plane:
+// ONE map's plane of `mode` -- gms_map_plane at the map's offset, or gms_slam_plane into the scratch plane / d_dst
+struct QuerySource {
+    gms_map *m;
+    gms_slam *s;
+    int32_t index, filter;
+};
+static inline QuerySource query_map(gms_map *m, int32_t mi) { return {m, nullptr, mi, 0}; }
+static inline QuerySource query_slam(gms_slam *s, int32_t which) { return {s ? s->map : nullptr, s, which, 0}; }
+int query_check(QuerySource &src, const char *what, const char *filter_name);
+int query_plane(const QuerySource &src, int32_t mode, int32_t *d_shown, uint32_t *d_dst, const uint32_t **plane);
+// the field of rectangle c of ONE map's plane into d_out (gms_clearance.hip; the cost-to-go fields inflate with it)
+int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out);
 // the cost-to-go fields' blocked plane for inflate > 0 (gms_reach.hip): the clearance field of ONE map's obstacle plane at R = inflate over
 // the whole map, balloted into gms_map::d_reach_plane (both allocated by the first request); the frontier regions share it
 int gms_reach_inflate(gms_map *m, const uint32_t *d_obstacles, int32_t inflate, int32_t mode, const uint32_t **d_blocked);

@@ -6,7 +6,7 @@
 // compiled differently for it.
 //
 //   the blocked plane   one bit per cell in the casts' layout (rows of 64-bit words, the padding zero).  inflate == 0: the casts' plane
-//                       or the clearance fields' second plane, read in place (gms_clear_plane; a gms_slam's: gms_clear_plane_slam).
+//                       or the map's second plane, read in place (query_plane; a gms_slam's: the shown particle's, packed per request).
 //                       inflate > 0: k_clear_field over the whole map at R = inflate into d_reach_d2, then k_reach_block ballots
 //                       d2 != FAR into d_reach_plane, a wavefront per 64 cells.
 //   k_reach_init        the working field all FAR, the control words and the tiles' flags zero.
@@ -49,16 +49,15 @@ static_assert(GMS_REACH_FAR == RCH_FAR && GMS_REACH_AXIS == 5 && GMS_REACH_DIAG 
 __device__ __forceinline__ uint32_t reach_from_below(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ uint32_t reach_from_above(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130, 0xf, 0xf, false); }
 
-// inflate > 0: the blocked plane from the clearance field d2 of the whole map (k_cast_plane's layout and ballot)
+// inflate > 0: the blocked plane from the clearance field d2 of the whole map (the planes' layout and ballot, gms_device.h)
 __global__ void __launch_bounds__(256)
 k_reach_block(const uint16_t *__restrict__ d2, int32_t W, int32_t wpr64, uint64_t *__restrict__ plane) {
-    const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int32_t wx = (int32_t)blockIdx.x * 4 + wave, y = (int32_t)blockIdx.y;
+    const int32_t lane = threadIdx.x & 63;
+    const int32_t wx = plane_wave_word(), y = (int32_t)blockIdx.y;
     if (wx >= wpr64) return;                                                    // (uniform per wavefront)
     const int32_t x = wx * 64 + lane;
     const uint32_t v = x < W ? d2[(size_t)y * (size_t)W + (size_t)x] : RCH_FAR;                   // (padding: not blocked, as the planes have it)
-    const uint64_t bits = __ballot(v != RCH_FAR);
-    if (lane == 0) plane[(size_t)y * (size_t)wpr64 + (size_t)wx] = bits;
+    plane_pack_word(plane, (size_t)y * (size_t)wpr64 + (size_t)wx, v != RCH_FAR);
 }
 
 // field: words32 32-bit words; ctl: ctl_words
@@ -74,7 +73,7 @@ __device__ __forceinline__ void reach_mark(uint32_t *flags, uint32_t *count, int
 }
 
 // seeds [K][2] (x, y), or -- seeds NULL -- the cell of particle `which` (>= 0, or the strongest of `filter` by the last update's
-// statistics, as k_clear_plane_slam picks it) under its pose
+// statistics, as k_slam_plane picks it) under its pose
 __global__ void __launch_bounds__(256)
 k_reach_seeds(GridDev g, uint16_t *__restrict__ field, const uint64_t *__restrict__ plane, int32_t wpr64, int32_t ntx, uint32_t *__restrict__ ctl,
               const int32_t *__restrict__ seeds, int32_t K, const PfStatsDev *__restrict__ stats, int32_t which, int32_t filter, int32_t n_per,
@@ -219,36 +218,17 @@ k_reach_copy(const uint16_t *__restrict__ field, int32_t W, int32_t x0, int32_t 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// r against a W x H map: gms_reach_size's checks, then the rectangle inside [0, W] x [0, H] (gms_view_check's rule)
-static int reach_check(const gms_reach *r, int32_t W, int32_t H, const char *what, int64_t *bytes) {
-    int rc = gms_reach_size(r, nullptr, nullptr, bytes);
-    if (rc) return rc;
-    if ((int64_t)r->x0 + r->w > W || (int64_t)r->y0 + r->h > H)
-        return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, r->x0, r->y0, r->w, r->h, W, H);
-    return GMS_OK;
-}
-
 static int32_t reach_batch() {
     const char *e = getenv("GMS_REACH_BATCH");
     const int32_t b = e ? atoi(e) : RCH_BATCH_DEFAULT;
     return std::min(64, std::max(1, b));
 }
 
-template <typename T>
-static int reach_alloc(T **p, size_t bytes, const char *what) {
-    if (*p) return GMS_OK;
-    if (hipMalloc(p, bytes) != hipSuccess) {
-        *p = nullptr;
-        return gms_fail(GMS_ERR_NOMEM, "gms_reach: %s of %zu bytes could not be allocated", what, bytes);
-    }
-    return GMS_OK;
-}
-
 // what a field needs on the handle (a handle's W and H never change, so nothing ever has to grow)
 static int reach_buffers(gms_map *m, bool inflated) {
     const size_t cells = (size_t)m->gd.cells, ntiles = (size_t)((m->gd.W + RCH_T - 1) / RCH_T) * (size_t)((m->gd.H + RCH_T - 1) / RCH_T);
-    int rc = reach_alloc(&m->d_reach_field, ((cells + 1) & ~(size_t)1) * sizeof(uint16_t), "the working field");
-    if (!rc) rc = reach_alloc(&m->d_reach_ctl, (RCH_CTL_WORDS + 2 * ntiles) * sizeof(uint32_t), "the tiles' flags");
+    int rc = gms_dev_alloc(&m->d_reach_field, ((cells + 1) & ~(size_t)1) * sizeof(uint16_t), "gms_reach", "the working field");
+    if (!rc) rc = gms_dev_alloc(&m->d_reach_ctl, (RCH_CTL_WORDS + 2 * ntiles) * sizeof(uint32_t), "gms_reach", "the tiles' flags");
     // (inflate > 0: the clearance field and the blocked plane are gms_reach_inflate's)
     if (!rc && !m->h_reach_ctl && hipHostMalloc(reinterpret_cast<void **>(&m->h_reach_ctl), RCH_CTL_WORDS * sizeof(uint32_t)) != hipSuccess) {
         m->h_reach_ctl = nullptr;
@@ -260,8 +240,8 @@ static int reach_buffers(gms_map *m, bool inflated) {
 // inflate > 0: the blocked plane of ONE map's obstacle plane -- "clearance at R = inflate, balloted" -- in d_reach_plane
 int gms_reach_inflate(gms_map *m, const uint32_t *d_obstacles, int32_t inflate, int32_t mode, const uint32_t **d_blocked) {
     const int32_t W = m->gd.W, H = m->gd.H, wpr64 = (W + 63) / 64;
-    int rc = reach_alloc(&m->d_reach_d2, (size_t)m->gd.cells * sizeof(uint16_t), "the inflation's clearance field");
-    if (!rc) rc = reach_alloc(&m->d_reach_plane, (size_t)H * (size_t)gms_clear_wpr(m) * sizeof(uint32_t), "the blocked plane");
+    int rc = gms_dev_alloc(&m->d_reach_d2, (size_t)m->gd.cells * sizeof(uint16_t), "gms_reach", "the inflation's clearance field");
+    if (!rc) rc = gms_dev_alloc(&m->d_reach_plane, (size_t)H * (size_t)gms_plane_wpr(m) * sizeof(uint32_t), "gms_reach", "the blocked plane");
     if (rc) return rc;
     const gms_clearance c = {0, 0, W, H, inflate, mode, 0};
     rc = gms_clear_launch(m, d_obstacles, &c, m->d_reach_d2);
@@ -328,81 +308,40 @@ static int reach_run(gms_map *m, const uint32_t *d_obstacles, const gms_reach *r
     return GMS_OK;
 }
 
-static int map_reach(gms_map *m, int32_t mi, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out, bool on_device) {
-    REQUIRE(m && r && seeds && out, "gms_map_reach: null argument (the map, the request, the seeds and the output are required)");
-    REQUIRE(mi >= 0 && mi < m->n_maps, "gms_map_reach: map index out of range");
-    REQUIRE(K >= 1 && K <= GMS_REACH_MAX_SEEDS, "gms_map_reach: 1 <= K <= GMS_REACH_MAX_SEEDS seeds");
-    int64_t bytes = 0;
-    int rc = reach_check(r, m->gd.W, m->gd.H, "gms_map_reach", &bytes);
+// the field of one map of a shared handle (seeds required) or of the shown particle of a per-particle one (K == 0 and no seeds: its own
+// cell); `shown` exists for a particle only
+static int reach(QuerySource src, const char *what, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out, int32_t *shown, bool on_device) {
+    if ((!src.m && !src.s) || !r || !out || (!src.s && !seeds))
+        return gms_fail(GMS_ERR_INVALID, "%s: null argument (the handle, the request, the output and -- for a map -- the seeds are required)", what);
+    gms_map *m = src.m;
+    int rc = src.s ? GMS_OK : query_check(src, what, nullptr);                  // (a map's index: ahead of the request, the shown particle behind it)
     if (rc) return rc;
-    REQUIRE(!on_device || (((uintptr_t)out & 1) == 0 && ((uintptr_t)seeds & 3) == 0), "gms_map_reach_dev: the output must be 2-byte aligned, the seeds 4-byte aligned");
+    if (!((seeds && K >= 1 && K <= GMS_REACH_MAX_SEEDS) || (src.s && K == 0 && !seeds)))
+        return gms_fail(GMS_ERR_INVALID, "%s: 1 <= K <= GMS_REACH_MAX_SEEDS seeds%s", what, src.s ? ", or K = 0 and no seeds (the shown particle's own cell)" : "");
+    int64_t bytes = 0;
+    rc = gms_reach_size(r, nullptr, nullptr, &bytes);
+    if (!rc) rc = gms_rect_check(r->x0, r->y0, r->w, r->h, m->gd.W, m->gd.H, what);
+    if (rc) return rc;
+    if (on_device && (((uintptr_t)out & 1) != 0 || ((uintptr_t)seeds & 3) != 0))
+        return gms_fail(GMS_ERR_INVALID, "%s_dev: the output must be 2-byte aligned, the seeds 4-byte aligned", what);
+    src.filter = r->filter;
+    if (src.s && (rc = query_check(src, what, "gms_reach.filter")) != 0) return rc;
     HIPCHK(hipSetDevice(m->device));
     rc = reach_buffers(m, r->inflate > 0);
     if (rc) return rc;
-    const size_t out_bytes = ((size_t)bytes + 15) & ~(size_t)15, seed_bytes = (size_t)K * 2 * sizeof(int32_t);
-    unsigned char *base = nullptr;
-    ReachSeeds sd = {seeds, K, nullptr, 0, 0, 0, nullptr};
-    uint16_t *d_out = out;
-    if (!on_device) {                                       // the views' staging: [16 bytes][out][seeds]
-        rc = gms_view_staging(m, (int64_t)(out_bytes + seed_bytes), &base);
-        if (rc) return rc;
-        d_out = reinterpret_cast<uint16_t *>(base + 16);
-        int32_t *stage = reinterpret_cast<int32_t *>(base + 16 + out_bytes);
-        HIPCHK(hipMemcpyAsync(stage, seeds, seed_bytes, hipMemcpyHostToDevice, m->stream));
-        sd.d_seeds = stage;
-    }
+    HostStage st(m, on_device);
+    const size_t seed_bytes = (size_t)K * 2 * sizeof(int32_t), p_out = st.part((size_t)bytes), p_seeds = st.part(seed_bytes);
+    rc = st.open();
+    if (!rc && seeds) rc = st.up(p_seeds, seeds, seed_bytes);
+    if (rc) return rc;
+    ReachSeeds sd = {seeds ? st.at(p_seeds, seeds) : nullptr, K, nullptr, 0, 0, 0, nullptr};
+    if (src.s) sd = {sd.d_seeds, K, src.s->pf->d_stats, src.index, src.filter, src.s->n_per, src.s->pf->d_pose};
     const uint32_t *plane = nullptr;
-    rc = gms_clear_plane(m, r->mode, &plane);
+    rc = query_plane(src, r->mode, st.shown(shown), nullptr, &plane);
+    if (!rc) rc = reach_run(m, plane, r, sd, st.at(p_out, out));
     if (rc) return rc;
-    rc = reach_run(m, plane + (size_t)mi * (size_t)m->gd.H * (size_t)gms_clear_wpr(m), r, sd, d_out);
-    if (rc || on_device) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
-}
-
-static int slam_reach(gms_slam *s, int32_t which, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out, int32_t *shown, bool on_device) {
-    REQUIRE(s && r && out, "gms_slam_reach: null argument (the handle, the request and the output are required)");
-    REQUIRE((K == 0 && !seeds) || (seeds && K >= 1 && K <= GMS_REACH_MAX_SEEDS),
-            "gms_slam_reach: 1 <= K <= GMS_REACH_MAX_SEEDS seeds, or K = 0 and no seeds (the shown particle's own cell)");
-    gms_map *m = s->map;
-    int64_t bytes = 0;
-    int rc = reach_check(r, m->gd.W, m->gd.H, "gms_slam_reach", &bytes);
-    if (rc) return rc;
-    REQUIRE(!on_device || (((uintptr_t)out & 1) == 0 && ((uintptr_t)seeds & 3) == 0), "gms_slam_reach_dev: the output must be 2-byte aligned, the seeds 4-byte aligned");
-    if (which == GMS_VIEW_STRONGEST) {
-        REQUIRE(r->filter >= 0 && r->filter < s->n_filters, "gms_slam_reach: gms_reach.filter out of range");
-        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_reach: a shard of a filter (its strongest particle may live on another rank): name the particle");
-        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_reach: no update since the handle was created or reset: there is no strongest particle yet");
-    } else REQUIRE(which >= 0 && which < s->n, "gms_slam_reach: particle index out of range");
-    HIPCHK(hipSetDevice(m->device));
-    rc = reach_buffers(m, r->inflate > 0);
-    if (rc) return rc;
-    const size_t out_bytes = ((size_t)bytes + 15) & ~(size_t)15, seed_bytes = (size_t)K * 2 * sizeof(int32_t);
-    const int32_t filter = which == GMS_VIEW_STRONGEST ? r->filter : 0;
-    unsigned char *base = nullptr;
-    ReachSeeds sd = {seeds, K, s->pf->d_stats, which, filter, s->n_per, s->pf->d_pose};
-    uint16_t *d_out = out;
-    int32_t *d_shown = shown;
-    if (!on_device) {                                       // the views' staging: [16 bytes: shown][out][seeds]
-        rc = gms_view_staging(m, (int64_t)(out_bytes + seed_bytes), &base);
-        if (rc) return rc;
-        d_shown = reinterpret_cast<int32_t *>(base);
-        d_out = reinterpret_cast<uint16_t *>(base + 16);
-        if (seeds) {
-            int32_t *stage = reinterpret_cast<int32_t *>(base + 16 + out_bytes);
-            HIPCHK(hipMemcpyAsync(stage, seeds, seed_bytes, hipMemcpyHostToDevice, m->stream));
-            sd.d_seeds = stage;
-        }
-    }
-    rc = gms_clear_plane_slam(s, which, filter, r->mode, d_shown);
-    if (rc) return rc;
-    rc = reach_run(m, m->d_clear_scratch, r, sd, d_out);
-    if (rc || on_device) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
-    if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
+    st.fetch(out, p_out, (size_t)bytes);
+    return st.finish(shown);
 }
 
 extern "C" {
@@ -419,15 +358,15 @@ int gms_reach_size(const gms_reach *r, int32_t *out_w, int32_t *out_h, int64_t *
     if (bytes) *bytes = (int64_t)r->w * r->h * (int64_t)sizeof(uint16_t);
     return GMS_OK;
 }
-int gms_map_reach(gms_map *m, int32_t mi, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out) { return map_reach(m, mi, r, seeds, K, out, false); }
+int gms_map_reach(gms_map *m, int32_t mi, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out) { return reach(query_map(m, mi), "gms_map_reach", r, seeds, K, out, nullptr, false); }
 int gms_map_reach_dev(gms_map *m, int32_t mi, const gms_reach *r, const int32_t *dev_seeds, int32_t K, uint16_t *dev_out) {
-    return map_reach(m, mi, r, dev_seeds, K, dev_out, true);
+    return reach(query_map(m, mi), "gms_map_reach", r, dev_seeds, K, dev_out, nullptr, true);
 }
 int gms_slam_reach(gms_slam *s, int32_t which, const gms_reach *r, const int32_t *seeds, int32_t K, uint16_t *out, int32_t *shown) {
-    return slam_reach(s, which, r, seeds, K, out, shown, false);
+    return reach(query_slam(s, which), "gms_slam_reach", r, seeds, K, out, shown, false);
 }
 int gms_slam_reach_dev(gms_slam *s, int32_t which, const gms_reach *r, const int32_t *dev_seeds, int32_t K, uint16_t *dev_out, int32_t *dev_shown) {
-    return slam_reach(s, which, r, dev_seeds, K, dev_out, dev_shown, true);
+    return reach(query_slam(s, which), "gms_slam_reach", r, dev_seeds, K, dev_out, dev_shown, true);
 }
 int gms_map_reach_stats(const gms_map *m, int32_t *rounds, int64_t *tile_runs) {
     REQUIRE(m, "gms_map_reach_stats: null handle");

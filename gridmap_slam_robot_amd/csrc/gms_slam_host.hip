@@ -714,30 +714,24 @@ static int slam_view(gms_slam *s, int32_t which, const gms_view *v, void *out, i
     int rc = gms_view_check(v, m->gd.W, m->gd.H, "gms_slam_view", &bytes);
     if (rc) return rc;
     REQUIRE(!on_device || v->format != GMS_VIEW_PACKED32 || ((uintptr_t)out & 3) == 0, "gms_slam_view_dev: a packed view needs a 4-byte aligned output");
-    if (which == GMS_VIEW_STRONGEST) {
-        REQUIRE(v->filter >= 0 && v->filter < s->n_filters, "gms_slam_view: gms_view.filter out of range");
-        if (pf_is_shard(s->pf)) return gms_fail(GMS_ERR_STATE, "gms_slam_view: a shard of a filter (its strongest particle may live on another rank): name the particle");
-        if (!s->have_strongest) return gms_fail(GMS_ERR_STATE, "gms_slam_view: no update since the handle was created or reset: there is no strongest particle yet");
-    } else REQUIRE(which >= 0 && which < s->n, "gms_slam_view: particle index out of range");
+    int32_t filter = 0;
+    rc = gms_slam_shown(s, which, v->filter, "gms_slam_view", "gms_view.filter", &filter);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(m->device));
     const SlamBufs sb = gms_slam_bufs(s);
-    const int32_t filter = which == GMS_VIEW_STRONGEST ? v->filter : 0;
     SlamField field = s->field;
     if (v->source == GMS_VIEW_LIKELIHOOD && field == SLAM_FIELD_FROM_PLANES) {       // the shown particle's field alone; the state stays as it is
         gms_launch_slam_likelihood_shown(m, sb, s->pf->d_stats, which, filter, s->code_words);
         field = SLAM_FIELD_IN_MEMORY;
     }
-    unsigned char *base = nullptr;
-    if (!on_device) { rc = gms_view_staging(m, bytes, &base); if (rc) return rc; }
-    gms_launch_slam_view(m, sb, s->pf->d_stats, which, filter, field, s->d_idx_lik, v, on_device ? out : base + 16,
-                         on_device ? shown : reinterpret_cast<int32_t *>(base));
+    HostStage st(m, on_device);
+    const size_t p_out = st.part((size_t)bytes);
+    rc = st.open();
+    if (rc) return rc;
+    gms_launch_slam_view(m, sb, s->pf->d_stats, which, filter, field, s->d_idx_lik, v, st.at(p_out, out), st.shown(shown));
     HIPCHK(hipGetLastError());
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(out, base + 16, (size_t)bytes, hipMemcpyDeviceToHost, m->stream));
-        if (shown) HIPCHK(hipMemcpyAsync(shown, base, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-    }
-    return GMS_OK;
+    st.fetch(out, p_out, (size_t)bytes);
+    return st.finish(shown);
 }
 int gms_slam_view(gms_slam *s, int32_t which, const gms_view *v, void *out, int32_t *shown) { return slam_view(s, which, v, out, shown, false); }
 int gms_slam_view_dev(gms_slam *s, int32_t which, const gms_view *v, void *dev_out, int32_t *dev_shown) { return slam_view(s, which, v, dev_out, dev_shown, true); }
@@ -826,11 +820,12 @@ static int slam_trajectory(gms_slam *s, const char *what, bool bundle, int32_t w
                            int32_t *count, int32_t *shown, bool on_device) {
     if (!s) return gms_fail(GMS_ERR_INVALID, "%s: null handle", what);
     if (!s->hist_cap) return gms_fail(GMS_ERR_STATE, "%s: the history is off (gms_slam_set_history)", what);
-    if (bundle || which == GMS_VIEW_STRONGEST) {
+    if (bundle) {
         if (filter < 0 || filter >= s->n_filters) return gms_fail(GMS_ERR_INVALID, "%s: filter out of range", what);
-    } else if (which < 0 || which >= s->n) return gms_fail(GMS_ERR_INVALID, "%s: particle index out of range", what);
-    if (!bundle && which == GMS_VIEW_STRONGEST && !s->have_strongest)
-        return gms_fail(GMS_ERR_STATE, "%s: no update since the handle was created or reset: there is no strongest particle yet", what);
+    } else {
+        int rc = gms_slam_shown(s, which, filter, what, "filter", &filter);
+        if (rc) return rc;
+    }
     const int32_t kept = (int32_t)std::min<int64_t>(s->hist_steps, s->hist_cap);
     if (count) *count = kept;
     if (cap < kept) return gms_fail(GMS_ERR_INVALID, "%s: room for %d steps, %d are kept", what, cap, kept);
@@ -840,21 +835,17 @@ static int slam_trajectory(gms_slam *s, const char *what, bool bundle, int32_t w
     HIPCHK(hipSetDevice(m->device));
     const int32_t nch = bundle ? s->n_per : 1;
     const size_t pose_bytes = (size_t)kept * nch * 3 * sizeof(float), anc_bytes = ancestors ? (size_t)kept * nch * sizeof(int32_t) : 0;
-    unsigned char *base = nullptr;
-    if (!on_device) { int rc = gms_view_staging(m, (int64_t)(pose_bytes + anc_bytes), &base); if (rc) return rc; }
-    float *d_out = on_device ? xytheta : reinterpret_cast<float *>(base + 16);
-    int32_t *d_anc = !ancestors ? nullptr : on_device ? ancestors : reinterpret_cast<int32_t *>(base + 16 + pose_bytes);
-    int32_t *d_shown = bundle ? nullptr : on_device ? shown : reinterpret_cast<int32_t *>(base);
+    HostStage st(m, on_device);
+    const size_t p_out = st.part(pose_bytes), p_anc = st.part(anc_bytes);
+    int rc = st.open();
+    if (rc) return rc;
     gms_launch_slam_hist_walk(m, slam_hist(s), s->d_hist_lin[s->hist_lin_cur], s->pf->d_stats, which, filter, bundle, kept,
-                              gms_slam_hist_walk_rows(s->n_per, s->hist_walk_mem), d_out, d_anc, d_shown);
+                              gms_slam_hist_walk_rows(s->n_per, s->hist_walk_mem), st.at(p_out, xytheta), ancestors ? st.at(p_anc, ancestors) : nullptr,
+                              bundle ? nullptr : st.shown(shown));
     HIPCHK(hipGetLastError());
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(xytheta, d_out, pose_bytes, hipMemcpyDeviceToHost, m->stream));
-        if (ancestors) HIPCHK(hipMemcpyAsync(ancestors, d_anc, anc_bytes, hipMemcpyDeviceToHost, m->stream));
-        if (shown && !bundle) HIPCHK(hipMemcpyAsync(shown, d_shown, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-    }
-    return GMS_OK;
+    st.fetch(xytheta, p_out, pose_bytes);
+    st.fetch(ancestors, p_anc, anc_bytes);
+    return st.finish(bundle ? nullptr : shown);
 }
 
 int gms_slam_trajectory(gms_slam *s, int32_t which, int32_t filter, float *xytheta, int32_t cap, int32_t *count, int32_t *shown) {
