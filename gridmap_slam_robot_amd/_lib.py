@@ -96,6 +96,21 @@ class GmsFrontier(C.Structure):
     ]
 
 
+class GmsGain(C.Structure):
+    """gms_gain: a view-gain request (gridmapslam.h "view gain")"""
+    _fields_ = [("max_range", C.c_int32), ("filter", C.c_int32)]
+
+
+class GmsGainRec(C.Structure):
+    """gms_gain_rec: one candidate pose's record, 32 bytes"""
+    _fields_ = [
+        ("unknown", C.c_int32), ("free_cells", C.c_int32), ("occupied", C.c_int32), ("hits", C.c_int32),
+        ("walked", C.c_int32), ("start_x", C.c_int32), ("start_y", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
+assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
 FRONTIER_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsFrontier._fields_])     # gms_frontier
 assert FRONTIER_DTYPE.itemsize == C.sizeof(GmsFrontier) == 56
 GMS_FRONTIER_NONE = 0xFFFFFFFF
@@ -317,6 +332,11 @@ def load() -> C.CDLL:
     sig("gms_slam_reach", C.c_int, vp, i32, rp, vp, i32, vp, vp)
     sig("gms_slam_reach_dev", C.c_int, vp, i32, rp, vp, i32, vp, vp)
     sig("gms_map_reach_stats", C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64))
+    gp = C.POINTER(GmsGain)
+    sig("gms_map_gain", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp)
+    sig("gms_map_gain_dev", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp)
+    sig("gms_slam_gain", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp, vp)
+    sig("gms_slam_gain_dev", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp, vp)
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

@@ -355,9 +355,11 @@ int gms_map_create(const gms_params *p, gms_map **out) {
     HIPCHK(hipStreamSynchronize(m->stream));
     map_log_replaced(m);
     m->pair_launches = 1;
-    {   // the casts' memory form wherever an LDS form exists (tests; gms_cast.hip)
+    {   // the casts' memory form wherever an LDS form exists (tests; gms_cast.hip), and the view gain's (gms_gain.hip)
         const char *cw_env = getenv("GMS_CAST_WALK");
         m->cast_walk_mem = cw_env && cw_env[0] == 'm';
+        const char *gw_env = getenv("GMS_GAIN_WALK");
+        m->gain_walk_mem = gw_env && gw_env[0] == 'm';
     }
     {   // the tiled batched ray cast: 8 KiB of slots + a 64 KiB tile + static LDS
         int lds_max = 0;

@@ -121,6 +121,7 @@ struct gms_map {
     // current: it is the plane of logData as it stands (map_planes_stale clears it)
     struct { uint32_t *d; int32_t current; } plane[2];
     int32_t cast_walk_mem;    // casts walk memory even where their window or class plane fits the LDS (GMS_CAST_WALK=mem: tests)
+    int32_t gain_walk_mem;    // view gains read plane bits from memory even where the plane windows fit the LDS (GMS_GAIN_WALK=mem: tests)
     int64_t cast_plane_builds;    // launches of the GMS_CLEAR_OCCUPIED plane's pre-pass so far (tests: an unchanged map is not packed again)
     uint32_t *d_clear_scratch;    // [H][gms_plane_wpr] a gms_slam's queries: the shown particle's plane, packed per request (gms_slam_plane)
     // cost-to-go fields (gms_reach.hip); everything below is allocated by the first field that needs it and only ever grows
@@ -499,9 +500,10 @@ void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out
 // a view of one map's array (GridMap.render's grey levels, gridmapslam.h "map views"; src: W x H doubles of v->source's kind)
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
 
-// ---- map queries: views, predicted scans (gms_cast.hip), clearance fields (gms_clearance.hip), cost-to-go fields (gms_reach.hip) and
-// frontier regions (gms_frontier.hip).  The layering: the query base (gms_query.hip: everything down to query_plane), then clearance, then
-// reach (it inflates with gms_clear_launch), then frontier (it inflates with gms_reach_inflate); cast beside clearance, on the base alone ----
+// ---- map queries: views, predicted scans (gms_cast.hip), view gain (gms_gain.hip), clearance fields (gms_clearance.hip), cost-to-go fields
+// (gms_reach.hip) and frontier regions (gms_frontier.hip).  The layering: the query base (gms_query.hip: everything down to query_plane), then
+// clearance, then reach (it inflates with gms_clear_launch), then frontier (it inflates with gms_reach_inflate); cast and gain beside
+// clearance, on the base alone ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);

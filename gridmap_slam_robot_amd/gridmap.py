@@ -156,6 +156,29 @@ def _cast_device_out(out, n: int) -> int:
     return int(out.data_ptr())
 
 
+def _gain_device_out(out, n: int) -> int:
+    """the device address of a caller's torch tensor that is to receive n gms_gain_rec records"""
+    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
+        raise ValueError("gain: out must be a contiguous torch tensor on the device")
+    if out.numel() * out.element_size() < _lib.GAIN_DTYPE.itemsize * n:
+        raise ValueError(f"gain: out holds {out.numel() * out.element_size()} bytes, the records need {_lib.GAIN_DTYPE.itemsize * n}")
+    return int(out.data_ptr())
+
+
+def probe_fan(n: int, range_m: float, fov: float = 2 * math.pi) -> np.ndarray:
+    """n probes of length range_m (metres), evenly spaced fov / n apart and centred on the heading -- probe i at the angle
+    (i - (n - 1) / 2) * fov / n in the robot's frame -- as BEAM_DTYPE [n] (hit = 0): what cast() and gain() take.  The default
+    fov is the full circle."""
+    if n < 1:
+        raise ValueError("probe_fan: n must be at least 1")
+    a = (np.arange(n, dtype=np.float64) - (n - 1) / 2) * (float(fov) / n)
+    b = np.zeros(n, dtype=BEAM_DTYPE)
+    b["local_x"] = float(range_m) * np.cos(a)
+    b["local_y"] = float(range_m) * np.sin(a)
+    b["distance"] = float(range_m)
+    return b
+
+
 def _clearance_args(W: int, H: int, rect, max_radius: int, not_free: bool, filter: int = 0):
     """(gms_clearance, output shape, bytes) of a clearance field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
     x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
@@ -440,6 +463,25 @@ class GridMap:
     def cast_at_dev(self, dev_probes: int, B: int, pf: "ParticleFilter", out, strongest: bool = False):
         check(load().gms_map_cast_at_dev(self._h, C.c_void_p(dev_probes), int(B), pf._h, 1 if strongest else 0,
                                          C.c_void_p(_cast_device_out(out, self.n_maps * B))))
+        return out
+
+    def gain(self, poses, probes, max_range: int, mi: int = 0) -> np.ndarray:
+        """The view gain (gridmapslam.h "view gain") of each of poses [P][3] in map mi: the DISTINCT cells the probes' walks see from
+        there -- each walk as cast() makes it without the extra_steps cells, cut at max_range cells (1 .. 255, Chebyshev) from the
+        start cell and ended by (and including) its first occupied cell -- counted by class.  Returns gms_gain_rec records [P]
+        (GAIN_DTYPE: unknown, free_cells, occupied, hits, walked, start_x, start_y, pad).  Probes: probe_fan()."""
+        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        b = _beams_of(probes).reshape(-1)
+        g = _lib.GmsGain(int(max_range), 0)
+        out = np.empty(len(p), dtype=_lib.GAIN_DTYPE)
+        check(load().gms_map_gain(self._h, int(mi), C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(out)))
+        return out
+
+    def gain_dev(self, dev_poses: int, P: int, dev_probes: int, B: int, out, max_range: int, mi: int = 0):
+        """gain() with device pointers; out: a contiguous torch device tensor of P * 32 bytes, written on the handle's stream"""
+        g = _lib.GmsGain(int(max_range), 0)
+        check(load().gms_map_gain_dev(self._h, int(mi), C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
+                                      C.c_void_p(_gain_device_out(out, P))))
         return out
 
     def cast_plane_builds(self) -> int:
@@ -1232,6 +1274,30 @@ class _SlamHandle:
         check(load().gms_slam_cast(self._h, int(which), int(filter), ptr(b), len(b), ptr(rec), C.byref(shown)))
         return rec, (None if every else int(shown.value))
 
+    def _gain(self, which, filter: int, poses, probes, max_range: int, out, shown_out):
+        """gms_slam_gain[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (records, shown)"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('gain: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        g = _lib.GmsGain(int(max_range), int(filter))
+        if out is not None:                                  # poses: (device address, P), probes: (device address, B)
+            (dev_poses, P), (dev_probes, B) = poses, probes
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("gain: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_gain_dev(self._h, int(which), C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
+                                           C.c_void_p(_gain_device_out(out, P)), sh))
+            return out, shown_out
+        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        b = _beams_of(probes).reshape(-1)
+        rec = np.empty(len(p), dtype=_lib.GAIN_DTYPE)
+        shown = C.c_int32(-1)
+        check(load().gms_slam_gain(self._h, int(which), C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(rec), C.byref(shown)))
+        return rec, int(shown.value)
+
     def _clearance(self, which, filter: int, rect, max_radius: int, not_free: bool, out, shown_out):
         """gms_slam_clearance[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (field, shown)"""
         if isinstance(which, str):
@@ -1497,6 +1563,13 @@ class SLAMParticleMaps(_SlamHandle):
         device tensor or None): the device form, which returns n_found alone."""
         return self._frontiers(which, 0, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
 
+    def gain(self, poses, probes, max_range: int, which="strongest", out=None, shown_out=None):
+        """The view gain of the CALLER'S candidate poses [P][3] in particle `which`'s OWN map (GridMap.gain's records): (records [P],
+        shown).  which = a particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first
+        update).  out / shown_out: torch device tensors, poses and probes then (device address, P) and (device address, B); nothing
+        is synchronised."""
+        return self._gain(which, 0, poses, probes, max_range, out, shown_out)
+
     def trajectory(self, which="strongest", out=None, shown_out=None):
         """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
         first over the kept updates of set_history() -- the path its map was built along, whatever resampling did to the slots since.
@@ -1717,6 +1790,15 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._frontiers(which, filter, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
+
+    def gain(self, poses, probes, max_range: int, which="strongest", filter: int = 0, out=None, shown_out=None):
+        """SLAMParticleMaps.gain for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
+        the handle-wide slot filter * num_particles + k in whose map the poses were judged, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._gain(which, filter, poses, probes, max_range, out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown

@@ -776,6 +776,63 @@ int gms_slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const
 int gms_slam_frontiers_dev(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
                            int32_t cap, int32_t *n_found, int32_t *dev_shown);
 
+/* ---- view gain: what a scan from a candidate pose would reveal -------------------------------------------------------------------
+ * What a goal picker asks after "where are the frontiers and what does each cost": how much never-observed space a scan taken at a
+ * candidate pose would see.  This library's own definition (the reference has no such method); all of it is integer arithmetic.
+ *
+ * A PROBE is a gms_beam of which local_x, local_y and distance are read, as for the casts.  For a candidate pose p, B probes and a map:
+ *   the WALK       probe b walks the cells of rayIterator.init(start + 0.5f, end + 0.5f, 0), start and end point as
+ *                  GridMap.java:175-188: the casts' walk WITHOUT the extra_steps cells past the end point, a prefix of that walk.
+ *   the RANGE CUT  with (cx, cy) the walk's first cell, a cell (x, y) belongs to the walk only while max(|x - cx|, |y - cy|) <=
+ *                  max_range (cells, 1 <= max_range <= 255); the walk ends at the first cell beyond.  It is monotone in both axes, so it
+ *                  never comes back.
+ *   OCCLUSION      the walk ends at, and includes, its first OCCUPIED cell (logData > 0, the casts' predicate).  UNKNOWN cells (logData
+ *                  0, -0.0 or NaN) are walked through, as FREE ones (logData < 0) are: the frontier regions' three classes.
+ *   the VISIBLE SET  a walk that starts outside the map visits nothing (RayIterator.hasNext), a walk ends where it leaves the map; the
+ *                  visible set of a pose is the union over its probes of the cells walked.  Each cell counts once, however many probes
+ *                  cross it (near the sensor nearly all of them do).
+ * Every walk's loop carries the bound 2 * max_range + 2 whatever its inputs (non-finite poses and probes included; no walk inside the
+ * range cut is that long), so a call always terminates.
+ *
+ * "Sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment" (a deferred `logData +=` pass is applied
+ * first, an owed resampling copy is looked through), "changes no later result of its handle" and the argument checks before anything is
+ * enqueued (GMS_ERR_INVALID, nothing touched) are the casts' rules.
+ *
+ * How: one workgroup per pose.  Both bit planes of the map are read in place (the casts' plane and the clearance fields' second one,
+ * packed only when stale: gms_map_cast_plane_builds does not move for a gain after a cast on an unchanged map).  The workgroup keeps a
+ * visited bitmap of the square of side 2 * max_range + 1 around the start cell, clipped to the map, in LDS (at most 17 words x 511
+ * rows, 35 KB); its lanes stride over the probes and set their cells' bits; then the bitmap is classed word by word against the planes
+ * with population counts.  Where the bitmap and both plane windows fit 64 KiB of LDS together the plane windows are staged there too;
+ * otherwise, and on every handle created with GMS_GAIN_WALK=mem in the environment (tests), plane bits are read from memory -- the
+ * same records either way. */
+typedef struct gms_gain {
+    int32_t max_range;          /* cells, 1 .. 255: the half side of the square a scan is taken to see */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+} gms_gain;
+typedef struct gms_gain_rec {   /* 32 bytes */
+    int32_t unknown;            /*  0: distinct visible cells with logData 0, -0.0 or NaN */
+    int32_t free_cells;         /*  4: ... with logData < 0 */
+    int32_t occupied;           /*  8: ... with logData > 0 (each ended at least one walk) */
+    int32_t hits;               /* 12: probes whose walk ended on an occupied cell */
+    int32_t walked;             /* 16: probes that visited at least one cell */
+    int32_t start_x, start_y;   /* 20, 24: the walks' first cell; -1, -1 when no probe walked (every count is then 0) */
+    int32_t pad;                /* 28: always 0 */
+} gms_gain_rec;
+/* Map mi of a shared or batched map: P candidate poses (poses [P][3] = x, y, theta; 1 <= P <= GMS_MAX_PARTICLES) and the same B probes
+ * for each (1 <= B <= the handle's max_beams); out [P].  The host form stages its inputs, reads the records back and synchronises; _dev
+ * takes device pointers (out 16-byte aligned), runs on the handle's stream and synchronises nothing. */
+int gms_map_gain(gms_map *m, int32_t mi, const gms_gain *g, const float *poses, int32_t P, const gms_beam *probes, int32_t B, gms_gain_rec *out);
+int gms_map_gain_dev(gms_map *m, int32_t mi, const gms_gain *g, const float *dev_poses, int32_t P, const gms_beam *dev_probes, int32_t B,
+                     gms_gain_rec *dev_out);
+/* The per-particle filter: the CALLER'S candidate poses in the map of the shown particle.  `which`, GMS_VIEW_STRONGEST, g->filter,
+ * *shown (may be NULL; _dev: a device int32_t *) and the GMS_ERR_STATE cases are gms_slam_view's; particle and generation are picked
+ * on the device, nothing is read back in front of the launches.  There is no GMS_CAST_ALL form: candidates are places in ONE map.
+ * gms_slam_frontiers' pre-pass packs both of the shown particle's planes, and the shared maps' kernel runs on those. */
+int gms_slam_gain(gms_slam *s, int32_t which, const gms_gain *g, const float *poses, int32_t P, const gms_beam *probes, int32_t B, gms_gain_rec *out,
+                  int32_t *shown);
+int gms_slam_gain_dev(gms_slam *s, int32_t which, const gms_gain *g, const float *dev_poses, int32_t P, const gms_beam *dev_probes, int32_t B,
+                      gms_gain_rec *dev_out, int32_t *dev_shown);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -159,6 +159,17 @@ public:
         check(gms_map_cast(h_, mi, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data()));
         return out;
     }
+    /** The view gain (gridmapslam.h "view gain"): for every candidate pose the distinct cells the probes' walks would see from it in
+     *  map mi, by class -- walks cut at maxRange cells (1 .. 255) from the start cell and ended by their first occupied cell. */
+    std::vector<gms_gain_rec> gain(const std::vector<Pose> &poses, const Observation &probes, int maxRange, int mi = 0) {
+        const auto &ms = probes.getMeasurements();
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        const gms_gain g{maxRange, 0};
+        std::vector<gms_gain_rec> out(poses.size());
+        check(gms_map_gain(h_, mi, &g, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data()));
+        return out;
+    }
     /** The clearance field (gridmapslam.h "clearance fields") of map mi: per cell of c's rectangle the squared distance in cells to the
      *  nearest obstacle cell of the whole map, GMS_CLEAR_FAR beyond c.max_radius; [h][w] row-major */
     std::vector<uint16_t> clearance(const gms_clearance &c, int mi = 0) {
@@ -503,6 +514,20 @@ public:
         std::vector<uint16_t> out((size_t)bytes / sizeof(uint16_t));
         int32_t picked = 0;
         check(gms_slam_clearance(h_, which, &c, out.data(), &picked));
+        if (shown) *shown = picked;
+        return out;
+    }
+    /** The view gain of the caller's candidate poses in particle `which`'s own map (GridMap::gain's records); *shown (may be null)
+     *  receives the particle in whose map they were judged */
+    std::vector<gms_gain_rec> gain(const std::vector<Pose> &poses, const Observation &probes, int maxRange, int which = GMS_VIEW_STRONGEST,
+                                   int *shown = nullptr) {
+        const auto &ms = probes.getMeasurements();
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        const gms_gain g{maxRange, 0};
+        std::vector<gms_gain_rec> out(poses.size());
+        int32_t picked = 0;
+        check(gms_slam_gain(h_, which, &g, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data(), &picked));
         if (shown) *shown = picked;
         return out;
     }
