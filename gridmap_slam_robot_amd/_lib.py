@@ -109,6 +109,15 @@ class GmsGainRec(C.Structure):
     ]
 
 
+class GmsScatter(C.Structure):
+    """gms_scatter: a seeding request (gridmapslam.h "particle seeding")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("inflate", C.c_int32), ("mode", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
+        ("jitter", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
 FRONTIER_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsFrontier._fields_])     # gms_frontier
@@ -337,6 +346,10 @@ def load() -> C.CDLL:
     sig("gms_map_gain_dev", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp)
     sig("gms_slam_gain", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp, vp)
     sig("gms_slam_gain_dev", C.c_int, vp, i32, gp, vp, i32, vp, i32, vp, vp)
+    scp = C.POINTER(GmsScatter)
+    sig("gms_scatter_check", C.c_int, scp)
+    sig("gms_pf_scatter", C.c_int, vp, scp, C.c_uint64, C.c_uint64, vp)
+    sig("gms_map_scatter_table_builds", C.c_int, vp, C.POINTER(C.c_int64))
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

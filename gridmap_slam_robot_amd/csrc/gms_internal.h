@@ -141,6 +141,16 @@ struct gms_map {
     int32_t front_cap;            // regions the table holds
     uint32_t *d_front_ctl;        // {regions, regions with count >= min_size}
     uint32_t *h_front_ctl;        // pinned: read back once per request
+    // particle seeding (gms_scatter.hip): the table of the last request -- every map's eligible plane and its scanned counts --, allocated
+    // by the first request; current: it is the table of logData as it stands for exactly that request (map_planes_stale clears it)
+    struct {
+        uint64_t *d_elig;         // [n_maps][words] the eligible plane, words = H * wpr64 64-bit words per map
+        uint32_t *d_pre;          // [n_maps][words] its word counts, scanned within blocks | [n_maps][blocks] the blocks' offsets | [n_maps] M
+        int32_t x0, y0, w, h, inflate, mode;      // the request it was built for (mode: GMS_CLEAR_NOT_FREE where inflate == 0)
+        int32_t current;
+        int64_t builds;           // tables built so far (tests: a scatter on an unchanged map builds none)
+    } scatter;
+    int32_t scatter_shift;        // the draw stages every (1 << shift)-th word's prefix at least this coarsely (GMS_SCATTER_SHIFT: tests of the search in memory)
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -178,8 +188,8 @@ struct gms_map {
 
 // ---- map state transitions (need_full_build, fac_current, lik_stale, apply_pending, bbox_dirty, bbox_cur): each is named for
 // what happened and sets every field that event affects ----
-// logData moved: neither bit plane is the plane of logData as it stands
-static inline void map_planes_stale(gms_map *m) { m->plane[GMS_CLEAR_OCCUPIED].current = m->plane[GMS_CLEAR_NOT_FREE].current = 0; }
+// logData moved: neither bit plane is the plane of logData as it stands, nor is the seeding table its table
+static inline void map_planes_stale(gms_map *m) { m->plane[GMS_CLEAR_OCCUPIED].current = m->plane[GMS_CLEAR_NOT_FREE].current = m->scatter.current = 0; }
 // logData (or, gms_map_upload_likelihood, the field) was replaced: the next rebuild covers every tile and leaves none alone
 static inline void map_log_replaced(gms_map *m) { m->need_full_build = 1; m->fac_current = 0; map_planes_stale(m); }
 // likelihoodData is up to date everywhere (made so, or about to be replaced wholesale)
@@ -501,9 +511,9 @@ void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
 
 // ---- map queries: views, predicted scans (gms_cast.hip), view gain (gms_gain.hip), clearance fields (gms_clearance.hip), cost-to-go fields
-// (gms_reach.hip) and frontier regions (gms_frontier.hip).  The layering: the query base (gms_query.hip: everything down to query_plane), then
-// clearance, then reach (it inflates with gms_clear_launch), then frontier (it inflates with gms_reach_inflate); cast and gain beside
-// clearance, on the base alone ----
+// (gms_reach.hip), frontier regions (gms_frontier.hip) and particle seeding (gms_scatter.hip).  The layering: the query base (gms_query.hip:
+// everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier and scatter (they inflate
+// with gms_reach_inflate); cast and gain beside clearance, on the base alone ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);

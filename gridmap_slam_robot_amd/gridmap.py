@@ -179,6 +179,19 @@ def probe_fan(n: int, range_m: float, fov: float = 2 * math.pi) -> np.ndarray:
     return b
 
 
+def scatter_slots(n: int, fraction: float):
+    """(first, count) of the slots a recovery step replaces by fresh uniform samples after a resample: the LAST round(fraction * n)
+    slots of a filter of n -- after resample() a slot's index says nothing about its particle, so any block serves --, at least one
+    while fraction > 0, never all n while fraction < 1.  (n, 0) for fraction <= 0: nothing to scatter.  What
+    ParticleFilter.scatter(first=..., count=...) takes."""
+    if n < 1:
+        raise ValueError("scatter_slots: n must be at least 1")
+    if not fraction > 0:
+        return n, 0
+    count = n if fraction >= 1 else min(max(int(round(fraction * n)), 1), max(n - 1, 1))
+    return n - count, count
+
+
 def _clearance_args(W: int, H: int, rect, max_radius: int, not_free: bool, filter: int = 0):
     """(gms_clearance, output shape, bytes) of a clearance field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
     x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
@@ -483,6 +496,12 @@ class GridMap:
         check(load().gms_map_gain_dev(self._h, int(mi), C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
                                       C.c_void_p(_gain_device_out(out, P))))
         return out
+
+    def scatter_table_builds(self) -> int:
+        """diagnostics: seeding tables built so far (ParticleFilter.scatter on an unchanged map with the same request builds none)"""
+        n = C.c_int64(0)
+        check(load().gms_map_scatter_table_builds(self._h, C.byref(n)))
+        return int(n.value)
 
     def cast_plane_builds(self) -> int:
         """diagnostics: launches of the casts' bit-plane pre-pass so far (casts of an unchanged map add none)"""
@@ -983,6 +1002,24 @@ class ParticleFilter:
     def sample_motion(self, d_center: float, d_theta: float, seed: int, sequence: int):
         """pose[i] = sampleMotionModel(pose[i], u) (SLAM.java:155-163 -> Odometry.apply, Odometry.java:77-96)."""
         check(load().gms_pf_sample_motion(self._h, d_center, d_theta, seed, sequence))
+
+    def scatter(self, rect=None, inflate: int = 0, mode: int = _lib.GMS_CLEAR_NOT_FREE, first: int = 0, count: Optional[int] = None, jitter: bool = True,
+                seed: int = 0, sequence: int = 0, want_count: bool = False):
+        """Seed slots [first, first + count) of every map's filter with poses drawn uniformly over the eligible cells of its map
+        (gridmapslam.h "particle seeding"): free, inside rect = (x0, y0, w, h) in cells (None: the whole map), no obstacle of `mode`
+        (GMS_CLEAR_NOT_FREE: a cell that is not free; GMS_CLEAR_OCCUPIED: an occupied one) within `inflate` cells.  count=None: to the end of the filter.  The
+        headings are uniform over (-pi, pi), the weights 1 / n_global.  The draw is Philox on (seed, the global slot, sequence): give
+        it a sequence sample_motion() does not use.  want_count: the eligible cells per map are read back (one synchronise) and
+        returned, an int or an int64 array [n_maps]; otherwise nothing is synchronised and None is returned.  Slots for the recovery
+        idiom: scatter_slots()."""
+        x0, y0, w, h = (0, 0, self.map.W, self.map.H) if rect is None else (int(c) for c in rect)
+        sc = _lib.GmsScatter(x0, y0, w, h, int(inflate), int(mode), int(first),
+                             self.n - int(first) if count is None else int(count), 1 if jitter else 0, 0)
+        M = np.zeros(self.n_maps, dtype=np.int64) if want_count else None
+        check(load().gms_pf_scatter(self._h, C.byref(sc), int(seed), int(sequence), None if M is None else ptr(M)))
+        if M is None:
+            return None
+        return int(M[0]) if self.n_maps == 1 else M
 
     def set_refine(self, on: bool = True):
         """scan steps (slam_update*) run findBestPose on every particle before weighting it (SLAM.java:96-97)."""

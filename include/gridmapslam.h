@@ -833,6 +833,65 @@ int gms_slam_gain(gms_slam *s, int32_t which, const gms_gain *g, const float *po
 int gms_slam_gain_dev(gms_slam *s, int32_t which, const gms_gain *g, const float *dev_poses, int32_t P, const gms_beam *dev_probes, int32_t B,
                       gms_gain_rec *dev_out, int32_t *dev_shown);
 
+/* ---- particle seeding: spread a filter over the places the robot can be ------------------------------------------------------------
+ * What global localisation on a known map starts from, and the recovery step of a Monte-Carlo localiser -- a share of the slots
+ * replaced by fresh uniform samples after a resample -- needs on the per-scan path: slots of a shared-map filter receive poses drawn
+ * uniformly over the eligible cells of their map, on the device.  This library's own definition (the reference has no such method: its
+ * reset() puts every particle at the origin, as gms_pf_create does).
+ *
+ * ELIGIBLE: a cell of map mi is eligible if it is FREE (logData < 0, the frontier regions' class: NaN, 0 and -0.0 are not free), lies
+ * inside the rectangle [x0, x0 + w) x [y0, y0 + h) (gms_view's rules) and is not BLOCKED exactly as the cost-to-go fields define it
+ * under `mode` and `inflate`: no obstacle cell of the WHOLE map within d2 <= inflate^2.  With inflate = 0 both modes give the free
+ * cells.  The map is seen as gms_map_download_log would return it at that moment: a deferred `logData +=` pass is applied first.
+ * RANK: the eligible cells of a map in ascending order of y * W + x; M is their number, per map.
+ * THE DRAW for slot i of map mi: one Philox4x32-10 block with key `seed` and counter {g, sequence}, g = (shard offset + i) +
+ * ((uint64_t)mi << 40) -- the motion model's counter layout (gms_pf_sample_motion), so a shard draws what the stand-alone filter draws
+ * for the same global slot; give seeding a `sequence` the motion model does not use.  With the output words c[0..3]:
+ *   the cell   r = the high 64 bits of ((uint64_t)c[0] << 32 | c[1]) * M; the cell (cx, cy) is the r-th eligible one, 0-based.
+ *   in it      jx = (float)(32768 + 7 * (c[2] >> 16)) * 2^-19, jy likewise from c[2] & 0xFFFF: multiples of 2^-19 in [1/16, 15/16),
+ *              exact in float; with jitter == 0 both are 0.5f.
+ *   the pose   fx = (float)cx + jx (one float add); x = (float)((double)position.x + (double)fx * (double)resolution) -- the product of
+ *              two floats is exact in double, so nothing here can be contracted --; y likewise;
+ *              theta = (float)(((double)(c[3] >> 8) - 8388607.5) * (pi * 2^-23)), inside (-pi, pi).
+ * WRITTEN: a slot of [first, first + count) gets that pose, its cached trig, the weight 1.0 / n_global and the log-weight 0.0, as
+ * gms_pf_create leaves them; every other slot is untouched, bit for bit.  Afterwards the filter is in the state gms_pf_set_poses
+ * followed by gms_pf_set_weights leaves.  A map with M == 0 writes nothing to its filter, and the call still returns GMS_OK.
+ * THE CELL GUARANTEE: the cell of a written pose under gms_map_clearance_poses' rule, (int)(((double)x - position.x) / resolution), is
+ * the drawn cell.  With Q = (|position| + extent) / resolution along an axis: fx is off its exact value by at most Q * 2^-24 cells (one
+ * float rounding of a number below Q), the float rounding of x moves it by at most |x| * 2^-24 <= Q * 2^-24 cells, and the three double
+ * roundings on the way there and back by at most 3 * Q * 2^-53: Q * (2^-23 + 3 * 2^-53) in all, below the margin of 1/16 cell on either
+ * side while Q < 2^19.  A map with Q > 2^18 along either axis (|error| <= 1/32 cell there) is refused with GMS_ERR_INVALID.
+ *
+ * Arguments are checked before anything is enqueued (GMS_ERR_INVALID, nothing touched): the rectangle inside the map, inflate, mode,
+ * jitter 0 or 1, first >= 0, count >= 1, first + count <= n, and a map whose plane (H rows of (W + 63) / 64 words) exceeds 2^20 words.
+ * GMS_ERR_STATE on the filter of a gms_slam: its particles live in their own maps and there is no one map to draw from.  A batched
+ * handle (n_maps > 1) is served in one call: map mi's filter draws from map mi.
+ * n_eligible [n_maps] may be NULL: nothing is read back and nothing is synchronised -- the per-scan injection path.  Otherwise the
+ * call synchronises once and stores M per map.
+ *
+ * How: (1) a lane per 64-bit plane word forms ~not-free & ~blocked & the rectangle's mask from the clearance fields' second plane read
+ * in place (packed only when stale: gms_map_cast_plane_builds does not move) and, with inflate > 0, the cost-to-go fields' blocked
+ * plane, and stores the word and its population count; (2) the counts are scanned, per map, in two launches -- blocks of 1024 words,
+ * then the blocks' totals, whose total is M; no workgroup waits on another --; (3) a lane per slot draws, searches the prefix for the
+ * word that holds rank r -- every 32nd word's prefix (coarser on planes of more than 2^18 words, or with GMS_SCATTER_SHIFT in the
+ * environment at the handle's creation: tests) staged in LDS, at most 32 KiB, the rest of the search in memory --, selects the set bit by
+ * halving population counts and writes pose, trig and weight.  M is read from device memory by that launch, never by the host.
+ * The table of (1) and (2) is kept on the gms_map and reused while logData is unchanged and the rectangle, inflate and mode are the
+ * same: a scatter on an unchanged map is launch (3) alone (gms_map_scatter_table_builds does not move). */
+typedef struct gms_scatter {
+    int32_t x0, y0, w, h;       /* the cell rectangle the poses are drawn from */
+    int32_t inflate;            /* cells, 0 .. 255 */
+    int32_t mode;               /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE: what `inflate` keeps away from */
+    int32_t first, count;       /* slots [first, first + count) of every map's filter, local to this handle; count >= 1 */
+    int32_t jitter;             /* 0: cell centres; 1: a position inside the cell */
+    int32_t pad;                /* not read */
+} gms_scatter;
+/* Pure host code, as gms_reach_size: everything about the request but the map's and the filter's bounds, which it does not know. */
+int gms_scatter_check(const gms_scatter *sc);
+int gms_pf_scatter(gms_pf *pf, const gms_scatter *sc, uint64_t seed, uint64_t sequence, int64_t *n_eligible);
+/* diagnostics: seeding tables built on this handle so far (tests: a scatter on an unchanged map with the same request builds none) */
+int gms_map_scatter_table_builds(const gms_map *m, int64_t *builds);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

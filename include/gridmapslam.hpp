@@ -283,6 +283,13 @@ public:
      *  720 factors, which underflows for nearly every particle of a wide cloud (gms_pf_set_log_normalize) */
     void setLogNormalize(bool on) { check(gms_pf_set_log_normalize(h_, on ? 1 : 0)); }
     Pose getWeightedPose() { float o[3]; check(gms_pf_weighted_pose(h_, o)); return Pose(o[0], o[1], o[2]); }
+    /** Particle seeding (gridmapslam.h "particle seeding"): the slots [sc.first, sc.first + sc.count) receive poses drawn uniformly
+     *  over the eligible cells of the map -- free, inside sc's rectangle, no obstacle within sc.inflate cells -- with uniform headings
+     *  and the weight 1 / nGlobal.  nEligible (may be null): the number of eligible cells, read back with one synchronise; without it
+     *  nothing is synchronised.  A single-map filter, as the rest of this class. */
+    void scatter(const gms_scatter &sc, uint64_t seed, uint64_t sequence, int64_t *nEligible = nullptr) {
+        check(gms_pf_scatter(h_, &sc, seed, sequence, nEligible));
+    }
     int size() const { return n_; }
     gms_pf *handle() { return h_; }
 
