@@ -118,11 +118,30 @@ class GmsScatter(C.Structure):
     ]
 
 
+class GmsModes(C.Structure):
+    """gms_modes: a pose-mode request (gridmapslam.h "pose modes")"""
+    _fields_ = [("bin_cells", C.c_int32), ("n_theta", C.c_int32), ("min_count", C.c_int32), ("pad", C.c_int32)]
+
+
+class GmsMode(C.Structure):
+    """gms_mode: one mode's record, 112 bytes"""
+    _fields_ = [
+        ("anchor_bx", C.c_int32), ("anchor_by", C.c_int32), ("anchor_bt", C.c_int32), ("count", C.c_int32),
+        ("bins", C.c_int32), ("strongest", C.c_int32), ("min_bx", C.c_int32), ("min_by", C.c_int32),
+        ("max_bx", C.c_int32), ("max_by", C.c_int32), ("pad", C.c_int32 * 2),
+        ("w", C.c_double), ("wx", C.c_double), ("wy", C.c_double), ("wc", C.c_double), ("ws", C.c_double),
+        ("wxx", C.c_double), ("wxy", C.c_double), ("wyy", C.c_double),
+    ]
+
+
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
 FRONTIER_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsFrontier._fields_])     # gms_frontier
 assert FRONTIER_DTYPE.itemsize == C.sizeof(GmsFrontier) == 56
 GMS_FRONTIER_NONE = 0xFFFFFFFF
+MODE_DTYPE = np.dtype([(n, "<f8" if t is C.c_double else ("<i4", (2,)) if n == "pad" else "<i4") for n, t in GmsMode._fields_])     # gms_mode
+assert MODE_DTYPE.itemsize == C.sizeof(GmsMode) == 112
+GMS_MODE_NONE = 0xFFFFFFFF
 CLEARANCE = GmsClearance
 GMS_REACH_AXIS, GMS_REACH_DIAG, GMS_REACH_FAR, GMS_REACH_MAX_SEEDS = 5, 7, 0xFFFF, 4096
 GMS_CLEAR_OCCUPIED, GMS_CLEAR_NOT_FREE = 0, 1
@@ -350,6 +369,10 @@ def load() -> C.CDLL:
     sig("gms_scatter_check", C.c_int, scp)
     sig("gms_pf_scatter", C.c_int, vp, scp, C.c_uint64, C.c_uint64, vp)
     sig("gms_map_scatter_table_builds", C.c_int, vp, C.POINTER(C.c_int64))
+    mp = C.POINTER(GmsModes)
+    sig("gms_modes_check", C.c_int, mp)
+    sig("gms_pf_modes", C.c_int, vp, i32, mp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+    sig("gms_pf_modes_dev", C.c_int, vp, i32, mp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

@@ -957,6 +957,8 @@ int gms_pf_destroy(gms_pf *pf) {
     hipFree(pf->d_w); hipFree(pf->d_w2); hipFree(pf->d_logw); hipFree(pf->d_cs); hipFree(pf->d_hitbeams);
     hipFree(pf->d_nhit); hipFree(pf->d_stats); hipFree(pf->d_r01); hipFree(pf->d_idx);
     hipFree(pf->d_ord); hipFree(pf->d_perm);
+    hipFree(pf->modes.d_part); hipFree(pf->modes.d_bins); hipFree(pf->modes.d_table); hipFree(pf->modes.d_ctl);
+    if (pf->modes.h_ctl) hipHostFree(pf->modes.h_ctl);
     pf_free_global(pf);
     if (pf->h_stats) hipHostFree(pf->h_stats);
     if (pf->h_stage) hipHostFree(pf->h_stage);

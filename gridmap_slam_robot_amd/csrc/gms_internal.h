@@ -262,6 +262,16 @@ struct gms_pf {
                                     // cumulative weights) as ONE chain in the reference's order (tests; slow)
     int32_t score_spread;           // -1 the launcher decides (launches of two or more workgroups per CU), 0 / 1 forced (GMS_SCORE_SPREAD, read at creation)
     int32_t order_mode;             // -1 the launcher decides (large launches only), 0 never, 1 always (GMS_SCORE_ORDER; results do not depend on it)
+    // pose modes (gms_modes.hip): scratch of the last request, allocated by the first one; the bins' part and the table grow and never shrink
+    struct {
+        uint32_t *d_part;           // [n] every particle's bin | [n] its label
+        uint32_t *d_bins;           // [bins_cap] the bins' counts | [bins_cap] the label field | [bins_cap] the root flags, scanned | [blocks] their offsets
+        int64_t bins_cap;
+        unsigned char *d_table;     // [table_cap] the modes' integers | [table_cap] the kept flags, scanned | [table_cap] the stored records' labels | [blocks] the flags' offsets
+        int64_t table_cap;
+        uint32_t *d_ctl;            // {modes, modes with count >= min_count, OUTSIDE particles, spare}
+        uint32_t *h_ctl;            // pinned: read back once per request
+    } modes;
     int32_t slam_owned;             // the filter of a gms_slam: its particles own maps, so resampling, sharding and the shared-map scan steps are refused on it
     int32_t *d_epoch2;              // the filter of a gms_slam, inside its draw only (slam_draw): {draws that ran so far, the last resample() drew}, kept by the resampling kernels (NULL otherwise)
     // What the derived device data describes.  Written by the pf_* transitions below only (and pf_alloc_global / pf_free_global).
@@ -511,9 +521,9 @@ void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
 
 // ---- map queries: views, predicted scans (gms_cast.hip), view gain (gms_gain.hip), clearance fields (gms_clearance.hip), cost-to-go fields
-// (gms_reach.hip), frontier regions (gms_frontier.hip) and particle seeding (gms_scatter.hip).  The layering: the query base (gms_query.hip:
+// (gms_reach.hip), frontier regions (gms_frontier.hip), particle seeding (gms_scatter.hip) and pose modes (gms_modes.hip).  The layering: the query base (gms_query.hip:
 // everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier and scatter (they inflate
-// with gms_reach_inflate); cast and gain beside clearance, on the base alone ----
+// with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only) ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);

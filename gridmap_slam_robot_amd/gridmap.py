@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
 __all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
-           "cells_of_poses", "descend"]
+           "cells_of_poses", "descend", "mode_estimate", "strongest_mode"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -258,14 +258,14 @@ def _frontier_cost(cost, W: int, H: int):
     return np.ascontiguousarray(a)
 
 
-def _frontier_device(t, nbytes: int, what: str):
+def _frontier_device(t, nbytes: int, what: str, who: str = "frontiers"):
     """the device address of a caller's torch tensor of at least nbytes (None: the output is omitted)"""
     if t is None:
         return None
     if not (getattr(t, "is_cuda", False) and t.is_contiguous()):
-        raise ValueError(f"frontiers: {what} must be a contiguous torch tensor on the device")
+        raise ValueError(f"{who}: {what} must be a contiguous torch tensor on the device")
     if t.numel() * t.element_size() < nbytes:
-        raise ValueError(f"frontiers: {what} holds {t.numel() * t.element_size()} bytes, {nbytes} are needed")
+        raise ValueError(f"{who}: {what} holds {t.numel() * t.element_size()} bytes, {nbytes} are needed")
     return C.c_void_p(int(t.data_ptr()))
 
 
@@ -288,6 +288,27 @@ def cells_of_poses(poses, position, resolution: float):
         q = np.where(np.isnan(q), 0.0, np.clip(np.trunc(q), -2147483648.0, 2147483647.0))
         out.append(q.astype(np.int64))
     return out[0], out[1]
+
+
+def mode_estimate(records) -> dict:
+    """Pose estimates of pose modes (ParticleFilter.modes' records), host numpy, float64 arrays over the records: "mean" [n][3] =
+    (wx / w, wy / w, atan2(ws, wc)); "cov" [n][2][2], the position covariance [[wxx / w - mx^2, wxy / w - mx * my], [., wyy / w -
+    my^2]]; "circular_variance" [n] = 1 - hypot(wc, ws) / w; "share" [n] = w / sum of w over the listed modes.  A mode of zero weight
+    gives NaN."""
+    r = np.asarray(records)
+    w = r["w"].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mx, my = r["wx"] / w, r["wy"] / w
+        cxy = r["wxy"] / w - mx * my
+        cov = np.stack([np.stack([r["wxx"] / w - mx * mx, cxy], axis=-1), np.stack([cxy, r["wyy"] / w - my * my], axis=-1)], axis=-2)
+        return dict(mean=np.stack([mx, my, np.arctan2(r["ws"], r["wc"])], axis=-1), cov=cov,
+                    circular_variance=1.0 - np.hypot(r["wc"], r["ws"]) / w, share=w / w.sum())
+
+
+def strongest_mode(records) -> int:
+    """The index of the record of the largest w among pose modes (ParticleFilter.modes' records), ties to the first; -1 for none"""
+    w = np.asarray(records)["w"]
+    return int(np.argmax(w)) if len(w) else -1
 
 
 _DESCEND_ORDER = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))       # E, N, W, S, NE, NW, SW, SE; north is y + 1
@@ -1020,6 +1041,33 @@ class ParticleFilter:
         if M is None:
             return None
         return int(M[0]) if self.n_maps == 1 else M
+
+    def modes(self, bin_cells: int, n_theta: int, min_count: int = 1, labels: bool = False, cap: int = 4096, mi: int = 0, records_out=None,
+              labels_out=None):
+        """The pose modes of map mi's filter (gridmapslam.h "pose modes"): the particles binned in squares of bin_cells cells and n_theta
+        heading bins (1 .. 64), the occupied bins grouped into maximal 26-connected sets, the heading wrapping.  Returns (records,
+        n_found, n_outside): records a structured array (MODE_DTYPE: anchor bin, count, bins, strongest member, box, the weighted
+        sums w, wx, wy, wc, ws, wxx, wxy, wyy in the header's order) of the modes with count >= min_count in ascending anchor order,
+        at most cap of them; n_found how many qualify; n_outside the particles off the map or with a non-finite heading.
+        labels=True appends every particle's label, uint32 [n]: its mode's anchor index (bt * BH + by) * BW + bx whatever min_count
+        is, GMS_MODE_NONE for a particle outside.  The sums cost one pass over the labels per stored record: keep cap or min_count
+        tight on large filters.  Estimates: mode_estimate(), strongest_mode().
+        records_out / labels_out: contiguous torch device tensors (room for cap = bytes // 112 gms_mode, 8-byte aligned; n * 4 bytes,
+        4-byte aligned), either may be None -- the device form, written on the handle's stream; returns (n_found, n_outside).  Every
+        form waits on the stream once."""
+        q = _lib.GmsModes(int(bin_cells), int(n_theta), int(min_count), 0)
+        nf, no = C.c_int32(0), C.c_int32(0)
+        if records_out is not None or labels_out is not None:
+            cap = 0 if records_out is None else records_out.numel() * records_out.element_size() // _lib.MODE_DTYPE.itemsize
+            check(load().gms_pf_modes_dev(self._h, int(mi), C.byref(q), _frontier_device(labels_out, self.n * 4, "labels_out", "modes"),
+                                          _frontier_device(records_out, 0, "records_out", "modes"), int(cap), C.byref(nf), C.byref(no)))
+            return int(nf.value), int(no.value)
+        rec = np.zeros(int(cap), dtype=_lib.MODE_DTYPE)
+        lab = np.empty(self.n, dtype=np.uint32) if labels else None
+        check(load().gms_pf_modes(self._h, int(mi), C.byref(q), None if lab is None else ptr(lab), ptr(rec) if cap else None, int(cap),
+                                  C.byref(nf), C.byref(no)))
+        out = (rec[:min(nf.value, int(cap))], int(nf.value), int(no.value))
+        return out + (lab,) if labels else out
 
     def set_refine(self, on: bool = True):
         """scan steps (slam_update*) run findBestPose on every particle before weighting it (SLAM.java:96-97)."""

@@ -892,6 +892,85 @@ int gms_pf_scatter(gms_pf *pf, const gms_scatter *sc, uint64_t seed, uint64_t se
 /* diagnostics: seeding tables built on this handle so far (tests: a scatter on an unchanged map with the same request builds none) */
 int gms_map_scatter_table_builds(const gms_map *m, int64_t *builds);
 
+/* ---- pose modes: the hypotheses a particle cloud still holds ---------------------------------------------------------------------------
+ * What a localiser on a scattered filter asks every scan: how many hypotheses are left, where is each, how much weight does it hold and
+ * how tight is it -- the heaviest cluster's pose and covariance, and "has the filter converged" as "does one cluster hold nearly all
+ * the weight".  gms_pf_weighted_pose's single mean is a pose in the wall between two rooms that look alike.  This library's own
+ * definition (the reference has no such method), in the frontier regions' style: everything that can be integer is integer, and the
+ * floating-point sums have one stated order, so every output is unique.
+ *
+ * THE BIN of a particle (x, y, theta) of map mi's filter: its cell (gx, gy) is gms_map_clearance_poses' (NaN -> 0 and the toward-zero
+ * cast included), and the particle is OUTSIDE exactly where that call returns GMS_CLEAR_OUTSIDE: gx < 0 || gy < 0 || gx >= W || gy >= H.
+ * The heading bin: k = (double)n_theta * 0.15915494309189535 (one double multiply), v = (double)theta * k, f = floor(v); a non-finite
+ * f, or |f| >= 2^31, makes the particle OUTSIDE; otherwise bt = f mod n_theta, taken non-negative in integer arithmetic.  No trig, no
+ * loops.  With bx = gx / bin_cells, by = gy / bin_cells, BW = ceil(W / bin_cells) and BH likewise, the bin's linear index is
+ * (bt * BH + by) * BW + bx.
+ * MODES: a bin is OCCUPIED if at least one particle of the filter lies in it.  Two distinct bins are ADJACENT if |dbx| <= 1, |dby| <= 1
+ * and their bt are equal or differ by 1 modulo n_theta: 26-connectivity with the heading wrapping.  n_theta = 1 has no heading
+ * neighbours; with n_theta = 2 the two layers are adjacent.  A MODE is a maximal connected set of occupied bins, its ANCHOR its bin of
+ * the smallest linear index.
+ *
+ * Two outputs, either may be omitted (NULL):
+ *   the LABEL per particle, uint32_t [n]: the anchor's linear index of the particle's mode, whatever min_count is, or GMS_MODE_NONE
+ *                     for an OUTSIDE particle.
+ *   the MODE TABLE    gms_mode records of the modes with count >= min_count, in ascending anchor order; the first `cap` of them are
+ *                     stored, *n_found (may be NULL) is the number that qualify and may exceed cap.  cap == 0 with records == NULL is
+ *                     allowed.
+ * *n_outside (may be NULL) is the number of OUTSIDE particles.
+ * STRONGEST: among the members whose weight is not NaN, the one of the largest weight, the first in index order among equals (a scan
+ * in index order under a strict >); -1 if every member's weight is NaN.
+ * THE SUMS over a mode's members, with a = the particle's weight as it stands on the handle (a pending scoring pass is combined first,
+ * as gms_pf_get_weights does), X = (double)x, Y = (double)y, C and S = the filter's cached cos and sin of the particle, widened (what
+ * Transform.fromRobotToWorld uses): the terms a, a * X, a * Y, a * C, a * S, a * (X * X), a * (X * Y), a * (Y * Y).  The inner products
+ * of two floats are exact in double, so each term has one rounding; nothing is contracted.
+ * THE ORDER is part of the definition: partial s_l, l = 0 .. 255, starts at +0.0 and adds the terms of the members i = l, l + 256,
+ * l + 512, ... in ascending i; the record holds ((s_0 + s_1) + s_2) + ... + s_255.  Adding +0.0 for a non-member gives the same bits as
+ * skipping it.  Non-finite weights or poses propagate as IEEE says.
+ *
+ * Checked before anything is enqueued (GMS_ERR_INVALID, nothing touched): the request's ranges, mi, cap >= 0, records given with
+ * cap == 0 (or missing with cap > 0), more than 2^22 bins (BW * BH * n_theta), and in the _dev form misaligned device pointers.
+ * GMS_ERR_STATE: the filter of a gms_slam (its particles live in their own maps), and a shard of a filter (gms_pf_set_shard with
+ * n_global != n: its bins would need an exchange).  The call changes no later result of its handle: poses, weights, log-weights, trig
+ * and what the handle knows of them are as gms_pf_get_weights leaves them.
+ *
+ * How: (1) a lane per particle computes the bin, stores it and raises the bin's count, the lanes of a wavefront that share a bin
+ * combined first; OUTSIDE particles are counted; (2) a lane per bin: an occupied bin starts as its own label and is united with its 13
+ * forward neighbours in the global label field, the heading wrapping, lock-free, the larger root always hung under the smaller, so the
+ * final root is the anchor (the frontier regions' rule); (3) every occupied bin chases to its root; (4) the roots are numbered in
+ * anchor order by a scan; count, bins and box by integer atomics, the lanes of a wavefront that share a label combined first; a second
+ * scan keeps count >= min_count; (5) a lane per particle writes its label; (6) one workgroup of 256 lanes per STORED record runs the
+ * sums and `strongest` in exactly the order above: lane partials in registers, then LDS, then one lane per sum adds the 256 in
+ * ascending order.  Scans and unions that span workgroups are separate launches; no workgroup waits on another.  Scratch (bin counts,
+ * label field, root numbering, tables) lives on the gms_pf, grows and never shrinks.
+ * COST: steps 1 to 5 are one pass over the particles and a few over the bins; step 6 reads all n labels once per stored record:
+ * stored records x n label reads.  min_count and cap are the caller's control over it.
+ * The number of modes is known on the device only: every form, _dev included, waits on the handle's stream once (the host form once
+ * more for its copies), and both outputs are complete when it returns. */
+#define GMS_MODE_NONE 0xFFFFFFFFu                              /* a label: the particle is OUTSIDE */
+typedef struct gms_modes {          /* the request */
+    int32_t bin_cells;              /* >= 1: cells per bin along x and y */
+    int32_t n_theta;                /* 1 .. 64 heading bins */
+    int32_t min_count;              /* >= 1: the smallest mode the table lists */
+    int32_t pad;                    /* not read */
+} gms_modes;
+typedef struct gms_mode {           /* 112 bytes */
+    int32_t anchor_bx, anchor_by, anchor_bt;  /*  0: the bin of the smallest linear index */
+    int32_t count;                            /* 12: member particles */
+    int32_t bins;                             /* 16: occupied bins */
+    int32_t strongest;                        /* 20: the member of the largest weight, or -1 */
+    int32_t min_bx, min_by, max_bx, max_by;   /* 24: the box in bins, inclusive (no heading box: it wraps) */
+    int32_t pad[2];                           /* 40: zero */
+    double  w, wx, wy, wc, ws, wxx, wxy, wyy; /* 48: the weighted sums */
+} gms_mode;
+/* Pure host code, as gms_scatter_check: the request's ranges -- not the map's bin limit, which it does not know. */
+int gms_modes_check(const gms_modes *q);
+/* Map mi's filter of a shared or batched handle.  labels [n], records [cap]: host memory, staged through the views' buffer.
+ * _dev: dev_labels (4-byte aligned) and dev_records (8-byte aligned) are device memory, written on the handle's stream; n_found and
+ * n_outside stay HOST pointers. */
+int gms_pf_modes(gms_pf *pf, int32_t mi, const gms_modes *q, uint32_t *labels, gms_mode *records, int32_t cap, int32_t *n_found, int32_t *n_outside);
+int gms_pf_modes_dev(gms_pf *pf, int32_t mi, const gms_modes *q, uint32_t *dev_labels, gms_mode *dev_records, int32_t cap, int32_t *n_found,
+                     int32_t *n_outside);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -290,6 +290,22 @@ public:
     void scatter(const gms_scatter &sc, uint64_t seed, uint64_t sequence, int64_t *nEligible = nullptr) {
         check(gms_pf_scatter(h_, &sc, seed, sequence, nEligible));
     }
+    /** The pose modes of the filter (gridmapslam.h "pose modes"): the particles binned in (x, y, theta) per q, the occupied bins grouped
+     *  into maximal 26-connected sets with the heading wrapping.  labels [size()] and records [cap] are host memory, either may be
+     *  null (records exactly when cap == 0); returns the number of modes with count >= q.min_count, of which the first cap are
+     *  stored in ascending anchor order.  nOutside (may be null): the particles off the map or with a non-finite heading.  Waits on
+     *  the stream.  A single-map filter, as the rest of this class. */
+    int32_t modes(const gms_modes &q, uint32_t *labels, gms_mode *records, int32_t cap, int32_t *nOutside = nullptr) {
+        int32_t found = 0;
+        check(gms_pf_modes(h_, 0, &q, labels, records, cap, &found, nOutside));
+        return found;
+    }
+    /** modes() into device memory (labels 4-byte, records 8-byte aligned), written on the handle's stream; complete on return */
+    int32_t modesDev(const gms_modes &q, uint32_t *devLabels, gms_mode *devRecords, int32_t cap, int32_t *nOutside = nullptr) {
+        int32_t found = 0;
+        check(gms_pf_modes_dev(h_, 0, &q, devLabels, devRecords, cap, &found, nOutside));
+        return found;
+    }
     int size() const { return n_; }
     gms_pf *handle() { return h_; }
 
