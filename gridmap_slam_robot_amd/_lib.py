@@ -373,6 +373,9 @@ def load() -> C.CDLL:
     sig("gms_modes_check", C.c_int, mp)
     sig("gms_pf_modes", C.c_int, vp, i32, mp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
     sig("gms_pf_modes_dev", C.c_int, vp, i32, mp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+    sig("gms_beam_model_check", C.c_int, i32, i32, vp)
+    sig("gms_pf_score_beams", C.c_int, vp, vp, i32, i32, i32, vp, vp)
+    sig("gms_pf_score_beams_dev", C.c_int, vp, vp, i32, i32, i32, vp, vp)
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

@@ -272,7 +272,13 @@ struct gms_pf {
         uint32_t *d_ctl;            // {modes, modes with count >= min_count, OUTSIDE particles, spare}
         uint32_t *h_ctl;            // pinned: read back once per request
     } modes;
-    int32_t slam_owned;             // the filter of a gms_slam: its particles own maps, so resampling, sharding and the shared-map scan steps are refused on it
+    // the beam sensor model (gms_beams.hip): the last call's tables, allocated by the first call
+    struct {
+        double *d_tab;              // factors [2][T] | their logarithms [2][T], T = behind + ahead + 2 <= 512
+        StageRing ring;             // pinned staging of those
+        int32_t ring_ready;
+    } beam;
+    int32_t slam_owned;            // the filter of a gms_slam: its particles own maps, so resampling, sharding and the shared-map scan steps are refused on it
     int32_t *d_epoch2;              // the filter of a gms_slam, inside its draw only (slam_draw): {draws that ran so far, the last resample() drew}, kept by the resampling kernels (NULL otherwise)
     // What the derived device data describes.  Written by the pf_* transitions below only (and pf_alloc_global / pf_free_global).
     // weights:
@@ -521,7 +527,8 @@ void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
 
 // ---- map queries: views, predicted scans (gms_cast.hip), view gain (gms_gain.hip), clearance fields (gms_clearance.hip), cost-to-go fields
-// (gms_reach.hip), frontier regions (gms_frontier.hip), particle seeding (gms_scatter.hip) and pose modes (gms_modes.hip).  The layering: the query base (gms_query.hip:
+// (gms_reach.hip), frontier regions (gms_frontier.hip), particle seeding (gms_scatter.hip), pose modes (gms_modes.hip) and the beam sensor
+// model (gms_beams.hip: beside cast, on the base alone).  The layering: the query base (gms_query.hip:
 // everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier and scatter (they inflate
 // with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only) ----
 struct gms_slam;

@@ -192,6 +192,38 @@ def scatter_slots(n: int, fraction: float):
     return n - count, count
 
 
+def beam_model_factors(resolution: float, behind: int, ahead: int, sigma: float, z_hit: float = 0.8, z_short: float = 0.1, z_rand: float = 0.05,
+                       z_miss: float = 0.9) -> np.ndarray:
+    """factors [2][T], T = behind + ahead + 2, for ParticleFilter.score_beams: the usual mixture of a ray-cast beam model, pure numpy
+    float64.  Entry k < T - 1 belongs to the residual d = k - behind in walk steps (the map's first wall d steps behind the measured
+    end point; negative: in front of it; d = -behind also stands for every wall further in front), entry T - 1 to "the walk found no
+    wall".  With r = d * resolution:
+
+      row 1 (beams that hit)     z_hit * exp(-0.5 * (r / sigma)^2)  +  z_short where d > 0  +  z_rand;      none: z_short + z_rand
+      row 0 (beams that missed)  z_rand for every d (the map has a wall where the beam saw none);           none: z_miss + z_rand
+
+    i.e. a Gaussian around agreement, a constant short-reading term where the beam ended in front of the map's wall (d > 0) or of
+    anything the walk could reach (none), a uniform floor everywhere, and a high value where a beam that saw nothing meets a map
+    that holds nothing.  The entries are weights, not densities: only their ratios matter once the filter normalises.
+    A walk step is one cell along x or y, so it is between resolution / sqrt(2) (a diagonal ray) and resolution (an axis-parallel
+    one) of range: sigma and the reach of behind / ahead in metres are direction dependent by that factor.  z_rand must be > 0 (every
+    entry must be, or gms_pf_score_beams refuses the table)."""
+    behind, ahead = int(behind), int(ahead)
+    if not (0 <= behind <= 255 and 0 <= ahead <= 255):
+        raise ValueError("beam_model_factors: 0 <= behind, ahead <= 255")
+    if not (sigma > 0 and resolution > 0 and z_rand > 0 and z_hit >= 0 and z_short >= 0 and z_miss >= 0):
+        raise ValueError("beam_model_factors: sigma, resolution and z_rand must be > 0, the other terms >= 0")
+    T = behind + ahead + 2
+    d = np.arange(-behind, ahead + 1, dtype=np.float64)
+    r = d * float(resolution)
+    f = np.empty((2, T), dtype=np.float64)
+    f[1, :T - 1] = float(z_hit) * np.exp(-0.5 * (r / float(sigma)) ** 2) + np.where(d > 0, float(z_short), 0.0) + float(z_rand)
+    f[1, T - 1] = float(z_short) + float(z_rand)
+    f[0, :T - 1] = float(z_rand)
+    f[0, T - 1] = float(z_miss) + float(z_rand)
+    return f
+
+
 def _clearance_args(W: int, H: int, rect, max_radius: int, not_free: bool, filter: int = 0):
     """(gms_clearance, output shape, bytes) of a clearance field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
     x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
@@ -1068,6 +1100,43 @@ class ParticleFilter:
                                   C.byref(nf), C.byref(no)))
         out = (rec[:min(nf.value, int(cap))], int(nf.value), int(no.value))
         return out + (lab,) if labels else out
+
+    def _beam_factors(self, factors, behind: int, ahead: int) -> np.ndarray:
+        f = np.ascontiguousarray(factors, dtype=np.float64)
+        if f.shape != (2, int(behind) + int(ahead) + 2):
+            raise ValueError(f"score_beams: factors must be [2][behind + ahead + 2] = (2, {int(behind) + int(ahead) + 2}), not {f.shape}")
+        return f
+
+    def score_beams(self, obs, factors, behind: int, ahead: int, residuals: bool = False):
+        """The beam sensor model (gridmapslam.h "beam sensor model"): every particle is weighted by where the map's first occupied
+        cell lies on each beam's walk relative to the measured end point -- what lies BETWEEN sensor and end point counts, unlike
+        score().  factors [2][behind + ahead + 2] (row 0: beams with hit == 0, row 1: hit != 0; every entry finite and > 0;
+        beam_model_factors() builds the usual mixture): entry k < T - 1 is for the residual d = k - behind walk steps (d < 0: the
+        map's wall in front of the end point, held at -behind; d > 0: behind it, up to `ahead`), the last entry for a walk that found
+        no wall.  The weight is the product of the beams' entries, the log-weight the sum of their logarithms, both in the header's
+        one order.  Afterwards the filter is as score() leaves it: normalize(), resample[_if](), set_log_normalize(), modes() work
+        unchanged.  residuals=True returns the table index per particle and beam, uint16 [n][B] ([n_maps][n][B] on a batched
+        handle), and waits for the stream; otherwise nothing is returned and nothing synchronised."""
+        b, B = self.map._beam_args(obs)
+        f = self._beam_factors(factors, behind, ahead)
+        res = np.empty(self._pshape((B,)), dtype=np.uint16) if residuals else None
+        check(load().gms_pf_score_beams(self._h, ptr(b), B, int(behind), int(ahead), ptr(f), None if res is None else ptr(res)))
+        return res
+
+    def score_beams_dev(self, dev_beams: int, B: int, factors, behind: int, ahead: int, residuals_out=None):
+        """score_beams() on device-resident beams [n_maps][B]; factors stay a host array.  residuals_out: None, or a contiguous torch
+        device tensor of at least n_maps * n * B 16-bit elements that receives the table indices.  Runs on the handle's stream and
+        synchronises nothing."""
+        f = self._beam_factors(factors, behind, ahead)
+        out = None
+        if residuals_out is not None:
+            if not (getattr(residuals_out, "is_cuda", False) and residuals_out.is_contiguous()):
+                raise ValueError("score_beams_dev: residuals_out must be a contiguous torch tensor on the device")
+            need = 2 * self.n_maps * self.n * int(B)
+            if residuals_out.numel() * residuals_out.element_size() < need:
+                raise ValueError(f"score_beams_dev: residuals_out holds {residuals_out.numel() * residuals_out.element_size()} bytes, the indices need {need}")
+            out = C.c_void_p(int(residuals_out.data_ptr()))
+        check(load().gms_pf_score_beams_dev(self._h, C.c_void_p(dev_beams), int(B), int(behind), int(ahead), ptr(f), out))
 
     def set_refine(self, on: bool = True):
         """scan steps (slam_update*) run findBestPose on every particle before weighting it (SLAM.java:96-97)."""

@@ -971,6 +971,50 @@ int gms_pf_modes(gms_pf *pf, int32_t mi, const gms_modes *q, uint32_t *labels, g
 int gms_pf_modes_dev(gms_pf *pf, int32_t mi, const gms_modes *q, uint32_t *dev_labels, gms_mode *dev_records, int32_t cap, int32_t *n_found,
                      int32_t *n_outside);
 
+/* ---- beam sensor model: weigh a particle by what lies BETWEEN the sensor and the end point -------------------------------------------
+ * gms_pf_score is the reference's probabilityOf, a beam-END-POINT model: the likelihood field under each end point, nothing of the way
+ * there.  A pose whose beams pass through a wall scores as well as one whose beams do not.  On a scattered filter (gms_pf_scatter) that
+ * keeps look-alike rooms alive; the ray-cast "beam" model every Monte-Carlo localiser offers beside it compares each measured range
+ * with the range the map predicts from the particle's pose.  This library's own definition (the reference has no such method), in
+ * integers down to the table look-up, and with one stated order for the product and the sum, so every output is unique.
+ *
+ * THE TABLE.  T = behind + ahead + 2, 0 <= behind, ahead <= 255.  The caller passes factors[2][T], host doubles: row 0 for beams with
+ * hit == 0, row 1 for beams with hit != 0; every entry finite and > 0.
+ * THE WALK of particle i (its pose and cached trig as they stand on the handle) and beam b: start and end point as GridMap.java:175-188,
+ * rayIterator.init(start + 0.5f, end + 0.5f, ahead) -- the predicted scans' walk with `ahead` in place of gms_params.extra_steps --,
+ * cut after W + H + ahead + 2 cells, ending where RayIterator.hasNext fails (it left the map, or `ahead` cells past the end point).
+ * THE RESIDUAL.  The first visited cell with logData > 0 (the casts' predicate: 0, -0.0 and NaN are not occupied) gives n_rem, the
+ * iterator's remaining count `n` AT that cell, before the step.  d = ahead + 1 - n_rem: for finite coordinates the walk index of that
+ * cell minus the walk index of the measured end cell; d < 0: the map has a wall in front of the end point, d > 0: behind it.  The
+ * table index is idx = n_rem > behind + ahead + 1 ? 0 : behind + ahead + 1 - n_rem, i.e. d + behind with d held at -behind from
+ * below.  A walk that finds no occupied cell -- it left the map, ended `ahead` steps past the end point, started outside or visited no
+ * cell -- gives idx = T - 1.  All of it is integer arithmetic on the iterator's own state: non-finite inputs need no rule of their own.
+ * THE WEIGHTS.  f[b] = factors[hit_b != 0][idx_b], lf[b] = logtab[hit_b != 0][idx_b], logtab = log() of every entry, taken once on the
+ * host (libm).  THE ORDER is part of the definition: partial l, l = 0 .. 255, starts at 1.0 (the product) and +0.0 (the sum) and takes
+ * the beams l, l + 256, ... in ascending order (an empty partial keeps its start); then the halving tree
+ * `for s in 128, 64, .., 1: p[l] = p[l] o p[l + s] for l < s`.  p[0] of the product is the particle's weight, p[0] of the sum its
+ * log-weight.  Nothing is contracted.
+ *
+ * beams [n_maps][B] as for gms_pf_score, 1 <= B <= the handle's max_beams; `factors` is a HOST pointer in both forms.  residuals may
+ * be NULL; if given, [n_maps][n][B], it receives idx per particle and beam (_dev: device memory, 2-byte aligned).  The host form
+ * synchronises only to read the residuals back; _dev synchronises nothing.
+ * Afterwards the filter is in exactly the state a gms_pf_score leaves: gms_pf_normalize, gms_pf_resample[_if],
+ * gms_pf_set_log_normalize, gms_pf_get_weights / _log_weights and gms_pf_modes work on these weights unchanged.  The call sees the map
+ * as gms_map_download_log would (a deferred `logData +=` pass is applied first), through the casts' bit plane (repeated calls on an
+ * unchanged map do not rebuild it, gms_map_cast_plane_builds), and changes neither poses nor map.  gms_pf_set_reference_order has no
+ * effect: the order above is the only one.  A shard scores its own particles (the score is local to a particle).
+ * Checked before anything is enqueued (GMS_ERR_INVALID, nothing touched): behind, ahead, B, NULL pointers, every entry of factors, the
+ * residuals' alignment.  GMS_ERR_STATE: the filter of a gms_slam (its particles live in their own maps).
+ *
+ * How: one workgroup of 256 lanes per particle, lane l walking the beams of partial l one after another through the window of the bit
+ * plane its scan can reach, staged in LDS as the predicted scans do (64 KiB at most; a larger window, or GMS_CAST_WALK=mem at creation,
+ * walks the plane in memory); the tree runs through LDS. */
+/* Pure host code: the ranges of behind and ahead, factors not NULL, 2 * (behind + ahead + 2) entries finite and > 0. */
+int gms_beam_model_check(int32_t behind, int32_t ahead, const double *factors);
+int gms_pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals);
+int gms_pf_score_beams_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B, int32_t behind, int32_t ahead, const double *factors,
+                           uint16_t *dev_residuals);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

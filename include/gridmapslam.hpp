@@ -306,6 +306,18 @@ public:
         check(gms_pf_modes_dev(h_, 0, &q, devLabels, devRecords, cap, &found, nOutside));
         return found;
     }
+    /** The beam sensor model (gridmapslam.h "beam sensor model"): every particle weighted by where the map's first wall lies on each
+     *  beam's walk relative to the measured end point.  factors [2][behind + ahead + 2] host doubles (row 0: beams that missed, row 1:
+     *  beams that hit), every entry finite and > 0; residuals (may be null) [size()][B] receives the table index per particle and
+     *  beam, and only then does the call wait on the stream.  Leaves the filter as score() does. */
+    void scoreBeams(const Observation &obs, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals = nullptr) {
+        check(gms_pf_score_beams(h_, obs.getMeasurements().data(), obs.getNumberOfMeasurements(), behind, ahead, factors, residuals));
+    }
+    /** scoreBeams() on device-resident beams [B] (devResiduals: device memory, 2-byte aligned, or null); factors stay host memory.
+     *  Runs on the handle's stream and synchronises nothing. */
+    void scoreBeamsDev(const gms_beam *devBeams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *devResiduals = nullptr) {
+        check(gms_pf_score_beams_dev(h_, devBeams, B, behind, ahead, factors, devResiduals));
+    }
     int size() const { return n_; }
     gms_pf *handle() { return h_; }
 
