@@ -10,8 +10,10 @@
 //                       inflate > 0: k_clear_field over the whole map at R = inflate into d_reach_d2, then k_reach_block ballots
 //                       d2 != FAR into d_reach_plane, a wavefront per 64 cells.
 //   k_reach_init        the working field all FAR, the control words and the tiles' flags zero.
-//   k_reach_seeds       a lane per seed: on the map and not blocked -> cost 0 and its tile active.  A gms_slam without seeds: the shown
-//                       particle's own cell, from its pose on the device.
+//   k_reach_seeds       a lane per seed: on the map and not blocked -> cost 0, and the tiles of the cell and of its eight neighbours active:
+//                       a round marks across an edge only where a cell CHANGED, and the seed's own cell never does, so a seed whose
+//                       neighbours inside its tile are all blocked (or whose tile is one cell) would hand nothing on.  A gms_slam
+//                       without seeds: the shown particle's own cell, from its pose on the device.
 //   k_reach_round       ONE ROUND: a workgroup of one wavefront per 64 x 64 tile; the tiles that are not active leave at once.  An active
 //                       tile loads its cells and a one-cell halo into LDS (66 x 66 uint16), relaxes to ITS fixpoint against that halo,
 //                       writes back what changed and marks the neighbours across every edge or corner whose cell changed active for the
@@ -93,7 +95,11 @@ k_reach_seeds(GridDev g, uint16_t *__restrict__ field, const uint64_t *__restric
     if (gx < 0 || gy < 0 || gx >= g.W || gy >= g.H) return;
     if ((plane[(size_t)gy * (size_t)wpr64 + (size_t)(gx >> 6)] >> (gx & 63)) & 1ull) return;
     field[(size_t)gy * (size_t)g.W + (size_t)gx] = 0;
-    reach_mark(ctl + RCH_CTL_WORDS, ctl + 2, (gy >> 6) * ntx + (gx >> 6));
+    for (int32_t dy = -1; dy <= 1; dy++)                                        // (a seed inside its tile marks that tile nine times: one count)
+        for (int32_t dx = -1; dx <= 1; dx++) {
+            const int32_t nx = gx + dx, ny = gy + dy;
+            if (nx >= 0 && ny >= 0 && nx < g.W && ny < g.H) reach_mark(ctl + RCH_CTL_WORDS, ctl + 2, (ny >> 6) * ntx + (nx >> 6));
+        }
 }
 
 // One directional sweep of the tile s (66 x 66, cell (t, l) at s[(l + 1) * SL + (t + 1) * ST]): lane l owns line l and walks t = 0 .. 63
