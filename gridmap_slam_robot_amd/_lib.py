@@ -118,6 +118,20 @@ class GmsScatter(C.Structure):
     ]
 
 
+class GmsLocate(C.Structure):
+    """gms_locate: a global scan-matching request (gridmapslam.h "global scan matching")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("n_theta", C.c_int32), ("tol", C.c_int32), ("mode", C.c_int32), ("min_score", C.c_int32),
+        ("cap", C.c_int32), ("free_only", C.c_int32), ("filter", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+class GmsLocateRec(C.Structure):
+    """gms_locate_rec: one pose's record, 16 bytes"""
+    _fields_ = [("score", C.c_int32), ("k", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
 class GmsModes(C.Structure):
     """gms_modes: a pose-mode request (gridmapslam.h "pose modes")"""
     _fields_ = [("bin_cells", C.c_int32), ("n_theta", C.c_int32), ("min_count", C.c_int32), ("pad", C.c_int32)]
@@ -136,6 +150,9 @@ class GmsMode(C.Structure):
 
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
+LOCATE_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsLocateRec._fields_])     # gms_locate_rec
+assert LOCATE_DTYPE.itemsize == C.sizeof(GmsLocateRec) == 16 and C.sizeof(GmsLocate) == 48
+GMS_LOCATE_SKIP = -32768
 FRONTIER_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsFrontier._fields_])     # gms_frontier
 assert FRONTIER_DTYPE.itemsize == C.sizeof(GmsFrontier) == 56
 GMS_FRONTIER_NONE = 0xFFFFFFFF
@@ -369,6 +386,14 @@ def load() -> C.CDLL:
     sig("gms_scatter_check", C.c_int, scp)
     sig("gms_pf_scatter", C.c_int, vp, scp, C.c_uint64, C.c_uint64, vp)
     sig("gms_map_scatter_table_builds", C.c_int, vp, C.POINTER(C.c_int64))
+    lp = C.POINTER(GmsLocate)
+    sig("gms_locate_check", C.c_int, lp)
+    sig("gms_locate_offsets", C.c_int, vp, i32, C.c_double, C.c_double, i32, C.c_double, vp)
+    sig("gms_map_locate", C.c_int, vp, i32, lp, vp, i32, vp, vp)
+    sig("gms_map_locate_dev", C.c_int, vp, i32, lp, vp, i32, vp, vp)
+    sig("gms_slam_locate", C.c_int, vp, i32, lp, vp, i32, vp, vp, vp)
+    sig("gms_slam_locate_dev", C.c_int, vp, i32, lp, vp, i32, vp, vp, vp)
+    sig("gms_map_locate_stats", C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64))
     mp = C.POINTER(GmsModes)
     sig("gms_modes_check", C.c_int, mp)
     sig("gms_pf_modes", C.c_int, vp, i32, mp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))

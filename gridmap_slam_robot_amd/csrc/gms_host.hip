@@ -250,6 +250,8 @@ static int map_free(gms_map *m) {
     hipFree(m->d_front_plane); hipFree(m->d_front_nf); hipFree(m->d_front_label); hipFree(m->d_front_wscan); hipFree(m->d_front_table); hipFree(m->d_front_ctl);
     if (m->h_front_ctl) hipHostFree(m->h_front_ctl);
     hipFree(m->scatter.d_elig); hipFree(m->scatter.d_pre);
+    hipFree(m->locate.d_pyr); hipFree(m->locate.d_list[0]); hipFree(m->locate.d_list[1]); hipFree(m->locate.d_ctl);
+    if (m->locate.h_ctl) hipHostFree(m->locate.h_ctl);
     hipFree(m->d_trace_cells); hipFree(m->d_trace_cls); hipFree(m->d_trace_cnt);
     if (m->h_beams) hipHostFree(m->h_beams);
     ring_free(m->beam_ring);
@@ -363,6 +365,8 @@ int gms_map_create(const gms_params *p, gms_map **out) {
         m->gain_walk_mem = gw_env && gw_env[0] == 'm';
         const char *ss_env = getenv("GMS_SCATTER_SHIFT");                      // a coarser staged search than the plane asks for (tests; gms_scatter.hip)
         m->scatter_shift = ss_env ? std::min(20, std::max(0, atoi(ss_env))) : 0;
+        const char *ll_env = getenv("GMS_LOCATE_LEVELS");                      // the scan matcher's top level, 0 = exhaustive (tests; gms_locate.hip)
+        m->locate_levels = ll_env && ll_env[0] ? std::min(7, std::max(0, atoi(ll_env))) : -1;
     }
     {   // the tiled batched ray cast: 8 KiB of slots + a 64 KiB tile + static LDS
         int lds_max = 0;

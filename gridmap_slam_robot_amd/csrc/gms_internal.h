@@ -151,6 +151,17 @@ struct gms_map {
         int64_t builds;           // tables built so far (tests: a scatter on an unchanged map builds none)
     } scatter;
     int32_t scatter_shift;        // the draw stages every (1 << shift)-th word's prefix at least this coarsely (GMS_SCATTER_SHIFT: tests of the search in memory)
+    // global scan matching (gms_locate.hip); allocated by the first request, the work lists grow and never shrink
+    struct {
+        uint64_t *d_pyr;          // [7][H][wpr64] the OR pyramid's planes P_1 .. P_7 (P_0 is the hit plane, read in place)
+        uint64_t *d_list[2];      // the work lists of alternate levels: entries k << 40 | y << 20 | x; after level 0 the survivors' keys
+        int64_t list_cap[2];      // entries each holds
+        uint32_t *d_ctl;          // {the two lists' counters, the threshold, 5 spare} | [GMS_MAX_BEAMS + 1] the proven leaves' score histogram
+        uint32_t *h_ctl;          // pinned: the first 8 words of it, read back once per level
+        int32_t levels;           // gms_map_locate_stats: the top level of the last request ...
+        int64_t evaluated[8];     // ... and the candidates it evaluated per level
+    } locate;
+    int32_t locate_levels;        // the top level of every request, whatever its rectangle (GMS_LOCATE_LEVELS = 0 .. 7: tests; 0 is the exhaustive search); -1: from the rectangle
     int32_t need_full_build;  // likelihood field must be rebuilt everywhere (upload/reset/copy)
     int32_t apply_pending;    // the last scan's counts are not in logData yet (deferred apply pass, gms_flush_apply)
     int32_t raycast_tile;     // batched ray casts accumulate in LDS tiles (k_raycast_tile; GMS_RAYCAST_TILE=0 turns it off)
@@ -527,9 +538,9 @@ void gms_launch_debug_f32(gms_map *m, int32_t op, const float *d_a, float *d_out
 void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_out);
 
 // ---- map queries: views, predicted scans (gms_cast.hip), view gain (gms_gain.hip), clearance fields (gms_clearance.hip), cost-to-go fields
-// (gms_reach.hip), frontier regions (gms_frontier.hip), particle seeding (gms_scatter.hip), pose modes (gms_modes.hip) and the beam sensor
-// model (gms_beams.hip: beside cast, on the base alone).  The layering: the query base (gms_query.hip:
-// everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier and scatter (they inflate
+// (gms_reach.hip), frontier regions (gms_frontier.hip), particle seeding (gms_scatter.hip), global scan matching (gms_locate.hip), pose modes
+// (gms_modes.hip) and the beam sensor model (gms_beams.hip: beside cast, on the base alone).  The layering: the query base (gms_query.hip:
+// everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier, scatter and locate (they inflate
 // with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only) ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message

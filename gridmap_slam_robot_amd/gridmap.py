@@ -179,6 +179,85 @@ def probe_fan(n: int, range_m: float, fov: float = 2 * math.pi) -> np.ndarray:
     return b
 
 
+def locate_offsets(scan, n_theta: int, resolution: float, theta0: float = 0.0, dtheta: Optional[float] = None) -> np.ndarray:
+    """The offset table of a scan for locate() (gridmapslam.h "global scan matching", gms_locate_offsets; no device needed): int16
+    [n_theta][B][2], entry (k, b) the end cell (dx, dy) of beam b relative to the pose's cell under the heading theta0 + k * dtheta
+    -- dtheta defaults to a full turn over n_theta --, the pose at the centre of its cell.  Beams that missed, non-finite ones and
+    those beyond 4095 cells become the pair (GMS_LOCATE_SKIP, GMS_LOCATE_SKIP) and do not count."""
+    b = _beams_of(scan).reshape(-1)
+    n_theta = int(n_theta)
+    if dtheta is None:
+        dtheta = 2.0 * math.pi / max(n_theta, 1)
+    out = np.empty((max(n_theta, 0), len(b), 2), dtype=np.int16)
+    check(load().gms_locate_offsets(ptr(b), len(b), float(theta0), float(dtheta), n_theta, float(resolution), ptr(out)))
+    return out
+
+
+def locate_poses(records, position, resolution: float, theta0: float = 0.0, dtheta: Optional[float] = None, n_theta: Optional[int] = None) -> np.ndarray:
+    """locate()'s records as poses, float64 [n][3]: x = position.x + (record.x + 0.5) * resolution, y likewise -- the centre of the
+    cell --, theta = theta0 + k * dtheta (dtheta, or a full turn over n_theta: what locate_offsets was given)."""
+    r = np.asarray(records)
+    if dtheta is None:
+        if n_theta is None:
+            raise ValueError("locate_poses: dtheta or n_theta is required")
+        dtheta = 2.0 * math.pi / int(n_theta)
+    out = np.empty((len(r), 3), dtype=np.float64)
+    out[:, 0] = float(position[0]) + (r["x"].astype(np.float64) + 0.5) * float(resolution)
+    out[:, 1] = float(position[1]) + (r["y"].astype(np.float64) + 0.5) * float(resolution)
+    out[:, 2] = float(theta0) + r["k"].astype(np.float64) * float(dtheta)
+    return out
+
+
+def locate_peaks(records, radius: int, k_radius: Optional[int] = None, n_theta: Optional[int] = None) -> np.ndarray:
+    """Greedy non-maximum suppression over locate()'s records (host code): the best `cap` records cluster around each peak, so walk
+    them in their order -- best first -- and keep a record unless a kept one lies within `radius` cells of it along both axes (and,
+    with k_radius, within k_radius heading indices; n_theta: the headings wrap around a full turn).  Returns the kept records."""
+    r = np.asarray(records)
+    keep = []
+    for i in range(len(r)):
+        x, y, k = int(r["x"][i]), int(r["y"][i]), int(r["k"][i])
+        for j in keep:
+            if abs(int(r["x"][j]) - x) > radius or abs(int(r["y"][j]) - y) > radius:
+                continue
+            if k_radius is not None:
+                dk = abs(int(r["k"][j]) - k)
+                if n_theta is not None:
+                    dk = min(dk, int(n_theta) - dk)
+                if dk > k_radius:
+                    continue
+            break
+        else:
+            keep.append(i)
+    return r[keep]
+
+
+def _locate_args(W: int, H: int, rect, offsets_shape, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, filter: int = 0):
+    """the gms_locate of a request on a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map; offsets_shape = (n_theta, B)"""
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
+    lc = _lib.GmsLocate(x0, y0, w, h, int(offsets_shape[0]), int(tol), _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED,
+                        int(min_score), int(cap), int(bool(free_only)), int(filter), 0)
+    return lc
+
+
+def _locate_table(offsets) -> np.ndarray:
+    """offsets as the int16 [n_theta][B][2] table the library takes"""
+    a = np.ascontiguousarray(offsets, dtype=np.int16)
+    if a.ndim != 3 or a.shape[2] != 2:
+        raise ValueError(f"locate: offsets must be [n_theta][B][2] (dx, dy) cells, not {a.shape}")
+    return a
+
+
+def _locate_device(out, n_out, cap: int):
+    """the device addresses of a caller's torch tensors that are to receive cap gms_locate_rec records and their number"""
+    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
+        raise ValueError("locate: out must be a contiguous torch tensor on the device")
+    if out.numel() * out.element_size() < _lib.LOCATE_DTYPE.itemsize * cap:
+        raise ValueError(f"locate: out holds {out.numel() * out.element_size()} bytes, the records need {_lib.LOCATE_DTYPE.itemsize * cap}")
+    if not (getattr(n_out, "is_cuda", False) and n_out.element_size() == 4 and n_out.numel() >= 1):
+        raise ValueError("locate: n_out must be an int32 torch tensor on the device")
+    return C.c_void_p(int(out.data_ptr())), C.c_void_p(int(n_out.data_ptr()))
+
+
 def scatter_slots(n: int, fraction: float):
     """(first, count) of the slots a recovery step replaces by fresh uniform samples after a resample: the LAST round(fraction * n)
     slots of a filter of n -- after resample() a slot's index says nothing about its particle, so any block serves --, at least one
@@ -549,6 +628,39 @@ class GridMap:
         check(load().gms_map_gain_dev(self._h, int(mi), C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
                                       C.c_void_p(_gain_device_out(out, P))))
         return out
+
+    def locate(self, offsets, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64, free_only: bool = True,
+               mi: int = 0, full: bool = False):
+        """Global scan matching (gridmapslam.h "global scan matching") in map mi: the candidates (k, x, y) -- a heading index of
+        offsets [n_theta][B][2] (locate_offsets()) and a cell of rect = (x0, y0, w, h) (None: the whole map), with free_only only
+        the known-free cells -- whose SCORE, the beams that end within tol cells of an obstacle (logData > 0, or with not_free every
+        cell not known free), is at least min_score: the best cap of them (<= 4096) as gms_locate_rec records (LOCATE_DTYPE: score, k,
+        x, y), score descending, then k, y, x ascending.  The result of the exhaustive search, found by a pruned multi-resolution
+        one.  full=True: (all cap records, n_out), the filler records {0, -1, -1, -1} behind the first n_out included.
+        Poses: locate_poses(); peaks: locate_peaks()."""
+        t = _locate_table(offsets)
+        lc = _locate_args(self.W, self.H, rect, t.shape, tol, not_free, min_score, cap, free_only)
+        rec = np.empty(max(int(cap), 0), dtype=_lib.LOCATE_DTYPE)
+        n = C.c_int32(0)
+        check(load().gms_map_locate(self._h, int(mi), C.byref(lc), ptr(t), t.shape[1], ptr(rec), C.byref(n)))
+        return (rec, int(n.value)) if full else rec[:n.value]
+
+    def locate_dev(self, dev_offsets: int, n_theta: int, B: int, out, n_out, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1,
+                   cap: int = 64, free_only: bool = True, mi: int = 0):
+        """locate() with device memory on the handle's stream: dev_offsets the table's device address (its entries within [-4095,
+        4095] or SKIP pairs: a precondition), out a contiguous torch device tensor of cap * 16 bytes (16-byte aligned), n_out an int32
+        one.  The call waits on the stream once per level of the search."""
+        lc = _locate_args(self.W, self.H, rect, (n_theta, B), tol, not_free, min_score, cap, free_only)
+        po, pn = _locate_device(out, n_out, int(cap))
+        check(load().gms_map_locate_dev(self._h, int(mi), C.byref(lc), C.c_void_p(dev_offsets), int(B), po, pn))
+        return out, n_out
+
+    def locate_stats(self) -> dict:
+        """diagnostics of the last locate() on this handle: {"levels": the top level L of its search, "evaluated": the candidates it
+        evaluated at levels 0 .. 7}"""
+        levels, ev = C.c_int32(0), (C.c_int64 * 8)()
+        check(load().gms_map_locate_stats(self._h, C.byref(levels), ev))
+        return {"levels": int(levels.value), "evaluated": [int(v) for v in ev]}
 
     def scatter_table_builds(self) -> int:
         """diagnostics: seeding tables built so far (ParticleFilter.scatter on an unchanged map with the same request builds none)"""
@@ -1452,6 +1564,31 @@ class _SlamHandle:
         check(load().gms_slam_gain(self._h, int(which), C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(rec), C.byref(shown)))
         return rec, int(shown.value)
 
+    def _locate(self, which, filter: int, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
+                shown_out):
+        """gms_slam_locate[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (records, shown)"""
+        if isinstance(which, str):
+            if which != "strongest":
+                raise ValueError('locate: which must be a particle index or "strongest"')
+            which = _lib.GMS_VIEW_STRONGEST
+        if out is not None:                                  # offsets: (device address, n_theta, B)
+            dev_offsets, n_theta, B = offsets
+            lc = _locate_args(self.W, self.H, rect, (n_theta, B), tol, not_free, min_score, cap, free_only, filter)
+            po, pn = _locate_device(out, n_out, int(cap))
+            sh = None
+            if shown_out is not None:
+                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
+                    raise ValueError("locate: shown_out must be an int32 torch tensor on the device")
+                sh = C.c_void_p(int(shown_out.data_ptr()))
+            check(load().gms_slam_locate_dev(self._h, int(which), C.byref(lc), C.c_void_p(dev_offsets), int(B), po, pn, sh))
+            return out, n_out, shown_out
+        t = _locate_table(offsets)
+        lc = _locate_args(self.W, self.H, rect, t.shape, tol, not_free, min_score, cap, free_only, filter)
+        rec = np.empty(max(int(cap), 0), dtype=_lib.LOCATE_DTYPE)
+        n, shown = C.c_int32(0), C.c_int32(-1)
+        check(load().gms_slam_locate(self._h, int(which), C.byref(lc), ptr(t), t.shape[1], ptr(rec), C.byref(n), C.byref(shown)))
+        return ((rec, int(n.value)) if full else rec[:n.value]), int(shown.value)
+
     def _clearance(self, which, filter: int, rect, max_radius: int, not_free: bool, out, shown_out):
         """gms_slam_clearance[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (field, shown)"""
         if isinstance(which, str):
@@ -1724,6 +1861,14 @@ class SLAMParticleMaps(_SlamHandle):
         is synchronised."""
         return self._gain(which, 0, poses, probes, max_range, out, shown_out)
 
+    def locate(self, offsets, which="strongest", rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
+               free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):
+        """Global scan matching in particle `which`'s OWN map (GridMap.locate's records): (records, shown).  which = a particle index
+        or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  out / n_out / shown_out:
+        torch device tensors, offsets then (device address, n_theta, B); returns (out, n_out, shown_out).  Diagnostics:
+        grid_map.locate_stats()."""
+        return self._locate(which, 0, offsets, rect, tol, not_free, min_score, cap, free_only, full, out, n_out, shown_out)
+
     def trajectory(self, which="strongest", out=None, shown_out=None):
         """(xytheta [kept][3], shown): the path particle `which` (a slot, or "strongest" as view() picks it) descends along, oldest
         first over the kept updates of set_history() -- the path its map was built along, whatever resampling did to the slots since.
@@ -1953,6 +2098,16 @@ class SLAMParticleMapsBatch(_SlamHandle):
         elif not 0 <= filter < self.num_filters:
             raise IndexError(f"filter {filter} out of range ({self.num_filters})")
         return self._gain(which, filter, poses, probes, max_range, out, shown_out)
+
+    def locate(self, offsets, which="strongest", filter: int = 0, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
+               free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):
+        """SLAMParticleMaps.locate for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
+        the handle-wide slot filter * num_particles + k in whose map the scan was matched, as view() reports it"""
+        if not isinstance(which, str):
+            which = self._slot(filter, which)
+        elif not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return self._locate(which, filter, offsets, rect, tol, not_free, min_score, cap, free_only, full, out, n_out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown

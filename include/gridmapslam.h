@@ -892,6 +892,95 @@ int gms_pf_scatter(gms_pf *pf, const gms_scatter *sc, uint64_t seed, uint64_t se
 /* diagnostics: seeding tables built on this handle so far (tests: a scatter on an unchanged map with the same request builds none) */
 int gms_map_scatter_table_builds(const gms_map *m, int64_t *builds);
 
+/* ---- global scan matching: which poses explain a scan best, anywhere in the map ---------------------------------------------------
+ * What start-up on a saved map, a kidnapped robot and a loop-closure check against an old map ask: given ONE scan and a map, the poses
+ * of a whole rectangle that explain it best -- without a scattered filter and several revolutions.  The multi-resolution correlative
+ * search (Olson 2009; what Cartographer uses for loop closure) on bit planes.  This library's own definition (the reference has no such
+ * method: its findBestPose looks at 1210 poses around a start that is nearly right); all of it is integer arithmetic, and what is
+ * returned is the result of the exhaustive search.
+ *
+ * The HIT PLANE: a cell is a HIT cell if an obstacle cell under `mode` (GMS_CLEAR_OCCUPIED: logData > 0; GMS_CLEAR_NOT_FREE:
+ *   !(logData < 0)) of the whole map lies within tol cells of it, d2 <= tol^2, 0 <= tol <= 255: exactly the cost-to-go fields' BLOCKED
+ *   plane at inflate = tol, and with tol == 0 the obstacle plane itself, read in place.  Cells outside the map are never hits.
+ * The scan as OFFSETS: int16_t offsets [n_theta][B][2]; (dx, dy) is the end cell of beam b relative to the pose's cell under heading
+ *   index k.  The pair (GMS_LOCATE_SKIP, GMS_LOCATE_SKIP) marks a beam that does not count; any other component must lie in
+ *   [-4095, 4095].  The host forms check that (GMS_ERR_INVALID).  For the _dev forms it is a PRECONDITION: a pair with a component
+ *   outside that range is treated as SKIP on the device and never used as an address.
+ * gms_locate_offsets makes the table from a scan; pure host code, usable without a device.  For k = 0 .. n_theta - 1:
+ *   theta = theta0 + (double)k * dtheta;  c = cos(theta), s = sin(theta) (libm);
+ *   ex = (double)local_x * c - (double)local_y * s,  ey = (double)local_x * s + (double)local_y * c -- both products and the sum each
+ *   rounded on their own, never fused (the library is compiled with -ffp-contract=off);
+ *   dx = (int)floor(ex / (double)resolution + 0.5), dy likewise: the pose stands at the centre of its cell.
+ *   A beam with hit == 0, a non-finite coordinate, or |dx| or |dy| > 4095 becomes SKIP.
+ * CANDIDATES: (k, x, y) with 0 <= k < n_theta and (x, y) a cell of the rectangle [x0, x0 + w) x [y0, y0 + h) (gms_view's rectangle
+ *   rules); with free_only = 1 only FREE cells (logData < 0, the frontier regions' class).  n_theta * w * h may not exceed 2^31 - 1, a
+ *   side of the map not 2^20 cells.
+ * SCORE(k, x, y): the number of non-SKIP beams b whose cell (x + dx, y + dy) is inside the map and is a HIT cell.
+ * THE RESULT: with N the number of candidates of SCORE >= min_score (1 <= min_score <= B): *n_out = min(cap, N), 1 <= cap <= 4096;
+ *   out[0 .. n_out) holds the first n_out of them in the order score descending, then k, then y, then x ascending; out[n_out .. cap) is
+ *   set to {0, -1, -1, -1}.  N itself is NOT returned: the call may therefore raise its working threshold to the cap-th best score it
+ *   has proven and never look at the candidates below it.  That changes nothing that is returned.
+ *
+ * "Sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment" (a deferred `logData +=` pass is applied
+ * first, an owed resampling copy is looked through), "changes no later result of its handle" and the argument checks before anything is
+ * enqueued (GMS_ERR_INVALID, nothing touched) are the casts' rules.  B ranges over 1 .. the handle's max_beams; a batched map handle
+ * serves map mi.
+ *
+ * How: the obstacle plane comes from the query base, read in place (packed only when stale: gms_map_cast_plane_builds does not move
+ * for a plane that is current), the hit plane for tol > 0 from the cost-to-go fields' inflation.  (1) An OR PYRAMID P_0 .. P_L in the
+ * planes' layout: bit (x, y) of P_l is the OR of the hit plane over [x, x + 2^l) x [y, y + 2^l) clipped to the map -- the window slides,
+ * nothing is decimated --, a lane per 64-bit word with funnel shifts across word boundaries.  (2) The search runs breadth first, one
+ * launch per level l = L .. 0 over a work list: a level-l candidate (k, bx, by), bx - x0 and by - y0 multiples of 2^l, stands for the
+ * translations of its 2^l x 2^l block; its BOUND, the number of non-SKIP beams with bit (bx + dx, by + dy) of P_l set (a coordinate in
+ * [-(2^l - 1), -1] clamped to 0: the window only grows), is at least every SCORE in the block.  A wavefront per candidate strides its
+ * lanes over the beams and counts with ballots.  A candidate whose BOUND is not below the threshold hands its children inside the
+ * rectangle to the next level.  The threshold starts at min_score and rises to the cap-th largest score of the leaves proven so far
+ * (every candidate also scores its block's own origin against P_0 into a histogram of B + 1 counters).  Pruning is strict, BOUND <
+ * threshold, so ties at the cut survive to the ranking.  (3) Level 0 computes scores, applies free_only and the threshold, and one
+ * workgroup selects and orders the best cap by the 64-bit key (B - score, k, y, x).  No workgroup waits on another.
+ * L comes from the rectangle (the largest L <= 7 with 2^(L+2) <= max(w, h)); GMS_LOCATE_LEVELS=n in the environment at the handle's
+ * creation forces it (tests; n = 0 is the exhaustive search on the device).  The same records at every L.
+ * The call WAITS ON THE STREAM once per level -- it reads the next work list's length back, eight words, as gms_map_reach_dev does
+ * between batches of rounds --, the _dev forms included; the host forms once more for the records.  A work list that would exceed 2^24
+ * entries returns GMS_ERR_NOMEM with the advice to raise min_score or shrink the rectangle, and nothing is written to the outputs.
+ * The pyramid (7 planes), the lists and the control words live on the handle, allocated by the first request; the lists only grow. */
+#define GMS_LOCATE_SKIP (-32768)                               /* INT16_MIN in both components: a beam that does not count */
+typedef struct gms_locate {
+    int32_t x0, y0, w, h;       /* the cell rectangle of candidate positions */
+    int32_t n_theta;            /* heading indices, 1 .. 1024: the rows of the offset table */
+    int32_t tol;                /* cells, 0 .. 255: how far from an obstacle cell a beam's end cell still counts */
+    int32_t mode;               /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE: what an obstacle cell is */
+    int32_t min_score;          /* 1 .. B: candidates below it are never returned */
+    int32_t cap;                /* 1 .. 4096: records returned at most */
+    int32_t free_only;          /* 1: only FREE cells are candidates; 0: every cell of the rectangle */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+    int32_t pad;                /* not read */
+} gms_locate;
+typedef struct gms_locate_rec { /* 16 bytes */
+    int32_t score;              /*  0: SCORE(k, x, y); a filler record: 0 */
+    int32_t k;                  /*  4: the heading index; a filler record: -1 */
+    int32_t x, y;               /*  8, 12: the pose's cell; a filler record: -1, -1 */
+} gms_locate_rec;
+/* Pure host code, as gms_scatter_check: everything about the request but the map's bounds and B, which it does not know. */
+int gms_locate_check(const gms_locate *lc);
+/* Pure host code: the offset table of a scan (above); offsets [n_theta][B][2]. */
+int gms_locate_offsets(const gms_beam *beams, int32_t B, double theta0, double dtheta, int32_t n_theta, double resolution, int16_t *offsets);
+/* Map mi of a shared or batched map; out [cap], *n_out the records that count.  The host form stages the table, reads the records
+ * back and synchronises; _dev takes device pointers (dev_out 16-byte aligned, dev_n_out a device int32_t *, the table 4-byte aligned)
+ * and runs on the handle's stream, on which it waits once per level. */
+int gms_map_locate(gms_map *m, int32_t mi, const gms_locate *lc, const int16_t *offsets, int32_t B, gms_locate_rec *out, int32_t *n_out);
+int gms_map_locate_dev(gms_map *m, int32_t mi, const gms_locate *lc, const int16_t *dev_offsets, int32_t B, gms_locate_rec *dev_out,
+                       int32_t *dev_n_out);
+/* The per-particle filter: the scan against the map of the shown particle.  `which`, GMS_VIEW_STRONGEST, lc->filter, *shown (may be
+ * NULL; _dev: a device int32_t *) and the GMS_ERR_STATE cases are gms_slam_view's; particle and generation are picked on the device. */
+int gms_slam_locate(gms_slam *s, int32_t which, const gms_locate *lc, const int16_t *offsets, int32_t B, gms_locate_rec *out, int32_t *n_out,
+                    int32_t *shown);
+int gms_slam_locate_dev(gms_slam *s, int32_t which, const gms_locate *lc, const int16_t *dev_offsets, int32_t B, gms_locate_rec *dev_out,
+                        int32_t *dev_n_out, int32_t *dev_shown);
+/* diagnostics of the last request on this handle (a gms_slam's: gms_slam_handles' map), as gms_map_reach_stats: *levels = L, evaluated
+ * [8] = the candidates evaluated at level l (0 beyond L, and below a level that left no candidate).  Either may be NULL. */
+int gms_map_locate_stats(const gms_map *m, int32_t *levels, int64_t *evaluated);
+
 /* ---- pose modes: the hypotheses a particle cloud still holds ---------------------------------------------------------------------------
  * What a localiser on a scattered filter asks every scan: how many hypotheses are left, where is each, how much weight does it hold and
  * how tight is it -- the heaviest cluster's pose and covariance, and "has the filter converged" as "does one cluster hold nearly all

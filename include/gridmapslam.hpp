@@ -211,6 +211,30 @@ public:
     gms_frontiers fullFrontiers(int minSize = 1, int inflate = 0) const { return gms_frontiers{0, 0, w_, hgt_, minSize, inflate, 0, 0}; }
     /** rounds launched and tile relaxations run for the last cost-to-go field of this handle */
     void reachStats(int32_t *rounds, int64_t *tileRuns) const { check(gms_map_reach_stats(h_, rounds, tileRuns)); }
+    /** The offset table of a scan for locate() (gridmapslam.h "global scan matching"; pure host code): [nTheta][B][2] end cells
+     *  relative to the pose's cell under the headings theta0 + k * dtheta; misses and beams beyond 4095 cells become SKIP pairs. */
+    std::vector<int16_t> locateOffsets(const Observation &z, double theta0, double dtheta, int nTheta) const {
+        const auto &ms = z.getMeasurements();
+        std::vector<int16_t> off((size_t)nTheta * ms.size() * 2);
+        check(gms_locate_offsets(ms.data(), (int32_t)ms.size(), theta0, dtheta, nTheta, (double)params_.resolution, off.data()));
+        return off;
+    }
+    /** Global scan matching in map mi: the best lc.cap candidates (heading index, cell) of lc's rectangle whose score -- the beams
+     *  of `offsets` [lc.n_theta][B][2] that end within lc.tol cells of an obstacle -- is at least lc.min_score, score descending,
+     *  then k, y, x ascending: the exhaustive search's result, found by a pruned multi-resolution one. */
+    std::vector<gms_locate_rec> locate(const gms_locate &lc, const std::vector<int16_t> &offsets, int mi = 0) {
+        std::vector<gms_locate_rec> rec((size_t)lc.cap);
+        int32_t n = 0;
+        check(gms_map_locate(h_, mi, &lc, offsets.data(), (int32_t)(offsets.size() / 2 / (size_t)(lc.n_theta > 0 ? lc.n_theta : 1)), rec.data(), &n));
+        rec.resize((size_t)n);
+        return rec;
+    }
+    /** the whole map's scan-matching request */
+    gms_locate fullLocate(int nTheta, int tol, int minScore, int cap = 64, bool freeOnly = true, bool notFree = false) const {
+        return gms_locate{0, 0, w_, hgt_, nTheta, tol, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, minScore, cap, freeOnly ? 1 : 0, 0, 0};
+    }
+    /** the top level of this handle's last locate() and the candidates it evaluated per level, evaluated[8] */
+    void locateStats(int32_t *levels, int64_t *evaluated) const { check(gms_map_locate_stats(h_, levels, evaluated)); }
     /** the clearance under every pose's cell, without making a field; GMS_CLEAR_OUTSIDE for a pose off the map */
     std::vector<uint16_t> clearanceOf(const std::vector<Pose> &poses, int maxRadius, bool notFree = false, int mi = 0) {
         std::vector<float> p(3 * poses.size());
@@ -551,6 +575,16 @@ public:
         check(gms_slam_clearance(h_, which, &c, out.data(), &picked));
         if (shown) *shown = picked;
         return out;
+    }
+    /** Global scan matching in particle `which`'s own map (GridMap::locate's records); *shown (may be null) receives the particle in
+     *  whose map the scan was matched */
+    std::vector<gms_locate_rec> locate(const gms_locate &lc, const std::vector<int16_t> &offsets, int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        std::vector<gms_locate_rec> rec((size_t)lc.cap);
+        int32_t n = 0, picked = 0;
+        check(gms_slam_locate(h_, which, &lc, offsets.data(), (int32_t)(offsets.size() / 2 / (size_t)(lc.n_theta > 0 ? lc.n_theta : 1)), rec.data(), &n, &picked));
+        rec.resize((size_t)n);
+        if (shown) *shown = picked;
+        return rec;
     }
     /** The view gain of the caller's candidate poses in particle `which`'s own map (GridMap::gain's records); *shown (may be null)
      *  receives the particle in whose map they were judged */
