@@ -133,6 +133,38 @@ def test_offsets_equal_the_formula_bit_for_bit(n_theta):
     assert zero[0, 20].tolist() == [4095, 0] and zero[0, 21].tolist() == [GMS_LOCATE_SKIP] * 2 and zero[0, 23].tolist() == [0, -1]
 
 
+def test_offsets_whose_floor_lands_on_the_ranges_ends():
+    """floor(e / resolution + 0.5) exactly +-4095 (the last offsets in range) and +-4096 (the first beyond: SKIP), in either component,
+    at resolution 1 where the quotient is exact, and at 0.05 and 0.25 against the formula"""
+    ends = [4095.0, 4095.49999, 4095.5, 4096.0, -4095.0, -4095.5, -4095.50001, -4096.0, -4096.5]
+    floors = [4095, 4095, 4096, 4096, -4095, -4095, -4096, -4096, -4096]
+    b = np.zeros(2 * len(ends) + 1, dtype=BEAM_DTYPE)
+    b["hit"] = 1
+    b["local_x"][:len(ends)] = ends                                            # the x component at the end, y = 0
+    b["local_y"][len(ends):-1] = ends                                          # the y component
+    b["local_x"][len(ends):-1] = 7.0
+    b["local_x"][-1], b["local_y"][-1] = 4095.0, -4095.0                       # both at once
+    got = locate_offsets(b, 1, 1.0)
+    assert np.array_equal(got, lx.offsets_of(b["local_x"], b["local_y"], b["hit"], 1, 1.0))
+    for i, f in enumerate(floors):
+        inside = abs(f) <= 4095
+        assert got[0, i].tolist() == ([f, 0] if inside else [GMS_LOCATE_SKIP] * 2), (ends[i], got[0, i])
+        assert got[0, len(ends) + i].tolist() == ([7, f] if inside else [GMS_LOCATE_SKIP] * 2), (ends[i], got[0, len(ends) + i])
+    assert got[0, -1].tolist() == [4095, -4095]
+    for res in (0.05, 0.25):                                                   # 0.25: exact quotients again; 0.05: whatever the division rounds to
+        for n_theta, theta0 in ((1, 0.0), (4, 0.0), (8, 0.3)):
+            c = b.copy()
+            c["local_x"] *= res
+            c["local_y"] *= res
+            got = locate_offsets(c, n_theta, res, theta0)
+            want = lx.offsets_of(c["local_x"], c["local_y"], c["hit"], n_theta, res, theta0)
+            assert np.array_equal(got, want), (res, n_theta, np.argwhere(got != want)[:3])
+            live = got[(got != GMS_LOCATE_SKIP).all(axis=2)].astype(np.int32)
+            assert (np.abs(live) <= 4095).all() and (theta0 != 0.0 or (np.abs(live) == 4095).any())
+    quarter = locate_offsets(b[:1], 4, 1.0)                                    # (4095, 0) turned by quarter turns stays on the range's end
+    assert quarter[:, 0].tolist() == [[4095, 0], [0, 4095], [-4095, 0], [0, -4095]]
+
+
 def test_offsets_refuse_bad_arguments():
     L = _lib.load()
     b, out = _scan(4, 1), np.zeros((1, 4, 2), np.int16)
