@@ -4,6 +4,7 @@ from __future__ import annotations
 import os
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -20,6 +21,11 @@ SOURCES = ["gms_host.hip", "gms_slam_host.hip", "gms_fused_kernels.hip", "gms_qu
 # -ffp-contract=off: the reference (JVM) never fuses a multiply with an add; parity depends on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
          "-shared", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
+# Kernel-argument preload, for the device translation unit only: gfx950 delivers the head of the kernel-argument segment in user
+# SGPRs with the wave's launch (14 dwords beside the segment's pointer), so a kernel's first loads and branches do not wait for a
+# scalar load of their addresses.  A structure passed by value ends the preloaded run, which is why the step kernels take their
+# descriptors last (k_score_c's argument-order note).  The other units keep the compiler's default.
+UNIT_FLAGS = {"gms_fused_kernels.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 
 
 def hipcc() -> str:
@@ -43,6 +49,8 @@ def source_hash() -> str:
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(f, "rb").read())
+    for unit in sorted(UNIT_FLAGS):
+        h.update(b"\0unit\0" + unit.encode() + b"\0" + " ".join(UNIT_FLAGS[unit]).encode())
     extra = extra_flags()
     if extra:
         h.update(b"\0flags\0" + " ".join(extra).encode())
@@ -72,11 +80,24 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return LIB
     os.makedirs(LIBDIR, exist_ok=True)
     extra = extra_flags()
-    cmd = [hipcc()] + FLAGS + extra + [f'-DGMS_SOURCE_HASH="{want}"', "-I", os.path.join(ROOT, "include"), "-I", CSRC]
-    cmd += [os.path.join(CSRC, s) for s in SOURCES] + ["-o", LIB]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    # A unit with flags of its own cannot share a command line with the others, so the library is built in three steps: such units to
+    # objects one by one, the other units to objects in one command, then the link (hipcc takes a command line of objects alone as
+    # one: beside a source file it reads every input as HIP source).  The objects live in a temporary directory of this build alone
+    # and go with it; the library is linked there too and moved into place whole, so two builds at once never share a file.
+    common = [hipcc()] + [a for a in FLAGS if a != "-shared"] + extra
+    common += [f'-DGMS_SOURCE_HASH="{want}"', "-I", os.path.join(ROOT, "include"), "-I", CSRC]
+    cmds = [common + UNIT_FLAGS[s] + ["-c", os.path.join(CSRC, s)] for s in SOURCES if s in UNIT_FLAGS]
+    cmds.append(common + ["-c"] + [os.path.join(CSRC, s) for s in SOURCES if s not in UNIT_FLAGS])
+    objects = [os.path.splitext(s)[0] + ".o" for s in SOURCES]
+    # (the extra flags reach the link as well: one that matters there, such as -g or -fsanitize, is not dropped)
+    cmds.append([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-unused-command-line-argument"]
+                + extra + objects + ["-o", os.path.basename(LIB)])
+    with tempfile.TemporaryDirectory(prefix=".build-", dir=LIBDIR) as tmp:
+        for cmd in cmds:
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.check_call(cmd, cwd=tmp)
+        os.replace(os.path.join(tmp, os.path.basename(LIB)), LIB)
     print(f"libgridmapslam: built {want}" + (f" (extra flags: {' '.join(extra)})" if extra else ""), file=sys.stderr)
     return LIB
 

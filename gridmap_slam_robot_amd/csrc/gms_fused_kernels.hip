@@ -31,15 +31,17 @@
 template <bool LOGNORM>   // (the log-normalising form is a separate instantiation: the default kernel is exactly what it was -- as one kernel
                           // with a uniform branch its ray blocks ran 1.1 us longer, measured A/B on one box)
 __global__ void __launch_bounds__(256)
-k_norm_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox,
-               int32_t nw_max, uint32_t n_ray_blocks,
-               const double *__restrict__ partials, int64_t nblk_global, double *__restrict__ w, const float *__restrict__ pose,
-               int32_t n, int64_t offset, PackedParticle *__restrict__ packed, double *__restrict__ cum,
+k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ partials, int64_t nblk_global, int32_t B,
+               int32_t nw_max, uint32_t n_ray_blocks, uint32_t n_norm_blocks, uint32_t n_near_blocks, int32_t n,
+               double *__restrict__ w, const float *__restrict__ pose, int64_t offset, uint32_t *__restrict__ cnt,
+               int32_t *__restrict__ bbox, PackedParticle *__restrict__ packed, double *__restrict__ cum,
                double *__restrict__ chunk_tot, int64_t nchunks, double *__restrict__ p2, PfStatsDev *__restrict__ stats,
-               uint32_t n_norm_blocks, double *__restrict__ logd, uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend,
-               uint32_t n_near_blocks, const double *__restrict__ logw_lognorm, uint32_t *__restrict__ res_ticket,
-               double *__restrict__ res_pre) {
+               double *__restrict__ logd, uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend,
+               const double *__restrict__ logw_lognorm, uint32_t *__restrict__ res_ticket, double *__restrict__ res_pre, GridDev g) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // (argument order: the beams, the partial vector and the role boundaries of the workgroup ranges -- what the beam loads, the pose
+    // fold and the first branches read -- fill the preloaded first 56 bytes of the kernel-argument segment; the grid descriptor, a
+    // structure, comes last: see k_score_c)
     // workgroups: [far-field ray blocks | near-field ray blocks) = n_ray_blocks, then normalise, then the riding apply pass
     // logw_lognorm != nullptr: the partial vector is block-relative (gms_pf_set_log_normalize, block_partials)
     // res_ticket != nullptr: the last normalise workgroup folds Neff and scans the chunk offsets for k_lik_resample (resample_prefix_last),
@@ -86,10 +88,11 @@ k_norm_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_
 // The likelihood pass of a paired step adds the scan's counts on the fly, so `logData += ...` (GridMap.java:223)
 // is off the critical path: it runs here, beside the next scan's weight reduction, before that scan's ray cast.
 __global__ void __launch_bounds__(256)
-k_partials_apply(double *__restrict__ w, double *__restrict__ logw, const float *__restrict__ pose, int32_t n, int64_t offset,
-                 int64_t nblk_global, double *__restrict__ partials, const double *__restrict__ part, int32_t part_nseg,
-                 GridDev g, double *__restrict__ logd, uint32_t *__restrict__ cnt, const int32_t *__restrict__ bbox,
-                 int32_t *__restrict__ bbox_idle, PfStatsDev *__restrict__ lognorm_stats) {
+k_partials_apply(const double *__restrict__ part, const float *__restrict__ pose, PfStatsDev *__restrict__ lognorm_stats, int32_t n,
+                 int32_t part_nseg, int64_t offset, int64_t nblk_global, double *__restrict__ w, double *__restrict__ logw,
+                 double *__restrict__ partials, double *__restrict__ logd, uint32_t *__restrict__ cnt,
+                 const int32_t *__restrict__ bbox, int32_t *__restrict__ bbox_idle, GridDev g) {
+    // (argument order: k_partials', then the apply pass's, the grid descriptor last: kernel-argument preload, see k_score_c)
     if (blockIdx.x < (uint32_t)nblk_global)
         partials_body(w, logw, pose, n, offset, nblk_global, partials, part, part_nseg, blockIdx.x, blockIdx.y, lognorm_stats);
     else
@@ -99,11 +102,11 @@ k_partials_apply(double *__restrict__ w, double *__restrict__ logw, const float 
 // ---- sharded filters, one all-gather per scan (gms_slam_update_sharded_*) ---------------------------------------
 // B': this shard's block partials and the raw pack of its particles (the two all-gather payloads)  |  previous apply
 __global__ void __launch_bounds__(256)
-k_partials_pack_apply(double *__restrict__ w, double *__restrict__ logw, const float *__restrict__ pose, int32_t n, int64_t offset,
-                      int64_t nblk_global, double *__restrict__ partials, const double *__restrict__ part, int32_t part_nseg,
-                      PackedParticle *__restrict__ packed_local, uint32_t n_local_blocks,
-                      GridDev g, double *__restrict__ logd, uint32_t *__restrict__ cnt, const int32_t *__restrict__ bbox,
-                      int32_t *__restrict__ bbox_idle) {
+k_partials_pack_apply(const double *__restrict__ part, const float *__restrict__ pose, int32_t n, int32_t part_nseg,
+                      uint32_t n_local_blocks, int64_t offset, int64_t nblk_global, double *__restrict__ w, double *__restrict__ logw,
+                      double *__restrict__ partials, PackedParticle *__restrict__ packed_local, double *__restrict__ logd,
+                      uint32_t *__restrict__ cnt, const int32_t *__restrict__ bbox, int32_t *__restrict__ bbox_idle, GridDev g) {
+    // (argument order: k_partials' with the role boundary, then the apply pass's, the grid descriptor last: see k_score_c)
     if (blockIdx.x < n_local_blocks) {
         partials_body(w, logw, pose, n, offset, nblk_global, partials, part, part_nseg, (uint32_t)(offset / GMS_BLOCK) + blockIdx.x, 0);
         pack_raw_block(w, pose, n, blockIdx.x, packed_local);         // each thread re-reads the weight it stored itself
@@ -115,14 +118,15 @@ k_partials_pack_apply(double *__restrict__ w, double *__restrict__ logw, const f
 // A': ray cast at the weighted pose  |  normalise this shard's weights + statistics  |  level 0 of the cumulative
 // normalised weights of the gathered raw population.  All three only need the gathered partial vector.
 __global__ void __launch_bounds__(256)
-k_raycast_norm_chunks(GridDev g, const gms_beam *__restrict__ beams, int32_t B, uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox,
-                      int32_t nw_max, uint32_t n_ray_blocks, uint32_t n_norm_blocks,
-                      const double *__restrict__ partials, int64_t nblk_global, double *__restrict__ w, const float *__restrict__ pose,
-                      int32_t n, int64_t offset, const PackedParticle *__restrict__ glob_raw, int64_t n_global, int64_t nchunks,
-                      double *__restrict__ cum, double *__restrict__ chunk_tot, double *__restrict__ p2,
-                      PfStatsDev *__restrict__ stats, uint32_t n_chunk_blocks, double *__restrict__ logd,
-                      uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend, uint32_t n_near_blocks) {
+k_raycast_norm_chunks(const gms_beam *__restrict__ beams, const double *__restrict__ partials, int64_t nblk_global, int32_t B,
+                      int32_t nw_max, uint32_t n_ray_blocks, uint32_t n_norm_blocks, uint32_t n_chunk_blocks, uint32_t n_near_blocks,
+                      int32_t n, double *__restrict__ w, const float *__restrict__ pose, int64_t offset,
+                      const PackedParticle *__restrict__ glob_raw, int64_t n_global, int64_t nchunks, double *__restrict__ cum,
+                      double *__restrict__ chunk_tot, double *__restrict__ p2, PfStatsDev *__restrict__ stats,
+                      uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox, double *__restrict__ logd,
+                      uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend, GridDev g) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // (argument order as k_norm_raycast's, with the chunk workgroups' role boundary beside the others: see k_score_c)
     if (blockIdx.x >= n_ray_blocks + n_norm_blocks + n_chunk_blocks) {           // the previous scan's deferred apply pass (see k_norm_raycast)
         const uint32_t first = n_ray_blocks + n_norm_blocks + n_chunk_blocks;
         apply_body(g, logd, cnt_pend, bbox_pend, nullptr, blockIdx.x - first, 0, gridDim.x - first);
@@ -150,16 +154,19 @@ k_raycast_norm_chunks(GridDev g, const gms_beam *__restrict__ beams, int32_t B, 
 // ---- C: likelihood rebuild (dirty tiles)  |  resample ---------------------------------------------------------
 template <int KH, int SPLIT>
 __global__ void __launch_bounds__(256)
-k_lik_resample(GridDev g, const double *__restrict__ logd, double *__restrict__ lik, double *__restrict__ fac, int64_t fac_stride,
-               const double *__restrict__ taps_g, const int32_t *__restrict__ bbox, int32_t tiles_x, int32_t tiles_y,
-               const uint32_t *__restrict__ cnt_pending, uint8_t *__restrict__ tile_state, uint32_t n_res_blocks,
-               const PackedParticle *__restrict__ glob, int64_t n_global, int64_t nchunks, const double *__restrict__ cum,
-               const double *__restrict__ chunk_off, const double *__restrict__ r01_maps, double r01, double fraction,
-               int32_t n, int64_t offset,
+k_lik_resample(const double *__restrict__ res_pre, const double *__restrict__ chunk_off, int64_t nchunks,
+               const int32_t *__restrict__ bbox, uint8_t *__restrict__ tile_state, int32_t *__restrict__ bbox_clear,
+               uint32_t n_res_blocks, int32_t lik_mode, const uint32_t *__restrict__ cnt_pending, const double *__restrict__ logd,
+               int32_t tiles_x, int32_t tiles_y, double *__restrict__ lik, double *__restrict__ fac, int64_t fac_stride,
+               const double *__restrict__ taps_g, const PackedParticle *__restrict__ glob, int64_t n_global,
+               const double *__restrict__ cum, const double *__restrict__ r01_maps, double r01, double fraction,
+               int32_t n, int32_t raw_weights, int64_t offset,
                float *__restrict__ pose2, float *__restrict__ cs2, double *__restrict__ w2, int32_t *__restrict__ idx_out,
-               const double *__restrict__ p2, int64_t nblk_global, PfStatsDev *__restrict__ stats, int32_t raw_weights,
-               int32_t *__restrict__ bbox_clear, int32_t lik_mode, const double *__restrict__ res_pre) {
+               const double *__restrict__ p2, int64_t nblk_global, PfStatsDev *__restrict__ stats, GridDev g) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // (argument order: the folded chunk offsets and Neff, the dirty box, the tile states and the role boundary -- what the two halves'
+    // first loads and branches read -- fill the preloaded first 56 bytes of the kernel-argument segment; the grid descriptor, a
+    // structure, comes last: see k_score_c)
     // the box half the next ray cast will raise: cleared here because that ray cast may share its launch with this scan's
     // deferred apply pass (k_raycast_apply), which otherwise does the clearing
     GMS_STAMP(GMS_STAMP_ROW(3, blockIdx.x), 0);
@@ -221,12 +228,13 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
     do {                                                                                                                              \
         if (smem > 48 * 1024)                                                                                                         \
             hipFuncSetAttribute(reinterpret_cast<const void *>(&k_norm_raycast<LN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL(k_norm_raycast<LN>, dim3(n_ray + n_norm + n_apply), dim3(256), smem, m->stream, m->gd, d_beams, B, m->d_cnt, bb, \
-                           rc_nw_max(m), n_ray, d_partials, nblk_global_of(pf), pf->d_w, pf->d_pose, pf->n, pf->offset, d_packed_local, \
+        hipLaunchKernelGGL(k_norm_raycast<LN>, dim3(n_ray + n_norm + n_apply), dim3(256), smem, m->stream, d_beams, d_partials,       \
+                           nblk_global_of(pf), B, rc_nw_max(m), n_ray, n_norm, n_near, pf->n, pf->d_w, pf->d_pose, pf->offset,         \
+                           m->d_cnt, bb, d_packed_local,                                                                               \
                            own ? pf->d_cum : (double *)nullptr, own ? pf->d_chunk_tot : (double *)nullptr, nchunks_of(pf),          \
-                           own ? pf->d_p2 : (double *)nullptr, pf->d_stats, n_norm, m->d_log, m->d_cnt_pend, pend, n_near,          \
+                           own ? pf->d_p2 : (double *)nullptr, pf->d_stats, m->d_log, m->d_cnt_pend, pend,                          \
                            LN ? (const double *)pf->d_logw : (const double *)nullptr, own ? pf->d_res_ticket : (uint32_t *)nullptr,       \
-                           pf->d_res_pre);                                                                                              \
+                           pf->d_res_pre, m->gd);                                                                                       \
     } while (0)
     if (lognorm) NR_LAUNCH(true); else NR_LAUNCH(false);
 #undef NR_LAUNCH
@@ -245,10 +253,10 @@ void gms_launch_partials_apply(gms_pf *pf, double *d_partials, bool apply_rides_
     const uint32_t n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS);
     int32_t *cur = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4, *idle = m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4;
     PfStatsDev *lognorm_stats = gms_pf_lognorm_now(pf) ? pf->d_stats : (PfStatsDev *)nullptr;
-    hipLaunchKernelGGL(k_partials_apply, dim3((uint32_t)nblk + n_apply, pf->n_maps), dim3(256), 0, m->stream, pf->d_w, pf->d_logw,
-                       pf->d_pose, pf->n, pf->offset, nblk, d_partials,
-                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->pending_nseg, m->gd, m->d_log,
-                       m->d_cnt_pend, cur, idle, lognorm_stats);
+    hipLaunchKernelGGL(k_partials_apply, dim3((uint32_t)nblk + n_apply, pf->n_maps), dim3(256), 0, m->stream,
+                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose, lognorm_stats, pf->n,
+                       pf->pending_nseg, pf->offset, nblk, pf->d_w, pf->d_logw, d_partials, m->d_log, m->d_cnt_pend,
+                       cur, idle, m->gd);
     pf_weights_combined(pf);
     gms_apply_done(m);
 }
@@ -282,11 +290,13 @@ void gms_launch_lik_resample(gms_pf *pf, double fraction) {
         if (smem > 48 * 1024)                                                                                             \
             hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lik_resample<KH, SP>),                                 \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                                   \
-        hipLaunchKernelGGL((k_lik_resample<KH, SP>), dim3((uint32_t)blocks + n_res, pf->n_maps), dim3(256), smem, m->stream, m->gd, m->d_log, \
-                           m->d_lik, m->d_fac, m->fac_stride, m->d_taps, bb, tiles_x, tiles_y, m->d_cnt, m->d_tile_state, n_res, pf->d_global, \
-                           pf->n_global, nch, pf->d_cum, pf->d_chunk_tot, r01_maps, pf->r01_scalar, fraction, pf->n, pf->offset, \
-                           pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, pf->d_p2, nblk_global_of(pf), pf->d_stats,       \
-                           pf->global_raw, m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4, lik_mode, pre);        \
+        hipLaunchKernelGGL((k_lik_resample<KH, SP>), dim3((uint32_t)blocks + n_res, pf->n_maps), dim3(256), smem, m->stream, pre,     \
+                           (const double *)pf->d_chunk_tot, nch, bb, m->d_tile_state,                                     \
+                           m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4, n_res, lik_mode, (const uint32_t *)m->d_cnt, \
+                           (const double *)m->d_log, tiles_x, tiles_y, m->d_lik, m->d_fac, m->fac_stride, (const double *)m->d_taps, \
+                           (const PackedParticle *)pf->d_global, pf->n_global, (const double *)pf->d_cum, r01_maps, pf->r01_scalar, \
+                           fraction, pf->n, (int32_t)pf->global_raw, pf->offset,                                          \
+                           pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, (const double *)pf->d_p2, nblk_global_of(pf), pf->d_stats, m->gd); \
     } while (0)
     if (k == 3) { if (split) LR_LAUNCH(3, 2); else LR_LAUNCH(3, 1); }
     else if (k == 5) { if (split) LR_LAUNCH(5, 2); else LR_LAUNCH(5, 1); }
@@ -308,10 +318,10 @@ void gms_launch_partials_pack_apply(gms_pf *pf, bool apply_rides_later) {
         n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS);
     }
     int32_t *cur = m->d_bbox + (size_t)m->bbox_cur * 4, *idle = m->d_bbox + (size_t)(1 - m->bbox_cur) * 4;
-    hipLaunchKernelGGL(k_partials_pack_apply, dim3(n_local + n_apply), dim3(256), 0, m->stream, pf->d_w, pf->d_logw, pf->d_pose,
-                       pf->n, pf->offset, nblk_global_of(pf), pf->d_partials,
-                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->pending_nseg,
-                       pf->d_global_own + pf->offset, n_local, m->gd, m->d_log, m->d_cnt_pend, cur, idle);
+    hipLaunchKernelGGL(k_partials_pack_apply, dim3(n_local + n_apply), dim3(256), 0, m->stream,
+                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose, pf->n, pf->pending_nseg,
+                       n_local, pf->offset, nblk_global_of(pf), pf->d_w, pf->d_logw, pf->d_partials,
+                       pf->d_global_own + pf->offset, m->d_log, m->d_cnt_pend, cur, idle, m->gd);
     pf_raw_packed(pf);
     if (n_apply) gms_apply_done(m);
 }
@@ -335,10 +345,11 @@ void gms_launch_raycast_norm_chunks(gms_pf *pf, const gms_beam *d_beams, int32_t
     if (smem > 48 * 1024)
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast_norm_chunks), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)smem);
-    hipLaunchKernelGGL(k_raycast_norm_chunks, dim3(n_ray + n_norm + n_chunk + n_apply), dim3(256), smem, m->stream, m->gd, d_beams, B,
-                       m->d_cnt, bb, rc_nw_max(m), n_ray, n_norm, pf->d_partials, nblk_global_of(pf), pf->d_w, pf->d_pose, pf->n,
-                       pf->offset, pf->d_global_own, pf->n_global, nchunks_of(pf), pf->d_cum, pf->d_chunk_tot, pf->d_p2, pf->d_stats,
-                       n_chunk, m->d_log, m->d_cnt_pend, pend, n_near);
+    hipLaunchKernelGGL(k_raycast_norm_chunks, dim3(n_ray + n_norm + n_chunk + n_apply), dim3(256), smem, m->stream, d_beams,
+                       pf->d_partials, nblk_global_of(pf), B, rc_nw_max(m), n_ray, n_norm, n_chunk, n_near, pf->n,
+                       pf->d_w, pf->d_pose, pf->offset, pf->d_global_own, pf->n_global, nchunks_of(pf),
+                       pf->d_cum, pf->d_chunk_tot, pf->d_p2, pf->d_stats, m->d_cnt, bb, m->d_log, m->d_cnt_pend,
+                       pend, m->gd);
     if (n_apply) gms_apply_done(m);
     pf_normalized_gathered(pf);                       // (sharded: the resample workgroups fold Neff and scan the offsets themselves)
 }

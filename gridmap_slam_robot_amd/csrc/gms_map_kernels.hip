@@ -503,11 +503,13 @@ static inline uint32_t rc_near_blocks(const gms_map *m, int32_t B) {
 
 template <bool TRACE, int RC_RAYS>
 __global__ void __launch_bounds__(RC_RAYS * 64)
-k_raycast(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t beam_stride,
-          const float *__restrict__ poses, int32_t pose_stride, const RayIn *__restrict__ single,
+k_raycast(const gms_beam *__restrict__ beams, const float *__restrict__ poses, const RayIn *__restrict__ single, int32_t B,
+          int32_t beam_stride, int32_t pose_stride, int32_t nw_max, uint32_t n_near_blocks, int32_t cap,
           uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox, int32_t *__restrict__ t_cells,
-          uint8_t *__restrict__ t_cls, int32_t cap, int32_t *__restrict__ t_counts, int32_t nw_max, uint32_t n_near_blocks) {
+          uint8_t *__restrict__ t_cls, int32_t *__restrict__ t_counts, GridDev g) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // (argument order: the beams, the poses and what the prologue's addresses and branches are formed from lead, the grid
+    // descriptor comes last: kernel-argument preload, see k_score_c)
     // grid.x = ray blocks + near-field blocks (the latter only for the count form with four rays per workgroup)
     const bool near = !TRACE && RC_RAYS == 4 && n_near_blocks && blockIdx.x >= gridDim.x - n_near_blocks;
     const RayPre pre = near ? raycast_near_prologue(beams, B, beam_stride, blockIdx.x - (gridDim.x - n_near_blocks), blockIdx.y, smem)
@@ -1157,11 +1159,13 @@ likelihood_body(const GridDev &g, const double *__restrict__ logd, double *__res
 
 template <int KH, bool PENDING, int SPLIT = 1>      // PENDING = false: no count grid is read (the code for it is not generated: 1.3 us of a 21 us full rebuild)
 __global__ void __launch_bounds__(256) GMS_LIK_WAVES
-k_likelihood(GridDev g, const double *__restrict__ logd, double *__restrict__ lik, double *__restrict__ fac,
-             int64_t fac_stride, const double *__restrict__ taps_g, const int32_t *__restrict__ bbox, int32_t dirty_only,
-             int32_t tiles_x, int32_t tiles_y, uint8_t *__restrict__ tile_state, const uint32_t *__restrict__ cnt_pending,
-             int32_t *__restrict__ bbox_clear, int32_t mode) {
+k_likelihood(const int32_t *__restrict__ bbox, uint8_t *__restrict__ tile_state, int32_t *__restrict__ bbox_clear,
+             const uint32_t *__restrict__ cnt_pending, int32_t dirty_only, int32_t mode, int32_t tiles_x, int32_t tiles_y,
+             const double *__restrict__ logd, double *__restrict__ lik, double *__restrict__ fac, int64_t fac_stride,
+             const double *__restrict__ taps_g, GridDev g) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // (argument order: the dirty box, the tile states and the modes the tile walk branches on lead, the grid descriptor comes
+    // last, as in k_lik_resample: kernel-argument preload, see k_score_c)
     // bbox_clear: the box half the NEXT ray cast will raise (it shares its launch with this scan's deferred apply pass,
     // which therefore cannot clear it: k_raycast_apply); nobody reads it during this launch
     if (bbox_clear && blockIdx.x == 0 && threadIdx.x < 4) bbox_clear[4 * blockIdx.y + threadIdx.x] = 0;
@@ -1174,10 +1178,12 @@ k_likelihood(GridDev g, const double *__restrict__ logd, double *__restrict__ li
 // scan's `logData[c] += ...` (GridMap.java:223, from the other count grid); the likelihood pass that follows adds this
 // scan's counts on the fly, as it does in the paired scan step.  grid.x = ray blocks + apply blocks, one map.
 __global__ void __launch_bounds__(256)
-k_raycast_apply(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t beam_stride, const float *__restrict__ poses,
-                int32_t pose_stride, uint32_t *__restrict__ cnt, int32_t *__restrict__ bbox_next, int32_t nw_max, uint32_t n_ray_blocks,
-                uint32_t n_near_blocks, double *__restrict__ logd, uint32_t *__restrict__ cnt_pend, const int32_t *__restrict__ bbox_pend) {
+k_raycast_apply(const gms_beam *__restrict__ beams, const float *__restrict__ poses, int32_t B, int32_t beam_stride,
+                int32_t pose_stride, int32_t nw_max, uint32_t n_ray_blocks, uint32_t n_near_blocks, uint32_t *__restrict__ cnt,
+                int32_t *__restrict__ bbox_next, double *__restrict__ logd, uint32_t *__restrict__ cnt_pend,
+                const int32_t *__restrict__ bbox_pend, GridDev g) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // (argument order as k_raycast's: kernel-argument preload, see k_score_c)
     if (blockIdx.x >= n_ray_blocks + n_near_blocks) {
         apply_body(g, logd, cnt_pend, bbox_pend, nullptr, blockIdx.x - n_ray_blocks - n_near_blocks, 0, gridDim.x - n_ray_blocks - n_near_blocks);
         return;
@@ -1407,8 +1413,8 @@ static void rc_launch(gms_map *m, dim3 grid, const gms_beam *d_beams, int32_t B,
     if (smem > 48 * 1024)
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast<TRACE, RAYS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)smem);
-    hipLaunchKernelGGL((k_raycast<TRACE, RAYS>), grid, dim3(RAYS * 64), smem, m->stream, m->gd, d_beams, B, beam_stride, d_poses,
-                       pose_stride, single, cnt, bbox, t_cells, t_cls, cap, t_counts, rc_nw_max(m), n_near);
+    hipLaunchKernelGGL((k_raycast<TRACE, RAYS>), grid, dim3(RAYS * 64), smem, m->stream, d_beams, d_poses, single, B,
+                       beam_stride, pose_stride, rc_nw_max(m), n_near, cap, cnt, bbox, t_cells, t_cls, t_counts, m->gd);
 }
 
 // batched ray casts of more than raycast_tile_min rays in all go through LDS tiles (k_raycast_tile)
@@ -1499,8 +1505,8 @@ void gms_launch_raycast_apply(gms_map *m, const gms_beam *d_beams, int32_t B, in
     const size_t smem = rc_smem(m, 4, n_near);
     if (smem > 48 * 1024)
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast_apply), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k_raycast_apply, dim3(n_ray + n_near + n_apply), dim3(256), smem, m->stream, m->gd, d_beams, B, beam_stride, d_poses,
-                       pose_stride, m->d_cnt, next, rc_nw_max(m), n_ray, n_near, m->d_log, m->d_cnt_pend, pend);
+    hipLaunchKernelGGL(k_raycast_apply, dim3(n_ray + n_near + n_apply), dim3(256), smem, m->stream, d_beams, d_poses, B, beam_stride,
+                       pose_stride, rc_nw_max(m), n_ray, n_near, m->d_cnt, next, m->d_log, m->d_cnt_pend, pend, m->gd);
     gms_apply_done(m);                      // the box of the scan just cast is the current half now
 }
 void gms_flush_apply(gms_map *m) {
@@ -1598,8 +1604,9 @@ void gms_launch_likelihood(gms_map *m, int32_t dirty_only, bool counts_pending, 
         if (smem > 48 * 1024)                                                                                 \
             hipFuncSetAttribute(reinterpret_cast<const void *>(&k_likelihood<KH, PEND, SP>),                 \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                       \
-        hipLaunchKernelGGL((k_likelihood<KH, PEND, SP>), grid, dim3(256), smem, m->stream, m->gd, m->d_log, m->d_lik, \
-                           m->d_fac, m->fac_stride, m->d_taps, bb, dirty_only, tiles_x, tiles_y, tstate, pend, bb_clear, mode);                         \
+        hipLaunchKernelGGL((k_likelihood<KH, PEND, SP>), grid, dim3(256), smem, m->stream, bb, tstate, bb_clear, pend,     \
+                           dirty_only, mode, tiles_x, tiles_y, m->d_log, m->d_lik, m->d_fac, m->fac_stride,   \
+                           m->d_taps, m->gd);                                                                 \
     } while (0)
     if (k == 3) LK_LAUNCH(3);
     else if (k == 5) LK_LAUNCH(5);

@@ -286,11 +286,16 @@ k_order(GridDev g, const float *__restrict__ pose_src, const float *__restrict__
 // neighbouring lanes share lines (C5: 1 / 2 / 3 / 4 -> 240 / 233 / 223 / 237 us; 3 divides the 45-beam segment: no padded batch).
 template <int U>
 __global__ void __launch_bounds__(1024)
-k_score_c(GridDev g, const double *__restrict__ fac_all, int64_t fac_stride, const gms_beam *__restrict__ beams,
-          int32_t B, int32_t beam_stride, const float *__restrict__ pose, const float *__restrict__ cs, int32_t n,
-          int32_t nseg, double *__restrict__ part, double *__restrict__ w, double *__restrict__ logw,
-          const float *__restrict__ pose_src, float *__restrict__ pose_dst, float *__restrict__ cs_dst,
-          const float4 *__restrict__ ord, const int32_t *__restrict__ perm, MotionArgs mo, int64_t offset, int32_t spread) {
+k_score_c(const float *__restrict__ pose_src, const gms_beam *__restrict__ beams, const float4 *__restrict__ ord,
+          const int32_t *__restrict__ perm, int32_t B, int32_t beam_stride, int32_t n, int32_t nseg, int32_t spread,
+          const float *__restrict__ pose, const float *__restrict__ cs, const double *__restrict__ fac_all, int64_t fac_stride,
+          int64_t offset, double *__restrict__ part, double *__restrict__ w, double *__restrict__ logw,
+          float *__restrict__ pose_dst, float *__restrict__ cs_dst, MotionArgs mo, GridDev g) {
+    // Argument order: what the workgroup map, the beam compaction and the pose load read -- the first memory instructions and the
+    // branches in front of them -- fills the first 52 bytes of the kernel-argument segment (pose_src .. spread: 13 dwords), which
+    // arrive in SGPRs with the wave's launch (kernel-argument preload, build.py); the structures cannot be preloaded and end the
+    // preloaded run, so they come last.  pose and cs lie at byte 56 and beyond: a launch that scores the resident poses (pose_src ==
+    // nullptr and no ord) still waits for a scalar load before its pose load; the scan step's poses enter through pose_src.
     __shared__ double2 s_beam[128 + U];        // this segment's beams with wasHit, in order
     __shared__ int32_t s_nb;
     // Workgroup -> (beam segment, particle group), XCD-aware: consecutive workgroup ids go round-robin over the 8 XCDs
@@ -875,9 +880,10 @@ partials_body(double *__restrict__ w, double *__restrict__ logw, const float *__
 }
 
 __global__ void __launch_bounds__(256)
-k_partials(double *__restrict__ w, double *__restrict__ logw, const float *__restrict__ pose, int32_t n,
-           int64_t offset, int64_t nblk_global, double *__restrict__ partials, const double *__restrict__ part,
-           int32_t part_nseg, PfStatsDev *__restrict__ lognorm_stats) {
+k_partials(const double *__restrict__ part, const float *__restrict__ pose, PfStatsDev *__restrict__ lognorm_stats, int32_t n,
+           int32_t part_nseg, int64_t offset, int64_t nblk_global, double *__restrict__ w, double *__restrict__ logw,
+           double *__restrict__ partials) {
+    // (argument order: the segment products, the poses and what their addresses are formed from lead: see k_score_c)
     GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 0);
     partials_body(w, logw, pose, n, offset, nblk_global, partials, part, part_nseg, blockIdx.x, blockIdx.y, lognorm_stats);
     GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 1);
@@ -1690,14 +1696,14 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
     int32_t spread = nseg * groups >= 2 * (int64_t)m->n_cus ? 1 : 0;
     if (pf->score_spread >= 0) spread = pf->score_spread;
     if (ordered)
-        hipLaunchKernelGGL(k_score_c<3>, dim3((unsigned)(nseg * groups), 1, pf->n_maps), dim3(threads), 0, m->stream, m->gd,
-                           m->d_fac, m->fac_stride, d_beams, B, beam_stride, pf->d_pose, pf->d_cs, pf->n, (int32_t)nseg,
-                           pf->d_part, pf->d_w, pf->d_logw, d_pose_src, pose_dst, cs_dst, pf->d_ord, pf->d_perm, mo, pf->offset, 0);
+        hipLaunchKernelGGL(k_score_c<3>, dim3((unsigned)(nseg * groups), 1, pf->n_maps), dim3(threads), 0, m->stream, d_pose_src,
+                           d_beams, pf->d_ord, pf->d_perm, B, beam_stride, pf->n, (int32_t)nseg, 0, pf->d_pose, pf->d_cs,
+                           m->d_fac, m->fac_stride, pf->offset, pf->d_part, pf->d_w, pf->d_logw, pose_dst, cs_dst, mo, m->gd);
     else
-        hipLaunchKernelGGL(k_score_c<1>, dim3((unsigned)(nseg * groups), 1, pf->n_maps), dim3(threads), 0, m->stream, m->gd,
-                           m->d_fac, m->fac_stride, d_beams, B, beam_stride, pf->d_pose, pf->d_cs, pf->n, (int32_t)nseg,
-                           pf->d_part, pf->d_w, pf->d_logw, d_pose_src, pose_dst, cs_dst, (const float4 *)nullptr,
-                           (const int32_t *)nullptr, mo, pf->offset, spread);
+        hipLaunchKernelGGL(k_score_c<1>, dim3((unsigned)(nseg * groups), 1, pf->n_maps), dim3(threads), 0, m->stream, d_pose_src,
+                           d_beams, (const float4 *)nullptr, (const int32_t *)nullptr, B, beam_stride, pf->n, (int32_t)nseg, spread,
+                           pf->d_pose, pf->d_cs, m->d_fac, m->fac_stride, pf->offset, pf->d_part, pf->d_w, pf->d_logw, pose_dst,
+                           cs_dst, mo, m->gd);
     if (motion) { std::swap(pf->d_pose, pf->d_pose2); std::swap(pf->d_cs, pf->d_cs2); }
     pf_scored(pf, nseg);                                          // segment products: combined by the next consumer of the weights
 }
@@ -1720,10 +1726,10 @@ void gms_launch_pf_partials(gms_pf *pf, double *d_partials) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_REDUCE);
     const int64_t nblk = nblk_global_of(pf);
-    hipLaunchKernelGGL(k_partials, dim3((unsigned)nblk, pf->n_maps), dim3(256), 0, m->stream, pf->d_w, pf->d_logw,
-                       pf->d_pose, pf->n, pf->offset, nblk, d_partials,
-                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->pending_nseg,
-                       gms_pf_lognorm_now(pf) ? pf->d_stats : (PfStatsDev *)nullptr);
+    hipLaunchKernelGGL(k_partials, dim3((unsigned)nblk, pf->n_maps), dim3(256), 0, m->stream,
+                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose,
+                       gms_pf_lognorm_now(pf) ? pf->d_stats : (PfStatsDev *)nullptr, pf->n, pf->pending_nseg, pf->offset, nblk,
+                       pf->d_w, pf->d_logw, d_partials);
     pf_weights_combined(pf);                                          // k_partials stored the combined weights
 }
 
