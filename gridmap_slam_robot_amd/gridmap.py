@@ -70,23 +70,54 @@ class Observation:
         return self.getNumberOfMeasurements()
 
 
-def _view_args(W: int, H: int, rect, decimate: int, likelihood: bool, packed: bool, filter: int = 0):
-    """(gms_view, output shape, numpy dtype) of a view of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
-    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
-    v = _lib.GmsView(x0, y0, w, h, int(decimate), _lib.GMS_VIEW_LIKELIHOOD if likelihood else _lib.GMS_VIEW_LOG,
-                     _lib.GMS_VIEW_PACKED32 if packed else _lib.GMS_VIEW_GREY8, int(filter))
+def _device_ptr(who: str, what: str, t, nbytes: int = 0, itemsize: Optional[int] = None, multiple: int = 1, contiguous: bool = True,
+                optional: bool = False):
+    """The device address (a c_void_p) of a caller's torch tensor t, argument `what` of the query `who`: on the device, contiguous
+    unless contiguous=False, of at least nbytes bytes, its elements of itemsize bytes (None: any) and their number a multiple of
+    `multiple`.  optional: None stands for an omitted output and passes through.  ValueError otherwise: the one check of them all."""
+    if t is None and optional:
+        return None
+    if not getattr(t, "is_cuda", False) or (contiguous and not t.is_contiguous()):
+        raise ValueError(f"{who}: {what} must be a {'contiguous ' if contiguous else ''}torch tensor on the device")
+    if (itemsize is not None and t.element_size() != itemsize) or t.numel() % multiple:
+        raise ValueError(f"{who}: {what} must hold {itemsize or t.element_size()}-byte elements, a multiple of {multiple} of them")
+    if t.numel() * t.element_size() < nbytes:
+        raise ValueError(f"{who}: {what} holds {t.numel() * t.element_size()} bytes, {nbytes} are needed")
+    return C.c_void_p(int(t.data_ptr()))
+
+
+def _shown_ptr(who: str, shown_out):
+    """the device address of the int32 word that receives the index of the particle shown (None: not wanted)"""
+    return _device_ptr(who, "shown_out", shown_out, 4, itemsize=4, contiguous=False, optional=True)
+
+
+def _which(who: str, which, allow_all: bool = False) -> int:
+    """the particle a per-particle query shows: an index passes through, "strongest" is GMS_VIEW_STRONGEST (picked on the device) and,
+    where the query allows it, "all" GMS_CAST_ALL"""
+    if not isinstance(which, str):
+        return int(which)
+    if which == "strongest":
+        return _lib.GMS_VIEW_STRONGEST
+    if allow_all and which == "all":
+        return _lib.GMS_CAST_ALL
+    raise ValueError(f'{who}: which must be a particle index or "strongest"' + (' or "all"' if allow_all else ""))
+
+
+def _rect(W: int, H: int, rect):
+    """rect = (x0, y0, w, h) in cells of a W x H map; None: the whole map"""
+    return (0, 0, W, H) if rect is None else tuple(int(c) for c in rect)
+
+
+def _obstacles(not_free: bool) -> int:
+    """the obstacle-mode word: every cell that is not known free, or the occupied ones alone"""
+    return _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED
+
+
+def _sized(size_fn, request):
+    """(request, output shape (oh, ow), bytes) of a field request, as the library's gms_*_size sizes it"""
     ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    check(load().gms_view_size(C.byref(v), C.byref(ow), C.byref(oh), C.byref(nbytes)))
-    return v, (oh.value, ow.value), np.dtype(np.uint32 if packed else np.uint8), nbytes.value
-
-
-def _view_device_out(out, nbytes: int) -> int:
-    """the device address of a caller's torch tensor that is to receive a view of nbytes bytes"""
-    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
-        raise ValueError("view: out must be a contiguous torch tensor on the device")
-    if out.numel() * out.element_size() < nbytes:
-        raise ValueError(f"view: out holds {out.numel() * out.element_size()} bytes, the view needs {nbytes}")
-    return int(out.data_ptr())
+    check(size_fn(C.byref(request), C.byref(ow), C.byref(oh), C.byref(nbytes)))
+    return request, (oh.value, ow.value), nbytes.value
 
 
 def world_rect_to_cells(grid_map, center, size):
@@ -145,24 +176,6 @@ def scan_residual(measured_beams, cast, resolution: float, hit_tolerance: float)
     out[~hit & ~pred] = RESIDUAL_AGREE
     out[~hit & pred] = RESIDUAL_MEASURED_LONGER
     return out
-
-
-def _cast_device_out(out, n: int) -> int:
-    """the device address of a caller's torch tensor that is to receive n gms_cast_hit records"""
-    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
-        raise ValueError("cast: out must be a contiguous torch tensor on the device")
-    if out.numel() * out.element_size() < 16 * n:
-        raise ValueError(f"cast: out holds {out.numel() * out.element_size()} bytes, the records need {16 * n}")
-    return int(out.data_ptr())
-
-
-def _gain_device_out(out, n: int) -> int:
-    """the device address of a caller's torch tensor that is to receive n gms_gain_rec records"""
-    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
-        raise ValueError("gain: out must be a contiguous torch tensor on the device")
-    if out.numel() * out.element_size() < _lib.GAIN_DTYPE.itemsize * n:
-        raise ValueError(f"gain: out holds {out.numel() * out.element_size()} bytes, the records need {_lib.GAIN_DTYPE.itemsize * n}")
-    return int(out.data_ptr())
 
 
 def probe_fan(n: int, range_m: float, fov: float = 2 * math.pi) -> np.ndarray:
@@ -233,10 +246,8 @@ def locate_peaks(records, radius: int, k_radius: Optional[int] = None, n_theta: 
 
 def _locate_args(W: int, H: int, rect, offsets_shape, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, filter: int = 0):
     """the gms_locate of a request on a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map; offsets_shape = (n_theta, B)"""
-    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
-    lc = _lib.GmsLocate(x0, y0, w, h, int(offsets_shape[0]), int(tol), _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED,
-                        int(min_score), int(cap), int(bool(free_only)), int(filter), 0)
-    return lc
+    return _lib.GmsLocate(*_rect(W, H, rect), int(offsets_shape[0]), int(tol), _obstacles(not_free), int(min_score), int(cap), int(bool(free_only)),
+                          int(filter), 0)
 
 
 def _locate_table(offsets) -> np.ndarray:
@@ -245,17 +256,6 @@ def _locate_table(offsets) -> np.ndarray:
     if a.ndim != 3 or a.shape[2] != 2:
         raise ValueError(f"locate: offsets must be [n_theta][B][2] (dx, dy) cells, not {a.shape}")
     return a
-
-
-def _locate_device(out, n_out, cap: int):
-    """the device addresses of a caller's torch tensors that are to receive cap gms_locate_rec records and their number"""
-    if not (getattr(out, "is_cuda", False) and out.is_contiguous()):
-        raise ValueError("locate: out must be a contiguous torch tensor on the device")
-    if out.numel() * out.element_size() < _lib.LOCATE_DTYPE.itemsize * cap:
-        raise ValueError(f"locate: out holds {out.numel() * out.element_size()} bytes, the records need {_lib.LOCATE_DTYPE.itemsize * cap}")
-    if not (getattr(n_out, "is_cuda", False) and n_out.element_size() == 4 and n_out.numel() >= 1):
-        raise ValueError("locate: n_out must be an int32 torch tensor on the device")
-    return C.c_void_p(int(out.data_ptr())), C.c_void_p(int(n_out.data_ptr()))
 
 
 def scatter_slots(n: int, fraction: float):
@@ -303,15 +303,6 @@ def beam_model_factors(resolution: float, behind: int, ahead: int, sigma: float,
     return f
 
 
-def _clearance_args(W: int, H: int, rect, max_radius: int, not_free: bool, filter: int = 0):
-    """(gms_clearance, output shape, bytes) of a clearance field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
-    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
-    c = _lib.GmsClearance(x0, y0, w, h, int(max_radius), _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED, int(filter))
-    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    check(load().gms_clearance_size(C.byref(c), C.byref(ow), C.byref(oh), C.byref(nbytes)))
-    return c, (oh.value, ow.value), nbytes.value
-
-
 def clearance_metres(d2, resolution: float) -> np.ndarray:
     """Clearance values (GridMap.clearance / clearance_poses: squared cell distances as uint16) as metres, float64: sqrt(d2) *
     resolution; GMS_CLEAR_FAR (beyond the radius, or no obstacle at all) becomes inf, GMS_CLEAR_OUTSIDE (a pose off the map) nan."""
@@ -320,15 +311,6 @@ def clearance_metres(d2, resolution: float) -> np.ndarray:
     out[a == _lib.GMS_CLEAR_FAR] = np.inf
     out[a == _lib.GMS_CLEAR_OUTSIDE] = np.nan
     return out
-
-
-def _reach_args(W: int, H: int, rect, max_cost: int, inflate: int, not_free: bool, filter: int = 0):
-    """(gms_reach, output shape, bytes) of a cost-to-go field of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
-    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
-    r = _lib.GmsReach(x0, y0, w, h, int(max_cost), int(inflate), _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED, int(filter))
-    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    check(load().gms_reach_size(C.byref(r), C.byref(ow), C.byref(oh), C.byref(nbytes)))
-    return r, (oh.value, ow.value), nbytes.value
 
 
 def _reach_seeds(seeds) -> np.ndarray:
@@ -350,15 +332,6 @@ def reach_metres(field, resolution: float) -> np.ndarray:
     return out
 
 
-def _frontier_args(W: int, H: int, rect, min_size: int, inflate: int, filter: int = 0):
-    """(gms_frontiers, label field shape, bytes) of a frontier request of a W x H map; rect = (x0, y0, w, h) in cells, None: the whole map"""
-    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(c) for c in rect)
-    f = _lib.GmsFrontiers(x0, y0, w, h, int(min_size), int(inflate), int(filter), 0)
-    ow, oh, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    check(load().gms_frontiers_size(C.byref(f), C.byref(ow), C.byref(oh), C.byref(nbytes)))
-    return f, (oh.value, ow.value), nbytes.value
-
-
 def _frontier_cost(cost, W: int, H: int):
     """a whole-map cost-to-go field (what reach() returns for the full rectangle) as the contiguous uint16 [H][W] the library takes"""
     if cost is None:
@@ -367,17 +340,6 @@ def _frontier_cost(cost, W: int, H: int):
     if a.shape != (H, W) or a.dtype != np.uint16:
         raise ValueError(f"frontiers: cost must be the whole map's uint16 [{H}][{W}] cost-to-go field, not {a.dtype} {a.shape}")
     return np.ascontiguousarray(a)
-
-
-def _frontier_device(t, nbytes: int, what: str, who: str = "frontiers"):
-    """the device address of a caller's torch tensor of at least nbytes (None: the output is omitted)"""
-    if t is None:
-        return None
-    if not (getattr(t, "is_cuda", False) and t.is_contiguous()):
-        raise ValueError(f"{who}: {what} must be a contiguous torch tensor on the device")
-    if t.numel() * t.element_size() < nbytes:
-        raise ValueError(f"{who}: {what} holds {t.numel() * t.element_size()} bytes, {nbytes} are needed")
-    return C.c_void_p(int(t.data_ptr()))
 
 
 def frontier_centroids(records) -> np.ndarray:
@@ -454,6 +416,114 @@ def descend(field, start) -> list:
             raise ValueError(f"descend: no predecessor at ({x}, {y}): not a whole-map cost-to-go field")
         path.append((x, y))
     return path
+
+
+class _Source:
+    """Where a map query reads its map, the Python counterpart of the library's QuerySource: map `index` of a gms_map handle
+    (kind "map": the entry points gms_map_*) or a particle of a gms_slam handle (kind "slam": gms_slam_*, `index` a handle-wide
+    slot or GMS_VIEW_STRONGEST of `filter`).  The entry points of a query take the same arguments on both; a particle's are followed
+    by the shown word, the index of the particle that was read."""
+
+    def __init__(self, kind: str, handle, index: int, W: int, H: int, filter: int = 0):
+        self.kind, self.lead, self.W, self.H, self.filter, self.shows = kind, (handle, int(index)), W, H, int(filter), kind == "slam"
+
+    def host(self, query: str, *args) -> tuple:
+        """gms_<kind>_<query>(handle, index, args...); returns what the source appends to the result: (shown,) or ()"""
+        fn = getattr(load(), f"gms_{self.kind}_{query}")
+        if not self.shows:
+            check(fn(*self.lead, *args))
+            return ()
+        shown = C.c_int32(-1)
+        check(fn(*self.lead, *args, C.byref(shown)))
+        return (int(shown.value),)
+
+    def dev(self, query: str, *args, shown_out=None) -> tuple:
+        """gms_<kind>_<query>_dev(handle, index, args...), shown_out the device word of a particle's; returns (shown_out,) or ()"""
+        tail = (_shown_ptr(query, shown_out),) if self.shows else ()
+        check(getattr(load(), f"gms_{self.kind}_{query}_dev")(*self.lead, *args, *tail))
+        return (shown_out,) if self.shows else ()
+
+
+# One body per query for a shared map and a particle's own: each returns a tuple, the query's values and then what the source appends.
+# out (frontiers: dev) given: the device form, into the caller's torch tensors on the handle's stream.
+def _query_view(src: _Source, rect, decimate: int, likelihood: bool, packed: bool, out, shown_out) -> tuple:
+    v = _lib.GmsView(*_rect(src.W, src.H, rect), int(decimate), _lib.GMS_VIEW_LIKELIHOOD if likelihood else _lib.GMS_VIEW_LOG,
+                     _lib.GMS_VIEW_PACKED32 if packed else _lib.GMS_VIEW_GREY8, src.filter)
+    v, shape, nbytes = _sized(load().gms_view_size, v)
+    if out is not None:
+        return (out,) + src.dev("view", C.byref(v), _device_ptr("view", "out", out, nbytes), shown_out=shown_out)
+    img = np.empty(shape, dtype=np.uint32 if packed else np.uint8)
+    return (img,) + src.host("view", C.byref(v), ptr(img))
+
+
+def _query_clearance(src: _Source, rect, max_radius: int, not_free: bool, out, shown_out) -> tuple:
+    c, shape, nbytes = _sized(load().gms_clearance_size, _lib.GmsClearance(*_rect(src.W, src.H, rect), int(max_radius), _obstacles(not_free), src.filter))
+    if out is not None:
+        return (out,) + src.dev("clearance", C.byref(c), _device_ptr("clearance", "out", out, nbytes), shown_out=shown_out)
+    field = np.empty(shape, dtype=np.uint16)
+    return (field,) + src.host("clearance", C.byref(c), ptr(field))
+
+
+def _query_reach(src: _Source, seeds, max_cost: int, inflate: int, not_free: bool, rect, out, shown_out) -> tuple:
+    """seeds None (a particle's map alone): the shown particle's own cell"""
+    r = _lib.GmsReach(*_rect(src.W, src.H, rect), int(max_cost), int(inflate), _obstacles(not_free), src.filter)
+    r, shape, nbytes = _sized(load().gms_reach_size, r)
+    if out is not None:
+        sp = _device_ptr("reach", "seeds", seeds, itemsize=4, multiple=2, optional=src.shows)
+        return (out,) + src.dev("reach", C.byref(r), sp, 0 if sp is None else seeds.numel() // 2, _device_ptr("reach", "out", out, nbytes),
+                                shown_out=shown_out)
+    sd = None if seeds is None and src.shows else _reach_seeds(seeds)
+    field = np.empty(shape, dtype=np.uint16)
+    return (field,) + src.host("reach", C.byref(r), None if sd is None else ptr(sd), 0 if sd is None else len(sd), ptr(field))
+
+
+def _query_gain(src: _Source, poses, probes, max_range: int, out, shown_out) -> tuple:
+    g = _lib.GmsGain(int(max_range), src.filter)
+    if out is not None:                                  # poses: (device address, P), probes: (device address, B)
+        (dev_poses, P), (dev_probes, B) = poses, probes
+        return (out,) + src.dev("gain", C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
+                                _device_ptr("gain", "out", out, _lib.GAIN_DTYPE.itemsize * int(P)), shown_out=shown_out)
+    p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+    b = _beams_of(probes).reshape(-1)
+    rec = np.empty(len(p), dtype=_lib.GAIN_DTYPE)
+    return (rec,) + src.host("gain", C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(rec))
+
+
+def _query_locate(src: _Source, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
+                  shown_out) -> tuple:
+    t = _locate_table(offsets) if out is None else None      # with out, offsets: (device address, n_theta, B)
+    n_theta, B = t.shape[:2] if out is None else offsets[1:]
+    lc = _locate_args(src.W, src.H, rect, (n_theta, B), tol, not_free, min_score, cap, free_only, src.filter)
+    if out is not None:
+        return (out, n_out) + src.dev("locate", C.byref(lc), C.c_void_p(offsets[0]), int(B),
+                                      _device_ptr("locate", "out", out, _lib.LOCATE_DTYPE.itemsize * int(cap)),
+                                      _device_ptr("locate", "n_out", n_out, 4, itemsize=4, contiguous=False), shown_out=shown_out)
+    rec = np.empty(max(int(cap), 0), dtype=_lib.LOCATE_DTYPE)
+    n = C.c_int32(0)
+    tail = src.host("locate", C.byref(lc), ptr(t), B, ptr(rec), C.byref(n))
+    return ((rec, int(n.value)) if full else rec[:n.value],) + tail
+
+
+def _query_frontiers(src: _Source, min_size: int, inflate: int, cost, rect, labels, cap: int, dev=None):
+    """dev = (records, labels, shown_out), torch device tensors or None each, cost then one too: the device form, which returns
+    n_found alone"""
+    f, shape, nbytes = _sized(load().gms_frontiers_size, _lib.GmsFrontiers(*_rect(src.W, src.H, rect), int(min_size), int(inflate), src.filter, 0))
+    n = C.c_int32(0)
+    if dev is not None:
+        records, labels, shown_out = dev
+        sfx = "_out" if src.shows else ""
+        cap = 0 if records is None else records.numel() * records.element_size() // _lib.FRONTIER_DTYPE.itemsize
+        src.dev("frontiers", C.byref(f), _device_ptr("frontiers", "cost", cost, src.W * src.H * 2, optional=True),
+                _device_ptr("frontiers", "labels" + sfx, labels, nbytes, optional=True),
+                _device_ptr("frontiers", "records" + sfx, records, optional=True), int(cap), C.byref(n), shown_out=shown_out)
+        return int(n.value)
+    cst = _frontier_cost(cost, src.W, src.H)
+    rec = np.zeros(int(cap), dtype=_lib.FRONTIER_DTYPE)
+    lab = np.empty(shape, dtype=np.uint32) if labels else None
+    tail = src.host("frontiers", C.byref(f), None if cst is None else ptr(cst), None if lab is None else ptr(lab), ptr(rec) if cap else None,
+                    int(cap), C.byref(n))
+    out = (rec[:min(n.value, int(cap))], int(n.value))
+    return (out + (lab,) if labels else out) + tail
 
 
 class GridMap:
@@ -539,6 +609,10 @@ class GridMap:
     def _shape(self):
         return (self.H, self.W) if self.n_maps == 1 else (self.n_maps, self.H, self.W)
 
+    def _src(self, mi: int) -> _Source:
+        """map mi as the source of a query"""
+        return _Source("map", self._h, mi, self.W, self.H)
+
     def reset(self):
         check(load().gms_map_reset(self._h))
 
@@ -568,13 +642,7 @@ class GridMap:
         g << 8 | g words instead of bytes.  Returns a numpy uint8 / uint32 array [ceil(h / d)][ceil(w / d)] (synchronises); with out -- a
         contiguous torch device tensor of that many bytes -- the picture is written there on the handle's stream, nothing is
         synchronised, and out is returned."""
-        v, shape, dtype, nbytes = _view_args(self.W, self.H, rect, decimate, likelihood, packed)
-        if out is not None:
-            check(load().gms_map_view_dev(self._h, int(mi), C.byref(v), C.c_void_p(_view_device_out(out, nbytes))))
-            return out
-        img = np.empty(shape, dtype=dtype)
-        check(load().gms_map_view(self._h, int(mi), C.byref(v), ptr(img)))
-        return img
+        return _query_view(self._src(mi), rect, decimate, likelihood, packed, out, None)[0]
 
     def world_rect(self, center, size):
         """(x0, y0, w, h): the cells under a world rectangle (centre, size in metres), clamped to the map (world_rect_to_cells)"""
@@ -594,7 +662,7 @@ class GridMap:
     def cast_dev(self, dev_poses: int, P: int, dev_probes: int, B: int, out, mi: int = 0):
         """cast() with device pointers; out: a contiguous torch device tensor of P * B * 16 bytes, written on the handle's stream"""
         check(load().gms_map_cast_dev(self._h, int(mi), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
-                                      C.c_void_p(_cast_device_out(out, P * B))))
+                                      _device_ptr("cast_dev", "out", out, 16 * P * B)))
         return out
 
     def cast_at(self, probes, pf: "ParticleFilter", strongest: bool = False) -> np.ndarray:
@@ -607,7 +675,7 @@ class GridMap:
 
     def cast_at_dev(self, dev_probes: int, B: int, pf: "ParticleFilter", out, strongest: bool = False):
         check(load().gms_map_cast_at_dev(self._h, C.c_void_p(dev_probes), int(B), pf._h, 1 if strongest else 0,
-                                         C.c_void_p(_cast_device_out(out, self.n_maps * B))))
+                                         _device_ptr("cast_at_dev", "out", out, 16 * self.n_maps * B)))
         return out
 
     def gain(self, poses, probes, max_range: int, mi: int = 0) -> np.ndarray:
@@ -615,19 +683,11 @@ class GridMap:
         there -- each walk as cast() makes it without the extra_steps cells, cut at max_range cells (1 .. 255, Chebyshev) from the
         start cell and ended by (and including) its first occupied cell -- counted by class.  Returns gms_gain_rec records [P]
         (GAIN_DTYPE: unknown, free_cells, occupied, hits, walked, start_x, start_y, pad).  Probes: probe_fan()."""
-        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        b = _beams_of(probes).reshape(-1)
-        g = _lib.GmsGain(int(max_range), 0)
-        out = np.empty(len(p), dtype=_lib.GAIN_DTYPE)
-        check(load().gms_map_gain(self._h, int(mi), C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(out)))
-        return out
+        return _query_gain(self._src(mi), poses, probes, max_range, None, None)[0]
 
     def gain_dev(self, dev_poses: int, P: int, dev_probes: int, B: int, out, max_range: int, mi: int = 0):
         """gain() with device pointers; out: a contiguous torch device tensor of P * 32 bytes, written on the handle's stream"""
-        g = _lib.GmsGain(int(max_range), 0)
-        check(load().gms_map_gain_dev(self._h, int(mi), C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
-                                      C.c_void_p(_gain_device_out(out, P))))
-        return out
+        return _query_gain(self._src(mi), (dev_poses, P), (dev_probes, B), max_range, out, None)[0]
 
     def locate(self, offsets, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64, free_only: bool = True,
                mi: int = 0, full: bool = False):
@@ -638,22 +698,14 @@ class GridMap:
         x, y), score descending, then k, y, x ascending.  The result of the exhaustive search, found by a pruned multi-resolution
         one.  full=True: (all cap records, n_out), the filler records {0, -1, -1, -1} behind the first n_out included.
         Poses: locate_poses(); peaks: locate_peaks()."""
-        t = _locate_table(offsets)
-        lc = _locate_args(self.W, self.H, rect, t.shape, tol, not_free, min_score, cap, free_only)
-        rec = np.empty(max(int(cap), 0), dtype=_lib.LOCATE_DTYPE)
-        n = C.c_int32(0)
-        check(load().gms_map_locate(self._h, int(mi), C.byref(lc), ptr(t), t.shape[1], ptr(rec), C.byref(n)))
-        return (rec, int(n.value)) if full else rec[:n.value]
+        return _query_locate(self._src(mi), offsets, rect, tol, not_free, min_score, cap, free_only, full, None, None, None)[0]
 
     def locate_dev(self, dev_offsets: int, n_theta: int, B: int, out, n_out, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1,
                    cap: int = 64, free_only: bool = True, mi: int = 0):
         """locate() with device memory on the handle's stream: dev_offsets the table's device address (its entries within [-4095,
         4095] or SKIP pairs: a precondition), out a contiguous torch device tensor of cap * 16 bytes (16-byte aligned), n_out an int32
         one.  The call waits on the stream once per level of the search."""
-        lc = _locate_args(self.W, self.H, rect, (n_theta, B), tol, not_free, min_score, cap, free_only)
-        po, pn = _locate_device(out, n_out, int(cap))
-        check(load().gms_map_locate_dev(self._h, int(mi), C.byref(lc), C.c_void_p(dev_offsets), int(B), po, pn))
-        return out, n_out
+        return _query_locate(self._src(mi), (dev_offsets, n_theta, B), rect, tol, not_free, min_score, cap, free_only, False, out, n_out, None)
 
     def locate_stats(self) -> dict:
         """diagnostics of the last locate() on this handle: {"levels": the top level L of its search, "evaluated": the candidates it
@@ -680,13 +732,7 @@ class GridMap:
         that is not known free, !(logData < 0) -- as uint16 [h][w]; GMS_CLEAR_FAR (0xFFFF) beyond max_radius (1 .. 255 cells).
         Returns a numpy array (synchronises); with out -- a contiguous torch device tensor of h * w * 2 bytes -- the field is written
         there on the handle's stream, nothing is synchronised, and out is returned (clearance_dev).  Metres: clearance_metres()."""
-        c, shape, nbytes = _clearance_args(self.W, self.H, rect, max_radius, not_free)
-        if out is not None:
-            check(load().gms_map_clearance_dev(self._h, int(mi), C.byref(c), C.c_void_p(_view_device_out(out, nbytes))))
-            return out
-        field = np.empty(shape, dtype=np.uint16)
-        check(load().gms_map_clearance(self._h, int(mi), C.byref(c), ptr(field)))
-        return field
+        return _query_clearance(self._src(mi), rect, max_radius, not_free, out, None)[0]
 
     def clearance_dev(self, out, rect=None, max_radius: int = 25, not_free: bool = False, mi: int = 0):
         """clearance() into out, a contiguous torch device tensor of h * w * 2 bytes, on the handle's stream"""
@@ -700,17 +746,7 @@ class GridMap:
         beyond max_cost.  Paths use the whole map.  Returns a numpy array; with out (a contiguous torch device tensor of h * w * 2
         bytes) seeds must be an int32 torch device tensor [K][2], the field is written there on the handle's stream, and out is
         returned (reach_dev).  Metres: reach_metres(); a path: descend()."""
-        r, shape, nbytes = _reach_args(self.W, self.H, rect, max_cost, inflate, not_free)
-        if out is not None:
-            if not (getattr(seeds, "is_cuda", False) and seeds.is_contiguous() and seeds.element_size() == 4 and seeds.numel() % 2 == 0):
-                raise ValueError("reach_dev: seeds must be a contiguous int32 torch tensor [K][2] on the device")
-            check(load().gms_map_reach_dev(self._h, int(mi), C.byref(r), C.c_void_p(int(seeds.data_ptr())), seeds.numel() // 2,
-                                           C.c_void_p(_view_device_out(out, nbytes))))
-            return out
-        sd = _reach_seeds(seeds)
-        field = np.empty(shape, dtype=np.uint16)
-        check(load().gms_map_reach(self._h, int(mi), C.byref(r), ptr(sd), len(sd), ptr(field)))
-        return field
+        return _query_reach(self._src(mi), seeds, max_cost, inflate, not_free, rect, out, None)[0]
 
     def reach_dev(self, out, seeds, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None, mi: int = 0):
         """reach() from device seeds into out, on the handle's stream; the call waits on that stream between batches of rounds"""
@@ -725,27 +761,14 @@ class GridMap:
         smallest cost, goal_cost that cost; without it goal = (-1, -1).  labels=True appends the label field of rect = (x0, y0, w, h)
         (None: the whole map), uint32 [h][w]: every frontier cell its region's anchor index y * W + x, GMS_FRONTIER_NONE elsewhere.
         Centroids: frontier_centroids()."""
-        f, shape, _ = _frontier_args(self.W, self.H, rect, min_size, inflate)
-        cst = _frontier_cost(cost, self.W, self.H)
-        rec = np.zeros(int(cap), dtype=_lib.FRONTIER_DTYPE)
-        lab = np.empty(shape, dtype=np.uint32) if labels else None
-        n = C.c_int32(0)
-        check(load().gms_map_frontiers(self._h, int(mi), C.byref(f), None if cst is None else ptr(cst), None if lab is None else ptr(lab),
-                                       ptr(rec) if cap else None, int(cap), C.byref(n)))
-        out = (rec[:min(n.value, int(cap))], int(n.value))
-        return out + (lab,) if labels else out
+        return _query_frontiers(self._src(mi), min_size, inflate, cost, rect, labels, cap)
 
     def frontiers_dev(self, records=None, labels=None, cost=None, min_size: int = 1, inflate: int = 0, rect=None, mi: int = 0) -> int:
         """frontiers() with device memory on the handle's stream: records (room for cap = bytes // 56 gms_frontier, 8-byte aligned),
         labels (h * w * 4 bytes, 4-byte aligned) and cost (the whole map's uint16 field) are contiguous torch device tensors, any of
         them None.  Returns n_found; the call waits on the stream once (once more when the handle's region table has to grow), so the
         outputs are complete when it returns."""
-        f, _, nbytes = _frontier_args(self.W, self.H, rect, min_size, inflate)
-        cap = 0 if records is None else records.numel() * records.element_size() // _lib.FRONTIER_DTYPE.itemsize
-        n = C.c_int32(0)
-        check(load().gms_map_frontiers_dev(self._h, int(mi), C.byref(f), _frontier_device(cost, self.W * self.H * 2, "cost"),
-                                           _frontier_device(labels, nbytes, "labels"), _frontier_device(records, 0, "records"), int(cap), C.byref(n)))
-        return int(n.value)
+        return _query_frontiers(self._src(mi), min_size, inflate, cost, rect, False, 0, dev=(records, labels, None))
 
     def reach_stats(self) -> dict:
         """diagnostics of the last cost-to-go field made on this handle: {"rounds": launches over the tiles, "tile_runs": tile
@@ -760,15 +783,13 @@ class GridMap:
         where that cell is off the map."""
         p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
         out = np.empty(len(p), dtype=np.uint16)
-        check(load().gms_map_clearance_poses(self._h, int(mi), ptr(p), len(p), int(max_radius),
-                                             _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED, ptr(out)))
+        check(load().gms_map_clearance_poses(self._h, int(mi), ptr(p), len(p), int(max_radius), _obstacles(not_free), ptr(out)))
         return out
 
     def clearance_poses_dev(self, dev_poses: int, P: int, out, max_radius: int = 25, not_free: bool = False, mi: int = 0):
         """clearance_poses() with a device pointer; out: a contiguous torch device tensor of P * 2 bytes, written on the handle's stream"""
-        check(load().gms_map_clearance_poses_dev(self._h, int(mi), C.c_void_p(dev_poses), int(P), int(max_radius),
-                                                 _lib.GMS_CLEAR_NOT_FREE if not_free else _lib.GMS_CLEAR_OCCUPIED,
-                                                 C.c_void_p(_view_device_out(out, 2 * int(P)))))
+        check(load().gms_map_clearance_poses_dev(self._h, int(mi), C.c_void_p(dev_poses), int(P), int(max_radius), _obstacles(not_free),
+                                                 _device_ptr("clearance_poses_dev", "out", out, 2 * int(P))))
         return out
 
     def copy_from(self, other: "GridMap"):
@@ -1177,8 +1198,7 @@ class ParticleFilter:
         it a sequence sample_motion() does not use.  want_count: the eligible cells per map are read back (one synchronise) and
         returned, an int or an int64 array [n_maps]; otherwise nothing is synchronised and None is returned.  Slots for the recovery
         idiom: scatter_slots()."""
-        x0, y0, w, h = (0, 0, self.map.W, self.map.H) if rect is None else (int(c) for c in rect)
-        sc = _lib.GmsScatter(x0, y0, w, h, int(inflate), int(mode), int(first),
+        sc = _lib.GmsScatter(*_rect(self.map.W, self.map.H, rect), int(inflate), int(mode), int(first),
                              self.n - int(first) if count is None else int(count), 1 if jitter else 0, 0)
         M = np.zeros(self.n_maps, dtype=np.int64) if want_count else None
         check(load().gms_pf_scatter(self._h, C.byref(sc), int(seed), int(sequence), None if M is None else ptr(M)))
@@ -1203,8 +1223,8 @@ class ParticleFilter:
         nf, no = C.c_int32(0), C.c_int32(0)
         if records_out is not None or labels_out is not None:
             cap = 0 if records_out is None else records_out.numel() * records_out.element_size() // _lib.MODE_DTYPE.itemsize
-            check(load().gms_pf_modes_dev(self._h, int(mi), C.byref(q), _frontier_device(labels_out, self.n * 4, "labels_out", "modes"),
-                                          _frontier_device(records_out, 0, "records_out", "modes"), int(cap), C.byref(nf), C.byref(no)))
+            check(load().gms_pf_modes_dev(self._h, int(mi), C.byref(q), _device_ptr("modes", "labels_out", labels_out, self.n * 4, optional=True),
+                                          _device_ptr("modes", "records_out", records_out, optional=True), int(cap), C.byref(nf), C.byref(no)))
             return int(nf.value), int(no.value)
         rec = np.zeros(int(cap), dtype=_lib.MODE_DTYPE)
         lab = np.empty(self.n, dtype=np.uint32) if labels else None
@@ -1240,14 +1260,7 @@ class ParticleFilter:
         device tensor of at least n_maps * n * B 16-bit elements that receives the table indices.  Runs on the handle's stream and
         synchronises nothing."""
         f = self._beam_factors(factors, behind, ahead)
-        out = None
-        if residuals_out is not None:
-            if not (getattr(residuals_out, "is_cuda", False) and residuals_out.is_contiguous()):
-                raise ValueError("score_beams_dev: residuals_out must be a contiguous torch tensor on the device")
-            need = 2 * self.n_maps * self.n * int(B)
-            if residuals_out.numel() * residuals_out.element_size() < need:
-                raise ValueError(f"score_beams_dev: residuals_out holds {residuals_out.numel() * residuals_out.element_size()} bytes, the indices need {need}")
-            out = C.c_void_p(int(residuals_out.data_ptr()))
+        out = _device_ptr("score_beams_dev", "residuals_out", residuals_out, 2 * self.n_maps * self.n * int(B), optional=True)
         check(load().gms_pf_score_beams_dev(self._h, C.c_void_p(dev_beams), int(B), int(behind), int(ahead), ptr(f), out))
 
     def set_refine(self, on: bool = True):
@@ -1496,173 +1509,52 @@ class _SlamHandle:
         check(load().gms_slam_trace_scan(self._h, int(slot), ptr(b), len(b), ptr(cells), ptr(cls), cap, ptr(counts)))
         return cells, cls, counts
 
+    def _src(self, query: str, which, filter: int) -> _Source:
+        """particle `which` -- a handle-wide slot or "strongest" (of `filter`, picked on the device) -- as the source of a query"""
+        return _Source("slam", self._h, _which(query, which), self.W, self.H, filter)
+
     def _view(self, which, filter: int, rect, decimate: int, likelihood: bool, packed: bool, out, shown_out):
-        """gms_slam_view[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (image, shown)"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('view: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
-        v, shape, dtype, nbytes = _view_args(self.W, self.H, rect, decimate, likelihood, packed, filter)
-        if out is not None:
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("view: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_view_dev(self._h, int(which), C.byref(v), C.c_void_p(_view_device_out(out, nbytes)), sh))
-            return out, shown_out
-        img = np.empty(shape, dtype=dtype)
-        shown = C.c_int32(-1)
-        check(load().gms_slam_view(self._h, int(which), C.byref(v), ptr(img), C.byref(shown)))
-        return img, int(shown.value)
+        """gms_slam_view[_dev]: (image, shown)"""
+        return _query_view(self._src("view", which, filter), rect, decimate, likelihood, packed, out, shown_out)
 
     def _cast(self, which, filter: int, probes, out, shown_out):
         """gms_slam_cast[_dev]: which = a handle-wide slot, "strongest" (of `filter`, picked on the device) or "all"; (records, shown)"""
-        if isinstance(which, str):
-            if which not in ("strongest", "all"):
-                raise ValueError('cast: which must be a particle index, "strongest" or "all"')
-            which = _lib.GMS_VIEW_STRONGEST if which == "strongest" else _lib.GMS_CAST_ALL
+        which = _which("cast", which, allow_all=True)
         every = which == _lib.GMS_CAST_ALL
         n_total = self.num_particles * int(self.params.n_maps)
         if out is not None:                                  # probes: (device address, B)
             dev_probes, B = probes
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("cast: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_cast_dev(self._h, int(which), int(filter), C.c_void_p(dev_probes), int(B),
-                                           C.c_void_p(_cast_device_out(out, (n_total if every else 1) * B)), sh))
+            check(load().gms_slam_cast_dev(self._h, which, int(filter), C.c_void_p(dev_probes), int(B),
+                                           _device_ptr("cast", "out", out, 16 * (n_total if every else 1) * B), _shown_ptr("cast", shown_out)))
             return out, shown_out
         b = _beams_of(probes).reshape(-1)
         rec = np.empty((n_total, len(b)) if every else (len(b),), dtype=CAST_DTYPE)
         shown = C.c_int32(-1)
-        check(load().gms_slam_cast(self._h, int(which), int(filter), ptr(b), len(b), ptr(rec), C.byref(shown)))
+        check(load().gms_slam_cast(self._h, which, int(filter), ptr(b), len(b), ptr(rec), C.byref(shown)))
         return rec, (None if every else int(shown.value))
 
     def _gain(self, which, filter: int, poses, probes, max_range: int, out, shown_out):
-        """gms_slam_gain[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (records, shown)"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('gain: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
-        g = _lib.GmsGain(int(max_range), int(filter))
-        if out is not None:                                  # poses: (device address, P), probes: (device address, B)
-            (dev_poses, P), (dev_probes, B) = poses, probes
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("gain: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_gain_dev(self._h, int(which), C.byref(g), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_probes), int(B),
-                                           C.c_void_p(_gain_device_out(out, P)), sh))
-            return out, shown_out
-        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        b = _beams_of(probes).reshape(-1)
-        rec = np.empty(len(p), dtype=_lib.GAIN_DTYPE)
-        shown = C.c_int32(-1)
-        check(load().gms_slam_gain(self._h, int(which), C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(rec), C.byref(shown)))
-        return rec, int(shown.value)
+        """gms_slam_gain[_dev]: (records, shown)"""
+        return _query_gain(self._src("gain", which, filter), poses, probes, max_range, out, shown_out)
 
     def _locate(self, which, filter: int, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
                 shown_out):
-        """gms_slam_locate[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (records, shown)"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('locate: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
-        if out is not None:                                  # offsets: (device address, n_theta, B)
-            dev_offsets, n_theta, B = offsets
-            lc = _locate_args(self.W, self.H, rect, (n_theta, B), tol, not_free, min_score, cap, free_only, filter)
-            po, pn = _locate_device(out, n_out, int(cap))
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("locate: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_locate_dev(self._h, int(which), C.byref(lc), C.c_void_p(dev_offsets), int(B), po, pn, sh))
-            return out, n_out, shown_out
-        t = _locate_table(offsets)
-        lc = _locate_args(self.W, self.H, rect, t.shape, tol, not_free, min_score, cap, free_only, filter)
-        rec = np.empty(max(int(cap), 0), dtype=_lib.LOCATE_DTYPE)
-        n, shown = C.c_int32(0), C.c_int32(-1)
-        check(load().gms_slam_locate(self._h, int(which), C.byref(lc), ptr(t), t.shape[1], ptr(rec), C.byref(n), C.byref(shown)))
-        return ((rec, int(n.value)) if full else rec[:n.value]), int(shown.value)
+        """gms_slam_locate[_dev]: (records, shown), or (out, n_out, shown_out)"""
+        return _query_locate(self._src("locate", which, filter), offsets, rect, tol, not_free, min_score, cap, free_only, full, out, n_out, shown_out)
 
     def _clearance(self, which, filter: int, rect, max_radius: int, not_free: bool, out, shown_out):
-        """gms_slam_clearance[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device); (field, shown)"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('clearance: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
-        c, shape, nbytes = _clearance_args(self.W, self.H, rect, max_radius, not_free, filter)
-        if out is not None:
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("clearance: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_clearance_dev(self._h, int(which), C.byref(c), C.c_void_p(_view_device_out(out, nbytes)), sh))
-            return out, shown_out
-        field = np.empty(shape, dtype=np.uint16)
-        shown = C.c_int32(-1)
-        check(load().gms_slam_clearance(self._h, int(which), C.byref(c), ptr(field), C.byref(shown)))
-        return field, int(shown.value)
+        """gms_slam_clearance[_dev]: (field, shown)"""
+        return _query_clearance(self._src("clearance", which, filter), rect, max_radius, not_free, out, shown_out)
 
     def _reach(self, which, filter: int, seeds, max_cost: int, inflate: int, not_free: bool, rect, out, shown_out):
-        """gms_slam_reach[_dev]: which = a handle-wide slot or "strongest" (of `filter`); seeds None: the shown particle's own cell"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('reach: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
-        r, shape, nbytes = _reach_args(self.W, self.H, rect, max_cost, inflate, not_free, filter)
-        if out is not None:
-            sp, K = None, 0
-            if seeds is not None:
-                if not (getattr(seeds, "is_cuda", False) and seeds.is_contiguous() and seeds.element_size() == 4 and seeds.numel() % 2 == 0):
-                    raise ValueError("reach: with out, seeds must be a contiguous int32 torch tensor [K][2] on the device (or None)")
-                sp, K = C.c_void_p(int(seeds.data_ptr())), seeds.numel() // 2
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("reach: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_reach_dev(self._h, int(which), C.byref(r), sp, K, C.c_void_p(_view_device_out(out, nbytes)), sh))
-            return out, shown_out
-        sd = None if seeds is None else _reach_seeds(seeds)
-        field = np.empty(shape, dtype=np.uint16)
-        shown = C.c_int32(-1)
-        check(load().gms_slam_reach(self._h, int(which), C.byref(r), None if sd is None else ptr(sd), 0 if sd is None else len(sd), ptr(field),
-                                    C.byref(shown)))
-        return field, int(shown.value)
+        """gms_slam_reach[_dev]: (field, shown); seeds None: the shown particle's own cell"""
+        return _query_reach(self._src("reach", which, filter), seeds, max_cost, inflate, not_free, rect, out, shown_out)
 
     def _frontiers(self, which, filter: int, min_size: int, inflate: int, cost, rect, labels, cap: int, records_out, labels_out, shown_out):
-        """gms_slam_frontiers[_dev]: which = a handle-wide slot or "strongest" (of `filter`, picked on the device)"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('frontiers: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
-        f, shape, nbytes = _frontier_args(self.W, self.H, rect, min_size, inflate, filter)
-        n = C.c_int32(0)
-        if records_out is not None or labels_out is not None or shown_out is not None or getattr(cost, "is_cuda", False):
-            cap = 0 if records_out is None else records_out.numel() * records_out.element_size() // _lib.FRONTIER_DTYPE.itemsize
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("frontiers: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_frontiers_dev(self._h, int(which), C.byref(f), _frontier_device(cost, self.W * self.H * 2, "cost"),
-                                                _frontier_device(labels_out, nbytes, "labels_out"), _frontier_device(records_out, 0, "records_out"),
-                                                int(cap), C.byref(n), sh))
-            return int(n.value)
-        cst = _frontier_cost(cost, self.W, self.H)
-        rec = np.zeros(int(cap), dtype=_lib.FRONTIER_DTYPE)
-        lab = np.empty(shape, dtype=np.uint32) if labels else None
-        shown = C.c_int32(-1)
-        check(load().gms_slam_frontiers(self._h, int(which), C.byref(f), None if cst is None else ptr(cst), None if lab is None else ptr(lab),
-                                        ptr(rec) if cap else None, int(cap), C.byref(n), C.byref(shown)))
-        out = (rec[:min(n.value, int(cap))], int(n.value))
-        return (out + (lab,) if labels else out) + (int(shown.value),)
+        """gms_slam_frontiers[_dev]: (records, n_found[, labels], shown); any device tensor among the arguments: the device form"""
+        dev = records_out is not None or labels_out is not None or shown_out is not None or getattr(cost, "is_cuda", False)
+        return _query_frontiers(self._src("frontiers", which, filter), min_size, inflate, cost, rect, labels, cap,
+                                dev=(records_out, labels_out, shown_out) if dev else None)
 
     def set_history(self, capacity: int):
         """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
@@ -1683,24 +1575,15 @@ class _SlamHandle:
 
     def _trajectory(self, which, filter: int, out, shown_out):
         """gms_slam_trajectory[_dev]: which = a handle-wide slot or "strongest" (of `filter`); (xytheta [kept][3] oldest first, shown)"""
-        if isinstance(which, str):
-            if which != "strongest":
-                raise ValueError('trajectory: which must be a particle index or "strongest"')
-            which = _lib.GMS_VIEW_STRONGEST
+        which = _which("trajectory", which)
         kept = self.history_len()[1]
         if out is not None:
-            if not (getattr(out, "is_cuda", False) and out.is_contiguous() and out.element_size() == 4 and out.numel() >= 3 * kept):
-                raise ValueError(f"trajectory: out must be a contiguous float32 torch tensor on the device of at least {kept} x 3 values")
-            sh = None
-            if shown_out is not None:
-                if not (getattr(shown_out, "is_cuda", False) and shown_out.element_size() == 4 and shown_out.numel() >= 1):
-                    raise ValueError("trajectory: shown_out must be an int32 torch tensor on the device")
-                sh = C.c_void_p(int(shown_out.data_ptr()))
-            check(load().gms_slam_trajectory_dev(self._h, int(which), int(filter), C.c_void_p(int(out.data_ptr())), out.numel() // 3, sh))
+            check(load().gms_slam_trajectory_dev(self._h, which, int(filter), _device_ptr("trajectory", "out", out, 12 * kept, itemsize=4),
+                                                 out.numel() // 3, _shown_ptr("trajectory", shown_out)))
             return out, shown_out
         xy = np.empty((kept, 3), dtype=np.float32)
         count, shown = C.c_int32(0), C.c_int32(-1)
-        check(load().gms_slam_trajectory(self._h, int(which), int(filter), ptr(xy), kept, C.byref(count), C.byref(shown)))
+        check(load().gms_slam_trajectory(self._h, which, int(filter), ptr(xy), kept, C.byref(count), C.byref(shown)))
         return xy[:count.value], int(shown.value)
 
     def _trajectories(self, filter: int, ancestors: bool):
@@ -2029,6 +1912,15 @@ class SLAMParticleMapsBatch(_SlamHandle):
             raise IndexError(f"particle {i} of filter {f}: out of range ({self.num_filters} x {self.num_particles})")
         return int(f) * self.num_particles + int(i)
 
+    def _local(self, filter: int, which=None):
+        """what a filter-local request passes on as `which`: a FILTER-LOCAL particle index as the handle-wide slot, anything else
+        ("strongest", "all", None: the filter as a whole) as it is, its filter range-checked"""
+        if which is not None and not isinstance(which, str):
+            return self._slot(filter, which)
+        if not 0 <= filter < self.num_filters:
+            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
+        return which
+
     def map_of(self, f: int, i: int, likelihood: bool = False) -> np.ndarray:
         """filter f's particle i's logData (or likelihoodData) as [H][W]"""
         return self._map_of(self._slot(f, i), likelihood)
@@ -2046,88 +1938,54 @@ class SLAMParticleMapsBatch(_SlamHandle):
              shown_out=None):
         """SLAMParticleMaps.view for filter `filter`: which = "strongest" (that filter's, picked on the device) or a FILTER-LOCAL particle
         index.  shown is the handle-wide slot filter * num_particles + k that was drawn (the index space of gms_slam_download_map)."""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._view(which, filter, rect, decimate, likelihood, packed, out, shown_out)
+        return self._view(self._local(filter, which), filter, rect, decimate, likelihood, packed, out, shown_out)
 
     def cast(self, probes, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.cast for filter `filter`: which = "strongest" (that filter's), a FILTER-LOCAL particle index, or "all":
         every particle of EVERY filter, records [S * n][B] in handle-wide slot order; shown is the handle-wide slot, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._cast(which, filter, probes, out, shown_out)
+        return self._cast(self._local(filter, which), filter, probes, out, shown_out)
 
     def clearance(self, which="strongest", filter: int = 0, rect=None, max_radius: int = 25, not_free: bool = False, out=None, shown_out=None):
         """SLAMParticleMaps.clearance for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
         is the handle-wide slot filter * num_particles + k whose field was made, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._clearance(which, filter, rect, max_radius, not_free, out, shown_out)
+        return self._clearance(self._local(filter, which), filter, rect, max_radius, not_free, out, shown_out)
 
     def reach(self, which="strongest", filter: int = 0, seeds=None, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None,
               out=None, shown_out=None):
         """SLAMParticleMaps.reach for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
         the handle-wide slot filter * num_particles + k whose field was made, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._reach(which, filter, seeds, max_cost, inflate, not_free, rect, out, shown_out)
+        return self._reach(self._local(filter, which), filter, seeds, max_cost, inflate, not_free, rect, out, shown_out)
 
     def frontiers(self, which="strongest", filter: int = 0, min_size: int = 1, inflate: int = 0, cost=None, rect=None, labels: bool = False,
                   cap: int = 4096, records_out=None, labels_out=None, shown_out=None):
         """SLAMParticleMaps.frontiers for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
         is the handle-wide slot filter * num_particles + k whose regions were made, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._frontiers(which, filter, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
+        return self._frontiers(self._local(filter, which), filter, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
 
     def gain(self, poses, probes, max_range: int, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.gain for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
         the handle-wide slot filter * num_particles + k in whose map the poses were judged, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._gain(which, filter, poses, probes, max_range, out, shown_out)
+        return self._gain(self._local(filter, which), filter, poses, probes, max_range, out, shown_out)
 
     def locate(self, offsets, which="strongest", filter: int = 0, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
                free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):
         """SLAMParticleMaps.locate for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
         the handle-wide slot filter * num_particles + k in whose map the scan was matched, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._locate(which, filter, offsets, rect, tol, not_free, min_score, cap, free_only, full, out, n_out, shown_out)
+        return self._locate(self._local(filter, which), filter, offsets, rect, tol, not_free, min_score, cap, free_only, full, out, n_out, shown_out)
 
     def trajectory(self, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.trajectory for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
         is the handle-wide slot that was followed, as view() reports it"""
-        if not isinstance(which, str):
-            which = self._slot(filter, which)
-        elif not 0 <= filter < self.num_filters:
-            raise IndexError(f"filter {filter} out of range ({self.num_filters})")
-        return self._trajectory(which, filter, out, shown_out)
+        return self._trajectory(self._local(filter, which), filter, out, shown_out)
 
     def trajectories(self, f: int, ancestors: bool = False):
         """filter f's particles' paths: xytheta [kept][n][3] (and, ancestors, the filter-local slots [kept][n])"""
-        if not 0 <= f < self.num_filters:
-            raise IndexError(f"filter {f} out of range ({self.num_filters})")
+        self._local(f)
         return self._trajectories(f, ancestors)
 
     def calculate_combined(self, f: int, likelihood: bool = False) -> np.ndarray:
         """GridMapApp.calculateCombined over filter f's particles: its logData [H][W] (likelihood: the field of it)"""
-        if not 0 <= f < self.num_filters:
-            raise IndexError(f"filter {f} out of range ({self.num_filters})")
+        self._local(f)
         check(load().gms_slam_combined(self._h))
         out = self.grid_map.download_likelihood() if likelihood else self.grid_map.download_log()
         return out.reshape(self.num_filters, self.H, self.W)[int(f)]
