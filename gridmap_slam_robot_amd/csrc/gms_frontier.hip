@@ -12,25 +12,25 @@
 //                       cost-to-go fields' blocked plane (gms_reach_inflate).  Both planes are read in place (query_plane; a gms_slam's:
 //                       the shown particle's, packed per request, twice).
 //   k_front_tiles       a workgroup per 64 x 64 tile; a tile whose 64 words are all zero leaves at once.  Every frontier cell starts as
-//                       its own root in LDS and is united with its W, N, NW and NE neighbours inside the tile (front_unite); then every
+//                       its own root in LDS and is united with its W, N, NW and NE neighbours inside the tile (region_unite); then every
 //                       cell chases to its root and writes the root's GLOBAL linear index into the label field.  Tile-local order is the
 //                       global order restricted to the tile, so that root is the tile's smallest member of the cell's component.
 //   k_front_merge       a lane per cell on the first column / row behind a tile border: united, in the global label field, with its (up
 //                       to) three neighbours across that border -- every pair adjacent across an edge or a corner, both diagonals.
 //   k_front_flatten     a wavefront per plane word: every frontier cell chases to its root and stores it; the ballot of "I am my own
 //                       root" is the root plane's word, its popcount the word's count.
-//   k_front_scan_*      exclusive scan of those counts (blocks of FRT_SCAN in one launch, the blocks' sums in a second, single
-//                       workgroup): the roots in linear order = the regions in anchor order; the total is the number of regions.
+//   gms_launch_scan     the exclusive scan of those counts: the roots in linear order = the regions in anchor order; the total is the
+//                       number of regions.
 //   k_front_table_init, k_front_reduce, k_front_finish
 //                       the table: a wavefront per plane word looks up every cell's region index, and the lanes that share one combine
-//                       (count, box and sums from the group's ballot alone; the goal key cost << 32 | index by a butterfly) before ONE
-//                       lane issues the atomics -- integer min / max / add only.  The finish decodes the goal and flags count >= min_size.
-//   k_front_scan_*, k_front_emit   the flags scanned, the kept regions' records stored in order, the first `cap` of them.
+//                       (wave_each_key: count, box and sums from the group's ballot alone; the goal key cost << 32 | index by a
+//                       butterfly) before ONE lane issues the atomics -- integer min / max / add only.  The finish decodes the goal and
+//                       flags count >= min_size.
+//   gms_launch_scan, k_front_emit   the flags scanned, the kept regions' records stored in order, the first `cap` of them.
 //   k_front_labels      the label rectangle: the label where the plane has a bit, GMS_FRONTIER_NONE elsewhere.
 //
-// front_unite is the lock-free union: find both roots, hang the LARGER under the smaller with atomicMin, and if that root had moved in
-// the meantime (the old value is not the root itself) go on with what it moved to.  A label only ever decreases and never exceeds its
-// own index, so chains end, nothing cycles, and nobody waits for anybody: a retry follows another lane's progress.
+// The union, the group loop, the wavefront minimum and the scan's look-up are the shared ones of gms_regions.h; the scan itself is the
+// query base's (gms_query.hip).
 //
 // LDS of k_front_tiles: 64 words + 4096 uint32 labels = 16.5 KiB.  A lane owns 16 cells of a row and visits the set bits only.
 #undef GMS_STAMPS
@@ -41,12 +41,11 @@
 
 #include <algorithm>
 
-#include "gms_device.h"
+#include "gms_regions.h"
 
 #define FRT_T 64                         // tile edge in cells = cells of a plane word
 #define FRT_NT 256
-#define FRT_SCAN 1024                    // items a workgroup of k_front_scan_blocks scans
-#define FRT_CAP0 4096                    // regions the handle's table holds at first (a multiple of FRT_SCAN)
+#define FRT_CAP0 4096                    // regions the handle's table holds at first (a multiple of GMS_SCAN)
 #define FRT_NONE 0xffffffffu
 #define FRT_NO_GOAL 0xffffffffffffffffull
 
@@ -54,26 +53,7 @@ static_assert(GMS_FRONTIER_NONE == FRT_NONE, "the header's constant is the kerne
 static_assert(sizeof(gms_frontiers) == 32 && sizeof(gms_frontier) == 56 && offsetof(gms_frontier, count) == 8 && offsetof(gms_frontier, goal_cost) == 12 &&
               offsetof(gms_frontier, min_x) == 16 && offsetof(gms_frontier, max_x) == 24 && offsetof(gms_frontier, goal_x) == 32 &&
               offsetof(gms_frontier, sum_x) == 40 && offsetof(gms_frontier, sum_y) == 48, "the header fixes the record's offsets");
-static_assert(FRT_CAP0 % FRT_SCAN == 0, "the table's parts stay 8-byte aligned");
-
-__device__ __forceinline__ uint32_t front_find(const uint32_t *L, uint32_t a) {
-    for (;;) {
-        const uint32_t p = __atomic_load_n(L + a, __ATOMIC_RELAXED);
-        if (p == a) return a;
-        a = p;
-    }
-}
-__device__ __forceinline__ void front_unite(uint32_t *L, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = front_find(L, a);
-        b = front_find(L, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(L + a, b);                               // the larger root under the smaller
-        if (old == a) return;
-        a = old;                                                                // a had moved: unite what it moved to
-    }
-}
+static_assert(FRT_CAP0 % GMS_SCAN == 0, "the table's parts stay 8-byte aligned");
 
 // occ, nf, blocked (NULL: inflate == 0): ONE map's planes, H rows of wpr64 words; out likewise
 __global__ void __launch_bounds__(FRT_NT)
@@ -118,17 +98,17 @@ k_front_tiles(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int3
     for (uint32_t b = mine; b; b &= b - 1u) {
         const int32_t lx = c0 + __builtin_ctz(b);
         const uint32_t c = (uint32_t)(r * FRT_T + lx);
-        if (lx > 0 && ((row >> (lx - 1)) & 1ull)) front_unite(s_lab, c, c - 1u);
-        if ((up >> lx) & 1ull) front_unite(s_lab, c, c - FRT_T);                // (N joins NW and NE through its own W link and NE's)
+        if (lx > 0 && ((row >> (lx - 1)) & 1ull)) region_unite(s_lab, c, c - 1u);
+        if ((up >> lx) & 1ull) region_unite(s_lab, c, c - FRT_T);                // (N joins NW and NE through its own W link and NE's)
         else {
-            if (lx > 0 && ((up >> (lx - 1)) & 1ull)) front_unite(s_lab, c, c - FRT_T - 1u);
-            if (lx < FRT_T - 1 && ((up >> (lx + 1)) & 1ull)) front_unite(s_lab, c, c - FRT_T + 1u);
+            if (lx > 0 && ((up >> (lx - 1)) & 1ull)) region_unite(s_lab, c, c - FRT_T - 1u);
+            if (lx < FRT_T - 1 && ((up >> (lx + 1)) & 1ull)) region_unite(s_lab, c, c - FRT_T + 1u);
         }
     }
     __syncthreads();
     for (uint32_t b = mine; b; b &= b - 1u) {
         const int32_t lx = c0 + __builtin_ctz(b);
-        const uint32_t root = front_find(s_lab, (uint32_t)(r * FRT_T + lx));
+        const uint32_t root = region_find(s_lab, (uint32_t)(r * FRT_T + lx));
         label[(size_t)(y0 + r) * (size_t)W + (size_t)(x0 + lx)] = (uint32_t)(y0 + (int32_t)(root >> 6)) * (uint32_t)W + (uint32_t)(x0 + (int32_t)(root & 63u));
     }
 }
@@ -149,7 +129,7 @@ k_front_merge(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int3
     const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x;
     for (int32_t d = -1; d <= 1; d++) {
         const int32_t ox = column ? x - 1 : x + d, oy = column ? y + d : y - 1;
-        if (bit(ox, oy)) front_unite(label, c, (uint32_t)oy * (uint32_t)W + (uint32_t)ox);
+        if (bit(ox, oy)) region_unite(label, c, (uint32_t)oy * (uint32_t)W + (uint32_t)ox);
     }
 }
 
@@ -164,7 +144,7 @@ k_front_flatten(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, in
     bool root = false;
     if ((bits >> lane) & 1ull) {
         const int32_t y = (int32_t)(word / wpr64), x = (int32_t)(word - (int64_t)y * wpr64) * 64 + lane;
-        const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x, r = front_find(label, c);
+        const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x, r = region_find(label, c);
         if (r != c) __atomic_store_n(label + c, r, __ATOMIC_RELAXED);           // (another lane's chase reads the old parent or the root: both lead there)
         root = r == c;
     }
@@ -173,56 +153,6 @@ k_front_flatten(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, in
         roots[word] = rb;
         wcount[word] = (uint32_t)__popcll(rb);
     }
-}
-
-// vals [n] -> the exclusive prefix of each within its block of FRT_SCAN, in place; sums [blocks] the blocks' totals.  n = n_cap, or --
-// n_dev -- min(*n_dev, n_cap); what lies behind n counts as 0 and is neither read nor written
-__global__ void __launch_bounds__(FRT_NT)
-k_front_scan_blocks(uint32_t *__restrict__ vals, const uint32_t *__restrict__ n_dev, int64_t n_cap, uint32_t *__restrict__ sums) {
-    __shared__ uint32_t s[FRT_NT];
-    const int32_t t = (int32_t)threadIdx.x;
-    const int64_t n = n_dev ? std::min<int64_t>((int64_t)*n_dev, n_cap) : n_cap, base = (int64_t)blockIdx.x * FRT_SCAN + t * 4;
-    uint32_t v[4], mine = 0u;
-    for (int32_t k = 0; k < 4; k++) {
-        v[k] = base + k < n ? vals[base + k] : 0u;
-        mine += v[k];
-    }
-    s[t] = mine;
-    __syncthreads();
-    for (int32_t off = 1; off < FRT_NT; off <<= 1) {
-        const uint32_t add = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    uint32_t run = s[t] - mine;
-    for (int32_t k = 0; k < 4; k++) {
-        if (base + k < n) vals[base + k] = run;
-        run += v[k];
-    }
-    if (t == FRT_NT - 1) sums[blockIdx.x] = s[t];
-}
-// ONE workgroup: sums [nb] -> their exclusive prefix in place, the total into *total
-__global__ void __launch_bounds__(FRT_NT)
-k_front_scan_top(uint32_t *__restrict__ sums, int32_t nb, uint32_t *__restrict__ total) {
-    __shared__ uint32_t s[FRT_NT];
-    const int32_t t = (int32_t)threadIdx.x;
-    uint32_t carry = 0u;
-    for (int32_t base = 0; base < nb; base += FRT_NT) {
-        const uint32_t v = base + t < nb ? sums[base + t] : 0u;
-        s[t] = v;
-        __syncthreads();
-        for (int32_t off = 1; off < FRT_NT; off <<= 1) {
-            const uint32_t add = t >= off ? s[t - off] : 0u;
-            __syncthreads();
-            s[t] += add;
-            __syncthreads();
-        }
-        if (base + t < nb) sums[base + t] = carry + s[t] - v;
-        carry += s[FRT_NT - 1];
-        __syncthreads();
-    }
-    if (t == 0) *total = carry;
 }
 
 // the first min(ctl[0], cap) entries of the table
@@ -235,17 +165,6 @@ k_front_table_init(gms_frontier *__restrict__ rec, unsigned long long *__restric
     }
 }
 
-// the minimum over the wavefront
-__device__ __forceinline__ uint64_t front_wave_min(uint64_t v) {
-#define GMS_STEP_(O)                                                                                                       \
-    {                                                                                                                      \
-        const uint64_t o = ((uint64_t)wave_xor<O>((uint32_t)(v >> 32)) << 32) | (uint64_t)wave_xor<O>((uint32_t)v);        \
-        v = o < v ? o : v;                                                                                                 \
-    }
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    return v;
-}
 // the sum of the positions of mask's set bits
 __device__ __forceinline__ uint32_t front_bit_sum(uint64_t mask) {
     return (uint32_t)__popcll(mask & 0xaaaaaaaaaaaaaaaaull) + 2u * (uint32_t)__popcll(mask & 0xccccccccccccccccull) +
@@ -271,7 +190,7 @@ k_front_reduce(const uint64_t *__restrict__ plane, const uint64_t *__restrict__ 
         const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x, r = label[c];
         const uint32_t ry = r / (uint32_t)W, rx = r - ry * (uint32_t)W;
         const size_t rw = (size_t)ry * (size_t)wpr64 + (size_t)(rx >> 6);
-        region = wblocks[rw / FRT_SCAN] + wscan[rw] + (uint32_t)__popcll(roots[rw] & ((1ull << (rx & 63u)) - 1ull));
+        region = scan_prefix(wscan, wblocks, rw) + (uint32_t)__popcll(roots[rw] & ((1ull << (rx & 63u)) - 1ull));
         if (region >= (uint32_t)cap) region = FRT_NONE;
         else if (r == c) { rec[region].anchor_x = x; rec[region].anchor_y = y; }                  // (the root alone writes these)
         if (cost) {
@@ -279,27 +198,20 @@ k_front_reduce(const uint64_t *__restrict__ plane, const uint64_t *__restrict__ 
             if (v != (uint32_t)GMS_REACH_FAR) key = ((uint64_t)v << 32) | c;
         }
     }
-    uint64_t todo = __ballot(region != FRT_NONE);
-    while (todo) {                                                              // (uniform: one turn per distinct region of the word)
-        const int32_t leader = __builtin_ctzll(todo);
-        const uint32_t R = (uint32_t)__shfl((int)region, leader);
-        const bool in = region == R;
-        const uint64_t grp = __ballot(in);
-        const uint64_t best = cost ? front_wave_min(in ? key : FRT_NO_GOAL) : FRT_NO_GOAL;
-        if (lane == leader) {
-            const int32_t n = __popcll(grp);
-            gms_frontier *q = rec + R;
-            atomicAdd(&q->count, n);
-            atomicMin(&q->min_x, xw + __builtin_ctzll(grp));
-            atomicMax(&q->max_x, xw + 63 - __builtin_clzll(grp));
-            atomicMin(&q->min_y, y);
-            atomicMax(&q->max_y, y);
-            atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + front_bit_sum(grp)));
-            atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_y), (unsigned long long)((int64_t)n * y));
-            if (best != FRT_NO_GOAL) atomicMin(goal + R, (unsigned long long)best);
-        }
-        todo &= ~grp;
-    }
+    wave_each_key(region, FRT_NONE, [&](uint32_t R, bool in, uint64_t grp, bool leader) {
+        const uint64_t best = cost ? wave_min(in ? key : (uint64_t)FRT_NO_GOAL) : FRT_NO_GOAL;
+        if (!leader) return;
+        const int32_t n = __popcll(grp);
+        gms_frontier *q = rec + R;
+        atomicAdd(&q->count, n);
+        atomicMin(&q->min_x, xw + __builtin_ctzll(grp));
+        atomicMax(&q->max_x, xw + 63 - __builtin_clzll(grp));
+        atomicMin(&q->min_y, y);
+        atomicMax(&q->max_y, y);
+        atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + front_bit_sum(grp)));
+        atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_y), (unsigned long long)((int64_t)n * y));
+        if (best != FRT_NO_GOAL) atomicMin(goal + R, (unsigned long long)best);
+    });
 }
 
 // the goals decoded; kept [i] = count >= min_size
@@ -326,7 +238,7 @@ k_front_emit(const gms_frontier *__restrict__ rec, const uint32_t *__restrict__ 
     const int64_t n = std::min<int64_t>((int64_t)ctl[0], cap);
     for (int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FRT_NT) {
         if (rec[i].count < min_size) continue;
-        const uint32_t at = kblocks[i / FRT_SCAN] + kept[i];
+        const uint32_t at = scan_prefix(kept, kblocks, i);
         if (at < (uint32_t)out_cap) out[at] = rec[i];
     }
 }
@@ -359,7 +271,7 @@ static int front_args(const gms_frontiers *f, int32_t W, int32_t H, const uint16
 }
 
 static inline size_t front_table_bytes(int32_t cap) {
-    return (size_t)cap * (sizeof(gms_frontier) + sizeof(uint64_t) + sizeof(uint32_t)) + ((size_t)cap / FRT_SCAN + 1) * sizeof(uint32_t);
+    return (size_t)cap * (sizeof(gms_frontier) + sizeof(uint64_t) + sizeof(uint32_t)) + ((size_t)cap / GMS_SCAN + 1) * sizeof(uint32_t);
 }
 struct FrontTable {
     gms_frontier *rec;
@@ -377,16 +289,9 @@ static inline FrontTable front_table(const gms_map *m) {
 }
 // a table of at least `need` regions (nothing of the handle's is in flight on it: the caller has waited)
 static int front_table_grow(gms_map *m, int64_t need) {
-    if (m->d_front_table && m->front_cap >= need) return GMS_OK;
-    const int64_t cap = (std::max<int64_t>(need, FRT_CAP0) + FRT_SCAN - 1) / FRT_SCAN * FRT_SCAN;
+    const int64_t cap = (std::max<int64_t>(need, FRT_CAP0) + GMS_SCAN - 1) / GMS_SCAN * GMS_SCAN;
     if (cap > INT_MAX / 2) return gms_fail(GMS_ERR_NOMEM, "gms_frontiers: a table of %lld regions", (long long)cap);
-    hipFree(m->d_front_table);
-    m->d_front_table = nullptr;
-    m->front_cap = 0;
-    int rc = gms_dev_alloc(&m->d_front_table, front_table_bytes((int32_t)cap), "gms_frontiers", "the region table");
-    if (rc) return rc;
-    m->front_cap = (int32_t)cap;
-    return GMS_OK;
+    return gms_dev_grow(&m->d_front_table, &m->front_cap, cap, GMS_SCAN, nullptr, [](size_t c) { return front_table_bytes((int32_t)c); }, "gms_frontiers", "the region table");
 }
 
 // what a request needs on the handle (a handle's W and H never change: only the table ever grows)
@@ -394,18 +299,13 @@ static int front_buffers(gms_map *m, bool per_particle) {
     const size_t plane_bytes = (size_t)m->gd.H * (size_t)gms_plane_wpr(m) * sizeof(uint32_t), words = plane_bytes / sizeof(uint64_t);
     int rc = gms_dev_alloc(&m->d_front_plane, 2 * plane_bytes, "gms_frontiers", "the frontier plane and the root plane");
     if (!rc) rc = gms_dev_alloc(&m->d_front_label, (size_t)m->gd.cells * sizeof(uint32_t), "gms_frontiers", "the label field");
-    if (!rc) rc = gms_dev_alloc(&m->d_front_wscan, (words + words / FRT_SCAN + 1) * sizeof(uint32_t), "gms_frontiers", "the root plane's scan");
+    if (!rc) rc = gms_dev_alloc(&m->d_front_wscan, (words + words / GMS_SCAN + 1) * sizeof(uint32_t), "gms_frontiers", "the root plane's scan");
     if (!rc) rc = gms_dev_alloc(&m->d_front_ctl, 2 * sizeof(uint32_t), "gms_frontiers", "the region counts");
     if (!rc && per_particle) rc = gms_dev_alloc(&m->d_front_nf, plane_bytes, "gms_frontiers", "the particle's second plane");
     if (!rc) rc = front_table_grow(m, FRT_CAP0);
-    if (!rc && !m->h_front_ctl && hipHostMalloc(reinterpret_cast<void **>(&m->h_front_ctl), 2 * sizeof(uint32_t)) != hipSuccess) {
-        m->h_front_ctl = nullptr;
-        rc = gms_fail(GMS_ERR_NOMEM, "gms_frontiers: pinned memory for the read-back could not be allocated");
-    }
+    if (!rc) rc = gms_pinned_alloc(&m->h_front_ctl, 2 * sizeof(uint32_t), "gms_frontiers");
     return rc;
 }
-
-static inline unsigned front_grid(int64_t n, int64_t per_block, int64_t most) { return (unsigned)std::max<int64_t>(1, std::min(most, (n + per_block - 1) / per_block)); }
 
 // The regions of ONE map's two planes (of logData as it stands) into the caller's device buffers; the handle's buffers exist.  Waits
 // on the stream once -- twice where the table has to grow -- and leaves the numbers of regions in h_front_ctl.
@@ -418,7 +318,7 @@ static int front_run(gms_map *m, const uint32_t *d_occ, const uint32_t *d_nf, co
         int rc = gms_reach_inflate(m, d_occ, f->inflate, GMS_CLEAR_OCCUPIED, &d_blocked);
         if (rc) return rc;
     }
-    const int64_t words = (int64_t)H * wpr64, wblocks_n = (words + FRT_SCAN - 1) / FRT_SCAN;
+    const int64_t words = (int64_t)H * wpr64;
     uint64_t *plane = reinterpret_cast<uint64_t *>(m->d_front_plane), *roots = plane + words;
     uint32_t *wscan = m->d_front_wscan, *wblocks = wscan + words, *ctl = m->d_front_ctl, *label = m->d_front_label;
     hipStream_t st = m->stream;
@@ -430,23 +330,21 @@ static int front_run(gms_map *m, const uint32_t *d_occ, const uint32_t *d_nf, co
         hipLaunchKernelGGL(k_front_merge, dim3((unsigned)((border + FRT_NT - 1) / FRT_NT)), dim3(FRT_NT), 0, st, plane, wpr64, W, H, ntx, nty, label);
     const unsigned word_waves = (unsigned)((words + FRT_NT / 64 - 1) / (FRT_NT / 64));
     hipLaunchKernelGGL(k_front_flatten, dim3(word_waves), dim3(FRT_NT), 0, st, plane, wpr64, W, H, label, roots, wscan);
-    hipLaunchKernelGGL(k_front_scan_blocks, dim3((unsigned)wblocks_n), dim3(FRT_NT), 0, st, wscan, (const uint32_t *)nullptr, words, wblocks);
-    hipLaunchKernelGGL(k_front_scan_top, dim3(1), dim3(FRT_NT), 0, st, wblocks, (int32_t)wblocks_n, ctl);
+    gms_launch_scan(st, wscan, nullptr, words, wblocks, ctl);
     HIPCHK(hipGetLastError());
     if (d_labels) {
         const int64_t n = (int64_t)f->w * f->h;
-        hipLaunchKernelGGL(k_front_labels, dim3(front_grid(n, FRT_NT, 4096)), dim3(FRT_NT), 0, st, plane, wpr64, label, W, f->x0, f->y0, f->w, f->h, d_labels);
+        hipLaunchKernelGGL(k_front_labels, dim3(gms_grid(n, FRT_NT, 4096)), dim3(FRT_NT), 0, st, plane, wpr64, label, W, f->x0, f->y0, f->w, f->h, d_labels);
         HIPCHK(hipGetLastError());
     }
     for (int32_t pass = 0;; pass++) {
         const int32_t tcap = m->front_cap;
         const FrontTable t = front_table(m);
-        const unsigned tgrid = front_grid(tcap, FRT_NT, 1024);
+        const unsigned tgrid = gms_grid(tcap, FRT_NT, 1024);
         hipLaunchKernelGGL(k_front_table_init, dim3(tgrid), dim3(FRT_NT), 0, st, t.rec, t.goal, ctl, tcap);
         hipLaunchKernelGGL(k_front_reduce, dim3(word_waves), dim3(FRT_NT), 0, st, plane, roots, wscan, wblocks, wpr64, W, H, label, d_cost, t.rec, t.goal, tcap);
         hipLaunchKernelGGL(k_front_finish, dim3(tgrid), dim3(FRT_NT), 0, st, t.rec, t.goal, ctl, tcap, f->min_size, W, t.kept);
-        hipLaunchKernelGGL(k_front_scan_blocks, dim3((unsigned)(tcap / FRT_SCAN)), dim3(FRT_NT), 0, st, t.kept, ctl, (int64_t)tcap, t.kblocks);
-        hipLaunchKernelGGL(k_front_scan_top, dim3(1), dim3(FRT_NT), 0, st, t.kblocks, tcap / FRT_SCAN, ctl + 1);
+        gms_launch_scan(st, t.kept, ctl, tcap, t.kblocks, ctl + 1);
         if (cap > 0) hipLaunchKernelGGL(k_front_emit, dim3(tgrid), dim3(FRT_NT), 0, st, t.rec, t.kept, t.kblocks, ctl, tcap, f->min_size, d_records, cap);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(m->h_front_ctl, ctl, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -136,7 +136,7 @@ struct gms_map {
     uint32_t *d_front_plane;      // [2][H][gms_plane_wpr] the frontier plane, and the plane of the regions' roots (label == own index)
     uint32_t *d_front_nf;         // [H][gms_plane_wpr] a gms_slam's: the shown particle's second plane (its first: d_clear_scratch)
     uint32_t *d_front_label;      // [H][W] the label field of the whole map; defined where the frontier plane has a bit
-    uint32_t *d_front_wscan;      // [words] the root plane's word counts, scanned within blocks of FRT_SCAN | [blocks] the blocks' offsets
+    uint32_t *d_front_wscan;      // [words] the root plane's word counts, scanned within blocks of GMS_SCAN | [blocks] the blocks' offsets
     unsigned char *d_front_table; // [front_cap] gms_frontier | [front_cap] the goals' 64-bit keys | [front_cap] the kept flags, scanned | [blocks] their offsets
     int32_t front_cap;            // regions the table holds
     uint32_t *d_front_ctl;        // {regions, regions with count >= min_size}
@@ -560,6 +560,45 @@ static inline int gms_dev_alloc(T **p, size_t bytes, const char *who, const char
     }
     return GMS_OK;
 }
+// its pinned counterpart, for the words a request reads back: *p stays what it is, or becomes `bytes` of pinned host memory
+template <typename T>
+static inline int gms_pinned_alloc(T **p, size_t bytes, const char *who) {
+    if (*p) return GMS_OK;
+    if (hipHostMalloc(reinterpret_cast<void **>(p), bytes) != hipSuccess) {
+        *p = nullptr;
+        return gms_fail(GMS_ERR_NOMEM, "%s: pinned memory for the read-back could not be allocated", who);
+    }
+    return GMS_OK;
+}
+// The one grow-only device buffer: *p keeps holding at least `need` items (*cap: how many it holds), or is replaced by one of `need`
+// rounded up to a multiple of `round` items, bytes(items) bytes; it never shrinks.  wait: the stream whose work may still read the old
+// buffer, waited on before that is freed, or NULL where the caller knows that nothing is in flight on it.
+template <typename T, typename C, typename F>
+static inline int gms_dev_grow(T **p, C *cap, int64_t need, int64_t round, const hipStream_t *wait, F bytes, const char *who, const char *what) {
+    if (*p && (int64_t)*cap >= need) return GMS_OK;
+    if (*p && wait) HIPCHK(hipStreamSynchronize(*wait));
+    hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const int64_t c = (need + round - 1) / round * round;
+    int rc = gms_dev_alloc(p, bytes((size_t)c), who, what);
+    if (!rc) *cap = (C)c;
+    return rc;
+}
+// workgroups for n items at per_block each: at least one, at most `most` (the kernels stride over the rest)
+static inline unsigned gms_grid(int64_t n, int64_t per_block, int64_t most) {
+    const int64_t b = (n + per_block - 1) / per_block;
+    return (unsigned)(b < 1 ? 1 : b > most ? most : b);
+}
+// The exclusive scan of uint32 counts (gms_query.hip), two launches on st, no workgroup waits on another.  vals [n]: every item becomes
+// the sum of those before it within its block of GMS_SCAN items, in place; sums [blocks = ceil(n_cap / GMS_SCAN)]: every block's
+// offset, the sum of the blocks before it; *total: the sum of all -- so item i's prefix is sums[i / GMS_SCAN] + vals[i] (scan_prefix).
+// n = n_cap, or -- n_dev, a count in device memory -- min(*n_dev, n_cap); what lies behind n counts as 0 and is neither read nor
+// written.  batch > 1: as many scans at once, entry b's items at vals + b * stride, its offsets at sums + b * sum_stride, its total in
+// total[b].  Any number of blocks: the second launch, one workgroup per entry, walks them GMS_SCAN at a time with a carry.
+#define GMS_SCAN 1024
+void gms_launch_scan(hipStream_t st, uint32_t *vals, const uint32_t *n_dev, int64_t n_cap, uint32_t *sums, uint32_t *total, int32_t batch = 1,
+                     int64_t stride = 0, int64_t sum_stride = 0);
 // a bit plane's 32-bit words per row (rows padded to 64 cells)
 static inline int32_t gms_plane_wpr(const gms_map *m) { return 2 * ((m->gd.W + 63) / 64); }
 // the plane of `mode` of logData as it stands, every map's: the deferred apply pass first, then the pre-pass unless the handle still

@@ -296,10 +296,7 @@ static int loc_buffers(gms_map *m, int32_t L) {
     const size_t words = (size_t)m->gd.H * (size_t)((m->gd.W + 63) / 64);
     int rc = gms_dev_alloc(&t.d_ctl, (LOC_CTL_WORDS + GMS_MAX_BEAMS + 1) * sizeof(uint32_t), "gms_locate", "the control words and the histogram");
     if (!rc && L > 0) rc = gms_dev_alloc(&t.d_pyr, LOC_MAX_LEVEL * words * sizeof(uint64_t), "gms_locate", "the OR pyramid");
-    if (!rc && !t.h_ctl && hipHostMalloc(reinterpret_cast<void **>(&t.h_ctl), LOC_CTL_WORDS * sizeof(uint32_t)) != hipSuccess) {
-        t.h_ctl = nullptr;
-        rc = gms_fail(GMS_ERR_NOMEM, "gms_locate: pinned memory for the read-back could not be allocated");
-    }
+    if (!rc) rc = gms_pinned_alloc(&t.h_ctl, LOC_CTL_WORDS * sizeof(uint32_t), "gms_locate");
     return rc;
 }
 

@@ -8,19 +8,19 @@
 //
 //   k_modes_clear       a lane per bin: count 0, label = own index; the three counters cleared.
 //   k_modes_bin         (1) a lane per particle: its bin (gms_map_clearance_poses' cell rule, the heading from one double multiply and a
-//                       floor) stored, the bin's count raised -- the lanes of a wavefront that share a bin combined first, ONE atomic
+//                       floor) stored, the bin's count raised -- the lanes of a wavefront that share a bin combined first (wave_each_key), ONE atomic
 //                       per distinct bin -- and the OUTSIDE particles counted, one atomic per wavefront.
 //   k_modes_unite       (2) a lane per bin: an occupied bin is united with its 13 forward neighbours -- 4 in its own heading layer, the
-//                       9 of layer bt + 1 mod n_theta -- in the global label field (modes_unite: the frontier regions' lock-free rule,
-//                       the larger root always under the smaller, so the final root is the anchor).  n_theta == 2 meets every
+//                       9 of layer bt + 1 mod n_theta -- in the global label field (region_unite, gms_regions.h: the larger root
+//                       always under the smaller, so the final root is the anchor).  n_theta == 2 meets every
 //                       cross-layer pair from both sides, which a union does not mind; n_theta == 1 has no other layer.
 //   k_modes_flatten     (3) every occupied bin chases to its root and stores it; "I am my own root" is the bin's flag.
-//   k_modes_scan_*      exclusive scan of the flags (blocks of MOD_SCAN in one launch, the blocks' sums in a second, single workgroup):
-//                       the roots in linear order = the modes in anchor order; the total is the number of modes.
+//   gms_launch_scan     the exclusive scan of the flags (gms_query.hip): the roots in linear order = the modes in anchor order; the
+//                       total is the number of modes.
 //   k_modes_table_init, k_modes_reduce, k_modes_finish
 //                       (4) the table: a wavefront per 64 bins looks up every occupied bin's mode, and the lanes that share one combine
-//                       (count, bins, box: butterflies over the group) before ONE lane issues the atomics -- integer min / max / add
-//                       only.  The finish flags count >= min_count; k_modes_scan_* again, then k_modes_emit stores the kept modes'
+//                       (wave_each_key; count, bins, box: butterflies over the group) before ONE lane issues the atomics -- integer
+//                       min / max / add only.  The finish flags count >= min_count; the scan again, then k_modes_emit stores the kept modes'
 //                       integers in order, the first `cap` of them, and each stored record's anchor index for step 6.
 //   k_modes_labels      (5) a lane per particle: the root of its bin, or GMS_MODE_NONE.
 //   k_modes_sums        (6) one workgroup of 256 lanes per STORED record: lane l walks the particles l, l + 256, ... in ascending order
@@ -37,10 +37,9 @@
 
 #include <algorithm>
 
-#include "gms_device.h"
+#include "gms_regions.h"
 
 #define MOD_NT 256
-#define MOD_SCAN 1024                    // items a workgroup of k_modes_scan_blocks scans
 #define MOD_NONE 0xffffffffu
 #define MOD_MAX_BINS ((int64_t)1 << 22)
 #define MOD_AHEAD 8                      // labels k_modes_sums loads ahead of its adds
@@ -61,26 +60,6 @@ struct ModesDev {
     int32_t bin_cells, n_theta, BW, BH, NB;
     double k;                            // (double)n_theta * 0.15915494309189535, rounded once on the host
 };
-
-__device__ __forceinline__ uint32_t modes_find(const uint32_t *L, uint32_t a) {
-    for (;;) {
-        const uint32_t p = __atomic_load_n(L + a, __ATOMIC_RELAXED);
-        if (p == a) return a;
-        a = p;
-    }
-}
-// gms_frontier.hip's front_unite: a label only ever decreases and never exceeds its own index, so chains end and nobody waits
-__device__ __forceinline__ void modes_unite(uint32_t *L, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = modes_find(L, a);
-        b = modes_find(L, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(L + a, b);                               // the larger root under the smaller
-        if (old == a) return;
-        a = old;                                                                // a had moved: unite what it moved to
-    }
-}
 
 __global__ void __launch_bounds__(MOD_NT)
 k_modes_clear(uint32_t *__restrict__ cnt, uint32_t *__restrict__ lab, int32_t NB, uint32_t *__restrict__ ctl) {
@@ -109,14 +88,9 @@ k_modes_bin(GridDev g, ModesDev q, const float *__restrict__ pose, int32_t n, ui
     }
     const uint64_t out = __ballot(i < n && bin == MOD_NONE);
     if (lane == 0 && out) atomicAdd(ctl + 2, (uint32_t)__popcll(out));
-    uint64_t todo = __ballot(bin != MOD_NONE);
-    while (todo) {                                                              // (uniform: one turn per distinct bin of the wavefront)
-        const int32_t leader = __builtin_ctzll(todo);
-        const uint32_t B = (uint32_t)__shfl((int)bin, leader);
-        const uint64_t grp = __ballot(bin == B);
-        if (lane == leader) atomicAdd(cnt + B, (uint32_t)__popcll(grp));
-        todo &= ~grp;
-    }
+    wave_each_key(bin, MOD_NONE, [&](uint32_t B, bool, uint64_t grp, bool leader) {
+        if (leader) atomicAdd(cnt + B, (uint32_t)__popcll(grp));
+    });
 }
 
 __global__ void __launch_bounds__(MOD_NT)
@@ -127,7 +101,7 @@ k_modes_unite(ModesDev q, const uint32_t *__restrict__ cnt, uint32_t *lab) {
     auto join = [&](int32_t ox, int32_t oy, int32_t ot) {
         if (ox < 0 || ox >= q.BW || oy < 0 || oy >= q.BH) return;
         const int32_t o = (ot * q.BH + oy) * q.BW + ox;
-        if (cnt[o] != 0u) modes_unite(lab, (uint32_t)b, (uint32_t)o);
+        if (cnt[o] != 0u) region_unite(lab, (uint32_t)b, (uint32_t)o);
     };
     join(bx + 1, by, bt);
     for (int32_t dx = -1; dx <= 1; dx++) join(bx + dx, by + 1, bt);
@@ -144,61 +118,11 @@ k_modes_flatten(const uint32_t *__restrict__ cnt, uint32_t *lab, int32_t NB, uin
     if (b >= NB) return;
     uint32_t root = 0u;
     if (cnt[b] != 0u) {
-        const uint32_t r = modes_find(lab, (uint32_t)b);
+        const uint32_t r = region_find(lab, (uint32_t)b);
         if (r != (uint32_t)b) __atomic_store_n(lab + b, r, __ATOMIC_RELAXED);   // (another lane's chase reads the old parent or the root: both lead there)
         root = r == (uint32_t)b ? 1u : 0u;
     }
     flag[b] = root;
-}
-
-// vals [n] -> the exclusive prefix of each within its block of MOD_SCAN, in place; sums [blocks] the blocks' totals.  n = n_cap, or --
-// n_dev -- min(*n_dev, n_cap); what lies behind n counts as 0 and is neither read nor written
-__global__ void __launch_bounds__(MOD_NT)
-k_modes_scan_blocks(uint32_t *__restrict__ vals, const uint32_t *__restrict__ n_dev, int32_t n_cap, uint32_t *__restrict__ sums) {
-    __shared__ uint32_t s[MOD_NT];
-    const int32_t t = (int32_t)threadIdx.x;
-    const int32_t n = n_dev ? (int32_t)std::min<uint32_t>(*n_dev, (uint32_t)n_cap) : n_cap, base = (int32_t)blockIdx.x * MOD_SCAN + t * 4;
-    uint32_t v[4], mine = 0u;
-    for (int32_t k = 0; k < 4; k++) {
-        v[k] = base + k < n ? vals[base + k] : 0u;
-        mine += v[k];
-    }
-    s[t] = mine;
-    __syncthreads();
-    for (int32_t off = 1; off < MOD_NT; off <<= 1) {
-        const uint32_t add = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    uint32_t run = s[t] - mine;
-    for (int32_t k = 0; k < 4; k++) {
-        if (base + k < n) vals[base + k] = run;
-        run += v[k];
-    }
-    if (t == MOD_NT - 1) sums[blockIdx.x] = s[t];
-}
-// ONE workgroup: sums [nb] -> their exclusive prefix in place, the total into *total
-__global__ void __launch_bounds__(MOD_NT)
-k_modes_scan_top(uint32_t *__restrict__ sums, int32_t nb, uint32_t *__restrict__ total) {
-    __shared__ uint32_t s[MOD_NT];
-    const int32_t t = (int32_t)threadIdx.x;
-    uint32_t carry = 0u;
-    for (int32_t base = 0; base < nb; base += MOD_NT) {
-        const uint32_t v = base + t < nb ? sums[base + t] : 0u;
-        s[t] = v;
-        __syncthreads();
-        for (int32_t off = 1; off < MOD_NT; off <<= 1) {
-            const uint32_t add = t >= off ? s[t - off] : 0u;
-            __syncthreads();
-            s[t] += add;
-            __syncthreads();
-        }
-        if (base + t < nb) sums[base + t] = carry + s[t] - v;
-        carry += s[MOD_NT - 1];
-        __syncthreads();
-    }
-    if (t == 0) *total = carry;
 }
 
 // the first min(ctl[0], tcap) rows
@@ -209,30 +133,11 @@ k_modes_table_init(ModeRow *__restrict__ row, const uint32_t *__restrict__ ctl, 
         row[i] = ModeRow{0, 0, 0, 0, 0, -1, INT_MAX, INT_MAX, -1, -1};
 }
 
-__device__ __forceinline__ int32_t modes_wave_add(int32_t v) {
-#define GMS_STEP_(O) v += wave_xor<O>(v);
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    return v;
-}
-__device__ __forceinline__ int32_t modes_wave_min(int32_t v) {
-#define GMS_STEP_(O) v = min(v, wave_xor<O>(v));
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    return v;
-}
-__device__ __forceinline__ int32_t modes_wave_max(int32_t v) {
-#define GMS_STEP_(O) v = max(v, wave_xor<O>(v));
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    return v;
-}
-
 // a wavefront per 64 bins.  num / nblk: the scan of the root flags; modes behind tcap are left out (there are none: see the head)
 __global__ void __launch_bounds__(MOD_NT)
 k_modes_reduce(ModesDev q, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ lab, const uint32_t *__restrict__ num, const uint32_t *__restrict__ nblk,
                ModeRow *row, int32_t tcap) {
-    const int32_t b = (int32_t)blockIdx.x * MOD_NT + (int32_t)threadIdx.x, lane = (int32_t)threadIdx.x & 63;
+    const int32_t b = (int32_t)blockIdx.x * MOD_NT + (int32_t)threadIdx.x;
     const int32_t c = b < q.NB ? (int32_t)cnt[b] : 0;
     uint32_t mode = MOD_NONE;
     int32_t bx = 0, by = 0;
@@ -240,30 +145,23 @@ k_modes_reduce(ModesDev q, const uint32_t *__restrict__ cnt, const uint32_t *__r
         const uint32_t r = lab[b];
         bx = b % q.BW;
         by = (b / q.BW) % q.BH;
-        mode = nblk[r / MOD_SCAN] + num[r];
+        mode = scan_prefix(num, nblk, r);
         if (mode >= (uint32_t)tcap) mode = MOD_NONE;
         else if (r == (uint32_t)b) { row[mode].anchor_bx = bx; row[mode].anchor_by = by; row[mode].anchor_bt = b / (q.BW * q.BH); }   // (the root alone writes these)
     }
-    uint64_t todo = __ballot(mode != MOD_NONE);
-    while (todo) {                                                              // (uniform: one turn per distinct mode of the wavefront)
-        const int32_t leader = __builtin_ctzll(todo);
-        const uint32_t R = (uint32_t)__shfl((int)mode, leader);
-        const bool in = mode == R;
-        const uint64_t grp = __ballot(in);
-        const int32_t members = modes_wave_add(in ? c : 0);
-        const int32_t lo_x = modes_wave_min(in ? bx : INT_MAX), lo_y = modes_wave_min(in ? by : INT_MAX);
-        const int32_t hi_x = modes_wave_max(in ? bx : -1), hi_y = modes_wave_max(in ? by : -1);
-        if (lane == leader) {
-            ModeRow *m = row + R;
-            atomicAdd(&m->count, members);
-            atomicAdd(&m->bins, (int32_t)__popcll(grp));
-            atomicMin(&m->min_bx, lo_x);
-            atomicMin(&m->min_by, lo_y);
-            atomicMax(&m->max_bx, hi_x);
-            atomicMax(&m->max_by, hi_y);
-        }
-        todo &= ~grp;
-    }
+    wave_each_key(mode, MOD_NONE, [&](uint32_t R, bool in, uint64_t grp, bool leader) {
+        const int32_t members = wave_add(in ? c : 0);
+        const int32_t lo_x = wave_min(in ? bx : INT_MAX), lo_y = wave_min(in ? by : INT_MAX);
+        const int32_t hi_x = wave_max(in ? bx : -1), hi_y = wave_max(in ? by : -1);
+        if (!leader) return;
+        ModeRow *m = row + R;
+        atomicAdd(&m->count, members);
+        atomicAdd(&m->bins, (int32_t)__popcll(grp));
+        atomicMin(&m->min_bx, lo_x);
+        atomicMin(&m->min_by, lo_y);
+        atomicMax(&m->max_bx, hi_x);
+        atomicMax(&m->max_by, hi_y);
+    });
 }
 
 // kept [i] = count >= min_count
@@ -281,7 +179,7 @@ k_modes_emit(ModesDev q, const ModeRow *__restrict__ row, const uint32_t *__rest
     for (int32_t i = (int32_t)blockIdx.x * MOD_NT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * MOD_NT) {
         const ModeRow r = row[i];
         if (r.count < min_count) continue;
-        const uint32_t at = kblocks[i / MOD_SCAN] + kept[i];
+        const uint32_t at = scan_prefix(kept, kblocks, i);
         if (at >= (uint32_t)out_cap) continue;
         gms_mode *o = out + at;
         o->anchor_bx = r.anchor_bx; o->anchor_by = r.anchor_by; o->anchor_bt = r.anchor_bt;
@@ -385,34 +283,16 @@ static inline ModesTable modes_table(const gms_pf *pf) {
     t.kblocks = t.anchors + cap;
     return t;
 }
-// *p of at least `need` items of `bytes(cap)` bytes; it grows (behind a wait on the stream) and never shrinks
-template <typename T, typename F>
-static int modes_grow(gms_pf *pf, T **p, int64_t *cap, int64_t need, F bytes, const char *what) {
-    if (*p && *cap >= need) return GMS_OK;
-    if (*p) HIPCHK(hipStreamSynchronize(pf->map->stream));
-    hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const int64_t c = (need + MOD_SCAN - 1) / MOD_SCAN * MOD_SCAN;
-    int rc = gms_dev_alloc(p, bytes((size_t)c), "gms_pf_modes", what);
-    if (rc) return rc;
-    *cap = c;
-    return GMS_OK;
-}
 static int modes_buffers(gms_pf *pf, int64_t NB, int64_t rows) {
     auto &s = pf->modes;
     int rc = gms_dev_alloc(&s.d_part, 2 * (size_t)pf->n * sizeof(uint32_t), "gms_pf_modes", "the particles' bins and labels");
     if (!rc) rc = gms_dev_alloc(&s.d_ctl, 4 * sizeof(uint32_t), "gms_pf_modes", "the counters");
-    if (!rc) rc = modes_grow(pf, &s.d_bins, &s.bins_cap, NB, [](size_t c) { return (3 * c + c / MOD_SCAN + 1) * sizeof(uint32_t); }, "the bin counts, the label field and its scan");
-    if (!rc) rc = modes_grow(pf, &s.d_table, &s.table_cap, rows, [](size_t c) { return c * (sizeof(ModeRow) + 2 * sizeof(uint32_t)) + (c / MOD_SCAN + 1) * sizeof(uint32_t); }, "the mode table");
-    if (!rc && !s.h_ctl && hipHostMalloc(reinterpret_cast<void **>(&s.h_ctl), 4 * sizeof(uint32_t)) != hipSuccess) {
-        s.h_ctl = nullptr;
-        rc = gms_fail(GMS_ERR_NOMEM, "gms_pf_modes: pinned memory for the read-back could not be allocated");
-    }
+    const hipStream_t *st = &pf->map->stream;                                   // (both grow behind a wait on it and never shrink)
+    if (!rc) rc = gms_dev_grow(&s.d_bins, &s.bins_cap, NB, GMS_SCAN, st, [](size_t c) { return (3 * c + c / GMS_SCAN + 1) * sizeof(uint32_t); }, "gms_pf_modes", "the bin counts, the label field and its scan");
+    if (!rc) rc = gms_dev_grow(&s.d_table, &s.table_cap, rows, GMS_SCAN, st, [](size_t c) { return c * (sizeof(ModeRow) + 2 * sizeof(uint32_t)) + (c / GMS_SCAN + 1) * sizeof(uint32_t); }, "gms_pf_modes", "the mode table");
+    if (!rc) rc = gms_pinned_alloc(&s.h_ctl, 4 * sizeof(uint32_t), "gms_pf_modes");
     return rc;
 }
-
-static inline unsigned modes_grid(int64_t n, int64_t most) { return (unsigned)std::max<int64_t>(1, std::min(most, (n + MOD_NT - 1) / MOD_NT)); }
 
 static int pf_modes(gms_pf *pf, int32_t mi, const gms_modes *q, uint32_t *labels, gms_mode *records, int32_t cap, int32_t *n_found, int32_t *n_outside,
                     bool on_device) {
@@ -452,19 +332,16 @@ static int pf_modes(gms_pf *pf, int32_t mi, const gms_modes *q, uint32_t *labels
     const float *pose = pf->d_pose + 3 * (size_t)mi * (size_t)n, *cs = pf->d_cs + 2 * (size_t)mi * (size_t)n;
     const double *wgt = pf->d_w + (size_t)mi * (size_t)n;
     hipStream_t s = m->stream;
-    const unsigned gb = (unsigned)((NB + MOD_NT - 1) / MOD_NT), gp = (unsigned)((n + MOD_NT - 1) / MOD_NT), gt = modes_grid(rows, 1024);
-    const int32_t nblocks = (int32_t)((NB + MOD_SCAN - 1) / MOD_SCAN);
+    const unsigned gb = (unsigned)((NB + MOD_NT - 1) / MOD_NT), gp = (unsigned)((n + MOD_NT - 1) / MOD_NT), gt = gms_grid(rows, MOD_NT, 1024);
     hipLaunchKernelGGL(k_modes_clear, dim3(gb), dim3(MOD_NT), 0, s, b.cnt, b.lab, d.NB, ctl);
     hipLaunchKernelGGL(k_modes_bin, dim3(gp), dim3(MOD_NT), 0, s, g, d, pose, n, pbin, b.cnt, ctl);
     hipLaunchKernelGGL(k_modes_unite, dim3(gb), dim3(MOD_NT), 0, s, d, b.cnt, b.lab);
     hipLaunchKernelGGL(k_modes_flatten, dim3(gb), dim3(MOD_NT), 0, s, b.cnt, b.lab, d.NB, b.num);
-    hipLaunchKernelGGL(k_modes_scan_blocks, dim3((unsigned)nblocks), dim3(MOD_NT), 0, s, b.num, (const uint32_t *)nullptr, d.NB, b.nblk);
-    hipLaunchKernelGGL(k_modes_scan_top, dim3(1), dim3(MOD_NT), 0, s, b.nblk, nblocks, ctl);
+    gms_launch_scan(s, b.num, nullptr, NB, b.nblk, ctl);
     hipLaunchKernelGGL(k_modes_table_init, dim3(gt), dim3(MOD_NT), 0, s, t.row, ctl, tcap);
     hipLaunchKernelGGL(k_modes_reduce, dim3(gb), dim3(MOD_NT), 0, s, d, b.cnt, b.lab, b.num, b.nblk, t.row, tcap);
     hipLaunchKernelGGL(k_modes_finish, dim3(gt), dim3(MOD_NT), 0, s, t.row, ctl, tcap, q->min_count, t.kept);
-    hipLaunchKernelGGL(k_modes_scan_blocks, dim3((unsigned)((rows + MOD_SCAN - 1) / MOD_SCAN)), dim3(MOD_NT), 0, s, t.kept, ctl, tcap, t.kblocks);
-    hipLaunchKernelGGL(k_modes_scan_top, dim3(1), dim3(MOD_NT), 0, s, t.kblocks, (rows + MOD_SCAN - 1) / MOD_SCAN, ctl + 1);
+    gms_launch_scan(s, t.kept, ctl, rows, t.kblocks, ctl + 1);                  // (the modes are min(n, bins) = rows at most)
     hipLaunchKernelGGL(k_modes_labels, dim3(gp), dim3(MOD_NT), 0, s, pbin, b.lab, n, plab, d_labels);
     if (stored > 0) {
         hipLaunchKernelGGL(k_modes_emit, dim3(gt), dim3(MOD_NT), 0, s, d, t.row, t.kept, t.kblocks, ctl, tcap, q->min_count, d_records, t.anchors, stored);

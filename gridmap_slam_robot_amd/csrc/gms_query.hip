@@ -12,6 +12,11 @@
 //                  none: k_slam_plane packs the SHOWN particle's -- from plane 0 of its class planes (code 2 occupied, code 1 free), or
 //                  from logData where the handle keeps no planes -- into a scratch plane of the handle; particle and generation are
 //                  picked there, on the device.
+//   the scan       gms_launch_scan (gms_internal.h): the exclusive scan of uint32 counts that frontier regions, pose modes and particle
+//                  seeding number their roots, kept records and eligible cells with.  k_scan_blocks: a workgroup of 256 lanes per
+//                  GMS_SCAN items, four per lane, an inclusive scan by shuffles inside each wavefront and the four wavefronts' sums
+//                  through LDS -- one barrier; k_scan_top: ONE workgroup per batch entry walks the blocks' totals with the same body,
+//                  GMS_SCAN at a time, the carry in a register.
 #undef GMS_STAMPS
 #include "gms_device.h"
 
@@ -55,7 +60,65 @@ k_slam_plane(GridDev g, SlamBufs sb, int64_t code_words, const PfStatsDev *__res
     plane_pack_word(plane, (size_t)y * (size_t)wpr64 + (size_t)wx, obstacle);
 }
 
+// The scan's block body: the workgroup's GMS_SCAN items v[base ..], four per lane, become carry + the sum of those before them; items
+// behind n count as 0 and are neither read nor written.  Returns the sum of the GMS_SCAN items, in every lane.  s_wave: 4 words of LDS
+__device__ __forceinline__ uint32_t scan_block(uint32_t *__restrict__ v, int64_t base, int64_t n, uint32_t carry, uint32_t *s_wave) {
+    const int32_t t = (int32_t)threadIdx.x, lane = t & 63;
+    const int64_t at = base + t * 4;
+    uint32_t c[4], mine = 0u;
+#pragma unroll
+    for (int32_t k = 0; k < 4; k++) {
+        c[k] = at + k < n ? v[at + k] : 0u;
+        mine += c[k];
+    }
+    uint32_t inc = mine;                                                        // the inclusive scan within the wavefront
+#pragma unroll
+    for (int32_t off = 1; off < 64; off <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)inc, off);
+        if (lane >= off) inc += up;
+    }
+    if (lane == 63) s_wave[t >> 6] = inc;
+    __syncthreads();
+    const uint32_t w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
+    uint32_t run = carry + inc - mine + (t >= 64 ? w0 : 0u) + (t >= 128 ? w1 : 0u) + (t >= 192 ? w2 : 0u);
+#pragma unroll
+    for (int32_t k = 0; k < 4; k++) {
+        if (at + k < n) v[at + k] = run;
+        run += c[k];
+    }
+    return w0 + w1 + w2 + w3;
+}
+static_assert(GMS_SCAN == 4 * 256, "scan_block: 256 lanes, four items each");
+
+// grid (blocks, batch): entry blockIdx.y's items at vals + y * stride, its blocks' totals into sums + y * sum_stride (gms_launch_scan)
+__global__ void __launch_bounds__(256)
+k_scan_blocks(uint32_t *__restrict__ vals, const uint32_t *__restrict__ n_dev, int64_t n_cap, int64_t stride, uint32_t *__restrict__ sums, int64_t sum_stride) {
+    __shared__ uint32_t s_wave[4];
+    const int64_t n = n_dev ? (*n_dev < n_cap ? (int64_t)*n_dev : n_cap) : n_cap;
+    const uint32_t sum = scan_block(vals + (size_t)blockIdx.y * (size_t)stride, (int64_t)blockIdx.x * GMS_SCAN, n, 0u, s_wave);
+    if (threadIdx.x == 0) sums[(size_t)blockIdx.y * (size_t)sum_stride + blockIdx.x] = sum;
+}
+// grid (1, batch), ONE workgroup per entry: its nb totals -> their exclusive prefix in place, the sum of all into total[blockIdx.y]
+__global__ void __launch_bounds__(256)
+k_scan_top(uint32_t *__restrict__ sums, int64_t nb, int64_t sum_stride, uint32_t *__restrict__ total) {
+    __shared__ uint32_t s_wave[4];
+    uint32_t *__restrict__ v = sums + (size_t)blockIdx.y * (size_t)sum_stride;
+    uint32_t carry = 0u;
+    for (int64_t base = 0; base < nb; base += GMS_SCAN) {
+        carry += scan_block(v, base, nb, carry, s_wave);
+        __syncthreads();                                                        // (the next round writes s_wave again)
+    }
+    if (threadIdx.x == 0) total[blockIdx.y] = carry;
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
+void gms_launch_scan(hipStream_t st, uint32_t *vals, const uint32_t *n_dev, int64_t n_cap, uint32_t *sums, uint32_t *total, int32_t batch, int64_t stride,
+                     int64_t sum_stride) {
+    const int64_t nb = (n_cap + GMS_SCAN - 1) / GMS_SCAN;
+    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nb, (unsigned)batch), dim3(256), 0, st, vals, n_dev, n_cap, stride, sums, sum_stride);
+    hipLaunchKernelGGL(k_scan_top, dim3(1, (unsigned)batch), dim3(256), 0, st, sums, nb, sum_stride, total);
+}
+
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what) {
     if ((int64_t)x0 + w > W || (int64_t)y0 + h > H)
         return gms_fail(GMS_ERR_INVALID, "%s: the rectangle (%d, %d) + %d x %d leaves the map's %d x %d cells", what, x0, y0, w, h, W, H);
@@ -123,17 +186,9 @@ int gms_slam_plane(gms_slam *s, int32_t which, int32_t filter, int32_t mode, int
 // The host forms' device staging: 16 bytes for the shown index, `bytes` behind them.  Kept on the handle and only ever grown (a stream
 // synchronise, then a larger allocation), so a sequence of requests of one size allocates once
 static int gms_view_staging(gms_map *m, size_t bytes, unsigned char **base) {
-    const size_t need = 16 + bytes;
-    if (m->view_cap < need) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        hipFree(m->d_view); m->d_view = nullptr; m->view_cap = 0;
-        const size_t cap = (need + 65535) & ~(size_t)65535;
-        int rc = gms_dev_alloc(&m->d_view, cap, "gms_view", "the host forms' staging");
-        if (rc) return rc;
-        m->view_cap = cap;
-    }
+    int rc = gms_dev_grow(&m->d_view, &m->view_cap, (int64_t)(16 + bytes), 65536, &m->stream, [](size_t c) { return c; }, "gms_view", "the host forms' staging");
     *base = m->d_view;
-    return GMS_OK;
+    return rc;
 }
 int HostStage::open() { return on_device ? GMS_OK : gms_view_staging(m, total, &base); }
 int HostStage::up(size_t part, const void *src, size_t bytes) {

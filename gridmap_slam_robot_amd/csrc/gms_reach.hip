@@ -236,10 +236,7 @@ static int reach_buffers(gms_map *m, bool inflated) {
     int rc = gms_dev_alloc(&m->d_reach_field, ((cells + 1) & ~(size_t)1) * sizeof(uint16_t), "gms_reach", "the working field");
     if (!rc) rc = gms_dev_alloc(&m->d_reach_ctl, (RCH_CTL_WORDS + 2 * ntiles) * sizeof(uint32_t), "gms_reach", "the tiles' flags");
     // (inflate > 0: the clearance field and the blocked plane are gms_reach_inflate's)
-    if (!rc && !m->h_reach_ctl && hipHostMalloc(reinterpret_cast<void **>(&m->h_reach_ctl), RCH_CTL_WORDS * sizeof(uint32_t)) != hipSuccess) {
-        m->h_reach_ctl = nullptr;
-        rc = gms_fail(GMS_ERR_NOMEM, "gms_reach: pinned memory for the read-back could not be allocated");
-    }
+    if (!rc) rc = gms_pinned_alloc(&m->h_reach_ctl, RCH_CTL_WORDS * sizeof(uint32_t), "gms_reach");
     return rc;
 }
 

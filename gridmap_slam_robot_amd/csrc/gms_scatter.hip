@@ -8,11 +8,11 @@
 //                  count are stored.  The not-free plane is the query base's (query_plane, packed only when stale); blocked, for
 //                  inflate > 0, is the cost-to-go fields' plane (gms_reach_inflate) of the obstacle plane of `mode`.  With inflate = 0
 //                  every obstacle of either mode is not free already, so the not-free plane alone decides.
-//   k_scat_scan    (2) the exclusive scan of the counts, per map: workgroups of 256 lanes scan blocks of SCT_SCAN words in place and
-//                  store the blocks' totals; the same kernel, one workgroup per map, then scans those totals, and its total is M.
-//                  Two launches, no workgroup waits on another.  A plane of more than SCT_SCAN^2 words is refused.
+//   gms_launch_scan  (2) the exclusive scan of the counts, every map's at once (gms_query.hip, its batched form): the words' counts
+//                  scanned within blocks of GMS_SCAN, the blocks' offsets, and the total, which is M.  A plane of more than GMS_SCAN^2
+//                  words is refused.
 //   k_scat_draw    (3) a lane per slot: the Philox block, r = mulhi64(c0:c1, M), the word that holds rank r, its r'-th set bit, the
-//                  pose, its trig and the weight.  The prefix of word w is top[w / SCT_SCAN] + pre[w]; a workgroup stages that sum for
+//                  pose, its trig and the weight.  The prefix of word w is top[w / GMS_SCAN] + pre[w] (scan_prefix); a workgroup stages that sum for
 //                  every (1 << shift)-th word in LDS (at most SCT_STAGE entries, shift >= SCT_SHIFT_MIN), searches there first -- the
 //                  first steps of all lanes read the same few entries, which broadcast; the last ones scatter over the 32 banks of a
 //                  half-wave as 32 random addresses do, a few lanes to a bank at worst -- and finishes within the (1 << shift) words
@@ -27,16 +27,14 @@
 #include <algorithm>
 #include <vector>
 
-#include "gms_device.h"
+#include "gms_regions.h"
 
 #define SCT_NT 256
-#define SCT_SCAN 1024                    // words a workgroup of k_scat_scan scans: 4 per lane
 #define SCT_STAGE 8192                   // staged prefix entries at most: 32 KiB of LDS
 #define SCT_SHIFT_MIN 5                  // every 32nd word is staged, or a coarser power of two where that exceeds SCT_STAGE
 #define SCT_BOUND 262144.0               // (|position| + extent) / resolution at most, per axis (gridmapslam.h: the cell guarantee)
 
 static_assert(sizeof(gms_scatter) == 40, "gms_scatter is ten int32_t");
-static_assert(SCT_SCAN == 4 * SCT_NT, "k_scat_scan: four words per lane");
 
 // nf, blocked (NULL: none): ONE map's planes, H rows of wpr64 words; elig, cnt: that map's part of the table
 __global__ void __launch_bounds__(SCT_NT)
@@ -58,42 +56,10 @@ k_scat_plane(const uint64_t *__restrict__ nf, const uint64_t *__restrict__ block
     cnt[i] = (uint32_t)__popcll(e);
 }
 
-// Map blockIdx.y's vals [n] (at vals + map * stride) -> the exclusive prefix of each within its block of SCT_SCAN, in place; the
-// blocks' totals into sums (at sums + map * sum_stride)
-__global__ void __launch_bounds__(SCT_NT)
-k_scat_scan(uint32_t *__restrict__ vals, int32_t n, int32_t stride, uint32_t *__restrict__ sums, int32_t sum_stride) {
-    __shared__ uint32_t s_wave[SCT_NT / 64];
-    const int32_t t = (int32_t)threadIdx.x, lane = t & 63, mi = (int32_t)blockIdx.y;
-    uint32_t *__restrict__ v = vals + (size_t)mi * (size_t)stride;
-    const int32_t base = (int32_t)blockIdx.x * SCT_SCAN + t * 4;
-    uint32_t c[4], mine = 0u;
-#pragma unroll
-    for (int32_t k = 0; k < 4; k++) {
-        c[k] = base + k < n ? v[base + k] : 0u;
-        mine += c[k];
-    }
-    uint32_t inc = mine;                                                        // the inclusive scan within the wavefront
-#pragma unroll
-    for (int32_t off = 1; off < 64; off <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)inc, off);
-        if (lane >= off) inc += up;
-    }
-    if (lane == 63) s_wave[t >> 6] = inc;
-    __syncthreads();
-    uint32_t run = inc - mine;
-    for (int32_t wv = 0; wv < (t >> 6); wv++) run += s_wave[wv];
-#pragma unroll
-    for (int32_t k = 0; k < 4; k++) {
-        if (base + k < n) v[base + k] = run;
-        run += c[k];
-    }
-    if (t == SCT_NT - 1) sums[(size_t)mi * (size_t)sum_stride + blockIdx.x] = run;
-}
-
 // what k_scat_draw needs of the table and the request
 struct ScatDraw {
     const uint64_t *elig;       // [n_maps][words]
-    const uint32_t *pre;        // [n_maps][words] the counts scanned within blocks of SCT_SCAN
+    const uint32_t *pre;        // [n_maps][words] the counts scanned within blocks of GMS_SCAN
     const uint32_t *top;        // [n_maps][nb] the blocks' offsets
     const uint32_t *M;          // [n_maps]
     int32_t words, wpr64, nb, shift, nst;
@@ -102,10 +68,6 @@ struct ScatDraw {
     uint64_t seed, sequence;
     double w0;                  // 1.0 / n_global
 };
-
-__device__ __forceinline__ uint32_t scat_prefix(const uint32_t *__restrict__ pre, const uint32_t *__restrict__ top, int32_t w) {
-    return top[w / SCT_SCAN] + pre[w];
-}
 
 // grid (workgroups over the slots, maps); dynamic LDS: nst staged entries
 __global__ void __launch_bounds__(SCT_NT)
@@ -116,7 +78,7 @@ k_scat_draw(GridDev g, ScatDraw a, float *__restrict__ pose, float *__restrict__
     if (M == 0u) return;                                                        // (uniform) nothing eligible: nothing written
     const uint64_t *__restrict__ elig = a.elig + (size_t)mi * (size_t)a.words;
     const uint32_t *__restrict__ pre = a.pre + (size_t)mi * (size_t)a.words, *__restrict__ top = a.top + (size_t)mi * (size_t)a.nb;
-    for (int32_t j = tid; j < a.nst; j += SCT_NT) s_pre[j] = scat_prefix(pre, top, j << a.shift);
+    for (int32_t j = tid; j < a.nst; j += SCT_NT) s_pre[j] = scan_prefix(pre, top, j << a.shift);
     __syncthreads();
     const int32_t i = (int32_t)blockIdx.x * SCT_NT + tid;
     if (i >= a.count) return;
@@ -144,9 +106,9 @@ k_scat_draw(GridDev g, ScatDraw a, float *__restrict__ pose, float *__restrict__
     hi = min(lo + (1 << a.shift), a.words);
     while (hi - lo > 1) {
         const int32_t mid = (lo + hi) >> 1;
-        if (scat_prefix(pre, top, mid) <= r) lo = mid; else hi = mid;
+        if (scan_prefix(pre, top, mid) <= r) lo = mid; else hi = mid;
     }
-    uint32_t kth = r - scat_prefix(pre, top, lo);                               // < popcount of the word
+    uint32_t kth = r - scan_prefix(pre, top, lo);                               // < popcount of the word
     uint64_t v = elig[lo];
     int32_t bit = 0;
 #pragma unroll
@@ -185,7 +147,7 @@ static int scat_table(gms_map *m, const gms_scatter *sc) {
     auto &t = m->scatter;
     const int32_t mode = sc->inflate > 0 ? sc->mode : GMS_CLEAR_NOT_FREE;       // (inflate = 0: both modes give the free cells)
     if (t.current && t.x0 == sc->x0 && t.y0 == sc->y0 && t.w == sc->w && t.h == sc->h && t.inflate == sc->inflate && t.mode == mode) return GMS_OK;
-    const int32_t wpr64 = (m->gd.W + 63) / 64, words = m->gd.H * wpr64, nb = (words + SCT_SCAN - 1) / SCT_SCAN;
+    const int32_t wpr64 = (m->gd.W + 63) / 64, words = m->gd.H * wpr64, nb = (words + GMS_SCAN - 1) / GMS_SCAN;
     const size_t all = (size_t)m->n_maps * (size_t)words;
     int rc = gms_dev_alloc(&t.d_elig, all * sizeof(uint64_t), "gms_pf_scatter", "the eligible plane");
     if (!rc) rc = gms_dev_alloc(&t.d_pre, (all + (size_t)m->n_maps * (size_t)(nb + 1)) * sizeof(uint32_t), "gms_pf_scatter", "the plane's scanned counts");
@@ -206,8 +168,7 @@ static int scat_table(gms_map *m, const gms_scatter *sc) {
                            reinterpret_cast<const uint64_t *>(blocked), wpr64, words, sc->x0, sc->y0, sc->w, sc->h, t.d_elig + (size_t)mi * (size_t)words,
                            t.d_pre + (size_t)mi * (size_t)words);
     }
-    hipLaunchKernelGGL(k_scat_scan, dim3((unsigned)nb, (unsigned)m->n_maps), dim3(SCT_NT), 0, m->stream, t.d_pre, words, words, d_top, nb);
-    hipLaunchKernelGGL(k_scat_scan, dim3(1, (unsigned)m->n_maps), dim3(SCT_NT), 0, m->stream, d_top, nb, nb, d_M, 1);
+    gms_launch_scan(m->stream, t.d_pre, nullptr, words, d_top, d_M, m->n_maps, words, nb);
     HIPCHK(hipGetLastError());
     t.x0 = sc->x0; t.y0 = sc->y0; t.w = sc->w; t.h = sc->h; t.inflate = sc->inflate; t.mode = mode;
     t.current = 1;
@@ -243,14 +204,14 @@ int gms_pf_scatter(gms_pf *pf, const gms_scatter *sc, uint64_t seed, uint64_t se
     if ((fabs(g.posx) + (double)g.W * g.res) / g.res > SCT_BOUND || (fabs(g.posy) + (double)g.H * g.res) / g.res > SCT_BOUND)
         return gms_fail(GMS_ERR_INVALID, "gms_pf_scatter: (|position| + extent) / resolution exceeds 2^18 cells: a pose's cell would not be certain");
     const int64_t words = (int64_t)g.H * ((g.W + 63) / 64);
-    if (words > (int64_t)SCT_SCAN * SCT_SCAN)
-        return gms_fail(GMS_ERR_INVALID, "gms_pf_scatter: a plane of %lld words exceeds the two scan levels' %d", (long long)words, SCT_SCAN * SCT_SCAN);
+    if (words > (int64_t)GMS_SCAN * GMS_SCAN)
+        return gms_fail(GMS_ERR_INVALID, "gms_pf_scatter: a plane of %lld words exceeds the two scan levels' %d", (long long)words, GMS_SCAN * GMS_SCAN);
     HIPCHK(hipSetDevice(m->device));
     rc = scat_table(m, sc);
     if (rc) return rc;
     gms_launch_pf_combine(pf);                                                  // the other slots' weights out of a pending scoring pass
     const auto &t = m->scatter;
-    const int32_t nb = (int32_t)((words + SCT_SCAN - 1) / SCT_SCAN), shift = scat_shift(m, words);
+    const int32_t nb = (int32_t)((words + GMS_SCAN - 1) / GMS_SCAN), shift = scat_shift(m, words);
     const size_t all = (size_t)m->n_maps * (size_t)words;
     ScatDraw a;
     a.elig = t.d_elig; a.pre = t.d_pre; a.top = t.d_pre + all; a.M = a.top + (size_t)m->n_maps * (size_t)nb;

@@ -27,8 +27,8 @@ NS = (1, 255, 256, 257, 1000)                          # k_scat_draw's workgroup
 SEED, SEQ = 0x123456789ABCDEF, 0xFEDCBA9876543210      # both halves of key and counter carry bits
 
 
-def _unit_constant(name):
-    src = open(os.path.join(ROOT, "gridmap_slam_robot_amd", "csrc", "gms_scatter.hip")).read()
+def _unit_constant(name, unit="gms_scatter.hip"):
+    src = open(os.path.join(ROOT, "gridmap_slam_robot_amd", "csrc", unit)).read()
     return int(re.search(r"#define %s (\d+)" % name, src).group(1))
 
 
@@ -94,11 +94,11 @@ def test_word_shapes_rectangles_and_populations(W, H):
 
 
 def test_a_map_that_needs_every_level_of_scan_and_search(monkeypatch):
-    """The unit scans blocks of SCT_SCAN plane words and then the blocks' totals, and stages every 2^SCT_SHIFT_MIN-th word's prefix:
-    a map of more than SCT_SCAN words has several scan blocks, block offsets that are not zero, several staged entries and a search
+    """The unit scans blocks of GMS_SCAN plane words and then the blocks' totals, and stages every 2^SCT_SHIFT_MIN-th word's prefix:
+    a map of more than GMS_SCAN words has several scan blocks, block offsets that are not zero, several staged entries and a search
     that ends in memory.  1100 x 1030 cells are 1030 rows of 18 words.  GMS_SCATTER_SHIFT=9 makes the staged level coarser (the form
     planes of more than SCT_STAGE << SCT_SHIFT_MIN words take): the same poses."""
-    scan, shift = _unit_constant("SCT_SCAN"), _unit_constant("SCT_SHIFT_MIN")
+    scan, shift = _unit_constant("GMS_SCAN", "gms_internal.h"), _unit_constant("SCT_SHIFT_MIN")
     W, H = 1100, 1030
     words = H * ((W + 63) // 64)
     assert words > 4 * scan and words >> shift > 64 and words < scan * scan
