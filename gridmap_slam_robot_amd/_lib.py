@@ -148,6 +148,22 @@ class GmsMode(C.Structure):
     ]
 
 
+class GmsAlignParams(C.Structure):
+    """gms_align_params: the parameters of a scan alignment (gridmapslam.h "continuous scan alignment"), 64 bytes"""
+    _fields_ = [
+        ("iters", C.c_int32), ("pad", C.c_int32), ("damp_t", C.c_double), ("damp_r", C.c_double), ("max_t", C.c_double), ("max_r", C.c_double),
+        ("eps_t", C.c_double), ("eps_r", C.c_double), ("det_min", C.c_double),
+    ]
+
+
+class GmsAlignRecord(C.Structure):
+    """gms_align_record: one aligned pose's record, 80 bytes"""
+    _fields_ = [
+        ("status", C.c_int32), ("iters_done", C.c_int32), ("n_used", C.c_int32), ("n_used0", C.c_int32),
+        ("score0", C.c_double), ("score", C.c_double), ("H", C.c_double * 6),
+    ]
+
+
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
 LOCATE_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsLocateRec._fields_])     # gms_locate_rec
@@ -159,6 +175,10 @@ GMS_FRONTIER_NONE = 0xFFFFFFFF
 MODE_DTYPE = np.dtype([(n, "<f8" if t is C.c_double else ("<i4", (2,)) if n == "pad" else "<i4") for n, t in GmsMode._fields_])     # gms_mode
 assert MODE_DTYPE.itemsize == C.sizeof(GmsMode) == 112
 GMS_MODE_NONE = 0xFFFFFFFF
+ALIGN_DTYPE = np.dtype([(n, ("<f8", (6,)) if n == "H" else "<f8" if t is C.c_double else "<i4") for n, t in GmsAlignRecord._fields_])     # gms_align_record
+assert ALIGN_DTYPE.itemsize == C.sizeof(GmsAlignRecord) == 80 and C.sizeof(GmsAlignParams) == 64
+GMS_ALIGN_ITERS, GMS_ALIGN_CONVERGED, GMS_ALIGN_NO_BEAM, GMS_ALIGN_SINGULAR = 0, 1, 2, 3      # gms_align_record.status
+GMS_MAX_PARTICLES = 1 << 20
 CLEARANCE = GmsClearance
 GMS_REACH_AXIS, GMS_REACH_DIAG, GMS_REACH_FAR, GMS_REACH_MAX_SEEDS = 5, 7, 0xFFFF, 4096
 GMS_CLEAR_OCCUPIED, GMS_CLEAR_NOT_FREE = 0, 1
@@ -401,6 +421,13 @@ def load() -> C.CDLL:
     sig("gms_beam_model_check", C.c_int, i32, i32, vp)
     sig("gms_pf_score_beams", C.c_int, vp, vp, i32, i32, i32, vp, vp)
     sig("gms_pf_score_beams_dev", C.c_int, vp, vp, i32, i32, i32, vp, vp)
+    ap = C.POINTER(GmsAlignParams)
+    sig("gms_align_params_default", C.c_int, ap)
+    sig("gms_align_check", C.c_int, ap)
+    sig("gms_map_align", C.c_int, vp, i32, vp, i32, vp, i32, ap, vp, vp)
+    sig("gms_map_align_dev", C.c_int, vp, i32, vp, i32, vp, i32, ap, vp, vp)
+    sig("gms_pf_align", C.c_int, vp, vp, i32, ap, vp)
+    sig("gms_pf_align_dev", C.c_int, vp, vp, i32, ap, vp)
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
 __all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
-           "cells_of_poses", "descend", "mode_estimate", "strongest_mode"]
+           "cells_of_poses", "descend", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -303,6 +303,52 @@ def beam_model_factors(resolution: float, behind: int, ahead: int, sigma: float,
     return f
 
 
+class AlignParams(_lib.GmsAlignParams):
+    """The parameters of align() (gridmapslam.h "continuous scan alignment", gms_align_params): the library's defaults
+    (gms_align_params_default: iters 8, damp_t 10, damp_r 1e4, max_t 2 cells, max_r 0.1 rad, eps_t 0.01 cells, eps_r 1e-4 rad, det_min
+    1e-6) with the keyword arguments written over them.  check() is gms_align_check: GmsError on a value out of range."""
+
+    def __init__(self, **fields):
+        super().__init__()
+        check(load().gms_align_params_default(C.byref(self)))
+        names = {n for n, _ in self._fields_}
+        for k, v in fields.items():
+            if k not in names or k == "pad":
+                raise TypeError(f"AlignParams: no field {k!r}")
+            setattr(self, k, int(v) if k == "iters" else float(v))
+
+    def check(self) -> "AlignParams":
+        check(load().gms_align_check(C.byref(self)))
+        return self
+
+
+def _align_params(params) -> _lib.GmsAlignParams:
+    if params is None:
+        return AlignParams()
+    return params if isinstance(params, _lib.GmsAlignParams) else AlignParams(**dict(params))
+
+
+def align_covariance(records, resolution: float) -> np.ndarray:
+    """The covariance of align()'s poses from their records' H, host numpy: float64 [n][3][3] in (metres, metres, radians), the inverse
+    of the information matrix H (cells, cells, radians) scaled by the resolution, up to the residuals' variance, which the caller
+    knows; NaN where H is singular or not finite."""
+    Hs = np.asarray(np.asarray(records)["H"], dtype=np.float64).reshape(-1, 6)
+    out = np.full((len(Hs), 3, 3), np.nan)
+    scale = np.array([float(resolution), float(resolution), 1.0])
+    for i, h in enumerate(Hs):
+        A = np.array([[h[0], h[1], h[2]], [h[1], h[3], h[4]], [h[2], h[4], h[5]]])
+        if not np.isfinite(A).all():
+            continue
+        with np.errstate(all="ignore"):
+            try:
+                inv = np.linalg.inv(A)
+            except np.linalg.LinAlgError:
+                continue
+        if np.isfinite(inv).all() and np.linalg.matrix_rank(A) == 3:
+            out[i] = inv * np.outer(scale, scale)
+    return out
+
+
 def clearance_metres(d2, resolution: float) -> np.ndarray:
     """Clearance values (GridMap.clearance / clearance_poses: squared cell distances as uint16) as metres, float64: sqrt(d2) *
     resolution; GMS_CLEAR_FAR (beyond the radius, or no obstacle at all) becomes inf, GMS_CLEAR_OUTSIDE (a pose off the map) nan."""
@@ -502,6 +548,22 @@ def _query_locate(src: _Source, offsets, rect, tol: int, not_free: bool, min_sco
     n = C.c_int32(0)
     tail = src.host("locate", C.byref(lc), ptr(t), B, ptr(rec), C.byref(n))
     return ((rec, int(n.value)) if full else rec[:n.value],) + tail
+
+
+def _query_align(src: _Source, scan, poses, params, records, out=None) -> tuple:
+    """out given: the device form -- scan = (device address, B), poses = (device address, P), records a torch device tensor or None"""
+    prm = _align_params(params)
+    if out is not None:
+        (dev_beams, B), (dev_poses, P) = scan, poses
+        return (out, records) + src.dev("align", C.c_void_p(dev_beams), int(B), C.c_void_p(dev_poses), int(P), C.byref(prm),
+                                        _device_ptr("align", "out", out, 12 * int(P), itemsize=4),
+                                        _device_ptr("align", "records_out", records, _lib.ALIGN_DTYPE.itemsize * int(P), optional=True))
+    p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+    b = _beams_of(scan).reshape(-1)
+    res = np.empty_like(p)
+    rec = np.empty(len(p), dtype=_lib.ALIGN_DTYPE) if records else None
+    tail = src.host("align", ptr(b), len(b), ptr(p), len(p), C.byref(prm), ptr(res), None if rec is None else ptr(rec))
+    return ((res, rec) if records else (res,)) + tail
 
 
 def _query_frontiers(src: _Source, min_size: int, inflate: int, cost, rect, labels, cap: int, dev=None):
@@ -706,6 +768,23 @@ class GridMap:
         4095] or SKIP pairs: a precondition), out a contiguous torch device tensor of cap * 16 bytes (16-byte aligned), n_out an int32
         one.  The call waits on the stream once per level of the search."""
         return _query_locate(self._src(mi), (dev_offsets, n_theta, B), rect, tol, not_free, min_score, cap, free_only, False, out, n_out, None)
+
+    def align(self, obs, poses, params=None, mi: int = 0, records: bool = False):
+        """Continuous scan alignment (gridmapslam.h "continuous scan alignment") in map mi: each of poses [P][3] is moved by a damped
+        Gauss-Newton scan matcher on the bilinearly interpolated likelihood field until the scan's end points lie on the field's ridges
+        -- a sub-cell pose from "about here", at 4 x B field values per iteration.  params: an AlignParams (None: the defaults), or a
+        dict of its fields.  Returns the poses, float32 [P][3]; records=True: (poses, records), ALIGN_DTYPE (status 0 ran all iters /
+        1 converged / 2 no usable beam / 3 singular, iters_done, n_used, n_used0, score0, score, H [6]: the information matrix at the
+        final pose -- align_covariance()).  The idiom after a global match: recs = m.locate(locate_offsets(scan, n_theta, res), ...);
+        start = locate_poses(recs, m.position, res, n_theta=n_theta); fine = m.align(scan, start)."""
+        r = _query_align(self._src(mi), obs, poses, params, records)
+        return r if records else r[0]
+
+    def align_dev(self, dev_beams: int, B: int, dev_poses: int, P: int, out, params=None, mi: int = 0, records_out=None):
+        """align() with device memory on the handle's stream: dev_beams [B] gms_beam and dev_poses [P][3] float are device addresses,
+        out a contiguous float32 torch device tensor of P * 3 elements (it may be the tensor behind dev_poses), records_out None or a
+        contiguous torch device tensor of P * 80 bytes, 8-byte aligned.  Nothing is synchronised.  Returns (out, records_out)."""
+        return _query_align(self._src(mi), (dev_beams, B), (dev_poses, P), params, records_out, out)
 
     def locate_stats(self) -> dict:
         """diagnostics of the last locate() on this handle: {"levels": the top level L of its search, "evaluated": the candidates it
@@ -1262,6 +1341,25 @@ class ParticleFilter:
         f = self._beam_factors(factors, behind, ahead)
         out = _device_ptr("score_beams_dev", "residuals_out", residuals_out, 2 * self.n_maps * self.n * int(B), optional=True)
         check(load().gms_pf_score_beams_dev(self._h, C.c_void_p(dev_beams), int(B), int(behind), int(ahead), ptr(f), out))
+
+    def align(self, obs, params=None, records: bool = False):
+        """GridMap.align() of every particle, in place (gridmapslam.h "continuous scan alignment", gms_pf_align): on a batched handle
+        map i's particles on map i with obs [n_maps][B].  Afterwards the filter is as set_poses() of the new poses would leave it: the
+        weights are untouched, a following score() weighs the aligned poses.  records=True returns the records, ALIGN_DTYPE [n]
+        ([n_maps][n]), and waits for the stream; otherwise nothing is returned and nothing synchronised."""
+        b, B = self.map._beam_args(obs)
+        prm = _align_params(params)
+        rec = np.empty(self._pshape(), dtype=_lib.ALIGN_DTYPE) if records else None
+        check(load().gms_pf_align(self._h, ptr(b), B, C.byref(prm), None if rec is None else ptr(rec)))
+        return rec
+
+    def align_dev(self, dev_beams: int, B: int, params=None, records_out=None):
+        """align() on device-resident beams [n_maps][B]; records_out: None, or a contiguous torch device tensor of n_maps * n * 80
+        bytes, 8-byte aligned.  Runs on the handle's stream and synchronises nothing."""
+        prm = _align_params(params)
+        out = _device_ptr("align_dev", "records_out", records_out, _lib.ALIGN_DTYPE.itemsize * self.n_maps * self.n, optional=True)
+        check(load().gms_pf_align_dev(self._h, C.c_void_p(dev_beams), int(B), C.byref(prm), out))
+        return records_out
 
     def set_refine(self, on: bool = True):
         """scan steps (slam_update*) run findBestPose on every particle before weighting it (SLAM.java:96-97)."""

@@ -1104,6 +1104,94 @@ int gms_pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t beh
 int gms_pf_score_beams_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B, int32_t behind, int32_t ahead, const double *factors,
                            uint16_t *dev_residuals);
 
+/* ---- continuous scan alignment: from "about here" to a sub-cell pose ------------------------------------------------------------------
+ * Every other pose the library derives from a scan lies on a lattice: gms_map_locate answers with a cell and a heading index,
+ * gms_pf_refine_poses tries 1210 poses in 4 cm / 3 degree steps.  This is a damped Gauss-Newton scan matcher on the bilinearly
+ * interpolated likelihood field (the fine matcher of Hector SLAM and Cartographer, on the field the library keeps anyway): a handful of
+ * iterations of 4 x B field values each.  This library's own definition (the reference has no such method).  Everything is IEEE double
+ * arithmetic unless marked float, every operation rounds on its own (nothing is contracted), every sum has one stated order: the
+ * result is unique.
+ *
+ * INPUTS.  L = likelihoodData of map mi as gms_map_download_likelihood would return it at the time of the call (a lazy rebuild of the
+ * field, with the counts of a deferred `logData +=` pass, is made first); W, H; res, pos_x, pos_y = the handle's float resolution and
+ * position, widened; beams [B], 1 <= B <= max_beams, of which local_x, local_y and hit are read; a pose (x, y, theta) of three floats;
+ * gms_align_params.
+ * ONE EVALUATION at the pose (x, y, theta): c, s = the float-rounded cos and sin of (double)theta, widened (Transform.fromRobotToWorld's
+ * trig, what every other entry point uses).  Only beams with hit != 0 take part; with lx = local_x, ly = local_y, each one:
+ *   X = lx*c - ly*s + x,  Y = lx*s + ly*c + y                       (left to right; x, y widened)
+ *   gu = (X - pos_x)/res - 0.5,  gv = (Y - pos_y)/res - 0.5         (the field value of cell i lives at its centre i + 0.5, consistent
+ *                                                                    with the truncation at GridMap.java:273-274)
+ *   fu = floor(gu), fv = floor(gv), as doubles;  fx = gu - fu, fy = gv - fv
+ *   the beam is USED iff fu >= 0 && fu <= W - 2 && fv >= 0 && fv <= H - 2   (NaN and +-Inf fail; only then i0 = (int)fu, j0 = (int)fv)
+ *   L00 = L[j0][i0], L10 = L[j0][i0 + 1], L01 = L[j0 + 1][i0], L11 = L[j0 + 1][i0 + 1]
+ *   M  = (1 - fy)*((1 - fx)*L00 + fx*L10) + fy*((1 - fx)*L01 + fx*L11)
+ *   Mu = (1 - fy)*(L10 - L00) + fy*(L11 - L01),  Mv = (1 - fx)*(L01 - L00) + fx*(L11 - L10)
+ *   ax = (-lx*s - ly*c)/res,  ay = (lx*c - ly*s)/res,  J = (Mu, Mv, Mu*ax + Mv*ay),  r = 1 - M
+ * and ten sums over the used beams, in this order of terms: H00 = sum J0*J0, H01 = J0*J1, H02 = J0*J2, H11 = J1*J1, H12 = J1*J2,
+ * H22 = J2*J2; g0 = J0*r, g1 = J1*r, g2 = J2*r; S = sum M; beside them the integer count n_used.
+ * THE ORDER is part of the definition: partial l, l = 0 .. 63, starts at +0.0 and takes the used beams among b = l, l + 64, ... in
+ * ascending order (a beam that is not used adds nothing); then the halving tree `for s in 32, 16, .., 1: p[l] = p[l] + p[l + s] for
+ * l < s`; p[0] is the sum.
+ * ONE STEP.  A00 = H00 + damp_t, A11 = H11 + damp_t, A22 = H22 + damp_r, A01 = H01, A02 = H02, A12 = H12;
+ *   C00 = A11*A22 - A12*A12,  C01 = A02*A12 - A01*A22,  C02 = A01*A12 - A02*A11,
+ *   C11 = A00*A22 - A02*A02,  C12 = A01*A02 - A00*A12,  C22 = A00*A11 - A01*A01,
+ *   det = A00*C00 + A01*C01 + A02*C02                                                   (left to right)
+ * If n_used == 0 the pose stops with status 2; otherwise if !(fabs(det) > det_min) -- a NaN lands here -- it stops with status 3.
+ * Otherwise d0 = (C00*g0 + C01*g1 + C02*g2)/det, d1 = (C01*g0 + C11*g1 + C12*g2)/det, d2 = (C02*g0 + C12*g1 + C22*g2)/det (left to
+ * right), d0 and d1 clamped to +-max_t (cells), d2 to +-max_r (radians) by `v > m ? m : (v < -m ? -m : v)` (a NaN passes), and the pose
+ * becomes x = (float)((double)x + d0*res), y = (float)((double)y + d1*res), theta = (float)((double)theta + d2); no wrap.  If the
+ * clamped |d0| <= eps_t, |d1| <= eps_t and |d2| <= eps_r the pose stops as converged, status 1.
+ * THE RUN.  Evaluate; unless stopped, step; at most `iters` steps.  After the last step one more evaluation at the final pose gives the
+ * reported S, n_used and H (a pose that stopped with status 2 or 3 reports the evaluation it stopped on).  So a run costs at most
+ * iters + 1 evaluations, and a pose that stops in its first step comes back bit-identical to its input.
+ *
+ * OUTPUT per pose: the final pose, and optionally one gms_align_record: status (0 ran all iters, 1 converged, 2 no usable beam,
+ * 3 singular), iters_done (the steps taken), n_used at the final and n_used0 at the start pose, score0 and score = S at the start and
+ * at the final pose, H[6] = H00, H01, H02, H11, H12, H22 at the final pose WITHOUT the damping: the information matrix of the match
+ * in (cells, cells, radians), up to the residuals' variance; a caller turns it into a covariance.
+ *
+ * gms_map_align: poses_in [P][3], 1 <= P <= GMS_MAX_PARTICLES, poses_out [P][3] (may equal poses_in), records [P] or NULL; host memory,
+ * staged through the views' buffer; it waits for the stream once.  _dev: the beams, poses and outputs are device memory (poses 4-byte,
+ * records and beams 8-byte aligned), read and written on the handle's stream; nothing is synchronised.
+ * gms_pf_align: every particle of a shared-map filter (every map's, on a batched handle: map i's particles on map i with beams
+ * [n_maps][B], as for gms_pf_score) is aligned IN PLACE; records [n_maps][n] or NULL.  Afterwards the filter is exactly as
+ * gms_pf_set_poses with the new poses would leave it: the cached trig is refreshed; weights, log-weights and the resampling state are
+ * untouched, so a following gms_pf_score equals a score after gms_pf_set_poses of the same poses.  A shard aligns its own particles.
+ * GMS_ERR_STATE: the filter of a gms_slam (its particles live in their own maps).  The host form synchronises only to read the
+ * records back; _dev synchronises nothing.
+ * None of these calls changes the map.  Checked before anything is enqueued (GMS_ERR_INVALID, the outputs untouched): NULL pointers,
+ * mi, B, P, the parameters (gms_align_check), and in the _dev forms the alignment above.
+ *
+ * How: one wavefront per pose, four poses per workgroup of 256 lanes; lane l owns partial l; the beams' (lx, ly) -- NaN for a beam that
+ * did not hit, which the USED test then refuses -- are staged once per workgroup in LDS, 16 bytes per beam; the tree runs as cross-lane
+ * register moves; the loop over the iterations is uniform per wavefront, a stopped pose idles to the end of its workgroup. */
+typedef struct gms_align_params {   /* 64 bytes */
+    int32_t iters;                  /* 1 .. 64 steps at most */
+    int32_t pad;                    /* not read */
+    double  damp_t, damp_r;         /* finite, >= 0: added to H00 and H11 / to H22 (Levenberg's damping) */
+    double  max_t, max_r;           /* > 0, +Inf allowed: the largest step along x and y in cells / of theta in radians */
+    double  eps_t, eps_r;           /* finite, >= 0: a step no larger than these stops the pose as converged */
+    double  det_min;                /* finite, >= 0: a determinant no larger in magnitude stops the pose as singular */
+} gms_align_params;
+typedef struct gms_align_record {   /* 80 bytes */
+    int32_t status;                 /*  0: 0 ran all iters, 1 converged, 2 no usable beam, 3 singular */
+    int32_t iters_done;             /*  4 */
+    int32_t n_used;                 /*  8: used beams at the final pose */
+    int32_t n_used0;                /* 12: ... at the start pose */
+    double  score0, score;          /* 16: S at the start and at the final pose */
+    double  H[6];                   /* 32: H00, H01, H02, H11, H12, H22 at the final pose */
+} gms_align_record;
+/* Pure host code.  The defaults: iters 8, damp_t 10, damp_r 1e4, max_t 2 cells, max_r 0.1 rad, eps_t 0.01 cells, eps_r 1e-4 rad,
+ * det_min 1e-6 (DESIGN.md section 4n says why); the check: the ranges above, non-finite values refused (max_t, max_r may be +Inf). */
+int gms_align_params_default(gms_align_params *p);
+int gms_align_check(const gms_align_params *p);
+int gms_map_align(gms_map *m, int32_t mi, const gms_beam *beams, int32_t B, const float *poses_in, int32_t P, const gms_align_params *params,
+                  float *poses_out, gms_align_record *records);
+int gms_map_align_dev(gms_map *m, int32_t mi, const gms_beam *dev_beams, int32_t B, const float *dev_poses_in, int32_t P,
+                      const gms_align_params *params, float *dev_poses_out, gms_align_record *dev_records);
+int gms_pf_align(gms_pf *pf, const gms_beam *beams, int32_t B, const gms_align_params *params, gms_align_record *records);
+int gms_pf_align_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B, const gms_align_params *params, gms_align_record *dev_records);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,
