@@ -1,6 +1,7 @@
 """Continuous scan alignment (include/gridmapslam.h "continuous scan alignment") restated from the header's text in plain Python: the
 pose as three floats between iterations, every other number a Python float (an IEEE double, never contracted), the trig from
 orc.pose_trig, the 64 partials and the halving tree as loops.  It shares nothing with the kernel; the tests compare for equality."""
+import functools
 import math
 
 import numpy as np
@@ -38,6 +39,13 @@ def _tree(p: list) -> float:
     return p[0]
 
 
+def grid_uv(lx: float, ly: float, c: float, s: float, x: float, y: float, res: float, pos_x: float, pos_y: float):
+    """(gu, gv): the end point of the beam (lx, ly) seen from (x, y) with the trig (c, s), in cells from the first cell's centre"""
+    X = lx * c - ly * s + x
+    Y = lx * s + ly * c + y
+    return (X - pos_x) / res - 0.5, (Y - pos_y) / res - 0.5
+
+
 def evaluate(L, W: int, H: int, res: float, pos_x: float, pos_y: float, beams, pose):
     """One evaluation: (Hm [6], g [3], S, n_used).  L: the field, flat [H * W]; res, pos_x, pos_y: the handle's floats, widened"""
     x, y, th = float(pose[0]), float(pose[1]), float(pose[2])
@@ -49,10 +57,7 @@ def evaluate(L, W: int, H: int, res: float, pos_x: float, pos_y: float, beams, p
         if hits[b] == 0:
             continue
         lx, ly = float(lxs[b]), float(lys[b])
-        X = lx * c - ly * s + x
-        Y = lx * s + ly * c + y
-        gu = (X - pos_x) / res - 0.5
-        gv = (Y - pos_y) / res - 0.5
+        gu, gv = grid_uv(lx, ly, c, s, x, y, res, pos_x, pos_y)
         fu, fv = _floor(gu), _floor(gv)
         if not (fu >= 0.0 and fu <= float(W - 2) and fv >= 0.0 and fv <= float(H - 2)):
             continue
@@ -160,3 +165,64 @@ def perturbed(true_pose, n: int, seed: int = 1) -> np.ndarray:
     rng = np.random.default_rng(seed)
     d = np.stack([rng.uniform(-1.5, 1.5, n) * RES, rng.uniform(-1.5, 1.5, n) * RES, np.radians(rng.uniform(-3.0, 3.0, n))], 1)
     return (np.asarray(true_pose, np.float64) + d).astype(np.float32)
+
+
+# ---- the same room on a map that is not square ------------------------------------------------------------------------------------------
+# 173 x 140 cells: W != H, W odd (the 16-byte row pairs start at addresses 0 and 8 mod 16 in alternate rows); an origin whose components
+# are unequal, non-zero and no multiples of the cell size.  The world's room (half size 2.56 m) lies inside.
+NS_W, NS_H = 173, 140
+NS_POS = (-3.12, -3.37)
+
+
+def ns_size(W: int = NS_W, H: int = NS_H):
+    """the metres that make a map of W x H cells"""
+    return ((W - 0.4) * RES, (H - 0.4) * RES)
+
+
+@functools.lru_cache(maxsize=None)
+def room_ns(W: int = NS_W, H: int = NS_H, pos=NS_POS, scans=(0, 1, 2, 3, 4)):
+    """(grid, logData, likelihood field, trace): a W x H map at 0.05 m and origin pos built with the oracle from the given scans of the
+    synthetic trace.  Shared between tests: nobody writes to what it returns"""
+    tr = synth.make_trace(EXT, RES, 120, T=8, seed=7)
+    g = orc.Grid(*ns_size(W, H), RES, pos[0], pos[1])
+    assert (g.W, g.H) == (W, H)
+    log = g.new_log()
+    for t in scans:
+        g.integrate(log, tr.scans[t], tr.poses[t])
+    lik = g.build_likelihood(log)
+    for a in (log, lik, tr.poses, tr.scans):
+        a.setflags(write=False)
+    return g, log, lik, tr
+
+
+@functools.lru_cache(maxsize=None)
+def discriminating_case(W: int, H: int, pos, iters: int):
+    """(start poses [37][3], the expectation for scan SCAN on the W x H room at pos, n_wh, n_pos).  Asserts that the restatement given
+    (H, W) for (W, H), or the origin's components exchanged, ends at other poses for n_wh > 0 and n_pos > 0 of the 37 (every read of
+    the exchanged runs stays inside the H * W values): a device that made either mistake could not equal the expectation"""
+    g, _, lik, tr = room_ns(W, H, pos)
+    start = perturbed(tr.poses[SCAN], 37, seed=22)
+    start.setflags(write=False)
+    prm = dict(default_params(), iters=iters)
+    want = align(lik, W, H, RES, pos[0], pos[1], tr.scans[SCAN], start, prm)
+    swapped_wh = align(lik, H, W, RES, pos[0], pos[1], tr.scans[SCAN], start, prm)[0]
+    swapped_pos = align(lik, W, H, RES, pos[1], pos[0], tr.scans[SCAN], start, prm)[0]
+    n_wh = int((bits(swapped_wh) != bits(want[0])).any(axis=1).sum())
+    n_pos = int((bits(swapped_pos) != bits(want[0])).any(axis=1).sum())
+    assert n_wh > 0 and n_pos > 0, (W, H, pos, iters, n_wh, n_pos)
+    return start, want, n_wh, n_pos
+
+
+# ---- comparing a device result with the restatement: equality, never a tolerance --------------------------------------------------------
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same(got, want, where=""):
+    """(poses, records) from the device against (poses, record arrays) from the restatement"""
+    (gp, gr), (wp, wr) = got, want
+    assert np.array_equal(bits(gp).reshape(-1, 3), bits(wp)), where
+    for k in RECORD_INTS:
+        assert np.array_equal(gr[k].reshape(-1), wr[k]), (where, k)
+    for k in ("score0", "score", "H"):
+        assert np.array_equal(gr[k].reshape(wr[k].shape), wr[k], equal_nan=True), (where, k)

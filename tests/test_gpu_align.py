@@ -18,18 +18,7 @@ POS = (-EXT / 2, -EXT / 2)
 NAN, INF = math.nan, math.inf
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same(got, want, where=""):
-    """(poses, records) from the device against (poses, record arrays) from the restatement"""
-    (gp, gr), (wp, wr) = got, want
-    assert np.array_equal(bits(gp).reshape(-1, 3), bits(wp)), where
-    for k in ax.RECORD_INTS:
-        assert np.array_equal(gr[k].reshape(-1), wr[k]), (where, k)
-    for k in ("score0", "score", "H"):
-        assert np.array_equal(gr[k].reshape(wr[k].shape), wr[k], equal_nan=True), (where, k)
+bits, same = ax.bits, ax.same                                                  # (shared with tests/test_gpu_align_shapes.py)
 
 
 def expect(L, scan, poses, prm=None, shape=(128, 128)):
