@@ -3,7 +3,9 @@ flood-fill expectation of tests/_frontier_expect.py on logData that was construc
 the feature is all-integer and every output is unique.  A request must see the map as a download would return it at that moment and
 must change no later result of its handle.
 
-The map is 200 x 136 cells: 4 x 3 tiles of 64 x 64 cells, ragged on both far edges (8 columns, 8 rows)."""
+The map is 200 x 136 cells: 4 x 3 tiles of 64 x 64 cells, ragged on both far edges (8 columns, 8 rows).  That is 544 plane words: the
+scan of the root plane stays inside one block of GMS_SCAN words here.  tests/test_gpu_scan_levels.py runs the regions on maps of more
+than one scan block."""
 import ctypes as C
 import functools
 import math

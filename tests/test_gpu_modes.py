@@ -3,8 +3,11 @@ cells_of_poses and the header's heading rule, a flood fill over a Python set, th
 is array_equal, the doubles as uint64 views: there is no tolerance.  The cached trig the sums read is what the handle's pose_trig makes
 of the headings (Map.debug_f32; tests/test_gpu_parity.py holds that against the oracle's libm).
 
-The shapes are the smallest that can go wrong: a 64 x 64 map at 0.05 m, and a 70 x 50 one whose last bins are partial under bin_cells
-4 and 7; filters of 1, 255, 256, 257 and 1000 particles around the 256 lanes of the sums' rows."""
+The shapes are small: a 64 x 64 map at 0.05 m, and a 70 x 50 one whose last bins are partial under bin_cells 4 and 7; filters of 1,
+255, 256, 257 and 1000 particles around the 256 lanes of the sums' rows.  They are the smallest at which the binning, the unions and
+the sums can go wrong, not the scans: no table here holds more than 300 modes, and anchors lie in one round of the scan's top level.
+tests/test_gpu_scan_levels.py carries the scans past one block of the table, past one round of the bins and through a table that
+grows."""
 import ctypes as C
 
 import numpy as np
@@ -365,8 +368,13 @@ def test_refused_calls_leave_the_outputs_alone():
     pf_big = _filter(big, [[1.0, 1.0, 0.0]] * 300)
     assert call(host[0], pf_big._h, 0, GmsModes(1, 64, 1, 0), host[1], host[2], 4) == GMS_ERR_INVALID and b"2^22" in L.gms_last_error()
     assert (nf.value, no.value) == (-7, -9)
-    assert call(host[0], pf_big._h, 0, GmsModes(1, 46, 1, 0), host[1], host[2], 4) == 0 and (nf.value, no.value, rec["count"][0]) == (1, 0, 300)
-    lab[:], rec["count"], nf.value, no.value = 0xABCDEF01, -5, -7, -9
+    want, want_lab, want_out = _expect(pf_big, big, 1, 46)
+    assert call(host[0], pf_big._h, 0, GmsModes(1, 46, 1, 0), host[1], host[2], 4) == 0 and (nf.value, no.value) == (len(want), want_out) == (1, 0)
+    assert np.array_equal(lab, want_lab), "the accepted field of more than 2^20 bins: every label"
+    _same_records(rec[:1], want, "... and its one record")
+    lab[:], nf.value, no.value = 0xABCDEF01, -7, -9
+    rec[:] = np.zeros((), MODE_DTYPE)
+    rec["count"] = -5
     d_lab, d_rec = torch.full((301,), 7, dtype=torch.int32, device="cuda"), torch.full((4 * 14 + 1,), 7, dtype=torch.int64, device="cuda")
     assert call(L.gms_pf_modes_dev, pf._h, 0, ok, d_lab.data_ptr() + 2, d_rec.data_ptr(), 4) == GMS_ERR_INVALID and b"aligned" in L.gms_last_error()
     assert call(L.gms_pf_modes_dev, pf._h, 0, ok, d_lab.data_ptr(), d_rec.data_ptr() + 4, 4) == GMS_ERR_INVALID and b"aligned" in L.gms_last_error()
