@@ -164,8 +164,38 @@ class GmsAlignRecord(C.Structure):
     ]
 
 
+class GmsRollout(C.Structure):
+    """gms_rollout: a trajectory-rollout request (gridmapslam.h "trajectory rollouts")"""
+    _fields_ = [("max_range", C.c_int32), ("inflate", C.c_int32), ("mode", C.c_int32), ("filter", C.c_int32)]
+
+
+class GmsRolloutRec(C.Structure):
+    """gms_rollout_rec: one (start pose, candidate) record, 32 bytes"""
+    _fields_ = [
+        ("first_hit", C.c_uint16), ("hit_point", C.c_uint16), ("min_d2", C.c_uint16), ("best_step", C.c_uint16),
+        ("best_cost", C.c_uint16), ("end_cost", C.c_uint16), ("flags", C.c_uint16), ("pad", C.c_uint16),
+        ("last_x", C.c_int32), ("last_y", C.c_int32), ("start_x", C.c_int32), ("start_y", C.c_int32),
+    ]
+
+
+class GmsRolloutRisk(C.Structure):
+    """gms_rollout_risk: one candidate over a filter's particles, 32 bytes"""
+    _fields_ = [
+        ("n_hit", C.c_uint32), ("n_start_blocked", C.c_uint32), ("min_first_hit", C.c_uint32), ("pad", C.c_uint32),
+        ("sum_first_hit", C.c_uint64), ("pad2", C.c_uint64),
+    ]
+
+
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
+ROLLOUT_STEP_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("c", "<f4"), ("s", "<f4")])     # gms_rollout_step
+ROLLOUT_DTYPE = np.dtype([(n, "<u2" if t is C.c_uint16 else "<i4") for n, t in GmsRolloutRec._fields_])     # gms_rollout_rec
+ROLLOUT_RISK_DTYPE = np.dtype([(n, "<u8" if t is C.c_uint64 else "<u4") for n, t in GmsRolloutRisk._fields_])     # gms_rollout_risk
+assert ROLLOUT_DTYPE.itemsize == C.sizeof(GmsRolloutRec) == 32 and ROLLOUT_RISK_DTYPE.itemsize == C.sizeof(GmsRolloutRisk) == 32
+assert ROLLOUT_STEP_DTYPE.itemsize == 16 and C.sizeof(GmsRollout) == 16
+GMS_ROLLOUT_MAX_K, GMS_ROLLOUT_MAX_T, GMS_ROLLOUT_MAX_F = 4096, 256, 64
+GMS_ROLLOUT_CANDIDATES = 16      # candidates a rollout workgroup takes (gms_rollout_candidates_per_workgroup() of the library as built)
+GMS_ROLLOUT_HIT_OUTSIDE, GMS_ROLLOUT_HIT_RANGE, GMS_ROLLOUT_HIT_BLOCKED, GMS_ROLLOUT_START_BLOCKED = 1, 2, 4, 8      # gms_rollout_rec.flags
 LOCATE_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsLocateRec._fields_])     # gms_locate_rec
 assert LOCATE_DTYPE.itemsize == C.sizeof(GmsLocateRec) == 16 and C.sizeof(GmsLocate) == 48
 GMS_LOCATE_SKIP = -32768
@@ -428,6 +458,16 @@ def load() -> C.CDLL:
     sig("gms_map_align_dev", C.c_int, vp, i32, vp, i32, vp, i32, ap, vp, vp)
     sig("gms_pf_align", C.c_int, vp, vp, i32, ap, vp)
     sig("gms_pf_align_dev", C.c_int, vp, vp, i32, ap, vp)
+    rop = C.POINTER(GmsRollout)
+    sig("gms_rollout_check", C.c_int, rop, i32, i32, i32)
+    sig("gms_rollout_arcs", C.c_int, vp, vp, i32, f64, i32, vp)
+    sig("gms_rollout_candidates_per_workgroup", C.c_int)
+    sig("gms_map_rollout", C.c_int, vp, i32, rop, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp)
+    sig("gms_map_rollout_dev", C.c_int, vp, i32, rop, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp)
+    sig("gms_slam_rollout", C.c_int, vp, i32, rop, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp)
+    sig("gms_slam_rollout_dev", C.c_int, vp, i32, rop, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp)
+    sig("gms_pf_rollout", C.c_int, vp, rop, vp, i32, i32, vp, i32, vp)
+    sig("gms_pf_rollout_dev", C.c_int, vp, rop, vp, i32, i32, vp, i32, vp)
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

@@ -14,10 +14,11 @@ LIB = os.path.join(LIBDIR, "libgridmapslam.so")
 # gms_fused_kernels.hip is the device translation unit: it includes gms_map_kernels.hip, gms_pf_kernels.hip and gms_slam_kernels.hip;
 # gms_query.hip (what the map queries share: checks, bit planes, staging), gms_cast.hip (predicted scans), gms_gain.hip (view gain),
 # gms_clearance.hip (clearance fields), gms_reach.hip (cost-to-go fields), gms_frontier.hip (frontier regions), gms_scatter.hip
-# (particle seeding), gms_locate.hip (global scan matching), gms_modes.hip (pose modes), gms_beams.hip (the beam sensor model) and
-# gms_align.hip (continuous scan alignment) are units of their own, kernels and C-ABI
+# (particle seeding), gms_locate.hip (global scan matching), gms_modes.hip (pose modes), gms_beams.hip (the beam sensor model),
+# gms_align.hip (continuous scan alignment) and gms_rollout.hip (trajectory rollouts) are units of their own, kernels and C-ABI
 SOURCES = ["gms_host.hip", "gms_slam_host.hip", "gms_fused_kernels.hip", "gms_query.hip", "gms_cast.hip", "gms_gain.hip", "gms_clearance.hip",
-           "gms_reach.hip", "gms_frontier.hip", "gms_scatter.hip", "gms_locate.hip", "gms_modes.hip", "gms_beams.hip", "gms_align.hip"]
+           "gms_reach.hip", "gms_frontier.hip", "gms_scatter.hip", "gms_locate.hip", "gms_modes.hip", "gms_beams.hip", "gms_align.hip",
+           "gms_rollout.hip"]
 # -ffp-contract=off: the reference (JVM) never fuses a multiply with an add; parity depends on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
          "-shared", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]

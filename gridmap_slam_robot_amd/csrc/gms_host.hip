@@ -363,6 +363,10 @@ int gms_map_create(const gms_params *p, gms_map **out) {
         m->cast_walk_mem = cw_env && cw_env[0] == 'm';
         const char *gw_env = getenv("GMS_GAIN_WALK");
         m->gain_walk_mem = gw_env && gw_env[0] == 'm';
+        const char *rw_env = getenv("GMS_ROLLOUT_WALK");                       // the rollouts' (gms_rollout.hip)
+        m->rollout_walk_mem = rw_env && rw_env[0] == 'm';
+        const char *rc_env = getenv("GMS_ROLLOUT_CPW");                        // candidates per rollout workgroup (tools/rollout_probe.py)
+        m->rollout_cpw = rc_env && rc_env[0] ? std::min(256, std::max(1, atoi(rc_env))) : GMS_ROLLOUT_CANDIDATES;
         const char *ss_env = getenv("GMS_SCATTER_SHIFT");                      // a coarser staged search than the plane asks for (tests; gms_scatter.hip)
         m->scatter_shift = ss_env ? std::min(20, std::max(0, atoi(ss_env))) : 0;
         const char *ll_env = getenv("GMS_LOCATE_LEVELS");                      // the scan matcher's top level, 0 = exhaustive (tests; gms_locate.hip)

@@ -122,6 +122,8 @@ struct gms_map {
     struct { uint32_t *d; int32_t current; } plane[2];
     int32_t cast_walk_mem;    // casts walk memory even where their window or class plane fits the LDS (GMS_CAST_WALK=mem: tests)
     int32_t gain_walk_mem;    // view gains read plane bits from memory even where the plane windows fit the LDS (GMS_GAIN_WALK=mem: tests)
+    int32_t rollout_walk_mem; // rollouts read plane bits from memory instead of the LDS window (GMS_ROLLOUT_WALK=mem: tests)
+    int32_t rollout_cpw;      // candidates a rollout workgroup takes: GMS_ROLLOUT_CANDIDATES (GMS_ROLLOUT_CPW = 1 .. 256: tools/rollout_probe.py)
     int64_t cast_plane_builds;    // launches of the GMS_CLEAR_OCCUPIED plane's pre-pass so far (tests: an unchanged map is not packed again)
     uint32_t *d_clear_scratch;    // [H][gms_plane_wpr] a gms_slam's queries: the shown particle's plane, packed per request (gms_slam_plane)
     // cost-to-go fields (gms_reach.hip); everything below is allocated by the first field that needs it and only ever grows
@@ -539,7 +541,8 @@ void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_o
 
 // ---- map queries: views, predicted scans (gms_cast.hip), view gain (gms_gain.hip), clearance fields (gms_clearance.hip), cost-to-go fields
 // (gms_reach.hip), frontier regions (gms_frontier.hip), particle seeding (gms_scatter.hip), global scan matching (gms_locate.hip), pose modes
-// (gms_modes.hip) and the beam sensor model (gms_beams.hip: beside cast, on the base alone).  The layering: the query base (gms_query.hip:
+// (gms_modes.hip), the beam sensor model (gms_beams.hip: beside cast, on the base alone) and trajectory rollouts (gms_rollout.hip: on reach,
+// whose blocked plane they test).  The layering: the query base (gms_query.hip:
 // everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier, scatter and locate (they inflate
 // with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only) ----
 struct gms_slam;

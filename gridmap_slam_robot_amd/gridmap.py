@@ -378,6 +378,64 @@ def reach_metres(field, resolution: float) -> np.ndarray:
     return out
 
 
+def _rollout_table(arcs) -> np.ndarray:
+    """arcs as the ROLLOUT_STEP_DTYPE [K][T] table the library takes: such records, or floats [K][T][4] = (dx, dy, c, s)"""
+    a = np.asarray(arcs)
+    if a.dtype != _lib.ROLLOUT_STEP_DTYPE:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError(f"rollout: arcs must be [K][T] steps (dx, dy, c, s), not {a.shape}")
+        a = a.view(_lib.ROLLOUT_STEP_DTYPE).reshape(a.shape[:2])
+    if a.ndim != 2:
+        raise ValueError(f"rollout: arcs must be [K][T] steps, not {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def rollout_arcs(v, omega, dt: float, T: int) -> np.ndarray:
+    """The arc table of K unicycle commands (gms_rollout_arcs, the library's C helper, so that every host gets the same table):
+    ROLLOUT_STEP_DTYPE [K][T], step j of command k the pose after (j + 1) * dt seconds at speed v[k] (m/s) and turn rate omega[k]
+    (rad/s) in the frame of the start pose; the straight line where |omega| < 1e-9.  What rollout() and rollout_risk() take."""
+    vv, ww = np.ascontiguousarray(v, dtype=np.float64).reshape(-1), np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    if len(vv) != len(ww):
+        raise ValueError(f"rollout_arcs: {len(vv)} speeds and {len(ww)} turn rates")
+    out = np.empty((len(vv), max(int(T), 0)), dtype=_lib.ROLLOUT_STEP_DTYPE)
+    check(load().gms_rollout_arcs(ptr(vv), ptr(ww), len(vv), float(dt), int(T), ptr(out)))
+    return out
+
+
+def footprint_box(length: float, width: float, spacing: float) -> np.ndarray:
+    """Outline points of a rectangular robot centred on its origin, length along x and width along y (metres), float32 [F][2]: each
+    side divided into ceil(side / spacing) equal parts, the corners once each, counter-clockwise from (-length / 2, -width / 2).  The
+    centre is not listed: rollouts always test it.  spacing at most the map's resolution leaves no cell of the outline untested.
+    ValueError where that takes more than GMS_ROLLOUT_MAX_F points."""
+    if not (length > 0 and width > 0 and spacing > 0):
+        raise ValueError("footprint_box: length, width and spacing must be > 0")
+    nx, ny = max(int(math.ceil(length / spacing)), 1), max(int(math.ceil(width / spacing)), 1)
+    hx, hy = length / 2.0, width / 2.0
+    xs, ys = [-hx + length * i / nx for i in range(nx)], [-hy + width * i / ny for i in range(ny)]
+    pts = [(x, -hy) for x in xs] + [(hx, y) for y in ys] + [(-x, hy) for x in xs] + [(-hx, -y) for y in ys]
+    if len(pts) > _lib.GMS_ROLLOUT_MAX_F:
+        raise ValueError(f"footprint_box: {len(pts)} points, at most {_lib.GMS_ROLLOUT_MAX_F} are taken: use a coarser spacing")
+    return np.asarray(pts, dtype=np.float32)
+
+
+def rollout_pick(records, T: Optional[int] = None, min_d2: int = 0, w_cost: float = 1.0, w_clear: float = 0.0) -> int:
+    """The index of the best candidate among ONE start pose's rollout records [K], plain numpy, or -1 where none is admissible.
+    Admissible: the arc is collision-free over all its steps (first_hit == T; T None: the largest first_hit of the records), the
+    footprint does not collide at the start pose, and min_d2 along it is at least `min_d2` (squared cells; GMS_CLEAR_FAR passes).
+    The objective, larger is better: -w_cost * best_cost + w_clear * sqrt(min_d2), GMS_REACH_FAR and GMS_CLEAR_FAR taken as their
+    values 65535; argmax, ties to the smallest index."""
+    r = np.asarray(records).reshape(-1)
+    if not len(r):
+        return -1
+    full = int(r["first_hit"].max()) if T is None else int(T)
+    ok = (r["first_hit"] == full) & ((r["flags"] & _lib.GMS_ROLLOUT_START_BLOCKED) == 0) & (r["min_d2"] >= int(min_d2))
+    if not ok.any():
+        return -1
+    score = -float(w_cost) * r["best_cost"].astype(np.float64) + float(w_clear) * np.sqrt(r["min_d2"].astype(np.float64))
+    return int(np.argmax(np.where(ok, score, -np.inf)))
+
+
 def _frontier_cost(cost, W: int, H: int):
     """a whole-map cost-to-go field (what reach() returns for the full rectangle) as the contiguous uint16 [H][W] the library takes"""
     if cost is None:
@@ -533,6 +591,24 @@ def _query_gain(src: _Source, poses, probes, max_range: int, out, shown_out) -> 
     b = _beams_of(probes).reshape(-1)
     rec = np.empty(len(p), dtype=_lib.GAIN_DTYPE)
     return (rec,) + src.host("gain", C.byref(g), ptr(p), len(p), ptr(b), len(b), ptr(rec))
+
+
+def _query_rollout(src: _Source, poses, arcs, points, max_range: int, inflate: int, not_free: bool, clear, cost, out, shown_out) -> tuple:
+    """poses None (a particle's map alone): the shown particle's own pose.  out given: the device form -- poses = (device address, P)
+    or None, arcs = (device address, K, T), points = (device address, F) or None, clear / cost torch device tensors or None"""
+    r = _lib.GmsRollout(int(max_range), int(inflate), _obstacles(not_free), src.filter)
+    if out is not None:
+        (dev_poses, P), (dev_arcs, K, T), (dev_points, F) = poses or (None, 0), arcs, points or (None, 0)
+        fields = [_device_ptr("rollout", n, f, 2 * src.W * src.H, itemsize=2, optional=True) for n, f in (("clear", clear), ("cost", cost))]
+        return (out,) + src.dev("rollout", C.byref(r), C.c_void_p(dev_poses), int(P), C.c_void_p(dev_arcs), int(K), int(T), C.c_void_p(dev_points), int(F),
+                                *fields, _device_ptr("rollout", "out", out, _lib.ROLLOUT_DTYPE.itemsize * max(int(P), 1) * int(K)), shown_out=shown_out)
+    p = None if poses is None and src.shows else np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+    a = _rollout_table(arcs)
+    f = np.zeros((0, 2), dtype=np.float32) if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    cl, co = _frontier_cost(clear, src.W, src.H), _frontier_cost(cost, src.W, src.H)
+    rec = np.empty((1 if p is None else len(p), a.shape[0]), dtype=_lib.ROLLOUT_DTYPE)
+    return (rec,) + src.host("rollout", C.byref(r), None if p is None else ptr(p), 0 if p is None else len(p), ptr(a), a.shape[0], a.shape[1],
+                             ptr(f) if len(f) else None, len(f), None if cl is None else ptr(cl), None if co is None else ptr(co), ptr(rec))
 
 
 def _query_locate(src: _Source, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
@@ -750,6 +826,22 @@ class GridMap:
     def gain_dev(self, dev_poses: int, P: int, dev_probes: int, B: int, out, max_range: int, mi: int = 0):
         """gain() with device pointers; out: a contiguous torch device tensor of P * 32 bytes, written on the handle's stream"""
         return _query_gain(self._src(mi), (dev_poses, P), (dev_probes, B), max_range, out, None)[0]
+
+    def rollout(self, poses, arcs, points=None, max_range: int = 255, inflate: int = 0, not_free: bool = True, clear=None, cost=None,
+                mi: int = 0) -> np.ndarray:
+        """Trajectory rollouts (gridmapslam.h "trajectory rollouts") from each of the start poses [P][3] in map mi: arcs [K][T]
+        (rollout_arcs()) are the candidates' poses in the start pose's frame, points [F][2] the footprint (footprint_box(); the
+        centre is always tested as well).  A point collides off the map, farther than max_range cells from the start cell, or on a
+        cell that reach() would block for inflate / not_free.  clear / cost: whole-map fields of clearance() / reach(), or None.
+        Returns gms_rollout_rec records [P][K] (ROLLOUT_DTYPE: first_hit, hit_point, min_d2, best_step, best_cost, end_cost, flags,
+        pad, last_x, last_y, start_x, start_y); rollout_pick() chooses among one pose's."""
+        return _query_rollout(self._src(mi), poses, arcs, points, max_range, inflate, not_free, clear, cost, None, None)[0]
+
+    def rollout_dev(self, dev_poses: int, P: int, dev_arcs: int, K: int, T: int, dev_points: int, F: int, out, max_range: int = 255, inflate: int = 0,
+                    not_free: bool = True, clear=None, cost=None, mi: int = 0):
+        """rollout() with device pointers (arcs 16-byte aligned); clear / cost: torch device uint16-sized tensors [H][W] or None; out: a
+        contiguous torch device tensor of P * K * 32 bytes, written on the handle's stream"""
+        return _query_rollout(self._src(mi), (dev_poses, P), (dev_arcs, K, T), (dev_points, F), max_range, inflate, not_free, clear, cost, out, None)[0]
 
     def locate(self, offsets, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64, free_only: bool = True,
                mi: int = 0, full: bool = False):
@@ -1361,6 +1453,26 @@ class ParticleFilter:
         check(load().gms_pf_align_dev(self._h, C.c_void_p(dev_beams), int(B), C.byref(prm), out))
         return records_out
 
+    def rollout_risk(self, arcs, points=None, max_range: int = 255, inflate: int = 0, not_free: bool = True) -> np.ndarray:
+        """GridMap.rollout() from EVERY particle's pose, read on the device, counted per candidate (gms_pf_rollout): gms_rollout_risk
+        records [K] ([n_maps][K] on a batched handle; ROLLOUT_RISK_DTYPE: n_hit, n_start_blocked, min_first_hit, pad, sum_first_hit,
+        pad2).  After a resample the weights are equal and n_hit / n is the collision probability of the command.  A shard counts
+        its own particles.  The filter is not changed."""
+        a = _rollout_table(arcs)
+        f = np.zeros((0, 2), dtype=np.float32) if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        r = _lib.GmsRollout(int(max_range), int(inflate), _obstacles(not_free), 0)
+        out = np.empty(self._pshape()[:-1] + (a.shape[0],), dtype=_lib.ROLLOUT_RISK_DTYPE)
+        check(load().gms_pf_rollout(self._h, C.byref(r), ptr(a), a.shape[0], a.shape[1], ptr(f) if len(f) else None, len(f), ptr(out)))
+        return out
+
+    def rollout_risk_dev(self, dev_arcs: int, K: int, T: int, dev_points: int, F: int, out, max_range: int = 255, inflate: int = 0, not_free: bool = True):
+        """rollout_risk() with device pointers (arcs 16-byte aligned); out: a contiguous torch device tensor of n_maps * K * 32 bytes.
+        Runs on the handle's stream and synchronises nothing."""
+        r = _lib.GmsRollout(int(max_range), int(inflate), _obstacles(not_free), 0)
+        check(load().gms_pf_rollout_dev(self._h, C.byref(r), C.c_void_p(dev_arcs), int(K), int(T), C.c_void_p(dev_points), int(F),
+                                        _device_ptr("rollout_risk_dev", "out", out, _lib.ROLLOUT_RISK_DTYPE.itemsize * self.n_maps * int(K))))
+        return out
+
     def set_refine(self, on: bool = True):
         """scan steps (slam_update*) run findBestPose on every particle before weighting it (SLAM.java:96-97)."""
         check(load().gms_pf_set_refine(self._h, 1 if on else 0))
@@ -1635,6 +1747,10 @@ class _SlamHandle:
         """gms_slam_gain[_dev]: (records, shown)"""
         return _query_gain(self._src("gain", which, filter), poses, probes, max_range, out, shown_out)
 
+    def _rollout(self, which, filter: int, poses, arcs, points, max_range: int, inflate: int, not_free: bool, clear, cost, out, shown_out):
+        """gms_slam_rollout[_dev]: (records, shown); poses None: the shown particle's own pose"""
+        return _query_rollout(self._src("rollout", which, filter), poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
+
     def _locate(self, which, filter: int, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
                 shown_out):
         """gms_slam_locate[_dev]: (records, shown), or (out, n_out, shown_out)"""
@@ -1841,6 +1957,19 @@ class SLAMParticleMaps(_SlamHandle):
         update).  out / shown_out: torch device tensors, poses and probes then (device address, P) and (device address, B); nothing
         is synchronised."""
         return self._gain(which, 0, poses, probes, max_range, out, shown_out)
+
+    def rollout(self, arcs, points=None, poses=None, which="strongest", max_range: int = 255, inflate: int = 0, not_free: bool = True, clear=None,
+                cost=None):
+        """Trajectory rollouts in particle `which`'s OWN map (GridMap.rollout's records): (records [P][K], shown).  which = a particle
+        index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  poses=None: ONE start
+        pose, the shown particle's own, read on the device; records [1][K]."""
+        return self._rollout(which, 0, poses, arcs, points, max_range, inflate, not_free, clear, cost, None, None)
+
+    def rollout_dev(self, out, arcs, points=None, poses=None, which="strongest", max_range: int = 255, inflate: int = 0, not_free: bool = True,
+                    clear=None, cost=None, shown_out=None):
+        """rollout() on the device: arcs = (device address, K, T), points = (device address, F) or None, poses = (device address, P) or
+        None, clear / cost / out / shown_out torch device tensors; (out, shown_out), nothing is synchronised"""
+        return self._rollout(which, 0, poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
 
     def locate(self, offsets, which="strongest", rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
                free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):
@@ -2064,6 +2193,17 @@ class SLAMParticleMapsBatch(_SlamHandle):
         """SLAMParticleMaps.gain for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
         the handle-wide slot filter * num_particles + k in whose map the poses were judged, as view() reports it"""
         return self._gain(self._local(filter, which), filter, poses, probes, max_range, out, shown_out)
+
+    def rollout(self, arcs, points=None, poses=None, which="strongest", filter: int = 0, max_range: int = 255, inflate: int = 0, not_free: bool = True,
+                clear=None, cost=None):
+        """SLAMParticleMaps.rollout for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
+        the handle-wide slot filter * num_particles + k in whose map the arcs were rolled, as view() reports it"""
+        return self._rollout(self._local(filter, which), filter, poses, arcs, points, max_range, inflate, not_free, clear, cost, None, None)
+
+    def rollout_dev(self, out, arcs, points=None, poses=None, which="strongest", filter: int = 0, max_range: int = 255, inflate: int = 0,
+                    not_free: bool = True, clear=None, cost=None, shown_out=None):
+        """SLAMParticleMaps.rollout_dev for filter `filter`"""
+        return self._rollout(self._local(filter, which), filter, poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
 
     def locate(self, offsets, which="strongest", filter: int = 0, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
                free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):

@@ -1192,6 +1192,131 @@ int gms_map_align_dev(gms_map *m, int32_t mi, const gms_beam *dev_beams, int32_t
 int gms_pf_align(gms_pf *pf, const gms_beam *beams, int32_t B, const gms_align_params *params, gms_align_record *records);
 int gms_pf_align_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B, const gms_align_params *params, gms_align_record *dev_records);
 
+/* ---- trajectory rollouts: which velocity command can be sent without hitting something ---------------------------------------------
+ * The inner loop of a local planner (dynamic window, lattice primitives): K candidate arcs, each sampled at T steps, the robot's
+ * footprint tested against the inflated obstacle plane at every step, and the clearance and cost-to-go fields read along the way.  This
+ * library's own definition (the reference has no such method); every result is an integer and unique.
+ *
+ * THE ARC TABLE  arcs [K][T] of gms_rollout_step {dx, dy, c, s} (four floats, 16 bytes): the robot's pose at step t of candidate k in
+ *                the frame of the START pose -- a translation in metres and the cosine and sine of the heading change.  The table is the
+ *                caller's, made on the host (gms_rollout_arcs makes unicycle arcs), like gms_map_locate's offsets and
+ *                gms_pf_score_beams' factors: the device takes no trig per step.  1 <= K <= GMS_ROLLOUT_MAX_K, 1 <= T <= GMS_ROLLOUT_MAX_T.
+ * THE FOOTPRINT  points [F][2] floats (fx, fy) in the robot frame, metres, 0 <= F <= GMS_ROLLOUT_MAX_F (F == 0: points may be NULL).  The
+ *                robot's centre (0, 0) is always tested as well, LAST, and has point index F.
+ * STEP ARITHMETIC  for a step {dx, dy, c, s} and a point (fx, fy), all widened to double, every product and sum rounded on its own
+ *                (nothing is contracted):  qx = dx + (c*fx - s*fy),  qy = dy + (s*fx + c*fy);  the world point is Transform.transformX /
+ *                transformY of (qx, qy) under the start pose (x, y, theta) with Transform.fromRobotToWorld's float-rounded trig, what
+ *                every other entry point uses:  wx = qx*C - qy*S + x,  wy = qx*S + qy*C + y  (left to right);  the cell is
+ *                gms_map_clearance_poses':  (int)((wx - position.x) / resolution), likewise y, with Java's cast (toward zero, NaN -> 0,
+ *                saturating).  The IDENTITY step is {0, 0, 1, 0}; the START CELL is the centre's cell under it.
+ * COLLISION      a point collides at a step if its cell is, tested in this order,
+ *                  GMS_ROLLOUT_HIT_OUTSIDE   off the map;
+ *                  GMS_ROLLOUT_HIT_RANGE     farther than max_range cells, Chebyshev, from the start cell (1 <= max_range <= 255: the view
+ *                                            gain's cut);
+ *                  GMS_ROLLOUT_HIT_BLOCKED   BLOCKED as the cost-to-go fields define it for `mode` and `inflate`.
+ * THE RECORD     per (start pose p, candidate k) one gms_rollout_rec, out [P][K]:
+ *                  first_hit   the smallest step at which any point collides; T if none.
+ *                  hit_point   the smallest colliding point index at that step; 0xFFFF if none.
+ *                  flags       the kind of that first hit (of point hit_point at step first_hit; 0 if none), and GMS_ROLLOUT_START_BLOCKED
+ *                              if any point collides under the identity step -- at the start pose itself; this is independent of
+ *                              first_hit.
+ *                  min_d2      the minimum of clear [H][W] -- a WHOLE-MAP clearance field, what gms_map_clearance returns for the full
+ *                              rectangle; may be NULL -- under the centre's cell over the steps < first_hit (the centre does not collide
+ *                              there, so its cell is on the map); GMS_CLEAR_FAR without a field or without such a step.
+ *                  best_step, best_cost   the smallest step < first_hit at which cost [H][W] -- a WHOLE-MAP cost-to-go field, the one
+ *                              gms_map_frontiers accepts; may be NULL -- is least under the centre's cell, and that cost (GMS_REACH_FAR
+ *                              if every such cell holds it: best_step is then the smallest such step, 0); 0xFFFF and GMS_REACH_FAR
+ *                              without a field or without such a step.
+ *                  end_cost    cost under the centre's cell at step first_hit - 1, the last collision-free one; GMS_REACH_FAR without a
+ *                              field or when first_hit == 0.
+ *                  last_x, last_y   the centre's cell at step first_hit - 1; the start cell when first_hit == 0.
+ *                  start_x, start_y the start cell.
+ * A non-finite pose, step or point is no error: the arithmetic above says which cell it lands in (a NaN coordinate: cell 0).
+ *
+ * "Sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment" (a deferred `logData +=` pass is applied
+ * first, an owed resampling copy is looked through), "changes no later result of its handle" and the argument checks before anything is
+ * enqueued (GMS_ERR_INVALID, nothing touched) are the casts' rules.
+ *
+ * How: the blocked plane is the cost-to-go fields' -- with inflate = 0 the map's plane of `mode` read in place and packed only when stale
+ * (gms_map_cast_plane_builds does not move for a current plane), with inflate > 0 their scratch plane.  One workgroup of 256 lanes per
+ * (start pose, block of GMS_ROLLOUT_CANDIDATES candidates) stages the square of side 2 * max_range + 1 around the start cell in LDS, one
+ * bit per cell, off-map cells set (at most 16 words x 511 rows, 33 KB), and the footprint beside it: outside, range and blocked are then
+ * one bounds test and one bit test.  One wavefront takes one candidate at a time: lanes own steps, 64 per pass, each lane loops over the
+ * F + 1 points, a ballot gives the first colliding step and ends the candidate's passes, and the minima in front of it are cross-lane
+ * reductions.  On a handle created with GMS_ROLLOUT_WALK=mem in the environment (tests) every look-up reads the plane in memory -- the
+ * same records either way. */
+#define GMS_ROLLOUT_MAX_K 4096
+#define GMS_ROLLOUT_MAX_T 256
+#define GMS_ROLLOUT_MAX_F 64
+#define GMS_ROLLOUT_CANDIDATES 16                             /* candidates a workgroup takes (the probe that chose it) */
+#define GMS_ROLLOUT_HIT_OUTSIDE 1u                            /* gms_rollout_rec.flags */
+#define GMS_ROLLOUT_HIT_RANGE 2u
+#define GMS_ROLLOUT_HIT_BLOCKED 4u
+#define GMS_ROLLOUT_START_BLOCKED 8u
+typedef struct gms_rollout_step {   /* 16 bytes */
+    float dx, dy;                   /* the translation, metres, in the start pose's frame */
+    float c, s;                     /* cosine and sine of the heading change */
+} gms_rollout_step;
+typedef struct gms_rollout {        /* 16 bytes */
+    int32_t max_range;              /* cells, 1 .. 255 */
+    int32_t inflate;                /* cells, 0 .. 255 */
+    int32_t mode;                   /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE */
+    int32_t filter;                 /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+} gms_rollout;
+typedef struct gms_rollout_rec {    /* 32 bytes */
+    uint16_t first_hit;             /*  0 */
+    uint16_t hit_point;             /*  2 */
+    uint16_t min_d2;                /*  4 */
+    uint16_t best_step;             /*  6 */
+    uint16_t best_cost;             /*  8 */
+    uint16_t end_cost;              /* 10 */
+    uint16_t flags;                 /* 12 */
+    uint16_t pad;                   /* 14: always 0 */
+    int32_t last_x, last_y;         /* 16, 20 */
+    int32_t start_x, start_y;       /* 24, 28 */
+} gms_rollout_rec;
+typedef struct gms_rollout_risk {   /* 32 bytes: one candidate over a filter's particles */
+    uint32_t n_hit;                 /*  0: particles with first_hit < T */
+    uint32_t n_start_blocked;       /*  4: particles whose footprint collides at their own pose */
+    uint32_t min_first_hit;         /*  8: the smallest first_hit (T if no particle hits) */
+    uint32_t pad;                   /* 12: always 0 */
+    uint64_t sum_first_hit;         /* 16: the sum of first_hit over the particles; the mean is sum / n, the caller's division */
+    uint64_t pad2;                  /* 24: always 0 */
+} gms_rollout_risk;
+/* Pure host code: the ranges of K, T and F above and of max_range, inflate and mode. */
+int gms_rollout_check(const gms_rollout *r, int32_t K, int32_t T, int32_t F);
+/* Pure host code: the table of K unicycle arcs, out [K][T].  Step j of candidate k is the pose after time t = (j + 1) * dt (dt finite,
+ * > 0) at speed v[k] (m/s) and turn rate omega[k] (rad/s), libm in double, each value rounded to float:  th = omega * t;  c = cos(th),
+ * s = sin(th);  with r = v / omega:  dx = r * sin(th),  dy = r * (1 - cos(th));  where |omega| < 1e-9 the straight line dx = v * t,
+ * dy = 0.  In C so that every host language gets the same table. */
+int gms_rollout_arcs(const double *v, const double *omega, int32_t K, double dt, int32_t T, gms_rollout_step *out);
+/* GMS_ROLLOUT_CANDIDATES of the library as built. */
+int gms_rollout_candidates_per_workgroup(void);
+/* Map mi of a shared or batched map: P start poses (poses [P][3] = x, y, theta; 1 <= P <= GMS_MAX_PARTICLES), the same arcs and
+ * footprint for each; clear and cost may each be NULL; out [P][K].  The host form stages its inputs (the fields too) through the views'
+ * buffer, reads the records back and synchronises; _dev takes device pointers (arcs and out 16-byte aligned, poses and points 4-byte,
+ * the fields 2-byte), runs on the handle's stream and synchronises nothing. */
+int gms_map_rollout(gms_map *m, int32_t mi, const gms_rollout *r, const float *poses, int32_t P, const gms_rollout_step *arcs, int32_t K, int32_t T,
+                    const float *points, int32_t F, const uint16_t *clear, const uint16_t *cost, gms_rollout_rec *out);
+int gms_map_rollout_dev(gms_map *m, int32_t mi, const gms_rollout *r, const float *dev_poses, int32_t P, const gms_rollout_step *dev_arcs, int32_t K, int32_t T,
+                        const float *dev_points, int32_t F, const uint16_t *dev_clear, const uint16_t *dev_cost, gms_rollout_rec *dev_out);
+/* The per-particle filter: the rollouts in the map of the shown particle.  `which`, GMS_VIEW_STRONGEST, r->filter, *shown (may be
+ * NULL; _dev: a device int32_t *) and the GMS_ERR_STATE cases are gms_slam_view's; particle and generation are picked on the device.
+ * Here only, P == 0 with poses NULL means: ONE start pose, the SHOWN particle's own, read on the device (gms_slam_reach's seed idiom);
+ * out is then [1][K]. */
+int gms_slam_rollout(gms_slam *s, int32_t which, const gms_rollout *r, const float *poses, int32_t P, const gms_rollout_step *arcs, int32_t K, int32_t T,
+                     const float *points, int32_t F, const uint16_t *clear, const uint16_t *cost, gms_rollout_rec *out, int32_t *shown);
+int gms_slam_rollout_dev(gms_slam *s, int32_t which, const gms_rollout *r, const float *dev_poses, int32_t P, const gms_rollout_step *dev_arcs, int32_t K, int32_t T,
+                         const float *dev_points, int32_t F, const uint16_t *dev_clear, const uint16_t *dev_cost, gms_rollout_rec *dev_out, int32_t *dev_shown);
+/* A shared-map filter: EVERY particle is a start pose, read from the filter's device poses, and the output is one gms_rollout_risk per
+ * candidate, out [K] (a batched handle: map i's particles in map i, out [n_maps][K]) -- n * K records would be hundreds of megabytes.
+ * The same kernel counts with integer atomics, so the result is unique whatever the scheduling.  After a resample the weights are equal
+ * and n_hit / n is the collision probability of the command; a weighted form is not offered.  A shard counts its own particles.
+ * GMS_ERR_STATE: the filter of a gms_slam (its particles live in their own maps).  r->filter is not read.  The filter is not changed. */
+int gms_pf_rollout(gms_pf *pf, const gms_rollout *r, const gms_rollout_step *arcs, int32_t K, int32_t T, const float *points, int32_t F, gms_rollout_risk *out);
+int gms_pf_rollout_dev(gms_pf *pf, const gms_rollout *r, const gms_rollout_step *dev_arcs, int32_t K, int32_t T, const float *dev_points, int32_t F,
+                       gms_rollout_risk *dev_out);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -170,6 +170,17 @@ public:
         check(gms_map_gain(h_, mi, &g, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data()));
         return out;
     }
+    /** Trajectory rollouts (gridmapslam.h "trajectory rollouts") from every start pose in map mi: arcs [K][T] (gms_rollout_arcs makes
+     *  unicycle arcs), points [F][2] the footprint, clear / cost whole-map fields or null; records [poses.size()][K], row-major. */
+    std::vector<gms_rollout_rec> rollout(const std::vector<Pose> &poses, const gms_rollout &req, const std::vector<gms_rollout_step> &arcs, int K, int T,
+                                         const std::vector<float> &points, const uint16_t *clear = nullptr, const uint16_t *cost = nullptr, int mi = 0) {
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        std::vector<gms_rollout_rec> out(poses.size() * (size_t)(K > 0 ? K : 0));
+        check(gms_map_rollout(h_, mi, &req, p.data(), (int32_t)poses.size(), arcs.data(), K, T, points.empty() ? nullptr : points.data(),
+                              (int32_t)(points.size() / 2), clear, cost, out.data()));
+        return out;
+    }
     /** The clearance field (gridmapslam.h "clearance fields") of map mi: per cell of c's rectangle the squared distance in cells to the
      *  nearest obstacle cell of the whole map, GMS_CLEAR_FAR beyond c.max_radius; [h][w] row-major */
     std::vector<uint16_t> clearance(const gms_clearance &c, int mi = 0) {
@@ -329,6 +340,13 @@ public:
         int32_t found = 0;
         check(gms_pf_modes_dev(h_, 0, &q, devLabels, devRecords, cap, &found, nOutside));
         return found;
+    }
+    /** GridMap::rollout from every particle's pose, counted per candidate (gms_pf_rollout): one gms_rollout_risk per candidate; after
+     *  a resample n_hit / size() is the collision probability of the command.  The filter is not changed. */
+    std::vector<gms_rollout_risk> rolloutRisk(const gms_rollout &req, const std::vector<gms_rollout_step> &arcs, int K, int T, const std::vector<float> &points) {
+        std::vector<gms_rollout_risk> out((size_t)(K > 0 ? K : 0));
+        check(gms_pf_rollout(h_, &req, arcs.data(), K, T, points.empty() ? nullptr : points.data(), (int32_t)(points.size() / 2), out.data()));
+        return out;
     }
     /** The beam sensor model (gridmapslam.h "beam sensor model"): every particle weighted by where the map's first wall lies on each
      *  beam's walk relative to the measured end point.  factors [2][behind + ahead + 2] host doubles (row 0: beams that missed, row 1:
@@ -585,6 +603,20 @@ public:
         rec.resize((size_t)n);
         if (shown) *shown = picked;
         return rec;
+    }
+    /** Trajectory rollouts in particle `which`'s own map (GridMap::rollout's records); no poses: ONE start pose, the shown particle's
+     *  own, read on the device.  *shown (may be null) receives the particle in whose map the arcs were rolled */
+    std::vector<gms_rollout_rec> rollout(const std::vector<Pose> &poses, const gms_rollout &req, const std::vector<gms_rollout_step> &arcs, int K, int T,
+                                         const std::vector<float> &points, const uint16_t *clear = nullptr, const uint16_t *cost = nullptr,
+                                         int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        std::vector<gms_rollout_rec> out((poses.empty() ? 1 : poses.size()) * (size_t)(K > 0 ? K : 0));
+        int32_t picked = 0;
+        check(gms_slam_rollout(h_, which, &req, poses.empty() ? nullptr : p.data(), (int32_t)poses.size(), arcs.data(), K, T,
+                               points.empty() ? nullptr : points.data(), (int32_t)(points.size() / 2), clear, cost, out.data(), &picked));
+        if (shown) *shown = picked;
+        return out;
     }
     /** The view gain of the caller's candidate poses in particle `which`'s own map (GridMap::gain's records); *shown (may be null)
      *  receives the particle in whose map they were judged */
