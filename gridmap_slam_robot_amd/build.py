@@ -15,7 +15,8 @@ LIB = os.path.join(LIBDIR, "libgridmapslam.so")
 # gms_query.hip (what the map queries share: checks, bit planes, staging), gms_cast.hip (predicted scans), gms_gain.hip (view gain),
 # gms_clearance.hip (clearance fields), gms_reach.hip (cost-to-go fields), gms_frontier.hip (frontier regions), gms_scatter.hip
 # (particle seeding), gms_locate.hip (global scan matching), gms_modes.hip (pose modes), gms_beams.hip (the beam sensor model),
-# gms_align.hip (continuous scan alignment) and gms_rollout.hip (trajectory rollouts) are units of their own, kernels and C-ABI
+# gms_align.hip (continuous scan alignment) and gms_rollout.hip (trajectory rollouts) are units of their own, kernels and C-ABI;
+# gms_probe.h is the device header the casts and the beam model share
 SOURCES = ["gms_host.hip", "gms_slam_host.hip", "gms_fused_kernels.hip", "gms_query.hip", "gms_cast.hip", "gms_gain.hip", "gms_clearance.hip",
            "gms_reach.hip", "gms_frontier.hip", "gms_scatter.hip", "gms_locate.hip", "gms_modes.hip", "gms_beams.hip", "gms_align.hip",
            "gms_rollout.hip"]

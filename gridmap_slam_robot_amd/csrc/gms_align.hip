@@ -180,11 +180,8 @@ static int align_check(const gms_align_params *p, const char *who) {
 // lik: map 0's field of the launch, the maps lik_stride apart; poses and records [maps][P]
 static int align_launch(gms_map *m, const double *lik, int64_t lik_stride, int32_t maps, const gms_beam *d_beams, int32_t B, int32_t beam_stride,
                         const float *d_in, float *d_out, float *d_cs, gms_align_record *d_rec, int32_t P, const gms_align_params *prm) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_align), hipFuncAttributeMaxDynamicSharedMemorySize, GMS_MAX_BEAMS * 16));
-        attr_set = true;
-    }
+    int rc = gms_kernel_lds<k_align>(GMS_MAX_BEAMS * 16);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_align, dim3((unsigned)((P + ALIGN_WAVES - 1) / ALIGN_WAVES), (unsigned)maps), dim3(ALIGN_NT), (size_t)B * 16, m->stream, m->gd, lik,
                        lik_stride, d_beams, B, beam_stride, d_in, d_out, d_cs, d_rec, P, *prm);
     HIPCHK(hipGetLastError());
@@ -236,13 +233,10 @@ static int pf_align(gms_pf *pf, const gms_beam *beams, int32_t B, const gms_alig
     if (on_device && (((uintptr_t)records & 7) != 0 || ((uintptr_t)beams & 7) != 0))
         return gms_fail(GMS_ERR_INVALID, "%s: the records and the beams must be 8-byte aligned", who);
     HIPCHK(hipSetDevice(m->device));
-    const gms_beam *d_beams = beams;
-    int32_t beam_stride = B;
-    if (!on_device) {
-        rc = gms_stage_beams(m, beams, B);
-        if (rc) return rc;
-        d_beams = m->d_beams; beam_stride = m->max_beams;
-    }
+    const gms_beam *d_beams;
+    int32_t beam_stride;
+    rc = gms_request_scan(m, beams, B, on_device, &d_beams, &beam_stride);
+    if (rc) return rc;
     HostStage st(m, on_device);
     const size_t rec_bytes = records ? (size_t)pf->n_maps * (size_t)pf->n * sizeof(gms_align_record) : 0;
     const size_t p_rec = st.part(rec_bytes);

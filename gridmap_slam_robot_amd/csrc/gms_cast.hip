@@ -5,13 +5,10 @@
 //
 //   the plane      the shared-map casts walk the map's GMS_CLEAR_OCCUPIED plane (gms_map_plane, gms_query.hip): logData > 0 of every map
 //                  at one bit per cell, kept on the handle until logData moves.
-//   k_cast_map     lane = probe, workgroup = 256 neighbouring probes of ONE pose.  The workgroup takes the box of its rays' start and end
-//                  cells (+ extra_steps + 1, clipped to the map), stages those rows' words of the plane in LDS when they fit what the
-//                  launch asked for, and every lane walks RayIterator's float recurrence (ray_init / ray_step, gms_device.h) to the first
-//                  set bit.  A cell outside the staged window (the box is an estimate of the float walk, never a promise) is read from the
-//                  plane in memory, so the window only ever decides WHERE a bit is read.  A window that does not fit, or
-//                  GMS_CAST_WALK=mem: every bit from memory (the plane's base and pitch are kernel arguments, i.e. scalar registers; a
-//                  lane's address is one multiply-add on top).
+//   k_cast_map     lane = probe, workgroup = 256 neighbouring probes of ONE pose.  The workgroup stages the window of its rays
+//                  (PlaneWindow, gms_probe.h: the box of one ray per lane, padded by extra_steps + 1) when it fits what the launch
+//                  asked for, and every lane walks to the first set bit (ray_first).  A window that does not fit, or
+//                  GMS_CAST_WALK=mem: every bit from memory (plane_bit).  What the window may and may not decide: PlaneWindow::bit.
 //   k_cast_slam    the per-particle filter, one workgroup per particle: pose, trig and the maps' generation from device state; plane 0 of
 //                  the particle's class planes (2 bits per cell, gms_slam_kernels.hip: 0 logData == 0 or NaN, 1 logData < 0, 2 logData > 0
 //                  -- code 2 IS "occupied", the class k_slam_codes_from_log and the apply pass of k_slam_particle write for logData > 0)
@@ -25,7 +22,7 @@
 
 #include <algorithm>
 
-#include "gms_device.h"
+#include "gms_probe.h"
 
 #define CAST_NT 256
 #define CAST_LDS_CAP (64 * 1024)         // k_cast_map's window: bytes of LDS a workgroup asks for at most
@@ -41,25 +38,15 @@ __device__ __forceinline__ gms_cast_hit cast_miss(float measured) {
 __device__ __forceinline__ void cast_store(gms_cast_hit *__restrict__ out, const gms_cast_hit &h) {
     *reinterpret_cast<int4 *>(out) = make_int4(h.step, h.x, h.y, (int32_t)__float_as_uint(h.range));
 }
-// a coordinate of a ray's end as a cell for the window's box: saturated, then held to one cell around the map
-__device__ __forceinline__ int32_t cast_box_cell(float v, int32_t n) { return max(-1, min(n, j_d2i(floor((double)v)))); }
-
-// FIRST: does the walk's current cell hold an occupied cell?  occ(x, y) is only ever asked for cells inside the map.
+// the record of the first occupied cell of a probe's walk (ray_first, gms_probe.h), or of none
 template <class Occ>
 __device__ __forceinline__ gms_cast_hit cast_walk(const GridDev &g, const RayIn &ray, Occ occ) {
-    RayDev r;
-    ray_init(r, ray.sx + 0.5f, ray.sy + 0.5f, ray.ex + 0.5f, ray.ey + 0.5f, g.extra);          // GridMap.java:210
-    const int32_t bound = g.W + g.H + g.extra + 2;
-    for (int32_t step = 0; step < bound && ray_has_next(r, g.W, g.H); step++) {                 // :211
-        if (occ(r.x, r.y)) {
-            gms_cast_hit h;
-            h.step = step; h.x = r.x; h.y = r.y;
-            h.range = cell_distance(ray.sx, ray.sy, r.x, r.y);                                  // :215-217
-            return h;
-        }
-        ray_step(r);
-    }
-    return cast_miss(ray.measured);
+    return ray_first(g, ray, g.extra, occ, [&](int32_t step, const RayDev &r) {
+        gms_cast_hit h;
+        h.step = step; h.x = r.x; h.y = r.y;
+        h.range = cell_distance(ray.sx, ray.sy, r.x, r.y);                                      // GridMap.java:215-217
+        return h;
+    }, cast_miss(ray.measured));
 }
 
 // poses: pose i at poses + i * pose_stride floats; per_map: pose i is cast in map i's plane (gms_map_cast_at of a batched handle),
@@ -73,60 +60,30 @@ k_cast_map(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, int64_t p
     const int32_t pi = (int32_t)(blockIdx.x / (uint32_t)bpp), b = (int32_t)(blockIdx.x % (uint32_t)bpp) * CAST_NT + (int32_t)threadIdx.x;
     if (per_map) plane += (size_t)pi * (size_t)plane_stride;
     if (threadIdx.x == 0) {
-        const float *pose = poses + (size_t)pi * (size_t)pose_stride;
-        float c, s;
-        pose_trig(pose[2], c, s);                                                               // GridMap.java:175
-        XformDev t;
-        t.c = (double)c; t.s = (double)s; t.px = (double)pose[0]; t.py = (double)pose[1];
-        s_t = t;
+        s_t = pose_xform(poses + (size_t)pi * (size_t)pose_stride);                             // GridMap.java:175
         s_box[0] = g.W; s_box[1] = g.H; s_box[2] = -1; s_box[3] = -1;
     }
     __syncthreads();
     const XformDev t = s_t;
     RayIn ray;
     ray.sx = ray.sy = ray.ex = ray.ey = ray.measured = 0.0f; ray.hit = 0;
-    if (b < B) {
-        const gms_beam m = probes[b];
-        ray.sx = (float)((xform_x(t, 0.0, 0.0) - g.posx) / g.res);                              // :178
-        ray.sy = (float)((xform_y(t, 0.0, 0.0) - g.posy) / g.res);                              // :179
-        ray.ex = (float)((xform_x(t, m.local_x, m.local_y) - g.posx) / g.res);                  // :185
-        ray.ey = (float)((xform_y(t, m.local_x, m.local_y) - g.posy) / g.res);                  // :186
-        ray.measured = (float)m.distance / g.resf;                                              // :188
-    }
-    int32_t wx0 = 0, wy0 = 0, ww = 0, wh = 0;                                                   // the staged window: words x rows (0: none)
+    if (b < B) ray = make_ray(g, t, probes[b]);
+    PlaneWindow win;                                                                            // (none: walk memory)
     if (lds_words > 0) {
         if (b < B) {
-            const int32_t ax = cast_box_cell(ray.sx + 0.5f, g.W), ay = cast_box_cell(ray.sy + 0.5f, g.H);
-            const int32_t bx = cast_box_cell(ray.ex + 0.5f, g.W), by = cast_box_cell(ray.ey + 0.5f, g.H);
-            atomicMin(&s_box[0], min(ax, bx)); atomicMin(&s_box[1], min(ay, by));
-            atomicMax(&s_box[2], max(ax, bx)); atomicMax(&s_box[3], max(ay, by));
+            int32_t box[4];
+            PlaneWindow::box_of(box, ray, g.W, g.H);
+            PlaneWindow::box_merge(s_box, box);
         }
         __syncthreads();
-        const int32_t pad = g.extra + 1;
-        const int32_t x0 = max(0, s_box[0] - pad), y0 = max(0, s_box[1] - pad), x1 = min(g.W - 1, s_box[2] + pad), y1 = min(g.H - 1, s_box[3] + pad);
-        if (x1 >= x0 && y1 >= y0) {
-            wx0 = x0 >> 5; wy0 = y0;
-            ww = (x1 >> 5) - wx0 + 1; wh = y1 - y0 + 1;
-            if ((int64_t)ww * wh > (int64_t)lds_words) ww = wh = 0;                             // does not fit: this workgroup walks memory
-        }
-        const int32_t n = ww * wh;
-        for (int32_t i = (int32_t)threadIdx.x; i < n; i += CAST_NT) {
-            const int32_t row = i / ww, w = i - row * ww;
-            s_win[i] = plane[(size_t)(wy0 + row) * (size_t)wpr + (size_t)(wx0 + w)];
-        }
+        win = PlaneWindow::clip(s_box, g.extra + 1, g.W, g.H, lds_words);
+        win.stage(s_win, plane, wpr, (int32_t)threadIdx.x, CAST_NT);
         __syncthreads();
     }
     if (b >= B) return;
     gms_cast_hit h;
-    if (ww > 0) {
-        h = cast_walk(g, ray, [&](int32_t x, int32_t y) {
-            const uint32_t cw = (uint32_t)((x >> 5) - wx0), cr = (uint32_t)(y - wy0);
-            const uint32_t word = (cw < (uint32_t)ww && cr < (uint32_t)wh) ? s_win[cr * (uint32_t)ww + cw] : plane[(size_t)y * (size_t)wpr + (size_t)(x >> 5)];
-            return ((word >> (x & 31)) & 1u) != 0u;
-        });
-    } else {
-        h = cast_walk(g, ray, [&](int32_t x, int32_t y) { return ((plane[(size_t)y * (size_t)wpr + (size_t)(x >> 5)] >> (x & 31)) & 1u) != 0u; });
-    }
+    if (win.ww > 0) h = cast_walk(g, ray, [&](int32_t x, int32_t y) { return win.bit(s_win, plane, wpr, x, y); });
+    else h = cast_walk(g, ray, [&](int32_t x, int32_t y) { return plane_bit(plane, wpr, x, y); });
     cast_store(out + (size_t)pi * (size_t)B + (size_t)b, h);
 }
 
@@ -147,17 +104,9 @@ k_cast_slam(GridDev g, SlamBufs sb, int64_t code_words, const PfStatsDev *__rest
         for (int32_t i = (int32_t)threadIdx.x; i < (int32_t)code_words; i += CAST_NT) s_codes[i] = codes[i];
         __syncthreads();
     }
-    XformDev t;
-    t.px = (double)pose[3 * (size_t)p]; t.py = (double)pose[3 * (size_t)p + 1]; t.c = (double)cs[2 * (size_t)p]; t.s = (double)cs[2 * (size_t)p + 1];
+    const XformDev t = pose_xform(pose + 3 * (size_t)p, cs + 2 * (size_t)p);
     for (int32_t b = (int32_t)threadIdx.x; b < B; b += CAST_NT) {
-        const gms_beam m = probes[b];
-        RayIn ray;
-        ray.sx = (float)((xform_x(t, 0.0, 0.0) - g.posx) / g.res);                              // GridMap.java:178
-        ray.sy = (float)((xform_y(t, 0.0, 0.0) - g.posy) / g.res);                              // :179
-        ray.ex = (float)((xform_x(t, m.local_x, m.local_y) - g.posx) / g.res);                  // :185
-        ray.ey = (float)((xform_y(t, m.local_x, m.local_y) - g.posy) / g.res);                  // :186
-        ray.measured = (float)m.distance / g.resf;                                              // :188
-        ray.hit = 0;
+        const RayIn ray = make_ray(g, t, probes[b]);
         gms_cast_hit h;
         if (CODES) {
             h = cast_walk(g, ray, [&](int32_t x, int32_t y) {
@@ -182,11 +131,8 @@ static int cast_launch(gms_map *m, int32_t mi, bool per_map, const float *d_pose
     const int64_t plane_stride = (int64_t)m->gd.H * wpr;
     const int64_t lds_words = m->cast_walk_mem ? 0 : std::min<int64_t>(CAST_LDS_CAP / 4, plane_stride);
     const int32_t bpp = (B + CAST_NT - 1) / CAST_NT;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cast_map), hipFuncAttributeMaxDynamicSharedMemorySize, CAST_LDS_CAP));
-        attr_set = true;
-    }
+    rc = gms_kernel_lds<k_cast_map>(CAST_LDS_CAP);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_cast_map, dim3((unsigned)((int64_t)P * bpp)), dim3(CAST_NT), (size_t)lds_words * 4, m->stream, m->gd,
                        plane + (size_t)mi * (size_t)plane_stride, wpr, plane_stride, per_map ? 1 : 0, d_probes, B, bpp, d_poses, pose_stride,
                        d_out, (int32_t)lds_words);

@@ -85,6 +85,20 @@ struct XformDev {
 };
 __device__ __forceinline__ double xform_x(const XformDev &t, double x, double y) { return x * t.c - y * t.s + t.px; }
 __device__ __forceinline__ double xform_y(const XformDev &t, double x, double y) { return x * t.s + y * t.c + t.py; }
+// Transform.fromRobotToWorld of a pose (x, y, theta): the one place a pose in memory becomes a transform.  The second form takes the
+// trig a filter keeps beside its poses (cs: what pose_trig gave for pose[2])
+__device__ __forceinline__ XformDev pose_xform(const float *pose) {
+    float c, s;
+    pose_trig(pose[2], c, s);
+    XformDev t;
+    t.c = (double)c; t.s = (double)s; t.px = (double)pose[0]; t.py = (double)pose[1];
+    return t;
+}
+__device__ __forceinline__ XformDev pose_xform(const float *pose, const float *cs) {
+    XformDev t;
+    t.px = (double)pose[0]; t.py = (double)pose[1]; t.c = (double)cs[0]; t.s = (double)cs[1];
+    return t;
+}
 
 // ---- RayIterator (J/slam/RayIterator.java:65-130) ---------------------------------------------
 struct RayDev {
@@ -211,21 +225,29 @@ __device__ __forceinline__ float cell_distance(float sx, float sy, int32_t cx, i
     return j_sqrtf(dX * dX + dY * dY);
 }
 
-// GridMap.integrateObservation's per-beam locals (GridMap.java:175-188)
-__device__ __forceinline__ RayIn make_ray(const GridDev &g, const gms_beam &m, const float *pose) {
-    XformDev t;
-    float c, s;
-    pose_trig(pose[2], c, s);
-    t.c = (double)c; t.s = (double)s; t.px = (double)pose[0]; t.py = (double)pose[1];
+// GridMap.integrateObservation's per-beam locals (GridMap.java:175-188) of beam m under the transform t: the one copy, for the scan step
+// and every ray query alike (a user that ignores `measured` or `hit` costs nothing: the dead field is dropped).  A macro, because the
+// pose form below cannot forward to the transform form: nested, the compiler commutes eight double adds of the step kernels (the same
+// values, another instruction stream), and the step kernels' code is not to move for the queries' sake.
+#define GMS_RAY_LOCALS(r, g, t, m)                                                  \
+    (r).sx = (float)((xform_x(t, 0.0, 0.0) - (g).posx) / (g).res);              /* :178 */ \
+    (r).sy = (float)((xform_y(t, 0.0, 0.0) - (g).posy) / (g).res);              /* :179 */ \
+    (r).ex = (float)((xform_x(t, (m).local_x, (m).local_y) - (g).posx) / (g).res);  /* :185 */ \
+    (r).ey = (float)((xform_y(t, (m).local_x, (m).local_y) - (g).posy) / (g).res);  /* :186 */ \
+    (r).measured = (float)(m).distance / (g).resf;                              /* :188 */ \
+    (r).hit = (m).hit != 0;
+__device__ __forceinline__ RayIn make_ray(const GridDev &g, const XformDev &t, const gms_beam &m) {
     RayIn r;
-    r.sx = (float)((xform_x(t, 0.0, 0.0) - g.posx) / g.res);                  // :178
-    r.sy = (float)((xform_y(t, 0.0, 0.0) - g.posy) / g.res);                  // :179
-    r.ex = (float)((xform_x(t, m.local_x, m.local_y) - g.posx) / g.res);      // :185
-    r.ey = (float)((xform_y(t, m.local_x, m.local_y) - g.posy) / g.res);      // :186
-    r.measured = (float)m.distance / g.resf;                                  // :188
-    r.hit = m.hit != 0;
+    GMS_RAY_LOCALS(r, g, t, m)
     return r;
 }
+__device__ __forceinline__ RayIn make_ray(const GridDev &g, const gms_beam &m, const float *pose) {
+    const XformDev t = pose_xform(pose);
+    RayIn r;
+    GMS_RAY_LOCALS(r, g, t, m)
+    return r;
+}
+#undef GMS_RAY_LOCALS
 
 // MathUtil.angleConstrain (J/math/MathUtil.java:65-72).  The Java loops do not terminate for
 // infinite or astronomically large angles; the device version gives up after 64 turns.

@@ -20,6 +20,9 @@
 //                  and classing read them there; otherwise, or with GMS_GAIN_WALK=mem, plane words come from memory.  The bitmap is
 //                  always in LDS: max_range <= 255 bounds it by 17 words x 511 rows = 34,748 bytes.  Staging decides where a bit is read,
 //                  never what is returned.
+//   its own code   k_gain does not take its ray set-up, window geometry and staging from gms_probe.h as the casts and the beam model do:
+//                  written on those helpers it computed the same records 0.4 to 1.3 % slower on two of the probe's figures, outside the
+//                  parent's own spread ("the probe geometry the ray queries share"), so the kernel stays as it was.
 //
 // LDS: at most GAIN_LDS_CAP = 64 KiB per workgroup (two per CU at the cap, k_cast_map's reasoning), the 128 bytes of bookkeeping
 // included.  Every walk's loop carries the bound 2 * max_range + 2: a monotone walk inside the square has at most 2 * max_range + 1 cells.
@@ -148,11 +151,8 @@ static int gain_launch(gms_map *m, const uint32_t *d_occ, const uint32_t *d_nf, 
     const int64_t budget = GAIN_LDS_CAP - GAIN_LDS_STATIC;
     if (cap_words * 4 > budget) return gms_fail(GMS_ERR_INTERNAL, "gms_gain: a visited bitmap of %lld bytes", (long long)(cap_words * 4));
     const bool staged = !m->gain_walk_mem && 3 * cap_words * 4 <= budget;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gain), hipFuncAttributeMaxDynamicSharedMemorySize, GAIN_LDS_CAP - GAIN_LDS_STATIC));
-        attr_set = true;
-    }
+    int rc = gms_kernel_lds<k_gain>(GAIN_LDS_CAP - GAIN_LDS_STATIC);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_gain, dim3((unsigned)P), dim3(GAIN_NT), (size_t)(staged ? 3 : 1) * (size_t)cap_words * 4, m->stream, m->gd, d_occ, d_nf, wpr, d_probes, B,
                        d_poses, max_range, d_out, (int32_t)cap_words, staged ? 1 : 0);
     HIPCHK(hipGetLastError());

@@ -494,6 +494,27 @@ int gms_fail(int code, const char *fmt, ...);
 extern "C" int gms_pf_place_shard(gms_pf *pf, int64_t offset, int64_t n_global);
 // host beams [n_maps][B] -> the map's device staging buffer [n_maps][max_beams] through the pinned ring (gms_host.hip)
 int gms_stage_beams(gms_map *m, const gms_beam *beams, int32_t B);
+// the scan of a filter-wide request (one scan per map): the host form's is staged into m->d_beams, the maps max_beams apart; a device
+// form's is the caller's own, the maps B apart
+static inline int gms_request_scan(gms_map *m, const gms_beam *beams, int32_t B, bool on_device, const gms_beam **d_beams, int32_t *beam_stride) {
+    *d_beams = beams; *beam_stride = B;
+    if (on_device) return GMS_OK;
+    const int rc = gms_stage_beams(m, beams, B);
+    if (rc) return rc;
+    *d_beams = m->d_beams; *beam_stride = m->max_beams;
+    return GMS_OK;
+}
+// the one opt-in of a kernel to `bytes` of dynamic LDS (past the 64 KiB a launch may ask for without it): set once per kernel and
+// process, in front of its first launch
+template <auto Kernel>
+static inline int gms_kernel_lds(int bytes) {
+    static bool set = false;
+    if (!set) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        set = true;
+    }
+    return GMS_OK;
+}
 // host beams [rows][B] (or none: beams NULL) -> dst [rows][pitch], then tab_bytes of tab behind them, as ONE copy out of a slot of ring
 // (gms_host.hip; the ring's slots hold rows * pitch beams + tab_bytes)
 int gms_stage_block(gms_map *m, StageRing &ring, const gms_beam *beams, int32_t B, int32_t rows, int32_t pitch, const void *tab, size_t tab_bytes,
@@ -544,7 +565,8 @@ void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_o
 // (gms_modes.hip), the beam sensor model (gms_beams.hip: beside cast, on the base alone) and trajectory rollouts (gms_rollout.hip: on reach,
 // whose blocked plane they test).  The layering: the query base (gms_query.hip:
 // everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier, scatter and locate (they inflate
-// with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only) ----
+// with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only).  Cast and beams share their device-side
+// probe geometry -- the staged plane window and the first-hit walk -- through gms_probe.h, a device header on gms_device.h alone ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);

@@ -108,11 +108,7 @@ k_rollout(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, RollStart 
     const gms_rollout_step ident = {0.0f, 0.0f, 1.0f, 0.0f};
     if (tid == 0) {
         const int32_t p = start.n_per > 0 ? (start.which >= 0 ? start.which : start.filter * start.n_per + start.stats[start.filter].strongest) : pi;
-        const float *pose = start.poses + (size_t)p * 3;
-        float c, s;
-        pose_trig(pose[2], c, s);
-        XformDev t;
-        t.c = (double)c; t.s = (double)s; t.px = (double)pose[0]; t.py = (double)pose[1];
+        const XformDev t = pose_xform(start.poses + (size_t)p * 3);
         s_t = t;
         int32_t sx, sy;
         roll_cell(g, t, ident, 0.0f, 0.0f, sx, sy);                             // the start cell: the centre's under the identity step

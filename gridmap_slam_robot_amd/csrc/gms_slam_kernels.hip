@@ -121,19 +121,6 @@ k_slam_codes_from_log(SlamBufs sb, int64_t cells, int32_t first, int64_t code_wo
     sb_code(sb, cur)[(size_t)p * 2 * (size_t)code_words + w] = word;
 }
 
-// GridMap.integrateObservation's per-beam locals (GridMap.java:175-188) from a transform that is already at hand (make_ray takes
-// the pose and its trig)
-__device__ __forceinline__ RayIn ps_make_ray(const GridDev &g, const XformDev &t, const gms_beam &m) {
-    RayIn r;
-    r.sx = (float)((xform_x(t, 0.0, 0.0) - g.posx) / g.res);                  // :178
-    r.sy = (float)((xform_y(t, 0.0, 0.0) - g.posy) / g.res);                  // :179
-    r.ex = (float)((xform_x(t, m.local_x, m.local_y) - g.posx) / g.res);      // :185
-    r.ey = (float)((xform_y(t, m.local_x, m.local_y) - g.posy) / g.res);      // :186
-    r.measured = (float)m.distance / g.resf;                                  // :188
-    r.hit = m.hit != 0;
-    return r;
-}
-
 #include <type_traits>
 
 #ifndef PS_APPLY
@@ -328,7 +315,7 @@ k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
         if (CODES) s_cell[b] = cell;
         if (integrate) {
             RayDev r;
-            const RayMeta mt = ray_meta(g, ps_make_ray(g, t, bm), r);
+            const RayMeta mt = ray_meta(g, make_ray(g, t, bm), r);
             if (b == (int32_t)threadIdx.x) { r_first = r; mt_first = mt; }
             if (mt.n_eff > 0) {
                 nzero += (mt.x_inc == 0 && mt.y_inc == 0) ? 1 : 0;
@@ -495,7 +482,7 @@ k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
                 if (ri < B) {
                     RayMeta mt;
                     if (g0 == 0) { mt = mt_first; r = r_first; }               // (ri == threadIdx.x)
-                    else mt = ray_meta(g, ps_make_ray(g, t, beams[ri]), r);    // the same arithmetic as the box pass above: same values
+                    else mt = ray_meta(g, make_ray(g, t, beams[ri]), r);    // the same arithmetic as the box pass above: same values
                     // a ray that never enters this band's rows is not walked for it (its box says so)
                     const bool in_band = mt.n_eff > 0 && !(max(mt.y0, mt.hy) < ty0 || min(mt.y0, mt.hy) >= ty0 + th);
                     const RayThr thr = s_thr[ri];
@@ -638,7 +625,7 @@ k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
         for (int32_t i = threadIdx.x; i < code_words; i += NT) gplane[i] = s_plane[i];
 }
 
-// The cell walk of k_slam_particle for ONE particle without touching its map (tests): the same ray set-up (ps_make_ray, ray_meta,
+// The cell walk of k_slam_particle for ONE particle without touching its map (tests): the same ray set-up (make_ray, ray_meta,
 // ray_thresholds), the same recurrence (ray_phase_a) and the same per-step function (ps_cell_of) as the counting kernel, but every
 // emitted step -- prior-class visits included -- is written out in walk order: for beam b, counts[b] cells (x, y) and their classes,
 // [B][cap] entries (RayIterator.java:107-130: the walk stops at the first cell outside the map).  One workgroup; wavefront 0 walks 64
@@ -662,7 +649,7 @@ k_slam_trace(GridDev g, const gms_beam *__restrict__ beams, int32_t B, const flo
             PsRay pr;
             pr.n_eff = 0; pr.x0 = pr.y0 = pr.x_inc = pr.y_inc = pr.hit = 0; pr.sx = pr.sy = pr.s_free = pr.s_prior = 0.0f;
             if (ri < B) {
-                const RayMeta mt = ray_meta(g, ps_make_ray(g, t, beams[ri]), r);
+                const RayMeta mt = ray_meta(g, make_ray(g, t, beams[ri]), r);
                 const RayThr thr = ray_thresholds(mt.measured, mt.hit, g.half_tol);
                 pr.x0 = mt.x0; pr.y0 = mt.y0; pr.x_inc = mt.x_inc; pr.y_inc = mt.y_inc; pr.n_eff = mt.n_eff; pr.hit = mt.hit;
                 pr.sx = mt.sx; pr.sy = mt.sy; pr.s_free = thr.s_free; pr.s_prior = thr.s_prior;
