@@ -9,7 +9,7 @@
 //                  scan's (local_x, local_y) in LDS once, 16 bytes per beam, NaN for a beam that did not hit -- the USED test refuses a
 //                  NaN by itself, so the loop needs no hit flag.  Lane l owns partial l: it walks the beams l, l + 64, ... in ascending
 //                  order, two adjacent field values per row (16 bytes, 8-byte aligned) and two rows per look-up, and adds the ten
-//                  terms into its registers.  The halving tree p[l] += p[l + s], s = 32 .. 1, runs as cross-lane register moves
+//                  terms into its registers (gms_align_device.h, shared with k_slam_align).  The halving tree p[l] += p[l + s], s = 32 .. 1, runs as cross-lane register moves
 //                  (wave_xor: for l < s lane l ^ s IS lane l + s) with the add kept to the lanes l < s; lane 0's sums are broadcast and
 //                  every lane solves the 3 x 3 system alike, so the loop over the iterations is uniform per wavefront.  A stopped
 //                  pose leaves the loop; its wavefront idles until the workgroup's other three are done.
@@ -21,91 +21,10 @@
 #include <math.h>
 #include <string.h>
 
-#include "gms_device.h"
+#include "gms_align_device.h"
 
 #define ALIGN_NT 256
 #define ALIGN_WAVES (ALIGN_NT / GMS_WAVE)
-static_assert(sizeof(gms_align_record) == 80 && sizeof(gms_align_params) == 64, "gridmapslam.h states both sizes");
-
-// two adjacent doubles of a field row: 8-byte aligned, so one 16-byte load where the target takes it
-typedef double align_pair __attribute__((ext_vector_type(2), aligned(8)));
-
-// lane 0's value in every lane
-__device__ __forceinline__ double wave_first(double v) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// the sums of one evaluation, in the header's order of terms
-struct AlignSums {
-    double h00, h01, h02, h11, h12, h22, g0, g1, g2, s;
-    int32_t n;
-};
-
-// the header's halving tree over the 64 lanes' partials; lane 0 holds the sums afterwards, the broadcast makes them uniform
-__device__ __forceinline__ void align_tree(AlignSums &a, int32_t lane) {
-#define GMS_STEP_(O)                                                                          \
-    {                                                                                         \
-        const bool low = lane < (O);                                                          \
-        const double t0 = wave_xor<O>(a.h00), t1 = wave_xor<O>(a.h01), t2 = wave_xor<O>(a.h02), t3 = wave_xor<O>(a.h11), t4 = wave_xor<O>(a.h12); \
-        const double t5 = wave_xor<O>(a.h22), t6 = wave_xor<O>(a.g0), t7 = wave_xor<O>(a.g1), t8 = wave_xor<O>(a.g2), t9 = wave_xor<O>(a.s);      \
-        const int32_t tn = wave_xor<O>(a.n);                                                  \
-        if (low) {                                                                            \
-            a.h00 = a.h00 + t0; a.h01 = a.h01 + t1; a.h02 = a.h02 + t2; a.h11 = a.h11 + t3; a.h12 = a.h12 + t4; \
-            a.h22 = a.h22 + t5; a.g0 = a.g0 + t6; a.g1 = a.g1 + t7; a.g2 = a.g2 + t8; a.s = a.s + t9;           \
-            a.n += tn;                                                                        \
-        }                                                                                     \
-    }
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    a.h00 = wave_first(a.h00); a.h01 = wave_first(a.h01); a.h02 = wave_first(a.h02); a.h11 = wave_first(a.h11); a.h12 = wave_first(a.h12);
-    a.h22 = wave_first(a.h22); a.g0 = wave_first(a.g0); a.g1 = wave_first(a.g1); a.g2 = wave_first(a.g2); a.s = wave_first(a.s);
-    a.n = __builtin_amdgcn_readfirstlane(a.n);
-}
-
-// one evaluation at the pose (x, y, theta): every lane returns the same sums
-__device__ __forceinline__ AlignSums align_eval(const GridDev &g, const double *__restrict__ lik, const double2 *s_beam, int32_t B, float x, float y,
-                                               float theta, int32_t lane) {
-    float cf, sf;
-    pose_trig(theta, cf, sf);
-    XformDev t;
-    t.c = (double)cf; t.s = (double)sf; t.px = (double)x; t.py = (double)y;
-    const double wmax = (double)(g.W - 2), hmax = (double)(g.H - 2);
-    AlignSums a;
-    a.h00 = a.h01 = a.h02 = a.h11 = a.h12 = a.h22 = a.g0 = a.g1 = a.g2 = a.s = 0.0;
-    a.n = 0;
-    for (int32_t b = lane; b < B; b += GMS_WAVE) {
-        const double2 l = s_beam[b];
-        const double lx = l.x, ly = l.y;
-        const double gu = (xform_x(t, lx, ly) - g.posx) / g.res - 0.5;
-        const double gv = (xform_y(t, lx, ly) - g.posy) / g.res - 0.5;
-        const double fu = floor(gu), fv = floor(gv);
-        if (fu >= 0.0 && fu <= wmax && fv >= 0.0 && fv <= hmax) {              // (a NaN or an infinity fails: nothing else is ever cast)
-            const int32_t i0 = (int32_t)fu, j0 = (int32_t)fv;
-            const double fx = gu - fu, fy = gv - fv;
-            const double *row = lik + (size_t)j0 * (size_t)g.W + (size_t)i0;
-            const align_pair r0 = *reinterpret_cast<const align_pair *>(row), r1 = *reinterpret_cast<const align_pair *>(row + g.W);
-            const double l00 = r0.x, l10 = r0.y, l01 = r1.x, l11 = r1.y;
-            const double m = (1.0 - fy) * ((1.0 - fx) * l00 + fx * l10) + fy * ((1.0 - fx) * l01 + fx * l11);
-            const double mu = (1.0 - fy) * (l10 - l00) + fy * (l11 - l01);
-            const double mv = (1.0 - fx) * (l01 - l00) + fx * (l11 - l10);
-            const double ax = (-lx * t.s - ly * t.c) / g.res;
-            const double ay = (lx * t.c - ly * t.s) / g.res;
-            const double j2 = mu * ax + mv * ay;
-            const double r = 1.0 - m;
-            a.h00 = a.h00 + mu * mu; a.h01 = a.h01 + mu * mv; a.h02 = a.h02 + mu * j2;
-            a.h11 = a.h11 + mv * mv; a.h12 = a.h12 + mv * j2; a.h22 = a.h22 + j2 * j2;
-            a.g0 = a.g0 + mu * r; a.g1 = a.g1 + mv * r; a.g2 = a.g2 + j2 * r;
-            a.s = a.s + m;
-            a.n++;
-        }
-    }
-    align_tree(a, lane);
-    return a;
-}
-
-__device__ __forceinline__ double align_clamp(double v, double m) { return v > m ? m : (v < -m ? -m : v); }
 
 // grid (ceil(P / 4), maps).  lik: map blockIdx.y's field at lik + y * lik_stride; beams likewise beam_stride apart; pose_in / pose_out
 // [maps][P][3] (may be the same), cs [maps][P][2] or NULL: the final poses' float-rounded trig; rec [maps][P] or NULL
@@ -128,24 +47,11 @@ k_align(GridDev g, const double *__restrict__ lik, int64_t lik_stride, const gms
     int32_t status = 0, done = 0, n0 = 0;
     double s0 = 0.0;
     AlignSums e;
+    const AlignFetchMemory fetch{lik, g.W};
     for (int32_t k = 0;; k++) {
-        e = align_eval(g, lik, s_beam, B, x, y, theta, lane);
+        e = align_eval(g, fetch, s_beam, B, x, y, theta, lane);
         if (k == 0) { n0 = e.n; s0 = e.s; }
-        if (status != 0 || k >= prm.iters) break;
-        if (e.n == 0) { status = 2; break; }
-        const double a00 = e.h00 + prm.damp_t, a01 = e.h01, a02 = e.h02, a11 = e.h11 + prm.damp_t, a12 = e.h12, a22 = e.h22 + prm.damp_r;
-        const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-        const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-        const double det = a00 * c00 + a01 * c01 + a02 * c02;
-        if (!(fabs(det) > prm.det_min)) { status = 3; break; }
-        const double d0 = align_clamp((c00 * e.g0 + c01 * e.g1 + c02 * e.g2) / det, prm.max_t);
-        const double d1 = align_clamp((c01 * e.g0 + c11 * e.g1 + c12 * e.g2) / det, prm.max_t);
-        const double d2 = align_clamp((c02 * e.g0 + c12 * e.g1 + c22 * e.g2) / det, prm.max_r);
-        x = (float)((double)x + d0 * g.res);
-        y = (float)((double)y + d1 * g.res);
-        theta = (float)((double)theta + d2);
-        done++;
-        if (fabs(d0) <= prm.eps_t && fabs(d1) <= prm.eps_t && fabs(d2) <= prm.eps_r) status = 1;
+        if (align_advance(e, k, prm, g.res, x, y, theta, status, done)) break;
     }
     if (lane != 0) return;
     pose_out[3 * gi] = x; pose_out[3 * gi + 1] = y; pose_out[3 * gi + 2] = theta;
@@ -154,17 +60,11 @@ k_align(GridDev g, const double *__restrict__ lik, int64_t lik_stride, const gms
         pose_trig(theta, cf, sf);
         cs[2 * gi] = cf; cs[2 * gi + 1] = sf;
     }
-    if (rec) {
-        gms_align_record r;
-        r.status = status; r.iters_done = done; r.n_used = e.n; r.n_used0 = n0;
-        r.score0 = s0; r.score = e.s;
-        r.H[0] = e.h00; r.H[1] = e.h01; r.H[2] = e.h02; r.H[3] = e.h11; r.H[4] = e.h12; r.H[5] = e.h22;
-        rec[gi] = r;
-    }
+    if (rec) rec[gi] = align_record(e, status, done, n0, s0);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-static int align_check(const gms_align_params *p, const char *who) {
+int gms_align_check_for(const gms_align_params *p, const char *who) {
     if (!p) return gms_fail(GMS_ERR_INVALID, "%s: null parameters", who);
     if (p->iters < 1 || p->iters > 64) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= iters <= 64", who);
     if (!(p->damp_t >= 0.0) || !(p->damp_t < INFINITY)) return gms_fail(GMS_ERR_INVALID, "%s: damp_t must be finite and >= 0", who);
@@ -193,7 +93,7 @@ static int map_align(gms_map *m, int32_t mi, const gms_beam *beams, int32_t B, c
     const char *who = on_device ? "gms_map_align_dev" : "gms_map_align";
     if (!m || !beams || !poses_in || !poses_out)
         return gms_fail(GMS_ERR_INVALID, "%s: null argument (the handle, the beams and both pose arrays are required)", who);
-    int rc = align_check(prm, who);
+    int rc = gms_align_check_for(prm, who);
     if (rc) return rc;
     if (B < 1 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= B <= gms_params.max_beams beams", who);
     if (P < 1 || P > GMS_MAX_PARTICLES) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= P <= GMS_MAX_PARTICLES poses", who);
@@ -224,7 +124,7 @@ static int map_align(gms_map *m, int32_t mi, const gms_beam *beams, int32_t B, c
 static int pf_align(gms_pf *pf, const gms_beam *beams, int32_t B, const gms_align_params *prm, gms_align_record *records, bool on_device) {
     const char *who = on_device ? "gms_pf_align_dev" : "gms_pf_align";
     if (!pf || !beams) return gms_fail(GMS_ERR_INVALID, "%s: null argument (the filter and the beams are required)", who);
-    int rc = align_check(prm, who);
+    int rc = gms_align_check_for(prm, who);
     if (rc) return rc;
     if (pf->slam_owned)
         return gms_fail(GMS_ERR_STATE, "%s: this filter's particles own maps (gms_slam): there is no one field to align on", who);
@@ -267,7 +167,7 @@ int gms_align_params_default(gms_align_params *p) {
     return GMS_OK;
 }
 
-int gms_align_check(const gms_align_params *p) { return align_check(p, "gms_align_params"); }
+int gms_align_check(const gms_align_params *p) { return gms_align_check_for(p, "gms_align_params"); }
 
 int gms_map_align(gms_map *m, int32_t mi, const gms_beam *beams, int32_t B, const float *poses_in, int32_t P, const gms_align_params *params,
                   float *poses_out, gms_align_record *records) {

@@ -449,6 +449,14 @@ struct gms_slam {
     int32_t hist_walk_mem;          // the back-trace chases through memory even where a row fits the LDS (GMS_SLAM_HISTORY_WALK=mem: tests)
     int32_t refine_lds;             // -1 the field in LDS whenever it fits (computed there from the class plane where it can be), 0 never, 2 staged from
                                     // memory wherever it fits (GMS_SLAM_REFINE_LDS: tests of the other forms)
+    // per-particle scan alignment (gms_slam_set_align; gms_slam_align.hip)
+    int32_t align_on;               // update() aligns every particle against its own field between computeLikelihoodMap and the weighting
+    gms_align_params align_prm;     // ... with these parameters (checked when they were set)
+    int32_t align_field;            // -1 the field's values from the class plane whenever it is kept and fits the LDS, 0 from memory always, 1 as -1
+                                    // (GMS_SLAM_ALIGN_FIELD=memory|planes: tests of both forms)
+    int32_t align_form;             // the form the last alignment launch took (gms_slam_align_form); 0: none yet
+    gms_align_record *d_align_rec;  // [n] the records of the last aligned update (allocated by gms_slam_set_align)
+    int32_t have_align_rec;         // an aligned update has run since they were allocated
 };
 
 // the history of a gms_slam as its kernels see it (gms_slam_set_history): a ring of cap rows, update number t in row t % cap
@@ -725,6 +733,14 @@ void gms_launch_slam_trace(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32
 bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, const MotionModel *motion, int32_t field_in_lds,
                             int64_t code_words, const SlamBatch *batch = nullptr);
 bool gms_slam_refine_from_planes(const gms_map *m, int32_t B, int32_t field_in_lds, int64_t code_words);
+// per-particle scan alignment (gms_slam_align.hip): whether a scan of B beams is aligned on values computed from the class planes (no
+// field has to be written in front of the launch), and the launch -- every particle held, in place; from_planes as that answer, else
+// sb.lik's current generation holds the field of logData as it stands; motion (may be NULL): the motion-model sample is drawn first;
+// d_rec [n] or NULL
+int gms_align_check_for(const gms_align_params *p, const char *who);       // gms_align_check with the caller's name in the message (gms_align.hip)
+bool gms_slam_align_from_planes(const gms_slam *s, int32_t B);
+int gms_launch_slam_align(gms_slam *s, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, bool from_planes, const MotionModel *motion,
+                          const gms_align_params *prm, gms_align_record *d_rec, const SlamBatch *batch = nullptr);
 // resample()'s copies into the generation the draw has just made current, where it drew (epoch[1]); what: bit 0 logData (+ the class
 // planes), bit 1 likelihoodData; d_idx_keep (may be NULL) receives the indices for a likelihoodData copy that is still owed
 void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const int32_t *d_idx, int32_t *d_idx_keep, int64_t code_words);

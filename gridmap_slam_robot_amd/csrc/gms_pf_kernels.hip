@@ -14,6 +14,7 @@
 //
 // HBM layout: poses SoA x[n], y[n], theta[n] (float); weights double[n]; all [n_maps][n].
 #include "gms_device.h"
+#include "gms_slam_device.h"
 
 #define SCAN_CHUNK 64
 #define RES_SUB_MAX_CHUNKS 1024     // resampling: populations of up to 65536 keep the octet boundaries of every chunk in LDS (64 KiB at the limit)
@@ -46,51 +47,8 @@ k_pose_trig(const float *__restrict__ src, float *__restrict__ dst, float *__res
 // reference's stream (commons-math Well1024a, unseeded: Odometry.java:28-30) cannot be reproduced; the variates
 // come from Philox4x32-10 keyed by `seed` with counter {GLOBAL particle index, sequence} -- the same numbers
 // whatever the sharding -- through Box-Muller on two 53-bit uniforms.  cs[] is refreshed in the same pass.
-__device__ __forceinline__ void philox_round(uint32_t c[4], const uint32_t k[2]) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-// Odometry.apply for one particle, on values (J/slam/Odometry.java:77-96): (x, y, th) move on, (fc, fs) is the new heading's trig.
-// index: the particle's global index (+ the map's counter offset); the variates are Philox4x32-10 on (index, sequence) keyed by seed.
-struct MotionArgs {
-    int32_t on;
-    double d_center, d_theta, d_center_sd, d_theta_sd;
-    uint64_t seed, sequence;
-    int64_t index0;             // global index of the launch's particle 0 (a shard's offset): the variates are keyed by the GLOBAL index
-};
-// one odometry step as the kernels take it; motion NULL: no sample is drawn (on = 0)
-static MotionArgs motion_args(const MotionModel *motion, int64_t index0) {
-    MotionArgs mo;
-    mo.on = 0; mo.d_center = mo.d_theta = mo.d_center_sd = mo.d_theta_sd = 0.0; mo.seed = mo.sequence = 0; mo.index0 = index0;
-    if (motion) {
-        mo.on = 1; mo.d_center = motion->d_center; mo.d_theta = motion->d_theta; mo.seed = motion->seed; mo.sequence = motion->sequence;
-        motion_deviations(motion->d_center, motion->d_theta, &mo.d_center_sd, &mo.d_theta_sd);
-    }
-    return mo;
-}
-__device__ __forceinline__ void motion_apply(float &x, float &y, float &th, float &fc, float &fs, uint64_t index, double d_center,
-                                             double d_theta, double d_center_sd, double d_theta_sd, uint64_t seed, uint64_t sequence) {
-    uint32_t c[4] = { (uint32_t)index, (uint32_t)(index >> 32), (uint32_t)sequence, (uint32_t)(sequence >> 32) };
-    uint32_t k[2] = { (uint32_t)seed, (uint32_t)(seed >> 32) };
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        philox_round(c, k);
-        k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
-    }
-    const double u1 = ((double)(((uint64_t)(c[0] >> 5) << 26) | (uint64_t)(c[1] >> 6)) + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = ((double)(((uint64_t)(c[2] >> 5) << 26) | (uint64_t)(c[3] >> 6)) + 0.5) * (1.0 / 9007199254740992.0);
-    const double rad = sqrt(-2.0 * log(u1));
-    const double z0 = rad * cos(2.0 * 3.141592653589793 * u2), z1 = rad * sin(2.0 * 3.141592653589793 * u2);
-    const double d = d_center + d_center_sd * z0;                                // ndCenter.sample()  :80
-    const double theta = d_theta + d_theta_sd * z1;                              // ndTheta.sample()   :81
-    th = (float)angle_constrain((double)th + theta);                             // :92
-    pose_trig(th, fc, fs);                                                       // MathUtil.cos(float) :93
-    x = (float)((double)x + (double)fc * d);                                     // :93  p.x += cos * d
-    y = (float)((double)y + (double)fs * d);                                     // :94
-}
+// (philox_round, MotionArgs, motion_args and motion_apply -- Odometry.apply for one particle, on values -- are in gms_slam_device.h:
+// k_slam_align, a unit of its own, draws the same sample)
 __device__ __forceinline__ void
 motion_body(float *__restrict__ pose, float *__restrict__ cs, int32_t n, int64_t offset, double d_center, double d_theta,
             double d_center_sd, double d_theta_sd, uint64_t seed, uint64_t sequence, int32_t mi, int32_t i) {

@@ -87,6 +87,7 @@ int gms_slam_destroy(gms_slam *s) {
     hipFree(s->d_epoch);
     hipFree(s->d_plan);
     hipFree(s->d_batch);
+    hipFree(s->d_align_rec);
     slam_hist_free(s);
     gms_ring_free(s->batch_ring);
     if (s->pf) gms_pf_destroy(s->pf);
@@ -141,6 +142,8 @@ static int slam_create(const gms_params *p, int32_t n_particles, int64_t offset,
     s->refine_lds = rl_env && rl_env[0] == '0' ? 0 : (rl_env && rl_env[0] == '2' ? 2 : -1);
     const char *rf_env = getenv("GMS_SLAM_REFINE_FIELD");
     s->refine_field = rf_env && rf_env[0] == 'c' ? 1 : (rf_env && rf_env[0] == 'l' ? 0 : -1);
+    const char *af_env = getenv("GMS_SLAM_ALIGN_FIELD");
+    s->align_field = af_env && af_env[0] == 'm' ? 0 : (af_env && af_env[0] == 'p' ? 1 : -1);
     const char *hw_env = getenv("GMS_SLAM_HISTORY_WALK");
     s->hist_walk_mem = hw_env && hw_env[0] == 'm';
     bool ok = true;
@@ -194,6 +197,7 @@ int gms_slam_reset(gms_slam *s) {                                               
     if (s->d_code[0]) HIPCHK(hipMemsetAsync(s->d_code[0], 0, (size_t)s->n * 2 * (size_t)s->code_words * sizeof(uint32_t), m->stream));   // every class "logData == 0"
     slam_was_reset(s);
     s->have_strongest = 0;                                                                   // (no update yet: nothing names a strongest particle)
+    s->have_align_rec = 0;                                                                   // (... and no aligned one: gms_slam_last_align)
     if (s->hist_cap) slam_hist_clear(s);                                                     // (the history starts over, at the same capacity)
     gms_launch_pf_init(s->pf);                                                               // Pose(0, 0, 0), weight 1 / numParticles (:68-71)
     pf_weights_set(s->pf);
@@ -224,6 +228,16 @@ int gms_slam_count(const gms_slam *s, int32_t *n, int32_t *W, int32_t *H) {
 
 static bool slam_skip_update(double d_theta) { return fabs(d_theta) > (3.141592653589793 / 180.0) * 30; }    // SLAM.java:82
 
+// computeLikelihoodMap(p.m) of every particle (SLAM.java:93) into sb.lik's current generation, from logData as it stands
+static void slam_write_field(gms_slam *s, const SlamBufs &sb) {
+    gms_map *m = s->map;
+    // (plane 0 == the classes of logData, 1/32 of the bytes: 623 us against 793 at 4096 x 256^2, where logData is 2 GB; at
+    //  500 x 120^2 -- 58 MB, inside the 256 MB infinity cache -- the blur's arithmetic binds and reading logData is 1.6 us FASTER)
+    const bool big = (size_t)s->n * (size_t)m->gd.cells * sizeof(double) > ((size_t)256 << 20);
+    if (s->d_code[0] && (s->refine_field < 0 ? big : s->refine_field == 1)) gms_launch_slam_likelihood_codes(m, sb, s->code_words, s->n, 0);
+    else gms_launch_slam_likelihood(m, sb, s->n);
+}
+
 // the per-particle body of SLAM.update(z, u) (SLAM.java:88-107) for the particles this handle holds; the weights stay raw.  batch (may be
 // NULL): every filter's own scan, count, odometry, seed and skipUpdate (B: the largest count; motion: the sequence, drawn where the
 // filter's table says so)
@@ -234,20 +248,22 @@ static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, c
     // asked for: slam_lik_current).  The pose refinement looks up most of a field: it gets all of it.
     // ... unless it computes it itself: a field that fits a workgroup's LDS is computed there from the same plane.
     const bool planes = s->d_code[0] != nullptr;
-    const bool on_demand = planes && (!s->refine || gms_slam_refine_from_planes(m, B, s->refine_lds, s->code_words));
+    // The scan alignment reads four values per beam and evaluation: computed from the same plane where that fits, else the field is written.
+    const bool align_planes = s->align_on && gms_slam_align_from_planes(s, B);
+    const bool on_demand = planes && (!s->refine || gms_slam_refine_from_planes(m, B, s->refine_lds, s->code_words)) && (!s->align_on || align_planes);
     const SlamBufs sb = gms_slam_bufs(s);
-    if (!on_demand) {
-        // (plane 0 == the classes of logData, 1/32 of the bytes: 623 us against 793 at 4096 x 256^2, where logData is 2 GB; at
-        //  500 x 120^2 -- 58 MB, inside the 256 MB infinity cache -- the blur's arithmetic binds and reading logData is 1.6 us FASTER)
-        const bool big = (size_t)s->n * (size_t)m->gd.cells * sizeof(double) > ((size_t)256 << 20);
-        if (s->d_code[0] && (s->refine_field < 0 ? big : s->refine_field == 1)) gms_launch_slam_likelihood_codes(m, sb, s->code_words, s->n, 0);
-        else gms_launch_slam_likelihood(m, sb, s->n);
-    }
+    if (!on_demand) slam_write_field(s, sb);
     slam_field_updated(s, on_demand);
     bool drawn = false;
     if (s->refine) {                                                                                        // :90, then :96 (the lattice form of :97)
         if (!gms_launch_slam_refine(pf, dev_beams, B, sb, motion, s->refine_lds, planes ? s->code_words : 0, batch))
             return gms_fail(GMS_ERR_INVALID, "gms_slam_update_per_particle: the pose refinement's tables do not fit the LDS for a scan of %d beams", B);
+        drawn = true;
+    }
+    if (s->align_on) {                                                                                      // :97's place: from the sample, or the lattice's best pose
+        const int rc = gms_launch_slam_align(s, dev_beams, B, sb, align_planes, drawn ? nullptr : motion, &s->align_prm, s->d_align_rec, batch);
+        if (rc) return rc;
+        s->have_align_rec = 1;
         drawn = true;
     }
     gms_launch_slam_particle(pf, dev_beams, B, sb, !on_demand, drawn ? nullptr : motion, skip_update ? 0 : 1, s->code_words, batch);   // :90, :99, :102-107
@@ -557,6 +573,100 @@ int gms_slam_resample_maps_if_batch(gms_slam *s, const double *r01, double fract
     if (rc) return rc;
     REQUIRE(fraction >= 0.0, "gms_slam_resample_maps_if_batch: fraction must be non-negative");
     return slam_resample(s, r01, fraction, nullptr, nullptr);
+}
+
+// ---- per-particle scan alignment (gridmapslam.h "per-particle scan alignment") ----
+// Every particle held, in place, against the field of its own logData as it stands.  Where the values do not come from the class planes
+// that field is written first -- into the OTHER generation's likelihoodData, which nothing reads once the current one is written out
+// (resample() overwrites every cell of it): what a download returns for likelihoodData stays what it was.
+static int slam_align(gms_slam *s, const gms_beam *beams, int32_t B, const gms_align_params *prm, gms_align_record *records, bool on_device) {
+    const char *who = on_device ? "gms_slam_align_dev" : "gms_slam_align";
+    if (!s || !beams) return gms_fail(GMS_ERR_INVALID, "%s: null argument (the handle and the beams are required)", who);
+    int rc = gms_align_check_for(prm, who);
+    if (rc) return rc;
+    if (!s->map || !s->pf) return gms_fail(GMS_ERR_INVALID, "%s: not a gms_slam handle", who);
+    rc = slam_enter(s, who, SLAM_ALLOW_SHARD);
+    if (rc) return rc;
+    gms_map *m = s->map;
+    if (B < 1 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= B <= gms_params.max_beams beams", who);
+    if (on_device && (((uintptr_t)records & 7) != 0 || ((uintptr_t)beams & 7) != 0))
+        return gms_fail(GMS_ERR_INVALID, "%s: the records and the beams must be 8-byte aligned", who);
+    HIPCHK(hipSetDevice(m->device));
+    const gms_beam *d_beams;
+    int32_t beam_stride;
+    rc = gms_request_scan(m, beams, B, on_device, &d_beams, &beam_stride);
+    if (rc) return rc;
+    HostStage st(m, on_device);
+    const size_t rec_bytes = records ? (size_t)s->n * sizeof(gms_align_record) : 0;
+    const size_t p_rec = st.part(rec_bytes);
+    if (rec_bytes) {
+        rc = st.open();
+        if (rc) return rc;
+    }
+    const bool from_planes = gms_slam_align_from_planes(s, B);
+    SlamBufs sb = gms_slam_bufs(s);
+    if (!from_planes) {
+        rc = slam_lik_current(s);
+        if (rc) return rc;
+        std::swap(sb.lik[0], sb.lik[1]);
+        slam_write_field(s, sb);
+    }
+    rc = gms_launch_slam_align(s, d_beams, B, sb, from_planes, nullptr, prm, records ? st.at(p_rec, records) : nullptr);
+    if (rc) return rc;
+    pf_particles_changed(s->pf);                                                // the state a gms_pf_set_poses leaves
+    if (!rec_bytes) return GMS_OK;
+    st.fetch(records, p_rec, rec_bytes);
+    return st.finish(nullptr);
+}
+
+int gms_slam_align(gms_slam *s, const gms_beam *beams, int32_t B, const gms_align_params *params, gms_align_record *records) {
+    return slam_align(s, beams, B, params, records, false);
+}
+int gms_slam_align_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, const gms_align_params *params, gms_align_record *dev_records) {
+    return slam_align(s, dev_beams, B, params, dev_records, true);
+}
+
+// update() aligns every particle between computeLikelihoodMap and the weighting (slam_update_core); NULL: off
+int gms_slam_set_align(gms_slam *s, const gms_align_params *params) {
+    REQUIRE(s, "gms_slam_set_align: null handle");
+    int rc = params ? gms_align_check_for(params, "gms_slam_set_align") : GMS_OK;
+    if (rc) return rc;
+    REQUIRE(s->map && s->pf, "gms_slam_set_align: not a gms_slam handle");
+    rc = slam_enter(s, "gms_slam_set_align", SLAM_ALLOW_SHARD | SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
+    if (!params) { s->align_on = 0; return GMS_OK; }
+    if (!s->d_align_rec) {
+        HIPCHK(hipSetDevice(s->map->device));
+        if (hipMalloc(&s->d_align_rec, (size_t)s->n * sizeof(gms_align_record)) != hipSuccess) {
+            s->d_align_rec = nullptr;
+            return gms_fail(GMS_ERR_NOMEM, "gms_slam_set_align: device allocation failed (%d records)", s->n);
+        }
+        s->have_align_rec = 0;
+    }
+    s->align_prm = *params;
+    s->align_on = 1;
+    return GMS_OK;
+}
+
+// the records [n_filters * n] of the last aligned update.  Synchronises.
+int gms_slam_last_align(gms_slam *s, gms_align_record *records) {
+    REQUIRE(s && records, "gms_slam_last_align: null argument");
+    REQUIRE(s->map && s->pf, "gms_slam_last_align: not a gms_slam handle");
+    const int rc = slam_enter(s, "gms_slam_last_align", SLAM_ALLOW_SHARD | SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
+    if (!s->have_align_rec) return gms_fail(GMS_ERR_STATE, "gms_slam_last_align: no aligned update has run on this handle (gms_slam_set_align)");
+    gms_map *m = s->map;
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipMemcpyAsync(records, s->d_align_rec, (size_t)s->n * sizeof(gms_align_record), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return GMS_OK;
+}
+
+// diagnostics: the form the last alignment launch of the handle took (GMS_SLAM_ALIGN_PLANES / _MEMORY; 0: none yet)
+int gms_slam_align_form(const gms_slam *s, int32_t *form) {
+    REQUIRE(s && form, "gms_slam_align_form: null argument");
+    *form = s->align_form;
+    return GMS_OK;
 }
 
 // One recorded revolution as GridMapApp.onHandleData treats it (J/app/GridMapApp.java:133-192) for the filter with a map per particle:

@@ -25,29 +25,9 @@
 //   k_slam_deskew       the de-skew in front of update() where the caller hands over a raw revolution (GridMapApp.java:143-175): one
 //                       revolution, or every filter's own in one launch (gms_slam_frame_per_particle / gms_slam_frame_batch)
 #include "gms_device.h"
+#include "gms_slam_device.h"
 
-// a generation's arrays out of SlamBufs by SELECTION, never by a run-time index into the by-value kernel argument (that moves the
-// struct -- and whatever else the compiler then keeps addressable -- into scratch memory: k_slam_gather_one ran at a quarter of its speed)
-__device__ __forceinline__ double *sb_log(const SlamBufs &sb, int32_t g) { return g ? sb.log[1] : sb.log[0]; }
-__device__ __forceinline__ double *sb_lik(const SlamBufs &sb, int32_t g) { return g ? sb.lik[1] : sb.lik[0]; }
-__device__ __forceinline__ uint32_t *sb_code(const SlamBufs &sb, int32_t g) { return g ? sb.code[1] : sb.code[0]; }
-// the generation pair of particle p's filter: {draws that ran, the last resample() drew} (one filter: sb.epoch itself)
-__device__ __forceinline__ const int32_t *sb_epoch(const SlamBufs &sb, int32_t p) { return sb.epoch + 2 * (p / sb.n_per); }
-// a batched update: particle p's filter f = p / n -- its scan, count, motion and skipUpdate (SlamFilterArgs), its generation pair.
-// The motion-model variates are keyed by the filter-local index (mo.index0 = -f n): what a stand-alone handle of that seed draws.
-__device__ __forceinline__ void slam_batch_filter(const SlamBatch &bt, int32_t p, const gms_beam *__restrict__ &beams, int32_t &B, MotionArgs &mo,
-                                                  int32_t &integrate, const int32_t *&epoch) {
-    const int32_t f = p / bt.n;
-    const SlamFilterArgs fa = bt.tab[f];
-    beams += (size_t)f * (size_t)bt.beam_stride;
-    B = fa.count;
-    mo.on &= fa.flags & 1;
-    mo.d_center = fa.d_center; mo.d_theta = fa.d_theta; mo.d_center_sd = fa.d_center_sd; mo.d_theta_sd = fa.d_theta_sd;
-    mo.seed = fa.seed;
-    mo.index0 = -(int64_t)f * bt.n;
-    integrate &= (fa.flags >> 1) & 1;
-    epoch += 2 * f;
-}
+// (sb_log / sb_lik / sb_code / sb_epoch and slam_batch_filter: gms_slam_device.h, shared with gms_slam_align.hip)
 
 // likelihoodData of every particle's map from its logData (mode 1 of likelihood_body: no factor table, no tile states, every tile)
 template <int KH>

@@ -1680,6 +1680,32 @@ class _SlamHandle:
         before weighting it (SLAM.java:96; the reference calls findBestPoseOptim, :97, and keeps this search commented out beside it)"""
         check(load().gms_slam_set_refine(self._h, int(bool(on))))
 
+    def set_align(self, params=True):
+        """gms_slam_set_align: every update aligns each particle against its own field (gridmapslam.h "per-particle scan alignment")
+        between computeLikelihoodMap and the weighting -- the build's stand-in for findBestPoseOptim (SLAM.java:97).  params: an
+        AlignParams or a dict of its fields, True for the library's defaults, None (or False) to switch it off.  With set_refine() on
+        as well: the lattice search first, the alignment from its best pose."""
+        if params is None or params is False:
+            check(load().gms_slam_set_align(self._h, None))
+            return
+        prm = _align_params(None if params is True else params)
+        check(load().gms_slam_set_align(self._h, C.byref(prm)))
+
+    def last_align(self) -> np.ndarray:
+        """gms_slam_last_align: the records of the last aligned update, ALIGN_DTYPE [n] ([n_maps][n] on a batched handle); GmsError
+        (GMS_ERR_STATE) before there is one.  Waits for the stream."""
+        S = int(self.params.n_maps)
+        rec = np.empty((S, self.num_particles) if S > 1 else (self.num_particles,), dtype=_lib.ALIGN_DTYPE)
+        check(load().gms_slam_last_align(self._h, ptr(rec)))
+        return rec
+
+    def align_form(self) -> int:
+        """diagnostics: the form the handle's last alignment launch took -- GMS_SLAM_ALIGN_PLANES (the field's values computed in LDS
+        from the particle's class plane) or GMS_SLAM_ALIGN_MEMORY (the field written first); 0 before the first"""
+        form = C.c_int32(0)
+        check(load().gms_slam_align_form(self._h, C.byref(form)))
+        return int(form.value)
+
     def maps_copied(self) -> int:
         v = C.c_int64(0)
         check(load().gms_slam_copies(self._h, C.byref(v)))
@@ -1842,6 +1868,25 @@ class SLAMParticleMaps(_SlamHandle):
         check(load().gms_slam_update_per_particle(self._h, ptr(b), len(b), int(have), float(dc), float(dt), int(seed),
                                                   self._next_sequence(sequence), C.byref(st) if fetch else None))
         return self._fetched(st) if fetch else None
+
+    def align(self, z, params=None, records: bool = False):
+        """gms_slam_align: every particle moved, in place, by the continuous scan alignment of scan z against the field of ITS OWN map
+        as logData stands (gridmapslam.h "per-particle scan alignment").  No map and no weight changes; a following
+        update(sample_motion=False) weighs and integrates at the aligned poses.  records=True returns the records, ALIGN_DTYPE [n], and
+        waits for the stream.  (Inside every update instead: set_align().)"""
+        b = _beams_of(z).reshape(-1)
+        prm = _align_params(params)
+        rec = np.empty(self.num_particles, dtype=_lib.ALIGN_DTYPE) if records else None
+        check(load().gms_slam_align(self._h, ptr(b), len(b), C.byref(prm), None if rec is None else ptr(rec)))
+        return rec
+
+    def align_dev(self, dev_beams: int, B: int, params=None, records_out=None):
+        """align() on device-resident beams [B]; records_out: None, or a contiguous torch device tensor of n * 80 bytes, 8-byte aligned.
+        Runs on the handle's stream and synchronises nothing."""
+        prm = _align_params(params)
+        out = _device_ptr("align_dev", "records_out", records_out, _lib.ALIGN_DTYPE.itemsize * self.num_particles, optional=True)
+        check(load().gms_slam_align_dev(self._h, C.c_void_p(dev_beams), int(B), C.byref(prm), out))
+        return records_out
 
     def _fetched(self, st) -> float:
         self.strongest, self.neff = st.strongest, st.neff

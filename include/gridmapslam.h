@@ -1192,6 +1192,46 @@ int gms_map_align_dev(gms_map *m, int32_t mi, const gms_beam *dev_beams, int32_t
 int gms_pf_align(gms_pf *pf, const gms_beam *beams, int32_t B, const gms_align_params *params, gms_align_record *records);
 int gms_pf_align_dev(gms_pf *pf, const gms_beam *dev_beams, int32_t B, const gms_align_params *params, gms_align_record *dev_records);
 
+/* ---- per-particle scan alignment: every particle of a gms_slam against its own map ------------------------------------------------------
+ * The reference's SLAM.update calls findBestPoseOptim(p.m, z, p.pose) for every particle against that particle's own field
+ * (SLAM.java:96-97) between computeLikelihoodMap (:93) and the weighting (:99); its BOBYQA objective is 0 / NaN, so it moves nothing.
+ * This is the build's stand-in at that place: the continuous scan alignment above, per particle (GMapping's per-particle scan matching).
+ *
+ * gms_slam_align: every particle i the handle holds is aligned IN PLACE.  The definition is exactly "continuous scan alignment" with
+ * L = the field computeLikelihoodMap(p_i.m) would write from particle i's logData as it stands -- the field the next update scores
+ * against --, W, H, res, pos the handle's, the start pose the particle's; 1 <= B <= max_beams; records [n] or NULL.  The call changes
+ * no map and no weight, and what gms_slam_download_map returns for likelihoodData is what it returned before.  Afterwards the filter is
+ * as gms_pf_set_poses with the new poses would leave it: the cached trig is refreshed.  A shard aligns its own block.  A batched handle
+ * (n_maps > 1): GMS_ERR_STATE, nothing touched -- use gms_slam_set_align there.  The host form waits for the stream only to read the
+ * records back.  _dev: dev_beams and dev_records are device memory, 8-byte aligned; runs on the handle's stream, synchronises nothing.
+ * Checked before anything is enqueued (GMS_ERR_INVALID, the outputs untouched): NULL handle or beams, the parameters
+ * (gms_align_check), B, and in the _dev form the alignment.
+ *
+ * gms_slam_set_align: non-NULL parameters are checked and copied; from then on every update of the handle -- gms_slam_update_per_particle
+ * [_dev], gms_slam_update_batch[_dev], gms_slam_update_local[_dev], both frame calls -- aligns each particle between
+ * computeLikelihoodMap and the weighting: the particle is weighted, its map updated and its history row written at the aligned pose.
+ * Where the update draws the motion-model sample the alignment starts from it; with gms_slam_set_refine on as well the order is the
+ * lattice search, then the alignment from the lattice's best pose (coarse to fine).  skipUpdate (|dTheta| > 30 degrees) skips only the
+ * map update, as without it.  B == 0: every pose stays as it is (status 2).  NULL: off, the default; an update then issues exactly
+ * the launches it issued before.
+ * gms_slam_last_align: the records [n_maps * n] of the last aligned update (so a caller counts statuses without a second pass);
+ * GMS_ERR_STATE before there is one (and after gms_slam_reset).  Synchronises.
+ *
+ * How: one workgroup per particle.  Where the handle keeps the particles' class planes (2 bits per cell) and a plane fits a workgroup's
+ * LDS beside the scan, the plane is staged there and the four values per beam are computed on demand per evaluation -- the horizontal
+ * sums of the rows j0 - k .. j0 + 1 + k at the columns i0 and i0 + 1, then the vertical sums: computeLikelihoodMap's operations in its
+ * order for those cells -- and one wavefront forms the sums, the tree, the solve and the step (GMS_SLAM_ALIGN_PLANES).  Otherwise the
+ * field is written to memory first and read there (GMS_SLAM_ALIGN_MEMORY).  Both give the same bits; the environment variable
+ * GMS_SLAM_ALIGN_FIELD=memory|planes, read at creation, forces a form where it exists.  gms_slam_align_form (diagnostics): the form the
+ * handle's last alignment launch took, 0 before the first. */
+#define GMS_SLAM_ALIGN_PLANES 1
+#define GMS_SLAM_ALIGN_MEMORY 2
+int gms_slam_align(gms_slam *s, const gms_beam *beams, int32_t B, const gms_align_params *params, gms_align_record *records);
+int gms_slam_align_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, const gms_align_params *params, gms_align_record *dev_records);
+int gms_slam_set_align(gms_slam *s, const gms_align_params *params);
+int gms_slam_last_align(gms_slam *s, gms_align_record *records);
+int gms_slam_align_form(const gms_slam *s, int32_t *form);
+
 /* ---- trajectory rollouts: which velocity command can be sent without hitting something ---------------------------------------------
  * The inner loop of a local planner (dynamic window, lattice primitives): K candidate arcs, each sampled at T steps, the robot's
  * footprint tested against the inflated obstacle plane at every step, and the clearance and cost-to-go fields read along the way.  This

@@ -480,7 +480,16 @@ public:
     void reset() { check(gms_slam_reset(h_)); }                                             // :65-77
     /** update() refines every particle's pose with GridMap.findBestPose against the particle's own field before weighting it (:96) */
     void setRefine(bool on) { check(gms_slam_set_refine(h_, on ? 1 : 0)); }
-    /** update(z, u) (:80-131); returns Neff.  seed / sequence select the motion model's variates (one sequence per frame). */
+    /** update() aligns every particle against its own field between computeLikelihoodMap and the weighting -- the stand-in for
+     *  findBestPoseOptim (:97; gridmapslam.h "per-particle scan alignment"); params null: off.  With setRefine: lattice first. */
+    void setAlign(const gms_align_params *params) { check(gms_slam_set_align(h_, params)); }
+    /** the same alignment as a call of its own: every particle in place, no map and no weight changes; records [n] or null */
+    void align(const Observation &z, const gms_align_params &params, gms_align_record *records = nullptr) {
+        check(gms_slam_align(h_, z.getMeasurements().data(), z.getNumberOfMeasurements(), &params, records));
+    }
+    /** the records [n] of the last aligned update (throws before there is one); waits for the stream */
+    void lastAlign(gms_align_record *records) { check(gms_slam_last_align(h_, records)); }
+    /** update(z, u) (:80-131); returns Neff. seed / sequence select the motion model's variates (one sequence per frame). */
     double update(const Observation &z, const Odometry &u, uint64_t seed, uint64_t sequence, bool sampleMotion = true) {
         gms_pf_stats st{};
         check(gms_slam_update_per_particle(h_, z.getMeasurements().data(), z.getNumberOfMeasurements(), sampleMotion ? 1 : 0, u.dCenter, u.dTheta,
