@@ -186,6 +186,20 @@ class GmsRolloutRisk(C.Structure):
     ]
 
 
+class GmsWarp(C.Structure):
+    """gms_warp: a map warp -- the pose of the source map's world frame in the destination's, the destination rectangle and the op
+    (gridmapslam.h "map warps"), 64 bytes"""
+    _fields_ = [
+        ("tx", C.c_double), ("ty", C.c_double), ("c", C.c_double), ("s", C.c_double), ("clamp", C.c_double),
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("op", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+class GmsWarpStats(C.Structure):
+    """gms_warp_stats: the class-pair counts of a warp, 80 bytes"""
+    _fields_ = [("pair", (C.c_int64 * 3) * 3), ("n_outside", C.c_int64)]
+
+
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
 ROLLOUT_STEP_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("c", "<f4"), ("s", "<f4")])     # gms_rollout_step
@@ -196,6 +210,9 @@ assert ROLLOUT_STEP_DTYPE.itemsize == 16 and C.sizeof(GmsRollout) == 16
 GMS_ROLLOUT_MAX_K, GMS_ROLLOUT_MAX_T, GMS_ROLLOUT_MAX_F = 4096, 256, 64
 GMS_ROLLOUT_CANDIDATES = 16      # candidates a rollout workgroup takes (gms_rollout_candidates_per_workgroup() of the library as built)
 GMS_ROLLOUT_HIT_OUTSIDE, GMS_ROLLOUT_HIT_RANGE, GMS_ROLLOUT_HIT_BLOCKED, GMS_ROLLOUT_START_BLOCKED = 1, 2, 4, 8      # gms_rollout_rec.flags
+WARP_STATS_DTYPE = np.dtype([("pair", "<i8", (3, 3)), ("n_outside", "<i8")])     # gms_warp_stats
+assert WARP_STATS_DTYPE.itemsize == C.sizeof(GmsWarpStats) == 80 and C.sizeof(GmsWarp) == 64
+GMS_WARP_COMPARE, GMS_WARP_REPLACE, GMS_WARP_ADD, GMS_WARP_FILL = 0, 1, 2, 3                     # gms_warp.op
 LOCATE_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsLocateRec._fields_])     # gms_locate_rec
 assert LOCATE_DTYPE.itemsize == C.sizeof(GmsLocateRec) == 16 and C.sizeof(GmsLocate) == 48
 GMS_LOCATE_SKIP = -32768
@@ -474,6 +491,13 @@ def load() -> C.CDLL:
     sig("gms_slam_rollout_dev", C.c_int, vp, i32, rop, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp)
     sig("gms_pf_rollout", C.c_int, vp, rop, vp, i32, i32, vp, i32, vp)
     sig("gms_pf_rollout_dev", C.c_int, vp, rop, vp, i32, i32, vp, i32, vp)
+    wp = C.POINTER(GmsWarp)
+    sig("gms_warp_pose", C.c_int, wp, f64, f64, f64)
+    sig("gms_warp_check", C.c_int, wp)
+    sig("gms_map_warp", C.c_int, vp, i32, vp, i32, wp, vp)
+    sig("gms_map_warp_dev", C.c_int, vp, i32, vp, i32, wp, vp)
+    sig("gms_slam_warp", C.c_int, vp, i32, i32, vp, i32, wp, vp, vp)
+    sig("gms_slam_warp_dev", C.c_int, vp, i32, i32, vp, i32, wp, vp, vp)
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

@@ -473,7 +473,7 @@ int gms_map_download_likelihood(gms_map *m, double *lik) {
 }
 
 // `later` waits (stream order, no host synchronise) for everything enqueued on `earlier` so far
-static int stream_after(hipStream_t later, hipStream_t earlier, const char *what) {
+int gms_stream_after(hipStream_t later, hipStream_t earlier, const char *what) {
     if (later == earlier) return GMS_OK;
     hipEvent_t ev;
     HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -496,11 +496,11 @@ int gms_map_copy(gms_map *dst, const gms_map *src) {                  // GridMap
     // The copies run on dst's stream and read src's arrays: dst's stream waits for what src's stream holds so far (the flushed
     // apply pass among it), and src's stream waits for the copies before anything enqueued on it later may write those arrays
     // again (a ray cast's apply pass, reset, upload): both directions in stream order, no host synchronise.
-    int rc = stream_after(dst->stream, src->stream, "gms_map_copy");
+    int rc = gms_stream_after(dst->stream, src->stream, "gms_map_copy");
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(dst->d_log, src->d_log, bytes, hipMemcpyDeviceToDevice, dst->stream));
     HIPCHK(hipMemcpyAsync(dst->d_lik, src->d_lik, bytes, hipMemcpyDeviceToDevice, dst->stream));
-    rc = stream_after(src->stream, dst->stream, "gms_map_copy");
+    rc = gms_stream_after(src->stream, dst->stream, "gms_map_copy");
     if (rc) return rc;
     gms_launch_factors(dst);
     map_log_replaced(dst);
@@ -521,10 +521,10 @@ int gms_map_combine(gms_map *dst, gms_map *src) {                        // Grid
     gms_ensure_lik(dst);               // the destination's likelihoodData keeps its last field (its logData is about to be replaced)
     gms_flush_apply(src);
     gms_flush_apply(dst);
-    int rc = stream_after(dst->stream, src->stream, "gms_map_combine");
+    int rc = gms_stream_after(dst->stream, src->stream, "gms_map_combine");
     if (rc) return rc;
     gms_launch_combine(src, dst);
-    rc = stream_after(src->stream, dst->stream, "gms_map_combine");
+    rc = gms_stream_after(src->stream, dst->stream, "gms_map_combine");
     if (rc) return rc;
     map_log_replaced(dst);
     HIPCHK(hipGetLastError());

@@ -500,6 +500,9 @@ int gms_fail(int code, const char *fmt, ...);
     } while (0)
 // gms_pf_set_shard behind its refuse_owned_maps guard (gms_host.hip; not exported): gms_slam_create_shard places its own filter through it
 extern "C" int gms_pf_place_shard(gms_pf *pf, int64_t offset, int64_t n_global);
+// `later` waits (stream order, no host synchronise) for everything enqueued on `earlier` so far (gms_host.hip; not exported): how two
+// handles on different streams hand arrays to each other (gms_map_copy, gms_map_combine, the map warps)
+extern "C" int gms_stream_after(hipStream_t later, hipStream_t earlier, const char *what);
 // host beams [n_maps][B] -> the map's device staging buffer [n_maps][max_beams] through the pinned ring (gms_host.hip)
 int gms_stage_beams(gms_map *m, const gms_beam *beams, int32_t B);
 // the scan of a filter-wide request (one scan per map): the host form's is staged into m->d_beams, the maps max_beams apart; a device

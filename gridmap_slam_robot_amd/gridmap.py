@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
 __all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
-           "cells_of_poses", "descend", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance"]
+           "cells_of_poses", "descend", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance", "warp_agreement", "map_as_scan"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -434,6 +434,78 @@ def rollout_pick(records, T: Optional[int] = None, min_d2: int = 0, w_cost: floa
         return -1
     score = -float(w_cost) * r["best_cost"].astype(np.float64) + float(w_clear) * np.sqrt(r["min_d2"].astype(np.float64))
     return int(np.argmax(np.where(ok, score, -np.inf)))
+
+
+_WARP_OPS = {"compare": _lib.GMS_WARP_COMPARE, "replace": _lib.GMS_WARP_REPLACE, "add": _lib.GMS_WARP_ADD, "fill": _lib.GMS_WARP_FILL}
+
+
+def _warp_request(W: int, H: int, pose, c, s, op, rect, clamp: float) -> _lib.GmsWarp:
+    """gms_warp for a destination of W x H cells: pose = (x, y, theta) of the SOURCE map's world frame in the destination's world
+    (gms_warp_pose: the host's libm), or -- c and s given -- (x, y) beside that cosine and sine, taken as they are (exact quarter
+    turns: c=0, s=1); None: the origin.  op: "compare", "replace", "add", "fill" or a GMS_WARP_* value; checked by gms_warp_check."""
+    w = _lib.GmsWarp()
+    w.x0, w.y0, w.w, w.h = _rect(W, H, rect)
+    w.op = _WARP_OPS[op] if isinstance(op, str) else int(op)
+    w.clamp = float(clamp)
+    p = (0.0, 0.0, 0.0) if pose is None else tuple(float(v) for v in pose)
+    if (c is None) != (s is None):
+        raise ValueError("warp: c and s are given together")
+    if c is None:
+        if len(p) != 3:
+            raise ValueError("warp: pose is (x, y, theta)")
+        check(load().gms_warp_pose(C.byref(w), p[0], p[1], p[2]))
+    else:
+        w.tx, w.ty, w.c, w.s = p[0], p[1], float(c), float(s)
+    check(load().gms_warp_check(C.byref(w)))
+    return w
+
+
+def _query_warp(src: _Source, dst: "GridMap", mi: int, w: _lib.GmsWarp, stats, stats_out, shown_out, dev: bool) -> tuple:
+    """gms_<kind>_warp[_dev]: a particle's source takes (which, filter) in front of the destination, a map's follows it.  Returns
+    (stats,) and then what the source appends; stats: a WARP_STATS_DTYPE record, None where not wanted, or -- dev -- stats_out"""
+    lead = (*src.lead, src.filter, dst._h, int(mi)) if src.shows else (dst._h, int(mi), *src.lead)
+    if dev:
+        sp = _device_ptr("warp", "stats_out", stats_out, _lib.WARP_STATS_DTYPE.itemsize, optional=True)
+        tail = (_shown_ptr("warp", shown_out),) if src.shows else ()
+        check(getattr(load(), f"gms_{src.kind}_warp_dev")(*lead, C.byref(w), sp, *tail))
+        return (stats_out, shown_out) if src.shows else (stats_out,)
+    rec = np.zeros((), dtype=_lib.WARP_STATS_DTYPE) if stats else None
+    shown = C.c_int32(-1)
+    tail = (C.byref(shown),) if src.shows else ()
+    check(getattr(load(), f"gms_{src.kind}_warp")(*lead, C.byref(w), None if rec is None else ptr(rec), *tail))
+    return (rec, int(shown.value)) if src.shows else (rec,)
+
+
+def warp_agreement(stats) -> dict:
+    """What the class-pair counts of a warp (WARP_STATS_DTYPE: pair[destination class][source class], classes 0 unknown, 1 free,
+    2 occupied) say about the pose, plain numpy: overlap -- both known --, agree -- free/free plus occupied/occupied --, conflict --
+    free/occupied plus occupied/free --, gained -- destination unknown, source known --, outside.  Compare first (op="compare"),
+    merge only where conflict is small beside agree: a false merge cannot be taken back."""
+    pair = np.asarray(stats["pair"], dtype=np.int64).reshape(3, 3)
+    return {"overlap": int(pair[1:, 1:].sum()), "agree": int(pair[1, 1] + pair[2, 2]), "conflict": int(pair[1, 2] + pair[2, 1]),
+            "gained": int(pair[0, 1] + pair[0, 2]), "outside": int(np.asarray(stats["n_outside"]).sum())}
+
+
+def map_as_scan(log, position, resolution: float, max_beams: int = 4096) -> np.ndarray:
+    """The occupied cells (logData > 0) of a host logData array [H][W] as gms_beam records: local_x / local_y the cell's centre in
+    that map's OWN world -- position + (index + 0.5) * resolution in double, position and resolution as floats, what the warp's
+    arithmetic widens --, distance their hypot, hit 1.  More than max_beams cells: every ceil(n / max_beams)-th in index order
+    (x + y * W).  The idiom: the pose that other.locate(locate_offsets(scan, ...)) -> locate_poses() -> other.align(scan, poses)
+    return for these beams in ANOTHER map is the pose of this map's world frame in that map's world -- it IS the pose of
+    other.warp_from(this, pose)."""
+    a = np.asarray(log, dtype=np.float64)
+    if a.ndim != 2 or max_beams < 1:
+        raise ValueError("map_as_scan: log is one map [H][W] and max_beams >= 1")
+    idx = np.flatnonzero(a.reshape(-1) > 0)
+    if len(idx) > max_beams:
+        idx = idx[::-(-len(idx) // int(max_beams))]
+    res, px, py = (np.float64(np.float32(v)) for v in (resolution, position[0], position[1]))
+    b = np.zeros(len(idx), dtype=BEAM_DTYPE)
+    b["local_x"] = px + ((idx % a.shape[1]).astype(np.float64) + 0.5) * res
+    b["local_y"] = py + ((idx // a.shape[1]).astype(np.float64) + 0.5) * res
+    b["distance"] = np.hypot(b["local_x"], b["local_y"])
+    b["hit"] = 1
+    return b
 
 
 def _frontier_cost(cost, W: int, H: int):
@@ -970,6 +1042,24 @@ class GridMap:
     def combine_from(self, batch: "GridMap"):
         """calculateCombined (J/app/GridMapApp.java:439-458): this (single) map := combination of batch's maps."""
         check(load().gms_map_combine(self._h, batch._h))
+
+    def warp_from(self, src: "GridMap", pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0, mi: int = 0, src_mi: int = 0,
+                  stats: bool = True):
+        """Map src_mi of src read through a rigid transform and compared with, copied into, added to or filled into rectangle rect
+        (None: all) of map mi (gridmapslam.h "map warps"): src of any size, corner and resolution.  pose = (x, y, theta): the pose of
+        src's world frame in this map's world -- or (x, y) with c and s, the cosine and sine as they are --; op "compare" (writes
+        nothing), "replace", "add" (log-odds fusion where src is known, clamped to [-clamp, clamp] when clamp > 0) or "fill" (only
+        where this map is unknown and src is known).  Returns the class-pair counts, a WARP_STATS_DTYPE record taken from this
+        map's values BEFORE the call (warp_agreement() reads it), or None with stats=False; synchronises."""
+        w = _warp_request(self.W, self.H, pose, c, s, op, rect, clamp)
+        return _query_warp(src._src(src_mi), self, mi, w, stats, None, None, False)[0]
+
+    def warp_from_dev(self, src: "GridMap", stats_out, pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0, mi: int = 0,
+                      src_mi: int = 0):
+        """warp_from() with the counts written to stats_out -- a contiguous torch device tensor of 80 bytes, 8-byte aligned, or None
+        -- on this handle's stream; nothing is synchronised"""
+        w = _warp_request(self.W, self.H, pose, c, s, op, rect, clamp)
+        return _query_warp(src._src(src_mi), self, mi, w, False, stats_out, None, True)[0]
 
     def deskew(self, angles, distances, hits, d_center: float, d_theta: float) -> "Observation":
         """The de-skew loop of GridMapApp.onHandleData (J/app/GridMapApp.java:143-175), on the device."""
@@ -1777,6 +1867,11 @@ class _SlamHandle:
         """gms_slam_rollout[_dev]: (records, shown); poses None: the shown particle's own pose"""
         return _query_rollout(self._src("rollout", which, filter), poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
 
+    def _warp(self, which, filter: int, dst, pose, c, s, op, rect, clamp: float, mi: int, stats, stats_out, shown_out, dev: bool):
+        """gms_slam_warp[_dev]: (stats, shown)"""
+        w = _warp_request(dst.W, dst.H, pose, c, s, op, rect, clamp)
+        return _query_warp(self._src("warp", which, filter), dst, mi, w, stats, stats_out, shown_out, dev)
+
     def _locate(self, which, filter: int, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
                 shown_out):
         """gms_slam_locate[_dev]: (records, shown), or (out, n_out, shown_out)"""
@@ -2016,6 +2111,19 @@ class SLAMParticleMaps(_SlamHandle):
         None, clear / cost / out / shown_out torch device tensors; (out, shown_out), nothing is synchronised"""
         return self._rollout(which, 0, poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
 
+    def warp_into(self, dst: GridMap, which="strongest", pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0, mi: int = 0,
+                  stats: bool = True):
+        """Particle `which`'s OWN map read through a rigid transform into map mi of dst (GridMap.warp_from's arguments, pose: this
+        filter's world frame in dst's world): (stats, shown).  which = a particle index or "strongest" (picked on the device as
+        view() picks it, GMS_ERR_STATE before the first update).  The filter is only read; dst may not be its own grid_map."""
+        return self._warp(which, 0, dst, pose, c, s, op, rect, clamp, mi, stats, None, None, False)
+
+    def warp_into_dev(self, dst: GridMap, stats_out, which="strongest", pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0,
+                      mi: int = 0, shown_out=None):
+        """warp_into() on dst's stream: stats_out / shown_out torch device tensors (80 bytes, 8-byte aligned; int32) or None;
+        (stats_out, shown_out), nothing is synchronised"""
+        return self._warp(which, 0, dst, pose, c, s, op, rect, clamp, mi, False, stats_out, shown_out, True)
+
     def locate(self, offsets, which="strongest", rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
                free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):
         """Global scan matching in particle `which`'s OWN map (GridMap.locate's records): (records, shown).  which = a particle index
@@ -2249,6 +2357,12 @@ class SLAMParticleMapsBatch(_SlamHandle):
                     not_free: bool = True, clear=None, cost=None, shown_out=None):
         """SLAMParticleMaps.rollout_dev for filter `filter`"""
         return self._rollout(self._local(filter, which), filter, poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
+
+    def warp_into(self, dst: GridMap, which="strongest", filter: int = 0, pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0,
+                  mi: int = 0, stats: bool = True):
+        """SLAMParticleMaps.warp_into for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
+        is the handle-wide slot filter * num_particles + k whose map was read, as view() reports it"""
+        return self._warp(self._local(filter, which), filter, dst, pose, c, s, op, rect, clamp, mi, stats, None, None, False)
 
     def locate(self, offsets, which="strongest", filter: int = 0, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
                free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):

@@ -1357,6 +1357,84 @@ int gms_pf_rollout(gms_pf *pf, const gms_rollout *r, const gms_rollout_step *arc
 int gms_pf_rollout_dev(gms_pf *pf, const gms_rollout *r, const gms_rollout_step *dev_arcs, int32_t K, int32_t T, const float *dev_points, int32_t F,
                        gms_rollout_risk *dev_out);
 
+/* ---- map warps: one map read through a rigid transform, compared with another or merged into it -------------------------------------
+ * Every map is fixed to the frame gms_params gave it; gms_map_copy and gms_map_combine need equal grids.  A warp reads the logData of a
+ * SOURCE map through a pose and compares it with, copies it into, adds it to or fills it into a rectangle of a DESTINATION map of any
+ * other size, corner and resolution: growing or re-centring a map, comparing two robots' or two sessions' maps, fusing them, and
+ * taking a particle's map out of a gms_slam.  This library's own definition (the reference has no such method); every count is an
+ * integer and every stored value is unique.
+ *
+ * THE POSE       gms_warp {tx, ty, c, s}: the pose of the SOURCE map's world frame in the DESTINATION's world,  p_dst = R p_src + t,
+ *                R = [[c, -s], [s, c]].  Cosine and sine are stored, not an angle: the device takes no trig, exact quarter turns can be
+ *                asked for (c = 0, s = 1), and a host that restates the arithmetic reads the doubles the kernel used.  gms_warp_pose
+ *                fills them from (x, y, theta) with the host's libm.  The pose gms_map_locate -> gms_map_align return for the source
+ *                map's occupied cells, handed over as beams, in the destination map IS this pose.
+ * THE ARITHMETIC all in double; both maps' float position.x, position.y and resolution are widened to double; every product, sum and
+ *                quotient is rounded on its own (nothing is contracted).  For cell (x, y) of the destination rectangle
+ *                    cx = pos_x_d + (x + 0.5) * res_d,   cy likewise                          the cell's centre
+ *                    dx = cx - tx,   dy = cy - ty
+ *                    u  = c * dx + s * dy,   v = c * dy - s * dx                              ... in the source's world
+ *                    qx = floor((u - pos_x_s) / res_s),   qy = floor((v - pos_y_s) / res_s)
+ *                The cell HAS A SOURCE CELL (qx, qy) if and only if 0 <= qx < W_s and 0 <= qy < H_s, compared as doubles before any
+ *                conversion to an integer (NaN fails); every other cell of the rectangle counts in n_outside and is left alone.
+ *                Nearest cell only: sampling the centre leaves half a cell between the arithmetic and a cell edge whenever the
+ *                transform is a whole-cell shift or a quarter turn.  Interpolation and coarsening rules are not offered.
+ * THE CLASSES    occupied l > 0 (class 2), free l < 0 (class 1), unknown everything else -- 0, -0.0, NaN -- (class 0): the predicates
+ *                of the planes and the casts.
+ * THE OPS        with d the destination cell's value and v its source cell's, both as a download would return them at this moment:
+ *                  GMS_WARP_COMPARE   writes nothing.
+ *                  GMS_WARP_REPLACE   d := v bit for bit, NaN and -0.0 included.
+ *                  GMS_WARP_ADD       only where v is known (class 1 or 2):  r = d + v;  with clamp > 0:  if (r > clamp) r = clamp;
+ *                                     if (r < -clamp) r = -clamp;  d := r.  A NaN in d stays as it is, bit for bit; an unknown source
+ *                                     cell never poisons or changes the destination.
+ *                  GMS_WARP_FILL      d := v bit for bit only where d is unknown and v is known.
+ * THE STATISTICS gms_warp_stats (may be NULL), filled for every op from the destination's values BEFORE the call:  pair[a][b] counts
+ *                the cells with a source cell whose destination class is a and whose source class is b;  n_outside the cells without
+ *                one.  The ten counters sum to w * h.  Both known: the overlap; pair[1][1] + pair[2][2] agree, pair[1][2] + pair[2][1]
+ *                conflict -- the evidence to accept or reject a candidate pose by BEFORE merging under it.
+ *
+ * Refused with GMS_ERR_INVALID and nothing touched: a NULL handle or request; a map index out of range; x0, y0 < 0, w, h < 1 or a
+ * rectangle that leaves the destination (the views' rule); an unknown op; a non-finite tx, ty, c, s or clamp; clamp < 0;
+ * |c*c + s*s - 1| > 1e-6 (a sanity bound on the input, no tolerance of the arithmetic); handles on different devices; the same map as
+ * source and destination (two maps of one batched handle are allowed); for gms_slam_warp the gms_slam's own map handle as destination.
+ *
+ * State: a destination written by REPLACE, ADD or FILL is left exactly as gms_map_upload_log of the resulting array would leave it -- a
+ * deferred `logData +=` pass is applied first (ADD adds to the applied values), likelihoodData stays until the next build, the bit
+ * planes, the factor table, the seeding table and the tiles' states are invalidated.  COMPARE changes no later result of either handle.
+ * The source is read as a download would return it, its own deferred pass included.  Cells outside the rectangle and the other maps of
+ * a batched handle are not touched.  The kernel runs on the DESTINATION's stream; where the source's handle runs on another one the two
+ * are ordered in both directions by events, as gms_map_combine orders them, and the host waits for nothing.
+ *
+ * How: one kernel per op.  A workgroup of 256 lanes takes a tile of 64 x 64 cells of the rectangle, a wavefront a row of 64 destination
+ * cells at a time -- one coalesced 512-byte load and store -- and gathers the source cells directly.  The counts are nine ballots per
+ * row and one for the outside, summed in registers over the tile's rows, combined through LDS, and added with one 64-bit integer atomic
+ * per non-zero counter and workgroup. */
+enum { GMS_WARP_COMPARE = 0, GMS_WARP_REPLACE = 1, GMS_WARP_ADD = 2, GMS_WARP_FILL = 3 };
+typedef struct gms_warp {           /* 64 bytes */
+    double tx, ty, c, s;            /*  0: the pose of the source map's world frame in the destination's world */
+    double clamp;                   /* 32: GMS_WARP_ADD: the result is clamped to [-clamp, clamp]; 0 = no clamp */
+    int32_t x0, y0, w, h;           /* 40: the destination cell rectangle, as gms_view's */
+    int32_t op, pad;                /* 56: GMS_WARP_*; pad is not read */
+} gms_warp;
+typedef struct gms_warp_stats {     /* 80 bytes */
+    int64_t pair[3][3];             /*  0: [class of the destination cell BEFORE the call][class of its source cell]; 0 unknown, 1 free, 2 occupied */
+    int64_t n_outside;              /* 72: cells of the rectangle without a source cell */
+} gms_warp_stats;
+/* Pure host code: tx = x, ty = y, c = cos(theta), s = sin(theta) with the host's libm (x, y, theta finite); the other fields stay. */
+int gms_warp_pose(gms_warp *w, double x, double y, double theta);
+/* Pure host code: every check above that needs no handle. */
+int gms_warp_check(const gms_warp *w);
+/* Map mi_src of src through w into map mi_dst of dst.  The host form synchronises the destination's stream and returns the counts;
+ * _dev writes them to device memory (8-byte aligned) on the destination's stream and synchronises nothing. */
+int gms_map_warp(gms_map *dst, int32_t mi_dst, gms_map *src, int32_t mi_src, const gms_warp *w, gms_warp_stats *stats);
+int gms_map_warp_dev(gms_map *dst, int32_t mi_dst, gms_map *src, int32_t mi_src, const gms_warp *w, gms_warp_stats *dev_stats);
+/* The per-particle filter as the source: the logData of the shown particle, as gms_slam_download_map would return it, into map mi_dst of
+ * dst.  `which`, GMS_VIEW_STRONGEST, `filter`, *shown (may be NULL; _dev: a device int32_t *) and the GMS_ERR_STATE cases are
+ * gms_slam_view's; particle and generation are picked on the device.  The filter is only read: no later result of it changes. */
+int gms_slam_warp(gms_slam *s, int32_t which, int32_t filter, gms_map *dst, int32_t mi_dst, const gms_warp *w, gms_warp_stats *stats, int32_t *shown);
+int gms_slam_warp_dev(gms_slam *s, int32_t which, int32_t filter, gms_map *dst, int32_t mi_dst, const gms_warp *w, gms_warp_stats *dev_stats,
+                      int32_t *dev_shown);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -170,6 +170,14 @@ public:
         check(gms_map_gain(h_, mi, &g, p.data(), (int32_t)poses.size(), ms.data(), (int32_t)ms.size(), out.data()));
         return out;
     }
+    /** Map srcMi of src read through the rigid transform w -- the pose of src's world frame in this map's world -- and compared with,
+     *  copied into, added to or filled into the rectangle of map mi (gridmapslam.h "map warps"; w.op: GMS_WARP_*).  Returns the
+     *  class-pair counts, taken from this map's values before the call. */
+    gms_warp_stats warpFrom(GridMap &src, const gms_warp &w, int mi = 0, int srcMi = 0) {
+        gms_warp_stats st{};
+        check(gms_map_warp(h_, mi, src.h_, srcMi, &w, &st));
+        return st;
+    }
     /** Trajectory rollouts (gridmapslam.h "trajectory rollouts") from every start pose in map mi: arcs [K][T] (gms_rollout_arcs makes
      *  unicycle arcs), points [F][2] the footprint, clear / cost whole-map fields or null; records [poses.size()][K], row-major. */
     std::vector<gms_rollout_rec> rollout(const std::vector<Pose> &poses, const gms_rollout &req, const std::vector<gms_rollout_step> &arcs, int K, int T,
@@ -612,6 +620,15 @@ public:
         rec.resize((size_t)n);
         if (shown) *shown = picked;
         return rec;
+    }
+    /** Particle `which`'s own map read through the rigid transform w into map mi of dst (GridMap::warpFrom's counts); the filter is
+     *  only read.  *shown (may be null) receives the particle whose map was read */
+    gms_warp_stats warpInto(GridMap &dst, const gms_warp &w, int which = GMS_VIEW_STRONGEST, int mi = 0, int *shown = nullptr) {
+        gms_warp_stats st{};
+        int32_t picked = 0;
+        check(gms_slam_warp(h_, which, 0, dst.handle(), mi, &w, &st, &picked));
+        if (shown) *shown = picked;
+        return st;
     }
     /** Trajectory rollouts in particle `which`'s own map (GridMap::rollout's records); no poses: ONE start pose, the shown particle's
      *  own, read on the device.  *shown (may be null) receives the particle in whose map the arcs were rolled */
