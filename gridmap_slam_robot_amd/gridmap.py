@@ -2364,6 +2364,11 @@ class SLAMParticleMapsBatch(_SlamHandle):
         is the handle-wide slot filter * num_particles + k whose map was read, as view() reports it"""
         return self._warp(self._local(filter, which), filter, dst, pose, c, s, op, rect, clamp, mi, stats, None, None, False)
 
+    def warp_into_dev(self, dst: GridMap, stats_out, which="strongest", filter: int = 0, pose=None, *, c=None, s=None, op="compare", rect=None,
+                      clamp: float = 0.0, mi: int = 0, shown_out=None):
+        """SLAMParticleMaps.warp_into_dev for filter `filter`"""
+        return self._warp(self._local(filter, which), filter, dst, pose, c, s, op, rect, clamp, mi, False, stats_out, shown_out, True)
+
     def locate(self, offsets, which="strongest", filter: int = 0, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64,
                free_only: bool = True, full: bool = False, out=None, n_out=None, shown_out=None):
         """SLAMParticleMaps.locate for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
