@@ -46,8 +46,9 @@ def grid_uv(lx: float, ly: float, c: float, s: float, x: float, y: float, res: f
     return (X - pos_x) / res - 0.5, (Y - pos_y) / res - 0.5
 
 
-def evaluate(L, W: int, H: int, res: float, pos_x: float, pos_y: float, beams, pose):
-    """One evaluation: (Hm [6], g [3], S, n_used).  L: the field, flat [H * W]; res, pos_x, pos_y: the handle's floats, widened"""
+def evaluate(L, W: int, H: int, res: float, pos_x: float, pos_y: float, beams, pose, visit=None):
+    """One evaluation: (Hm [6], g [3], S, n_used).  L: the field, flat [H * W]; res, pos_x, pos_y: the handle's floats, widened.
+    visit (off by default): called as visit(b, i0, j0) for every used beam, before its terms; it takes no part in any value"""
     x, y, th = float(pose[0]), float(pose[1]), float(pose[2])
     c, s = orc.pose_trig(np.float32(th))
     part = [[0.0] * 64 for _ in range(10)]
@@ -62,6 +63,8 @@ def evaluate(L, W: int, H: int, res: float, pos_x: float, pos_y: float, beams, p
         if not (fu >= 0.0 and fu <= float(W - 2) and fv >= 0.0 and fv <= float(H - 2)):
             continue
         i0, j0 = int(fu), int(fv)
+        if visit is not None:
+            visit(b, i0, j0)
         fx, fy = gu - fu, gv - fv
         L00, L10 = float(L[j0 * W + i0]), float(L[j0 * W + i0 + 1])
         L01, L11 = float(L[(j0 + 1) * W + i0]), float(L[(j0 + 1) * W + i0 + 1])
@@ -102,13 +105,13 @@ def _clamp(v: float, m: float) -> float:
     return m if v > m else (-m if v < -m else v)
 
 
-def align_one(L, W, H, res, pos_x, pos_y, beams, pose, prm: dict):
-    """(final pose float32 [3], record dict) of one pose"""
+def align_one(L, W, H, res, pos_x, pos_y, beams, pose, prm: dict, visit=None):
+    """(final pose float32 [3], record dict) of one pose.  visit (off by default): visit(k, b, i0, j0) for every used beam of evaluation k"""
     p = [_f32(float(pose[0])), _f32(float(pose[1])), _f32(float(pose[2]))]
     status, done, k = STATUS_ITERS, 0, 0
     n0 = s0 = None
     while True:
-        Hm, g, S, n = evaluate(L, W, H, res, pos_x, pos_y, beams, p)
+        Hm, g, S, n = evaluate(L, W, H, res, pos_x, pos_y, beams, p, None if visit is None else functools.partial(visit, k))
         if k == 0:
             n0, s0 = n, S
         if status != STATUS_ITERS or k == prm["iters"]:
@@ -131,16 +134,17 @@ def align_one(L, W, H, res, pos_x, pos_y, beams, pose, prm: dict):
     return np.array(p, dtype=np.float32), rec
 
 
-def align(L, W, H, resolution, pos_x, pos_y, beams, poses, prm: dict):
+def align(L, W, H, resolution, pos_x, pos_y, beams, poses, prm: dict, visit=None):
     """poses [P][3] -> (float32 [P][3], records as a dict of arrays: the integers int32 [P], score0 / score float64 [P], H float64 [P][6]).
-    resolution, pos_x, pos_y: the handle's float32 values"""
+    resolution, pos_x, pos_y: the handle's float32 values.  visit (off by default): visit(i, k, b, i0, j0) for every used beam b of
+    evaluation k of pose i, (i0, j0) its first cell -- which cells a case reaches (tests/_slam_align_edge_cases.py)"""
     res, px, py = float(np.float32(resolution)), float(np.float32(pos_x)), float(np.float32(pos_y))
     L = np.ascontiguousarray(L, dtype=np.float64).reshape(-1)
     poses = np.asarray(poses, dtype=np.float32).reshape(-1, 3)
     out = np.empty_like(poses)
     rec = dict(status=[], iters_done=[], n_used=[], n_used0=[], score0=[], score=[], H=[])
     for i in range(len(poses)):
-        out[i], r = align_one(L, W, H, res, px, py, beams, poses[i], prm)
+        out[i], r = align_one(L, W, H, res, px, py, beams, poses[i], prm, None if visit is None else functools.partial(visit, i))
         for k in rec:
             rec[k].append(r[k])
     return out, {k: np.array(v, dtype=np.int32 if k in RECORD_INTS else np.float64) for k, v in rec.items()}

@@ -62,12 +62,14 @@ def _device(W, H, res, N, B, T, taps=None, seed=61, env=None, monkeypatch=None, 
     return dev
 
 
-def _expect(g, z, P, prm, logs=None, o=None):
-    """the restatement per particle on the field of its own logData: (poses float32 [n][3], records as a dict of arrays)"""
+def _expect(g, z, P, prm, logs=None, o=None, visit=None):
+    """the restatement per particle on the field of its own logData: (poses float32 [n][3], records as a dict of arrays).  visit (off
+    by default): _align_expect.align's visitor, called with the particle's index first"""
     poses, recs = np.empty((len(P), 3), np.float32), []
     for i in range(len(P)):
         L = g.build_likelihood(o.log(i) if logs is None else logs[i])
-        p, r = ax.align(L, g.W, g.H, g.resolution, g.pos[0], g.pos[1], z, np.asarray(P[i:i + 1], np.float32), prm)
+        p, r = ax.align(L, g.W, g.H, g.resolution, g.pos[0], g.pos[1], z, np.asarray(P[i:i + 1], np.float32), prm,
+                        None if visit is None else (lambda _, k, b, i0, j0, i=i: visit(i, k, b, i0, j0)))
         poses[i] = p[0]
         recs.append(r)
     return poses, {k: np.concatenate([r[k] for r in recs]) for k in recs[0]}
@@ -154,7 +156,7 @@ def test_map_shapes_and_blur_kernels(case, form, monkeypatch):
     dev.close()
 
 
-@pytest.mark.parametrize("B", [1, 63, 64, 65, 129, 300])
+@pytest.mark.parametrize("B", [1, 15, 16, 17, 63, 64, 65, 129, 300])
 def test_beam_counts(B):
     geo = (4.0, 4.0, 0.05, 8, B, 2)
     g, o, tr = _scene(*geo)
