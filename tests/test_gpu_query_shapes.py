@@ -39,6 +39,9 @@ FAR, NONE = 0xFFFF, 0xFFFFFFFF
 # of the traversable cells under BOTH predicates (test_the_expectations_contain_what_they_are_meant_to): with the unknown cells
 # blocked as well, 22 % of the cells, turn 0 walls the seed in on 128 x 128 and cuts the seven rows of 192 x 7.
 SEED_TURN = {(128, 128): 1, (192, 7): 7}
+# ... and the second log by W * 1000 + H + 500000 + 1000000 * turn: on 129 x 65 the first turn that occupies cell (128, 64), the only cell
+# of the last, ragged word of a sixteen-cell grouping of the map (tests/test_slam_query_inputs.py)
+SECOND_TURN = {(129, 65): 4}
 CAP = 8192
 N_BEAMS, N_PARTICLES = 48, 65
 
@@ -82,7 +85,7 @@ def log_of(shape, name):
     elif name == "random":
         log = _random_log(shape, W * 1000 + H + 1000000 * SEED_TURN.get(shape, 0))
     elif name == "second":                                                 # another random log, for the handle that is reused
-        log = _random_log(shape, W * 1000 + H + 500000)
+        log = _random_log(shape, W * 1000 + H + 500000 + 1000000 * SECOND_TURN.get(shape, 0))
     else:                                                                  # "last column": column W - 1 never observed, the rest free
         log = np.full((H, W), L_FREE)
         log[:, W - 1] = 0.0
