@@ -426,6 +426,8 @@ struct gms_slam {
     StageRing batch_ring;           // pinned staging of that block, or of a frame's raw revolutions and table (gms_slam_frame_batch)
     std::vector<int32_t> frame_counts;   // [n_filters] measurements of every filter's revolution in the last frame call (empty: none yet; gms_slam_last_beams)
     int32_t *d_plan;                // a shard's resample(): [3][n] device staging of {export list | local sources | positions in the received buffer}
+    int32_t shard_moves;            // a shard: the last gms_slam_shard_draw drew and its copies are still to be made -- gms_slam_shard_export and
+                                    // gms_slam_shard_gather are open (the gather closes them again; so do a draw that does not draw and gms_slam_reset)
     int32_t lazy_lik;               // resample() copies logData at once and likelihoodData when somebody asks for it: the next update's
                                     // computeLikelihoodMap overwrites every cell of it before anything on the path reads one (GMS_SLAM_LAZY_LIK_COPY=0: both at once)
     SlamField field;                // where every particle's likelihoodData stands (handle-wide).  Written by the slam_* transitions below only.

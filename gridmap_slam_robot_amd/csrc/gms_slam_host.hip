@@ -198,6 +198,7 @@ int gms_slam_reset(gms_slam *s) {                                               
     slam_was_reset(s);
     s->have_strongest = 0;                                                                   // (no update yet: nothing names a strongest particle)
     s->have_align_rec = 0;                                                                   // (... and no aligned one: gms_slam_last_align)
+    s->shard_moves = 0;                                                                      // (... and no draw whose copies a shard still owes)
     if (s->hist_cap) slam_hist_clear(s);                                                     // (the history starts over, at the same capacity)
     gms_launch_pf_init(s->pf);                                                               // Pose(0, 0, 0), weight 1 / numParticles (:68-71)
     pf_weights_set(s->pf);
@@ -505,6 +506,7 @@ int gms_slam_shard_draw(gms_slam *s, double r01, double fraction, int32_t *did, 
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
     slam_shard_drew(s);
+    s->shard_moves = 0;
     rc = slam_draw(s, &r01, fraction, nullptr, nullptr);
     if (rc) return rc;
     int32_t e[2] = {0, 0};
@@ -512,6 +514,16 @@ int gms_slam_shard_draw(gms_slam *s, double r01, double fraction, int32_t *did, 
     HIPCHK(hipMemcpy(e, s->d_epoch, sizeof(e), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(sources, s->pf->d_idx, (size_t)s->n * sizeof(int32_t), hipMemcpyDeviceToHost));
     *did = e[1];
+    s->shard_moves = e[1] != 0;                        // (where the rule said no, no generation changed: there is no "previous" one to move maps from)
+    return GMS_OK;
+}
+// what export and gather open with behind slam_enter: a shard whose last draw drew and has not been gathered yet.  Without one the
+// generation pair has not advanced, the kernels' "previous" generation is a stale one and a gather would overwrite the live maps from it
+static int slam_shard_moves_open(const gms_slam *s, const char *what) {
+    if (!s->d_plan) return gms_fail(GMS_ERR_INVALID, "%s: not a shard", what);
+    if (!s->shard_moves)
+        return gms_fail(GMS_ERR_STATE, "%s: no draw to move maps for (gms_slam_shard_draw has not run since the last reset, its rule said no, or "
+                                       "gms_slam_shard_gather has made that draw's copies already)", what);
     return GMS_OK;
 }
 // doubles per record of a particle: logData + its two class planes
@@ -527,7 +539,9 @@ int gms_slam_shard_export(gms_slam *s, const int32_t *local_indices, int32_t cou
     REQUIRE(s && (count == 0 || (local_indices && dev_dst)), "null argument");
     int rc0 = slam_enter(s, "gms_slam_shard_export", SLAM_ALLOW_SHARD);
     if (rc0) return rc0;
-    REQUIRE(s->d_plan && count >= 0 && count <= s->n, "gms_slam_shard_export: not a shard, or more records than particles");
+    rc0 = slam_shard_moves_open(s, "gms_slam_shard_export");
+    if (rc0) return rc0;
+    REQUIRE(count >= 0 && count <= s->n, "gms_slam_shard_export: more records than particles");
     if (count == 0) return GMS_OK;
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
@@ -544,7 +558,8 @@ int gms_slam_shard_gather(gms_slam *s, const int32_t *src_local, const int32_t *
     REQUIRE(s && src_local && recv_pos, "null argument");
     int rc0 = slam_enter(s, "gms_slam_shard_gather", SLAM_ALLOW_SHARD);
     if (rc0) return rc0;
-    REQUIRE(s->d_plan, "gms_slam_shard_gather: not a shard");
+    rc0 = slam_shard_moves_open(s, "gms_slam_shard_gather");
+    if (rc0) return rc0;
     gms_map *m = s->map;
     HIPCHK(hipSetDevice(m->device));
     for (int32_t k = 0; k < s->n; k++) {
@@ -555,6 +570,7 @@ int gms_slam_shard_gather(gms_slam *s, const int32_t *src_local, const int32_t *
     HIPCHK(hipMemcpyAsync(s->d_plan + 2 * (size_t)s->n, recv_pos, (size_t)s->n * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     gms_launch_slam_shard_gather(s->pf, gms_slam_bufs(s), s->d_plan + s->n, s->d_plan + 2 * (size_t)s->n, dev_recv, s->code_words);
+    s->shard_moves = 0;                                // the draw's copies are made: a second gather (after an update: over the live maps) is refused
     HIPCHK(hipGetLastError());
     return GMS_OK;
 }

@@ -383,7 +383,14 @@ int gms_slam_update_local(gms_slam *s, const gms_beam *beams, int32_t B, int32_t
 int gms_slam_update_local_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t sample_motion, double d_center, double d_theta,
                               uint64_t seed, uint64_t sequence);
 /* fraction < 0: unconditional; else `if (neff < fraction * n_global) resample()`.  *did: it drew; sources [n_local]: global source indices.
- * Synchronises. */
+ * Synchronises.
+ * The order of the three calls is kept by the handle.  A draw that drew (*did != 0) advances the maps' generation and opens export and
+ * gather: gms_slam_shard_export may run any number of times, each reading the generation the draw left behind, and ONE
+ * gms_slam_shard_gather makes the copies and closes both again -- a second gather would copy over maps that an update may have written
+ * since.  Before the first draw, after a draw whose rule said no (*did == 0: no generation changed, there is nothing to move and the
+ * "previous" generation is a stale one), after the gather and after gms_slam_reset both return GMS_ERR_STATE and touch nothing.  A
+ * gather refused for its plan (a source out of range, a remote slot without a record) leaves the draw open.  recv_pos is not checked
+ * against the length of dev_recv, which the call does not carry: that bound is the caller's. */
 int gms_slam_shard_draw(gms_slam *s, double r01, double fraction, int32_t *did, int32_t *sources);
 int gms_slam_record_doubles(const gms_slam *s, int64_t *doubles);
 int gms_slam_shard_export(gms_slam *s, const int32_t *local_indices, int32_t count, double *dev_dst);

@@ -45,11 +45,22 @@ def _stand_alone(ext, res, N, scans, start, r01s, fractions, refine=False):
     return out, logs, liks
 
 
-@pytest.mark.parametrize("world,refine", [(2, False), (4, False), (2, True)])
-def test_shards_on_one_gpu_equal_the_stand_alone_filter(world, refine):
-    ext, res, B, N, T = 6.0, 0.05, 90, 4 * GMS_BLOCK, (10 if not refine else 5)
+def _fractions(T):
     # (the plain product's Neff collapses on every frame: every third frame runs the rule with a threshold nothing falls below)
-    fractions = [1e-9 if k % 3 == 2 else 0.5 for k in range(T)]
+    return [1e-9 if k % 3 == 2 else 0.5 for k in range(T)]
+
+
+# (world, refine, ext, N, T).  Behind the three cases at 120 x 120 cells and four blocks: an ODD world, whose middle rank both sends and
+# receives on either side; 41 x 41 -- an odd cell count, so the planes start at an odd double of the record, which is shorter than one
+# chunk of the record movers (tests/_shard_record_cases.py); 313 x 313, where a plane is 24 512 bytes, just under the 24 576 a handle keeps
+CASES = [(2, False, 6.0, 4 * GMS_BLOCK, 10), (4, False, 6.0, 4 * GMS_BLOCK, 10), (2, True, 6.0, 4 * GMS_BLOCK, 5),
+         (3, False, 6.0, 3 * GMS_BLOCK, 10), (2, False, 2.05, 2 * GMS_BLOCK, 6), (2, False, 15.65, 2 * GMS_BLOCK, 4)]
+
+
+@pytest.mark.parametrize("world,refine,ext,N,T", CASES, ids=["2-False", "4-False", "2-True", "3-False-6.0", "2-False-2.05", "2-False-15.65"])
+def test_shards_on_one_gpu_equal_the_stand_alone_filter(world, refine, ext, N, T):
+    res, B = 0.05, 90
+    fractions = _fractions(T)
     scans, start = _scans(ext, B, T)
     r01s = np.random.default_rng(9).random(T)
     want, want_logs, want_liks = _stand_alone(ext, res, N, scans, start, r01s, fractions, refine)
@@ -111,7 +122,7 @@ def test_shards_on_one_gpu_equal_the_stand_alone_filter(world, refine):
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
     if os.path.isdir(out):
         import json
-        with open(os.path.join(out, f"slam_sharded_{world}{'_refine' if refine else ''}.json"), "w") as fh:
+        with open(os.path.join(out, f"slam_sharded_{world}{'_refine' if refine else ''}{'' if (ext, N) == (6.0, 4 * GMS_BLOCK) else f'_{ext}_{N}'}.json"), "w") as fh:
             json.dump({"what": "maps that crossed a shard boundary in resample(), shards as threads on one GPU", "shards": world, "particles": N,
                        "frames": T, "resampling_steps": n_res, "records_moved": moved, "records_moved_per_step": moved / max(1, n_res),
                        "fraction_of_maps_moved": moved / max(1, n_res) / N}, fh, indent=1)
@@ -171,12 +182,14 @@ def test_one_rank_over_real_rccl_collectives():
         dist.destroy_process_group()
 
 
-def test_one_rank_through_the_library_route():
+@pytest.mark.parametrize("ext", [4.0, 2.05])
+def test_one_rank_through_the_library_route(ext):
     """gms_slam_update_sharded_maps / gms_slam_resample_sharded_maps: the exchanges inside the library (RCCL all-reduce and all-gathers on a
     communicator of ONE rank -- what one GPU can run; the grouped ncclSend / ncclRecv of the records has no peer here and has never
-    executed) against the stand-alone handle, and a shard whose block is not the whole population refused by the one-rank communicator."""
+    executed) against the stand-alone handle, and a shard whose block is not the whole population refused by the one-rank communicator.
+    80 x 80 cells, and 41 x 41: an odd cell count."""
     from gridmap_slam_robot_amd.distributed import RcclComm
-    ext, res, B, N, T = 4.0, 0.05, 72, 2 * GMS_BLOCK, 5
+    res, B, N, T = 0.05, 72, 2 * GMS_BLOCK, 5
     scans, start = _scans(ext, B, T)
     r01s = np.random.default_rng(2).random(T)
     fractions = [0.5, 1e-9, 0.5, 0.5, 1e-9]
