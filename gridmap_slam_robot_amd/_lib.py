@@ -186,6 +186,20 @@ class GmsRolloutRisk(C.Structure):
     ]
 
 
+class GmsRoute(C.Structure):
+    """gms_route: a route request (gridmapslam.h "routes"), 24 bytes"""
+    _fields_ = [("max_cells", C.c_int32), ("max_waypoints", C.c_int32), ("look", C.c_int32), ("inflate", C.c_int32), ("mode", C.c_int32),
+                ("filter", C.c_int32)]
+
+
+class GmsRouteRec(C.Structure):
+    """gms_route_rec: one start's record, 32 bytes"""
+    _fields_ = [
+        ("n_cells", C.c_uint32), ("n_waypoints", C.c_uint32), ("start_cost", C.c_uint16), ("end_cost", C.c_uint16), ("min_d2", C.c_uint16),
+        ("flags", C.c_uint16), ("min_d2_at", C.c_uint32), ("end_x", C.c_int32), ("end_y", C.c_int32), ("pad", C.c_uint32),
+    ]
+
+
 class GmsWarp(C.Structure):
     """gms_warp: a map warp -- the pose of the source map's world frame in the destination's, the destination rectangle and the op
     (gridmapslam.h "map warps"), 64 bytes"""
@@ -210,6 +224,10 @@ assert ROLLOUT_STEP_DTYPE.itemsize == 16 and C.sizeof(GmsRollout) == 16
 GMS_ROLLOUT_MAX_K, GMS_ROLLOUT_MAX_T, GMS_ROLLOUT_MAX_F = 4096, 256, 64
 GMS_ROLLOUT_CANDIDATES = 16      # candidates a rollout workgroup takes (gms_rollout_candidates_per_workgroup() of the library as built)
 GMS_ROLLOUT_HIT_OUTSIDE, GMS_ROLLOUT_HIT_RANGE, GMS_ROLLOUT_HIT_BLOCKED, GMS_ROLLOUT_START_BLOCKED = 1, 2, 4, 8      # gms_rollout_rec.flags
+ROUTE_DTYPE = np.dtype([(n, {C.c_uint16: "<u2", C.c_uint32: "<u4", C.c_int32: "<i4"}[t]) for n, t in GmsRouteRec._fields_])     # gms_route_rec
+assert ROUTE_DTYPE.itemsize == C.sizeof(GmsRouteRec) == 32 and C.sizeof(GmsRoute) == 24
+GMS_ROUTE_MAX_P, GMS_ROUTE_MAX_CELLS, GMS_ROUTE_MAX_LOOK = 65536, 16384, 4096
+GMS_ROUTE_NO_PATH, GMS_ROUTE_BROKEN, GMS_ROUTE_CELLS_CUT, GMS_ROUTE_WAYPOINTS_CUT, GMS_ROUTE_MISMATCH = 1, 2, 4, 8, 16      # gms_route_rec.flags
 WARP_STATS_DTYPE = np.dtype([("pair", "<i8", (3, 3)), ("n_outside", "<i8")])     # gms_warp_stats
 assert WARP_STATS_DTYPE.itemsize == C.sizeof(GmsWarpStats) == 80 and C.sizeof(GmsWarp) == 64
 GMS_WARP_COMPARE, GMS_WARP_REPLACE, GMS_WARP_ADD, GMS_WARP_FILL = 0, 1, 2, 3                     # gms_warp.op
@@ -491,6 +509,12 @@ def load() -> C.CDLL:
     sig("gms_slam_rollout_dev", C.c_int, vp, i32, rop, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp)
     sig("gms_pf_rollout", C.c_int, vp, rop, vp, i32, i32, vp, i32, vp)
     sig("gms_pf_rollout_dev", C.c_int, vp, rop, vp, i32, i32, vp, i32, vp)
+    rtp = C.POINTER(GmsRoute)
+    sig("gms_route_check", C.c_int, rtp)
+    sig("gms_map_route", C.c_int, vp, i32, rtp, vp, i32, vp, vp, vp, vp, vp)
+    sig("gms_map_route_dev", C.c_int, vp, i32, rtp, vp, i32, vp, vp, vp, vp, vp)
+    sig("gms_slam_route", C.c_int, vp, i32, rtp, vp, i32, vp, vp, vp, vp, vp, vp)
+    sig("gms_slam_route_dev", C.c_int, vp, i32, rtp, vp, i32, vp, vp, vp, vp, vp, vp)
     wp = C.POINTER(GmsWarp)
     sig("gms_warp_pose", C.c_int, wp, f64, f64, f64)
     sig("gms_warp_check", C.c_int, wp)

@@ -134,6 +134,9 @@ struct gms_map {
     uint32_t *h_reach_ctl;        // pinned: the first 8 words of it, read back once per batch of rounds
     int32_t reach_rounds;         // gms_map_reach_stats: rounds launched for the last field
     int64_t reach_tile_runs;      // ... and tile relaxations that ran
+    // routes (gms_route.hip): the descended paths of a request that gave no `cells`, [P][max_cells][2]; grows and never shrinks
+    int32_t *d_route_path;
+    int64_t route_cap;            // cells it holds
     // frontier regions (gms_frontier.hip); allocated by the first request, the region table grows and never shrinks
     uint32_t *d_front_plane;      // [2][H][gms_plane_wpr] the frontier plane, and the plane of the regions' roots (label == own index)
     uint32_t *d_front_nf;         // [H][gms_plane_wpr] a gms_slam's: the shown particle's second plane (its first: d_clear_scratch)

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
 __all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
-           "cells_of_poses", "descend", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance", "warp_agreement", "map_as_scan"]
+           "cells_of_poses", "descend", "route_points", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance", "warp_agreement", "map_as_scan"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -359,13 +359,13 @@ def clearance_metres(d2, resolution: float) -> np.ndarray:
     return out
 
 
-def _reach_seeds(seeds) -> np.ndarray:
-    """seeds as the int32 [K][2] (x, y) array the library takes"""
+def _reach_seeds(seeds, who: str = "reach", what: str = "seeds") -> np.ndarray:
+    """seeds (route: starts) as the int32 [K][2] (x, y) array the library takes"""
     a = np.ascontiguousarray(seeds, dtype=np.int32)
     if a.ndim == 1 and a.size == 2:
         a = a.reshape(1, 2)
     if a.ndim != 2 or a.shape[1] != 2:
-        raise ValueError(f"reach: seeds must be [K][2] (x, y) cells, not {a.shape}")
+        raise ValueError(f"{who}: {what} must be [K][2] (x, y) cells, not {a.shape}")
     return a
 
 
@@ -508,13 +508,13 @@ def map_as_scan(log, position, resolution: float, max_beams: int = 4096) -> np.n
     return b
 
 
-def _frontier_cost(cost, W: int, H: int):
-    """a whole-map cost-to-go field (what reach() returns for the full rectangle) as the contiguous uint16 [H][W] the library takes"""
+def _frontier_cost(cost, W: int, H: int, who: str = "frontiers", what: str = "cost", kind: str = "cost-to-go"):
+    """a whole-map field (what reach() or clearance() returns for the full rectangle) as the contiguous uint16 [H][W] the library takes"""
     if cost is None:
         return None
     a = np.asarray(cost)
     if a.shape != (H, W) or a.dtype != np.uint16:
-        raise ValueError(f"frontiers: cost must be the whole map's uint16 [{H}][{W}] cost-to-go field, not {a.dtype} {a.shape}")
+        raise ValueError(f"{who}: {what} must be the whole map's uint16 [{H}][{W}] {kind} field, not {a.dtype} {a.shape}")
     return np.ascontiguousarray(a)
 
 
@@ -592,6 +592,15 @@ def descend(field, start) -> list:
             raise ValueError(f"descend: no predecessor at ({x}, {y}): not a whole-map cost-to-go field")
         path.append((x, y))
     return path
+
+
+def route_points(waypoints, n: int, position, resolution: float) -> np.ndarray:
+    """The world coordinates of ONE route's waypoints (GridMap.route's waypoints [max_waypoints][2] of one start and its record's
+    n_waypoints; a cell list and n_cells do as well): the cell centres, position + (cell + 0.5) * resolution in double with the map's
+    float position and resolution widened, float64 [n][2] = (x, y)."""
+    w = np.asarray(waypoints).reshape(-1, 2)[:int(n)].astype(np.float64)
+    res = np.float64(np.float32(resolution))
+    return np.stack([np.float64(np.float32(position[0])) + (w[:, 0] + 0.5) * res, np.float64(np.float32(position[1])) + (w[:, 1] + 0.5) * res], axis=-1)
 
 
 class _Source:
@@ -681,6 +690,36 @@ def _query_rollout(src: _Source, poses, arcs, points, max_range: int, inflate: i
     rec = np.empty((1 if p is None else len(p), a.shape[0]), dtype=_lib.ROLLOUT_DTYPE)
     return (rec,) + src.host("rollout", C.byref(r), None if p is None else ptr(p), 0 if p is None else len(p), ptr(a), a.shape[0], a.shape[1],
                              ptr(f) if len(f) else None, len(f), None if cl is None else ptr(cl), None if co is None else ptr(co), ptr(rec))
+
+
+def _query_route(src: _Source, field, starts, look: int, inflate: int, not_free: bool, max_cells: int, max_waypoints: int, clear, cells, dev=None) -> tuple:
+    """starts None (a particle's map alone): the shown particle's own cell.  dev = (out, waypoints, shown_out), torch device tensors
+    (shown_out or None): the device form -- field, starts, clear and cells (or None) then torch device tensors too"""
+    r = _lib.GmsRoute(int(max_cells), int(max_waypoints), int(look), int(inflate), _obstacles(not_free), src.filter)
+    check(load().gms_route_check(C.byref(r)))
+    if dev is not None:
+        out, waypoints, shown_out = dev
+        sp = _device_ptr("route", "starts", starts, itemsize=4, multiple=2, optional=src.shows)
+        P = 0 if sp is None else starts.numel() // 2
+        n = max(P, 1)
+        src.dev("route", C.byref(r), sp, P, _device_ptr("route", "field", field, 2 * src.W * src.H, itemsize=2),
+                _device_ptr("route", "clear", clear, 2 * src.W * src.H, itemsize=2, optional=True),
+                _device_ptr("route", "out", out, _lib.ROUTE_DTYPE.itemsize * n), _device_ptr("route", "waypoints", waypoints, 8 * n * r.max_waypoints, itemsize=4),
+                _device_ptr("route", "cells", cells, 8 * n * r.max_cells, itemsize=4, optional=True), shown_out=shown_out)
+        return (out, waypoints) + ((cells,) if cells is not None else ()) + ((shown_out,) if src.shows else ())
+    if starts is None and not src.shows:
+        raise ValueError("route: starts are required (a particle's map alone has a cell of its own)")
+    sd = None if starts is None else _reach_seeds(starts, "route", "starts")
+    n = 1 if sd is None else len(sd)
+    if field is None:
+        raise ValueError("route: field, the whole map's cost-to-go field, is required")
+    co, cl = _frontier_cost(field, src.W, src.H, "route", "field"), _frontier_cost(clear, src.W, src.H, "route", "clear", "clearance")
+    rec = np.zeros(n, dtype=_lib.ROUTE_DTYPE)
+    wps = np.zeros((n, r.max_waypoints, 2), dtype=np.int32)
+    cel = np.zeros((n, r.max_cells, 2), dtype=np.int32) if cells else None
+    tail = src.host("route", C.byref(r), None if sd is None else ptr(sd), 0 if sd is None else n, ptr(co), None if cl is None else ptr(cl), ptr(rec), ptr(wps),
+                    None if cel is None else ptr(cel))
+    return (rec, wps) + ((cel,) if cells else ()) + tail
 
 
 def _query_locate(src: _Source, offsets, rect, tol: int, not_free: bool, min_score: int, cap: int, free_only: bool, full: bool, out, n_out,
@@ -914,6 +953,22 @@ class GridMap:
         """rollout() with device pointers (arcs 16-byte aligned); clear / cost: torch device uint16-sized tensors [H][W] or None; out: a
         contiguous torch device tensor of P * K * 32 bytes, written on the handle's stream"""
         return _query_rollout(self._src(mi), (dev_poses, P), (dev_arcs, K, T), (dev_points, F), max_range, inflate, not_free, clear, cost, out, None)[0]
+
+    def route(self, field, starts, *, look: int = 64, inflate: int = 0, not_free: bool = True, max_cells: int = 4096, max_waypoints: int = 64, clear=None,
+              cells: bool = False, mi: int = 0):
+        """Routes (gridmapslam.h "routes") from each of the start cells [P][2] over field, a whole-map cost-to-go field of reach() for the
+        same inflate / not_free: the cheapest 8-connected path down to a seed -- descend()'s cells -- pulled taut by line of sight over
+        at most `look` path cells through what reach() blocks.  clear: a whole-map field of clearance(), or None.  Returns (records
+        [P] of ROUTE_DTYPE: n_cells, n_waypoints, start_cost, end_cost, min_d2, flags, min_d2_at, end_x, end_y, pad; waypoints int32
+        [P][max_waypoints][2], zero behind n_waypoints) and with cells=True the cell lists int32 [P][max_cells][2] as well;
+        route_points() turns one route into world coordinates."""
+        return _query_route(self._src(mi), field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells)
+
+    def route_dev(self, field, starts, out, waypoints, *, look: int = 64, inflate: int = 0, not_free: bool = True, max_cells: int = 4096,
+                  max_waypoints: int = 64, clear=None, cells=None, mi: int = 0):
+        """route() on torch device tensors, on the handle's stream: field / clear uint16-sized [H][W], starts int32 [P][2], out P * 32
+        bytes, waypoints int32 [P][max_waypoints][2], cells int32 [P][max_cells][2] or None; entries behind the counts are not written"""
+        return _query_route(self._src(mi), field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells, (out, waypoints, None))
 
     def locate(self, offsets, rect=None, tol: int = 1, not_free: bool = False, min_score: int = 1, cap: int = 64, free_only: bool = True,
                mi: int = 0, full: bool = False):
@@ -1867,6 +1922,10 @@ class _SlamHandle:
         """gms_slam_rollout[_dev]: (records, shown); poses None: the shown particle's own pose"""
         return _query_rollout(self._src("rollout", which, filter), poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
 
+    def _route(self, which, filter: int, field, starts, look: int, inflate: int, not_free: bool, max_cells: int, max_waypoints: int, clear, cells, dev):
+        """gms_slam_route[_dev]: (records, waypoints[, cells], shown); starts None: the shown particle's own cell"""
+        return _query_route(self._src("route", which, filter), field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells, dev)
+
     def _warp(self, which, filter: int, dst, pose, c, s, op, rect, clamp: float, mi: int, stats, stats_out, shown_out, dev: bool):
         """gms_slam_warp[_dev]: (stats, shown)"""
         w = _warp_request(dst.W, dst.H, pose, c, s, op, rect, clamp)
@@ -2110,6 +2169,18 @@ class SLAMParticleMaps(_SlamHandle):
         """rollout() on the device: arcs = (device address, K, T), points = (device address, F) or None, poses = (device address, P) or
         None, clear / cost / out / shown_out torch device tensors; (out, shown_out), nothing is synchronised"""
         return self._rollout(which, 0, poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
+
+    def route(self, field, starts=None, which="strongest", *, look: int = 64, inflate: int = 0, not_free: bool = True, max_cells: int = 4096,
+              max_waypoints: int = 64, clear=None, cells: bool = False):
+        """Routes through particle `which`'s OWN map over that particle's field (GridMap.route's values): (records, waypoints[, cells],
+        shown).  which = a particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first
+        update).  starts=None: ONE start, the shown particle's own pose cell, read on the device."""
+        return self._route(which, 0, field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells, None)
+
+    def route_dev(self, field, out, waypoints, starts=None, which="strongest", *, look: int = 64, inflate: int = 0, not_free: bool = True,
+                  max_cells: int = 4096, max_waypoints: int = 64, clear=None, cells=None, shown_out=None):
+        """route() on torch device tensors (GridMap.route_dev's): (out, waypoints[, cells], shown_out), nothing is synchronised"""
+        return self._route(which, 0, field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells, (out, waypoints, shown_out))
 
     def warp_into(self, dst: GridMap, which="strongest", pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0, mi: int = 0,
                   stats: bool = True):
@@ -2357,6 +2428,18 @@ class SLAMParticleMapsBatch(_SlamHandle):
                     not_free: bool = True, clear=None, cost=None, shown_out=None):
         """SLAMParticleMaps.rollout_dev for filter `filter`"""
         return self._rollout(self._local(filter, which), filter, poses, arcs, points, max_range, inflate, not_free, clear, cost, out, shown_out)
+
+    def route(self, field, starts=None, which="strongest", filter: int = 0, *, look: int = 64, inflate: int = 0, not_free: bool = True,
+              max_cells: int = 4096, max_waypoints: int = 64, clear=None, cells: bool = False):
+        """SLAMParticleMaps.route for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is
+        the handle-wide slot filter * num_particles + k through whose map the routes were taken, as view() reports it"""
+        return self._route(self._local(filter, which), filter, field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells, None)
+
+    def route_dev(self, field, out, waypoints, starts=None, which="strongest", filter: int = 0, *, look: int = 64, inflate: int = 0,
+                  not_free: bool = True, max_cells: int = 4096, max_waypoints: int = 64, clear=None, cells=None, shown_out=None):
+        """SLAMParticleMaps.route_dev for filter `filter`"""
+        return self._route(self._local(filter, which), filter, field, starts, look, inflate, not_free, max_cells, max_waypoints, clear, cells,
+                           (out, waypoints, shown_out))
 
     def warp_into(self, dst: GridMap, which="strongest", filter: int = 0, pose=None, *, c=None, s=None, op="compare", rect=None, clamp: float = 0.0,
                   mi: int = 0, stats: bool = True):

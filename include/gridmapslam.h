@@ -1364,6 +1364,108 @@ int gms_pf_rollout(gms_pf *pf, const gms_rollout *r, const gms_rollout_step *arc
 int gms_pf_rollout_dev(gms_pf *pf, const gms_rollout *r, const gms_rollout_step *dev_arcs, int32_t K, int32_t T, const float *dev_points, int32_t F,
                        gms_rollout_risk *dev_out);
 
+/* ---- routes: which way to drive, as a handful of straight legs ---------------------------------------------------------------------
+ * The link between a cost-to-go field and the rollouts: for P start cells over a whole-map cost-to-go field, the cheapest 8-connected
+ * path down to a seed, and that path pulled taut to waypoints by line of sight through the blocked plane.  This library's own
+ * definition (the reference has no such method); all of it is integer arithmetic and every output is unique.
+ *
+ * INPUTS         cost [H][W]: a WHOLE-MAP cost-to-go field, what gms_map_reach returns for the full rectangle; required.
+ *                clear [H][W]: a WHOLE-MAP clearance field, what gms_map_clearance returns for the full rectangle; may be NULL.
+ *                starts [P][2]: int32_t (x, y) cells, 1 <= P <= GMS_ROUTE_MAX_P.
+ *                gms_route {max_cells, max_waypoints, look, inflate, mode, filter}: 1 <= max_cells <= GMS_ROUTE_MAX_CELLS (a descent
+ *                never has more than 0xFFFE / GMS_REACH_AXIS + 1 = 13107 cells), 1 <= max_waypoints <= max_cells, 1 <= look <=
+ *                GMS_ROUTE_MAX_LOOK, inflate and mode as in gms_reach, filter as in the other requests.
+ * BLOCKED        exactly the cost-to-go fields' predicate for `mode` and `inflate`.
+ * THE DESCENT    With FAR = GMS_REACH_FAR: a start off the map, or with cost == FAR, has no path: n_cells = 0, n_waypoints = 0 and the
+ *                flag GMS_ROUTE_NO_PATH.  Otherwise path[0] is the start cell, and while the current cell's cost is not 0 the next
+ *                cell is the FIRST neighbour n in the order E, N, W, S, NE, NW, SW, SE (north = y + 1) for which all of these hold:
+ *                n is on the map;  cost[n] != FAR;  cost[n] + step == cost[current], step GMS_REACH_AXIS along an axis and
+ *                GMS_REACH_DIAG diagonally, formed in 32 bits;  for a diagonal, both cells it squeezes between -- (n.x, current.y)
+ *                and (current.x, n.y) -- are on the map and not FAR.  If no neighbour qualifies the descent stops there with
+ *                GMS_ROUTE_BROKEN: the field is no cost-to-go field; this is no error of the call.  If a next cell exists but the
+ *                path already holds max_cells cells, it stays at those with GMS_ROUTE_CELLS_CUT.  The cost falls by at least 5 per
+ *                step, so the descent ends whatever the field holds; nothing but the meaning of the result depends on the field
+ *                being consistent with the map.
+ * VISIBLE(a, b)  for cells a, b on the map with dx = b.x - a.x, dy = b.y - a.y: every cell (x, y) of the bounding box of a and b with
+ *                    2 * |(x - a.x) * dy - (y - a.y) * dx| <= |dx| + |dy|
+ *                is not BLOCKED.  This is the closed supercover of the segment between the two cell centres: a cell the segment only
+ *                touches at a corner counts, a and b themselves count.  So a line of sight never passes between two diagonally
+ *                adjacent blocked cells, and it agrees with the cost-to-go fields' "no corner cutting": a legal diagonal step is
+ *                VISIBLE, an illegal one is not.  Two cells of one path that are k <= look indices apart differ by at most k <=
+ *                4096 = 2^12 per axis, so both products are at most 2^24 and twice their difference at most 2^26: 32 bits hold them.
+ * PULLING        w[0] = path[0], i = 0.  While i < n_cells - 1:  if max_waypoints waypoints are written already, stop with
+ *                GMS_ROUTE_WAYPOINTS_CUT (in front of the search);  j = the LARGEST index in (i, min(i + look, n_cells - 1)] with
+ *                VISIBLE(path[i], path[j]);  if there is none, j = i + 1 and GMS_ROUTE_MISMATCH is set -- the field was made for
+ *                another mode or inflate, or for another map;  append path[j];  i = j.  Without a cut the last waypoint is the
+ *                path's last cell.  look = 1 returns the path itself.
+ * THE RECORD     per start one gms_route_rec, out [P]:
+ *                  n_cells, n_waypoints   the cells of the descended path and the waypoints written.
+ *                  start_cost  cost under the start cell; FAR for a start off the map.
+ *                  end_cost    cost under the path's last cell: 0 when a seed was reached; FAR with NO_PATH.
+ *                  min_d2, min_d2_at   the minimum of clear over the path's cells and the smallest path index where it is taken;
+ *                              GMS_CLEAR_FAR and 0 without a field or without a path.
+ *                  flags       the GMS_ROUTE_* flags above.
+ *                  end_x, end_y   the path's last cell; the start cell with NO_PATH.
+ * OUTPUTS        out [P];  waypoints [P][max_waypoints][2] int32_t (x, y);  cells [P][max_cells][2] int32_t, may be NULL.  Entries
+ *                behind n_waypoints and n_cells are not written: they keep what the caller's buffer held.
+ *
+ * "Sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment", "changes no later result of its
+ * handle" and the argument checks before anything is enqueued (GMS_ERR_INVALID, nothing touched) are the casts' rules.
+ *
+ * How: the blocked plane is the cost-to-go fields' (gms_map_cast_plane_builds does not move for a current plane).  One wavefront per
+ * start.  The descent is a chain of dependent loads, one round trip per step: nine lanes load the 3 x 3 block around the current cell
+ * -- lane k < 8 the k-th neighbour in the order above, lane 8 the cell itself, off the map reads as FAR --, the side cells of a diagonal
+ * come from the axis lanes by cross-lane moves, and a ballot's lowest bit is the next cell; the cells are kept one per lane and
+ * stored 64 at a time.  The path lives in `cells`, or without it in a scratch buffer of the handle that only grows (P * max_cells * 8
+ * bytes).  The clearance minimum is one pass over the path, 64 cells at a time.  The pull gives every lane one candidate j, 64 per
+ * pass from the far end of the window down; a lane walks its supercover along the major axis from path[i] (at most three cells per
+ * column, no division) and leaves at its first blocked cell; a ballot's lowest bit is the largest visible j and ends the passes. */
+#define GMS_ROUTE_MAX_P 65536
+#define GMS_ROUTE_MAX_CELLS 16384
+#define GMS_ROUTE_MAX_LOOK 4096
+#define GMS_ROUTE_NO_PATH 1u                                   /* gms_route_rec.flags */
+#define GMS_ROUTE_BROKEN 2u
+#define GMS_ROUTE_CELLS_CUT 4u
+#define GMS_ROUTE_WAYPOINTS_CUT 8u
+#define GMS_ROUTE_MISMATCH 16u
+typedef struct gms_route {          /* 24 bytes */
+    int32_t max_cells;              /* 1 .. GMS_ROUTE_MAX_CELLS */
+    int32_t max_waypoints;          /* 1 .. max_cells */
+    int32_t look;                   /* path indices a line of sight may skip, 1 .. GMS_ROUTE_MAX_LOOK */
+    int32_t inflate;                /* cells, 0 .. 255 */
+    int32_t mode;                   /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE */
+    int32_t filter;                 /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+} gms_route;
+typedef struct gms_route_rec {      /* 32 bytes */
+    uint32_t n_cells;               /*  0 */
+    uint32_t n_waypoints;           /*  4 */
+    uint16_t start_cost;            /*  8 */
+    uint16_t end_cost;              /* 10 */
+    uint16_t min_d2;                /* 12 */
+    uint16_t flags;                 /* 14 */
+    uint32_t min_d2_at;             /* 16 */
+    int32_t end_x, end_y;           /* 20, 24 */
+    uint32_t pad;                   /* 28: always 0 */
+} gms_route_rec;
+/* Pure host code: the ranges of max_cells, max_waypoints, look, inflate and mode above. */
+int gms_route_check(const gms_route *r);
+/* Map mi of a shared or batched map.  The host form stages its inputs (both fields too) and the caller's waypoints and cells
+ * through the views' buffer -- so what lies behind the counts comes back as it went --, reads everything back and synchronises
+ * once; _dev takes device pointers (out 16-byte aligned, waypoints and cells 8-byte, starts 4-byte, the fields 2-byte), runs on the
+ * handle's stream and synchronises nothing (but where the path scratch has to grow: then it waits for that stream first). */
+int gms_map_route(gms_map *m, int32_t mi, const gms_route *r, const int32_t *starts, int32_t P, const uint16_t *cost, const uint16_t *clear,
+                  gms_route_rec *out, int32_t *waypoints, int32_t *cells);
+int gms_map_route_dev(gms_map *m, int32_t mi, const gms_route *r, const int32_t *dev_starts, int32_t P, const uint16_t *dev_cost, const uint16_t *dev_clear,
+                      gms_route_rec *dev_out, int32_t *dev_waypoints, int32_t *dev_cells);
+/* The per-particle filter: the routes through the map of the shown particle, over that particle's field.  `which`,
+ * GMS_VIEW_STRONGEST, r->filter, *shown (may be NULL; _dev: a device int32_t *) and the GMS_ERR_STATE cases are gms_slam_rollout's.
+ * Here only, P == 0 with starts NULL means: ONE start, the SHOWN particle's own pose cell, read on the device (gms_slam_reach's seed
+ * idiom); out is then [1]. */
+int gms_slam_route(gms_slam *s, int32_t which, const gms_route *r, const int32_t *starts, int32_t P, const uint16_t *cost, const uint16_t *clear,
+                   gms_route_rec *out, int32_t *waypoints, int32_t *cells, int32_t *shown);
+int gms_slam_route_dev(gms_slam *s, int32_t which, const gms_route *r, const int32_t *dev_starts, int32_t P, const uint16_t *dev_cost, const uint16_t *dev_clear,
+                       gms_route_rec *dev_out, int32_t *dev_waypoints, int32_t *dev_cells, int32_t *dev_shown);
+
 /* ---- map warps: one map read through a rigid transform, compared with another or merged into it -------------------------------------
  * Every map is fixed to the frame gms_params gave it; gms_map_copy and gms_map_combine need equal grids.  A warp reads the logData of a
  * SOURCE map through a pose and compares it with, copies it into, adds it to or fills it into a rectangle of a DESTINATION map of any

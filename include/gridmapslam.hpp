@@ -189,6 +189,18 @@ public:
                               (int32_t)(points.size() / 2), clear, cost, out.data()));
         return out;
     }
+    /** Routes (gridmapslam.h "routes") from every start cell -- starts = x0, y0, x1, y1, ... -- in map mi over cost, a whole-map
+     *  cost-to-go field for req's inflate and mode; clear a whole-map clearance field or null.  One record per start; waypoints becomes
+     *  [starts][req.max_waypoints][2] and, where wanted, *cells [starts][req.max_cells][2], both zero behind a record's counts. */
+    std::vector<gms_route_rec> route(const std::vector<int32_t> &starts, const gms_route &req, const uint16_t *cost, std::vector<int32_t> &waypoints,
+                                     const uint16_t *clear = nullptr, std::vector<int32_t> *cells = nullptr, int mi = 0) {
+        const size_t n = starts.size() / 2;
+        std::vector<gms_route_rec> out(n);
+        waypoints.assign(n * (size_t)(req.max_waypoints > 0 ? req.max_waypoints : 0) * 2, 0);
+        if (cells) cells->assign(n * (size_t)(req.max_cells > 0 ? req.max_cells : 0) * 2, 0);
+        check(gms_map_route(h_, mi, &req, starts.data(), (int32_t)n, cost, clear, out.data(), waypoints.data(), cells ? cells->data() : nullptr));
+        return out;
+    }
     /** The clearance field (gridmapslam.h "clearance fields") of map mi: per cell of c's rectangle the squared distance in cells to the
      *  nearest obstacle cell of the whole map, GMS_CLEAR_FAR beyond c.max_radius; [h][w] row-major */
     std::vector<uint16_t> clearance(const gms_clearance &c, int mi = 0) {
@@ -641,6 +653,21 @@ public:
         int32_t picked = 0;
         check(gms_slam_rollout(h_, which, &req, poses.empty() ? nullptr : p.data(), (int32_t)poses.size(), arcs.data(), K, T,
                                points.empty() ? nullptr : points.data(), (int32_t)(points.size() / 2), clear, cost, out.data(), &picked));
+        if (shown) *shown = picked;
+        return out;
+    }
+    /** Routes through particle `which`'s own map over that particle's field (GridMap::route's values); no starts: ONE start, the shown
+     *  particle's own pose cell, read on the device.  *shown (may be null) receives the particle through whose map they were taken */
+    std::vector<gms_route_rec> route(const std::vector<int32_t> &starts, const gms_route &req, const uint16_t *cost, std::vector<int32_t> &waypoints,
+                                     const uint16_t *clear = nullptr, std::vector<int32_t> *cells = nullptr, int which = GMS_VIEW_STRONGEST,
+                                     int *shown = nullptr) {
+        const size_t n = starts.empty() ? 1 : starts.size() / 2;
+        std::vector<gms_route_rec> out(n);
+        waypoints.assign(n * (size_t)(req.max_waypoints > 0 ? req.max_waypoints : 0) * 2, 0);
+        if (cells) cells->assign(n * (size_t)(req.max_cells > 0 ? req.max_cells : 0) * 2, 0);
+        int32_t picked = 0;
+        check(gms_slam_route(h_, which, &req, starts.empty() ? nullptr : starts.data(), (int32_t)(starts.size() / 2), cost, clear, out.data(), waypoints.data(),
+                             cells ? cells->data() : nullptr, &picked));
         if (shown) *shown = picked;
         return out;
     }
