@@ -80,8 +80,7 @@ int gms_align_check_for(const gms_align_params *p, const char *who) {
 // lik: map 0's field of the launch, the maps lik_stride apart; poses and records [maps][P]
 static int align_launch(gms_map *m, const double *lik, int64_t lik_stride, int32_t maps, const gms_beam *d_beams, int32_t B, int32_t beam_stride,
                         const float *d_in, float *d_out, float *d_cs, gms_align_record *d_rec, int32_t P, const gms_align_params *prm) {
-    int rc = gms_kernel_lds<k_align>(GMS_MAX_BEAMS * 16);
-    if (rc) return rc;
+    HIPCHK(gms_kernel_lds<k_align>(m->device, GMS_MAX_BEAMS * 16));
     hipLaunchKernelGGL(k_align, dim3((unsigned)((P + ALIGN_WAVES - 1) / ALIGN_WAVES), (unsigned)maps), dim3(ALIGN_NT), (size_t)B * 16, m->stream, m->gd, lik,
                        lik_stride, d_beams, B, beam_stride, d_in, d_out, d_cs, d_rec, P, *prm);
     HIPCHK(hipGetLastError());

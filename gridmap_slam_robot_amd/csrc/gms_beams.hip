@@ -143,8 +143,7 @@ static int pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t 
     const int32_t wpr = gms_plane_wpr(m);
     const int64_t plane_stride = (int64_t)m->gd.H * wpr;
     const int64_t lds_words = m->cast_walk_mem ? 0 : std::min<int64_t>(BEAM_LDS_CAP / 4, plane_stride);
-    rc = gms_kernel_lds<k_beam_score>(BEAM_LDS_CAP);
-    if (rc) return rc;
+    HIPCHK(gms_kernel_lds<k_beam_score>(m->device, BEAM_LDS_CAP));
     hipLaunchKernelGGL(k_beam_score, dim3((unsigned)pf->n, (unsigned)pf->n_maps), dim3(BEAM_NT), (size_t)lds_words * 4, m->stream, m->gd, plane, wpr,
                        plane_stride, d_beams, B, beam_stride, pf->d_pose, pf->d_cs, pf->n, behind, ahead, bm.d_tab, pf->d_w, pf->d_logw,
                        residuals ? st.at(p_res, residuals) : nullptr, (int32_t)lds_words);

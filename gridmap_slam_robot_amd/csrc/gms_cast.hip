@@ -131,8 +131,7 @@ static int cast_launch(gms_map *m, int32_t mi, bool per_map, const float *d_pose
     const int64_t plane_stride = (int64_t)m->gd.H * wpr;
     const int64_t lds_words = m->cast_walk_mem ? 0 : std::min<int64_t>(CAST_LDS_CAP / 4, plane_stride);
     const int32_t bpp = (B + CAST_NT - 1) / CAST_NT;
-    rc = gms_kernel_lds<k_cast_map>(CAST_LDS_CAP);
-    if (rc) return rc;
+    HIPCHK(gms_kernel_lds<k_cast_map>(m->device, CAST_LDS_CAP));
     hipLaunchKernelGGL(k_cast_map, dim3((unsigned)((int64_t)P * bpp)), dim3(CAST_NT), (size_t)lds_words * 4, m->stream, m->gd,
                        plane + (size_t)mi * (size_t)plane_stride, wpr, plane_stride, per_map ? 1 : 0, d_probes, B, bpp, d_poses, pose_stride,
                        d_out, (int32_t)lds_words);

@@ -140,8 +140,7 @@ static inline int32_t clear_tile_rows(int32_t R, int32_t h) { return std::min(h,
 int gms_clear_launch(gms_map *m, const uint32_t *d_plane, const gms_clearance *c, uint16_t *d_out) {
     const int32_t R = c->max_radius, TY = clear_tile_rows(R, c->h), rows_cap = std::min(TY + 2 * R, m->gd.H);
     const size_t lds = (size_t)rows_cap * CLR_ROW_BYTES;
-    int rc = gms_kernel_lds<k_clear_field>(CLR_LDS_CAP);
-    if (rc) return rc;
+    HIPCHK(gms_kernel_lds<k_clear_field>(m->device, CLR_LDS_CAP));
     const int32_t words = ((c->x0 + c->w - 1) >> 5) - (c->x0 >> 5) + 1, bands = (c->h + TY - 1) / TY;
     if (bands > 65535) return gms_fail(GMS_ERR_INVALID, "gms_clearance: a rectangle of %d rows exceeds one launch", c->h);
     hipLaunchKernelGGL(k_clear_field, dim3((unsigned)words, (unsigned)bands), dim3(CLR_NT), lds, m->stream, d_plane, gms_plane_wpr(m), m->gd.H, c->x0, c->y0,

@@ -216,28 +216,18 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
     if (smem < smem_pre) smem = smem_pre;
     // a deferred apply pass rides along: the ray cast then raises the OTHER box half (cleared by the previous likelihood launch)
     // while the pass reads the pending scan's half; afterwards that other half is the current one (gms_apply_done)
-    uint32_t n_apply = 0;
-    if (m->apply_pending) {
-        const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
-        n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS_RIDING ? all : GMS_APPLY_BLOCKS_RIDING);
-    }
-    int32_t *pend = m->d_bbox + (size_t)m->bbox_cur * 4;
-    int32_t *bb = n_apply ? m->d_bbox + (size_t)(1 - m->bbox_cur) * 4 : pend;
-    const bool lognorm = gms_pf_lognorm_now(pf);
-#define NR_LAUNCH(LN)                                                                                                                 \
-    do {                                                                                                                              \
-        if (smem > 48 * 1024)                                                                                                         \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_norm_raycast<LN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL(k_norm_raycast<LN>, dim3(n_ray + n_norm + n_apply), dim3(256), smem, m->stream, d_beams, d_partials,       \
-                           nblk_global_of(pf), B, rc_nw_max(m), n_ray, n_norm, n_near, pf->n, pf->d_w, pf->d_pose, pf->offset,         \
-                           m->d_cnt, bb, d_packed_local,                                                                               \
-                           own ? pf->d_cum : (double *)nullptr, own ? pf->d_chunk_tot : (double *)nullptr, nchunks_of(pf),          \
-                           own ? pf->d_p2 : (double *)nullptr, pf->d_stats, m->d_log, m->d_cnt_pend, pend,                          \
-                           LN ? (const double *)pf->d_logw : (const double *)nullptr, own ? pf->d_res_ticket : (uint32_t *)nullptr,       \
-                           pf->d_res_pre, m->gd);                                                                                       \
-    } while (0)
-    if (lognorm) NR_LAUNCH(true); else NR_LAUNCH(false);
-#undef NR_LAUNCH
+    const uint32_t n_apply = m->apply_pending ? apply_blocks(m, GMS_APPLY_BLOCKS_RIDING) : 0u;
+    int32_t *pend = map_box(m);
+    int32_t *bb = n_apply ? map_box(m, true) : pend;
+    auto launch = [&](auto lognorm) {
+        gms_launch<k_norm_raycast<lognorm()>>(m, dim3(n_ray + n_norm + n_apply), dim3(256), smem, d_beams, d_partials, nblk_global_of(pf), B,
+                                              rc_nw_max(m), n_ray, n_norm, n_near, pf->n, pf->d_w, pf->d_pose, pf->offset, m->d_cnt, bb, d_packed_local,
+                                              own ? pf->d_cum : (double *)nullptr, own ? pf->d_chunk_tot : (double *)nullptr, nchunks_of(pf),
+                                              own ? pf->d_p2 : (double *)nullptr, pf->d_stats, m->d_log, m->d_cnt_pend, pend,
+                                              lognorm() ? (const double *)pf->d_logw : (const double *)nullptr,
+                                              own ? pf->d_res_ticket : (uint32_t *)nullptr, pf->d_res_pre, m->gd);
+    };
+    if (gms_pf_lognorm_now(pf)) launch(gms_c<true>{}); else launch(gms_c<false>{});
     if (n_apply) gms_apply_done(m);
     pf_normalized(pf, own, own);                                      // (resample_prefix_last wrote stats.norm_sum / sq_sum)
 }
@@ -249,14 +239,12 @@ void gms_launch_partials_apply(gms_pf *pf, double *d_partials, bool apply_rides_
     if (!m->apply_pending || apply_rides_later) { gms_launch_pf_partials(pf, d_partials); return; }
     ProfScope ps(m, GMS_K_REDUCE);
     const int64_t nblk = nblk_global_of(pf);
-    const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
-    const uint32_t n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS);
-    int32_t *cur = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4, *idle = m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4;
+    const uint32_t n_apply = apply_blocks(m, GMS_APPLY_BLOCKS);
     PfStatsDev *lognorm_stats = gms_pf_lognorm_now(pf) ? pf->d_stats : (PfStatsDev *)nullptr;
     hipLaunchKernelGGL(k_partials_apply, dim3((uint32_t)nblk + n_apply, pf->n_maps), dim3(256), 0, m->stream,
                        pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose, lognorm_stats, pf->n,
                        pf->pending_nseg, pf->offset, nblk, pf->d_w, pf->d_logw, d_partials, m->d_log, m->d_cnt_pend,
-                       cur, idle, m->gd);
+                       map_box(m), map_box(m, true), m->gd);
     pf_weights_combined(pf);
     gms_apply_done(m);
 }
@@ -271,37 +259,26 @@ void gms_launch_lik_resample(gms_pf *pf, double fraction) {
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
     const size_t smem_l = gms_likelihood_lds_bytes(m->gd.khalf, k != 0);
-    int32_t blocks = tiles_x * tiles_y;
-    const int32_t cap = gms_likelihood_blocks_cap(m, smem_l);
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) & ~7;
+    const int32_t blocks = lik_tile_blocks(m, smem_l, tiles_x, tiles_y);
     const int64_t nch = nchunks_of(pf);
     const size_t smem_r = gms_resample_lds_bytes(nch);
     const size_t smem = smem_l > smem_r ? smem_l : smem_r;
     const uint32_t n_res = (uint32_t)((pf->n + 255) / 256);
-    const int32_t *bb = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4;
     const double *r01_maps = pf->n_maps == 1 ? (const double *)nullptr : pf->d_r01_src;
     int32_t lik_mode = m->lik_lazy ? 2 : 3;                   // the factor table only: likelihoodData follows on demand (gms_ensure_lik)
     if (m->fac_current && m->lik_skip) lik_mode |= 4;         // tiles whose codes this scan does not change are left alone (likelihood_body)
     map_field_built(m, lik_mode);
     const bool split = k != 0 && gms_likelihood_split(m, blocks);              // (likelihood_body, "split")
-#define LR_LAUNCH(KH, SP)                                                                                                 \
-    do {                                                                                                                  \
-        if (smem > 48 * 1024)                                                                                             \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lik_resample<KH, SP>),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                                   \
-        hipLaunchKernelGGL((k_lik_resample<KH, SP>), dim3((uint32_t)blocks + n_res, pf->n_maps), dim3(256), smem, m->stream, pre,     \
-                           (const double *)pf->d_chunk_tot, nch, bb, m->d_tile_state,                                     \
-                           m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4, n_res, lik_mode, (const uint32_t *)m->d_cnt, \
-                           (const double *)m->d_log, tiles_x, tiles_y, m->d_lik, m->d_fac, m->fac_stride, (const double *)m->d_taps, \
-                           (const PackedParticle *)pf->d_global, pf->n_global, (const double *)pf->d_cum, r01_maps, pf->r01_scalar, \
-                           fraction, pf->n, (int32_t)pf->global_raw, pf->offset,                                          \
-                           pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, (const double *)pf->d_p2, nblk_global_of(pf), pf->d_stats, m->gd); \
-    } while (0)
-    if (k == 3) { if (split) LR_LAUNCH(3, 2); else LR_LAUNCH(3, 1); }
-    else if (k == 5) { if (split) LR_LAUNCH(5, 2); else LR_LAUNCH(5, 1); }
-    else LR_LAUNCH(0, 1);
-#undef LR_LAUNCH
+    auto launch = [&](auto kh, auto parts) {
+        gms_launch<k_lik_resample<kh(), parts()>>(m, dim3((uint32_t)blocks + n_res, pf->n_maps), dim3(256), smem, pre, pf->d_chunk_tot, nch, map_box(m),
+                                                  m->d_tile_state, map_box(m, true), n_res, lik_mode, m->d_cnt, m->d_log, tiles_x, tiles_y, m->d_lik,
+                                                  m->d_fac, m->fac_stride, m->d_taps, pf->d_global, pf->n_global, pf->d_cum, r01_maps, pf->r01_scalar,
+                                                  fraction, pf->n, (int32_t)pf->global_raw, pf->offset, pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx,
+                                                  pf->d_p2, nblk_global_of(pf), pf->d_stats, m->gd);
+    };
+    if (k == 3) { if (split) launch(gms_c<3>{}, gms_c<2>{}); else launch(gms_c<3>{}, gms_c<1>{}); }
+    else if (k == 5) { if (split) launch(gms_c<5>{}, gms_c<2>{}); else launch(gms_c<5>{}, gms_c<1>{}); }
+    else launch(gms_c<0>{}, gms_c<1>{});
     pf_prefix_consumed(pf);
 }
 
@@ -312,16 +289,12 @@ void gms_launch_partials_pack_apply(gms_pf *pf, bool apply_rides_later) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_REDUCE);
     const uint32_t n_local = (uint32_t)((pf->n + GMS_BLOCK - 1) / GMS_BLOCK);
-    uint32_t n_apply = 0;
-    if (m->apply_pending && !apply_rides_later) {      // (rides later: beside this scan's ray cast, gms_launch_raycast_norm_chunks)
-        const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
-        n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS);
-    }
-    int32_t *cur = m->d_bbox + (size_t)m->bbox_cur * 4, *idle = m->d_bbox + (size_t)(1 - m->bbox_cur) * 4;
+    // (rides later: beside this scan's ray cast, gms_launch_raycast_norm_chunks)
+    const uint32_t n_apply = m->apply_pending && !apply_rides_later ? apply_blocks(m, GMS_APPLY_BLOCKS) : 0u;
     hipLaunchKernelGGL(k_partials_pack_apply, dim3(n_local + n_apply), dim3(256), 0, m->stream,
                        pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose, pf->n, pf->pending_nseg,
                        n_local, pf->offset, nblk_global_of(pf), pf->d_w, pf->d_logw, pf->d_partials,
-                       pf->d_global_own + pf->offset, m->d_log, m->d_cnt_pend, cur, idle, m->gd);
+                       pf->d_global_own + pf->offset, m->d_log, m->d_cnt_pend, map_box(m), map_box(m, true), m->gd);
     pf_raw_packed(pf);
     if (n_apply) gms_apply_done(m);
 }
@@ -335,21 +308,13 @@ void gms_launch_raycast_norm_chunks(gms_pf *pf, const gms_beam *d_beams, int32_t
     const uint32_t n_chunk = (uint32_t)nblk_global_of(pf);
     const size_t smem = rc_smem(m, RCF_RAYS, n_near);
     // a deferred apply pass rides beside the ray cast, as in gms_launch_norm_raycast
-    uint32_t n_apply = 0;
-    if (raycast && m->apply_pending) {
-        const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
-        n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS_RIDING ? all : GMS_APPLY_BLOCKS_RIDING);
-    }
-    int32_t *pend = m->d_bbox + (size_t)m->bbox_cur * 4;
-    int32_t *bb = n_apply ? m->d_bbox + (size_t)(1 - m->bbox_cur) * 4 : pend;
-    if (smem > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast_norm_chunks), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-    hipLaunchKernelGGL(k_raycast_norm_chunks, dim3(n_ray + n_norm + n_chunk + n_apply), dim3(256), smem, m->stream, d_beams,
-                       pf->d_partials, nblk_global_of(pf), B, rc_nw_max(m), n_ray, n_norm, n_chunk, n_near, pf->n,
-                       pf->d_w, pf->d_pose, pf->offset, pf->d_global_own, pf->n_global, nchunks_of(pf),
-                       pf->d_cum, pf->d_chunk_tot, pf->d_p2, pf->d_stats, m->d_cnt, bb, m->d_log, m->d_cnt_pend,
-                       pend, m->gd);
+    const uint32_t n_apply = raycast && m->apply_pending ? apply_blocks(m, GMS_APPLY_BLOCKS_RIDING) : 0u;
+    int32_t *pend = map_box(m);
+    int32_t *bb = n_apply ? map_box(m, true) : pend;
+    gms_launch<k_raycast_norm_chunks>(m, dim3(n_ray + n_norm + n_chunk + n_apply), dim3(256), smem, d_beams, pf->d_partials, nblk_global_of(pf), B,
+                                      rc_nw_max(m), n_ray, n_norm, n_chunk, n_near, pf->n, pf->d_w, pf->d_pose, pf->offset, pf->d_global_own,
+                                      pf->n_global, nchunks_of(pf), pf->d_cum, pf->d_chunk_tot, pf->d_p2, pf->d_stats, m->d_cnt, bb, m->d_log,
+                                      m->d_cnt_pend, pend, m->gd);
     if (n_apply) gms_apply_done(m);
     pf_normalized_gathered(pf);                       // (sharded: the resample workgroups fold Neff and scan the offsets themselves)
 }

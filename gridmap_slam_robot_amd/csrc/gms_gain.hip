@@ -151,8 +151,7 @@ static int gain_launch(gms_map *m, const uint32_t *d_occ, const uint32_t *d_nf, 
     const int64_t budget = GAIN_LDS_CAP - GAIN_LDS_STATIC;
     if (cap_words * 4 > budget) return gms_fail(GMS_ERR_INTERNAL, "gms_gain: a visited bitmap of %lld bytes", (long long)(cap_words * 4));
     const bool staged = !m->gain_walk_mem && 3 * cap_words * 4 <= budget;
-    int rc = gms_kernel_lds<k_gain>(GAIN_LDS_CAP - GAIN_LDS_STATIC);
-    if (rc) return rc;
+    HIPCHK(gms_kernel_lds<k_gain>(m->device, GAIN_LDS_CAP - GAIN_LDS_STATIC));
     hipLaunchKernelGGL(k_gain, dim3((unsigned)P), dim3(GAIN_NT), (size_t)(staged ? 3 : 1) * (size_t)cap_words * 4, m->stream, m->gd, d_occ, d_nf, wpr, d_probes, B,
                        d_poses, max_range, d_out, (int32_t)cap_words, staged ? 1 : 0);
     HIPCHK(hipGetLastError());

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "gridmapslam.h"
@@ -520,16 +523,45 @@ static inline int gms_request_scan(gms_map *m, const gms_beam *beams, int32_t B,
     *d_beams = m->d_beams; *beam_stride = m->max_beams;
     return GMS_OK;
 }
-// the one opt-in of a kernel to `bytes` of dynamic LDS (past the 64 KiB a launch may ask for without it): set once per kernel and
-// process, in front of its first launch
+// ---- the one launch path of the kernels that take dynamic LDS ----
+// What a launch may ask for without opting in.  The runtime takes 64 KiB unasked on this hardware; 48 KiB, the threshold most launchers
+// already went by, is the conservative choice: an opt-in too many costs one host call per kernel and device, once.
+#define GMS_LDS_FREE ((size_t)48 * 1024)
+// devices whose opt-ins are remembered; a handle on a device beyond them opts in at every launch above GMS_LDS_FREE
+#define GMS_LDS_DEVICES 64
+// The opt-in of Kernel to `bytes` of dynamic LDS on `device` (the handle's, which every entry point has made current: HIP keeps a
+// function, and this attribute, per device).  The high-water mark of what was set is kept per (kernel, device) and the runtime is
+// called only when a launch asks for more: the launchers pass whatever this launch needs, the units with a constant cap pass the cap.
+// Handles may be driven from different threads: the mark is a relaxed atomic -- it orders nothing, it only has to be read and written
+// whole -- and it is raised after the attribute was set, under a lock, so two threads may both set the attribute and can never both skip it
+// or leave the mark above what the runtime holds.  A failed opt-in leaves the mark alone; the launch behind it then fails as well.
 template <auto Kernel>
-static inline int gms_kernel_lds(int bytes) {
-    static bool set = false;
-    if (!set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        set = true;
-    }
-    return GMS_OK;
+static inline hipError_t gms_kernel_lds(int32_t device, size_t bytes) {
+    static std::atomic<size_t> mark[GMS_LDS_DEVICES];          // (0: nothing set, GMS_LDS_FREE holds)
+    static std::mutex raising;
+    if (bytes <= GMS_LDS_FREE) return hipSuccess;
+    const bool known = device >= 0 && device < GMS_LDS_DEVICES;
+    if (known && bytes <= mark[device].load(std::memory_order_relaxed)) return hipSuccess;
+    std::lock_guard<std::mutex> lock(raising);
+    if (known && bytes <= mark[device].load(std::memory_order_relaxed)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && known) mark[device].store(bytes, std::memory_order_relaxed);
+    return e;
+}
+// Kernel on the handle's stream with smem bytes of dynamic LDS, opted in to where that is needed.  Errors surface as the launch's own:
+// the entry point's hipGetLastError reports them
+template <auto Kernel, typename... Args>
+static inline void gms_launch(const gms_map *m, dim3 grid, dim3 block, size_t smem, const Args &...args) {
+    (void)gms_kernel_lds<Kernel>(m->device, smem);
+    hipLaunchKernelGGL(Kernel, grid, block, smem, m->stream, args...);
+}
+// a run-time choice as a type, for the launchers' dispatch to kernel template arguments: `if (k == 3) launch(gms_c<3>{})`, and the
+// generic lambda `[&](auto kh)` names the instantiation k_x<kh()>.  Every launcher lists its combinations itself
+template <auto V>
+using gms_c = std::integral_constant<decltype(V), V>;
+// the box of every map (gms_map::d_bbox: two halves of [n_maps][4]): the half in use, or -- idle -- the other one
+static inline int32_t *map_box(const gms_map *m, bool idle = false) {
+    return m->d_bbox + (size_t)(idle ? 1 - m->bbox_cur : m->bbox_cur) * m->n_maps * 4;
 }
 // host beams [rows][B] (or none: beams NULL) -> dst [rows][pitch], then tab_bytes of tab behind them, as ONE copy out of a slot of ring
 // (gms_host.hip; the ring's slots hold rows * pitch beams + tab_bytes)
@@ -542,6 +574,10 @@ int gms_ring_acquire(StageRing &r, void **out);
 int gms_ring_commit(StageRing &r, hipStream_t stream);
 
 // ---- kernel launchers (gms_map_kernels.hip / gms_pf_kernels.hip) -----------------------------
+// Each enqueues on the handle's stream and returns; the entry point that called it checks hipGetLastError.  Kernels with dynamic LDS
+// go through gms_launch above (the opt-in is nobody else's business); a launcher that picks among instantiations writes the argument
+// list once, in a generic lambda over gms_c tags, and lists the combinations in plain ifs.  The geometry several launchers share is
+// said once: map_box here, apply_blocks / lik_resident / lik_tile_blocks in gms_map_kernels.hip, slam_lik_blocks in gms_slam_kernels.hip.
 
 void gms_launch_raycast(gms_map *m, const gms_beam *d_beams, int32_t B, int32_t beam_stride, const float *d_poses,
                         int32_t pose_stride, bool take_pending_apply = false);

@@ -1410,11 +1410,13 @@ static void rc_launch(gms_map *m, dim3 grid, const gms_beam *d_beams, int32_t B,
                       int32_t cap, int32_t *t_counts, uint32_t n_near = 0) {
     const size_t smem = rc_smem(m, RAYS, n_near);
     grid.x += n_near;                                       // near-field workgroups behind the ray blocks (raycast_near_body)
-    if (smem > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast<TRACE, RAYS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-    hipLaunchKernelGGL((k_raycast<TRACE, RAYS>), grid, dim3(RAYS * 64), smem, m->stream, d_beams, d_poses, single, B,
-                       beam_stride, pose_stride, rc_nw_max(m), n_near, cap, cnt, bbox, t_cells, t_cls, t_counts, m->gd);
+    gms_launch<k_raycast<TRACE, RAYS>>(m, grid, dim3(RAYS * 64), smem, d_beams, d_poses, single, B, beam_stride, pose_stride, rc_nw_max(m),
+                                       n_near, cap, cnt, bbox, t_cells, t_cls, t_counts, m->gd);
+}
+// workgroups of the apply pass per map: one per tile of APPLY_TW x APPLY_TH cells, `cap` at most (they stride over the rest)
+static inline uint32_t apply_blocks(const gms_map *m, int32_t cap) {
+    const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
+    return (uint32_t)(all < cap ? all : cap);
 }
 
 // batched ray casts of more than raycast_tile_min rays in all go through LDS tiles (k_raycast_tile)
@@ -1428,26 +1430,23 @@ void gms_launch_raycast(gms_map *m, const gms_beam *d_beams, int32_t B, int32_t 
     const bool riding = take_pending_apply && tile && m->apply_pending;
     if (!riding) gms_flush_apply(m);
     ProfScope ps(m, GMS_K_RAYCAST);
-    int32_t *bb = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4;
+    int32_t *bb = map_box(m);
     if (tile) {
         // batched maps: throughput-bound; 64 consecutive beams per workgroup, counts accumulated in an LDS tile
-        const size_t smem = RCT_LDS_BYTES;
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         const uint32_t n_ray = (uint32_t)((B + RCT_RAYS - 1) / RCT_RAYS);
         uint32_t n_apply = 0;
         int32_t *next = bb;
         if (riding) {
-            const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
 #ifndef GMS_APPLY_RIDING_TILE
 #define GMS_APPLY_RIDING_TILE 4        // workgroups of four 256-thread slices per map (C5 step, us: 1 / 2 / 3 / 4 / 6 / 8 / 16 / 32: 462 / 427 / 421 / 419 / 422 / 422 / 427 / 427; the pass beside the partials: 431)
 #endif
-            n_apply = (uint32_t)((all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS) + 3) / 4;
+            n_apply = (apply_blocks(m, GMS_APPLY_BLOCKS) + 3) / 4;
             if (n_apply > GMS_APPLY_RIDING_TILE) n_apply = GMS_APPLY_RIDING_TILE;
             if (n_apply < 1) n_apply = 1;
-            next = m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4;
+            next = map_box(m, true);
         }
-        hipLaunchKernelGGL(k_raycast_tile, dim3(n_ray + n_apply, m->n_maps), dim3(RCT_THREADS), smem, m->stream, m->gd,
-                           d_beams, B, beam_stride, d_poses, pose_stride, m->d_cnt, next, n_ray, m->d_log, m->d_cnt_pend, bb);
+        gms_launch<k_raycast_tile>(m, dim3(n_ray + n_apply, m->n_maps), dim3(RCT_THREADS), RCT_LDS_BYTES, m->gd, d_beams, B, beam_stride, d_poses,
+                                   pose_stride, m->d_cnt, next, n_ray, m->d_log, m->d_cnt_pend, bb);
         if (riding) gms_apply_done(m);
     } else if ((int64_t)B * m->n_maps > m->raycast_tile_min)       // (GMS_RAYCAST_TILE=0, or not enough LDS: 16 rays per workgroup, direct atomics)
         rc_launch<false, 16>(m, dim3((B + 15) / 16, m->n_maps), d_beams, B, beam_stride, d_poses, pose_stride, nullptr, m->d_cnt, bb,
@@ -1477,8 +1476,7 @@ void gms_launch_apply_ray(gms_map *m, RayIn ray) {
     RayIn *d_ray = reinterpret_cast<RayIn *>(m->d_beams);
     hipLaunchKernelGGL(k_store_ray, dim3(1), dim3(1), 0, m->stream, d_ray, ray);
     ProfScope ps(m, GMS_K_RAYCAST);
-    rc_launch<false, 4>(m, dim3(1, 1), nullptr, 1, m->max_beams, nullptr, 3, d_ray, m->d_cnt,
-                        m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4, nullptr, nullptr, 0, nullptr);
+    rc_launch<false, 4>(m, dim3(1, 1), nullptr, 1, m->max_beams, nullptr, 3, d_ray, m->d_cnt, map_box(m), nullptr, nullptr, 0, nullptr);
 }
 
 // The paired scan step leaves its counts un-applied (the likelihood pass adds them on the fly) so that the apply pass
@@ -1487,26 +1485,19 @@ void gms_launch_apply_ray(gms_map *m, RayIn ray) {
 // of the box cleared, the box consumed.
 static void apply_launch(gms_map *m) {
     ProfScope ps(m, GMS_K_APPLY);
-    const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
-    dim3 grid(all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS, m->n_maps);
-    int32_t *cur = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4, *idle = m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4;
+    dim3 grid(apply_blocks(m, GMS_APPLY_BLOCKS), m->n_maps);
     // a deferred pass applies the grid that was set aside (gms_defer_apply); the immediate one the grid just cast into
-    hipLaunchKernelGGL(k_apply, grid, dim3(256), 0, m->stream, m->gd, m->d_log, m->apply_pending ? m->d_cnt_pend : m->d_cnt, cur, idle);
+    hipLaunchKernelGGL(k_apply, grid, dim3(256), 0, m->stream, m->gd, m->d_log, m->apply_pending ? m->d_cnt_pend : m->d_cnt, map_box(m),
+                       map_box(m, true));
 }
 // this scan's ray cast beside the previous scan's deferred apply pass (k_raycast_apply); single maps, scans of <= 4096 beams
 void gms_launch_raycast_apply(gms_map *m, const gms_beam *d_beams, int32_t B, int32_t beam_stride, const float *d_poses,
                               int32_t pose_stride) {
     ProfScope ps(m, GMS_K_RAYCAST);
     const uint32_t n_ray = (uint32_t)((B + 3) / 4);
-    const int32_t all = ((m->gd.W + APPLY_TW - 1) / APPLY_TW) * ((m->gd.H + APPLY_TH - 1) / APPLY_TH);
-    const uint32_t n_apply = (uint32_t)(all < GMS_APPLY_BLOCKS ? all : GMS_APPLY_BLOCKS);
-    int32_t *pend = m->d_bbox + (size_t)m->bbox_cur * 4, *next = m->d_bbox + (size_t)(1 - m->bbox_cur) * 4;
-    const uint32_t n_near = rc_near_blocks(m, B);
-    const size_t smem = rc_smem(m, 4, n_near);
-    if (smem > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_raycast_apply), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k_raycast_apply, dim3(n_ray + n_near + n_apply), dim3(256), smem, m->stream, d_beams, d_poses, B, beam_stride,
-                       pose_stride, rc_nw_max(m), n_ray, n_near, m->d_cnt, next, m->d_log, m->d_cnt_pend, pend, m->gd);
+    const uint32_t n_apply = apply_blocks(m, GMS_APPLY_BLOCKS), n_near = rc_near_blocks(m, B);
+    gms_launch<k_raycast_apply>(m, dim3(n_ray + n_near + n_apply), dim3(256), rc_smem(m, 4, n_near), d_beams, d_poses, B, beam_stride, pose_stride,
+                                rc_nw_max(m), n_ray, n_near, m->d_cnt, map_box(m, true), m->d_log, m->d_cnt_pend, map_box(m), m->gd);
     gms_apply_done(m);                      // the box of the scan just cast is the current half now
 }
 void gms_flush_apply(gms_map *m) {
@@ -1528,17 +1519,21 @@ size_t gms_likelihood_lds_bytes(int32_t k, bool coded) {
     if (coded && (k == 3 || k == 5)) return ((RH * ((RW + 7) & ~(size_t)7) + 15) & ~(size_t)15) + RH * (LK_TW + 1) * sizeof(double);
     return (RH * (RW + 1) + RH * (LK_TW + 1) + (2 * (size_t)k + 1)) * sizeof(double);
 }
-int32_t gms_likelihood_blocks_cap(const gms_map *m, size_t smem) {
-    // persistent workgroups: as many as stay resident (LDS per CU and CU count of the map's device, read once at gms_map_create:
-    // 160 KiB and 256 on MI355X; registers allow five)
+// likelihood workgroups of smem bytes that stay resident on the map's device (LDS per CU and CU count, read once at gms_map_create:
+// 160 KiB and 256 on MI355X; registers allow five per CU)
 #ifndef GMS_LIK_WG_PER_CU
 #define GMS_LIK_WG_PER_CU 5
 #endif
-    const int32_t n_maps = m->n_maps;
+static inline int32_t lik_resident(const gms_map *m, size_t smem) {
     int32_t per_cu = (int32_t)((size_t)m->lds_per_cu / (smem + 256));
     if (per_cu > GMS_LIK_WG_PER_CU) per_cu = GMS_LIK_WG_PER_CU;
     if (per_cu < 1) per_cu = 1;
-    const int32_t resident = per_cu * m->n_cus;
+    return per_cu * m->n_cus;
+}
+int32_t gms_likelihood_blocks_cap(const gms_map *m, size_t smem) {
+    // persistent workgroups: as many as stay resident
+    const int32_t n_maps = m->n_maps;
+    const int32_t resident = lik_resident(m, smem);
     if (n_maps <= 4) return resident / n_maps;
     // many maps: two residencies' worth of workgroups over all maps, a quarter of one at most per map.  A map's dirty box is a few
     // dozen tiles; workgroups beyond that only cost their dispatch (C5, 64 maps: 320 / 160 / 80 / 40 / 20 / 10 per map ->
@@ -1547,6 +1542,13 @@ int32_t gms_likelihood_blocks_cap(const gms_map *m, size_t smem) {
     if (per_map > resident / 4) per_map = resident / 4;
     if (per_map < 8) per_map = 8;
     return per_map;
+}
+// the grid of a rebuild by persistent workgroups, per map: each walks tiles blockIdx.x, += gridDim.x
+static inline int32_t lik_tile_blocks(const gms_map *m, size_t smem, int32_t tiles_x, int32_t tiles_y) {
+    int32_t blocks = tiles_x * tiles_y;
+    const int32_t cap = gms_likelihood_blocks_cap(m, smem);
+    if (blocks > cap) blocks = cap;
+    return (blocks + 7) & ~7;                        // keep the XCD round-robin aligned
 }
 
 // Whether a dirty-tile rebuild launched with `blocks` workgroups per map may split its tiles in two: one map, and twice the tiles of the
@@ -1577,15 +1579,11 @@ void gms_launch_likelihood(gms_map *m, int32_t dirty_only, bool counts_pending, 
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
     const size_t smem = gms_likelihood_lds_bytes(m->gd.khalf, k != 0);
-    // persistent workgroups, each walks tiles blockIdx.x, += gridDim.x
-    int32_t blocks = tiles_x * tiles_y;
-    const int32_t cap = gms_likelihood_blocks_cap(m, smem);
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) & ~7;                      // keep the XCD round-robin aligned
+    const int32_t blocks = lik_tile_blocks(m, smem, tiles_x, tiles_y);
     dim3 grid(blocks, m->n_maps);
-    const int32_t *bb = m->d_bbox + (size_t)m->bbox_cur * m->n_maps * 4;
+    const int32_t *bb = map_box(m);
     const uint32_t *pend = counts_pending ? m->d_cnt : (const uint32_t *)nullptr;
-    int32_t *bb_clear = counts_pending ? m->d_bbox + (size_t)(1 - m->bbox_cur) * m->n_maps * 4 : (int32_t *)nullptr;
+    int32_t *bb_clear = counts_pending ? map_box(m, true) : (int32_t *)nullptr;
     uint8_t *tstate = m->d_tile_state;
     if (materialize) {
         dirty_only = 0; bb_clear = nullptr; tstate = nullptr;
@@ -1595,24 +1593,19 @@ void gms_launch_likelihood(gms_map *m, int32_t dirty_only, bool counts_pending, 
     // a dirty-tile rebuild of a single map splits its tiles over two workgroups each when the largest box a scan can touch still leaves
     // every (tile, part) a workgroup of its own (likelihood_body, "split")
     const bool split = k != 0 && dirty_only && counts_pending && gms_likelihood_split(m, blocks);
-#define LK_LAUNCH(KH)                                                                                         \
-    do {                                                                                                      \
-        if (split) LK_LAUNCH2(KH, true, 2); else if (counts_pending) LK_LAUNCH2(KH, true, 1); else LK_LAUNCH2(KH, false, 1); \
-    } while (0)
-#define LK_LAUNCH2(KH, PEND, SP)                                                                              \
-    do {                                                                                                      \
-        if (smem > 48 * 1024)                                                                                 \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_likelihood<KH, PEND, SP>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                       \
-        hipLaunchKernelGGL((k_likelihood<KH, PEND, SP>), grid, dim3(256), smem, m->stream, bb, tstate, bb_clear, pend,     \
-                           dirty_only, mode, tiles_x, tiles_y, m->d_log, m->d_lik, m->d_fac, m->fac_stride,   \
-                           m->d_taps, m->gd);                                                                 \
-    } while (0)
-    if (k == 3) LK_LAUNCH(3);
-    else if (k == 5) LK_LAUNCH(5);
-    else { if (counts_pending) LK_LAUNCH2(0, true, 1); else LK_LAUNCH2(0, false, 1); }
-#undef LK_LAUNCH
-#undef LK_LAUNCH2
+    auto launch = [&](auto kh, auto pending, auto parts) {
+        gms_launch<k_likelihood<kh(), pending(), parts()>>(m, grid, dim3(256), smem, bb, tstate, bb_clear, pend, dirty_only, mode, tiles_x, tiles_y,
+                                                            m->d_log, m->d_lik, m->d_fac, m->fac_stride, m->d_taps, m->gd);
+    };
+    auto coded = [&](auto kh) {                      // the compile-time half widths: pending counts or none, and with them whole tiles or halves
+        if (split) launch(kh, gms_c<true>{}, gms_c<2>{});
+        else if (counts_pending) launch(kh, gms_c<true>{}, gms_c<1>{});
+        else launch(kh, gms_c<false>{}, gms_c<1>{});
+    };
+    if (k == 3) coded(gms_c<3>{});
+    else if (k == 5) coded(gms_c<5>{});
+    else if (counts_pending) launch(gms_c<0>{}, gms_c<true>{}, gms_c<1>{});
+    else launch(gms_c<0>{}, gms_c<false>{}, gms_c<1>{});
     if (immediate) map_box_consumed(m);
 }
 

@@ -1741,14 +1741,10 @@ void gms_launch_pf_resample(gms_pf *pf, double fraction) {
     gms_launch_pf_chunk_sums(pf);
     ProfScope ps(m, GMS_K_RESAMPLE);
     const int64_t nch = nchunks_of(pf);
-    const size_t smem = gms_resample_lds_bytes(nch);
-    if (smem > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resample), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-    hipLaunchKernelGGL(k_resample, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), smem, m->stream, pf->d_global,
-                       pf->n_global, nch, pf->d_cum, pf->d_chunk_tot, pf->n_maps == 1 ? (const double *)nullptr : pf->d_r01_src,
-                       pf->r01_scalar, fraction, pf->n, pf->offset,
-                       pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, pf->d_p2, nblk_global_of(pf), pf->d_stats, pf->global_raw, pf->d_epoch2);
+    gms_launch<k_resample>(m, dim3((pf->n + 255) / 256, pf->n_maps), dim3(256), gms_resample_lds_bytes(nch), pf->d_global, pf->n_global, nch,
+                           pf->d_cum, pf->d_chunk_tot, pf->n_maps == 1 ? (const double *)nullptr : pf->d_r01_src, pf->r01_scalar, fraction, pf->n,
+                           pf->offset, pf->d_pose2, pf->d_cs2, pf->d_w2, pf->d_idx, pf->d_p2, nblk_global_of(pf), pf->d_stats, pf->global_raw,
+                           pf->d_epoch2);
     pf_neff_folded(pf);
 }
 
@@ -1756,12 +1752,8 @@ void gms_launch_pf_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_
     gms_map *m = pf->map;
     launch_compact(pf, d_beams, B, beam_stride);
     ProfScope ps(m, GMS_K_REFINE);
-    const size_t smem = (size_t)B * sizeof(double2);
-    if (smem > 32 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_refine), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-    hipLaunchKernelGGL(k_refine, dim3(pf->n, pf->n_maps), dim3(256), smem, m->stream, m->gd, m->d_fac, m->fac_stride,
-                       pf->d_hitbeams, pf->d_nhit, m->max_beams, pf->d_pose, pf->d_cs, pf->n);
+    gms_launch<k_refine>(m, dim3(pf->n, pf->n_maps), dim3(256), (size_t)B * sizeof(double2), m->gd, m->d_fac, m->fac_stride, pf->d_hitbeams,
+                         pf->d_nhit, m->max_beams, pf->d_pose, pf->d_cs, pf->n);
 }
 
 // ---- the reference-order audit path (gms_pf_set_reference_order) ----

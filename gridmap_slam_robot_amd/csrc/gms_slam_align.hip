@@ -31,7 +31,6 @@
 #include "gms_slam_device.h"
 
 #define SA_NT 256                       // PLANES: four wavefronts, sixteen beams per pass of the field's values
-#define SA_MAX_DEVICES 64               // devices whose LDS opt-in per instantiation the launcher remembers
 #define SA_MAXTAPS 15                  // the class planes are kept for blur kernels of up to 15 taps (gms_slam_create)
 
 // the horizontal sum of row y at column gx (Util.java:391-401 over the columns inside the map), literal taps: field_pass's
@@ -207,21 +206,12 @@ int gms_launch_slam_align(gms_slam *s, const gms_beam *d_beams, int32_t B, const
     const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
     const size_t smem = from_planes ? slam_align_lds(Bpad, s->code_words) : (size_t)Bpad * 16;
-    // (the opt-in to dynamic LDS is made when an instantiation first needs more than it was given on this device, not once per update)
-#define SA_LAUNCH(PL, BT)                                                                                                               \
-    do {                                                                                                                                \
-        static size_t granted[SA_MAX_DEVICES];                                                                                          \
-        const bool known = m->device >= 0 && m->device < SA_MAX_DEVICES;                                                                \
-        if (!known || smem > granted[m->device]) {                                                                                      \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_align<PL, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-            if (known) granted[m->device] = smem;                                                                                       \
-        }                                                                                                                               \
-        hipLaunchKernelGGL((k_slam_align<PL, BT>), dim3(grid), dim3(PL ? SA_NT : GMS_WAVE), smem, m->stream, m->gd, d_beams, B, Bpad, sb, \
-                           pf->d_pose, pf->d_cs, d_rec, mo, (int32_t)s->code_words, m->d_taps, m->taps_plain, *prm, bt);                \
-    } while (0)
-    if (from_planes) { if (batch) SA_LAUNCH(true, true); else SA_LAUNCH(true, false); }
-    else { if (batch) SA_LAUNCH(false, true); else SA_LAUNCH(false, false); }
-#undef SA_LAUNCH
+    auto launch = [&](auto planes, auto batched) {
+        gms_launch<k_slam_align<planes(), batched()>>(m, dim3(grid), dim3(planes() ? SA_NT : GMS_WAVE), smem, m->gd, d_beams, B, Bpad, sb, pf->d_pose,
+                                                      pf->d_cs, d_rec, mo, (int32_t)s->code_words, m->d_taps, m->taps_plain, *prm, bt);
+    };
+    if (from_planes) { if (batch) launch(gms_c<true>{}, gms_c<true>{}); else launch(gms_c<true>{}, gms_c<false>{}); }
+    else { if (batch) launch(gms_c<false>{}, gms_c<true>{}); else launch(gms_c<false>{}, gms_c<false>{}); }
     HIPCHK(hipGetLastError());
     s->align_form = from_planes ? GMS_SLAM_ALIGN_PLANES : GMS_SLAM_ALIGN_MEMORY;
     return GMS_OK;

@@ -1235,30 +1235,25 @@ k_slam_shard_gather(SlamBufs sb, const int32_t *__restrict__ src_local, const in
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
+// workgroups per map for the fields of n particles' maps of `tiles` tiles each: a workgroup per tile while that stays a few rounds of
+// the chip; beyond it persistent workgroups walk a map's tiles
+// (4096 maps of 32 tiles: 32 / 16 / 8 / 4 workgroups per map 889 / 886 / 850 / 916 us; 500 maps of 8 tiles: 8 / 4 / 2 / 1: 25.3 / 26.8 / 27.4 / 32.1 us)
+static inline int32_t slam_lik_blocks(const gms_map *m, size_t smem, int32_t tiles, int32_t n) {
+    const int64_t resident = lik_resident(m, smem);
+    int32_t blocks = tiles;
+    while (blocks > 1 && (int64_t)blocks * n > 32 * resident) blocks = (blocks + 1) / 2;
+    return blocks;
+}
 void gms_launch_slam_likelihood(gms_map *m, const SlamBufs &sb, int32_t n) {
     ProfScope ps(m, GMS_K_LIKELIHOOD);
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
     const size_t smem = gms_likelihood_lds_bytes(m->gd.khalf, k != 0);
-    // a workgroup per tile while that stays a few rounds of the chip; beyond it persistent workgroups walk a map's tiles
-    int32_t blocks = tiles_x * tiles_y;
-    int32_t per_cu = (int32_t)((size_t)m->lds_per_cu / (smem + 256));
-    if (per_cu > GMS_LIK_WG_PER_CU) per_cu = GMS_LIK_WG_PER_CU;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t resident = (int64_t)per_cu * m->n_cus;
-    // (4096 maps of 32 tiles: 32 / 16 / 8 / 4 workgroups per map 889 / 886 / 850 / 916 us; 500 maps of 8 tiles: 8 / 4 / 2 / 1: 25.3 / 26.8 / 27.4 / 32.1 us)
-    while (blocks > 1 && (int64_t)blocks * n > 32 * resident) blocks = (blocks + 1) / 2;
-    dim3 grid((unsigned)blocks, (unsigned)n);
-#define SLK_LAUNCH(KH)                                                                                                          \
-    do {                                                                                                                          \
-        if (smem > 48 * 1024)                                                                                                     \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_likelihood<KH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL((k_slam_likelihood<KH>), grid, dim3(256), smem, m->stream, m->gd, sb, m->d_taps, tiles_x, tiles_y);          \
-    } while (0)
-    if (k == 3) SLK_LAUNCH(3);
-    else if (k == 5) SLK_LAUNCH(5);
-    else SLK_LAUNCH(0);
-#undef SLK_LAUNCH
+    dim3 grid((unsigned)slam_lik_blocks(m, smem, tiles_x * tiles_y, n), (unsigned)n);
+    auto launch = [&](auto kh) { gms_launch<k_slam_likelihood<kh()>>(m, grid, dim3(256), smem, m->gd, sb, m->d_taps, tiles_x, tiles_y); };
+    if (k == 3) launch(gms_c<3>{});
+    else if (k == 5) launch(gms_c<5>{});
+    else launch(gms_c<0>{});
 }
 
 int64_t gms_slam_code_words(int64_t cells) { return slam_code_words(cells); }
@@ -1268,23 +1263,13 @@ void gms_launch_slam_likelihood_codes(gms_map *m, const SlamBufs &sb, int64_t co
     const int32_t k = m->lik_kh;
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
     const size_t smem = gms_likelihood_lds_bytes(m->gd.khalf, k != 0);
-    int32_t blocks = tiles_x * tiles_y;
-    int32_t per_cu = (int32_t)((size_t)m->lds_per_cu / (smem + 256));
-    if (per_cu > GMS_LIK_WG_PER_CU) per_cu = GMS_LIK_WG_PER_CU;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t resident = (int64_t)per_cu * m->n_cus;
-    while (blocks > 1 && (int64_t)blocks * n > 32 * resident) blocks = (blocks + 1) / 2;
-    dim3 grid((unsigned)blocks, (unsigned)n);
-#define SLK_LAUNCH(KH)                                                                                                          \
-    do {                                                                                                                          \
-        if (smem > 48 * 1024)                                                                                                     \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_likelihood_codes<KH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL((k_slam_likelihood_codes<KH>), grid, dim3(256), smem, m->stream, m->gd, sb, code_words, plane, m->d_taps, tiles_x, tiles_y); \
-    } while (0)
-    if (k == 3) SLK_LAUNCH(3);
-    else if (k == 5) SLK_LAUNCH(5);
-    else SLK_LAUNCH(0);
-#undef SLK_LAUNCH
+    dim3 grid((unsigned)slam_lik_blocks(m, smem, tiles_x * tiles_y, n), (unsigned)n);
+    auto launch = [&](auto kh) {
+        gms_launch<k_slam_likelihood_codes<kh()>>(m, grid, dim3(256), smem, m->gd, sb, code_words, plane, m->d_taps, tiles_x, tiles_y);
+    };
+    if (k == 3) launch(gms_c<3>{});
+    else if (k == 5) launch(gms_c<5>{});
+    else launch(gms_c<0>{});
 }
 
 // plane 0 of particles first .. first + count - 1 from their logData
@@ -1331,20 +1316,17 @@ void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, co
     if (m->slam_threads == 512 || m->slam_threads == 1024) threads = m->slam_threads;
     const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
-#define PS_LAUNCH1(NT, NA, CD, BT)                                                                                                      \
-    do {                                                                                                                                \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_particle<NT, NP, NA, CD, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL((k_slam_particle<NT, NP, NA, CD, BT>), dim3(grid), dim3(NT), smem, m->stream, m->gd, d_beams, B, Bpad, sb,           \
-                           field_in_memory ? 1 : 0, pf->d_pose, pf->d_cs, pf->d_w, pf->d_logw, mo, integrate, (int32_t)(tile * 4), (int32_t)code_words, \
-                           m->d_taps, m->taps_plain, bt);                                                                               \
-    } while (0)
-#define PS_LAUNCH(NT, NA, CD) do { if (batch) PS_LAUNCH1(NT, NA, CD, true); else PS_LAUNCH1(NT, NA, CD, false); } while (0)
-#define PS_LAUNCH2(NT, NA) do { if (d_code) PS_LAUNCH(NT, NA, true); else PS_LAUNCH(NT, NA, false); } while (0)
-    if (threads == 512) { if (narrow_allowed) PS_LAUNCH2(512, true); else PS_LAUNCH2(512, false); }
-    else { if (narrow_allowed) PS_LAUNCH2(1024, true); else PS_LAUNCH2(1024, false); }
-#undef PS_LAUNCH2
-#undef PS_LAUNCH
-#undef PS_LAUNCH1
+    constexpr gms_c<true> yes{};
+    constexpr gms_c<false> no{};
+    auto launch = [&](auto nt, auto narrow, auto codes, auto batched) {
+        gms_launch<k_slam_particle<nt(), NP, narrow(), codes(), batched()>>(m, dim3(grid), dim3(nt()), smem, m->gd, d_beams, B, Bpad, sb,
+                                                                            field_in_memory ? 1 : 0, pf->d_pose, pf->d_cs, pf->d_w, pf->d_logw, mo, integrate,
+                                                                            (int32_t)(tile * 4), (int32_t)code_words, m->d_taps, m->taps_plain, bt);
+    };
+    auto by_batch = [&](auto nt, auto narrow, auto codes) { if (batch) launch(nt, narrow, codes, yes); else launch(nt, narrow, codes, no); };
+    auto by_codes = [&](auto nt, auto narrow) { if (d_code) by_batch(nt, narrow, yes); else by_batch(nt, narrow, no); };
+    if (threads == 512) { if (narrow_allowed) by_codes(gms_c<512>{}, yes); else by_codes(gms_c<512>{}, no); }
+    else { if (narrow_allowed) by_codes(gms_c<1024>{}, yes); else by_codes(gms_c<1024>{}, no); }
     pf_scored(pf, 1);
 }
 
@@ -1405,19 +1387,15 @@ bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, cons
     ProfScope ps(m, GMS_K_REFINE);
     const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
-#define SR_LAUNCH1(LF, KF, BT)                                                                                                          \
-    do {                                                                                                                                \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_refine<LF, KF, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.smem); \
-        hipLaunchKernelGGL((k_slam_refine<LF, KF, BT>), dim3(grid), dim3(SR_NT_OF(LF, KF)), r.smem, m->stream, m->gd, d_beams, B, r.Bpad, sb, \
-                           pf->d_pose, pf->d_cs, mo, r.fp, r.nt_batch, (int32_t)code_words, m->d_taps, bt);                            \
-    } while (0)
-#define SR_LAUNCH(LF, KF) do { if (batch) SR_LAUNCH1(LF, KF, true); else SR_LAUNCH1(LF, KF, false); } while (0)
-    if (r.khf == 3) SR_LAUNCH(true, 3);
-    else if (r.khf == 5) SR_LAUNCH(true, 5);
-    else if (r.ldsf) SR_LAUNCH(true, 0);
-    else SR_LAUNCH(false, 0);
-#undef SR_LAUNCH
-#undef SR_LAUNCH1
+    auto launch = [&](auto ldsf, auto khf, auto batched) {
+        gms_launch<k_slam_refine<ldsf(), khf(), batched()>>(m, dim3(grid), dim3(SR_NT_OF(ldsf(), khf())), r.smem, m->gd, d_beams, B, r.Bpad, sb, pf->d_pose,
+                                                            pf->d_cs, mo, r.fp, r.nt_batch, (int32_t)code_words, m->d_taps, bt);
+    };
+    auto by_batch = [&](auto ldsf, auto khf) { if (batch) launch(ldsf, khf, gms_c<true>{}); else launch(ldsf, khf, gms_c<false>{}); };
+    if (r.khf == 3) by_batch(gms_c<true>{}, gms_c<3>{});
+    else if (r.khf == 5) by_batch(gms_c<true>{}, gms_c<5>{});
+    else if (r.ldsf) by_batch(gms_c<true>{}, gms_c<0>{});
+    else by_batch(gms_c<false>{}, gms_c<0>{});
     return true;
 }
 
@@ -1559,12 +1537,12 @@ void gms_launch_slam_view(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_st
     const ViewDev vd = view_dev(m, v);
     const dim3 grid = view_grid(vd);
     const bool lik = v->source == GMS_VIEW_LIKELIHOOD;
-#define SV_LAUNCH(LIK, PACKED)                                                                                                    \
-    hipLaunchKernelGGL((k_slam_view<LIK, PACKED>), grid, dim3(256), 0, m->stream, sb, d_stats, which, filter, (int32_t)field, d_idx_lik, \
-                       m->gd.cells, vd, d_out, d_shown)
-    if (v->format == GMS_VIEW_PACKED32) { if (lik) SV_LAUNCH(true, true); else SV_LAUNCH(false, true); }
-    else { if (lik) SV_LAUNCH(true, false); else SV_LAUNCH(false, false); }
-#undef SV_LAUNCH
+    auto launch = [&](auto likelihood, auto packed) {
+        gms_launch<k_slam_view<likelihood(), packed()>>(m, grid, dim3(256), 0, sb, d_stats, which, filter, (int32_t)field, d_idx_lik, m->gd.cells, vd,
+                                                        d_out, d_shown);
+    };
+    if (v->format == GMS_VIEW_PACKED32) { if (lik) launch(gms_c<true>{}, gms_c<true>{}); else launch(gms_c<false>{}, gms_c<true>{}); }
+    else { if (lik) launch(gms_c<true>{}, gms_c<false>{}); else launch(gms_c<false>{}, gms_c<false>{}); }
 }
 
 void gms_launch_slam_likelihood_shown(gms_map *m, const SlamBufs &sb, const PfStatsDev *d_stats, int32_t which, int32_t filter, int64_t code_words) {
@@ -1573,17 +1551,12 @@ void gms_launch_slam_likelihood_shown(gms_map *m, const SlamBufs &sb, const PfSt
     const int32_t tiles_x = (m->gd.W + LK_TW - 1) / LK_TW, tiles_y = (m->gd.H + LK_TH - 1) / LK_TH;
     const size_t smem = gms_likelihood_lds_bytes(m->gd.khalf, k != 0);
     const dim3 grid((unsigned)(tiles_x * tiles_y));                                  // one map: a workgroup per tile
-#define SLS_LAUNCH(KH)                                                                                                          \
-    do {                                                                                                                          \
-        if (smem > 48 * 1024)                                                                                                     \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_likelihood_shown<KH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL((k_slam_likelihood_shown<KH>), grid, dim3(256), smem, m->stream, m->gd, sb, d_stats, which, filter, code_words, m->d_taps, \
-                           tiles_x, tiles_y);                                                                                     \
-    } while (0)
-    if (k == 3) SLS_LAUNCH(3);
-    else if (k == 5) SLS_LAUNCH(5);
-    else SLS_LAUNCH(0);
-#undef SLS_LAUNCH
+    auto launch = [&](auto kh) {
+        gms_launch<k_slam_likelihood_shown<kh()>>(m, grid, dim3(256), smem, m->gd, sb, d_stats, which, filter, code_words, m->d_taps, tiles_x, tiles_y);
+    };
+    if (k == 3) launch(gms_c<3>{});
+    else if (k == 5) launch(gms_c<5>{});
+    else launch(gms_c<0>{});
 }
 
 // ---- the particles' paths (gms_slam_set_history; gridmapslam.h "trajectories") -------------------------------------------------
@@ -1735,9 +1708,7 @@ void gms_launch_slam_hist_walk(gms_map *m, const SlamHist &h, const int32_t *d_l
                                int32_t kept, int32_t rows, float *d_out, int32_t *d_anc, int32_t *d_shown) {
     if (rows > 0) {
         const size_t smem = (size_t)2 * HW_WORDS * 4 + (size_t)(bundle ? h.n_per : 1) * 4;
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slam_hist_walk<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k_slam_hist_walk<true>, dim3(1), dim3(HW_NT), smem, m->stream, h, d_lin, d_stats, which, filter, bundle ? 1 : 0, kept, rows, d_out,
-                           d_anc, d_shown);
+        gms_launch<k_slam_hist_walk<true>>(m, dim3(1), dim3(HW_NT), smem, h, d_lin, d_stats, which, filter, bundle ? 1 : 0, kept, rows, d_out, d_anc, d_shown);
     } else {
         hipLaunchKernelGGL(k_slam_hist_walk<false>, dim3(1), dim3(HW_NT), 0, m->stream, h, d_lin, d_stats, which, filter, bundle ? 1 : 0, kept, 0, d_out, d_anc,
                            d_shown);
