@@ -244,6 +244,7 @@ ALIGN_DTYPE = np.dtype([(n, ("<f8", (6,)) if n == "H" else "<f8" if t is C.c_dou
 assert ALIGN_DTYPE.itemsize == C.sizeof(GmsAlignRecord) == 80 and C.sizeof(GmsAlignParams) == 64
 GMS_ALIGN_ITERS, GMS_ALIGN_CONVERGED, GMS_ALIGN_NO_BEAM, GMS_ALIGN_SINGULAR = 0, 1, 2, 3      # gms_align_record.status
 GMS_SLAM_ALIGN_PLANES, GMS_SLAM_ALIGN_MEMORY = 1, 2                                          # gms_slam_align_form
+GMS_SLAM_BEAMS_MULTIPLY, GMS_SLAM_BEAMS_REPLACE = 0, 1                                       # gms_slam_set_beam_model's combine
 GMS_MAX_PARTICLES = 1 << 20
 CLEARANCE = GmsClearance
 GMS_REACH_AXIS, GMS_REACH_DIAG, GMS_REACH_FAR, GMS_REACH_MAX_SEEDS = 5, 7, 0xFFFF, 4096
@@ -497,6 +498,9 @@ def load() -> C.CDLL:
     sig("gms_slam_align", C.c_int, vp, vp, i32, ap, vp)
     sig("gms_slam_align_dev", C.c_int, vp, vp, i32, ap, vp)
     sig("gms_slam_set_align", C.c_int, vp, ap)
+    sig("gms_slam_score_beams", C.c_int, vp, vp, i32, i32, i32, vp, vp)
+    sig("gms_slam_score_beams_dev", C.c_int, vp, vp, i32, i32, i32, vp, vp)
+    sig("gms_slam_set_beam_model", C.c_int, vp, i32, i32, vp, i32)
     sig("gms_slam_last_align", C.c_int, vp, vp)
     sig("gms_slam_align_form", C.c_int, vp, C.POINTER(C.c_int32))
     rop = C.POINTER(GmsRollout)

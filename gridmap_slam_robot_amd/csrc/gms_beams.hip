@@ -6,7 +6,7 @@
 //
 //   k_beam_score   one workgroup of 256 lanes per (particle, map).  Lane l owns partial l: it walks the beams l, l + 256, ... of the scan
 //                  one after another with `ahead` extra cells through the map's GMS_CLEAR_OCCUPIED plane to the first set bit
-//                  (ray_first, gms_probe.h), takes the table index from the iterator's remaining count there, and multiplies / adds
+//                  (beam_walk, gms_probe.h), takes the table index from the iterator's remaining count there, and multiplies / adds
 //                  the two tables' entries into its partials.  In front of the walks the workgroup stages the window of its rays
 //                  (PlaneWindow: every lane's box over its beams, padded by ahead + 1) when it fits what the launch asked for; a
 //                  window that does not fit, or GMS_CAST_WALK=mem: every bit from memory.  What the window may and may not decide:
@@ -25,14 +25,7 @@
 
 #define BEAM_NT 256
 #define BEAM_LDS_CAP (64 * 1024)         // the window: bytes of LDS a workgroup asks for at most
-#define BEAM_T_MAX 512                   // behind + ahead + 2 at most
-#define BEAM_TAB_BYTES (4 * BEAM_T_MAX * sizeof(double))
-
-// the table index of one beam from the iterator's remaining count at the first wall (ray_first, gms_probe.h): top = behind + ahead + 1
-template <class Occ>
-__device__ __forceinline__ int32_t beam_walk(const GridDev &g, const RayIn &ray, int32_t ahead, int32_t top, Occ occ) {
-    return ray_first(g, ray, ahead, occ, [&](int32_t, const RayDev &r) { return r.n > top ? 0 : top - r.n; }, top);   // (r.n >= 1 there: at most top - 1; top: none)
-}
+#define BEAM_TAB_BYTES GMS_BEAM_TAB_BYTES
 
 // grid (particles, maps).  plane: map 0's, the maps plane_stride words apart; beams: map 0's, the maps beam_stride apart; tab:
 // factors [2][T] then their logarithms [2][T]; residuals: [n_maps][n][B] or NULL; lds_words: the window the launch asked for (0: walk memory)
@@ -85,7 +78,7 @@ k_beam_score(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, int64_t
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-static int beam_model_check(int32_t behind, int32_t ahead, const double *factors, const char *who) {
+int gms_beam_model_check_for(int32_t behind, int32_t ahead, const double *factors, const char *who) {
     if (behind < 0 || behind > 255) return gms_fail(GMS_ERR_INVALID, "%s: 0 <= behind <= 255 steps", who);
     if (ahead < 0 || ahead > 255) return gms_fail(GMS_ERR_INVALID, "%s: 0 <= ahead <= 255 steps", who);
     if (!factors) return gms_fail(GMS_ERR_INVALID, "%s: null factors (two rows of behind + ahead + 2 doubles are required)", who);
@@ -100,7 +93,7 @@ static int pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t 
                           bool on_device) {
     const char *who = on_device ? "gms_pf_score_beams_dev" : "gms_pf_score_beams";
     if (!pf || !beams) return gms_fail(GMS_ERR_INVALID, "%s: null argument (the filter, the beams and the factors are required)", who);
-    int rc = beam_model_check(behind, ahead, factors, who);
+    int rc = gms_beam_model_check_for(behind, ahead, factors, who);
     if (rc) return rc;
     if (pf->slam_owned)
         return gms_fail(GMS_ERR_STATE, "%s: this filter's particles own maps (gms_slam): there is no one map to walk", who);
@@ -156,7 +149,7 @@ static int pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t 
 
 extern "C" {
 
-int gms_beam_model_check(int32_t behind, int32_t ahead, const double *factors) { return beam_model_check(behind, ahead, factors, "gms_beam_model"); }
+int gms_beam_model_check(int32_t behind, int32_t ahead, const double *factors) { return gms_beam_model_check_for(behind, ahead, factors, "gms_beam_model"); }
 
 int gms_pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals) {
     return pf_score_beams(pf, beams, B, behind, ahead, factors, residuals, false);

@@ -465,6 +465,17 @@ struct gms_slam {
     int32_t align_form;             // the form the last alignment launch took (gms_slam_align_form); 0: none yet
     gms_align_record *d_align_rec;  // [n] the records of the last aligned update (allocated by gms_slam_set_align)
     int32_t have_align_rec;         // an aligned update has run since they were allocated
+    // the beam sensor model on the particles' own maps (gms_slam_score_beams, gms_slam_set_beam_model; gms_slam_beams.hip)
+    struct {
+        double *d_tab;              // two tables, each factors [2][T] | their logarithms [2][T] in GMS_BEAM_TAB_BYTES: [0] the last
+                                    // stand-alone call's, [1] the model's that every update applies
+        StageRing ring;             // pinned staging of either
+        int32_t ring_ready;
+        double *d_wgt;              // [n] beam weights | [n] beam log-weights of the update under way (allocated by gms_slam_set_beam_model)
+        int32_t on;                 // update() weighs every particle by the model, through its own map as it stands in front of the scan
+        int32_t behind, ahead;      // ... with this table (checked when it was set)
+        int32_t combine;            // GMS_SLAM_BEAMS_MULTIPLY / _REPLACE
+    } beam;
 };
 
 // the history of a gms_slam as its kernels see it (gms_slam_set_history): a ring of cap rows, update number t in row t % cap
@@ -785,6 +796,18 @@ int gms_align_check_for(const gms_align_params *p, const char *who);       // gm
 bool gms_slam_align_from_planes(const gms_slam *s, int32_t B);
 int gms_launch_slam_align(gms_slam *s, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, bool from_planes, const MotionModel *motion,
                           const gms_align_params *prm, gms_align_record *d_rec, const SlamBatch *batch = nullptr);
+// the beam sensor model (gms_beams.hip, gms_slam_beams.hip): a table is factors [2][T] | their logarithms [2][T], T = behind + ahead + 2
+#define GMS_BEAM_T_MAX 512
+#define GMS_BEAM_TAB_BYTES (4 * GMS_BEAM_T_MAX * sizeof(double))
+int gms_beam_model_check_for(int32_t behind, int32_t ahead, const double *factors, const char *who);   // gms_beam_model_check with the caller's name in the message
+// ... on the particles' own maps (gms_slam_beams.hip).  The table through the handle's pinned ring into slot `which` of beam.d_tab (0: a
+// stand-alone call's, 1: the model's); the launch -- every particle held walks its own logData of the current generation at its pose
+// (motion non-NULL: the motion-model sample is drawn first and written, as gms_launch_slam_align does), weights into d_wgt / d_logw [n],
+// d_res [n][B] or NULL; and the update's combine of beam.d_wgt into the filter's raw weights behind gms_launch_slam_particle
+int gms_slam_beam_table(gms_slam *s, const char *who, int32_t behind, int32_t ahead, const double *factors, int32_t which);
+void gms_launch_slam_beams(gms_slam *s, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, const MotionModel *motion, int32_t behind, int32_t ahead,
+                           int32_t which, double *d_wgt, double *d_logw, uint16_t *d_res, const SlamBatch *batch = nullptr);
+void gms_launch_slam_weight_combine(gms_slam *s, int32_t B, const SlamBatch *batch = nullptr);
 // resample()'s copies into the generation the draw has just made current, where it drew (epoch[1]); what: bit 0 logData (+ the class
 // planes), bit 1 likelihoodData; d_idx_keep (may be NULL) receives the indices for a likelihoodData copy that is still owed
 void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const int32_t *d_idx, int32_t *d_idx_keep, int64_t code_words);

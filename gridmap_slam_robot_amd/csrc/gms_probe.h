@@ -1,5 +1,5 @@
 // gms_probe.h -- the probe geometry the ray queries share (device only; DESIGN.md "the probe geometry the ray queries share"): the window
-// of a bit plane a workgroup stages in LDS for its rays, and the walk to the first set bit; k_cast_map and k_beam_score use all of it.  The pose's transform and the ray's locals
+// of a bit plane a workgroup stages in LDS for its rays, and the walk to the first set bit; k_cast_map, k_beam_score and k_slam_beam_score use it.  The pose's transform and the ray's locals
 // (pose_xform, make_ray) live in gms_device.h, where the scan step takes them from as well.
 //
 // Every expression keeps the reference's operand order and casts (gms_device.h; the build never contracts a multiply with an add).
@@ -65,6 +65,14 @@ struct PlaneWindow {
         const uint32_t word = (cw < (uint32_t)ww && cr < (uint32_t)wh) ? s_win[cr * (uint32_t)ww + cw] : plane[(size_t)y * (size_t)wpr + (size_t)(x >> 5)];
         return ((word >> (x & 31)) & 1u) != 0u;
     }
+    // ... of a plane that exists nowhere but in the window (k_slam_beam_score packs it from a particle's logData): the same rule, a cell
+    // outside the window answered by mem(x, y)
+    template <class Mem>
+    __device__ __forceinline__ bool bit_else(const uint32_t *s_win, int32_t x, int32_t y, Mem mem) const {
+        const uint32_t cw = (uint32_t)((x >> 5) - wx0), cr = (uint32_t)(y - wy0);
+        if (cw < (uint32_t)ww && cr < (uint32_t)wh) return ((s_win[cr * (uint32_t)ww + cw] >> (x & 31)) & 1u) != 0u;
+        return mem(x, y);
+    }
 };
 
 // integrateObservation's walk (GridMap.java:210-211) with `extra` steps past the end, to the FIRST cell for which occ(x, y) holds; occ is
@@ -81,4 +89,10 @@ __device__ __forceinline__ T ray_first(const GridDev &g, const RayIn &ray, int32
         ray_step(r);
     }
     return none;
+}
+
+// the beam sensor model's table index of one beam from the iterator's remaining count at the first wall: top = behind + ahead + 1
+template <class Occ>
+__device__ __forceinline__ int32_t beam_walk(const GridDev &g, const RayIn &ray, int32_t ahead, int32_t top, Occ occ) {
+    return ray_first(g, ray, ahead, occ, [&](int32_t, const RayDev &r) { return r.n > top ? 0 : top - r.n; }, top);   // (r.n >= 1 there: at most top - 1; top: none)
 }

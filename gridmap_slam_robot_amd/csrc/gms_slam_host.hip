@@ -88,6 +88,8 @@ int gms_slam_destroy(gms_slam *s) {
     hipFree(s->d_plan);
     hipFree(s->d_batch);
     hipFree(s->d_align_rec);
+    hipFree(s->beam.d_tab); hipFree(s->beam.d_wgt);
+    if (s->beam.ring_ready) gms_ring_free(s->beam.ring);
     slam_hist_free(s);
     gms_ring_free(s->batch_ring);
     if (s->pf) gms_pf_destroy(s->pf);
@@ -267,7 +269,15 @@ static int slam_update_core(gms_slam *s, const gms_beam *dev_beams, int32_t B, c
         s->have_align_rec = 1;
         drawn = true;
     }
+    // the beam sensor model (gms_slam_set_beam_model): through the particle's own map as it stands BEFORE this scan goes into it -- behind
+    // it every particle would find its own end cell occupied --, at the pose it is weighted at: the sample, the lattice's, the aligned one
+    const bool beams = s->beam.on && B > 0;
+    if (beams) {
+        gms_launch_slam_beams(s, dev_beams, B, sb, drawn ? nullptr : motion, s->beam.behind, s->beam.ahead, 1, s->beam.d_wgt, s->beam.d_wgt + s->n, nullptr, batch);
+        drawn = true;
+    }
     gms_launch_slam_particle(pf, dev_beams, B, sb, !on_demand, drawn ? nullptr : motion, skip_update ? 0 : 1, s->code_words, batch);   // :90, :99, :102-107
+    if (beams) gms_launch_slam_weight_combine(s, B, batch);                                                 // p.weight (:99) times the model's, or the model's
     if (s->hist_cap) {                                                                                      // the poses stand (the normalisation moves none): one row
         gms_launch_slam_hist_append(m, slam_hist(s), pf->d_pose, s->d_hist_lin[s->hist_lin_cur]);
         s->hist_steps++;
@@ -682,6 +692,71 @@ int gms_slam_last_align(gms_slam *s, gms_align_record *records) {
 int gms_slam_align_form(const gms_slam *s, int32_t *form) {
     REQUIRE(s && form, "gms_slam_align_form: null argument");
     *form = s->align_form;
+    return GMS_OK;
+}
+
+// ---- the beam sensor model on the particles' own maps (gridmapslam.h "per-particle beam sensor model"; kernels: gms_slam_beams.hip) ----
+static int slam_score_beams(gms_slam *s, const gms_beam *beams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals,
+                            bool on_device) {
+    const char *who = on_device ? "gms_slam_score_beams_dev" : "gms_slam_score_beams";
+    if (!s || !beams) return gms_fail(GMS_ERR_INVALID, "%s: null argument (the handle, the beams and the factors are required)", who);
+    int rc = gms_beam_model_check_for(behind, ahead, factors, who);
+    if (rc) return rc;
+    if (!s->map || !s->pf) return gms_fail(GMS_ERR_INVALID, "%s: not a gms_slam handle", who);
+    rc = slam_enter(s, who, SLAM_ALLOW_SHARD);
+    if (rc) return rc;
+    gms_map *m = s->map;
+    if (B < 1 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= B <= gms_params.max_beams beams", who);
+    if (on_device && ((uintptr_t)residuals & 1) != 0) return gms_fail(GMS_ERR_INVALID, "%s: the residuals must be 2-byte aligned", who);
+    HIPCHK(hipSetDevice(m->device));
+    rc = gms_slam_beam_table(s, who, behind, ahead, factors, 0);
+    if (rc) return rc;
+    const gms_beam *d_beams;
+    int32_t beam_stride;
+    rc = gms_request_scan(m, beams, B, on_device, &d_beams, &beam_stride);
+    if (rc) return rc;
+    HostStage st(m, on_device);
+    const size_t res_bytes = residuals ? (size_t)s->n * (size_t)B * sizeof(uint16_t) : 0;
+    const size_t p_res = st.part(res_bytes);
+    if (res_bytes) {
+        rc = st.open();
+        if (rc) return rc;
+    }
+    gms_launch_slam_beams(s, d_beams, B, gms_slam_bufs(s), nullptr, behind, ahead, 0, s->pf->d_w, s->pf->d_logw,
+                          residuals ? st.at(p_res, residuals) : nullptr);
+    HIPCHK(hipGetLastError());
+    pf_scored(s->pf, 0);                                                        // raw weights: the state gms_slam_update_local_dev leaves
+    if (!res_bytes) return GMS_OK;
+    st.fetch(residuals, p_res, res_bytes);
+    return st.finish(nullptr);
+}
+
+int gms_slam_score_beams(gms_slam *s, const gms_beam *beams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals) {
+    return slam_score_beams(s, beams, B, behind, ahead, factors, residuals, false);
+}
+int gms_slam_score_beams_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t behind, int32_t ahead, const double *factors,
+                             uint16_t *dev_residuals) {
+    return slam_score_beams(s, dev_beams, B, behind, ahead, factors, dev_residuals, true);
+}
+
+// update() weighs every particle by the model through its own map, in front of the scan's integration (slam_update_core); factors NULL: off
+int gms_slam_set_beam_model(gms_slam *s, int32_t behind, int32_t ahead, const double *factors, int32_t combine) {
+    REQUIRE(s, "gms_slam_set_beam_model: null handle");
+    int rc = factors ? gms_beam_model_check_for(behind, ahead, factors, "gms_slam_set_beam_model") : GMS_OK;
+    if (rc) return rc;
+    if (factors && combine != GMS_SLAM_BEAMS_MULTIPLY && combine != GMS_SLAM_BEAMS_REPLACE)
+        return gms_fail(GMS_ERR_INVALID, "gms_slam_set_beam_model: combine must be GMS_SLAM_BEAMS_MULTIPLY or GMS_SLAM_BEAMS_REPLACE, not %d", combine);
+    REQUIRE(s->map && s->pf, "gms_slam_set_beam_model: not a gms_slam handle");
+    rc = slam_enter(s, "gms_slam_set_beam_model", SLAM_ALLOW_SHARD | SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
+    if (!factors) { s->beam.on = 0; return GMS_OK; }
+    HIPCHK(hipSetDevice(s->map->device));
+    rc = gms_dev_alloc(&s->beam.d_wgt, (size_t)2 * s->n * sizeof(double), "gms_slam_set_beam_model", "the beam weights");
+    if (rc) return rc;
+    rc = gms_slam_beam_table(s, "gms_slam_set_beam_model", behind, ahead, factors, 1);
+    if (rc) return rc;
+    s->beam.behind = behind; s->beam.ahead = ahead; s->beam.combine = combine;
+    s->beam.on = 1;
     return GMS_OK;
 }
 

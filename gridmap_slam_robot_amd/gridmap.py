@@ -1836,6 +1836,29 @@ class _SlamHandle:
         prm = _align_params(None if params is True else params)
         check(load().gms_slam_set_align(self._h, C.byref(prm)))
 
+    @staticmethod
+    def _beam_table(who: str, factors, behind: int, ahead: int) -> np.ndarray:
+        f = np.ascontiguousarray(factors, dtype=np.float64)
+        if f.shape != (2, int(behind) + int(ahead) + 2):
+            raise ValueError(f"{who}: factors must be [2][behind + ahead + 2] = (2, {int(behind) + int(ahead) + 2}), not {f.shape}")
+        return f
+
+    def set_beam_model(self, factors, behind: int = 0, ahead: int = 0, combine="multiply"):
+        """gms_slam_set_beam_model: every update weighs each particle by the beam sensor model as well (gridmapslam.h "per-particle
+        beam sensor model") -- the walk of every beam through the particle's OWN map as it stands before this scan is integrated, at
+        the pose the particle is weighted at (after the motion sample, set_refine() and set_align(), where on).  factors [2][behind +
+        ahead + 2] as ParticleFilter.score_beams takes them (beam_model_factors() builds the usual mixture); combine: "multiply" -- raw
+        weight = probabilityOf * beam weight -- or "replace" -- the beam weight alone.  set_beam_model(None) switches it off (the
+        default); reset() keeps the setting."""
+        if factors is None or factors is False:
+            check(load().gms_slam_set_beam_model(self._h, 0, 0, None, 0))
+            return
+        modes = {"multiply": _lib.GMS_SLAM_BEAMS_MULTIPLY, "replace": _lib.GMS_SLAM_BEAMS_REPLACE}
+        if combine not in modes:
+            raise ValueError(f'set_beam_model: combine must be "multiply" or "replace", not {combine!r}')
+        f = self._beam_table("set_beam_model", factors, behind, ahead)
+        check(load().gms_slam_set_beam_model(self._h, int(behind), int(ahead), ptr(f), modes[combine]))
+
     def last_align(self) -> np.ndarray:
         """gms_slam_last_align: the records of the last aligned update, ALIGN_DTYPE [n] ([n_maps][n] on a batched handle); GmsError
         (GMS_ERR_STATE) before there is one.  Waits for the stream."""
@@ -2041,6 +2064,26 @@ class SLAMParticleMaps(_SlamHandle):
         out = _device_ptr("align_dev", "records_out", records_out, _lib.ALIGN_DTYPE.itemsize * self.num_particles, optional=True)
         check(load().gms_slam_align_dev(self._h, C.c_void_p(dev_beams), int(B), C.byref(prm), out))
         return records_out
+
+    def score_beams(self, z, factors, behind: int, ahead: int, residuals: bool = False):
+        """gms_slam_score_beams: the beam sensor model of every particle through ITS OWN map as logData stands (gridmapslam.h
+        "per-particle beam sensor model"; the table, the walk and the order of ParticleFilter.score_beams).  No pose and no map
+        changes.  Afterwards the filter holds RAW weights and log-weights (pf.get_weights(), pf.get_log_weights()), as a sharded
+        update leaves them: pf.normalize() finishes as update() does, and resample[_if]() work after that.  residuals=True returns
+        the table index per particle and beam, uint16 [n][B], and waits for the stream.  (Inside every update: set_beam_model().)"""
+        b = _beams_of(z).reshape(-1)
+        f = self._beam_table("score_beams", factors, behind, ahead)
+        res = np.empty((self.num_particles, len(b)), dtype=np.uint16) if residuals else None
+        check(load().gms_slam_score_beams(self._h, ptr(b), len(b), int(behind), int(ahead), ptr(f), None if res is None else ptr(res)))
+        return res
+
+    def score_beams_dev(self, dev_beams: int, B: int, factors, behind: int, ahead: int, residuals_out=None):
+        """score_beams() on device-resident beams [B]; factors stay a host array.  residuals_out: None, or a contiguous torch device
+        tensor of at least n * B 16-bit elements.  Runs on the handle's stream and synchronises nothing."""
+        f = self._beam_table("score_beams_dev", factors, behind, ahead)
+        out = _device_ptr("score_beams_dev", "residuals_out", residuals_out, 2 * self.num_particles * int(B), optional=True)
+        check(load().gms_slam_score_beams_dev(self._h, C.c_void_p(dev_beams), int(B), int(behind), int(ahead), ptr(f), out))
+        return residuals_out
 
     def _fetched(self, st) -> float:
         self.strongest, self.neff = st.strongest, st.neff

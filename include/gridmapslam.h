@@ -1239,6 +1239,50 @@ int gms_slam_set_align(gms_slam *s, const gms_align_params *params);
 int gms_slam_last_align(gms_slam *s, gms_align_record *records);
 int gms_slam_align_form(const gms_slam *s, int32_t *form);
 
+/* ---- per-particle beam sensor model: every particle of a gms_slam against its own map ----------------------------------------------------
+ * gms_slam's update weighs a particle by probabilityOf, the end-point model, on the field of the particle's own map.  In a
+ * Rao-Blackwellised filter that is where the beam model matters most: a particle that has drifted sees its old walls in front of, or
+ * behind, the measured end points, and the blurred field still gives a decent value next to a doubled wall, so a stale map survives
+ * resampling as easily as a consistent one.
+ *
+ * The definition is "beam sensor model" above, word for word -- THE TABLE, THE WALK, THE RESIDUAL, THE WEIGHTS, THE ORDER (256 strided
+ * partials, then the halving tree), gms_beam_model_check -- with ONE change: particle i's walk runs through particle i's own logData,
+ * as gms_slam_download_map(i) would return it at that moment.  The predicate is the same, logData > 0: 0, -0.0 and NaN are not
+ * occupied.  (The particles' class planes are thresholded for the likelihood field; they are not this predicate and are not used.)
+ *
+ * gms_slam_score_beams[_dev]: every particle the handle holds gets the weight and the log-weight the definition gives for its pose,
+ * pose and cached trig taken as they stand.  1 <= B <= max_beams; residuals [n][B] or NULL.  The call changes no pose, no map and no
+ * likelihoodData.  It leaves the filter with RAW weights, the state gms_slam_update_local_dev leaves: gms_pf_get_weights and
+ * gms_pf_get_log_weights read them, gms_pf_normalize on the filter of gms_slam_handles finishes as an update does, and
+ * gms_slam_resample_maps[_if] work unchanged after that.  A shard scores its own block.  A batched handle (n_maps > 1): GMS_ERR_STATE,
+ * nothing touched -- use gms_slam_set_beam_model there.  Checked before anything is enqueued (GMS_ERR_INVALID, the outputs untouched):
+ * NULL handle or beams, gms_beam_model_check, B, and in the _dev form the residuals' 2-byte alignment.  `factors` is a HOST pointer in
+ * both forms.  The host form synchronises only to read the residuals back; _dev synchronises nothing.
+ *
+ * gms_slam_set_beam_model: the arguments are checked (gms_beam_model_check; combine one of the two below) and the table is copied
+ * with its logarithms.  From then on every update of the handle -- gms_slam_update_per_particle[_dev], gms_slam_update_batch[_dev],
+ * gms_slam_update_local[_dev], both frame calls -- applies the model: each particle is weighted through its own map as it stands BEFORE
+ * this scan is integrated (behind it every particle would find its own end cell occupied), at the pose it is weighted at -- the pose
+ * after the motion sample, the lattice refinement and the alignment, in that order, where each is on.  The raw weight and the raw
+ * log-weight the update writes are then combined: MULTIPLY -- weight = probabilityOf(...) * beam weight, one double multiply, not
+ * contracted, log-weight = the sum of the two; REPLACE -- both are the beam model's own.  skipUpdate (|dTheta| > 30 degrees) skips
+ * only the map update, as without the model.  B == 0 (a batched handle: a filter whose count is 0) leaves the raw weight as the update
+ * gives it.  On a batched handle each filter is scored with its own scan and count.  factors NULL: off, the default; an update then
+ * issues exactly the launches it issued before.  gms_slam_reset keeps the setting, as it keeps gms_slam_set_align's.
+ *
+ * How: one workgroup of 256 lanes per particle.  No packed plane of a particle's map exists in memory and none is written: the
+ * workgroup forms the box of its rays, pads it by ahead + 1, and packs that window of `logData > 0` straight from the particle's
+ * logData into LDS -- a wavefront reads 64 consecutive cells of a row and its ballot is two words of the window (64 KiB at most).  A
+ * larger window, or GMS_CAST_WALK=mem at creation, reads logData[y W + x] > 0 from memory at every step; all forms give the same bits.
+ * Inside an update a second kernel, one lane per particle, combines the weights behind the update's own and in front of the
+ * normalisation. */
+#define GMS_SLAM_BEAMS_MULTIPLY 0   /* raw weight = probabilityOf(...) * beam weight (one double multiply, not contracted) */
+#define GMS_SLAM_BEAMS_REPLACE  1   /* raw weight = beam weight */
+int gms_slam_score_beams(gms_slam *s, const gms_beam *beams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals);
+int gms_slam_score_beams_dev(gms_slam *s, const gms_beam *dev_beams, int32_t B, int32_t behind, int32_t ahead, const double *factors,
+                             uint16_t *dev_residuals);
+int gms_slam_set_beam_model(gms_slam *s, int32_t behind, int32_t ahead, const double *factors, int32_t combine);  /* factors NULL: off (default) */
+
 /* ---- trajectory rollouts: which velocity command can be sent without hitting something ---------------------------------------------
  * The inner loop of a local planner (dynamic window, lattice primitives): K candidate arcs, each sampled at T steps, the robot's
  * footprint tested against the inflated obstacle plane at every step, and the clearance and cost-to-go fields read along the way.  This

@@ -509,6 +509,16 @@ public:
     }
     /** the records [n] of the last aligned update (throws before there is one); waits for the stream */
     void lastAlign(gms_align_record *records) { check(gms_slam_last_align(h_, records)); }
+    /** the beam sensor model of every particle through ITS OWN map (gridmapslam.h "per-particle beam sensor model"): raw weights and
+     *  log-weights as update_local leaves them, no pose and no map changes; factors [2][behind + ahead + 2] host doubles, residuals [n][B] or null */
+    void score_beams(const Observation &z, const double *factors, int32_t behind, int32_t ahead, uint16_t *residuals = nullptr) {
+        check(gms_slam_score_beams(h_, z.getMeasurements().data(), z.getNumberOfMeasurements(), behind, ahead, factors, residuals));
+    }
+    /** every update weighs each particle by that model as well, through its map as it stands before the scan goes into it; combine:
+     *  GMS_SLAM_BEAMS_MULTIPLY or GMS_SLAM_BEAMS_REPLACE; factors null: off */
+    void set_beam_model(const double *factors, int32_t behind = 0, int32_t ahead = 0, int32_t combine = GMS_SLAM_BEAMS_MULTIPLY) {
+        check(gms_slam_set_beam_model(h_, behind, ahead, factors, combine));
+    }
     /** update(z, u) (:80-131); returns Neff. seed / sequence select the motion model's variates (one sequence per frame). */
     double update(const Observation &z, const Odometry &u, uint64_t seed, uint64_t sequence, bool sampleMotion = true) {
         gms_pf_stats st{};
