@@ -214,6 +214,16 @@ class GmsWarpStats(C.Structure):
     _fields_ = [("pair", (C.c_int64 * 3) * 3), ("n_outside", C.c_int64)]
 
 
+class GmsCensus(C.Structure):
+    """gms_census: a census of a gms_slam's particle maps (gridmapslam.h "census of the particles' maps"), 16 bytes"""
+    _fields_ = [("min_known", C.c_int32), ("filter", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GmsCensusTotals(C.Structure):
+    """gms_census_totals: cells by consensus class, contested cells and the minority sum, 32 bytes"""
+    _fields_ = [("cls", C.c_uint32 * 3), ("contested", C.c_uint32), ("minority", C.c_uint64), ("n", C.c_uint32), ("min_known", C.c_uint32)]
+
+
 GAIN_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsGainRec._fields_])     # gms_gain_rec
 assert GAIN_DTYPE.itemsize == C.sizeof(GmsGainRec) == 32
 ROLLOUT_STEP_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("c", "<f4"), ("s", "<f4")])     # gms_rollout_step
@@ -231,6 +241,13 @@ GMS_ROUTE_NO_PATH, GMS_ROUTE_BROKEN, GMS_ROUTE_CELLS_CUT, GMS_ROUTE_WAYPOINTS_CU
 WARP_STATS_DTYPE = np.dtype([("pair", "<i8", (3, 3)), ("n_outside", "<i8")])     # gms_warp_stats
 assert WARP_STATS_DTYPE.itemsize == C.sizeof(GmsWarpStats) == 80 and C.sizeof(GmsWarp) == 64
 GMS_WARP_COMPARE, GMS_WARP_REPLACE, GMS_WARP_ADD, GMS_WARP_FILL = 0, 1, 2, 3                     # gms_warp.op
+CENSUS_TOTALS_DTYPE = np.dtype([("cls", "<u4", (3,)), ("contested", "<u4"), ("minority", "<u8"), ("n", "<u4"), ("min_known", "<u4")])     # gms_census_totals
+CENSUS_AGREE_DTYPE = np.dtype([("pair", "<u4", (3, 3)), ("zero", "<u4")])     # one particle's record of the agreement
+assert CENSUS_TOTALS_DTYPE.itemsize == C.sizeof(GmsCensusTotals) == 32 and CENSUS_AGREE_DTYPE.itemsize == 40 and C.sizeof(GmsCensus) == 16
+GMS_CENSUS_WRITE_MAP = 1                                                                         # gms_census.flags
+# the cells a workgroup of the counting pass takes, the particles of its chunk, the cells a workgroup of the agreement pass takes
+# (gms_census_geometry() of the library as built)
+GMS_CENSUS_TILE, GMS_CENSUS_CHUNK, GMS_CENSUS_AGREE = 512, 32, 4096
 LOCATE_DTYPE = np.dtype([(n, "<i4") for n, _ in GmsLocateRec._fields_])     # gms_locate_rec
 assert LOCATE_DTYPE.itemsize == C.sizeof(GmsLocateRec) == 16 and C.sizeof(GmsLocate) == 48
 GMS_LOCATE_SKIP = -32768
@@ -526,6 +543,11 @@ def load() -> C.CDLL:
     sig("gms_map_warp_dev", C.c_int, vp, i32, vp, i32, wp, vp)
     sig("gms_slam_warp", C.c_int, vp, i32, i32, vp, i32, wp, vp, vp)
     sig("gms_slam_warp_dev", C.c_int, vp, i32, i32, vp, i32, wp, vp, vp)
+    cp = C.POINTER(GmsCensus)
+    sig("gms_census_check", C.c_int, cp, i32, i32)
+    sig("gms_census_geometry", C.c_int, vp, vp, vp)
+    sig("gms_slam_census", C.c_int, vp, cp, vp, vp, vp, vp)
+    sig("gms_slam_census_dev", C.c_int, vp, cp, vp, vp, vp, vp)
     fp = C.POINTER(GmsFrontiers)
     sig("gms_frontiers_size", C.c_int, fp, vp, vp, vp)
     sig("gms_map_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))

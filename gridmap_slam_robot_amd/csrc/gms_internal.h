@@ -476,6 +476,9 @@ struct gms_slam {
         int32_t behind, ahead;      // ... with this table (checked when it was set)
         int32_t combine;            // GMS_SLAM_BEAMS_MULTIPLY / _REPLACE
     } beam;
+    // the census of the particles' maps (gms_slam_census; gms_census.hip): the count field [cells] uint32, then the consensus bytes
+    // [cells] of a call that passes none; allocated by the first call (the map's size never changes)
+    uint32_t *d_census;
 };
 
 // the history of a gms_slam as its kernels see it (gms_slam_set_history): a ring of cap rows, update number t in row t % cap
@@ -704,7 +707,7 @@ struct HostStage {
     bool on_device;
     unsigned char *base = nullptr;
     size_t total = 0;
-    struct { void *dst; size_t part, bytes; } out[3];
+    struct { void *dst; size_t part, bytes; } out[4];
     int32_t n_out = 0;
     HostStage(gms_map *mm, bool dev) : m(mm), on_device(dev) {}
     size_t part(size_t bytes) { const size_t at = 16 + total; total += (bytes + 15) & ~(size_t)15; return at; }
@@ -812,6 +815,16 @@ void gms_launch_slam_weight_combine(gms_slam *s, int32_t B, const SlamBatch *bat
 // planes), bit 1 likelihoodData; d_idx_keep (may be NULL) receives the indices for a likelihoodData copy that is still owed
 void gms_launch_slam_gather(gms_pf *pf, const SlamBufs &sb, int32_t what, const int32_t *d_idx, int32_t *d_idx_keep, int64_t code_words);
 void gms_launch_slam_combine(gms_map *dst, const SlamBufs &sb, int32_t n_filters);   // filter f's particles into map f of dst
+// the census of filter `filter`'s maps (gms_census.hip).  count: a workgroup per GMS_CENSUS_TILE cells and GMS_CENSUS_CHUNK particles adds
+// `free | occupied << 16` into d_field [cells], which the caller has zeroed; consensus: d_field into the bytes, map f's logData (+-1.0 /
+// +0.0) and the totals (zeroed by the caller), each where non-NULL; agree: a workgroup per particle and GMS_CENSUS_AGREE cells adds the
+// class pairs into d_agree [n_per][10], zeroed by the caller
+#define GMS_CENSUS_TILE 512
+#define GMS_CENSUS_CHUNK 32
+#define GMS_CENSUS_AGREE 4096
+void gms_launch_census_count(gms_map *m, const SlamBufs &sb, int32_t filter, uint32_t *d_field);
+void gms_launch_census_consensus(gms_map *m, const uint32_t *d_field, int32_t n, int32_t min_known, uint8_t *d_consensus, double *d_log, gms_census_totals *d_totals);
+void gms_launch_census_agree(gms_map *m, const SlamBufs &sb, int32_t filter, const uint8_t *d_consensus, uint32_t *d_agree);
 // a view of one particle's map: which >= 0 the particle, which < 0 the strongest of `filter` by d_stats[filter] (picked on the device).
 // field: where a likelihood view reads (ignored by a log view) -- SLAM_FIELD_IN_MEMORY the current generation, SLAM_FIELD_OWED_COPY the
 // source d_idx_lik names in the other one where the last resample() drew.  d_shown (may be NULL) receives the handle-wide index.

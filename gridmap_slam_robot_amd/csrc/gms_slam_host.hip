@@ -88,6 +88,7 @@ int gms_slam_destroy(gms_slam *s) {
     hipFree(s->d_plan);
     hipFree(s->d_batch);
     hipFree(s->d_align_rec);
+    hipFree(s->d_census);
     hipFree(s->beam.d_tab); hipFree(s->beam.d_wgt);
     if (s->beam.ring_ready) gms_ring_free(s->beam.ring);
     slam_hist_free(s);
@@ -903,6 +904,84 @@ int gms_slam_combined(gms_slam *s) {
     map_log_replaced(m);
     HIPCHK(hipGetLastError());
     return gms_map_build_likelihood(m);                                                       // :457
+}
+
+// ---- the census of the particles' maps (gridmapslam.h; the kernels are gms_census.hip's) ----
+static int census_check(const gms_census *c, int32_t n_per, int32_t n_filters, const char *who) {
+    if (!c) return gms_fail(GMS_ERR_INVALID, "%s: null request", who);
+    if (n_per < 1 || n_per > 65535) return gms_fail(GMS_ERR_INVALID, "%s: %d particles per filter (1 .. 65535: a count is 16 bits)", who, n_per);
+    if (n_filters < 1) return gms_fail(GMS_ERR_INVALID, "%s: %d filters", who, n_filters);
+    if (c->min_known < 1 || c->min_known > n_per)
+        return gms_fail(GMS_ERR_INVALID, "%s: gms_census.min_known must be in 1 .. %d (the particles of a filter), not %d", who, n_per, c->min_known);
+    if (c->filter < 0 || c->filter >= n_filters)
+        return gms_fail(GMS_ERR_INVALID, "%s: gms_census.filter must be in 0 .. %d, not %d", who, n_filters - 1, c->filter);
+    if (c->flags & ~GMS_CENSUS_WRITE_MAP) return gms_fail(GMS_ERR_INVALID, "%s: gms_census.flags holds bits other than GMS_CENSUS_WRITE_MAP", who);
+    if (c->reserved != 0) return gms_fail(GMS_ERR_INVALID, "%s: gms_census.reserved must be 0", who);
+    return GMS_OK;
+}
+
+// The checks first, nothing touched.  Then the handle's own map settled where it is written, the field zeroed and counted, the pass
+// over the field where anything but the counts is asked for, the pass over the maps where the records are.
+static int slam_census(gms_slam *s, const gms_census *c, uint16_t *counts, uint8_t *consensus, uint32_t *agree, gms_census_totals *totals, bool on_device,
+                       const char *who) {
+    int rc = slam_enter(s, who, SLAM_ALLOW_BATCHED);
+    if (rc) return rc;
+    rc = census_check(c, s->n_per, s->n_filters, who);
+    if (rc) return rc;
+    const bool write_map = (c->flags & GMS_CENSUS_WRITE_MAP) != 0;
+    if (!counts && !consensus && !agree && !totals && !write_map)
+        return gms_fail(GMS_ERR_INVALID, "%s: nothing asked for (every output NULL and no GMS_CENSUS_WRITE_MAP)", who);
+    if (on_device && ((((uintptr_t)counts | (uintptr_t)agree) & 3) != 0 || ((uintptr_t)totals & 7) != 0))
+        return gms_fail(GMS_ERR_INVALID, "%s: counts and agree must be 4-byte aligned, totals 8-byte aligned", who);
+    gms_map *m = s->map;
+    HIPCHK(hipSetDevice(m->device));
+    const size_t cells = (size_t)m->gd.cells;
+    rc = gms_dev_alloc(&s->d_census, cells * 5, who, "the count field and the consensus bytes");
+    if (rc) return rc;
+    if (write_map) gms_map_settle(m);                                                          // what gms_map_upload_log opens with
+    const size_t agree_bytes = agree ? (size_t)s->n_per * 10 * sizeof(uint32_t) : 0;
+    HostStage st(m, on_device);
+    const size_t p_counts = st.part(counts ? cells * 4 : 0), p_cons = st.part(consensus ? cells : 0), p_agree = st.part(agree_bytes),
+                 p_totals = st.part(totals ? sizeof(gms_census_totals) : 0);
+    rc = st.open();
+    if (rc) return rc;
+    // the field is the caller's counts where they are asked for: {fr, oc} as uint16 pairs ARE the little-endian count words
+    uint32_t *d_field = counts ? reinterpret_cast<uint32_t *>(st.at(p_counts, counts)) : s->d_census;
+    uint8_t *d_cons = consensus ? st.at(p_cons, consensus) : agree ? reinterpret_cast<uint8_t *>(s->d_census + cells) : nullptr;
+    uint32_t *d_agree = agree ? st.at(p_agree, agree) : nullptr;
+    gms_census_totals *d_totals = totals ? st.at(p_totals, totals) : nullptr;
+    const SlamBufs sb = gms_slam_bufs(s);
+    HIPCHK(hipMemsetAsync(d_field, 0, cells * 4, m->stream));
+    gms_launch_census_count(m, sb, c->filter, d_field);
+    if (d_cons || d_totals || write_map) {
+        if (d_totals) HIPCHK(hipMemsetAsync(d_totals, 0, sizeof(gms_census_totals), m->stream));
+        gms_launch_census_consensus(m, d_field, s->n_per, c->min_known, d_cons, write_map ? m->d_log + (size_t)c->filter * cells : nullptr, d_totals);
+    }
+    if (d_agree) {
+        HIPCHK(hipMemsetAsync(d_agree, 0, agree_bytes, m->stream));
+        gms_launch_census_agree(m, sb, c->filter, d_cons, d_agree);
+    }
+    HIPCHK(hipGetLastError());
+    if (write_map) map_log_replaced(m);
+    if (counts) st.fetch(counts, p_counts, cells * 4);
+    if (consensus) st.fetch(consensus, p_cons, cells);
+    if (agree) st.fetch(agree, p_agree, agree_bytes);
+    if (totals) st.fetch(totals, p_totals, sizeof(gms_census_totals));
+    return st.finish(nullptr);
+}
+
+int gms_census_check(const gms_census *c, int32_t n_per, int32_t n_filters) { return census_check(c, n_per, n_filters, "gms_census_check"); }
+int gms_census_geometry(int32_t *tile_cells, int32_t *chunk_particles, int32_t *agree_cells) {
+    if (tile_cells) *tile_cells = GMS_CENSUS_TILE;
+    if (chunk_particles) *chunk_particles = GMS_CENSUS_CHUNK;
+    if (agree_cells) *agree_cells = GMS_CENSUS_AGREE;
+    return GMS_OK;
+}
+int gms_slam_census(gms_slam *s, const gms_census *c, uint16_t *counts, uint8_t *consensus, uint32_t *agree, gms_census_totals *totals) {
+    return slam_census(s, c, counts, consensus, agree, totals, false, "gms_slam_census");
+}
+int gms_slam_census_dev(gms_slam *s, const gms_census *c, uint16_t *dev_counts, uint8_t *dev_consensus, uint32_t *dev_agree, gms_census_totals *dev_totals) {
+    return slam_census(s, c, dev_counts, dev_consensus, dev_agree, dev_totals, true, "gms_slam_census_dev");
 }
 
 // A view of one particle's map (gridmapslam.h "map views"): GridMapApp.render's "strongest" and "chosen" cases (GridMapApp.java:374-393)

@@ -24,7 +24,8 @@ from . import _lib
 from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, ptr
 
 __all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
-           "cells_of_poses", "descend", "route_points", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance", "warp_agreement", "map_as_scan"]
+           "cells_of_poses", "descend", "route_points", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance", "warp_agreement", "map_as_scan",
+           "census_entropy", "census_outliers"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -484,6 +485,29 @@ def warp_agreement(stats) -> dict:
     pair = np.asarray(stats["pair"], dtype=np.int64).reshape(3, 3)
     return {"overlap": int(pair[1:, 1:].sum()), "agree": int(pair[1, 1] + pair[2, 2]), "conflict": int(pair[1, 2] + pair[2, 1]),
             "gained": int(pair[0, 1] + pair[0, 2]), "outside": int(np.asarray(stats["n_outside"]).sum())}
+
+
+def census_entropy(counts, n: int) -> np.ndarray:
+    """The per-cell Shannon entropy in bits of the three-way split of a filter's n particles that a census counted (counts [H][W][2]
+    = {fr, oc}): H(fr / n, oc / n, (n - fr - oc) / n), 0 where all particles agree, log2(3) where they split evenly.  Plain numpy on
+    the host."""
+    c = np.asarray(counts).astype(np.float64)
+    if c.shape[-1] != 2:
+        raise ValueError("census_entropy: counts must be [...][2] = {fr, oc}")
+    n = int(n)
+    p = np.stack([c[..., 0], c[..., 1], n - c[..., 0] - c[..., 1]], axis=-1) / n
+    if n < 1 or (p < 0).any():
+        raise ValueError("census_entropy: n must be positive and at least fr + oc in every cell")
+    terms = np.zeros_like(p)
+    np.log2(p, out=terms, where=p > 0)
+    return 0.0 - (p * terms).sum(axis=-1)
+
+
+def census_outliers(agree) -> np.ndarray:
+    """Per particle the cells where it contradicts the consensus of a census (CENSUS_AGREE_DTYPE records: pair[the particle's
+    class][the consensus class]): pair[1][2] + pair[2][1], free against occupied plus occupied against free."""
+    pair = np.asarray(agree["pair"], dtype=np.int64)
+    return pair[..., 1, 2] + pair[..., 2, 1]
 
 
 def map_as_scan(log, position, resolution: float, max_beams: int = 4096) -> np.ndarray:
@@ -1973,6 +1997,36 @@ class _SlamHandle:
         return _query_frontiers(self._src("frontiers", which, filter), min_size, inflate, cost, rect, labels, cap,
                                 dev=(records_out, labels_out, shown_out) if dev else None)
 
+    def _census_request(self, min_known: int, filter: int, write_map: bool) -> _lib.GmsCensus:
+        c = _lib.GmsCensus(int(min_known), int(filter), _lib.GMS_CENSUS_WRITE_MAP if write_map else 0, 0)
+        check(load().gms_census_check(C.byref(c), self.num_particles, int(self.params.n_maps)))
+        return c
+
+    def _census(self, filter: int, min_known: int, counts: bool, consensus: bool, agree: bool, totals: bool, write_map: bool) -> dict:
+        """gms_slam_census: the outputs asked for, by name"""
+        c = self._census_request(min_known, filter, write_map)
+        out = {}
+        if counts:
+            out["counts"] = np.empty((self.H, self.W, 2), dtype=np.uint16)
+        if consensus:
+            out["consensus"] = np.empty((self.H, self.W), dtype=np.uint8)
+        if agree:
+            out["agree"] = np.empty(self.num_particles, dtype=_lib.CENSUS_AGREE_DTYPE)
+        if totals:
+            out["totals"] = np.zeros((), dtype=_lib.CENSUS_TOTALS_DTYPE)
+        check(load().gms_slam_census(self._h, C.byref(c), *(ptr(out[k]) if k in out else None for k in ("counts", "consensus", "agree", "totals"))))
+        return out
+
+    def _census_dev(self, filter: int, min_known: int, counts, consensus, agree, totals, write_map: bool):
+        """gms_slam_census_dev on torch device tensors (None: not wanted)"""
+        c = self._census_request(min_known, filter, write_map)
+        cells = self.W * self.H
+        check(load().gms_slam_census_dev(self._h, C.byref(c), _device_ptr("census_dev", "counts", counts, 4 * cells, optional=True),
+                                         _device_ptr("census_dev", "consensus", consensus, cells, itemsize=1, optional=True),
+                                         _device_ptr("census_dev", "agree", agree, _lib.CENSUS_AGREE_DTYPE.itemsize * self.num_particles, optional=True),
+                                         _device_ptr("census_dev", "totals", totals, _lib.CENSUS_TOTALS_DTYPE.itemsize, optional=True)))
+        return counts, consensus, agree, totals
+
     def set_history(self, capacity: int):
         """gms_slam_set_history: keep every particle's pose and parent slot of the last `capacity` updates on the device, through
         resampling (0: off, the memory freed).  reset() clears the history and keeps it on.  Refused on a shard of a filter."""
@@ -2263,6 +2317,21 @@ class SLAMParticleMaps(_SlamHandle):
         check(load().gms_slam_combined(self._h))
         return self.grid_map.download_log()
 
+    def census(self, min_known: int = 1, counts: bool = True, consensus: bool = True, agree: bool = False, totals: bool = True,
+               write_map: bool = False) -> dict:
+        """The census of the particles' maps (gridmapslam.h "census of the particles' maps"): what the ENSEMBLE says, cell by cell.
+        A dict of the outputs asked for -- "counts" uint16 [H][W][2] = {particles that hold the cell free, occupied}; "consensus" uint8
+        [H][W], 0 unknown where fewer than min_known particles know the cell, else 2 occupied where oc >= fr, else 1 free; "totals" a
+        CENSUS_TOTALS_DTYPE record; "agree" CENSUS_AGREE_DTYPE [n], every particle's pair[its class][the consensus class] over all
+        cells (census_outliers()).  write_map: the consensus is also written, as +1.0 / -1.0 / +0.0, to grid_map's own logData, where
+        every GridMap query then works on it.  The map uncertainty: census_entropy(counts, n).  The filter is only read."""
+        return self._census(0, min_known, counts, consensus, agree, totals, write_map)
+
+    def census_dev(self, min_known: int = 1, counts=None, consensus=None, agree=None, totals=None, write_map: bool = False):
+        """census() into torch device tensors (None: not wanted) -- counts of W * H * 4 bytes and agree of n * 40 bytes, 4-byte
+        aligned; consensus of W * H bytes; totals of 32 bytes, 8-byte aligned -- on the handle's stream: nothing is synchronised."""
+        return self._census_dev(0, min_known, counts, consensus, agree, totals, write_map)
+
     def trace_scan(self, i: int, z, cap: int = 0):
         """(cells [B][cap][2], classes [B][cap], counts [B]): the cell walk of integrateObservation for particle i at its current pose
         as the update kernel walks and classifies it (prior-class visits included), in walk order; nothing is written to a map"""
@@ -2517,6 +2586,17 @@ class SLAMParticleMapsBatch(_SlamHandle):
         check(load().gms_slam_combined(self._h))
         out = self.grid_map.download_likelihood() if likelihood else self.grid_map.download_log()
         return out.reshape(self.num_filters, self.H, self.W)[int(f)]
+
+    def census(self, filter: int = 0, min_known: int = 1, counts: bool = True, consensus: bool = True, agree: bool = False, totals: bool = True,
+               write_map: bool = False) -> dict:
+        """SLAMParticleMaps.census over filter `filter`'s particles alone; write_map writes map `filter` of grid_map, the others stay"""
+        self._local(filter)
+        return self._census(filter, min_known, counts, consensus, agree, totals, write_map)
+
+    def census_dev(self, filter: int = 0, min_known: int = 1, counts=None, consensus=None, agree=None, totals=None, write_map: bool = False):
+        """SLAMParticleMaps.census_dev for filter `filter`"""
+        self._local(filter)
+        return self._census_dev(filter, min_known, counts, consensus, agree, totals, write_map)
 
     def trace_scan(self, f: int, i: int, z, cap: int = 0):
         return self._trace_scan(self._slot(f, i), z, cap)

@@ -1588,6 +1588,67 @@ int gms_slam_warp(gms_slam *s, int32_t which, int32_t filter, gms_map *dst, int3
 int gms_slam_warp_dev(gms_slam *s, int32_t which, int32_t filter, gms_map *dst, int32_t mi_dst, const gms_warp *w, gms_warp_stats *dev_stats,
                       int32_t *dev_shown);
 
+/* ---- census of the particles' maps: what the ENSEMBLE of a gms_slam's maps says, cell by cell ------------------------------------------
+ * Every other query of a gms_slam looks at one particle's map; gms_slam_combined looks at all of them, but as the reference's
+ * noisy-OR picture (a never-observed cell is p = 0.5 in every particle and comes out "occupied").  The census is the unweighted vote
+ * of one filter's particles -- after a resample the population itself carries the weights -- : a majority map to plan on that does
+ * not jump when the strongest particle changes, the per-cell split that is the map uncertainty, and every particle's distance from the
+ * consensus.  This library's own definition (the reference has no such method); everything is integer arithmetic and every output is
+ * unique whatever the scheduling.
+ *
+ * THE CLASS      of a cell of a particle's logData l, the predicates of the planes, the casts and the warps: free (1) l < 0, occupied
+ *                (2) l > 0, unknown (0) everything else -- +0.0, -0.0, NaN.  -inf is free, +inf occupied, denormals count by sign.
+ * THE COUNTS     for filter f of the handle (n particles per filter, n <= 65535) and every cell of the whole map:  fr = how many of
+ *                its particles hold the cell free, oc = how many occupied.  counts is uint16 [H][W][2] = {fr, oc}; equivalently one
+ *                little-endian uint32 per cell, fr in the low half, oc in the high half.
+ * THE CONSENSUS  of a cell under min_known in [1, n]:  unknown (0) if fr + oc < min_known;  else occupied (2) if oc >= fr -- a tie
+ *                goes to the obstacle, the conservative side for planning --;  else free (1).  consensus is uint8 [H][W].
+ * THE TOTALS     gms_census_totals:  cls[k] the cells of consensus class k;  contested the cells with fr > 0 and oc > 0;  minority
+ *                the sum over all cells of min(fr, oc);  n and min_known as the call took them.
+ * THE AGREEMENT  one record of ten uint32 per particle of the filter:  pair[3][3], indexed [the particle's class][the consensus
+ *                class], counted over all cells of the map, and a tenth word that is 0.  The nine entries sum to W * H.  A depleted
+ *                filter shows as identical records, a drifted particle as a large pair[1][2] + pair[2][1].
+ * WRITE_MAP      GMS_CENSUS_WRITE_MAP in flags: the consensus is also written to logData of the handle's own map (a batched handle:
+ *                map f), as gms_slam_combined writes there -- +1.0 occupied, -1.0 free, +0.0 unknown -- and the map is left exactly
+ *                as gms_map_upload_log of that array would leave it (the deferred pass first, likelihoodData until the next build,
+ *                planes and tables invalidated).  Every gms_map_* query then works on the consensus through gms_slam_handles.
+ *
+ * Any output may be NULL; all of them NULL without WRITE_MAP is refused.  Refused with GMS_ERR_INVALID and nothing touched: a NULL
+ * handle or request, min_known outside [1, n], filter outside [0, n_filters), flag bits other than GMS_CENSUS_WRITE_MAP, a non-zero
+ * reserved word, nothing asked for, and -- _dev -- counts or agree not 4-byte aligned or totals not 8-byte aligned.  GMS_ERR_STATE on
+ * a shard of a filter (gms_slam_create_shard): the counts of shards are additive, so a sharded form is one all-reduce of the count
+ * field away, and it is not built.  The call reads the current generation of the filter's logData (which flips on resampling,
+ * picked on the device) and changes nothing of the filter: poses, weights, maps, class planes, field state and history stay.
+ * The count field and, where the caller passes none, the consensus bytes are scratch of the handle, allocated by the first call.
+ *
+ * How: a counting pass that streams the filter's n x cells doubles once -- a workgroup takes a tile of cells and a chunk of
+ * particles (gms_census_geometry), a lane a pair of cells by one 16-byte load per particle where the pair is 16-byte aligned, sums
+ * `free | occupied << 16` in a register and adds its chunk with one integer atomic per non-zero cell word into the zeroed field --;
+ * a pass over the field that writes the consensus and forms the totals by ballots; and, only where agree is asked for, a second pass
+ * over the maps against the consensus bytes, nine ballots per cell, one atomic per counter and workgroup. */
+enum { GMS_CENSUS_WRITE_MAP = 1 };
+typedef struct gms_census {         /* 16 bytes */
+    int32_t min_known;              /*  0: cells that fewer particles than this have seen stay unknown; 1 .. n */
+    int32_t filter;                 /*  4: the filter of a batched handle; 0 on a plain one */
+    int32_t flags;                  /*  8: GMS_CENSUS_WRITE_MAP */
+    int32_t reserved;               /* 12: must be 0 */
+} gms_census;
+typedef struct gms_census_totals {  /* 32 bytes */
+    uint32_t cls[3];                /*  0: cells by consensus class: unknown, free, occupied */
+    uint32_t contested;             /* 12: cells with fr > 0 and oc > 0 */
+    uint64_t minority;              /* 16: sum over all cells of min(fr, oc) */
+    uint32_t n, min_known;          /* 24: as the call took them */
+} gms_census_totals;
+/* Pure host code: every bound of the request for a handle of n_filters filters of n_per particles each, with the reason. */
+int gms_census_check(const gms_census *c, int32_t n_per, int32_t n_filters);
+/* Pure host code: the cells a workgroup of the counting pass takes, the particles of its chunk, and the cells a workgroup of the
+ * agreement pass takes (any may be NULL): where the kernels' edges are, for tests and for sizing. */
+int gms_census_geometry(int32_t *tile_cells, int32_t *chunk_particles, int32_t *agree_cells);
+/* counts uint16 [H][W][2], consensus uint8 [H][W], agree uint32 [n][10], totals: host memory; synchronises the handle's stream. */
+int gms_slam_census(gms_slam *s, const gms_census *c, uint16_t *counts, uint8_t *consensus, uint32_t *agree, gms_census_totals *totals);
+/* The same into device memory on the handle's stream: nothing is waited for and nothing read back. */
+int gms_slam_census_dev(gms_slam *s, const gms_census *c, uint16_t *dev_counts, uint8_t *dev_consensus, uint32_t *dev_agree, gms_census_totals *dev_totals);
+
 /* ---- device-resident inputs ---------------------------------------------------------------------
  * The same entry points for callers whose scans / poses already live in HBM (a trace staged once, a
  * torch tensor, the output of a device-side motion model).  dev_beams is [n_maps][B] gms_beam,

@@ -652,6 +652,21 @@ public:
         if (shown) *shown = picked;
         return st;
     }
+    /** The census of the particles' maps (gridmapslam.h "census of the particles' maps"): the totals, and -- each where non-null --
+     *  counts resized to W * H * 2 {fr, oc}, consensus to W * H classes, agree to n * 10 words (pair[3][3] and a zero per particle).
+     *  writeMap: the consensus also goes to the handle's own map as +1.0 / -1.0 / +0.0.  The filter is only read */
+    gms_census_totals census(int minKnown = 1, std::vector<uint16_t> *counts = nullptr, std::vector<uint8_t> *consensus = nullptr,
+                             std::vector<uint32_t> *agree = nullptr, bool writeMap = false, int filter = 0) {
+        int32_t n = 0, W = 0, H = 0;
+        check(gms_slam_count(h_, &n, &W, &H));
+        const gms_census c{minKnown, filter, writeMap ? GMS_CENSUS_WRITE_MAP : 0, 0};
+        if (counts) counts->assign((size_t)W * (size_t)H * 2, 0);
+        if (consensus) consensus->assign((size_t)W * (size_t)H, 0);
+        if (agree) agree->assign((size_t)n * 10, 0);
+        gms_census_totals t{};
+        check(gms_slam_census(h_, &c, counts ? counts->data() : nullptr, consensus ? consensus->data() : nullptr, agree ? agree->data() : nullptr, &t));
+        return t;
+    }
     /** Trajectory rollouts in particle `which`'s own map (GridMap::rollout's records); no poses: ONE start pose, the shown particle's
      *  own, read on the device.  *shown (may be null) receives the particle in whose map the arcs were rolled */
     std::vector<gms_rollout_rec> rollout(const std::vector<Pose> &poses, const gms_rollout &req, const std::vector<gms_rollout_step> &arcs, int K, int T,
