@@ -28,8 +28,10 @@
 // ---- A: normalise + pack  |  ray cast at the weighted pose --------------------------------------------------
 // The ray-cast workgroups fold the weighted pose from the partial vector themselves (the arithmetic of
 // fold_stats: SLAM.java:165-178), because the workgroup that publishes it runs beside them.
-template <bool LOGNORM>   // (the log-normalising form is a separate instantiation: the default kernel is exactly what it was -- as one kernel
+template <bool LOGNORM, bool WAVE>   // (the log-normalising form is a separate instantiation: the default kernel is exactly what it was -- as one kernel
                           // with a uniform branch its ray blocks ran 1.1 us longer, measured A/B on one box)
+                          // WAVE: `partials` holds one row per WAVEFRONT (k_partials_wave), (n + 63) / 64 of them: a lane of either fold adds its
+                          // block's four rows first, as k_partials' LDS combine would have (fold_sum).  Plain normalisation only.
 __global__ void __launch_bounds__(256)
 k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ partials, int64_t nblk_global, int32_t B,
                int32_t nw_max, uint32_t n_ray_blocks, uint32_t n_norm_blocks, uint32_t n_near_blocks, int32_t n,
@@ -46,6 +48,7 @@ k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ pa
     // logw_lognorm != nullptr: the partial vector is block-relative (gms_pf_set_log_normalize, block_partials)
     // res_ticket != nullptr: the last normalise workgroup folds Neff and scans the chunk offsets for k_lik_resample (resample_prefix_last),
     // in the shadow of the ray cast
+    static_assert(!(LOGNORM && WAVE), "a log-normalising pass needs its block's reference: block rows");
     GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 0);
     if (blockIdx.x >= n_ray_blocks + n_norm_blocks) {
         // The PREVIOUS scan's `logData[c] += ...` (GridMap.java:223) from the other count grid: it needs nothing of this launch
@@ -68,7 +71,7 @@ k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ pa
         if (LOGNORM) {                                                 // the population's reference, then the rescaled sums
             fold_lognorm<4>(partials, nblk_global, cols, f, L);
         } else {
-            fold_sums<4>(partials, nblk_global, cols, f, L);           // one round trip, one barrier pair
+            fold_sums<4, WAVE>(partials, nblk_global, cols, f, L, ((int64_t)n + 63) / 64);           // one round trip, one barrier pair
         }
         // every thread holds the four sums (the fold's last step reads them from LDS in every wavefront) and forms the pose itself:
         // the same three divisions on the same bits, nothing to publish, no barrier
@@ -77,7 +80,7 @@ k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ pa
         if (near) raycast_near_body(g, pre, wpose, cnt, bbox, 0, smem);
         else raycast_body<false, RCF_RAYS, 4>(g, pre, wpose, B, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, blockIdx.x, 0, smem, n_near_blocks ? 1 : 0);
     } else {
-        normalize_pack_body(partials, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2, stats,
+        normalize_pack_body<WAVE>(partials, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2, stats,
                             blockIdx.x - n_ray_blocks, 0, LOGNORM ? logw_lognorm : (const double *)nullptr, res_ticket, n_norm_blocks,
                             res_pre, smem);
         GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 14);
@@ -203,8 +206,9 @@ bool gms_can_pair_launches(const gms_pf *pf, int32_t B) {
 }
 
 // normalise (SLAM.java:120-124) beside integrateObservation at the weighted pose (:93, GridMap.java:173-191)
+// wave_rows: d_partials holds the wavefront rows of gms_launch_pf_partials_wave (gms_pf_wave_partials_now)
 void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticle *d_packed_local, bool own,
-                             const gms_beam *d_beams, int32_t B) {
+                             const gms_beam *d_beams, int32_t B, bool wave_rows) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_RAYCAST);
     const uint32_t n_near = rc_near_blocks(m, B);
@@ -219,15 +223,17 @@ void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticl
     const uint32_t n_apply = m->apply_pending ? apply_blocks(m, GMS_APPLY_BLOCKS_RIDING) : 0u;
     int32_t *pend = map_box(m);
     int32_t *bb = n_apply ? map_box(m, true) : pend;
-    auto launch = [&](auto lognorm) {
-        gms_launch<k_norm_raycast<lognorm()>>(m, dim3(n_ray + n_norm + n_apply), dim3(256), smem, d_beams, d_partials, nblk_global_of(pf), B,
+    auto launch = [&](auto lognorm, auto wave) {
+        gms_launch<k_norm_raycast<lognorm(), wave()>>(m, dim3(n_ray + n_norm + n_apply), dim3(256), smem, d_beams, d_partials, nblk_global_of(pf), B,
                                               rc_nw_max(m), n_ray, n_norm, n_near, pf->n, pf->d_w, pf->d_pose, pf->offset, m->d_cnt, bb, d_packed_local,
                                               own ? pf->d_cum : (double *)nullptr, own ? pf->d_chunk_tot : (double *)nullptr, nchunks_of(pf),
                                               own ? pf->d_p2 : (double *)nullptr, pf->d_stats, m->d_log, m->d_cnt_pend, pend,
                                               lognorm() ? (const double *)pf->d_logw : (const double *)nullptr,
                                               own ? pf->d_res_ticket : (uint32_t *)nullptr, pf->d_res_pre, m->gd);
     };
-    if (gms_pf_lognorm_now(pf)) launch(gms_c<true>{}); else launch(gms_c<false>{});
+    if (gms_pf_lognorm_now(pf)) launch(gms_c<true>{}, gms_c<false>{});
+    else if (wave_rows) launch(gms_c<false>{}, gms_c<true>{});
+    else launch(gms_c<false>{}, gms_c<false>{});
     if (n_apply) gms_apply_done(m);
     pf_normalized(pf, own, own);                                      // (resample_prefix_last wrote stats.norm_sum / sq_sum)
 }

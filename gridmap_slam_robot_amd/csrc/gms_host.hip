@@ -936,8 +936,8 @@ static int64_t nchunks_of(int64_t n) { return (n + 63) / 64; }
 
 static void pf_free_global(gms_pf *pf) {
     hipFree(pf->d_partials); hipFree(pf->d_p2); hipFree(pf->d_global_own); hipFree(pf->d_chunk_tot); hipFree(pf->d_cum);
-    hipFree(pf->d_res_pre); hipFree(pf->d_res_ticket);
-    pf->d_partials = pf->d_p2 = nullptr; pf->d_global = pf->d_global_own = nullptr; pf->d_chunk_tot = pf->d_cum = nullptr;
+    hipFree(pf->d_res_pre); hipFree(pf->d_res_ticket); hipFree(pf->d_wave_partials);
+    pf->d_partials = pf->d_p2 = pf->d_wave_partials = nullptr; pf->d_global = pf->d_global_own = nullptr; pf->d_chunk_tot = pf->d_cum = nullptr;
     pf->d_res_pre = nullptr; pf->d_res_ticket = nullptr; pf->res_pre_ready = 0; pf->have_global = 0;
 }
 
@@ -946,6 +946,7 @@ static int pf_alloc_global(gms_pf *pf) {
     const size_t M = pf->n_maps;
     const size_t nblk = nblk_of(pf->n_global), nch = nchunks_of(pf->n_global);
     HIPCHK(hipMalloc(&pf->d_partials, M * nblk * GMS_PARTIAL_STRIDE * sizeof(double)));
+    HIPCHK(hipMalloc(&pf->d_wave_partials, nch * GMS_PARTIAL_STRIDE * sizeof(double)));     // (one map's: a scan chunk is a wavefront's particles)
     HIPCHK(hipMalloc(&pf->d_p2, M * nblk * 2 * sizeof(double)));
     HIPCHK(hipMalloc(&pf->d_global_own, M * pf->n_global * sizeof(PackedParticle)));
     pf->d_global = pf->d_global_own;
@@ -1401,8 +1402,12 @@ static int slam_update_impl(gms_pf *pf, const float *dev_xytheta, const MotionMo
     if (pair && gms_can_pair_launches(pf, B)) {
         // The weight branch and the map branch are independent once the partials exist: they share launches
         // (gms_fused_kernels.hip).  (Two streams were measured: the event fork/join costs more than it hides.)
-        gms_launch_partials_apply(pf, pf->d_partials, true);                              // :100-115
-        gms_launch_norm_raycast(pf, pf->d_partials, pf->d_global_own, true, dev_beams, B);   // :120-124 | :93 | previous scan's :223
+        // (the pending apply pass rides beside the ray cast; under plain normalisation the partials go as one row per wavefront and
+        // the folds of the second launch add a block's four: no barrier, no LDS and no lone storing wavefront between scoring and ray cast)
+        const bool wave_rows = gms_pf_wave_partials_now(pf);
+        if (wave_rows) gms_launch_pf_partials_wave(pf);                                   // :100-115
+        else gms_launch_partials_apply(pf, pf->d_partials, true);
+        gms_launch_norm_raycast(pf, wave_rows ? pf->d_wave_partials : pf->d_partials, pf->d_global_own, true, dev_beams, B, wave_rows);   // :120-124 | :93 | previous scan's :223
         return paired_likelihood_resample(pf, r01, resample_fraction);           // :105 | GridMapApp.java:185-186
     }
     if (pair && pf->n_maps > 1 && B > 0 && !m->need_full_build && m->pair_launches) {

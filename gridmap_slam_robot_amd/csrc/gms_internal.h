@@ -257,6 +257,7 @@ struct gms_pf {
     double *d_part;                 // [n_maps][GMS_SCORE_MAXSEG][n] per-segment products (k_score_c)
     int32_t *d_nhit;                // [n_maps]
     double *d_partials;             // [n_maps][nblk_global][GMS_PARTIAL_STRIDE]
+    double *d_wave_partials;        // [nchunks][GMS_PARTIAL_STRIDE] one row per wavefront: the stand-alone single-map scan step (k_partials_wave)
     double *d_p2;                   // [n_maps][nblk_global][2] {sum wn, sum wn^2} of the normalised global population
     PackedParticle *d_global_own;   // the library's own buffer; d_global may alias a caller's all-gather result
     double *d_chunk_tot;            // [n_maps][nchunks] scan chunk totals / offsets
@@ -745,7 +746,7 @@ void gms_launch_pf_chunk_sums(gms_pf *pf);
 void gms_launch_partials_apply(gms_pf *pf, double *d_partials, bool apply_rides_later = false);
 bool gms_can_pair_launches(const gms_pf *pf, int32_t B);
 void gms_launch_norm_raycast(gms_pf *pf, const double *d_partials, PackedParticle *d_packed_local, bool own,
-                             const gms_beam *d_beams, int32_t B);
+                             const gms_beam *d_beams, int32_t B, bool wave_rows = false);
 void gms_launch_lik_resample(gms_pf *pf, double fraction);
 void gms_launch_deskew_motion(gms_pf *pf, const double *d_angle, const double *d_distance, const uint8_t *d_hit, int32_t length,
                               double d_center, double d_theta, uint64_t seed, uint64_t sequence);
@@ -766,6 +767,8 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
                          const MotionModel *motion = nullptr);   // d_pose_src: set the poses in the same launch
 void gms_launch_pf_partials(gms_pf *pf, double *d_partials);
 bool gms_pf_lognorm_now(const gms_pf *pf);
+bool gms_pf_wave_partials_now(const gms_pf *pf);
+void gms_launch_pf_partials_wave(gms_pf *pf);
 void gms_launch_pf_pack(gms_pf *pf, PackedParticle *d_packed);
 void gms_launch_pf_apply_partials(gms_pf *pf, const double *d_partials, PackedParticle *d_packed_local, bool own);
 void gms_launch_pf_stats_only(gms_pf *pf, const double *d_partials, PfStatsDev *d_stats_out);

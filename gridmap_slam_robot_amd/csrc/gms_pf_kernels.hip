@@ -615,10 +615,90 @@ __device__ __forceinline__ void block_partials(double *__restrict__ w, double *_
     out[COL_MAX] = mv; out[COL_ARG] = mx; out[COL_MLW] = ml;
 }
 
-// fold per-block partials in block order
-__device__ __forceinline__ double fold_sum(const double *__restrict__ p, int64_t nblk, int col, double *lds) {
+// The single-wavefront form of block_partials (k_partials_wave; the stand-alone single-map scan step, plain normalisation): one
+// wavefront = 64 consecutive particles by global index, the same loads, the same per-lane terms and the same butterflies, and then
+// the wavefront's OWN row: no barrier, no LDS, no wait for the block's other wavefronts.  What block_partials' LDS combine adds --
+// ((w0 + w1) + w2) + w3 over the block's four wavefronts, the strongest and the max-log in wavefront order -- is left to whoever
+// folds the rows (wave_rows_*, below), a lane per block, in the shadow of the round trip that fetches them.
+__device__ __forceinline__ void wave_partials(double *__restrict__ w, double *__restrict__ logw, const float *__restrict__ pose,
+                                              int32_t n, int64_t i, double out[GMS_PARTIAL_STRIDE],
+                                              const double *__restrict__ part, int32_t part_nseg) {
+    const bool in = i < n;
+    double v, lw;
+    if (part) {
+        v = 0.0; lw = -INFINITY;
+        if (in) {
+            combine_segments(part, 0, n, part_nseg, i, v, lw);
+            w[i] = v; logw[i] = lw;
+        }
+    } else {
+        v = in ? w[i] : 0.0;
+        lw = in ? logw[i] : -INFINITY;
+    }
+    const float px = in ? pose[3 * i] : 0.0f, py = in ? pose[3 * i + 1] : 0.0f, pt = in ? pose[3 * i + 2] : 0.0f;
+    double s = 0.0, nz = 0.0, mv = -INFINITY, mx = 9.0e15, ml = -INFINITY, sq = 0.0, xw = 0.0, yw = 0.0, tw = 0.0;
+    if (in) {                                                             // block_partials' terms, operation for operation
+        s += v;
+        sq += v * v;
+        xw += (double)px * v;                                             // SLAM.java:170
+        yw += (double)py * v;                                             // :171
+        tw += angle_constrain((double)pt) * v;                            // :172
+        if (v == 0.0) nz += 1.0;
+        if (v > mv) { mv = v; mx = (double)i; }
+        else if (mx > 8.0e15 && v == v) { mv = v; mx = (double)i; }
+        if (lw > ml) ml = lw;
+    }
+    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 2);
+    double sums[6] = { s, nz, sq, xw, yw, tw };
+#pragma unroll
+    for (int c = 0; c < 6; c++) sums[c] = wave_sum_f64(sums[c]);
+#define GMS_STEP_(O) { const double v2 = wave_xor<O>(mv), i2 = wave_xor<O>(mx); argmax_merge(mv, mx, v2, i2); \
+                       const double l2 = wave_xor<O>(ml); if (l2 > ml) ml = l2; }
+    GMS_BUTTERFLY(GMS_STEP_)
+#undef GMS_STEP_
+    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 3);
+    out[COL_SUM] = sums[0]; out[COL_NZ] = sums[1]; out[COL_SQ] = sums[2];
+    out[COL_XW] = sums[3]; out[COL_YW] = sums[4]; out[COL_TW] = sums[5];
+    out[COL_MAX] = mv; out[COL_ARG] = mx; out[COL_MLW] = ml;
+}
+
+// Block b's entry of a column from the rows of its four wavefronts (k_partials_wave), formed as block_partials' LDS combine forms
+// it, so the bits are the block row's.  A wavefront beyond the population has no row and enters as block_partials' empty wavefront
+// does (`missing`: 0.0 in a sum, -inf as a maximum, 9.0e15 as its index); its load is clamped, not branched round.
+__device__ __forceinline__ void wave_rows_load(const double *__restrict__ p, int64_t b, int col, int64_t nwaves, double missing,
+                                               double (&r)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int64_t wv = 4 * b + k;
+        const double v = p[(wv < nwaves ? wv : nwaves - 1) * GMS_PARTIAL_STRIDE + col];
+        r[k] = wv < nwaves ? v : missing;
+    }
+}
+__device__ __forceinline__ double wave_rows_sum(const double (&r)[4]) { return ((r[0] + r[1]) + r[2]) + r[3]; }
+__device__ __forceinline__ double wave_rows_max(const double (&r)[4]) {
+    double m = r[0];
+    for (int k = 1; k < 4; k++) if (r[k] > m) m = r[k];
+    return m;
+}
+__device__ __forceinline__ void wave_rows_argmax(const double (&rv)[4], const double (&ri)[4], double &v, double &i) {
+    v = rv[0]; i = ri[0];
+    for (int k = 1; k < 4; k++) argmax_merge(v, i, rv[k], ri[k]);
+}
+
+// fold per-block partials in block order.  WAVE (here and in the folds below): p holds the wavefront rows of k_partials_wave,
+// nwaves of them, and a lane forms its block's entries from four rows first (wave_rows_*); everything after that is the same code.
+template <bool WAVE = false>
+__device__ __forceinline__ double fold_sum(const double *__restrict__ p, int64_t nblk, int col, double *lds, int64_t nwaves = 0) {
     double acc = 0.0;
-    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) acc += p[b * GMS_PARTIAL_STRIDE + col];
+    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
+        if constexpr (WAVE) {
+            double r[4];
+            wave_rows_load(p, b, col, nwaves, 0.0, r);
+            acc += wave_rows_sum(r);
+        } else {
+            acc += p[b * GMS_PARTIAL_STRIDE + col];
+        }
+    }
     return group_sum(acc, lds);
 }
 
@@ -626,17 +706,26 @@ __device__ __forceinline__ double fold_sum(const double *__restrict__ p, int64_t
 // (a fold_sum per column is a dependent memory round trip + two barriers each: 2-3 us of pure latency for the four
 // columns the ray-cast workgroups need).  Per column the arithmetic is fold_sum's, operation for operation: the
 // per-thread strided sum, the wave butterfly, ((w0 + w1) + w2) + w3 over the group's waves -- same bits.
-template <int NC>
+// WAVE: the 4 NC loads of a block's wavefront rows are issued together too, the three adds per column run in that round trip's shadow.
+template <int NC, bool WAVE = false>
 __device__ __forceinline__ void fold_sums(const double *__restrict__ p, int64_t nblk, const int (&col)[NC], double (&out)[NC],
-                                          RedLds &L) {
+                                          RedLds &L, int64_t nwaves = 0) {
     static_assert(NC <= GMS_PARTIAL_STRIDE, "RedLds::m has GMS_PARTIAL_STRIDE rows");
     double acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) acc[c] = 0.0;
     for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
         double v[NC];
+        if constexpr (WAVE) {
+            double r[NC][4];
 #pragma unroll
-        for (int c = 0; c < NC; c++) v[c] = p[b * GMS_PARTIAL_STRIDE + col[c]];
+            for (int c = 0; c < NC; c++) wave_rows_load(p, b, col[c], nwaves, 0.0, r[c]);
+#pragma unroll
+            for (int c = 0; c < NC; c++) v[c] = wave_rows_sum(r[c]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < NC; c++) v[c] = p[b * GMS_PARTIAL_STRIDE + col[c]];
+        }
 #pragma unroll
         for (int c = 0; c < NC; c++) acc[c] += v[c];
     }
@@ -684,8 +773,9 @@ __device__ __forceinline__ void fold_sums_scaled(const double *__restrict__ p, i
     for (int c = 0; c < NC; c++) out[c] = ((L.m[c][g4] + L.m[c][g4 + 1]) + L.m[c][g4 + 2]) + L.m[c][g4 + 3];
 }
 
+template <bool WAVE = false>
 __device__ __forceinline__ void fold_argmax(const double *__restrict__ p, int64_t nblk, int colv, int coli, double &mv,
-                                            double &mx, RedLds &L);
+                                            double &mx, RedLds &L, int64_t nwaves = 0);
 // The log-normalising fold in one piece: the population's reference M = max_b m_b, then the rescaled sums.  Up to GRP blocks
 // (65 536 particles) every thread holds its block's entries from ONE round trip to memory -- this fold sits in front of the ray
 // cast's pose, on the step's critical path --; more blocks take the two passes.  Every caller gets the same bits (one function).
@@ -727,12 +817,25 @@ __device__ __forceinline__ double fold_lognorm(const double *__restrict__ p, int
     return M;
 }
 
+template <bool WAVE>
 __device__ __forceinline__ void fold_argmax(const double *__restrict__ p, int64_t nblk, int colv, int coli, double &mv,
-                                            double &mx, RedLds &L) {
+                                            double &mx, RedLds &L, int64_t nwaves) {
     mv = -INFINITY; mx = 9.0e15;
     bool first = true;
     for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
-        const double v2 = p[b * GMS_PARTIAL_STRIDE + colv], i2 = coli >= 0 ? p[b * GMS_PARTIAL_STRIDE + coli] : (double)b;
+        double v2, i2;
+        if constexpr (WAVE) {                                          // the block's entry from its wavefronts' first, in wavefront order
+            double rv[4], ri[4];
+            wave_rows_load(p, b, colv, nwaves, -INFINITY, rv);
+            if (coli >= 0) {
+                wave_rows_load(p, b, coli, nwaves, 9.0e15, ri);
+                wave_rows_argmax(rv, ri, v2, i2);
+            } else {
+                v2 = wave_rows_max(rv); i2 = (double)b;
+            }
+        } else {
+            v2 = p[b * GMS_PARTIAL_STRIDE + colv]; i2 = coli >= 0 ? p[b * GMS_PARTIAL_STRIDE + coli] : (double)b;
+        }
         if (first) { mv = v2; mx = i2; first = false; } else argmax_merge(mv, mx, v2, i2);
     }
     group_argmax(mv, mx, L.a, L.b);
@@ -740,12 +843,16 @@ __device__ __forceinline__ void fold_argmax(const double *__restrict__ p, int64_
 
 // all statistics from the (all-reduced) partial vector; every thread of the workgroup must call.  lognorm: the columns are
 // block-relative (block_partials): *ref_out receives M, the population's largest log-weight, the returned sum is sum exp(logw - M).
+// WAVE: p holds wavefront rows (fold_sum; plain normalisation only: a log-normalising pass keeps block rows).
+template <bool WAVE = false>
 __device__ __forceinline__ double fold_stats(const double *__restrict__ p, int64_t nblk, PfStatsDev *s, bool write,
                                              const float *__restrict__ pose, int64_t pose_base, int64_t pose_n, RedLds &L,
-                                             const PackedParticle *__restrict__ glob = nullptr, bool lognorm = false, double *ref_out = nullptr) {
+                                             const PackedParticle *__restrict__ glob = nullptr, bool lognorm = false, double *ref_out = nullptr,
+                                             int64_t nwaves = 0) {
     double ml = 0.0, mli;
+    if constexpr (WAVE) lognorm = false;
     if (!write) {
-        if (!lognorm) return fold_sum(p, nblk, COL_SUM, L.a);
+        if (!lognorm) return fold_sum<WAVE>(p, nblk, COL_SUM, L.a, nwaves);
         const int c1[1] = { COL_SUM };
         double f1[1];
         ml = fold_lognorm<1>(p, nblk, c1, f1, L);
@@ -755,11 +862,11 @@ __device__ __forceinline__ double fold_stats(const double *__restrict__ p, int64
     const int cols[5] = { COL_SUM, COL_NZ, COL_XW, COL_YW, COL_TW };
     double f[5];
     if (lognorm) { ml = fold_lognorm<5>(p, nblk, cols, f, L); if (ref_out) *ref_out = ml; }
-    else fold_sums<5>(p, nblk, cols, f, L);
+    else fold_sums<5, WAVE>(p, nblk, cols, f, L, nwaves);
     const double sum = f[0], nz = f[1], xw = f[2], yw = f[3], tw = f[4];
     double mv, mx;
-    fold_argmax(p, nblk, COL_MAX, COL_ARG, mv, mx, L);
-    if (!lognorm) fold_argmax(p, nblk, COL_MLW, -1, ml, mli, L);
+    fold_argmax<WAVE>(p, nblk, COL_MAX, COL_ARG, mv, mx, L, nwaves);
+    if (!lognorm) fold_argmax<WAVE>(p, nblk, COL_MLW, -1, ml, mli, L, nwaves);
     if (threadIdx.x == 0) {
         s->n_ambiguous = 0;
         s->weight_sum = sum;
@@ -844,6 +951,38 @@ k_partials(const double *__restrict__ part, const float *__restrict__ pose, PfSt
     // (argument order: the segment products, the poses and what their addresses are formed from lead: see k_score_c)
     GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 0);
     partials_body(w, logw, pose, n, offset, nblk_global, partials, part, part_nseg, blockIdx.x, blockIdx.y, lognorm_stats);
+    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 1);
+}
+
+// The block partials of a stand-alone single-map filter as one row per WAVEFRONT (wave_partials): workgroups of 64 lanes, no
+// barrier, no LDS, no atomics; rows[(n + 63) / 64][GMS_PARTIAL_STRIDE], read by k_norm_raycast<false, true> alone.
+// Workgroup id -> wavefront: GMS_WAVE_PARTIALS_XCD_BLOCKS = 1 gives the four wavefronts of a block to ids eight apart (one XCD, id & 7),
+// 0 takes them in id order (a block's wavefronts on four XCDs).  The grid covers whole groups of 32 under the first form; a wavefront
+// beyond the population leaves at once.  By the stamps at C3 the two are one (three runs each, medians, 0 / 1: entered -> left 3.06 /
+// 3.04 us, entered -> the next launch's pose folded 6.96 / 6.81 with 0.2 between the runs of either): the plain order stays.
+#ifndef GMS_WAVE_PARTIALS_XCD_BLOCKS
+#define GMS_WAVE_PARTIALS_XCD_BLOCKS 0
+#endif
+static_assert(EPT == 1 && GMS_BLOCK == 4 * GMS_WAVE, "a reduction block is four wavefronts of one particle per lane");
+__global__ void __launch_bounds__(64)
+k_partials_wave(const double *__restrict__ part, const float *__restrict__ pose, int32_t n, int32_t part_nseg,
+                double *__restrict__ w, double *__restrict__ logw, double *__restrict__ rows) {
+    // (argument order: the segment products, the poses and what their addresses are formed from lead: see k_score_c)
+    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 0);
+#if GMS_WAVE_PARTIALS_XCD_BLOCKS
+    const uint32_t j = blockIdx.x >> 3;
+    const int64_t wv = 4 * (int64_t)((j >> 2) * 8 + (blockIdx.x & 7)) + (j & 3);
+#else
+    const int64_t wv = blockIdx.x;
+#endif
+    if (wv * GMS_WAVE >= n) return;                                     // (uniform)
+    double out[GMS_PARTIAL_STRIDE];
+    wave_partials(w, logw, pose, n, wv * GMS_WAVE + threadIdx.x, out, part, part_nseg);
+    if (threadIdx.x == 0) {
+        double *p = rows + wv * GMS_PARTIAL_STRIDE;
+#pragma unroll
+        for (int k = 0; k < GMS_PARTIAL_STRIDE; k++) p[k] = out[k];
+    }
     GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 1);
 }
 
@@ -984,6 +1123,8 @@ resample_prefix_last(const double *__restrict__ p2, int64_t nblk, const double *
 // phase 2: every workgroup folds the (all-reduced) partials; weight /= weightSum (SLAM.java:120-121);
 // packs {w,x,y,theta} (the all-gather payload / the resampling source).  A stand-alone filter also
 // gets the dense weight copy and level 0 of the cumulative weights here (cum != nullptr).
+// WAVE: partials_all holds the wavefront rows of k_partials_wave (one map, the whole population here: (n + 63) / 64 rows).
+template <bool WAVE = false>
 __device__ __forceinline__ void
 normalize_pack_body(const double *__restrict__ partials_all, int64_t nblk_global, double *__restrict__ w,
                     const float *__restrict__ pose, int32_t n, int64_t offset, PackedParticle *__restrict__ packed,
@@ -997,7 +1138,8 @@ normalize_pack_body(const double *__restrict__ partials_all, int64_t nblk_global
     const int32_t mi = (int32_t)by;
     const double *p = partials_all + (size_t)mi * nblk_global * GMS_PARTIAL_STRIDE;
     double M = 0.0;
-    const double sum = fold_stats(p, nblk_global, stats + mi, bx == 0, pose + (size_t)mi * n * 3, offset, n, L, nullptr, logw_lognorm != nullptr, &M);
+    const double sum = fold_stats<WAVE>(p, nblk_global, stats + mi, bx == 0, pose + (size_t)mi * n * 3, offset, n, L, nullptr, logw_lognorm != nullptr, &M,
+                                        ((int64_t)n + 63) / 64);
     const int32_t i = (int32_t)bx * 256 + threadIdx.x;
     double wn = 0.0;
     if (logw_lognorm) {                                                    // (uniform)
@@ -1689,6 +1831,26 @@ void gms_launch_pf_partials(gms_pf *pf, double *d_partials) {
                        gms_pf_lognorm_now(pf) ? pf->d_stats : (PfStatsDev *)nullptr, pf->n, pf->pending_nseg, pf->offset, nblk,
                        pf->d_w, pf->d_logw, d_partials);
     pf_weights_combined(pf);                                          // k_partials stored the combined weights
+}
+
+// whether the scan step's partials go as wavefront rows (k_partials_wave -> k_norm_raycast<false, true>): a stand-alone single-map
+// filter under plain normalisation; the caller has checked that the two launches pair (gms_can_pair_launches)
+bool gms_pf_wave_partials_now(const gms_pf *pf) {
+    return pf->n_maps == 1 && pf->offset == 0 && pf->n_global == pf->n && !gms_pf_lognorm_now(pf);
+}
+
+// the block partials as one row per wavefront, into pf->d_wave_partials
+void gms_launch_pf_partials_wave(gms_pf *pf) {
+    gms_map *m = pf->map;
+    ProfScope ps(m, GMS_K_REDUCE);
+    uint32_t grid = (uint32_t)nchunks_of(pf);                          // a scan chunk is a wavefront's 64 particles
+#if GMS_WAVE_PARTIALS_XCD_BLOCKS
+    grid = (grid + 31u) / 32u * 32u;
+#endif
+    hipLaunchKernelGGL(k_partials_wave, dim3(grid), dim3(GMS_WAVE), 0, m->stream,
+                       pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose, pf->n, pf->pending_nseg,
+                       pf->d_w, pf->d_logw, pf->d_wave_partials);
+    pf_weights_combined(pf);                                          // k_partials_wave stored the combined weights
 }
 
 void gms_launch_pf_apply_partials(gms_pf *pf, const double *d_partials, PackedParticle *d_packed_local, bool own) {
