@@ -31,7 +31,7 @@
 template <bool LOGNORM, bool WAVE>   // (the log-normalising form is a separate instantiation: the default kernel is exactly what it was -- as one kernel
                           // with a uniform branch its ray blocks ran 1.1 us longer, measured A/B on one box)
                           // WAVE: `partials` holds one row per WAVEFRONT (k_partials_wave), (n + 63) / 64 of them: a lane of either fold adds its
-                          // block's four rows first, as k_partials' LDS combine would have (fold_sum).  Plain normalisation only.
+                          // block's four rows first, as k_partials' LDS combine would have (WaveRows).  Plain normalisation only.
 __global__ void __launch_bounds__(256)
 k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ partials, int64_t nblk_global, int32_t B,
                int32_t nw_max, uint32_t n_ray_blocks, uint32_t n_norm_blocks, uint32_t n_near_blocks, int32_t n,
@@ -50,6 +50,7 @@ k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ pa
     // in the shadow of the ray cast
     static_assert(!(LOGNORM && WAVE), "a log-normalising pass needs its block's reference: block rows");
     GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 0);
+    const auto rows = [&] { if constexpr (WAVE) return WaveRows{ partials, ((int64_t)n + 63) / 64 }; else return BlockRows{ partials }; }();
     if (blockIdx.x >= n_ray_blocks + n_norm_blocks) {
         // The PREVIOUS scan's `logData[c] += ...` (GridMap.java:223) from the other count grid: it needs nothing of this launch
         // and only has to be done before this scan's likelihood pass.  Its ~5 us hide under the ray cast's 17 us latency chain
@@ -68,10 +69,10 @@ k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ pa
                                 : raycast_prologue<RCF_RAYS, 4>(beams, B, B, nullptr, nw_max, blockIdx.x, 0, smem);
         const int cols[4] = { COL_SUM, COL_XW, COL_YW, COL_TW };
         double f[4];
-        if (LOGNORM) {                                                 // the population's reference, then the rescaled sums
-            fold_lognorm<4>(partials, nblk_global, cols, f, L);
+        if constexpr (LOGNORM) {                                       // the population's reference, then the rescaled sums
+            fold_lognorm<4>(rows, nblk_global, cols, f, L);
         } else {
-            fold_sums<4, WAVE>(partials, nblk_global, cols, f, L, ((int64_t)n + 63) / 64);           // one round trip, one barrier pair
+            fold_sums<4>(rows, nblk_global, cols, f, L);               // one round trip, one barrier pair
         }
         // every thread holds the four sums (the fold's last step reads them from LDS in every wavefront) and forms the pose itself:
         // the same three divisions on the same bits, nothing to publish, no barrier
@@ -80,7 +81,7 @@ k_norm_raycast(const gms_beam *__restrict__ beams, const double *__restrict__ pa
         if (near) raycast_near_body(g, pre, wpose, cnt, bbox, 0, smem);
         else raycast_body<false, RCF_RAYS, 4>(g, pre, wpose, B, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, blockIdx.x, 0, smem, n_near_blocks ? 1 : 0);
     } else {
-        normalize_pack_body<WAVE>(partials, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2, stats,
+        normalize_pack_body<LOGNORM>(rows, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2, stats,
                             blockIdx.x - n_ray_blocks, 0, LOGNORM ? logw_lognorm : (const double *)nullptr, res_ticket, n_norm_blocks,
                             res_pre, smem);
         GMS_STAMP(GMS_STAMP_ROW(2, blockIdx.x), 14);
@@ -142,7 +143,7 @@ k_raycast_norm_chunks(const gms_beam *__restrict__ beams, const double *__restri
                                 : raycast_prologue<RCF_RAYS, 4>(beams, B, B, nullptr, nw_max, blockIdx.x, 0, smem);
         const int cols[4] = { COL_SUM, COL_XW, COL_YW, COL_TW };
         double f[4];
-        fold_sums<4>(partials, nblk_global, cols, f, L);               // one round trip, one barrier pair
+        fold_sums<4>(BlockRows{ partials }, nblk_global, cols, f, L);  // one round trip, one barrier pair
         const float wpose[3] = { (float)(f[1] / f[0]), (float)(f[2] / f[0]), (float)(f[3] / f[0]) };       // SLAM.java:176
         if (near) raycast_near_body(g, pre, wpose, cnt, bbox, 0, smem);
         else raycast_body<false, RCF_RAYS, 4>(g, pre, wpose, B, nullptr, cnt, bbox, nullptr, nullptr, 0, nullptr, blockIdx.x, 0, smem, n_near_blocks ? 1 : 0);

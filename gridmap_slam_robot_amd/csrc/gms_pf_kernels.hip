@@ -442,10 +442,10 @@ k_score_combine(const double *__restrict__ part, int32_t n, int32_t nseg, double
 
 // ---------------------------------------------------------------------------------------------
 // Blocked reductions.  A reduction block is GMS_BLOCK = 256 consecutive particles (by GLOBAL index)
-// and is reduced by a "group" of 256 consecutive threads (4 waves), EPT = GMS_BLOCK/256 particles per thread.
+// and is reduced by a "group" of 256 consecutive threads (4 waves), one particle per lane.
 // Shape, identical in every kernel that uses it:
-//   thread t folds its EPT particles t, t+256, ... of the block sequentially (EPT = 1: just its own),
-//   64-lane xor butterfly per wave, then ((w0 + w1) + w2) + w3 over the group's four waves;
+//   a wavefront's 64 lanes meet in a 64-lane xor butterfly (wave_row: what one wavefront contributes),
+//   the group's four waves as ((w0 + w1) + w2) + w3 (group_combine: how four wavefronts meet);
 //   blocks are folded in block order (thread t takes blocks t, t+256, ... then the group shape).
 // Kernels run 1 or 4 groups per workgroup; every thread of the workgroup must make the calls (they
 // contain barriers).  Because the shape depends only on global indices, the results are the same for
@@ -453,9 +453,10 @@ k_score_combine(const double *__restrict__ part, int32_t n, int32_t nseg, double
 // ---------------------------------------------------------------------------------------------
 #define MAX_WAVES 16
 #define GRP 256
-#define EPT (GMS_BLOCK / GRP)
-#define EPB (EPT < 4 ? EPT : 4)      // particles in flight per thread
+static_assert(GMS_BLOCK == GRP && GRP == 4 * GMS_WAVE, "a reduction block is four wavefronts of one particle per lane");
 
+// one column over L.a / L.b (a caller's later code may reuse the array it hands in: resample_prefix_last); several columns at
+// once: group_combine
 __device__ __forceinline__ double group_sum(double v, double *lds /* [MAX_WAVES] */) {
     v = wave_sum_f64(v);
     const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
@@ -463,6 +464,20 @@ __device__ __forceinline__ double group_sum(double v, double *lds /* [MAX_WAVES]
     if ((threadIdx.x & 63) == 0) lds[wave] = v;
     __syncthreads();
     return ((lds[g4] + lds[g4 + 1]) + lds[g4 + 2]) + lds[g4 + 3];
+}
+
+// the group's largest v, in wavefront order; NaN never wins (the callers enter -inf for it)
+__device__ __forceinline__ double group_max(double v, double *lds /* [MAX_WAVES] */) {
+#define GMS_STEP_(O) { const double v2 = wave_xor<O>(v); if (v2 > v) v = v2; }
+    GMS_BUTTERFLY(GMS_STEP_)
+#undef GMS_STEP_
+    const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds[wave] = v;
+    __syncthreads();
+    double m = lds[g4];
+    for (int k = 1; k < 4; k++) if (lds[g4 + k] > m) m = lds[g4 + k];
+    return m;
 }
 
 // (value, index) max with "first maximum wins" (SLAM.java:110-115: strict >); NaN never wins
@@ -486,6 +501,34 @@ struct RedLds {
     double a[MAX_WAVES], b[MAX_WAVES];
     double m[GMS_PARTIAL_STRIDE][MAX_WAVES];
 };
+
+// How the group's four wavefronts meet: s holds NC per-wavefront values (butterflies done); lane 0 of every wavefront publishes
+// them in L.m between ONE barrier pair, and every thread of the group leaves with ((w0 + w1) + w2) + w3 per column.
+// BEST: best = a wavefront's strongest (value, index) and its largest log-weight ride the same pair (rows NC, NC + 1, NC + 2)
+// and meet in wavefront order (argmax_merge: the first maximum wins).
+// GROUP_BARRIER_TAKEN: the caller's last step ended in a barrier and nothing has read L.m since: no leading barrier.
+enum GroupLead { GROUP_BARRIER, GROUP_BARRIER_TAKEN };
+template <int NC, bool BEST = false>
+__device__ __forceinline__ void group_combine(double (&s)[NC], RedLds &L, GroupLead lead = GROUP_BARRIER, double *best = nullptr) {
+    static_assert(NC + (BEST ? 3 : 0) <= GMS_PARTIAL_STRIDE, "RedLds::m has GMS_PARTIAL_STRIDE rows");
+    const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
+    if (lead == GROUP_BARRIER) __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) L.m[c][wave] = s[c];
+        if constexpr (BEST) { L.m[NC][wave] = best[0]; L.m[NC + 1][wave] = best[1]; L.m[NC + 2][wave] = best[2]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NC; c++) s[c] = ((L.m[c][g4] + L.m[c][g4 + 1]) + L.m[c][g4 + 2]) + L.m[c][g4 + 3];
+    if constexpr (BEST) {
+        best[0] = L.m[NC][g4]; best[1] = L.m[NC + 1][g4]; best[2] = L.m[NC + 2][g4];
+        for (int k = 1; k < 4; k++) {
+            argmax_merge(best[0], best[1], L.m[NC][g4 + k], L.m[NC + 1][g4 + k]);
+            if (L.m[NC + 2][g4 + k] > best[2]) best[2] = L.m[NC + 2][g4 + k];
+        }
+    }
+}
 
 // Partial columns of one block of GMS_BLOCK particles (GMS_PARTIAL_STRIDE = 9):
 //   0 sum w            (SLAM.java:100)          5 sum w*w          (-> calculateNeff, SLAM.java:180-190)
@@ -516,189 +559,161 @@ struct RedLds {
 // lognorm (gms_pf_set_log_normalize): the underflow-free normalisation SURVEY 9.6 asks for beside the reference's plain product,
 // weight = exp(logw - M) / sum, M the largest log-weight of the map's population, WITHOUT a pass of its own in front: this block's
 // columns are taken relative to the block's OWN largest log-weight m_b (column COL_MLW) -- v = exp(logw - m_b) -- and whoever folds
-// the partial vector rescales every block by exp(m_b - M) (fold_sums_scaled: the online-softmax rearrangement; the sums differ from
+// the partial vector rescales every block by exp(m_b - M) (the SCALED form of fold_sums: the online-softmax rearrangement; the sums differ from
 // sum exp(logw - M) by a few ulps).  The weights themselves are formed from the log-weights where they are normalised
 // (normalize_pack_body), exp(logw - M) / sum: nothing block-relative is ever stored.  COL_MAX / COL_ARG then hold the largest
 // LOG-weight and its first index (the strongest particle is the first maximum of the log-weights: two different log-weights may
 // round to the same weight).  (Round 4 took M from a launch of its own, k_logmax, in front of this one: +4 us per step.)
-static_assert(EPT == 1, "the log-normalising form of block_partials takes one particle per thread");
 __device__ __forceinline__ double lognorm_ref(double m) { return m > -INFINITY ? m : 0.0; }      // a block (or a population) whose products are all 0 or NaN: nothing to rescale by
+
+// One lane's particle of a weight reduction: weight, log-weight and pose of particle i of w / logw / pose; a lane beyond the
+// population (!in) holds the empty particle.  part != nullptr: the weight is formed here from its segment products (particle
+// part_p of map part_mi's part_n) and stored with its log-weight.
+struct RedParticle { double v, lw; float x, y, t; };
+__device__ __forceinline__ RedParticle load_particle(double *__restrict__ w, double *__restrict__ logw, const float *__restrict__ pose,
+                                                     int64_t i, bool in, const double *__restrict__ part, int32_t part_mi,
+                                                     int32_t part_n, int32_t part_nseg, int64_t part_p) {
+    RedParticle q;
+    if (part) {
+        q.v = 0.0; q.lw = -INFINITY;
+        if (in) {
+            combine_segments(part, part_mi, part_n, part_nseg, part_p, q.v, q.lw);
+            w[i] = q.v; logw[i] = q.lw;
+        }
+    } else {
+        q.v = in ? w[i] : 0.0;
+        q.lw = in ? logw[i] : -INFINITY;
+    }
+    q.x = in ? pose[3 * i] : 0.0f; q.y = in ? pose[3 * i + 1] : 0.0f; q.t = in ? pose[3 * i + 2] : 0.0f;
+    return q;
+}
+
+// What one wavefront contributes: its row of the partial columns, in every lane.  sum: w, count of w == 0, w*w, x*w, y*w,
+// theta*w; best: the strongest's key and global index, the largest log-weight.
+struct PartialRow {
+    double sum[6], best[3];
+    __device__ __forceinline__ void columns(double out[GMS_PARTIAL_STRIDE]) const {
+        out[COL_SUM] = sum[0]; out[COL_NZ] = sum[1]; out[COL_SQ] = sum[2];
+        out[COL_XW] = sum[3]; out[COL_YW] = sum[4]; out[COL_TW] = sum[5];
+        out[COL_MAX] = best[0]; out[COL_ARG] = best[1]; out[COL_MLW] = best[2];
+    }
+};
+// q: the lane's particle (in: it has one), gi its global index, key what the strongest is chosen by: the weight, or the
+// log-weight in a log-normalising pass.  The first maximum wins (SLAM.java:110-115): lanes ascend with the index and > is strict;
+// the first key that is no NaN displaces the seed, a NaN never wins.
+__device__ __forceinline__ PartialRow wave_row(const RedParticle &q, bool in, int64_t gi, double key) {
+    double s = 0.0, nz = 0.0, mv = -INFINITY, mx = 9.0e15, ml = -INFINITY, sq = 0.0, xw = 0.0, yw = 0.0, tw = 0.0;
+    if (in) {
+        s += q.v;
+        sq += q.v * q.v;
+        xw += (double)q.x * q.v;                                          // SLAM.java:170
+        yw += (double)q.y * q.v;                                          // :171
+        tw += angle_constrain((double)q.t) * q.v;                         // :172
+        if (q.v == 0.0) nz += 1.0;
+        if (key > mv) { mv = key; mx = (double)gi; }
+        else if (mx > 8.0e15 && key == key) { mv = key; mx = (double)gi; }
+        if (q.lw > ml) ml = q.lw;
+    }
+    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 2);
+    PartialRow r = { { s, nz, sq, xw, yw, tw }, { 0.0, 0.0, 0.0 } };
+#pragma unroll
+    for (int c = 0; c < 6; c++) r.sum[c] = wave_sum_f64(r.sum[c]);
+#define GMS_STEP_(O) { const double v2 = wave_xor<O>(mv), i2 = wave_xor<O>(mx); argmax_merge(mv, mx, v2, i2); \
+                       const double l2 = wave_xor<O>(ml); if (l2 > ml) ml = l2; }
+    GMS_BUTTERFLY(GMS_STEP_)
+#undef GMS_STEP_
+    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 3);
+    r.best[0] = mv; r.best[1] = mx; r.best[2] = ml;
+    return r;
+}
+
+// A block's row (k_partials): load -> [log-normalising: the block's reference, v = exp(logw - m_b), between barriers of its
+// own] -> the wavefront's row -> the four wavefronts' rows meet, one barrier pair for all nine columns.
 __device__ __forceinline__ void block_partials(double *__restrict__ w, double *__restrict__ logw,
                                                const float *__restrict__ pose, int64_t cnt, int64_t base,
                                                double out[GMS_PARTIAL_STRIDE], RedLds &L,
                                                const double *__restrict__ part = nullptr, int32_t part_mi = 0,
                                                int32_t part_n = 0, int32_t part_nseg = 0, int64_t part_p0 = 0,
                                                bool lognorm = false) {
-    const int32_t tl = threadIdx.x & (GRP - 1);
-    double s = 0.0, nz = 0.0, mv = -INFINITY, mx = 9.0e15, ml = -INFINITY, sq = 0.0, xw = 0.0, yw = 0.0, tw = 0.0;
-#pragma unroll
-    for (int e0 = 0; e0 < EPT; e0 += EPB) {
-        double v[EPB], lw[EPB];
-        float px[EPB], py[EPB], pt[EPB];
-#pragma unroll
-        for (int e = 0; e < EPB; e++) {
-            const int64_t i = tl + (e0 + e) * GRP;
-            const bool in = i < cnt;
-            if (part) {
-                v[e] = 0.0; lw[e] = -INFINITY;
-                if (in) {
-                    combine_segments(part, part_mi, part_n, part_nseg, part_p0 + i, v[e], lw[e]);
-                    w[i] = v[e]; logw[i] = lw[e];
-                }
-            } else {
-                v[e] = in ? w[i] : 0.0;
-                lw[e] = in ? logw[i] : -INFINITY;
-            }
-            px[e] = in ? pose[3 * i] : 0.0f; py[e] = in ? pose[3 * i + 1] : 0.0f; pt[e] = in ? pose[3 * i + 2] : 0.0f;
-        }
-        if (lognorm) {                                                     // (uniform; one particle per thread)
-            double mloc = lw[0] == lw[0] ? lw[0] : -INFINITY;              // a NaN product does not set the scale
-#define GMS_STEP_(O) { const double v2 = wave_xor<O>(mloc); if (v2 > mloc) mloc = v2; }
-            GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-            const int32_t wv = threadIdx.x >> 6, g4 = (wv >> 2) << 2;
-            __syncthreads();
-            if ((threadIdx.x & 63) == 0) L.b[wv] = mloc;
-            __syncthreads();
-            double mb = L.b[g4];
-            for (int k = 1; k < 4; k++) if (L.b[g4 + k] > mb) mb = L.b[g4 + k];
-            if (tl < cnt) v[0] = exp(lw[0] - lognorm_ref(mb));
-        }
-#pragma unroll
-        for (int e = 0; e < EPB; e++) {
-            const int64_t i = tl + (e0 + e) * GRP;
-            if (i < cnt) {
-                s += v[e];
-                sq += v[e] * v[e];
-                xw += (double)px[e] * v[e];                               // SLAM.java:170
-                yw += (double)py[e] * v[e];                               // :171
-                tw += angle_constrain((double)pt[e]) * v[e];              // :172
-                if (v[e] == 0.0) nz += 1.0;
-                const double key = lognorm ? lw[e] : v[e];                // (log-normalising: the strongest is the first maximum of the log-weights)
-                if (key > mv) { mv = key; mx = (double)(base + i); }      // ascending index: strict > keeps the first
-                else if (mx > 8.0e15 && key == key) { mv = key; mx = (double)(base + i); }
-                if (lw[e] > ml) ml = lw[e];
-            }
-        }
+    const int64_t i = threadIdx.x & (GRP - 1);
+    const bool in = i < cnt;
+    RedParticle q = load_particle(w, logw, pose, i, in, part, part_mi, part_n, part_nseg, part_p0 + i);
+    if (lognorm) {                                                         // (uniform)
+        const double mb = group_max(q.lw == q.lw ? q.lw : -INFINITY, L.b);    // a NaN product does not set the scale
+        if (in) q.v = exp(q.lw - lognorm_ref(mb));
     }
-    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 2);
-    // one barrier pair for all nine columns: wave butterflies first, then the four waves of the group
-    // are combined in wave order by every thread (same shape as group_sum / group_argmax)
-    double sums[6] = { s, nz, sq, xw, yw, tw };
-#pragma unroll
-    for (int c = 0; c < 6; c++) sums[c] = wave_sum_f64(sums[c]);
-    double mli = 0.0;
-#define GMS_STEP_(O) { const double v2 = wave_xor<O>(mv), i2 = wave_xor<O>(mx); argmax_merge(mv, mx, v2, i2); \
-                       const double l2 = wave_xor<O>(ml); if (l2 > ml) ml = l2; }
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
-    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 3);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) L.m[c][wave] = sums[c];
-        L.m[6][wave] = mv; L.m[7][wave] = mx; L.m[8][wave] = ml;
-    }
-    __syncthreads();
+    PartialRow r = wave_row(q, in, base + i, lognorm ? q.lw : q.v);       // (log-normalising: the strongest is the first maximum of the log-weights)
+    group_combine<6, true>(r.sum, L, GROUP_BARRIER, r.best);
     GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 4);
-#pragma unroll
-    for (int c = 0; c < 6; c++) sums[c] = ((L.m[c][g4] + L.m[c][g4 + 1]) + L.m[c][g4 + 2]) + L.m[c][g4 + 3];
-    mv = L.m[6][g4]; mx = L.m[7][g4]; ml = L.m[8][g4];
-    for (int k = 1; k < 4; k++) {
-        argmax_merge(mv, mx, L.m[6][g4 + k], L.m[7][g4 + k]);
-        if (L.m[8][g4 + k] > ml) ml = L.m[8][g4 + k];
-    }
-    (void)mli;
-    out[COL_SUM] = sums[0]; out[COL_NZ] = sums[1]; out[COL_SQ] = sums[2];
-    out[COL_XW] = sums[3]; out[COL_YW] = sums[4]; out[COL_TW] = sums[5];
-    out[COL_MAX] = mv; out[COL_ARG] = mx; out[COL_MLW] = ml;
+    r.columns(out);
 }
 
-// The single-wavefront form of block_partials (k_partials_wave; the stand-alone single-map scan step, plain normalisation): one
-// wavefront = 64 consecutive particles by global index, the same loads, the same per-lane terms and the same butterflies, and then
-// the wavefront's OWN row: no barrier, no LDS, no wait for the block's other wavefronts.  What block_partials' LDS combine adds --
-// ((w0 + w1) + w2) + w3 over the block's four wavefronts, the strongest and the max-log in wavefront order -- is left to whoever
-// folds the rows (wave_rows_*, below), a lane per block, in the shadow of the round trip that fetches them.
+// A wavefront's row on its own (k_partials_wave; the stand-alone single-map scan step, plain normalisation): one wavefront = 64
+// consecutive particles by global index, load -> row, and that is all: no barrier, no LDS, no wait for the block's other
+// wavefronts.  How the block's four rows meet (group_combine) is left to whoever folds them (WaveRows, below), a lane per block,
+// in the shadow of the round trip that fetches them.
 __device__ __forceinline__ void wave_partials(double *__restrict__ w, double *__restrict__ logw, const float *__restrict__ pose,
                                               int32_t n, int64_t i, double out[GMS_PARTIAL_STRIDE],
                                               const double *__restrict__ part, int32_t part_nseg) {
     const bool in = i < n;
-    double v, lw;
-    if (part) {
-        v = 0.0; lw = -INFINITY;
-        if (in) {
-            combine_segments(part, 0, n, part_nseg, i, v, lw);
-            w[i] = v; logw[i] = lw;
+    const RedParticle q = load_particle(w, logw, pose, i, in, part, 0, n, part_nseg, i);
+    wave_row(q, in, i, q.v).columns(out);
+}
+
+// Where a fold reads block b's entry of a column, passed by value.  Two kinds, the same three accessors: sum (a summed column),
+// max (a maximum) and best (a (value, index) pair of columns).
+// BlockRows: p holds one row per block (k_partials): the entry is one load.
+struct BlockRows {
+    static constexpr bool BLOCK = true;
+    const double *__restrict__ p;
+    __device__ __forceinline__ double sum(int64_t b, int col) const { return p[b * GMS_PARTIAL_STRIDE + col]; }
+    __device__ __forceinline__ double max(int64_t b, int col) const { return p[b * GMS_PARTIAL_STRIDE + col]; }
+    __device__ __forceinline__ void best(int64_t b, int colv, int coli, double &v, double &i) const {
+        v = p[b * GMS_PARTIAL_STRIDE + colv]; i = p[b * GMS_PARTIAL_STRIDE + coli];
+    }
+};
+// WaveRows: p holds one row per WAVEFRONT (k_partials_wave), n of them: the entry is formed from the block's four rows as
+// group_combine forms it, so the bits are the block row's.  A wavefront beyond the population has no row and enters as
+// block_partials' empty wavefront does (`missing`: 0.0 in a sum, -inf as a maximum, 9.0e15 as its index); its load is clamped,
+// not branched round.
+struct WaveRows {
+    static constexpr bool BLOCK = false;
+    const double *__restrict__ p;
+    int64_t n;
+    __device__ __forceinline__ void load(int64_t b, int col, double missing, double (&r)[4]) const {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t wv = 4 * b + k;
+            const double v = p[(wv < n ? wv : n - 1) * GMS_PARTIAL_STRIDE + col];
+            r[k] = wv < n ? v : missing;
         }
-    } else {
-        v = in ? w[i] : 0.0;
-        lw = in ? logw[i] : -INFINITY;
     }
-    const float px = in ? pose[3 * i] : 0.0f, py = in ? pose[3 * i + 1] : 0.0f, pt = in ? pose[3 * i + 2] : 0.0f;
-    double s = 0.0, nz = 0.0, mv = -INFINITY, mx = 9.0e15, ml = -INFINITY, sq = 0.0, xw = 0.0, yw = 0.0, tw = 0.0;
-    if (in) {                                                             // block_partials' terms, operation for operation
-        s += v;
-        sq += v * v;
-        xw += (double)px * v;                                             // SLAM.java:170
-        yw += (double)py * v;                                             // :171
-        tw += angle_constrain((double)pt) * v;                            // :172
-        if (v == 0.0) nz += 1.0;
-        if (v > mv) { mv = v; mx = (double)i; }
-        else if (mx > 8.0e15 && v == v) { mv = v; mx = (double)i; }
-        if (lw > ml) ml = lw;
+    __device__ __forceinline__ double sum(int64_t b, int col) const {
+        double r[4];
+        load(b, col, 0.0, r);
+        return ((r[0] + r[1]) + r[2]) + r[3];
     }
-    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 2);
-    double sums[6] = { s, nz, sq, xw, yw, tw };
-#pragma unroll
-    for (int c = 0; c < 6; c++) sums[c] = wave_sum_f64(sums[c]);
-#define GMS_STEP_(O) { const double v2 = wave_xor<O>(mv), i2 = wave_xor<O>(mx); argmax_merge(mv, mx, v2, i2); \
-                       const double l2 = wave_xor<O>(ml); if (l2 > ml) ml = l2; }
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 3);
-    out[COL_SUM] = sums[0]; out[COL_NZ] = sums[1]; out[COL_SQ] = sums[2];
-    out[COL_XW] = sums[3]; out[COL_YW] = sums[4]; out[COL_TW] = sums[5];
-    out[COL_MAX] = mv; out[COL_ARG] = mx; out[COL_MLW] = ml;
-}
+    __device__ __forceinline__ double max(int64_t b, int col) const {
+        double r[4];
+        load(b, col, -INFINITY, r);
+        double m = r[0];
+        for (int k = 1; k < 4; k++) if (r[k] > m) m = r[k];
+        return m;
+    }
+    __device__ __forceinline__ void best(int64_t b, int colv, int coli, double &v, double &i) const {
+        double rv[4], ri[4];
+        load(b, colv, -INFINITY, rv);
+        load(b, coli, 9.0e15, ri);
+        v = rv[0]; i = ri[0];
+        for (int k = 1; k < 4; k++) argmax_merge(v, i, rv[k], ri[k]);
+    }
+};
 
-// Block b's entry of a column from the rows of its four wavefronts (k_partials_wave), formed as block_partials' LDS combine forms
-// it, so the bits are the block row's.  A wavefront beyond the population has no row and enters as block_partials' empty wavefront
-// does (`missing`: 0.0 in a sum, -inf as a maximum, 9.0e15 as its index); its load is clamped, not branched round.
-__device__ __forceinline__ void wave_rows_load(const double *__restrict__ p, int64_t b, int col, int64_t nwaves, double missing,
-                                               double (&r)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int64_t wv = 4 * b + k;
-        const double v = p[(wv < nwaves ? wv : nwaves - 1) * GMS_PARTIAL_STRIDE + col];
-        r[k] = wv < nwaves ? v : missing;
-    }
-}
-__device__ __forceinline__ double wave_rows_sum(const double (&r)[4]) { return ((r[0] + r[1]) + r[2]) + r[3]; }
-__device__ __forceinline__ double wave_rows_max(const double (&r)[4]) {
-    double m = r[0];
-    for (int k = 1; k < 4; k++) if (r[k] > m) m = r[k];
-    return m;
-}
-__device__ __forceinline__ void wave_rows_argmax(const double (&rv)[4], const double (&ri)[4], double &v, double &i) {
-    v = rv[0]; i = ri[0];
-    for (int k = 1; k < 4; k++) argmax_merge(v, i, rv[k], ri[k]);
-}
-
-// fold per-block partials in block order.  WAVE (here and in the folds below): p holds the wavefront rows of k_partials_wave,
-// nwaves of them, and a lane forms its block's entries from four rows first (wave_rows_*); everything after that is the same code.
-template <bool WAVE = false>
-__device__ __forceinline__ double fold_sum(const double *__restrict__ p, int64_t nblk, int col, double *lds, int64_t nwaves = 0) {
+// fold per-block partials in block order
+template <class Rows>
+__device__ __forceinline__ double fold_sum(Rows rows, int64_t nblk, int col, double *lds) {
     double acc = 0.0;
-    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
-        if constexpr (WAVE) {
-            double r[4];
-            wave_rows_load(p, b, col, nwaves, 0.0, r);
-            acc += wave_rows_sum(r);
-        } else {
-            acc += p[b * GMS_PARTIAL_STRIDE + col];
-        }
-    }
+    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) acc += rows.sum(b, col);
     return group_sum(acc, lds);
 }
 
@@ -706,167 +721,102 @@ __device__ __forceinline__ double fold_sum(const double *__restrict__ p, int64_t
 // (a fold_sum per column is a dependent memory round trip + two barriers each: 2-3 us of pure latency for the four
 // columns the ray-cast workgroups need).  Per column the arithmetic is fold_sum's, operation for operation: the
 // per-thread strided sum, the wave butterfly, ((w0 + w1) + w2) + w3 over the group's waves -- same bits.
-// WAVE: the 4 NC loads of a block's wavefront rows are issued together too, the three adds per column run in that round trip's shadow.
-template <int NC, bool WAVE = false>
-__device__ __forceinline__ void fold_sums(const double *__restrict__ p, int64_t nblk, const int (&col)[NC], double (&out)[NC],
-                                          RedLds &L, int64_t nwaves = 0) {
-    static_assert(NC <= GMS_PARTIAL_STRIDE, "RedLds::m has GMS_PARTIAL_STRIDE rows");
+// Wavefront rows: the 4 NC loads of a block's rows are in flight together too, the three adds per column run in that round trip's shadow.
+// SCALED: the columns are block-relative (a log-normalising pass, block_partials): block b's entries are multiplied by
+// exp(m_b - M), m_b its own reference (COL_MLW), M the population's.  Same shape, same order.
+template <int NC, bool SCALED = false, class Rows>
+__device__ __forceinline__ void fold_sums(Rows rows, int64_t nblk, const int (&col)[NC], double (&out)[NC], RedLds &L, double M = 0.0) {
+    static_assert(!SCALED || Rows::BLOCK, "a block's own reference is a column of its row: block rows");
+    [[maybe_unused]] const double R = lognorm_ref(M);
     double acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) acc[c] = 0.0;
     for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
         double v[NC];
-        if constexpr (WAVE) {
-            double r[NC][4];
 #pragma unroll
-            for (int c = 0; c < NC; c++) wave_rows_load(p, b, col[c], nwaves, 0.0, r[c]);
+        for (int c = 0; c < NC; c++) v[c] = rows.sum(b, col[c]);
+        if constexpr (SCALED) {
+            const double sc = exp(lognorm_ref(rows.max(b, COL_MLW)) - R);
 #pragma unroll
-            for (int c = 0; c < NC; c++) v[c] = wave_rows_sum(r[c]);
+            for (int c = 0; c < NC; c++) acc[c] += v[c] * sc;
         } else {
 #pragma unroll
-            for (int c = 0; c < NC; c++) v[c] = p[b * GMS_PARTIAL_STRIDE + col[c]];
+            for (int c = 0; c < NC; c++) acc[c] += v[c];
         }
-#pragma unroll
-        for (int c = 0; c < NC; c++) acc[c] += v[c];
     }
 #pragma unroll
-    for (int c = 0; c < NC; c++) acc[c] = wave_sum_f64(acc[c]);
-    const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) L.m[c][wave] = acc[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; c++) out[c] = ((L.m[c][g4] + L.m[c][g4 + 1]) + L.m[c][g4 + 2]) + L.m[c][g4 + 3];
+    for (int c = 0; c < NC; c++) out[c] = wave_sum_f64(acc[c]);
+    group_combine(out, L);
 }
 
-// The same fold over block-relative columns of a log-normalising pass (block_partials): block b's entries are multiplied by
-// exp(m_b - M), m_b its own reference (COL_MLW), M the population's.  Same shape, same order.
-template <int NC>
-__device__ __forceinline__ void fold_sums_scaled(const double *__restrict__ p, int64_t nblk, const int (&col)[NC], double (&out)[NC],
-                                                 RedLds &L, double M) {
-    static_assert(NC <= GMS_PARTIAL_STRIDE, "RedLds::m has GMS_PARTIAL_STRIDE rows");
-    const double R = lognorm_ref(M);
-    double acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++) acc[c] = 0.0;
+// coli < 0: the largest entry of column colv alone, mx its block
+template <class Rows>
+__device__ __forceinline__ void fold_argmax(Rows rows, int64_t nblk, int colv, int coli, double &mv, double &mx, RedLds &L) {
+    mv = -INFINITY; mx = 9.0e15;
+    bool first = true;
     for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
-        double v[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) v[c] = p[b * GMS_PARTIAL_STRIDE + col[c]];
-        const double sc = exp(lognorm_ref(p[b * GMS_PARTIAL_STRIDE + COL_MLW]) - R);
-#pragma unroll
-        for (int c = 0; c < NC; c++) acc[c] += v[c] * sc;
+        double v2, i2;
+        if (coli >= 0) rows.best(b, colv, coli, v2, i2);
+        else { v2 = rows.max(b, colv); i2 = (double)b; }
+        if (first) { mv = v2; mx = i2; first = false; } else argmax_merge(mv, mx, v2, i2);
     }
-#pragma unroll
-    for (int c = 0; c < NC; c++) acc[c] = wave_sum_f64(acc[c]);
-    const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) L.m[c][wave] = acc[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; c++) out[c] = ((L.m[c][g4] + L.m[c][g4 + 1]) + L.m[c][g4 + 2]) + L.m[c][g4 + 3];
+    group_argmax(mv, mx, L.a, L.b);
 }
 
-template <bool WAVE = false>
-__device__ __forceinline__ void fold_argmax(const double *__restrict__ p, int64_t nblk, int colv, int coli, double &mv,
-                                            double &mx, RedLds &L, int64_t nwaves = 0);
 // The log-normalising fold in one piece: the population's reference M = max_b m_b, then the rescaled sums.  Up to GRP blocks
 // (65 536 particles) every thread holds its block's entries from ONE round trip to memory -- this fold sits in front of the ray
 // cast's pose, on the step's critical path --; more blocks take the two passes.  Every caller gets the same bits (one function).
 template <int NC>
-__device__ __forceinline__ double fold_lognorm(const double *__restrict__ p, int64_t nblk, const int (&col)[NC], double (&out)[NC], RedLds &L) {
+__device__ __forceinline__ double fold_lognorm(BlockRows rows, int64_t nblk, const int (&col)[NC], double (&out)[NC], RedLds &L) {
     if (nblk > GRP) {
         double ml, mli;
-        fold_argmax(p, nblk, COL_MLW, -1, ml, mli, L);
-        fold_sums_scaled<NC>(p, nblk, col, out, L, ml);
+        fold_argmax(rows, nblk, COL_MLW, -1, ml, mli, L);
+        fold_sums<NC, true>(rows, nblk, col, out, L, ml);
         return ml;
     }
     const int64_t b = threadIdx.x & (GRP - 1);
     const bool in = b < nblk;
     double v[NC];
 #pragma unroll
-    for (int c = 0; c < NC; c++) v[c] = in ? p[b * GMS_PARTIAL_STRIDE + col[c]] : 0.0;
-    const double mb = in ? p[b * GMS_PARTIAL_STRIDE + COL_MLW] : -INFINITY;
-    double mloc = mb == mb ? mb : -INFINITY;
-#define GMS_STEP_(O) { const double v2 = wave_xor<O>(mloc); if (v2 > mloc) mloc = v2; }
-    GMS_BUTTERFLY(GMS_STEP_)
-#undef GMS_STEP_
-    const int32_t wave = threadIdx.x >> 6, g4 = (wave >> 2) << 2;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) L.b[wave] = mloc;
-    __syncthreads();
-    double M = L.b[g4];
-    for (int k = 1; k < 4; k++) if (L.b[g4 + k] > M) M = L.b[g4 + k];
+    for (int c = 0; c < NC; c++) v[c] = in ? rows.sum(b, col[c]) : 0.0;
+    const double mb = in ? rows.max(b, COL_MLW) : -INFINITY;
+    const double M = group_max(mb == mb ? mb : -INFINITY, L.b);
     const double sc = in ? exp(lognorm_ref(mb) - lognorm_ref(M)) : 0.0;
-    double acc[NC];
 #pragma unroll
-    for (int c = 0; c < NC; c++) acc[c] = wave_sum_f64(0.0 + v[c] * sc);       // (0.0 + x: the strided accumulation of fold_sums_scaled, one term)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) L.m[c][wave] = acc[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; c++) out[c] = ((L.m[c][g4] + L.m[c][g4 + 1]) + L.m[c][g4 + 2]) + L.m[c][g4 + 3];
+    for (int c = 0; c < NC; c++) out[c] = wave_sum_f64(0.0 + v[c] * sc);       // (0.0 + x: the strided accumulation of the scaled fold_sums, one term)
+    group_combine(out, L, GROUP_BARRIER_TAKEN);                                // (group_max ended in a barrier)
     return M;
-}
-
-template <bool WAVE>
-__device__ __forceinline__ void fold_argmax(const double *__restrict__ p, int64_t nblk, int colv, int coli, double &mv,
-                                            double &mx, RedLds &L, int64_t nwaves) {
-    mv = -INFINITY; mx = 9.0e15;
-    bool first = true;
-    for (int64_t b = threadIdx.x & (GRP - 1); b < nblk; b += GRP) {
-        double v2, i2;
-        if constexpr (WAVE) {                                          // the block's entry from its wavefronts' first, in wavefront order
-            double rv[4], ri[4];
-            wave_rows_load(p, b, colv, nwaves, -INFINITY, rv);
-            if (coli >= 0) {
-                wave_rows_load(p, b, coli, nwaves, 9.0e15, ri);
-                wave_rows_argmax(rv, ri, v2, i2);
-            } else {
-                v2 = wave_rows_max(rv); i2 = (double)b;
-            }
-        } else {
-            v2 = p[b * GMS_PARTIAL_STRIDE + colv]; i2 = coli >= 0 ? p[b * GMS_PARTIAL_STRIDE + coli] : (double)b;
-        }
-        if (first) { mv = v2; mx = i2; first = false; } else argmax_merge(mv, mx, v2, i2);
-    }
-    group_argmax(mv, mx, L.a, L.b);
 }
 
 // all statistics from the (all-reduced) partial vector; every thread of the workgroup must call.  lognorm: the columns are
 // block-relative (block_partials): *ref_out receives M, the population's largest log-weight, the returned sum is sum exp(logw - M).
-// WAVE: p holds wavefront rows (fold_sum; plain normalisation only: a log-normalising pass keeps block rows).
-template <bool WAVE = false>
-__device__ __forceinline__ double fold_stats(const double *__restrict__ p, int64_t nblk, PfStatsDev *s, bool write,
+// LOGNORM = false: compiled without the log-normalising form, `lognorm` is not read; wavefront rows must say so (a
+// log-normalising pass keeps block rows).
+template <bool LOGNORM = true, class Rows>
+__device__ __forceinline__ double fold_stats(Rows rows, int64_t nblk, PfStatsDev *s, bool write,
                                              const float *__restrict__ pose, int64_t pose_base, int64_t pose_n, RedLds &L,
-                                             const PackedParticle *__restrict__ glob = nullptr, bool lognorm = false, double *ref_out = nullptr,
-                                             int64_t nwaves = 0) {
+                                             const PackedParticle *__restrict__ glob = nullptr, bool lognorm = false, double *ref_out = nullptr) {
+    static_assert(!LOGNORM || Rows::BLOCK, "a log-normalising fold needs its block's reference: block rows");
     double ml = 0.0, mli;
-    if constexpr (WAVE) lognorm = false;
+    if constexpr (!LOGNORM) lognorm = false;
     if (!write) {
-        if (!lognorm) return fold_sum<WAVE>(p, nblk, COL_SUM, L.a, nwaves);
-        const int c1[1] = { COL_SUM };
-        double f1[1];
-        ml = fold_lognorm<1>(p, nblk, c1, f1, L);
-        if (ref_out) *ref_out = ml;
-        return f1[0];
+        if (!lognorm) return fold_sum(rows, nblk, COL_SUM, L.a);
+        if constexpr (LOGNORM) {
+            const int c1[1] = { COL_SUM };
+            double f1[1];
+            ml = fold_lognorm<1>(rows, nblk, c1, f1, L);
+            if (ref_out) *ref_out = ml;
+            return f1[0];
+        }
     }
     const int cols[5] = { COL_SUM, COL_NZ, COL_XW, COL_YW, COL_TW };
     double f[5];
-    if (lognorm) { ml = fold_lognorm<5>(p, nblk, cols, f, L); if (ref_out) *ref_out = ml; }
-    else fold_sums<5, WAVE>(p, nblk, cols, f, L, nwaves);
+    if (lognorm) { if constexpr (LOGNORM) { ml = fold_lognorm<5>(rows, nblk, cols, f, L); if (ref_out) *ref_out = ml; } }
+    else fold_sums<5>(rows, nblk, cols, f, L);
     const double sum = f[0], nz = f[1], xw = f[2], yw = f[3], tw = f[4];
     double mv, mx;
-    fold_argmax<WAVE>(p, nblk, COL_MAX, COL_ARG, mv, mx, L, nwaves);
-    if (!lognorm) fold_argmax<WAVE>(p, nblk, COL_MLW, -1, ml, mli, L, nwaves);
+    fold_argmax(rows, nblk, COL_MAX, COL_ARG, mv, mx, L);
+    if (!lognorm) fold_argmax(rows, nblk, COL_MLW, -1, ml, mli, L);
     if (threadIdx.x == 0) {
         s->n_ambiguous = 0;
         s->weight_sum = sum;
@@ -956,25 +906,16 @@ k_partials(const double *__restrict__ part, const float *__restrict__ pose, PfSt
 
 // The block partials of a stand-alone single-map filter as one row per WAVEFRONT (wave_partials): workgroups of 64 lanes, no
 // barrier, no LDS, no atomics; rows[(n + 63) / 64][GMS_PARTIAL_STRIDE], read by k_norm_raycast<false, true> alone.
-// Workgroup id -> wavefront: GMS_WAVE_PARTIALS_XCD_BLOCKS = 1 gives the four wavefronts of a block to ids eight apart (one XCD, id & 7),
-// 0 takes them in id order (a block's wavefronts on four XCDs).  The grid covers whole groups of 32 under the first form; a wavefront
-// beyond the population leaves at once.  By the stamps at C3 the two are one (three runs each, medians, 0 / 1: entered -> left 3.06 /
-// 3.04 us, entered -> the next launch's pose folded 6.96 / 6.81 with 0.2 between the runs of either): the plain order stays.
-#ifndef GMS_WAVE_PARTIALS_XCD_BLOCKS
-#define GMS_WAVE_PARTIALS_XCD_BLOCKS 0
-#endif
-static_assert(EPT == 1 && GMS_BLOCK == 4 * GMS_WAVE, "a reduction block is four wavefronts of one particle per lane");
+// Workgroup id -> wavefront: in id order, so a block's four wavefronts run on four XCDs.  Giving them to ids eight apart instead (one
+// XCD, id & 7) measured the same by the stamps at C3 (three runs each, medians, id order / one XCD: entered -> left 3.06 / 3.04 us,
+// entered -> the next launch's pose folded 6.96 / 6.81 with 0.2 between the runs of either; profiles/wave_partials, recorded by the
+// commit "Scan step: block partials as one row per wavefront, no LDS pass"): the plain order stayed.
 __global__ void __launch_bounds__(64)
 k_partials_wave(const double *__restrict__ part, const float *__restrict__ pose, int32_t n, int32_t part_nseg,
                 double *__restrict__ w, double *__restrict__ logw, double *__restrict__ rows) {
     // (argument order: the segment products, the poses and what their addresses are formed from lead: see k_score_c)
     GMS_STAMP(GMS_STAMP_ROW(1, blockIdx.x), 0);
-#if GMS_WAVE_PARTIALS_XCD_BLOCKS
-    const uint32_t j = blockIdx.x >> 3;
-    const int64_t wv = 4 * (int64_t)((j >> 2) * 8 + (blockIdx.x & 7)) + (j & 3);
-#else
     const int64_t wv = blockIdx.x;
-#endif
     if (wv * GMS_WAVE >= n) return;                                     // (uniform)
     double out[GMS_PARTIAL_STRIDE];
     wave_partials(w, logw, pose, n, wv * GMS_WAVE + threadIdx.x, out, part, part_nseg);
@@ -1123,10 +1064,10 @@ resample_prefix_last(const double *__restrict__ p2, int64_t nblk, const double *
 // phase 2: every workgroup folds the (all-reduced) partials; weight /= weightSum (SLAM.java:120-121);
 // packs {w,x,y,theta} (the all-gather payload / the resampling source).  A stand-alone filter also
 // gets the dense weight copy and level 0 of the cumulative weights here (cum != nullptr).
-// WAVE: partials_all holds the wavefront rows of k_partials_wave (one map, the whole population here: (n + 63) / 64 rows).
-template <bool WAVE = false>
+// rows_all: the partial vectors of all maps, nblk_global rows each (wavefront rows: one map's).  LOGNORM: as fold_stats'.
+template <bool LOGNORM = true, class Rows>
 __device__ __forceinline__ void
-normalize_pack_body(const double *__restrict__ partials_all, int64_t nblk_global, double *__restrict__ w,
+normalize_pack_body(Rows rows_all, int64_t nblk_global, double *__restrict__ w,
                     const float *__restrict__ pose, int32_t n, int64_t offset, PackedParticle *__restrict__ packed,
                     double *__restrict__ cum, double *__restrict__ chunk_tot, int64_t nchunks,
                     double *__restrict__ p2_all, PfStatsDev *__restrict__ stats, uint32_t bx, uint32_t by,
@@ -1136,10 +1077,10 @@ normalize_pack_body(const double *__restrict__ partials_all, int64_t nblk_global
     // formed here from the log-weights, exp(logw - M) / sum
     __shared__ RedLds L;
     const int32_t mi = (int32_t)by;
-    const double *p = partials_all + (size_t)mi * nblk_global * GMS_PARTIAL_STRIDE;
+    Rows rows = rows_all;
+    rows.p += (size_t)mi * nblk_global * GMS_PARTIAL_STRIDE;
     double M = 0.0;
-    const double sum = fold_stats<WAVE>(p, nblk_global, stats + mi, bx == 0, pose + (size_t)mi * n * 3, offset, n, L, nullptr, logw_lognorm != nullptr, &M,
-                                        ((int64_t)n + 63) / 64);
+    const double sum = fold_stats<LOGNORM>(rows, nblk_global, stats + mi, bx == 0, pose + (size_t)mi * n * 3, offset, n, L, nullptr, logw_lognorm != nullptr, &M);
     const int32_t i = (int32_t)bx * 256 + threadIdx.x;
     double wn = 0.0;
     if (logw_lognorm) {                                                    // (uniform)
@@ -1169,7 +1110,7 @@ k_normalize_pack(const double *__restrict__ partials_all, int64_t nblk_global, d
                  const float *__restrict__ pose, int32_t n, int64_t offset, PackedParticle *__restrict__ packed,
                  double *__restrict__ cum, double *__restrict__ chunk_tot, int64_t nchunks,
                  double *__restrict__ p2_all, PfStatsDev *__restrict__ stats, const double *__restrict__ logw_lognorm) {
-    normalize_pack_body(partials_all, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2_all, stats, blockIdx.x,
+    normalize_pack_body(BlockRows{ partials_all }, nblk_global, w, pose, n, offset, packed, cum, chunk_tot, nchunks, p2_all, stats, blockIdx.x,
                         blockIdx.y, logw_lognorm);
 }
 
@@ -1210,7 +1151,7 @@ normalize_own_body(const double *__restrict__ partials, int64_t nblk_global, dou
                    int32_t n, int64_t offset, const PackedParticle *__restrict__ glob_raw, PfStatsDev *__restrict__ stats,
                    uint32_t bx) {
     __shared__ RedLds L;
-    const double sum = fold_stats(partials, nblk_global, stats, bx == 0, pose, offset, n, L, glob_raw);
+    const double sum = fold_stats(BlockRows{ partials }, nblk_global, stats, bx == 0, pose, offset, n, L, glob_raw);
     const int32_t i = (int32_t)bx * 256 + threadIdx.x;
     if (i < n) w[i] = w[i] / sum;
 }
@@ -1222,7 +1163,7 @@ chunk_sums_raw_body(const PackedParticle *__restrict__ glob_raw, int64_t n_globa
                     double *__restrict__ chunk_tot, double *__restrict__ p2, int64_t nblk_global,
                     const double *__restrict__ partials, uint32_t bx) {
     __shared__ RedLds L;
-    const double sum = fold_sum(partials, nblk_global, COL_SUM, L.a);
+    const double sum = fold_sum(BlockRows{ partials }, nblk_global, COL_SUM, L.a);
     const int64_t i = (int64_t)bx * 256 + threadIdx.x;
     const double v = i < n_global ? glob_raw[i].w / sum : 0.0;
     block_chunk_scan(v, i, n_global, bx, nchunks, cum, chunk_tot, p2 + (size_t)bx * 2, chunk_sub_of(chunk_tot, nchunks, 1, 0));
@@ -1245,7 +1186,7 @@ k_stats_only(const double *__restrict__ partials_all, int64_t nblk_global, const
              int64_t offset, PfStatsDev *__restrict__ stats) {
     __shared__ RedLds L;
     const int32_t mi = blockIdx.x;
-    fold_stats(partials_all + (size_t)mi * nblk_global * GMS_PARTIAL_STRIDE, nblk_global, stats + mi, true,
+    fold_stats(BlockRows{ partials_all + (size_t)mi * nblk_global * GMS_PARTIAL_STRIDE }, nblk_global, stats + mi, true,
                pose + (size_t)mi * n * 3, offset, n, L);
 }
 
@@ -1843,10 +1784,7 @@ bool gms_pf_wave_partials_now(const gms_pf *pf) {
 void gms_launch_pf_partials_wave(gms_pf *pf) {
     gms_map *m = pf->map;
     ProfScope ps(m, GMS_K_REDUCE);
-    uint32_t grid = (uint32_t)nchunks_of(pf);                          // a scan chunk is a wavefront's 64 particles
-#if GMS_WAVE_PARTIALS_XCD_BLOCKS
-    grid = (grid + 31u) / 32u * 32u;
-#endif
+    const uint32_t grid = (uint32_t)nchunks_of(pf);                    // a scan chunk is a wavefront's 64 particles
     hipLaunchKernelGGL(k_partials_wave, dim3(grid), dim3(GMS_WAVE), 0, m->stream,
                        pf->pending_nseg ? (const double *)pf->d_part : (const double *)nullptr, pf->d_pose, pf->n, pf->pending_nseg,
                        pf->d_w, pf->d_logw, pf->d_wave_partials);

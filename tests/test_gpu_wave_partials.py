@@ -138,6 +138,39 @@ def test_populations_at_the_wavefront_and_block_edges(n):
     _step_against_separate(n, lambda k: _cloud(n, k), lambda k: _trace().scans[WARM + k], B)
 
 
+@pytest.mark.parametrize("n", [64, 320, 1088])
+@pytest.mark.parametrize("route", ["log-normalising", "two maps"])
+def test_block_rows_of_the_scan_step_equal_the_separate_calls(n, route):
+    """The two routes of the scan step that keep BLOCK rows, where the tests above take wavefront rows: log-normalisation on
+    (k_partials' block-relative rows through the scaled fold) and two maps in one handle under plain normalisation (the batched
+    k_partials).  Each against gms_pf_score -> normalize -> stats on a filter of its own, bit for bit: the weights, the
+    statistics (weight_sum, strongest, n_zero, max_log_weight) and the weighted pose.  No resampling, and the separate calls go
+    first: the weights stay comparable and both filters score against the same map, which the step then updates."""
+    M = 2 if route == "two maps" else 1
+    tr = _trace()
+    m = GridMap(EXT, EXT, RES, ORIGIN, n_maps=M, max_beams=384)
+    for t in range(WARM):
+        m.update(np.stack([tr.scans[t]] * M) if M > 1 else tr.scans[t], np.stack([tr.poses[t]] * M) if M > 1 else tr.poses[t])
+    P = np.stack([synth.make_particles(tr.poses[WARM], n, seed=60 + i, sigma_xy=0.03, sigma_theta_deg=2.0) for i in range(M)])
+    scan = np.stack([tr.scans[WARM]] * M) if M > 1 else tr.scans[WARM]
+    step, sep = ParticleFilter(m, n), ParticleFilter(m, n)
+    for f in (step, sep):
+        f.set_log_normalize(route == "log-normalising")
+    sep.set_poses(P if M > 1 else P[0]); sep.score(scan)
+    st_sep = sep.normalize()
+    step.slam_update(P if M > 1 else P[0], scan, np.full(M, 0.4), 0.0, True)
+    st_step = step.stats()
+    keys = {"weight_sum", "strongest", "n_zero", "max_log_weight"}
+    for a, b in zip(st_step if M > 1 else [st_step], st_sep if M > 1 else [st_sep]):
+        assert set(a) >= keys and {k: a[k] for k in keys} == {k: b[k] for k in keys} and a["weight_sum"] > 0, (route, n, a, b)
+    assert np.array_equal(step.get_weights(), sep.get_weights()), (route, n)
+    assert np.array_equal(step.get_log_weights(), sep.get_log_weights()), (route, n)
+    assert np.array_equal(step.last_step()["weighted_pose"], sep.last_step()["weighted_pose"]), (route, n)
+    assert np.array_equal(np.asarray(step.last_step()["weighted_pose"]).reshape(M, 3), np.asarray(sep.weighted_pose()).reshape(M, 3)), (route, n)
+    for h in (step, sep, m):
+        h.close()
+
+
 N_PAT = 576                                      # blocks 0 and 1 full, block 2 one wavefront
 
 
