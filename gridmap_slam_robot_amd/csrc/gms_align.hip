@@ -6,10 +6,10 @@
 // differently for it.
 //
 //   k_align        one wavefront per pose, four poses per workgroup of 256 lanes, grid (ceil(P / 4), maps).  The workgroup stages the
-//                  scan's (local_x, local_y) in LDS once, 16 bytes per beam, NaN for a beam that did not hit -- the USED test refuses a
-//                  NaN by itself, so the loop needs no hit flag.  Lane l owns partial l: it walks the beams l, l + 64, ... in ascending
-//                  order, two adjacent field values per row (16 bytes, 8-byte aligned) and two rows per look-up, and adds the ten
-//                  terms into its registers (gms_align_device.h, shared with k_slam_align).  The halving tree p[l] += p[l + s], s = 32 .. 1, runs as cross-lane register moves
+//                  scan's (local_x, local_y) in LDS once, 16 bytes per beam (align_stage_scan).  Lane l owns partial l: it walks the
+//                  beams l, l + 64, ... in ascending order, two adjacent field values per row (16 bytes, 8-byte aligned) and two rows
+//                  per look-up, and adds the ten terms into its registers (gms_align_device.h, shared with k_slam_align: staging,
+//                  evaluation, step and store).  The halving tree p[l] += p[l + s], s = 32 .. 1, runs as cross-lane register moves
 //                  (wave_xor: for l < s lane l ^ s IS lane l + s) with the add kept to the lanes l < s; lane 0's sums are broadcast and
 //                  every lane solves the 3 x 3 system alike, so the loop over the iterations is uniform per wavefront.  A stopped
 //                  pose leaves the loop; its wavefront idles until the workgroup's other three are done.
@@ -35,10 +35,7 @@ k_align(GridDev g, const double *__restrict__ lik, int64_t lik_stride, const gms
     const int32_t tid = (int32_t)threadIdx.x, lane = tid & 63, mi = (int32_t)blockIdx.y;
     lik += (size_t)mi * (size_t)lik_stride;
     beams += (size_t)mi * (size_t)beam_stride;
-    for (int32_t b = tid; b < B; b += ALIGN_NT) {
-        const gms_beam m = beams[b];
-        s_beam[b] = m.hit != 0 ? make_double2(m.local_x, m.local_y) : make_double2(NAN, NAN);
-    }
+    align_stage_scan(s_beam, beams, B, tid, ALIGN_NT);
     __syncthreads();
     const int32_t p = (int32_t)blockIdx.x * ALIGN_WAVES + (tid >> 6);
     if (p >= P) return;                                                         // (uniform per wavefront; no barrier follows)
@@ -54,13 +51,7 @@ k_align(GridDev g, const double *__restrict__ lik, int64_t lik_stride, const gms
         if (align_advance(e, k, prm, g.res, x, y, theta, status, done)) break;
     }
     if (lane != 0) return;
-    pose_out[3 * gi] = x; pose_out[3 * gi + 1] = y; pose_out[3 * gi + 2] = theta;
-    if (cs) {
-        float cf, sf;
-        pose_trig(theta, cf, sf);
-        cs[2 * gi] = cf; cs[2 * gi + 1] = sf;
-    }
-    if (rec) rec[gi] = align_record(e, status, done, n0, s0);
+    align_store(pose_out, cs, rec, gi, x, y, theta, e, status, done, n0, s0);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------

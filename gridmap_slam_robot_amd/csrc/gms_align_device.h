@@ -1,6 +1,7 @@
 // gms_align_device.h -- the arithmetic of the continuous scan alignment (gridmapslam.h "continuous scan alignment") that its kernels
 // share: k_align (gms_align.hip: poses on one field in memory) and k_slam_align (gms_slam_align.hip: every particle on its own field).
-// One copy of the per-beam terms, the halving tree, the adjugate solve and the step: bit parity between the two rests on it.
+// One copy of the scan's staging, the per-beam terms, the halving tree, the adjugate solve, the step and the final store: bit parity
+// between the two rests on it.
 #pragma once
 #include <math.h>
 
@@ -84,6 +85,15 @@ __device__ __forceinline__ void align_add(AlignSums &a, const GridDev &g, const 
     a.n++;
 }
 
+// the scan's (local_x, local_y) into s_beam [B], NaN for a beam that did not hit -- the USED test refuses a NaN by itself, so the
+// evaluation needs no hit flag; the workgroup's nt lanes stride over the beams (the caller's barrier follows)
+__device__ __forceinline__ void align_stage_scan(double2 *s_beam, const gms_beam *__restrict__ beams, int32_t B, int32_t tid, int32_t nt) {
+    for (int32_t b = tid; b < B; b += nt) {
+        const gms_beam m = beams[b];
+        s_beam[b] = m.hit != 0 ? make_double2(m.local_x, m.local_y) : make_double2(NAN, NAN);
+    }
+}
+
 // one evaluation at the pose (x, y, theta) by one wavefront: lane l owns partial l and walks the beams l, l + 64, ... in ascending
 // order; every lane returns the same sums.  s_beam: the scan's (local_x, local_y), NaN for a beam that did not hit (the USED test
 // refuses it).  fetch(b, i0, j0, l00, l10, l01, l11): the field's four values of beam b, whose cells have passed the test
@@ -142,11 +152,20 @@ __device__ __forceinline__ bool align_advance(const AlignSums &e, int32_t k, con
     return false;
 }
 
-// a pose's record from its last evaluation e and the first one's (n0, s0)
-__device__ __forceinline__ gms_align_record align_record(const AlignSums &e, int32_t status, int32_t done, int32_t n0, double s0) {
+// What one lane stores of pose i when its loop has ended: the pose, its float-rounded trig (cs NULL: none) and its record (rec NULL:
+// none) from the last evaluation e and the first one's (n0, s0)
+__device__ __forceinline__ void align_store(float *pose, float *cs, gms_align_record *rec, size_t i, float x, float y, float theta, const AlignSums &e,
+                                            int32_t status, int32_t done, int32_t n0, double s0) {
+    pose[3 * i] = x; pose[3 * i + 1] = y; pose[3 * i + 2] = theta;
+    if (cs) {
+        float cf, sf;
+        pose_trig(theta, cf, sf);
+        cs[2 * i] = cf; cs[2 * i + 1] = sf;
+    }
+    if (!rec) return;
     gms_align_record r;
     r.status = status; r.iters_done = done; r.n_used = e.n; r.n_used0 = n0;
     r.score0 = s0; r.score = e.s;
     r.H[0] = e.h00; r.H[1] = e.h01; r.H[2] = e.h02; r.H[3] = e.h11; r.H[4] = e.h12; r.H[5] = e.h22;
-    return r;
+    rec[i] = r;
 }

@@ -4,13 +4,9 @@
 // A translation unit of its own, kernels and C-ABI, on the query base beside gms_cast.hip: no kernel of the other units is compiled
 // differently for it.
 //
-//   k_beam_score   one workgroup of 256 lanes per (particle, map).  Lane l owns partial l: it walks the beams l, l + 256, ... of the scan
-//                  one after another with `ahead` extra cells through the map's GMS_CLEAR_OCCUPIED plane to the first set bit
-//                  (beam_walk, gms_probe.h), takes the table index from the iterator's remaining count there, and multiplies / adds
-//                  the two tables' entries into its partials.  In front of the walks the workgroup stages the window of its rays
-//                  (PlaneWindow: every lane's box over its beams, padded by ahead + 1) when it fits what the launch asked for; a
-//                  window that does not fit, or GMS_CAST_WALK=mem: every bit from memory.  What the window may and may not decide:
-//                  PlaneWindow::bit.  The 256 partials meet in a halving tree through LDS.
+//   k_beam_score   one workgroup of 256 lanes per (particle, map): the pose's transform, beam_score (gms_beams_device.h: the window, the
+//                  walks, the partials, the tree) over the map's GMS_CLEAR_OCCUPIED plane, the store.  The per-particle form is
+//                  k_slam_beam_score (gms_slam_beams.hip): the same body over another source.
 //
 // LDS: min(64 KiB, the whole plane of one map) of window + 4 KiB of partials -- two workgroups per CU at the cap.  Every walk's loop
 // carries the bound W + H + ahead + 2; the loop over a lane's beams ends at B <= max_beams.
@@ -21,11 +17,15 @@
 
 #include <algorithm>
 
-#include "gms_probe.h"
+#include "gms_beams_device.h"
 
-#define BEAM_NT 256
-#define BEAM_LDS_CAP (64 * 1024)         // the window: bytes of LDS a workgroup asks for at most
-#define BEAM_TAB_BYTES GMS_BEAM_TAB_BYTES
+// beam_score's source over a packed plane in memory
+struct BeamPlaneSource {
+    const uint32_t *__restrict__ plane;
+    int32_t wpr;
+    __device__ __forceinline__ void fill(const PlaneWindow &win, uint32_t *s_win, int32_t tid) const { win.stage(s_win, plane, wpr, tid, BEAM_NT); }
+    __device__ __forceinline__ bool mem(int32_t x, int32_t y) const { return plane_bit(plane, wpr, x, y); }
+};
 
 // grid (particles, maps).  plane: map 0's, the maps plane_stride words apart; beams: map 0's, the maps beam_stride apart; tab:
 // factors [2][T] then their logarithms [2][T]; residuals: [n_maps][n][B] or NULL; lds_words: the window the launch asked for (0: walk memory)
@@ -37,44 +37,12 @@ k_beam_score(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, int64_t
     extern __shared__ __align__(16) uint32_t s_win[];
     __shared__ double s_p[BEAM_NT], s_s[BEAM_NT];
     __shared__ int32_t s_box[4];
-    const int32_t tid = (int32_t)threadIdx.x, mi = (int32_t)blockIdx.y;
+    const int32_t mi = (int32_t)blockIdx.y;
     const size_t gi = (size_t)mi * (size_t)n + (size_t)blockIdx.x;
-    plane += (size_t)mi * (size_t)plane_stride;
-    beams += (size_t)mi * (size_t)beam_stride;
-    const int32_t top = behind + ahead + 1, T = top + 1;
-    const XformDev t = pose_xform(pose + 3 * gi, cs + 2 * gi);
-    PlaneWindow win;                                                                            // (none: walk memory)
-    if (lds_words > 0) {
-        if (tid == 0) { s_box[0] = g.W; s_box[1] = g.H; s_box[2] = -1; s_box[3] = -1; }
-        __syncthreads();
-        int32_t box[4];
-        PlaneWindow::box_none(box, g.W, g.H);
-        for (int32_t b = tid; b < B; b += BEAM_NT) PlaneWindow::box_add(box, make_ray(g, t, beams[b]), g.W, g.H);
-        if (tid < B) PlaneWindow::box_merge(s_box, box);
-        __syncthreads();
-        win = PlaneWindow::clip(s_box, ahead + 1, g.W, g.H, lds_words);
-        win.stage(s_win, plane, wpr, tid, BEAM_NT);
-        __syncthreads();
-    }
-    double p = 1.0, s = 0.0;
-    uint16_t *__restrict__ res = residuals ? residuals + gi * (size_t)B : nullptr;
-    for (int32_t b = tid; b < B; b += BEAM_NT) {
-        const RayIn ray = make_ray(g, t, beams[b]);
-        int32_t idx;
-        if (win.ww > 0) idx = beam_walk(g, ray, ahead, top, [&](int32_t x, int32_t y) { return win.bit(s_win, plane, wpr, x, y); });
-        else idx = beam_walk(g, ray, ahead, top, [&](int32_t x, int32_t y) { return plane_bit(plane, wpr, x, y); });
-        const int32_t at = (ray.hit ? T : 0) + idx;
-        p = p * tab[at];
-        s = s + tab[2 * T + at];
-        if (res) res[b] = (uint16_t)idx;
-    }
-    s_p[tid] = p; s_s[tid] = s;
-    __syncthreads();
-    for (int32_t h = BEAM_NT / 2; h >= 1; h >>= 1) {
-        if (tid < h) { s_p[tid] = s_p[tid] * s_p[tid + h]; s_s[tid] = s_s[tid] + s_s[tid + h]; }
-        __syncthreads();
-    }
-    if (tid == 0) { wgt[gi] = s_p[0]; logw[gi] = s_s[0]; }
+    const BeamPlaneSource src{plane + (size_t)mi * (size_t)plane_stride, wpr};
+    const BeamSums sums = beam_score(g, pose_xform(pose + 3 * gi, cs + 2 * gi), beams + (size_t)mi * (size_t)beam_stride, B, behind, ahead, tab,
+                                     residuals, gi, lds_words, s_win, s_p, s_s, s_box, src);
+    if (threadIdx.x == 0) { wgt[gi] = sums.p; logw[gi] = sums.s; }
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
@@ -89,6 +57,28 @@ int gms_beam_model_check_for(int32_t behind, int32_t ahead, const double *factor
     return GMS_OK;
 }
 
+int gms_beam_table_put(gms_map *m, BeamTables &bt, const char *who, int32_t behind, int32_t ahead, const double *factors, int32_t which, int32_t n_tables) {
+    if (!bt.ring_ready) {
+        const int rc = gms_ring_alloc(bt.ring, GMS_BEAM_TAB_BYTES);
+        if (rc) { gms_ring_free(bt.ring); return rc; }
+        bt.ring_ready = 1;
+    }
+    int rc = gms_dev_alloc(&bt.d_tab, (size_t)n_tables * GMS_BEAM_TAB_BYTES, who, "the factor tables");
+    if (rc) return rc;
+    void *slot = nullptr;
+    rc = gms_ring_acquire(bt.ring, &slot);
+    if (rc) return rc;
+    const int32_t T = behind + ahead + 2;
+    double *h = static_cast<double *>(slot);
+    for (int32_t i = 0; i < 2 * T; i++) { h[i] = factors[i]; h[2 * T + i] = log(factors[i]); }
+    gms_launch_copy(m, bt.d_tab + (size_t)which * 4 * GMS_BEAM_T_MAX, h, (size_t)4 * T * sizeof(double));
+    return gms_ring_commit(bt.ring, m->stream);
+}
+void gms_beam_table_free(BeamTables &bt) {
+    hipFree(bt.d_tab); gms_ring_free(bt.ring);
+    bt.d_tab = nullptr; bt.ring_ready = 0;
+}
+
 static int pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t behind, int32_t ahead, const double *factors, uint16_t *residuals,
                           bool on_device) {
     const char *who = on_device ? "gms_pf_score_beams_dev" : "gms_pf_score_beams";
@@ -101,23 +91,7 @@ static int pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t 
     if (B < 1 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= B <= gms_params.max_beams beams", who);
     if (on_device && ((uintptr_t)residuals & 1) != 0) return gms_fail(GMS_ERR_INVALID, "%s: the residuals must be 2-byte aligned", who);
     HIPCHK(hipSetDevice(m->device));
-    // the tables: factors [2][T], then log() of each, through a pinned slot into the filter's device copy
-    const int32_t T = behind + ahead + 2;
-    auto &bm = pf->beam;
-    if (!bm.ring_ready) {
-        rc = gms_ring_alloc(bm.ring, BEAM_TAB_BYTES);
-        if (rc) { gms_ring_free(bm.ring); return rc; }
-        bm.ring_ready = 1;
-    }
-    rc = gms_dev_alloc(&bm.d_tab, BEAM_TAB_BYTES, who, "the factor tables");
-    if (rc) return rc;
-    void *slot = nullptr;
-    rc = gms_ring_acquire(bm.ring, &slot);
-    if (rc) return rc;
-    double *h = static_cast<double *>(slot);
-    for (int32_t i = 0; i < 2 * T; i++) { h[i] = factors[i]; h[2 * T + i] = log(factors[i]); }
-    gms_launch_copy(m, bm.d_tab, h, (size_t)4 * T * sizeof(double));
-    rc = gms_ring_commit(bm.ring, m->stream);
+    rc = gms_beam_table_put(m, pf->beam, who, behind, ahead, factors, 0, 1);
     if (rc) return rc;
     const gms_beam *d_beams;
     int32_t beam_stride;
@@ -138,7 +112,7 @@ static int pf_score_beams(gms_pf *pf, const gms_beam *beams, int32_t B, int32_t 
     const int64_t lds_words = m->cast_walk_mem ? 0 : std::min<int64_t>(BEAM_LDS_CAP / 4, plane_stride);
     HIPCHK(gms_kernel_lds<k_beam_score>(m->device, BEAM_LDS_CAP));
     hipLaunchKernelGGL(k_beam_score, dim3((unsigned)pf->n, (unsigned)pf->n_maps), dim3(BEAM_NT), (size_t)lds_words * 4, m->stream, m->gd, plane, wpr,
-                       plane_stride, d_beams, B, beam_stride, pf->d_pose, pf->d_cs, pf->n, behind, ahead, bm.d_tab, pf->d_w, pf->d_logw,
+                       plane_stride, d_beams, B, beam_stride, pf->d_pose, pf->d_cs, pf->n, behind, ahead, pf->beam.d_tab, pf->d_w, pf->d_logw,
                        residuals ? st.at(p_res, residuals) : nullptr, (int32_t)lds_words);
     HIPCHK(hipGetLastError());
     pf_scored(pf, 0);                                                                           // the state a gms_pf_score leaves

@@ -82,8 +82,9 @@ k_cast_map(GridDev g, const uint32_t *__restrict__ plane, int32_t wpr, int64_t p
     }
     if (b >= B) return;
     gms_cast_hit h;
-    if (win.ww > 0) h = cast_walk(g, ray, [&](int32_t x, int32_t y) { return win.bit(s_win, plane, wpr, x, y); });
-    else h = cast_walk(g, ray, [&](int32_t x, int32_t y) { return plane_bit(plane, wpr, x, y); });
+    const auto mem = [&](int32_t x, int32_t y) { return plane_bit(plane, wpr, x, y); };
+    if (win.ww > 0) h = cast_walk(g, ray, [&](int32_t x, int32_t y) { return win.bit(s_win, x, y, mem); });
+    else h = cast_walk(g, ray, mem);
     cast_store(out + (size_t)pi * (size_t)B + (size_t)b, h);
 }
 

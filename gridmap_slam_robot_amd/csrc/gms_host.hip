@@ -969,7 +969,7 @@ int gms_pf_destroy(gms_pf *pf) {
     hipFree(pf->d_ord); hipFree(pf->d_perm);
     hipFree(pf->modes.d_part); hipFree(pf->modes.d_bins); hipFree(pf->modes.d_table); hipFree(pf->modes.d_ctl);
     if (pf->modes.h_ctl) hipHostFree(pf->modes.h_ctl);
-    hipFree(pf->beam.d_tab); ring_free(pf->beam.ring);
+    gms_beam_table_free(pf->beam);
     pf_free_global(pf);
     if (pf->h_stats) hipHostFree(pf->h_stats);
     if (pf->h_stage) hipHostFree(pf->h_stage);

@@ -88,6 +88,14 @@ struct StageRing {
     int32_t next = 0;
 };
 
+// The beam sensor model's factor tables on the device (gms_beams.hip): n_tables slots of GMS_BEAM_TAB_BYTES, each factors [2][T] | their
+// logarithms [2][T], T = behind + ahead + 2 <= GMS_BEAM_T_MAX; allocated by the first gms_beam_table_put, freed by gms_beam_table_free
+struct BeamTables {
+    double *d_tab;
+    StageRing ring;                 // pinned staging of a table on its way
+    int32_t ring_ready;
+};
+
 struct gms_map {
     gms_params prm;
     GridDev gd;
@@ -292,12 +300,7 @@ struct gms_pf {
         uint32_t *d_ctl;            // {modes, modes with count >= min_count, OUTSIDE particles, spare}
         uint32_t *h_ctl;            // pinned: read back once per request
     } modes;
-    // the beam sensor model (gms_beams.hip): the last call's tables, allocated by the first call
-    struct {
-        double *d_tab;              // factors [2][T] | their logarithms [2][T], T = behind + ahead + 2 <= 512
-        StageRing ring;             // pinned staging of those
-        int32_t ring_ready;
-    } beam;
+    BeamTables beam;                // the beam sensor model (gms_beams.hip): ONE table, the last call's
     int32_t slam_owned;            // the filter of a gms_slam: its particles own maps, so resampling, sharding and the shared-map scan steps are refused on it
     int32_t *d_epoch2;              // the filter of a gms_slam, inside its draw only (slam_draw): {draws that ran so far, the last resample() drew}, kept by the resampling kernels (NULL otherwise)
     // What the derived device data describes.  Written by the pf_* transitions below only (and pf_alloc_global / pf_free_global).
@@ -410,6 +413,7 @@ struct SlamBatch {
     const SlamFilterArgs *tab;
     int32_t n, beam_stride;
 };
+static inline SlamBatch slam_batch_of(const gms_pf *pf, const SlamBatch *batch) { return batch ? *batch : SlamBatch{nullptr, pf->n, 0}; }
 
 // where the likelihoodData of a gms_slam's particles stands between the calls that write it
 enum SlamField : int32_t {
@@ -467,11 +471,7 @@ struct gms_slam {
     gms_align_record *d_align_rec;  // [n] the records of the last aligned update (allocated by gms_slam_set_align)
     int32_t have_align_rec;         // an aligned update has run since they were allocated
     // the beam sensor model on the particles' own maps (gms_slam_score_beams, gms_slam_set_beam_model; gms_slam_beams.hip)
-    struct {
-        double *d_tab;              // two tables, each factors [2][T] | their logarithms [2][T] in GMS_BEAM_TAB_BYTES: [0] the last
-                                    // stand-alone call's, [1] the model's that every update applies
-        StageRing ring;             // pinned staging of either
-        int32_t ring_ready;
+    struct : BeamTables {           // TWO tables: [0] the last stand-alone call's, [1] the model's that every update applies
         double *d_wgt;              // [n] beam weights | [n] beam log-weights of the update under way (allocated by gms_slam_set_beam_model)
         int32_t on;                 // update() weighs every particle by the model, through its own map as it stands in front of the scan
         int32_t behind, ahead;      // ... with this table (checked when it was set)
@@ -633,7 +633,8 @@ void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_o
 // whose blocked plane they test).  The layering: the query base (gms_query.hip:
 // everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier, scatter and locate (they inflate
 // with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only).  Cast and beams share their device-side
-// probe geometry -- the staged plane window and the first-hit walk -- through gms_probe.h, a device header on gms_device.h alone ----
+// probe geometry -- the staged plane window and the first-hit walk -- through gms_probe.h, a device header on gms_device.h alone; the two
+// beam models share their whole workgroup body through gms_beams_device.h on top of it ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);
@@ -806,11 +807,12 @@ int gms_launch_slam_align(gms_slam *s, const gms_beam *d_beams, int32_t B, const
 #define GMS_BEAM_T_MAX 512
 #define GMS_BEAM_TAB_BYTES (4 * GMS_BEAM_T_MAX * sizeof(double))
 int gms_beam_model_check_for(int32_t behind, int32_t ahead, const double *factors, const char *who);   // gms_beam_model_check with the caller's name in the message
-// ... on the particles' own maps (gms_slam_beams.hip).  The table through the handle's pinned ring into slot `which` of beam.d_tab (0: a
-// stand-alone call's, 1: the model's); the launch -- every particle held walks its own logData of the current generation at its pose
-// (motion non-NULL: the motion-model sample is drawn first and written, as gms_launch_slam_align does), weights into d_wgt / d_logw [n],
-// d_res [n][B] or NULL; and the update's combine of beam.d_wgt into the filter's raw weights behind gms_launch_slam_particle
-int gms_slam_beam_table(gms_slam *s, const char *who, int32_t behind, int32_t ahead, const double *factors, int32_t which);
+// the factors (checked by the caller) and their logarithms through the pinned ring into slot `which` of the n_tables in bt.d_tab, on m's stream
+int gms_beam_table_put(gms_map *m, BeamTables &bt, const char *who, int32_t behind, int32_t ahead, const double *factors, int32_t which, int32_t n_tables);
+void gms_beam_table_free(BeamTables &bt);
+// ... on the particles' own maps (gms_slam_beams.hip): the launch -- every particle held walks its own logData of the current generation
+// at its pose (motion non-NULL: the motion-model sample is drawn first and written) with table `which` of s->beam, weights into d_wgt /
+// d_logw [n], d_res [n][B] or NULL; and the update's combine of beam.d_wgt into the filter's raw weights behind gms_launch_slam_particle
 void gms_launch_slam_beams(gms_slam *s, const gms_beam *d_beams, int32_t B, const SlamBufs &sb, const MotionModel *motion, int32_t behind, int32_t ahead,
                            int32_t which, double *d_wgt, double *d_logw, uint16_t *d_res, const SlamBatch *batch = nullptr);
 void gms_launch_slam_weight_combine(gms_slam *s, int32_t B, const SlamBatch *batch = nullptr);

@@ -1,6 +1,7 @@
 // gms_probe.h -- the probe geometry the ray queries share (device only; DESIGN.md "the probe geometry the ray queries share"): the window
-// of a bit plane a workgroup stages in LDS for its rays, and the walk to the first set bit; k_cast_map, k_beam_score and k_slam_beam_score use it.  The pose's transform and the ray's locals
-// (pose_xform, make_ray) live in gms_device.h, where the scan step takes them from as well.
+// of a bit plane a workgroup stages in LDS for its rays, and the walk to the first set bit; k_cast_map and the beam models' one body
+// (gms_beams_device.h) use it.  The pose's transform and the ray's locals (pose_xform, make_ray) live in gms_device.h, where the scan
+// step takes them from as well.
 //
 // Every expression keeps the reference's operand order and casts (gms_device.h; the build never contracts a multiply with an add).
 #pragma once
@@ -22,9 +23,11 @@ __device__ __forceinline__ bool plane_bit(const uint32_t *__restrict__ plane, in
 //               values and places the barriers)
 //   clip        the box grown by `pad` cells -- the walk's extra steps + 1 -- and clipped to the map, in words; a window of more than
 //               lds_words words does not fit: 0 x 0, this workgroup walks memory
-//   stage       the window's words into LDS, the workgroup's nt lanes striding over them (the caller's barrier follows)
-//   bit         THE rule: a cell inside the window is read from LDS, any other from the plane in memory.  The box is an estimate of the
-//               float walk, never a promise, so the window only ever decides WHERE a bit is read, never what is returned.
+//   stage       the window's words into LDS from a packed plane, the workgroup's nt lanes striding over them (the caller's barrier
+//               follows); a plane that exists nowhere but in the window is packed there by its owner (gms_slam_beams.hip)
+//   bit         THE rule: a cell inside the window is read from LDS, any other is answered by mem(x, y) -- plane_bit, or whatever the
+//               window was filled from.  The box is an estimate of the float walk, never a promise, so the window only ever decides
+//               WHERE a bit is read, never what is returned.
 struct PlaneWindow {
     int32_t wx0 = 0, wy0 = 0, ww = 0, wh = 0;
 
@@ -60,15 +63,8 @@ struct PlaneWindow {
             dst[i] = plane[(size_t)(wy0 + row) * (size_t)wpr + (size_t)(wx0 + w)];
         }
     }
-    __device__ __forceinline__ bool bit(const uint32_t *s_win, const uint32_t *__restrict__ plane, int32_t wpr, int32_t x, int32_t y) const {
-        const uint32_t cw = (uint32_t)((x >> 5) - wx0), cr = (uint32_t)(y - wy0);
-        const uint32_t word = (cw < (uint32_t)ww && cr < (uint32_t)wh) ? s_win[cr * (uint32_t)ww + cw] : plane[(size_t)y * (size_t)wpr + (size_t)(x >> 5)];
-        return ((word >> (x & 31)) & 1u) != 0u;
-    }
-    // ... of a plane that exists nowhere but in the window (k_slam_beam_score packs it from a particle's logData): the same rule, a cell
-    // outside the window answered by mem(x, y)
     template <class Mem>
-    __device__ __forceinline__ bool bit_else(const uint32_t *s_win, int32_t x, int32_t y, Mem mem) const {
+    __device__ __forceinline__ bool bit(const uint32_t *s_win, int32_t x, int32_t y, Mem mem) const {
         const uint32_t cw = (uint32_t)((x >> 5) - wx0), cr = (uint32_t)(y - wy0);
         if (cw < (uint32_t)ww && cr < (uint32_t)wh) return ((s_win[cr * (uint32_t)ww + cw] >> (x & 31)) & 1u) != 0u;
         return mem(x, y);

@@ -3,9 +3,9 @@
 // per-particle scan matching step.  The definition is gms_align.hip's, the arithmetic gms_align_device.h's; what is new is where the
 // field's values come from.
 //
-//   k_slam_align   one workgroup per particle (as k_slam_refine).  Wavefront 0 draws the motion-model sample where the update asked for
-//                  one and no refinement launch ran in front (the Philox counters of k_slam_particle / k_slam_refine), the workgroup
-//                  stages the scan's (local_x, local_y) in LDS, NaN for a beam that did not hit.
+//   k_slam_align   one workgroup per particle, with the per-particle prologue (gms_slam_device.h: slam_generation, slam_pose_draw -- the
+//                  motion-model sample where the update asked for one and no refinement launch ran in front); the workgroup stages
+//                  the scan's (local_x, local_y) in LDS (align_stage_scan).
 //     PLANES       the particle's class plane 0 (2 bits per cell: the classes of logData as it stands) is staged beside them.  Per
 //                  evaluation, sixteen lanes per beam form the field's four values round the beam's end point on demand: lane r the
 //                  horizontal sums of row j0 - k + r at the columns i0 and i0 + 1 (rows j0 - k .. j0 + 1 + k: at most sixteen), then
@@ -122,12 +122,7 @@ k_slam_align(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t B
     constexpr int NT = PLANES ? SA_NT : GMS_WAVE;
     const int32_t p = (int32_t)blockIdx.x, tid = (int32_t)threadIdx.x, lane = tid & 63;
     const int32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int32_t *epoch = sb.epoch;
-    if constexpr (BATCH) {
-        int32_t integrate = 0;
-        slam_batch_filter(bt, p, beams, B, mo, integrate, epoch);
-    }
-    const int32_t cur = epoch[0] & 1;                                          // the current generation of the particles' maps (SlamBufs)
+    const int32_t cur = slam_generation<BATCH>(sb, bt, p, beams, B, mo);
     double2 *s_beam = reinterpret_cast<double2 *>(smem);                       // [Bpad]
     double *s_val = reinterpret_cast<double *>(s_beam + Bpad);                 // [Bpad][4] (PLANES)
     uint32_t *s_plane = reinterpret_cast<uint32_t *>(s_val + 4 * (size_t)Bpad);   // [code_words] (PLANES)
@@ -135,20 +130,13 @@ k_slam_align(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t B
     __shared__ int32_t s_stop;
     __shared__ double s_taps[SA_MAXTAPS + 1];
 
-    for (int32_t b = tid; b < B; b += NT) {
-        const gms_beam m = beams[b];
-        s_beam[b] = m.hit != 0 ? make_double2(m.local_x, m.local_y) : make_double2(NAN, NAN);
-    }
+    align_stage_scan(s_beam, beams, B, tid, NT);
     if (PLANES) {
         const uint32_t *__restrict__ gplane = sb_code(sb, cur) + (size_t)p * 2 * (size_t)code_words;     // plane 0: logData as it stands
         for (int32_t i = tid; i < code_words; i += NT) s_plane[i] = gplane[i];
         if (tid < SA_MAXTAPS + 1) s_taps[tid] = tid < g.ktaps ? taps_g[tid] : 0.0;
     }
-    if (wave == 0) {                                   // sampleMotionModel (SLAM.java:90), as k_slam_particle draws it, or the pose as it stands
-        float x = pose[3 * (size_t)p], y = pose[3 * (size_t)p + 1], th = pose[3 * (size_t)p + 2], c, sn;
-        if (mo.on) motion_apply(x, y, th, c, sn, (uint64_t)(mo.index0 + p), mo.d_center, mo.d_theta, mo.d_center_sd, mo.d_theta_sd, mo.seed, mo.sequence);
-        if (lane == 0) { s_pose[0] = x; s_pose[1] = y; s_pose[2] = th; }
-    }
+    if (wave == 0) slam_pose_draw<false>(mo, p, lane, pose, cs, s_pose);
     __syncthreads();
     float x = s_pose[0], y = s_pose[1], theta = s_pose[2];
     const double *lik = PLANES ? nullptr : sb_lik(sb, cur) + (size_t)p * (size_t)g.cells;
@@ -175,11 +163,7 @@ k_slam_align(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t B
         if (s_stop) break;                             // (wavefront 0 writes both again only behind the next barrier, which every reader of this round has then passed)
     }
     if (tid != 0) return;
-    pose[3 * (size_t)p] = x; pose[3 * (size_t)p + 1] = y; pose[3 * (size_t)p + 2] = theta;
-    float cf, sf;
-    pose_trig(theta, cf, sf);
-    cs[2 * (size_t)p] = cf; cs[2 * (size_t)p + 1] = sf;
-    if (rec) rec[p] = align_record(e, status, done, n0, s0);
+    align_store(pose, cs, rec, (size_t)p, x, y, theta, e, status, done, n0, s0);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
@@ -203,7 +187,7 @@ int gms_launch_slam_align(gms_slam *s, const gms_beam *d_beams, int32_t B, const
     gms_map *m = s->map;
     const MotionArgs mo = motion_args(motion, pf->offset);
     const int32_t Bpad = B < 8 ? 8 : (B + 7) & ~7;
-    const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
+    const SlamBatch bt = slam_batch_of(pf, batch);
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
     const size_t smem = from_planes ? slam_align_lds(Bpad, s->code_words) : (size_t)Bpad * 16;
     auto launch = [&](auto planes, auto batched) {

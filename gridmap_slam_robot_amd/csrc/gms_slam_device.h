@@ -1,6 +1,10 @@
 // gms_slam_device.h -- what the kernels of a gms_slam share across translation units (gms_pf_kernels.hip and gms_slam_kernels.hip in
-// the device unit, gms_slam_align.hip on its own): the motion-model sample of one particle and the handle's buffers as a kernel
-// addresses them.  One copy of each: the draw inside k_slam_particle, k_slam_refine and k_slam_align is the same draw, bit for bit.
+// the device unit, gms_slam_align.hip and gms_slam_beams.hip on their own): the motion-model sample of one particle, the handle's
+// buffers as a kernel addresses them, and the prologue of a kernel that takes one workgroup per particle -- slam_generation (the
+// batch's filter, the maps' current generation) and slam_pose_draw (wavefront 0 draws the motion-model sample or reads the pose).
+// All four such kernels take slam_generation.  k_slam_align and k_slam_beam_score take slam_pose_draw too; k_slam_particle and
+// k_slam_refine, the two kernels the benchmark times, keep its lines written out: with the helper their instruction streams differ
+// from the hand-written ones (operands commuted in the Philox rounds, other registers), and they change only where that is free.
 #pragma once
 #include "gms_device.h"
 
@@ -72,4 +76,38 @@ __device__ __forceinline__ void slam_batch_filter(const SlamBatch &bt, int32_t p
     mo.index0 = -(int64_t)f * bt.n;
     integrate &= (fa.flags >> 1) & 1;
     epoch += 2 * f;
+}
+// The first lines of a kernel that takes one workgroup per particle p: BATCH, the particle's filter first (slam_batch_filter: its scan,
+// count, motion and generation pair; integrate: its skipUpdate, for the kernel that integrates); then the current generation of the
+// particles' maps (SlamBufs)
+template <bool BATCH>
+__device__ __forceinline__ int32_t slam_generation(const SlamBufs &sb, const SlamBatch &bt, int32_t p, const gms_beam *__restrict__ &beams, int32_t &B,
+                                                   MotionArgs &mo, int32_t &integrate) {
+    const int32_t *epoch = sb.epoch;
+    if constexpr (BATCH) slam_batch_filter(bt, p, beams, B, mo, integrate, epoch);
+    return epoch[0] & 1;
+}
+template <bool BATCH>
+__device__ __forceinline__ int32_t slam_generation(const SlamBufs &sb, const SlamBatch &bt, int32_t p, const gms_beam *__restrict__ &beams, int32_t &B, MotionArgs &mo) {
+    int32_t integrate = 0;
+    return slam_generation<BATCH>(sb, bt, p, beams, B, mo, integrate);
+}
+// Wavefront 0's part of it, every lane: sampleMotionModel (SLAM.java:90, Odometry.java:77-96) where the update asked for a sample and no
+// launch in front drew it -- written back to pose / cs by lane 0 -- or the pose as it stands; lane 0 publishes x, y, theta into s_pose
+// [0..2] and, TRIG, the heading's float trig into s_pose[3..4] (cs[] always matches pose[]: k_pose_trig).  The caller's barrier
+// follows.  Returns theta
+template <bool TRIG>
+__device__ __forceinline__ float slam_pose_draw(const MotionArgs &mo, int32_t p, int32_t lane, float *pose, float *cs, float *s_pose) {
+    float x = pose[3 * (size_t)p], y = pose[3 * (size_t)p + 1], th = pose[3 * (size_t)p + 2], c, sn;
+    if (mo.on) motion_apply(x, y, th, c, sn, (uint64_t)(mo.index0 + p), mo.d_center, mo.d_theta, mo.d_center_sd, mo.d_theta_sd, mo.seed, mo.sequence);   // (uniform)
+    else if (TRIG) { c = cs[2 * (size_t)p]; sn = cs[2 * (size_t)p + 1]; }
+    if (lane == 0) {
+        s_pose[0] = x; s_pose[1] = y; s_pose[2] = th;
+        if (TRIG) { s_pose[3] = c; s_pose[4] = sn; }
+        if (mo.on) {
+            pose[3 * (size_t)p] = x; pose[3 * (size_t)p + 1] = y; pose[3 * (size_t)p + 2] = th;
+            cs[2 * (size_t)p] = c; cs[2 * (size_t)p + 1] = sn;
+        }
+    }
+    return th;
 }

@@ -89,8 +89,7 @@ int gms_slam_destroy(gms_slam *s) {
     hipFree(s->d_batch);
     hipFree(s->d_align_rec);
     hipFree(s->d_census);
-    hipFree(s->beam.d_tab); hipFree(s->beam.d_wgt);
-    if (s->beam.ring_ready) gms_ring_free(s->beam.ring);
+    gms_beam_table_free(s->beam); hipFree(s->beam.d_wgt);
     slam_hist_free(s);
     gms_ring_free(s->batch_ring);
     if (s->pf) gms_pf_destroy(s->pf);
@@ -710,7 +709,7 @@ static int slam_score_beams(gms_slam *s, const gms_beam *beams, int32_t B, int32
     if (B < 1 || B > m->max_beams) return gms_fail(GMS_ERR_INVALID, "%s: 1 <= B <= gms_params.max_beams beams", who);
     if (on_device && ((uintptr_t)residuals & 1) != 0) return gms_fail(GMS_ERR_INVALID, "%s: the residuals must be 2-byte aligned", who);
     HIPCHK(hipSetDevice(m->device));
-    rc = gms_slam_beam_table(s, who, behind, ahead, factors, 0);
+    rc = gms_beam_table_put(m, s->beam, who, behind, ahead, factors, 0, 2);
     if (rc) return rc;
     const gms_beam *d_beams;
     int32_t beam_stride;
@@ -754,7 +753,7 @@ int gms_slam_set_beam_model(gms_slam *s, int32_t behind, int32_t ahead, const do
     HIPCHK(hipSetDevice(s->map->device));
     rc = gms_dev_alloc(&s->beam.d_wgt, (size_t)2 * s->n * sizeof(double), "gms_slam_set_beam_model", "the beam weights");
     if (rc) return rc;
-    rc = gms_slam_beam_table(s, "gms_slam_set_beam_model", behind, ahead, factors, 1);
+    rc = gms_beam_table_put(s->map, s->beam, "gms_slam_set_beam_model", behind, ahead, factors, 1, 2);
     if (rc) return rc;
     s->beam.behind = behind; s->beam.ahead = ahead; s->beam.combine = combine;
     s->beam.on = 1;

@@ -27,7 +27,7 @@
 #include "gms_device.h"
 #include "gms_slam_device.h"
 
-// (sb_log / sb_lik / sb_code / sb_epoch and slam_batch_filter: gms_slam_device.h, shared with gms_slam_align.hip)
+// (sb_log / sb_lik / sb_code / sb_epoch, slam_batch_filter and slam_generation: gms_slam_device.h, shared with gms_slam_align.hip and gms_slam_beams.hip)
 
 // likelihoodData of every particle's map from its logData (mode 1 of likelihood_body: no factor table, no tile states, every tile)
 template <int KH>
@@ -188,9 +188,7 @@ k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
                 const double *__restrict__ taps_g, int32_t taps_plain, SlamBatch bt) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int32_t p = blockIdx.x;
-    const int32_t *epoch = sb.epoch;
-    if constexpr (BATCH) slam_batch_filter(bt, p, beams, B, mo, integrate, epoch);
-    const int32_t cur = epoch[0] & 1;                  // the current generation of the particles' maps (SlamBufs)
+    const int32_t cur = slam_generation<BATCH>(sb, bt, p, beams, B, mo, integrate);
     double *__restrict__ log_all = sb_log(sb, cur);
     const double *__restrict__ lik_all = field_in_memory ? sb_lik(sb, cur) : nullptr;
     uint32_t *__restrict__ code_all = sb_code(sb, cur);
@@ -243,7 +241,7 @@ k_slam_particle(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_
                 if (i0 + u * (NT - 64) < code_words) s_plane[i0 + u * (NT - 64)] = plw[u];
         }
     }
-    if (wave == 0) {
+    if (wave == 0) {                                   // (slam_pose_draw<true>'s lines, written out: gms_slam_device.h says why)
         float x = pose[3 * (size_t)p], y = pose[3 * (size_t)p + 1], th = pose[3 * (size_t)p + 2], c, sn;
         if (mo.on) {                                                           // (uniform)
             motion_apply(x, y, th, c, sn, (uint64_t)(mo.index0 + p), mo.d_center, mo.d_theta, mo.d_center_sd, mo.d_theta_sd, mo.seed, mo.sequence);
@@ -733,12 +731,8 @@ k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t 
     static_assert(KHF == 0 || LDSF, "the field is computed into LDS");
     extern __shared__ __align__(16) unsigned char smem[];
     const int32_t p = blockIdx.x;
-    const int32_t *epoch = sb.epoch;
-    if constexpr (BATCH) {
-        int32_t integrate = 0;
-        slam_batch_filter(bt, p, beams, B, mo, integrate, epoch);
-    }
-    const double *__restrict__ lik_all = sb_lik(sb, epoch[0] & 1);
+    const int32_t cur = slam_generation<BATCH>(sb, bt, p, beams, B, mo);
+    const double *__restrict__ lik_all = sb_lik(sb, cur);
     constexpr int NT = SR_NT_OF(LDSF, KHF), NW = NT / 64;
     double *s_f = reinterpret_cast<double *>(smem);                            // [H + 1][fp] factors, column W and row H neutral (LDSF)
     // (every carve offset a multiple of 16: a 16-byte LDS access off its alignment is replayed at 64 cycles -- 121 x 121 doubles are not)
@@ -753,7 +747,7 @@ k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t 
     const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
     GMS_STAMP(GMS_STAMP_ROW(3, blockIdx.x), 0);
 
-    if (wave == 0) {                                   // sampleMotionModel (SLAM.java:90), as k_slam_particle draws it; the theta steps' trig
+    if (wave == 0) {                                   // slam_pose_draw<false>'s lines, written out (gms_slam_device.h says why); the theta steps' trig
         float x = pose[3 * (size_t)p], y = pose[3 * (size_t)p + 1], th = pose[3 * (size_t)p + 2], c, sn;
         if (mo.on) {
             motion_apply(x, y, th, c, sn, (uint64_t)(mo.index0 + p), mo.d_center, mo.d_theta, mo.d_center_sd, mo.d_theta_sd, mo.seed, mo.sequence);
@@ -799,7 +793,7 @@ k_slam_refine(GridDev g, const gms_beam *__restrict__ beams, int32_t B, int32_t 
     if (KHF > 0) {
         // ---- pass 1: horizontal sums.  16 (the power of two that holds a row's strips) threads per row, thread = strip
         constexpr int K = KHF > 0 ? KHF : 1, NTAP = 2 * K + 1, STRIP = K <= 3 ? 8 : 4, NV = STRIP + 2 * K;      // NV <= 14 classes: 28 bits
-        const uint32_t *__restrict__ gpl = sb_code(sb, epoch[0] & 1) + (size_t)p * 2 * (size_t)code_words;    // plane 0: logData as it stands (the start of the update)
+        const uint32_t *__restrict__ gpl = sb_code(sb, cur) + (size_t)p * 2 * (size_t)code_words;    // plane 0: logData as it stands (the start of the update)
         double tp[NTAP];
 #pragma unroll
         for (int i = 0; i < NTAP; i++) tp[i] = taps_g[i];
@@ -1314,7 +1308,7 @@ void gms_launch_slam_particle(gms_pf *pf, const gms_beam *d_beams, int32_t B, co
     // the read-modify-write of the touched cells -- overlap), 1024 when the tile leaves room for one only.  GMS_SLAM_THREADS forces one.
     int32_t threads = smem <= lds_wg / 2 ? 512 : 1024;
     if (m->slam_threads == 512 || m->slam_threads == 1024) threads = m->slam_threads;
-    const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
+    const SlamBatch bt = slam_batch_of(pf, batch);
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
     constexpr gms_c<true> yes{};
     constexpr gms_c<false> no{};
@@ -1385,7 +1379,7 @@ bool gms_launch_slam_refine(gms_pf *pf, const gms_beam *d_beams, int32_t B, cons
     if (!r.ok) return false;
     const MotionArgs mo = motion_args(motion, pf->offset);
     ProfScope ps(m, GMS_K_REFINE);
-    const SlamBatch bt = batch ? *batch : SlamBatch{nullptr, pf->n, 0};
+    const SlamBatch bt = slam_batch_of(pf, batch);
     const unsigned grid = (unsigned)pf->n * (unsigned)pf->n_maps;
     auto launch = [&](auto ldsf, auto khf, auto batched) {
         gms_launch<k_slam_refine<ldsf(), khf(), batched()>>(m, dim3(grid), dim3(SR_NT_OF(ldsf(), khf())), r.smem, m->gd, d_beams, B, r.Bpad, sb, pf->d_pose,
