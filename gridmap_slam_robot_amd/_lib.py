@@ -71,6 +71,15 @@ class GmsClearance(C.Structure):
     ]
 
 
+class GmsSkeleton(C.Structure):
+    """gms_skeleton: a rectangle of a map as nearest-obstacle sites and free-space skeleton (gridmapslam.h "sites and skeleton")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("max_radius", C.c_int32), ("mode", C.c_int32), ("min_clear", C.c_int32), ("min_gap", C.c_int32), ("filter", C.c_int32),
+        ("pad", C.c_int32 * 3),
+    ]
+
+
 class GmsReach(C.Structure):
     """gms_reach: a rectangle of a map's cost-to-go field (gridmapslam.h "cost-to-go fields")"""
     _fields_ = [
@@ -267,6 +276,10 @@ CLEARANCE = GmsClearance
 GMS_REACH_AXIS, GMS_REACH_DIAG, GMS_REACH_FAR, GMS_REACH_MAX_SEEDS = 5, 7, 0xFFFF, 4096
 GMS_CLEAR_OCCUPIED, GMS_CLEAR_NOT_FREE = 0, 1
 GMS_CLEAR_FAR, GMS_CLEAR_OUTSIDE = 0xFFFF, 0xFFFE
+GMS_SITE_NONE, GMS_SITE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
+SKELETON_TOTALS_DTYPE = np.dtype([("sited", "<i8"), ("skeleton", "<i8"), ("min_d2", "<i4"), ("max_d2", "<i4"), ("pad", "<i4", (2,))])     # gms_skeleton_totals
+NEAREST_DTYPE = np.dtype([("site", "<u4"), ("d2", "<u4")])                                   # gms_nearest
+assert C.sizeof(GmsSkeleton) == 48 and SKELETON_TOTALS_DTYPE.itemsize == 32 and NEAREST_DTYPE.itemsize == 8
 GMS_VIEW_GREY8, GMS_VIEW_PACKED32 = 0, 1
 GMS_VIEW_LOG, GMS_VIEW_LIKELIHOOD = 0, 1
 GMS_VIEW_STRONGEST = -1
@@ -474,6 +487,14 @@ def load() -> C.CDLL:
     sig("gms_map_clearance_poses_dev", C.c_int, vp, i32, vp, i32, i32, i32, vp)
     sig("gms_slam_clearance", C.c_int, vp, i32, cl, vp, vp)
     sig("gms_slam_clearance_dev", C.c_int, vp, i32, cl, vp, vp)
+    sk = C.POINTER(GmsSkeleton)
+    sig("gms_skeleton_size", C.c_int, sk, vp, vp, vp, vp)
+    sig("gms_map_skeleton", C.c_int, vp, i32, sk, vp, vp, vp)
+    sig("gms_map_skeleton_dev", C.c_int, vp, i32, sk, vp, vp, vp)
+    sig("gms_map_nearest_poses", C.c_int, vp, i32, vp, i32, i32, i32, vp)
+    sig("gms_map_nearest_poses_dev", C.c_int, vp, i32, vp, i32, i32, i32, vp)
+    sig("gms_slam_skeleton", C.c_int, vp, i32, sk, vp, vp, vp, vp)
+    sig("gms_slam_skeleton_dev", C.c_int, vp, i32, sk, vp, vp, vp, vp)
     rp = C.POINTER(GmsReach)
     sig("gms_reach_size", C.c_int, rp, vp, vp, vp)
     sig("gms_map_reach", C.c_int, vp, i32, rp, vp, i32, vp)

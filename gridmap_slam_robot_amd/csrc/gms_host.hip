@@ -248,6 +248,7 @@ static int map_free(gms_map *m) {
     hipFree(m->d_reach_field); hipFree(m->d_reach_d2); hipFree(m->d_reach_plane); hipFree(m->d_reach_ctl);
     if (m->h_reach_ctl) hipHostFree(m->h_reach_ctl);
     hipFree(m->d_route_path);
+    hipFree(m->d_site_field);
     hipFree(m->d_front_plane); hipFree(m->d_front_nf); hipFree(m->d_front_label); hipFree(m->d_front_wscan); hipFree(m->d_front_table); hipFree(m->d_front_ctl);
     if (m->h_front_ctl) hipHostFree(m->h_front_ctl);
     hipFree(m->scatter.d_elig); hipFree(m->scatter.d_pre);

@@ -148,6 +148,10 @@ struct gms_map {
     // routes (gms_route.hip): the descended paths of a request that gave no `cells`, [P][max_cells][2]; grows and never shrinks
     int32_t *d_route_path;
     int64_t route_cap;            // cells it holds
+    // sites and skeleton (gms_skeleton.hip): the site field the ridge pass reads, the request's rectangle and one cell around it; grows
+    // and never shrinks
+    uint32_t *d_site_field;
+    int64_t site_cap;             // cells it holds
     // frontier regions (gms_frontier.hip); allocated by the first request, the region table grows and never shrinks
     uint32_t *d_front_plane;      // [2][H][gms_plane_wpr] the frontier plane, and the plane of the regions' roots (label == own index)
     uint32_t *d_front_nf;         // [H][gms_plane_wpr] a gms_slam's: the shown particle's second plane (its first: d_clear_scratch)

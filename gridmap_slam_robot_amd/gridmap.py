@@ -25,7 +25,7 @@ from ._lib import BEAM_DTYPE, CAST_DTYPE, GmsParams, GmsPfStats, check, load, pt
 
 __all__ = ["GridMap", "Observation", "ParticleFilter", "SLAM", "Pose", "scan_residual", "clearance_metres", "reach_metres", "frontier_centroids",
            "cells_of_poses", "descend", "route_points", "mode_estimate", "strongest_mode", "AlignParams", "align_covariance", "warp_agreement", "map_as_scan",
-           "census_entropy", "census_outliers"]
+           "census_entropy", "census_outliers", "site_cells", "site_vectors", "skeleton_cells"]
 
 
 def Pose(x: float, y: float, theta: float) -> np.ndarray:
@@ -360,6 +360,36 @@ def clearance_metres(d2, resolution: float) -> np.ndarray:
     return out
 
 
+def site_cells(site, W: int) -> tuple:
+    """Sites (GridMap.skeleton's site field or nearest_poses' "site": uint32 oy * W + ox) as cells: (ox, oy, valid), int64, int64 and
+    bool arrays of the input's shape.  valid is False, and ox = oy = -1, where the site is GMS_SITE_NONE (no obstacle within the
+    radius) or GMS_SITE_OUTSIDE (a pose off the map)."""
+    s = np.asarray(site).astype(np.int64)
+    valid = (s != _lib.GMS_SITE_NONE) & (s != _lib.GMS_SITE_OUTSIDE)
+    return np.where(valid, s % int(W), -1), np.where(valid, s // int(W), -1), valid
+
+
+def site_vectors(site, x0: int, y0: int, W: int, resolution: float) -> np.ndarray:
+    """The metric vector from the centre of every cell of a site field [h][w] of the rectangle at (x0, y0) to the centre of its site,
+    float64 [h][w][2] = (dx, dy) in metres: (ox - x, oy - y) * resolution, the map's float resolution widened.  NaN where the cell
+    has no site.  The direction away from the nearest wall is its negative."""
+    s = np.asarray(site)
+    ox, oy, valid = site_cells(s, W)
+    ys, xs = np.mgrid[int(y0):int(y0) + s.shape[0], int(x0):int(x0) + s.shape[1]]
+    res = np.float64(np.float32(resolution))
+    v = np.stack([(ox - xs) * res, (oy - ys) * res], axis=-1)
+    v[~valid] = np.nan
+    return v
+
+
+def skeleton_cells(skel) -> tuple:
+    """The skeleton cells of a skeleton field (GridMap.skeleton's skel [h][w]: d2 on the skeleton, else 0): (ys, xs, d2), the cells in
+    row-major order within the rectangle and their squared clearance in cells; doorways are the local minima of d2 along it."""
+    k = np.asarray(skel)
+    ys, xs = np.nonzero(k)
+    return ys, xs, k[ys, xs]
+
+
 def _reach_seeds(seeds, who: str = "reach", what: str = "seeds") -> np.ndarray:
     """seeds (route: starts) as the int32 [K][2] (x, y) array the library takes"""
     a = np.ascontiguousarray(seeds, dtype=np.int32)
@@ -671,6 +701,25 @@ def _query_clearance(src: _Source, rect, max_radius: int, not_free: bool, out, s
         return (out,) + src.dev("clearance", C.byref(c), _device_ptr("clearance", "out", out, nbytes), shown_out=shown_out)
     field = np.empty(shape, dtype=np.uint16)
     return (field,) + src.host("clearance", C.byref(c), ptr(field))
+
+
+def _query_skeleton(src: _Source, rect, max_radius: int, not_free: bool, min_clear: int, min_gap: int, want, dev, shown_out) -> tuple:
+    """want: which of (site, skel, totals) the host form returns, None for the others; dev: the device form's (site, skel, totals)
+    torch tensors, None for an output that is not wanted"""
+    q = _lib.GmsSkeleton(*_rect(src.W, src.H, rect), int(max_radius), _obstacles(not_free), int(min_clear), int(min_gap), src.filter)
+    ow, oh, sb, kb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    check(load().gms_skeleton_size(C.byref(q), C.byref(ow), C.byref(oh), C.byref(sb), C.byref(kb)))
+    if dev is not None:
+        site, skel, totals = dev
+        ptrs = (_device_ptr("skeleton", "site", site, sb.value, optional=True), _device_ptr("skeleton", "skel", skel, kb.value, optional=True),
+                _device_ptr("skeleton", "totals", totals, _lib.SKELETON_TOTALS_DTYPE.itemsize, optional=True))
+        return (site, skel, totals) + src.dev("skeleton", C.byref(q), *ptrs, shown_out=shown_out)
+    shape = (oh.value, ow.value)
+    site = np.empty(shape, dtype=np.uint32) if want[0] else None
+    skel = np.empty(shape, dtype=np.uint16) if want[1] else None
+    totals = np.zeros(1, dtype=_lib.SKELETON_TOTALS_DTYPE) if want[2] else None
+    tail = src.host("skeleton", C.byref(q), *(None if a is None else ptr(a) for a in (site, skel, totals)))
+    return (site, skel, None if totals is None else totals[0]) + tail
 
 
 def _query_reach(src: _Source, seeds, max_cost: int, inflate: int, not_free: bool, rect, out, shown_out) -> tuple:
@@ -1098,6 +1147,36 @@ class GridMap:
         rounds, runs = C.c_int32(0), C.c_int64(0)
         check(load().gms_map_reach_stats(self._h, C.byref(rounds), C.byref(runs)))
         return {"rounds": int(rounds.value), "tile_runs": int(runs.value)}
+
+    def skeleton(self, rect=None, max_radius: int = 25, not_free: bool = False, min_clear: int = 1, min_gap: int = 2, mi: int = 0,
+                 site: bool = True, skel: bool = True, totals: bool = True):
+        """Nearest-obstacle sites and the free-space skeleton (gridmapslam.h "sites and skeleton") of map mi over rect = (x0, y0, w, h)
+        (None: the whole map): (site uint32 [h][w], skel uint16 [h][w], totals).  site: the nearest obstacle cell oy * W + ox, the
+        smaller index at equal distance, GMS_SITE_NONE beyond max_radius (site_cells, site_vectors); skel: d2 on the cells equally
+        far from two pieces of wall at least min_gap cells apart and at least min_clear cells away, else 0 (skeleton_cells); totals:
+        one SKELETON_TOTALS_DTYPE record.  An output switched off is not computed and comes back as None; one must stay on."""
+        return _query_skeleton(self._src(mi), rect, max_radius, not_free, min_clear, min_gap, (site, skel, totals), None, None)[:3]
+
+    def skeleton_dev(self, site=None, skel=None, totals=None, rect=None, max_radius: int = 25, not_free: bool = False, min_clear: int = 1,
+                     min_gap: int = 2, mi: int = 0):
+        """skeleton() into contiguous torch device tensors on the handle's stream, nothing synchronised: site of h * w * 4 bytes, skel
+        of h * w * 2, totals of 32; None: that output is not computed"""
+        return _query_skeleton(self._src(mi), rect, max_radius, not_free, min_clear, min_gap, None, (site, skel, totals), None)[:3]
+
+    def nearest_poses(self, poses, max_radius: int = 25, not_free: bool = False, mi: int = 0) -> np.ndarray:
+        """The nearest obstacle cell under each of poses [P][3] (x, y, theta; theta is not read) without making a field: NEAREST_DTYPE
+        [P] = (site, d2), the site field's value at the pose's cell (clearance_poses' cell) and its squared distance;
+        (GMS_SITE_OUTSIDE, GMS_CLEAR_OUTSIDE) off the map, (GMS_SITE_NONE, GMS_CLEAR_FAR) with nothing within max_radius."""
+        p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        out = np.empty(len(p), dtype=_lib.NEAREST_DTYPE)
+        check(load().gms_map_nearest_poses(self._h, int(mi), ptr(p), len(p), int(max_radius), _obstacles(not_free), ptr(out)))
+        return out
+
+    def nearest_poses_dev(self, dev_poses: int, P: int, out, max_radius: int = 25, not_free: bool = False, mi: int = 0):
+        """nearest_poses() with a device pointer; out: a contiguous torch device tensor of P * 8 bytes, written on the handle's stream"""
+        check(load().gms_map_nearest_poses_dev(self._h, int(mi), C.c_void_p(dev_poses), int(P), int(max_radius), _obstacles(not_free),
+                                               _device_ptr("nearest_poses_dev", "out", out, 8 * int(P))))
+        return out
 
     def clearance_poses(self, poses, max_radius: int = 25, not_free: bool = False, mi: int = 0) -> np.ndarray:
         """The clearance under each of poses [P][3] (x, y, theta; theta is not read) without making a field: uint16 [P], the field's
@@ -1987,6 +2066,10 @@ class _SlamHandle:
         """gms_slam_clearance[_dev]: (field, shown)"""
         return _query_clearance(self._src("clearance", which, filter), rect, max_radius, not_free, out, shown_out)
 
+    def _skeleton(self, which, filter: int, rect, max_radius: int, not_free: bool, min_clear: int, min_gap: int, want, dev, shown_out):
+        """gms_slam_skeleton[_dev]: (site, skel, totals, shown)"""
+        return _query_skeleton(self._src("skeleton", which, filter), rect, max_radius, not_free, min_clear, min_gap, want, dev, shown_out)
+
     def _reach(self, which, filter: int, seeds, max_cost: int, inflate: int, not_free: bool, rect, out, shown_out):
         """gms_slam_reach[_dev]: (field, shown); seeds None: the shown particle's own cell"""
         return _query_reach(self._src("reach", which, filter), seeds, max_cost, inflate, not_free, rect, out, shown_out)
@@ -2230,6 +2313,14 @@ class SLAMParticleMaps(_SlamHandle):
         particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  out /
         shown_out: torch device tensors for the field and the int32 index; nothing is synchronised."""
         return self._clearance(which, 0, rect, max_radius, not_free, out, shown_out)
+
+    def skeleton(self, which="strongest", rect=None, max_radius: int = 25, not_free: bool = False, min_clear: int = 1, min_gap: int = 2,
+                 site: bool = True, skel: bool = True, totals: bool = True, dev=None, shown_out=None):
+        """Sites and skeleton of particle `which`'s OWN map (GridMap.skeleton's values): (site, skel, totals, shown).  which = a
+        particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).  dev: the
+        device form, (site, skel, totals) torch device tensors (None: not computed), and shown_out the int32 index; nothing is
+        synchronised."""
+        return self._skeleton(which, 0, rect, max_radius, not_free, min_clear, min_gap, (site, skel, totals), dev, shown_out)
 
     def reach(self, which="strongest", seeds=None, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None, out=None,
               shown_out=None):
@@ -2512,6 +2603,12 @@ class SLAMParticleMapsBatch(_SlamHandle):
         """SLAMParticleMaps.clearance for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
         is the handle-wide slot filter * num_particles + k whose field was made, as view() reports it"""
         return self._clearance(self._local(filter, which), filter, rect, max_radius, not_free, out, shown_out)
+
+    def skeleton(self, which="strongest", filter: int = 0, rect=None, max_radius: int = 25, not_free: bool = False, min_clear: int = 1,
+                 min_gap: int = 2, site: bool = True, skel: bool = True, totals: bool = True, dev=None, shown_out=None):
+        """SLAMParticleMaps.skeleton for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
+        is the handle-wide slot filter * num_particles + k whose map was read, as view() reports it"""
+        return self._skeleton(self._local(filter, which), filter, rect, max_radius, not_free, min_clear, min_gap, (site, skel, totals), dev, shown_out)
 
     def reach(self, which="strongest", filter: int = 0, seeds=None, max_cost: int = 0xFFFE, inflate: int = 0, not_free: bool = True, rect=None,
               out=None, shown_out=None):

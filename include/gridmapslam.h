@@ -645,6 +645,93 @@ int gms_map_clearance_poses_dev(gms_map *m, int32_t mi, const float *dev_poses, 
 int gms_slam_clearance(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *out, int32_t *shown);
 int gms_slam_clearance_dev(gms_slam *s, int32_t which, const gms_clearance *c, uint16_t *dev_out, int32_t *dev_shown);
 
+/* ---- sites and skeleton: which obstacle is the nearest one, and where free space is equally far from two walls --------------------
+ * The site of a cell is what a reactive controller, a potential field, an ESDF gradient and a "push this waypoint off the wall" step
+ * are made of; the skeleton is the generalised Voronoi diagram of the grid, the maximum-clearance roadmap: corridor centre lines,
+ * doorways as local minima of the clearance along it, junctions as places to decide.  This library's own definition (the reference has
+ * no such method).  All of it is integer arithmetic, and both results are unique.
+ *
+ * OBSTACLE.  gms_clearance's definition for `mode`: GMS_CLEAR_OCCUPIED or GMS_CLEAR_NOT_FREE.  Cells outside the map are no obstacles.
+ *
+ * SITE.  The site of a map cell c = (x, y) is the obstacle cell o = (ox, oy) of the WHOLE map that minimises the pair
+ * (d2, oy * W + ox) lexicographically.
+ *   - d2 = (x - ox)^2 + (y - oy)^2.
+ *   - Only obstacles with d2 <= max_radius^2 count, and 1 <= max_radius <= 255.
+ *   - Encoded as uint32_t oy * W + ox.
+ *   - GMS_SITE_NONE = 0xFFFFFFFF where no obstacle lies within the radius.
+ *   - An obstacle cell is its own site.
+ *   - d2(c) is the site's distance.  By construction it equals what gms_map_clearance returns for the same mode and radius.
+ *
+ * SKELETON.  Parameters:
+ *   - min_clear >= 1, in cells;
+ *   - min_gap >= 2, in cells;
+ *   - min_clear <= max_radius;
+ *   - min_gap <= 2 * max_radius.
+ * A map cell c is a skeleton cell iff all of these hold:
+ *   1. c is no obstacle, site(c) != NONE, and d2(c) >= min_clear^2.
+ *   2. c has an axis neighbour n (of the four, inside the map) that is no obstacle and has site(n) != NONE.  The squared distance
+ *      between the two site cells must be >= min_gap^2.
+ *   3. For that n: d2(c) > d2(n), or d2(c) == d2(n) and c's linear index is below n's.  So of a pair that straddles the ridge, the cell
+ *      farther from the walls is marked.  A tie goes to the smaller index.
+ * The neighbour n may lie outside the requested rectangle.  The definition is over the whole map.
+ * Cells farther than max_radius from every obstacle carry no skeleton.  A caller who wants one in a large hall raises the radius.
+ *
+ * The outputs for the rectangle x0, y0, w, h (gms_view's rules; [h][w], row-major, row 0 = y0, no row padding).  Each may be NULL, but
+ * not all of them:
+ *   site    uint32_t [h][w]: as defined above.
+ *   skel    uint16_t [h][w]: d2(c) where c is a skeleton cell, else 0 (min_clear >= 1 makes 0 unambiguous).  The non-zero values are
+ *           the clearance along the skeleton, so doorways are its local minima.
+ *   totals  one gms_skeleton_totals over the rectangle.
+ * Tracing the skeleton into a graph of junctions and edges and pruning spurs are the caller's, from skel on the host.
+ *
+ * A call sees the map as gms_map_download_log / gms_slam_download_map would return it at that moment, changes no later result of its
+ * handle, checks its arguments before anything is enqueued (GMS_ERR_INVALID, nothing touched, the reason in gms_last_error) and reuses
+ * a current plane without repacking (gms_map_cast_plane_builds): the clearance fields' rules.  A map of 2^32 - 2 cells or more is
+ * refused. */
+#define GMS_SITE_NONE 0xFFFFFFFFu                              /* no obstacle within max_radius */
+#define GMS_SITE_OUTSIDE 0xFFFFFFFEu                           /* gms_map_nearest_poses: the pose's cell is outside the map */
+typedef struct gms_skeleton {
+    int32_t x0, y0, w, h;       /* the cell rectangle */
+    int32_t max_radius;         /* cells, 1 .. 255 */
+    int32_t mode;               /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE */
+    int32_t min_clear;          /* cells, 1 .. max_radius: skeleton cells are at least this far from their site */
+    int32_t min_gap;            /* cells, 2 .. 2 * max_radius: ... and separate sites at least this far apart */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+    int32_t pad[3];
+} gms_skeleton;
+typedef struct gms_skeleton_totals {
+    int64_t sited;              /* cells of the rectangle with a site */
+    int64_t skeleton;           /* skeleton cells of the rectangle */
+    int32_t min_d2, max_d2;     /* over the skeleton cells; both 0 when there are none */
+    int32_t pad[2];             /* zero */
+} gms_skeleton_totals;
+typedef struct gms_nearest {
+    uint32_t site;              /* the site of the pose's cell, GMS_SITE_NONE or GMS_SITE_OUTSIDE */
+    uint32_t d2;                /* its squared distance in cells, GMS_CLEAR_FAR or GMS_CLEAR_OUTSIDE */
+} gms_nearest;
+/* The outputs' size in cells and bytes (any of the four may be NULL).  Pure host code: checks w, h >= 1, x0, y0 >= 0, the radius, the
+ * mode, min_clear and min_gap -- not the map's bounds, which it does not know.  This library's own definition. */
+int gms_skeleton_size(const gms_skeleton *q, int32_t *out_w, int32_t *out_h, int64_t *site_bytes, int64_t *skel_bytes);
+/* Map mi of a shared or batched map; this library's own definition, no reference method stands behind it.  site, skel, totals: host
+ * memory, staged through the views' buffer; the call synchronises.  _dev: device memory (site 4-byte, skel 2-byte, totals 8-byte
+ * aligned), written on the handle's stream; nothing is synchronised.  The sites are the clearance fields' separable transform with the
+ * arg-min kept, into the caller's array where nothing else is asked for; skel and totals come from a second launch over a site field of
+ * the rectangle and one cell around it, kept on the handle (it grows and never shrinks: no allocation per call once warm). */
+int gms_map_skeleton(gms_map *m, int32_t mi, const gms_skeleton *q, uint32_t *site, uint16_t *skel, gms_skeleton_totals *totals);
+int gms_map_skeleton_dev(gms_map *m, int32_t mi, const gms_skeleton *q, uint32_t *dev_site, uint16_t *dev_skel, gms_skeleton_totals *dev_totals);
+/* The site and its squared distance under P points without making a field; out [P]; this library's own definition.  The pose's cell
+ * is gms_map_clearance_poses' (Java's cast, NaN -> 0).  {GMS_SITE_OUTSIDE, GMS_CLEAR_OUTSIDE} where that cell is off the map,
+ * {GMS_SITE_NONE, GMS_CLEAR_FAR} where nothing lies within the radius; every other record is the field's at that cell.  _dev: out is
+ * device memory, 4-byte aligned. */
+int gms_map_nearest_poses(gms_map *m, int32_t mi, const float *poses, int32_t P, int32_t max_radius, int32_t mode, gms_nearest *out);
+int gms_map_nearest_poses_dev(gms_map *m, int32_t mi, const float *dev_poses, int32_t P, int32_t max_radius, int32_t mode, gms_nearest *dev_out);
+/* One particle's map of the per-particle filter; this library's own definition.  `which`, GMS_VIEW_STRONGEST, q->filter, *shown and
+ * the GMS_ERR_STATE cases are gms_slam_view's.  gms_slam_clearance's pre-pass packs the shown particle's plane into the handle's
+ * scratch plane, and the shared maps' kernels run on that. */
+int gms_slam_skeleton(gms_slam *s, int32_t which, const gms_skeleton *q, uint32_t *site, uint16_t *skel, gms_skeleton_totals *totals, int32_t *shown);
+int gms_slam_skeleton_dev(gms_slam *s, int32_t which, const gms_skeleton *q, uint32_t *dev_site, uint16_t *dev_skel, gms_skeleton_totals *dev_totals,
+                          int32_t *dev_shown);
+
 /* ---- cost-to-go fields: how far it is to drive from a set of places to everywhere else -------------------------------------------
  * What grid planners, the choice of exploration goals and every "can I get there at all" check start from, and this library's own
  * definition (the reference has no such method).  All of it is integer arithmetic, and the field is unique.

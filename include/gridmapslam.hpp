@@ -210,6 +210,31 @@ public:
         check(gms_map_clearance(h_, mi, &c, out.data()));
         return out;
     }
+    /** Sites and skeleton (gridmapslam.h "sites and skeleton") of map mi over q's rectangle, each [h][w] row-major: site (may be null)
+     *  the nearest obstacle cell oy * W + ox of every cell, GMS_SITE_NONE beyond q.max_radius; skel (may be null) d2 on the skeleton
+     *  cells, else 0.  Returns the totals over the rectangle. */
+    gms_skeleton_totals skeleton(const gms_skeleton &q, std::vector<uint32_t> *site, std::vector<uint16_t> *skel = nullptr, int mi = 0) {
+        int64_t siteBytes = 0, skelBytes = 0;
+        check(gms_skeleton_size(&q, nullptr, nullptr, &siteBytes, &skelBytes));
+        if (site) site->resize((size_t)siteBytes / sizeof(uint32_t));
+        if (skel) skel->resize((size_t)skelBytes / sizeof(uint16_t));
+        gms_skeleton_totals totals{};
+        check(gms_map_skeleton(h_, mi, &q, site ? site->data() : nullptr, skel ? skel->data() : nullptr, &totals));
+        return totals;
+    }
+    /** the whole map's skeleton request */
+    gms_skeleton fullSkeleton(int maxRadius, bool notFree = false, int minClear = 1, int minGap = 2) const {
+        return gms_skeleton{0, 0, w_, hgt_, maxRadius, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, minClear, minGap, 0, {0, 0, 0}};
+    }
+    /** the nearest obstacle cell under every pose's cell and its squared distance, without making a field; {GMS_SITE_OUTSIDE,
+     *  GMS_CLEAR_OUTSIDE} for a pose off the map, {GMS_SITE_NONE, GMS_CLEAR_FAR} with nothing within maxRadius */
+    std::vector<gms_nearest> nearest_poses(const std::vector<Pose> &poses, int maxRadius, bool notFree = false, int mi = 0) {
+        std::vector<float> p(3 * poses.size());
+        for (size_t i = 0; i < poses.size(); i++) { p[3 * i] = poses[i].x; p[3 * i + 1] = poses[i].y; p[3 * i + 2] = poses[i].theta; }
+        std::vector<gms_nearest> out(poses.size());
+        check(gms_map_nearest_poses(h_, mi, p.data(), (int32_t)poses.size(), maxRadius, notFree ? GMS_CLEAR_NOT_FREE : GMS_CLEAR_OCCUPIED, out.data()));
+        return out;
+    }
     /** The cost-to-go field (gridmapslam.h "cost-to-go fields") of map mi: per cell of r's rectangle the cost of the cheapest path from
      *  any of seeds ({x, y} pairs) through the cells that are not blocked, GMS_REACH_FAR beyond r.max_cost; [h][w] row-major */
     std::vector<uint16_t> reach(const gms_reach &r, const std::vector<int32_t> &seeds, int mi = 0) {
@@ -632,6 +657,20 @@ public:
         check(gms_slam_clearance(h_, which, &c, out.data(), &picked));
         if (shown) *shown = picked;
         return out;
+    }
+    /** Sites and skeleton of particle `which`'s own map (GridMap::skeleton's values and totals); *shown (may be null) receives the
+     *  particle whose map was read */
+    gms_skeleton_totals skeleton(const gms_skeleton &q, std::vector<uint32_t> *site, std::vector<uint16_t> *skel = nullptr, int which = GMS_VIEW_STRONGEST,
+                                 int *shown = nullptr) {
+        int64_t siteBytes = 0, skelBytes = 0;
+        check(gms_skeleton_size(&q, nullptr, nullptr, &siteBytes, &skelBytes));
+        if (site) site->resize((size_t)siteBytes / sizeof(uint32_t));
+        if (skel) skel->resize((size_t)skelBytes / sizeof(uint16_t));
+        gms_skeleton_totals totals{};
+        int32_t picked = 0;
+        check(gms_slam_skeleton(h_, which, &q, site ? site->data() : nullptr, skel ? skel->data() : nullptr, &totals, &picked));
+        if (shown) *shown = picked;
+        return totals;
     }
     /** Global scan matching in particle `which`'s own map (GridMap::locate's records); *shown (may be null) receives the particle in
      *  whose map the scan was matched */
