@@ -1005,6 +1005,9 @@ int gms_pf_create(gms_map *m, int32_t n, gms_pf **out) {               // Partic
     ok = ok && hipMalloc(&pf->d_ord, T * sizeof(float4)) == hipSuccess && hipMalloc(&pf->d_perm, T * 4) == hipSuccess;
     pf->order_mode = -1;
     if (const char *v = getenv("GMS_SCORE_ORDER")) pf->order_mode = atoi(v);
+    pf->seg_order = -1;
+    pf->seg_order_launches = 0;
+    if (const char *v = getenv("GMS_SCORE_SEGORDER")) pf->seg_order = atoi(v) != 0;
     pf->score_threads = 0;
     if (const char *v = getenv("GMS_SCORE_THREADS")) pf->score_threads = atoi(v);
     pf->score_spread = -1;
@@ -1533,6 +1536,12 @@ int gms_pf_set_reference_order(gms_pf *pf, int32_t on) {
 int gms_pf_set_refine(gms_pf *pf, int32_t on) {                          // SLAM.java:96-97
     REQUIRE(pf, "null filter");
     pf->refine = on != 0;
+    return GMS_OK;
+}
+
+int gms_pf_segment_order_launches(const gms_pf *pf, int64_t *launches) {
+    REQUIRE(pf && launches, "gms_pf_segment_order_launches: null argument");
+    *launches = pf->seg_order_launches;
     return GMS_OK;
 }
 

@@ -294,6 +294,9 @@ struct gms_pf {
                                     // cumulative weights) as ONE chain in the reference's order (tests; slow)
     int32_t score_spread;           // -1 the launcher decides (launches of two or more workgroups per CU), 0 / 1 forced (GMS_SCORE_SPREAD, read at creation)
     int32_t order_mode;             // -1 the launcher decides (large launches only), 0 never, 1 always (GMS_SCORE_ORDER; results do not depend on it)
+    int32_t seg_order;              // the scoring workgroups' lanes in the order of their segment's end-point lines (k_score_c<1, true>): -1 the launcher
+                                    // decides (single map, 1024-lane workgroups), 0 / 1 forced for every multi-wavefront shape of a single map (GMS_SCORE_SEGORDER); GMS_SCORE_ORDER=0 turns it off too
+    int64_t seg_order_launches;     // scoring launches that took that order so far (gms_pf_segment_order_launches: tests)
     // pose modes (gms_modes.hip): scratch of the last request, allocated by the first one; the bins' part and the table grow and never shrink
     struct {
         uint32_t *d_part;           // [n] every particle's bin | [n] its label

@@ -242,7 +242,23 @@ k_order(GridDev g, const float *__restrict__ pose_src, const float *__restrict__
 // U: look-ups in flight per lane beside the software pipeline.  1 for particles in the caller's order (C3: 1 / 2 / 3 / 4 -> 20.6 / 21.2 /
 // 24.9 / 21.0 us: more gathers in flight from 64 unrelated lanes thrash the L1 patch); 3 for particles in k_order's locality order, whose
 // neighbouring lanes share lines (C5: 1 / 2 / 3 / 4 -> 240 / 233 / 223 / 237 us; 3 divides the 45-beam segment: no padded batch).
-template <int U>
+//
+// SEG: the workgroup's lanes take its particles in the order of the SEGMENT's end-point lines (U == 1, no k_order order, more than one
+// wavefront).  A workgroup owns one beam segment, a wedge of 22.5 degrees at 720 beams: two of its particles read the same 128-byte
+// line of the table exactly when their end points fall into the same row and the same group of 16 cells, and which particles those are
+// differs from segment to segment -- the displacement R(theta) * beam turns with the beam -- so that no order of the population and no
+// order by heading serves all sixteen.  Key: row and 16-cell group of the end point of the segment's MIDDLE hit beam, row bits leading,
+// folded to 256 buckets: ((row & 63) << 2) | (group & 3) (counted on the host for the bench's C3 cloud, tools/score_segment_order_count.py:
+// 2.80 distinct lines per quad of lanes and 18.1 per look-up instruction against 3.94 and 48.2 in the caller's order; 1024 buckets of 7 + 3
+// bits count 2.74 and 17.5, the unfolded key 2.74 and 17.5: the fold is the one whose scan a wavefront does in one pass); an end point outside
+// the map or under beam_cell_fast's guard, and a lane without a particle, take the last bucket.  A counting sort in LDS -- histogram
+// by atomicAdd, whose returned value is the lane's rank in its bucket; an exclusive scan of the buckets by wavefront butterflies, every
+// wavefront for itself; {x, y, cos, sin} as floats and the particle index scattered to the slot; every lane reads slot threadIdx.x
+// back -- costs two barriers and no global memory.  A product does not depend on the lane that forms it, nor on the arrival order
+// inside a bucket: same bits as SEG = false.  The motion-model sample and segment 0's pose stores happen BEFORE the exchange, on the
+// unsorted lane.
+#define SEG_BUCKETS 256
+template <int U, bool SEG = false>
 __global__ void __launch_bounds__(1024)
 k_score_c(const float *__restrict__ pose_src, const gms_beam *__restrict__ beams, const float4 *__restrict__ ord,
           const int32_t *__restrict__ perm, int32_t B, int32_t beam_stride, int32_t n, int32_t nseg, int32_t spread,
@@ -304,14 +320,18 @@ k_score_c(const float *__restrict__ pose_src, const gms_beam *__restrict__ beams
         if (threadIdx.x < U) s_beam[base + threadIdx.x] = make_double2(0.0, 0.0);   // padding of the last batch
         if (threadIdx.x == 0) s_nb = base;
     }
+    if constexpr (SEG) {
+        extern __shared__ __align__(16) uint32_t s_seg[];             // [SEG_BUCKETS] counts (cleared in the shadow of the pose load)
+        for (int32_t b = threadIdx.x; b < SEG_BUCKETS; b += blockDim.x) s_seg[b] = 0u;
+    }
     // pose_src: the poses enter the filter through this launch (SLAM.java:90): every segment's workgroup takes its
     // particles' trig itself -- the arithmetic hides under the first wavefront's beam compaction -- and segment 0
     // stores pose and trig where the other kernels expect them (what k_pose_trig does in a launch of its own)
     // ord: the lanes take the particles in k_order's locality order; op is the particle whose product this lane forms
     const int32_t p = grp * blockDim.x + threadIdx.x;
     const size_t li = (size_t)mi * n + (p < n ? p : 0);
-    const int32_t op = ord ? perm[li] : (p < n ? p : 0);
-    const size_t gi = (size_t)mi * n + op;
+    int32_t op = ord ? perm[li] : (p < n ? p : 0);
+    size_t gi = (size_t)mi * n + op;
     XformDev t;
     if (ord) {
         const float4 o = ord[li];
@@ -344,7 +364,52 @@ k_score_c(const float *__restrict__ pose_src, const gms_beam *__restrict__ beams
     __syncthreads();
     GMS_STAMP(GMS_STAMP_ROW(0, blockIdx.x), 1);
     const int32_t nb = s_nb;
-    if (p >= n) return;
+    if constexpr (SEG) {
+        static_assert(U == 1, "the segment order serves particles in the caller's order");
+        if (nb > 0) {                                                  // (uniform)
+            extern __shared__ __align__(16) uint32_t s_seg[];
+            uint32_t *s_count = s_seg;                                                 // [SEG_BUCKETS]
+            uint32_t *s_start = s_seg + SEG_BUCKETS + (threadIdx.x >> 6) * SEG_BUCKETS;      // [16][SEG_BUCKETS] every wavefront's own copy of the starts
+            int32_t *s_op = (int32_t *)(s_seg + 17 * SEG_BUCKETS);                     // [1024]
+            float4 *s_slot = (float4 *)(s_seg + 17 * SEG_BUCKETS + 1024);              // [blockDim.x] (16-byte aligned: 21504 bytes in)
+            const int32_t tid = threadIdx.x, lane = tid & 63;
+            const double2 bm = s_beam[nb >> 1];
+            bool guard = false;
+            const int32_t gx = j_cell_fast(xform_x(t, bm.x, bm.y) - g.posx, g.rinv, guard);
+            const int32_t gy = j_cell_fast(xform_y(t, bm.x, bm.y) - g.posy, g.rinv, guard);
+            uint32_t key = ((((uint32_t)gy & 63u) << 2) | (((uint32_t)gx >> 4) & 3u)) & (SEG_BUCKETS - 1);   // (NaN converts to cell 0, as it scores)
+            if (guard | ((uint32_t)gx >= (uint32_t)g.W) | ((uint32_t)gy >= (uint32_t)g.H) | (p >= n)) key = SEG_BUCKETS - 1;
+            const uint32_t rank = atomicAdd(&s_count[key], 1u);
+            __syncthreads();
+            // exclusive scan of the 256 buckets, by EVERY wavefront for itself (lane l owns buckets 4 l .. 4 l + 3, one 16-byte read): a copy
+            // of the starts per wavefront costs 1 KB each and saves the two barriers a shared scan needs
+            static_assert(SEG_BUCKETS == 256, "four buckets per lane");
+            const uint4 c = ((const uint4 *)s_count)[lane];
+            uint32_t total = c.x + c.y + c.z + c.w, below = 0;         // the whole wavefront / the lanes below this one
+#define GMS_STEP_(O) { const uint32_t o = wave_xor<O>(total); below += (lane & O) ? o : 0u; total += o; }
+            GMS_STEP_(1) GMS_STEP_(2) GMS_STEP_(4) GMS_STEP_(8) GMS_STEP_(16) GMS_STEP_(32)
+#undef GMS_STEP_
+            ((uint4 *)s_start)[lane] = make_uint4(below, below + c.x, below + c.x + c.y, below + c.x + c.y + c.z);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // (a wavefront's LDS accesses are served in order)
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const uint32_t slot = s_start[key] + rank;                 // < blockDim.x: the counts sum to it
+            s_slot[slot] = make_float4((float)t.px, (float)t.py, (float)t.c, (float)t.s);    // (they were floats: nothing is lost)
+            s_op[slot] = p < n ? op : -1;
+            __syncthreads();
+            const float4 o = s_slot[tid];
+            t.px = (double)o.x; t.py = (double)o.y; t.c = (double)o.z; t.s = (double)o.w;
+            op = s_op[tid];
+            gi = (size_t)mi * n + (op < 0 ? 0 : op);
+#ifdef GMS_STAMPS
+            asm volatile("; the stamp below waits for the slot" :: "v"(o.x), "v"(op) : "memory");
+#endif
+            GMS_STAMP(GMS_STAMP_ROW(0, blockIdx.x), 5);
+            if (op < 0) return;
+        } else if (p >= n) return;
+    } else {
+        if (p >= n) return;
+    }
     double prod = 1.0;                                                 // GridMap.java:262
     // Software pipeline: the cell indices of batch b+1 are computed while the look-ups of batch b are in
     // flight, so the vector ALU work hides under the gather latency inside each wavefront (the gathers,
@@ -1736,7 +1801,20 @@ void gms_launch_pf_score(gms_pf *pf, const gms_beam *d_beams, int32_t B, int32_t
     // two or more workgroups per CU (see k_score_c's workgroup map; 24 576 particles, 1.5 per CU: 35.5 us without, 37.5 with; 32 768: 48.7 / 43.3)
     int32_t spread = nseg * groups >= 2 * (int64_t)m->n_cus ? 1 : 0;
     if (pf->score_spread >= 0) spread = pf->score_spread;
-    if (ordered)
+    // the segment order (k_score_c<1, true>), single-map handles only: GMS_SCORE_ORDER=0 keeps the caller's order; otherwise launches of
+    // 1024-lane workgroups take it (C3, one workgroup per CU: the step 42.9 -> 41.7 us; 65 536 particles, four per CU with the spread
+    // map: 115.7 -> 91.5 us); 512- and 256-lane workgroups do not (8192 particles: 36.1 -> 36.9 us with it, config 2: no difference).
+    // GMS_SCORE_SEGORDER=1 / 0 asks for it at every shape of more than one wavefront / at none
+    const bool seg_order = !ordered && pf->n_maps == 1 && threads > 64 && pf->order_mode != 0 &&
+                           (pf->seg_order > 0 || (pf->seg_order < 0 && threads == 1024));
+    if (seg_order) pf->seg_order_launches++;
+    if (seg_order)
+        hipLaunchKernelGGL((k_score_c<1, true>), dim3((unsigned)(nseg * groups), 1, pf->n_maps), dim3(threads),
+                           (size_t)(17 * SEG_BUCKETS + 1024) * 4 + (size_t)threads * sizeof(float4), m->stream, d_pose_src,
+                           d_beams, (const float4 *)nullptr, (const int32_t *)nullptr, B, beam_stride, pf->n, (int32_t)nseg, spread,
+                           pf->d_pose, pf->d_cs, m->d_fac, m->fac_stride, pf->offset, pf->d_part, pf->d_w, pf->d_logw, pose_dst,
+                           cs_dst, mo, m->gd);
+    else if (ordered)
         hipLaunchKernelGGL(k_score_c<3>, dim3((unsigned)(nseg * groups), 1, pf->n_maps), dim3(threads), 0, m->stream, d_pose_src,
                            d_beams, pf->d_ord, pf->d_perm, B, beam_stride, pf->n, (int32_t)nseg, 0, pf->d_pose, pf->d_cs,
                            m->d_fac, m->fac_stride, pf->offset, pf->d_part, pf->d_w, pf->d_logw, pose_dst, cs_dst, mo, m->gd);

@@ -1592,6 +1592,12 @@ class ParticleFilter:
         check(load().gms_pf_did_resample(self._h, ptr(f)))
         return bool(f[0]) if self.n_maps == 1 else f.astype(bool)
 
+    def segment_order_launches(self) -> int:
+        """scoring launches so far whose workgroups took their particles in the segment's end-point order (development, tests)"""
+        n = C.c_int64(0)
+        check(load().gms_pf_segment_order_launches(self._h, C.byref(n)))
+        return int(n.value)
+
     def last_step(self) -> dict:
         """Device-side record of the last normalise / scan step: the weighted pose of the SCORED population (what a
         fused scan step integrated the scan at), the strongest particle's pose, did_resample, n_ambiguous."""

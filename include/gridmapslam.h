@@ -1881,6 +1881,10 @@ int gms_map_tile_stats(gms_map *m, int32_t enable, int64_t *out4);
 int gms_debug_f32(gms_map *m, int32_t op, const float *in, float *out, int64_t n);
 /* Launches of the casts' bit-plane pre-pass on this handle so far (gms_map_cast): casts of an unchanged map add none. */
 int gms_map_cast_plane_builds(const gms_map *m, int64_t *builds);
+/* Development: how many of this filter's scoring launches so far ordered their workgroups' lanes by the segment's end-point lines
+ * (k_score_c<1, true>: single-map handles, 1024-lane workgroups; GMS_SCORE_SEGORDER, GMS_SCORE_ORDER=0).  Results
+ * do not depend on it; tests read it to know which kernel ran. */
+int gms_pf_segment_order_launches(const gms_pf *pf, int64_t *launches);
 /* Development: instrumented builds (-DGMS_STAMPS) write wall-clock stamps of their kernels' stages to dev_buffer
  * ([workgroup][16] uint64, 10 ns units; NULL turns it off); a product build returns GMS_ERR_STATE.  tools/stamps.py. */
 int gms_debug_set_stamps(gms_map *m, void *dev_buffer);

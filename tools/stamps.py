@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STAGES = {
-    0: ("k_score_c", {0: "entered", 3: "pose loaded (thread 0)", 4: "trig done (thread 0)", 1: "beams compacted, trig done", 2: "products stored"}),
+    0: ("k_score_c", {0: "entered", 3: "pose loaded (thread 0)", 4: "trig done (thread 0)", 1: "beams compacted, trig done", 5: "ordered (segment order: slot read back)", 2: "products stored"}),
     1: ("k_partials", {0: "entered", 2: "weights combined, sums accumulated (thread 0)", 3: "butterflies done", 4: "waves combined", 1: "left"}),
     2: ("k_norm_raycast", {0: "entered", 1: "ray: pose folded", 2: "far: rays set up", 3: "far: recurrence done (producer)", 4: "far: first consumer done",
                            5: "far: box committed", 9: "near: tile cleared", 10: "near: 64 steps counted", 11: "near: tile flushed", 12: "near: box committed",
@@ -72,6 +72,22 @@ def main():
     print("  k_score_c lookup phase per workgroup (us), by blockIdx & 7 (XCD) rows and blockIdx >> 3 columns:")
     for x in range(8):
         print("   ", " ".join(f"{dur[x + 8 * j]:5.1f}" for j in range(32)))
+    # the scoring workgroups' prologue and look-up phase: entered -> pose loaded -> barrier -> ordered (the segment order's sort; absent
+    # in a launch in the caller's order) -> products stored
+    def row(what, v):
+        v = v[~np.isnan(v)] * 0.01
+        if v.size:
+            print(f"  k_score_c per workgroup: {what:44s} n={v.size:4d}  min {v.min():6.2f}  median {np.median(v):6.2f}  max {v.max():6.2f}")
+    w = sc[:256]
+    has_order = not np.isnan(w[:, 5]).all()
+    row("entered -> pose loaded", w[:, 3] - w[:, 0])
+    row("pose loaded -> barrier", w[:, 1] - w[:, 3])
+    if has_order:
+        row("barrier -> ordered (the sort)", w[:, 5] - w[:, 1])
+        row("ordered -> products stored (look-up phase)", w[:, 2] - w[:, 5])
+    row("barrier -> products stored", w[:, 2] - w[:, 1])
+    row("entered -> products stored", w[:, 2] - w[:, 0])
+    print(f"  k_score_c: last products stored {(np.nanmax(w[:, 2]) - t0) * 0.01:.2f} us after the first workgroup entered")
     return 0
 
 
