@@ -22,6 +22,7 @@ LIB = os.path.join(LIBDIR, "libgridmapslam.so")
 # every particle on its own map) are kernel units whose C-ABI is gms_slam_host.hip's;
 # gms_probe.h is the device header the casts and the beam models share, gms_beams_device.h the ONE workgroup body of the two beam models
 # (each unit supplies its source of occupancy bits), gms_align_device.h the two alignment units' (staging, evaluation, step, store),
+# gms_nearest_device.h the ONE separable nearest-obstacle transform of gms_clearance.hip and gms_skeleton.hip (each unit instantiates its policy),
 # gms_slam_device.h what the device unit, gms_slam_align.hip and gms_slam_beams.hip share of a gms_slam's kernels (the per-particle prologue)
 SOURCES = ["gms_host.hip", "gms_slam_host.hip", "gms_fused_kernels.hip", "gms_query.hip", "gms_cast.hip", "gms_gain.hip", "gms_clearance.hip",
            "gms_reach.hip", "gms_frontier.hip", "gms_scatter.hip", "gms_locate.hip", "gms_modes.hip", "gms_beams.hip", "gms_align.hip",

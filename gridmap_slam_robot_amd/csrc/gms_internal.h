@@ -641,7 +641,9 @@ void gms_launch_view(gms_map *m, const double *src, const gms_view *v, void *d_o
 // everything down to query_plane), then clearance, then reach (it inflates with gms_clear_launch), then frontier, scatter and locate (they inflate
 // with gms_reach_inflate); cast and gain beside clearance, on the base alone, as modes (it takes the staging only).  Cast and beams share their device-side
 // probe geometry -- the staged plane window and the first-hit walk -- through gms_probe.h, a device header on gms_device.h alone; the two
-// beam models share their whole workgroup body through gms_beams_device.h on top of it ----
+// beam models share their whole workgroup body through gms_beams_device.h on top of it.  Clearance and sites and skeleton
+// (gms_skeleton.hip, beside clearance on the base) are ONE separable transform under two policies, kernels, launcher and checks, in
+// gms_nearest_device.h on gms_regions.h ----
 struct gms_slam;
 // the rectangle (x0, y0) + w x h (already w, h >= 1 and x0, y0 >= 0) inside a W x H map: the one copy of the test and its message
 int gms_rect_check(int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t W, int32_t H, const char *what);

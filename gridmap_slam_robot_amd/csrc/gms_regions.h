@@ -1,6 +1,6 @@
 // gms_regions.h -- the device helpers the feature units that label components and compact records share (gms_frontier.hip, gms_modes.hip;
-// gms_scatter.hip for the scan's look-up): the lock-free union, the "one turn per distinct key of the wavefront" loop, the integer
-// wavefront reductions and the look-up into a scan made by gms_launch_scan (gms_query.hip).  The step kernels' unit
+// gms_scatter.hip for the scan's look-up; gms_nearest_device.h for the wavefront minima): the lock-free union, the "one turn per
+// distinct key of the wavefront" loop, the integer wavefront reductions and the look-up into a scan made by gms_launch_scan (gms_query.hip).  The step kernels' unit
 // (gms_fused_kernels.hip) does not include it, and gms_device.h stays what it was: no kernel of the other units is compiled differently.
 #pragma once
 
@@ -64,6 +64,7 @@ __device__ __forceinline__ void wave_each_key(uint32_t key, uint32_t none, F f) 
 GMS_WAVE_REDUCE_(wave_add, int32_t, GMS_STEP_ADD_)
 GMS_WAVE_REDUCE_(wave_min, int32_t, GMS_STEP_MIN_)
 GMS_WAVE_REDUCE_(wave_max, int32_t, GMS_STEP_MAX_)
+GMS_WAVE_REDUCE_(wave_min, uint32_t, GMS_STEP_MIN_)
 GMS_WAVE_REDUCE_(wave_min, uint64_t, GMS_STEP_MIN64_)
 #undef GMS_STEP_ADD_
 #undef GMS_STEP_MIN_
