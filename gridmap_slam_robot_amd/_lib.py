@@ -105,6 +105,33 @@ class GmsFrontier(C.Structure):
     ]
 
 
+class GmsRooms(C.Structure):
+    """gms_rooms: a request for a map's rooms and doors (gridmapslam.h "rooms and doors")"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("core", C.c_int32), ("inflate", C.c_int32), ("mode", C.c_int32), ("min_core", C.c_int32), ("max_cost", C.c_int32),
+        ("filter", C.c_int32), ("pad", C.c_int32 * 2),
+    ]
+
+
+class GmsRoom(C.Structure):
+    """gms_room: one room's record, 56 bytes"""
+    _fields_ = [
+        ("anchor_x", C.c_int32), ("anchor_y", C.c_int32), ("core_count", C.c_int32), ("count", C.c_int32),
+        ("min_x", C.c_int32), ("min_y", C.c_int32), ("max_x", C.c_int32), ("max_y", C.c_int32),
+        ("max_depth", C.c_int32), ("doors", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64),
+    ]
+
+
+class GmsDoor(C.Structure):
+    """gms_door: one pair of touching rooms, 48 bytes"""
+    _fields_ = [
+        ("a", C.c_uint32), ("b", C.c_uint32), ("count", C.c_int32),
+        ("min_x", C.c_int32), ("min_y", C.c_int32), ("max_x", C.c_int32), ("max_y", C.c_int32), ("pad", C.c_int32),
+        ("sum_x2", C.c_int64), ("sum_y2", C.c_int64),
+    ]
+
+
 class GmsGain(C.Structure):
     """gms_gain: a view-gain request (gridmapslam.h "view gain")"""
     _fields_ = [("max_range", C.c_int32), ("filter", C.c_int32)]
@@ -263,6 +290,10 @@ GMS_LOCATE_SKIP = -32768
 FRONTIER_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsFrontier._fields_])     # gms_frontier
 assert FRONTIER_DTYPE.itemsize == C.sizeof(GmsFrontier) == 56
 GMS_FRONTIER_NONE = 0xFFFFFFFF
+ROOM_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<i4") for n, _ in GmsRoom._fields_])     # gms_room
+DOOR_DTYPE = np.dtype([(n, "<i8" if n.startswith("sum_") else "<u4" if n in ("a", "b") else "<i4") for n, _ in GmsDoor._fields_])     # gms_door
+assert ROOM_DTYPE.itemsize == C.sizeof(GmsRoom) == 56 and DOOR_DTYPE.itemsize == C.sizeof(GmsDoor) == 48 and C.sizeof(GmsRooms) == 48
+GMS_ROOM_NONE, GMS_ROOMS_MAX, GMS_ROOMS_STAGES = 0xFFFFFFFF, 0xFFFF, 5
 MODE_DTYPE = np.dtype([(n, "<f8" if t is C.c_double else ("<i4", (2,)) if n == "pad" else "<i4") for n, t in GmsMode._fields_])     # gms_mode
 assert MODE_DTYPE.itemsize == C.sizeof(GmsMode) == 112
 GMS_MODE_NONE = 0xFFFFFFFF
@@ -576,6 +607,15 @@ def load() -> C.CDLL:
     sig("gms_map_frontiers_dev", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32))
     sig("gms_slam_frontiers", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32), vp)
     sig("gms_slam_frontiers_dev", C.c_int, vp, i32, fp, vp, vp, vp, i32, C.POINTER(C.c_int32), vp)
+    rp, ip = C.POINTER(GmsRooms), C.POINTER(C.c_int32)
+    sig("gms_rooms_check", C.c_int, rp)
+    sig("gms_rooms_size", C.c_int, rp, vp, vp, vp, vp)
+    sig("gms_map_rooms", C.c_int, vp, i32, rp, vp, vp, vp, i32, ip, vp, i32, ip)
+    sig("gms_map_rooms_dev", C.c_int, vp, i32, rp, vp, vp, vp, i32, ip, vp, i32, ip)
+    sig("gms_slam_rooms", C.c_int, vp, i32, rp, vp, vp, vp, i32, ip, vp, i32, ip, vp)
+    sig("gms_slam_rooms_dev", C.c_int, vp, i32, rp, vp, vp, vp, i32, ip, vp, i32, ip, vp)
+    sig("gms_map_rooms_stats", C.c_int, vp, ip, C.POINTER(C.c_int64), ip)
+    sig("gms_map_rooms_stage_us", C.c_int, vp, C.POINTER(C.c_double))
     _lib = L
     return L
 

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libgridmapslam.so")
 # gms_clearance.hip (clearance fields), gms_reach.hip (cost-to-go fields), gms_frontier.hip (frontier regions), gms_scatter.hip
 # (particle seeding), gms_locate.hip (global scan matching), gms_modes.hip (pose modes), gms_beams.hip (the beam sensor model),
 # gms_align.hip (continuous scan alignment), gms_rollout.hip (trajectory rollouts), gms_route.hip (routes), gms_warp.hip (maps under a rigid transform)
-# and gms_skeleton.hip (nearest-obstacle sites and the free-space skeleton) are units of their own, kernels and C-ABI;
+# gms_skeleton.hip (nearest-obstacle sites and the free-space skeleton) and gms_rooms.hip (rooms and doors) are units of their own, kernels and C-ABI;
 # gms_census.hip (the census of a gms_slam's particle maps: counts, consensus, agreement) is a kernel unit whose C-ABI is gms_slam_host.hip's;
 # gms_slam_align.hip (the alignment of every particle of a gms_slam on its own field) and gms_slam_beams.hip (the beam sensor model of
 # every particle on its own map) are kernel units whose C-ABI is gms_slam_host.hip's;
@@ -26,7 +26,8 @@ LIB = os.path.join(LIBDIR, "libgridmapslam.so")
 # gms_slam_device.h what the device unit, gms_slam_align.hip and gms_slam_beams.hip share of a gms_slam's kernels (the per-particle prologue)
 SOURCES = ["gms_host.hip", "gms_slam_host.hip", "gms_fused_kernels.hip", "gms_query.hip", "gms_cast.hip", "gms_gain.hip", "gms_clearance.hip",
            "gms_reach.hip", "gms_frontier.hip", "gms_scatter.hip", "gms_locate.hip", "gms_modes.hip", "gms_beams.hip", "gms_align.hip",
-           "gms_slam_align.hip", "gms_slam_beams.hip", "gms_rollout.hip", "gms_route.hip", "gms_warp.hip", "gms_census.hip", "gms_skeleton.hip"]
+           "gms_slam_align.hip", "gms_slam_beams.hip", "gms_rollout.hip", "gms_route.hip", "gms_warp.hip", "gms_census.hip", "gms_skeleton.hip",
+           "gms_rooms.hip"]
 # -ffp-contract=off: the reference (JVM) never fuses a multiply with an add; parity depends on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
          "-shared", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]

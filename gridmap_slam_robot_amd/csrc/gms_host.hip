@@ -251,6 +251,8 @@ static int map_free(gms_map *m) {
     hipFree(m->d_site_field);
     hipFree(m->d_front_plane); hipFree(m->d_front_nf); hipFree(m->d_front_label); hipFree(m->d_front_wscan); hipFree(m->d_front_table); hipFree(m->d_front_ctl);
     if (m->h_front_ctl) hipHostFree(m->h_front_ctl);
+    hipFree(m->d_rooms_field); hipFree(m->d_rooms_label); hipFree(m->d_rooms_plane); hipFree(m->d_rooms_wscan); hipFree(m->d_rooms_ctl); hipFree(m->d_rooms_table); hipFree(m->d_rooms_doors);
+    if (m->h_rooms_ctl) hipHostFree(m->h_rooms_ctl);
     hipFree(m->scatter.d_elig); hipFree(m->scatter.d_pre);
     hipFree(m->locate.d_pyr); hipFree(m->locate.d_list[0]); hipFree(m->locate.d_list[1]); hipFree(m->locate.d_ctl);
     if (m->locate.h_ctl) hipHostFree(m->locate.h_ctl);

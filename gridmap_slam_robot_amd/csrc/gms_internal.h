@@ -161,6 +161,21 @@ struct gms_map {
     int32_t front_cap;            // regions the table holds
     uint32_t *d_front_ctl;        // {regions, regions with count >= min_size}
     uint32_t *h_front_ctl;        // pinned: read back once per request
+    // rooms and doors (gms_rooms.hip); allocated by the first request, the two tables grow and never shrink
+    uint32_t *d_rooms_field;      // [H][W] the cores' cell counts at their roots, then the working keys cost << 16 | rank the tiles relax
+    uint32_t *d_rooms_label;      // [H][W] the cores' label field; defined where the core plane has a bit
+    uint32_t *d_rooms_plane;      // [2][H][gms_plane_wpr] the core plane, and the plane of the kept cores' roots
+    uint32_t *d_rooms_wscan;      // [words] the kept roots' word counts, scanned within blocks of GMS_SCAN | [blocks] the blocks' offsets
+    uint32_t *d_rooms_ctl;        // {tile runs (64 bits), the active count of four rounds, rooms, door entries, door table overflow, 7 spare} | [2][tiles] the tiles' active flags
+    uint32_t *h_rooms_ctl;        // pinned: the first 16 words of it
+    unsigned char *d_rooms_table; // [rooms_cap] gms_room | [rooms_cap] the rooms' anchor indices by rank | [3][rooms_cap] the doors per smaller room: scanned, kept, filled | [blocks + 1] the scan's offsets and total
+    int32_t rooms_cap;            // rooms the table holds
+    unsigned char *d_rooms_doors; // [rooms_door_cap] the pair keys rank_a << 16 | rank_b, open addressing | [rooms_door_cap] what each entry accumulates | [rooms_door_cap] the entries' indices by run
+    int32_t rooms_door_cap;       // entries the door table holds, a power of two
+    int32_t rooms_rounds;         // gms_map_rooms_stats: rounds launched by the last call
+    int64_t rooms_tile_runs;      // ... tile relaxations that ran
+    int32_t rooms_door_rebuilds;  // ... and how often the door table was doubled and filled again
+    double rooms_stage_us[GMS_ROOMS_STAGES];  // gms_map_rooms_stage_us: the last call's parts on the host clock (GMS_ROOMS_STAGES in the environment), else 0
     // particle seeding (gms_scatter.hip): the table of the last request -- every map's eligible plane and its scanned counts --, allocated
     // by the first request; current: it is the table of logData as it stands for exactly that request (map_planes_stale clears it)
     struct {

@@ -579,6 +579,80 @@ def frontier_centroids(records) -> np.ndarray:
     return np.stack([r["sum_x"] / n, r["sum_y"] / n], axis=-1)
 
 
+def room_centroids(records) -> np.ndarray:
+    """The centroids of rooms (GridMap.rooms' room records) in cells, float64 [n][2] = (x, y): sum / count"""
+    r = np.asarray(records)
+    n = r["count"].astype(np.float64)
+    return np.stack([r["sum_x"] / n, r["sum_y"] / n], axis=-1)
+
+
+def door_points(doors, position, resolution: float) -> np.ndarray:
+    """The mean opening position of every door record (GridMap.rooms' doors) in world coordinates, float64 [n][2]: the mean of the
+    contact pairs' cell centres, position + (sum / (2 count) + 0.5) * resolution"""
+    d = np.asarray(doors)
+    n = 2.0 * d["count"].astype(np.float64)
+    res = np.float64(np.float32(resolution))
+    return np.stack([np.float64(np.float32(position[0])) + (d["sum_x2"] / n + 0.5) * res, np.float64(np.float32(position[1])) + (d["sum_y2"] / n + 0.5) * res], axis=-1)
+
+
+def rooms_of_cells(labels, cells, x0: int = 0, y0: int = 0) -> np.ndarray:
+    """Which room each of cells [n][2] = (x, y) lies in -- a frontier goal, a particle's cell (cells_of_poses) --, from the label field
+    GridMap.rooms returns for the rectangle at (x0, y0): uint32 [n], the room's anchor index, GMS_ROOM_NONE for a cell without a room
+    or outside the rectangle"""
+    lab = np.asarray(labels)
+    c = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+    x, y = c[:, 0] - int(x0), c[:, 1] - int(y0)
+    inside = (x >= 0) & (y >= 0) & (x < lab.shape[1]) & (y < lab.shape[0])
+    out = np.full(len(c), _lib.GMS_ROOM_NONE, dtype=np.uint32)
+    out[inside] = lab[y[inside], x[inside]]
+    return out
+
+
+def room_graph(rooms, doors, W: Optional[int] = None) -> dict:
+    """The rooms' adjacency: {anchor index: {neighbour's anchor index: the door's contact count}}, the labels' values as keys.  With
+    W, the map's width in cells, every room of `rooms` is a key (anchor_y * W + anchor_x), a room without a door with an empty
+    dict; without it only the rooms that a door names appear."""
+    d = np.asarray(doors)
+    g = {}
+    if W is not None:
+        r = np.asarray(rooms)
+        g = {int(k): {} for k in (r["anchor_y"].astype(np.int64) * int(W) + r["anchor_x"]).tolist()}
+    for a, b, n in zip(d["a"].tolist(), d["b"].tolist(), d["count"].tolist()):
+        g.setdefault(a, {})[b] = n
+        g.setdefault(b, {})[a] = n
+    return g
+
+
+def _query_rooms(src: "_Source", core: int, inflate: int, not_free: bool, min_core: int, max_cost: int, rect, want, caps, dev=None):
+    """want = (labels, depth): which fields the host form returns; caps = (cap_rooms, cap_doors).  dev = (labels, depth, rooms, doors,
+    shown_out), torch device tensors or None each: the device form, which returns (n_rooms, n_doors)"""
+    q = _lib.GmsRooms(*_rect(src.W, src.H, rect), int(core), int(inflate), _obstacles(not_free), int(min_core), int(max_cost), src.filter)
+    ow, oh, lb, db = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    check(load().gms_rooms_size(C.byref(q), C.byref(ow), C.byref(oh), C.byref(lb), C.byref(db)))
+    nr, nd = C.c_int32(0), C.c_int32(0)
+    if dev is not None:
+        labels, depth, rooms, doors, shown_out = dev
+        cap_r = 0 if rooms is None else rooms.numel() * rooms.element_size() // _lib.ROOM_DTYPE.itemsize
+        cap_d = 0 if doors is None else doors.numel() * doors.element_size() // _lib.DOOR_DTYPE.itemsize
+        src.dev("rooms", C.byref(q), _device_ptr("rooms", "labels", labels, lb.value, optional=True), _device_ptr("rooms", "depth", depth, db.value, optional=True),
+                _device_ptr("rooms", "rooms", rooms, optional=True), int(cap_r), C.byref(nr), _device_ptr("rooms", "doors", doors, optional=True), int(cap_d),
+                C.byref(nd), shown_out=shown_out)
+        return int(nr.value), int(nd.value)
+    shape = (oh.value, ow.value)
+    cap_r, cap_d = int(caps[0]), int(caps[1])
+    lab = np.empty(shape, dtype=np.uint32) if want[0] else None
+    dep = np.empty(shape, dtype=np.uint16) if want[1] else None
+    rooms = np.zeros(cap_r, dtype=_lib.ROOM_DTYPE)
+    doors = np.zeros(cap_d, dtype=_lib.DOOR_DTYPE)
+    tail = src.host("rooms", C.byref(q), None if lab is None else ptr(lab), None if dep is None else ptr(dep), ptr(rooms) if cap_r else None, cap_r, C.byref(nr),
+                    ptr(doors) if cap_d else None, cap_d, C.byref(nd))
+    out = {"rooms": rooms[:min(nr.value, cap_r)], "doors": doors[:min(nd.value, cap_d)], "n_rooms": int(nr.value), "n_doors": int(nd.value), "labels": lab,
+           "depth": dep}
+    if tail:
+        out["shown"] = tail[0]
+    return out
+
+
 def cells_of_poses(poses, position, resolution: float):
     """probabilityOf's cell of every pose of poses [P][3] (GridMap.java:273-274): (int)((x - position.x) / resolution) in double -- the
     pose's floats and the map's float position and resolution widened -- with Java's cast: toward zero (a coordinate in (-1, 0) cells
@@ -1140,6 +1214,36 @@ class GridMap:
         them None.  Returns n_found; the call waits on the stream once (once more when the handle's region table has to grow), so the
         outputs are complete when it returns."""
         return _query_frontiers(self._src(mi), min_size, inflate, cost, rect, False, 0, dev=(records, labels, None))
+
+    def rooms(self, core: int = 15, inflate: int = 5, not_free: bool = True, min_core: int = 1, max_cost: int = 0xFFFE, rect=None,
+              labels: bool = True, depth: bool = False, cap_rooms: int = 1024, cap_doors: int = 4096, mi: int = 0) -> dict:
+        """Rooms and doors (gridmapslam.h "rooms and doors") of map mi: the cells not blocked at inflation `core` fall into 4-connected
+        cores, the cores of at least min_core cells are the rooms, ranked by their anchors, and every cell not blocked at inflation
+        `inflate` goes to the room that minimises (cost-to-go, rank) within max_cost.  Returns a dict: "rooms" (ROOM_DTYPE, rank
+        order, at most cap_rooms), "doors" (DOOR_DTYPE: one record per pair of rooms whose cells touch across a cell edge, ascending
+        (a, b), at most cap_doors), "n_rooms" / "n_doors" (the true numbers), "labels" (uint32 [h][w] of rect, the room's anchor index
+        y * W + x or GMS_ROOM_NONE; None unless asked for) and "depth" (uint16 [h][w], the cost outside the room's core, GMS_REACH_FAR
+        without a room; None unless asked for).  Helpers: room_centroids, door_points, rooms_of_cells, room_graph."""
+        return _query_rooms(self._src(mi), core, inflate, not_free, min_core, max_cost, rect, (labels, depth), (cap_rooms, cap_doors))
+
+    def rooms_dev(self, labels=None, depth=None, rooms=None, doors=None, core: int = 15, inflate: int = 5, not_free: bool = True, min_core: int = 1,
+                  max_cost: int = 0xFFFE, rect=None, mi: int = 0) -> tuple:
+        """rooms() with device memory on the handle's stream: labels (h * w * 4 bytes), depth (h * w * 2 bytes), rooms (room for
+        bytes // 56 gms_room, 8-byte aligned) and doors (bytes // 48 gms_door, 8-byte aligned) are contiguous torch device tensors, any
+        of them None.  Returns (n_rooms, n_doors); the call waits on the stream for the number of rooms, between batches of rounds
+        and for the door table, and returns with the last copies into the outputs enqueued."""
+        return _query_rooms(self._src(mi), core, inflate, not_free, min_core, max_cost, rect, None, None, dev=(labels, depth, rooms, doors, None))
+
+    def rooms_stats(self) -> dict:
+        """diagnostics of the last rooms() on this handle: {"rounds": launches over the tiles, "tile_runs": tile relaxations that
+        actually ran, "door_rebuilds": how often the door table was doubled and filled again, "stage_us": the host clock's
+        microseconds of the call's parts (planes, cores, rounds, fields and records, doors) where GMS_ROOMS_STAGES is set in the
+        environment -- the call then waits on the stream after each --, else zeros}"""
+        rounds, runs, rebuilds = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        us = (C.c_double * _lib.GMS_ROOMS_STAGES)()
+        check(load().gms_map_rooms_stats(self._h, C.byref(rounds), C.byref(runs), C.byref(rebuilds)))
+        check(load().gms_map_rooms_stage_us(self._h, us))
+        return {"rounds": int(rounds.value), "tile_runs": int(runs.value), "door_rebuilds": int(rebuilds.value), "stage_us": list(us)}
 
     def reach_stats(self) -> dict:
         """diagnostics of the last cost-to-go field made on this handle: {"rounds": launches over the tiles, "tile_runs": tile
@@ -2086,6 +2190,10 @@ class _SlamHandle:
         return _query_frontiers(self._src("frontiers", which, filter), min_size, inflate, cost, rect, labels, cap,
                                 dev=(records_out, labels_out, shown_out) if dev else None)
 
+    def _rooms(self, which, filter: int, core: int, inflate: int, not_free: bool, min_core: int, max_cost: int, rect, want, caps, dev):
+        """gms_slam_rooms[_dev]: the host form's dict with "shown", or -- dev = (labels, depth, rooms, doors, shown_out) -- (n_rooms, n_doors)"""
+        return _query_rooms(self._src("rooms", which, filter), core, inflate, not_free, min_core, max_cost, rect, want, caps, dev=dev)
+
     def _census_request(self, min_known: int, filter: int, write_map: bool) -> _lib.GmsCensus:
         c = _lib.GmsCensus(int(min_known), int(filter), _lib.GMS_CENSUS_WRITE_MAP if write_map else 0, 0)
         check(load().gms_census_check(C.byref(c), self.num_particles, int(self.params.n_maps)))
@@ -2343,6 +2451,18 @@ class SLAMParticleMaps(_SlamHandle):
         particle's whole-map field, as reach() returns it.  records_out / labels_out / shown_out (torch device tensors, cost then a
         device tensor or None): the device form, which returns n_found alone."""
         return self._frontiers(which, 0, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
+
+    def rooms(self, which="strongest", core: int = 15, inflate: int = 5, not_free: bool = True, min_core: int = 1, max_cost: int = 0xFFFE, rect=None,
+              labels: bool = True, depth: bool = False, cap_rooms: int = 1024, cap_doors: int = 4096) -> dict:
+        """Rooms and doors of particle `which`'s OWN map (GridMap.rooms' dict, with "shown": the particle that was read).  which = a
+        particle index or "strongest" (picked on the device as view() picks it, GMS_ERR_STATE before the first update).
+        Diagnostics: grid_map.rooms_stats()."""
+        return self._rooms(which, 0, core, inflate, not_free, min_core, max_cost, rect, (labels, depth), (cap_rooms, cap_doors), None)
+
+    def rooms_dev(self, which="strongest", labels=None, depth=None, rooms=None, doors=None, shown_out=None, core: int = 15, inflate: int = 5,
+                  not_free: bool = True, min_core: int = 1, max_cost: int = 0xFFFE, rect=None) -> tuple:
+        """rooms() into torch device tensors (GridMap.rooms_dev's), shown_out the int32 index; returns (n_rooms, n_doors)"""
+        return self._rooms(which, 0, core, inflate, not_free, min_core, max_cost, rect, None, None, (labels, depth, rooms, doors, shown_out))
 
     def gain(self, poses, probes, max_range: int, which="strongest", out=None, shown_out=None):
         """The view gain of the CALLER'S candidate poses [P][3] in particle `which`'s OWN map (GridMap.gain's records): (records [P],
@@ -2627,6 +2747,18 @@ class SLAMParticleMapsBatch(_SlamHandle):
         """SLAMParticleMaps.frontiers for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown
         is the handle-wide slot filter * num_particles + k whose regions were made, as view() reports it"""
         return self._frontiers(self._local(filter, which), filter, min_size, inflate, cost, rect, labels, cap, records_out, labels_out, shown_out)
+
+    def rooms(self, which="strongest", filter: int = 0, core: int = 15, inflate: int = 5, not_free: bool = True, min_core: int = 1,
+              max_cost: int = 0xFFFE, rect=None, labels: bool = True, depth: bool = False, cap_rooms: int = 1024, cap_doors: int = 4096) -> dict:
+        """SLAMParticleMaps.rooms for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; "shown"
+        is the handle-wide slot filter * num_particles + k whose map was read, as view() reports it"""
+        return self._rooms(self._local(filter, which), filter, core, inflate, not_free, min_core, max_cost, rect, (labels, depth), (cap_rooms, cap_doors), None)
+
+    def rooms_dev(self, which="strongest", filter: int = 0, labels=None, depth=None, rooms=None, doors=None, shown_out=None, core: int = 15,
+                  inflate: int = 5, not_free: bool = True, min_core: int = 1, max_cost: int = 0xFFFE, rect=None) -> tuple:
+        """SLAMParticleMaps.rooms_dev for filter `filter`"""
+        return self._rooms(self._local(filter, which), filter, core, inflate, not_free, min_core, max_cost, rect, None, None,
+                           (labels, depth, rooms, doors, shown_out))
 
     def gain(self, poses, probes, max_range: int, which="strongest", filter: int = 0, out=None, shown_out=None):
         """SLAMParticleMaps.gain for filter `filter`: which = "strongest" (that filter's) or a FILTER-LOCAL particle index; shown is

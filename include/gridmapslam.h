@@ -870,6 +870,117 @@ int gms_slam_frontiers(gms_slam *s, int32_t which, const gms_frontiers *f, const
 int gms_slam_frontiers_dev(gms_slam *s, int32_t which, const gms_frontiers *f, const uint16_t *dev_cost, uint32_t *dev_labels, gms_frontier *dev_records,
                            int32_t cap, int32_t *n_found, int32_t *dev_shown);
 
+/* ---- rooms and doors: from geometry to places ----------------------------------------------------------------------------------------
+ * Which room a cell, a frontier goal or a particle is in, which rooms exist, which are connected and where the door between two of
+ * them is: what an exploration or task planner builds on top of the fields above (visit rooms one at a time, rank frontiers per room,
+ * plan room to room before planning cells).  The method is the morphological room segmentation of the survey literature (Bormann et
+ * al., "Room segmentation: survey, implementation, and analysis", ICRA 2016) -- erode the free space until rooms fall apart, then grow
+ * the pieces back by a wavefront -- stated in this library's own integer terms (the reference has no such method), so every output is
+ * unique.  All of it is over the WHOLE map; only the two field outputs are a rectangle (gms_view's rules, as the frontier label field).
+ *
+ * TRAVERSABLE: a cell that the cost-to-go fields do not call BLOCKED for (mode, inflate), 0 <= inflate <= 254: exactly gms_map_reach's
+ * rule, cells off the map included (they do not exist).
+ * CORE CELL: a cell not BLOCKED for (mode, core), inflate < core <= 255.  Every core cell is traversable.
+ * CORE: a maximal 4-connected set of core cells.  This equals connectivity under the cost-to-go fields' MOVES restricted to core
+ * cells: a legal diagonal step needs both cells it squeezes between, and either of them joins its two ends by axis steps.  Its ANCHOR
+ * is its member of the smallest linear index y * W + x, its size its cell count.
+ * ROOM: a core with size >= min_core (min_core >= 1).  Rooms are ranked 0, 1, ... in ascending anchor order.  More than GMS_ROOMS_MAX
+ * rooms: GMS_ERR_INVALID with the count in gms_last_error, no output written, the handle as good as before for later calls.
+ * GROWTH: for every traversable cell c, key(c) = the lexicographic minimum of (summed step cost, rank of the room the path starts in)
+ * over the cost-to-go fields' legal paths (axis GMS_REACH_AXIS, diagonal GMS_REACH_DIAG, no corner cutting, through traversable cells
+ * only) from any cell of any room to c; paths whose cost exceeds max_cost (1 .. 0xFFFE) are dropped, and candidate costs are formed so
+ * that they cannot wrap.  A cell of a room has (0, own rank).  Cells of cores that did not qualify are grown into like any other
+ * traversable cell.  A cell equally far from two rooms belongs to the one with the smaller anchor.  A traversable cell that no room
+ * reaches within max_cost, and every blocked cell, has no room.  This is a shortest-path problem over an ordered pair, so the fixpoint
+ * is unique however the relaxation is scheduled.
+ *
+ * The outputs (each may be NULL):
+ *   labels  uint32_t [h][w]: the anchor index of the cell's room, else GMS_ROOM_NONE.
+ *   depth   uint16_t [h][w]: the cost component of key -- how far outside its room's core the cell lies; 0 inside the core,
+ *           GMS_REACH_FAR where there is no room.
+ *   rooms   one gms_room per room in rank order; the first cap_rooms are stored, *n_rooms (may be NULL) is the true number.
+ *   doors   one gms_door per unordered pair of rooms a < b (by anchor) with at least one CONTACT: a pair of axis-adjacent cells (p, q)
+ *           with label(p) = a and label(q) = b.  Diagonal contact does not count.  `count` is the number of contacts -- the door's
+ *           width in cells, summed over all openings between the two rooms --, the box is over all contact cells, sum_x2 / sum_y2 are
+ *           the sums of px + qx and py + qy: the mean opening position is sum / (2 count) cells, the caller's division.  In ascending
+ *           (a, b) order; the first cap_doors are stored, *n_doors (may be NULL) is the true number.
+ * cap == 0 with a NULL table is allowed for either.
+ *
+ * "Sees the map as a download would return it at that moment", "changes no later result of its handle" and the argument checks before
+ * anything is enqueued (GMS_ERR_INVALID, nothing touched) are the clearance fields' rules.  A map of 2^32 - 1 cells or more is refused.
+ *
+ * How: (1) the blocked plane at R = core (gms_map_reach's inflation) becomes the core plane in a plane of this call's own, so that the
+ * inflation at R = inflate can follow; (2) the cores by the frontiers' labelling with 4-connectivity -- tile-local union in LDS, the
+ * lock-free union across tile edges, the chase to the root -- and their sizes by integer atomics at the root; (3) the roots with
+ * size >= min_core ranked by a scan; their number is read back once; (4) every room cell gets the working key 0 << 16 | rank in a
+ * uint32 field of the whole map, every other cell 0xFFFFFFFF, and the tiles around the rooms' rims are marked; (5) ROUNDS as
+ * gms_map_reach's, on the key cost << 16 | rank, whose numeric order is the lexicographic one: a relaxation is
+ * min(cur, neighbour + (step << 16)), one 32-bit store publishes cost and label together; rounds <= max_cost / GMS_REACH_AXIS + 2,
+ * GMS_ERR_INTERNAL beyond (GMS_ROOMS_BATCH in the environment: rounds per read-back, default 8); (6) the room records by integer
+ * atomics, the lanes that share a room combined first; (7) the contacts -- every cell looks east and south -- into an open-addressing
+ * table on the handle, which doubles and is filled again while it is more than half full; the entries leave in key order: the doors
+ * whose smaller room is a form one run, the runs are laid out by a scan over the rooms, and an entry's place within its run is the
+ * number of smaller keys there -- work of the sum of the squared run lengths (a hall with 1000 doors: 10^6 loads).  EVERY
+ * form, _dev included, waits on the handle's stream: once for the number of rooms, once per batch of rounds, once per door table. */
+#define GMS_ROOM_NONE 0xFFFFFFFFu                              /* a label: no room */
+#define GMS_ROOMS_MAX 0xFFFF                                   /* rooms a call can rank */
+typedef struct gms_rooms {
+    int32_t x0, y0, w, h;       /* the cell rectangle of labels and depth */
+    int32_t core;               /* cells, inflate + 1 .. 255: the erosion that makes rooms fall apart */
+    int32_t inflate;            /* cells, 0 .. 254: the robot's inflation, as in gms_reach */
+    int32_t mode;               /* GMS_CLEAR_OCCUPIED / GMS_CLEAR_NOT_FREE */
+    int32_t min_core;           /* >= 1: the smallest core that is a room */
+    int32_t max_cost;           /* 1 .. 0xFFFE: how far a room grows out of its core */
+    int32_t filter;             /* batched gms_slam handles with GMS_VIEW_STRONGEST: whose strongest particle (ignored elsewhere) */
+    int32_t pad[2];             /* not read */
+} gms_rooms;                    /* 48 bytes */
+typedef struct gms_room {       /* 56 bytes */
+    int32_t anchor_x, anchor_y; /*  0,  4: the core's member of the smallest linear index */
+    int32_t core_count;         /*  8: cells of the core */
+    int32_t count;              /* 12: cells labelled with this room */
+    int32_t min_x, min_y;       /* 16, 20: the bounding box of those cells, inclusive */
+    int32_t max_x, max_y;       /* 24, 28 */
+    int32_t max_depth;          /* 32: the largest depth among them */
+    int32_t doors;              /* 36: door records that name this room */
+    int64_t sum_x, sum_y;       /* 40, 48: their coordinate sums; the centroid is sum / count, the caller's division */
+} gms_room;
+typedef struct gms_door {       /* 48 bytes */
+    uint32_t a, b;              /*  0,  4: the two rooms' anchor indices, a < b */
+    int32_t count;              /*  8: contacts */
+    int32_t min_x, min_y;       /* 12, 16: the bounding box of all contact cells, inclusive */
+    int32_t max_x, max_y;       /* 20, 24 */
+    int32_t pad;                /* 28: zero */
+    int64_t sum_x2, sum_y2;     /* 32, 40: the sums of px + qx and of py + qy over the contacts */
+} gms_door;
+/* Pure host code: everything about the request but the map's bounds, which it does not know -- w, h >= 1, x0, y0 >= 0,
+ * 0 <= inflate <= 254, inflate < core <= 255, the mode, min_core >= 1, 1 <= max_cost <= 0xFFFE.  gms_rooms_size also returns the
+ * rectangle's size in cells and the two fields' sizes in bytes (any of the four may be NULL). */
+int gms_rooms_check(const gms_rooms *q);
+int gms_rooms_size(const gms_rooms *q, int32_t *out_w, int32_t *out_h, int64_t *label_bytes, int64_t *depth_bytes);
+/* Map mi of a shared or batched map.  labels, depth, rooms, doors: host memory, staged through the views' buffer.
+ * _dev: dev_labels (4-byte aligned), dev_depth (2-byte aligned), dev_rooms and dev_doors (8-byte aligned) are device memory, written on
+ * the handle's stream (a misaligned pointer: GMS_ERR_INVALID, nothing touched); n_rooms and n_doors stay HOST pointers, and the call
+ * waits on that stream as said above; it returns with the last copies into the outputs enqueued, not waited for. */
+int gms_map_rooms(gms_map *m, int32_t mi, const gms_rooms *q, uint32_t *labels, uint16_t *depth, gms_room *rooms, int32_t cap_rooms, int32_t *n_rooms,
+                  gms_door *doors, int32_t cap_doors, int32_t *n_doors);
+int gms_map_rooms_dev(gms_map *m, int32_t mi, const gms_rooms *q, uint32_t *dev_labels, uint16_t *dev_depth, gms_room *dev_rooms, int32_t cap_rooms,
+                      int32_t *n_rooms, gms_door *dev_doors, int32_t cap_doors, int32_t *n_doors);
+/* One particle's own map of the per-particle filter: `which`, GMS_VIEW_STRONGEST, q->filter, *shown (may be NULL; _dev: a device
+ * int32_t *) and the GMS_ERR_STATE cases are gms_slam_view's.  gms_slam_clearance's pre-pass packs the shown particle's obstacle bits,
+ * and the shared maps' kernels run on those. */
+int gms_slam_rooms(gms_slam *s, int32_t which, const gms_rooms *q, uint32_t *labels, uint16_t *depth, gms_room *rooms, int32_t cap_rooms, int32_t *n_rooms,
+                   gms_door *doors, int32_t cap_doors, int32_t *n_doors, int32_t *shown);
+int gms_slam_rooms_dev(gms_slam *s, int32_t which, const gms_rooms *q, uint32_t *dev_labels, uint16_t *dev_depth, gms_room *dev_rooms, int32_t cap_rooms,
+                       int32_t *n_rooms, gms_door *dev_doors, int32_t cap_doors, int32_t *n_doors, int32_t *dev_shown);
+/* The last call on this handle (any may be NULL): the rounds launched, the tile relaxations that actually ran, and how often the door
+ * table was doubled and filled again.  A gms_slam's: on the gms_map of gms_slam_handles. */
+int gms_map_rooms_stats(const gms_map *m, int32_t *rounds, int64_t *tile_runs, int32_t *door_rebuilds);
+/* Measurement: with GMS_ROOMS_STAGES set in the environment a call waits on the stream at the end of each of its parts -- planes,
+ * cores, rounds, fields and records, doors -- and keeps the host clock's microseconds of each; us [GMS_ROOMS_STAGES] receives those of
+ * the last call on this handle, all 0 without the variable (nothing is waited for then). */
+#define GMS_ROOMS_STAGES 5
+int gms_map_rooms_stage_us(const gms_map *m, double *us);
+
 /* ---- view gain: what a scan from a candidate pose would reveal -------------------------------------------------------------------
  * What a goal picker asks after "where are the frontiers and what does each cost": how much never-observed space a scan taken at a
  * candidate pose would see.  This library's own definition (the reference has no such method); all of it is integer arithmetic.

@@ -267,6 +267,30 @@ public:
     gms_frontiers fullFrontiers(int minSize = 1, int inflate = 0) const { return gms_frontiers{0, 0, w_, hgt_, minSize, inflate, 0, 0}; }
     /** rounds launched and tile relaxations run for the last cost-to-go field of this handle */
     void reachStats(int32_t *rounds, int64_t *tileRuns) const { check(gms_map_reach_stats(h_, rounds, tileRuns)); }
+    /** Rooms and doors of map mi (gridmapslam.h "rooms and doors"): the room records in rank order (at most capRooms); *doors (may be
+     *  null) receives the door records in ascending (a, b) order (at most capDoors), *labels / *depth (may be null) the two fields of
+     *  q's rectangle, *found (may be null) the true numbers {rooms, doors}. */
+    std::vector<gms_room> rooms(const gms_rooms &q, int capRooms = 1024, std::vector<gms_door> *doors = nullptr, int capDoors = 4096,
+                                std::vector<uint32_t> *labels = nullptr, std::vector<uint16_t> *depth = nullptr, int *found = nullptr, int mi = 0) {
+        int64_t lb = 0, db = 0;
+        check(gms_rooms_size(&q, nullptr, nullptr, &lb, &db));
+        if (labels) labels->resize((size_t)lb / sizeof(uint32_t));
+        if (depth) depth->resize((size_t)db / sizeof(uint16_t));
+        std::vector<gms_room> rec((size_t)capRooms);
+        if (doors) doors->resize((size_t)capDoors);
+        const int cd = doors ? capDoors : 0;
+        int32_t nr = 0, nd = 0;
+        check(gms_map_rooms(h_, mi, &q, labels ? labels->data() : nullptr, depth ? depth->data() : nullptr, capRooms ? rec.data() : nullptr, capRooms, &nr,
+                            cd ? doors->data() : nullptr, cd, &nd));
+        rec.resize((size_t)(nr < capRooms ? nr : capRooms));
+        if (doors) doors->resize((size_t)(nd < cd ? nd : cd));
+        if (found) { found[0] = nr; found[1] = nd; }
+        return rec;
+    }
+    /** the whole map's rooms request */
+    gms_rooms fullRooms(int core = 15, int inflate = 5, int mode = GMS_CLEAR_NOT_FREE, int minCore = 1, int maxCost = 0xFFFE) const {
+        return gms_rooms{0, 0, w_, hgt_, core, inflate, mode, minCore, maxCost, 0, {0, 0}};
+    }
     /** The offset table of a scan for locate() (gridmapslam.h "global scan matching"; pure host code): [nTheta][B][2] end cells
      *  relative to the pose's cell under the headings theta0 + k * dtheta; misses and beams beyond 4095 cells become SKIP pairs. */
     std::vector<int16_t> locateOffsets(const Observation &z, double theta0, double dtheta, int nTheta) const {
@@ -633,6 +657,26 @@ public:
         check(gms_slam_frontiers(h_, which, &f, cost ? cost->data() : nullptr, labels ? labels->data() : nullptr, cap ? rec.data() : nullptr, cap, &n, &picked));
         rec.resize((size_t)(n < cap ? n : cap));
         if (found) *found = n;
+        if (shown) *shown = picked;
+        return rec;
+    }
+    /** Rooms and doors of particle `which`'s own map (GridMap::rooms' values); *shown (may be null) receives the particle that was read */
+    std::vector<gms_room> rooms(const gms_rooms &q, int capRooms = 1024, std::vector<gms_door> *doors = nullptr, int capDoors = 4096,
+                                std::vector<uint32_t> *labels = nullptr, std::vector<uint16_t> *depth = nullptr, int *found = nullptr,
+                                int which = GMS_VIEW_STRONGEST, int *shown = nullptr) {
+        int64_t lb = 0, db = 0;
+        check(gms_rooms_size(&q, nullptr, nullptr, &lb, &db));
+        if (labels) labels->resize((size_t)lb / sizeof(uint32_t));
+        if (depth) depth->resize((size_t)db / sizeof(uint16_t));
+        std::vector<gms_room> rec((size_t)capRooms);
+        if (doors) doors->resize((size_t)capDoors);
+        const int cd = doors ? capDoors : 0;
+        int32_t nr = 0, nd = 0, picked = 0;
+        check(gms_slam_rooms(h_, which, &q, labels ? labels->data() : nullptr, depth ? depth->data() : nullptr, capRooms ? rec.data() : nullptr, capRooms, &nr,
+                             cd ? doors->data() : nullptr, cd, &nd, &picked));
+        rec.resize((size_t)(nr < capRooms ? nr : capRooms));
+        if (doors) doors->resize((size_t)(nd < cd ? nd : cd));
+        if (found) { found[0] = nr; found[1] = nd; }
         if (shown) *shown = picked;
         return rec;
     }
