@@ -23,6 +23,8 @@ LIB = os.path.join(LIBDIR, "libgridmapslam.so")
 # gms_probe.h is the device header the casts and the beam models share, gms_beams_device.h the ONE workgroup body of the two beam models
 # (each unit supplies its source of occupancy bits), gms_align_device.h the two alignment units' (staging, evaluation, step, store),
 # gms_nearest_device.h the ONE separable nearest-obstacle transform of gms_clearance.hip and gms_skeleton.hip (each unit instantiates its policy),
+# gms_relax_device.h the ONE tile relaxation of gms_reach.hip and gms_rooms.hip (round body, sweep, marks, the host's round loop; each unit
+# instantiates its policy), gms_regions.h the union, the ONE tile labelling of gms_frontier.hip and gms_rooms.hip, the group loop and the reductions,
 # gms_slam_device.h what the device unit, gms_slam_align.hip and gms_slam_beams.hip share of a gms_slam's kernels (the per-particle prologue)
 SOURCES = ["gms_host.hip", "gms_slam_host.hip", "gms_fused_kernels.hip", "gms_query.hip", "gms_cast.hip", "gms_gain.hip", "gms_clearance.hip",
            "gms_reach.hip", "gms_frontier.hip", "gms_scatter.hip", "gms_locate.hip", "gms_modes.hip", "gms_beams.hip", "gms_align.hip",

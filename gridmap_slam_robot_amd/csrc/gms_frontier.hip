@@ -11,12 +11,9 @@
 //                       and south are the words of the rows above and below; free = not the second plane; inflate > 0: and not the
 //                       cost-to-go fields' blocked plane (gms_reach_inflate).  Both planes are read in place (query_plane; a gms_slam's:
 //                       the shown particle's, packed per request, twice).
-//   k_front_tiles       a workgroup per 64 x 64 tile; a tile whose 64 words are all zero leaves at once.  Every frontier cell starts as
-//                       its own root in LDS and is united with its W, N, NW and NE neighbours inside the tile (region_unite); then every
-//                       cell chases to its root and writes the root's GLOBAL linear index into the label field.  Tile-local order is the
-//                       global order restricted to the tile, so that root is the tile's smallest member of the cell's component.
-//   k_front_merge       a lane per cell on the first column / row behind a tile border: united, in the global label field, with its (up
-//                       to) three neighbours across that border -- every pair adjacent across an edge or a corner, both diagonals.
+//   k_front_tiles, k_front_merge   the 8-connected labelling: region_tile_label and region_border_merge of gms_regions.h with the
+//                       diagonal links -- the tile-local union in LDS, then the cells behind a tile border united with their (up to)
+//                       three neighbours across it.
 //   k_front_flatten     a wavefront per plane word: every frontier cell chases to its root and stores it; the ballot of "I am my own
 //                       root" is the root plane's word, its popcount the word's count.
 //   gms_launch_scan     the exclusive scan of those counts: the roots in linear order = the regions in anchor order; the total is the
@@ -29,10 +26,8 @@
 //   gms_launch_scan, k_front_emit   the flags scanned, the kept regions' records stored in order, the first `cap` of them.
 //   k_front_labels      the label rectangle: the label where the plane has a bit, GMS_FRONTIER_NONE elsewhere.
 //
-// The union, the group loop, the wavefront minimum and the scan's look-up are the shared ones of gms_regions.h; the scan itself is the
-// query base's (gms_query.hip).
-//
-// LDS of k_front_tiles: 64 words + 4096 uint32 labels = 16.5 KiB.  A lane owns 16 cells of a row and visits the set bits only.
+// The union, the labelling, the group loop, the wavefront minimum and the scan's look-up are the shared ones of gms_regions.h; the scan
+// itself is the query base's (gms_query.hip).
 #undef GMS_STAMPS
 #include <limits.h>
 #include <stddef.h>
@@ -43,8 +38,8 @@
 
 #include "gms_regions.h"
 
-#define FRT_T 64                         // tile edge in cells = cells of a plane word
-#define FRT_NT 256
+#define FRT_T REGION_T                   // tile edge in cells = cells of a plane word
+#define FRT_NT REGION_NT
 #define FRT_CAP0 4096                    // regions the handle's table holds at first (a multiple of GMS_SCAN)
 #define FRT_NONE 0xffffffffu
 #define FRT_NO_GOAL 0xffffffffffffffffull
@@ -78,59 +73,13 @@ k_front_plane(const uint64_t *__restrict__ occ, const uint64_t *__restrict__ nf,
 // plane: the frontier plane; label [H][W]; grid (ntx, nty)
 __global__ void __launch_bounds__(FRT_NT)
 k_front_tiles(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, uint32_t *__restrict__ label) {
-    __shared__ uint64_t s_word[FRT_T];
-    __shared__ uint32_t s_lab[FRT_T * FRT_T];
-    const int32_t t = (int32_t)threadIdx.x, tx = (int32_t)blockIdx.x, x0 = tx * FRT_T, y0 = (int32_t)blockIdx.y * FRT_T;
-    uint64_t w = 0ull;
-    if (t < FRT_T) {
-        w = y0 + t < H ? plane[(size_t)(y0 + t) * (size_t)wpr64 + (size_t)tx] : 0ull;
-        s_word[t] = w;
-    }
-    if (!__syncthreads_or(w != 0ull)) return;
-    const int32_t r = t >> 2, c0 = (t & 3) * 16;                                // this lane's 16 cells of row r
-    const uint32_t mine = (uint32_t)(s_word[r] >> c0) & 0xffffu;
-    for (uint32_t b = mine; b; b &= b - 1u) {
-        const uint32_t c = (uint32_t)(r * FRT_T + c0 + __builtin_ctz(b));
-        s_lab[c] = c;
-    }
-    __syncthreads();
-    const uint64_t row = s_word[r], up = r > 0 ? s_word[r - 1] : 0ull;
-    for (uint32_t b = mine; b; b &= b - 1u) {
-        const int32_t lx = c0 + __builtin_ctz(b);
-        const uint32_t c = (uint32_t)(r * FRT_T + lx);
-        if (lx > 0 && ((row >> (lx - 1)) & 1ull)) region_unite(s_lab, c, c - 1u);
-        if ((up >> lx) & 1ull) region_unite(s_lab, c, c - FRT_T);                // (N joins NW and NE through its own W link and NE's)
-        else {
-            if (lx > 0 && ((up >> (lx - 1)) & 1ull)) region_unite(s_lab, c, c - FRT_T - 1u);
-            if (lx < FRT_T - 1 && ((up >> (lx + 1)) & 1ull)) region_unite(s_lab, c, c - FRT_T + 1u);
-        }
-    }
-    __syncthreads();
-    for (uint32_t b = mine; b; b &= b - 1u) {
-        const int32_t lx = c0 + __builtin_ctz(b);
-        const uint32_t root = region_find(s_lab, (uint32_t)(r * FRT_T + lx));
-        label[(size_t)(y0 + r) * (size_t)W + (size_t)(x0 + lx)] = (uint32_t)(y0 + (int32_t)(root >> 6)) * (uint32_t)W + (uint32_t)(x0 + (int32_t)(root & 63u));
-    }
+    region_tile_label<true>(plane, wpr64, W, H, label);
 }
 
-// a lane per cell of column 64 k (k = 1 .. ntx - 1; the first (ntx - 1) * H lanes) and of row 64 k (k = 1 .. nty - 1; W lanes each)
+// a lane per cell behind a tile border, united with its (up to) three neighbours across it
 __global__ void __launch_bounds__(FRT_NT)
 k_front_merge(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, int32_t ntx, int32_t nty, uint32_t *label) {
-    const int64_t i = (int64_t)blockIdx.x * FRT_NT + threadIdx.x, nv = (int64_t)(ntx - 1) * H, nh = (int64_t)(nty - 1) * W;
-    if (i >= nv + nh) return;
-    auto bit = [&](int32_t x, int32_t y) -> bool {
-        return x >= 0 && x < W && y >= 0 && y < H && ((plane[(size_t)y * (size_t)wpr64 + (size_t)(x >> 6)] >> (x & 63)) & 1ull) != 0ull;
-    };
-    const bool column = i < nv;
-    int32_t x, y;
-    if (column) { x = ((int32_t)(i / H) + 1) * FRT_T; y = (int32_t)(i % H); }
-    else { const int64_t j = i - nv; y = ((int32_t)(j / W) + 1) * FRT_T; x = (int32_t)(j % W); }
-    if (!bit(x, y)) return;
-    const uint32_t c = (uint32_t)y * (uint32_t)W + (uint32_t)x;
-    for (int32_t d = -1; d <= 1; d++) {
-        const int32_t ox = column ? x - 1 : x + d, oy = column ? y + d : y - 1;
-        if (bit(ox, oy)) region_unite(label, c, (uint32_t)oy * (uint32_t)W + (uint32_t)ox);
-    }
+    region_border_merge<true>(plane, wpr64, W, H, ntx, nty, label);
 }
 
 // a wavefront per word of the plane; roots: the root plane; wcount [words]
@@ -163,13 +112,6 @@ k_front_table_init(gms_frontier *__restrict__ rec, unsigned long long *__restric
         rec[i] = gms_frontier{0, 0, 0, GMS_REACH_FAR, INT_MAX, INT_MAX, -1, -1, -1, -1, 0, 0};
         goal[i] = FRT_NO_GOAL;
     }
-}
-
-// the sum of the positions of mask's set bits
-__device__ __forceinline__ uint32_t front_bit_sum(uint64_t mask) {
-    return (uint32_t)__popcll(mask & 0xaaaaaaaaaaaaaaaaull) + 2u * (uint32_t)__popcll(mask & 0xccccccccccccccccull) +
-           4u * (uint32_t)__popcll(mask & 0xf0f0f0f0f0f0f0f0ull) + 8u * (uint32_t)__popcll(mask & 0xff00ff00ff00ff00ull) +
-           16u * (uint32_t)__popcll(mask & 0xffff0000ffff0000ull) + 32u * (uint32_t)__popcll(mask & 0xffffffff00000000ull);
 }
 
 // a wavefront per word of the plane.  roots / wscan / wblocks: the root plane and the scan of its counts; cost (may be NULL) [H][W];
@@ -208,7 +150,7 @@ k_front_reduce(const uint64_t *__restrict__ plane, const uint64_t *__restrict__ 
         atomicMax(&q->max_x, xw + 63 - __builtin_clzll(grp));
         atomicMin(&q->min_y, y);
         atomicMax(&q->max_y, y);
-        atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + front_bit_sum(grp)));
+        atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + region_bit_sum(grp)));
         atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_y), (unsigned long long)((int64_t)n * y));
         if (best != FRT_NO_GOAL) atomicMin(goal + R, (unsigned long long)best);
     });

@@ -11,24 +11,17 @@
 //   the two blocked planes   gms_reach_inflate at R = core into the handle's scratch plane; k_rooms_core turns it into the CORE PLANE (a
 //                       bit per core cell, the padding zero) in a plane of this unit's own, so that the scratch plane is free for
 //                       gms_reach_inflate at R = inflate (inflate == 0: the obstacle plane itself, read in place).
-//   k_rooms_tiles, k_rooms_merge, k_rooms_flatten   the frontiers' labelling with 4-connectivity: the tile-local union in LDS (W and N
-//                       links), region_unite across the tile EDGES only, the chase to the root; the flatten also counts every core's
-//                       cells at its root (wave_each_key, one atomic per group) -- in the working field, which nobody uses yet.
+//   k_rooms_tiles, k_rooms_merge, k_rooms_flatten   the 4-connected labelling: region_tile_label and region_border_merge of gms_regions.h
+//                       without the diagonal links, then the chase to the root; the flatten also counts every core's cells at its root
+//                       (wave_each_key, one atomic per group) -- in the working field, which nobody uses yet.
 //   k_rooms_keep        the plane of the roots with count >= min_core and its word counts; gms_launch_scan ranks them in anchor order;
 //                       the total, the number of rooms, is read back once (the tables' size, the 0xFFFF check).
 //   k_rooms_seed        every cell of a room gets the working key 0 << 16 | rank, every other cell 0xFFFFFFFF; the root writes its
 //                       record's anchor and core_count.  A room cell with one of its eight neighbours on the map outside the core
 //                       plane is on the RIM; the tile of a rim cell and the tiles of its eight neighbours are marked active (a seed
-//                       never changes, so it must mark by itself: k_reach_seeds' rule), one lane per wavefront from the rim's ballot.
-//   k_rooms_round       ONE ROUND, k_reach_round's scheme on the uint32 field cost << 16 | rank, whose numeric order is the
-//                       lexicographic order of (cost, rank): a relaxation is min(cur, neighbour + (step << 16)), and one aligned
-//                       32-bit store publishes cost and label together.  One wavefront per 64 x 64 tile; an active tile loads its
-//                       cells and a one-cell halo into LDS, relaxes to ITS fixpoint by four directional sweeps (the value from the
-//                       west / east in a register, the diagonal ones by the DPP wavefront shifts), writes back what changed and marks
-//                       the neighbours across every edge or corner whose cell changed for the NEXT round.  No workgroup waits on
-//                       another; a halo read old or new is an upper bound in the same order, and the neighbour's mark brings the tile
-//                       back: k_reach_round's proof, word for word.  The cap test is made on the neighbour's key BEFORE the add
-//                       (key < (max_cost - step + 1) << 16), so no candidate is ever formed that could wrap.
+//                       never changes, so it must mark by itself), one lane per wavefront from the rim's ballot.
+//   k_rooms_round       ONE ROUND of the tile relaxation on the uint32 field cost << 16 | rank: relax_round<RoomKeys> of
+//                       gms_relax_device.h, which holds the scheme, its proof, the sweeps, the cap test and the LDS banks' argument.
 //   k_rooms_out         labels and depth of the rectangle through the rank -> anchor table.
 //   k_rooms_records     count, box, sums and max_depth per room by integer atomics, the lanes that share a room combined first.
 //   k_rooms_contacts    a lane per cell looks east and south, so every contact is seen once; the pair's key rank_a << 16 | rank_b
@@ -41,12 +34,6 @@
 //                       start plus the number of smaller keys within the run -- the sum of the squared run lengths in all, not the
 //                       square of the table.  It writes its record there and adds one to `doors` of both rooms.  k_rooms_emit
 //                       copies the first cap_rooms room records out.
-//
-// LDS of k_rooms_round: 66 rows of 67 dwords = 17688 bytes.  ds_read_b32 / ds_write_b32 bank by (address / 4) mod 32 within each
-// 32-lane half.  The east / west sweeps have a lane per row: lane l touches dword 67 l + c, bank (3 l + c) mod 32, and 3 is odd, so the
-// 32 lanes of a half hit 32 different banks.  An even pitch -- the 66 dwords the tile's width suggests, or twice the uint16 kernel's
-// 33 -- would put lanes l and l + 16 of a half on one bank (16 * 66 = 33 * 32), two-way on every access of the sweep.  The south /
-// north sweeps and the tile's load and store have a lane per column: 64 consecutive dwords, conflict-free at any pitch.
 #undef GMS_STAMPS
 #include <limits.h>
 #include <stddef.h>
@@ -57,19 +44,16 @@
 #include <algorithm>
 
 #include "gms_regions.h"
+#include "gms_relax_device.h"
 
-#define RMS_T 64                         // tile edge in cells = lanes of the round's workgroup = cells of a plane word
-#define RMS_ROWS (RMS_T + 2)             // the tile and its halo
-#define RMS_P 67                         // LDS row pitch in dwords: odd (the header comment)
+#define RMS_T RLX_T                      // tile edge in cells = cells of a plane word
 #define RMS_NT 256
-#define RMS_NONE 0xffffffffu
-#define RMS_CTL_WORDS 16                 // d_rooms_ctl: [0..1] tile runs, [2..5] active counts, [6] rooms, [7] door entries, [8] door table overflow; the flags behind
-#define RMS_BATCH_DEFAULT 8              // rounds per read-back (GMS_ROOMS_BATCH)
+#define RMS_NONE RoomKeys::FAR
+#define RMS_CTL_WORDS RoomKeys::CTL_WORDS                                       // d_rooms_ctl: [0..1] tile runs, [2..5] active counts, [6] rooms, [7] door entries, [8] door table overflow; the flags behind
 #define RMS_DOOR_CAP0 64                 // entries the handle's door table holds at first (a power of two; it is kept at most half full)
-#define RMS_AXIS ((uint32_t)GMS_REACH_AXIS << 16)
-#define RMS_DIAG ((uint32_t)GMS_REACH_DIAG << 16)
 
 static_assert(GMS_ROOM_NONE == RMS_NONE && GMS_ROOMS_MAX == 0xFFFF, "the header's constants are the kernels'");
+static_assert(RMS_T == REGION_T && RMS_NT == REGION_NT, "the labelling's tile and workgroup are the relaxation's tile and this unit's workgroup");
 static_assert(sizeof(gms_rooms) == 48 && sizeof(gms_room) == 56 && offsetof(gms_room, core_count) == 8 && offsetof(gms_room, min_x) == 16 &&
               offsetof(gms_room, max_depth) == 32 && offsetof(gms_room, doors) == 36 && offsetof(gms_room, sum_x) == 40, "the header fixes the room record's offsets");
 static_assert(sizeof(gms_door) == 48 && offsetof(gms_door, count) == 8 && offsetof(gms_door, min_x) == 12 && offsetof(gms_door, sum_x2) == 32,
@@ -80,20 +64,6 @@ struct RoomsDoorAcc {
     int32_t count, min_x, min_y, max_x, max_y, pad;
     unsigned long long sum_x2, sum_y2;
 };
-
-__device__ __forceinline__ uint32_t rooms_from_below(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false); }   // wave_shr:1
-__device__ __forceinline__ uint32_t rooms_from_above(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130, 0xf, 0xf, false); }   // wave_shl:1
-
-// the sum of the positions of mask's set bits
-__device__ __forceinline__ uint32_t rooms_bit_sum(uint64_t mask) {
-    return (uint32_t)__popcll(mask & 0xaaaaaaaaaaaaaaaaull) + 2u * (uint32_t)__popcll(mask & 0xccccccccccccccccull) +
-           4u * (uint32_t)__popcll(mask & 0xf0f0f0f0f0f0f0f0ull) + 8u * (uint32_t)__popcll(mask & 0xff00ff00ff00ff00ull) +
-           16u * (uint32_t)__popcll(mask & 0xffff0000ffff0000ull) + 32u * (uint32_t)__popcll(mask & 0xffffffff00000000ull);
-}
-
-__device__ __forceinline__ void rooms_mark(uint32_t *flags, uint32_t *count, int32_t tile) {
-    if (atomicExch(&flags[tile], 1u) == 0u) atomicAdd(count, 1u);
-}
 
 // blocked: ONE map's blocked plane at inflation `core`, H rows of wpr64 words; core: the core plane; field: [cells] zeroed (the cores'
 // counts); ctl zeroed
@@ -113,50 +83,13 @@ k_rooms_core(const uint64_t *__restrict__ blocked, int32_t W, int32_t H, int32_t
 // plane: the core plane; label [H][W]; grid (ntx, nty)
 __global__ void __launch_bounds__(RMS_NT)
 k_rooms_tiles(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, uint32_t *__restrict__ label) {
-    __shared__ uint64_t s_word[RMS_T];
-    __shared__ uint32_t s_lab[RMS_T * RMS_T];
-    const int32_t t = (int32_t)threadIdx.x, tx = (int32_t)blockIdx.x, x0 = tx * RMS_T, y0 = (int32_t)blockIdx.y * RMS_T;
-    uint64_t w = 0ull;
-    if (t < RMS_T) {
-        w = y0 + t < H ? plane[(size_t)(y0 + t) * (size_t)wpr64 + (size_t)tx] : 0ull;
-        s_word[t] = w;
-    }
-    if (!__syncthreads_or(w != 0ull)) return;
-    const int32_t r = t >> 2, c0 = (t & 3) * 16;                                // this lane's 16 cells of row r
-    const uint32_t mine = (uint32_t)(s_word[r] >> c0) & 0xffffu;
-    for (uint32_t b = mine; b; b &= b - 1u) {
-        const uint32_t c = (uint32_t)(r * RMS_T + c0 + __builtin_ctz(b));
-        s_lab[c] = c;
-    }
-    __syncthreads();
-    const uint64_t row = s_word[r], up = r > 0 ? s_word[r - 1] : 0ull;
-    for (uint32_t b = mine; b; b &= b - 1u) {                                   // 4-connectivity: the W and the N link, no diagonal ones
-        const int32_t lx = c0 + __builtin_ctz(b);
-        const uint32_t c = (uint32_t)(r * RMS_T + lx);
-        if (lx > 0 && ((row >> (lx - 1)) & 1ull)) region_unite(s_lab, c, c - 1u);
-        if ((up >> lx) & 1ull) region_unite(s_lab, c, c - RMS_T);
-    }
-    __syncthreads();
-    for (uint32_t b = mine; b; b &= b - 1u) {
-        const int32_t lx = c0 + __builtin_ctz(b);
-        const uint32_t root = region_find(s_lab, (uint32_t)(r * RMS_T + lx));
-        label[(size_t)(y0 + r) * (size_t)W + (size_t)(x0 + lx)] = (uint32_t)(y0 + (int32_t)(root >> 6)) * (uint32_t)W + (uint32_t)(x0 + (int32_t)(root & 63u));
-    }
+    region_tile_label<false>(plane, wpr64, W, H, label);
 }
 
-// a lane per cell of column 64 k (k = 1 .. ntx - 1; the first (ntx - 1) * H lanes) and of row 64 k (k = 1 .. nty - 1; W lanes each):
-// united with the ONE cell across the edge -- 4-connectivity has no link across a corner
+// a lane per cell behind a tile border, united with the ONE cell across the edge -- 4-connectivity has no link across a corner
 __global__ void __launch_bounds__(RMS_NT)
 k_rooms_merge(const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, int32_t ntx, int32_t nty, uint32_t *label) {
-    const int64_t i = (int64_t)blockIdx.x * RMS_NT + threadIdx.x, nv = (int64_t)(ntx - 1) * H, nh = (int64_t)(nty - 1) * W;
-    if (i >= nv + nh) return;
-    auto bit = [&](int32_t x, int32_t y) -> bool { return ((plane[(size_t)y * (size_t)wpr64 + (size_t)(x >> 6)] >> (x & 63)) & 1ull) != 0ull; };
-    const bool column = i < nv;
-    int32_t x, y;
-    if (column) { x = ((int32_t)(i / H) + 1) * RMS_T; y = (int32_t)(i % H); }
-    else { const int64_t j = i - nv; y = ((int32_t)(j / W) + 1) * RMS_T; x = (int32_t)(j % W); }
-    const int32_t ox = column ? x - 1 : x, oy = column ? y : y - 1;             // (x, y >= 64 on its axis: the other cell is on the map)
-    if (bit(x, y) && bit(ox, oy)) region_unite(label, (uint32_t)y * (uint32_t)W + (uint32_t)x, (uint32_t)oy * (uint32_t)W + (uint32_t)ox);
+    region_border_merge<false>(plane, wpr64, W, H, ntx, nty, label);
 }
 
 // a wavefront per word of the core plane: the chase to the root, and every core's cells counted at its root (count [cells], zeroed)
@@ -255,53 +188,15 @@ k_rooms_seed(const uint64_t *__restrict__ core, const uint64_t *__restrict__ kep
     uint32_t *flags = ctl + RMS_CTL_WORDS, *cnt = ctl + 2;                      // round 0's flags and count
     const int32_t ty = y >> 6, tile = ty * ntx + wx;
     const bool w = (rim & 1ull) && wx > 0, e = (rim >> 63) && wx + 1 < ntx, n = (y & 63) == 0 && ty > 0, s = (y & 63) == 63 && ty + 1 < nty;
-    rooms_mark(flags, cnt, tile);
-    if (w) rooms_mark(flags, cnt, tile - 1);
-    if (e) rooms_mark(flags, cnt, tile + 1);
-    if (n) rooms_mark(flags, cnt, tile - ntx);
-    if (s) rooms_mark(flags, cnt, tile + ntx);
-    if (n && w) rooms_mark(flags, cnt, tile - ntx - 1);
-    if (n && e) rooms_mark(flags, cnt, tile - ntx + 1);
-    if (s && w) rooms_mark(flags, cnt, tile + ntx - 1);
-    if (s && e) rooms_mark(flags, cnt, tile + ntx + 1);
-}
-
-// One directional sweep of the tile s (66 x 66 at pitch RMS_P, cell (t, l) at s[(l + 1) * SL + (t + 1) * ST]): lane l owns line l and
-// walks t = 0 .. 63 (DIR > 0) or 63 .. 0.  me / lo / hi: the blocked bits (bit t) of lines l, l - 1 and l + 1; start_blocked: the halo
-// cell the walk starts from.  lim_axis / lim_diag: a neighbour's key takes the step iff it is below.  true: the lane lowered a cell
-template <int SL, int ST, int DIR>
-__device__ __forceinline__ bool rooms_sweep(uint32_t *s, int32_t lane, uint64_t me, uint64_t lo, uint64_t hi, bool start_blocked, uint32_t lim_axis,
-                                            uint32_t lim_diag) {
-    constexpr int T0 = DIR > 0 ? 0 : RMS_T - 1;
-    uint32_t *cell = s + (lane + 1) * SL + (T0 + 1) * ST;
-    // the halo lines beside lane 0 and lane 63, entry t in lane t; the corner the walk starts beside, everywhere
-    const uint32_t line_lo = s[0 * SL + (lane + 1) * ST], line_hi = s[(RMS_ROWS - 1) * SL + (lane + 1) * ST];
-    uint32_t halo_lo = s[0 * SL + (T0 - DIR + 1) * ST], halo_hi = s[(RMS_ROWS - 1) * SL + (T0 - DIR + 1) * ST];
-    uint32_t prev = cell[-DIR * ST];
-    bool prev_free = !start_blocked, changed = false;
-    uint32_t cur = *cell;
-#pragma unroll 4
-    for (int32_t i = 0; i < RMS_T; i++) {
-        const int32_t t = T0 + DIR * i;
-        const uint32_t next = i + 1 < RMS_T ? cell[DIR * ST] : 0u;              // (nobody writes it before this lane does)
-        uint32_t from_lo = rooms_from_below(prev), from_hi = rooms_from_above(prev);
-        if (lane == 0) from_lo = halo_lo;
-        if (lane == RMS_T - 1) from_hi = halo_hi;
-        const bool me_b = (me >> t) & 1ull, lo_b = (lo >> t) & 1ull, hi_b = (hi >> t) & 1ull;
-        uint32_t best = cur;
-        if (prev < lim_axis) best = min(best, prev + RMS_AXIS);                 // (the cap test ahead of the add: nothing wraps)
-        if (prev_free && !lo_b && from_lo < lim_diag) best = min(best, from_lo + RMS_DIAG);       // the two cells the step squeezes between
-        if (prev_free && !hi_b && from_hi < lim_diag) best = min(best, from_hi + RMS_DIAG);
-        if (me_b) best = RMS_NONE;
-        if (best != cur) { *cell = best; changed = true; }
-        prev = best;
-        prev_free = !me_b;
-        halo_lo = (uint32_t)__builtin_amdgcn_readlane((int)line_lo, t);
-        halo_hi = (uint32_t)__builtin_amdgcn_readlane((int)line_hi, t);
-        cur = next;
-        cell += DIR * ST;
-    }
-    return changed;
+    relax_mark(flags, cnt, tile);
+    if (w) relax_mark(flags, cnt, tile - 1);
+    if (e) relax_mark(flags, cnt, tile + 1);
+    if (n) relax_mark(flags, cnt, tile - ntx);
+    if (s) relax_mark(flags, cnt, tile + ntx);
+    if (n && w) relax_mark(flags, cnt, tile - ntx - 1);
+    if (n && e) relax_mark(flags, cnt, tile - ntx + 1);
+    if (s && w) relax_mark(flags, cnt, tile + ntx - 1);
+    if (s && e) relax_mark(flags, cnt, tile + ntx + 1);
 }
 
 // field [H][W] of keys; plane: ONE map's blocked plane at inflation `inflate`, H rows of wpr64 words; grid (ntx, nty), a wavefront per
@@ -309,76 +204,8 @@ __device__ __forceinline__ bool rooms_sweep(uint32_t *s, int32_t lane, uint64_t 
 __global__ void __launch_bounds__(RMS_T)
 k_rooms_round(uint32_t *field, const uint64_t *__restrict__ plane, int32_t wpr64, int32_t W, int32_t H, uint32_t *ctl, int32_t round, uint32_t lim_axis,
               uint32_t lim_diag) {
-    __shared__ uint32_t s[RMS_ROWS * RMS_P];
-    const int32_t lane = (int32_t)threadIdx.x, tx = (int32_t)blockIdx.x, ty = (int32_t)blockIdx.y, ntx = (int32_t)gridDim.x, nty = (int32_t)gridDim.y;
-    const int32_t tile = ty * ntx + tx, ntiles = ntx * nty;
-    uint32_t *count = ctl + 2, *flags_cur = ctl + RMS_CTL_WORDS + (size_t)(round & 1) * (size_t)ntiles;
-    uint32_t *flags_next = ctl + RMS_CTL_WORDS + (size_t)((round + 1) & 1) * (size_t)ntiles;
-    if (tile == 0 && lane == 0) count[(round + 2) & 3] = 0u;                   // (this round counts into slot round + 1; round - 1 counted into this round's)
-    if (flags_cur[tile] == 0u) return;                                          // (uniform)
-    __syncthreads();
-    if (lane == 0) {
-        flags_cur[tile] = 0u;                                                   // (nobody else touches this round's flag of this tile)
-        atomicAdd(reinterpret_cast<unsigned long long *>(ctl), 1ull);
-    }
-    const int32_t x0 = tx * RMS_T, y0 = ty * RMS_T, x = x0 + lane;
-    for (int32_t r = 0; r < RMS_ROWS; r++) {                                    // the tile and its halo; what lies off the map has no room
-        const int32_t y = y0 + r - 1;
-        const bool row_in = y >= 0 && y < H;
-        const uint32_t *src = field + (size_t)(row_in ? y : 0) * (size_t)W;
-        s[r * RMS_P + lane + 1] = row_in && x < W ? __atomic_load_n(src + x, __ATOMIC_RELAXED) : RMS_NONE;
-        if (lane < 2) {
-            const int32_t xe = lane == 0 ? x0 - 1 : x0 + RMS_T;
-            s[r * RMS_P + (lane == 0 ? 0 : RMS_ROWS - 1)] = row_in && xe >= 0 && xe < W ? __atomic_load_n(src + xe, __ATOMIC_RELAXED) : RMS_NONE;
-        }
-    }
-    // the blocked bits: a tile's row is one word of the plane; what lies off the map is blocked
-    const uint64_t ragged = W - x0 < RMS_T ? ~0ull << (W - x0) : 0ull;
-    auto row_word = [&](int32_t y) -> uint64_t { return y >= 0 && y < H ? (plane[(size_t)y * (size_t)wpr64 + (size_t)tx] | ragged) : ~0ull; };
-    auto left_bit = [&](int32_t y) -> bool { return y >= 0 && y < H && tx > 0 ? (plane[(size_t)y * (size_t)wpr64 + (size_t)(tx - 1)] >> 63) != 0ull : true; };
-    auto right_bit = [&](int32_t y) -> bool { return y >= 0 && y < H && x0 + RMS_T < W ? (plane[(size_t)y * (size_t)wpr64 + (size_t)(tx + 1)] & 1ull) != 0ull : true; };
-    const uint64_t row_me = row_word(y0 + lane), row_lo = row_word(y0 + lane - 1), row_hi = row_word(y0 + lane + 1);
-    const bool row_left = left_bit(y0 + lane), row_right = right_bit(y0 + lane);
-    uint64_t col_me = 0ull;                                                     // lane = column: bit y of it
-    for (int32_t r = 0; r < RMS_T; r++) col_me |= ((row_word(y0 + r) >> lane) & 1ull) << r;
-    uint64_t col_lo = (uint64_t)__shfl_up((long long)col_me, 1), col_hi = (uint64_t)__shfl_down((long long)col_me, 1);
-    const uint64_t halo_left = __ballot(row_left), halo_right = __ballot(row_right);
-    if (lane == 0) col_lo = halo_left;
-    if (lane == RMS_T - 1) col_hi = halo_right;
-    const bool col_top = (row_word(y0 - 1) >> lane) & 1ull, col_bottom = (row_word(y0 + RMS_T) >> lane) & 1ull;
-    __syncthreads();
-    for (int32_t pass = 0; pass < RMS_T * RMS_T; pass++) {                      // (the vote ends it; the bound is the tile's cells)
-        bool changed = rooms_sweep<RMS_P, 1, 1>(s, lane, row_me, row_lo, row_hi, row_left, lim_axis, lim_diag);
-        changed |= rooms_sweep<RMS_P, 1, -1>(s, lane, row_me, row_lo, row_hi, row_right, lim_axis, lim_diag);
-        __syncthreads();
-        changed |= rooms_sweep<1, RMS_P, 1>(s, lane, col_me, col_lo, col_hi, col_top, lim_axis, lim_diag);
-        changed |= rooms_sweep<1, RMS_P, -1>(s, lane, col_me, col_lo, col_hi, col_bottom, lim_axis, lim_diag);
-        __syncthreads();
-        if (!__any(changed)) break;
-    }
-    uint32_t moved = 0u;                                                        // bit 0: a cell of row 0 changed, 1: of row 63, 2: of column 0, 3: of column 63
-    const int32_t rows = min(RMS_T, H - y0);
-    if (x < W)
-        for (int32_t r = 0; r < rows; r++) {
-            uint32_t *dst = field + (size_t)(y0 + r) * (size_t)W + (size_t)x;
-            const uint32_t v = s[(r + 1) * RMS_P + lane + 1];
-            if (v != *dst) {
-                __atomic_store_n(dst, v, __ATOMIC_RELAXED);                     // (one aligned dword: cost and rank are published together)
-                moved |= (r == 0 ? 1u : 0u) | (r == RMS_T - 1 ? 2u : 0u) | (lane == 0 ? 4u : 0u) | (lane == RMS_T - 1 ? 8u : 0u);
-            }
-        }
-    const uint64_t top = __ballot(moved & 1u), bottom = __ballot(moved & 2u), left = __ballot(moved & 4u), right = __ballot(moved & 8u);
-    if (lane != 0) return;
-    uint32_t *cnt = count + ((round + 1) & 3);
-    const bool n = ty > 0, so = ty + 1 < nty, w = tx > 0, e = tx + 1 < ntx;
-    if (top && n) rooms_mark(flags_next, cnt, tile - ntx);
-    if (bottom && so) rooms_mark(flags_next, cnt, tile + ntx);
-    if (left && w) rooms_mark(flags_next, cnt, tile - 1);
-    if (right && e) rooms_mark(flags_next, cnt, tile + 1);
-    if ((top & 1ull) && n && w) rooms_mark(flags_next, cnt, tile - ntx - 1);                      // the corner cells: the tile across the corner
-    if ((top >> 63) && n && e) rooms_mark(flags_next, cnt, tile - ntx + 1);
-    if ((bottom & 1ull) && so && w) rooms_mark(flags_next, cnt, tile + ntx - 1);
-    if ((bottom >> 63) && so && e) rooms_mark(flags_next, cnt, tile + ntx + 1);
+    __shared__ uint32_t s[RLX_ROWS * RoomKeys::PITCH];
+    relax_round<RoomKeys>(s, field, plane, wpr64, W, H, ctl, round, RoomKeys::Params{lim_axis, lim_diag});
 }
 
 // labels, depth (either may be NULL) [h][w]
@@ -414,7 +241,7 @@ k_rooms_records(const uint32_t *__restrict__ field, int32_t wpr64, int32_t W, in
         atomicMin(&q->min_y, y);
         atomicMax(&q->max_y, y);
         atomicMax(&q->max_depth, deepest);
-        atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + rooms_bit_sum(grp)));
+        atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_x), (unsigned long long)((int64_t)n * xw + region_bit_sum(grp)));
         atomicAdd(reinterpret_cast<unsigned long long *>(&q->sum_y), (unsigned long long)((int64_t)n * y));
     });
 }
@@ -469,7 +296,7 @@ k_rooms_contacts(const uint32_t *__restrict__ field, int32_t wpr64, int32_t W, i
             const int32_t e = rooms_door_entry(keys, mask, K, ctl);
             if (e < 0) return;
             const int32_t n = __popcll(grp), dx = dir == 0 ? 1 : 0, dy = 1 - dx;
-            const int64_t sx = (int64_t)n * xw + rooms_bit_sum(grp);            // the sum of the group's px
+            const int64_t sx = (int64_t)n * xw + region_bit_sum(grp);           // the sum of the group's px
             RoomsDoorAcc *q = acc + e;
             atomicAdd(&q->count, n);
             atomicMin(&q->min_x, xw + __builtin_ctzll(grp));
@@ -532,12 +359,6 @@ k_rooms_emit(const gms_room *__restrict__ rec, int32_t n, gms_room *__restrict__
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-static int32_t rooms_batch() {
-    const char *e = getenv("GMS_ROOMS_BATCH");
-    const int32_t b = e ? atoi(e) : RMS_BATCH_DEFAULT;
-    return std::min(64, std::max(1, b));
-}
-
 static inline size_t rooms_door_bytes(size_t cap) { return cap * (2 * sizeof(uint32_t) + sizeof(RoomsDoorAcc)); }
 static inline size_t rooms_table_bytes(size_t cap) { return cap * (sizeof(gms_room) + 4 * sizeof(uint32_t)) + (cap / GMS_SCAN + 2) * sizeof(uint32_t); }
 
@@ -579,11 +400,7 @@ static int rooms_buffers(gms_map *m) {
     return rc;
 }
 
-static int rooms_read_ctl(gms_map *m) {
-    HIPCHK(hipMemcpyAsync(m->h_rooms_ctl, m->d_rooms_ctl, RMS_CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return GMS_OK;
-}
+static int rooms_read_ctl(gms_map *m) { return relax_read_ctl(m->stream, m->d_rooms_ctl, m->h_rooms_ctl, RMS_CTL_WORDS); }
 
 // Rooms and doors of ONE map's obstacle plane (already of logData as it stands) into the caller's device buffers; the handle's buffers
 // exist.  Leaves the numbers of rooms and doors in *n_rooms and *n_doors.
@@ -632,27 +449,17 @@ static int rooms_run(gms_map *m, const uint32_t *d_obstacles, const gms_rooms *q
     if (R > 0) hipLaunchKernelGGL(k_rooms_table_init, dim3(gms_grid(R, RMS_NT, 1024)), dim3(RMS_NT), 0, st, rec, dcnt, dsize, dfill, R);
     hipLaunchKernelGGL(k_rooms_seed, dim3(word_waves), dim3(RMS_NT), 0, st, core, kept, wscan, wblocks, wpr64, W, H, label, field, ntx, nty, ctl, rec, anchor, R);
     HIPCHK(hipGetLastError());
-    // Rounds in batches, the active count read back once per batch: k_reach_round's bound.  After round k every cell whose best path
-    // crosses fewer than k tile borders is final, a path within the cap has at most max_cost / 5 steps, and one more round sees nothing move.
-    const int32_t bound = q->max_cost / GMS_REACH_AXIS + 2, batch = rooms_batch();
     const uint32_t lim_axis = q->max_cost >= GMS_REACH_AXIS ? (uint32_t)(q->max_cost - GMS_REACH_AXIS + 1) << 16 : 0u;
     const uint32_t lim_diag = q->max_cost >= GMS_REACH_DIAG ? (uint32_t)(q->max_cost - GMS_REACH_DIAG + 1) << 16 : 0u;
-    int32_t rounds = 0;
     m->rooms_rounds = 0;
     m->rooms_tile_runs = 0;
     m->rooms_door_rebuilds = 0;
-    while (R > 0) {
-        const int32_t now = std::min(batch, bound - rounds);
-        for (int32_t i = 0; i < now; i++, rounds++)
-            hipLaunchKernelGGL(k_rooms_round, dim3((unsigned)ntx, (unsigned)nty), dim3(RMS_T), 0, st, field, plane, wpr64, W, H, ctl, rounds, lim_axis, lim_diag);
-        HIPCHK(hipGetLastError());
-        if ((rc = rooms_read_ctl(m)) != 0) return rc;
-        m->rooms_rounds = rounds;
-        m->rooms_tile_runs = (int64_t)(((uint64_t)m->h_rooms_ctl[1] << 32) | m->h_rooms_ctl[0]);
-        if (m->h_rooms_ctl[2 + (rounds & 3)] == 0u) break;                      // what the last round marked for the next one
-        if (rounds >= bound)
-            return gms_fail(GMS_ERR_INTERNAL, "gms_rooms: tiles still active after %d rounds, the bound for max_cost = %d", rounds, q->max_cost);
-    }
+    const auto round = [&](int32_t k) {
+        hipLaunchKernelGGL(k_rooms_round, dim3((unsigned)ntx, (unsigned)nty), dim3(RMS_T), 0, st, field, plane, wpr64, W, H, ctl, k, lim_axis, lim_diag);
+    };
+    if (R > 0 && (rc = relax_rounds(st, ctl, m->h_rooms_ctl, RMS_CTL_WORDS, q->max_cost, relax_batch("GMS_ROOMS_BATCH"), round, "gms_rooms", &m->rooms_rounds,
+                                    &m->rooms_tile_runs)) != 0)
+        return rc;
     stages.end(2);
     if (d_labels || d_depth) {
         const int64_t n = (int64_t)q->w * q->h;

@@ -1,6 +1,6 @@
-"""The map queries on maps at the plane-word and tile edges: clearance fields, cost-to-go fields, frontier regions, view gain and the
-beam sensor model of the shared maps, each against its plain expectation (tests/_clearance_expect.py, _reach_expect.py,
-_frontier_expect.py, _gain_expect.py, _beams_expect.py), on thirteen shapes -- the smallest on each side of each edge of the units'
+"""The map queries on maps at the plane-word and tile edges: clearance fields, cost-to-go fields, rooms and doors, frontier regions, view
+gain and the beam sensor model of the shared maps, each against its plain expectation (tests/_clearance_expect.py, _reach_expect.py,
+_rooms_expect.py, _frontier_expect.py, _gain_expect.py, _beams_expect.py), on thirteen shapes -- the smallest on each side of each edge of the units'
 arithmetic: one cell, one 32-bit plane word, one 64-bit plane word / one 64 x 64 tile, two tiles, and one cell past each.  The other
 device tests of these units all run on 200 x 136 cells.
 
@@ -19,6 +19,8 @@ import _clearance_expect as xe
 import _frontier_expect as fx
 import _gain_expect as gx
 import _reach_expect as rx
+import _rooms_expect as ro
+import test_gpu_frontiers as tf
 from gridmap_slam_robot_amd import GAIN_DTYPE, GridMap, ParticleFilter, beam_model_factors, probe_fan
 from gridmap_slam_robot_amd._lib import BEAM_DTYPE
 from oracle import oracle as orc
@@ -313,6 +315,103 @@ def test_cost_to_go_over_the_corner_where_four_tiles_meet(flip_x, flip_y, monkey
         for not_free in (True, False):
             _same(m.reach(seeds, not_free=not_free), want, f"flip_x = {flip_x}, flip_y = {flip_y}, GMS_REACH_BATCH = {batch}, not_free = {not_free}")
         m.close()
+
+
+# ---- 2b: rooms and doors, the same relaxation on (cost, rank) keys and the 4-connected labelling ------------------------------------------
+ROOMS = dict(core=2, inflate=0, not_free=False, min_core=1)                 # a 5 x 5 free box in walls has ONE core cell, its centre
+
+
+def _rooms_same(m, log, where, **kw):
+    want = ro.expect(log, **kw)
+    m.upload_log(log)
+    ro.same(m.rooms(labels=True, depth=True, cap_rooms=CAP, cap_doors=CAP, **kw), want, where)
+    return want
+
+
+@functools.lru_cache(maxsize=None)
+def two_rooms_of(shape):
+    """walls with two free boxes, (2, 2) .. (12, 12) in the first tile and the 9 x 9 box in the far corner, which on 65 x 64 and 64 x 65
+    reaches into the ragged column / row, joined by a one-cell corridor along y = 7 and x = W - 5"""
+    W, H = shape
+    log = ro.walls(W, H)
+    ro.carve(log, 2, 2, 12, 12)
+    ro.carve(log, W - 9, H - 9, W - 1, H - 1)
+    ro.carve(log, 13, 7, W - 5, 7)
+    ro.carve(log, W - 5, 7, W - 5, H - 10)
+    log.flags.writeable = False
+    return log
+
+
+@pytest.mark.parametrize("shape", [(65, 64), (64, 65), (128, 128)], ids=str)
+def test_rooms_one_round_per_read_back(shape, monkeypatch):
+    monkeypatch.setenv("GMS_ROOMS_BATCH", "1")                                 # rounds launched = rounds needed
+    W, H = shape
+    m = _map(shape)
+    want = _rooms_same(m, two_rooms_of(shape), f"{shape}, two rooms", **ROOMS)
+    assert want["n_rooms"] == 2 and want["n_doors"] == 1 and want["labels"][H - 1, W - 1] == want["doors"]["b"][0], "the far room holds the last cell"
+    st = m.rooms_stats()
+    assert st["rounds"] >= 2, f"the growth crossed a tile border: {st}"
+    m.close()
+
+
+@functools.lru_cache(maxsize=None)
+def rooms_corner_case(flip_x, flip_y):
+    """corner_case's corridors in a 130 x 130 map of walls, a 5 x 5 free box around each of its three seeds: three rooms whose cores
+    are the seed and the cell beside it towards the corridor, so that the depth is corner_case's cost-to-go less one step.  A = (63, 64)
+    settles two rounds after B and C have, B and C keep their smaller keys (depth 225 against 225, then 230 from A at 220) and hand
+    nothing on, and D's key (227, the rank of A's room; 230 from B or C) arrives over the corner where the four tiles meet alone"""
+    small, seeds, cells = corner_case(flip_x, flip_y)
+    log = ro.walls(130, 130)
+    log[:128, :128] = small
+    for x, y in seeds:
+        ro.carve(log, x - 2, y - 2, x + 2, y + 2)
+    if flip_y:
+        # A's room now lies above the other two and would rank first: a tie at B or C (225 from either side) would go to it, B and C
+        # would change and hand D on themselves.  Five-cell-wide arms, away from the corridors, carry the other two rooms' cores up to
+        # row 2, so that A's room ranks last as it does without the flip.
+        (x1, y1), (x3, y3) = seeds[0], seeds[1]
+        xa = 7 if flip_x else 120                                              # a free column beyond the third seed's box
+        ro.carve(log, min(x1, xa) - 2, y1 - 2, max(x1, xa) + 2, y1 + 2)
+        ro.carve(log, xa - 2, 0, xa + 2, y1 + 2)
+        ro.carve(log, x3 - 2, 0, x3 + 2, y3 + 2)
+    log.flags.writeable = False
+    return log, seeds, cells
+
+
+@pytest.mark.parametrize("flip_x,flip_y", [(False, False), (True, False), (False, True), (True, True)])
+def test_rooms_over_the_corner_where_four_tiles_meet(flip_x, flip_y, monkeypatch):
+    monkeypatch.setenv("GMS_ROOMS_BATCH", "1")
+    log, seeds, (A, B, C, D) = rooms_corner_case(flip_x, flip_y)
+    want = ro.expect(log, **ROOMS)
+    depth, label = (lambda c: int(want["depth"][c[1], c[0]])), (lambda c: int(want["labels"][c[1], c[0]]))
+    assert want["n_rooms"] == 3 and (flip_y or want["rooms"]["core_count"].tolist() == [2, 2, 2])
+    assert depth(A) == 220 and depth(B) == depth(C) == 225 and depth(D) == 227, "the diagonal over the corner is the cheapest way to D"
+    assert label(D) == label(A) != NONE and len({label(A), label(B), label(C), NONE}) == 4, "D is reached, and from A's room, not from B's or C's"
+    assert [label(c) for c in (B, C, A)] == [want["labels"][s[1], s[0]] for s in seeds], "each of A, B, C belongs to the room at the end of its corridor"
+    assert len({(c[0] // T, c[1] // T) for c in (A, B, C, D)}) == 4
+    m = _map((130, 130))
+    m.upload_log(log)
+    ro.same(m.rooms(labels=True, depth=True, cap_rooms=CAP, cap_doors=CAP, **ROOMS), want, f"flip_x = {flip_x}, flip_y = {flip_y}")
+    m.close()
+
+
+def test_rooms_cores_touching_diagonally_across_a_tile_border_are_two():
+    """core cells (63, y) and (64, y + 1) and no other: two cores under the rooms' 4-connectivity, and -- the same plane as a
+    frontier plane -- ONE region under the frontiers' 8-connectivity"""
+    y = 40
+    log = ro.walls(130, 130)
+    for cx, cy in ((63, y), (64, y + 1)):                                      # at core = 1 the centre of a free plus is its only core cell
+        ro.carve(log, cx - 1, cy, cx + 1, cy)
+        ro.carve(log, cx, cy - 1, cx, cy + 1)
+    m = _map((130, 130))
+    want = _rooms_same(m, log, "two pluses", core=1, inflate=0, not_free=False, min_core=1)
+    m.close()
+    assert want["n_rooms"] == 2 and want["rooms"]["core_count"].tolist() == [1, 1]
+    assert (want["rooms"]["anchor_x"].tolist(), want["rooms"]["anchor_y"].tolist()) == ([63, 64], [y, y + 1])
+    m = tf._map()
+    rec = tf._check(m, tf._cells(tf._unknown(), [(63, y), (64, y + 1)]), "the two cells as a frontier plane")[0]
+    m.close()
+    assert rec["count"].tolist() == [2] and (rec["anchor_x"][0], rec["anchor_y"][0]) == (63, y)
 
 
 # ---- 3: frontiers -------------------------------------------------------------------------------------------------------------------------
